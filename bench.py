@@ -4,6 +4,12 @@
 A "step" is one pass of the hot path over one batch of synthetic input, inputs resident in HBM before the timed region,
 hyper-parameters fixed.
 
+A plain run sets up, warms up (--warmup steps), times --steps steps and prints ONE JSON line whose headline is `value`
+(iterations/s) and `ms_per_step`.  --full adds everything else this script measures: the roofline and per-kernel figures
+(HIP events in the timed region, un-timed extra passes), the int8-emulated second line, the CPU baseline, and at N > 1 the
+C4 section.  --dump-outputs DIR writes what the last timed step returned (dump_outputs below); the inputs are seeded, so two
+builds run with the same arguments can be compared output for output.
+
 --gpus 1 (default)  workload C3 = BASELINE.json configs[2], the configuration the metric is quoted on:
     fit (K build -> Cholesky -> alpha -> LML, rows A1-A5) + predict on 10 000 resident candidates (A6-A7), both
     through ONE call (gp_fit_predict; --separate-calls times gp_fit + gp_predict instead), + EI scoring + device
@@ -443,6 +449,38 @@ def static_traffic(N, D, M):
                                             "algorithmic_bytes_per_launch": tj.get("algorithmic_bytes_per_launch")}
 
 
+DUMP_MAX_ROWS = 1000000   # posterior rows written by --dump-outputs; above this a fixed sample (seed 0) of them, 24 MB at most
+
+
+def dump_outputs(path, out, first_row, rank, rdv):
+    """--dump-outputs: what the last timed step returned to its caller, as float64 .npy files under `path` -- the LML, log
+    det, jitter, fmin, the merged arg-best (row, value) and, where the step predicts (C3), the posterior mean and variance of
+    the whole candidate table (every rank's block, gathered to rank 0 over the control channel)."""
+    lml, best_row, best_value, extra = out
+    mean, var = extra["mean"], extra["var"]
+    if rdv is not None:
+        blocks = rdv.gather((first_row, mean, var))
+        if rank != 0:
+            return
+        if mean is not None:
+            blocks.sort(key=lambda b: b[0])
+            mean = np.concatenate([b[1] for b in blocks])
+            var = np.concatenate([b[2] for b in blocks])
+    os.makedirs(path, exist_ok=True)
+    arrays = {"lml": lml, "logdet": extra["logdet"], "jitter": extra["jitter"], "fmin": extra["fmin"],
+              "best_row": best_row, "best_value": best_value}
+    arrays = {k: np.array([v], dtype=np.float64) for k, v in arrays.items()}
+    if mean is not None:
+        rows = np.arange(mean.shape[0])
+        if rows.size > DUMP_MAX_ROWS:
+            rows = np.sort(np.random.default_rng(0).choice(rows.size, DUMP_MAX_ROWS, replace=False))
+            arrays["rows"] = rows.astype(np.float64)
+        arrays["mean"] = np.asarray(mean[rows], dtype=np.float64)
+        arrays["var"] = np.asarray(var[rows], dtype=np.float64)
+    for k, v in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), v)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -470,7 +508,15 @@ def main():
                     help="N > 1, default workload: skip the second measurement (C4: ONE table of --c4-M candidates split over the ranks)")
     ap.add_argument("--c4-M", type=int, default=1000000, help="N > 1, default workload: size of the C4 section's candidate table")
     ap.add_argument("--c4-steps", type=int, default=3, help="timed iterations of the C4 section")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: roofline / per-kernel figures, the int8-emulated second line, the CPU "
+                         "baseline, N > 1: the C4 section, C4: the single-GPU reference pass")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (posterior mean / variance, LML, "
+                         "fmin, arg-best row and value) as DIR/<name>.npy, float64")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.small_calls:
         recs = small_calls(cpu=not args.no_cpu_baseline)
@@ -501,7 +547,7 @@ def main():
     # BASELINE.json's candidate-sharding configuration (C4: one table of 10^6 candidates split over the ranks) is measured in the
     # same run as a second object of the line (c4_sharded); `--workload c4` runs it as the line itself.
     workload = args.workload if args.workload != "auto" else "c3"
-    with_c4 = args.workload == "auto" and world > 1 and not args.no_c4_section
+    with_c4 = args.full and args.workload == "auto" and world > 1 and not args.no_c4_section
     if world > 1:
         os.environ.setdefault("NCCL_DEBUG_FILE", "/dev/stderr")   # RCCL's log lines belong on stderr: stdout carries the ONE JSON line
         os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")  # dmabuf IPC (the host driver's only mode): set before HIP loads,
@@ -602,6 +648,7 @@ def main():
     fused = workload == "c3" and not args.separate_calls
 
     def step():
+        mu = var = None
         if fused:  # gp_fit + gp_predict as one pipelined pass (bitwise the same results; include/gphip.h)
             (lml, logdet, jit), mu, var = h.fit_predict(True)
         else:
@@ -611,12 +658,12 @@ def main():
         fmin = h.fmin()
         idx, val = h.acq_argbest(_lib.GP_ACQ_EI, 0.01, fmin, -1)   # C4: posterior + EI over the block, chunked
         gi, gv = exchange(val, lo + idx)
-        return lml, gi, gv
+        return lml, gi, gv, {"logdet": logdet, "jitter": jit, "fmin": fmin, "mean": mu, "var": var}
 
     # C4 on N > 1 ranks: rank 0 times one un-profiled pass over the WHOLE table on its own GPU first (the single-GPU
     # base the sharded rate is to be read against); the other ranks wait at the barrier
     c4_ref = None
-    if workload == "c4" and world > 1 and not args.no_c4_reference:
+    if args.full and workload == "c4" and world > 1 and not args.no_c4_reference:
         if rank == 0:
             full = np.random.default_rng(1236).uniform(0, 1, (M_total, D))
             h.set_candidates(full)
@@ -633,17 +680,21 @@ def main():
 
     for _ in range(args.warmup):
         out = step()
-    h.profile(True)          # HIP events around every launch of the dominant kernel (fp64 MFMA GEMM), on its stream
+    if args.full:
+        h.profile(True)      # HIP events around every launch of the dominant kernel (fp64 MFMA GEMM), on its stream
     barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps):
         out = step()
     barrier()
     elapsed = time.perf_counter() - t0
-    gs = h.gemm_stats()
-    busy_ms = h.gemm_busy()
-    phases_timed = {p["name"]: round(p["ms"], 3) for p in h.phases()}   # of the last call of the last timed step
-    h.profile(False)
+    if args.full:
+        gs = h.gemm_stats()
+        busy_ms = h.gemm_busy()
+        phases_timed = {p["name"]: round(p["ms"], 3) for p in h.phases()}   # of the last call of the last timed step
+        h.profile(False)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, out, lo, rank, rdv)
     ranks_agree, rank_records = True, None
     if rdv is not None:
         elapsed = max_over_ranks(elapsed)
@@ -657,7 +708,7 @@ def main():
     # int8 matrix cores in residue form (option "emulate_fp64", csrc/rns.hip; fp64-equivalent results, parity-tested in
     # tests/test_gpu_emulation.py).  The headline above stays true fp64.
     emulated = None
-    if workload == "c3" and world == 1 and not args.no_emulated_line:
+    if args.full and workload == "c3" and world == 1 and not args.no_emulated_line:
         h.set_option("emulate_fp64", 1)
         ref_best = (out[1], out[2])
         step()
@@ -689,48 +740,49 @@ def main():
                                   "frac": rs["ops"] / max(rs["ms"], 1e-9) / 1e9 / 5000.0,
                                   "ops_per_launch_avg": rs["ops"] / max(rs["launches"], 1)}}
 
-    # un-timed: per-phase rates from gp_fit and gp_predict run one after the other (the median of three calls each: a single call
-    # right after the emulated section has been seen 4 ms off)
-    def phases_of(fn):
-        runs = []
-        for _ in range(3):
-            fn()
-            runs.append(h.phases())
-        return sorted(runs, key=lambda ph: sum(p["ms"] for p in ph))[1]
-    ph_fit = phases_of(h.fit)
-    fit_ms = sum(p["ms"] for p in ph_fit)
-    if workload == "c3":
-        ph_pred = phases_of(lambda: h.predict(True))
-    else:
-        h.acq_argbest(_lib.GP_ACQ_EI, 0.01, h.fmin(), -1)
-        ph_pred = h.phases()
-    phases = {p["name"]: round(p["ms"], 3) for p in ph_fit}
-    for p in ph_pred:   # (a chunked predict reports its LAST chunk's phases: gp_last_phases holds one call's worth)
-        phases[p["name"]] = round(p["ms"], 3)
-    chol = [p for p in ph_fit if p["name"] == "cholesky"][0]
-    kb = [p for p in ph_fit if p["name"] == "kbuild"][0]
-    solve = [p for p in ph_pred if p["name"].startswith("cand_solve")][-1]
+    if args.full:
+        # un-timed: per-phase rates from gp_fit and gp_predict run one after the other (the median of three calls each: a single call
+        # right after the emulated section has been seen 4 ms off)
+        def phases_of(fn):
+            runs = []
+            for _ in range(3):
+                fn()
+                runs.append(h.phases())
+            return sorted(runs, key=lambda ph: sum(p["ms"] for p in ph))[1]
+        ph_fit = phases_of(h.fit)
+        fit_ms = sum(p["ms"] for p in ph_fit)
+        if workload == "c3":
+            ph_pred = phases_of(lambda: h.predict(True))
+        else:
+            h.acq_argbest(_lib.GP_ACQ_EI, 0.01, h.fmin(), -1)
+            ph_pred = h.phases()
+        phases = {p["name"]: round(p["ms"], 3) for p in ph_fit}
+        for p in ph_pred:   # (a chunked predict reports its LAST chunk's phases: gp_last_phases holds one call's worth)
+            phases[p["name"]] = round(p["ms"], 3)
+        chol = [p for p in ph_fit if p["name"] == "cholesky"][0]
+        kb = [p for p in ph_fit if p["name"] == "kbuild"][0]
+        solve = [p for p in ph_pred if p["name"].startswith("cand_solve")][-1]
 
-    # un-timed: the second fp64 symbol (15 % of GPU time in r02's kernel stats, no flop accounting there): events around
-    # every launch of gemm_nt_kernel<1, 64, 2, false, 64> in ONE extra step (they stall the latency chain, so not in the
-    # timed region)
-    h.profile(2)
-    step()
-    cs = h.gemm_stats()
-    h.profile(False)
-
-    # un-timed: the dominant kernel WITHOUT a neighbour of its own kind -- gp_fit then gp_predict as two calls (no candidate update
-    # shares the chip with a trailing update), HIP events around every launch of the symbol as in the timed region.  A rocprofv3
-    # --stats run of `bench.py --separate-calls` averages exactly these launches (profiles/r05_bench_kernel_stats_fp64.csv).
-    sep = None
-    if workload == "c3":
-        h.fit(); h.predict(True)
-        h.profile(True)
-        for _ in range(3):
-            h.fit(); h.predict(True)
-        sep = h.gemm_stats()
-        sep["busy_ms"] = h.gemm_busy()
+        # un-timed: the second fp64 symbol (15 % of GPU time in r02's kernel stats, no flop accounting there): events around
+        # every launch of gemm_nt_kernel<1, 64, 2, false, 64> in ONE extra step (they stall the latency chain, so not in the
+        # timed region)
+        h.profile(2)
+        step()
+        cs = h.gemm_stats()
         h.profile(False)
+
+        # un-timed: the dominant kernel WITHOUT a neighbour of its own kind -- gp_fit then gp_predict as two calls (no candidate update
+        # shares the chip with a trailing update), HIP events around every launch of the symbol as in the timed region.  A rocprofv3
+        # --stats run of `bench.py --separate-calls` averages exactly these launches (profiles/r05_bench_kernel_stats_fp64.csv).
+        sep = None
+        if workload == "c3":
+            h.fit(); h.predict(True)
+            h.profile(True)
+            for _ in range(3):
+                h.fit(); h.predict(True)
+            sep = h.gemm_stats()
+            sep["busy_ms"] = h.gemm_busy()
+            h.profile(False)
 
     # N > 1, default workload: the candidate-sharding configuration in the same run (see above).  ONE table for the whole job
     # (seed 1236), this rank's contiguous block of it; rank 0 first times one pass over the WHOLE table on its own GPU (the
@@ -787,10 +839,6 @@ def main():
     if rank == 0:
         ms_per_step = elapsed / args.steps * 1e3
         job_rate = args.steps / elapsed
-        achieved = gs["flops"] / max(gs["ms"], 1e-9) / 1e9              # per launch: flops / SUM of the launch durations
-        achieved_busy = gs["flops"] / max(busy_ms, 1e-9) / 1e9         # flops / UNION of the launch intervals
-        traffic, traffic_src = static_traffic(N, D, M) if workload == "c3" else (None, None)
-        kb_gbs = kb["bytes"] / max(kb["ms"], 1e-9) / 1e6
         if workload == "c3":
             cfg = {"workload": "C3 (BASELINE.json configs[2]): N=%d, D=%d RBF iso, fit (K, Cholesky, alpha, LML) + predict "
                                "mean/var at M=%d candidates + EI arg-best" % (N, D, M_total),
@@ -802,16 +850,13 @@ def main():
                 cfg["note_n_gpus"] = ("ONE model, the N = 1 run's table of %d candidates split over %d ranks (%d here): the fit does "
                                       "not shard (replicas only, SURVEY.md 8e), every rank refits and scores its block, the ranks "
                                       "all-gather their arg-best over RCCL; value = job iterations/s, expected ~ 1 / (fit + "
-                                      "solve / N).  C4 (10^6-row table split over the ranks) is measured in the same run: "
-                                      "c4_sharded" % (M_total, world, M))
-                cfg["fit_ms_per_iter_not_scaling"] = round(fit_ms, 3)
+                                      "solve / N).  C4 (10^6-row table split over the ranks) is measured in the same run "
+                                      "with --full: c4_sharded" % (M_total, world, M))
         else:
             cfg = {"workload": "C4 (BASELINE.json configs[3]): N=%d, D=%d Matern-5/2 iso, fit (replicated per rank) + posterior "
                                "+ EI over ONE table of %d candidates split over %d rank(s) + device arg-best + RCCL "
                                "all-gather of (best, row) + lowest-index merge" % (N, D, M_total, world),
                    "candidates_total": M_total, "candidates_this_rank": M,
-                   "fit_ms_per_iter_not_scaling": round(fit_ms, 3),
-                   "predict_ei_ms_per_iter_this_rank": round(ms_per_step - fit_ms, 3),
                    "single_gpu_reference": c4_ref,
                    "speedup_vs_single_gpu": None if not c4_ref else c4_ref["single_gpu_iter_s"] * 1e3 / ms_per_step,
                    "best_row_matches_single_gpu": None if not c4_ref else bool(c4_ref["best_row"] == int(out[1]))}
@@ -825,16 +870,7 @@ def main():
                                 ("torch.distributed.run" if world > 1 else "single process"),
                     "ranks_agree_on_winner": ranks_agree if world > 1 else None, "rank_records": rank_records,
                     "emulate_fp64": 0,
-                    "lml": out[0], "best_candidate_global_row": int(out[1]), "best_value": float(out[2]),
-                    "phases_ms_last_timed_call": phases_timed, "phases_ms": phases,
-                    "phases_note": "phases_ms: gp_fit and the predict pass run one after the other AFTER the timed region, the "
-                                   "median of three calls each (the per-phase rates below come from it)",
-                    "cholesky_tflops": chol["flops"] / chol["ms"] / 1e9,
-                    "cholesky_frac_of_fp64_mfma_peak": chol["flops"] / chol["ms"] / 1e9 / FP64_MFMA_PEAK_TFLOPS,
-                    "cand_solve_tflops": solve["flops"] / solve["ms"] / 1e9,
-                    # the same phase counting what it executes: N^2 M plus the products with the inverted diagonal panels
-                    # (M N x panel width; 768 columns by default) -- the rate to hold against the GEMM kernel's own
-                    "cand_solve_executed_tflops": solve["flops"] * (1.0 + panel_cols / N) / solve["ms"] / 1e9})
+                    "lml": out[0], "best_candidate_global_row": int(out[1]), "best_value": float(out[2])})
         result = {
             "metric": "GP fit+predict iters/sec at N=%d D=%d" % (N, D),
             "value": value, "unit": "fit+predict iters/s",
@@ -842,56 +878,78 @@ def main():
             "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": scaling,
             "vs_baseline": None, "dtype": "f64", "data": "synthetic",
             "config": cfg,
-            "roofline": {"bound": "mfma", "kernel": GEMM_SYMBOL + " (C -= A B^T on fp64 v_mfma_f64_16x16x4_f64, 8 waves)",
-                         # flops of the launches / the time the chip actually spent on them: the UNION of the launches' [start, end]
-                         # intervals (HIP events on the stream each launch runs on).  In gp_fit_predict ~25 launches per step overlap
-                         # (candidate updates beside the factorisation's trailing updates), so the SUM of their durations counts
-                         # shared time twice and exceeds the step itself: that figure is kept as *_per_launch.
-                         "achieved": achieved_busy, "peak": FP64_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
-                         "frac": achieved_busy / FP64_MFMA_PEAK_TFLOPS, "traffic": traffic, "traffic_unit": "bytes per launch",
-                         "traffic_provenance": traffic_src,
-                         "busy_ms_total": busy_ms,
-                         "achieved_per_launch": achieved, "frac_per_launch": achieved / FP64_MFMA_PEAK_TFLOPS,
-                         "launches": gs["launches"], "kernel_ms_total": gs["ms"],
-                         "avg_launch_ms": gs["ms"] / max(gs["launches"], 1),
-                         "flops_per_launch_avg": gs["flops"] / max(gs["launches"], 1),
-                         "launch_filter": "every launch of that kernel symbol in the timed region (launches of >= 1400 output "
-                                          "tiles: trailing updates, candidate updates; > 90 %% of the flops), %.0f per step"
-                                          % (gs["launches"] / max(args.steps, 1)),
-                         # the same symbol with no launch of its own kind beside it: gp_fit then gp_predict, 3 un-timed passes
-                         "separate_calls_reference": None if sep is None else {
-                             "launches": sep["launches"], "kernel_ms_total": sep["ms"],
-                             "avg_launch_ms": sep["ms"] / max(sep["launches"], 1),
-                             "flops_per_launch_avg": sep["flops"] / max(sep["launches"], 1),
-                             "achieved": sep["flops"] / max(sep["ms"], 1e-9) / 1e9,
-                             "frac": sep["flops"] / max(sep["ms"], 1e-9) / 1e9 / FP64_MFMA_PEAK_TFLOPS,
-                             "busy_ms_total": sep["busy_ms"],
-                             "rocprof": "profiles/r05_bench_kernel_stats_fp64.csv: rocprofv3 --kernel-trace --stats of "
-                                        "`bench.py --separate-calls` (every launch of the symbol un-overlapped)"},
-                         # the whole step against the same peak: N^3/3 (Cholesky) + N^2 M (candidate solve) algorithmic flops of
-                         # ONE rank's step / ms_per_step -- K builds, chain, reductions and launch gaps all inside the time
-                         "step_algorithmic_flops": N ** 3 / 3.0 + float(N) * N * M,
-                         "step_achieved": (N ** 3 / 3.0 + float(N) * N * M) / (ms_per_step * 1e-3) / 1e12,
-                         "step_frac": (N ** 3 / 3.0 + float(N) * N * M) / (ms_per_step * 1e-3) / 1e12 / FP64_MFMA_PEAK_TFLOPS},
-            "chain_gemm": {"bound": "mfma", "kernel": "gemm_nt_kernel<1, 64, 2, false, 64> (the same C -= A B^T as 64 x 64 work "
-                                                      "units: the factorisation chain's in-panel / look-ahead updates)",
-                           "launches_per_step": cs["launches"], "kernel_ms_per_step": cs["ms"],
-                           "avg_launch_ms": cs["ms"] / max(cs["launches"], 1),
-                           "flops_per_launch_avg": cs["flops"] / max(cs["launches"], 1),
-                           "achieved": cs["flops"] / max(cs["ms"], 1e-9) / 1e9, "peak": FP64_MFMA_PEAK_TFLOPS,
-                           "unit": "TFLOP/s", "frac": cs["flops"] / max(cs["ms"], 1e-9) / 1e9 / FP64_MFMA_PEAK_TFLOPS,
-                           "note": "ONE extra un-timed step with HIP events around every launch of this symbol (latency-bound "
-                                   "launches of the chain: their rate is set by launch + drain time, not by the matrix pipe)"},
-            "kbuild": {"bound": "hbm", "kernel": "kbuild_kernel (+ set_rhs_kernel: the 'kbuild' phase of gp_fit, HIP events)",
-                       "algorithmic_bytes": kb["bytes"], "ms": kb["ms"], "achieved": kb_gbs, "peak": HBM_PEAK_GBS,
-                       "unit": "GB/s", "frac": kb_gbs / HBM_PEAK_GBS,
-                       "counter_evidence": "profiles/r04_traffic.json (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE)"},
         }
+        if args.full:
+            # the per-phase and per-kernel figures of the un-timed passes above and of the events in the timed region
+            achieved = gs["flops"] / max(gs["ms"], 1e-9) / 1e9              # per launch: flops / SUM of the launch durations
+            achieved_busy = gs["flops"] / max(busy_ms, 1e-9) / 1e9         # flops / UNION of the launch intervals
+            traffic, traffic_src = static_traffic(N, D, M) if workload == "c3" else (None, None)
+            kb_gbs = kb["bytes"] / max(kb["ms"], 1e-9) / 1e6
+            if workload == "c3" and world > 1:
+                cfg["fit_ms_per_iter_not_scaling"] = round(fit_ms, 3)
+            elif workload == "c4":
+                cfg.update({"fit_ms_per_iter_not_scaling": round(fit_ms, 3),
+                            "predict_ei_ms_per_iter_this_rank": round(ms_per_step - fit_ms, 3)})
+            cfg.update({"phases_ms_last_timed_call": phases_timed, "phases_ms": phases,
+                        "phases_note": "phases_ms: gp_fit and the predict pass run one after the other AFTER the timed region, the "
+                                       "median of three calls each (the per-phase rates below come from it)",
+                        "cholesky_tflops": chol["flops"] / chol["ms"] / 1e9,
+                        "cholesky_frac_of_fp64_mfma_peak": chol["flops"] / chol["ms"] / 1e9 / FP64_MFMA_PEAK_TFLOPS,
+                        "cand_solve_tflops": solve["flops"] / solve["ms"] / 1e9,
+                        # the same phase counting what it executes: N^2 M plus the products with the inverted diagonal panels
+                        # (M N x panel width; 768 columns by default) -- the rate to hold against the GEMM kernel's own
+                        "cand_solve_executed_tflops": solve["flops"] * (1.0 + panel_cols / N) / solve["ms"] / 1e9})
+            result.update({
+                "roofline": {"bound": "mfma", "kernel": GEMM_SYMBOL + " (C -= A B^T on fp64 v_mfma_f64_16x16x4_f64, 8 waves)",
+                             # flops of the launches / the time the chip actually spent on them: the UNION of the launches' [start, end]
+                             # intervals (HIP events on the stream each launch runs on).  In gp_fit_predict ~25 launches per step overlap
+                             # (candidate updates beside the factorisation's trailing updates), so the SUM of their durations counts
+                             # shared time twice and exceeds the step itself: that figure is kept as *_per_launch.
+                             "achieved": achieved_busy, "peak": FP64_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
+                             "frac": achieved_busy / FP64_MFMA_PEAK_TFLOPS, "traffic": traffic, "traffic_unit": "bytes per launch",
+                             "traffic_provenance": traffic_src,
+                             "busy_ms_total": busy_ms,
+                             "achieved_per_launch": achieved, "frac_per_launch": achieved / FP64_MFMA_PEAK_TFLOPS,
+                             "launches": gs["launches"], "kernel_ms_total": gs["ms"],
+                             "avg_launch_ms": gs["ms"] / max(gs["launches"], 1),
+                             "flops_per_launch_avg": gs["flops"] / max(gs["launches"], 1),
+                             "launch_filter": "every launch of that kernel symbol in the timed region (launches of >= 1400 output "
+                                              "tiles: trailing updates, candidate updates; > 90 %% of the flops), %.0f per step"
+                                              % (gs["launches"] / max(args.steps, 1)),
+                             # the same symbol with no launch of its own kind beside it: gp_fit then gp_predict, 3 un-timed passes
+                             "separate_calls_reference": None if sep is None else {
+                                 "launches": sep["launches"], "kernel_ms_total": sep["ms"],
+                                 "avg_launch_ms": sep["ms"] / max(sep["launches"], 1),
+                                 "flops_per_launch_avg": sep["flops"] / max(sep["launches"], 1),
+                                 "achieved": sep["flops"] / max(sep["ms"], 1e-9) / 1e9,
+                                 "frac": sep["flops"] / max(sep["ms"], 1e-9) / 1e9 / FP64_MFMA_PEAK_TFLOPS,
+                                 "busy_ms_total": sep["busy_ms"],
+                                 "rocprof": "profiles/r05_bench_kernel_stats_fp64.csv: rocprofv3 --kernel-trace --stats of "
+                                            "`bench.py --separate-calls` (every launch of the symbol un-overlapped)"},
+                             # the whole step against the same peak: N^3/3 (Cholesky) + N^2 M (candidate solve) algorithmic flops of
+                             # ONE rank's step / ms_per_step -- K builds, chain, reductions and launch gaps all inside the time
+                             "step_algorithmic_flops": N ** 3 / 3.0 + float(N) * N * M,
+                             "step_achieved": (N ** 3 / 3.0 + float(N) * N * M) / (ms_per_step * 1e-3) / 1e12,
+                             "step_frac": (N ** 3 / 3.0 + float(N) * N * M) / (ms_per_step * 1e-3) / 1e12 / FP64_MFMA_PEAK_TFLOPS},
+                "chain_gemm": {"bound": "mfma", "kernel": "gemm_nt_kernel<1, 64, 2, false, 64> (the same C -= A B^T as 64 x 64 work "
+                                                          "units: the factorisation chain's in-panel / look-ahead updates)",
+                               "launches_per_step": cs["launches"], "kernel_ms_per_step": cs["ms"],
+                               "avg_launch_ms": cs["ms"] / max(cs["launches"], 1),
+                               "flops_per_launch_avg": cs["flops"] / max(cs["launches"], 1),
+                               "achieved": cs["flops"] / max(cs["ms"], 1e-9) / 1e9, "peak": FP64_MFMA_PEAK_TFLOPS,
+                               "unit": "TFLOP/s", "frac": cs["flops"] / max(cs["ms"], 1e-9) / 1e9 / FP64_MFMA_PEAK_TFLOPS,
+                               "note": "ONE extra un-timed step with HIP events around every launch of this symbol (latency-bound "
+                                       "launches of the chain: their rate is set by launch + drain time, not by the matrix pipe)"},
+                "kbuild": {"bound": "hbm", "kernel": "kbuild_kernel (+ set_rhs_kernel: the 'kbuild' phase of gp_fit, HIP events)",
+                           "algorithmic_bytes": kb["bytes"], "ms": kb["ms"], "achieved": kb_gbs, "peak": HBM_PEAK_GBS,
+                           "unit": "GB/s", "frac": kb_gbs / HBM_PEAK_GBS,
+                           "counter_evidence": "profiles/r04_traffic.json (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE)"},
+            })
         if emulated is not None:
             result["emulated_fp64_second_line"] = emulated
         if c4_sec is not None:
             result["c4_sharded"] = c4_sec
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             result["cpu_baseline"] = cpu_baseline(N, D, 10000, sample_only=args.cpu_baseline_sample)
         print(json.dumps(result))
         sys.stdout.flush()

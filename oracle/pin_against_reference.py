@@ -14,7 +14,9 @@ Checks, with /root/reference mounted:
      (model_tests.py:84-119), finite-difference gradients
      (model_tests.py:664-723 / kernel_tests.py:414-422).
 Exit status 0 iff everything holds.  tests/test_oracle_pin.py runs the same
-checks under pytest (skipped where the reference tree is absent).
+checks under pytest; where the reference tree is absent, what the reference
+returned is read from tests/golden/pin_reference.npz (Recorded below, stored by
+tests/golden/generate_pin.py).
 """
 import ctypes
 import sys
@@ -27,36 +29,84 @@ from oracle import cpu_ref as O  # noqa: E402
 from oracle import ref_leaf  # noqa: E402
 
 
+GOLDEN = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden", "pin_reference.npz")
+
+
 def _dp(a):
     return a.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
 
 
-def check_linalg(R):
-    linalg, diag, normalizer, general = R
+class Recorded(object):
+    """What the reference returned in the checks: ``rec(key, fn)`` calls ``fn`` -- the reference's own code -- where the
+    reference tree is present (and keeps the result for tests/golden/generate_pin.py to store), and reads the stored result
+    from tests/golden/pin_reference.npz where it is not.  Tuples and lists keep their structure; 0-d values come back as
+    Python scalars."""
+
+    def __init__(self, live):
+        self.live = live
+        self.kept = {}
+        if not live:
+            with np.load(GOLDEN, allow_pickle=False) as z:
+                self._stored = {k: z[k] for k in z.files}
+
+    def __call__(self, key, fn):
+        if self.live:
+            v = fn()
+            self._keep(key, v)
+            return v
+        return self._read(key)
+
+    def _keep(self, key, v):
+        if isinstance(v, (tuple, list)):
+            self.kept[key + "#n"] = np.array([len(v), isinstance(v, list)])
+            for i, e in enumerate(v):
+                self._keep("%s#%d" % (key, i), e)
+        else:
+            self.kept[key] = np.asarray(v)
+
+    def _read(self, key):
+        if key + "#n" in self._stored:
+            n, is_list = self._stored[key + "#n"]
+            v = [self._read("%s#%d" % (key, i)) for i in range(n)]
+            return v if is_list else tuple(v)
+        a = self._stored[key]
+        return a.item() if a.ndim == 0 else a.copy()
+
+
+def _raises(fn, exc):
+    try:
+        fn()
+    except exc:
+        return True
+    return False
+
+
+def check_linalg(R, rec):
+    linalg, diag, normalizer, general = R if R is not None else (None,) * 4
     rng = np.random.default_rng(0)
     A = rng.standard_normal((60, 60))
     A = A @ A.T + 60 * np.eye(60)
-    Ai, L, Li, logdet = linalg.pdinv(A)
+    Ai, L, Li, logdet = rec("linalg/pdinv", lambda: linalg.pdinv(A))
     oAi, oL, oLi, ologdet, jit = O.pdinv(A)
     assert jit == 0.0
     for a, b in ((Ai, oAi), (L, oL), (Li, oLi)):
         assert np.array_equal(a, b), "pdinv mismatch"
     assert logdet == ologdet
     B = rng.standard_normal((60, 3))
-    assert np.array_equal(linalg.dpotrs(L, B, lower=1)[0], O.dpotrs(oL, B, lower=1)[0])
-    assert np.array_equal(linalg.dtrtrs(L, B)[0], O.dtrtrs(oL, B)[0])
-    assert np.array_equal(linalg.dpotri(L)[0], O.dpotri(oL)[0])
-    assert np.array_equal(linalg.dtrtri(L), O.dtrtri(oL))
+    assert np.array_equal(rec("linalg/dpotrs", lambda: linalg.dpotrs(L, B, lower=1)[0]), O.dpotrs(oL, B, lower=1)[0])
+    assert np.array_equal(rec("linalg/dtrtrs", lambda: linalg.dtrtrs(L, B)[0]), O.dtrtrs(oL, B)[0])
+    assert np.array_equal(rec("linalg/dpotri", lambda: linalg.dpotri(L)[0]), O.dpotri(oL)[0])
+    assert np.array_equal(rec("linalg/dtrtri", lambda: linalg.dtrtri(L)), O.dtrtri(oL))
     X = rng.standard_normal((50, 7))
-    assert np.array_equal(linalg.tdot(X), O.tdot(X))
+    assert np.array_equal(rec("linalg/tdot", lambda: linalg.tdot(X)), O.tdot(X))
     S1 = rng.standard_normal((33, 33)); S2 = S1.copy()
-    linalg.symmetrify(S1); O.symmetrify(S2)
+    S1 = rec("linalg/symmetrify", lambda: (linalg.symmetrify(S1), S1)[1]); O.symmetrify(S2)
     assert np.array_equal(S1, S2)
     S1 = rng.standard_normal((33, 33)); S2 = S1.copy()
-    linalg.symmetrify(S1, upper=True); O.symmetrify(S2, upper=True)
+    S1 = rec("linalg/symmetrify_upper", lambda: (linalg.symmetrify(S1, upper=True), S1)[1]); O.symmetrify(S2, upper=True)
     assert np.array_equal(S1, S2)
     D1 = A.copy(); D2 = A.copy()
-    diag.add(D1, 0.37); O.diag_add(D2, 0.37)
+    D1 = rec("diag/add", lambda: (diag.add(D1, 0.37), D1)[1]); O.diag_add(D2, 0.37)
     assert np.array_equal(D1, D2)
     # jitter ladder, as linalg_test.py:8-37
     rs = np.random.RandomState(0)
@@ -65,36 +115,37 @@ def check_linalg(R):
     w, v = np.linalg.eigh(Aj)
     w[0] = -np.mean(np.diag(Aj)) * 1e-6 * 10 ** 3.5
     Aj = (v * w) @ v.T
-    Lr = linalg.jitchol(Aj, maxtries=5)
+    Lr = rec("linalg/jitchol", lambda: linalg.jitchol(Aj, maxtries=5))
     Lo, jit = O.jitchol(Aj, maxtries=5)
     assert np.array_equal(Lr, Lo) and jit > 0
-    for fn in (lambda: linalg.jitchol(Aj, maxtries=4), lambda: O.jitchol(Aj, maxtries=4)):
-        try:
-            fn()
-        except np.linalg.LinAlgError:
-            pass
-        else:
+    for fails in (rec("linalg/jitchol_4_fails", lambda: _raises(lambda: linalg.jitchol(Aj, maxtries=4), np.linalg.LinAlgError)),
+                  _raises(lambda: O.jitchol(Aj, maxtries=4), np.linalg.LinAlgError)):
+        if not fails:
             raise AssertionError("jitchol(maxtries=4) must fail")
     # normaliser
     Y = rng.standard_normal((40, 2)) * 3 + 1
-    n1 = normalizer.Standardize(); n1.scale_by(Y)
+
+    def ref_standardize():
+        n1 = normalizer.Standardize(); n1.scale_by(Y)
+        return n1.normalize(Y), n1.inverse_mean(Y), n1.inverse_variance(Y)
+    r_norm, r_mean, r_var = rec("normalizer/Standardize", ref_standardize)
     n2 = O.Standardize(); n2.scale_by(Y)
-    assert np.array_equal(n1.normalize(Y), n2.normalize(Y))
-    assert np.array_equal(n1.inverse_mean(Y), n2.inverse_mean(Y))
-    assert np.array_equal(n1.inverse_variance(Y), n2.inverse_variance(Y))
+    assert np.array_equal(r_norm, n2.normalize(Y))
+    assert np.array_equal(r_mean, n2.inverse_mean(Y))
+    assert np.array_equal(r_var, n2.inverse_variance(Y))
     # GPyOpt general
     m = rng.standard_normal((30, 1)); s = np.abs(rng.standard_normal((30, 1))); s[3] = 1e-12
-    q1 = general.get_quantiles(0.01, 0.2, m, s.copy())
+    q1 = rec("general/get_quantiles", lambda: general.get_quantiles(0.01, 0.2, m, s.copy()))
     q2 = O.get_quantiles(0.01, 0.2, m, s.copy())
     for a, b in zip(q1, q2):
         assert np.array_equal(a, b)
     y = rng.standard_normal((25, 1))
     for t in ("stats", "maxmin"):
-        assert np.array_equal(general.normalize(y, t), O.normalize(y, t))
+        assert np.array_equal(rec("general/normalize_" + t, lambda: general.normalize(y, t)), O.normalize(y, t))
     return "linalg/diag/normalizer/general: bit-identical"
 
 
-def check_native(lib):
+def check_native(lib, rec):
     # cython_tests.py:39-67 shapes
     rng = np.random.default_rng(1)
     k = O.RBF(10, variance=1.3, lengthscale=rng.uniform(0.5, 2, 10), ARD=True)
@@ -103,29 +154,37 @@ def check_native(lib):
     invdist = k._inv_dist(X, Z)
     dL_dr = k.dK_dr(k._scaled_dist(X, Z)) * dL_dK
     tmp = np.ascontiguousarray(invdist * dL_dr)
-    g = np.zeros(10)
-    lib._lengthscale_grads(300, 20, 10, _dp(tmp), _dp(X), _dp(Z), _dp(g))
+
+    def ref_native():
+        g = np.zeros(10)
+        lib._lengthscale_grads(300, 20, 10, _dp(tmp), _dp(X), _dp(Z), _dp(g))
+        grad = np.zeros((300, 10))
+        lib._grad_X(300, 10, 20, _dp(X), _dp(Z), _dp(tmp), _dp(grad))
+        return g, grad
+    g, grad = rec("native/stationary_utils", ref_native)
     ref_len = -g / k.lengthscale ** 3
     _, mine = k.update_gradients_full(dL_dK, X, Z)
     np.testing.assert_allclose(mine, ref_len, rtol=1e-12)
-    grad = np.zeros((300, 10))
-    lib._grad_X(300, 10, 20, _dp(X), _dp(Z), _dp(tmp), _dp(grad))
     np.testing.assert_allclose(k.gradients_X(dL_dK, X, Z), grad / k.lengthscale ** 2, rtol=1e-12, atol=1e-14)
     return "stationary_utils.c (_grad_X, _lengthscale_grads): rtol 1e-12"
 
 
-def check_lml_through_reference(R):
-    linalg, diag, _, _ = R
+def check_lml_through_reference(R, rec):
+    linalg, diag, _, _ = R if R is not None else (None,) * 4
     rng = np.random.default_rng(2)
     X = rng.uniform(0, 1, (64, 3)); Y = rng.standard_normal((64, 1))
     for kern in (O.RBF(3, 1.2, 0.4), O.Matern52(3, 0.8, [0.3, 0.5, 0.9], ARD=True)):
         # reference's own building blocks, in the order of exact_gaussian_inference.py:50-70
         K = kern.K(X)
-        Ky = K.copy(); diag.add(Ky, 0.05 + 1e-8)
-        Wi, LW, LWi, W_logdet = linalg.pdinv(Ky)
-        alpha, _ = linalg.dpotrs(LW, Y, lower=1)
-        lml = 0.5 * (-Y.size * np.log(2 * np.pi) - Y.shape[1] * W_logdet - np.sum(alpha * Y))
-        dL_dK = 0.5 * (linalg.tdot(alpha) - Y.shape[1] * Wi)
+
+        def ref_inference():
+            Ky = K.copy(); diag.add(Ky, 0.05 + 1e-8)
+            Wi, LW, LWi, W_logdet = linalg.pdinv(Ky)
+            alpha, _ = linalg.dpotrs(LW, Y, lower=1)
+            lml = 0.5 * (-Y.size * np.log(2 * np.pi) - Y.shape[1] * W_logdet - np.sum(alpha * Y))
+            dL_dK = 0.5 * (linalg.tdot(alpha) - Y.shape[1] * Wi)
+            return lml, dL_dK, alpha
+        lml, dL_dK, alpha = rec("lml/" + type(kern).__name__, ref_inference)
         post = O.exact_gaussian_inference(kern, X, Y, 0.05)
         assert lml == post["lml"]
         assert np.array_equal(dL_dK, post["dL_dK"])
@@ -217,7 +276,7 @@ def _oracle_model(kname="rbf", seed=3, noise=1e-2, N=80, D=2):
     return gm, Xs
 
 
-def check_acquisitions(A):
+def check_acquisitions(A, rec):
     """The reference's own AcquisitionEI / LCB / MPI / LP classes (verbatim modules) evaluated on an oracle-backed
     model against the oracle's restatements: values, gradients and the negated acquisition_function."""
     worst = 0.0
@@ -226,140 +285,173 @@ def check_acquisitions(A):
             gm, Xs = _oracle_model(kname, noise=noise)
             space = _Space([(0.0, 1.0)] * Xs.shape[1])
             fmin = gm.get_fmin()
+            tag = "acq/%s_%g/" % (kname, noise)
+            acqs = (A["EI"].AcquisitionEI(gm, space, None, None, jitter=0.01),
+                    A["LCB"].AcquisitionLCB(gm, space, None, None, exploration_weight=2),
+                    A["MPI"].AcquisitionMPI(gm, space, None, None, jitter=0.01)) if A is not None else (None,) * 3
             cases = (
-                (A["EI"].AcquisitionEI(gm, space, None, None, jitter=0.01), O.acq_EI(gm, Xs, 0.01, fmin),
-                 O.acq_EI_withGradients(gm, Xs, 0.01, fmin)),
-                (A["LCB"].AcquisitionLCB(gm, space, None, None, exploration_weight=2), O.acq_LCB(gm, Xs, 2.0),
-                 O.acq_LCB_withGradients(gm, Xs, 2.0)),
-                (A["MPI"].AcquisitionMPI(gm, space, None, None, jitter=0.01), O.acq_MPI(gm, Xs, 0.01, fmin),
-                 O.acq_MPI_withGradients(gm, Xs, 0.01, fmin)),
+                ("EI", acqs[0], O.acq_EI(gm, Xs, 0.01, fmin), O.acq_EI_withGradients(gm, Xs, 0.01, fmin)),
+                ("LCB", acqs[1], O.acq_LCB(gm, Xs, 2.0), O.acq_LCB_withGradients(gm, Xs, 2.0)),
+                ("MPI", acqs[2], O.acq_MPI(gm, Xs, 0.01, fmin), O.acq_MPI_withGradients(gm, Xs, 0.01, fmin)),
             )
-            for acq, f0, (f1, df1) in cases:
-                f = acq._compute_acq(Xs)
-                fg, dfg = acq._compute_acq_withGradients(Xs)
-                assert np.array_equal(f, f0) and np.array_equal(fg, f1) and np.array_equal(dfg, df1), type(acq).__name__
-                assert np.array_equal(acq.acquisition_function(Xs), O.acquisition_function(f0))
-                a, da = acq.acquisition_function_withGradients(Xs)
+            for name, acq, f0, (f1, df1) in cases:
+                f = rec(tag + name + "/compute", lambda: acq._compute_acq(Xs))
+                fg, dfg = rec(tag + name + "/compute_withGradients", lambda: acq._compute_acq_withGradients(Xs))
+                assert np.array_equal(f, f0) and np.array_equal(fg, f1) and np.array_equal(dfg, df1), name
+                assert np.array_equal(rec(tag + name + "/acquisition_function", lambda: acq.acquisition_function(Xs)),
+                                      O.acquisition_function(f0))
+                a, da = rec(tag + name + "/acquisition_function_withGradients", lambda: acq.acquisition_function_withGradients(Xs))
                 assert np.array_equal(a, O.acquisition_function(f1)) and np.array_equal(da, -df1)
             # local penalisation around EI (transform 'none') and LCB (switches itself to 'softplus', LP.py:31-32)
             Xb = Xs[:3]
-            for base, transform in ((cases[0][0], "none"), (cases[1][0], "softplus")):
-                lp = A["LP"].AcquisitionLP(gm, space, None, base, transform="none")
-                assert lp.transform == transform
-                L, Min = 2.5, float(gm.model.Y.min())
-                lp.update_batches(Xb, L, Min)
+            L, Min = 2.5, float(gm.model.Y.min())
+            grad_rows = range(4, Xs.shape[0], 7)   # rows 0..2 are the batch points themselves (|x - x0| = 0)
+            for name, base, transform in (("EI", acqs[0], "none"), ("LCB", acqs[1], "softplus")):
+
+                def ref_lp():
+                    lp = A["LP"].AcquisitionLP(gm, space, None, base, transform="none")
+                    lp.update_batches(Xb, L, Min)
+                    neg = base.acquisition_function(Xs)
+                    ref = lp.acquisition_function(Xs)
+                    # gradient: the reference only broadcasts for one row at a time (LP.py:112-133); each row evaluated
+                    # as the reference evaluates it
+                    rows = [base.acquisition_function_withGradients(Xs[r:r + 1]) + (lp.d_acquisition_function(Xs[r:r + 1]),)
+                            for r in grad_rows]
+                    return lp.transform, lp.r_x0, lp.s_x0, neg, ref, rows
+                lp_transform, r_x0, s_x0, neg, ref, rows = rec(tag + "LP_" + name, ref_lp)
+                assert lp_transform == transform
                 r0, s0 = O.lp_hammer_precompute(gm, Xb, L, Min)
-                assert np.array_equal(lp.r_x0, r0) and np.array_equal(lp.s_x0, s0)
-                neg = base.acquisition_function(Xs)
-                ref = lp.acquisition_function(Xs)
+                assert np.array_equal(r_x0, r0) and np.array_equal(s_x0, s0)
                 mine = O.lp_penalized_acquisition(neg, Xs, Xb, r0, s0, transform)
                 worst = max(worst, float(np.max(np.abs(ref - mine) / np.maximum(1.0, np.abs(ref)))))
-                # gradient: the reference only broadcasts for one row at a time (LP.py:112-133)
-                for r in range(4, Xs.shape[0], 7):   # rows 0..2 are the batch points themselves (|x - x0| = 0)
-                    xr = Xs[r:r + 1]
-                    negr, negdr = base.acquisition_function_withGradients(xr)   # as the reference evaluates it: one row
-                    gref = lp.d_acquisition_function(xr)
-                    gmine = O.lp_d_acquisition(negr, negdr, xr, Xb, r0, s0, transform)
+                for r, (negr, negdr, gref) in zip(grad_rows, rows):
+                    gmine = O.lp_d_acquisition(negr, negdr, Xs[r:r + 1], Xb, r0, s0, transform)
                     worst = max(worst, float(np.max(np.abs(gref - gmine) / np.maximum(1.0, np.abs(gref)))))
     assert worst < 1e-13, worst
     return "AcquisitionEI/LCB/MPI verbatim == oracle bit-identical; AcquisitionLP value/gradient within %.1e" % worst
 
 
-def check_lp_evaluator(A):
-    """estimate_L and LocalPenalization.compute_batch of the verbatim evaluator module against the oracle's, same
-    numpy seed, oracle-backed model; compute_batch with the acquisition's optimiser replaced by an arg-min over a fixed
-    candidate table (the optimiser itself is scipy, out of scope)."""
-    ev = A["lp_evaluator"]
-    gm, Xs = _oracle_model("Mat52", seed=5)
-    bounds = [(0.0, 1.0)] * Xs.shape[1]
-    np.random.seed(7)
-    try:
-        L_ref = ev.estimate_L(gm.model, bounds)
-    except (TypeError, IndexError, ValueError) as e:
-        # scipy >= 1.5 hands minimize()'s scalar `fun` back as a float; the reference (pinned to scipy 1.2.0,
-        # to_install.txt:12) indexes it as res.fun[0][0].  Its algorithm up to that line is what can run here.
-        L_ref = None
-        note = "reference estimate_L does not run on this scipy (%s: %s)" % (type(e).__name__, e)
-    np.random.seed(7)
-    L_mine = O.estimate_L(gm.model, bounds)
-    if L_ref is not None:
-        assert abs(L_ref - L_mine) <= 1e-12 * abs(L_ref), (L_ref, L_mine)
-        note = "estimate_L verbatim == oracle (%.12g)" % L_mine
-    else:
-        # same sampling stream and the same starting point: replay the reference's lines 60-65 by hand
-        np.random.seed(7)
-        gen = sys.modules["GPyOpt.util.general"]
-        samples = np.vstack([gen.samples_multidimensional_uniform(bounds, 500), gm.model.X])
-        dm, _ = gm.model.predictive_gradients(samples)
-        start = -np.sqrt((dm * dm).sum(1)).min()
-        assert L_mine >= -start - 1e-12, (L_mine, start)
-    space = _Space(bounds)
-    table = Xs
-
-    class TableLP(A["LP"].AcquisitionLP):
+def _tabled(cls, table):
+    """``cls`` with its optimiser replaced by an arg-min over a fixed candidate table."""
+    class TableLP(cls):
         def optimize(self, duplicate_manager=None):
             a = self.acquisition_function(table)
             i = int(np.argmin(a))
             return table[i:i + 1], a[i]
+    return TableLP
+
+
+def check_lp_evaluator(A, rec):
+    """estimate_L and LocalPenalization.compute_batch of the verbatim evaluator module against the oracle's, same
+    numpy seed, oracle-backed model; compute_batch with the acquisition's optimiser replaced by an arg-min over a fixed
+    candidate table (the optimiser itself is scipy, out of scope).  Without the reference tree the oracle's batch loop
+    drives the oracle's own AcquisitionLP (pinned to the verbatim one by check_acquisitions)."""
+    ev = A["lp_evaluator"] if A is not None else None
+    gm, Xs = _oracle_model("Mat52", seed=5)
+    bounds = [(0.0, 1.0)] * Xs.shape[1]
+
+    def ref_estimate_L():
+        np.random.seed(7)
+        try:
+            return True, float(ev.estimate_L(gm.model, bounds)), ""
+        except (TypeError, IndexError, ValueError) as e:
+            # scipy >= 1.5 hands minimize()'s scalar `fun` back as a float; the reference (pinned to scipy 1.2.0,
+            # to_install.txt:12) indexes it as res.fun[0][0].  Its algorithm up to that line is what can run here.
+            return False, float("nan"), "%s: %s" % (type(e).__name__, e)
+    ran, L_ref, err = rec("lp_evaluator/estimate_L", ref_estimate_L)
+    np.random.seed(7)
+    L_mine = O.estimate_L(gm.model, bounds)
+    if ran:
+        assert abs(L_ref - L_mine) <= 1e-12 * abs(L_ref), (L_ref, L_mine)
+        note = "estimate_L verbatim == oracle (%.12g)" % L_mine
+    else:
+        note = "reference estimate_L does not run on this scipy (%s)" % err
+        # same sampling stream and the same starting point: replay the reference's lines 60-65 by hand
+
+        def ref_samples():
+            np.random.seed(7)
+            return sys.modules["GPyOpt.util.general"].samples_multidimensional_uniform(bounds, 500)
+        samples = np.vstack([rec("lp_evaluator/samples", ref_samples), gm.model.X])
+        dm, _ = gm.model.predictive_gradients(samples)
+        start = -np.sqrt((dm * dm).sum(1)).min()
+        assert L_mine >= -start - 1e-12, (L_mine, start)
+    space = _Space(bounds)
     gm.analytical_gradient_prediction = True
-    base = A["EI"].AcquisitionEI(gm, space, None, None, jitter=0.01)
-    sys.modules["GPyOpt.acquisitions"].AcquisitionLP = A["LP"].AcquisitionLP
-    lp = TableLP(gm, space, None, base)
-    saved = ev.estimate_L
-    if L_ref is None:
-        ev.estimate_L = O.estimate_L   # the verbatim batch loop around the one function that cannot run here
-    try:
-        np.random.seed(11)
-        B_ref = ev.LocalPenalization(lp, 4).compute_batch()
-    finally:
-        ev.estimate_L = saved
+    if A is not None:
+        TableLP = _tabled(A["LP"].AcquisitionLP, Xs)
+        base = A["EI"].AcquisitionEI(gm, space, None, None, jitter=0.01)
+
+    def ref_batch():
+        sys.modules["GPyOpt.acquisitions"].AcquisitionLP = A["LP"].AcquisitionLP
+        lp = TableLP(gm, space, None, base)
+        saved = ev.estimate_L
+        if not ran:
+            ev.estimate_L = O.estimate_L   # the verbatim batch loop around the one function that cannot run here
+        try:
+            np.random.seed(11)
+            return ev.LocalPenalization(lp, 4).compute_batch()
+        finally:
+            ev.estimate_L = saved
+    B_ref = rec("lp_evaluator/compute_batch", ref_batch)
     np.random.seed(11)
-    B_mine = O.lp_compute_batch(TableLP(gm, space, None, base), 4)
+    lp_mine = TableLP(gm, space, None, base) if A is not None else _tabled(O.OracleLP, Xs)(gm, space, "EI")
+    B_mine = O.lp_compute_batch(lp_mine, 4)
     assert B_ref.shape == (4, Xs.shape[1]) and np.array_equal(B_ref, B_mine)
     note += "; LocalPenalization.compute_batch verbatim == oracle (4 points)"
     return note
 
 
-def check_gower_space_and_table_loop(A):
+def check_gower_space_and_table_loop(A, rec):
     """The fork's mixed design space and the table loop of run.py:1234-1258 under the Gower kernel:
     (1) the reference's verbatim ``Design_space`` (GPyOpt/GPyOpt/core/task/space.py) against ``O.MixedSpace`` on the four
     methods the path calls; (2) the loop driven by the reference's verbatim AcquisitionLP / AcquisitionEI / AcquisitionLCB
     objects on an oracle-backed Gower model against the same loop driven by ``O.OracleLP`` -- identical rows, L and final
     score vector."""
     import importlib
-    space_mod = importlib.import_module("GPyOpt.core.task.space")
+    space_mod = importlib.import_module("GPyOpt.core.task.space") if A is not None else None
     domains = [
         [{'name': 'a', 'type': 'discrete', 'domain': (0, 1, 2, 3)}, {'name': 'x', 'type': 'continuous', 'domain': (-2.0, 5.0)},
          {'name': 'b', 'type': 'discrete', 'domain': (10, 20)}, {'name': 'y', 'type': 'continuous', 'domain': (0.0, 0.5)}],
         [{'name': 'm', 'type': 'discrete', 'domain': tuple(range(5))}, {'name': 'p', 'type': 'discrete', 'domain': tuple(range(7))},
          {'name': 'q', 'type': 'discrete', 'domain': (0, 1, 2)}, {'name': 'r', 'type': 'discrete', 'domain': (0, 1)},
          {'name': 'c', 'type': 'continuous', 'domain': (12.0, 48.0)}, {'name': 'l', 'type': 'continuous', 'domain': (25.4, 100.0)}]]
-    for dom in domains:
-        ref, mine = space_mod.Design_space(dom), O.MixedSpace(dom)
-        assert ref.lengthscales() == mine.lengthscales()
-        assert ref.get_continuous_dims() == mine.get_continuous_dims()
-        assert ref.get_discrete_dims() == mine.get_discrete_dims()
-        assert ref.get_bounds() == mine.get_bounds()
+    for i, dom in enumerate(domains):
+        mine = O.MixedSpace(dom)
+
+        def ref_space():
+            ref = space_mod.Design_space(dom)
+            return ref.lengthscales(), ref.get_continuous_dims(), ref.get_discrete_dims(), ref.get_bounds()
+        lengthscales, cont, disc, bounds = rec("gower/space%d" % i, ref_space)
+        assert lengthscales == mine.lengthscales()
+        assert cont == mine.get_continuous_dims()
+        assert disc == mine.get_discrete_dims()
+        assert bounds == mine.get_bounds()
     dom = domains[1]
-    ref, mine = space_mod.Design_space(dom), O.MixedSpace(dom)
+    # the Gower kernel reads the design space: the verbatim one where the reference is present (equal to MixedSpace on
+    # every method it calls, above)
+    ref, mine = space_mod.Design_space(dom) if A is not None else None, O.MixedSpace(dom)
     rng = np.random.default_rng(8)
     X, table = mine.draw(rng, 70), mine.draw(rng, 400)
     Y = O.normalize(np.sin(X[:, 4:5] / 6.0) + 0.2 * X[:, 0:1] - 0.1 * (X[:, 2:3] == 1) + 0.02 * rng.standard_normal((70, 1)))
     worst = 0.0
     for base, cls_key, kw in (("EI", "EI", dict(jitter=0.01)), ("LCB", "LCB", dict(exploration_weight=2))):
-        gp = O.OracleGP(X, Y, O.make_kernel("Mat52", 6, 0.9, [1.5], Gower=True, space=ref), 1e-6)
+        gp = O.OracleGP(X, Y, O.make_kernel("Mat52", 6, 0.9, [1.5], Gower=True, space=ref if A is not None else mine), 1e-6)
         gm = O.OracleGPModel(gp)
         gm.analytical_gradient_prediction = True
-        cls = getattr(A[cls_key], "Acquisition" + cls_key)
-        lp_ref = A["LP"].AcquisitionLP(gm, ref, None, cls(gm, ref, None, None, **kw))
+
+        def ref_loop():
+            cls = getattr(A[cls_key], "Acquisition" + cls_key)
+            lp_ref = A["LP"].AcquisitionLP(gm, ref, None, cls(gm, ref, None, None, **kw))
+            np.random.seed(21)
+            rows_ref, L_ref, Min_ref = O.lp_table_batch(lp_ref, table, 5)
+            return lp_ref.transform, rows_ref, L_ref, Min_ref, lp_ref.acquisition_function(table)
+        transform_ref, rows_ref, L_ref, Min_ref, a = rec("gower/loop_" + base, ref_loop)
         lp_mine = O.OracleLP(gm, mine, base)
-        assert lp_ref.transform == lp_mine.transform
-        np.random.seed(21)
-        rows_ref, L_ref, Min_ref = O.lp_table_batch(lp_ref, table, 5)
+        assert transform_ref == lp_mine.transform
         np.random.seed(21)
         rows_mine, L_mine, Min_mine = O.lp_table_batch(lp_mine, table, 5)
         assert rows_ref == rows_mine and L_ref == L_mine and Min_ref == Min_mine
-        a, b = lp_ref.acquisition_function(table), lp_mine.acquisition_function(table)
+        b = lp_mine.acquisition_function(table)
         worst = max(worst, float(np.max(np.abs(a - b) / np.maximum(1.0, np.abs(a)))))
     assert worst < 1e-13, worst
     return "Design_space verbatim == MixedSpace; table loop on verbatim AcquisitionLP == OracleLP (rows, L; scores %.1e)" % worst
@@ -369,17 +461,18 @@ def main():
     if not ref_leaf.available():
         print("reference tree absent: cannot pin"); return 2
     R = ref_leaf.load()
-    print(check_linalg(R))
+    rec = Recorded(True)
+    print(check_linalg(R, rec))
     lib = ref_leaf.load_stationary_utils()
     if lib is None:
         print("oracle/_ref/libstationary_utils.so missing: run `make -C oracle`"); return 2
-    print(check_native(lib))
-    print(check_lml_through_reference(R))
+    print(check_native(lib, rec))
+    print(check_lml_through_reference(R, rec))
     print(check_invariants())
     A = ref_leaf.load_acquisitions()
-    print(check_acquisitions(A))
-    print(check_lp_evaluator(A))
-    print(check_gower_space_and_table_loop(A))
+    print(check_acquisitions(A, rec))
+    print(check_lp_evaluator(A, rec))
+    print(check_gower_space_and_table_loop(A, rec))
     print("ORACLE PINNED")
     return 0
 

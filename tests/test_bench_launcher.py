@@ -229,3 +229,35 @@ def test_rendezvous_place_is_private(tmp_path, monkeypatch):
     key2, path2 = bench.rendezvous_place()
     st = os.stat(os.path.dirname(path2))
     assert st.st_uid == os.getuid() and (st.st_mode & 0o077) == 0 and len(key2) == 64
+
+
+def test_dump_outputs_writes_float64_arrays_and_samples_a_large_table(tmp_path, monkeypatch):
+    """bench.dump_outputs (--dump-outputs): every array float64, the whole posterior when it is small, a fixed sample of its rows
+    (the same sample every run, its row numbers beside it) when it is larger than DUMP_MAX_ROWS."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    try:
+        import bench
+    finally:
+        sys.path.pop(0)
+    rng = np.random.default_rng(3)
+    mean, var = rng.standard_normal((50, 1)), rng.uniform(0.1, 1.0, (50, 1))
+    out = (-12.5, 17, -0.25, {"logdet": 3.0, "jitter": 0.0, "fmin": -1.5, "mean": mean, "var": var})
+    bench.dump_outputs(str(tmp_path / "all"), out, 0, 0, None)
+    got = {f[:-4]: np.load(str(tmp_path / "all" / f)) for f in os.listdir(str(tmp_path / "all"))}
+    assert set(got) == {"mean", "var", "lml", "logdet", "jitter", "fmin", "best_row", "best_value"}
+    assert all(a.dtype == np.float64 for a in got.values())
+    assert np.array_equal(got["mean"], mean) and np.array_equal(got["var"], var)
+    assert got["lml"][0] == -12.5 and got["best_row"][0] == 17 and got["best_value"][0] == -0.25 and got["fmin"][0] == -1.5
+    monkeypatch.setattr(bench, "DUMP_MAX_ROWS", 20)
+    for d in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / d), out, 0, 0, None)
+    rows = np.load(str(tmp_path / "s1" / "rows.npy")).astype(int)
+    assert rows.shape == (20,) and np.all(np.diff(rows) > 0)
+    assert np.array_equal(np.load(str(tmp_path / "s1" / "mean.npy")), mean[rows])
+    assert np.array_equal(rows, np.load(str(tmp_path / "s2" / "rows.npy")).astype(int))
+    # the C4 step predicts nothing it returns: scalars only
+    bench.dump_outputs(str(tmp_path / "c4"), out[:3] + ({"logdet": 3.0, "jitter": 0.0, "fmin": -1.5, "mean": None, "var": None},),
+                       0, 0, None)
+    assert sorted(os.listdir(str(tmp_path / "c4"))) == sorted(k + ".npy" for k in ("lml", "logdet", "jitter", "fmin", "best_row",
+                                                                                      "best_value"))

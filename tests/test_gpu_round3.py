@@ -204,7 +204,7 @@ def test_optimize_on_a_flat_ridge_ends_at_the_same_likelihood(monkeypatch, mode,
 
 
 def test_bench_starts_its_own_ranks_on_one_device():
-    """`python bench.py --gpus 2` with no launcher around it (the shape of the driver's command): the parent spawns two fresh rank
+    """`python bench.py --full --gpus 2` with no launcher around it: the parent spawns two fresh rank
     processes, they rendezvous over 127.0.0.1 and print ONE JSON line from rank 0 that holds BOTH multi-rank measurements (reduced
     here: N = 2048): the metric's own workload as ONE job -- the table of the N = 1 run split over the ranks, an arg-best exchange per
     step, value = job iterations/s (strong scaling), the winner the N = 1 run finds -- and the candidate-sharding configuration C4 --
@@ -218,8 +218,9 @@ def test_bench_starts_its_own_ranks_on_one_device():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "GPHIP_EMULATE_FP64")}
     env["GPHIP_BENCH_SAME_DEVICE"] = "1"
-    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--N", "2048", "--M", "3000", "--c4-M", "20000",
-                          "--steps", "2", "--warmup", "1"], cwd=root, env=env, capture_output=True, text=True, timeout=600)
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--gpus", "2", "--N", "2048", "--M", "3000",
+                          "--c4-M", "20000", "--steps", "2", "--warmup", "1"], cwd=root, env=env, capture_output=True, text=True,
+                         timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith('{"metric"')]
     assert len(lines) == 1, out.stdout[-2000:]
@@ -255,7 +256,7 @@ def test_bench_starts_its_own_ranks_on_one_device():
 
 
 def test_bench_line_keeps_the_driver_contract():
-    """One short `python bench.py` (N = 1, the quoted workload, two timed steps, CPU baseline and the emulated line switched off
+    """One short `python bench.py --full` (N = 1, the quoted workload, two timed steps, CPU baseline and the emulated line switched off
     to stay within seconds): ONE JSON line with the keys the driver reads, the metric of BASELINE.json, true fp64, and the roofline
     entry for the dominant kernel measured inside the timed region -- per launch and for the whole step."""
     import json
@@ -264,7 +265,7 @@ def test_bench_line_keeps_the_driver_contract():
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
-    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "2", "--warmup", "1", "--no-cpu-baseline",
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--steps", "2", "--warmup", "1", "--no-cpu-baseline",
                           "--no-emulated-line"], cwd=root, env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith('{"metric"')]
@@ -288,6 +289,31 @@ def test_bench_line_keeps_the_driver_contract():
     assert abs(r["step_algorithmic_flops"] - (N ** 3 / 3.0 + float(N) * N * M)) < 1.0
     assert abs(r["step_achieved"] - r["step_algorithmic_flops"] / (d["ms_per_step"] * 1e-3) / 1e12) < 1e-9
     assert 0.3 < r["step_frac"] < 1.0
+
+
+def test_plain_bench_line_and_its_dumped_outputs(tmp_path):
+    """A plain `python bench.py` (no --full) times the steps and prints the headline only; --dump-outputs writes what the last
+    timed step returned -- the posterior of every candidate and the winner the line reports -- as float64 .npy files."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--N", "2048", "--M", "3000", "--steps", "3", "--warmup", "1",
+                          "--dump-outputs", str(tmp_path)], cwd=root, env=env, capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-2000:]
+    d = json.loads(out.stdout.strip())
+    assert d["steps"] == 3 and d["warmup"] == 1 and abs(d["value"] * d["ms_per_step"] * 1e-3 - 1.0) < 1e-9
+    for k in ("roofline", "chain_gemm", "kbuild", "emulated_fp64_second_line", "cpu_baseline"):
+        assert k not in d, k
+    got = {f[:-4]: np.load(os.path.join(str(tmp_path), f)) for f in os.listdir(str(tmp_path))}
+    assert set(got) == {"mean", "var", "lml", "logdet", "jitter", "fmin", "best_row", "best_value"}
+    assert all(a.dtype == np.float64 for a in got.values())
+    assert got["mean"].shape == (3000, 1) and got["var"].shape == (3000, 1) and np.all(got["var"] > 0)
+    cfg = d["config"]
+    assert got["lml"][0] == cfg["lml"] and got["best_row"][0] == cfg["best_candidate_global_row"]
+    assert got["best_value"][0] == cfg["best_value"]
 
 
 @pytest.mark.parametrize("kname", ["rbf", "matern52"])

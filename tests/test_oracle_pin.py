@@ -1,43 +1,44 @@
-"""CPU (build container only): the oracle against the reference's verbatim leaf modules and compiled C."""
+"""CPU: the oracle and the host mirror against the reference's verbatim leaf modules and compiled C.
+
+Where the reference tree is present every reference value is computed live; elsewhere it is read from
+tests/golden/pin_reference.npz, which tests/golden/generate_pin.py stores from a live run of these same tests."""
 import pytest
 
 from oracle import pin_against_reference as pin
 from oracle import ref_leaf
 
-needs_ref = pytest.mark.skipif(not ref_leaf.available(), reason="reference tree not mounted (GPU box)")
+LIVE = ref_leaf.available()
+REC = pin.Recorded(LIVE)
 
 
-@needs_ref
 def test_linalg_bit_identical():
-    assert "bit-identical" in pin.check_linalg(ref_leaf.load())
+    assert "bit-identical" in pin.check_linalg(ref_leaf.load() if LIVE else None, REC)
 
 
-@needs_ref
 def test_native_reductions():
-    lib = ref_leaf.load_stationary_utils()
-    if lib is None:
-        pytest.skip("oracle/_ref not built")
-    pin.check_native(lib)
+    lib = None
+    if LIVE:
+        lib = ref_leaf.load_stationary_utils()
+        if lib is None:
+            pytest.skip("oracle/_ref not built")
+    pin.check_native(lib, REC)
 
 
-@needs_ref
 def test_lml_through_reference():
-    pin.check_lml_through_reference(ref_leaf.load())
+    pin.check_lml_through_reference(ref_leaf.load() if LIVE else None, REC)
 
 
-@needs_ref
 def test_acquisition_layer_verbatim():
     """EI / LCB / MPI / LP and the local-penalisation evaluator: the reference's own modules on an oracle-backed model."""
-    A = ref_leaf.load_acquisitions()
-    assert "bit-identical" in pin.check_acquisitions(A)
-    assert "compute_batch verbatim == oracle" in pin.check_lp_evaluator(A)
+    A = ref_leaf.load_acquisitions() if LIVE else None
+    assert "bit-identical" in pin.check_acquisitions(A, REC)
+    assert "compute_batch verbatim == oracle" in pin.check_lp_evaluator(A, REC)
 
 
-@needs_ref
 def test_gower_space_and_table_loop_verbatim():
     """The reference's own Design_space and AcquisitionLP driving the run.py:1234-1258 loop under the Gower kernel."""
-    A = ref_leaf.load_acquisitions()
-    assert "table loop on verbatim AcquisitionLP == OracleLP" in pin.check_gower_space_and_table_loop(A)
+    A = ref_leaf.load_acquisitions() if LIVE else None
+    assert "table loop on verbatim AcquisitionLP == OracleLP" in pin.check_gower_space_and_table_loop(A, REC)
 
 
 def test_reference_test_invariants():
@@ -45,35 +46,40 @@ def test_reference_test_invariants():
     pin.check_invariants()
 
 
-@needs_ref
 def test_product_design_space_against_the_verbatim_one():
     """The host mirror's Design_space (bounds, Gower additions, rounding of an optimiser's end point onto the domain) against
     the reference's own class (GPyOpt/GPyOpt/core/task/space.py:263-272,328-362,436-445,483-492), imported verbatim."""
     import importlib
     import numpy as np
     import gaussian_process_optimization_amd as gpo
-    ref_leaf.load_acquisitions()
-    space_mod = importlib.import_module("GPyOpt.core.task.space")
+    if LIVE:
+        ref_leaf.load_acquisitions()
+        space_mod = importlib.import_module("GPyOpt.core.task.space")
     dom = [{'name': 'm', 'type': 'discrete', 'domain': tuple(range(6))}, {'name': 'p', 'type': 'discrete', 'domain': (1, 4, 9, 16)},
            {'name': 'c', 'type': 'continuous', 'domain': (12.0, 48.0)}, {'name': 'q', 'type': 'discrete', 'domain': (0, 1)},
            {'name': 'l', 'type': 'continuous', 'domain': (-2.5, 100.0)}]
-    ref, mine = space_mod.Design_space(dom), gpo.Design_space(dom)
-    assert ref.get_bounds() == mine.get_bounds()
-    assert ref.lengthscales() == mine.lengthscales()
-    assert ref.get_continuous_dims() == mine.get_continuous_dims() and ref.get_discrete_dims() == mine.get_discrete_dims()
-    assert ref.dimensionality == mine.dimensionality and ref.model_dimensionality == mine.model_dimensionality
-    assert ref.has_constraints() == mine.has_constraints()
+    ref = space_mod.Design_space(dom) if LIVE else None
+    mine = gpo.Design_space(dom)
+    bounds, lengthscales, cont, disc, dims, has_constraints = REC("design_space/methods", lambda: (
+        ref.get_bounds(), ref.lengthscales(), ref.get_continuous_dims(), ref.get_discrete_dims(),
+        (ref.dimensionality, ref.model_dimensionality), ref.has_constraints()))
+    assert bounds == mine.get_bounds()
+    assert lengthscales == mine.lengthscales()
+    assert cont == mine.get_continuous_dims() and disc == mine.get_discrete_dims()
+    assert dims == (mine.dimensionality, mine.model_dimensionality)
+    assert has_constraints == mine.has_constraints()
     rng = np.random.default_rng(0)
-    lo = np.array([b[0] for b in ref.get_bounds()], dtype=float)
-    hi = np.array([b[1] for b in ref.get_bounds()], dtype=float)
-    for _ in range(200):
-        x = lo + (hi - lo) * rng.uniform(-0.1, 1.1, 5)          # also a little outside the box, as a line search may end
-        np.testing.assert_array_equal(np.asarray(ref.round_optimum(x), dtype=float), mine.round_optimum(x))
+    lo = np.array([b[0] for b in bounds], dtype=float)
+    hi = np.array([b[1] for b in bounds], dtype=float)
+    xs = [lo + (hi - lo) * rng.uniform(-0.1, 1.1, 5) for _ in range(200)]   # also a little outside the box, as a line search may end
+    rounded = REC("design_space/round_optimum", lambda: np.array([np.asarray(ref.round_optimum(x), dtype=float) for x in xs]))
+    for x, r in zip(xs, rounded):
+        np.testing.assert_array_equal(r, mine.round_optimum(x))
     x = rng.uniform(0, 1, (7, 5))
-    np.testing.assert_array_equal(ref.indicator_constraints(x), mine.indicator_constraints(x))
+    np.testing.assert_array_equal(REC("design_space/indicator_constraints", lambda: ref.indicator_constraints(x)),
+                                  mine.indicator_constraints(x))
 
 
-@needs_ref
 def test_product_host_helpers_against_the_verbatim_ones():
     """The host mirror's remaining arithmetic helpers against the reference's own (GPyOpt/GPyOpt/util/general.py): `normalize`
     (:203-234, both modes), `get_quantiles` (:113-129) and the sampling stream `estimate_L` draws its 500 starting points from
@@ -82,30 +88,38 @@ def test_product_host_helpers_against_the_verbatim_ones():
     import gaussian_process_optimization_amd as gpo
     from gaussian_process_optimization_amd import acquisitions as A
     from gaussian_process_optimization_amd.bayesian_optimization import normalize
-    _, _, _, general = ref_leaf.load()
+    _, _, normalizer, general = ref_leaf.load() if LIVE else (None,) * 4
     rng = np.random.default_rng(1)
     Y = rng.standard_normal((37, 1)) * 3.0 + 5.0
     for mode in ("stats", "maxmin"):
-        assert np.array_equal(normalize(Y, mode), general.normalize(Y, mode))
+        assert np.array_equal(normalize(Y, mode), REC("helpers/normalize_" + mode, lambda: general.normalize(Y, mode)))
     m, s = rng.standard_normal((50, 1)), np.abs(rng.standard_normal((50, 1))) * 0.3
     s[3] = 1e-12                                            # below the floor
     got = A.get_quantiles(0.01, -0.2, m, s.copy())
-    ref = general.get_quantiles(0.01, -0.2, m, s.copy())
+    ref = REC("helpers/get_quantiles", lambda: general.get_quantiles(0.01, -0.2, m, s.copy()))
     for a, b in zip(got, ref):
         assert np.array_equal(a, b)
     from gaussian_process_optimization_amd.gp_regression import Standardize
-    _, _, normalizer, _ = ref_leaf.load()
     Ym = rng.standard_normal((40, 3)) * [1.0, 5.0, 0.2] + [0.0, -3.0, 10.0]
-    mine_n, ref_n = Standardize(), normalizer.Standardize()
+    mine_n = Standardize()
     mine_n.scale_by(Ym)
-    ref_n.scale_by(Ym)
-    assert np.array_equal(mine_n.mean, ref_n.mean) and np.array_equal(mine_n.std, ref_n.std)
-    assert np.array_equal(mine_n.normalize(Ym), ref_n.normalize(Ym))
-    assert np.array_equal(mine_n.inverse_mean(Ym[:5]), ref_n.inverse_mean(Ym[:5]))
-    assert np.array_equal(mine_n.inverse_variance(np.abs(Ym[:5, :1])), ref_n.inverse_variance(np.abs(Ym[:5, :1])))
+
+    def ref_standardize():
+        ref_n = normalizer.Standardize()
+        ref_n.scale_by(Ym)
+        return (ref_n.mean, ref_n.std, ref_n.normalize(Ym), ref_n.inverse_mean(Ym[:5]),
+                ref_n.inverse_variance(np.abs(Ym[:5, :1])))
+    r_mean, r_std, r_norm, r_imean, r_ivar = REC("helpers/Standardize", ref_standardize)
+    assert np.array_equal(mine_n.mean, r_mean) and np.array_equal(mine_n.std, r_std)
+    assert np.array_equal(mine_n.normalize(Ym), r_norm)
+    assert np.array_equal(mine_n.inverse_mean(Ym[:5]), r_imean)
+    assert np.array_equal(mine_n.inverse_variance(np.abs(Ym[:5, :1])), r_ivar)
     bounds = [(0, 5), (12.0, 48.0), (-1.0, 1.0)]
-    np.random.seed(5)
-    ref_draws = general.samples_multidimensional_uniform(bounds, 500)
+
+    def ref_samples():
+        np.random.seed(5)
+        return general.samples_multidimensional_uniform(bounds, 500)
+    ref_draws = REC("helpers/samples_multidimensional_uniform", ref_samples)
 
     class _Flat(object):                                    # estimate_L's model: only the draws matter here
         X = np.zeros((1, 3))
@@ -121,7 +135,6 @@ def test_product_host_helpers_against_the_verbatim_ones():
     assert np.array_equal(flat.seen, ref_draws)
 
 
-@needs_ref
 def test_product_design_samples_and_acquisition_optimiser_against_the_verbatim_ones():
     """Under the same numpy seed the host mirror draws the reference's random design (experiment_design/random_design.py, with and
     without constraints, discrete and continuous variables in any order) and its acquisition optimiser ends where the reference's
@@ -133,18 +146,22 @@ def test_product_design_samples_and_acquisition_optimiser_against_the_verbatim_o
     import gaussian_process_optimization_amd as gpo
     from gaussian_process_optimization_amd.bayesian_optimization import AcquisitionOptimizer
     from oracle import cpu_ref as O
-    ref_leaf.load_acquisitions()
-    ref_leaf._pkg("GPyOpt.optimization", ref_leaf.REF + "/GPyOpt/GPyOpt/optimization")
-    ref_leaf._pkg("GPyOpt.experiment_design", ref_leaf.REF + "/GPyOpt/GPyOpt/experiment_design")
-    space_mod = importlib.import_module("GPyOpt.core.task.space")
-    rd = importlib.import_module("GPyOpt.experiment_design.random_design")
-    opt = importlib.import_module("GPyOpt.optimization.optimizer")
+    if LIVE:
+        ref_leaf.load_acquisitions()
+        ref_leaf._pkg("GPyOpt.optimization", ref_leaf.REF + "/GPyOpt/GPyOpt/optimization")
+        ref_leaf._pkg("GPyOpt.experiment_design", ref_leaf.REF + "/GPyOpt/GPyOpt/experiment_design")
+        space_mod = importlib.import_module("GPyOpt.core.task.space")
+        rd = importlib.import_module("GPyOpt.experiment_design.random_design")
+        opt = importlib.import_module("GPyOpt.optimization.optimizer")
     dom = [{'name': 'c', 'type': 'continuous', 'domain': (0.0, 1.0)}, {'name': 'm', 'type': 'discrete', 'domain': (0, 1, 2)},
            {'name': 'l', 'type': 'continuous', 'domain': (-1.0, 2.0)}, {'name': 'q', 'type': 'discrete', 'domain': (0.0, 0.5, 1.0)}]
-    for cons in (None, [{'name': 'k', 'constraint': 'x[:,0] + x[:,2] - 1.5'}]):
-        ref, mine = space_mod.Design_space(dom, cons), gpo.Design_space(dom, cons)
-        np.random.seed(12)
-        a = rd.RandomDesign(ref).get_samples(300)
+    for i, cons in enumerate((None, [{'name': 'k', 'constraint': 'x[:,0] + x[:,2] - 1.5'}])):
+        mine = gpo.Design_space(dom, cons)
+
+        def ref_samples():
+            np.random.seed(12)
+            return rd.RandomDesign(space_mod.Design_space(dom, cons)).get_samples(300)
+        a = REC("design_samples/random_design%d" % i, ref_samples)
         np.random.seed(12)
         b = mine.samples_uniform(300)
         assert np.array_equal(a, b)
@@ -155,19 +172,23 @@ def test_product_design_samples_and_acquisition_optimiser_against_the_verbatim_o
     f = lambda x: -O.acq_EI(gm, np.atleast_2d(x), 0.01, fmin)                                       # noqa: E731
     f_df = lambda x: tuple(-v for v in O.acq_EI_withGradients(gm, np.atleast_2d(x), 0.01, fmin))      # noqa: E731
     box = [{'name': 'x', 'type': 'continuous', 'domain': (0.0, 1.0), 'dimensionality': 2}]
-    ref, mine = space_mod.Design_space(box), gpo.Design_space(box)
-    np.random.seed(3)
-    Xd = rd.RandomDesign(ref).get_samples(1000)
-    anchors = Xd[np.argsort(f(Xd).flatten())[:5], :]                                                  # anchor_points_generator.py:59-61
-    lb = opt.OptLbfgs(ref.get_bounds())
-    ends = [opt.apply_optimizer(lb, a, f=f, df=None, f_df=f_df, space=ref) for a in anchors]
-    x_ref, fx_ref = min(ends, key=lambda t: t[1])                                                     # acquisition_optimizer.py:74-77
+    mine = gpo.Design_space(box)
+
+    def ref_optimum():
+        ref = space_mod.Design_space(box)
+        np.random.seed(3)
+        Xd = rd.RandomDesign(ref).get_samples(1000)
+        anchors = Xd[np.argsort(f(Xd).flatten())[:5], :]                                              # anchor_points_generator.py:59-61
+        lb = opt.OptLbfgs(ref.get_bounds())
+        ends = [opt.apply_optimizer(lb, a, f=f, df=None, f_df=f_df, space=ref) for a in anchors]
+        x_ref, fx_ref = min(ends, key=lambda t: t[1])                                                 # acquisition_optimizer.py:74-77
+        return np.asarray(x_ref), float(np.ravel(fx_ref)[0])
+    x_ref, fx_ref = REC("design_samples/acquisition_optimizer", ref_optimum)
     np.random.seed(3)
     x_mine, fx_mine = AcquisitionOptimizer(mine, 'lbfgs').optimize(f=f, f_df=f_df)
-    assert np.array_equal(np.asarray(x_ref), x_mine) and float(np.ravel(fx_ref)[0]) == fx_mine
+    assert np.array_equal(x_ref, x_mine) and fx_ref == fx_mine
 
 
-@needs_ref
 def test_product_host_acquisition_layer_against_the_verbatim_one():
     """The host mirror's acquisition classes on a FOREIGN model (an oracle-backed BOModel: the `_Rule` formulas and the host side
     of AcquisitionLP / LocalPenalization / estimate_L, what the device path falls back to for models it cannot see) against the
@@ -175,52 +196,61 @@ def test_product_host_acquisition_layer_against_the_verbatim_one():
     import numpy as np
     import gaussian_process_optimization_amd as gpo
     from oracle import cpu_ref as O
-    A = ref_leaf.load_acquisitions()
+    A = ref_leaf.load_acquisitions() if LIVE else None
     X, Y, Xs = O.synthetic_problem(70, 2, 50, seed=6)
     gm = O.OracleGPModel(O.OracleGP(X, Y, O.make_kernel("rbf", 2, 1.2, [0.35]), 1e-2))
     gm.analytical_gradient_prediction = True
     space = pin._Space([(0.0, 1.0)] * 2)
-    pairs = [(gpo.AcquisitionEI(gm, space, None, None, jitter=0.01), A["EI"].AcquisitionEI(gm, space, None, None, jitter=0.01)),
-             (gpo.AcquisitionLCB(gm, space, None, None, exploration_weight=2), A["LCB"].AcquisitionLCB(gm, space, None, None, exploration_weight=2)),
-             (gpo.AcquisitionMPI(gm, space, None, None, jitter=0.01), A["MPI"].AcquisitionMPI(gm, space, None, None, jitter=0.01))]
+    pairs = [("EI", gpo.AcquisitionEI(gm, space, None, None, jitter=0.01),
+              lambda: A["EI"].AcquisitionEI(gm, space, None, None, jitter=0.01)),
+             ("LCB", gpo.AcquisitionLCB(gm, space, None, None, exploration_weight=2),
+              lambda: A["LCB"].AcquisitionLCB(gm, space, None, None, exploration_weight=2)),
+             ("MPI", gpo.AcquisitionMPI(gm, space, None, None, jitter=0.01),
+              lambda: A["MPI"].AcquisitionMPI(gm, space, None, None, jitter=0.01))]
+    refs = {name: make() for name, _, make in pairs} if LIVE else {}
     Xb = Xs[:3]
-    for mine, ref in pairs:
-        assert np.array_equal(mine.acquisition_function(Xs), ref.acquisition_function(Xs))
+    grad_rows = range(4, 20, 5)        # the reference's gradient only broadcasts for one row at a time (LP.py:112-133)
+    for name, mine, _ in pairs:
+        ref = refs.get(name)
+        assert np.array_equal(mine.acquisition_function(Xs),
+                              REC("host_acq/%s/acquisition_function" % name, lambda: ref.acquisition_function(Xs)))
         fm, dm = mine.acquisition_function_withGradients(Xs)
-        fr, dr = ref.acquisition_function_withGradients(Xs)
+        fr, dr = REC("host_acq/%s/acquisition_function_withGradients" % name, lambda: ref.acquisition_function_withGradients(Xs))
         assert np.array_equal(fm, fr)
         np.testing.assert_allclose(dm, dr, rtol=1e-12, atol=0)     # (the shared chain rule adds the two terms in another order)
         lp_m = gpo.AcquisitionLP(gm, space, None, mine)
-        lp_r = A["LP"].AcquisitionLP(gm, space, None, ref)
-        assert lp_m.transform == lp_r.transform
-        for batch in (None, Xb):
+
+        def ref_lp():
+            lp_r = A["LP"].AcquisitionLP(gm, space, None, ref)
+            per_batch = []
+            for batch in (None, Xb):
+                lp_r.update_batches(batch, 2.5, float(Y.min()))
+                per_batch.append((lp_r.r_x0 if batch is not None else np.zeros(0), lp_r.s_x0 if batch is not None else np.zeros(0),
+                                  lp_r.acquisition_function(Xs[4:]), [lp_r.d_acquisition_function(Xs[r:r + 1]) for r in grad_rows]))
+            return lp_r.transform, per_batch
+        transform, per_batch = REC("host_acq/%s/LP" % name, ref_lp)
+        assert lp_m.transform == transform
+        for batch, (r_x0, s_x0, values, grefs) in zip((None, Xb), per_batch):
             lp_m.update_batches(batch, 2.5, float(Y.min()))
-            lp_r.update_batches(batch, 2.5, float(Y.min()))
             if batch is not None:
-                assert np.array_equal(lp_m.r_x0, lp_r.r_x0) and np.array_equal(lp_m.s_x0, lp_r.s_x0)
-            np.testing.assert_allclose(lp_m.acquisition_function(Xs[4:]), lp_r.acquisition_function(Xs[4:]), rtol=1e-13, atol=0)
-            for r in range(4, 20, 5):      # the reference's gradient only broadcasts for one row at a time (LP.py:112-133)
+                assert np.array_equal(lp_m.r_x0, r_x0) and np.array_equal(lp_m.s_x0, s_x0)
+            np.testing.assert_allclose(lp_m.acquisition_function(Xs[4:]), values, rtol=1e-13, atol=0)
+            for r, gref in zip(grad_rows, grefs):
                 gmine = lp_m.acquisition_function_withGradients(Xs[r:r + 1])[1]
-                gref = lp_r.d_acquisition_function(Xs[r:r + 1])
                 np.testing.assert_allclose(gmine, gref, rtol=1e-12, atol=1e-300)
     # the batch loop with the acquisition's optimiser replaced by an arg-min over a table, as oracle/pin_against_reference.py does
     table = Xs
 
-    def tabled(cls):
-        class T(cls):
-            def optimize(self, duplicate_manager=None):
-                a = self.acquisition_function(table)
-                i = int(np.argmin(a))
-                return table[i:i + 1], a[i]
-        return T
-    ev = A["lp_evaluator"]
-    saved = ev.estimate_L
-    ev.estimate_L = O.estimate_L          # (the reference's own indexes res.fun[0][0] and does not run on this scipy)
-    try:
-        np.random.seed(2)
-        B_ref = ev.LocalPenalization(tabled(A["LP"].AcquisitionLP)(gm, space, None, pairs[0][1]), 4).compute_batch()
-    finally:
-        ev.estimate_L = saved
+    def ref_batch():
+        ev = A["lp_evaluator"]
+        saved = ev.estimate_L
+        ev.estimate_L = O.estimate_L      # (the reference's own indexes res.fun[0][0] and does not run on this scipy)
+        try:
+            np.random.seed(2)
+            return ev.LocalPenalization(pin._tabled(A["LP"].AcquisitionLP, table)(gm, space, None, refs["EI"]), 4).compute_batch()
+        finally:
+            ev.estimate_L = saved
+    B_ref = REC("host_acq/compute_batch", ref_batch)
     np.random.seed(2)
-    B_mine = gpo.LocalPenalization(tabled(gpo.AcquisitionLP)(gm, space, None, pairs[0][0]), 4).compute_batch()
+    B_mine = gpo.LocalPenalization(pin._tabled(gpo.AcquisitionLP, table)(gm, space, None, pairs[0][1]), 4).compute_batch()
     assert np.array_equal(B_ref, B_mine)

@@ -5,9 +5,9 @@ cd "$GRAFT_REPO_ROOT" || exit 1
 tag=${1:-r5bench}
 out=gpurun_out/$tag
 mkdir -p $out
-timeout -k 10 500 python3 bench.py > $out/bench.json 2> $out/bench.err; echo "bench rc=$?"
-GPHIP_BENCH_SAME_DEVICE=1 timeout -k 10 400 python3 bench.py --gpus 2 --c4-M 200000 --steps 3 2> $out/bench2.err > $out/bench2.out; echo "self-launched rc=$?"
-GPHIP_BENCH_SAME_DEVICE=1 timeout -k 10 400 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29731 bench.py --gpus 2 --c4-M 200000 --steps 3 2> $out/bench2_torchrun.err > $out/bench2_torchrun.out; echo "torchrun rc=$?"
+timeout -k 10 500 python3 bench.py --full > $out/bench.json 2> $out/bench.err; echo "bench rc=$?"
+GPHIP_BENCH_SAME_DEVICE=1 timeout -k 10 400 python3 bench.py --full --gpus 2 --c4-M 200000 --steps 3 2> $out/bench2.err > $out/bench2.out; echo "self-launched rc=$?"
+GPHIP_BENCH_SAME_DEVICE=1 timeout -k 10 400 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29731 bench.py --full --gpus 2 --c4-M 200000 --steps 3 2> $out/bench2_torchrun.err > $out/bench2_torchrun.out; echo "torchrun rc=$?"
 python3 - <<PY
 import json
 d1 = json.loads([l for l in open("$out/bench.json") if l.startswith('{"metric"')][0])

@@ -13,8 +13,8 @@ if [ "$what" = suite ]; then
   rc=$?; echo "pytest rc=$rc"; tail -4 $out/pytest.log
   exit $rc
 fi
-timeout -k 10 500 python3 bench.py > $out/bench.json 2> $out/bench.err; echo "bench rc=$?"
-( cd /tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$R/$out/ks_fp64" -o ks -- python3 "$R/bench.py" --separate-calls --no-cpu-baseline --no-emulated-line > "$R/$out/bench_separate_calls.json" 2> "$R/$out/ks_fp64.log" ); echo "stats (separate calls) rc=$?"
+timeout -k 10 500 python3 bench.py --full > $out/bench.json 2> $out/bench.err; echo "bench rc=$?"
+( cd /tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$R/$out/ks_fp64" -o ks -- python3 "$R/bench.py" --full --separate-calls --no-cpu-baseline --no-emulated-line > "$R/$out/bench_separate_calls.json" 2> "$R/$out/ks_fp64.log" ); echo "stats (separate calls) rc=$?"
 f=$(find $out/ks_fp64 -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp "$f" $out/kernel_stats_fp64.csv
 find $out/ks_fp64 -name "*kernel_trace.csv" -delete
 # one-location calls: wall-clock table, BO iteration, kernel durations, counter traffic of the two streaming kernels
@@ -32,7 +32,7 @@ python3 tools/pmc_traffic.py $out/rows_FETCH_SIZE $out/rows_WRITE_SIZE $out/rows
 python3 tools/pmc_traffic.py $out/rows_FETCH_SIZE $out/rows_WRITE_SIZE $out/rows_backward_traffic.json --kernel rows_backward_kernel --mode stream > /dev/null; echo "backward traffic rc=$?"
 find $out -name "*counter_collection.csv" -delete
 timeout -k 10 300 python3 tools/gpbench.py configs_timing > $out/configs.txt 2>&1; cat $out/configs.txt
-GPHIP_BENCH_SAME_DEVICE=1 timeout -k 10 300 python3 bench.py --gpus 2 --c4-M 200000 --steps 3 2> $out/bench2.err | grep '^{"metric"' > $out/bench2.json; echo "bench --gpus 2 (same device) rc=$?"
+GPHIP_BENCH_SAME_DEVICE=1 timeout -k 10 300 python3 bench.py --full --gpus 2 --c4-M 200000 --steps 3 2> $out/bench2.err | grep '^{"metric"' > $out/bench2.json; echo "bench --gpus 2 (same device) rc=$?"
 python3 - <<PY
 import json
 d = json.loads([l for l in open("$out/bench.json") if l.startswith('{"metric"')][0])
