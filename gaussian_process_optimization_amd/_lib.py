@@ -51,6 +51,8 @@ SIGNATURES = [
     ("gp_lml_grad", ctypes.c_int, [_vp, c_double_p, c_double_p, c_double_p]),
     ("gp_fit_grad", ctypes.c_int, [_vp, ctypes.c_int, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p,
                                    c_double_p]),
+    ("gp_fit_grad_batch", ctypes.c_int, [_vp, ctypes.c_int, c_double_p, c_double_p, c_double_p, ctypes.c_int, c_double_p,
+                                         c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, c_int_p]),
     ("gp_set_candidates", ctypes.c_int, [_vp, c_double_p, ctypes.c_int64]),
     ("gp_predict", ctypes.c_int, [_vp, ctypes.c_int, c_double_p, c_double_p]),
     ("gp_predict_full_cov", ctypes.c_int, [_vp, ctypes.c_int, c_double_p, c_double_p]),
@@ -257,6 +259,31 @@ class Handle(object):
                                   ctypes.byref(dv), dptr(dl), ctypes.byref(dn))
         check(self.lib, rc, "gp_fit_grad")
         return (lml.value, logdet.value, jit.value), (dv.value, dl, dn.value)
+
+    def fit_grad_batch(self, variances, lengthscales, noises, maxtries=5):
+        """gp_fit_grad for R parameter vectors in one call (the resident fit is untouched).  ``lengthscales`` is [R, nls] with nls
+        the last set_params' lengthscale count.  Returns ((lml, logdet, jitter) [R] each, (dvariance [R], dlengthscale [R, nls],
+        dnoise [R]), status [R]); status[r] != 0 is what gp_fit_grad returns for member r, whose numbers are then NaN."""
+        var = as_f64(np.atleast_1d(variances), 1)
+        noi = as_f64(np.atleast_1d(noises), 1)
+        R = var.size
+        want = getattr(self, "n_ls", None)
+        if want is None:
+            raise ValueError("set_params has not been called on this handle")
+        ls = np.asarray(lengthscales, dtype=float)
+        if ls.ndim != 2 or ls.shape != (R, want):
+            raise ValueError("lengthscales has shape %s, expected (%d, %d): one row per member, one entry per lengthscale of "
+                             "the model" % (ls.shape, R, want))
+        if noi.size != R:
+            raise ValueError("variances and noises differ in length (%d, %d)" % (R, noi.size))
+        ls = np.ascontiguousarray(ls)
+        lml, logdet, jit = np.empty(R), np.empty(R), np.empty(R)
+        dv, dl, dn = np.empty(R), np.empty((R, want)), np.empty(R)
+        status = np.zeros(R, dtype=np.int32)
+        rc = self.lib.gp_fit_grad_batch(self.h, int(R), dptr(var), dptr(ls), dptr(noi), int(maxtries), dptr(lml), dptr(logdet),
+                                        dptr(jit), dptr(dv), dptr(dl), dptr(dn), status.ctypes.data_as(c_int_p))
+        check(self.lib, rc, "gp_fit_grad_batch")
+        return (lml, logdet, jit), (dv, dl, dn), status
 
     def fit_state(self):
         lml, logdet, jit = ctypes.c_double(), ctypes.c_double(), ctypes.c_double()

@@ -335,14 +335,14 @@ extern "C" int gp_destroy(gp_t *g) {
     if (g->comm) ncclCommDestroy(g->comm);
     double *ptrs[] = {g->dX, g->dY, g->dA, g->dInvL, g->dAlpha, g->dW, g->dMu, g->dScal, g->dRedV,
                       g->dXs, g->dT, g->dMean, g->dVar, g->dAcq, g->dWi, g->dT2, g->dDm, g->dDv, g->dDacq, g->dCov, g->dInvP, g->dInvPw, g->dLp, g->dComm,
-                      g->dX2, g->dK2, g->dLi, g->dRows};
+                      g->dX2, g->dK2, g->dLi, g->dRows, g->dBatch};
     for (double *p : ptrs)
         if (p) hipFree(p);
     if (g->dRowsCounter) hipFree(g->dRowsCounter);
     if (g->hRowsOut) hipHostFree(g->hRowsOut);
     if (g->dInfo) hipFree(g->dInfo);
     if (g->dRedI) hipFree(g->dRedI);
-    for (signed char *p : {g->dLr, g->dSr, g->dRr, g->dRm, g->dWr})
+    for (signed char *p : {g->dLr, g->dSr, g->dRr, g->dRm, g->dWr, g->dBatchAux})
         if (p) hipFree(p);
     for (auto &kv : g->tile_lists) hipFree(kv.second);
     // events recorded on the shared streams go first; the streams themselves belong to the per-device set shared by

@@ -328,7 +328,7 @@ int factor_lookahead(gp_ctx *g, const PredPipe &pp) {
     return la_events_ok(g);   // (an error return makes fit_impl quiesce every stream before it reports)
 }
 
-__global__ void dot_ay_kernel(const double *alpha, long lda_, const double *Y, long N, int P, double *out) {
+__device__ __forceinline__ void dot_ay_body(const double *alpha, long lda_, const double *Y, long N, int P, double *out) {
     __shared__ double sh[16];
     const int p = blockIdx.x;
     double s = 0.0;
@@ -342,6 +342,19 @@ __global__ void dot_ay_kernel(const double *alpha, long lda_, const double *Y, l
         for (int i = 0; i < 16; ++i) r += sh[i];
         out[p] = r;
     }
+}
+
+__global__ void dot_ay_kernel(const double *alpha, long lda_, const double *Y, long N, int P, double *out) {
+    dot_ay_body(alpha, lda_, Y, N, P, out);
+}
+// member z = blockIdx.z of gp_fit_grad_batch: alpha + z sV, results at out + z so
+__global__ void dot_ay_batch_kernel(const double *alpha, long sV, long lda_, const double *Y, long N, int P, double *out, long so) {
+    const long z = blockIdx.z;
+    dot_ay_body(alpha + z * sV, lda_, Y, N, P, out + z * so);
+}
+void launch_dot_ay_batch(hipStream_t s, const double *alpha, long sV, long lda_, const double *Y, long N, int P, double *out, long so,
+                         int nb) {
+    GP_LAUNCH(dot_ay_batch_kernel, dim3(P, 1, nb), dim3(1024), 0, s, alpha, sV, lda_, Y, N, P, out, so);
 }
 
 // Shared body of gp_fit and gp_fit_predict.  pipe != 0: the candidate solve of the resident candidates is

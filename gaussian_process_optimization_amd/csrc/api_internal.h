@@ -210,6 +210,11 @@ struct gp_ctx {
     int emulate_fit = 1;            // emulate_fp64 also covers the factorisation's trailing update
     bool emu_off_call = false;      // this call fell back to true fp64 (an operand left the fixed-point range)
     long emu_fallbacks = 0;         // how often that happened
+    // gp_fit_grad_batch (api_batch.hip): buffers of its own, sized to the R and Npad in use -- never the resident fit's
+    double *dBatch = nullptr;
+    long capBatch = 0;
+    signed char *dBatchAux = nullptr;   // per-member KernParams table, then factorisation status words
+    long capBatchAux = 0;
     bool dead = false;  // gp_shutdown ran: the device's streams are gone, only gp_destroy is still valid
 };
 
@@ -312,6 +317,8 @@ int wi_lauum(gp_ctx *g);
 int wi_rns(gp_ctx *g);
 int ensure_wi(gp_ctx *g);
 int ensure_linv(gp_ctx *g);
+void launch_dot_ay_batch(hipStream_t s, const double *alpha, long sV, long lda_, const double *Y, long N, int P, double *out, long so,
+                         int nb);   // api_factor.hip: alpha_p . y_p of nb members (gp_fit_grad_batch)
 int lml_grad_impl(gp_ctx *g, double *dvariance, double *dlengthscale, double *dnoise, bool reset_phases);
 int ensure_grad_buffers(gp_ctx *g, long elemsBeta, long M);
 int run_predict_grad(gp_ctx *g);

@@ -259,6 +259,24 @@ void launch_dldk(hipStream_t s, double *out, long ldo, const double *alpha, long
 // zero the strict upper triangle of the nt diagonal 128-tiles (the factor's tiles keep the symmetric input there)
 void launch_zero_upper_diag(hipStream_t s, double *A, long lda, int nt);
 
+// ---- batched twins of the launches above (gp_fit_grad_batch, api_batch.hip) --------------------------------------------------
+// nb members side by side, member z at base + z * stride (blockIdx.z, or blockIdx.x for the one-workgroup kernels); each runs
+// the same body as its single-member kernel, so a member gets the per-tile arithmetic of the single call.  Per-member parameters
+// come from a device table (kpt[z]); kp0 (host) is member 0's, for what selects the instance and the LDS size.
+void launch_kbuild_batch(hipStream_t s, double *A, long lda, long sA, const double *X, long N, long Npad, const KernParams &kp0,
+                         const KernParams *kpt, const double *diag_add, int nb);
+void launch_add_diag_batch(hipStream_t s, double *A, long sA, long lda, long N, const double *v, int nb);
+void launch_set_rhs_batch(hipStream_t s, double *A, long lda, long sA, const double *Y, long N, long Npad, int P, int nb);
+void launch_potrf_tile_batch(hipStream_t s, double *A, long lda, long sA, int t, double *invL, long sI, int *info, int sInfo,
+                             int nb);
+void launch_logdet_batch(hipStream_t s, const double *A, long lda, long sA, long N, double *out, long so, int nb);
+void launch_trsv_backward_batch(hipStream_t s, const double *L, long lda, long sL, const double *invP, long sP, int W, long Npad,
+                                int P, double *Aout, double *w, long sV, int nb);
+void launch_symmetrize_scale_batch(hipStream_t s, double *A, long sA, long ld, long n, double scale, int nb);
+void launch_lml_grad_batch(hipStream_t s, const double *X, long N, long Npad, const KernParams &kp0, const KernParams *kpt, int ard,
+                           int d0, const double *alpha, long sV, int P, const double *Wi, long sW, long ldw, double *partial,
+                           long sP, double *out, long so, int nb);
+
 // ---- rns.hip: fp64-equivalent contraction on the int8 matrix cores (option "emulate_fp64") -----------------------------
 #define GP_RNS_T 14
 #define GP_RNS_KMAX 8192   // longest contraction (bytes) one residue launch may take: see rns_reduce_f in rns.hip

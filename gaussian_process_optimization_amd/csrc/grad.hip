@@ -58,7 +58,7 @@ __global__ void symmetrize_kernel(double *A, long ld, long n) {
         if (gi < n && gj < n && gj > gi) A[gi * ld + gj] = t[tx][r];
     }
 }
-__global__ void symmetrize_scale_kernel(double *A, long ld, long n, double scale) {
+__device__ __forceinline__ void symmetrize_scale_body(double *A, long ld, long n, double scale) {
     __shared__ double t[32][33];
     const int bx = blockIdx.x, by = blockIdx.y;  // by >= bx: source tile (by, bx) in the lower part
     if (bx > by) return;
@@ -77,6 +77,16 @@ __global__ void symmetrize_scale_kernel(double *A, long ld, long n, double scale
         if (gi < n && gj < n && gj > gi) A[gi * ld + gj] = scale * t[tx][r];
     }
 }
+__global__ void symmetrize_scale_kernel(double *A, long ld, long n, double scale) {
+    symmetrize_scale_body(A, ld, n, scale);
+}
+__global__ void symmetrize_scale_batch_kernel(double *A, long sA, long ld, long n, double scale) {
+    symmetrize_scale_body(A + (long)blockIdx.z * sA, ld, n, scale);
+}
+void launch_symmetrize_scale_batch(hipStream_t s, double *A, long sA, long ld, long n, double scale, int nb) {
+    const unsigned nbk = (unsigned)((n + 31) / 32);
+    GP_LAUNCH(symmetrize_scale_batch_kernel, dim3(nbk, nbk, (unsigned)nb), dim3(256), 0, s, A, sA, ld, n, scale);
+}
 void launch_symmetrize_scale(hipStream_t s, double *A, long ld, long n, double scale) {
     const unsigned nb = (unsigned)((n + 31) / 32);
     GP_LAUNCH(symmetrize_scale_kernel, dim3(nb, nb), dim3(256), 0, s, A, ld, n, scale);
@@ -89,9 +99,8 @@ void launch_symmetrize(hipStream_t s, double *A, long ld, long n) {
 // ---- LML hyper-gradients: one pass over the lower tiles ------------------------------------------
 #define NACC (GCH + 2)
 // partial[tile][NACC]: [0] sum K dL_dK (w), [1] sum diag dL_dK, [2+q] sum w g dL_dK dq^2 (ARD) or [2] sum w g dL_dK r^2 (iso)
-__global__ __launch_bounds__(256) void lml_grad_tile_kernel(const double *X, long N, KernParams kp, int ard, int d0,
-                                                            const double *alpha, long lda_, int P, const double *Wi,
-                                                            long ldw, double *partial) {
+__device__ __forceinline__ void lml_grad_tile_body(const double *X, long N, const KernParams &kp, int ard, int d0, const double *alpha,
+                                                   long lda_, int P, const double *Wi, long ldw, double *partial) {
     extern __shared__ __attribute__((aligned(16))) double sm[];
     const int D = kp.D;
     double *xi = sm;                        // [D][128]
@@ -200,7 +209,20 @@ __global__ __launch_bounds__(256) void lml_grad_tile_kernel(const double *X, lon
     if (tid < NACC) partial[(t * gridDim.y + blockIdx.y) * NACC + tid] = ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid];
 }
 
-__global__ __launch_bounds__(1024) void sum_partials_kernel(const double *partial, long ntile, int nacc, double *out) {
+__global__ __launch_bounds__(256) void lml_grad_tile_kernel(const double *X, long N, KernParams kp, int ard, int d0,
+                                                            const double *alpha, long lda_, int P, const double *Wi,
+                                                            long ldw, double *partial) {
+    lml_grad_tile_body(X, N, kp, ard, d0, alpha, lda_, P, Wi, ldw, partial);
+}
+// member z = blockIdx.z of gp_fit_grad_batch: parameters kpt[z], alpha + z sV, Ky^-1 at Wi + z sW, partials at partial + z sP
+__global__ __launch_bounds__(256) void lml_grad_tile_batch_kernel(const double *X, long N, const KernParams *kpt, int ard, int d0,
+                                                                  const double *alpha, long sV, long lda_, int P, const double *Wi,
+                                                                  long sW, long ldw, double *partial, long sP) {
+    const long z = blockIdx.z;
+    lml_grad_tile_body(X, N, kpt[z], ard, d0, alpha + z * sV, lda_, P, Wi + z * sW, ldw, partial + z * sP);
+}
+
+__device__ __forceinline__ void sum_partials_body(const double *partial, long ntile, int nacc, double *out) {
     __shared__ double sh[16];
     const int q = blockIdx.x;
     double s = 0.0;
@@ -213,6 +235,28 @@ __global__ __launch_bounds__(1024) void sum_partials_kernel(const double *partia
         for (int i = 0; i < 16; ++i) r += sh[i];
         out[q] = r;
     }
+}
+
+__global__ __launch_bounds__(1024) void sum_partials_kernel(const double *partial, long ntile, int nacc, double *out) {
+    sum_partials_body(partial, ntile, nacc, out);
+}
+__global__ __launch_bounds__(1024) void sum_partials_batch_kernel(const double *partial, long sP, long ntile, int nacc, double *out,
+                                                                  long so) {
+    const long z = blockIdx.z;
+    sum_partials_body(partial + z * sP, ntile, nacc, out + z * so);
+}
+
+// the same pass for nb members (gp_fit_grad_batch); kp0: member 0's parameters on the host (D, Gower: the LDS size)
+void launch_lml_grad_batch(hipStream_t s, const double *X, long N, long Npad, const KernParams &kp0, const KernParams *kpt, int ard,
+                           int d0, const double *alpha, long sV, int P, const double *Wi, long sW, long ldw, double *partial,
+                           long sP, double *out, long so, int nb) {
+    const int nt = (int)(Npad / GP_TILE);
+    const long ntile = (long)nt * (nt + 1) / 2;
+    const size_t shm = ((size_t)(kp0.gower ? 4 : 2) * kp0.D * GP_TILE + (size_t)2 * P * GP_TILE) * sizeof(double);
+    const unsigned split = ntile < 256 ? 4u : 1u;   // (as launch_lml_grad: the per-member partials land in the same order)
+    GP_LAUNCH(lml_grad_tile_batch_kernel, dim3((unsigned)ntile, split, (unsigned)nb), dim3(256), shm, s, X, N, kpt, ard, d0, alpha,
+              sV, Npad, P, Wi, sW, ldw, partial, sP);
+    GP_LAUNCH(sum_partials_batch_kernel, dim3(NACC, 1, (unsigned)nb), dim3(1024), 0, s, partial, sP, ntile * split, NACC, out, so);
 }
 
 // out (device, NACC doubles): sums for dims [d0, d0+GCH)
@@ -326,6 +370,15 @@ __global__ void add_diag2_kernel(double *A, long lda, long n, double v) {
 }
 void launch_add_diag(hipStream_t s, double *A, long lda, long N, double v) {
     GP_LAUNCH(add_diag2_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, A, lda, N, v);
+}
+// member z's diagonal += v[z] (gp_fit_grad_batch: each member's own jitter)
+__global__ void add_diag_batch_kernel(double *A, long sA, long lda, long n, const double *v) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    const long z = blockIdx.z;
+    if (i < n) A[z * sA + i * lda + i] += v[z];
+}
+void launch_add_diag_batch(hipStream_t s, double *A, long sA, long lda, long N, const double *v, int nb) {
+    GP_LAUNCH(add_diag_batch_kernel, dim3((unsigned)((N + 255) / 256), 1, (unsigned)nb), dim3(256), 0, s, A, sA, lda, N, v);
 }
 // out[0] = sum_i A[i][i], out[1] = min_i A[i][i]  (jitchol looks at both: linalg.py:61-66)
 __global__ __launch_bounds__(1024) void trace_kernel(const double *A, long lda, long N, double *out) {

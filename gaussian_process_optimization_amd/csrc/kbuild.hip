@@ -37,8 +37,8 @@ __device__ __forceinline__ void stage_rows_T(double *dst, const double *X, long 
 // across its 32 rows; DU = 0: run-time loop (D > 16, and the Gower product kernel).
 // grid: lower tiles enumerated row-wise (tm >= tn): t = tm(tm+1)/2 + tn
 template <int DU>
-__global__ __launch_bounds__(256) void kbuild_kernel(double *A, long lda, const double *X, long N, long Npad,
-                                                     KernParams kp, double diag_add, int full, int nt) {
+__device__ __forceinline__ void kbuild_body(double *A, long lda, const double *X, long N, long Npad, const KernParams &kp,
+                                            double diag_add, int full, int nt) {
     extern __shared__ __attribute__((aligned(16))) double sm[];
     const int DS = DU > 0 ? DU : kp.D;        // staged dimensions
     double *xi = sm;                          // [DS][128]
@@ -124,6 +124,19 @@ __global__ __launch_bounds__(256) void kbuild_kernel(double *A, long lda, const 
     }
 }
 
+template <int DU>
+__global__ __launch_bounds__(256) void kbuild_kernel(double *A, long lda, const double *X, long N, long Npad,
+                                                     KernParams kp, double diag_add, int full, int nt) {
+    kbuild_body<DU>(A, lda, X, N, Npad, kp, diag_add, full, nt);
+}
+// member z = blockIdx.z of a batch (gp_fit_grad_batch): its own matrix at A + z sA, parameters kpt[z], diagonal term diag_add[z]
+template <int DU>
+__global__ __launch_bounds__(256) void kbuild_batch_kernel(double *A, long lda, long sA, const double *X, long N, long Npad,
+                                                           const KernParams *kpt, const double *diag_add, int nt) {
+    const long z = blockIdx.z;
+    kbuild_body<DU>(A + z * sA, lda, X, N, Npad, kpt[z], diag_add[z], 0, nt);
+}
+
 void launch_kbuild(hipStream_t s, double *A, long lda, const double *X, long N, long Npad,
                    const KernParams &kp, double diag_add, int full) {
     const int nt = (int)(Npad / GP_TILE);
@@ -138,11 +151,21 @@ void launch_kbuild(hipStream_t s, double *A, long lda, const double *X, long N, 
         GP_LAUNCH(kbuild_kernel<0>, dim3((unsigned)nblk), dim3(256), shm, s, A, lda, X, N, Npad, kp, diag_add, full, nt);
 }
 
-__global__ void set_rhs_kernel(double *A, long lda, const double *Y, long N, long Npad, int P) {
+__device__ __forceinline__ void set_rhs_body(double *A, long lda, const double *Y, long N, long Npad, int P) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     const int p = blockIdx.y;
     if (i >= Npad) return;
     A[(Npad + p) * lda + i] = (p < P && i < N) ? Y[i * P + p] : 0.0;
+}
+__global__ void set_rhs_kernel(double *A, long lda, const double *Y, long N, long Npad, int P) {
+    set_rhs_body(A, lda, Y, N, Npad, P);
+}
+__global__ void set_rhs_batch_kernel(double *A, long lda, long sA, const double *Y, long N, long Npad, int P) {
+    set_rhs_body(A + (long)blockIdx.z * sA, lda, Y, N, Npad, P);
+}
+void launch_set_rhs_batch(hipStream_t s, double *A, long lda, long sA, const double *Y, long N, long Npad, int P, int nb) {
+    dim3 grid((unsigned)((Npad + 255) / 256), GP_MAX_RHS, (unsigned)nb);
+    GP_LAUNCH(set_rhs_batch_kernel, grid, dim3(256), 0, s, A, lda, sA, Y, N, Npad, P);
 }
 
 void launch_set_rhs(hipStream_t s, double *A, long lda, const double *Y, long N, long Npad, int P) {
@@ -271,4 +294,21 @@ void launch_cross_k_rows(hipStream_t s, double *T, long ldt, const double *Xs, i
     if (M < 1 || M > CKR_MAX_M) return;
     GP_LAUNCH(cross_k_rows_kernel, dim3((unsigned)((Npad + 255) / 256)), dim3(256), (size_t)M * kp.D * sizeof(double), s, T, ldt, Xs, M,
               X, N, Npad, kp);
+}
+
+// the lower tiles of nb members' matrices in one launch (gp_fit_grad_batch); kp0 is member 0's parameters on the host (kernel, D
+// and the Gower setting -- what picks the instance and the LDS size -- are the same for every member)
+void launch_kbuild_batch(hipStream_t s, double *A, long lda, long sA, const double *X, long N, long Npad, const KernParams &kp0,
+                         const KernParams *kpt, const double *diag_add, int nb) {
+    const int nt = (int)(Npad / GP_TILE);
+    const long nblk = (long)nt * (nt + 1) / 2;
+    const int DU = kp0.gower ? 0 : (kp0.D <= 8 ? 8 : (kp0.D <= 16 ? 16 : 0));
+    const size_t shm = (size_t)2 * (DU ? DU : kp0.D) * GP_TILE * sizeof(double);
+    const dim3 grid((unsigned)nblk, 1, (unsigned)nb);
+    if (DU == 8)
+        GP_LAUNCH(kbuild_batch_kernel<8>, grid, dim3(256), shm, s, A, lda, sA, X, N, Npad, kpt, diag_add, nt);
+    else if (DU == 16)
+        GP_LAUNCH(kbuild_batch_kernel<16>, grid, dim3(256), shm, s, A, lda, sA, X, N, Npad, kpt, diag_add, nt);
+    else
+        GP_LAUNCH(kbuild_batch_kernel<0>, grid, dim3(256), shm, s, A, lda, sA, X, N, Npad, kpt, diag_add, nt);
 }

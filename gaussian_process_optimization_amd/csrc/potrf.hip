@@ -649,6 +649,17 @@ __global__ __launch_bounds__(512) void potrf_tile_kernel(double *A, long lda, in
     potrf_tile_body<false>(A, lda, t, invL, info, T, Dinv, zrow);
 }
 
+// diagonal tile t of nb members' matrices (member z at A + z sA, invL + z sI, info + z sInfo): the body above, one workgroup each
+__global__ __launch_bounds__(512) void potrf_tile_batch_kernel(double *A, long lda, long sA, int t, double *invL, long sI, int *info,
+                                                               int sInfo) {
+    __shared__ __attribute__((aligned(16))) double T[GP_TILE * TS];
+    __shared__ __attribute__((aligned(16))) double Dinv[8 * DBLK];
+    __shared__ __attribute__((aligned(16))) double zrow[16];
+    if (threadIdx.x < 16) zrow[threadIdx.x] = 0.0;
+    const long z = blockIdx.x;
+    potrf_tile_body<false>(A + z * sA, lda, t, invL + z * sI, info + z * sInfo, T, Dinv, zrow);
+}
+
 // Test hook (option "debug_potrf_lds"): extra dynamic LDS requested with every diagonal-tile launch.  Beyond what the CU has
 // left beside the kernel's 151 KB of static LDS the launch is REFUSED -- which is what the launch checks are there to catch.
 static int g_debug_lds = 0;
@@ -660,4 +671,9 @@ void launch_potrf_pair(hipStream_t s, double *A, long lda, int t, double *invL, 
 
 void launch_potrf_tile(hipStream_t s, double *A, long lda, int t, double *invL, int *info) {
     GP_LAUNCH(potrf_tile_kernel, dim3(1), dim3(512), (size_t)g_debug_lds, s, A, lda, t, invL, info);
+}
+
+void launch_potrf_tile_batch(hipStream_t s, double *A, long lda, long sA, int t, double *invL, long sI, int *info, int sInfo,
+                             int nb) {
+    GP_LAUNCH(potrf_tile_batch_kernel, dim3((unsigned)nb), dim3(512), 0, s, A, lda, sA, t, invL, sI, info, sInfo);
 }

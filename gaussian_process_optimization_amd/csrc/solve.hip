@@ -30,12 +30,22 @@ __device__ __forceinline__ double block_sum(double v, double *sh) {
 }
 
 // ---- logdet = 2 sum log L_ii  (GPy/GPy/util/linalg.py:208) --------------------------------
-__global__ __launch_bounds__(1024) void logdet_kernel(const double *A, long lda, long N, double *out) {
+__device__ __forceinline__ void logdet_body(const double *A, long lda, long N, double *out) {
     __shared__ double sh[16];
     double s = 0.0;
     for (long i = threadIdx.x; i < N; i += 1024) s += log(A[i * lda + i]);
     s = block_sum<1024>(s, sh);
     if (threadIdx.x == 0) out[0] = 2.0 * s;
+}
+__global__ __launch_bounds__(1024) void logdet_kernel(const double *A, long lda, long N, double *out) {
+    logdet_body(A, lda, N, out);
+}
+// one workgroup per member (gp_fit_grad_batch): member z's factor at A + z sA, its result at out + z so
+__global__ __launch_bounds__(1024) void logdet_batch_kernel(const double *A, long lda, long sA, long N, double *out, long so) {
+    logdet_body(A + (long)blockIdx.x * sA, lda, N, out + (long)blockIdx.x * so);
+}
+void launch_logdet_batch(hipStream_t s, const double *A, long lda, long sA, long N, double *out, long so, int nb) {
+    GP_LAUNCH(logdet_batch_kernel, dim3((unsigned)nb), dim3(1024), 0, s, A, lda, sA, N, out, so);
 }
 void launch_logdet(hipStream_t s, const double *A, long lda, long N, double *out) {
     GP_LAUNCH(logdet_kernel, dim3(1), dim3(1024), 0, s, A, lda, N, out);
@@ -61,9 +71,8 @@ void launch_rhs_sumsq(hipStream_t s, const double *A, long lda, long N, long Npa
 //   w_j    += L[J rows, j cols]^T alpha_J, j < J   (panel_update: one workgroup per 128 columns)
 // 2 launches per panel (32 at N = 16384) instead of one per 128-row block; L is streamed once.
 #define PT 1024  // threads of the panel kernels: 128 columns x 8 row groups, 8 independent loads in flight each
-__global__ __launch_bounds__(PT) void panel_solve_kernel(const double *invP, long ldp, int Kp, const double *Z,
-                                                         long ldz, const double *w, long ldw, int P, long off,
-                                                         double *Aout) {
+__device__ __forceinline__ void panel_solve_body(const double *invP, long ldp, int Kp, const double *Z, long ldz, const double *w,
+                                                 long ldw, int P, long off, double *Aout) {
     __shared__ double part[PT];
     extern __shared__ double v[];  // Kp
     const int tid = threadIdx.x;
@@ -97,8 +106,13 @@ __global__ __launch_bounds__(PT) void panel_solve_kernel(const double *invP, lon
         __syncthreads();
     }
 }
-__global__ __launch_bounds__(PT) void panel_update_kernel(const double *L, long lda, int Kp, long rowoff,
-                                                          const double *alpha, long ldz, int P, double *w, long ldw) {
+__global__ __launch_bounds__(PT) void panel_solve_kernel(const double *invP, long ldp, int Kp, const double *Z,
+                                                         long ldz, const double *w, long ldw, int P, long off,
+                                                         double *Aout) {
+    panel_solve_body(invP, ldp, Kp, Z, ldz, w, ldw, P, off, Aout);
+}
+__device__ __forceinline__ void panel_update_body(const double *L, long lda, int Kp, long rowoff, const double *alpha, long ldz,
+                                                  int P, double *w, long ldw) {
     __shared__ double part[PT];
     extern __shared__ double al[];  // Kp
     const int tid = threadIdx.x;
@@ -131,6 +145,22 @@ __global__ __launch_bounds__(PT) void panel_update_kernel(const double *L, long 
         __syncthreads();
     }
 }
+__global__ __launch_bounds__(PT) void panel_update_kernel(const double *L, long lda, int Kp, long rowoff,
+                                                          const double *alpha, long ldz, int P, double *w, long ldw) {
+    panel_update_body(L, lda, Kp, rowoff, alpha, ldz, P, w, ldw);
+}
+// member z = blockIdx.z of gp_fit_grad_batch: strides sP (inverted panels), sL (factor and, below it, the RHS rows), sV (alpha, w)
+__global__ __launch_bounds__(PT) void panel_solve_batch_kernel(const double *invP, long sP, long ldp, int Kp, const double *Z, long sL,
+                                                               long ldz, const double *w, long sV, long ldw, int P, long off,
+                                                               double *Aout) {
+    const long z = blockIdx.z;
+    panel_solve_body(invP + z * sP, ldp, Kp, Z + z * sL, ldz, w + z * sV, ldw, P, off, Aout + z * sV);
+}
+__global__ __launch_bounds__(PT) void panel_update_batch_kernel(const double *L, long sL, long lda, int Kp, long rowoff,
+                                                                const double *alpha, long sV, long ldz, int P, double *w, long ldw) {
+    const long z = blockIdx.z;
+    panel_update_body(L + z * sL, lda, Kp, rowoff, alpha + z * sV, ldz, P, w + z * sV, ldw);
+}
 __global__ void zero_kernel(double *p, long n) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) p[i] = 0.0;
@@ -152,6 +182,28 @@ void launch_trsv_backward(hipStream_t s, const double *L, long lda, const double
         if (J0 > 0)
             GP_LAUNCH(panel_update_kernel, dim3(J0), dim3(PT), Kp * sizeof(double), s, L, lda, Kp, off, Aout,
                                ldz, P, w, Npad);
+    }
+}
+
+// the same back-substitution for nb members (gp_fit_grad_batch) in the same launches: member z's factor and RHS rows at
+// L + z sL, its inverted panels at invP + z sP, its alpha / workspace at Aout + z sV / w + z sV (w contiguous over members)
+void launch_trsv_backward_batch(hipStream_t s, const double *L, long lda, long sL, const double *invP, long sP, int W, long Npad,
+                                int P, double *Aout, double *w, long sV, int nb) {
+    const long nw = sV * nb;
+    GP_LAUNCH(zero_kernel, dim3((unsigned)((nw + 255) / 256)), dim3(256), 0, s, w, nw);
+    const int nt = (int)(Npad / GP_TILE);
+    const long PB = (long)W * GP_TILE;
+    const int nJ = (nt + W - 1) / W;
+    const double *Z = L + Npad * lda;
+    for (int J = nJ - 1; J >= 0; --J) {
+        const int J0 = J * W, J1 = std::min(J0 + W, nt);
+        const int Kp = (J1 - J0) * GP_TILE;
+        const long off = (long)J0 * GP_TILE;
+        GP_LAUNCH(panel_solve_batch_kernel, dim3(J1 - J0, 1, nb), dim3(PT), Kp * sizeof(double), s, invP + (long)J * PB * PB, sP,
+                  PB, Kp, Z, sL, lda, w, sV, Npad, P, off, Aout);
+        if (J0 > 0)
+            GP_LAUNCH(panel_update_batch_kernel, dim3(J0, 1, nb), dim3(PT), Kp * sizeof(double), s, L, sL, lda, Kp, off, Aout, sV,
+                      lda, P, w, Npad);
     }
 }
 

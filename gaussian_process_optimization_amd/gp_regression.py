@@ -15,7 +15,9 @@ from scipy import optimize as _sopt
 
 from . import _lib
 from .kern import RBF, Stationary, gower_config
-from .parameterization import Param, Parameterized
+from .parameterization import Param, Parameterized, lbfgsb_lockstep
+
+_BATCH_MAX_R, _BATCH_MAX_NPAD = 64, 2048   # gp_fit_grad_batch's limits (include/gphip.h)
 
 
 class Gaussian(Parameterized):
@@ -494,9 +496,54 @@ class GPRegression(Parameterized):
         x = np.random.normal(size=self.optimizer_array.size)
         self.optimizer_array = x
 
+    def _search_options(self, kwargs):
+        optimizer = kwargs.get("optimizer")
+        if optimizer not in (None, "lbfgs", "lbfgsb", "bfgs", "scg"):
+            raise ValueError("unknown optimizer %r" % optimizer)
+        return int(kwargs.get("max_iters", 1000)), kwargs.get("bfgs_factor"), kwargs.get("gtol")
+
+    def _batch_objective(self, xs):
+        """The transformed-space objective of ``_obj_grad`` for every row of ``xs`` from ONE gp_fit_grad_batch: the natural
+        gradients through the transforms' chain rule (fixed / bounded noise included), a member that is not positive definite
+        even with jitter a wall (1e10, zero gradient) as in ``_obj_grad``."""
+        k, nls = xs.shape[0], self.kern.lengthscale.size
+        var, ls, noise = np.empty(k), np.empty((k, nls)), np.empty(k)
+        for j in range(k):
+            self.optimizer_array = xs[j]
+            var[j], ls[j], noise[j] = float(self.kern.variance), self.kern.lengthscale.values, float(self.likelihood.variance)
+        (lml, _, _), (dv, dl, dn), status = self._h.fit_grad_batch(var, ls, noise, self.max_jitter_tries)
+        f, g = np.empty(k), np.zeros_like(xs)
+        for j in range(k):
+            if status[j] != 0:
+                f[j] = 1e10
+                continue
+            self.optimizer_array = xs[j]     # (the chain-rule factors are taken at this member's parameters)
+            dvj, dlj = dv[j], dl[j]
+            if self._uses_gower() and self.gower_gradients != 'fork':
+                dvj, dlj = dvj * self.kern.input_dim, np.zeros_like(dlj)
+            f[j] = -float(lml[j])
+            g[j] = -self._transform_gradients([(self.kern.variance, dvj), (self.kern.lengthscale, dlj),
+                                               (self.likelihood.variance, dn[j])])
+        return f, g
+
+    def _lockstep_applies(self, num_restarts):
+        npad = -(-self.num_data // 128) * 128
+        return (1 <= num_restarts <= _BATCH_MAX_R and npad <= _BATCH_MAX_NPAD and self.optimizer_array.size > 0
+                and not (self._uses_gower() and self.gower_gradients == 'differences'))
+
     def optimize_restarts(self, num_restarts=10, robust=False, verbose=True, parallel=False, num_processes=None,
                           **kwargs):
-        """paramz Model.optimize_restarts: keep the best of ``num_restarts`` L-BFGS runs."""
+        """paramz Model.optimize_restarts: keep the best of ``num_restarts`` L-BFGS runs.
+
+        ``parallel=True`` runs the restarts in lockstep (``lbfgsb_lockstep``): each round of L-BFGS steps of all running
+        restarts costs ONE device call, gp_fit_grad_batch, instead of one gp_fit_grad per restart in turn.  The starting
+        points are drawn as the serial loop draws them (restart 0 from the current parameters, then ``randomize()`` in
+        order: the same ``np.random`` consumption), each restart follows its serial path, and ``runs``, ``robust`` and
+        ``verbose`` behave as in the serial loop.  Falls back to the serial loop where the batch call does not apply: more
+        than 64 restarts, more than 2048 padded training rows, or a Gower model with ``gower_gradients == 'differences'``.
+        ``num_processes`` is accepted and ignored (paramz' multiprocessing is not used)."""
+        if parallel and self._lockstep_applies(num_restarts):
+            return self._optimize_restarts_lockstep(num_restarts, robust, verbose, **kwargs)
         initial = self.optimizer_array.copy()
         runs = []
         for i in range(num_restarts):
@@ -513,6 +560,36 @@ class GPRegression(Parameterized):
                         print("Warning - optimization restart %d/%d failed: %s" % (i + 1, num_restarts, e))
                 else:
                     raise
+        if runs:
+            best = min(runs, key=lambda t: t[0])
+            self.optimizer_array = best[1]
+        else:
+            self.optimizer_array = initial
+        self._ensure_fit()
+        return runs
+
+    def _optimize_restarts_lockstep(self, num_restarts, robust, verbose, **kwargs):
+        max_iters, factr, pgtol = self._search_options(kwargs)
+        initial = self.optimizer_array.copy()
+        starts = [initial]
+        for _ in range(1, num_restarts):
+            self.randomize()
+            starts.append(self.optimizer_array.copy())
+        self.optimizer_array = initial
+        self._push_params()      # kernel, ARD and Gower set-up of the context the batch reads
+        results = lbfgsb_lockstep(self._batch_objective, starts, max_iters=max_iters, factr=factr, pgtol=pgtol)
+        runs = []
+        for i, res in enumerate(results):
+            if isinstance(res, BaseException):
+                if not robust:
+                    raise res
+                if verbose:
+                    print("Warning - optimization restart %d/%d failed: %s" % (i + 1, num_restarts, res))
+                continue
+            self.optimizer_array = res[0]
+            runs.append((self.objective_function(), self.optimizer_array.copy()))
+            if verbose:
+                print("Optimization restart %d/%d, f = %s" % (i + 1, num_restarts, runs[-1][0]))
         if runs:
             best = min(runs, key=lambda t: t[0])
             self.optimizer_array = best[1]

@@ -36,18 +36,19 @@ class BOModel(object):
 
 class GPModel(BOModel):
     """Exact GP surrogate on the device.  Keyword arguments, attributes and return conventions are GPyOpt's
-    (gpmodel.py:9-177); ``device`` (HIP ordinal) is the one addition."""
+    (gpmodel.py:9-177); ``device`` (HIP ordinal) and ``parallel_restarts`` (the restarts in lockstep,
+    GPRegression.optimize_restarts(parallel=True); default False) are the additions."""
     analytical_gradient_prediction = True
 
     def __init__(self, kernel=None, noise_var=None, exact_feval=False, optimizer='bfgs', max_iters=1000,
                  optimize_restarts=5, sparse=False, num_inducing=10, verbose=True, ARD=False, Gower=False,
-                 space=None, device=0):
+                 space=None, device=0, parallel_restarts=False):
         if sparse:
             raise NotImplementedError("sparse GP is a different model family (out of scope)")
         vars(self).update(kernel=kernel, noise_var=noise_var, exact_feval=exact_feval, optimizer=optimizer,
                           max_iters=max_iters, optimize_restarts=optimize_restarts, sparse=sparse,
                           num_inducing=num_inducing, verbose=verbose, ARD=ARD, Gower=Gower, space=space, device=device,
-                          model=None)
+                          parallel_restarts=parallel_restarts, model=None)
 
     @staticmethod
     def fromConfig(config):
@@ -84,6 +85,8 @@ class GPModel(BOModel):
         if self.optimize_restarts == 1:
             self.model.optimize(messages=False, ipython_notebook=False, **search)
         else:
+            if self.parallel_restarts:   # the restarts in lockstep, one gp_fit_grad_batch per round (GPRegression.optimize_restarts)
+                search["parallel"] = True
             self.model.optimize_restarts(num_restarts=self.optimize_restarts, verbose=self.verbose, **search)
 
     def _predict(self, X, full_cov, include_likelihood):
@@ -129,7 +132,8 @@ class GPModel(BOModel):
     def copy(self):
         twin = GPModel(kernel=self.model.kern.copy(), noise_var=self.noise_var, exact_feval=self.exact_feval,
                        optimizer=self.optimizer, max_iters=self.max_iters, optimize_restarts=self.optimize_restarts,
-                       verbose=self.verbose, ARD=self.ARD, Gower=self.Gower, space=self.space, device=self.device)
+                       verbose=self.verbose, ARD=self.ARD, Gower=self.Gower, space=self.space, device=self.device,
+                       parallel_restarts=self.parallel_restarts)
         twin._create_model(self.model.X, self.model.Y)
         twin.updateModel(self.model.X, self.model.Y, None, None)
         return twin

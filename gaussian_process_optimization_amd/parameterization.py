@@ -10,7 +10,10 @@ transforms with their chain-rule factors, and change notification.  Optimiser
 trajectories are therefore "parity unpinned" (SURVEY.md 8c); LML, gradients and
 posteriors at fixed hyper-parameters do not depend on this module.
 """
+import threading
+
 import numpy as np
+from scipy import optimize as _sopt
 
 _LIM_VAL = 36.0
 _EPS = np.finfo(np.float64).resolution
@@ -238,3 +241,72 @@ class Parameterized(object):
     def constrain_positive(self, warning=True):
         for p in self.flattened_parameters():
             p.constrain_positive(warning)
+
+
+def lbfgsb_lockstep(fbatch, x0s, max_iters=1000, factr=None, pgtol=None):
+    """R ``scipy.optimize.fmin_l_bfgs_b`` runs in lockstep over ONE batch objective (optimize_restarts(parallel=True)).
+
+    ``fbatch(xs)`` takes the points of the still-running instances, ``xs[k, n]`` (rows in instance order), and returns
+    ``(f[k], g[k, n])`` -- or ``(f, g, errors)`` with ``errors[j]`` None or an exception that instance j's evaluation raises.
+    Each instance runs in a thread of its own with the serial ``optimize``'s options (maxiter = maxfun = max_iters, factr,
+    pgtol); its objective call posts x and waits.  When every running instance has posted, one ``fbatch`` call is made and
+    the values are handed back; a finished instance leaves the batch.  The L-BFGS-B state lives in each call's own arrays
+    (scipy passes it all to setulb), so every instance follows the path a serial run from its start takes.
+
+    Returns one entry per start, in order: the ``(x, f, d)`` of ``fmin_l_bfgs_b``, or the exception its run raised."""
+    x0s = [np.asarray(x, dtype=float) for x in x0s]
+    R = len(x0s)
+    extra = {}
+    if factr is not None:
+        extra["factr"] = float(factr)
+    if pgtol is not None:
+        extra["pgtol"] = float(pgtol)
+    cv = threading.Condition()
+    posted, replies, running = {}, {}, set(range(R))
+    out = [None] * R
+
+    def instance(r):
+        def objective(x):
+            with cv:
+                posted[r] = np.array(x, dtype=float)
+                cv.notify_all()
+                while r not in replies:
+                    cv.wait()
+                rep = replies.pop(r)
+            if isinstance(rep, BaseException):
+                raise rep
+            return rep
+
+        try:
+            out[r] = _sopt.fmin_l_bfgs_b(objective, x0s[r], maxiter=int(max_iters), maxfun=int(max_iters), **extra)
+        except BaseException as e:  # noqa: BLE001  (the instance's failure is its result; the others go on)
+            out[r] = e
+        finally:
+            with cv:
+                running.discard(r)
+                cv.notify_all()
+
+    threads = [threading.Thread(target=instance, args=(r,), daemon=True) for r in range(R)]
+    for t in threads:
+        t.start()
+    while True:
+        with cv:
+            while running and not running.issubset(posted):
+                cv.wait()
+            if not running:
+                break
+            idx = sorted(posted)
+            xs = np.stack([posted.pop(r) for r in idx])
+        try:
+            res = fbatch(xs)
+            f, g = np.asarray(res[0], dtype=float), np.asarray(res[1], dtype=float)
+            errors = res[2] if len(res) > 2 else [None] * len(idx)
+            reply = {r: (errors[j] if errors[j] is not None else (float(f[j]), g[j].copy())) for j, r in enumerate(idx)}
+        except BaseException as e:  # noqa: BLE001  (a failed batch call fails the instances that were waiting on it)
+            reply = {r: e for r in idx}
+        with cv:
+            replies.update(reply)
+            cv.notify_all()
+    for t in threads:
+        t.join()
+    return out

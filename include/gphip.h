@@ -132,6 +132,19 @@ int gp_get_dl_dk(gp_t *gp, double *dL_dK);
 int gp_fit_grad(gp_t *gp, int maxtries, double *lml, double *logdet, double *jitter_used, double *dvariance,
                 double *dlengthscale, double *dnoise);
 
+/* gp_fit_grad for R parameter vectors over the resident (X, Y) in ONE call: member r has variance[r], lengthscale[r*nls ...]
+ * (nls = 1, or D with ard, from the last gp_set_params) and noise[r]; kernel, ard and the Gower set-up are the context's.
+ * Replaces the serial restarts of GPModel.updateModel (GPyOpt/GPyOpt/models/gpmodel.py:78-93: optimize_restarts of
+ * GPy/GPy/core/model.py:96-127 evaluations) with restarts in lockstep, one call per round of L-BFGS steps.  Member r runs the
+ * single-stream route of gp_fit_grad (jitter ladder of linalg.py:62-75 per member: only failed members are factored again)
+ * with the member as a batch index of every launch.  status[r] = 0, or what gp_fit_grad returns for that member (its outputs
+ * are then NaN); a failed member does not fail the call.  Npad <= 2048 and 1 <= R <= 64, else GP_ERR_ARG; positive
+ * parameters.  Always true fp64 ("emulate_fp64" does not apply).  The resident fit (L, alpha, Ky^-1, parameters, fitted /
+ * predicted state) is untouched: the batch has buffers of its own, allocated at first use, about 5 Npad^2 doubles per member. */
+int gp_fit_grad_batch(gp_t *gp, int R, const double *variance, const double *lengthscale, const double *noise, int maxtries,
+                      double *lml, double *logdet, double *jitter_used, double *dvariance, double *dlengthscale, double *dnoise,
+                      int *status);
+
 /* ---- predict -----------------------------------------------------------
  * Candidates Xs[M,D] are made resident once; the calls below then run on them. */
 int gp_set_candidates(gp_t *gp, const double *Xs, int64_t M);

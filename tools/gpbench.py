@@ -1046,6 +1046,77 @@ def rows_fuzz():
     h.close()
 
 
+@command
+def batch_restarts():
+    """gp_fit_grad_batch against R x gp_fit_grad (N x R grid, medians of bursts, largest member difference), then
+    optimize_restarts(5) serial against parallel at N = 300, D = 8 ARD.  Argument "trace": one batched evaluation at N = 300, R = 5
+    (for a rocprofv3 --kernel-trace --stats run) and nothing else (test tooling)."""
+    import sys, time
+    import numpy as np
+    import gaussian_process_optimization_amd as gpo
+    from gaussian_process_optimization_amd import _lib
+    D = 8
+    def data(N, seed=1):
+        rng = np.random.default_rng(seed)
+        X = rng.uniform(0, 1, (N, D)); Y = (np.sin(6 * X).sum(1, keepdims=True) + 0.1 * rng.standard_normal((N, 1)))
+        return X, Y
+    def members(R, seed=2):
+        rng = np.random.default_rng(seed)
+        return (10.0 ** rng.uniform(-1, 1, R), np.sqrt(D) * 10.0 ** rng.uniform(-1, 0.3, (R, D)), 10.0 ** rng.uniform(-3, -1, R))
+    h = _lib.Handle(0)
+    if sys.argv[1:] == ["trace"]:
+        X, Y = data(300); h.set_data(X, Y); v, l, n = members(5); h.set_params(1, 1, v[0], l[0], n[0])
+        for _ in range(3): h.fit_grad_batch(v, l, n)
+        h.synchronize(); h.close(); return
+    def median_ms(fn, bursts=7, reps=5):
+        fn(); h.synchronize()
+        out = []
+        for _ in range(bursts):
+            t0 = time.perf_counter()
+            for _ in range(reps): fn()
+            h.synchronize(); out.append((time.perf_counter() - t0) / reps * 1e3)
+        return float(np.median(out)), float(np.min(out)), float(np.max(out))
+    print("%6s %4s %12s %12s %8s %10s %10s" % ("N", "R", "batch_ms", "R_single_ms", "speedup", "bitwise", "max_rel"), flush=True)
+    for N in [64, 128, 300, 512, 1024, 2048]:
+        X, Y = data(N); h.set_data(X, Y)
+        for R in [1, 5, 10, 20, 64]:
+            v, l, n = members(R)
+            h.set_params(1, 1, v[0], l[0], n[0])
+            res = h.fit_grad_batch(v, l, n)
+            tb = median_ms(lambda: h.fit_grad_batch(v, l, n))
+            exact, worst = 0, 0.0
+            refs = []
+            for r in range(R):
+                h.set_params(1, 1, v[r], l[r], n[r]); f, g = h.fit_grad(D)
+                ref = np.r_[f, g[0], g[1], g[2]]
+                got = np.r_[res[0][0][r], res[0][1][r], res[0][2][r], res[1][0][r], res[1][1][r], res[1][2][r]]
+                exact += int(np.array_equal(got, ref))
+                den = np.r_[np.abs(ref[:3]), np.full(ref.size - 3, np.max(np.abs(ref[3:])))]
+                worst = max(worst, float(np.max(np.where(den > 0, np.abs(got - ref) / np.where(den > 0, den, 1), 0))))
+                refs.append((v[r], l[r], n[r]))
+            def serial():
+                for (vv, ll, nn) in refs:
+                    h.set_params(1, 1, vv, ll, nn); h.fit_grad(D)
+            ts = median_ms(serial, bursts=5, reps=2)
+            print("%6d %4d %12.3f %12.3f %8.2f %6d/%-3d %10.2e" % (N, R, tb[0], ts[0], ts[0] / tb[0], exact, R, worst), flush=True)
+    h.close()
+    # the model layer: optimize_restarts(5) serial against parallel, N = 300, D = 8 ARD (medians over repeated searches)
+    X, Y = data(300, seed=5)
+    for parallel in (False, True, False, True):
+        times, fs = [], None
+        for rep in range(5):
+            m = gpo.models.GPRegression(X, Y, gpo.kern.Matern52(D, ARD=True), noise_var=1e-2)
+            m.Gaussian_noise.constrain_bounded(1e-9, 1e6, warning=False)
+            np.random.seed(7)
+            t0 = time.perf_counter()
+            runs = m.optimize_restarts(5, verbose=False, max_iters=1000, parallel=parallel)
+            times.append((time.perf_counter() - t0) * 1e3)
+            fs = [round(f, 9) for f, _ in runs]
+            m.close()
+        print("optimize_restarts(5) N=300 D=8 ARD parallel=%s: median %.1f ms (min %.1f, max %.1f) over 5; f = %s"
+              % (parallel, float(np.median(times)), min(times), max(times), fs), flush=True)
+
+
 def main():
     if len(sys.argv) < 2 or sys.argv[1] in ("-h", "--help", "--list"):
         print(__doc__)
