@@ -147,8 +147,12 @@ void phase_end(gp_ctx *g, int id) {
 }
 
 // ---- GEMM wrapper with accounting ---------------------------------------------------------------
+// The instance is chosen from the tiles of ONE problem (n: a launch over several members gives each the instance it would get
+// alone, and with it the same per-tile arithmetic); the accounting is that of the whole launch (n_all).  gp_profile brackets a
+// launch over members when it would bracket one member's, and records the launch's tiles and flops.
 void gemm(gp_ctx *g, hipStream_t s, int mode, double *C, long ldc, const double *A, long lda, const double *B, long ldb, int b_mul, int K, TileSet ts, const GemmOpt &o) {
-    const long n = tileset_count(ts) * o.batch;
+    if (o.batch <= 0 || o.members <= 0) return;
+    const long n = tileset_count(ts) * (o.batch / o.members), n_all = tileset_count(ts) * o.batch;
     if (n <= 0 || K <= 0) return;
     GemmOpt oo = o;
     if (n >= 1024 && !oo.stagger) oo.stagger = g->stagger;
@@ -184,7 +188,7 @@ void gemm(gp_ctx *g, hipStream_t s, int mode, double *C, long ldc, const double 
         e0 = g->gemm_events[g->gemm_ev_used++];
         e1 = g->gemm_events[g->gemm_ev_used++];
         GP_NOTE(hipEventRecord(e0, s));
-        g->gemm_tiles.push_back(n);
+        g->gemm_tiles.push_back(n_all);
         g->gemm_K.push_back((o.k_tri || o.k_end_tri) ? -K : K);
     }
     if (g->supertile > 1 && !o.tile_list && !o.k_end_tri && o.batch == 1 && tileset_count(ts) >= 2048) {
@@ -204,9 +208,45 @@ void gemm(gp_ctx *g, hipStream_t s, int mode, double *C, long ldc, const double 
     if (timed) {
         GP_NOTE(hipEventRecord(e1, s));
         g->gemm_launches++;
-        g->gemm_flops += 2.0 * GP_TILE * GP_TILE * (double)K * (double)n * ((o.k_tri || o.k_end_tri) ? 0.5 : 1.0);
+        g->gemm_flops += 2.0 * GP_TILE * GP_TILE * (double)K * (double)n_all * ((o.k_tri || o.k_end_tri) ? 0.5 : 1.0);
     }
-    g->gemm_flops_all += 2.0 * GP_TILE * GP_TILE * (double)K * (double)n * ((o.k_tri || o.k_end_tri) ? 0.5 : 1.0);
+    g->gemm_flops_all += 2.0 * GP_TILE * GP_TILE * (double)K * (double)n_all * ((o.k_tri || o.k_end_tri) ? 0.5 : 1.0);
+}
+
+// ---- members (api_internal.h) -------------------------------------------------------------------
+Members ctx_members(gp_ctx *g) {
+    Members m;
+    m.A = g->dA;
+    m.lda = g->Npad;
+    m.invL = g->dInvL;
+    m.info = g->dInfo;
+    m.invP = g->dInvP;
+    m.invPw = g->dInvPw;
+    m.W = g->invp_W;
+    m.alpha = g->dAlpha;
+    m.w = g->dW;
+    m.T = g->dT;
+    m.T2 = g->dT2;
+    m.Wi = g->dWi;
+    m.partial = g->dT;   // free once Ky^-1 is in dWi
+    m.scal = g->dScal;
+    m.kp = &g->kp;
+    return m;
+}
+
+Members members_range(const Members &m, int m0, int nb) {
+    Members r = m;
+    r.nb = nb;
+    r.A += m0 * m.sA;
+    r.invL += m0 * m.sI;
+    r.info += 4 * m0;
+    r.scal += m0 * m.sS;
+    for (double **q : {&r.invP, &r.invPw}) *q += m0 * m.sP;
+    for (double **q : {&r.alpha, &r.w}) *q += m0 * m.sV;
+    for (double **q : {&r.T, &r.T2, &r.Wi, &r.partial}) *q += m0 * m.sT;
+    for (const KernParams **q : {&r.kp, &r.kpt}) *q += m0;
+    for (const double **q : {&r.diag, &r.diag_tab, &r.jit, &r.jit_tab}) *q += m0;
+    return r;
 }
 
 // ---- memory helpers -----------------------------------------------------------------------------

@@ -4,37 +4,51 @@
 // (inference/latent_function_inference/exact_gaussian_inference.py:37-74).
 #include "api_internal.h"
 
+// K, the jitter of a repeated attempt (jitchol retries factor (Ky + jitter I): it lands on the assembled diagonal, linalg.py:69)
+// and the RHS rows of m's members
+void build_ky(gp_ctx *g, const Members &m, bool jittered) {
+    launch_kbuild(g->s, m.A, m.lda, g->dX, g->N, g->Npad, m.kp[0], m.diag[0], 0, m.nb, m.sA, m.kpt, m.diag_tab);
+    if (jittered) launch_add_diag(g->s, m.A, m.lda, g->N, m.jit[0], m.nb, m.sA, m.jit_tab);
+    launch_set_rhs(g->s, m.A, m.lda, g->dY, g->N, g->Npad, g->P, m.nb, m.sA);
+}
+
 // ---- blocked right-looking Cholesky (two-level: 128-column steps inside panel_tiles-wide panels) ----
-// A: nt x nt tiles (lower) plus R1 - nt extra row tiles that ride through the panel solves and updates (the RHS rows)
+// m.A: nt x nt tiles (lower) plus R1 - nt extra row tiles that ride through the panel solves and updates (the RHS rows)
 // side_inv (the model's own factor only): the inverted diagonal panel of each panel is built on the side stream as soon as that
 // panel's columns are final, beside the trailing update and the next panel -- one event record per panel on this stream.
 // One step of the in-panel factorisation starting at tile column j of a panel that ends at J1; returns the next column.
 // Option "inner_tiles" 2 (default 1: measured neutral) takes two columns at a time: the 256 x 256 diagonal block in ONE launch
 // (potrf_pair_kernel: both diagonal tiles, the tile between them solved and the second one updated inside), ONE launch that
 // solves both tile columns of the rows below (trsm2.hip), ONE K = 256 update of the panel's remaining columns -- three
-// dependent launches per 256 columns where the 128-column step takes six, and contractions twice as long.
-static int chain_step(gp_ctx *g, hipStream_t s, double *A, long lda, int j, int J1, int R1, double *invL, int *info) {
-    if (g->inner_tiles >= 2 && j + 1 < J1 && R1 - (j + 2) >= g->inner_min_rows) {
-        launch_potrf_pair(s, A, lda, j, invL, info);
+// dependent launches per 256 columns where the 128-column step takes six, and contractions twice as long.  (One member only:
+// the pair kernels have no batched twin.)
+static int chain_step(gp_ctx *g, hipStream_t s, const Members &m, int j, int J1, int R1) {
+    double *A = m.A, *invL = m.invL;
+    const long lda = m.lda;
+    if (g->inner_tiles >= 2 && m.nb == 1 && j + 1 < J1 && R1 - (j + 2) >= g->inner_min_rows) {
+        launch_potrf_pair(s, A, lda, j, invL, m.info);
         launch_trsm2(s, A, lda, j, invL, j + 2, R1);
         if (j + 2 < J1)
             gemm(g, s, 1, A, lda, A + (long)j * GP_TILE, lda, A + (long)j * GP_TILE, lda, 1, 2 * GP_TILE,
                  TileSet{0, R1, j + 2, J1, 1});
         return j + 2;
     }
-    launch_potrf_tile(s, A, lda, j, invL, info);
+    launch_potrf_tile(s, A, lda, j, invL, m.info, m.nb, m.sA, m.sI, 4);
     // panel solve: A[i, j] <- A[i, j] * inv(L_jj)^T for the row tiles below (and the RHS tile)
     gemm(g, s, 0, A, lda, A + (long)j * GP_TILE, lda, invL + (long)j * GP_TILE * GP_TILE, GP_TILE, 0, GP_TILE,
-         TileSet{j + 1, R1, j, j + 1, 0}, inplace_opt());
+         TileSet{j + 1, R1, j, j + 1, 0}, member_opt(m, inplace_opt(), m.sA, m.sA, m.sI));
     // update of the remaining columns of this panel (K = 128)
     if (j + 1 < J1)
-        gemm(g, s, 1, A, lda, A + (long)j * GP_TILE, lda, A + (long)j * GP_TILE, lda, 1, GP_TILE, TileSet{0, R1, j + 1, J1, 1});
+        gemm(g, s, 1, A, lda, A + (long)j * GP_TILE, lda, A + (long)j * GP_TILE, lda, 1, GP_TILE, TileSet{0, R1, j + 1, J1, 1},
+             member_opt(m, GemmOpt(), m.sA, m.sA, m.sA));
     return j + 1;
 }
 
-void factor_buf(gp_ctx *g, double *A, long lda, int nt, int R1, double *invL, int *info, bool side_inv) {
+void factor_buf(gp_ctx *g, const Members &m, int nt, int R1, bool side_inv) {
     const int W = g->panel_tiles;
     hipStream_t s = g->s;
+    double *A = m.A;
+    const long lda = m.lda;
     if (side_inv) {
         hipEvent_t e0 = la_event(g, EV_MISC, 0);
         GP_NOTE(hipEventRecord(e0, s));
@@ -42,7 +56,7 @@ void factor_buf(gp_ctx *g, double *A, long lda, int nt, int R1, double *invL, in
     }
     for (int J0 = 0; J0 < nt; J0 += W) {
         const int J1 = std::min(J0 + W, nt);
-        for (int j = J0; j < J1;) j = chain_step(g, s, A, lda, j, J1, R1, invL, info);
+        for (int j = J0; j < J1;) j = chain_step(g, s, m, j, J1, R1);
         if (side_inv) {
             hipEvent_t eF = la_event(g, EV_CHAIN, J0 / W);
             GP_NOTE(hipEventRecord(eF, s));
@@ -52,7 +66,7 @@ void factor_buf(gp_ctx *g, double *A, long lda, int nt, int R1, double *invL, in
         // trailing update with the whole panel (K = W * 128): the dense contraction on MFMA
         if (J1 < nt)
             gemm(g, s, 1, A, lda, A + (long)J0 * GP_TILE, lda, A + (long)J0 * GP_TILE, lda, 1, (J1 - J0) * GP_TILE,
-                 TileSet{0, R1, J1, nt, 1});
+                 TileSet{0, R1, J1, nt, 1}, member_opt(m, GemmOpt(), m.sA, m.sA, m.sA));
     }
     if (side_inv) {
         hipEvent_t ei = la_event(g, EV_MISC, 4);
@@ -75,7 +89,7 @@ int factor(gp_ctx *g) {
         if ((rc = dev_realloc(&g->dInvP, &g->capInvP, (long)nJ * PB * PB))) return rc;
         if ((rc = dev_realloc(&g->dInvPw, &g->capInvPw, (long)nJ * PB * PB))) return rc;
     }
-    factor_buf(g, g->dA, g->Npad, nt, nt + 1, g->dInvL, g->dInfo, side);
+    factor_buf(g, ctx_members(g), nt, nt + 1, side);
     if (side) {
         g->invp_W = W;
         g->invp_valid = true;   // (fit_impl drops it again when the attempt turns out not positive definite)
@@ -83,26 +97,6 @@ int factor(gp_ctx *g) {
     }
     return 0;
 }
-
-void build_panel_inv_one(gp_ctx *g, hipStream_t s, int J, int W, int nt) {
-    const long lda = g->Npad;
-    const long PB = (long)W * GP_TILE;
-    const int J0 = J * W, Wp = std::min(W, nt - J0);
-    double *Wb = g->dInvPw + (long)J * PB * PB;
-    const double *Lb = g->dA + (long)J * (PB * lda + PB);
-    const double *Ib = g->dInvL + (long)J0 * GP_TILE * GP_TILE;
-    launch_set_identity_blocks(s, Wb, PB, 1);
-    for (int b = 0; b < Wp; ++b) {
-        gemm(g, s, 0, Wb, PB, Wb + (long)b * GP_TILE, PB, Ib + (long)b * GP_TILE * GP_TILE, GP_TILE, 0, GP_TILE,
-             TileSet{0, b + 1, b, b + 1, 0}, inplace_opt());
-        if (b + 1 < Wp)
-            gemm(g, s, 1, Wb, PB, Wb + (long)b * GP_TILE, PB, Lb + (long)b * GP_TILE, lda, 1, GP_TILE,
-                 TileSet{0, b + 1, b + 1, Wp, 0});
-    }
-    launch_transpose_blocks(s, g->dInvP + (long)J * PB * PB, Wb, PB, 1);
-}
-
-static inline long Npad_rows(gp_ctx *g) { return g->Npad; }
 
 int factor_lookahead(gp_ctx *g, const PredPipe &pp) {
     int rc;
@@ -160,10 +154,11 @@ int factor_lookahead(gp_ctx *g, const PredPipe &pp) {
     std::vector<char> far_issued(nJ / std::max(1, Gf) + 2, 0);
     int mid_Jg = -1, mid_end = 0, mid_first = 0, mid_base = 0, mid_next = 0;
     if (Gf > 1) GP_NOTE(hipStreamWaitEvent(sfar, e0, 0));
+    const Members cm = ctx_members(g);
     for (int J = 0; J < nJ; ++J) {
         const int J0 = pb[J], J1 = pb[J + 1], J2 = pb[J + 2];
         bool bulk_recorded = false;
-        for (int j = J0; j < J1;) j = chain_step(g, sp, A, lda, j, J1, R1, g->dInvL, g->dInfo);
+        for (int j = J0; j < J1;) j = chain_step(g, sp, cm, j, J1, R1);
         hipEvent_t eF = la_event(g, EV_CHAIN, J);
         GP_NOTE(hipEventRecord(eF, sp));
         const int K = (J1 - J0) * GP_TILE;
@@ -251,7 +246,7 @@ int factor_lookahead(gp_ctx *g, const PredPipe &pp) {
                 auto rebuild_next = [&]() {
                     if (pbi(J + 2) < nt)
                         launch_rns_reconstruct256(sb, g->dRm, rg.nt256, rg.nt256, rg.nt256, pbi(J + 2), std::min(pbi(J + 3), nt),
-                                                  Npad_rows(g), A, lda, rg.back, 1);
+                                                  g->Npad, A, lda, rg.back, 1);
                 };
                 if (Gf == 1) {
                     rlaunch(sb, J, J2, nt, J == 0 ? 1 : 0);
@@ -352,9 +347,43 @@ __global__ void dot_ay_batch_kernel(const double *alpha, long sV, long lda_, con
     const long z = blockIdx.z;
     dot_ay_body(alpha + z * sV, lda_, Y, N, P, out + z * so);
 }
-void launch_dot_ay_batch(hipStream_t s, const double *alpha, long sV, long lda_, const double *Y, long N, int P, double *out, long so,
-                         int nb) {
-    GP_LAUNCH(dot_ay_batch_kernel, dim3(P, 1, nb), dim3(1024), 0, s, alpha, sV, lda_, Y, N, P, out, so);
+static void launch_dot_ay(hipStream_t s, const double *alpha, long lda_, const double *Y, long N, int P, double *out, int nb, long sV,
+                          long so) {
+    if (nb > 1)
+        GP_LAUNCH(dot_ay_batch_kernel, dim3(P, 1, nb), dim3(1024), 0, s, alpha, sV, lda_, Y, N, P, out, so);
+    else
+        GP_LAUNCH(dot_ay_kernel, dim3(P), dim3(1024), 0, s, alpha, lda_, Y, N, P, out);
+}
+
+// log det, alpha = L^-T z and alpha . y of m's members: 45 short dependent launches
+void alpha_lml(gp_ctx *g, hipStream_t s, const Members &m) {
+    const long Npad = g->Npad;
+    launch_logdet(s, m.A, m.lda, g->N, m.scal, m.nb, m.sA, m.sS);
+    launch_trsv_backward(s, m.A, m.lda, m.invP, m.W, Npad, m.A + Npad * m.lda, m.lda, g->P, m.alpha, m.w, m.nb, m.sA, m.sP, m.sV);
+    launch_dot_ay(s, m.alpha, Npad, g->dY, g->N, g->P, m.scal + 8, m.nb, m.sV, m.sS);
+}
+
+// ---- host arithmetic of one fit, per member ----
+// what the diagonal of K gets, and the diagonal of Ky the jitter ladder starts from
+void ky_diag(const KernParams &kp, double noise, double *diag_add, double *diag0) {
+    *diag_add = noise + 1e-8;  // exact_gaussian_inference.py:56
+    *diag0 = (kp.gower ? std::pow(kp.variance, kp.D) : kp.variance) + *diag_add;
+}
+// One step of the jitter ladder (GPy/GPy/util/linalg.py:62-75) after an attempt that failed with `info`: 0 with the next jitter
+// in *jitter, or the code the fit ends with.
+int ladder_step(double diag0, int maxtries, int info, double *jitter, int *tries) {
+    if (!(diag0 > 0.0)) return GP_ERR_NOT_PD_DIAG;
+    *jitter = *tries == 0 ? diag0 * 1e-6 : *jitter * 10.0;
+    ++*tries;
+    if (*tries > maxtries || !std::isfinite(*jitter)) return info > 0 ? info : 1;
+    return 0;
+}
+// scal: [0] log det, [8, 8 + P) alpha . y
+double lml_from_scalars(long N, int P, const double *scal) {
+    double fit = 0.0;
+    for (int p = 0; p < P; ++p) fit += scal[8 + p];
+    const double log_2_pi = std::log(2.0 * M_PI);
+    return 0.5 * (-(double)N * P * log_2_pi - P * scal[0] - fit);  // exact_gaussian_inference.py:62
 }
 
 // Shared body of gp_fit and gp_fit_predict.  pipe != 0: the candidate solve of the resident candidates is
@@ -374,7 +403,7 @@ struct QuiesceOnError {
 int fit_impl(gp_ctx *g, int maxtries, int pipe, int include_noise) {
     HIPCHK(hipSetDevice(g->device));
     QuiesceOnError guard{g};
-    const long N = g->N, Npad = g->Npad, lda = g->Npad;
+    const long N = g->N, Npad = g->Npad;
     const int P = g->P;
     const int nt_ = (int)(Npad / GP_TILE);
     // pipe 1: candidate solve of the resident candidates; pipe 2: the solve of the identity (L^-T, for Ky^-1)
@@ -401,8 +430,8 @@ int fit_impl(gp_ctx *g, int maxtries, int pipe, int include_noise) {
                               : (g->pipe_stages > 0 ? g->pipe_stages : std::max(1, (nJ * 14 + 50) / 100) + (nJ <= 12 ? 1 : 0));  // small N: the chain is everything
         pp.start_pct = pipe == 2 ? g->pipe_start_pct_grad : (g->pipe_start_pct >= 0 ? g->pipe_start_pct : (nJ <= 24 ? 32 : 40));
     }
-    const double diag_add = g->noise + 1e-8;  // exact_gaussian_inference.py:56
-    const double diag0 = (g->kp.gower ? std::pow(g->kp.variance, g->D) : g->kp.variance) + diag_add;
+    double diag_add, diag0;
+    ky_diag(g->kp, g->noise, &diag_add, &diag0);
     g->nphases = 0;
     g->emu_off_call = false;
     g->fitted = false;
@@ -422,10 +451,10 @@ int fit_impl(gp_ctx *g, int maxtries, int pipe, int include_noise) {
         g->lr_valid = false;     // residue planes of L belong to one factorisation attempt
         g->jitter_try = jitter;
         int ph = phase_begin(g, "kbuild", 0.0, 8.0 * N * g->D + 8.0 * (double)N * N / 2);
-        launch_kbuild(g->s, g->dA, lda, g->dX, N, Npad, g->kp, diag_add, 0);
-        // jitchol retries factor (Ky + jitter I): the jitter lands on the assembled diagonal (linalg.py:69)
-        if (jitter != 0.0) launch_add_diag(g->s, g->dA, lda, N, jitter);
-        launch_set_rhs(g->s, g->dA, lda, g->dY, N, Npad, P);
+        Members m = ctx_members(g);
+        m.diag = &diag_add;
+        m.jit = &jitter;
+        build_ky(g, m, jitter != 0.0);
         phase_end(g, ph);
         HIPCHK(hipMemsetAsync(g->dInfo, 0, sizeof(int) * 4, g->s));
         if (pipe == 1) {
@@ -470,15 +499,11 @@ int fit_impl(gp_ctx *g, int maxtries, int pipe, int include_noise) {
         if (info == 0) break;
         g->invp_valid = false;
         // jitter ladder, GPy/GPy/util/linalg.py:62-75
-        if (!(diag0 > 0.0)) return fail(GP_ERR_NOT_PD_DIAG, "not pd: non-positive diagonal elements");
-        if (tries == 0)
-            jitter = diag0 * 1e-6;
-        else
-            jitter *= 10.0;
-        ++tries;
-        if (tries > maxtries || !std::isfinite(jitter)) {
+        const int rcl = ladder_step(diag0, maxtries, info, &jitter, &tries);
+        if (rcl == GP_ERR_NOT_PD_DIAG) return fail(rcl, "not pd: non-positive diagonal elements");
+        if (rcl) {
             g_err = "not positive definite, even with jitter.";
-            return info > 0 ? info : 1;
+            return rcl;
         }
         g->nphases = 0;
     }
@@ -486,11 +511,6 @@ int fit_impl(gp_ctx *g, int maxtries, int pipe, int include_noise) {
     // alpha = L^-T z, log det and alpha'y: 45 short dependent launches (latency-bound, 1 ms).  When candidate / L^-T
     // stages are still to run on the main stream they go on the side stream instead, beside those long launches.
     bool side_alpha = false;
-    auto alpha_lml = [&](hipStream_t st) {
-        launch_logdet(st, g->dA, lda, N, g->dScal);
-        launch_trsv_backward(st, g->dA, lda, g->dInvP, g->invp_W, Npad, g->dA + Npad * lda, lda, P, g->dAlpha, g->dW);
-        GP_LAUNCH(dot_ay_kernel, dim3(P), dim3(1024), 0, st, g->dAlpha, Npad, g->dY, N, P, g->dScal + 8);
-    };
     if (pipe) {
         const int W = std::min(g->panel_tiles, nt_);
         const int nJ = (nt_ + W - 1) / W;
@@ -502,10 +522,10 @@ int fit_impl(gp_ctx *g, int maxtries, int pipe, int include_noise) {
             if (g->s_inv && g->side_alpha) GP_NOTE(hipEventRecord(eI, g->s));
             // the long launches first: the 45 short launches of alpha / log det take the host 0.7 ms to enqueue, during which
             // the main stream sat empty when they went first
-            solve_rows(g, g->dT, g->dT2, (int)(mcpad / GP_TILE), pipe == 2 ? 1 : 0, g->pipe_done);
+            solve_rows(g, ctx_members(g), (int)(mcpad / GP_TILE), pipe == 2 ? 1 : 0, g->pipe_done);
             if (g->s_inv && g->side_alpha) {
                 GP_NOTE(hipStreamWaitEvent(g->s_inv, eI, 0));
-                alpha_lml(g->s_inv);
+                alpha_lml(g, g->s_inv, ctx_members(g));
                 GP_NOTE(hipEventRecord(la_event(g, EV_MISC, 6), g->s_inv));
                 side_alpha = true;
             }
@@ -525,7 +545,7 @@ int fit_impl(gp_ctx *g, int maxtries, int pipe, int include_noise) {
     } else {
         int rci = ensure_panel_inv(g);
         if (rci) return rci;
-        alpha_lml(g->s);
+        alpha_lml(g, g->s, ctx_members(g));
     }
     phase_end(g, ph);
     if (pipe == 1) {
@@ -537,11 +557,8 @@ int fit_impl(gp_ctx *g, int maxtries, int pipe, int include_noise) {
     std::vector<double> sc(8 + P);
     HIPCHK(hipMemcpyAsync(sc.data(), g->dScal, sizeof(double) * (8 + P), hipMemcpyDeviceToHost, g->s));
     GP_SYNC(g->s);
-    double fit = 0.0;
-    for (int p = 0; p < P; ++p) fit += sc[8 + p];
     g->logdet = sc[0];
-    const double log_2_pi = std::log(2.0 * M_PI);
-    g->lml = 0.5 * (-(double)N * P * log_2_pi - P * g->logdet - fit);  // exact_gaussian_inference.py:62
+    g->lml = lml_from_scalars(N, P, sc.data());
     g->fitted = true;
     if (pipe == 1) {
         g->predicted = true;

@@ -2,6 +2,28 @@
 // Reference: Stationary.update_gradients_full (stationary.py:218-238), GP.predictive_gradients (gp.py:407-454).
 #include "api_internal.h"
 
+// the fused dL_dK reduction for m's members: one pass per GP_GRAD_CH dimensions, its sums at m.scal + 64 + pass * GP_GRAD_NACC
+void lml_grad_passes(gp_ctx *g, const Members &m) {
+    int pass = 0;
+    for (int d0 = 0; d0 < g->D; d0 += GP_GRAD_CH, ++pass) {
+        launch_lml_grad(g->s, g->dX, g->N, g->Npad, m.kp[0], g->ard, d0, m.alpha, g->P, m.Wi, g->Npad, m.partial,
+                        m.scal + 64 + pass * GP_GRAD_NACC, m.nb, m.kpt, m.sV, m.sT, m.sT, m.sS);
+        if (!g->ard) break;
+    }
+}
+
+// the gradients from those sums (h = scal + 64)
+void grads_from_sums(const double *h, const KernParams &kp, int ard, double *dvariance, double *dlengthscale, double *dnoise) {
+    *dvariance = h[0] / kp.variance;  // stationary.py:224
+    *dnoise = h[1];                   // gaussian.py:78-79
+    if (ard) {
+        for (int d = 0; d < kp.D; ++d)   // -sum tmp (dx_q)^2 / l_q^3, stationary.py:230-235,260-261
+            dlengthscale[d] = -h[(d / GP_GRAD_CH) * GP_GRAD_NACC + 2 + (d % GP_GRAD_CH)] / kp.ls[d];
+    } else {
+        dlengthscale[0] = -h[2] / kp.ls[0];  // -sum(dL_dr * r) / l, stationary.py:237-238
+    }
+}
+
 int lml_grad_impl(gp_ctx *g, double *dvariance, double *dlengthscale, double *dnoise, bool reset_phases) {
     if (!g || !dvariance || !dlengthscale || !dnoise) return fail(GP_ERR_ARG, "null argument");
     GP_DEAD_CHECK(g);
@@ -13,33 +35,15 @@ int lml_grad_impl(gp_ctx *g, double *dvariance, double *dlengthscale, double *dn
     int rc;
     if (reset_phases) g->nphases = 0;
     if ((rc = ensure_wi(g))) return rc;
-    const long Npad = g->Npad;
-    const int nt = (int)(Npad / GP_TILE), D = g->D;
-    const long ntile = (long)nt * (nt + 1) / 2;
     // per-tile partials live in dT (free after ensure_wi): ntile * NACC doubles << Npad^2
-    double *partial = g->dT;
     int ph = phase_begin(g, "lml_grad", 0.0, 8.0 * (double)g->N * g->N / 2);
-    std::vector<double> host((size_t)GP_GRAD_NACC * ((D + GP_GRAD_CH - 1) / GP_GRAD_CH));
-    int pass = 0;
-    for (int d0 = 0; d0 < D; d0 += GP_GRAD_CH, ++pass) {
-        launch_lml_grad(g->s, g->dX, g->N, Npad, g->kp, g->ard, d0, g->dAlpha, g->P, g->dWi, Npad, partial,
-                        g->dScal + 64 + pass * GP_GRAD_NACC);
-        if (!g->ard) break;
-    }
+    lml_grad_passes(g, ctx_members(g));
     phase_end(g, ph);
-    const int npass = g->ard ? (D + GP_GRAD_CH - 1) / GP_GRAD_CH : 1;
-    HIPCHK(hipMemcpyAsync(host.data(), g->dScal + 64, sizeof(double) * GP_GRAD_NACC * npass, hipMemcpyDeviceToHost,
-                          g->s));
+    const int npass = g->ard ? (g->D + GP_GRAD_CH - 1) / GP_GRAD_CH : 1;
+    std::vector<double> host((size_t)GP_GRAD_NACC * npass);
+    HIPCHK(hipMemcpyAsync(host.data(), g->dScal + 64, sizeof(double) * host.size(), hipMemcpyDeviceToHost, g->s));
     GP_SYNC(g->s);
-    (void)ntile;
-    *dvariance = host[0] / g->kp.variance;  // stationary.py:224
-    *dnoise = host[1];                      // gaussian.py:78-79
-    if (g->ard) {
-        for (int d = 0; d < D; ++d)         // -sum tmp (dx_q)^2 / l_q^3, stationary.py:230-235,260-261
-            dlengthscale[d] = -host[(d / GP_GRAD_CH) * GP_GRAD_NACC + 2 + (d % GP_GRAD_CH)] / g->kp.ls[d];
-    } else {
-        dlengthscale[0] = -host[2] / g->kp.ls[0];  // -sum(dL_dr * r) / l, stationary.py:237-238
-    }
+    grads_from_sums(host.data(), g->kp, g->ard, dvariance, dlengthscale, dnoise);
     return 0;
 }
 

@@ -232,6 +232,43 @@ static inline GemmOpt inplace_opt() {
     return o;
 }
 
+// ---- members ------------------------------------------------------------------------------------------------------------
+// Where the operands of the single-stream fit-and-gradient sequences live, and how many independent problems ("members": the
+// context's X, Y and shapes, each with hyper-parameters of its own) ride side by side in every launch.  Member z's operand is
+// at base + z * stride.  The context's own fit is ONE member over its buffers (ctx_members, strides unused); gp_fit_grad_batch
+// passes nb members over g->dBatch.  The sequences below are written once over this description; which kernel a launch of one
+// or of several members runs is the launchers' business (gphip_internal.h) and gemm()'s.
+struct Members {
+    int nb = 1;
+    long sA = 0, sI = 0, sP = 0, sV = 0, sT = 0, sS = 0;   // per-member strides (doubles) of the operand groups below, in their order
+    double *A = nullptr;      // Ky / L (lower) and, below it, the RHS rows: leading dimension lda
+    long lda = 0;
+    double *invL = nullptr;   // inverted diagonal tiles
+    double *invP = nullptr, *invPw = nullptr;   // inverted diagonal panels of W tiles and their build workspace
+    int W = 0;
+    double *alpha = nullptr, *w = nullptr;      // P x Npad each
+    // Npad x Npad each: the identity / running right-hand side, L^-T, Ky^-1 (may be T again) and the gradient pass's per-tile
+    // partials (any of them that is free by then)
+    double *T = nullptr, *T2 = nullptr, *Wi = nullptr, *partial = nullptr;
+    double *scal = nullptr;   // [0] log det, [8, 8 + P) alpha . y, [64 + pass * GP_GRAD_NACC ...) gradient sums
+    int *info = nullptr;      // 4 status words per member
+    // per-member values: on the host (nb entries; a launch of one member passes them in its kernel arguments) and the same
+    // in device tables (launches of several members index them; unused, and may be null, for one member)
+    const KernParams *kp = nullptr, *kpt = nullptr;
+    const double *diag = nullptr, *diag_tab = nullptr;   // what the diagonal of K gets: noise + 1e-8
+    const double *jit = nullptr, *jit_tab = nullptr;     // the jitter of the attempt in progress
+};
+Members ctx_members(gp_ctx *g);                          // api_core.hip: the context's buffers as they are NOW (take it at the point of use)
+Members members_range(const Members &m, int m0, int nb); // members [m0, m0 + nb) of m
+// the GEMM options of a launch over m's members: per-member strides of C, A and B
+static inline GemmOpt member_opt(const Members &m, GemmOpt o, long sC, long sA, long sB) {
+    o.batch = o.members = m.nb;
+    o.sC = sC;
+    o.sA = sA;
+    o.sB = sB;
+    return o;
+}
+
 // Pipelined candidate solve (gp_fit_predict): as soon as panel J of L is final (chain(J) done), two more
 // streams run, behind the factorisation and at low priority,
 //   s_inv : invP_J = L_JJ^-1 (the per-panel build of ensure_panel_inv),
@@ -293,8 +330,13 @@ void gemm(gp_ctx *g, hipStream_t s, int mode, double *C, long ldc, const double 
 void rns_gemm(gp_ctx *g, hipStream_t s, const signed char *A, long lda, long a_plane, const signed char *B, long ldb, long b_plane, signed char *R, int mt_all, int nt_all, int mt, int c0, int c1, int K, int first, int tri = 0);
 int dev_realloc(double **p, long *cap, long need);
 void destroy_ctx_events(gp_ctx *g);
-void factor_buf(gp_ctx *g, double *A, long lda, int nt, int R1, double *invL, int *info, bool side_inv = false);
+void build_ky(gp_ctx *g, const Members &m, bool jittered);
+void factor_buf(gp_ctx *g, const Members &m, int nt, int R1, bool side_inv = false);
 int factor(gp_ctx *g);
+void alpha_lml(gp_ctx *g, hipStream_t s, const Members &m);
+void ky_diag(const KernParams &kp, double noise, double *diag_add, double *diag0);
+int ladder_step(double diag0, int maxtries, int info, double *jitter, int *tries);
+double lml_from_scalars(long N, int P, const double *scal);
 void build_panel_inv_one(gp_ctx *g, hipStream_t s, int J, int W, int nt);
 int byte_realloc(signed char **p, long *cap, long need);
 int rns_prepare(gp_ctx *g, double jitter, RnsGeom *r);
@@ -304,7 +346,9 @@ int ensure_bulk_stream(gp_ctx *g);
 hipEvent_t la_event(gp_ctx *g, int kind, size_t i);
 int la_events_ok(gp_ctx *g);
 int ensure_panel_inv(gp_ctx *g);
-void solve_rows(gp_ctx *g, double *T, double *S, int mt, int trapezoid, int J_from = 0);
+void identity_blocks(hipStream_t s, double *T, long n, int nb);
+void panel_inv_members(gp_ctx *g, const Members &m);
+void solve_rows(gp_ctx *g, const Members &m, int mt, int trapezoid, int J_from = 0);
 int solve_rows_rns(gp_ctx *g, double *T, double *S, int mt, const RnsSolveOpt &opt = RnsSolveOpt());
 int fit_impl(gp_ctx *g, int maxtries, int pipe, int include_noise);
 int run_predict(gp_ctx *g, int include_noise, bool tiles_only = false);   // tiles_only: never the small-M path (the caller uses dT2 as a padded tile operand)
@@ -313,12 +357,13 @@ int run_acq(gp_ctx *g, int type, double par, double fmin, double y_mean, double 
 struct LpBatch { double *X = nullptr, *r = nullptr, *s = nullptr; };
 int upload_lp_batch(gp_ctx *g, const double *Xb, int nb, const double *r0, const double *s0, LpBatch *b);
 int run_acq_lp(gp_ctx *g, int type, double par, double fmin, double y_mean, double y_std, int transform, const double *Xb, int nb, const double *r0, const double *s0);
+void lauum(gp_ctx *g, const Members &m);
 int wi_lauum(gp_ctx *g);
 int wi_rns(gp_ctx *g);
 int ensure_wi(gp_ctx *g);
 int ensure_linv(gp_ctx *g);
-void launch_dot_ay_batch(hipStream_t s, const double *alpha, long sV, long lda_, const double *Y, long N, int P, double *out, long so,
-                         int nb);   // api_factor.hip: alpha_p . y_p of nb members (gp_fit_grad_batch)
+void lml_grad_passes(gp_ctx *g, const Members &m);
+void grads_from_sums(const double *h, const KernParams &kp, int ard, double *dvariance, double *dlengthscale, double *dnoise);
 int lml_grad_impl(gp_ctx *g, double *dvariance, double *dlengthscale, double *dnoise, bool reset_phases);
 int ensure_grad_buffers(gp_ctx *g, long elemsBeta, long M);
 int run_predict_grad(gp_ctx *g);

@@ -60,12 +60,12 @@ int run_predict(gp_ctx *g, int include_noise, bool tiles_only) {
             if (rc == GP_ERR_RANGE) {   // non-finite candidates / factor: this chunk again in true fp64 (NaNs propagate as in the reference)
                 ++g->emu_fallbacks;
                 launch_cross_k(g->s, g->dT, Npad, g->dXs + m0 * g->D, mc, mcpad, g->dX, g->N, Npad, g->kp);
-                solve_rows(g, g->dT, g->dT2, (int)(mcpad / GP_TILE), 0);
+                solve_rows(g, ctx_members(g), (int)(mcpad / GP_TILE), 0);
             } else if (rc) {
                 return rc;
             }
         } else {
-            solve_rows(g, g->dT, g->dT2, (int)(mcpad / GP_TILE), 0);
+            solve_rows(g, ctx_members(g), (int)(mcpad / GP_TILE), 0);
         }
         phase_end(g, ph);
         ph = phase_begin(g, "reduce", 0.0, 8.0 * (double)N * mc);
@@ -350,7 +350,12 @@ extern "C" int gp_posterior_samples(gp_t *g, int include_noise, const double *Z,
         }
         if (jitter != 0.0) launch_add_diag(g->s, C, Mpad, M, jitter);
         HIPCHK(hipMemsetAsync(g->dInfo, 0, sizeof(int) * 4, g->s));
-        factor_buf(g, C, Mpad, mt, mt, invL, g->dInfo);
+        Members cov;   // one member: the posterior covariance, no RHS rows
+        cov.A = C;
+        cov.lda = Mpad;
+        cov.invL = invL;
+        cov.info = g->dInfo;
+        factor_buf(g, cov, mt, mt);
         HIPCHK(hipMemcpyAsync(&info, g->dInfo, sizeof(int), hipMemcpyDeviceToHost, g->s));
         GP_SYNC(g->s);
         if (g->emulate_fp64 && info == 0) {

@@ -6,8 +6,41 @@
 // invP_J = L_JJ^-1 for every panel J of W tiles (PB = W*128 rows), so that every triangular solve
 // against L -- candidates (dtrtrs, posterior.py:294), alpha (dpotrs, exact_gaussian_inference.py:60),
 // Ky^-1 (dpotri, linalg.py:127-145) -- is ONE product per panel on the MFMA GEMM instead of a chain of
-// W dependent 128-column steps.  Built batched over all panels at once: the solve of the identity
-// against L_JJ (2W-1 small launches, each covering every panel) gives L_JJ^-T, then one transpose.
+// W dependent 128-column steps.  Built as the solve of the identity against L_JJ, which gives L_JJ^-T
+// (2W-1 small launches), then one transpose.  The GEMM has ONE batch index: the context's build spends
+// it on the panels (every launch covers every full panel), the build for several members on the members
+// (every launch covers one panel of every member); build_panel_inv_one takes one panel (the factorisation's side stream).
+
+// The solve itself, for diagonal panels of Wp tiles: Wb (PB x PB blocks, the identity on entry) becomes L_JJ^-T.  `o` carries
+// the launch's batch and the strides of Wb; sL / sI are those of the panel of L at Lb and of its inverted diagonal tiles at Ib.
+static void panel_inv_steps(gp_ctx *g, hipStream_t s, double *Wb, long PB, const double *Lb, long lda, const double *Ib, int Wp,
+                            GemmOpt o, long sL, long sI) {
+    for (int b = 0; b < Wp; ++b) {
+        o.inplace = 1;
+        o.sB = sI;
+        gemm(g, s, 0, Wb, PB, Wb + (long)b * GP_TILE, PB, Ib + (long)b * GP_TILE * GP_TILE, GP_TILE, 0, GP_TILE,
+             TileSet{0, b + 1, b, b + 1, 0}, o);
+        if (b + 1 < Wp) {
+            o.inplace = 0;
+            o.sB = sL;
+            gemm(g, s, 1, Wb, PB, Wb + (long)b * GP_TILE, PB, Lb + (long)b * GP_TILE, lda, 1, GP_TILE,
+                 TileSet{0, b + 1, b + 1, Wp, 0}, o);
+        }
+    }
+}
+
+void build_panel_inv_one(gp_ctx *g, hipStream_t s, int J, int W, int nt) {
+    const long lda = g->Npad;
+    const long PB = (long)W * GP_TILE;
+    const int J0 = J * W, Wp = std::min(W, nt - J0);
+    double *Wb = g->dInvPw + (long)J * PB * PB;
+    const double *Lb = g->dA + (long)J * (PB * lda + PB);
+    const double *Ib = g->dInvL + (long)J0 * GP_TILE * GP_TILE;
+    launch_set_identity_blocks(s, Wb, PB, 1);
+    panel_inv_steps(g, s, Wb, PB, Lb, lda, Ib, Wp, GemmOpt(), 0, 0);
+    launch_transpose_blocks(s, g->dInvP + (long)J * PB * PB, Wb, PB, 1);
+}
+
 int ensure_panel_inv(gp_ctx *g) {
     const long Npad = g->Npad, lda = g->Npad;
     const int nt = (int)(Npad / GP_TILE);
@@ -31,21 +64,10 @@ int ensure_panel_inv(gp_ctx *g) {
         double *Wb = Wk + z0 * PB * PB;
         const double *Lb = g->dA + z0 * (PB * lda + PB);
         const double *Ib = g->dInvL + z0 * (long)W * GP_TILE * GP_TILE;
-        for (int b = 0; b < Wp; ++b) {
-            GemmOpt o;
-            o.batch = batch;
-            o.inplace = 1;
-            o.sC = o.sA = PB * PB;
-            o.sB = (long)W * GP_TILE * GP_TILE;
-            gemm(g, s, 0, Wb, PB, Wb + (long)b * GP_TILE, PB, Ib + (long)b * GP_TILE * GP_TILE, GP_TILE, 0, GP_TILE,
-                 TileSet{0, b + 1, b, b + 1, 0}, o);
-            if (b + 1 < Wp) {
-                o.inplace = 0;
-                o.sB = PB * lda + PB;
-                gemm(g, s, 1, Wb, PB, Wb + (long)b * GP_TILE, PB, Lb + (long)b * GP_TILE, lda, 1, GP_TILE,
-                     TileSet{0, b + 1, b + 1, Wp, 0}, o);
-            }
-        }
+        GemmOpt o;
+        o.batch = batch;
+        o.sC = o.sA = PB * PB;
+        panel_inv_steps(g, s, Wb, PB, Lb, lda, Ib, Wp, o, PB * lda + PB, (long)W * GP_TILE * GP_TILE);
     }
     launch_transpose_blocks(s, g->dInvP, Wk, PB, nJ);
     g->invp_W = W;
@@ -53,23 +75,43 @@ int ensure_panel_inv(gp_ctx *g) {
     return 0;
 }
 
+// nb identity blocks of n x n, stacked: launch_set_identity_blocks in pieces whose grid stays within 32768 rows
+void identity_blocks(hipStream_t s, double *T, long n, int nb) {
+    const int per = (int)std::max(1L, 32768 / n);
+    for (int b0 = 0; b0 < nb; b0 += per) launch_set_identity_blocks(s, T + (long)b0 * n * n, n, std::min(per, nb - b0));
+}
+
+// The same panels (W tiles wide) for m's members, contiguous in m.invP / m.invPw: one panel of every member per launch.
+void panel_inv_members(gp_ctx *g, const Members &m) {
+    const long lda = m.lda, PB = (long)m.W * GP_TILE;
+    const int W = m.W, nt = (int)(g->Npad / GP_TILE), nJ = (nt + W - 1) / W;
+    identity_blocks(g->s, m.invPw, PB, m.nb * nJ);
+    for (int J = 0; J < nJ; ++J)
+        panel_inv_steps(g, g->s, m.invPw + (long)J * PB * PB, PB, m.A + (long)J * (PB * lda + PB), lda,
+                        m.invL + (long)J * W * GP_TILE * GP_TILE, std::min(W, nt - J * W), member_opt(m, GemmOpt(), m.sP, m.sP, 0),
+                        m.sA, m.sI);
+    launch_transpose_blocks(g->s, m.invP, m.invPw, PB, m.nb * nJ);
+}
+
 // Row solve  S = T L^-T  for `mt` row tiles of T (row-major, ld = Npad); T is consumed as the running
 // right-hand side.  trapezoid = 1: T is block upper-triangular (row tile r is zero left of column tile r:
 // the identity, for L^-T), so panel J only touches the row tiles above its end.
-void solve_rows(gp_ctx *g, double *T, double *S, int mt, int trapezoid, int J_from) {
-    const long Npad = g->Npad, lda = g->Npad;
-    const int nt = (int)(Npad / GP_TILE);
-    const int W = g->invp_W;
+// m.T / m.T2 are T / S.
+void solve_rows(gp_ctx *g, const Members &m, int mt, int trapezoid, int J_from) {
+    const long Npad = g->Npad, lda = m.lda;
+    const int nt = (int)(Npad / GP_TILE), W = m.W;
     const long PB = (long)W * GP_TILE;
-    const double *L = g->dA;
+    double *T = m.T, *S = m.T2;
+    const double *L = m.A;
     hipStream_t s = g->s;
+    const GemmOpt upd = member_opt(m, GemmOpt(), m.sT, m.sT, m.sA);   // T[:, > J] -= S[:, J] L[> J, J]^T
     auto panel_solve = [&](int J, int J0, int J1, int rows) {
         GemmOpt o;
         o.k_end_tri = 1;
         o.b_sub = J0;
         // S[:, J] = T[:, J] invP_J^T   (invP_J lower triangular: column tile c contracts k <= c)
-        gemm(g, s, 0, S, Npad, T + (long)J0 * GP_TILE, Npad, g->dInvP + (long)J * PB * PB, PB, 1, (J1 - J0) * GP_TILE,
-             TileSet{0, rows, J0, J1, 0}, o);
+        gemm(g, s, 0, S, Npad, T + (long)J0 * GP_TILE, Npad, m.invP + (long)J * PB * PB, PB, 1, (J1 - J0) * GP_TILE,
+             TileSet{0, rows, J0, J1, 0}, member_opt(m, o, m.sT, m.sT, m.sP));
     };
     for (int J0 = J_from * W, J = J_from; J0 < nt;) {
         const int J1 = std::min(J0 + W, nt), J2 = std::min(J1 + W, nt);
@@ -83,17 +125,16 @@ void solve_rows(gp_ctx *g, double *T, double *S, int mt, int trapezoid, int J_fr
         // same products in the same order as with one launch per panel: bitwise the same result.
         const bool two = g->pair_panels && !trapezoid && J2 > J1 && J2 < nt;
         if (!two) {
-            // T[:, > J] -= S[:, J] L[> J, J]^T
             gemm(g, s, 1, T, Npad, S + (long)J0 * GP_TILE, Npad, L + (long)J0 * GP_TILE, lda, 1, Kp,
-                 TileSet{0, rows, J1, nt, 0});
+                 TileSet{0, rows, J1, nt, 0}, upd);
             J0 = J1;
             ++J;
             continue;
         }
-        gemm(g, s, 1, T, Npad, S + (long)J0 * GP_TILE, Npad, L + (long)J0 * GP_TILE, lda, 1, Kp, TileSet{0, rows, J1, J2, 0});
+        gemm(g, s, 1, T, Npad, S + (long)J0 * GP_TILE, Npad, L + (long)J0 * GP_TILE, lda, 1, Kp, TileSet{0, rows, J1, J2, 0}, upd);
         panel_solve(J + 1, J1, J2, rows);
         gemm(g, s, 1, T, Npad, S + (long)J0 * GP_TILE, Npad, L + (long)J0 * GP_TILE, lda, 1, (J2 - J0) * GP_TILE,
-             TileSet{0, rows, J2, nt, 0});
+             TileSet{0, rows, J2, nt, 0}, upd);
         J0 = J2;
         J += 2;
     }
@@ -105,36 +146,38 @@ void solve_rows(gp_ctx *g, double *T, double *S, int mt, int trapezoid, int J_fr
 // Ky^-1 = W W^T with the contraction of tile row a starting at column a*128: another N^3/3.
 // Reference: pdinv / dpotri (GPy/GPy/util/linalg.py:127-145,193-214), Posterior.woodbury_inv
 // (posterior.py:176-196).
-// Ky^-1 from dT2 = L^-T (block upper triangular) into dWi
-int wi_lauum(gp_ctx *g) {
+// Ky^-1 from m.T2 = L^-T (block upper triangular) into m.Wi
+void lauum(gp_ctx *g, const Members &m) {
     const long Npad = g->Npad;
     const int nt = (int)(Npad / GP_TILE);
     hipStream_t s = g->s;
-    int ph;
-    ph = phase_begin(g, "potri_lauum", (double)g->N * g->N * g->N / 3.0, 0.0);
+    GemmOpt o;
+    o.k_tri = 1;
     if (g->lauum_panels) {
         // Ky^-1 = (L^-T)(L^-T)^T accumulated k-panel by k-panel: panel p (W tiles of k) adds to the tiles (i, c), c <= i,
         // with i below the panel's end.  Every tile of a launch then walks the SAME k range, so the workgroups of an
         // XCD share their operand panels in L2 like the trailing updates do; as one launch over k = i*128 .. N each
         // tile streams its own up-to-33 MB row panels at its own offset and the product runs at the fabric's pace
         // (47 TFLOP/s at N = 32768).  The accumulator holds -Ky^-1 (C -= A B^T is the kernel's update form).
-        HIPCHK(hipMemsetAsync(g->dWi, 0, sizeof(double) * Npad * Npad, s));
+        GP_NOTE(hipMemsetAsync(m.Wi, 0, sizeof(double) * (Npad * Npad + (m.nb - 1) * m.sT), s));   // (members are contiguous)
         const int W = g->panel_tiles;
         for (int k0 = 0; k0 < nt; k0 += W) {
             const int k1 = std::min(k0 + W, nt);
-            GemmOpt o;
-            o.k_tri = 1;
             o.k_sub = k0;
-            gemm(g, s, 1, g->dWi, Npad, g->dT2 + (long)k0 * GP_TILE, Npad, g->dT2 + (long)k0 * GP_TILE, Npad, 1,
-                 (k1 - k0) * GP_TILE, TileSet{0, k1, 0, k1, 1}, o);
+            gemm(g, s, 1, m.Wi, Npad, m.T2 + (long)k0 * GP_TILE, Npad, m.T2 + (long)k0 * GP_TILE, Npad, 1, (k1 - k0) * GP_TILE,
+                 TileSet{0, k1, 0, k1, 1}, member_opt(m, o, m.sT, m.sT, m.sT));
         }
-        launch_symmetrize_scale(s, g->dWi, Npad, Npad, -1.0);
+        launch_symmetrize_scale(s, m.Wi, Npad, Npad, -1.0, m.nb, m.sT);
     } else {
-        GemmOpt o;
-        o.k_tri = 1;
-        gemm(g, s, 0, g->dWi, Npad, g->dT2, Npad, g->dT2, Npad, 1, (int)Npad, TileSet{0, nt, 0, nt, 1}, o);
-        launch_symmetrize(s, g->dWi, Npad, Npad);
+        gemm(g, s, 0, m.Wi, Npad, m.T2, Npad, m.T2, Npad, 1, (int)Npad, TileSet{0, nt, 0, nt, 1}, member_opt(m, o, m.sT, m.sT, m.sT));
+        launch_symmetrize(s, m.Wi, Npad, Npad, m.nb, m.sT);
     }
+}
+
+// ... for the context's own fit, as a phase
+int wi_lauum(gp_ctx *g) {
+    const int ph = phase_begin(g, "potri_lauum", (double)g->N * g->N * g->N / 3.0, 0.0);
+    lauum(g, ctx_members(g));
     phase_end(g, ph);
     return 0;
 }
@@ -171,7 +214,7 @@ int ensure_wi(gp_ctx *g) {
     } else if (!g->w_in_t2) {
         int ph = phase_begin(g, "potri_solve", (double)g->N * g->N * g->N / 3.0, 0.0);
         launch_set_identity(s, T, Npad, Npad);
-        solve_rows(g, T, g->dT2, nt, 1);  // dT2 = L^-T (block upper triangular)
+        solve_rows(g, ctx_members(g), nt, 1);  // dT2 = L^-T (block upper triangular)
         phase_end(g, ph);
     }
     g->w_in_t2 = true;
@@ -197,7 +240,7 @@ int ensure_linv(gp_ctx *g) {
     if (!g->w_in_t2) {
         int ph = phase_begin(g, "potri_solve", (double)g->N * g->N * g->N / 3.0, 0.0);
         launch_set_identity(g->s, g->dT, Npad, Npad);
-        solve_rows(g, g->dT, g->dT2, nt, 1);  // dT2 = L^-T (true fp64 in either arithmetic mode)
+        solve_rows(g, ctx_members(g), nt, 1);  // dT2 = L^-T (true fp64 in either arithmetic mode)
         phase_end(g, ph);
         g->w_in_t2 = true;
         g->predicted = false;  // dT was reused

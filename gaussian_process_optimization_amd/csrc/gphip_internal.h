@@ -112,6 +112,8 @@ struct GemmOpt {
     int k_end_tri = 0;  // k ends after column tile (tc - b_sub) (B block lower-triangular)
     int b_sub = 0;      // B row tile = (tc - b_sub) * b_mul
     int batch = 1;      // blockIdx.y instances with pointer strides sC, sA, sB (elements)
+    int members = 1;    // ... of which this many are whole problems side by side (not parts of one): gemm() chooses the instance
+                        // from one problem's tiles, batch / members of them, so that each gets the instance it would get alone
     long sC = 0, sA = 0, sB = 0;
     const short *tile_list = nullptr;  // device pointer, 2 shorts per tile, tileset_count(ts) tiles
     int stagger = 0;                   // odd-wave-slot workgroups start stagger * 1024 cycles late
@@ -130,7 +132,8 @@ void launch_gemm_nt(hipStream_t s, int mode, double *C, long ldc, const double *
 // Factor the 128x128 diagonal tile t of A (row-major, lda) in place (lower) and write
 // its inverse (row-major 128x128, lower, zero above) to invL + t*128*128.
 // info: device int, 0 = ok, else 1-based global column of the first non-positive pivot.
-void launch_potrf_tile(hipStream_t s, double *A, long lda, int t, double *invL, int *info);
+void launch_potrf_tile(hipStream_t s, double *A, long lda, int t, double *invL, int *info, int nb = 1, long sA = 0, long sI = 0,
+                       int sInfo = 0);
 // The same for the diagonal tiles t and t + 1 in one launch, including L10 = A10 inv(L00)^T and A11 -= L10 L10^T between them.
 void launch_potrf_pair(hipStream_t s, double *A, long lda, int t, double *invL, int *info);
 // Both tile columns of the rows below a factored pair, one launch: for every 32-row strip of the row tiles [r0, r1)
@@ -138,11 +141,18 @@ void launch_potrf_pair(hipStream_t s, double *A, long lda, int t, double *invL, 
 void launch_trsm2(hipStream_t s, double *A, long lda, int t, const double *invL, int r0, int r1);
 void potrf_set_debug_lds(int bytes);   // test hook: dynamic LDS added to every diagonal-tile launch (a refused launch beyond ~9 KB)
 
-// Ky lower tiles (incl. diagonal tiles in full) from X; padding rows get identity.
-void launch_kbuild(hipStream_t s, double *A, long lda, const double *X, long N, long Npad,
-                   const KernParams &kp, double diag_add, int full);
+// ---- launches that take members ---------------------------------------------------------------------------------------------
+// The launchers with a trailing `nb` run nb independent problems ("members") side by side: member z at base + z * stride
+// (blockIdx.z, or blockIdx.x for the one-workgroup kernels).  One member (the default) is the single-member kernel with the
+// values given on the host (kp, diag_add, v); several are its _batch twin, which runs the same body per member -- the per-tile
+// arithmetic of the single launch -- and reads per-member values from device tables (kpt[z], diag_tab[z], v_tab[z]), kp then
+// being the first member's: what selects the instance and the LDS size.  Only the launchers ask "one member or several".
+
+// Ky lower tiles (incl. diagonal tiles in full) from X; padding rows get identity.  (Several members: lower tiles only.)
+void launch_kbuild(hipStream_t s, double *A, long lda, const double *X, long N, long Npad, const KernParams &kp, double diag_add,
+                   int full, int nb = 1, long sA = 0, const KernParams *kpt = nullptr, const double *diag_tab = nullptr);
 // RHS rows: A[(Npad + p)*lda + i] = Y[i*P + p] (zero for i >= N, and rows p >= P zero)
-void launch_set_rhs(hipStream_t s, double *A, long lda, const double *Y, long N, long Npad, int P);
+void launch_set_rhs(hipStream_t s, double *A, long lda, const double *Y, long N, long Npad, int P, int nb = 1, long sA = 0);
 // T[c*ldt + i] = k(xs_c, x_i) for c < M, i < N; zero in the padding.
 void launch_cross_k(hipStream_t s, double *T, long ldt, const double *Xs, long M, long Mpad,
                     const double *X, long N, long Npad, const KernParams &kp);
@@ -152,14 +162,14 @@ void launch_cross_k_rows(hipStream_t s, double *T, long ldt, const double *Xs, i
                          const KernParams &kp);
 
 // logdet = 2 * sum_i log A[i*lda+i], i < N (deterministic single-block reduction)
-void launch_logdet(hipStream_t s, const double *A, long lda, long N, double *out);
+void launch_logdet(hipStream_t s, const double *A, long lda, long N, double *out, int nb = 1, long sA = 0, long so = 0);
 // out[p] = sum_i z_p[i]^2 for the RHS rows z_p = A[(Npad+p)*lda + i]
 void launch_rhs_sumsq(hipStream_t s, const double *A, long lda, long N, long Npad, int P, double *out);
 
 // Backward substitution alpha = L^-T z using the inverse diagonal tiles.
 //   z rows: Z + p*ldz (p < P), alpha rows: Aout + p*ldz; w: workspace P*Npad; invP: inverted diagonal panels.
-void launch_trsv_backward(hipStream_t s, const double *L, long lda, const double *invP, int W, long Npad,
-                          const double *Z, long ldz, int P, double *Aout, double *w);
+void launch_trsv_backward(hipStream_t s, const double *L, long lda, const double *invP, int W, long Npad, const double *Z, long ldz,
+                          int P, double *Aout, double *w, int nb = 1, long sL = 0, long sP = 0, long sV = 0);
 
 // Row reductions over the solved candidate rows T[c, 0:N]:
 //   var[c] = kss - sum_i T[c,i]^2 (+ noise_add), mean[c*P+p] = sum_i T[c,i] * Z[p*ldz + i]
@@ -231,18 +241,19 @@ void launch_transpose_tri(hipStream_t s, double *dst, const double *src, long n,
 #define GP_GRAD_CH 16
 #define GP_GRAD_NACC (GP_GRAD_CH + 2)
 void launch_set_identity(hipStream_t s, double *T, long ld, long n);
-void launch_symmetrize(hipStream_t s, double *A, long ld, long n);
+void launch_symmetrize(hipStream_t s, double *A, long ld, long n, int nb = 1, long sA = 0);
 // A = scale * lower(A), mirrored into the upper triangle
-void launch_symmetrize_scale(hipStream_t s, double *A, long ld, long n, double scale);
-void launch_lml_grad(hipStream_t s, const double *X, long N, long Npad, const KernParams &kp, int ard, int d0,
-                     const double *alpha, int P, const double *Wi, long ldw, double *partial, double *out);
+void launch_symmetrize_scale(hipStream_t s, double *A, long ld, long n, double scale, int nb = 1, long sA = 0);
+void launch_lml_grad(hipStream_t s, const double *X, long N, long Npad, const KernParams &kp, int ard, int d0, const double *alpha,
+                     int P, const double *Wi, long ldw, double *partial, double *out, int nb = 1, const KernParams *kpt = nullptr,
+                     long sV = 0, long sW = 0, long sP = 0, long so = 0);
 void launch_predict_grad(hipStream_t s, const double *Xs, long M, const double *X, long N, const KernParams &kp,
                          const double *alpha, long lda_, int P, const double *beta, long ldb, double *dmdx,
                          double *dvdx);
 void launch_acq_grad(hipStream_t s, int type, double par, double fmin, double y_mean, double y_std, const double *mean,
                      const double *var, const double *dmdx, const double *dvdx, long M, int D, double *out,
                      double *dout);
-void launch_add_diag(hipStream_t s, double *A, long lda, long N, double v);
+void launch_add_diag(hipStream_t s, double *A, long lda, long N, double v, int nb = 1, long sA = 0, const double *v_tab = nullptr);
 void launch_trace(hipStream_t s, const double *A, long lda, long N, double *out);   // out[0] = trace, out[1] = smallest diagonal entry
 
 // nb blocks of n x n (row-major, leading dimension n, stacked): identity / transpose (dst_b = src_b^T)
@@ -258,24 +269,6 @@ void launch_dldk(hipStream_t s, double *out, long ldo, const double *alpha, long
                  long ldw, long N);
 // zero the strict upper triangle of the nt diagonal 128-tiles (the factor's tiles keep the symmetric input there)
 void launch_zero_upper_diag(hipStream_t s, double *A, long lda, int nt);
-
-// ---- batched twins of the launches above (gp_fit_grad_batch, api_batch.hip) --------------------------------------------------
-// nb members side by side, member z at base + z * stride (blockIdx.z, or blockIdx.x for the one-workgroup kernels); each runs
-// the same body as its single-member kernel, so a member gets the per-tile arithmetic of the single call.  Per-member parameters
-// come from a device table (kpt[z]); kp0 (host) is member 0's, for what selects the instance and the LDS size.
-void launch_kbuild_batch(hipStream_t s, double *A, long lda, long sA, const double *X, long N, long Npad, const KernParams &kp0,
-                         const KernParams *kpt, const double *diag_add, int nb);
-void launch_add_diag_batch(hipStream_t s, double *A, long sA, long lda, long N, const double *v, int nb);
-void launch_set_rhs_batch(hipStream_t s, double *A, long lda, long sA, const double *Y, long N, long Npad, int P, int nb);
-void launch_potrf_tile_batch(hipStream_t s, double *A, long lda, long sA, int t, double *invL, long sI, int *info, int sInfo,
-                             int nb);
-void launch_logdet_batch(hipStream_t s, const double *A, long lda, long sA, long N, double *out, long so, int nb);
-void launch_trsv_backward_batch(hipStream_t s, const double *L, long lda, long sL, const double *invP, long sP, int W, long Npad,
-                                int P, double *Aout, double *w, long sV, int nb);
-void launch_symmetrize_scale_batch(hipStream_t s, double *A, long sA, long ld, long n, double scale, int nb);
-void launch_lml_grad_batch(hipStream_t s, const double *X, long N, long Npad, const KernParams &kp0, const KernParams *kpt, int ard,
-                           int d0, const double *alpha, long sV, int P, const double *Wi, long sW, long ldw, double *partial,
-                           long sP, double *out, long so, int nb);
 
 // ---- rns.hip: fp64-equivalent contraction on the int8 matrix cores (option "emulate_fp64") -----------------------------
 #define GP_RNS_T 14

@@ -83,17 +83,17 @@ __global__ void symmetrize_scale_kernel(double *A, long ld, long n, double scale
 __global__ void symmetrize_scale_batch_kernel(double *A, long sA, long ld, long n, double scale) {
     symmetrize_scale_body(A + (long)blockIdx.z * sA, ld, n, scale);
 }
-void launch_symmetrize_scale_batch(hipStream_t s, double *A, long sA, long ld, long n, double scale, int nb) {
+void launch_symmetrize_scale(hipStream_t s, double *A, long ld, long n, double scale, int nb, long sA) {
     const unsigned nbk = (unsigned)((n + 31) / 32);
-    GP_LAUNCH(symmetrize_scale_batch_kernel, dim3(nbk, nbk, (unsigned)nb), dim3(256), 0, s, A, sA, ld, n, scale);
+    if (nb > 1)
+        GP_LAUNCH(symmetrize_scale_batch_kernel, dim3(nbk, nbk, (unsigned)nb), dim3(256), 0, s, A, sA, ld, n, scale);
+    else
+        GP_LAUNCH(symmetrize_scale_kernel, dim3(nbk, nbk), dim3(256), 0, s, A, ld, n, scale);
 }
-void launch_symmetrize_scale(hipStream_t s, double *A, long ld, long n, double scale) {
-    const unsigned nb = (unsigned)((n + 31) / 32);
-    GP_LAUNCH(symmetrize_scale_kernel, dim3(nb, nb), dim3(256), 0, s, A, ld, n, scale);
-}
-void launch_symmetrize(hipStream_t s, double *A, long ld, long n) {
-    const unsigned nb = (unsigned)((n + 31) / 32);
-    GP_LAUNCH(symmetrize_kernel, dim3(nb, nb), dim3(256), 0, s, A, ld, n);
+void launch_symmetrize(hipStream_t s, double *A, long ld, long n, int nb, long sA) {
+    if (nb > 1) return launch_symmetrize_scale(s, A, ld, n, 1.0, nb, sA);   // (x 1.0: the mirror alone)
+    const unsigned nbk = (unsigned)((n + 31) / 32);
+    GP_LAUNCH(symmetrize_kernel, dim3(nbk, nbk), dim3(256), 0, s, A, ld, n);
 }
 
 // ---- LML hyper-gradients: one pass over the lower tiles ------------------------------------------
@@ -246,30 +246,27 @@ __global__ __launch_bounds__(1024) void sum_partials_batch_kernel(const double *
     sum_partials_body(partial + z * sP, ntile, nacc, out + z * so);
 }
 
-// the same pass for nb members (gp_fit_grad_batch); kp0: member 0's parameters on the host (D, Gower: the LDS size)
-void launch_lml_grad_batch(hipStream_t s, const double *X, long N, long Npad, const KernParams &kp0, const KernParams *kpt, int ard,
-                           int d0, const double *alpha, long sV, int P, const double *Wi, long sW, long ldw, double *partial,
-                           long sP, double *out, long so, int nb) {
-    const int nt = (int)(Npad / GP_TILE);
-    const long ntile = (long)nt * (nt + 1) / 2;
-    const size_t shm = ((size_t)(kp0.gower ? 4 : 2) * kp0.D * GP_TILE + (size_t)2 * P * GP_TILE) * sizeof(double);
-    const unsigned split = ntile < 256 ? 4u : 1u;   // (as launch_lml_grad: the per-member partials land in the same order)
-    GP_LAUNCH(lml_grad_tile_batch_kernel, dim3((unsigned)ntile, split, (unsigned)nb), dim3(256), shm, s, X, N, kpt, ard, d0, alpha,
-              sV, Npad, P, Wi, sW, ldw, partial, sP);
-    GP_LAUNCH(sum_partials_batch_kernel, dim3(NACC, 1, (unsigned)nb), dim3(1024), 0, s, partial, sP, ntile * split, NACC, out, so);
-}
-
 // out (device, NACC doubles): sums for dims [d0, d0+GCH)
-void launch_lml_grad(hipStream_t s, const double *X, long N, long Npad, const KernParams &kp, int ard, int d0,
-                     const double *alpha, int P, const double *Wi, long ldw, double *partial, double *out) {
+// nb > 1: the same pass for nb members, member z with parameters kpt[z] (device), alpha + z sV, Ky^-1 at Wi + z sW, partials at
+// partial + z sP and sums at out + z so; kp (the first member's, host) gives D and the Gower setting: the LDS size
+void launch_lml_grad(hipStream_t s, const double *X, long N, long Npad, const KernParams &kp, int ard, int d0, const double *alpha,
+                     int P, const double *Wi, long ldw, double *partial, double *out, int nb, const KernParams *kpt, long sV,
+                     long sW, long sP, long so) {
     const int nt = (int)(Npad / GP_TILE);
     const long ntile = (long)nt * (nt + 1) / 2;
     const size_t shm = ((size_t)(kp.gower ? 4 : 2) * kp.D * GP_TILE + (size_t)2 * P * GP_TILE) * sizeof(double);
     // few tiles (N <= ~2900): four workgroups per tile, 32 rows each -- 6 workgroups of 128 x 128 covariance evaluations were a
     // quarter of an LML + gradient evaluation at N = 300; the partial sums are added per (tile, quarter) in the same fixed order
     const unsigned split = ntile < 256 ? 4u : 1u;
-    GP_LAUNCH(lml_grad_tile_kernel, dim3((unsigned)ntile, split), dim3(256), shm, s, X, N, kp, ard, d0, alpha, Npad,
-                       P, Wi, ldw, partial);
+    if (nb > 1) {
+        GP_LAUNCH(lml_grad_tile_batch_kernel, dim3((unsigned)ntile, split, (unsigned)nb), dim3(256), shm, s, X, N, kpt, ard, d0,
+                  alpha, sV, Npad, P, Wi, sW, ldw, partial, sP);
+        GP_LAUNCH(sum_partials_batch_kernel, dim3(NACC, 1, (unsigned)nb), dim3(1024), 0, s, partial, sP, ntile * split, NACC, out,
+                  so);
+        return;
+    }
+    GP_LAUNCH(lml_grad_tile_kernel, dim3((unsigned)ntile, split), dim3(256), shm, s, X, N, kp, ard, d0, alpha, Npad, P, Wi, ldw,
+              partial);
     GP_LAUNCH(sum_partials_kernel, dim3(NACC), dim3(1024), 0, s, partial, ntile * split, NACC, out);
 }
 
@@ -368,17 +365,17 @@ __global__ void add_diag2_kernel(double *A, long lda, long n, double v) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) A[i * lda + i] += v;
 }
-void launch_add_diag(hipStream_t s, double *A, long lda, long N, double v) {
-    GP_LAUNCH(add_diag2_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, A, lda, N, v);
-}
 // member z's diagonal += v[z] (gp_fit_grad_batch: each member's own jitter)
 __global__ void add_diag_batch_kernel(double *A, long sA, long lda, long n, const double *v) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     const long z = blockIdx.z;
     if (i < n) A[z * sA + i * lda + i] += v[z];
 }
-void launch_add_diag_batch(hipStream_t s, double *A, long sA, long lda, long N, const double *v, int nb) {
-    GP_LAUNCH(add_diag_batch_kernel, dim3((unsigned)((N + 255) / 256), 1, (unsigned)nb), dim3(256), 0, s, A, sA, lda, N, v);
+void launch_add_diag(hipStream_t s, double *A, long lda, long N, double v, int nb, long sA, const double *v_tab) {
+    if (nb > 1)
+        GP_LAUNCH(add_diag_batch_kernel, dim3((unsigned)((N + 255) / 256), 1, (unsigned)nb), dim3(256), 0, s, A, sA, lda, N, v_tab);
+    else
+        GP_LAUNCH(add_diag2_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, A, lda, N, v);
 }
 // out[0] = sum_i A[i][i], out[1] = min_i A[i][i]  (jitchol looks at both: linalg.py:61-66)
 __global__ __launch_bounds__(1024) void trace_kernel(const double *A, long lda, long N, double *out) {

@@ -137,12 +137,18 @@ __global__ __launch_bounds__(256) void kbuild_batch_kernel(double *A, long lda, 
     kbuild_body<DU>(A + z * sA, lda, X, N, Npad, kpt[z], diag_add[z], 0, nt);
 }
 
-void launch_kbuild(hipStream_t s, double *A, long lda, const double *X, long N, long Npad,
-                   const KernParams &kp, double diag_add, int full) {
+static void launch_kbuild_members(hipStream_t s, double *A, long lda, long sA, const double *X, long N, long Npad, int DU, size_t shm,
+                                  const KernParams *kpt, const double *diag_tab, int nb);
+
+// nb > 1: the lower tiles of nb members' matrices in one launch; kernel, D and the Gower setting -- what picks the instance and
+// the LDS size -- are the same for every member, so kp (the first member's) chooses for all
+void launch_kbuild(hipStream_t s, double *A, long lda, const double *X, long N, long Npad, const KernParams &kp, double diag_add,
+                   int full, int nb, long sA, const KernParams *kpt, const double *diag_tab) {
     const int nt = (int)(Npad / GP_TILE);
     const long nblk = full ? (long)nt * nt : (long)nt * (nt + 1) / 2;
     const int DU = kp.gower ? 0 : (kp.D <= 8 ? 8 : (kp.D <= 16 ? 16 : 0));
     const size_t shm = (size_t)2 * (DU ? DU : kp.D) * GP_TILE * sizeof(double);
+    if (nb > 1) return launch_kbuild_members(s, A, lda, sA, X, N, Npad, DU, shm, kpt, diag_tab, nb);
     if (DU == 8)
         GP_LAUNCH(kbuild_kernel<8>, dim3((unsigned)nblk), dim3(256), shm, s, A, lda, X, N, Npad, kp, diag_add, full, nt);
     else if (DU == 16)
@@ -163,12 +169,13 @@ __global__ void set_rhs_kernel(double *A, long lda, const double *Y, long N, lon
 __global__ void set_rhs_batch_kernel(double *A, long lda, long sA, const double *Y, long N, long Npad, int P) {
     set_rhs_body(A + (long)blockIdx.z * sA, lda, Y, N, Npad, P);
 }
-void launch_set_rhs_batch(hipStream_t s, double *A, long lda, long sA, const double *Y, long N, long Npad, int P, int nb) {
-    dim3 grid((unsigned)((Npad + 255) / 256), GP_MAX_RHS, (unsigned)nb);
-    GP_LAUNCH(set_rhs_batch_kernel, grid, dim3(256), 0, s, A, lda, sA, Y, N, Npad, P);
-}
 
-void launch_set_rhs(hipStream_t s, double *A, long lda, const double *Y, long N, long Npad, int P) {
+void launch_set_rhs(hipStream_t s, double *A, long lda, const double *Y, long N, long Npad, int P, int nb, long sA) {
+    if (nb > 1) {
+        dim3 grid((unsigned)((Npad + 255) / 256), GP_MAX_RHS, (unsigned)nb);
+        GP_LAUNCH(set_rhs_batch_kernel, grid, dim3(256), 0, s, A, lda, sA, Y, N, Npad, P);
+        return;
+    }
     dim3 grid((unsigned)((Npad + 255) / 256), GP_MAX_RHS);
     GP_LAUNCH(set_rhs_kernel, grid, dim3(256), 0, s, A, lda, Y, N, Npad, P);
 }
@@ -296,19 +303,15 @@ void launch_cross_k_rows(hipStream_t s, double *T, long ldt, const double *Xs, i
               X, N, Npad, kp);
 }
 
-// the lower tiles of nb members' matrices in one launch (gp_fit_grad_batch); kp0 is member 0's parameters on the host (kernel, D
-// and the Gower setting -- what picks the instance and the LDS size -- are the same for every member)
-void launch_kbuild_batch(hipStream_t s, double *A, long lda, long sA, const double *X, long N, long Npad, const KernParams &kp0,
-                         const KernParams *kpt, const double *diag_add, int nb) {
+// (defined last: the batch instances stay behind every other kernel of this file in the code object)
+static void launch_kbuild_members(hipStream_t s, double *A, long lda, long sA, const double *X, long N, long Npad, int DU, size_t shm,
+                                  const KernParams *kpt, const double *diag_tab, int nb) {
     const int nt = (int)(Npad / GP_TILE);
-    const long nblk = (long)nt * (nt + 1) / 2;
-    const int DU = kp0.gower ? 0 : (kp0.D <= 8 ? 8 : (kp0.D <= 16 ? 16 : 0));
-    const size_t shm = (size_t)2 * (DU ? DU : kp0.D) * GP_TILE * sizeof(double);
-    const dim3 grid((unsigned)nblk, 1, (unsigned)nb);
+    const dim3 grid((unsigned)((long)nt * (nt + 1) / 2), 1, (unsigned)nb);   // (lower tiles only)
     if (DU == 8)
-        GP_LAUNCH(kbuild_batch_kernel<8>, grid, dim3(256), shm, s, A, lda, sA, X, N, Npad, kpt, diag_add, nt);
+        GP_LAUNCH(kbuild_batch_kernel<8>, grid, dim3(256), shm, s, A, lda, sA, X, N, Npad, kpt, diag_tab, nt);
     else if (DU == 16)
-        GP_LAUNCH(kbuild_batch_kernel<16>, grid, dim3(256), shm, s, A, lda, sA, X, N, Npad, kpt, diag_add, nt);
+        GP_LAUNCH(kbuild_batch_kernel<16>, grid, dim3(256), shm, s, A, lda, sA, X, N, Npad, kpt, diag_tab, nt);
     else
-        GP_LAUNCH(kbuild_batch_kernel<0>, grid, dim3(256), shm, s, A, lda, sA, X, N, Npad, kpt, diag_add, nt);
+        GP_LAUNCH(kbuild_batch_kernel<0>, grid, dim3(256), shm, s, A, lda, sA, X, N, Npad, kpt, diag_tab, nt);
 }

@@ -669,11 +669,9 @@ void launch_potrf_pair(hipStream_t s, double *A, long lda, int t, double *invL, 
     GP_LAUNCH(potrf_pair_kernel, dim3(1), dim3(512), (size_t)g_debug_lds, s, A, lda, t, invL, info);
 }
 
-void launch_potrf_tile(hipStream_t s, double *A, long lda, int t, double *invL, int *info) {
-    GP_LAUNCH(potrf_tile_kernel, dim3(1), dim3(512), (size_t)g_debug_lds, s, A, lda, t, invL, info);
-}
-
-void launch_potrf_tile_batch(hipStream_t s, double *A, long lda, long sA, int t, double *invL, long sI, int *info, int sInfo,
-                             int nb) {
-    GP_LAUNCH(potrf_tile_batch_kernel, dim3((unsigned)nb), dim3(512), 0, s, A, lda, sA, t, invL, sI, info, sInfo);
+void launch_potrf_tile(hipStream_t s, double *A, long lda, int t, double *invL, int *info, int nb, long sA, long sI, int sInfo) {
+    if (nb > 1)
+        GP_LAUNCH(potrf_tile_batch_kernel, dim3((unsigned)nb), dim3(512), 0, s, A, lda, sA, t, invL, sI, info, sInfo);
+    else
+        GP_LAUNCH(potrf_tile_kernel, dim3(1), dim3(512), (size_t)g_debug_lds, s, A, lda, t, invL, info);
 }

@@ -44,11 +44,11 @@ __global__ __launch_bounds__(1024) void logdet_kernel(const double *A, long lda,
 __global__ __launch_bounds__(1024) void logdet_batch_kernel(const double *A, long lda, long sA, long N, double *out, long so) {
     logdet_body(A + (long)blockIdx.x * sA, lda, N, out + (long)blockIdx.x * so);
 }
-void launch_logdet_batch(hipStream_t s, const double *A, long lda, long sA, long N, double *out, long so, int nb) {
-    GP_LAUNCH(logdet_batch_kernel, dim3((unsigned)nb), dim3(1024), 0, s, A, lda, sA, N, out, so);
-}
-void launch_logdet(hipStream_t s, const double *A, long lda, long N, double *out) {
-    GP_LAUNCH(logdet_kernel, dim3(1), dim3(1024), 0, s, A, lda, N, out);
+void launch_logdet(hipStream_t s, const double *A, long lda, long N, double *out, int nb, long sA, long so) {
+    if (nb > 1)
+        GP_LAUNCH(logdet_batch_kernel, dim3((unsigned)nb), dim3(1024), 0, s, A, lda, sA, N, out, so);
+    else
+        GP_LAUNCH(logdet_kernel, dim3(1), dim3(1024), 0, s, A, lda, N, out);
 }
 
 // ---- out[p] = z_p . z_p  (= Y^T Ky^-1 Y, the data-fit term of exact_gaussian_inference.py:62) ----
@@ -166,9 +166,11 @@ __global__ void zero_kernel(double *p, long n) {
     if (i < n) p[i] = 0.0;
 }
 // invP: panels of W tiles, each stored as a PB x PB row-major block (PB = W*128) at invP + J*PB*PB
-void launch_trsv_backward(hipStream_t s, const double *L, long lda, const double *invP, int W, long Npad,
-                          const double *Z, long ldz, int P, double *Aout, double *w) {
-    const long nw = (long)P * Npad;
+// nb > 1: the same back-substitution for nb members in the same launches: member z's factor at L + z sL and its right-hand
+// rows at Z + z sL, its inverted panels at invP + z sP, its alpha / workspace at Aout + z sV / w + z sV (w contiguous over members)
+void launch_trsv_backward(hipStream_t s, const double *L, long lda, const double *invP, int W, long Npad, const double *Z, long ldz,
+                          int P, double *Aout, double *w, int nb, long sL, long sP, long sV) {
+    const long nw = nb > 1 ? sV * nb : (long)P * Npad;
     GP_LAUNCH(zero_kernel, dim3((unsigned)((nw + 255) / 256)), dim3(256), 0, s, w, nw);
     const int nt = (int)(Npad / GP_TILE);
     const long PB = (long)W * GP_TILE;
@@ -177,33 +179,18 @@ void launch_trsv_backward(hipStream_t s, const double *L, long lda, const double
         const int J0 = J * W, J1 = std::min(J0 + W, nt);
         const int Kp = (J1 - J0) * GP_TILE;
         const long off = (long)J0 * GP_TILE;
-        GP_LAUNCH(panel_solve_kernel, dim3(J1 - J0), dim3(PT), Kp * sizeof(double), s, invP + (long)J * PB * PB,
-                           PB, Kp, Z, ldz, w, Npad, P, off, Aout);
+        const double *Pj = invP + (long)J * PB * PB;
+        if (nb > 1) {
+            GP_LAUNCH(panel_solve_batch_kernel, dim3(J1 - J0, 1, nb), dim3(PT), Kp * sizeof(double), s, Pj, sP, PB, Kp, Z, sL, ldz,
+                      w, sV, Npad, P, off, Aout);
+            if (J0 > 0)
+                GP_LAUNCH(panel_update_batch_kernel, dim3(J0, 1, nb), dim3(PT), Kp * sizeof(double), s, L, sL, lda, Kp, off, Aout,
+                          sV, ldz, P, w, Npad);
+            continue;
+        }
+        GP_LAUNCH(panel_solve_kernel, dim3(J1 - J0), dim3(PT), Kp * sizeof(double), s, Pj, PB, Kp, Z, ldz, w, Npad, P, off, Aout);
         if (J0 > 0)
-            GP_LAUNCH(panel_update_kernel, dim3(J0), dim3(PT), Kp * sizeof(double), s, L, lda, Kp, off, Aout,
-                               ldz, P, w, Npad);
-    }
-}
-
-// the same back-substitution for nb members (gp_fit_grad_batch) in the same launches: member z's factor and RHS rows at
-// L + z sL, its inverted panels at invP + z sP, its alpha / workspace at Aout + z sV / w + z sV (w contiguous over members)
-void launch_trsv_backward_batch(hipStream_t s, const double *L, long lda, long sL, const double *invP, long sP, int W, long Npad,
-                                int P, double *Aout, double *w, long sV, int nb) {
-    const long nw = sV * nb;
-    GP_LAUNCH(zero_kernel, dim3((unsigned)((nw + 255) / 256)), dim3(256), 0, s, w, nw);
-    const int nt = (int)(Npad / GP_TILE);
-    const long PB = (long)W * GP_TILE;
-    const int nJ = (nt + W - 1) / W;
-    const double *Z = L + Npad * lda;
-    for (int J = nJ - 1; J >= 0; --J) {
-        const int J0 = J * W, J1 = std::min(J0 + W, nt);
-        const int Kp = (J1 - J0) * GP_TILE;
-        const long off = (long)J0 * GP_TILE;
-        GP_LAUNCH(panel_solve_batch_kernel, dim3(J1 - J0, 1, nb), dim3(PT), Kp * sizeof(double), s, invP + (long)J * PB * PB, sP,
-                  PB, Kp, Z, sL, lda, w, sV, Npad, P, off, Aout);
-        if (J0 > 0)
-            GP_LAUNCH(panel_update_batch_kernel, dim3(J0, 1, nb), dim3(PT), Kp * sizeof(double), s, L, sL, lda, Kp, off, Aout, sV,
-                      lda, P, w, Npad);
+            GP_LAUNCH(panel_update_kernel, dim3(J0), dim3(PT), Kp * sizeof(double), s, L, lda, Kp, off, Aout, ldz, P, w, Npad);
     }
 }
 
