@@ -56,9 +56,9 @@ extern "C" int gp_fit_grad_batch(gp_t *g, int R, const double *variance, const d
     m.sS = 64 + 4 * GP_GRAD_NACC;   // (D <= 64: 4 gradient passes)
     const long per = m.sA + m.sI + 2 * m.sP + 2 * m.sV + 2 * m.sT + m.sS + 2;
     int rc;
-    if ((rc = dev_realloc(&g->dBatch, &g->capBatch, per * R))) return rc;
+    if ((rc = g->dBatch.reserve(per * R))) return rc;
     const size_t kp_bytes = (sizeof(KernParams) * R + 255) / 256 * 256;
-    if ((rc = byte_realloc(&g->dBatchAux, &g->capBatchAux, (long)(kp_bytes + sizeof(int) * 4 * R)))) return rc;
+    if ((rc = g->dBatchAux.reserve((long)(kp_bytes + sizeof(int) * 4 * R)))) return rc;
     m.A = g->dBatch;
     m.invL = m.A + R * m.sA;
     m.invP = m.invL + R * m.sI;
@@ -69,7 +69,7 @@ extern "C" int gp_fit_grad_batch(gp_t *g, int R, const double *variance, const d
     m.T2 = m.partial = m.T + R * m.sT;  // L^-T, then the gradient partials (free after the product)
     m.scal = m.T2 + R * m.sT;
     double *dDiag = m.scal + R * m.sS, *dJit = dDiag + R;
-    KernParams *dKp = (KernParams *)g->dBatchAux;
+    KernParams *dKp = (KernParams *)g->dBatchAux.p;
     m.info = (int *)(g->dBatchAux + kp_bytes);
 
     // per-member parameters: the context's kernel, dimension and Gower set-up with the member's variance / lengthscale(s)

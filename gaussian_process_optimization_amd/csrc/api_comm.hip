@@ -99,15 +99,8 @@ static void apply_fit_record(gp_ctx *g, const double *rec) {
     g->jitter = rec[0];   // a receiver's gp_fmin is y - (noise + 1e-8 + jitter) alpha with the ROOT's jitter
     g->lml = rec[1];
     g->logdet = rec[2];
-    g->fitted = true;
-    g->fmin_valid = false;
-    g->wi_valid = false;
-    g->li_valid = false;
-    g->rows_calls_since_fit = 0;
-    g->w_in_t2 = false;
-    g->invp_valid = false;
-    g->lr_valid = false;
-    g->predicted = false;
+    fit_dropped(g);
+    g->fitted = true;   // ... and the factor that arrived is a fit: dA, dInvL, dAlpha and the scalars above are the root's
 }
 
 extern "C" int gp_comm_bcast_fit(gp_t *g, int root) {
@@ -172,7 +165,7 @@ extern "C" int gp_comm_allgather_topk(gp_t *g, int k, const double *vals, const 
     if (g->nranks > 128) return fail(GP_ERR_ARG, "nranks > 128");
     HIPCHK(hipSetDevice(g->device));
     int rc;
-    if ((rc = dev_realloc(&g->dComm, &g->capComm, 2L * GP_TOPK_MAX * (1 + 128)))) return rc;
+    if ((rc = g->dComm.reserve(2L * GP_TOPK_MAX * (1 + 128)))) return rc;
     // k records of {double val, int64 idx} per rank, moved as 2k x 8 bytes
     std::vector<double> rec(2 * (size_t)k);
     for (int j = 0; j < k; ++j) {

@@ -196,10 +196,10 @@ void gemm(gp_ctx *g, hipStream_t s, int mode, double *C, long ldc, const double 
         auto it = g->tile_lists.find(key);
         if (it == g->tile_lists.end()) {
             std::vector<short> l = build_tile_list(ts, g->supertile);
-            short *d = nullptr;
-            if (hipMalloc((void **)&d, l.size() * sizeof(short)) == hipSuccess) {
+            DevBuf<short> d;
+            if (d.alloc((long)l.size()) == hipSuccess) {   // (not reserve: a launch without its list is no error)
                 hipMemcpy(d, l.data(), l.size() * sizeof(short), hipMemcpyHostToDevice);
-                it = g->tile_lists.emplace(key, d).first;
+                it = g->tile_lists.emplace(key, std::move(d)).first;
             }
         }
         if (it != g->tile_lists.end()) oo.tile_list = it->second;
@@ -247,18 +247,6 @@ Members members_range(const Members &m, int m0, int nb) {
     for (const KernParams **q : {&r.kp, &r.kpt}) *q += m0;
     for (const double **q : {&r.diag, &r.diag_tab, &r.jit, &r.jit_tab}) *q += m0;
     return r;
-}
-
-// ---- memory helpers -----------------------------------------------------------------------------
-int dev_realloc(double **p, long *cap, long need) {
-    if (need <= *cap && *p) return 0;
-    if (*p) hipFree(*p);
-    *p = nullptr;
-    *cap = 0;
-    hipError_t e = hipMalloc((void **)p, (size_t)need * sizeof(double));
-    if (e != hipSuccess) return fail(GP_ERR_HIP, "hipMalloc(%ld doubles) -> %s", need, hipGetErrorString(e));
-    *cap = need;
-    return 0;
 }
 
 extern "C" const char *gp_last_error(void) { return g_err.c_str(); }
@@ -310,17 +298,13 @@ extern "C" int gp_create(gp_t **out, int device) {
         g->s_inv = d.inv;
         g->s_pred = d.pred;
     }
-    hipError_t e = hipMalloc((void **)&g->dInfo, sizeof(int) * 4);
-    if (e == hipSuccess) e = hipMalloc((void **)&g->dScal, sizeof(double) * 512);
-    if (e == hipSuccess) e = hipMalloc((void **)&g->dRedV, sizeof(double) * 512);
-    if (e == hipSuccess) e = hipMalloc((void **)&g->dRedI, sizeof(long long) * 1024);
-    if (e != hipSuccess) {
-        if (g->dInfo) hipFree(g->dInfo);
-        for (double *p : {g->dScal, g->dRedV})
-            if (p) hipFree(p);
-        if (g->dRedI) hipFree(g->dRedI);
+    int rc = g->dInfo.reserve(4);
+    if (!rc) rc = g->dScal.reserve(512);
+    if (!rc) rc = g->dRedV.reserve(512);
+    if (!rc) rc = g->dRedI.reserve(1024);
+    if (rc) {
         delete g;
-        return fail(GP_ERR_HIP, "gp_create: hipMalloc -> %s", hipGetErrorString(e));
+        return rc;
     }
     {
         std::lock_guard<std::mutex> lk(g_ds_mu);
@@ -373,95 +357,97 @@ extern "C" int gp_destroy(gp_t *g) {
     hipSetDevice(g->device);
     hipDeviceSynchronize();
     if (g->comm) ncclCommDestroy(g->comm);
-    double *ptrs[] = {g->dX, g->dY, g->dA, g->dInvL, g->dAlpha, g->dW, g->dMu, g->dScal, g->dRedV,
-                      g->dXs, g->dT, g->dMean, g->dVar, g->dAcq, g->dWi, g->dT2, g->dDm, g->dDv, g->dDacq, g->dCov, g->dInvP, g->dInvPw, g->dLp, g->dComm,
-                      g->dX2, g->dK2, g->dLi, g->dRows, g->dBatch};
-    for (double *p : ptrs)
-        if (p) hipFree(p);
-    if (g->dRowsCounter) hipFree(g->dRowsCounter);
     if (g->hRowsOut) hipHostFree(g->hRowsOut);
-    if (g->dInfo) hipFree(g->dInfo);
-    if (g->dRedI) hipFree(g->dRedI);
-    for (signed char *p : {g->dLr, g->dSr, g->dRr, g->dRm, g->dWr, g->dBatchAux})
-        if (p) hipFree(p);
-    for (auto &kv : g->tile_lists) hipFree(kv.second);
     // events recorded on the shared streams go first; the streams themselves belong to the per-device set shared by
     // every context of the process and are destroyed by gp_shutdown / the exit hook
     destroy_ctx_events(g);
-    delete g;
+    delete g;   // every device buffer is freed by its DevBuf
+    return 0;
+}
+
+// ---- options --------------------------------------------------------------------------------------
+// The options that are one int of the context, and how each takes its value:
+//   OPT_RANGE  stored when in [lo, hi], GP_ERR_ARG otherwise      OPT_BOOL  0 or 1
+//   OPT_FLOOR  GP_ERR_ARG below lo, clamped to 1 << 20 above      OPT_RAW   as it is
+// gp_set_option looks a name up here first; what an option does beyond the store follows the table there.
+enum OptShape { OPT_RANGE, OPT_FLOOR, OPT_BOOL, OPT_RAW };
+struct OptDesc {
+    const char *name;
+    int gp_ctx::*field;
+    OptShape shape;
+    int lo, hi;
+};
+static const OptDesc g_options[] = {
+    {"panel_tiles", &gp_ctx::panel_tiles, OPT_RANGE, 1, 64},
+    {"inner_tiles", &gp_ctx::inner_tiles, OPT_RANGE, 1, 2},
+    {"inner_min_rows", &gp_ctx::inner_min_rows, OPT_FLOOR, 0},
+    {"own_keep_per_row", &gp_ctx::own_keep_per_row, OPT_FLOOR, 0},
+    {"own_keep_pipe_pct", &gp_ctx::own_keep_pipe_pct, OPT_RANGE, 0, 400},
+    {"own_keep_base", &gp_ctx::own_keep_base, OPT_FLOOR, 0},
+    {"lookahead", &gp_ctx::lookahead, OPT_BOOL},
+    {"lookahead_min_tiles", &gp_ctx::lookahead_min_tiles, OPT_FLOOR, 0},
+    {"pipe_start_pct", &gp_ctx::pipe_start_pct, OPT_RANGE, -1, 100},   // -1: automatic
+    {"small_below", &gp_ctx::small_below, OPT_RAW},
+    {"pipe_stages_grad", &gp_ctx::pipe_stages_grad, OPT_FLOOR, 0},
+    {"pipe_start_pct_grad", &gp_ctx::pipe_start_pct_grad, OPT_RANGE, 0, 100},
+    {"pipe_stages", &gp_ctx::pipe_stages, OPT_FLOOR, 0},
+    {"lauum_panels", &gp_ctx::lauum_panels, OPT_RAW},
+    {"side_alpha", &gp_ctx::side_alpha, OPT_RAW},
+    {"pair_panels", &gp_ctx::pair_panels, OPT_BOOL},
+    {"pair_tri", &gp_ctx::pair_tri, OPT_RAW},
+    {"fmin_direct", &gp_ctx::fmin_direct, OPT_RAW},
+    {"chain_small_below", &gp_ctx::chain_small_below, OPT_RAW},
+    {"waves8", &gp_ctx::waves8, OPT_BOOL},
+    {"stagger", &gp_ctx::stagger, OPT_RAW},
+    {"trsm_rows64", &gp_ctx::trsm_rows64, OPT_RAW},
+    {"rns_group_fit", &gp_ctx::rns_group_fit, OPT_RANGE, 1, 16},
+    {"rns_group", &gp_ctx::rns_group, OPT_RANGE, 1, 16},
+    {"emulate_fit", &gp_ctx::emulate_fit, OPT_BOOL},
+    {"emulate_fp64", &gp_ctx::emulate_fp64, OPT_BOOL},
+    {"rows_build", &gp_ctx::rows_build, OPT_RANGE, -1, 1},   // -1: by rule, 0: never, 1: at the first call
+    {"rows_nt", &gp_ctx::rows_nt, OPT_RANGE, -1, 1},         // -1: automatic
+};
+
+static int store_option(gp_ctx *g, const OptDesc &o, int64_t value) {
+    if (o.shape == OPT_RANGE && (value < o.lo || value > o.hi))
+        return fail(GP_ERR_ARG, "%s out of range [%d, %d]", o.name, o.lo, o.hi);
+    if (o.shape == OPT_FLOOR && value < o.lo) return fail(GP_ERR_ARG, "%s < %d", o.name, o.lo);
+    if (o.shape == OPT_FLOOR) value = std::min<int64_t>(value, 1 << 20);
+    if (o.shape == OPT_BOOL) value = value ? 1 : 0;
+    g->*o.field = (int)value;
     return 0;
 }
 
 extern "C" int gp_set_option(gp_t *g, const char *name, int64_t value) {
     if (!g || !name) return fail(GP_ERR_ARG, "null argument");
     GP_DEAD_CHECK(g);
-    if (!strcmp(name, "panel_tiles")) {
-        if (value < 1 || value > 64) return fail(GP_ERR_ARG, "panel_tiles out of range");
-        g->panel_tiles = (int)value;
-    } else if (!strcmp(name, "inner_tiles")) {
-        if (value != 1 && value != 2) return fail(GP_ERR_ARG, "inner_tiles must be 1 or 2");
-        g->inner_tiles = (int)value;
-    } else if (!strcmp(name, "inner_min_rows")) {
-        if (value < 0) return fail(GP_ERR_ARG, "inner_min_rows < 0");
-        g->inner_min_rows = (int)std::min<int64_t>(value, 1 << 20);
-    } else if (!strcmp(name, "own_keep_per_row")) {
-        if (value < 0) return fail(GP_ERR_ARG, "own_keep_per_row < 0");
-        g->own_keep_per_row = (int)std::min<int64_t>(value, 1 << 20);
-    } else if (!strcmp(name, "own_keep_pipe_pct")) {
-        if (value < 0 || value > 400) return fail(GP_ERR_ARG, "own_keep_pipe_pct out of range");
-        g->own_keep_pipe_pct = (int)value;
-    } else if (!strcmp(name, "own_keep_base")) {
-        if (value < 0) return fail(GP_ERR_ARG, "own_keep_base < 0");
-        g->own_keep_base = (int)std::min<int64_t>(value, 1 << 20);
-    } else if (!strcmp(name, "lookahead")) {
-        g->lookahead = value ? 1 : 0;
-    } else if (!strcmp(name, "lookahead_min_tiles")) {
-        if (value < 0) return fail(GP_ERR_ARG, "lookahead_min_tiles < 0");
-        g->lookahead_min_tiles = (int)std::min<int64_t>(value, 1 << 20);
-    } else if (!strcmp(name, "pipe_start_pct")) {
-        if (value < -1 || value > 100) return fail(GP_ERR_ARG, "pipe_start_pct out of range");
-        g->pipe_start_pct = (int)value;   // -1: automatic
-    } else if (!strcmp(name, "small_below")) {
-        g->small_below = (int)value;
-    } else if (!strcmp(name, "profile_min_tiles")) {
+    for (const OptDesc &o : g_options) {
+        if (strcmp(name, o.name)) continue;
+        int rc = store_option(g, o, value);
+        if (rc) return rc;
+        // what a stored value invalidates
+        if (o.field == &gp_ctx::lauum_panels) {
+            // the factor stays, and with it invp_valid, lr_valid and predicted: only what the Ky^-1 route built is dropped
+            g->wi_valid = false;
+            g->li_valid = false;
+            g->rows_calls_since_fit = 0;
+            g->w_in_t2 = false;
+        } else if (o.field == &gp_ctx::fmin_direct) {
+            g->fmin_valid = false;
+        } else if (o.field == &gp_ctx::emulate_fp64) {
+            g->predicted = false;
+        }
+        return 0;
+    }
+    // the options that are not one int of the context
+    if (!strcmp(name, "profile_min_tiles")) {
         if (value < 0) return fail(GP_ERR_ARG, "profile_min_tiles < 0");
         g->profile_min_tiles = value;
-    } else if (!strcmp(name, "pipe_stages_grad")) {
-        if (value < 0) return fail(GP_ERR_ARG, "pipe_stages_grad < 0");
-        g->pipe_stages_grad = (int)std::min<int64_t>(value, 1 << 20);
-    } else if (!strcmp(name, "pipe_start_pct_grad")) {
-        if (value < 0 || value > 100) return fail(GP_ERR_ARG, "pipe_start_pct_grad out of range");
-        g->pipe_start_pct_grad = (int)value;
-    } else if (!strcmp(name, "pipe_stages")) {
-        if (value < 0) return fail(GP_ERR_ARG, "pipe_stages < 0");
-        g->pipe_stages = (int)std::min<int64_t>(value, 1 << 20);
-    } else if (!strcmp(name, "lauum_panels")) {
-        g->lauum_panels = (int)value;
-        g->wi_valid = false;
-        g->li_valid = false;
-        g->rows_calls_since_fit = 0;
-        g->w_in_t2 = false;
-    } else if (!strcmp(name, "side_alpha")) {
-        g->side_alpha = (int)value;
-    } else if (!strcmp(name, "pair_panels")) {
-        g->pair_panels = value ? 1 : 0;
-    } else if (!strcmp(name, "pair_tri")) {
-        g->pair_tri = (int)value;
-    } else if (!strcmp(name, "fmin_direct")) {
-        g->fmin_direct = (int)value;
-        g->fmin_valid = false;
-    } else if (!strcmp(name, "chain_small_below")) {
-        g->chain_small_below = (int)value;
-    } else if (!strcmp(name, "waves8")) {
-        g->waves8 = value ? 1 : 0;
-    } else if (!strcmp(name, "stagger")) {
-        g->stagger = (int)value;
     } else if (!strcmp(name, "supertile")) {
         if (value < 0 || value > 64) return fail(GP_ERR_ARG, "supertile out of range");
         if (g->supertile != (int)value) {   // the cached tile orders belong to the old edge
             HIPCHK(hipSetDevice(g->device));
             HIPCHK(hipDeviceSynchronize());
-            for (auto &kv : g->tile_lists) hipFree(kv.second);
             g->tile_lists.clear();
         }
         g->supertile = (int)value;
@@ -469,33 +455,14 @@ extern "C" int gp_set_option(gp_t *g, const char *name, int64_t value) {
         if (value != g->bulk_reserved)
             return fail(GP_ERR_ARG, "reserve_cus is fixed when the device's streams are created (%d); set GPHIP_RESERVE_CUS "
                                     "before the first gp_create", g->bulk_reserved);
-    } else if (!strcmp(name, "trsm_rows64")) {
-        g->trsm_rows64 = (int)value;
     } else if (!strcmp(name, "rns_interleave")) {
         rns_set_interleave((int)value);   // process-wide A/B switch of the residue GEMM's workgroup order (default 1)
-    } else if (!strcmp(name, "rns_group_fit")) {
-        if (value < 1 || value > 16) return fail(GP_ERR_ARG, "rns_group_fit must be in [1, 16]");
-        g->rns_group_fit = (int)value;
-    } else if (!strcmp(name, "rns_group")) {
-        if (value < 1 || value > 16) return fail(GP_ERR_ARG, "rns_group must be in [1, 16]");
-        g->rns_group = (int)value;
-    } else if (!strcmp(name, "emulate_fit")) {
-        g->emulate_fit = value ? 1 : 0;
-    } else if (!strcmp(name, "emulate_fp64")) {
-        g->emulate_fp64 = value ? 1 : 0;
-        g->predicted = false;
     } else if (!strcmp(name, "debug_potrf_lds")) {
         if (value < 0 || value > (1 << 20)) return fail(GP_ERR_ARG, "debug_potrf_lds out of range");
         potrf_set_debug_lds((int)value);   // process-wide test hook: forces refused diagonal-tile launches (tests/test_gpu_round4.py)
     } else if (!strcmp(name, "debug_rows_skew")) {
         // test hook: shifts the arrival base of the one-location path's next pass, so that no workgroup finishes it
         g->rows_counter_base += (unsigned int)value;
-    } else if (!strcmp(name, "rows_build")) {
-        if (value < -1 || value > 1) return fail(GP_ERR_ARG, "rows_build out of range (-1: by rule, 0: never, 1: at the first call)");
-        g->rows_build = (int)value;
-    } else if (!strcmp(name, "rows_nt")) {
-        if (value < -1 || value > 1) return fail(GP_ERR_ARG, "rows_nt out of range (-1: automatic, 0, 1)");
-        g->rows_nt = (int)value;
     } else if (!strcmp(name, "small_m")) {
         if (value < 0 || value > 8) return fail(GP_ERR_ARG, "small_m out of range (0..8)");
         g->small_m = value;
@@ -529,23 +496,20 @@ extern "C" int gp_set_data(gp_t *g, const double *X, const double *Y, int64_t N,
     GP_SYNC(g->s);
     const long Npad = round_up(N, GP_TILE);
     if (Npad > g->capN || P > g->capP || !g->dA) {
-        double **bufs[] = {&g->dX, &g->dY, &g->dA, &g->dInvL, &g->dAlpha, &g->dW, &g->dMu};
-        for (double **b : bufs) {
-            if (*b) hipFree(*b);
-            *b = nullptr;
-        }
+        for (DevBuf<double> *b : {&g->dX, &g->dY, &g->dA, &g->dInvL, &g->dAlpha, &g->dW, &g->dMu}) b->release();
         const long capN = Npad;
         const int capP = std::max(P, g->capP);
-        HIPCHK(hipMalloc((void **)&g->dX, sizeof(double) * capN * GP_MAX_D));
-        HIPCHK(hipMalloc((void **)&g->dY, sizeof(double) * capN * capP));
-        HIPCHK(hipMalloc((void **)&g->dA, sizeof(double) * (capN + GP_MAX_RHS) * capN));
-        HIPCHK(hipMalloc((void **)&g->dInvL, sizeof(double) * capN * GP_TILE));
+        int rc;
+        if ((rc = g->dX.reserve(capN * GP_MAX_D))) return rc;
+        if ((rc = g->dY.reserve(capN * capP))) return rc;
+        if ((rc = g->dA.reserve((capN + GP_MAX_RHS) * capN))) return rc;
+        if ((rc = g->dInvL.reserve(capN * GP_TILE))) return rc;
         // the diagonal-tile kernel writes the lower block triangle of each inverted tile only (potrf.hip): the blocks above
         // it are zero from here on
         HIPCHK(hipMemsetAsync(g->dInvL, 0, sizeof(double) * capN * GP_TILE, g->s));
-        HIPCHK(hipMalloc((void **)&g->dAlpha, sizeof(double) * capN * capP));
-        HIPCHK(hipMalloc((void **)&g->dW, sizeof(double) * capN * capP));
-        HIPCHK(hipMalloc((void **)&g->dMu, sizeof(double) * capN * 16));
+        if ((rc = g->dAlpha.reserve(capN * capP))) return rc;
+        if ((rc = g->dW.reserve(capN * capP))) return rc;
+        if ((rc = g->dMu.reserve(capN * 16))) return rc;
         g->capN = capN;
         g->capP = capP;
     }
@@ -557,15 +521,7 @@ extern "C" int gp_set_data(gp_t *g, const double *X, const double *Y, int64_t N,
     HIPCHK(hipMemcpyAsync(g->dY, Y, sizeof(double) * N * P, hipMemcpyHostToDevice, g->s));
     GP_SYNC(g->s);
     g->have_data = true;
-    g->fitted = false;
-    g->fmin_valid = false;
-    g->wi_valid = false;
-    g->li_valid = false;
-    g->rows_calls_since_fit = 0;
-    g->w_in_t2 = false;
-    g->invp_valid = false;
-    g->lr_valid = false;
-    g->predicted = false;
+    fit_dropped(g);
     g->kp.D = D;
     return 0;
 }
@@ -586,15 +542,7 @@ extern "C" int gp_set_gower(gp_t *g, int enable, const int *is_discrete, const d
         g->kp.gdiv[d] = is_discrete[d] ? 1.0 : range[d];
         if (!is_discrete[d] && !(range[d] > 0.0)) return fail(GP_ERR_ARG, "range of dimension %d must be positive", d);
     }
-    g->fitted = false;
-    g->fmin_valid = false;
-    g->wi_valid = false;
-    g->li_valid = false;
-    g->rows_calls_since_fit = 0;
-    g->w_in_t2 = false;
-    g->invp_valid = false;
-    g->lr_valid = false;
-    g->predicted = false;
+    fit_dropped(g);
     return 0;
 }
 
@@ -610,26 +558,7 @@ extern "C" int gp_set_params(gp_t *g, int kernel, int ard, double variance, cons
     g->ard = ard ? 1 : 0;
     g->noise = noise;
     g->have_params = true;
-    g->fitted = false;
-    g->fmin_valid = false;
-    g->wi_valid = false;
-    g->li_valid = false;
-    g->rows_calls_since_fit = 0;
-    g->w_in_t2 = false;
-    g->invp_valid = false;
-    g->lr_valid = false;
-    g->predicted = false;
-    return 0;
-}
-
-int byte_realloc(signed char **p, long *cap, long need) {
-    if (need <= *cap && *p) return 0;
-    if (*p) hipFree(*p);
-    *p = nullptr;
-    *cap = 0;
-    hipError_t e = hipMalloc((void **)p, (size_t)need);
-    if (e != hipSuccess) return fail(GP_ERR_HIP, "hipMalloc(%ld bytes) -> %s", need, hipGetErrorString(e));
-    *cap = need;
+    fit_dropped(g);
     return 0;
 }
 
@@ -712,14 +641,8 @@ extern "C" int gp_kernel_matrix(gp_t *g, double *K) {
     GP_SYNC(g->s);
     HIPCHK(hipMemcpy2D(K, sizeof(double) * N, g->dA, sizeof(double) * g->Npad, sizeof(double) * N, N,
                        hipMemcpyDeviceToHost));
-    g->fitted = false;  // dA was overwritten
-    g->wi_valid = false;
-    g->li_valid = false;
-    g->rows_calls_since_fit = 0;
-    g->w_in_t2 = false;
-    g->invp_valid = false;
-    g->lr_valid = false;
-    g->predicted = false;
+    factor_results_dropped(g);
+    g->fitted = false;  // dA was overwritten; fmin_valid is left alone -- fmin was taken from dY and dAlpha, which still hold what they did
     return 0;
 }
 
@@ -733,8 +656,8 @@ extern "C" int gp_cross_kernel_matrix(gp_t *g, const double *X2, int64_t M2, dou
     HIPCHK(hipSetDevice(g->device));
     const long N = g->N, Npad = g->Npad, M2pad = round_up(M2, GP_TILE);
     int rc;
-    if ((rc = dev_realloc(&g->dX2, &g->capX2, (long)M2 * g->D))) return rc;
-    if ((rc = dev_realloc(&g->dK2, &g->capK2, Npad * M2pad))) return rc;
+    if ((rc = g->dX2.reserve((long)M2 * g->D))) return rc;
+    if ((rc = g->dK2.reserve(Npad * M2pad))) return rc;
     HIPCHK(hipMemcpyAsync(g->dX2, X2, sizeof(double) * M2 * g->D, hipMemcpyHostToDevice, g->s));
     launch_cross_k(g->s, g->dK2, M2pad, g->dX, N, Npad, g->dX2, M2, M2pad, g->kp);
     GP_SYNC(g->s);

@@ -86,8 +86,8 @@ int factor(gp_ctx *g) {
         const long PB = (long)W * GP_TILE;
         const int nJ = (nt + W - 1) / W;
         int rc;
-        if ((rc = dev_realloc(&g->dInvP, &g->capInvP, (long)nJ * PB * PB))) return rc;
-        if ((rc = dev_realloc(&g->dInvPw, &g->capInvPw, (long)nJ * PB * PB))) return rc;
+        if ((rc = g->dInvP.reserve((long)nJ * PB * PB))) return rc;
+        if ((rc = g->dInvPw.reserve((long)nJ * PB * PB))) return rc;
     }
     factor_buf(g, ctx_members(g), nt, nt + 1, side);
     if (side) {
@@ -117,8 +117,8 @@ int factor_lookahead(gp_ctx *g, const PredPipe &pp) {
     // Every inverted diagonal panel (alpha, the candidate solve and Ky^-1 all need them) is built on the side stream as soon
     // as its panel of L is final, beside the rest of the factorisation: after the join nothing is left to build (as a pass of
     // its own, 2W - 1 short launches in series, it held the main stream for 0.3 ms between the factor and its first consumer).
-    if ((rc = dev_realloc(&g->dInvP, &g->capInvP, (long)nJu * PB * PB))) return rc;
-    if ((rc = dev_realloc(&g->dInvPw, &g->capInvPw, (long)nJu * PB * PB))) return rc;
+    if ((rc = g->dInvP.reserve((long)nJu * PB * PB))) return rc;
+    if ((rc = g->dInvPw.reserve((long)nJu * PB * PB))) return rc;
     GP_NOTE(hipStreamWaitEvent(g->s_inv, e0, 0));
     if (pp.on) {
         GP_NOTE(hipStreamWaitEvent(g->s_pred, e0, 0));
@@ -146,7 +146,7 @@ int factor_lookahead(gp_ctx *g, const PredPipe &pp) {
     if (emu) {
         if ((rc = rns_prepare(g, g->jitter_try, &rg))) return rc;
         const long need = (long)GP_RNS_T * rg.nt256 * rg.nt256 * 65536;
-        if ((rc = byte_realloc(&g->dRm, &g->capRm, need))) return rc;
+        if ((rc = g->dRm.reserve(need))) return rc;
     }
     // emulated: panels per residue launch (the far launches ride on the otherwise idle candidate stream)
     const int Gf = (emu && !pp.on) ? std::max(1, std::min(g->rns_group_fit, (int)(GP_RNS_KMAX / PB))) : 1;
@@ -415,11 +415,11 @@ int fit_impl(gp_ctx *g, int maxtries, int pipe, int include_noise) {
         const long PB = (long)W * GP_TILE;
         const int nJ = (nt_ + W - 1) / W;
         if (pipe == 1 && (rc = ensure_out(g))) return rc;
-        if ((rc = dev_realloc(&g->dT, &g->capT, mcpad * Npad))) return rc;
-        if ((rc = dev_realloc(&g->dT2, &g->capT2, mcpad * Npad))) return rc;
-        if (pipe == 2 && (rc = dev_realloc(&g->dWi, &g->capWi, Npad * Npad))) return rc;
-        if ((rc = dev_realloc(&g->dInvP, &g->capInvP, (long)nJ * PB * PB))) return rc;
-        if ((rc = dev_realloc(&g->dInvPw, &g->capInvPw, (long)nJ * PB * PB))) return rc;
+        if ((rc = g->dT.reserve(mcpad * Npad))) return rc;
+        if ((rc = g->dT2.reserve(mcpad * Npad))) return rc;
+        if (pipe == 2 && (rc = g->dWi.reserve(Npad * Npad))) return rc;
+        if ((rc = g->dInvP.reserve((long)nJ * PB * PB))) return rc;
+        if ((rc = g->dInvPw.reserve((long)nJ * PB * PB))) return rc;
         pp.on = true;
         pp.mt = (int)(mcpad / GP_TILE);
         pp.T = g->dT;
@@ -434,15 +434,7 @@ int fit_impl(gp_ctx *g, int maxtries, int pipe, int include_noise) {
     ky_diag(g->kp, g->noise, &diag_add, &diag0);
     g->nphases = 0;
     g->emu_off_call = false;
-    g->fitted = false;
-    g->fmin_valid = false;
-    g->wi_valid = false;
-    g->li_valid = false;
-    g->rows_calls_since_fit = 0;
-    g->w_in_t2 = false;
-    g->invp_valid = false;
-    g->lr_valid = false;
-    g->predicted = false;
+    fit_dropped(g);
 
     double jitter = 0.0;
     int tries = 0;  // number of jittered attempts so far

@@ -76,19 +76,13 @@ extern "C" int gp_fit_grad(gp_t *g, int maxtries, double *lml, double *logdet, d
 // ---- second candidate-sized buffer (beta = K(Xs,X) Ky^-1, or the full covariance) -----------------
 int ensure_grad_buffers(gp_ctx *g, long elemsBeta, long M) {
     int rc;
-    if ((rc = dev_realloc(&g->dCov, &g->capCov, elemsBeta))) return rc;
+    if ((rc = g->dCov.reserve(elemsBeta))) return rc;
     const long need = M * (long)g->D * std::max(1, g->P);
-    if (!g->dDm || g->capD < need) {
-        for (double **b : {&g->dDm, &g->dDv, &g->dDacq}) {
-            if (*b) hipFree(*b);
-            *b = nullptr;
-        }
-        HIPCHK(hipMalloc((void **)&g->dDm, sizeof(double) * need));
-        HIPCHK(hipMalloc((void **)&g->dDv, sizeof(double) * need));
-        HIPCHK(hipMalloc((void **)&g->dDacq, sizeof(double) * need));
-        g->capD = need;
-    }
-    return 0;
+    if (g->dDacq.cap >= need) return 0;   // the last of the three to be allocated: all are there, at one capacity
+    for (DevBuf<double> *b : {&g->dDm, &g->dDv, &g->dDacq}) b->release();
+    if ((rc = g->dDm.reserve(need))) return rc;
+    if ((rc = g->dDv.reserve(need))) return rc;
+    return g->dDacq.reserve(need);
 }
 
 // predictive gradients of all resident candidates into dDm [M, D, P] and dDv [M, D]
@@ -108,9 +102,9 @@ int run_predict_grad(gp_ctx *g) {
         const long M = g->M, N = g->N, Npad = g->Npad;
         if ((rc = ensure_panel_inv(g))) return rc;
         if ((rc = ensure_out(g))) return rc;
-        if ((rc = dev_realloc(&g->dT, &g->capT, std::max(g->capT, (long)GP_TILE * Npad)))) return rc;
-        if ((rc = dev_realloc(&g->dT2, &g->capT2, std::max(g->capT2, (long)GP_TILE * Npad)))) return rc;
-        if ((rc = ensure_grad_buffers(g, std::max(g->capCov, (long)GP_TILE * Npad), M))) return rc;
+        if ((rc = g->dT.reserve((long)GP_TILE * Npad))) return rc;
+        if ((rc = g->dT2.reserve((long)GP_TILE * Npad))) return rc;
+        if ((rc = ensure_grad_buffers(g, (long)GP_TILE * Npad, M))) return rc;
         g->w_in_t2 = false;
         launch_cross_k_rows(g->s, g->dT, Npad, g->dXs, (int)M, g->dX, N, Npad, g->kp);
         launch_small_forward_solve(g->s, g->dA, Npad, g->dInvP, g->invp_W, Npad, g->dT, g->dT2, Npad, (int)M);   // dT2 = w rows
@@ -126,7 +120,7 @@ int run_predict_grad(gp_ctx *g) {
     const long M = g->M, N = g->N, Npad = g->Npad;
     const int nt = (int)(Npad / GP_TILE);
     const long mc_max = std::min(g->mc_max, round_up(M, GP_TILE));
-    if ((rc = dev_realloc(&g->dT, &g->capT, std::max(g->capT, mc_max * Npad)))) return rc;
+    if ((rc = g->dT.reserve(mc_max * Npad))) return rc;
     if ((rc = ensure_grad_buffers(g, mc_max * Npad, M))) return rc;
     for (long m0 = 0; m0 < M; m0 += mc_max) {
         const long mc = std::min(mc_max, M - m0);
@@ -158,7 +152,7 @@ extern "C" int gp_predict_grad(gp_t *g, double *dmdx, double *dvdx) {
         // neither Ky^-1 nor K(X*, X) Ky^-1 -- one pass of O(M N D) instead of 2 N^3 / 3 + N^2 M flops
         if (!g->fitted) return fail(GP_ERR_STATE, "gp_fit first");
         if (g->M < 1) return fail(GP_ERR_STATE, "gp_set_candidates first");
-        if ((rc = ensure_grad_buffers(g, std::max<long>(g->capCov, 1), g->M))) return rc;
+        if ((rc = ensure_grad_buffers(g, 1, g->M))) return rc;
         launch_predict_grad(g->s, g->dXs, g->M, g->dX, g->N, g->kp, g->dAlpha, g->Npad, g->P, nullptr, 0, g->dDm, g->dDv);
         HIPCHK(hipMemcpyAsync(dmdx, g->dDm, sizeof(double) * g->M * g->D * g->P, hipMemcpyDeviceToHost, g->s));
         GP_SYNC(g->s);

@@ -270,7 +270,7 @@ static int group_allgather(gp_group *grp, int k, const std::vector<double> &v, c
         gp_ctx *g = grp->m[i];
         HIPCHK(hipSetDevice(g->device));
         int rc;
-        if ((rc = dev_realloc(&g->dComm, &g->capComm, 2L * GP_TOPK_MAX * (1 + 128)))) return rc;
+        if ((rc = g->dComm.reserve(2L * GP_TOPK_MAX * (1 + 128)))) return rc;
         for (int j = 0; j < k; ++j) {
             rec[i][2 * j] = v[(size_t)i * k + j];
             memcpy(&rec[i][2 * j + 1], &ix[(size_t)i * k + j], 8);

@@ -19,6 +19,7 @@
 #include <mutex>
 #include <set>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 extern thread_local std::string g_err;
@@ -61,6 +62,39 @@ struct Phase {
 };
 #define MAX_PHASES 16
 
+// One device allocation and its owner.  reserve(n) only ever grows: a no-op while n elements fit, otherwise the old block is
+// freed and exactly n elements are allocated -- the contents are NOT kept.  Converts to T * where a launch takes the pointer.
+// A buffer that was never reserved makes no HIP call, so a gp_ctx without a device behind it can be built and dropped.
+template <class T>
+struct DevBuf {
+    T *p = nullptr;
+    long cap = 0;   // elements
+    DevBuf() = default;
+    DevBuf(DevBuf &&o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    ~DevBuf() { release(); }
+    operator T *() const { return p; }
+    void release() {
+        if (p) (void)hipFree(p);
+        p = nullptr;
+        cap = 0;
+    }
+    hipError_t alloc(long n) {   // release, then exactly n elements; null and 0 when that fails
+        release();
+        const hipError_t e = hipMalloc((void **)&p, (size_t)n * sizeof(T));
+        if (e == hipSuccess) cap = n; else p = nullptr;
+        return e;
+    }
+    int reserve(long n) { return (n <= cap && p) ? 0 : grow(n); }   // the fast path of the ~40 us *_rows calls stays inline
+    __attribute__((noinline)) int grow(long n) {
+        const hipError_t e = alloc(n);
+        if (e == hipSuccess) return 0;
+        return std::is_same<T, double>::value ? fail(GP_ERR_HIP, "hipMalloc(%ld doubles) -> %s", n, hipGetErrorString(e))
+                                              : fail(GP_ERR_HIP, "hipMalloc(%ld bytes) -> %s", n * (long)sizeof(T), hipGetErrorString(e));
+    }
+};
+
 struct gp_ctx {
     int device = 0;
     hipStream_t s = nullptr;       // main stream
@@ -71,76 +105,67 @@ struct gp_ctx {
     // stream-ordering events of the look-ahead factorisation, one dense vector per role (EV_* below)
     std::vector<hipEvent_t> la_events[6];
     bool ev_error = false;         // a stream-ordering event could not be created (la_event); checked by la_events_ok
-    // data
+    // data: the seven buffers of gp_set_data share the capacity (capN rows, capP right-hand sides) and reallocate together
     long N = 0, Npad = 0;
     int D = 0, P = 0;
-    double *dX = nullptr, *dY = nullptr;
-    double *dA = nullptr;     // (Npad + 128) x Npad: Ky / L (lower) and, below it, the RHS rows (Y^T -> z^T)
-    double *dInvL = nullptr;  // nt tiles of 128 x 128: inverted diagonal tiles of L
-    double *dAlpha = nullptr; // P x Npad
-    double *dW = nullptr;     // P x Npad workspace
-    double *dMu = nullptr;    // (1 + TM_SPLIT) * N : training mean + partials
-    int *dInfo = nullptr;
-    double *dScal = nullptr;  // small scalars: [0] logdet, [8..8+P) sumsq / dot
-    double *dRedV = nullptr;  // 512 doubles of reduction scratch
-    long long *dRedI = nullptr;
+    DevBuf<double> dX, dY;
+    DevBuf<double> dA;     // (Npad + 128) x Npad: Ky / L (lower) and, below it, the RHS rows (Y^T -> z^T)
+    DevBuf<double> dInvL;  // nt tiles of 128 x 128: inverted diagonal tiles of L
+    DevBuf<double> dAlpha; // P x Npad
+    DevBuf<double> dW;     // P x Npad workspace
+    DevBuf<double> dMu;    // (1 + TM_SPLIT) * N : training mean + partials
+    DevBuf<int> dInfo;
+    DevBuf<double> dScal;  // small scalars: [0] logdet, [8..8+P) sumsq / dot
+    DevBuf<double> dRedV;  // 512 doubles of reduction scratch
+    DevBuf<long long> dRedI;
     long capN = 0;
     int capP = 0;
     // params
     KernParams kp{};
     int ard = 0;
     double noise = 0.0;
-    bool have_data = false, have_params = false, fitted = false;
+    bool have_data = false, have_params = false;
     double jitter = 0.0, lml = 0.0, logdet = 0.0;
-    bool fmin_valid = false;
     double fmin = 0.0;
+    // What the buffers hold.  A new factor in dA drops every one of these (factor_results_dropped, fit_dropped below); between
+    // factors each is set where its buffer is filled and cleared where the buffer is reused for something else.
+    bool fitted = false;       // dA holds L of the current data and parameters, dAlpha its alpha, lml / logdet / jitter belong to it
+    bool fmin_valid = false;   // fmin is min over the training mean of the current fit
+    bool wi_valid = false;     // dWi holds Ky^-1 of the factor
+    bool li_valid = false;     // dLi holds L^-1 of the factor
+    long rows_calls_since_fit = 0;   // *_rows calls that wanted the inverse factor since the last fit (build policy, api_rows.hip)
+    bool w_in_t2 = false;      // dT2 still holds W = L^-T of the current factor (ensure_linv / ensure_wi)
+    bool invp_valid = false;   // dInvP holds the inverted diagonal panels of the factor, invp_W tiles wide
+    bool lr_valid = false;     // dLr belongs to the current factor
+    bool predicted = false;    // dMean / dVar hold the posterior of the resident candidates (noise as predicted_noise), dT / dT2 what its solve left
     // candidates
     long M = 0;
-    double *dXs = nullptr;
-    long capM = 0;
-    double *dT = nullptr;  // Mc_pad x Npad
-    long capT = 0;         // elements
-    double *dMean = nullptr, *dVar = nullptr, *dAcq = nullptr;
-    long capOut = 0;
-    bool predicted = false;
+    DevBuf<double> dXs;
+    DevBuf<double> dT;     // Mc_pad x Npad
+    DevBuf<double> dMean, dVar, dAcq;   // one capacity: the three reallocate together (ensure_out)
     int predicted_noise = -1;
-    // Wi
-    double *dWi = nullptr;
-    long capWi = 0;
-    bool wi_valid = false;
-    double *dT2 = nullptr;   // solved candidate rows S = K(Xs,X) L^-T (the running right-hand side stays in dT)
-    long capT2 = 0;
-    bool w_in_t2 = false;    // dT2 still holds W = L^-T of the current factor (ensure_linv / ensure_wi)
+    DevBuf<double> dWi;
+    DevBuf<double> dT2;    // solved candidate rows S = K(Xs,X) L^-T (the running right-hand side stays in dT)
     // the explicit inverse factor and the scratch of the fused one-row path (onerow.hip, api_rows.hip)
-    double *dLi = nullptr;   // L^-1, lower triangular, Npad x Npad row-major, zeros above the diagonal
-    long capLi = 0;
-    bool li_valid = false;
-    double *dRows = nullptr; // RowsWork partials
-    long capRows = 0;
-    unsigned int *dRowsCounter = nullptr;
+    DevBuf<double> dLi;    // L^-1, lower triangular, Npad x Npad row-major, zeros above the diagonal
+    DevBuf<double> dRows;  // RowsWork partials
+    DevBuf<unsigned int> dRowsCounter;
     double *hRowsOut = nullptr;          // pinned, device-visible result block of the fused path (+ the ticket behind it)
     double rows_ticket = 0.0;            // counts the fused passes; the finishing workgroup writes it back
     unsigned int rows_counter_base = 0;  // arrivals the counter holds from the passes before this one
     std::vector<double> lp_cache;        // local-penalisation batch as last uploaded (Xb | r | s), skipped when unchanged
     int lp_cache_nb = -1;
     long rows_fused_calls = 0, rows_fallback_calls = 0;
-    long rows_calls_since_fit = 0;       // *_rows calls that wanted the inverse factor since the last fit (build policy, api_rows.hip)
     int rows_build = -1;                 // inverse factor of the one-location path: -1 by the rule of api_rows.hip, 0 never, 1 at the first call (option "rows_build")
     int rows_nt = -1;                    // fused one-row path: non-temporal loads of the inverse factor (option "rows_nt"; -1: when its
                                          // lower triangle exceeds the 256 MiB Infinity Cache, N > 8192 -- measured -10 % at N = 16384,
                                          // +10 % at N = 4096 where the next call finds the factor cached: profiles/r05_small_calls.txt)
-    double *dLp = nullptr;   // local-penalisation batch (centres, radii, scales)
-    double *dX2 = nullptr, *dK2 = nullptr;  // gp_cross_kernel_matrix: second input set and K(X, X2)
-    long capX2 = 0, capK2 = 0;
-    long capLp = 0;
-    double *dCov = nullptr;  // full covariance / beta scratch
-    long capCov = 0;
-    double *dInvP = nullptr, *dInvPw = nullptr;  // inverted diagonal panels L_JJ^-1 (+ build workspace)
-    long capInvP = 0, capInvPw = 0;
+    DevBuf<double> dLp;    // local-penalisation batch (centres, radii, scales)
+    DevBuf<double> dX2, dK2;  // gp_cross_kernel_matrix: second input set and K(X, X2)
+    DevBuf<double> dCov;   // full covariance / beta scratch
+    DevBuf<double> dInvP, dInvPw;  // inverted diagonal panels L_JJ^-1 (+ build workspace)
     int invp_W = 0;
-    bool invp_valid = false;
-    double *dDm = nullptr, *dDv = nullptr, *dDacq = nullptr;
-    long capD = 0;
+    DevBuf<double> dDm, dDv, dDacq;   // one capacity: the three reallocate together (ensure_grad_buffers)
     // options
     int panel_tiles = 6;
     int lookahead = 1;
@@ -167,7 +192,7 @@ struct gp_ctx {
     size_t rns_ev_used = 0;
     double rns_ops = 0.0;                 // int8 multiply-adds x 2 of those launches
     std::vector<long> gemm_tiles;
-    std::map<std::array<int, 5>, short *> tile_lists;  // cached L2-friendly tile orders (device)
+    std::map<std::array<int, 5>, DevBuf<short>> tile_lists;  // cached L2-friendly tile orders (device)
     int supertile = 8;  // long rectangular / triangular launches walk 8 x 8 super-tiles per XCD (fabric traffic 5.35 -> 3.72 GB per launch, same time)
     int small_below = 1400;  // launches with fewer 128-tiles than this use 64x64 workgroup tiles
     int chain_small_below = 400;  // ... the same threshold for the launches of the factorisation's chain stream
@@ -192,31 +217,42 @@ struct gp_ctx {
     // comm
     ncclComm_t comm = nullptr;
     int rank = 0, nranks = 1;
-    double *dComm = nullptr;  // gather scratch of the top-k exchange
-    long capComm = 0;
+    DevBuf<double> dComm;  // gather scratch of the top-k exchange
     // fp64 emulation on the int8 matrix cores (rns.hip)
     int emulate_fp64 = 0;
     int rns_group = 8; // panels per residue launch of the emulated candidate solve
     int rns_group_fit = 8;  // ... and of the emulated trailing update of the factorisation
-    signed char *dLr = nullptr, *dSr = nullptr, *dRr = nullptr;  // residue planes of L, of the current S panel, accumulator
-    signed char *dRm = nullptr;                                   // residue accumulator of the trailing matrix (factorisation)
-    signed char *dWr = nullptr;                                   // residue planes of W = L^-T (emulated Ky^-1)
-    long capWr = 0;
-    long capLr = 0, capSr = 0, capRr = 0, capRm = 0;
-    bool lr_valid = false;          // dLr belongs to the current factor
-    std::vector<char> lr_done;      // ... per panel: rows below the panel's diagonal block converted
+    DevBuf<signed char> dLr, dSr, dRr;  // residue planes of L, of the current S panel, accumulator
+    DevBuf<signed char> dRm;            // residue accumulator of the trailing matrix (factorisation)
+    DevBuf<signed char> dWr;            // residue planes of W = L^-T (emulated Ky^-1)
+    std::vector<char> lr_done;      // dLr, per panel: rows below the panel's diagonal block converted
     int lr_W = 0, lr_e = 0;
     double jitter_try = 0.0;        // jitter of the factorisation attempt in progress (fixes the fixed-point scale)
     int emulate_fit = 1;            // emulate_fp64 also covers the factorisation's trailing update
     bool emu_off_call = false;      // this call fell back to true fp64 (an operand left the fixed-point range)
     long emu_fallbacks = 0;         // how often that happened
     // gp_fit_grad_batch (api_batch.hip): buffers of its own, sized to the R and Npad in use -- never the resident fit's
-    double *dBatch = nullptr;
-    long capBatch = 0;
-    signed char *dBatchAux = nullptr;   // per-member KernParams table, then factorisation status words
-    long capBatchAux = 0;
+    DevBuf<double> dBatch;
+    DevBuf<signed char> dBatchAux;   // per-member KernParams table, then factorisation status words
     bool dead = false;  // gp_shutdown ran: the device's streams are gone, only gp_destroy is still valid
 };
+
+// A new factor is about to be (or has been) written to dA: nothing derived from the old one may be served again.
+static inline void factor_results_dropped(gp_ctx *g) {
+    g->wi_valid = false;
+    g->li_valid = false;
+    g->rows_calls_since_fit = 0;
+    g->w_in_t2 = false;
+    g->invp_valid = false;
+    g->lr_valid = false;
+    g->predicted = false;
+}
+// ... and dA no longer holds a fit of the current data and parameters at all.
+static inline void fit_dropped(gp_ctx *g) {
+    factor_results_dropped(g);
+    g->fitted = false;
+    g->fmin_valid = false;
+}
 
 static inline long round_up(long x, long m) { return (x + m - 1) / m * m; }
 
@@ -328,7 +364,6 @@ int phase_begin(gp_ctx *g, const char *name, double flops, double bytes);
 void phase_end(gp_ctx *g, int id);
 void gemm(gp_ctx *g, hipStream_t s, int mode, double *C, long ldc, const double *A, long lda, const double *B, long ldb, int b_mul, int K, TileSet ts, const GemmOpt &o = GemmOpt());
 void rns_gemm(gp_ctx *g, hipStream_t s, const signed char *A, long lda, long a_plane, const signed char *B, long ldb, long b_plane, signed char *R, int mt_all, int nt_all, int mt, int c0, int c1, int K, int first, int tri = 0);
-int dev_realloc(double **p, long *cap, long need);
 void destroy_ctx_events(gp_ctx *g);
 void build_ky(gp_ctx *g, const Members &m, bool jittered);
 void factor_buf(gp_ctx *g, const Members &m, int nt, int R1, bool side_inv = false);
@@ -338,7 +373,6 @@ void ky_diag(const KernParams &kp, double noise, double *diag_add, double *diag0
 int ladder_step(double diag0, int maxtries, int info, double *jitter, int *tries);
 double lml_from_scalars(long N, int P, const double *scal);
 void build_panel_inv_one(gp_ctx *g, hipStream_t s, int J, int W, int nt);
-int byte_realloc(signed char **p, long *cap, long need);
 int rns_prepare(gp_ctx *g, double jitter, RnsGeom *r);
 void rns_convert_panel(gp_ctx *g, hipStream_t s, const RnsGeom &r, int J, int *flag);
 int factor_lookahead(gp_ctx *g, const PredPipe &pp = PredPipe());

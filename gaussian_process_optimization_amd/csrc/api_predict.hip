@@ -11,7 +11,7 @@ extern "C" int gp_set_candidates(gp_t *g, const double *Xs, int64_t M) {
     HIPCHK(hipSetDevice(g->device));
     GP_SYNC(g->s);
     int rc;
-    if ((rc = dev_realloc(&g->dXs, &g->capM, (long)M * g->D))) return rc;
+    if ((rc = g->dXs.reserve((long)M * g->D))) return rc;
     HIPCHK(hipMemcpy(g->dXs, Xs, sizeof(double) * M * g->D, hipMemcpyHostToDevice));
     g->M = M;
     g->predicted = false;
@@ -28,8 +28,8 @@ int run_predict(gp_ctx *g, int include_noise, bool tiles_only) {
     g->nphases = 0;
     const long mc_max = std::min(g->mc_max, round_up(M, GP_TILE));
     if ((rc = ensure_panel_inv(g))) return rc;
-    if ((rc = dev_realloc(&g->dT, &g->capT, mc_max * Npad))) return rc;
-    if ((rc = dev_realloc(&g->dT2, &g->capT2, mc_max * Npad))) return rc;
+    if ((rc = g->dT.reserve(mc_max * Npad))) return rc;
+    if ((rc = g->dT2.reserve(mc_max * Npad))) return rc;
     g->w_in_t2 = false;   // dT2 takes the solved candidate rows
     if (M <= g->small_m && !tiles_only) {
         // A handful of rows (the acquisition optimiser's one-row calls): the solve as matrix-vector work bound by ONE read of
@@ -80,16 +80,12 @@ int run_predict(gp_ctx *g, int include_noise, bool tiles_only) {
 
 int ensure_out(gp_ctx *g) {
     const long need = g->M * (long)std::max(1, g->P);
-    if (g->dMean && g->dVar && g->dAcq && g->capOut >= need) return 0;
-    for (double **b : {&g->dMean, &g->dVar, &g->dAcq}) {
-        if (*b) hipFree(*b);
-        *b = nullptr;
-    }
-    HIPCHK(hipMalloc((void **)&g->dMean, sizeof(double) * need));
-    HIPCHK(hipMalloc((void **)&g->dVar, sizeof(double) * need));
-    HIPCHK(hipMalloc((void **)&g->dAcq, sizeof(double) * need));
-    g->capOut = need;
-    return 0;
+    if (g->dAcq.cap >= need) return 0;   // the last of the three to be allocated: all are there, at one capacity
+    for (DevBuf<double> *b : {&g->dMean, &g->dVar, &g->dAcq}) b->release();
+    int rc;
+    if ((rc = g->dMean.reserve(need))) return rc;
+    if ((rc = g->dVar.reserve(need))) return rc;
+    return g->dAcq.reserve(need);
 }
 
 extern "C" int gp_predict(gp_t *g, int include_noise, double *mean, double *var) {
@@ -180,7 +176,7 @@ int upload_lp_batch(gp_ctx *g, const double *Xb, int nb, const double *r0, const
     if (nb < 0 || nb > 256) return fail(GP_ERR_ARG, "batch size out of range (0..256)");
     g->lp_cache_nb = -1;   // (api_rows.hip keeps the last batch it uploaded; this upload replaces it)
     int rc;
-    if ((rc = dev_realloc(&g->dLp, &g->capLp, (long)256 * (GP_MAX_D + 2)))) return rc;
+    if ((rc = g->dLp.reserve((long)256 * (GP_MAX_D + 2)))) return rc;
     b->X = g->dLp;
     b->r = g->dLp + 256 * GP_MAX_D;
     b->s = b->r + 256;
@@ -257,7 +253,7 @@ extern "C" int gp_predict_full_cov(gp_t *g, int include_noise, double *mean, dou
     int rc;
     if ((rc = ensure_out(g))) return rc;
     if ((rc = run_predict(g, include_noise, true))) return rc;  // leaves S = K(Xs,X) L^-T in dT2 (single chunk, zero padding rows: tile path)
-    if ((rc = dev_realloc(&g->dCov, &g->capCov, std::max(g->capCov, Mpad * Mpad)))) return rc;
+    if ((rc = g->dCov.reserve(Mpad * Mpad))) return rc;
     const int mt = (int)(Mpad / GP_TILE);
     launch_kbuild(g->s, g->dCov, Mpad, g->dXs, M, Mpad, g->kp, 0.0, 1);  // K(Xs, Xs)
     gemm(g, g->s, 1, g->dCov, Mpad, g->dT2, Npad, g->dT2, Npad, 1, (int)Npad, TileSet{0, mt, 0, mt, 0});
@@ -283,7 +279,7 @@ extern "C" int gp_acq_topk(gp_t *g, int type, double par, double fmin, double y_
     HIPCHK(hipSetDevice(g->device));
     int rc;
     if ((rc = run_acq(g, type, par, fmin, y_mean, y_std))) return rc;
-    if ((rc = dev_realloc(&g->dComm, &g->capComm, 2L * GP_TOPK_MAX * (1 + 128)))) return rc;
+    if ((rc = g->dComm.reserve(2L * GP_TOPK_MAX * (1 + 128)))) return rc;
     double *dv = g->dComm;
     long long *di = (long long *)(g->dComm + GP_TOPK_MAX);
     const int kk = (int)std::min<long>(k, g->M);
@@ -325,7 +321,7 @@ extern "C" int gp_posterior_samples(gp_t *g, int include_noise, const double *Z,
     if ((rc = ensure_out(g))) return rc;
     if ((rc = run_predict(g, include_noise, true))) return rc;  // S_c = K(Xs,X) L^-T in dT2 (single chunk, zero padding rows: tile path), mean in dMean
     // dCov: [cov Mpad x Mpad][Z^T Spad x Mpad][dev Spad x Mpad]; the inverted diagonal tiles go to dT (free now)
-    if ((rc = dev_realloc(&g->dCov, &g->capCov, std::max(g->capCov, Mpad * Mpad + 2 * Spad * Mpad)))) return rc;
+    if ((rc = g->dCov.reserve(Mpad * Mpad + 2 * Spad * Mpad))) return rc;
     double *C = g->dCov, *Zd = g->dCov + Mpad * Mpad, *Dv = Zd + Spad * Mpad;
     double *invL = g->dT;
     const int mt = (int)(Mpad / GP_TILE), st = (int)(Spad / GP_TILE);

@@ -46,8 +46,8 @@ int rns_prepare(gp_ctx *g, double jitter, RnsGeom *r) {
     r->scale = std::ldexp(1.0, 52 - e);
     r->back = std::ldexp(1.0, 2 * e);
     const long need = (long)GP_RNS_T * r->Lplane;
-    if (need > g->capLr || !g->dLr) {
-        int rc = byte_realloc(&g->dLr, &g->capLr, need);
+    if (need > g->dLr.cap || !g->dLr) {
+        int rc = g->dLr.reserve(need);
         if (rc) return rc;
         HIPCHK(hipMemsetAsync(g->dLr, 0, (size_t)need, g->s));
         GP_SYNC(g->s);
@@ -97,16 +97,16 @@ int solve_rows_rns(gp_ctx *g, double *T, double *S, int mt, const RnsSolveOpt &o
     if (W % 2) G = 1;
     const bool keep = opt.Wr != nullptr;
     const long KS = keep ? opt.wpitch : G * PB;   // row pitch of the S planes
-    auto zalloc = [&](signed char **p, long *cap, long need) -> int {
-        if (need <= *cap && *p) return 0;
-        int r2 = byte_realloc(p, cap, need);
+    auto zalloc = [&](DevBuf<signed char> &b, long need) -> int {
+        if (need <= b.cap && b) return 0;
+        int r2 = b.reserve(need);
         if (r2) return r2;
-        if (hipMemsetAsync(*p, 0, (size_t)need, g->s) != hipSuccess) return fail(GP_ERR_HIP, "hipMemsetAsync");
+        if (hipMemsetAsync(b, 0, (size_t)need, g->s) != hipSuccess) return fail(GP_ERR_HIP, "hipMemsetAsync");
         return 0;
     };
     if (PB > GP_RNS_KMAX) return fail(GP_ERR_ARG, "emulate_fp64: panel_tiles too wide for one residue contraction");
-    if (!keep && (rc = zalloc(&g->dSr, &g->capSr, (long)GP_RNS_T * Mc256 * KS))) return rc;
-    if ((rc = zalloc(&g->dRr, &g->capRr, (long)GP_RNS_T * mt256 * nt256 * 65536))) return rc;
+    if (!keep && (rc = zalloc(g->dSr, (long)GP_RNS_T * Mc256 * KS))) return rc;
+    if ((rc = zalloc(g->dRr, (long)GP_RNS_T * mt256 * nt256 * 65536))) return rc;
     hipStream_t s = g->s;
     int *flag = g->dInfo + 2;
     HIPCHK(hipMemsetAsync(flag, 0, sizeof(int), s));
@@ -194,7 +194,7 @@ int wi_rns(gp_ctx *g) {
     if (!(lam > 0.0)) return GP_ERR_RANGE;
     const int eS = std::max(0, 1 + (int)std::ceil(std::log2(1.0 / std::sqrt(lam))));
     const long wpitch = Npad, wrows = (long)nt256 * 256, wplane = wrows * wpitch;
-    if ((rc = byte_realloc(&g->dWr, &g->capWr, (long)GP_RNS_T * wplane))) return rc;
+    if ((rc = g->dWr.reserve((long)GP_RNS_T * wplane))) return rc;
     HIPCHK(hipMemsetAsync(g->dWr, 0, (size_t)GP_RNS_T * wplane, s));
     int ph = phase_begin(g, "potri_solve_emulated", (double)g->N * g->N * g->N / 3.0, 0.0);
     launch_set_identity(s, g->dT, Npad, Npad);

@@ -30,14 +30,14 @@ static int rows_scratch(gp_ctx *g, RowsWork *w) {
     const long n_w = nch * ROWS_MAX_M * Npad, n_b = nrb * ROWS_MAX_M * Npad, n_m = nch * ROWS_MAX_M, n_v = nrb * ROWS_MAX_M;
     const long n_g = (long)rows_gpart_elems(g->N);
     int rc;
-    if ((rc = dev_realloc(&g->dRows, &g->capRows, n_w + n_b + n_m + n_v + n_g))) return rc;
+    if ((rc = g->dRows.reserve(n_w + n_b + n_m + n_v + n_g))) return rc;
     w->wpart = g->dRows;
     w->bpart = w->wpart + n_w;
     w->meanpart = w->bpart + n_b;
     w->vpart = w->meanpart + n_m;
     w->gpart = w->vpart + n_v;
     if (!g->dRowsCounter) {
-        HIPCHK(hipMalloc((void **)&g->dRowsCounter, sizeof(unsigned int)));
+        if ((rc = g->dRowsCounter.reserve(1))) return rc;
         HIPCHK(hipMemsetAsync(g->dRowsCounter, 0, sizeof(unsigned int), g->s));
     }
     w->counter = g->dRowsCounter;

@@ -51,8 +51,8 @@ int ensure_panel_inv(gp_ctx *g) {
     const long PB = (long)W * GP_TILE;
     const int nJ = (nt + W - 1) / W, nF = nt / W, Wl = nt % W;
     int rc;
-    if ((rc = dev_realloc(&g->dInvP, &g->capInvP, (long)nJ * PB * PB))) return rc;
-    if ((rc = dev_realloc(&g->dInvPw, &g->capInvPw, (long)nJ * PB * PB))) return rc;
+    if ((rc = g->dInvP.reserve((long)nJ * PB * PB))) return rc;
+    if ((rc = g->dInvPw.reserve((long)nJ * PB * PB))) return rc;
     double *Wk = g->dInvPw;
     hipStream_t s = g->s;
     launch_set_identity_blocks(s, Wk, PB, nJ);
@@ -189,9 +189,9 @@ int ensure_wi(gp_ctx *g) {
     const int nt = (int)(Npad / GP_TILE);
     int rc;
     if ((rc = ensure_panel_inv(g))) return rc;
-    if ((rc = dev_realloc(&g->dT, &g->capT, Npad * Npad))) return rc;
-    if ((rc = dev_realloc(&g->dT2, &g->capT2, Npad * Npad))) return rc;
-    if ((rc = dev_realloc(&g->dWi, &g->capWi, Npad * Npad))) return rc;
+    if ((rc = g->dT.reserve(Npad * Npad))) return rc;
+    if ((rc = g->dT2.reserve(Npad * Npad))) return rc;
+    if ((rc = g->dWi.reserve(Npad * Npad))) return rc;
     double *T = g->dT;
     hipStream_t s = g->s;
     if (g->emulate_fp64 && g->emulate_fit && g->invp_W % 2 == 0) {
@@ -234,9 +234,9 @@ int ensure_linv(gp_ctx *g) {
     const int nt = (int)(Npad / GP_TILE);
     int rc;
     if ((rc = ensure_panel_inv(g))) return rc;
-    if ((rc = dev_realloc(&g->dT, &g->capT, Npad * Npad))) return rc;
-    if ((rc = dev_realloc(&g->dT2, &g->capT2, Npad * Npad))) return rc;
-    if ((rc = dev_realloc(&g->dLi, &g->capLi, Npad * Npad))) return rc;
+    if ((rc = g->dT.reserve(Npad * Npad))) return rc;
+    if ((rc = g->dT2.reserve(Npad * Npad))) return rc;
+    if ((rc = g->dLi.reserve(Npad * Npad))) return rc;
     if (!g->w_in_t2) {
         int ph = phase_begin(g, "potri_solve", (double)g->N * g->N * g->N / 3.0, 0.0);
         launch_set_identity(g->s, g->dT, Npad, Npad);
