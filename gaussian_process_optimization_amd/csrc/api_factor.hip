@@ -44,35 +44,36 @@ static int chain_step(gp_ctx *g, hipStream_t s, const Members &m, int j, int J1,
     return j + 1;
 }
 
+// Record event (kind, i) on stream `from` and make every stream of `to` wait for it: the fork, every join and the hand-over
+// of a finished panel.  (A null entry is a stream that takes no part this time.)
+static void record_wait(gp_ctx *g, int kind, size_t i, hipStream_t from, std::initializer_list<hipStream_t> to) {
+    hipEvent_t e = la_event(g, kind, i);
+    GP_NOTE(hipEventRecord(e, from));
+    for (hipStream_t t : to)
+        if (t) GP_NOTE(hipStreamWaitEvent(t, e, 0));
+}
+
+// C[r0 .. R1, c0 .. c1) -= A[:, J0 .. J1) A[c0 .. c1, J0 .. J1)^T of m.A on stream s: the update every tile right of a panel takes from it
+static void panel_update(gp_ctx *g, hipStream_t s, const Members &m, int J0, int J1, TileSet ts) {
+    const double *P = m.A + (long)J0 * GP_TILE;
+    gemm(g, s, 1, m.A, m.lda, P, m.lda, P, m.lda, 1, (J1 - J0) * GP_TILE, ts, member_opt(m, GemmOpt(), m.sA, m.sA, m.sA));
+}
+
 void factor_buf(gp_ctx *g, const Members &m, int nt, int R1, bool side_inv) {
     const int W = g->panel_tiles;
     hipStream_t s = g->s;
-    double *A = m.A;
-    const long lda = m.lda;
-    if (side_inv) {
-        hipEvent_t e0 = la_event(g, EV_MISC, 0);
-        GP_NOTE(hipEventRecord(e0, s));
-        GP_NOTE(hipStreamWaitEvent(g->s_inv, e0, 0));
-    }
+    if (side_inv) record_wait(g, EV_MISC, 0, s, {g->s_inv});
     for (int J0 = 0; J0 < nt; J0 += W) {
         const int J1 = std::min(J0 + W, nt);
         for (int j = J0; j < J1;) j = chain_step(g, s, m, j, J1, R1);
         if (side_inv) {
-            hipEvent_t eF = la_event(g, EV_CHAIN, J0 / W);
-            GP_NOTE(hipEventRecord(eF, s));
-            GP_NOTE(hipStreamWaitEvent(g->s_inv, eF, 0));
+            record_wait(g, EV_CHAIN, J0 / W, s, {g->s_inv});
             build_panel_inv_one(g, g->s_inv, J0 / W, W, nt);
         }
         // trailing update with the whole panel (K = W * 128): the dense contraction on MFMA
-        if (J1 < nt)
-            gemm(g, s, 1, A, lda, A + (long)J0 * GP_TILE, lda, A + (long)J0 * GP_TILE, lda, 1, (J1 - J0) * GP_TILE,
-                 TileSet{0, R1, J1, nt, 1}, member_opt(m, GemmOpt(), m.sA, m.sA, m.sA));
+        if (J1 < nt) panel_update(g, s, m, J0, J1, TileSet{0, R1, J1, nt, 1});
     }
-    if (side_inv) {
-        hipEvent_t ei = la_event(g, EV_MISC, 4);
-        GP_NOTE(hipEventRecord(ei, g->s_inv));
-        GP_NOTE(hipStreamWaitEvent(s, ei, 0));
-    }
+    if (side_inv) record_wait(g, EV_MISC, 4, g->s_inv, {s});
 }
 
 // The single-stream factorisation of the model's Ky (N <= 768, and the sizes where the look-ahead's per-panel events, waits and
@@ -82,13 +83,8 @@ int factor(gp_ctx *g) {
     const int nt = (int)(g->Npad / GP_TILE);
     const int W = g->panel_tiles;
     const bool side = nt > W && g->s_inv;
-    if (side) {
-        const long PB = (long)W * GP_TILE;
-        const int nJ = (nt + W - 1) / W;
-        int rc;
-        if ((rc = g->dInvP.reserve((long)nJ * PB * PB))) return rc;
-        if ((rc = g->dInvPw.reserve((long)nJ * PB * PB))) return rc;
-    }
+    int rc;
+    if (side && (rc = reserve_panel_inv(g, W, nt))) return rc;
     factor_buf(g, ctx_members(g), nt, nt + 1, side);
     if (side) {
         g->invp_W = W;
@@ -98,227 +94,220 @@ int factor(gp_ctx *g) {
     return 0;
 }
 
+// ---- the look-ahead scheduler: factor_lookahead's panel loop over the strands below ----
+// What one factorisation is laid out as, computed once before the loop (host arithmetic only).
+struct LaPlan {
+    int nt, R1, W, nJ;
+    std::vector<int> pb;      // panel boundaries (uniform panels of W tiles; two sentinels)
+    int pstages, pred_start;  // pipelined stages: how many ride behind the factorisation, and the panel that releases them
+    bool emu;                 // the trailing update runs in residue form
+    int Gf;                   // emulated: panels per residue launch (the far launches ride on the otherwise idle candidate stream)
+    int edge(int k) const { return pb[std::min(k, nJ + 1)]; }
+};
+static LaPlan la_plan(const gp_ctx *g, const PredPipe &pp) {
+    LaPlan p;
+    p.nt = (int)(g->Npad / GP_TILE);
+    p.R1 = p.nt + 1;
+    p.W = g->panel_tiles;
+    for (int j = 0; j < p.nt; j += p.W) p.pb.push_back(j);
+    p.pb.push_back(p.nt);
+    p.pb.push_back(p.nt);
+    p.nJ = (int)p.pb.size() - 2;
+    // Only the first `pipe_stages` candidate stages ride behind the factorisation (on the CU-masked stream, released
+    // at panel pred_start); the caller runs the rest on the main stream, on every CU, once the factor is complete.
+    p.pstages = pp.on ? std::max(1, std::min(p.nJ, pp.stages)) : 0;
+    p.pred_start = std::max(0, std::min(p.nJ - 1, p.nJ * pp.start_pct / 100));
+    p.emu = emu_fit_applies(g);
+    p.Gf = (p.emu && !pp.on) ? std::max(1, std::min(g->rns_group_fit, (int)(GP_RNS_KMAX / ((long)p.W * GP_TILE)))) : 1;
+    return p;
+}
+
+// Columns owned by the chain stream (options own_keep_*): in the head of the factorisation the chain finishes panel J+1 long
+// before bulk(J) has drained and would wait for it, with the CUs kept free of the bulk stream idle.  bulk(J) therefore keeps
+// only what lasts as long as the chain is busy with the next panel (a count of tiles linear in the rows below it); the
+// rest -- the last tile columns oc .. nt -- takes panel J's update on THIS stream, after chain(J), on every CU.  The owned
+// range only shrinks with J, so own(J) never meets a tile bulk(J-1) writes, and a column handed back to the bulk stream
+// had its last update here before chain(J+1), which bulk(J+1) waits for.  Same contraction per tile in the same order:
+// the same bits as without.
+// Returns oc for the panel whose look-ahead target ends at tile J2; own_prev is the count owned at the previous panel (nt before the first).
+static int first_owned_column(int nt, int J2, int W, int own_prev, int keep_base, int keep_per_row, int keep_pipe_pct, bool piped) {
+    if (keep_per_row <= 0 || J2 >= nt) return nt;
+    const long n = nt - J2;
+    // tiles right of J2 (with the rhs row) minus the kept ones (the chain's time per panel grows with the panel width: per_row is per 6 tiles)
+    long keep = keep_base + (long)keep_per_row * n * W / 6;
+    // (one-call entry points: once the candidate stages share the bulk stream's CUs the trailing update lasts longer and the
+    // chain waits again; the bulk stream then keeps own_keep_pipe_pct % of the rule's share)
+    // (never at the FIRST panel that owns columns: there own_prev is still its initial nt, and keep = 0 would hand the
+    // whole trailing update to the chain stream -- pipe_start_pct = 0, or so few panels that pred_start rounds to 0)
+    if (piped && own_prev < nt) keep = keep * keep_pipe_pct / 100;
+    const long t_own = n * (n + 1) / 2 + n - keep;
+    int c = 0;
+    while (c < own_prev && (long)(c + 1) * (c + 2) / 2 + (c + 1) <= t_own) ++c;
+    return nt - c;
+}
+
+// Two concurrent MFMA-bound launches run slower than one after the other (measured 51 vs 63 TFLOP/s), and
+// the candidate stream is CU-masked like the trailing update (the diagonal-tile workgroup needs an empty
+// CU), which costs it 1/8 of the chip.  So only the first `pipe_stages` stages ride here, released once
+// the factorisation turns latency-bound (panel >= pred_start): they fill the CUs the chain leaves idle in
+// the tail.  The rest run after the join on the main stream, on every CU (fit_impl).  Measured at C3:
+// 73.4 ms against 77.0 for gp_fit + gp_predict; every stage pipelined: 78.1.
+// Releases the stages that panel J (>= pred_start) makes runnable; m is the context's members with the width in use (T / T2 are the pipe's T / S).
+static void release_stages(gp_ctx *g, const LaPlan &p, const PredPipe &pp, const Members &m, int J, int *next) {
+    for (; *next <= J && *next < p.pstages; ++*next) {
+        const int Q = *next;
+        GP_NOTE(hipStreamWaitEvent(g->s_pred, la_event(g, EV_CHAIN, J), 0));
+        GP_NOTE(hipStreamWaitEvent(g->s_pred, la_event(g, EV_INVP, Q), 0));
+        solve_step(g, g->s_pred, m, Q, pp.trapezoid ? std::min(pp.mt, p.edge(Q + 1)) : pp.mt);
+    }
+}
+
+// fp64 trailing update of panel J on the bulk stream: everything between the look-ahead target and the owned columns
+static void trail_fp64(gp_ctx *g, const LaPlan &p, const Members &m, int J, int oc) {
+    if (p.pb[J + 2] < oc) panel_update(g, g->s_bulk, m, p.pb[J], p.pb[J + 1], TileSet{0, p.R1, p.pb[J + 2], oc, 1});
+    GP_NOTE(hipEventRecord(la_event(g, EV_BULK, J), g->s_bulk));
+}
+
+// "emulate_fp64": the trailing update (the launches of the bulk stream) in residue form on the int8 matrix cores
+// (rns.hip).  The Schur complement right of the look-ahead panel lives as Ky (untouched, in dA) minus an exact integer
+// accumulator dRm; a panel's columns are rebuilt in fp64 once, right before they become the look-ahead target.  The
+// chain (diagonal tiles, panel solves, in-panel and look-ahead updates) and the right-hand-side tile row stay fp64.
+//
+// Panels in groups of Gf (all panel edges sit on 256-column accumulator blocks).  Pair (panel j, column
+// panel c >= j+2; c = j+1 is the fp64 look-ahead) is served exactly once, by
+//   near(J)  on the bulk stream, every iteration: the group's panels so far -> the columns of panel J+2,
+//   mid(g)   on the bulk stream, from the group's last panel on, ONE column panel per iteration: the whole group
+//            -> the next Gf column panels, each slice an iteration before its columns are rebuilt (as one
+//            launch of 3.7 ms at N = 16384 it sat in front of near(J+1) and the chain stalled 2.6 ms behind it),
+//   far(g)   on a stream of its own: the whole group -> everything right of that,
+// so the accumulator makes one round trip per group for the far columns and the long launch (K = Gf PB)
+// overlaps the next group's chain.  Ordering: near(J) and mid(g) accumulate into blocks far(g-1) / far(g-2)
+// wrote (mid waits for far(g-1); near follows mid(g-1) in stream order); far(g) follows far(g-1) in stream
+// order; the chain's reconstruction of panel J+1's columns waits for bulk(J-1) = near(J-1), recorded
+// BEFORE mid so that the chain does not wait for it.  The integers summed are those of Gf = 1.
+struct EmuTrail {
+    gp_ctx *g;
+    const LaPlan &p;
+    const Members &m;
+    RnsGeom rg;
+    std::vector<char> far_issued;
+    int mid_Jg = -1, mid_end = 0, mid_first = 0, mid_base = 0, mid_next = 0;   // the slices of mid(g) still to come
+
+    int prepare() {
+        int rc;
+        if ((rc = rns_prepare(g, g->jitter_try, &rg))) return rc;
+        far_issued.assign(p.nJ / p.Gf + 2, 0);
+        return g->dRm.reserve((long)GP_RNS_T * rg.nt256 * rg.nt256 * 65536);
+    }
+    // panels Jfirst .. (tiles up to Tend) -> tile columns [t0, t1)
+    void rlaunch(hipStream_t st, int Jfirst, int Tend, int t0, int t1, int first) const {
+        t1 = std::min(t1, p.nt);
+        if (t0 >= t1) return;
+        const int T0 = p.pb[Jfirst];
+        rns_gemm(g, st, g->dLr + (long)T0 * GP_TILE, rg.Lpitch, rg.Lplane, g->dLr + (long)T0 * GP_TILE, rg.Lpitch, rg.Lplane,
+                 g->dRm, rg.nt256, rg.nt256, rg.nt256, t0 / 2, (t1 + 1) / 2, (Tend - T0) * GP_TILE, first, 1);
+    }
+    // rebuild the columns of panel J+2 in fp64 (Ky minus everything accumulated for them: panels 0 .. J) as soon as
+    // the last residue launch into them is enqueued -- on this stream, off the chain
+    void rebuild_next(int J) const {
+        if (p.edge(J + 2) < p.nt)
+            launch_rns_reconstruct256(g->s_bulk, g->dRm, rg.nt256, rg.nt256, rg.nt256, p.edge(J + 2), std::min(p.edge(J + 3), p.nt),
+                                      g->Npad, m.A, m.lda, rg.back, 1);
+    }
+    // panel J's share, on the bulk stream (and the far stream): records bulk(J)
+    void update(int J) {
+        hipStream_t sb = g->s_bulk, sfar = g->s_pred;
+        const int J1 = p.pb[J + 1], J2 = p.pb[J + 2], Gf = p.Gf;
+        rns_convert_panel(g, sb, rg, J, g->dInfo + 2);
+        // the right-hand-side tile row rides in fp64
+        panel_update(g, sb, m, p.pb[J], J1, TileSet{p.nt, p.R1, J2, p.nt, 0});
+        if (Gf == 1) {
+            rlaunch(sb, J, J1, J2, p.nt, J == 0 ? 1 : 0);
+            rebuild_next(J);
+            GP_NOTE(hipEventRecord(la_event(g, EV_BULK, J), sb));
+            return;
+        }
+        const int gi = J / Gf, Jg = gi * Gf;
+        const int first = gi == 0 ? 1 : 0;
+        GP_NOTE(hipEventRecord(la_event(g, EV_CONV, J), sb));
+        rlaunch(sb, Jg, J1, p.edge(J + 2), p.edge(J + 3), first);
+        rebuild_next(J);
+        GP_NOTE(hipEventRecord(la_event(g, EV_BULK, J), sb));
+        if (J % Gf == Gf - 1) {
+            if (gi >= 1 && far_issued[gi - 1]) GP_NOTE(hipStreamWaitEvent(sb, la_event(g, EV_FAR, gi - 1), 0));
+            mid_Jg = Jg;            // the slices of mid(g): column panel mid_base + k at iteration J + k
+            mid_end = J1;
+            mid_first = first;
+            mid_base = J + 3;
+            mid_next = 0;
+            if (p.edge(J + 3 + Gf) < p.nt) {
+                GP_NOTE(hipStreamWaitEvent(sfar, la_event(g, EV_CONV, J), 0));
+                rlaunch(sfar, Jg, J1, p.edge(J + 3 + Gf), p.nt, first);
+                GP_NOTE(hipEventRecord(la_event(g, EV_FAR, gi), sfar));
+                far_issued[gi] = true;
+            }
+        }
+        if (mid_Jg >= 0 && mid_next < Gf) {
+            rlaunch(sb, mid_Jg, mid_end, p.edge(mid_base + mid_next), p.edge(mid_base + mid_next + 1), mid_first);
+            ++mid_next;
+        }
+    }
+};
+
 int factor_lookahead(gp_ctx *g, const PredPipe &pp) {
     int rc;
     if ((rc = ensure_bulk_stream(g))) return rc;
-    const long lda = g->Npad;
-    const int nt = (int)(g->Npad / GP_TILE);
-    const int R1 = nt + 1;
-    const int W = g->panel_tiles;
-    double *A = g->dA;
+    const LaPlan p = la_plan(g, pp);
+    const int nt = p.nt;
     hipStream_t sp = g->s_panel, sb = g->s_bulk;
-    // fork
-    hipEvent_t e0 = la_event(g, EV_MISC, 0);
-    GP_NOTE(hipEventRecord(e0, g->s));
-    GP_NOTE(hipStreamWaitEvent(sp, e0, 0));
-    GP_NOTE(hipStreamWaitEvent(sb, e0, 0));
-    const long PB = (long)W * GP_TILE;
-    const int nJu = (nt + W - 1) / W;
+    // the candidate stream takes part for the pipelined stages or, emulated, for the far launches (never both: Gf > 1 only without a pipe)
+    hipStream_t spred = pp.on ? g->s_pred : nullptr, sfar = p.Gf > 1 ? g->s_pred : nullptr;
     // Every inverted diagonal panel (alpha, the candidate solve and Ky^-1 all need them) is built on the side stream as soon
     // as its panel of L is final, beside the rest of the factorisation: after the join nothing is left to build (as a pass of
     // its own, 2W - 1 short launches in series, it held the main stream for 0.3 ms between the factor and its first consumer).
-    if ((rc = g->dInvP.reserve((long)nJu * PB * PB))) return rc;
-    if ((rc = g->dInvPw.reserve((long)nJu * PB * PB))) return rc;
-    GP_NOTE(hipStreamWaitEvent(g->s_inv, e0, 0));
-    if (pp.on) {
-        GP_NOTE(hipStreamWaitEvent(g->s_pred, e0, 0));
-        if (pp.init) pp.init(g->s_pred);
-    }
+    if ((rc = reserve_panel_inv(g, p.W, nt))) return rc;
+    Members cm = ctx_members(g);
+    cm.W = p.W;   // (g->invp_W is set at the end only: the pipelined stages, which run on cm.T / cm.T2, need the width now)
+    // fork
+    record_wait(g, EV_MISC, 0, g->s, {sp, sb, g->s_inv, spred, sfar});
+    if (pp.on && pp.init) pp.init(spred);
+    EmuTrail emu{g, p, cm};
+    if (p.emu && (rc = emu.prepare())) return rc;
     int next_pred = 0;
     int own_prev = nt;   // columns owned by the chain stream at the previous panel (the range never grows)
-    // Only the first `pipe_stages` candidate stages ride behind the factorisation (on the CU-masked stream, released
-    // at panel pred_start); the caller runs the rest on the main stream, on every CU, once the factor is complete.
-    const int pstages = pp.on ? std::max(1, std::min(nJu, pp.stages)) : 0;
-    const int pred_start = std::max(0, std::min(nJu - 1, nJu * pp.start_pct / 100));
-    // panel boundaries (uniform panels of W tiles; two sentinels)
-    std::vector<int> pb;
-    for (int j = 0; j < nt; j += W) pb.push_back(j);
-    pb.push_back(nt);
-    pb.push_back(nt);
-    const int nJ = (int)pb.size() - 2;
-    // "emulate_fp64": the trailing update (the launches of the bulk stream) in residue form on the int8 matrix cores
-    // (rns.hip).  The Schur complement right of the look-ahead panel lives as Ky (untouched, in dA) minus an exact integer
-    // accumulator dRm; a panel's columns are rebuilt in fp64 once, right before they become the look-ahead target.  The
-    // chain (diagonal tiles, panel solves, in-panel and look-ahead updates) and the right-hand-side tile row stay fp64.
-    const bool emu = emu_fit_applies(g);
-    RnsGeom rg;
-    int *rflag = g->dInfo + 2;
-    if (emu) {
-        if ((rc = rns_prepare(g, g->jitter_try, &rg))) return rc;
-        const long need = (long)GP_RNS_T * rg.nt256 * rg.nt256 * 65536;
-        if ((rc = g->dRm.reserve(need))) return rc;
-    }
-    // emulated: panels per residue launch (the far launches ride on the otherwise idle candidate stream)
-    const int Gf = (emu && !pp.on) ? std::max(1, std::min(g->rns_group_fit, (int)(GP_RNS_KMAX / PB))) : 1;
-    hipStream_t sfar = g->s_pred;
-    std::vector<char> far_issued(nJ / std::max(1, Gf) + 2, 0);
-    int mid_Jg = -1, mid_end = 0, mid_first = 0, mid_base = 0, mid_next = 0;
-    if (Gf > 1) GP_NOTE(hipStreamWaitEvent(sfar, e0, 0));
-    const Members cm = ctx_members(g);
-    for (int J = 0; J < nJ; ++J) {
-        const int J0 = pb[J], J1 = pb[J + 1], J2 = pb[J + 2];
-        bool bulk_recorded = false;
-        for (int j = J0; j < J1;) j = chain_step(g, sp, cm, j, J1, R1);
-        hipEvent_t eF = la_event(g, EV_CHAIN, J);
-        GP_NOTE(hipEventRecord(eF, sp));
-        const int K = (J1 - J0) * GP_TILE;
-        GP_NOTE(hipStreamWaitEvent(g->s_inv, eF, 0));
-        build_panel_inv_one(g, g->s_inv, J, W, nt);
-        if (pp.on) {
-            if (J < pstages) GP_NOTE(hipEventRecord(la_event(g, EV_INVP, J), g->s_inv));
-            // Two concurrent MFMA-bound launches run slower than one after the other (measured 51 vs 63 TFLOP/s), and
-            // the candidate stream is CU-masked like the trailing update (the diagonal-tile workgroup needs an empty
-            // CU), which costs it 1/8 of the chip.  So only the first `pipe_stages` stages ride here, released once
-            // the factorisation turns latency-bound (panel >= pred_start): they fill the CUs the chain leaves idle in
-            // the tail.  The rest run after the join on the main stream, on every CU (fit_impl).  Measured at C3:
-            // 73.4 ms against 77.0 for gp_fit + gp_predict; every stage pipelined: 78.1.
-            if (J >= pred_start) {
-                for (; next_pred <= J && next_pred < pstages; ++next_pred) {
-                    const int Q = next_pred, Q0 = Q * W, Q1 = std::min(Q0 + W, nt);
-                    const int KQ = (Q1 - Q0) * GP_TILE;
-                    const int prow = pp.trapezoid ? std::min(pp.mt, Q1) : pp.mt;
-                    GP_NOTE(hipStreamWaitEvent(g->s_pred, la_event(g, EV_CHAIN, J), 0));
-                    GP_NOTE(hipStreamWaitEvent(g->s_pred, la_event(g, EV_INVP, Q), 0));
-                    GemmOpt o;
-                    o.k_end_tri = 1;
-                    o.b_sub = Q0;
-                    gemm(g, g->s_pred, 0, pp.S, g->Npad, pp.T + (long)Q0 * GP_TILE, g->Npad, g->dInvP + (long)Q * PB * PB,
-                         PB, 1, KQ, TileSet{0, prow, Q0, Q1, 0}, o);
-                    if (Q1 < nt)
-                        gemm(g, g->s_pred, 1, pp.T, g->Npad, pp.S + (long)Q0 * GP_TILE, g->Npad, A + (long)Q0 * GP_TILE, lda,
-                             1, KQ, TileSet{0, prow, Q1, nt, 0});
-                }
-            }
-        }
+    for (int J = 0; J < p.nJ; ++J) {
+        const int J0 = p.pb[J], J1 = p.pb[J + 1], J2 = p.pb[J + 2];
+        for (int j = J0; j < J1;) j = chain_step(g, sp, cm, j, J1, p.R1);
+        record_wait(g, EV_CHAIN, J, sp, {g->s_inv});
+        build_panel_inv_one(g, g->s_inv, J, p.W, nt);
+        if (J < p.pstages) GP_NOTE(hipEventRecord(la_event(g, EV_INVP, J), g->s_inv));
+        if (pp.on && J >= p.pred_start) release_stages(g, p, pp, cm, J, &next_pred);
         if (J1 >= nt) break;
-        // Columns owned by the chain stream (options own_keep_*): in the head of the factorisation the chain finishes panel J+1 long
-        // before bulk(J) has drained and would wait for it, with the CUs kept free of the bulk stream idle.  bulk(J) therefore keeps
-        // only what lasts as long as the chain is busy with the next panel (a count of tiles linear in the rows below it); the
-        // rest -- the last tile columns oc .. nt -- takes panel J's update on THIS stream, after chain(J), on every CU.  The owned
-        // range only shrinks with J, so own(J) never meets a tile bulk(J-1) writes, and a column handed back to the bulk stream
-        // had its last update here before chain(J+1), which bulk(J+1) waits for.  Same contraction per tile in the same order:
-        // the same bits as without.
-        int oc = nt;
-        if (!emu && g->own_keep_per_row > 0 && J2 < nt) {
-            const long n = nt - J2;
-            // tiles right of J2 (with the rhs row) minus the kept ones (the chain's time per panel grows with the panel width: per_row is per 6 tiles)
-            long keep = g->own_keep_base + (long)g->own_keep_per_row * n * W / 6;
-            // (one-call entry points: once the candidate stages share the bulk stream's CUs the trailing update lasts longer and the
-            // chain waits again; the bulk stream then keeps own_keep_pipe_pct % of the rule's share)
-            // (never at the FIRST panel that owns columns: there own_prev is still its initial nt, and keep = 0 would hand the
-            // whole trailing update to the chain stream -- pipe_start_pct = 0, or so few panels that pred_start rounds to 0)
-            if (pp.on && J >= pred_start && own_prev < nt) keep = keep * g->own_keep_pipe_pct / 100;
-            long t_own = n * (n + 1) / 2 + n - keep;
-            int c = 0;
-            while (c < own_prev && (long)(c + 1) * (c + 2) / 2 + (c + 1) <= t_own) ++c;
-            own_prev = c;
-            oc = nt - c;
-        }
-        if (oc < nt && J >= 1)
-            gemm(g, sp, 1, A, lda, A + (long)J0 * GP_TILE, lda, A + (long)J0 * GP_TILE, lda, 1, K, TileSet{0, R1, oc, nt, 1});
+        const int oc = p.emu ? nt : first_owned_column(nt, J2, p.W, own_prev, g->own_keep_base, g->own_keep_per_row,
+                                                       g->own_keep_pipe_pct, pp.on && J >= p.pred_start);
+        own_prev = nt - oc;
+        if (oc < nt && J >= 1) panel_update(g, sp, cm, J0, J1, TileSet{0, p.R1, oc, nt, 1});
         // the look-ahead update is on the critical path: enqueue it before the trailing update so that its
         // workgroups reach the dispatcher first once bulk(J-1) has drained
         if (J >= 1) GP_NOTE(hipStreamWaitEvent(sp, la_event(g, EV_BULK, J - 1), 0));
         // (emulated: the look-ahead panel's columns took everything the residue accumulator holds for them -- panels
         // 0 .. J-1 -- on the bulk stream, before bulk(J-1) was recorded)
-        gemm(g, sp, 1, A, lda, A + (long)J0 * GP_TILE, lda, A + (long)J0 * GP_TILE, lda, 1, K,
-             TileSet{0, R1, J1, J2, 1});
+        panel_update(g, sp, cm, J0, J1, TileSet{0, p.R1, J1, J2, 1});
         if (oc < nt && J == 0)   // (the first panel has no bulk launch to wait for: the critical update goes first)
-            gemm(g, sp, 1, A, lda, A + (long)J0 * GP_TILE, lda, A + (long)J0 * GP_TILE, lda, 1, K, TileSet{0, R1, oc, nt, 1});
-        if (J2 < nt) {
-            GP_NOTE(hipStreamWaitEvent(sb, eF, 0));
-            if (emu) {
-                rns_convert_panel(g, sb, rg, J, rflag);
-                // the right-hand-side tile row rides in fp64
-                gemm(g, sb, 1, A, lda, A + (long)J0 * GP_TILE, lda, A + (long)J0 * GP_TILE, lda, 1, K,
-                     TileSet{nt, R1, J2, nt, 0});
-                auto rlaunch = [&](hipStream_t st, int Jfirst, int t0, int t1, int first, int Tend = -1) {   // panels Jfirst..J (tiles up to Tend) -> tiles [t0, t1)
-                    t1 = std::min(t1, nt);
-                    if (t0 >= t1) return;
-                    const int T0 = pb[Jfirst];
-                    rns_gemm(g, st, g->dLr + (long)T0 * GP_TILE, rg.Lpitch, rg.Lplane, g->dLr + (long)T0 * GP_TILE, rg.Lpitch,
-                                       rg.Lplane, g->dRm, rg.nt256, rg.nt256, rg.nt256, t0 / 2, (t1 + 1) / 2,
-                                       ((Tend < 0 ? J1 : Tend) - T0) * GP_TILE, first, 1);
-                };
-                auto pbi = [&](int k) { return pb[std::min(k, nJ + 1)]; };
-                // rebuild the columns of panel J+2 in fp64 (Ky minus everything accumulated for them: panels 0 .. J) as soon as
-                // the last residue launch into them is enqueued -- on this stream, off the chain
-                auto rebuild_next = [&]() {
-                    if (pbi(J + 2) < nt)
-                        launch_rns_reconstruct256(sb, g->dRm, rg.nt256, rg.nt256, rg.nt256, pbi(J + 2), std::min(pbi(J + 3), nt),
-                                                  g->Npad, A, lda, rg.back, 1);
-                };
-                if (Gf == 1) {
-                    rlaunch(sb, J, J2, nt, J == 0 ? 1 : 0);
-                    rebuild_next();
-                } else {
-                    // Panels in groups of Gf (all panel edges sit on 256-column accumulator blocks).  Pair (panel j, column
-                    // panel c >= j+2; c = j+1 is the fp64 look-ahead) is served exactly once, by
-                    //   near(J)  on the bulk stream, every iteration: the group's panels so far -> the columns of panel J+2,
-                    //   mid(g)   on the bulk stream, from the group's last panel on, ONE column panel per iteration: the whole group
-                    //            -> the next Gf column panels, each slice an iteration before its columns are rebuilt (as one
-                    //            launch of 3.7 ms at N = 16384 it sat in front of near(J+1) and the chain stalled 2.6 ms behind it),
-                    //   far(g)   on a stream of its own: the whole group -> everything right of that,
-                    // so the accumulator makes one round trip per group for the far columns and the long launch (K = Gf PB)
-                    // overlaps the next group's chain.  Ordering: near(J) and mid(g) accumulate into blocks far(g-1) / far(g-2)
-                    // wrote (mid waits for far(g-1); near follows mid(g-1) in stream order); far(g) follows far(g-1) in stream
-                    // order; the chain's reconstruction of panel J+1's columns waits for bulk(J-1) = near(J-1), recorded
-                    // BEFORE mid so that the chain does not wait for it.  The integers summed are those of Gf = 1.
-                    const int gi = J / Gf, Jg = gi * Gf;
-                    const int first = gi == 0 ? 1 : 0;
-                    GP_NOTE(hipEventRecord(la_event(g, EV_CONV, J), sb));
-                    rlaunch(sb, Jg, pbi(J + 2), pbi(J + 3), first);
-                    rebuild_next();
-                    GP_NOTE(hipEventRecord(la_event(g, EV_BULK, J), sb));
-                    bulk_recorded = true;
-                    if (J % Gf == Gf - 1) {
-                        if (gi >= 1 && far_issued[gi - 1]) GP_NOTE(hipStreamWaitEvent(sb, la_event(g, EV_FAR, gi - 1), 0));
-                        mid_Jg = Jg;            // the slices of mid(g): column panel mid_base + k at iteration J + k
-                        mid_end = J1;
-                        mid_first = first;
-                        mid_base = J + 3;
-                        mid_next = 0;
-                        if (pbi(J + 3 + Gf) < nt) {
-                            GP_NOTE(hipStreamWaitEvent(sfar, la_event(g, EV_CONV, J), 0));
-                            rlaunch(sfar, Jg, pbi(J + 3 + Gf), nt, first);
-                            GP_NOTE(hipEventRecord(la_event(g, EV_FAR, gi), sfar));
-                            far_issued[gi] = true;
-                        }
-                    }
-                    if (mid_Jg >= 0 && mid_next < Gf) {
-                        rlaunch(sb, mid_Jg, pbi(mid_base + mid_next), pbi(mid_base + mid_next + 1), mid_first, mid_end);
-                        ++mid_next;
-                    }
-                }
-            } else {
-                if (J2 < oc)
-                    gemm(g, sb, 1, A, lda, A + (long)J0 * GP_TILE, lda, A + (long)J0 * GP_TILE, lda, 1, K,
-                         TileSet{0, R1, J2, oc, 1});
-            }
-            if (!bulk_recorded) GP_NOTE(hipEventRecord(la_event(g, EV_BULK, J), sb));
-        }
+            panel_update(g, sp, cm, J0, J1, TileSet{0, p.R1, oc, nt, 1});
+        if (J2 >= nt) continue;
+        GP_NOTE(hipStreamWaitEvent(sb, la_event(g, EV_CHAIN, J), 0));
+        if (p.emu) emu.update(J);
+        else trail_fp64(g, p, cm, J, oc);
     }
-    // join
-    hipEvent_t ep = la_event(g, EV_MISC, 1), eb = la_event(g, EV_MISC, 2);
-    GP_NOTE(hipEventRecord(ep, sp));
-    GP_NOTE(hipEventRecord(eb, sb));
-    GP_NOTE(hipStreamWaitEvent(g->s, ep, 0));
-    GP_NOTE(hipStreamWaitEvent(g->s, eb, 0));
-    if (Gf > 1) {   // (every far launch ends before the factor is complete: mid of the next group waits for it; join anyway)
-        hipEvent_t ef = la_event(g, EV_MISC, 7);
-        GP_NOTE(hipEventRecord(ef, sfar));
-        GP_NOTE(hipStreamWaitEvent(g->s, ef, 0));
-    }
-    g->pipe_done = pstages;
-    if (pp.on) {
-        hipEvent_t eq = la_event(g, EV_MISC, 3);
-        GP_NOTE(hipEventRecord(eq, g->s_pred));
-        GP_NOTE(hipStreamWaitEvent(g->s, eq, 0));
-    }
-    hipEvent_t ei = la_event(g, EV_MISC, 4);
-    GP_NOTE(hipEventRecord(ei, g->s_inv));
-    GP_NOTE(hipStreamWaitEvent(g->s, ei, 0));
-    g->invp_W = W;
+    // join  (every far launch ends before the factor is complete: mid of the next group waits for it; join anyway)
+    record_wait(g, EV_MISC, 1, sp, {g->s});
+    record_wait(g, EV_MISC, 2, sb, {g->s});
+    if (sfar) record_wait(g, EV_MISC, 7, sfar, {g->s});
+    g->pipe_done = p.pstages;
+    if (spred) record_wait(g, EV_MISC, 3, spred, {g->s});
+    record_wait(g, EV_MISC, 4, g->s_inv, {g->s});
+    g->invp_W = p.W;
     g->invp_valid = true;   // (fit_impl drops it again when the attempt turns out not positive definite)
     return la_events_ok(g);   // (an error return makes fit_impl quiesce every stream before it reports)
 }
@@ -386,8 +375,16 @@ double lml_from_scalars(long N, int P, const double *scal) {
     return 0.5 * (-(double)N * P * log_2_pi - P * scal[0] - fit);  // exact_gaussian_inference.py:62
 }
 
-// Shared body of gp_fit and gp_fit_predict.  pipe != 0: the candidate solve of the resident candidates is
-// pipelined behind the factorisation (PredPipe above) and the posterior reductions are appended.
+// The factorisation's status word, read back (the stream is drained); *bad, when `emu`: an entry of L left the fixed-point range
+// of the residue path.
+int factor_status(gp_ctx *g, bool emu, int *info, int *bad) {
+    *bad = 0;
+    HIPCHK(hipMemcpyAsync(info, g->dInfo, sizeof(int), hipMemcpyDeviceToHost, g->s));
+    GP_SYNC(g->s);
+    if (emu && *info == 0) HIPCHK(hipMemcpy(bad, g->dInfo + 2, sizeof(int), hipMemcpyDeviceToHost));
+    return 0;
+}
+
 // Any error return of fit_impl after work was forked onto the side streams must leave them joined: the guard waits for
 // every stream of the context unless the normal exit (where the joins are stream-ordered) dismissed it.
 struct QuiesceOnError {
@@ -400,97 +397,123 @@ struct QuiesceOnError {
     }
 };
 
-int fit_impl(gp_ctx *g, int maxtries, int pipe, int include_noise) {
+// The PredPipe of a kind: buffers, what fills T, and how many stages ride behind the factorisation from which panel on.
+static int make_pipe(gp_ctx *g, Pipe kind, PredPipe *pp) {
+    const long N = g->N, Npad = g->Npad;
+    const int nt = (int)(Npad / GP_TILE), W = std::min(g->panel_tiles, nt), nJ = (nt + W - 1) / W;
+    const bool cand = kind == Pipe::Candidates;
+    const long mcpad = cand ? round_up(g->M, GP_TILE) : Npad;
+    int rc;
+    if (cand && (rc = ensure_out(g))) return rc;
+    if ((rc = g->dT.reserve(mcpad * Npad))) return rc;
+    if ((rc = g->dT2.reserve(mcpad * Npad))) return rc;
+    if (!cand && (rc = g->dWi.reserve(Npad * Npad))) return rc;
+    if ((rc = reserve_panel_inv(g, W, nt))) return rc;
+    pp->on = true;
+    pp->mt = (int)(mcpad / GP_TILE);
+    pp->nJ = nJ;
+    pp->trapezoid = !cand;
+    // stages and release point; 0 / -1 = automatic: the share of the panels that was best at N = 16384 (3 of 22 candidate
+    // stages, 8 of 22 L^-T stages), released at 32 % of up to 24 panels, 40 % beyond (measured N = 8192 ... 32768)
+    if (cand) {
+        pp->init = [g, mcpad, N, Npad](hipStream_t st) { launch_cross_k(st, g->dT, Npad, g->dXs, g->M, mcpad, g->dX, N, Npad, g->kp); };
+        pp->phase = "cholesky+cand_solve";
+        pp->rest_phase = "cand_solve_rest";
+        pp->flops = (double)N * N * N / 3.0 + (double)N * N * g->M;
+        pp->stages = g->pipe_stages;
+        if (pp->stages <= 0) pp->stages = std::max(1, (nJ * 14 + 50) / 100) + (nJ <= 12 ? 1 : 0);   // small N: the chain is everything
+        pp->start_pct = g->pipe_start_pct;
+        if (pp->start_pct < 0) pp->start_pct = nJ <= 24 ? 32 : 40;
+    } else {
+        pp->init = [g, Npad](hipStream_t st) { launch_set_identity(st, g->dT, Npad, Npad); };
+        pp->phase = "cholesky+potri_stages";
+        pp->rest_phase = "potri_solve_rest";
+        pp->flops = (double)N * N * N / 3.0;
+        pp->stages = g->pipe_stages_grad;
+        if (pp->stages <= 0) pp->stages = std::max(1, (nJ * 36 + 50) / 100);
+        pp->start_pct = g->pipe_start_pct_grad;
+    }
+    return 0;
+}
+
+// One attempt of the ladder, as two phases: Ky with this jitter, then its factor -- pipelined, look-ahead or single-stream.
+static int factor_attempt(gp_ctx *g, const PredPipe &pp, const double *diag_add, const double *jitter) {
+    const double N = (double)g->N;
+    const int nt = (int)(g->Npad / GP_TILE);
+    g->lr_valid = false;     // residue planes of L belong to one factorisation attempt
+    g->jitter_try = *jitter;
+    int ph = phase_begin(g, "kbuild", 0.0, 8.0 * N * g->D + 8.0 * N * N / 2);
+    Members m = ctx_members(g);
+    m.diag = diag_add;
+    m.jit = jitter;
+    build_ky(g, m, *jitter != 0.0);
+    phase_end(g, ph);
+    HIPCHK(hipMemsetAsync(g->dInfo, 0, sizeof(int) * 4, g->s));
+    ph = phase_begin(g, pp.on ? pp.phase : "cholesky", pp.on ? pp.flops : N * N * N / 3.0, 0.0);
+    // (the emulated trailing update lives in the look-ahead scheduler)
+    const bool la = pp.on || (g->lookahead && nt > g->panel_tiles && (nt > g->lookahead_min_tiles || emu_fit_applies(g)));
+    const int rc = la ? factor_lookahead(g, pp) : factor(g);
+    if (rc) return rc;
+    phase_end(g, ph);
+    return 0;
+}
+
+// The stages the pipe left to do, on the main stream and every CU.  alpha = L^-T z, log det and alpha'y are 45 short dependent
+// launches (latency-bound, 1 ms): while stages are still to run they go on the side stream, beside those long launches
+// (*side_alpha: done there, EV_MISC 6 marks their end).
+static int rest_stages(gp_ctx *g, const PredPipe &pp, bool *side_alpha) {
+    if (g->pipe_done >= pp.nJ) return 0;
+    const int phr = phase_begin(g, pp.rest_phase, 0.0, 0.0);
+    const int rci = ensure_panel_inv(g);
+    if (rci) return rci;
+    *side_alpha = g->s_inv && g->side_alpha;
+    hipEvent_t eI = la_event(g, EV_MISC, 5);
+    if (*side_alpha) GP_NOTE(hipEventRecord(eI, g->s));
+    // the long launches first: the 45 short launches of alpha / log det take the host 0.7 ms to enqueue, during which
+    // the main stream sat empty when they went first
+    solve_rows(g, ctx_members(g), pp.mt, pp.trapezoid, g->pipe_done);
+    if (*side_alpha) {
+        GP_NOTE(hipStreamWaitEvent(g->s_inv, eI, 0));
+        alpha_lml(g, g->s_inv, ctx_members(g));
+        GP_NOTE(hipEventRecord(la_event(g, EV_MISC, 6), g->s_inv));
+    }
+    phase_end(g, phr);
+    return 0;
+}
+
+// Shared body of gp_fit, gp_fit_predict and gp_fit_grad.  With a pipe the solve of the resident candidates (or of the identity,
+// for Ky^-1) is pipelined behind the factorisation (PredPipe) and finished afterwards; Candidates appends the posterior reductions.
+int fit_impl(gp_ctx *g, int maxtries, Pipe kind, int include_noise) {
     HIPCHK(hipSetDevice(g->device));
     QuiesceOnError guard{g};
     const long N = g->N, Npad = g->Npad;
     const int P = g->P;
-    const int nt_ = (int)(Npad / GP_TILE);
-    // pipe 1: candidate solve of the resident candidates; pipe 2: the solve of the identity (L^-T, for Ky^-1)
-    const long mcpad = pipe == 1 ? round_up(g->M, GP_TILE) : (pipe == 2 ? Npad : 0);
+    int rc;
     PredPipe pp;
-    if (pipe) {
-        int rc;
-        const int W = std::min(g->panel_tiles, nt_);
-        const long PB = (long)W * GP_TILE;
-        const int nJ = (nt_ + W - 1) / W;
-        if (pipe == 1 && (rc = ensure_out(g))) return rc;
-        if ((rc = g->dT.reserve(mcpad * Npad))) return rc;
-        if ((rc = g->dT2.reserve(mcpad * Npad))) return rc;
-        if (pipe == 2 && (rc = g->dWi.reserve(Npad * Npad))) return rc;
-        if ((rc = g->dInvP.reserve((long)nJ * PB * PB))) return rc;
-        if ((rc = g->dInvPw.reserve((long)nJ * PB * PB))) return rc;
-        pp.on = true;
-        pp.mt = (int)(mcpad / GP_TILE);
-        pp.T = g->dT;
-        pp.S = g->dT2;
-        pp.trapezoid = (pipe == 2);
-        // 0 = automatic: the share of the panels that was best at N = 16384 (3 of 22 candidate stages, 8 of 22 L^-T stages)
-        pp.stages = pipe == 2 ? (g->pipe_stages_grad > 0 ? g->pipe_stages_grad : std::max(1, (nJ * 36 + 50) / 100))
-                              : (g->pipe_stages > 0 ? g->pipe_stages : std::max(1, (nJ * 14 + 50) / 100) + (nJ <= 12 ? 1 : 0));  // small N: the chain is everything
-        pp.start_pct = pipe == 2 ? g->pipe_start_pct_grad : (g->pipe_start_pct >= 0 ? g->pipe_start_pct : (nJ <= 24 ? 32 : 40));
-    }
+    if (kind != Pipe::None && (rc = make_pipe(g, kind, &pp))) return rc;
     double diag_add, diag0;
     ky_diag(g->kp, g->noise, &diag_add, &diag0);
     g->nphases = 0;
     g->emu_off_call = false;
     fit_dropped(g);
 
+    // the jitter ladder, GPy/GPy/util/linalg.py:62-75
     double jitter = 0.0;
     int tries = 0;  // number of jittered attempts so far
-    int info = 0;
-    for (;;) {
-        g->lr_valid = false;     // residue planes of L belong to one factorisation attempt
-        g->jitter_try = jitter;
-        int ph = phase_begin(g, "kbuild", 0.0, 8.0 * N * g->D + 8.0 * (double)N * N / 2);
-        Members m = ctx_members(g);
-        m.diag = &diag_add;
-        m.jit = &jitter;
-        build_ky(g, m, jitter != 0.0);
-        phase_end(g, ph);
-        HIPCHK(hipMemsetAsync(g->dInfo, 0, sizeof(int) * 4, g->s));
-        if (pipe == 1) {
-            pp.init = [g, mcpad, N, Npad](hipStream_t st) {
-                launch_cross_k(st, g->dT, Npad, g->dXs, g->M, mcpad, g->dX, N, Npad, g->kp);
-            };
-            ph = phase_begin(g, "cholesky+cand_solve", (double)N * N * N / 3.0 + (double)N * N * g->M, 0.0);
-            int rcf = factor_lookahead(g, pp);
-            if (rcf) return rcf;
-        } else if (pipe == 2) {
-            ph = phase_begin(g, "cholesky+potri_stages", (double)N * N * N / 3.0, 0.0);
-            pp.init = [g, Npad](hipStream_t st) { launch_set_identity(st, g->dT, Npad, Npad); };
-            int rcf = factor_lookahead(g, pp);
-            if (rcf) return rcf;
-        } else {
-            ph = phase_begin(g, "cholesky", (double)N * N * N / 3.0, 0.0);
-            // (the emulated trailing update lives in the look-ahead scheduler)
-            if (g->lookahead && nt_ > g->panel_tiles && (nt_ > g->lookahead_min_tiles || emu_fit_applies(g))) {
-                int rcf = factor_lookahead(g);
-                if (rcf) return rcf;
-            } else {
-                int rcf = factor(g);
-                if (rcf) return rcf;
-            }
-        }
-        phase_end(g, ph);
-        HIPCHK(hipMemcpyAsync(&info, g->dInfo, sizeof(int), hipMemcpyDeviceToHost, g->s));
-        GP_SYNC(g->s);
-        if (g->emulate_fp64 && !g->emu_off_call && info == 0) {
-            int bad = 0;
-            HIPCHK(hipMemcpy(&bad, g->dInfo + 2, sizeof(int), hipMemcpyDeviceToHost));
-            if (bad) {
-                // an entry of L outside the fixed-point range (non-finite data): the same attempt again in true fp64, whose
-                // result is what the reference would return for such data
-                g->emu_off_call = true;
-                ++g->emu_fallbacks;
-                g->nphases = 0;
-                g->invp_valid = false;
-                continue;
-            }
+    for (int info = 0, bad = 0;;) {
+        if ((rc = factor_attempt(g, pp, &diag_add, &jitter))) return rc;
+        if ((rc = factor_status(g, g->emulate_fp64 && !g->emu_off_call, &info, &bad))) return rc;
+        if (bad) {
+            // emulation fallback -- an entry of L outside the fixed-point range (non-finite data): the same attempt again in
+            // true fp64, whose result is what the reference would return for such data
+            g->emu_off_call = true;
+            ++g->emu_fallbacks;
+            g->nphases = 0;
+            g->invp_valid = false;
+            continue;
         }
         if (info == 0) break;
         g->invp_valid = false;
-        // jitter ladder, GPy/GPy/util/linalg.py:62-75
         const int rcl = ladder_step(diag0, maxtries, info, &jitter, &tries);
         if (rcl == GP_ERR_NOT_PD_DIAG) return fail(rcl, "not pd: non-positive diagonal elements");
         if (rcl) {
@@ -500,59 +523,38 @@ int fit_impl(gp_ctx *g, int maxtries, int pipe, int include_noise) {
         g->nphases = 0;
     }
     g->jitter = jitter;
-    // alpha = L^-T z, log det and alpha'y: 45 short dependent launches (latency-bound, 1 ms).  When candidate / L^-T
-    // stages are still to run on the main stream they go on the side stream instead, beside those long launches.
-    bool side_alpha = false;
-    if (pipe) {
-        const int W = std::min(g->panel_tiles, nt_);
-        const int nJ = (nt_ + W - 1) / W;
-        if (g->pipe_done < nJ) {  // the remaining stages on the main stream, every CU
-            int phr = phase_begin(g, pipe == 2 ? "potri_solve_rest" : "cand_solve_rest", 0.0, 0.0);
-            int rci = ensure_panel_inv(g);
-            if (rci) return rci;
-            hipEvent_t eI = la_event(g, EV_MISC, 5);
-            if (g->s_inv && g->side_alpha) GP_NOTE(hipEventRecord(eI, g->s));
-            // the long launches first: the 45 short launches of alpha / log det take the host 0.7 ms to enqueue, during which
-            // the main stream sat empty when they went first
-            solve_rows(g, ctx_members(g), (int)(mcpad / GP_TILE), pipe == 2 ? 1 : 0, g->pipe_done);
-            if (g->s_inv && g->side_alpha) {
-                GP_NOTE(hipStreamWaitEvent(g->s_inv, eI, 0));
-                alpha_lml(g, g->s_inv, ctx_members(g));
-                GP_NOTE(hipEventRecord(la_event(g, EV_MISC, 6), g->s_inv));
-                side_alpha = true;
-            }
-            phase_end(g, phr);
-        }
-        if (pipe == 2) {
-            int rcl = wi_lauum(g);
-            if (rcl) return rcl;
-            g->wi_valid = true;
-            g->w_in_t2 = true;   // dT2 = L^-T of this factor: ensure_linv transposes it instead of solving again
-        }
-    }
 
+    // what the pipe left over, with alpha on the side stream where that pays; Ky^-1 from the identity's solve
+    bool side_alpha = false;
+    if (pp.on && (rc = rest_stages(g, pp, &side_alpha))) return rc;
+    if (kind == Pipe::Identity) {
+        if ((rc = wi_lauum(g))) return rc;
+        g->wi_valid = true;
+        g->w_in_t2 = true;   // dT2 = L^-T of this factor: ensure_linv transposes it instead of solving again
+    }
     int ph = phase_begin(g, "alpha_lml", 2.0 * (double)N * N * P, 8.0 * (double)N * N / 2);
     if (side_alpha) {
         GP_NOTE(hipStreamWaitEvent(g->s, la_event(g, EV_MISC, 6), 0));
     } else {
-        int rci = ensure_panel_inv(g);
-        if (rci) return rci;
+        if ((rc = ensure_panel_inv(g))) return rc;
         alpha_lml(g, g->s, ctx_members(g));
     }
     phase_end(g, ph);
-    if (pipe == 1) {
+    if (kind == Pipe::Candidates) {
         ph = phase_begin(g, "reduce", 0.0, 8.0 * (double)N * g->M);
         launch_predict_reduce(g->s, g->dT2, Npad, g->M, N, g->dA + Npad * Npad, Npad, P, g->kp.variance,
                               include_noise ? g->noise : 0.0, g->dMean, g->dVar);
         phase_end(g, ph);
     }
+
+    // read-back
     std::vector<double> sc(8 + P);
     HIPCHK(hipMemcpyAsync(sc.data(), g->dScal, sizeof(double) * (8 + P), hipMemcpyDeviceToHost, g->s));
     GP_SYNC(g->s);
     g->logdet = sc[0];
     g->lml = lml_from_scalars(N, P, sc.data());
     g->fitted = true;
-    if (pipe == 1) {
+    if (kind == Pipe::Candidates) {
         g->predicted = true;
         g->predicted_noise = include_noise ? 1 : 0;
     }
@@ -564,7 +566,7 @@ extern "C" int gp_fit(gp_t *g, int maxtries, double *lml, double *logdet, double
     if (!g) return fail(GP_ERR_ARG, "null gp");
     GP_DEAD_CHECK(g);
     if (!g->have_data || !g->have_params) return fail(GP_ERR_STATE, "set data and params before gp_fit");
-    int rc = fit_impl(g, maxtries, 0, 0);
+    int rc = fit_impl(g, maxtries, Pipe::None, 0);
     if (rc) return rc;
     if (lml) *lml = g->lml;
     if (logdet) *logdet = g->logdet;
@@ -590,9 +592,9 @@ extern "C" int gp_fit_predict(gp_t *g, int maxtries, int include_noise, double *
                           g->M > g->small_m;
     int rc;
     if (can_pipe) {
-        if ((rc = fit_impl(g, maxtries, 1, include_noise))) return rc;
+        if ((rc = fit_impl(g, maxtries, Pipe::Candidates, include_noise))) return rc;
     } else {
-        if ((rc = fit_impl(g, maxtries, 0, 0))) return rc;
+        if ((rc = fit_impl(g, maxtries, Pipe::None, 0))) return rc;
         if ((rc = ensure_out(g))) return rc;
         if ((rc = run_predict(g, include_noise))) return rc;
     }

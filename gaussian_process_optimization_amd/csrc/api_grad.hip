@@ -66,7 +66,7 @@ extern "C" int gp_fit_grad(gp_t *g, int maxtries, double *lml, double *logdet, d
     const bool emu_wi = g->emulate_fp64 && g->emulate_fit && g->panel_tiles % 2 == 0;
     const bool can_pipe = g->lookahead && nt > g->panel_tiles && !emu_wi;
     int rc;
-    if ((rc = fit_impl(g, maxtries, can_pipe ? 2 : 0, 0))) return rc;
+    if ((rc = fit_impl(g, maxtries, can_pipe ? Pipe::Identity : Pipe::None, 0))) return rc;
     if (lml) *lml = g->lml;
     if (logdet) *logdet = g->logdet;
     if (jitter_used) *jitter_used = g->jitter;

@@ -310,13 +310,17 @@ static inline GemmOpt member_opt(const Members &m, GemmOpt o, long sC, long sA, 
 //   s_inv : invP_J = L_JJ^-1 (the per-panel build of ensure_panel_inv),
 //   s_pred: S[:, J] = T[:, J] invP_J^T ;  T[:, > J] -= S[:, J] L[> J, J]^T
 // so that the candidates' N^2 M flops fill the CUs the latency chain of the late panels leaves idle.
+// (the solve runs on the context's dT / dT2 as T / S)
+enum class Pipe { None, Candidates, Identity };   // what fit_impl pipelines: nothing, the resident candidates' solve, the identity's (L^-T, for Ky^-1)
 struct PredPipe {
     bool on = false;
     int mt = 0;          // candidate row tiles
-    double *T = nullptr, *S = nullptr;
+    int nJ = 0;          // panels of the factor
     std::function<void(hipStream_t)> init;  // fills T (cross covariance / identity) on the candidate stream, beside the factorisation's head
     bool trapezoid = false;  // T is block upper-triangular (the identity: the solve for L^-T), row tiles above the panel's end only
     int stages = 0, start_pct = 0;
+    const char *phase = nullptr, *rest_phase = nullptr;   // profile phases: factorisation with the stages behind it, the stages after it
+    double flops = 0.0;                                    // ... of the former
 };
 
 // The candidate solve S = T L^-T with the running right-hand side's updates  T[:, > J] -= S_J L[> J, J]^T  carried in
@@ -371,6 +375,7 @@ int factor(gp_ctx *g);
 void alpha_lml(gp_ctx *g, hipStream_t s, const Members &m);
 void ky_diag(const KernParams &kp, double noise, double *diag_add, double *diag0);
 int ladder_step(double diag0, int maxtries, int info, double *jitter, int *tries);
+int factor_status(gp_ctx *g, bool emu, int *info, int *bad);
 double lml_from_scalars(long N, int P, const double *scal);
 void build_panel_inv_one(gp_ctx *g, hipStream_t s, int J, int W, int nt);
 int rns_prepare(gp_ctx *g, double jitter, RnsGeom *r);
@@ -379,12 +384,14 @@ int factor_lookahead(gp_ctx *g, const PredPipe &pp = PredPipe());
 int ensure_bulk_stream(gp_ctx *g);
 hipEvent_t la_event(gp_ctx *g, int kind, size_t i);
 int la_events_ok(gp_ctx *g);
+int reserve_panel_inv(gp_ctx *g, int W, int nt);
 int ensure_panel_inv(gp_ctx *g);
 void identity_blocks(hipStream_t s, double *T, long n, int nb);
 void panel_inv_members(gp_ctx *g, const Members &m);
+void solve_step(gp_ctx *g, hipStream_t s, const Members &m, int J, int rows);
 void solve_rows(gp_ctx *g, const Members &m, int mt, int trapezoid, int J_from = 0);
 int solve_rows_rns(gp_ctx *g, double *T, double *S, int mt, const RnsSolveOpt &opt = RnsSolveOpt());
-int fit_impl(gp_ctx *g, int maxtries, int pipe, int include_noise);
+int fit_impl(gp_ctx *g, int maxtries, Pipe kind, int include_noise);
 int run_predict(gp_ctx *g, int include_noise, bool tiles_only = false);   // tiles_only: never the small-M path (the caller uses dT2 as a padded tile operand)
 int ensure_out(gp_ctx *g);
 int run_acq(gp_ctx *g, int type, double par, double fmin, double y_mean, double y_std);

@@ -333,10 +333,9 @@ extern "C" int gp_posterior_samples(gp_t *g, int include_noise, const double *Z,
     // jitchol scales its ladder by the mean of the diagonal of the matrix it factors (linalg.py:62-66: diagA.mean() * 1e-6):
     // here the POSTERIOR covariance, whose diagonal near training points is orders of magnitude below the prior variance
     double diag_stat[2] = {0.0, 0.0};   // trace and smallest entry of the diagonal of the matrix to factor
-    double diag_mean = 0.0;
     double jitter = 0.0;
-    int tries = 0, info = 0;
-    for (;;) {
+    int tries = 0;
+    for (int info = 0, bad = 0;;) {
         launch_kbuild(g->s, C, Mpad, g->dXs, M, Mpad, g->kp, 0.0, 1);  // K(Xs, Xs), identity on the padding rows
         gemm(g, g->s, 1, C, Mpad, g->dT2, Npad, g->dT2, Npad, 1, (int)Npad, TileSet{0, mt, 0, mt, 0});
         if (include_noise) launch_add_diag(g->s, C, Mpad, M, g->noise);
@@ -352,23 +351,18 @@ extern "C" int gp_posterior_samples(gp_t *g, int include_noise, const double *Z,
         cov.invL = invL;
         cov.info = g->dInfo;
         factor_buf(g, cov, mt, mt);
-        HIPCHK(hipMemcpyAsync(&info, g->dInfo, sizeof(int), hipMemcpyDeviceToHost, g->s));
-        GP_SYNC(g->s);
-        if (g->emulate_fp64 && info == 0) {
-            int bad = 0;
-            HIPCHK(hipMemcpy(&bad, g->dInfo + 2, sizeof(int), hipMemcpyDeviceToHost));
-            if (bad) return fail(GP_ERR_STATE, "emulate_fp64: an entry of L left the fixed-point range");
-        }
+        if ((rc = factor_status(g, g->emulate_fp64, &info, &bad))) return rc;
+        if (bad) return fail(GP_ERR_STATE, "emulate_fp64: an entry of L left the fixed-point range");
         if (info == 0) break;
-        // jitchol: mean(diag) * 1e-6 * 10^k (linalg.py:62-75)
-        if (tries == 0) diag_mean = diag_stat[0] / (double)M;
         // np.any(diagA <= 0.) raises before any jitter is tried (linalg.py:61-62): ANY entry, not the mean -- a posterior
         // variance that came out slightly negative at a training point is such an entry
-        if (diag_stat[1] <= 0.0 || !(diag_mean > 0.0)) return fail(GP_ERR_NOT_PD_DIAG, "not pd: non-positive diagonal elements");
-        jitter = tries == 0 ? diag_mean * 1e-6 : jitter * 10.0;
-        if (++tries > maxtries || !std::isfinite(jitter)) {
+        if (diag_stat[1] <= 0.0) return fail(GP_ERR_NOT_PD_DIAG, "not pd: non-positive diagonal elements");
+        // jitchol: mean(diag) * 1e-6 * 10^k (linalg.py:62-75)
+        const int rcl = ladder_step(diag_stat[0] / (double)M, maxtries, info, &jitter, &tries);
+        if (rcl == GP_ERR_NOT_PD_DIAG) return fail(rcl, "not pd: non-positive diagonal elements");
+        if (rcl) {
             g_err = "not positive definite, even with jitter.";
-            return info > 0 ? info : 1;
+            return rcl;
         }
     }
     launch_zero_upper_diag(g->s, C, Mpad, mt);

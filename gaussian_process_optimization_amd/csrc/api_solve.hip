@@ -29,6 +29,13 @@ static void panel_inv_steps(gp_ctx *g, hipStream_t s, double *Wb, long PB, const
     }
 }
 
+// room for the inverted diagonal panels of an nt-tile factor in panels of W tiles, and for their build workspace
+int reserve_panel_inv(gp_ctx *g, int W, int nt) {
+    const long PB = (long)W * GP_TILE, n = (long)((nt + W - 1) / W) * PB * PB;
+    const int rc = g->dInvP.reserve(n);
+    return rc ? rc : g->dInvPw.reserve(n);
+}
+
 void build_panel_inv_one(gp_ctx *g, hipStream_t s, int J, int W, int nt) {
     const long lda = g->Npad;
     const long PB = (long)W * GP_TILE;
@@ -51,8 +58,7 @@ int ensure_panel_inv(gp_ctx *g) {
     const long PB = (long)W * GP_TILE;
     const int nJ = (nt + W - 1) / W, nF = nt / W, Wl = nt % W;
     int rc;
-    if ((rc = g->dInvP.reserve((long)nJ * PB * PB))) return rc;
-    if ((rc = g->dInvPw.reserve((long)nJ * PB * PB))) return rc;
+    if ((rc = reserve_panel_inv(g, W, nt))) return rc;
     double *Wk = g->dInvPw;
     hipStream_t s = g->s;
     launch_set_identity_blocks(s, Wk, PB, nJ);
@@ -96,46 +102,50 @@ void panel_inv_members(gp_ctx *g, const Members &m) {
 // Row solve  S = T L^-T  for `mt` row tiles of T (row-major, ld = Npad); T is consumed as the running
 // right-hand side.  trapezoid = 1: T is block upper-triangular (row tile r is zero left of column tile r:
 // the identity, for L^-T), so panel J only touches the row tiles above its end.
-// m.T / m.T2 are T / S.
+// m.T / m.T2 are T / S, m.W the panel width.
+// S[:, J] = T[:, J] invP_J^T for `rows` row tiles   (invP_J lower triangular: column tile c contracts k <= c)
+static void panel_solve(gp_ctx *g, hipStream_t s, const Members &m, int J, int rows) {
+    const long Npad = g->Npad, PB = (long)m.W * GP_TILE;
+    const int J0 = J * m.W, J1 = std::min(J0 + m.W, (int)(Npad / GP_TILE));
+    GemmOpt o;
+    o.k_end_tri = 1;
+    o.b_sub = J0;
+    gemm(g, s, 0, m.T2, Npad, m.T + (long)J0 * GP_TILE, Npad, m.invP + (long)J * PB * PB, PB, 1, (J1 - J0) * GP_TILE,
+         TileSet{0, rows, J0, J1, 0}, member_opt(m, o, m.sT, m.sT, m.sP));
+}
+// T[:, c0 .. c1) -= S[:, J0 .. J1) L[c0 .. c1, J0 .. J1)^T   (tile columns)
+static void rows_update(gp_ctx *g, hipStream_t s, const Members &m, int J0, int J1, int rows, int c0, int c1) {
+    gemm(g, s, 1, m.T, g->Npad, m.T2 + (long)J0 * GP_TILE, g->Npad, m.A + (long)J0 * GP_TILE, m.lda, 1, (J1 - J0) * GP_TILE,
+         TileSet{0, rows, c0, c1, 0}, member_opt(m, GemmOpt(), m.sT, m.sT, m.sA));
+}
+// One step of the solve on stream s: panel J's product with its inverted diagonal panel, then the update of everything right
+// of it.  (solve_rows's unpaired step, and a pipelined stage of the look-ahead factorisation, whose caller sets m.W itself.)
+void solve_step(gp_ctx *g, hipStream_t s, const Members &m, int J, int rows) {
+    const int nt = (int)(g->Npad / GP_TILE), J0 = J * m.W, J1 = std::min(J0 + m.W, nt);
+    panel_solve(g, s, m, J, rows);
+    if (J1 < nt) rows_update(g, s, m, J0, J1, rows, J1, nt);
+}
+
 void solve_rows(gp_ctx *g, const Members &m, int mt, int trapezoid, int J_from) {
-    const long Npad = g->Npad, lda = m.lda;
-    const int nt = (int)(Npad / GP_TILE), W = m.W;
-    const long PB = (long)W * GP_TILE;
-    double *T = m.T, *S = m.T2;
-    const double *L = m.A;
+    const int nt = (int)(g->Npad / GP_TILE), W = m.W;
     hipStream_t s = g->s;
-    const GemmOpt upd = member_opt(m, GemmOpt(), m.sT, m.sT, m.sA);   // T[:, > J] -= S[:, J] L[> J, J]^T
-    auto panel_solve = [&](int J, int J0, int J1, int rows) {
-        GemmOpt o;
-        o.k_end_tri = 1;
-        o.b_sub = J0;
-        // S[:, J] = T[:, J] invP_J^T   (invP_J lower triangular: column tile c contracts k <= c)
-        gemm(g, s, 0, S, Npad, T + (long)J0 * GP_TILE, Npad, m.invP + (long)J * PB * PB, PB, 1, (J1 - J0) * GP_TILE,
-             TileSet{0, rows, J0, J1, 0}, member_opt(m, o, m.sT, m.sT, m.sP));
-    };
-    for (int J0 = J_from * W, J = J_from; J0 < nt;) {
-        const int J1 = std::min(J0 + W, nt), J2 = std::min(J1 + W, nt);
-        const int Kp = (J1 - J0) * GP_TILE;
+    for (int J = J_from; J * W < nt;) {
+        const int J0 = J * W, J1 = std::min(J0 + W, nt), J2 = std::min(J1 + W, nt);
         const int rows = trapezoid ? std::min(mt, J1) : mt;
-        panel_solve(J, J0, J1, rows);
-        if (J1 >= nt) break;
         // Two panels per update (full row sets only): panel J+1's columns take panel J's update as a small launch of
         // their own, then ONE launch contracts both panels (K = 2 PB) into everything right of them -- half the round
         // trips of the running right-hand side through HBM and a contraction twice as long.  The accumulator sees the
         // same products in the same order as with one launch per panel: bitwise the same result.
         const bool two = g->pair_panels && !trapezoid && J2 > J1 && J2 < nt;
         if (!two) {
-            gemm(g, s, 1, T, Npad, S + (long)J0 * GP_TILE, Npad, L + (long)J0 * GP_TILE, lda, 1, Kp,
-                 TileSet{0, rows, J1, nt, 0}, upd);
-            J0 = J1;
+            solve_step(g, s, m, J, rows);
             ++J;
             continue;
         }
-        gemm(g, s, 1, T, Npad, S + (long)J0 * GP_TILE, Npad, L + (long)J0 * GP_TILE, lda, 1, Kp, TileSet{0, rows, J1, J2, 0}, upd);
-        panel_solve(J + 1, J1, J2, rows);
-        gemm(g, s, 1, T, Npad, S + (long)J0 * GP_TILE, Npad, L + (long)J0 * GP_TILE, lda, 1, (J2 - J0) * GP_TILE,
-             TileSet{0, rows, J2, nt, 0}, upd);
-        J0 = J2;
+        panel_solve(g, s, m, J, rows);
+        rows_update(g, s, m, J0, J1, rows, J1, J2);
+        panel_solve(g, s, m, J + 1, rows);
+        rows_update(g, s, m, J0, J2, rows, J2, nt);
         J += 2;
     }
 }

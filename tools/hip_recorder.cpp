@@ -1,0 +1,109 @@
+// hip_recorder: a stand-in for the HIP runtime (and RCCL) that runs NO kernel and needs no GPU.  Device memory is host memory
+// from a bump allocator, copies are memcpy, and every call that orders or feeds a stream is written to $HIP_RECORDER_LOG in host
+// order: launches (kernel, grid, block, LDS, stream; for gemm_nt_kernel every field of its GemmArgs, pointers as allocation index +
+// offset), hipEventRecord, hipStreamWaitEvent, memsets, copies, synchronisations, allocations.  Streams and events are numbered by
+// first appearance.  The numbers an entry point returns are meaningless (zeros); the factorisation's status word reads 0, so a
+// fit takes its first attempt ($HIP_RECORDER_FAIL=n: the first n status words read 1 instead, which walks the jitter ladder).
+// What it is for: a refactor of host code must leave this log unchanged.
+//
+// Build a recording libgphip.so from the objects of a normal build (make -C gaussian_process_optimization_amd/csrc), in a copy
+// of the package outside the tree:
+//   g++ -O1 -fPIC -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -c tools/hip_recorder.cpp -o hip_recorder.o
+//   g++ -shared -fPIC gaussian_process_optimization_amd/csrc/*.o hip_recorder.o -o <copy>/gaussian_process_optimization_amd/libgphip.so
+//   PYTHONPATH=<copy> HIP_RECORDER_LOG=case1.log python tools/stream_ops.py 1
+// (struct GemmArgs below mirrors csrc/gemm.hip.)
+#include <hip/hip_runtime_api.h>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <map>
+#include <string>
+#include <sys/mman.h>
+#include <vector>
+// device memory: a bump allocator over one reserved range, so that a pointer prints as allocation index + offset
+static char *g_base = nullptr;
+static size_t g_top = 0;
+static std::vector<std::pair<size_t, size_t>> g_allocs;   // offset, size
+static void *dev_alloc(size_t n) {
+    if (!g_base) g_base = (char *)mmap(nullptr, 1ul << 37, PROT_READ | PROT_WRITE, MAP_PRIVATE | MAP_ANONYMOUS | MAP_NORESERVE, -1, 0);
+    n = (n + 4095) / 4096 * 4096 + 4096;
+    void *p = g_base + g_top;
+    g_allocs.push_back({g_top, n});
+    g_top += n;
+    return p;
+}
+static std::string pname(const void *p) {
+    char b[64];
+    if (!p) return "null";
+    const size_t o = (const char *)p - g_base;
+    for (size_t i = g_allocs.size(); i-- > 0;)
+        if (o >= g_allocs[i].first && o < g_allocs[i].first + g_allocs[i].second) { snprintf(b, 64, "a%zu+%zu", i, o - g_allocs[i].first); return b; }
+    return "host";
+}
+struct GemmArgs { double *C; long ldc; const double *A; long lda; const double *B; long ldb; int b_mul, K, r0, r1, c0, c1, tri, k_tri, k_sub, k_end_tri, b_sub; long sC, sA, sB; const short *tile_list; int stagger, pair; };
+static FILE *lg() { static FILE *f = fopen(getenv("HIP_RECORDER_LOG") ? getenv("HIP_RECORDER_LOG") : "/dev/null", "w"); return f; }
+static std::map<const void *, std::string> &kn() { static std::map<const void *, std::string> m; return m; }
+static std::map<const void *, int> g_s, g_e;
+static int sid(const void *s) { auto it = g_s.find(s); if (it == g_s.end()) it = g_s.emplace(s, (int)g_s.size()).first; return it->second; }
+static int eid(const void *e) { auto it = g_e.find(e); if (it == g_e.end()) it = g_e.emplace(e, (int)g_e.size()).first; return it->second; }
+struct Cfg { dim3 g, b; size_t sh; hipStream_t s; };
+static thread_local Cfg g_cfg;
+extern "C" {
+void **__hipRegisterFatBinary(const void *) { return (void **)malloc(8); }
+void __hipUnregisterFatBinary(void **) {}
+void __hipRegisterFunction(void **, const void *host, char *, const char *name, unsigned, void *, void *, void *, void *, int *) { kn()[host] = name; }
+void __hipRegisterVar(void **, void *, char *, char *, int, size_t, int, int) {}
+hipError_t __hipPushCallConfiguration(dim3 g, dim3 b, size_t sh, hipStream_t s) { g_cfg = Cfg{g, b, sh, s}; return hipSuccess; }
+hipError_t __hipPopCallConfiguration(dim3 *g, dim3 *b, size_t *sh, hipStream_t *s) { *g = g_cfg.g; *b = g_cfg.b; *sh = g_cfg.sh; *s = g_cfg.s; return hipSuccess; }
+hipError_t hipLaunchKernel(const void *f, dim3 g, dim3 b, void **args, size_t sh, hipStream_t s) {
+    const std::string name = kn().count(f) ? kn()[f] : "?";
+    fprintf(lg(), "launch %s grid %u,%u,%u block %u,%u,%u shmem %zu s%d", name.c_str(), g.x, g.y, g.z, b.x, b.y, b.z, sh, sid(s));
+    if (name.find("gemm_nt_kernel") != std::string::npos) {
+        const GemmArgs &a = *(const GemmArgs *)args[0];
+        fprintf(lg(), " C %s ldc %ld A %s lda %ld B %s ldb %ld b_mul %d K %d ts %d,%d,%d,%d,%d ktri %d ksub %d kend %d bsub %d s %ld,%ld,%ld list %s stag %d pair %d",
+                pname(a.C).c_str(), a.ldc, pname(a.A).c_str(), a.lda, pname(a.B).c_str(), a.ldb, a.b_mul, a.K, a.r0, a.r1, a.c0, a.c1, a.tri, a.k_tri, a.k_sub,
+                a.k_end_tri, a.b_sub, a.sC, a.sA, a.sB, pname(a.tile_list).c_str(), a.stagger, a.pair);
+    }
+    fprintf(lg(), "\n");
+    return hipSuccess;
+}
+hipError_t hipDeviceGetStreamPriorityRange(int *lo, int *hi) { *lo = 0; *hi = -1; return hipSuccess; }
+hipError_t hipDeviceSynchronize() { fprintf(lg(), "devsync\n"); return hipSuccess; }
+hipError_t hipEventCreate(hipEvent_t *e) { *e = (hipEvent_t)malloc(1); return hipSuccess; }
+hipError_t hipEventCreateWithFlags(hipEvent_t *e, unsigned) { *e = (hipEvent_t)malloc(1); return hipSuccess; }
+hipError_t hipEventDestroy(hipEvent_t) { return hipSuccess; }
+hipError_t hipEventElapsedTime(float *ms, hipEvent_t, hipEvent_t) { *ms = 0.f; return hipSuccess; }
+hipError_t hipEventRecord(hipEvent_t e, hipStream_t s) { fprintf(lg(), "record e%d s%d\n", eid(e), sid(s)); return hipSuccess; }
+hipError_t hipStreamWaitEvent(hipStream_t s, hipEvent_t e, unsigned) { fprintf(lg(), "wait s%d e%d\n", sid(s), eid(e)); return hipSuccess; }
+hipError_t hipExtStreamCreateWithCUMask(hipStream_t *s, uint32_t, const uint32_t *) { *s = (hipStream_t)malloc(1); return hipSuccess; }
+hipError_t hipStreamCreateWithFlags(hipStream_t *s, unsigned) { *s = (hipStream_t)malloc(1); return hipSuccess; }
+hipError_t hipStreamCreateWithPriority(hipStream_t *s, unsigned, int) { *s = (hipStream_t)malloc(1); return hipSuccess; }
+hipError_t hipStreamDestroy(hipStream_t) { return hipSuccess; }
+hipError_t hipStreamSynchronize(hipStream_t s) { fprintf(lg(), "sync s%d\n", sid(s)); return hipSuccess; }
+hipError_t hipFree(void *p) { fprintf(lg(), "free %s\n", pname(p).c_str()); return hipSuccess; }
+hipError_t hipHostFree(void *p) { free(p); return hipSuccess; }
+hipError_t hipHostMalloc(void **p, size_t n, unsigned) { *p = calloc(1, n); return hipSuccess; }
+hipError_t hipMalloc(void **p, size_t n) { *p = dev_alloc(n); fprintf(lg(), "malloc %zu\n", n); return *p ? hipSuccess : hipErrorOutOfMemory; }
+hipError_t hipGetDeviceCount(int *n) { *n = 1; return hipSuccess; }
+hipError_t hipGetDevicePropertiesR0600(hipDeviceProp_tR0600 *p, int) { memset(p, 0, sizeof *p); p->multiProcessorCount = 256; strcpy(p->name, "recorder"); strcpy(p->gcnArchName, "gfx950"); return hipSuccess; }
+const char *hipGetErrorString(hipError_t) { return "recorder"; }
+hipError_t hipGetLastError() { return hipSuccess; }
+hipError_t hipMemcpy(void *d, const void *s, size_t n, hipMemcpyKind k) { fprintf(lg(), "memcpy %zu kind %d\n", n, (int)k); memcpy(d, s, n); return hipSuccess; }
+hipError_t hipMemcpyAsync(void *d, const void *s, size_t n, hipMemcpyKind k, hipStream_t st) {
+    static int fail = getenv("HIP_RECORDER_FAIL") ? atoi(getenv("HIP_RECORDER_FAIL")) : 0;
+    fprintf(lg(), "memcpyAsync %zu kind %d s%d\n", n, (int)k, sid(st));
+    memcpy(d, s, n);
+    if (n == sizeof(int) && k == hipMemcpyDeviceToHost && fail > 0 && fail--) *(int *)d = 1;   // a status word that reports a failed pivot
+    return hipSuccess;
+}
+static void cp2d(void *d, size_t dp, const void *s, size_t sp, size_t w, size_t h) { for (size_t i = 0; i < h; ++i) memcpy((char *)d + i * dp, (const char *)s + i * sp, w); }
+hipError_t hipMemcpy2D(void *d, size_t dp, const void *s, size_t sp, size_t w, size_t h, hipMemcpyKind k) { fprintf(lg(), "memcpy2D %zu x %zu kind %d\n", w, h, (int)k); cp2d(d, dp, s, sp, w, h); return hipSuccess; }
+hipError_t hipMemcpy2DAsync(void *d, size_t dp, const void *s, size_t sp, size_t w, size_t h, hipMemcpyKind k, hipStream_t st) { fprintf(lg(), "memcpy2DAsync %zu x %zu kind %d s%d\n", w, h, (int)k, sid(st)); cp2d(d, dp, s, sp, w, h); return hipSuccess; }
+hipError_t hipMemcpyToSymbol(const void *, const void *, size_t, size_t, hipMemcpyKind) { return hipSuccess; }
+hipError_t hipMemset(void *d, int v, size_t n) { fprintf(lg(), "memset %zu\n", n); if (n <= (1 << 20)) memset(d, v, n); return hipSuccess; }
+hipError_t hipMemsetAsync(void *d, int v, size_t n, hipStream_t s) { fprintf(lg(), "memsetAsync %zu s%d\n", n, sid(s)); if (n <= (1 << 20)) memset(d, v, n); return hipSuccess; }
+hipError_t hipSetDevice(int) { return hipSuccess; }
+int ncclAllGather() { return 0; } int ncclBroadcast() { return 0; } int ncclCommAbort() { return 0; } int ncclCommCount() { return 0; }
+int ncclCommDestroy() { return 0; } int ncclCommInitAll() { return 0; } int ncclCommInitRank() { return 0; } int ncclCommUserRank() { return 0; }
+const char *ncclGetErrorString() { return "recorder"; } int ncclGetUniqueId() { return 0; } int ncclGetVersion() { return 0; } int ncclGroupEnd() { return 0; } int ncclGroupStart() { return 0; }
+}
