@@ -174,6 +174,21 @@ def check(lib, rc, what):
     raise RuntimeError("%s failed (%d): %s" % (what, rc, msg))
 
 
+def _fit_scalars():
+    """The (lml, logdet, jitter) out-parameters of the fit entry points."""
+    return ctypes.c_double(), ctypes.c_double(), ctypes.c_double()
+
+
+def _lp_args(Xb, r_x0, s_x0):
+    """The penaliser's batch as (arrays kept alive, nb, pointers to Xb, r_x0, s_x0); no batch is nb = 0 and null pointers."""
+    if Xb is None:
+        return None, 0, None, None, None
+    Xb = as_f64(np.atleast_2d(Xb), 2)
+    r = as_f64(np.atleast_1d(r_x0), 1)
+    s = as_f64(np.atleast_1d(s_x0), 1)
+    return (Xb, r, s), Xb.shape[0], dptr(Xb), dptr(r), dptr(s)
+
+
 class Handle(object):
     """Owns one gp_t (one device)."""
 
@@ -235,14 +250,14 @@ class Handle(object):
         check(self.lib, self.lib.gp_set_gower(self.h, 1, disc.ctypes.data_as(c_int_p), dptr(rng)), "gp_set_gower")
 
     def fit(self, maxtries=5):
-        lml, logdet, jit = ctypes.c_double(), ctypes.c_double(), ctypes.c_double()
+        lml, logdet, jit = _fit_scalars()
         rc = self.lib.gp_fit(self.h, int(maxtries), ctypes.byref(lml), ctypes.byref(logdet), ctypes.byref(jit))
         check(self.lib, rc, "gp_fit")
         return lml.value, logdet.value, jit.value
 
     def fit_predict(self, include_noise=True, maxtries=5):
         """gp_fit + gp_predict on the resident candidates as one pipelined pass."""
-        lml, logdet, jit = ctypes.c_double(), ctypes.c_double(), ctypes.c_double()
+        lml, logdet, jit = _fit_scalars()
         mean = np.empty((self.M, self.P))
         var = np.empty((self.M, 1))
         rc = self.lib.gp_fit_predict(self.h, int(maxtries), int(bool(include_noise)), ctypes.byref(lml),
@@ -252,7 +267,7 @@ class Handle(object):
 
     def fit_grad(self, nls, maxtries=5):
         """gp_fit + gp_lml_grad as one call: ((lml, logdet, jitter), (dvariance, dlengthscale[nls], dnoise))."""
-        lml, logdet, jit = ctypes.c_double(), ctypes.c_double(), ctypes.c_double()
+        lml, logdet, jit = _fit_scalars()
         dv, dn = ctypes.c_double(), ctypes.c_double()
         dl = self._grad_ls(nls)
         rc = self.lib.gp_fit_grad(self.h, int(maxtries), ctypes.byref(lml), ctypes.byref(logdet), ctypes.byref(jit),
@@ -286,7 +301,7 @@ class Handle(object):
         return (lml, logdet, jit), (dv, dl, dn), status
 
     def fit_state(self):
-        lml, logdet, jit = ctypes.c_double(), ctypes.c_double(), ctypes.c_double()
+        lml, logdet, jit = _fit_scalars()
         check(self.lib, self.lib.gp_get_fit_state(self.h, ctypes.byref(lml), ctypes.byref(logdet), ctypes.byref(jit)),
               "gp_get_fit_state")
         return lml.value, logdet.value, jit.value
@@ -459,16 +474,8 @@ class Handle(object):
         check(self.lib, self.lib.gp_rows_stats(self.h, ctypes.byref(a), ctypes.byref(b)), "gp_rows_stats")
         return dict(fused=a.value, fallback=b.value)
 
-    def _lp_args(self, Xb, r_x0, s_x0):
-        if Xb is None:
-            return None, 0, None, None, None
-        Xb = as_f64(np.atleast_2d(Xb), 2)
-        r = as_f64(np.atleast_1d(r_x0), 1)
-        s = as_f64(np.atleast_1d(s_x0), 1)
-        return (Xb, r, s), Xb.shape[0], dptr(Xb), dptr(r), dptr(s)
-
     def acq_lp(self, type_, par, fmin, transform, Xb=None, r_x0=None, s_x0=None, y_mean=0.0, y_std=1.0):
-        keep, nb, pX, pr, ps = self._lp_args(Xb, r_x0, s_x0)
+        keep, nb, pX, pr, ps = _lp_args(Xb, r_x0, s_x0)
         out = np.empty(self.M)
         check(self.lib, self.lib.gp_acq_lp(self.h, int(type_), float(par), float(fmin), float(y_mean), float(y_std),
                                            int(transform), pX, nb, pr, ps, dptr(out)), "gp_acq_lp")
@@ -476,7 +483,7 @@ class Handle(object):
 
     def acq_lp_grad(self, type_, par, fmin, transform, Xb=None, r_x0=None, s_x0=None, y_mean=0.0, y_std=1.0):
         """Penalised acquisition and its gradient at the resident candidates: (value[M], gradient[M, D])."""
-        keep, nb, pX, pr, ps = self._lp_args(Xb, r_x0, s_x0)
+        keep, nb, pX, pr, ps = _lp_args(Xb, r_x0, s_x0)
         out = np.empty(self.M)
         dout = np.empty((self.M, self.D))
         check(self.lib, self.lib.gp_acq_lp_grad(self.h, int(type_), float(par), float(fmin), float(y_mean), float(y_std),
@@ -485,7 +492,7 @@ class Handle(object):
 
     def acq_lp_argbest(self, type_, par, fmin, transform, sense, Xb=None, r_x0=None, s_x0=None, exclude=(),
                        y_mean=0.0, y_std=1.0):
-        keep, nb, pX, pr, ps = self._lp_args(Xb, r_x0, s_x0)
+        keep, nb, pX, pr, ps = _lp_args(Xb, r_x0, s_x0)
         ex = np.asarray(list(exclude), dtype=np.int64)
         idx, val = ctypes.c_int64(), ctypes.c_double()
         check(self.lib, self.lib.gp_acq_lp_argbest(self.h, int(type_), float(par), float(fmin), float(y_mean),
@@ -636,7 +643,7 @@ class Group(object):
         check(self.lib, self.lib.gp_group_set_option(self.h, name.encode(), int(value)), "gp_group_set_option")
 
     def fit(self, maxtries=5):
-        lml, logdet, jit = ctypes.c_double(), ctypes.c_double(), ctypes.c_double()
+        lml, logdet, jit = _fit_scalars()
         check(self.lib, self.lib.gp_group_fit(self.h, int(maxtries), ctypes.byref(lml), ctypes.byref(logdet),
                                               ctypes.byref(jit)), "gp_group_fit")
         return lml.value, logdet.value, jit.value
@@ -662,11 +669,7 @@ class Group(object):
 
     def acq_lp_argbest(self, type_, par, fmin, transform, sense, Xb=None, r_x0=None, s_x0=None, exclude=(), y_mean=0.0,
                        y_std=1.0):
-        if Xb is None:
-            keep, nb, pX, pr, ps = None, 0, None, None, None
-        else:
-            Xb, r, sc = as_f64(np.atleast_2d(Xb), 2), as_f64(np.atleast_1d(r_x0), 1), as_f64(np.atleast_1d(s_x0), 1)
-            keep, nb, pX, pr, ps = (Xb, r, sc), Xb.shape[0], dptr(Xb), dptr(r), dptr(sc)
+        keep, nb, pX, pr, ps = _lp_args(Xb, r_x0, s_x0)
         ex = np.asarray(list(exclude), dtype=np.int64)
         idx, val = ctypes.c_int64(), ctypes.c_double()
         check(self.lib, self.lib.gp_group_acq_lp_argbest(self.h, int(type_), float(par), float(fmin), float(y_mean),

@@ -31,7 +31,7 @@ extern "C" int gp_fit_grad_batch(gp_t *g, int R, const double *variance, const d
     if (g->Npad > GP_BATCH_MAX_NPAD)
         return fail(GP_ERR_ARG, "gp_fit_grad_batch covers Npad <= %d (N = %ld pads to %ld): use gp_fit_grad", GP_BATCH_MAX_NPAD,
                     g->N, g->Npad);
-    if (g->P > 16) return fail(GP_ERR_ARG, "gp_fit_grad_batch supports P <= 16");
+    if (g->P > GP_GRAD_MAX_P) return fail(GP_ERR_ARG, "gp_fit_grad_batch supports P <= %d", GP_GRAD_MAX_P);
     const int D = g->D, nls = g->ard ? D : 1;
     for (int r = 0; r < R; ++r) {
         if (!(variance[r] > 0.0)) return fail(GP_ERR_ARG, "member %d: variance must be positive", r);
@@ -53,7 +53,7 @@ extern "C" int gp_fit_grad_batch(gp_t *g, int R, const double *variance, const d
     m.sP = (long)nJ * PB * PB;
     m.sV = (long)P * Npad;
     m.sT = Npad * Npad;
-    m.sS = 64 + 4 * GP_GRAD_NACC;   // (D <= 64: 4 gradient passes)
+    m.sS = SCAL_GRAD.off + SCAL_GRAD.len;   // log det, alpha . y and every gradient pass's sums of a member
     const long per = m.sA + m.sI + 2 * m.sP + 2 * m.sV + 2 * m.sT + m.sS + 2;
     int rc;
     if ((rc = g->dBatch.reserve(per * R))) return rc;
@@ -137,10 +137,10 @@ extern "C" int gp_fit_grad_batch(gp_t *g, int R, const double *variance, const d
             continue;
         }
         const double *s = sc.data() + (size_t)m.sS * r;
-        logdet[r] = s[0];
+        logdet[r] = s[SCAL_LOGDET.off];
         lml[r] = lml_from_scalars(N, P, s);
         jitter_used[r] = jit[r];
-        grads_from_sums(s + 64, kp[r], g->ard, &dvariance[r], &dlengthscale[(long)r * nls], &dnoise[r]);
+        grads_from_sums(s + SCAL_GRAD.off, kp[r], g->ard, &dvariance[r], &dlengthscale[(long)r * nls], &dnoise[r]);
     }
     return 0;
 }

@@ -61,29 +61,52 @@ extern "C" int gp_comm_destroy(gp_t *g) {
     return 0;
 }
 
-extern "C" int gp_comm_allgather_best(gp_t *g, double val, int64_t idx, double *vals, int64_t *idxs) {
-    if (!g || !vals || !idxs) return fail(GP_ERR_ARG, "null argument");
+// ---- the all-gather of {value, row} records ---------------------------------------------------------------------------------
+// A record moves as 2 x 8 bytes: the value, and the row's bits in a double's place.
+void pack_pairs(const double *v, const int64_t *ix, size_t n, double *rec) {
+    for (size_t j = 0; j < n; ++j) {
+        rec[2 * j] = v[j];
+        memcpy(&rec[2 * j + 1], &ix[j], 8);
+    }
+}
+void unpack_pairs(const double *rec, size_t n, double *v, int64_t *ix) {
+    for (size_t j = 0; j < n; ++j) {
+        v[j] = rec[2 * j];
+        memcpy(&ix[j], &rec[2 * j + 1], 8);
+    }
+}
+
+// a live context with a communicator, its device current
+static int comm_ready(gp_ctx *g) {
     GP_DEAD_CHECK(g);
     if (!g->comm) return fail(GP_ERR_STATE, "gp_comm_init first");
-    if (g->nranks > 128) return fail(GP_ERR_ARG, "nranks > 128");
+    if (g->nranks > GP_COMM_MAX_RANKS) return fail(GP_ERR_ARG, "nranks > %d", GP_COMM_MAX_RANKS);
     HIPCHK(hipSetDevice(g->device));
-    // one 16-byte record per rank: {double val, int64 idx} moved as 2 x 8 bytes
-    double *send = g->dRedV + 300;       // 2 doubles
-    double *recv = g->dRedV + 304;       // 2 * nranks doubles (<= 208 here: nranks <= 100)
-    if (2 * g->nranks > 200) return fail(GP_ERR_ARG, "nranks too large for the gather scratch");
-    double rec[2];
-    rec[0] = val;
-    memcpy(&rec[1], &idx, 8);
-    HIPCHK(hipMemcpyAsync(send, rec, 16, hipMemcpyHostToDevice, g->s));
-    NCCLCHK(ncclAllGather(send, recv, 2, ncclDouble, g->comm, g->s));
-    std::vector<double> out(2 * g->nranks);
-    HIPCHK(hipMemcpyAsync(out.data(), recv, 16 * g->nranks, hipMemcpyDeviceToHost, g->s));
-    GP_SYNC(g->s);
-    for (int r = 0; r < g->nranks; ++r) {
-        vals[r] = out[2 * r];
-        memcpy(&idxs[r], &out[2 * r + 1], 8);
-    }
     return 0;
+}
+
+// k records of this rank through the device slots send / recv (recv holds recv_len doubles); every rank's, in rank order, come back
+static int allgather_pairs(gp_ctx *g, int k, const double *vals, const int64_t *idxs, double *send, double *recv, long recv_len,
+                           double *all_vals, int64_t *all_idxs) {
+    if (2L * k * g->nranks > recv_len) return fail(GP_ERR_ARG, "nranks too large for the gather scratch");
+    const size_t nd = 2 * (size_t)k;
+    std::vector<double> rec(nd), out(nd * g->nranks);
+    pack_pairs(vals, idxs, k, rec.data());
+    HIPCHK(hipMemcpyAsync(send, rec.data(), sizeof(double) * nd, hipMemcpyHostToDevice, g->s));
+    NCCLCHK(ncclAllGather(send, recv, nd, ncclDouble, g->comm, g->s));
+    HIPCHK(hipMemcpyAsync(out.data(), recv, sizeof(double) * out.size(), hipMemcpyDeviceToHost, g->s));
+    GP_SYNC(g->s);
+    unpack_pairs(out.data(), (size_t)k * g->nranks, all_vals, all_idxs);
+    return 0;
+}
+
+// (one record a rank: a slot of the reduction scratch serves, no buffer of its own)
+extern "C" int gp_comm_allgather_best(gp_t *g, double val, int64_t idx, double *vals, int64_t *idxs) {
+    if (!g || !vals || !idxs) return fail(GP_ERR_ARG, "null argument");
+    int rc;
+    if ((rc = comm_ready(g))) return rc;
+    return allgather_pairs(g, 1, &val, &idx, g->dRedV + REDV_GATHER_SEND.off, g->dRedV + REDV_GATHER_RECV.off, REDV_GATHER_RECV.len,
+                           vals, idxs);
 }
 
 // The fit's host scalars ride along with the factor as one small record; a receiving rank takes them over and drops
@@ -116,7 +139,8 @@ extern "C" int gp_comm_bcast_fit(gp_t *g, int root) {
     // (y - (noise + 1e-8 + jitter) alpha) and reports the root's LML / log det
     double rec[GP_FIT_RECORD_LEN];
     pack_fit_record(g, rec);
-    double *dRec = g->dScal + 400;
+    static_assert(GP_FIT_RECORD_LEN == SCAL_FIT_RECORD.len, "the fit record's slot");
+    double *dRec = g->dScal + SCAL_FIT_RECORD.off;
     if (g->rank == root) HIPCHK(hipMemcpyAsync(dRec, rec, sizeof rec, hipMemcpyHostToDevice, g->s));
     NCCLCHK(ncclGroupStart());
     NCCLCHK(ncclBroadcast(g->dA, g->dA, (size_t)(Npad + GP_MAX_RHS) * Npad, ncclDouble, root, g->comm, g->s));
@@ -159,28 +183,9 @@ extern "C" int gp_comm_selftest_fit_record(const double *root_state, double *sta
 extern "C" int gp_comm_allgather_topk(gp_t *g, int k, const double *vals, const int64_t *idxs, double *all_vals,
                            int64_t *all_idxs) {
     if (!g || !vals || !idxs || !all_vals || !all_idxs) return fail(GP_ERR_ARG, "null argument");
-    GP_DEAD_CHECK(g);
-    if (!g->comm) return fail(GP_ERR_STATE, "gp_comm_init first");
-    if (k < 1 || k > GP_TOPK_MAX) return fail(GP_ERR_ARG, "k out of range (1..%d)", GP_TOPK_MAX);
-    if (g->nranks > 128) return fail(GP_ERR_ARG, "nranks > 128");
-    HIPCHK(hipSetDevice(g->device));
     int rc;
-    if ((rc = g->dComm.reserve(2L * GP_TOPK_MAX * (1 + 128)))) return rc;
-    // k records of {double val, int64 idx} per rank, moved as 2k x 8 bytes
-    std::vector<double> rec(2 * (size_t)k);
-    for (int j = 0; j < k; ++j) {
-        rec[2 * j] = vals[j];
-        memcpy(&rec[2 * j + 1], &idxs[j], 8);
-    }
-    double *send = g->dComm, *recv = g->dComm + 2 * GP_TOPK_MAX;
-    HIPCHK(hipMemcpyAsync(send, rec.data(), 16 * (size_t)k, hipMemcpyHostToDevice, g->s));
-    NCCLCHK(ncclAllGather(send, recv, 2 * (size_t)k, ncclDouble, g->comm, g->s));
-    std::vector<double> out(2 * (size_t)k * g->nranks);
-    HIPCHK(hipMemcpyAsync(out.data(), recv, 16 * (size_t)k * g->nranks, hipMemcpyDeviceToHost, g->s));
-    GP_SYNC(g->s);
-    for (size_t r = 0; r < (size_t)k * g->nranks; ++r) {
-        all_vals[r] = out[2 * r];
-        memcpy(&all_idxs[r], &out[2 * r + 1], 8);
-    }
-    return 0;
+    if ((rc = comm_ready(g))) return rc;
+    if ((rc = check_k(k))) return rc;
+    if ((rc = g->dComm.reserve(COMM_CAP))) return rc;
+    return allgather_pairs(g, k, vals, idxs, g->dComm + COMM_SEND.off, g->dComm + COMM_RECV.off, COMM_RECV.len, all_vals, all_idxs);
 }

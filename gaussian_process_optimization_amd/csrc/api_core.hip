@@ -299,9 +299,9 @@ extern "C" int gp_create(gp_t **out, int device) {
         g->s_pred = d.pred;
     }
     int rc = g->dInfo.reserve(4);
-    if (!rc) rc = g->dScal.reserve(512);
-    if (!rc) rc = g->dRedV.reserve(512);
-    if (!rc) rc = g->dRedI.reserve(1024);
+    if (!rc) rc = g->dScal.reserve(SCAL_CAP);
+    if (!rc) rc = g->dRedV.reserve(REDV_CAP);
+    if (!rc) rc = g->dRedI.reserve(REDI_CAP);
     if (rc) {
         delete g;
         return rc;
@@ -608,9 +608,7 @@ int la_events_ok(gp_ctx *g) {
 
 extern "C" int gp_get_alpha(gp_t *g, double *alpha) {
     if (!g || !alpha) return fail(GP_ERR_ARG, "null argument");
-    GP_DEAD_CHECK(g);
-    if (!g->fitted) return fail(GP_ERR_STATE, "gp_fit first");
-    HIPCHK(hipSetDevice(g->device));
+    GP_FITTED(g);
     std::vector<double> tmp((size_t)g->P * g->Npad);
     HIPCHK(hipMemcpy(tmp.data(), g->dAlpha, sizeof(double) * g->P * g->Npad, hipMemcpyDeviceToHost));
     for (long i = 0; i < g->N; ++i)
@@ -620,9 +618,7 @@ extern "C" int gp_get_alpha(gp_t *g, double *alpha) {
 
 extern "C" int gp_get_chol(gp_t *g, double *L) {
     if (!g || !L) return fail(GP_ERR_ARG, "null argument");
-    GP_DEAD_CHECK(g);
-    if (!g->fitted) return fail(GP_ERR_STATE, "gp_fit first");
-    HIPCHK(hipSetDevice(g->device));
+    GP_FITTED(g);
     const long N = g->N;
     HIPCHK(hipMemcpy2D(L, sizeof(double) * N, g->dA, sizeof(double) * g->Npad, sizeof(double) * N, N,
                        hipMemcpyDeviceToHost));

@@ -347,9 +347,9 @@ static void launch_dot_ay(hipStream_t s, const double *alpha, long lda_, const d
 // log det, alpha = L^-T z and alpha . y of m's members: 45 short dependent launches
 void alpha_lml(gp_ctx *g, hipStream_t s, const Members &m) {
     const long Npad = g->Npad;
-    launch_logdet(s, m.A, m.lda, g->N, m.scal, m.nb, m.sA, m.sS);
+    launch_logdet(s, m.A, m.lda, g->N, m.scal + SCAL_LOGDET.off, m.nb, m.sA, m.sS);
     launch_trsv_backward(s, m.A, m.lda, m.invP, m.W, Npad, m.A + Npad * m.lda, m.lda, g->P, m.alpha, m.w, m.nb, m.sA, m.sP, m.sV);
-    launch_dot_ay(s, m.alpha, Npad, g->dY, g->N, g->P, m.scal + 8, m.nb, m.sV, m.sS);
+    launch_dot_ay(s, m.alpha, Npad, g->dY, g->N, g->P, m.scal + SCAL_DOT.off, m.nb, m.sV, m.sS);
 }
 
 // ---- host arithmetic of one fit, per member ----
@@ -370,9 +370,9 @@ int ladder_step(double diag0, int maxtries, int info, double *jitter, int *tries
 // scal: [0] log det, [8, 8 + P) alpha . y
 double lml_from_scalars(long N, int P, const double *scal) {
     double fit = 0.0;
-    for (int p = 0; p < P; ++p) fit += scal[8 + p];
+    for (int p = 0; p < P; ++p) fit += scal[SCAL_DOT.off + p];
     const double log_2_pi = std::log(2.0 * M_PI);
-    return 0.5 * (-(double)N * P * log_2_pi - P * scal[0] - fit);  // exact_gaussian_inference.py:62
+    return 0.5 * (-(double)N * P * log_2_pi - P * scal[SCAL_LOGDET.off] - fit);  // exact_gaussian_inference.py:62
 }
 
 // The factorisation's status word, read back (the stream is drained); *bad, when `emu`: an entry of L left the fixed-point range
@@ -548,10 +548,10 @@ int fit_impl(gp_ctx *g, int maxtries, Pipe kind, int include_noise) {
     }
 
     // read-back
-    std::vector<double> sc(8 + P);
-    HIPCHK(hipMemcpyAsync(sc.data(), g->dScal, sizeof(double) * (8 + P), hipMemcpyDeviceToHost, g->s));
+    std::vector<double> sc(SCAL_DOT.off + P);   // log det ... the last output's alpha . y
+    HIPCHK(hipMemcpyAsync(sc.data(), g->dScal, sizeof(double) * sc.size(), hipMemcpyDeviceToHost, g->s));
     GP_SYNC(g->s);
-    g->logdet = sc[0];
+    g->logdet = sc[SCAL_LOGDET.off];
     g->lml = lml_from_scalars(N, P, sc.data());
     g->fitted = true;
     if (kind == Pipe::Candidates) {

@@ -2,17 +2,17 @@
 // Reference: Stationary.update_gradients_full (stationary.py:218-238), GP.predictive_gradients (gp.py:407-454).
 #include "api_internal.h"
 
-// the fused dL_dK reduction for m's members: one pass per GP_GRAD_CH dimensions, its sums at m.scal + 64 + pass * GP_GRAD_NACC
+// the fused dL_dK reduction for m's members: one pass per GP_GRAD_CH dimensions, its GP_GRAD_NACC sums side by side in SCAL_GRAD
 void lml_grad_passes(gp_ctx *g, const Members &m) {
     int pass = 0;
     for (int d0 = 0; d0 < g->D; d0 += GP_GRAD_CH, ++pass) {
         launch_lml_grad(g->s, g->dX, g->N, g->Npad, m.kp[0], g->ard, d0, m.alpha, g->P, m.Wi, g->Npad, m.partial,
-                        m.scal + 64 + pass * GP_GRAD_NACC, m.nb, m.kpt, m.sV, m.sT, m.sT, m.sS);
+                        m.scal + SCAL_GRAD.off + pass * GP_GRAD_NACC, m.nb, m.kpt, m.sV, m.sT, m.sT, m.sS);
         if (!g->ard) break;
     }
 }
 
-// the gradients from those sums (h = scal + 64)
+// the gradients from those sums (h = the host copy of SCAL_GRAD)
 void grads_from_sums(const double *h, const KernParams &kp, int ard, double *dvariance, double *dlengthscale, double *dnoise) {
     *dvariance = h[0] / kp.variance;  // stationary.py:224
     *dnoise = h[1];                   // gaussian.py:78-79
@@ -26,12 +26,10 @@ void grads_from_sums(const double *h, const KernParams &kp, int ard, double *dva
 
 int lml_grad_impl(gp_ctx *g, double *dvariance, double *dlengthscale, double *dnoise, bool reset_phases) {
     if (!g || !dvariance || !dlengthscale || !dnoise) return fail(GP_ERR_ARG, "null argument");
-    GP_DEAD_CHECK(g);
-    if (!g->fitted) return fail(GP_ERR_STATE, "gp_fit first");
-    if (g->P > 16) return fail(GP_ERR_ARG, "gp_lml_grad supports P <= 16");
+    GP_FITTED(g);
+    if (g->P > GP_GRAD_MAX_P) return fail(GP_ERR_ARG, "gp_lml_grad supports P <= %d", GP_GRAD_MAX_P);
     // (a Gower model gets the fork's values: K through the Gower branch in the variance gradient, Euclidean dK/dr on the kernel's own
     // lengthscale in the lengthscale gradients, stationary.py:218-238 -- not derivatives of its LML, which the host layer knows)
-    HIPCHK(hipSetDevice(g->device));
     int rc;
     if (reset_phases) g->nphases = 0;
     if ((rc = ensure_wi(g))) return rc;
@@ -41,7 +39,7 @@ int lml_grad_impl(gp_ctx *g, double *dvariance, double *dlengthscale, double *dn
     phase_end(g, ph);
     const int npass = g->ard ? (g->D + GP_GRAD_CH - 1) / GP_GRAD_CH : 1;
     std::vector<double> host((size_t)GP_GRAD_NACC * npass);
-    HIPCHK(hipMemcpyAsync(host.data(), g->dScal + 64, sizeof(double) * host.size(), hipMemcpyDeviceToHost, g->s));
+    HIPCHK(hipMemcpyAsync(host.data(), g->dScal + SCAL_GRAD.off, sizeof(double) * host.size(), hipMemcpyDeviceToHost, g->s));
     GP_SYNC(g->s);
     grads_from_sums(host.data(), g->kp, g->ard, dvariance, dlengthscale, dnoise);
     return 0;
@@ -59,7 +57,7 @@ extern "C" int gp_fit_grad(gp_t *g, int maxtries, double *lml, double *logdet, d
     if (!g || !dvariance || !dlengthscale || !dnoise) return fail(GP_ERR_ARG, "null argument");
     GP_DEAD_CHECK(g);
     if (!g->have_data || !g->have_params) return fail(GP_ERR_STATE, "set data and params before gp_fit_grad");
-    if (g->P > 16) return fail(GP_ERR_ARG, "gp_lml_grad supports P <= 16");
+    if (g->P > GP_GRAD_MAX_P) return fail(GP_ERR_ARG, "gp_lml_grad supports P <= %d", GP_GRAD_MAX_P);
     HIPCHK(hipSetDevice(g->device));
     const int nt = (int)(g->Npad / GP_TILE);
     // emulated: Ky^-1 in residue form after the factorisation (wi_rns) instead of fp64 stages pipelined behind it
@@ -92,8 +90,6 @@ int ensure_grad_buffers(gp_ctx *g, long elemsBeta, long M) {
 // ranges: cross_k reads the latter, predict_grad_kernel the former.  Inconsistent as a derivative, but it is the function
 // the reference's L-BFGS (run.py:1206-1225) and estimate_L (run.py:1244) see.
 int run_predict_grad(gp_ctx *g) {
-    if (!g->fitted) return fail(GP_ERR_STATE, "gp_fit first");
-    if (g->M < 1) return fail(GP_ERR_STATE, "gp_set_candidates first");
     int rc;
     if (g->M <= g->small_m && !g->wi_valid) {
         // A handful of locations right after a fit: beta = Ky^-1 k* by TWO substitutions against L (dpotrs, the reference's own route
@@ -142,76 +138,76 @@ int run_predict_grad(gp_ctx *g) {
     return 0;
 }
 
+// dDm [M, D, P] (and dDv [M, D]) to the caller, drained
+static int grads_out(gp_ctx *g, double *dmdx, double *dvdx) {
+    HIPCHK(hipMemcpyAsync(dmdx, g->dDm, sizeof(double) * g->M * g->D * g->P, hipMemcpyDeviceToHost, g->s));
+    if (dvdx) HIPCHK(hipMemcpyAsync(dvdx, g->dDv, sizeof(double) * g->M * g->D, hipMemcpyDeviceToHost, g->s));
+    GP_SYNC(g->s);
+    return 0;
+}
+
 extern "C" int gp_predict_grad(gp_t *g, double *dmdx, double *dvdx) {
     if (!g || !dmdx) return fail(GP_ERR_ARG, "null argument");
-    GP_DEAD_CHECK(g);
-    HIPCHK(hipSetDevice(g->device));
+    GP_SCORING(g);
     int rc;
     if (!dvdx) {
         // the mean's gradients alone (what estimate_L maximises, batch_local_penalization.py:55-58): gradients_X(alpha^T, X*, X) needs
         // neither Ky^-1 nor K(X*, X) Ky^-1 -- one pass of O(M N D) instead of 2 N^3 / 3 + N^2 M flops
-        if (!g->fitted) return fail(GP_ERR_STATE, "gp_fit first");
-        if (g->M < 1) return fail(GP_ERR_STATE, "gp_set_candidates first");
         if ((rc = ensure_grad_buffers(g, 1, g->M))) return rc;
         launch_predict_grad(g->s, g->dXs, g->M, g->dX, g->N, g->kp, g->dAlpha, g->Npad, g->P, nullptr, 0, g->dDm, g->dDv);
-        HIPCHK(hipMemcpyAsync(dmdx, g->dDm, sizeof(double) * g->M * g->D * g->P, hipMemcpyDeviceToHost, g->s));
-        GP_SYNC(g->s);
-        return 0;
+    } else if ((rc = run_predict_grad(g))) {
+        return rc;
     }
-    if ((rc = run_predict_grad(g))) return rc;
-    HIPCHK(hipMemcpyAsync(dmdx, g->dDm, sizeof(double) * g->M * g->D * g->P, hipMemcpyDeviceToHost, g->s));
-    HIPCHK(hipMemcpyAsync(dvdx, g->dDv, sizeof(double) * g->M * g->D, hipMemcpyDeviceToHost, g->s));
-    GP_SYNC(g->s);
-    return 0;
-}
-
-static int run_acq_grad(gp_ctx *g, int type, double par, double fmin, double y_mean, double y_std);
-
-extern "C" int gp_acq_grad(gp_t *g, int type, double par, double fmin, double y_mean, double y_std, double *out, double *dout) {
-    if (!g || !out || !dout) return fail(GP_ERR_ARG, "null argument");
-    GP_DEAD_CHECK(g);
-    HIPCHK(hipSetDevice(g->device));
-    int rc;
-    if ((rc = run_acq_grad(g, type, par, fmin, y_mean, y_std))) return rc;
-    HIPCHK(hipMemcpyAsync(out, g->dAcq, sizeof(double) * g->M, hipMemcpyDeviceToHost, g->s));
-    HIPCHK(hipMemcpyAsync(dout, g->dDacq, sizeof(double) * g->M * g->D, hipMemcpyDeviceToHost, g->s));
-    GP_SYNC(g->s);
-    return 0;
+    return grads_out(g, dmdx, dvdx);
 }
 
 // the base acquisition's negated value and gradient of every resident candidate into dAcq [M] and dDacq [M, D]
-static int run_acq_grad(gp_ctx *g, int type, double par, double fmin, double y_mean, double y_std) {
-    if (!g->fitted) return fail(GP_ERR_STATE, "gp_fit first");
-    if (g->M < 1) return fail(GP_ERR_STATE, "gp_set_candidates first");
-    if (g->P != 1) return fail(GP_ERR_ARG, "acquisitions need P == 1");
-    if (type < GP_ACQ_EI || type > GP_ACQ_MPI) return fail(GP_ERR_ARG, "unknown acquisition %d", type);
+static int run_acq_grad(gp_ctx *g, const AcqSpec &a) {
     int rc;
+    if ((rc = check_acq(g, a))) return rc;
     if ((rc = ensure_out(g))) return rc;
     if ((rc = run_predict_grad(g))) return rc;
     if (!g->predicted || g->predicted_noise != 1)      // (the substitution route of a handful of rows leaves mean / variance behind)
         if ((rc = run_predict(g, 1))) return rc;
-    launch_acq_grad(g->s, type, par, fmin, y_mean, y_std, g->dMean, g->dVar, g->dDm, g->dDv, g->M, g->D, g->dAcq,
-                    g->dDacq);
+    launch_acq_grad(g->s, a.type, a.par, a.fmin, a.y_mean, a.y_std, g->dMean, g->dVar, g->dDm, g->dDv, g->M, g->D, g->dAcq, g->dDacq);
     return 0;
 }
 
-// AcquisitionLP.acquisition_function_withGradients (GPyOpt/GPyOpt/acquisitions/LP.py:112-140): the base acquisition's value
-// and gradient, then the log transform and the penaliser as an epilogue over the same buffers.
-extern "C" int gp_acq_lp_grad(gp_t *g, int type, double par, double fmin, double y_mean, double y_std, int transform,
-                              const double *Xb, int nb, const double *r_x0, const double *s_x0, double *out, double *dout) {
-    if (!g || !out || !dout || (nb > 0 && (!Xb || !r_x0 || !s_x0))) return fail(GP_ERR_ARG, "null argument");
-    GP_DEAD_CHECK(g);
-    if (transform != 0 && transform != 1) return fail(GP_ERR_ARG, "transform must be 0 (none) or 1 (softplus)");
-    HIPCHK(hipSetDevice(g->device));
+// The negated acquisition of the resident candidates -- penalised when lp is given -- to out [M] and, when dout is given, its
+// x-gradient to dout [M, D], drained.  With the penaliser and a gradient: the base acquisition's value and gradient, then the log
+// transform and the penaliser as an epilogue over the same buffers (AcquisitionLP.acquisition_function_withGradients,
+// GPyOpt/GPyOpt/acquisitions/LP.py:112-140).
+int acq_values(gp_ctx *g, const AcqSpec &a, const LpSpec *lp, double *out, double *dout) {
     int rc;
-    if ((rc = run_acq_grad(g, type, par, fmin, y_mean, y_std))) return rc;
-    LpBatch b;
-    if ((rc = upload_lp_batch(g, Xb, nb, r_x0, s_x0, &b))) return rc;
-    launch_lp_grad(g->s, g->dAcq, g->dDacq, g->dXs, g->M, g->D, b.X, nb, b.r, b.s, transform);
+    if (!dout) {
+        if ((rc = lp ? run_acq_lp(g, a, *lp) : run_acq(g, a))) return rc;
+    } else {
+        if (lp && (rc = check_lp(*lp))) return rc;
+        if ((rc = run_acq_grad(g, a))) return rc;
+        if (lp) {
+            LpBatch b;
+            if ((rc = upload_lp_batch(g, *lp, &b))) return rc;
+            launch_lp_grad(g->s, g->dAcq, g->dDacq, g->dXs, g->M, g->D, b.X, lp->nb, b.r, b.s, lp->transform);
+        }
+    }
     HIPCHK(hipMemcpyAsync(out, g->dAcq, sizeof(double) * g->M, hipMemcpyDeviceToHost, g->s));
-    HIPCHK(hipMemcpyAsync(dout, g->dDacq, sizeof(double) * g->M * g->D, hipMemcpyDeviceToHost, g->s));
+    if (dout) HIPCHK(hipMemcpyAsync(dout, g->dDacq, sizeof(double) * g->M * g->D, hipMemcpyDeviceToHost, g->s));
     GP_SYNC(g->s);
     return 0;
+}
+
+extern "C" int gp_acq_grad(gp_t *g, int type, double par, double fmin, double y_mean, double y_std, double *out, double *dout) {
+    if (!g || !out || !dout) return fail(GP_ERR_ARG, "null argument");
+    GP_SCORING(g);
+    return acq_values(g, AcqSpec{type, par, fmin, y_mean, y_std}, nullptr, out, dout);
+}
+
+extern "C" int gp_acq_lp_grad(gp_t *g, int type, double par, double fmin, double y_mean, double y_std, int transform,
+                              const double *Xb, int nb, const double *r_x0, const double *s_x0, double *out, double *dout) {
+    if (!g || !out || !dout) return fail(GP_ERR_ARG, "null argument");
+    GP_SCORING(g);
+    const LpSpec lp{transform, Xb, nb, r_x0, s_x0};
+    return acq_values(g, AcqSpec{type, par, fmin, y_mean, y_std}, &lp, out, dout);
 }
 
 // ---- dL_dK = 0.5 (alpha alpha^T - P Ky^-1)  (exact_gaussian_inference.py:70) -------------------------------
@@ -219,9 +215,7 @@ extern "C" int gp_acq_lp_grad(gp_t *g, int type, double par, double fmin, double
 // consume it on the host.  gp_lml_grad forms the same matrix implicitly inside its fused reduction.
 extern "C" int gp_get_dl_dk(gp_t *g, double *dL_dK) {
     if (!g || !dL_dK) return fail(GP_ERR_ARG, "null argument");
-    GP_DEAD_CHECK(g);
-    if (!g->fitted) return fail(GP_ERR_STATE, "gp_fit first");
-    HIPCHK(hipSetDevice(g->device));
+    GP_FITTED(g);
     int rc;
     if ((rc = ensure_wi(g))) return rc;  // leaves dT free (Npad x Npad)
     const long N = g->N, Npad = g->Npad;

@@ -134,13 +134,19 @@ extern "C" int gp_group_member(gp_group_t *grp, int i, gp_t **member) {
     return 0;
 }
 
-extern "C" int gp_group_set_option(gp_group_t *grp, const char *name, int64_t value) {
+// fn(member) on every member in turn, on the calling thread (host-only settings: nothing to run side by side)
+template <class F>
+static int each_member(gp_group *grp, F fn) {
     if (!grp) return fail(GP_ERR_ARG, "null group");
     for (gp_ctx *g : grp->m) {
-        int rc = gp_set_option(g, name, value);
+        int rc = fn(g);
         if (rc) return rc;
     }
     return 0;
+}
+
+extern "C" int gp_group_set_option(gp_group_t *grp, const char *name, int64_t value) {
+    return each_member(grp, [&](gp_ctx *g) { return gp_set_option(g, name, value); });
 }
 
 extern "C" int gp_group_set_data(gp_group_t *grp, const double *X, const double *Y, int64_t N, int D, int P) {
@@ -149,21 +155,11 @@ extern "C" int gp_group_set_data(gp_group_t *grp, const double *X, const double 
 }
 
 extern "C" int gp_group_set_params(gp_group_t *grp, int kernel, int ard, double variance, const double *lengthscale, double noise) {
-    if (!grp) return fail(GP_ERR_ARG, "null group");
-    for (gp_ctx *g : grp->m) {
-        int rc = gp_set_params(g, kernel, ard, variance, lengthscale, noise);
-        if (rc) return rc;
-    }
-    return 0;
+    return each_member(grp, [&](gp_ctx *g) { return gp_set_params(g, kernel, ard, variance, lengthscale, noise); });
 }
 
 extern "C" int gp_group_set_gower(gp_group_t *grp, int enable, const int *is_discrete, const double *range) {
-    if (!grp) return fail(GP_ERR_ARG, "null group");
-    for (gp_ctx *g : grp->m) {
-        int rc = gp_set_gower(g, enable, is_discrete, range);
-        if (rc) return rc;
-    }
-    return 0;
+    return each_member(grp, [&](gp_ctx *g) { return gp_set_gower(g, enable, is_discrete, range); });
 }
 
 // Every member factors its own replica, the devices side by side ("replicas only": no traffic, the wall time of one fit).
@@ -229,26 +225,25 @@ static int merge_best(const std::vector<double> &v, const std::vector<int64_t> &
     return 0;
 }
 
-static int exchange_and_merge_best(gp_group *grp, std::vector<double> &v, std::vector<int64_t> &ix, int sense, int64_t *idx,
-                                   double *val);
-
-extern "C" int gp_group_acq_argbest(gp_group_t *grp, int type, double par, double fmin, double y_mean, double y_std, int sense,
-                         int64_t *idx, double *val) {
-    if (!grp || !idx || !val) return fail(GP_ERR_ARG, "null argument");
-    if (grp->M < 1) return fail(GP_ERR_STATE, "gp_group_set_candidates first");
-    if (sense != 1 && sense != -1) return fail(GP_ERR_ARG, "sense must be +1 or -1");
-    const int n = (int)grp->m.size();
-    std::vector<double> v(n, sense > 0 ? -INFINITY : INFINITY);
-    std::vector<int64_t> ix(n, -1);
-    int rc = for_members(grp, [&](int i) {
-        if (grp->hi[i] == grp->lo[i]) return 0;
-        int64_t li = -1;
-        int r = gp_acq_argbest(grp->m[i], type, par, fmin, y_mean, y_std, sense, &li, &v[i]);
-        if (r == 0) ix[i] = grp->lo[i] + li;
-        return r;
-    });
-    if (rc) return rc;
-    return exchange_and_merge_best(grp, v, ix, sense, idx, val);
+// k rounds of the lowest-index arg-best over the gathered pairs: a stable sort by (value, global row); pairs with idx < 0 are
+// empty slots, a tail that cannot be filled is idx = -1
+static void merge_topk(const std::vector<double> &v, const std::vector<int64_t> &ix, int sense, int k, int64_t *idx, double *val) {
+    std::vector<char> used(v.size(), 0);
+    for (int j = 0; j < k; ++j) {
+        long best = -1;
+        for (size_t r = 0; r < v.size(); ++r) {
+            if (used[r] || ix[r] < 0) continue;
+            if (best < 0 || (sense > 0 ? v[r] > v[best] : v[r] < v[best]) || (v[r] == v[best] && ix[r] < ix[best])) best = (long)r;
+        }
+        if (best < 0) {
+            idx[j] = -1;
+            val[j] = acq_empty(sense);
+        } else {
+            used[best] = 1;
+            idx[j] = ix[best];
+            val[j] = v[best];
+        }
+    }
 }
 
 // The group's one collective, issued for ALL members from the calling thread inside ncclGroupStart / ncclGroupEnd: k records
@@ -260,6 +255,7 @@ static int group_allgather(gp_group *grp, int k, const std::vector<double> &v, c
                            std::vector<double> &gv, std::vector<int64_t> &gi) {
     const int n = (int)grp->m.size();
     const size_t nd = 2 * (size_t)k;                       // doubles per member
+    if ((long)(nd * n) > COMM_RECV.len) return fail(GP_ERR_ARG, "too many members for the gather scratch");
     for (int i = 0; i < n; ++i) {
         gp_ctx *g = grp->m[i];
         if (g->dead) return fail(GP_ERR_STATE, "member %d: the library was shut down (gp_shutdown)", i);
@@ -270,18 +266,15 @@ static int group_allgather(gp_group *grp, int k, const std::vector<double> &v, c
         gp_ctx *g = grp->m[i];
         HIPCHK(hipSetDevice(g->device));
         int rc;
-        if ((rc = g->dComm.reserve(2L * GP_TOPK_MAX * (1 + 128)))) return rc;
-        for (int j = 0; j < k; ++j) {
-            rec[i][2 * j] = v[(size_t)i * k + j];
-            memcpy(&rec[i][2 * j + 1], &ix[(size_t)i * k + j], 8);
-        }
-        HIPCHK(hipMemcpyAsync(g->dComm, rec[i].data(), sizeof(double) * nd, hipMemcpyHostToDevice, g->s));
+        if ((rc = g->dComm.reserve(COMM_CAP))) return rc;
+        pack_pairs(&v[(size_t)i * k], &ix[(size_t)i * k], k, rec[i].data());
+        HIPCHK(hipMemcpyAsync(g->dComm + COMM_SEND.off, rec[i].data(), sizeof(double) * nd, hipMemcpyHostToDevice, g->s));
     }
     ncclResult_t bad = ncclSuccess;
     ncclGroupStart();
     for (int i = 0; i < n; ++i) {
         gp_ctx *g = grp->m[i];
-        ncclResult_t r = ncclAllGather(g->dComm, g->dComm + 2 * GP_TOPK_MAX, nd, ncclDouble, g->comm, g->s);
+        ncclResult_t r = ncclAllGather(g->dComm + COMM_SEND.off, g->dComm + COMM_RECV.off, nd, ncclDouble, g->comm, g->s);
         if (r != ncclSuccess && bad == ncclSuccess) bad = r;
     }
     ncclResult_t rend = ncclGroupEnd();
@@ -301,7 +294,7 @@ static int group_allgather(gp_group *grp, int k, const std::vector<double> &v, c
         gp_ctx *g = grp->m[i];
         hipError_t e = hipSetDevice(g->device);
         if (e == hipSuccess)
-            e = hipMemcpyAsync(out[i].data(), g->dComm + 2 * GP_TOPK_MAX, sizeof(double) * nd * n, hipMemcpyDeviceToHost, g->s);
+            e = hipMemcpyAsync(out[i].data(), g->dComm + COMM_RECV.off, sizeof(double) * nd * n, hipMemcpyDeviceToHost, g->s);
         hipError_t es = hipStreamSynchronize(g->s);
         if (e == hipSuccess) e = es;
         if (e != hipSuccess && !first) first = fail(GP_ERR_HIP, "member %d: gather -> %s", i, hipGetErrorString(e));
@@ -309,33 +302,62 @@ static int group_allgather(gp_group *grp, int k, const std::vector<double> &v, c
     if (first) return first;
     gv.resize((size_t)n * n * k);
     gi.resize((size_t)n * n * k);
-    for (int i = 0; i < n; ++i)
-        for (size_t r = 0; r < (size_t)n * k; ++r) {
-            gv[(size_t)i * n * k + r] = out[i][2 * r];
-            memcpy(&gi[(size_t)i * n * k + r], &out[i][2 * r + 1], 8);
-        }
+    for (int i = 0; i < n; ++i) unpack_pairs(out[i].data(), (size_t)n * k, &gv[(size_t)i * n * k], &gi[(size_t)i * n * k]);
     return 0;
 }
 
-// Shared tail of the arg-best entry points: every member has its (value, global row) pair -- exchange (RCCL when the members hold
-// communicators) and merge.
-static int exchange_and_merge_best(gp_group *grp, std::vector<double> &v, std::vector<int64_t> &ix, int sense, int64_t *idx,
-                                   double *val) {
-    const int n = (int)grp->m.size();
-    if (grp->rccl) {
-        std::vector<double> gv;
-        std::vector<int64_t> gi;
-        // (the collective starts only once EVERY member has its pair, and is enqueued for all of them by this one thread)
-        int rc = group_allgather(grp, 1, v, ix, gv, gi);
+// Every member has its k (value, global row) pairs in v / ix.  Members that hold communicators exchange them (the collective
+// starts only once EVERY member has its pairs, and is enqueued for all of them by this one thread): every member then holds all
+// pairs, member 0's copy is what gets merged, and the others must equal it.  Without communicators v / ix are all pairs already.
+static int exchange(gp_group *grp, int k, std::vector<double> &v, std::vector<int64_t> &ix) {
+    if (!grp->rccl) return 0;
+    const size_t n = grp->m.size(), all = n * k;
+    std::vector<double> gv;
+    std::vector<int64_t> gi;
+    int rc = group_allgather(grp, k, v, ix, gv, gi);
+    if (rc) return rc;
+    for (size_t i = 1; i < n; ++i)
+        if (memcmp(&gv[i * all], &gv[0], sizeof(double) * all) || memcmp(&gi[i * all], &gi[0], sizeof(int64_t) * all))
+            return fail(GP_ERR_RCCL, "members disagree on the gathered pairs");
+    v.assign(gv.begin(), gv.begin() + all);
+    ix.assign(gi.begin(), gi.begin() + all);
+    return 0;
+}
+
+// The scoring entry points' common frame.  Every member whose block is not empty scores it: score(member index, rows [k],
+// values [k]) fills its k pairs (a pair it leaves at row -1 is empty), whose LOCAL rows are made global here.
+struct Pairs {
+    std::vector<double> v;
+    std::vector<int64_t> ix;
+    Pairs(gp_group *grp, int k, int sense) : v(grp->m.size() * k, acq_empty(sense)), ix(grp->m.size() * k, -1) {}
+};
+template <class F>
+static int score_blocks(gp_group *grp, int k, Pairs &p, F score) {
+    return for_members(grp, [&](int i) {
+        if (grp->hi[i] == grp->lo[i]) return 0;
+        int64_t *rows = &p.ix[(size_t)i * k];
+        int rc = score(i, rows, &p.v[(size_t)i * k]);
         if (rc) return rc;
-        // every member holds all pairs now; member 0's copy is merged (the others must equal it)
-        for (int i = 1; i < n; ++i)
-            if (memcmp(&gv[(size_t)i * n], &gv[0], sizeof(double) * n) || memcmp(&gi[(size_t)i * n], &gi[0], sizeof(int64_t) * n))
-                return fail(GP_ERR_RCCL, "members disagree on the gathered pairs");
-        v.assign(gv.begin(), gv.begin() + n);
-        ix.assign(gi.begin(), gi.begin() + n);
-    }
-    return merge_best(v, ix, sense, idx, val);
+        for (int j = 0; j < k; ++j)
+            if (rows[j] >= 0) rows[j] += grp->lo[i];
+        return 0;
+    });
+}
+static int group_ready(gp_group *grp, int sense) {
+    if (grp->M < 1) return fail(GP_ERR_STATE, "gp_group_set_candidates first");
+    return check_sense(sense);
+}
+
+extern "C" int gp_group_acq_argbest(gp_group_t *grp, int type, double par, double fmin, double y_mean, double y_std, int sense,
+                         int64_t *idx, double *val) {
+    if (!grp || !idx || !val) return fail(GP_ERR_ARG, "null argument");
+    int rc;
+    if ((rc = group_ready(grp, sense))) return rc;
+    const AcqSpec a{type, par, fmin, y_mean, y_std};
+    Pairs p(grp, 1, sense);
+    rc = score_blocks(grp, 1, p, [&](int i, int64_t *row, double *v) { return acq_argbest(grp->m[i], a, nullptr, sense, nullptr, 0, row, v); });
+    if (rc || (rc = exchange(grp, 1, p.v, p.ix))) return rc;
+    return merge_best(p.v, p.ix, sense, idx, val);
 }
 
 // The local-penalisation acquisition over the whole table (run.py:1238-1257: penalised scores of the candidate table, arg-max,
@@ -344,29 +366,37 @@ static int exchange_and_merge_best(gp_group *grp, std::vector<double> &v, std::v
 extern "C" int gp_group_acq_lp_argbest(gp_group_t *grp, int type, double par, double fmin, double y_mean, double y_std, int transform,
                             const double *Xb, int nb, const double *r_x0, const double *s_x0, int sense, const int64_t *exclude,
                             int nex, int64_t *idx, double *val) {
-    if (!grp || !idx || !val || (nex > 0 && !exclude)) return fail(GP_ERR_ARG, "null argument");
-    if (grp->M < 1) return fail(GP_ERR_STATE, "gp_group_set_candidates first");
-    if (sense != 1 && sense != -1) return fail(GP_ERR_ARG, "sense must be +1 or -1");
-    if (nex < 0 || nex > 256) return fail(GP_ERR_ARG, "too many excluded rows (<= 256)");
-    for (int e = 0; e < nex; ++e)
-        if (exclude[e] < 0 || exclude[e] >= grp->M) return fail(GP_ERR_ARG, "excluded row out of range");
-    const int n = (int)grp->m.size();
-    std::vector<double> v(n, sense > 0 ? -INFINITY : INFINITY);
-    std::vector<int64_t> ix(n, -1);
-    int rc = for_members(grp, [&](int i) {
-        if (grp->hi[i] == grp->lo[i]) return 0;
+    if (!grp || !idx || !val) return fail(GP_ERR_ARG, "null argument");
+    int rc;
+    if ((rc = group_ready(grp, sense))) return rc;
+    if ((rc = check_exclude(exclude, nex, grp->M))) return rc;
+    const AcqSpec a{type, par, fmin, y_mean, y_std};
+    const LpSpec lp{transform, Xb, nb, r_x0, s_x0};
+    if ((rc = check_lp(lp))) return rc;
+    Pairs p(grp, 1, sense);
+    rc = score_blocks(grp, 1, p, [&](int i, int64_t *row, double *v) {
         std::vector<int64_t> mine;
         for (int e = 0; e < nex; ++e)
             if (exclude[e] >= grp->lo[i] && exclude[e] < grp->hi[i]) mine.push_back(exclude[e] - grp->lo[i]);
         if ((long)mine.size() == grp->hi[i] - grp->lo[i]) return 0;   // every row of this block is taken already
-        int64_t li = -1;
-        int r = gp_acq_lp_argbest(grp->m[i], type, par, fmin, y_mean, y_std, transform, Xb, nb, r_x0, s_x0, sense, mine.data(),
-                                  (int)mine.size(), &li, &v[i]);
-        if (r == 0) ix[i] = grp->lo[i] + li;
-        return r;
+        return acq_argbest(grp->m[i], a, &lp, sense, mine.data(), (int)mine.size(), row, v);
     });
-    if (rc) return rc;
-    return exchange_and_merge_best(grp, v, ix, sense, idx, val);
+    if (rc || (rc = exchange(grp, 1, p.v, p.ix))) return rc;
+    return merge_best(p.v, p.ix, sense, idx, val);
+}
+
+extern "C" int gp_group_acq_topk(gp_group_t *grp, int type, double par, double fmin, double y_mean, double y_std, int sense, int k,
+                      int64_t *idx, double *val) {
+    if (!grp || !idx || !val) return fail(GP_ERR_ARG, "null argument");
+    int rc;
+    if ((rc = group_ready(grp, sense))) return rc;
+    if ((rc = check_k(k))) return rc;
+    const AcqSpec a{type, par, fmin, y_mean, y_std};
+    Pairs p(grp, k, sense);
+    rc = score_blocks(grp, k, p, [&](int i, int64_t *rows, double *v) { return acq_topk(grp->m[i], a, sense, k, rows, v); });
+    if (rc || (rc = exchange(grp, k, p.v, p.ix))) return rc;
+    merge_topk(p.v, p.ix, sense, k, idx, val);
+    return 0;
 }
 
 // ---- the merges as host-only entry points (no device, no group): what every layout applies to the gathered pairs -------------
@@ -376,68 +406,9 @@ extern "C" int gp_merge_best(int n, const double *vals, const int64_t *idxs, int
     return merge_best(std::vector<double>(vals, vals + n), std::vector<int64_t>(idxs, idxs + n), sense, idx, val);
 }
 
-static void merge_topk(const std::vector<double> &v, const std::vector<int64_t> &ix, int sense, int k, int64_t *idx, double *val);
-
 extern "C" int gp_merge_topk(int n, const double *vals, const int64_t *idxs, int sense, int k, int64_t *idx, double *val) {
     if (n < 1 || k < 1 || !vals || !idxs || !idx || !val) return fail(GP_ERR_ARG, "bad argument");
     if (sense != 1 && sense != -1) return fail(GP_ERR_ARG, "sense must be +1 or -1");
     merge_topk(std::vector<double>(vals, vals + n), std::vector<int64_t>(idxs, idxs + n), sense, k, idx, val);
     return 0;
-}
-
-extern "C" int gp_group_acq_topk(gp_group_t *grp, int type, double par, double fmin, double y_mean, double y_std, int sense, int k,
-                      int64_t *idx, double *val) {
-    if (!grp || !idx || !val) return fail(GP_ERR_ARG, "null argument");
-    if (grp->M < 1) return fail(GP_ERR_STATE, "gp_group_set_candidates first");
-    if (sense != 1 && sense != -1) return fail(GP_ERR_ARG, "sense must be +1 or -1");
-    if (k < 1 || k > GP_TOPK_MAX) return fail(GP_ERR_ARG, "k out of range (1..%d)", GP_TOPK_MAX);
-    const int n = (int)grp->m.size();
-    const double empty = sense > 0 ? -INFINITY : INFINITY;
-    std::vector<double> v((size_t)n * k, empty);
-    std::vector<int64_t> ix((size_t)n * k, -1);
-    std::vector<double> gv;
-    std::vector<int64_t> gi;
-    int rc = for_members(grp, [&](int i) {
-        if (grp->hi[i] == grp->lo[i]) return 0;
-        int64_t *ii = &ix[(size_t)i * k];
-        int r = gp_acq_topk(grp->m[i], type, par, fmin, y_mean, y_std, sense, k, ii, &v[(size_t)i * k]);
-        if (r) return r;
-        for (int j = 0; j < k; ++j)
-            if (ii[j] >= 0) ii[j] += grp->lo[i];
-        return 0;
-    });
-    if (rc) return rc;
-    if (grp->rccl) {
-        if ((rc = group_allgather(grp, k, v, ix, gv, gi))) return rc;
-        for (int i = 1; i < n; ++i)
-            if (memcmp(&gv[(size_t)i * n * k], &gv[0], sizeof(double) * n * k) ||
-                memcmp(&gi[(size_t)i * n * k], &gi[0], sizeof(int64_t) * n * k))
-                return fail(GP_ERR_RCCL, "members disagree on the gathered pairs");
-        v.assign(gv.begin(), gv.begin() + (size_t)n * k);
-        ix.assign(gi.begin(), gi.begin() + (size_t)n * k);
-    }
-    merge_topk(v, ix, sense, k, idx, val);
-    return 0;
-}
-
-// k rounds of the lowest-index arg-best over the gathered pairs: a stable sort by (value, global row); pairs with idx < 0 are
-// empty slots, a tail that cannot be filled is idx = -1
-static void merge_topk(const std::vector<double> &v, const std::vector<int64_t> &ix, int sense, int k, int64_t *idx, double *val) {
-    const double empty = sense > 0 ? -INFINITY : INFINITY;
-    std::vector<char> used(v.size(), 0);
-    for (int j = 0; j < k; ++j) {
-        long best = -1;
-        for (size_t r = 0; r < v.size(); ++r) {
-            if (used[r] || ix[r] < 0) continue;
-            if (best < 0 || (sense > 0 ? v[r] > v[best] : v[r] < v[best]) || (v[r] == v[best] && ix[r] < ix[best])) best = (long)r;
-        }
-        if (best < 0) {
-            idx[j] = -1;
-            val[j] = empty;
-        } else {
-            used[best] = 1;
-            idx[j] = ix[best];
-            val[j] = v[best];
-        }
-    }
 }

@@ -54,6 +54,68 @@ void gp_clear_stale_note();
             return fail(GP_ERR_STATE, "the library was shut down (gp_shutdown): destroy this context and create a new one"); \
     } while (0)
 
+// The preamble of an entry point that works on a fit (GP_FITTED) or scores the resident candidates (GP_SCORING): the context is
+// alive, holds what the call needs, and its device is current.  (Null arguments are the entry point's own first check.)
+#define GP_READY(g, candidates)                                                                     \
+    do {                                                                                            \
+        GP_DEAD_CHECK(g);                                                                           \
+        if (!(g)->fitted) return fail(GP_ERR_STATE, "gp_fit first");                                \
+        if ((candidates) && (g)->M < 1) return fail(GP_ERR_STATE, "gp_set_candidates first");       \
+        HIPCHK(hipSetDevice((g)->device));                                                          \
+    } while (0)
+#define GP_FITTED(g) GP_READY(g, false)
+#define GP_SCORING(g) GP_READY(g, true)
+
+// ---- scratch map ----------------------------------------------------------------------------------------------------------
+// Where everything lives in the small device buffers that several units carve up: offset and length (in elements) of every
+// slot, in this one place.  gp_create (api_core.hip) reserves the *_CAP of dScal, dRedV and dRedI once; dComm and dLp are
+// reserved at their *_CAP by their first user.  Each static_assert below lists slots that can be live in the same call: they
+// lie inside the capacity and do not overlap.
+struct Slot { long off, len; };
+template <size_t n>
+constexpr bool slots_ok(const Slot (&s)[n], long cap) {
+    for (size_t i = 0; i < n; ++i) {
+        if (s[i].off < 0 || s[i].len < 1 || s[i].off + s[i].len > cap) return false;
+        for (size_t j = 0; j < i; ++j)
+            if (s[i].off < s[j].off + s[j].len && s[j].off < s[i].off + s[i].len) return false;
+    }
+    return true;
+}
+#define GP_GRAD_MAX_P 16    // gp_lml_grad / gp_fit_grad: outputs whose alpha . y fit in front of the gradient sums
+#define GP_LP_MAX_NB 256    // rows of a local-penalisation batch
+#define GP_EXCLUDE_MAX 256  // excluded rows of gp_acq_lp_argbest
+#define GP_COMM_MAX_RANKS 128
+// dScal, per member (Members::scal; gp_fit_grad_batch strides its members by SCAL_GRAD's end)
+constexpr long SCAL_CAP = 512;
+constexpr Slot SCAL_LOGDET{0, 1};
+constexpr Slot SCAL_DOT{8, GP_MAX_RHS};                  // alpha . y of each output (alpha_lml)
+constexpr Slot SCAL_DOT_GRAD{8, GP_GRAD_MAX_P};          // ... as far as it goes in a call that also takes the gradient
+constexpr Slot SCAL_GRAD{64, GP_MAX_D / GP_GRAD_CH * GP_GRAD_NACC};   // GP_GRAD_NACC sums per pass of GP_GRAD_CH dimensions
+constexpr Slot SCAL_FIT_RECORD{400, 4};                  // gp_comm_bcast_fit
+constexpr Slot SCAL_TRACE{420, 2};                       // trace and smallest diagonal entry, gp_posterior_samples
+static_assert(GP_MAX_D % GP_GRAD_CH == 0, "whole gradient passes");
+static_assert(slots_ok({SCAL_LOGDET, SCAL_DOT, SCAL_FIT_RECORD, SCAL_TRACE}, SCAL_CAP), "dScal: a fit of up to GP_MAX_RHS outputs");
+static_assert(slots_ok({SCAL_LOGDET, SCAL_DOT_GRAD, SCAL_GRAD, SCAL_FIT_RECORD, SCAL_TRACE}, SCAL_CAP), "dScal: fit and gradient");
+// dRedV (doubles) and dRedI (rows): the two-level arg-best reduction; what rides beside it
+constexpr long REDV_CAP = 512, REDI_CAP = 1024;
+constexpr Slot RED_PARTIAL{0, 256};                      // first-level winners, in both buffers (launch_argbest: <= 256 blocks)
+constexpr Slot RED_RESULT{256, 1};                       // the winner, in both buffers
+constexpr Slot REDV_GATHER_SEND{300, 2};                 // gp_comm_allgather_best: this rank's {value, row} ...
+constexpr Slot REDV_GATHER_RECV{304, 200};               // ... and every rank's: 2 * nranks doubles
+constexpr Slot REDI_EXCLUDE{300, GP_EXCLUDE_MAX};        // rows masked before the reduction
+static_assert(slots_ok({RED_PARTIAL, RED_RESULT, REDV_GATHER_SEND, REDV_GATHER_RECV}, REDV_CAP), "dRedV");
+static_assert(slots_ok({RED_PARTIAL, RED_RESULT, REDI_EXCLUDE}, REDI_CAP), "dRedI");
+// dComm (doubles; rows travel as 8 bytes in a double's place): the local top-k, or a gather of up to GP_TOPK_MAX records a rank
+constexpr long COMM_CAP = 2L * GP_TOPK_MAX * (1 + GP_COMM_MAX_RANKS);
+constexpr Slot COMM_TOPK_VAL{0, GP_TOPK_MAX}, COMM_TOPK_ROW{GP_TOPK_MAX, GP_TOPK_MAX};
+constexpr Slot COMM_SEND{0, 2 * GP_TOPK_MAX}, COMM_RECV{2 * GP_TOPK_MAX, 2L * GP_TOPK_MAX * GP_COMM_MAX_RANKS};
+static_assert(slots_ok({COMM_TOPK_VAL, COMM_TOPK_ROW}, COMM_CAP), "dComm: gp_acq_topk");
+static_assert(slots_ok({COMM_SEND, COMM_RECV}, COMM_CAP), "dComm: gathers");
+// dLp: the penaliser's batch
+constexpr long LP_CAP = (long)GP_LP_MAX_NB * (GP_MAX_D + 2);
+constexpr Slot LP_X{0, (long)GP_LP_MAX_NB * GP_MAX_D}, LP_R{LP_X.off + LP_X.len, GP_LP_MAX_NB}, LP_S{LP_R.off + LP_R.len, GP_LP_MAX_NB};
+static_assert(slots_ok({LP_X, LP_R, LP_S}, LP_CAP), "dLp");
+
 struct Phase {
     const char *name;
     hipEvent_t e0, e1;
@@ -115,9 +177,9 @@ struct gp_ctx {
     DevBuf<double> dW;     // P x Npad workspace
     DevBuf<double> dMu;    // (1 + TM_SPLIT) * N : training mean + partials
     DevBuf<int> dInfo;
-    DevBuf<double> dScal;  // small scalars: [0] logdet, [8..8+P) sumsq / dot
-    DevBuf<double> dRedV;  // 512 doubles of reduction scratch
-    DevBuf<long long> dRedI;
+    DevBuf<double> dScal;  // small scalars (scratch map above: SCAL_*)
+    DevBuf<double> dRedV;  // reduction scratch, values (RED_*, REDV_*)
+    DevBuf<long long> dRedI;   // ... and rows (RED_*, REDI_*)
     long capN = 0;
     int capP = 0;
     // params
@@ -160,7 +222,7 @@ struct gp_ctx {
     int rows_nt = -1;                    // fused one-row path: non-temporal loads of the inverse factor (option "rows_nt"; -1: when its
                                          // lower triangle exceeds the 256 MiB Infinity Cache, N > 8192 -- measured -10 % at N = 16384,
                                          // +10 % at N = 4096 where the next call finds the factor cached: profiles/r05_small_calls.txt)
-    DevBuf<double> dLp;    // local-penalisation batch (centres, radii, scales)
+    DevBuf<double> dLp;    // local-penalisation batch: centres, radii, scales (LP_*)
     DevBuf<double> dX2, dK2;  // gp_cross_kernel_matrix: second input set and K(X, X2)
     DevBuf<double> dCov;   // full covariance / beta scratch
     DevBuf<double> dInvP, dInvPw;  // inverted diagonal panels L_JJ^-1 (+ build workspace)
@@ -217,7 +279,7 @@ struct gp_ctx {
     // comm
     ncclComm_t comm = nullptr;
     int rank = 0, nranks = 1;
-    DevBuf<double> dComm;  // gather scratch of the top-k exchange
+    DevBuf<double> dComm;  // local top-k and gather scratch of the exchanges (COMM_*)
     // fp64 emulation on the int8 matrix cores (rns.hip)
     int emulate_fp64 = 0;
     int rns_group = 8; // panels per residue launch of the emulated candidate solve
@@ -286,7 +348,7 @@ struct Members {
     // Npad x Npad each: the identity / running right-hand side, L^-T, Ky^-1 (may be T again) and the gradient pass's per-tile
     // partials (any of them that is free by then)
     double *T = nullptr, *T2 = nullptr, *Wi = nullptr, *partial = nullptr;
-    double *scal = nullptr;   // [0] log det, [8, 8 + P) alpha . y, [64 + pass * GP_GRAD_NACC ...) gradient sums
+    double *scal = nullptr;   // SCAL_LOGDET, SCAL_DOT and SCAL_GRAD of the scratch map
     int *info = nullptr;      // 4 status words per member
     // per-member values: on the host (nb entries; a launch of one member passes them in its kernel arguments) and the same
     // in device tables (launches of several members index them; unused, and may be null, for one member)
@@ -394,10 +456,28 @@ int solve_rows_rns(gp_ctx *g, double *T, double *S, int mt, const RnsSolveOpt &o
 int fit_impl(gp_ctx *g, int maxtries, Pipe kind, int include_noise);
 int run_predict(gp_ctx *g, int include_noise, bool tiles_only = false);   // tiles_only: never the small-M path (the caller uses dT2 as a padded tile operand)
 int ensure_out(gp_ctx *g);
-int run_acq(gp_ctx *g, int type, double par, double fmin, double y_mean, double y_std);
-struct LpBatch { double *X = nullptr, *r = nullptr, *s = nullptr; };
-int upload_lp_batch(gp_ctx *g, const double *Xb, int nb, const double *r0, const double *s0, LpBatch *b);
-int run_acq_lp(gp_ctx *g, int type, double par, double fmin, double y_mean, double y_std, int transform, const double *Xb, int nb, const double *r0, const double *s0);
+// What to score, as the C boundary got it: the base acquisition, and the local penaliser on top of it (the batch on the HOST)
+struct AcqSpec { int type; double par, fmin, y_mean, y_std; };
+struct LpSpec { int transform; const double *Xb; int nb; const double *r0, *s0; };
+int check_acq(const gp_ctx *g, const AcqSpec &a);   // a single-output model, a known acquisition
+int check_lp(const LpSpec &lp);                     // transform 0 / 1, 0 <= nb <= GP_LP_MAX_NB, a batch where nb > 0
+int check_sense(int sense);
+int check_k(int k);
+int check_exclude(const int64_t *exclude, int nex, int64_t M);
+static inline double acq_empty(int sense) { return sense > 0 ? -INFINITY : INFINITY; }   // the value no candidate loses to
+struct LpBatch { double *X = nullptr, *r = nullptr, *s = nullptr; };   // the batch on the device
+static inline LpBatch lp_slots(const gp_ctx *g) { return LpBatch{g->dLp + LP_X.off, g->dLp + LP_R.off, g->dLp + LP_S.off}; }
+RowsAcq rows_acq(const AcqSpec &a, const LpSpec *lp, const LpBatch &b);   // the fused path's kernel argument (lp null: base only)
+int run_acq(gp_ctx *g, const AcqSpec &a);
+int upload_lp_batch(gp_ctx *g, const LpSpec &lp, LpBatch *b);
+int run_acq_lp(gp_ctx *g, const AcqSpec &a, const LpSpec &lp);
+int acq_values(gp_ctx *g, const AcqSpec &a, const LpSpec *lp, double *out, double *dout);   // api_grad.hip
+// gp_acq_argbest / gp_acq_lp_argbest and gp_acq_topk over the specs, preamble included (lp null: no penaliser)
+int acq_argbest(gp_ctx *g, const AcqSpec &a, const LpSpec *lp, int sense, const int64_t *exclude, int nex, int64_t *idx, double *val);
+int acq_topk(gp_ctx *g, const AcqSpec &a, int sense, int k, int64_t *idx, double *val);
+// {value, row} records of the gathers: n pairs of doubles, the second holding the row's 8 bytes (api_comm.hip)
+void pack_pairs(const double *v, const int64_t *ix, size_t n, double *rec);
+void unpack_pairs(const double *rec, size_t n, double *v, int64_t *ix);
 void lauum(gp_ctx *g, const Members &m);
 int wi_lauum(gp_ctx *g);
 int wi_rns(gp_ctx *g);

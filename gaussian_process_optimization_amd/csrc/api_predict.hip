@@ -90,10 +90,7 @@ int ensure_out(gp_ctx *g) {
 
 extern "C" int gp_predict(gp_t *g, int include_noise, double *mean, double *var) {
     if (!g) return fail(GP_ERR_ARG, "null gp");
-    GP_DEAD_CHECK(g);
-    if (!g->fitted) return fail(GP_ERR_STATE, "gp_fit first");
-    if (g->M < 1) return fail(GP_ERR_STATE, "gp_set_candidates first");
-    HIPCHK(hipSetDevice(g->device));
+    GP_SCORING(g);
     int rc;
     if ((rc = ensure_out(g))) return rc;
     if ((rc = run_predict(g, include_noise))) return rc;
@@ -103,151 +100,146 @@ extern "C" int gp_predict(gp_t *g, int include_noise, double *mean, double *var)
     return 0;
 }
 
+// ---- the checks of what a caller asks to have scored, one each --------------------------------------------------------------
+int check_acq(const gp_ctx *g, const AcqSpec &a) {
+    if (g->P != 1) return fail(GP_ERR_ARG, "acquisitions need P == 1");
+    if (a.type < GP_ACQ_EI || a.type > GP_ACQ_MPI) return fail(GP_ERR_ARG, "unknown acquisition %d", a.type);
+    return 0;
+}
+int check_lp(const LpSpec &lp) {
+    if (lp.transform != 0 && lp.transform != 1) return fail(GP_ERR_ARG, "transform must be 0 (none) or 1 (softplus)");
+    if (lp.nb < 0 || lp.nb > GP_LP_MAX_NB) return fail(GP_ERR_ARG, "batch size out of range (0..%d)", GP_LP_MAX_NB);
+    if (lp.nb > 0 && (!lp.Xb || !lp.r0 || !lp.s0)) return fail(GP_ERR_ARG, "null argument");
+    return 0;
+}
+int check_sense(int sense) { return sense == 1 || sense == -1 ? 0 : fail(GP_ERR_ARG, "sense must be +1 or -1"); }
+int check_k(int k) { return k >= 1 && k <= GP_TOPK_MAX ? 0 : fail(GP_ERR_ARG, "k out of range (1..%d)", GP_TOPK_MAX); }
+int check_exclude(const int64_t *exclude, int nex, int64_t M) {   // rows already taken (run.py:1249-1252 masks them)
+    if (nex < 0 || nex > GP_EXCLUDE_MAX) return fail(GP_ERR_ARG, "too many excluded rows (<= %d)", GP_EXCLUDE_MAX);
+    if (nex > 0 && !exclude) return fail(GP_ERR_ARG, "null argument");
+    for (int i = 0; i < nex; ++i)
+        if (exclude[i] < 0 || exclude[i] >= M) return fail(GP_ERR_ARG, "excluded row out of range");
+    return 0;
+}
+
+// ---- arg-best: the two-level reduction into RED_RESULT, and its read-back ----------------------------------------------------
+static void argbest_launch(gp_ctx *g, const double *v, long n, int sense) {
+    launch_argbest(g->s, v, n, sense, g->dRedV + RED_RESULT.off, g->dRedI + RED_RESULT.off, g->dRedV + RED_PARTIAL.off,
+                   g->dRedI + RED_PARTIAL.off);
+}
+static void mask_rows(gp_ctx *g, const long long *rows, int n, int sense) { launch_mask(g->s, g->dAcq, rows, n, acq_empty(sense)); }
+// lowest index among the best of v[0, n), drained (idx may be null: the value alone)
+static int argbest_read(gp_ctx *g, const double *v, long n, int sense, int64_t *idx, double *val) {
+    argbest_launch(g, v, n, sense);
+    double hv = 0.0;
+    long long hi = 0;
+    HIPCHK(hipMemcpyAsync(&hv, g->dRedV + RED_RESULT.off, sizeof(double), hipMemcpyDeviceToHost, g->s));
+    if (idx) HIPCHK(hipMemcpyAsync(&hi, g->dRedI + RED_RESULT.off, sizeof(long long), hipMemcpyDeviceToHost, g->s));
+    GP_SYNC(g->s);
+    *val = hv;
+    if (idx) *idx = (int64_t)hi;
+    return 0;
+}
+
 extern "C" int gp_fmin(gp_t *g, double *fmin) {
     if (!g || !fmin) return fail(GP_ERR_ARG, "null argument");
-    GP_DEAD_CHECK(g);
-    if (!g->fitted) return fail(GP_ERR_STATE, "gp_fit first");
+    GP_FITTED(g);
     if (g->P != 1) return fail(GP_ERR_ARG, "gp_fmin needs P == 1");
-    HIPCHK(hipSetDevice(g->device));
     if (!g->fmin_valid) {
         if (g->fmin_direct)
             launch_train_mean(g->s, g->dX, g->N, g->kp, g->dAlpha, g->dMu);
         else
             launch_train_mean_identity(g->s, g->dY, g->dAlpha, g->noise + 1e-8 + g->jitter, g->N, g->dMu);
-        launch_argbest(g->s, g->dMu, g->N, -1, g->dRedV + 256, g->dRedI + 256, g->dRedV, g->dRedI);
-        double v = 0.0;
-        HIPCHK(hipMemcpyAsync(&v, g->dRedV + 256, sizeof(double), hipMemcpyDeviceToHost, g->s));
-        GP_SYNC(g->s);
-        g->fmin = v;
+        int rc;
+        if ((rc = argbest_read(g, g->dMu, g->N, -1, nullptr, &g->fmin))) return rc;
         g->fmin_valid = true;
     }
     *fmin = g->fmin;
     return 0;
 }
 
-int run_acq(gp_ctx *g, int type, double par, double fmin, double y_mean, double y_std) {
-    if (g->P != 1) return fail(GP_ERR_ARG, "acquisitions need P == 1");
-    if (type < GP_ACQ_EI || type > GP_ACQ_MPI) return fail(GP_ERR_ARG, "unknown acquisition %d", type);
+int run_acq(gp_ctx *g, const AcqSpec &a) {
     int rc;
+    if ((rc = check_acq(g, a))) return rc;
     if ((rc = ensure_out(g))) return rc;
     if (!g->predicted || g->predicted_noise != 1)
         if ((rc = run_predict(g, 1))) return rc;  // GPModel.predict: with_noise=True (gpmodel.py:102)
-    launch_acq(g->s, type, par, fmin, y_mean, y_std, g->dMean, g->dVar, g->M, g->dAcq);
+    launch_acq(g->s, a.type, a.par, a.fmin, a.y_mean, a.y_std, g->dMean, g->dVar, g->M, g->dAcq);
     return 0;
 }
 
 extern "C" int gp_acq(gp_t *g, int type, double par, double fmin, double y_mean, double y_std, double *out) {
     if (!g || !out) return fail(GP_ERR_ARG, "null argument");
-    GP_DEAD_CHECK(g);
-    if (!g->fitted) return fail(GP_ERR_STATE, "gp_fit first");
-    if (g->M < 1) return fail(GP_ERR_STATE, "gp_set_candidates first");
-    HIPCHK(hipSetDevice(g->device));
+    GP_SCORING(g);
+    return acq_values(g, AcqSpec{type, par, fmin, y_mean, y_std}, nullptr, out, nullptr);
+}
+
+// The winner among the resident candidates of the acquisition -- penalised when lp is given --, the rows of exclude [nex] out of
+// the running (run.py:1249-1252 masks the rows already taken)
+int acq_argbest(gp_ctx *g, const AcqSpec &a, const LpSpec *lp, int sense, const int64_t *exclude, int nex, int64_t *idx, double *val) {
+    if (!g || !idx || !val) return fail(GP_ERR_ARG, "null argument");
+    GP_SCORING(g);
     int rc;
-    if ((rc = run_acq(g, type, par, fmin, y_mean, y_std))) return rc;
-    HIPCHK(hipMemcpyAsync(out, g->dAcq, sizeof(double) * g->M, hipMemcpyDeviceToHost, g->s));
-    GP_SYNC(g->s);
-    return 0;
+    if ((rc = check_sense(sense))) return rc;
+    if ((rc = check_exclude(exclude, nex, g->M))) return rc;
+    if ((rc = lp ? run_acq_lp(g, a, *lp) : run_acq(g, a))) return rc;
+    if (nex > 0) {
+        long long *rows = g->dRedI + REDI_EXCLUDE.off;
+        HIPCHK(hipMemcpyAsync(rows, exclude, sizeof(long long) * nex, hipMemcpyHostToDevice, g->s));
+        mask_rows(g, rows, nex, sense);
+    }
+    return argbest_read(g, g->dAcq, g->M, sense, idx, val);
 }
 
 extern "C" int gp_acq_argbest(gp_t *g, int type, double par, double fmin, double y_mean, double y_std, int sense, int64_t *idx,
                    double *val) {
-    if (!g || !idx || !val) return fail(GP_ERR_ARG, "null argument");
-    GP_DEAD_CHECK(g);
-    if (!g->fitted) return fail(GP_ERR_STATE, "gp_fit first");
-    if (g->M < 1) return fail(GP_ERR_STATE, "gp_set_candidates first");
-    if (sense != 1 && sense != -1) return fail(GP_ERR_ARG, "sense must be +1 or -1");
-    HIPCHK(hipSetDevice(g->device));
-    int rc;
-    if ((rc = run_acq(g, type, par, fmin, y_mean, y_std))) return rc;
-    launch_argbest(g->s, g->dAcq, g->M, sense, g->dRedV + 256, g->dRedI + 256, g->dRedV, g->dRedI);
-    double v = 0.0;
-    long long i = 0;
-    HIPCHK(hipMemcpyAsync(&v, g->dRedV + 256, sizeof(double), hipMemcpyDeviceToHost, g->s));
-    HIPCHK(hipMemcpyAsync(&i, g->dRedI + 256, sizeof(long long), hipMemcpyDeviceToHost, g->s));
-    GP_SYNC(g->s);
-    *val = v;
-    *idx = (int64_t)i;
-    return 0;
+    return acq_argbest(g, AcqSpec{type, par, fmin, y_mean, y_std}, nullptr, sense, nullptr, 0, idx, val);
 }
 
 // ---- local penalisation (batch acquisition of run.py:1238-1257; GPyOpt/GPyOpt/acquisitions/LP.py) -----------
 // the batch centres, radii and scales of the penaliser (<= 256 rows) in a small device buffer of their own
-int upload_lp_batch(gp_ctx *g, const double *Xb, int nb, const double *r0, const double *s0, LpBatch *b) {
-    if (nb < 0 || nb > 256) return fail(GP_ERR_ARG, "batch size out of range (0..256)");
+int upload_lp_batch(gp_ctx *g, const LpSpec &lp, LpBatch *b) {
     g->lp_cache_nb = -1;   // (api_rows.hip keeps the last batch it uploaded; this upload replaces it)
     int rc;
-    if ((rc = g->dLp.reserve((long)256 * (GP_MAX_D + 2)))) return rc;
-    b->X = g->dLp;
-    b->r = g->dLp + 256 * GP_MAX_D;
-    b->s = b->r + 256;
-    if (nb > 0) {
-        HIPCHK(hipMemcpyAsync(b->X, Xb, sizeof(double) * nb * g->D, hipMemcpyHostToDevice, g->s));
-        HIPCHK(hipMemcpyAsync(b->r, r0, sizeof(double) * nb, hipMemcpyHostToDevice, g->s));
-        HIPCHK(hipMemcpyAsync(b->s, s0, sizeof(double) * nb, hipMemcpyHostToDevice, g->s));
+    if ((rc = g->dLp.reserve(LP_CAP))) return rc;
+    *b = lp_slots(g);
+    if (lp.nb > 0) {
+        HIPCHK(hipMemcpyAsync(b->X, lp.Xb, sizeof(double) * lp.nb * g->D, hipMemcpyHostToDevice, g->s));
+        HIPCHK(hipMemcpyAsync(b->r, lp.r0, sizeof(double) * lp.nb, hipMemcpyHostToDevice, g->s));
+        HIPCHK(hipMemcpyAsync(b->s, lp.s0, sizeof(double) * lp.nb, hipMemcpyHostToDevice, g->s));
     }
     return 0;
 }
 
-int run_acq_lp(gp_ctx *g, int type, double par, double fmin, double y_mean, double y_std, int transform, const double *Xb, int nb, const double *r0, const double *s0) {
+int run_acq_lp(gp_ctx *g, const AcqSpec &a, const LpSpec &lp) {
     int rc;
-    if ((rc = run_acq(g, type, par, fmin, y_mean, y_std))) return rc;
+    if ((rc = check_lp(lp))) return rc;
+    if ((rc = run_acq(g, a))) return rc;
     LpBatch b;
-    if ((rc = upload_lp_batch(g, Xb, nb, r0, s0, &b))) return rc;
-    launch_lp(g->s, g->dAcq, g->dXs, g->M, g->D, b.X, nb, b.r, b.s, transform, g->dAcq);
+    if ((rc = upload_lp_batch(g, lp, &b))) return rc;
+    launch_lp(g->s, g->dAcq, g->dXs, g->M, g->D, b.X, lp.nb, b.r, b.s, lp.transform, g->dAcq);
     return 0;
 }
 
 extern "C" int gp_acq_lp(gp_t *g, int type, double par, double fmin, double y_mean, double y_std, int transform,
               const double *Xb, int nb, const double *r_x0, const double *s_x0, double *out) {
-    if (!g || !out || (nb > 0 && (!Xb || !r_x0 || !s_x0))) return fail(GP_ERR_ARG, "null argument");
-    GP_DEAD_CHECK(g);
-    if (!g->fitted) return fail(GP_ERR_STATE, "gp_fit first");
-    if (g->M < 1) return fail(GP_ERR_STATE, "gp_set_candidates first");
-    HIPCHK(hipSetDevice(g->device));
-    int rc;
-    if ((rc = run_acq_lp(g, type, par, fmin, y_mean, y_std, transform, Xb, nb, r_x0, s_x0))) return rc;
-    HIPCHK(hipMemcpyAsync(out, g->dAcq, sizeof(double) * g->M, hipMemcpyDeviceToHost, g->s));
-    GP_SYNC(g->s);
-    return 0;
+    if (!g || !out) return fail(GP_ERR_ARG, "null argument");
+    GP_SCORING(g);
+    const LpSpec lp{transform, Xb, nb, r_x0, s_x0};
+    return acq_values(g, AcqSpec{type, par, fmin, y_mean, y_std}, &lp, out, nullptr);
 }
 
 extern "C" int gp_acq_lp_argbest(gp_t *g, int type, double par, double fmin, double y_mean, double y_std, int transform,
                       const double *Xb, int nb, const double *r_x0, const double *s_x0, int sense,
                       const int64_t *exclude, int nex, int64_t *idx, double *val) {
-    if (!g || !idx || !val || (nb > 0 && (!Xb || !r_x0 || !s_x0)) || (nex > 0 && !exclude))
-        return fail(GP_ERR_ARG, "null argument");
-    GP_DEAD_CHECK(g);
-    if (!g->fitted) return fail(GP_ERR_STATE, "gp_fit first");
-    if (g->M < 1) return fail(GP_ERR_STATE, "gp_set_candidates first");
-    if (sense != 1 && sense != -1) return fail(GP_ERR_ARG, "sense must be +1 or -1");
-    if (nex < 0 || nex > 256) return fail(GP_ERR_ARG, "too many excluded rows (<= 256)");
-    HIPCHK(hipSetDevice(g->device));
-    int rc;
-    if ((rc = run_acq_lp(g, type, par, fmin, y_mean, y_std, transform, Xb, nb, r_x0, s_x0))) return rc;
-    if (nex > 0) {  // rows already taken never win (run.py:1249-1252 masks them)
-        for (int i = 0; i < nex; ++i)
-            if (exclude[i] < 0 || exclude[i] >= g->M) return fail(GP_ERR_ARG, "excluded row out of range");
-        HIPCHK(hipMemcpyAsync(g->dRedI + 300, exclude, sizeof(long long) * nex, hipMemcpyHostToDevice, g->s));
-        launch_mask(g->s, g->dAcq, g->dRedI + 300, nex, sense > 0 ? -INFINITY : INFINITY);
-    }
-    launch_argbest(g->s, g->dAcq, g->M, sense, g->dRedV + 256, g->dRedI + 256, g->dRedV, g->dRedI);
-    double v = 0.0;
-    long long i = 0;
-    HIPCHK(hipMemcpyAsync(&v, g->dRedV + 256, sizeof(double), hipMemcpyDeviceToHost, g->s));
-    HIPCHK(hipMemcpyAsync(&i, g->dRedI + 256, sizeof(long long), hipMemcpyDeviceToHost, g->s));
-    GP_SYNC(g->s);
-    *val = v;
-    *idx = (int64_t)i;
-    return 0;
+    const LpSpec lp{transform, Xb, nb, r_x0, s_x0};
+    return acq_argbest(g, AcqSpec{type, par, fmin, y_mean, y_std}, &lp, sense, exclude, nex, idx, val);
 }
 
 // full_cov = True branch of PosteriorExact._raw_predict (posterior.py:280-284)
 extern "C" int gp_predict_full_cov(gp_t *g, int include_noise, double *mean, double *cov) {
     if (!g || !cov) return fail(GP_ERR_ARG, "null argument");
-    GP_DEAD_CHECK(g);
-    if (!g->fitted) return fail(GP_ERR_STATE, "gp_fit first");
-    if (g->M < 1) return fail(GP_ERR_STATE, "gp_set_candidates first");
-    HIPCHK(hipSetDevice(g->device));
+    GP_SCORING(g);
     const long M = g->M, Npad = g->Npad, Mpad = round_up(M, GP_TILE);
     if (Mpad > g->mc_max) return fail(GP_ERR_ARG, "full covariance needs M <= mc_max (%ld)", g->mc_max);
     int rc;
@@ -268,26 +260,22 @@ extern "C" int gp_predict_full_cov(gp_t *g, int include_noise, double *mean, dou
 // ---- top-k of the acquisition scores (anchor_points_generator.py:61: argsort(scores)[:num_anchor]) ---------------
 // k rounds of the deterministic arg-best reduction, each followed by masking the winner on the device: ties resolve
 // to the lowest index in every round, i.e. the order of a stable sort by (score, index).
-extern "C" int gp_acq_topk(gp_t *g, int type, double par, double fmin, double y_mean, double y_std, int sense, int k,
-                int64_t *idx, double *val) {
+int acq_topk(gp_ctx *g, const AcqSpec &a, int sense, int k, int64_t *idx, double *val) {
     if (!g || !idx || !val) return fail(GP_ERR_ARG, "null argument");
-    GP_DEAD_CHECK(g);
-    if (!g->fitted) return fail(GP_ERR_STATE, "gp_fit first");
-    if (g->M < 1) return fail(GP_ERR_STATE, "gp_set_candidates first");
-    if (sense != 1 && sense != -1) return fail(GP_ERR_ARG, "sense must be +1 or -1");
-    if (k < 1 || k > GP_TOPK_MAX) return fail(GP_ERR_ARG, "k out of range (1..%d)", GP_TOPK_MAX);
-    HIPCHK(hipSetDevice(g->device));
+    GP_SCORING(g);
     int rc;
-    if ((rc = run_acq(g, type, par, fmin, y_mean, y_std))) return rc;
-    if ((rc = g->dComm.reserve(2L * GP_TOPK_MAX * (1 + 128)))) return rc;
-    double *dv = g->dComm;
-    long long *di = (long long *)(g->dComm + GP_TOPK_MAX);
+    if ((rc = check_sense(sense))) return rc;
+    if ((rc = check_k(k))) return rc;
+    if ((rc = run_acq(g, a))) return rc;
+    if ((rc = g->dComm.reserve(COMM_CAP))) return rc;
+    double *dv = g->dComm + COMM_TOPK_VAL.off;
+    long long *di = (long long *)(g->dComm + COMM_TOPK_ROW.off);
     const int kk = (int)std::min<long>(k, g->M);
     for (int j = 0; j < kk; ++j) {
-        launch_argbest(g->s, g->dAcq, g->M, sense, g->dRedV + 256, g->dRedI + 256, g->dRedV, g->dRedI);
-        HIPCHK(hipMemcpyAsync(dv + j, g->dRedV + 256, 8, hipMemcpyDeviceToDevice, g->s));
-        HIPCHK(hipMemcpyAsync(di + j, g->dRedI + 256, 8, hipMemcpyDeviceToDevice, g->s));
-        launch_mask(g->s, g->dAcq, g->dRedI + 256, 1, sense > 0 ? -INFINITY : INFINITY);
+        argbest_launch(g, g->dAcq, g->M, sense);
+        HIPCHK(hipMemcpyAsync(dv + j, g->dRedV + RED_RESULT.off, 8, hipMemcpyDeviceToDevice, g->s));
+        HIPCHK(hipMemcpyAsync(di + j, g->dRedI + RED_RESULT.off, 8, hipMemcpyDeviceToDevice, g->s));
+        mask_rows(g, g->dRedI + RED_RESULT.off, 1, sense);
     }
     std::vector<long long> hi(kk);
     HIPCHK(hipMemcpyAsync(val, dv, sizeof(double) * kk, hipMemcpyDeviceToHost, g->s));
@@ -296,9 +284,14 @@ extern "C" int gp_acq_topk(gp_t *g, int type, double par, double fmin, double y_
     for (int j = 0; j < kk; ++j) idx[j] = (int64_t)hi[j];
     for (int j = kk; j < k; ++j) {  // fewer candidates than k: the tail is marked empty
         idx[j] = -1;
-        val[j] = sense > 0 ? -INFINITY : INFINITY;
+        val[j] = acq_empty(sense);
     }
     return 0;
+}
+
+extern "C" int gp_acq_topk(gp_t *g, int type, double par, double fmin, double y_mean, double y_std, int sense, int k,
+                int64_t *idx, double *val) {
+    return acq_topk(g, AcqSpec{type, par, fmin, y_mean, y_std}, sense, k, idx, val);
 }
 
 // ---- posterior samples of the latent function (GP.posterior_samples_f, gp.py:581-609) ------------------------
@@ -310,11 +303,8 @@ extern "C" int gp_acq_topk(gp_t *g, int type, double par, double fmin, double y_
 extern "C" int gp_posterior_samples(gp_t *g, int include_noise, const double *Z, int S, int maxtries, double *mean, double *dev,
                          double *jitter_used) {
     if (!g || !Z || !dev) return fail(GP_ERR_ARG, "null argument");
-    GP_DEAD_CHECK(g);
-    if (!g->fitted) return fail(GP_ERR_STATE, "gp_fit first");
-    if (g->M < 1) return fail(GP_ERR_STATE, "gp_set_candidates first");
+    GP_SCORING(g);
     if (S < 1) return fail(GP_ERR_ARG, "S < 1");
-    HIPCHK(hipSetDevice(g->device));
     const long M = g->M, Npad = g->Npad, Mpad = round_up(M, GP_TILE), Spad = round_up(S, GP_TILE);
     if (Mpad > g->mc_max) return fail(GP_ERR_ARG, "posterior samples need M <= mc_max (%ld)", g->mc_max);
     int rc;
@@ -340,8 +330,8 @@ extern "C" int gp_posterior_samples(gp_t *g, int include_noise, const double *Z,
         gemm(g, g->s, 1, C, Mpad, g->dT2, Npad, g->dT2, Npad, 1, (int)Npad, TileSet{0, mt, 0, mt, 0});
         if (include_noise) launch_add_diag(g->s, C, Mpad, M, g->noise);
         if (tries == 0) {
-            launch_trace(g->s, C, Mpad, M, g->dScal + 420);
-            HIPCHK(hipMemcpyAsync(diag_stat, g->dScal + 420, 2 * sizeof(double), hipMemcpyDeviceToHost, g->s));
+            launch_trace(g->s, C, Mpad, M, g->dScal + SCAL_TRACE.off);
+            HIPCHK(hipMemcpyAsync(diag_stat, g->dScal + SCAL_TRACE.off, sizeof diag_stat, hipMemcpyDeviceToHost, g->s));
         }
         if (jitter != 0.0) launch_add_diag(g->s, C, Mpad, M, jitter);
         HIPCHK(hipMemsetAsync(g->dInfo, 0, sizeof(int) * 4, g->s));

@@ -70,71 +70,90 @@ static int rows_wait(gp_ctx *g, RowsWork &w, unsigned finish_grid) {
 }
 
 // the penaliser's batch on the device; re-uploaded only when it changed (an L-BFGS run keeps one batch for hundreds of calls)
-static int rows_lp_batch(gp_ctx *g, const double *Xb, int nb, const double *r0, const double *s0, LpBatch *b) {
+static int rows_lp_batch(gp_ctx *g, const LpSpec &lp, LpBatch *b) {
+    const int nb = lp.nb;
     const size_t nx = (size_t)nb * g->D;
     bool same = g->lp_cache_nb == nb && g->lp_cache.size() == nx + 2 * (size_t)nb && g->dLp;
     if (same && nb > 0)
-        same = !memcmp(g->lp_cache.data(), Xb, sizeof(double) * nx) && !memcmp(g->lp_cache.data() + nx, r0, sizeof(double) * nb) &&
-               !memcmp(g->lp_cache.data() + nx + nb, s0, sizeof(double) * nb);
+        same = !memcmp(g->lp_cache.data(), lp.Xb, sizeof(double) * nx) && !memcmp(g->lp_cache.data() + nx, lp.r0, sizeof(double) * nb) &&
+               !memcmp(g->lp_cache.data() + nx + nb, lp.s0, sizeof(double) * nb);
     if (same) {
-        b->X = g->dLp;
-        b->r = g->dLp + 256 * GP_MAX_D;
-        b->s = b->r + 256;
+        *b = lp_slots(g);
         return 0;
     }
     int rc;
-    if ((rc = upload_lp_batch(g, Xb, nb, r0, s0, b))) return rc;
+    if ((rc = upload_lp_batch(g, lp, b))) return rc;
     g->lp_cache.resize(nx + 2 * (size_t)nb);
     if (nb > 0) {
-        memcpy(g->lp_cache.data(), Xb, sizeof(double) * nx);
-        memcpy(g->lp_cache.data() + nx, r0, sizeof(double) * nb);
-        memcpy(g->lp_cache.data() + nx + nb, s0, sizeof(double) * nb);
+        memcpy(g->lp_cache.data(), lp.Xb, sizeof(double) * nx);
+        memcpy(g->lp_cache.data() + nx, lp.r0, sizeof(double) * nb);
+        memcpy(g->lp_cache.data() + nx + nb, lp.s0, sizeof(double) * nb);
     }
     g->lp_cache_nb = nb;
     return 0;
 }
 
-// One pass of the fused path per ROWS_MAX_M locations.  want_grad selects forward + backward + finish; otherwise forward + finish.
+RowsAcq rows_acq(const AcqSpec &a, const LpSpec *lp, const LpBatch &b) {   // (RowsAcq: on, the base acquisition, lp, the penaliser)
+    if (!lp) return RowsAcq{1, a.type, a.par, a.fmin, a.y_mean, a.y_std, 0, 0, 0, nullptr, nullptr, nullptr};
+    return RowsAcq{1, a.type, a.par, a.fmin, a.y_mean, a.y_std, 1, lp->transform, lp->nb, b.X, b.r, b.s};
+}
+
+// The pass loop of the fused path: ROWS_MAX_M locations per pass, each with a ticket and a counter base of its own.
+// launch(rx, w) puts a pass on the stream and returns how many workgroups arrive at its counter; unpack(m0, mc, MV, o) takes
+// the results of locations [m0, m0 + mc) out of the pinned block o, laid out for MV locations (gphip_internal.h).  With a phase
+// name a profiled context times each pass: `cost` reads of the inverse factor's triangle, and as many N^2 products per location.
+template <class Launch, class Unpack>
+static int rows_passes(gp_ctx *g, const double *Xs, int M, const char *phase, double cost, Launch launch, Unpack unpack) {
+    int rc;
+    RowsWork w;
+    if ((rc = rows_scratch(g, &w))) return rc;
+    const int D = g->D;
+    const bool timed = phase && g->profiling;
+    if (timed) g->nphases = 0;
+    for (int m0 = 0; m0 < M; m0 += ROWS_MAX_M) {
+        const int mc = std::min(ROWS_MAX_M, M - m0);
+        RowsX rx;
+        rx.M = mc;
+        memcpy(rx.xs, Xs + (long)m0 * D, sizeof(double) * mc * D);
+        const int ph = timed ? phase_begin(g, phase, cost * (double)g->N * g->N * mc, cost * 8.0 * (double)g->N * g->N / 2) : -1;
+        if (m0 > 0) {
+            w.ticket = (g->rows_ticket += 1.0);
+            w.counter_base = g->rows_counter_base;
+        }
+        const unsigned arrivals = launch(rx, w);
+        if (timed) phase_end(g, ph);
+        if ((rc = rows_wait(g, w, arrivals))) return rc;
+        unpack(m0, mc, mc == 1 ? 1 : ROWS_MAX_M, g->hRowsOut);
+    }
+    ++g->rows_fused_calls;
+    return 0;
+}
+
+// The fused path over the inverse factor.  want_grad selects forward + backward + finish; otherwise forward + finish.
 // Results: mean / var / acq [M], dmdx / dvdx / dacq [M, D] (any may be null).
 static int rows_fused(gp_ctx *g, const double *Xs, int M, int include_noise, int want_grad, const RowsAcq &aq, double *mean,
                       double *var, double *acq, double *dmdx, double *dvdx, double *dacq) {
     int rc;
     if ((rc = ensure_linv(g))) return rc;
-    RowsWork w;
-    if ((rc = rows_scratch(g, &w))) return rc;
     const int D = g->D;
-    const bool timed = g->profiling;
-    if (timed) g->nphases = 0;
-    for (int m0 = 0; m0 < M; m0 += ROWS_MAX_M) {
-        const int mc = std::min(ROWS_MAX_M, M - m0);
-        const int MV = mc == 1 ? 1 : ROWS_MAX_M;
-        RowsX rx;
-        rx.M = mc;
-        memcpy(rx.xs, Xs + (long)m0 * D, sizeof(double) * mc * D);
-        int ph = timed ? phase_begin(g, want_grad ? "rows_fused_grad" : "rows_fused", (want_grad ? 2.0 : 1.0) * (double)g->N * g->N * mc,
-                                     (want_grad ? 2.0 : 1.0) * 8.0 * (double)g->N * g->N / 2)
-                       : -1;
-        if (m0 > 0) {
-            w.ticket = (g->rows_ticket += 1.0);
-            w.counter_base = g->rows_counter_base;
-        }
-        launch_rows(g->s, g->dLi, g->Npad, rx, g->kp, g->dX, g->N, g->dAlpha, want_grad, g->kp.variance,
-                    include_noise ? g->noise : 0.0, aq, w, g->hRowsOut, g->rows_nt < 0 ? (g->Npad > 8192 ? 1 : 0) : g->rows_nt);
-        if (timed) phase_end(g, ph);
-        if ((rc = rows_wait(g, w, rows_finish_grid(g->N)))) return rc;
-        const double *o = g->hRowsOut;
-        for (int m = 0; m < mc; ++m) {
-            if (mean) mean[m0 + m] = o[m];
-            if (var) var[m0 + m] = o[MV + m];
-            if (acq) acq[m0 + m] = o[2 * MV + m];
-            const double *gm = o + 3 * MV + (long)m * D, *gv = gm + (long)MV * D, *ga = gv + (long)MV * D;
-            if (dmdx) memcpy(dmdx + (long)(m0 + m) * D, gm, sizeof(double) * D);
-            if (dvdx) memcpy(dvdx + (long)(m0 + m) * D, gv, sizeof(double) * D);
-            if (dacq) memcpy(dacq + (long)(m0 + m) * D, ga, sizeof(double) * D);
-        }
-    }
-    ++g->rows_fused_calls;
-    return 0;
+    return rows_passes(
+        g, Xs, M, want_grad ? "rows_fused_grad" : "rows_fused", want_grad ? 2.0 : 1.0,
+        [&](const RowsX &rx, const RowsWork &w) {
+            launch_rows(g->s, g->dLi, g->Npad, rx, g->kp, g->dX, g->N, g->dAlpha, want_grad, g->kp.variance,
+                        include_noise ? g->noise : 0.0, aq, w, g->hRowsOut, g->rows_nt < 0 ? (g->Npad > 8192 ? 1 : 0) : g->rows_nt);
+            return rows_finish_grid(g->N);
+        },
+        [&](int m0, int mc, int MV, const double *o) {
+            for (int m = 0; m < mc; ++m) {
+                if (mean) mean[m0 + m] = o[m];
+                if (var) var[m0 + m] = o[MV + m];
+                if (acq) acq[m0 + m] = o[2 * MV + m];
+                const double *gm = o + 3 * MV + (long)m * D, *gv = gm + (long)MV * D, *ga = gv + (long)MV * D;
+                if (dmdx) memcpy(dmdx + (long)(m0 + m) * D, gm, sizeof(double) * D);
+                if (dvdx) memcpy(dvdx + (long)(m0 + m) * D, gv, sizeof(double) * D);
+                if (dacq) memcpy(dacq + (long)(m0 + m) * D, ga, sizeof(double) * D);
+            }
+        });
 }
 
 // The posterior of a handful of locations: gp_set_candidates + gp_predict (+ gp_predict_grad when dmdx / dvdx are given) as ONE
@@ -142,37 +161,24 @@ static int rows_fused(gp_ctx *g, const double *Xs, int M, int include_noise, int
 extern "C" int gp_predict_rows(gp_t *g, const double *Xs, int64_t M, int include_noise, double *mean, double *var, double *dmdx,
                                double *dvdx) {
     if (!g || !Xs) return fail(GP_ERR_ARG, "null argument");
-    GP_DEAD_CHECK(g);
-    if (!g->fitted) return fail(GP_ERR_STATE, "gp_fit first");
+    GP_FITTED(g);
     if (M < 1) return fail(GP_ERR_ARG, "M < 1");
     if (dvdx && !dmdx) return fail(GP_ERR_ARG, "dvdx needs dmdx");
     if (dmdx && !dvdx && (mean || var)) return fail(GP_ERR_ARG, "the mean's gradient alone (dvdx NULL) comes without mean / var");
-    HIPCHK(hipSetDevice(g->device));
+    int rc;
     if (dmdx && !dvdx) {
         // d mean / dx alone: one pass over the training points, no inverse factor, no substitutions (estimate_L's inner call)
         if (rows_fused_ok(g, M)) {
-            int rc;
-            RowsWork w;
-            if ((rc = rows_scratch(g, &w))) return rc;
-            for (int m0 = 0; m0 < (int)M; m0 += ROWS_MAX_M) {
-                const int mc = std::min(ROWS_MAX_M, (int)M - m0);
-                const int MV = mc == 1 ? 1 : ROWS_MAX_M;
-                RowsX rx;
-                rx.M = mc;
-                memcpy(rx.xs, Xs + (long)m0 * g->D, sizeof(double) * mc * g->D);
-                if (m0 > 0) {
-                    w.ticket = (g->rows_ticket += 1.0);
-                    w.counter_base = g->rows_counter_base;
-                }
-                launch_rows_mean_grad(g->s, rx, g->kp, g->dX, g->N, g->dAlpha, w, g->hRowsOut);
-                if ((rc = rows_wait(g, w, rows_mean_grad_grid(g->N)))) return rc;
-                memcpy(dmdx + (long)m0 * g->D, g->hRowsOut + 3 * MV, sizeof(double) * mc * g->D);
-            }
-            ++g->rows_fused_calls;
-            return 0;
+            const int D = g->D;
+            return rows_passes(
+                g, Xs, (int)M, nullptr, 0.0,
+                [&](const RowsX &rx, const RowsWork &w) {
+                    launch_rows_mean_grad(g->s, rx, g->kp, g->dX, g->N, g->dAlpha, w, g->hRowsOut);
+                    return rows_mean_grad_grid(g->N);
+                },
+                [&](int m0, int mc, int MV, const double *o) { memcpy(dmdx + (long)m0 * D, o + 3 * MV, sizeof(double) * mc * D); });
         }
         ++g->rows_fallback_calls;
-        int rc;
         if ((rc = gp_set_candidates(g, Xs, M))) return rc;
         return gp_predict_grad(g, dmdx, nullptr);
     }
@@ -182,7 +188,6 @@ extern "C" int gp_predict_rows(gp_t *g, const double *Xs, int64_t M, int include
         return rows_fused(g, Xs, (int)M, include_noise, want_grad, aq, mean, var, nullptr, dmdx, dvdx, nullptr);
     }
     ++g->rows_fallback_calls;
-    int rc;
     if ((rc = gp_set_candidates(g, Xs, M))) return rc;
     if (mean || var)
         if ((rc = gp_predict(g, include_noise, mean, var))) return rc;
@@ -197,43 +202,22 @@ extern "C" int gp_acq_rows(gp_t *g, const double *Xs, int64_t M, int type, doubl
                            int lp, int transform, const double *Xb, int nb, const double *r_x0, const double *s_x0, double *out,
                            double *dout) {
     if (!g || !Xs || !out) return fail(GP_ERR_ARG, "null argument");
-    GP_DEAD_CHECK(g);
-    if (!g->fitted) return fail(GP_ERR_STATE, "gp_fit first");
+    GP_FITTED(g);
     if (M < 1) return fail(GP_ERR_ARG, "M < 1");
-    if (g->P != 1) return fail(GP_ERR_ARG, "acquisitions need P == 1");
-    if (type < GP_ACQ_EI || type > GP_ACQ_MPI) return fail(GP_ERR_ARG, "unknown acquisition %d", type);
-    if (lp && transform != 0 && transform != 1) return fail(GP_ERR_ARG, "transform must be 0 (none) or 1 (softplus)");
-    if (lp && nb > 0 && (!Xb || !r_x0 || !s_x0)) return fail(GP_ERR_ARG, "null argument");
-    if (lp && (nb < 0 || nb > 256)) return fail(GP_ERR_ARG, "batch size out of range (0..256)");
-    HIPCHK(hipSetDevice(g->device));
-    const int want_grad = dout != nullptr;
+    const AcqSpec a{type, par, fmin, y_mean, y_std};
+    const LpSpec batch{transform, Xb, nb, r_x0, s_x0}, *pen = lp ? &batch : nullptr;
     int rc;
+    if ((rc = check_acq(g, a))) return rc;
+    if (pen && (rc = check_lp(*pen))) return rc;
     if (rows_fused_ok(g, M) && rows_use_factor(g)) {
-        RowsAcq aq{};
-        aq.on = 1;
-        aq.type = type;
-        aq.par = par;
-        aq.fmin = fmin;
-        aq.y_mean = y_mean;
-        aq.y_std = y_std;
-        aq.lp = lp ? 1 : 0;
-        aq.transform = transform;
-        aq.nb = lp ? nb : 0;
-        if (lp) {
-            LpBatch b;
-            if ((rc = rows_lp_batch(g, Xb, nb, r_x0, s_x0, &b))) return rc;
-            aq.Xb = b.X;
-            aq.r0 = b.r;
-            aq.s0 = b.s;
-        }
-        return rows_fused(g, Xs, (int)M, 1, want_grad, aq, nullptr, nullptr, out, nullptr, nullptr, dout);   // with_noise=True, gpmodel.py:102
+        LpBatch b;
+        if (pen && (rc = rows_lp_batch(g, *pen, &b))) return rc;
+        return rows_fused(g, Xs, (int)M, 1, dout != nullptr, rows_acq(a, pen, b), nullptr, nullptr, out, nullptr, nullptr,
+                          dout);   // with_noise=True, gpmodel.py:102
     }
     ++g->rows_fallback_calls;
     if ((rc = gp_set_candidates(g, Xs, M))) return rc;
-    if (lp)
-        return want_grad ? gp_acq_lp_grad(g, type, par, fmin, y_mean, y_std, transform, Xb, nb, r_x0, s_x0, out, dout)
-                         : gp_acq_lp(g, type, par, fmin, y_mean, y_std, transform, Xb, nb, r_x0, s_x0, out);
-    return want_grad ? gp_acq_grad(g, type, par, fmin, y_mean, y_std, out, dout) : gp_acq(g, type, par, fmin, y_mean, y_std, out);
+    return acq_values(g, a, pen, out, dout);
 }
 
 // how many *_rows calls took the fused path / the batched entry points since the context was created (route checks in tests)

@@ -1,9 +1,12 @@
 // hip_recorder: a stand-in for the HIP runtime (and RCCL) that runs NO kernel and needs no GPU.  Device memory is host memory
 // from a bump allocator, copies are memcpy, and every call that orders or feeds a stream is written to $HIP_RECORDER_LOG in host
 // order: launches (kernel, grid, block, LDS, stream; for gemm_nt_kernel every field of its GemmArgs, pointers as allocation index +
-// offset), hipEventRecord, hipStreamWaitEvent, memsets, copies, synchronisations, allocations.  Streams and events are numbered by
-// first appearance.  The numbers an entry point returns are meaningless (zeros); the factorisation's status word reads 0, so a
-// fit takes its first attempt ($HIP_RECORDER_FAIL=n: the first n status words read 1 instead, which walks the jitter ladder).
+// offset; for the scoring kernels whose parameters are pointers and scalars only, every argument), hipEventRecord,
+// hipStreamWaitEvent, memsets and copies (with destination and source), all-gathers, synchronisations, allocations.  Streams and
+// events are numbered by first appearance.  The numbers an entry point returns are meaningless (zeros); the factorisation's status
+// word reads 0, so a fit takes its first attempt ($HIP_RECORDER_FAIL=n: the first n status words read 1 instead, which walks the
+// jitter ladder).  Two things are acted out because the host code waits for them: the finishing kernels of the one-location path
+// hand their ticket back, and the RCCL stand-ins give out communicators (of ONE rank: an all-gather copies send to receive).
 // What it is for: a refactor of host code must leave this log unchanged.
 //
 // Build a recording libgphip.so from the objects of a normal build (make -C gaussian_process_optimization_amd/csrc), in a copy
@@ -11,8 +14,9 @@
 //   g++ -O1 -fPIC -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -c tools/hip_recorder.cpp -o hip_recorder.o
 //   g++ -shared -fPIC gaussian_process_optimization_amd/csrc/*.o hip_recorder.o -o <copy>/gaussian_process_optimization_amd/libgphip.so
 //   PYTHONPATH=<copy> HIP_RECORDER_LOG=case1.log python tools/stream_ops.py 1
-// (struct GemmArgs below mirrors csrc/gemm.hip.)
+// (struct GemmArgs below mirrors csrc/gemm.hip; ROWS_OUT_DOUBLES and the argument positions in rows_ticket csrc/onerow.hip.)
 #include <hip/hip_runtime_api.h>
+#include <rccl/rccl.h>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -46,6 +50,30 @@ static std::map<const void *, std::string> &kn() { static std::map<const void *,
 static std::map<const void *, int> g_s, g_e;
 static int sid(const void *s) { auto it = g_s.find(s); if (it == g_s.end()) it = g_s.emplace(s, (int)g_s.size()).first; return it->second; }
 static int eid(const void *e) { auto it = g_e.find(e); if (it == g_e.end()) it = g_e.emplace(e, (int)g_e.size()).first; return it->second; }
+// every argument of a kernel whose parameters are pointers and scalars, by the parameter types in its mangled name (after the
+// kernel's own name): P[K]<t> or a substitution S<n>_ is a pointer; d a double; i / j 32 bits; l / m / x / y 64 bits
+static const char *const kScoring[] = {"argbest_kernel", "mask_kernel", "acq_kernel", "acq_grad_kernel", "lp_kernel", "lp_grad_kernel", "predict_reduce_kernel"};
+static void log_args(FILE *f, const std::string &mangled, void **args) {
+    for (const char *k : kScoring) {
+        const std::string key = std::to_string(strlen(k)) + k;
+        if (mangled.compare(0, 2 + key.size(), "_Z" + key)) continue;
+        int n = 0;
+        for (const char *t = mangled.c_str() + 2 + key.size(); *t; ++t, ++n) {
+            if (*t == 'P') { t += (t[1] == 'K') ? 2 : 1; fprintf(f, " %s", pname(*(void **)args[n]).c_str()); }
+            else if (*t == 'S') { while (*t != '_') ++t; fprintf(f, " %s", pname(*(void **)args[n]).c_str()); }
+            else if (*t == 'd') fprintf(f, " %.17g", *(double *)args[n]);
+            else if (*t == 'i' || *t == 'j') fprintf(f, " %d", *(int *)args[n]);
+            else fprintf(f, " %lld", *(long long *)args[n]);
+        }
+        return;
+    }
+}
+// rows_finish_kernel / rows_mean_grad_kernel: the last argument (ticket) goes behind the result block, the last but one
+#define ROWS_OUT_DOUBLES (3 * 4 * (1 + 64))
+static void rows_ticket(const std::string &name, void **args) {
+    const int nargs = name.find("rows_finish_kernel") != std::string::npos ? 21 : name.find("rows_mean_grad_kernel") != std::string::npos ? 10 : 0;
+    if (nargs) (*(double **)args[nargs - 2])[ROWS_OUT_DOUBLES] = *(double *)args[nargs - 1];
+}
 struct Cfg { dim3 g, b; size_t sh; hipStream_t s; };
 static thread_local Cfg g_cfg;
 extern "C" {
@@ -64,6 +92,8 @@ hipError_t hipLaunchKernel(const void *f, dim3 g, dim3 b, void **args, size_t sh
                 pname(a.C).c_str(), a.ldc, pname(a.A).c_str(), a.lda, pname(a.B).c_str(), a.ldb, a.b_mul, a.K, a.r0, a.r1, a.c0, a.c1, a.tri, a.k_tri, a.k_sub,
                 a.k_end_tri, a.b_sub, a.sC, a.sA, a.sB, pname(a.tile_list).c_str(), a.stagger, a.pair);
     }
+    log_args(lg(), name, args);
+    rows_ticket(name, args);
     fprintf(lg(), "\n");
     return hipSuccess;
 }
@@ -88,22 +118,37 @@ hipError_t hipGetDeviceCount(int *n) { *n = 1; return hipSuccess; }
 hipError_t hipGetDevicePropertiesR0600(hipDeviceProp_tR0600 *p, int) { memset(p, 0, sizeof *p); p->multiProcessorCount = 256; strcpy(p->name, "recorder"); strcpy(p->gcnArchName, "gfx950"); return hipSuccess; }
 const char *hipGetErrorString(hipError_t) { return "recorder"; }
 hipError_t hipGetLastError() { return hipSuccess; }
-hipError_t hipMemcpy(void *d, const void *s, size_t n, hipMemcpyKind k) { fprintf(lg(), "memcpy %zu kind %d\n", n, (int)k); memcpy(d, s, n); return hipSuccess; }
+hipError_t hipMemcpy(void *d, const void *s, size_t n, hipMemcpyKind k) { fprintf(lg(), "memcpy %zu kind %d %s <- %s\n", n, (int)k, pname(d).c_str(), pname(s).c_str()); memcpy(d, s, n); return hipSuccess; }
 hipError_t hipMemcpyAsync(void *d, const void *s, size_t n, hipMemcpyKind k, hipStream_t st) {
     static int fail = getenv("HIP_RECORDER_FAIL") ? atoi(getenv("HIP_RECORDER_FAIL")) : 0;
-    fprintf(lg(), "memcpyAsync %zu kind %d s%d\n", n, (int)k, sid(st));
+    fprintf(lg(), "memcpyAsync %zu kind %d s%d %s <- %s\n", n, (int)k, sid(st), pname(d).c_str(), pname(s).c_str());
     memcpy(d, s, n);
     if (n == sizeof(int) && k == hipMemcpyDeviceToHost && fail > 0 && fail--) *(int *)d = 1;   // a status word that reports a failed pivot
     return hipSuccess;
 }
 static void cp2d(void *d, size_t dp, const void *s, size_t sp, size_t w, size_t h) { for (size_t i = 0; i < h; ++i) memcpy((char *)d + i * dp, (const char *)s + i * sp, w); }
-hipError_t hipMemcpy2D(void *d, size_t dp, const void *s, size_t sp, size_t w, size_t h, hipMemcpyKind k) { fprintf(lg(), "memcpy2D %zu x %zu kind %d\n", w, h, (int)k); cp2d(d, dp, s, sp, w, h); return hipSuccess; }
-hipError_t hipMemcpy2DAsync(void *d, size_t dp, const void *s, size_t sp, size_t w, size_t h, hipMemcpyKind k, hipStream_t st) { fprintf(lg(), "memcpy2DAsync %zu x %zu kind %d s%d\n", w, h, (int)k, sid(st)); cp2d(d, dp, s, sp, w, h); return hipSuccess; }
+hipError_t hipMemcpy2D(void *d, size_t dp, const void *s, size_t sp, size_t w, size_t h, hipMemcpyKind k) { fprintf(lg(), "memcpy2D %zu x %zu kind %d %s <- %s\n", w, h, (int)k, pname(d).c_str(), pname(s).c_str()); cp2d(d, dp, s, sp, w, h); return hipSuccess; }
+hipError_t hipMemcpy2DAsync(void *d, size_t dp, const void *s, size_t sp, size_t w, size_t h, hipMemcpyKind k, hipStream_t st) { fprintf(lg(), "memcpy2DAsync %zu x %zu kind %d s%d %s <- %s\n", w, h, (int)k, sid(st), pname(d).c_str(), pname(s).c_str()); cp2d(d, dp, s, sp, w, h); return hipSuccess; }
 hipError_t hipMemcpyToSymbol(const void *, const void *, size_t, size_t, hipMemcpyKind) { return hipSuccess; }
-hipError_t hipMemset(void *d, int v, size_t n) { fprintf(lg(), "memset %zu\n", n); if (n <= (1 << 20)) memset(d, v, n); return hipSuccess; }
-hipError_t hipMemsetAsync(void *d, int v, size_t n, hipStream_t s) { fprintf(lg(), "memsetAsync %zu s%d\n", n, sid(s)); if (n <= (1 << 20)) memset(d, v, n); return hipSuccess; }
+hipError_t hipMemset(void *d, int v, size_t n) { fprintf(lg(), "memset %zu %s\n", n, pname(d).c_str()); if (n <= (1 << 20)) memset(d, v, n); return hipSuccess; }
+hipError_t hipMemsetAsync(void *d, int v, size_t n, hipStream_t s) { fprintf(lg(), "memsetAsync %zu s%d %s\n", n, sid(s), pname(d).c_str()); if (n <= (1 << 20)) memset(d, v, n); return hipSuccess; }
 hipError_t hipSetDevice(int) { return hipSuccess; }
-int ncclAllGather() { return 0; } int ncclBroadcast() { return 0; } int ncclCommAbort() { return 0; } int ncclCommCount() { return 0; }
-int ncclCommDestroy() { return 0; } int ncclCommInitAll() { return 0; } int ncclCommInitRank() { return 0; } int ncclCommUserRank() { return 0; }
-const char *ncclGetErrorString() { return "recorder"; } int ncclGetUniqueId() { return 0; } int ncclGetVersion() { return 0; } int ncclGroupEnd() { return 0; } int ncclGroupStart() { return 0; }
+static ncclComm_t one_rank_comm() { return (ncclComm_t)malloc(1); }
+ncclResult_t ncclAllGather(const void *send, void *recv, size_t count, ncclDataType_t, ncclComm_t, hipStream_t s) {
+    fprintf(lg(), "allgather %zu s%d %s <- %s\n", count, sid(s), pname(recv).c_str(), pname(send).c_str());
+    memmove(recv, send, count * sizeof(double));   // (ncclDouble is the only type the library gathers)
+    return ncclSuccess;
+}
+ncclResult_t ncclBroadcast(const void *, void *, size_t, ncclDataType_t, int, ncclComm_t, hipStream_t) { return ncclSuccess; }
+ncclResult_t ncclCommAbort(ncclComm_t) { return ncclSuccess; }
+ncclResult_t ncclCommCount(const ncclComm_t, int *n) { *n = 1; return ncclSuccess; }
+ncclResult_t ncclCommDestroy(ncclComm_t) { return ncclSuccess; }
+ncclResult_t ncclCommInitAll(ncclComm_t *comms, int n, const int *) { for (int i = 0; i < n; ++i) comms[i] = one_rank_comm(); return ncclSuccess; }
+ncclResult_t ncclCommInitRank(ncclComm_t *comm, int, ncclUniqueId, int) { *comm = one_rank_comm(); return ncclSuccess; }
+ncclResult_t ncclCommUserRank(const ncclComm_t, int *r) { *r = 0; return ncclSuccess; }
+const char *ncclGetErrorString(ncclResult_t) { return "recorder"; }
+ncclResult_t ncclGetUniqueId(ncclUniqueId *id) { memset(id, 0, sizeof *id); return ncclSuccess; }
+ncclResult_t ncclGetVersion(int *v) { *v = 0; return ncclSuccess; }
+ncclResult_t ncclGroupEnd() { return ncclSuccess; }
+ncclResult_t ncclGroupStart() { return ncclSuccess; }
 }

@@ -1,13 +1,14 @@
-"""One case of the stream-operation comparison between two builds (profiles/r09_scheduler_strands.txt): every strand of the
-factorisation scheduler, each call made twice (the first allocates, the second is the steady state).  Run it under
-rocprofv3 --kernel-trace / --hip-trace on a GPU, or against a library linked with tools/hip_recorder.cpp anywhere.
-usage: stream_ops.py <case: 1 2 3 4a 4b 5 6a 6b 7 8 9>"""
+"""One case of the stream-operation comparison between two builds (profiles/r09_scheduler_strands.txt, r10_scoring_layer.txt):
+every strand of the factorisation scheduler (1 ... 9) and the scoring entry points (s1 ... s5), each call made twice (the first
+allocates, the second is the steady state).  Run it under rocprofv3 --kernel-trace / --hip-trace on a GPU, or against a library
+linked with tools/hip_recorder.cpp anywhere.  The scoring cases save every array and scalar they got back when given a path.
+usage: stream_ops.py <case: 1 2 3 4a 4b 5 6a 6b 7 8 9 s1 s2 s3 s4a s4b s5> [results.npz]"""
 import sys
 import numpy as np
 from gaussian_process_optimization_amd import _lib
 
 case = sys.argv[1]
-D = 5
+D = 3 if case.startswith("s") else 5
 def problem(N, M=0, seed=7):
     rng = np.random.default_rng(seed)
     X = rng.uniform(0, 1, (N, D)); Y = np.sin(3 * X).sum(1, keepdims=True) + 0.1 * rng.standard_normal((N, 1))
@@ -55,6 +56,51 @@ elif case == "9":   # the default owned-column rule where it owns columns, with 
     for pct in (0, 50):
         h.set_option("own_keep_pipe_pct", pct)
         h.fit(); h.fit_predict(True); h.fit_grad(1)
+elif case.startswith("s"):
+    EI, LCB = _lib.GP_ACQ_EI, _lib.GP_ACQ_LCB
+    got = {}
+    def keep(name, fn):   # fn twice; what the second call returned, flattened into got[name.i]
+        r = twice(fn)
+        for i, x in enumerate(r if isinstance(r, tuple) else (r,)): got["%s.%d" % (name, i)] = np.asarray(x)
+        return r
+    rng = np.random.default_rng(11)
+    Xb, r0, s0 = rng.uniform(0, 1, (3, D)), np.array([0.05, 0.2, 0.01]), np.array([0.03, 0.1, 0.02])
+    def table_calls(o, fmin, M):   # what Handle and Group share
+        keep("acq_argbest", lambda: o.acq_argbest(EI, 0.01, fmin, -1))
+        keep("acq_topk", lambda: o.acq_topk(LCB, 2.0, fmin, +1, 5))
+        keep("acq_lp_argbest", lambda: o.acq_lp_argbest(EI, 0.01, fmin, 1, -1, Xb, r0, s0, exclude=range(0, 2 * min(256, M // 2), 2)))
+    if case == "s1":
+        setup(300, 1001); h.fit(); fmin = keep("fmin", h.fmin)
+        keep("acq", lambda: h.acq(EI, 0.01, fmin)); keep("acq_grad", lambda: h.acq_grad(LCB, 2.0, fmin))
+        table_calls(h, fmin, 1001)
+        keep("acq_lp", lambda: h.acq_lp(EI, 0.01, fmin, 1, Xb, r0, s0)); keep("acq_lp0", lambda: h.acq_lp(EI, 0.01, fmin, 0))
+        keep("acq_lp_grad", lambda: h.acq_lp_grad(EI, 0.01, fmin, 1, Xb, r0, s0))
+    elif case in ("s2", "s3"):   # s3: N = 4500, where the first *_rows calls after a fit take the batched entry points
+        setup(300 if case == "s2" else 4500, 9); h.fit(); fmin = h.fmin(); Xs = problem(300, 9)[2]
+        for n, M in enumerate((1, 4, 5, 9) if case == "s2" else (1, 1, 1, 5, 1, 1, 1, 1)):
+            for grad in (False, True):
+                keep("%d.predict_rows%d%d" % (n, M, grad), lambda: h.predict_rows(Xs[:M], True, grad))
+                for lp in (None, (1, Xb, r0, s0), (0, None, None, None)):
+                    keep("%d.acq_rows%d%d%s" % (n, M, grad, lp and lp[0]), lambda: h.acq_rows(Xs[:M], EI, 0.01, fmin, grad=grad, lp=lp))
+            keep("%d.mean_grad_rows%d" % (n, M), lambda: h.mean_grad_rows(Xs[:M]))
+        got["rows_stats"] = np.array(sorted(h.rows_stats().items()), dtype=object)[:, 1].astype(np.int64)
+    elif case in ("s4a", "s4b"):
+        X, Y, Xs = problem(300, 1001)
+        grp = _lib.Group((0, 0) if case == "s4a" else (0,))
+        grp.set_option("emulate_fp64", 0); grp.set_data(X, Y); grp.set_params(0, 0, 1.2, [0.5], 1e-2)
+        got["fit"] = np.array(grp.fit()); fmin = grp.fmin()
+        for M in (1001, 3):
+            twice(lambda: grp.set_candidates(Xs[:M])); table_calls(grp, fmin, M)
+            got.update({k + "/%d" % M: got.pop(k) for k in list(got) if k.startswith("acq")})
+        grp.close()
+    elif case == "s5":
+        setup(300); h.comm_init(h.comm_unique_id(), 0, 1)
+        keep("allgather_best", lambda: h.comm_allgather_best(-0.25, 123456789012, 1))
+        keep("allgather_topk", lambda: h.comm_allgather_topk(np.arange(5) * 0.5, np.arange(5) + (1 << 40), 1))
+    else:
+        raise SystemExit("unknown case")
+    print(case, {k: float(np.sum(v)) for k, v in got.items()})
+    if len(sys.argv) > 2: np.savez(sys.argv[2], **got)
 else:
     raise SystemExit("unknown case")
 h.close()
