@@ -17,6 +17,7 @@ c_int64_p = ctypes.POINTER(ctypes.c_int64)
 c_int_p = ctypes.POINTER(ctypes.c_int)
 
 GP_KERNEL_RBF, GP_KERNEL_MATERN52 = 0, 1
+GP_KERNEL_MATERN32, GP_KERNEL_EXPONENTIAL = 2, 3
 GP_ACQ_EI, GP_ACQ_LCB, GP_ACQ_MPI = 0, 1, 2
 GP_ERR_ARG, GP_ERR_HIP, GP_ERR_STATE, GP_ERR_RCCL, GP_ERR_NOT_PD_DIAG = -1, -2, -3, -4, -5
 

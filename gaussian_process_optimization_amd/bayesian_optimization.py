@@ -259,6 +259,17 @@ class RandomBatch(SamplingBasedBatchEvaluator):
         return np.vstack([x] + [a for a, _ in zip(anchors, range(k))])
 
 
+KERNEL_NAMES = {'RBF': _kern.RBF, 'ExpQuad': _kern.ExpQuad, 'Matern52': _kern.Matern52, 'Matern32': _kern.Matern32,
+                'Exponential': _kern.Exponential, 'OU': _kern.OU}
+
+
+def kernel_from_name(name, input_dim, ARD=False):
+    """The kernel object behind ``BayesianOptimization(kernel='<name>')``."""
+    if name not in KERNEL_NAMES:
+        raise ValueError("unknown kernel %r: choose one of %s" % (name, ", ".join(sorted(KERNEL_NAMES))))
+    return KERNEL_NAMES[name](input_dim, ARD=ARD)
+
+
 class BayesianOptimization(object):
     """GPyOpt.methods.BayesianOptimization for model_type='GP' (bayesian_optimization.py:76-170)."""
 
@@ -283,8 +294,7 @@ class BayesianOptimization(object):
         # arguments_manager.py:78-147
         kernel = kwargs.get('kernel', None)
         if isinstance(kernel, str):
-            kernel = {'RBF': _kern.RBF, 'Matern52': _kern.Matern52}[kernel](self.space.dimensionality,
-                                                                            ARD=kwargs.get('ARD', False))
+            kernel = kernel_from_name(kernel, self.space.dimensionality, ARD=kwargs.get('ARD', False))
         self.model = model if model is not None else GPModel(
             kernel=kernel, noise_var=kwargs.get('noise_var', None), exact_feval=exact_feval,
             optimizer=kwargs.get('model_optimizer_type', 'lbfgs'), max_iters=kwargs.get('max_iters', 1000),

@@ -531,11 +531,16 @@ extern "C" int gp_set_data(gp_t *g, const double *X, const double *Y, int64_t N,
 // formulas stay Euclidean in the fork.  Both are reproduced for the predictive gradients (gp_predict_grad, gp_acq_grad,
 // gp_acq_lp_grad: Gower K(Xs, X) inside Euclidean gradients_X, see run_predict_grad) and for the hyper-parameter gradients
 // (gp_lml_grad: Gower K in the variance gradient, Euclidean dK/dr in the lengthscale gradients, stationary.py:218-238).
+static bool gower_refused(int kernel) { return kernel == GP_KERNEL_MATERN32 || kernel == GP_KERNEL_EXPONENTIAL; }
+
 extern "C" int gp_set_gower(gp_t *g, int enable, const int *is_discrete, const double *range) {
     if (!g) return fail(GP_ERR_ARG, "null gp");
     GP_DEAD_CHECK(g);
     if (!g->have_data) return fail(GP_ERR_STATE, "gp_set_data first");
     if (enable && (!is_discrete || !range)) return fail(GP_ERR_ARG, "null argument");
+    if (enable && g->have_params && gower_refused(g->kp.kernel))
+        return fail(GP_ERR_ARG, "gp_set_gower: the Gower option covers GP_KERNEL_RBF and GP_KERNEL_MATERN52 only; gp_set_params chose kernel %d",
+                    g->kp.kernel);
     g->kp.gower = enable ? 1 : 0;
     for (int d = 0; d < g->D && enable; ++d) {
         g->kp.gdisc[d] = is_discrete[d] ? 1 : 0;
@@ -550,7 +555,10 @@ extern "C" int gp_set_params(gp_t *g, int kernel, int ard, double variance, cons
     if (!g || !lengthscale) return fail(GP_ERR_ARG, "null argument");
     GP_DEAD_CHECK(g);
     if (!g->have_data) return fail(GP_ERR_STATE, "gp_set_data must precede gp_set_params");
-    if (kernel != GP_KERNEL_RBF && kernel != GP_KERNEL_MATERN52) return fail(GP_ERR_ARG, "unknown kernel %d", kernel);
+    if (kernel < GP_KERNEL_RBF || kernel > GP_KERNEL_EXPONENTIAL) return fail(GP_ERR_ARG, "unknown kernel %d", kernel);
+    if (g->kp.gower && gower_refused(kernel))
+        return fail(GP_ERR_ARG, "gp_set_params: kernel %d cannot follow gp_set_gower(enable): the Gower option covers GP_KERNEL_RBF and GP_KERNEL_MATERN52 only",
+                    kernel);
     g->kp.kernel = kernel;
     g->kp.D = g->D;
     g->kp.variance = variance;

@@ -66,25 +66,69 @@ __device__ __forceinline__ double gp_exp_nonpos(double x) {
     return ldexp(p, (int)n);
 }
 
-// the stationary covariance as a function of r^2, and with it g(r) = dK_dr(r) / r (finite at r = 0 for both kernels):
-// RBF.K_of_r / dK_dr (rbf.py:50-54), Matern52.K_of_r / dK_dr (stationary.py:575-579)
-__device__ __forceinline__ double gp_k_of_r2(int kernel, double variance, double r2) {
-    if (kernel == 0) return variance * gp_exp_nonpos(-0.5 * r2);
-    const double s5 = 2.23606797749978969640917366873128;  // sqrt(5)
+// the stationary covariance as a function of r^2, and with it g(r) = dK_dr(r) / r:
+// RBF.K_of_r / dK_dr (rbf.py:50-54), Matern52.K_of_r / dK_dr (stationary.py:575-579), Matern32.K_of_r / dK_dr
+// (stationary.py:478-482), Exponential.K_of_r / dK_dr (stationary.py:388-392).  The family is uniform across a launch, so
+// the branches are scalar; the RBF and Matern-5/2 branches are the expressions they were before the other two came.
+// g is finite at r = 0 for the first three.  The Exponential's dK_dr / r = -K / r is singular there, and the reference never
+// divides by that zero: _inv_dist (stationary.py:251-258) is 0 where the distance is 0, so a coincident pair adds exactly 0
+// to gradients_X and to the lengthscale gradients.  Hence g = 0 where r2 == 0, selected before the division (the divisor is
+// never 0).  Away from 0 |g| is not bounded by |K| (it grows as 1 / r): every call site multiplies g by a scaled difference
+// or by r^2, which brings the product back to O(K).
+//
+// The four families come in two pairs, GP_FAMILY_PAIR(kernel) = 0 (RBF, Matern-5/2) or 1 (Matern-3/2, Exponential).  The K-build
+// tile kernels (kbuild.hip) and the LML-gradient tile kernels (grad.hip) take the pair as a template parameter chosen on the
+// host: with all four families inlined kbuild_batch_kernel<8> and lml_grad_tile_kernel each lost one occupancy step
+// (profiles/kernel_families_resources.txt), and pair 0 of the split compiles to the code it was before.  Every other caller
+// keeps the run-time choice among the four.
+#define GP_FAMILY_PAIR(kernel) ((kernel) >= 2 ? 1 : 0)
+template <int PAIR>
+__device__ __forceinline__ double gp_k_of_r2_pair(int kernel, double variance, double r2) {
+    if (PAIR == 0) {
+        if (kernel == 0) return variance * gp_exp_nonpos(-0.5 * r2);
+        const double s5 = 2.23606797749978969640917366873128;  // sqrt(5)
+        const double r = sqrt(r2);
+        return variance * (1.0 + s5 * r + (5.0 / 3.0) * r2) * gp_exp_nonpos(-s5 * r);
+    }
     const double r = sqrt(r2);
-    return variance * (1.0 + s5 * r + (5.0 / 3.0) * r2) * gp_exp_nonpos(-s5 * r);
+    if (kernel == 2) {
+        const double s3 = 1.73205080756887729352744634150587;  // sqrt(3)
+        return variance * (1.0 + s3 * r) * gp_exp_nonpos(-s3 * r);
+    }
+    return variance * gp_exp_nonpos(-r);
+}
+__device__ __forceinline__ double gp_k_of_r2(int kernel, double variance, double r2) {
+    return GP_FAMILY_PAIR(kernel) ? gp_k_of_r2_pair<1>(kernel, variance, r2) : gp_k_of_r2_pair<0>(kernel, variance, r2);
+}
+template <int PAIR>
+__device__ __forceinline__ void gp_k_and_g_pair(int kernel, double variance, double r2, double &k, double &g) {
+    if (PAIR == 0) {
+        if (kernel == 0) {
+            k = variance * gp_exp_nonpos(-0.5 * r2);
+            g = -k;  // dK_dr = -r k
+        } else {
+            const double s5 = 2.23606797749978969640917366873128;
+            const double r = sqrt(r2);
+            const double e = gp_exp_nonpos(-s5 * r);
+            k = variance * (1.0 + s5 * r + (5.0 / 3.0) * r2) * e;
+            g = -(5.0 / 3.0) * variance * (1.0 + s5 * r) * e;  // (10/3 r - 5 r - 5 sqrt5/3 r^2) e / r
+        }
+    } else if (kernel == 2) {
+        const double s3 = 1.73205080756887729352744634150587;
+        const double r = sqrt(r2);
+        const double e = gp_exp_nonpos(-s3 * r);
+        k = variance * (1.0 + s3 * r) * e;
+        g = -3.0 * variance * e;  // dK_dr = -3 variance r e
+    } else {
+        const double r = sqrt(r2);
+        k = variance * gp_exp_nonpos(-r);
+        const bool zero = (r2 == 0.0);
+        g = zero ? 0.0 : -k / (zero ? 1.0 : r);  // dK_dr = -k; the divisor is never 0
+    }
 }
 __device__ __forceinline__ void gp_k_and_g(int kernel, double variance, double r2, double &k, double &g) {
-    if (kernel == 0) {
-        k = variance * gp_exp_nonpos(-0.5 * r2);
-        g = -k;  // dK_dr = -r k
-    } else {
-        const double s5 = 2.23606797749978969640917366873128;
-        const double r = sqrt(r2);
-        const double e = gp_exp_nonpos(-s5 * r);
-        k = variance * (1.0 + s5 * r + (5.0 / 3.0) * r2) * e;
-        g = -(5.0 / 3.0) * variance * (1.0 + s5 * r) * e;  // (10/3 r - 5 r - 5 sqrt5/3 r^2) e / r
-    }
+    if (GP_FAMILY_PAIR(kernel)) gp_k_and_g_pair<1>(kernel, variance, r2, k, g);
+    else gp_k_and_g_pair<0>(kernel, variance, r2, k, g);
 }
 
 // divisor used when staging inputs for a covariance evaluation

@@ -99,6 +99,8 @@ void launch_symmetrize(hipStream_t s, double *A, long ld, long n, int nb, long s
 // ---- LML hyper-gradients: one pass over the lower tiles ------------------------------------------
 #define NACC (GCH + 2)
 // partial[tile][NACC]: [0] sum K dL_dK (w), [1] sum diag dL_dK, [2+q] sum w g dL_dK dq^2 (ARD) or [2] sum w g dL_dK r^2 (iso)
+// FP: the family pair GP_FAMILY_PAIR(kp.kernel), chosen on the host (gphip_internal.h)
+template <int FP>
 __device__ __forceinline__ void lml_grad_tile_body(const double *X, long N, const KernParams &kp, int ard, int d0, const double *alpha,
                                                    long lda_, int P, const double *Wi, long ldw, double *partial) {
     extern __shared__ __attribute__((aligned(16))) double sm[];
@@ -174,14 +176,14 @@ __device__ __forceinline__ void lml_grad_tile_body(const double *X, long N, cons
             for (int p = 0; p < P; ++p) aa = fma(ai[p * GP_TILE + r], aj[p * GP_TILE + c], aa);
             const double dLdK = 0.5 * (aa - (double)P * w2[e]);  // exact_gaussian_inference.py:70
             double kv, gv;
-            k_and_g(kp.kernel, kp.variance, s, kv, gv);
+            gp_k_and_g_pair<FP>(kp.kernel, kp.variance, s, kv, gv);
             const bool diag = (gcc == gr);
             if (kp.gower) {              // product of the 1-D factors, diagonal included (variance^D there, as the fork's K has it)
                 kv = 1.0;
                 for (int d = 0; d < D; ++d) {
                     const double df = ui[d * GP_TILE + r] - uj[d * GP_TILE + c];
                     const double rr = kp.gdisc[d] ? (df != 0.0 ? 1.0 : 0.0) : fabs(df);
-                    kv *= gp_k_of_r2(kp.kernel, kp.variance, rr * rr);
+                    kv *= gp_k_of_r2_pair<FP>(kp.kernel, kp.variance, rr * rr);
                 }
             } else if (diag) {
                 kv = kp.variance;  // Kdiag is exactly the variance (stationary.py:162-166, r = 0)
@@ -209,17 +211,19 @@ __device__ __forceinline__ void lml_grad_tile_body(const double *X, long N, cons
     if (tid < NACC) partial[(t * gridDim.y + blockIdx.y) * NACC + tid] = ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid];
 }
 
+template <int FP>
 __global__ __launch_bounds__(256) void lml_grad_tile_kernel(const double *X, long N, KernParams kp, int ard, int d0,
                                                             const double *alpha, long lda_, int P, const double *Wi,
                                                             long ldw, double *partial) {
-    lml_grad_tile_body(X, N, kp, ard, d0, alpha, lda_, P, Wi, ldw, partial);
+    lml_grad_tile_body<FP>(X, N, kp, ard, d0, alpha, lda_, P, Wi, ldw, partial);
 }
 // member z = blockIdx.z of gp_fit_grad_batch: parameters kpt[z], alpha + z sV, Ky^-1 at Wi + z sW, partials at partial + z sP
+template <int FP>
 __global__ __launch_bounds__(256) void lml_grad_tile_batch_kernel(const double *X, long N, const KernParams *kpt, int ard, int d0,
                                                                   const double *alpha, long sV, long lda_, int P, const double *Wi,
                                                                   long sW, long ldw, double *partial, long sP) {
     const long z = blockIdx.z;
-    lml_grad_tile_body(X, N, kpt[z], ard, d0, alpha + z * sV, lda_, P, Wi + z * sW, ldw, partial + z * sP);
+    lml_grad_tile_body<FP>(X, N, kpt[z], ard, d0, alpha + z * sV, lda_, P, Wi + z * sW, ldw, partial + z * sP);
 }
 
 __device__ __forceinline__ void sum_partials_body(const double *partial, long ntile, int nacc, double *out) {
@@ -258,15 +262,24 @@ void launch_lml_grad(hipStream_t s, const double *X, long N, long Npad, const Ke
     // few tiles (N <= ~2900): four workgroups per tile, 32 rows each -- 6 workgroups of 128 x 128 covariance evaluations were a
     // quarter of an LML + gradient evaluation at N = 300; the partial sums are added per (tile, quarter) in the same fixed order
     const unsigned split = ntile < 256 ? 4u : 1u;
+    const int fp = GP_FAMILY_PAIR(kp.kernel);
     if (nb > 1) {
-        GP_LAUNCH(lml_grad_tile_batch_kernel, dim3((unsigned)ntile, split, (unsigned)nb), dim3(256), shm, s, X, N, kpt, ard, d0,
-                  alpha, sV, Npad, P, Wi, sW, ldw, partial, sP);
+        if (fp)
+            GP_LAUNCH(lml_grad_tile_batch_kernel<1>, dim3((unsigned)ntile, split, (unsigned)nb), dim3(256), shm, s, X, N, kpt, ard,
+                      d0, alpha, sV, Npad, P, Wi, sW, ldw, partial, sP);
+        else
+            GP_LAUNCH(lml_grad_tile_batch_kernel<0>, dim3((unsigned)ntile, split, (unsigned)nb), dim3(256), shm, s, X, N, kpt, ard,
+                      d0, alpha, sV, Npad, P, Wi, sW, ldw, partial, sP);
         GP_LAUNCH(sum_partials_batch_kernel, dim3(NACC, 1, (unsigned)nb), dim3(1024), 0, s, partial, sP, ntile * split, NACC, out,
                   so);
         return;
     }
-    GP_LAUNCH(lml_grad_tile_kernel, dim3((unsigned)ntile, split), dim3(256), shm, s, X, N, kp, ard, d0, alpha, Npad, P, Wi, ldw,
-              partial);
+    if (fp)
+        GP_LAUNCH(lml_grad_tile_kernel<1>, dim3((unsigned)ntile, split), dim3(256), shm, s, X, N, kp, ard, d0, alpha, Npad, P, Wi,
+                  ldw, partial);
+    else
+        GP_LAUNCH(lml_grad_tile_kernel<0>, dim3((unsigned)ntile, split), dim3(256), shm, s, X, N, kp, ard, d0, alpha, Npad, P, Wi,
+                  ldw, partial);
     GP_LAUNCH(sum_partials_kernel, dim3(NACC), dim3(1024), 0, s, partial, ntile * split, NACC, out);
 }
 

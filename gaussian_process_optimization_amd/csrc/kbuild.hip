@@ -16,11 +16,16 @@
 #include "gphip_internal.h"
 
 #define k_of_r2 gp_k_of_r2   // gphip_internal.h
+// FP (template parameter of the tile kernels): the family pair GP_FAMILY_PAIR(kp.kernel), chosen on the host (gphip_internal.h)
 // one 1-D factor of the Gower product kernel: K_of_r(|dx|) for a continuous dimension (dx already divided by
 // the variable's range), K_of_r(dx != 0) for a discrete one (stationary.py:122-129)
-__device__ __forceinline__ double gower_factor(int kernel, double variance, double dx, int disc) {
+template <int FP>
+__device__ __forceinline__ double gower_factor_pair(int kernel, double variance, double dx, int disc) {
     const double r = disc ? (dx != 0.0 ? 1.0 : 0.0) : fabs(dx);
-    return k_of_r2(kernel, variance, r * r);
+    return gp_k_of_r2_pair<FP>(kernel, variance, r * r);
+}
+__device__ __forceinline__ double gower_factor(int kernel, double variance, double dx, int disc) {
+    return gower_factor_pair<0>(kernel, variance, dx, disc);   // (the Gower option is refused for pair 1: gp_set_params)
 }
 
 // Stage rows [row0, row0+128) of X (N x D row-major) divided by the lengthscale (stationary.py:188-191) into LDS transposed: dst[d*128 + r].
@@ -36,7 +41,7 @@ __device__ __forceinline__ void stage_rows_T(double *dst, const double *X, long 
 // DU > 0: the dimension loop unrolled to DU (LDS rows D .. DU-1 are staged as zeros), the thread's two columns held in registers
 // across its 32 rows; DU = 0: run-time loop (D > 16, and the Gower product kernel).
 // grid: lower tiles enumerated row-wise (tm >= tn): t = tm(tm+1)/2 + tn
-template <int DU>
+template <int DU, int FP>
 __device__ __forceinline__ void kbuild_body(double *A, long lda, const double *X, long N, long Npad, const KernParams &kp,
                                             double diag_add, int full, int nt) {
     extern __shared__ __attribute__((aligned(16))) double sm[];
@@ -81,8 +86,8 @@ __device__ __forceinline__ void kbuild_body(double *A, long lda, const double *X
             for (int d = 0; d < kp.D; ++d) {
                 const double a = xi[d * GP_TILE + r];
                 const double2_t b = *(const double2_t *)(xj + d * GP_TILE + cx);
-                p0 *= gower_factor(kp.kernel, kp.variance, a - b[0], kp.gdisc[d]);
-                p1 *= gower_factor(kp.kernel, kp.variance, a - b[1], kp.gdisc[d]);
+                p0 *= gower_factor_pair<FP>(kp.kernel, kp.variance, a - b[0], kp.gdisc[d]);
+                p1 *= gower_factor_pair<FP>(kp.kernel, kp.variance, a - b[1], kp.gdisc[d]);
             }
             out[0] = p0;
             out[1] = p1;
@@ -105,8 +110,8 @@ __device__ __forceinline__ void kbuild_body(double *A, long lda, const double *X
                     s1 = fma(d1, d1, s1);
                 }
             }
-            out[0] = k_of_r2(kp.kernel, kp.variance, s0);
-            out[1] = k_of_r2(kp.kernel, kp.variance, s1);
+            out[0] = gp_k_of_r2_pair<FP>(kp.kernel, kp.variance, s0);
+            out[1] = gp_k_of_r2_pair<FP>(kp.kernel, kp.variance, s1);
         }
         // diagonal and padding
         if (gr >= N) {
@@ -124,21 +129,27 @@ __device__ __forceinline__ void kbuild_body(double *A, long lda, const double *X
     }
 }
 
-template <int DU>
+template <int DU, int FP>
 __global__ __launch_bounds__(256) void kbuild_kernel(double *A, long lda, const double *X, long N, long Npad,
                                                      KernParams kp, double diag_add, int full, int nt) {
-    kbuild_body<DU>(A, lda, X, N, Npad, kp, diag_add, full, nt);
+    kbuild_body<DU, FP>(A, lda, X, N, Npad, kp, diag_add, full, nt);
 }
 // member z = blockIdx.z of a batch (gp_fit_grad_batch): its own matrix at A + z sA, parameters kpt[z], diagonal term diag_add[z]
-template <int DU>
+template <int DU, int FP>
 __global__ __launch_bounds__(256) void kbuild_batch_kernel(double *A, long lda, long sA, const double *X, long N, long Npad,
                                                            const KernParams *kpt, const double *diag_add, int nt) {
     const long z = blockIdx.z;
-    kbuild_body<DU>(A + z * sA, lda, X, N, Npad, kpt[z], diag_add[z], 0, nt);
+    kbuild_body<DU, FP>(A + z * sA, lda, X, N, Npad, kpt[z], diag_add[z], 0, nt);
 }
 
-static void launch_kbuild_members(hipStream_t s, double *A, long lda, long sA, const double *X, long N, long Npad, int DU, size_t shm,
-                                  const KernParams *kpt, const double *diag_tab, int nb);
+static void launch_kbuild_members(hipStream_t s, double *A, long lda, long sA, const double *X, long N, long Npad, int DU, int fp,
+                                  size_t shm, const KernParams *kpt, const double *diag_tab, int nb);
+// the <DU, pair> instance of a tile kernel for the run-time pair fp
+#define KB_LAUNCH_PAIR(kernel, DU, fp, ...)                       \
+    do {                                                          \
+        if (fp) GP_LAUNCH((kernel<DU, 1>), __VA_ARGS__);          \
+        else GP_LAUNCH((kernel<DU, 0>), __VA_ARGS__);             \
+    } while (0)
 
 // nb > 1: the lower tiles of nb members' matrices in one launch; kernel, D and the Gower setting -- what picks the instance and
 // the LDS size -- are the same for every member, so kp (the first member's) chooses for all
@@ -148,13 +159,14 @@ void launch_kbuild(hipStream_t s, double *A, long lda, const double *X, long N, 
     const long nblk = full ? (long)nt * nt : (long)nt * (nt + 1) / 2;
     const int DU = kp.gower ? 0 : (kp.D <= 8 ? 8 : (kp.D <= 16 ? 16 : 0));
     const size_t shm = (size_t)2 * (DU ? DU : kp.D) * GP_TILE * sizeof(double);
-    if (nb > 1) return launch_kbuild_members(s, A, lda, sA, X, N, Npad, DU, shm, kpt, diag_tab, nb);
+    const int fp = GP_FAMILY_PAIR(kp.kernel);
+    if (nb > 1) return launch_kbuild_members(s, A, lda, sA, X, N, Npad, DU, fp, shm, kpt, diag_tab, nb);
     if (DU == 8)
-        GP_LAUNCH(kbuild_kernel<8>, dim3((unsigned)nblk), dim3(256), shm, s, A, lda, X, N, Npad, kp, diag_add, full, nt);
+        KB_LAUNCH_PAIR(kbuild_kernel, 8, fp, dim3((unsigned)nblk), dim3(256), shm, s, A, lda, X, N, Npad, kp, diag_add, full, nt);
     else if (DU == 16)
-        GP_LAUNCH(kbuild_kernel<16>, dim3((unsigned)nblk), dim3(256), shm, s, A, lda, X, N, Npad, kp, diag_add, full, nt);
+        KB_LAUNCH_PAIR(kbuild_kernel, 16, fp, dim3((unsigned)nblk), dim3(256), shm, s, A, lda, X, N, Npad, kp, diag_add, full, nt);
     else
-        GP_LAUNCH(kbuild_kernel<0>, dim3((unsigned)nblk), dim3(256), shm, s, A, lda, X, N, Npad, kp, diag_add, full, nt);
+        KB_LAUNCH_PAIR(kbuild_kernel, 0, fp, dim3((unsigned)nblk), dim3(256), shm, s, A, lda, X, N, Npad, kp, diag_add, full, nt);
 }
 
 __device__ __forceinline__ void set_rhs_body(double *A, long lda, const double *Y, long N, long Npad, int P) {
@@ -181,7 +193,7 @@ void launch_set_rhs(hipStream_t s, double *A, long lda, const double *Y, long N,
 }
 
 // T[c][i] = k(xs_c, x_i); tiles (tc over candidates, ti over training points)
-template <int DU>
+template <int DU, int FP>
 __global__ __launch_bounds__(256) void cross_k_kernel(double *T, long ldt, const double *Xs, long M, const double *X,
                                                       long N, KernParams kp, int nti) {
     extern __shared__ __attribute__((aligned(16))) double sm[];
@@ -216,8 +228,8 @@ __global__ __launch_bounds__(256) void cross_k_kernel(double *T, long ldt, const
             for (int d = 0; d < kp.D; ++d) {
                 const double a = xc[d * GP_TILE + r];
                 const double2_t b = *(const double2_t *)(xt + d * GP_TILE + cx);
-                k0 *= gower_factor(kp.kernel, kp.variance, a - b[0], kp.gdisc[d]);
-                k1 *= gower_factor(kp.kernel, kp.variance, a - b[1], kp.gdisc[d]);
+                k0 *= gower_factor_pair<FP>(kp.kernel, kp.variance, a - b[0], kp.gdisc[d]);
+                k1 *= gower_factor_pair<FP>(kp.kernel, kp.variance, a - b[1], kp.gdisc[d]);
             }
         } else {
             double s0 = 0.0, s1 = 0.0;
@@ -238,8 +250,8 @@ __global__ __launch_bounds__(256) void cross_k_kernel(double *T, long ldt, const
                     s1 = fma(d1, d1, s1);
                 }
             }
-            k0 = k_of_r2(kp.kernel, kp.variance, s0);
-            k1 = k_of_r2(kp.kernel, kp.variance, s1);
+            k0 = gp_k_of_r2_pair<FP>(kp.kernel, kp.variance, s0);
+            k1 = gp_k_of_r2_pair<FP>(kp.kernel, kp.variance, s1);
         }
         double2_t out;
         out[0] = (gcand < M && gi < N) ? k0 : 0.0;
@@ -254,12 +266,13 @@ void launch_cross_k(hipStream_t s, double *T, long ldt, const double *Xs, long M
     const int DU = kp.gower ? 0 : (kp.D <= 8 ? 8 : (kp.D <= 16 ? 16 : 0));
     const size_t shm = (size_t)2 * (DU ? DU : kp.D) * GP_TILE * sizeof(double);
     const dim3 grid((unsigned)((long)ntc * nti));
+    const int fp = GP_FAMILY_PAIR(kp.kernel);
     if (DU == 8)
-        GP_LAUNCH(cross_k_kernel<8>, grid, dim3(256), shm, s, T, ldt, Xs, M, X, N, kp, nti);
+        KB_LAUNCH_PAIR(cross_k_kernel, 8, fp, grid, dim3(256), shm, s, T, ldt, Xs, M, X, N, kp, nti);
     else if (DU == 16)
-        GP_LAUNCH(cross_k_kernel<16>, grid, dim3(256), shm, s, T, ldt, Xs, M, X, N, kp, nti);
+        KB_LAUNCH_PAIR(cross_k_kernel, 16, fp, grid, dim3(256), shm, s, T, ldt, Xs, M, X, N, kp, nti);
     else
-        GP_LAUNCH(cross_k_kernel<0>, grid, dim3(256), shm, s, T, ldt, Xs, M, X, N, kp, nti);
+        KB_LAUNCH_PAIR(cross_k_kernel, 0, fp, grid, dim3(256), shm, s, T, ldt, Xs, M, X, N, kp, nti);
 }
 
 // ---- K(Xs, X) for a handful of candidate rows (the small-M path, smallm.hip): one training point per thread, every candidate ----
@@ -304,14 +317,14 @@ void launch_cross_k_rows(hipStream_t s, double *T, long ldt, const double *Xs, i
 }
 
 // (defined last: the batch instances stay behind every other kernel of this file in the code object)
-static void launch_kbuild_members(hipStream_t s, double *A, long lda, long sA, const double *X, long N, long Npad, int DU, size_t shm,
-                                  const KernParams *kpt, const double *diag_tab, int nb) {
+static void launch_kbuild_members(hipStream_t s, double *A, long lda, long sA, const double *X, long N, long Npad, int DU, int fp,
+                                  size_t shm, const KernParams *kpt, const double *diag_tab, int nb) {
     const int nt = (int)(Npad / GP_TILE);
     const dim3 grid((unsigned)((long)nt * (nt + 1) / 2), 1, (unsigned)nb);   // (lower tiles only)
     if (DU == 8)
-        GP_LAUNCH(kbuild_batch_kernel<8>, grid, dim3(256), shm, s, A, lda, sA, X, N, Npad, kpt, diag_tab, nt);
+        KB_LAUNCH_PAIR(kbuild_batch_kernel, 8, fp, grid, dim3(256), shm, s, A, lda, sA, X, N, Npad, kpt, diag_tab, nt);
     else if (DU == 16)
-        GP_LAUNCH(kbuild_batch_kernel<16>, grid, dim3(256), shm, s, A, lda, sA, X, N, Npad, kpt, diag_tab, nt);
+        KB_LAUNCH_PAIR(kbuild_batch_kernel, 16, fp, grid, dim3(256), shm, s, A, lda, sA, X, N, Npad, kpt, diag_tab, nt);
     else
-        GP_LAUNCH(kbuild_batch_kernel<0>, grid, dim3(256), shm, s, A, lda, sA, X, N, Npad, kpt, diag_tab, nt);
+        KB_LAUNCH_PAIR(kbuild_batch_kernel, 0, fp, grid, dim3(256), shm, s, A, lda, sA, X, N, Npad, kpt, diag_tab, nt);
 }

@@ -83,12 +83,23 @@ class _PosteriorView(object):
         return self._m._h.woodbury_inv()
 
 
+def _set_params_and_gower(h, k, noise, gower):
+    """Hyper-parameters and the Gower set-up of kernel ``k`` on a handle or group.  The device refuses Matern32 / Exponential while
+    Gower is on, whichever call comes second, so a Gower set-up left by an earlier kernel is switched off BEFORE the parameters
+    go in, and a new one is switched on AFTER them."""
+    if gower is None:
+        h.set_gower()
+    h.set_params(k._kernel_id, k.ARD, float(k.variance), k.lengthscale.values, noise)
+    if gower is not None:
+        h.set_gower(*gower)
+
+
 class GPRegression(Parameterized):
     """Gaussian Process model for regression with a Gaussian likelihood, on one MI355X.
 
     :param X: input observations [N, D]
     :param Y: observed values [N, P]
-    :param kernel: ``kern.RBF`` / ``kern.Matern52`` (defaults to RBF, gp_regression.py:31-32)
+    :param kernel: ``kern.RBF`` / ``ExpQuad`` / ``Matern52`` / ``Matern32`` / ``Exponential`` / ``OU`` (defaults to RBF, gp_regression.py:31-32)
     :param normalizer: ``True`` standardises Y (gp.py:73-84)
     :param noise_var: Gaussian noise variance (default 1)
     :param device: HIP device ordinal
@@ -103,7 +114,7 @@ class GPRegression(Parameterized):
         if kernel is None:
             kernel = RBF(X.shape[1])
         if not isinstance(kernel, Stationary):
-            raise TypeError("kernel must be kern.RBF or kern.Matern52")
+            raise TypeError("kernel must be one of the kern.Stationary classes (RBF, ExpQuad, Matern52, Matern32, Exponential, OU)")
         self.kern = kernel
         self.kern._device = int(device)     # kern.K evaluates on the owning model's device (kern.py, _scratch_handle)
         self.likelihood = Gaussian(variance=noise_var)
@@ -177,12 +188,8 @@ class GPRegression(Parameterized):
 
     def _push_params(self):
         k = self.kern
-        self._h.set_params(k._kernel_id, k.ARD, float(k.variance), k.lengthscale.values,
-                           float(self.likelihood.variance))
-        if k.Gower and k.space is not None:
-            self._h.set_gower(*gower_config(k.space, k.input_dim))
-        else:
-            self._h.set_gower()
+        gower = gower_config(k.space, k.input_dim) if (k.Gower and k.space is not None) else None
+        _set_params_and_gower(self._h, k, float(self.likelihood.variance), gower)
 
     def _device_group(self, devices):
         """The model replicated on ``devices`` (HIP ordinals; one may repeat) for scoring ONE candidate table on all of them
@@ -202,11 +209,7 @@ class GPRegression(Parameterized):
             if grp._data_epoch != self._data_epoch:
                 grp.set_data(self.X, self.Y_normalized)
                 grp._data_epoch = self._data_epoch
-            grp.set_params(k._kernel_id, k.ARD, float(k.variance), k.lengthscale.values, float(self.likelihood.variance))
-            if gower is None:
-                grp.set_gower()
-            else:
-                grp.set_gower(*gower)
+            _set_params_and_gower(grp, k, float(self.likelihood.variance), gower)
             grp.fit(self.max_jitter_tries)
             grp._signature = signature
         return grp

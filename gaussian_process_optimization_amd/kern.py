@@ -1,7 +1,10 @@
-"""Host-side kernel descriptors mirroring ``GPy.kern.RBF`` / ``GPy.kern.Matern52``.
+"""Host-side kernel descriptors mirroring ``GPy.kern.RBF`` (alias ``ExpQuad``), ``Matern52``, ``Matern32``
+and ``Exponential`` (twin ``OU``).
 
 Reference: GPy/GPy/kern/src/stationary.py:23-82 (Stationary.__init__: variance,
-lengthscale, ARD), rbf.py:12-57 (RBF), stationary.py:546-579 (Matern52).  These
+lengthscale, ARD), rbf.py:12-57 (RBF), stationary.py:546-579 (Matern52), :447-482
+(Matern32), :384-392 (Exponential), :427-444 (OU).  The fork's ``Gower=`` / ``space=``
+arguments exist on RBF and Matern52 only, as in the reference tree.  These
 objects only *hold* hyper-parameters; every covariance evaluation happens on
 the GPU inside libgphip (kbuild.hip).  ``K``/``Kdiag`` are provided for API
 parity and run through the device as well.
@@ -14,6 +17,7 @@ from .parameterization import Param, Parameterized
 
 class Stationary(Parameterized):
     _kernel_id = None
+    _takes_gower = True      # the constructor has the fork's Gower= / space= arguments (RBF, Matern52)
 
     def __init__(self, input_dim, variance=1., lengthscale=None, ARD=False, active_dims=None, name="stationary",
                  Gower=False, space=None):
@@ -54,11 +58,14 @@ class Stationary(Parameterized):
         h = _scratch_handle(int(getattr(self, "_device", 0)))
         X = _lib.as_f64(X, 2)
         h.set_data(X, np.zeros((X.shape[0], 1)))
-        h.set_params(self._kernel_id, self.ARD, float(self.variance), self.lengthscale.values, 0.0)
-        if self.Gower and self.space is not None:
-            h.set_gower(*gower_config(self.space, self.input_dim))
-        else:
+        # the scratch context is shared: a Gower set-up left by another kernel goes off BEFORE the parameters go in (the device
+        # refuses Matern32 / Exponential while it is on), a new one goes on AFTER them
+        gower = self.Gower and self.space is not None
+        if not gower:
             h.set_gower()
+        h.set_params(self._kernel_id, self.ARD, float(self.variance), self.lengthscale.values, 0.0)
+        if gower:
+            h.set_gower(*gower_config(self.space, self.input_dim))
         out = h.kernel_matrix() if X2 is None else h.cross_kernel_matrix(X2)
         if X.shape[0] > _SCRATCH_KEEP_N:      # an N x N device buffer of gigabytes is not kept alive behind the caller's back
             release_scratch(int(getattr(self, "_device", 0)))
@@ -70,8 +77,9 @@ class Stationary(Parameterized):
         return ret
 
     def copy(self):
-        return self.__class__(self.input_dim, float(self.variance), self.lengthscale.values.copy(), self.ARD,
-                              Gower=self.Gower, space=self.space)
+        extra = dict(Gower=self.Gower, space=self.space) if self._takes_gower else {}
+        return self.__class__(self.input_dim, float(self.variance), self.lengthscale.values.copy(), self.ARD, name=self.name,
+                              **extra)
 
 
 _SCRATCH = {}
@@ -126,3 +134,37 @@ class Matern52(Stationary):
     def __init__(self, input_dim, variance=1., lengthscale=None, ARD=False, active_dims=None, name="Mat52",
                  Gower=False, space=None):
         super(Matern52, self).__init__(input_dim, variance, lengthscale, ARD, active_dims, name, Gower, space)
+
+
+class ExpQuad(RBF):
+    """GPy.kern.ExpQuad -- the RBF covariance under its other name (the same device kernel)."""
+    _takes_gower = False
+
+    def __init__(self, input_dim, variance=1., lengthscale=None, ARD=False, active_dims=None, name="ExpQuad"):
+        super(ExpQuad, self).__init__(input_dim, variance, lengthscale, ARD, active_dims, name)
+
+
+class Matern32(Stationary):
+    """GPy.kern.Matern32 -- k(r) = variance (1 + sqrt3 r) exp(-sqrt3 r)  (stationary.py:478-479)."""
+    _kernel_id = _lib.GP_KERNEL_MATERN32
+    _takes_gower = False
+
+    def __init__(self, input_dim, variance=1., lengthscale=None, ARD=False, active_dims=None, name="Mat32"):
+        super(Matern32, self).__init__(input_dim, variance, lengthscale, ARD, active_dims, name)
+
+
+class Exponential(Stationary):
+    """GPy.kern.Exponential -- k(r) = variance exp(-r)  (stationary.py:388-389).  dK_dr / r is singular at r = 0; the device
+    follows the reference's _inv_dist (stationary.py:251-258): a coincident pair adds 0 to every gradient."""
+    _kernel_id = _lib.GP_KERNEL_EXPONENTIAL
+    _takes_gower = False
+
+    def __init__(self, input_dim, variance=1., lengthscale=None, ARD=False, active_dims=None, name="Exponential"):
+        super(Exponential, self).__init__(input_dim, variance, lengthscale, ARD, active_dims, name)
+
+
+class OU(Exponential):
+    """GPy.kern.OU -- the Ornstein-Uhlenbeck covariance, k(r) = variance exp(-r)  (stationary.py:427-444): Exponential's twin."""
+
+    def __init__(self, input_dim, variance=1., lengthscale=None, ARD=False, active_dims=None, name="OU"):
+        super(OU, self).__init__(input_dim, variance, lengthscale, ARD, active_dims, name)

@@ -28,9 +28,15 @@ extern "C" {
 
 typedef struct gp_ctx gp_t;
 
-/* kernel families: GPy/GPy/kern/src/rbf.py:12-57, stationary.py:546-579 */
+/* kernel families: GPy/GPy/kern/src/rbf.py:12-57 (RBF, alias ExpQuad), stationary.py:546-579 (Matern52),
+ * stationary.py:447-482 (Matern32), stationary.py:384-392 (Exponential; OU :427-444 is the same covariance).
+ * Out of scope: RatQuad (its `power` is a third hyper-parameter, which needs new outputs on gp_lml_grad, gp_fit_grad and
+ * gp_fit_grad_batch); Cosine, kernel sums and products, active_dims; the Gower option with Matern32 / Exponential (the
+ * fork gives Gower= / space= to RBF and Matern52 only). */
 #define GP_KERNEL_RBF 0
 #define GP_KERNEL_MATERN52 1
+#define GP_KERNEL_MATERN32 2
+#define GP_KERNEL_EXPONENTIAL 3
 
 /* acquisitions: GPyOpt/GPyOpt/acquisitions/{EI,LCB,MPI}.py */
 #define GP_ACQ_EI 0
@@ -70,6 +76,8 @@ int gp_set_data(gp_t *gp, const double *X, const double *Y, int64_t N, int D, in
 
 /* Kernel + Gaussian-noise hyper-parameters in natural space
  * (Stationary.__init__ stationary.py:61-82; Gaussian variance likelihoods/gaussian.py:43).
+ * kernel is one of GP_KERNEL_RBF, _MATERN52, _MATERN32, _EXPONENTIAL; any other id is GP_ERR_ARG, and so is _MATERN32 or
+ * _EXPONENTIAL while the Gower option is on (gp_set_gower refuses likewise when it comes second).
  * lengthscale has 1 entry (ard = 0) or D entries (ard = 1). */
 int gp_set_params(gp_t *gp, int kernel, int ard, double variance, const double *lengthscale, double noise);
 
