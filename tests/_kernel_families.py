@@ -1,4 +1,5 @@
-"""Oracle kernels for the Matern-3/2 and Exponential families, as subclasses of the oracle's ``Stationary`` (oracle/cpu_ref.py).
+"""Oracle kernels for the Matern-3/2 and Exponential families, as subclasses of the oracle's ``Stationary`` (oracle/cpu_ref.py),
+and direct-distance variants of all four families (``make(name, ...)`` takes "rbf" and "Mat52" as well: the oracle's own classes).
 
 Each family states only ``K_of_r`` and ``dK_dr`` (GPy/GPy/kern/src/stationary.py:478-482 for Matern32, :388-392 for
 Exponential); distances, ``K``, ``_inv_dist``, ``update_gradients_full`` and ``gradients_X`` are the oracle's, so ``OracleGP``,
@@ -7,7 +8,8 @@ Exponential); distances, ``K``, ``_inv_dist``, ``update_gradients_full`` and ``g
 The ``*Direct`` variants replace the Gram trick of ``_unscaled_dist`` (stationary.py:155-173) by direct differences summed in
 ``np.longdouble``.  The Gram trick carries ~1e-8 of absolute noise in r next to a coincident pair, and the Exponential
 covariance is not differentiable at r = 0: that noise is the oracle's error, not the device's.  They serve the K comparison at
-1e-13 (with ``extended=True`` the distance stays in long double, so K_of_r is evaluated there too) and the duplicated-rows case.
+1e-13 (with ``extended=True`` the distance stays in long double, so K_of_r is evaluated there too), the duplicated-rows case, and
+inputs far from the origin, where the Gram trick cancels |x / l|^2 ~ 1e6 against r^2 ~ 1 (tests/test_family_shapes_host.py).
 """
 import numpy as np
 
@@ -72,7 +74,16 @@ class ExponentialDirect(_DirectDistance, Exponential):
     pass
 
 
-FAMILIES = {"Mat32": (Matern32, Matern32Direct), "Exponential": (Exponential, ExponentialDirect)}
+class RBFDirect(_DirectDistance, O.RBF):
+    pass
+
+
+class Matern52Direct(_DirectDistance, O.Matern52):
+    pass
+
+
+FAMILIES = {"Mat32": (Matern32, Matern32Direct), "Exponential": (Exponential, ExponentialDirect),
+            "rbf": (O.RBF, RBFDirect), "Mat52": (O.Matern52, Matern52Direct)}
 
 
 def make(name, input_dim, variance, lengthscale, ARD, direct=False, extended=False):
