@@ -79,6 +79,7 @@ SIGNATURES = [
                                    ctypes.c_double, ctypes.c_double, ctypes.c_int, ctypes.c_int, _vp, ctypes.c_int,
                                    _vp, _vp, _vp, _vp]),
     ("gp_rows_stats", ctypes.c_int, [_vp, c_int64_p, c_int64_p]),
+    ("gp_rows_pass_stats", ctypes.c_int, [_vp, c_int64_p, c_int64_p]),
     ("gp_comm_unique_id", ctypes.c_int, [ctypes.c_char_p]),
     ("gp_comm_init", ctypes.c_int, [_vp, ctypes.c_char_p, ctypes.c_int, ctypes.c_int]),
     ("gp_comm_destroy", ctypes.c_int, [_vp]),
@@ -474,6 +475,12 @@ class Handle(object):
         a, b = ctypes.c_int64(), ctypes.c_int64()
         check(self.lib, self.lib.gp_rows_stats(self.h, ctypes.byref(a), ctypes.byref(b)), "gp_rows_stats")
         return dict(fused=a.value, fallback=b.value)
+
+    def rows_pass_stats(self):
+        """Passes of the fused path so far: of at most four locations (``narrow``) and of 5 .. 8 (``wide``)."""
+        a, b = ctypes.c_int64(), ctypes.c_int64()
+        check(self.lib, self.lib.gp_rows_pass_stats(self.h, ctypes.byref(a), ctypes.byref(b)), "gp_rows_pass_stats")
+        return dict(narrow=a.value, wide=b.value)
 
     def acq_lp(self, type_, par, fmin, transform, Xb=None, r_x0=None, s_x0=None, y_mean=0.0, y_std=1.0):
         keep, nb, pX, pr, ps = _lp_args(Xb, r_x0, s_x0)

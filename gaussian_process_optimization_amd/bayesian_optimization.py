@@ -21,6 +21,7 @@ from scipy import optimize as _sopt
 from . import kern as _kern
 from .acquisitions import AcquisitionEI, AcquisitionLCB, AcquisitionMPI, AcquisitionLP, LocalPenalization
 from .gpmodel import GPModel
+from .parameterization import lbfgsb_lockstep, SCIPY_DEFAULT
 
 
 def normalize(Y, normalization_type='stats'):
@@ -143,8 +144,11 @@ class Design_space(object):
 class AcquisitionOptimizer(object):
     """optimization/acquisition_optimizer.py:46-77 with ObjectiveAnchorPointsGenerator (:85-98)."""
 
-    def __init__(self, space, optimizer='lbfgs', num_samples=1000, num_anchor=5, maxiter=1000):
+    def __init__(self, space, optimizer='lbfgs', num_samples=1000, num_anchor=5, maxiter=1000, parallel=False):
+        """``parallel``: the L-BFGS runs from the anchors advance in lockstep (``_lbfgs_from_anchors``) instead of one after
+        the other -- with ``f_df`` and the 'lbfgs' optimiser; anything else runs the serial loop."""
         self.space = space
+        self.parallel = parallel
         self.optimizer_name = optimizer
         self.num_samples = num_samples
         self.num_anchor = num_anchor
@@ -156,6 +160,14 @@ class AcquisitionOptimizer(object):
         anchors = X[np.argsort(scores)[:min(len(scores), self.num_anchor)], :]
         bounds = self.space.get_bounds()
         best_x, best_fx = None, np.inf
+        if self.lockstep(f_df):
+            xs = _lbfgs_from_anchors(self.space, anchors, f_df, self.maxiter)
+            for k in range(0, len(xs), LOCKSTEP_GROUP):          # the rounded optima of a group scored in ONE call
+                fxs = np.asarray(f(np.vstack(xs[k:k + LOCKSTEP_GROUP])), dtype=float).ravel()
+                for x, fx in zip(xs[k:k + LOCKSTEP_GROUP], fxs):
+                    if float(fx) < best_fx:
+                        best_x, best_fx = x, float(fx)
+            return best_x, best_fx
         for a in anchors:
             if f_df is not None and self.optimizer_name == 'lbfgs':
                 def _f_df(x):                        # optimizer.py:45-47
@@ -173,6 +185,38 @@ class AcquisitionOptimizer(object):
             if fx < best_fx:
                 best_x, best_fx = x, fx
         return best_x, best_fx
+
+    def lockstep(self, f_df):
+        """True when the anchors are refined in lockstep: asked for, gradients at hand, L-BFGS."""
+        return bool(self.parallel) and f_df is not None and self.optimizer_name == 'lbfgs'
+
+
+LOCKSTEP_GROUP = 8      # anchors per lockstep group: what ONE gp_acq_rows call takes (acquisitions._FEW_ROWS)
+
+
+def _lbfgs_from_anchors(space, anchors, f_df, maxiter=1000):
+    """``_lbfgs_from_anchor`` for every anchor, the runs of a group of up to ``LOCKSTEP_GROUP`` anchors advancing in lockstep
+    (parameterization.lbfgsb_lockstep): each round's posted points go to ``f_df`` as the rows of ONE call.  A row's value and
+    gradient do not depend on its company (include/gphip.h, gp_*_rows), so every run takes the steps its serial run takes;
+    the abnormal-line-search fallback and ``round_optimum`` are applied per anchor.  Returns the [1, D] optima in anchor order."""
+    bounds = space.get_bounds()
+
+    def fbatch(xs):
+        fx, dfx = f_df(xs)
+        return np.asarray(fx, dtype=float).reshape(-1), np.asarray(dfx, dtype=float).reshape(xs.shape[0], -1)
+
+    anchors = [np.asarray(a, dtype=float) for a in anchors]
+    out = []
+    for k in range(0, len(anchors), LOCKSTEP_GROUP):
+        group = anchors[k:k + LOCKSTEP_GROUP]
+        for a, res in zip(group, lbfgsb_lockstep(fbatch, group, max_iters=maxiter, bounds=bounds, maxfun=SCIPY_DEFAULT)):
+            if isinstance(res, BaseException):
+                raise res
+            x = np.atleast_2d(res[0])
+            if res[2].get('task', b'') in (b'ABNORMAL_TERMINATION_IN_LNSRCH', 'ABNORMAL_TERMINATION_IN_LNSRCH'):
+                x = np.atleast_2d(a)
+            out.append(space.round_optimum(x))
+    return out
 
 
 def _lbfgs_from_anchor(space, a, f, f_df, maxiter=1000):
@@ -245,8 +289,11 @@ class ThompsonBatch(SamplingBasedBatchEvaluator):
         return _lbfgs_from_anchor(self.space, a, self.f, self.f_df)
 
     def compute_batch_without_duplicate_logic(self):
-        anchors = self.get_anchor_points()
-        return np.vstack([self.optimize_anchor_point(a) for a, _ in zip(anchors, range(self.batch_size))])
+        anchors = self.get_anchor_points()[:self.batch_size]
+        optimizer = self.acquisition.optimizer
+        if optimizer is not None and optimizer.lockstep(self.f_df):
+            return np.vstack(_lbfgs_from_anchors(self.space, anchors, self.f_df))
+        return np.vstack([self.optimize_anchor_point(a) for a in anchors])
 
 
 class RandomBatch(SamplingBasedBatchEvaluator):
@@ -277,7 +324,8 @@ class BayesianOptimization(object):
                  initial_design_numdata=5, initial_design_type='random', acquisition_type='EI', normalize_Y=True,
                  exact_feval=False, acquisition_optimizer_type='lbfgs', model_update_interval=1,
                  evaluator_type='sequential', batch_size=1, num_cores=1, verbosity=False, verbosity_model=False,
-                 maximize=False, de_duplication=False, model=None, acquisition=None, device=0, **kwargs):
+                 maximize=False, de_duplication=False, model=None, acquisition=None, device=0, parallel_anchors=False,
+                 **kwargs):
         if model_type not in ('GP',) and model is None:
             raise NotImplementedError("model_type %r is outside the accelerated path" % model_type)
         if evaluator_type not in ('sequential', 'local_penalization', 'thompson_sampling', 'random', None):
@@ -301,7 +349,7 @@ class BayesianOptimization(object):
             optimize_restarts=kwargs.get('optimize_restarts', 5), verbose=verbosity_model,
             ARD=kwargs.get('ARD', False), Gower=kwargs.get('Gower', False), space=self.space, device=device,
             parallel_restarts=kwargs.get('parallel_restarts', False))
-        self.acquisition_optimizer = AcquisitionOptimizer(self.space, acquisition_optimizer_type)
+        self.acquisition_optimizer = AcquisitionOptimizer(self.space, acquisition_optimizer_type, parallel=parallel_anchors)
         # arguments_manager.py:42-75
         jitter = kwargs.get('acquisition_jitter', 0.01)
         weight = kwargs.get('acquisition_weight', 2)

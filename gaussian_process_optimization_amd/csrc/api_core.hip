@@ -406,6 +406,7 @@ static const OptDesc g_options[] = {
     {"emulate_fp64", &gp_ctx::emulate_fp64, OPT_BOOL},
     {"rows_build", &gp_ctx::rows_build, OPT_RANGE, -1, 1},   // -1: by rule, 0: never, 1: at the first call
     {"rows_nt", &gp_ctx::rows_nt, OPT_RANGE, -1, 1},         // -1: automatic
+    {"rows_wide", &gp_ctx::rows_wide, OPT_BOOL},             // 5 .. 8 locations in one pass (0: passes of four)
 };
 
 static int store_option(gp_ctx *g, const OptDesc &o, int64_t value) {

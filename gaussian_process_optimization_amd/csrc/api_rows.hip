@@ -4,9 +4,17 @@
 // result block; everything it cannot take goes through gp_set_candidates + the batched entry points, same results.
 #include "api_internal.h"
 
-// fused path: up to 8 locations of a single-output model whose coordinates fit the kernel arguments
+// fused path: up to 8 locations of a single-output model whose coordinates fit the kernel arguments -- of each pass, that is: four
+// locations at a time (ROWS_MAX_M), or all of 5 .. 8 in one wide pass when M * D fits as a whole (rows_pass_width)
 static bool rows_fused_ok(const gp_ctx *g, int64_t M) {
     return g->small_m > 0 && M >= 1 && M <= g->small_m && g->P == 1 && (long)std::min<int64_t>(M, ROWS_MAX_M) * g->D <= ROWS_MAX_XS;
+}
+
+// Locations per pass of an M-location call: M itself while one pass can take them -- up to ROWS_MAX_M always, up to ROWS_WIDE_M
+// where the wide instances are on (option "rows_wide") and M * D coordinates fit the kernel arguments -- else ROWS_MAX_M.
+static int rows_pass_width(const gp_ctx *g, int M) {
+    if (M <= ROWS_MAX_M) return M;
+    return g->rows_wide && M <= ROWS_WIDE_M && (long)M * g->D <= ROWS_MAX_XS ? M : ROWS_MAX_M;
 }
 
 // When to build the inverse factor (N^3 / 3 flops once per fit: 0.7 ms at N = 4096, 4.4 ms at N = 8192, 28 ms at N = 16384).  A gradient
@@ -27,7 +35,8 @@ static int rows_scratch(gp_ctx *g, RowsWork *w) {
     const int nt = (int)(Npad / GP_TILE);
     const long nch = nt > 0 ? (nt - 1) / 8 + 1 : 1;
     const long nrb = (long)nt * (GP_TILE / rows_block_height(nt));   // row blocks of the backward pass
-    const long n_w = nch * ROWS_MAX_M * Npad, n_b = nrb * ROWS_MAX_M * Npad, n_m = nch * ROWS_MAX_M, n_v = nrb * ROWS_MAX_M;
+    // sized for a wide pass; a pass lays its partials out for its own MV (rows_layout) from the front of each array
+    const long n_w = nch * ROWS_WIDE_M * Npad, n_b = nrb * ROWS_WIDE_M * Npad, n_m = nch * ROWS_WIDE_M, n_v = nrb * ROWS_WIDE_M;
     const long n_g = (long)rows_gpart_elems(g->N);
     int rc;
     if ((rc = g->dRows.reserve(n_w + n_b + n_m + n_v + n_g))) return rc;
@@ -98,7 +107,7 @@ RowsAcq rows_acq(const AcqSpec &a, const LpSpec *lp, const LpBatch &b) {   // (R
     return RowsAcq{1, a.type, a.par, a.fmin, a.y_mean, a.y_std, 1, lp->transform, lp->nb, b.X, b.r, b.s};
 }
 
-// The pass loop of the fused path: ROWS_MAX_M locations per pass, each with a ticket and a counter base of its own.
+// The pass loop of the fused path: rows_pass_width locations per pass, each pass with a ticket and a counter base of its own.
 // launch(rx, w) puts a pass on the stream and returns how many workgroups arrive at its counter; unpack(m0, mc, MV, o) takes
 // the results of locations [m0, m0 + mc) out of the pinned block o, laid out for MV locations (gphip_internal.h).  With a phase
 // name a profiled context times each pass: `cost` reads of the inverse factor's triangle, and as many N^2 products per location.
@@ -110,8 +119,9 @@ static int rows_passes(gp_ctx *g, const double *Xs, int M, const char *phase, do
     const int D = g->D;
     const bool timed = phase && g->profiling;
     if (timed) g->nphases = 0;
-    for (int m0 = 0; m0 < M; m0 += ROWS_MAX_M) {
-        const int mc = std::min(ROWS_MAX_M, M - m0);
+    const int width = rows_pass_width(g, M);
+    for (int m0 = 0; m0 < M; m0 += width) {
+        const int mc = std::min(width, M - m0);
         RowsX rx;
         rx.M = mc;
         memcpy(rx.xs, Xs + (long)m0 * D, sizeof(double) * mc * D);
@@ -123,7 +133,8 @@ static int rows_passes(gp_ctx *g, const double *Xs, int M, const char *phase, do
         const unsigned arrivals = launch(rx, w);
         if (timed) phase_end(g, ph);
         if ((rc = rows_wait(g, w, arrivals))) return rc;
-        unpack(m0, mc, mc == 1 ? 1 : ROWS_MAX_M, g->hRowsOut);
+        ++(mc > ROWS_MAX_M ? g->rows_wide_passes : g->rows_narrow_passes);
+        unpack(m0, mc, rows_layout(mc), g->hRowsOut);
     }
     ++g->rows_fused_calls;
     return 0;
@@ -225,5 +236,13 @@ extern "C" int gp_rows_stats(gp_t *g, int64_t *fused, int64_t *fallback) {
     if (!g) return fail(GP_ERR_ARG, "null gp");
     if (fused) *fused = g->rows_fused_calls;
     if (fallback) *fallback = g->rows_fallback_calls;
+    return 0;
+}
+
+// how many passes of at most ROWS_MAX_M locations / wide passes the fused path has made since the context was created (route check)
+extern "C" int gp_rows_pass_stats(gp_t *g, int64_t *narrow, int64_t *wide) {
+    if (!g) return fail(GP_ERR_ARG, "null gp");
+    if (narrow) *narrow = g->rows_narrow_passes;
+    if (wide) *wide = g->rows_wide_passes;
     return 0;
 }

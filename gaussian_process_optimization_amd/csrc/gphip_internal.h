@@ -244,6 +244,7 @@ void launch_small_wi_product(hipStream_t s, const double *Wi, long ldw, long Npa
 
 // ---- onerow.hip: the acquisition optimiser's one-row calls as three launches over the explicit inverse factor ------------------
 #define ROWS_MAX_M 4       // locations per pass of the fused path
+#define ROWS_WIDE_M 8      // ... or per WIDE pass: 5 .. 8 locations in one read of the inverse factor (option "rows_wide")
 #define ROWS_MAX_XS 128    // ... with M * D <= ROWS_MAX_XS doubles travelling in the kernel arguments
 struct RowsX {
     int M;
@@ -256,7 +257,7 @@ struct RowsAcq {
     int lp, transform, nb;    // local penalisation (LP.py): on / log transform / batch size
     const double *Xb, *r0, *s0;
 };
-#define ROWS_OUT_DOUBLES (3 * ROWS_MAX_M * (1 + GP_MAX_D))   // result block; one more double behind it carries the call's ticket
+#define ROWS_OUT_DOUBLES (3 * ROWS_WIDE_M * (1 + GP_MAX_D))   // result block (sized for a wide pass); one more double behind it carries the call's ticket
 struct RowsWork {             // device scratch (api_rows.hip sizes it): every partial has one writer
     double *wpart, *bpart, *meanpart, *vpart, *gpart;
     unsigned int *counter;    // arrival counter of the finishing kernels: never reset between calls, each pass counts from its own base
@@ -264,6 +265,7 @@ struct RowsWork {             // device scratch (api_rows.hip sizes it): every p
     double ticket;            // written behind the results by the workgroup that finishes the call: the host checks it (a launch that
                               // did not complete must not leave the previous call's numbers in the block)
 };
+inline int rows_layout(int M) { return M == 1 ? 1 : M <= ROWS_MAX_M ? ROWS_MAX_M : ROWS_WIDE_M; }   // the MV a pass of M locations is laid out for
 long rows_tiles(int nt);
 int rows_block_height(int nt);   // rows of the tile per workgroup: 32 for matrices of a few tiles, else 128
 size_t rows_gpart_elems(long N);
@@ -271,7 +273,7 @@ size_t rows_gpart_elems(long N);
 // after every pass (api_rows.hip rows_wait), so launcher and host take it from here.
 inline unsigned rows_finish_grid(long N) { return (unsigned)((N + 63) / 64); }       // rows_finish_kernel: 64 training rows per workgroup
 inline unsigned rows_mean_grad_grid(long N) { return (unsigned)((N + 255) / 256); }  // rows_mean_grad_kernel: one row per thread
-// results (host-visible block of 3 MV (1 + D) doubles, MV = 1 for M = 1 else ROWS_MAX_M):
+// results (host-visible block of 3 MV (1 + D) doubles, MV = rows_layout(M): 1 for M = 1, ROWS_MAX_M up to 4, ROWS_WIDE_M above):
 //   [mean MV][var MV][acq MV][dmdx MV D][dvdx MV D][dacq MV D]
 void launch_rows(hipStream_t s, const double *Li, long Npad, const RowsX &rx, const KernParams &kp, const double *X, long N,
                  const double *alpha, int want_grad, double kss, double noise_add, const RowsAcq &aq, const RowsWork &w,

@@ -14,6 +14,8 @@
 //   rows_finish_kernel     beta -> the two gradients_X sums over the training points, then -- in the last workgroup to arrive --
 //                          mean, variance, acquisition, penaliser, written straight into the caller's pinned result block
 //
+// Up to ROWS_MAX_M locations share a pass (MV = 1 or 4), 5 .. ROWS_WIDE_M a WIDE pass (MV = 8: rows_forward_wide_kernel and the
+// MV = 8 instances of the other kernels); per location the arithmetic and its order are the same in all of them.
 // x travels in the kernel arguments and the results land in host-visible memory: no copy commands either side of the launches.
 // The smallm.hip route walked ~22 panels x 2 dependent launches for the same substitution (1.36 ms per gradient call at
 // N = 16384, 0.18 ms at N = 512).  A posterior-only call (no gradient) is forward + finish: two launches, one read of Li.
@@ -175,6 +177,143 @@ __global__ __launch_bounds__(256) void rows_forward_kernel(const double *Li, lon
     }
 }
 
+// ---- forward, wide: the same sums for up to ROWS_WIDE_M locations in ONE read of Li -------------------------------------------------------
+// One level of the rw_wave_sum tree for two values at once: lanes with bit o clear keep p[i] + p[i + o], lanes with it set keep
+// q[i] + q[i - o] -- what the tree's lane i - o computes for q, operands swapped, and floating-point addition is commutative.
+__device__ __forceinline__ double rw_fold(double p, double q, int lane, int o) {
+    const bool up = lane & o;
+    return (up ? q : p) + __shfl_xor(up ? p : q, o);
+}
+// The 16 sums of a row pair (v[2 m + row]) through ONE tree: 8 + 4 + 2 + 1 folds, then the last two levels on the survivor.  Lane 4 g
+// ends up with rw_wave_sum's lane-0 value of v[rw_fold_index(4 g)], bit for bit (17 shuffles for 16 x 6).
+__device__ __forceinline__ double rw_wave_sum16(const double (&v)[16], int lane) {
+    double a[8], b[4];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) a[k] = rw_fold(v[2 * k], v[2 * k + 1], lane, 32);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) b[k] = rw_fold(a[2 * k], a[2 * k + 1], lane, 16);
+    const double c0 = rw_fold(b[0], b[1], lane, 8), c1 = rw_fold(b[2], b[3], lane, 8);
+    double s = rw_fold(c0, c1, lane, 4);
+    s += __shfl_xor(s, 2);
+    s += __shfl_xor(s, 1);
+    return s;
+}
+__device__ __forceinline__ int rw_fold_index(int lane) {   // lane bits 5, 4, 3, 2 -> index bits 0, 1, 2, 3
+    return ((lane >> 5) & 1) | (((lane >> 4) & 1) << 1) | (((lane >> 3) & 1) << 2) | (((lane >> 2) & 1) << 3);
+}
+
+// rows_forward_kernel for MV = ROWS_WIDE_M.  k* stays in LDS (64 KiB: two workgroups per CU) and is re-read per row pair -- eight
+// locations' worth in registers would be 256 VGPRs -- and the 16 wave sums of a row pair share one tree.  Per location the
+// arithmetic is rows_forward_kernel's, in its order: the same bits, whatever the slot and the company.
+template <int RB, bool NT>
+__global__ __launch_bounds__(256) void rows_forward_wide_kernel(const double *Li, long ld, RowsX rx, KernParams kp, const double *X,
+                                                                long N, const double *alpha, double *wpart, long Npad, int nt,
+                                                                double *meanpart) {
+    constexpr int MV = ROWS_WIDE_M;
+    __shared__ __attribute__((aligned(16))) double ks[MV][RW_CW];
+    __shared__ double xs_s[ROWS_MAX_XS];
+    __shared__ double red[4];
+    constexpr int SUB = GP_TILE / RB;
+    int R, C;
+    rw_decode((int)blockIdx.x / SUB, R, C);
+    const int sub = (int)blockIdx.x % SUB;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int D = kp.D, M = rx.M;
+    const long c0 = (long)C * RW_CW;
+    const int klim = min(RW_CW, (R + 1) * GP_TILE - (int)c0);   // a multiple of 128
+    for (int i = tid; i < M * D; i += 256) xs_s[i] = rx.xs[i] / kp_div(kp, i % D);
+    __syncthreads();
+    for (int j = tid; j < RW_CW; j += 256) {
+        const long i = c0 + j;
+        double acc[MV];
+#pragma unroll
+        for (int m = 0; m < MV; ++m) acc[m] = kp.gower ? 1.0 : 0.0;
+        const bool live = j < klim && i < N;
+        if (live) {
+            for (int d = 0; d < D; ++d) {
+                const double b = X[i * D + d] / kp_div(kp, d);
+#pragma unroll
+                for (int m = 0; m < MV; ++m) {
+                    if (m < M) {
+                        const double df = xs_s[m * D + d] - b;
+                        if (kp.gower) {
+                            const double r = kp.gdisc[d] ? (df != 0.0 ? 1.0 : 0.0) : fabs(df);
+                            acc[m] *= gp_k_of_r2(kp.kernel, kp.variance, r * r);
+                        } else {
+                            acc[m] = fma(df, df, acc[m]);
+                        }
+                    }
+                }
+            }
+        }
+#pragma unroll
+        for (int m = 0; m < MV; ++m)
+            ks[m][j] = (live && m < M) ? (kp.gower ? acc[m] : gp_k_of_r2(kp.kernel, kp.variance, acc[m])) : 0.0;
+    }
+    __syncthreads();
+    if (R == nt - 1 && sub == 0) {   // the last row block meets every chunk: it carries the mean's partial sums
+        for (int m = 0; m < M; ++m) {
+            double s = 0.0;
+            for (int j = tid; j < klim; j += 256)
+                if (c0 + j < N) s = fma(ks[m][j], alpha[c0 + j], s);
+            s = rw_block_sum(s, red);
+            if (tid == 0) meanpart[C * MV + m] = s;
+        }
+    }
+    const long rbase = (long)R * GP_TILE + sub * RB + wave * (RB / 4);
+    const double2_t zero2 = {0.0, 0.0};
+    const int slot = rw_fold_index(lane);
+    const bool writer = (lane & 3) == 0 && (slot >> 1) < M;
+    double *const o = wpart + ((long)C * MV + (slot >> 1)) * Npad + rbase + (slot & 1);
+    // The next row pair's loads go out before this one's products, and the products are held to one location at a time
+    // (sched_barrier): left alone the compiler gathers all eight locations' k* reads, 364 registers and one workgroup per CU
+    // (profiles/rows_wide_resources.txt).
+    const double *const pl = Li + rbase * ld + c0 + 2 * lane;
+    double2_t x0[RW_Q], x1[RW_Q], n0[RW_Q], n1[RW_Q];
+#pragma unroll
+    for (int q = 0; q < RW_Q; ++q) {
+        x0[q] = (128 * q < klim) ? rw_load2<NT>(pl + 128 * q) : zero2;
+        x1[q] = (128 * q < klim) ? rw_load2<NT>(pl + ld + 128 * q) : zero2;
+    }
+    for (int r = 0; r < RB / 4; r += 2) {
+        if (r + 2 < RB / 4) {
+            const double *p0 = pl + (long)(r + 2) * ld;
+#pragma unroll
+            for (int q = 0; q < RW_Q; ++q) {
+                n0[q] = (128 * q < klim) ? rw_load2<NT>(p0 + 128 * q) : zero2;
+                n1[q] = (128 * q < klim) ? rw_load2<NT>(p0 + ld + 128 * q) : zero2;
+            }
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        double v[2 * MV];
+#pragma unroll
+        for (int m = 0; m < MV; ++m) {
+            double a0 = 0.0, a1 = 0.0, b0 = 0.0, b1 = 0.0;
+#pragma unroll
+            for (int q = 0; q < RW_Q; ++q) {
+                const double2_t k = *(const double2_t *)&ks[m][2 * lane + 128 * q];
+                a0 = fma(x0[q][0], k[0], a0);
+                a1 = fma(x0[q][1], k[1], a1);
+                b0 = fma(x1[q][0], k[0], b0);
+                b1 = fma(x1[q][1], k[1], b1);
+            }
+            v[2 * m] = a0 + a1;
+            v[2 * m + 1] = b0 + b1;
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        const double s = rw_wave_sum16(v, lane);
+        if (writer) o[r] = s;
+        if (r + 2 < RB / 4) {
+#pragma unroll
+            for (int q = 0; q < RW_Q; ++q) {
+                x0[q] = n0[q];
+                x1[q] = n1[q];
+            }
+        }
+    }
+}
+
 // ---- backward: bpart[R][m][k] = sum_{r in block R} Li[r, k] w_m[r];  vpart[R][m] = sum_{r in block R} w_m[r]^2 -------------------------
 template <int MV, int RB, bool NT>
 __global__ __launch_bounds__(256) void rows_backward_kernel(const double *Li, long ld, const double *wpart, long Npad, int M,
@@ -247,14 +386,15 @@ __global__ __launch_bounds__(256) void rows_backward_kernel(const double *Li, lo
 // grid = ceil(N / 64) workgroups of 256 threads; a workgroup carries 64 training points n.  Its four waves first split the
 // row-block partials of those points between them -- beta_m[n] = sum_{R >= n / rbh} bpart[R][m][n] (gradient call), or
 // w_m[n] = sum_C wpart[C][m][n] for |w|^2 (value call) -- wave v takes every fourth partial, the four sums are added in wave
-// order.  Wave 0 then takes point n through the two gradients_X sums (the geometry of predict_grad_kernel in grad.hip: Euclidean
-// scaled differences on the kernel's own lengthscale -- under Gower too, as the fork does, stationary.py:336-364).  Per-workgroup
+// order.  Wave 0 (in a wide pass wave m % 4 for location m) then takes point n through the two gradients_X sums (the geometry of
+// predict_grad_kernel in grad.hip: Euclidean scaled differences on the kernel's own lengthscale -- under Gower too, as the fork
+// does, stationary.py:336-364).  Per-workgroup
 // sums go to gpart, and the LAST workgroup to arrive (device-scope counter, counted from this pass's base: it is never reset, so a
 // pass cannot inherit a stale count) reduces them in workgroup order -- eight interleaved slices, added in slice order -- and
 // writes the results, then the pass's ticket behind them.
 // gpart row (per workgroup): [2 M D gradient sums | M sums of w^2], RW_GROW doubles apart
 // out (host-visible): [mean MV][var MV][acq MV][dmdx MV D][dvdx MV D][dacq MV D]
-#define RW_GROW (2 * ROWS_MAX_XS + ROWS_MAX_M)
+#define RW_GROW (2 * ROWS_MAX_XS + ROWS_WIDE_M)
 template <int MV>
 __global__ __launch_bounds__(256) void rows_finish_kernel(RowsX rx, KernParams kp, const double *X, long N, const double *alpha,
                                                           const double *wpart, const double *bpart, const double *meanpart,
@@ -264,8 +404,8 @@ __global__ __launch_bounds__(256) void rows_finish_kernel(RowsX rx, KernParams k
                                                           double ticket) {
     __shared__ double xs_s[ROWS_MAX_XS], xraw_s[ROWS_MAX_XS];
     __shared__ double part_s[4][MV][64];
-    __shared__ double fin_s[8][RW_GROW + 2 * ROWS_MAX_M];
-    __shared__ double res_s[RW_GROW + 2 * ROWS_MAX_M];
+    __shared__ double fin_s[8][RW_GROW + 2 * ROWS_WIDE_M];
+    __shared__ double res_s[RW_GROW + 2 * ROWS_WIDE_M];
     __shared__ int last_s;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int D = kp.D, M = rx.M;
@@ -289,8 +429,9 @@ __global__ __launch_bounds__(256) void rows_finish_kernel(RowsX rx, KernParams k
         part_s[wave][m][lane] = s;
     }
     __syncthreads();
-    if (wave == 0) {
-        for (int m = 0; m < M; ++m) {
+    constexpr int MW = MV > ROWS_MAX_M ? 4 : 1;   // waves that share the locations between them (a wide pass: all four)
+    if (wave < MW) {
+        for (int m = wave; m < M; m += MW) {
             const double b = ((part_s[0][m][lane] + part_s[1][m][lane]) + part_s[2][m][lane]) + part_s[3][m][lane];
             if (!want_grad) {
                 const double v = rw_wave_sum(b * b);
@@ -443,6 +584,8 @@ void launch_rows_mean_grad(hipStream_t s, const RowsX &rx, const KernParams &kp,
     const unsigned grid = rows_mean_grad_grid(N);
     if (rx.M == 1)
         GP_LAUNCH(rows_mean_grad_kernel<1>, dim3(grid), dim3(256), 0, s, rx, kp, X, N, alpha, w.gpart, w.counter, w.counter_base, out, w.ticket);
+    else if (rx.M > ROWS_MAX_M)
+        GP_LAUNCH(rows_mean_grad_kernel<ROWS_WIDE_M>, dim3(grid), dim3(256), 0, s, rx, kp, X, N, alpha, w.gpart, w.counter, w.counter_base, out, w.ticket);
     else
         GP_LAUNCH(rows_mean_grad_kernel<ROWS_MAX_M>, dim3(grid), dim3(256), 0, s, rx, kp, X, N, alpha, w.gpart, w.counter, w.counter_base, out, w.ticket);
 }
@@ -459,7 +602,10 @@ static void launch_rows_t(hipStream_t s, const double *Li, long Npad, const Rows
     const int nt = (int)(Npad / GP_TILE);
     const unsigned tiles = (unsigned)rows_tiles(nt) * (GP_TILE / RB);
     const unsigned fin = rows_finish_grid(N);
-    GP_LAUNCH((rows_forward_kernel<MV, RB, NT>), dim3(tiles), dim3(256), 0, s, Li, Npad, rx, kp, X, N, alpha, w.wpart, Npad, nt, w.meanpart);
+    if constexpr (MV > ROWS_MAX_M)
+        GP_LAUNCH((rows_forward_wide_kernel<RB, NT>), dim3(tiles), dim3(256), 0, s, Li, Npad, rx, kp, X, N, alpha, w.wpart, Npad, nt, w.meanpart);
+    else
+        GP_LAUNCH((rows_forward_kernel<MV, RB, NT>), dim3(tiles), dim3(256), 0, s, Li, Npad, rx, kp, X, N, alpha, w.wpart, Npad, nt, w.meanpart);
     if (want_grad)
         GP_LAUNCH((rows_backward_kernel<MV, RB, NT>), dim3(tiles), dim3(256), 0, s, Li, Npad, w.wpart, Npad, rx.M, w.bpart, w.vpart);
     GP_LAUNCH(rows_finish_kernel<MV>, dim3(fin), dim3(256), 0, s, rx, kp, X, N, alpha, w.wpart, w.bpart, w.meanpart, w.vpart, Npad, nt,
@@ -475,10 +621,14 @@ void launch_rows(hipStream_t s, const double *Li, long Npad, const RowsX &rx, co
         if (low) RW_GO(1, 32, false);
         else if (nt_loads) RW_GO(1, GP_TILE, true);
         else RW_GO(1, GP_TILE, false);
-    } else {
+    } else if (rx.M <= ROWS_MAX_M) {
         if (low) RW_GO(ROWS_MAX_M, 32, false);
         else if (nt_loads) RW_GO(ROWS_MAX_M, GP_TILE, true);
         else RW_GO(ROWS_MAX_M, GP_TILE, false);
+    } else {
+        if (low) RW_GO(ROWS_WIDE_M, 32, false);
+        else if (nt_loads) RW_GO(ROWS_WIDE_M, GP_TILE, true);
+        else RW_GO(ROWS_WIDE_M, GP_TILE, false);
     }
 #undef RW_GO
 }

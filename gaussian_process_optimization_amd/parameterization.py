@@ -243,13 +243,18 @@ class Parameterized(object):
             p.constrain_positive(warning)
 
 
-def lbfgsb_lockstep(fbatch, x0s, max_iters=1000, factr=None, pgtol=None):
+SCIPY_DEFAULT = "scipy"     # lbfgsb_lockstep(maxfun=SCIPY_DEFAULT): leave maxfun to fmin_l_bfgs_b's own default
+
+
+def lbfgsb_lockstep(fbatch, x0s, max_iters=1000, factr=None, pgtol=None, bounds=None, maxfun=None):
     """R ``scipy.optimize.fmin_l_bfgs_b`` runs in lockstep over ONE batch objective (optimize_restarts(parallel=True)).
 
     ``fbatch(xs)`` takes the points of the still-running instances, ``xs[k, n]`` (rows in instance order), and returns
     ``(f[k], g[k, n])`` -- or ``(f, g, errors)`` with ``errors[j]`` None or an exception that instance j's evaluation raises.
     Each instance runs in a thread of its own with the serial ``optimize``'s options (maxiter = maxfun = max_iters, factr,
-    pgtol); its objective call posts x and waits.  When every running instance has posted, one ``fbatch`` call is made and
+    pgtol); its objective call posts x and waits.  ``bounds`` (one (low, high) per variable) goes to every instance as it is;
+    ``maxfun`` replaces max_iters as the evaluation limit, ``SCIPY_DEFAULT`` leaves it to scipy (what a caller that passes
+    ``maxiter`` alone gets: the acquisition optimiser).  When every running instance has posted, one ``fbatch`` call is made and
     the values are handed back; a finished instance leaves the batch.  The L-BFGS-B state lives in each call's own arrays
     (scipy passes it all to setulb), so every instance follows the path a serial run from its start takes.
 
@@ -261,30 +266,38 @@ def lbfgsb_lockstep(fbatch, x0s, max_iters=1000, factr=None, pgtol=None):
         extra["factr"] = float(factr)
     if pgtol is not None:
         extra["pgtol"] = float(pgtol)
-    cv = threading.Condition()
-    posted, replies, running = {}, {}, set(range(R))
+    if bounds is not None:
+        extra["bounds"] = bounds
+    if maxfun is None:
+        extra["maxfun"] = int(max_iters)
+    elif maxfun != SCIPY_DEFAULT:
+        extra["maxfun"] = int(maxfun)
+    cv = threading.Condition()          # guards posted / running; only the driver waits on it, woken when a round is complete
+    posted, running = {}, set(range(R))
+    replies, answered = [None] * R, [threading.Event() for _ in range(R)]     # one hand-back per instance: nobody else wakes up
     out = [None] * R
 
     def instance(r):
         def objective(x):
             with cv:
                 posted[r] = np.array(x, dtype=float)
-                cv.notify_all()
-                while r not in replies:
-                    cv.wait()
-                rep = replies.pop(r)
+                if running.issubset(posted):
+                    cv.notify()
+            answered[r].wait()
+            answered[r].clear()
+            rep = replies[r]
             if isinstance(rep, BaseException):
                 raise rep
             return rep
 
         try:
-            out[r] = _sopt.fmin_l_bfgs_b(objective, x0s[r], maxiter=int(max_iters), maxfun=int(max_iters), **extra)
+            out[r] = _sopt.fmin_l_bfgs_b(objective, x0s[r], maxiter=int(max_iters), **extra)
         except BaseException as e:  # noqa: BLE001  (the instance's failure is its result; the others go on)
             out[r] = e
         finally:
             with cv:
                 running.discard(r)
-                cv.notify_all()
+                cv.notify()
 
     threads = [threading.Thread(target=instance, args=(r,), daemon=True) for r in range(R)]
     for t in threads:
@@ -304,9 +317,9 @@ def lbfgsb_lockstep(fbatch, x0s, max_iters=1000, factr=None, pgtol=None):
             reply = {r: (errors[j] if errors[j] is not None else (float(f[j]), g[j].copy())) for j, r in enumerate(idx)}
         except BaseException as e:  # noqa: BLE001  (a failed batch call fails the instances that were waiting on it)
             reply = {r: e for r in idx}
-        with cv:
-            replies.update(reply)
-            cv.notify_all()
+        for r in idx:
+            replies[r] = reply[r]
+            answered[r].set()
     for t in threads:
         t.join()
     return out

@@ -243,12 +243,14 @@ int gp_acq_lp_argbest(gp_t *gp, int type, double par, double fmin, double y_mean
  * (GPyOpt/GPyOpt/optimization/optimizer.py:36-61 -> acquisitions/base.py:33-50, LP.py:105-140 -> models/gpmodel.py:95-142
  * -> GPy/GPy/core/gp.py:297-354,407-454).  These two entry points are gp_set_candidates followed by the batched calls
  * named below, as ONE call taking the locations Xs[M, D] by value; for M <= option "small_m" (8) locations of a
- * single-output model with min(M, 4) D <= 128 they run as three launches (two for a value-only call) per pass of up to
- * four locations over the explicit inverse factor L^-1 (dtrtri, linalg.py:217-227; built once per fit -- at the first
- * call for N <= 4096, above that after the first N / 768 calls, which go through substitutions against L: option
- * "rows_build" -- at half the work of Ky^-1) with no copy commands (csrc/onerow.hip), otherwise through the batched calls
- * themselves.  Same results either way to rounding
- * (tests/test_gpu_rows.py: 1e-9 on well-conditioned models, the north-star 1e-6 against the oracle everywhere); the
+ * single-output model with min(M, 4) D <= 128 they run as three launches (two for a value-only call) per pass over the
+ * explicit inverse factor L^-1 (dtrtri, linalg.py:217-227; built once per fit -- at the first call for N <= 4096, above
+ * that after the first N / 768 calls, which go through substitutions against L: option "rows_build" -- at half the work of
+ * Ky^-1) with no copy commands (csrc/onerow.hip), otherwise through the batched calls themselves.  A pass takes up to four
+ * locations; 5 .. 8 locations with M D <= 128 are ONE wide pass (option "rows_wide", default 1), otherwise -- and with
+ * "rows_wide" = 0 -- passes of four.  A location's results are the same bits whatever its slot, its company and the kind of
+ * its pass.  Fused path and batched calls give the same results to rounding (tests/test_gpu_rows.py: 1e-9 on
+ * well-conditioned models, the north-star 1e-6 against the oracle everywhere); the
  * resident candidate block of gp_set_candidates is unspecified afterwards.
  *
  * gp_predict_rows = gp_predict(include_noise, mean[M], var[M]) and, when dmdx / dvdx are given,
@@ -264,6 +266,8 @@ int gp_acq_rows(gp_t *gp, const double *Xs, int64_t M, int type, double par, dou
                 double *dout);
 /* how many of those calls took the fused path / the batched calls since gp_create (route checks of the tests) */
 int gp_rows_stats(gp_t *gp, int64_t *fused, int64_t *fallback);
+/* how many passes of at most four locations / wide passes (5 .. 8 locations) the fused path has made since gp_create */
+int gp_rows_pass_stats(gp_t *gp, int64_t *narrow, int64_t *wide);
 
 /* ---- multi-GPU (one process per GPU; RCCL over xGMI) ---------------------
  * The candidate table shards across ranks; every rank holds a replica of the
@@ -405,6 +409,8 @@ int gp_synchronize(gp_t *gp);
  *   "small_m"            up to this many candidates (default 8, 0 = never) are solved as matrix-vector work bound by one read of L
  *                        (csrc/smallm.hip: the acquisition optimiser's one-row calls) instead of through the 128-row tile path;
  *                        gp_predict_full_cov / gp_posterior_samples always take the tile path
+ *   "rows_wide"          1 (default): a gp_*_rows call of 5 .. 8 locations with M D <= 128 is ONE pass over the inverse factor
+ *                        (csrc/onerow.hip, the wide instances); 0: passes of four locations.  The same bits either way
  *   "debug_potrf_lds"    test hook, process-wide: extra dynamic LDS requested with every diagonal-tile launch (a refused launch beyond
  *                        ~9 KB: what the launch checks are tested with)
  *   "profile_min_tiles"  see gp_profile
