@@ -6,6 +6,7 @@ Drop-in surface for the path GPyOpt/GPy sit on:
     m = gpo.models.GPRegression(X, Y, gpo.kern.RBF(D), noise_var=1e-2)   # GPy.models.GPRegression
     m.log_likelihood(); m.predict(Xs); m.predictive_gradients(Xs); m.optimize()
     bo = gpo.methods.BayesianOptimization(f=None, domain=..., X=X, Y=Y)  # GPyOpt.methods
+    mw = gpo.models.InputWarpedGP(X, Y, gpo.kern.Matern52(D))            # GPy.models.InputWarpedGP (Kumaraswamy warping)
     acq = gpo.acquisitions.AcquisitionEI(gpo.GPModel(...), ...)           # GPyOpt.acquisitions
 
 Host code is plain Python + ctypes over the C-ABI in include/gphip.h; every
@@ -18,6 +19,8 @@ from . import _lib
 from . import kern
 from .gp_regression import GPRegression, Gaussian, Standardize
 from .gpmodel import GPModel, BOModel
+from . import input_warping
+from .input_warped_gp import InputWarpedGP, InputWarpedGPModel
 from . import acquisitions
 from .acquisitions import (AcquisitionEI, AcquisitionLCB, AcquisitionMPI, AcquisitionBase, AcquisitionLP,
                            LocalPenalization, estimate_L)
@@ -25,11 +28,13 @@ from .bayesian_optimization import BayesianOptimization, Design_space, Acquisiti
 from .sharded import ShardedCandidates, merge_best
 
 # namespaces named like the reference packages
-models = _types.SimpleNamespace(GPRegression=GPRegression, GPModel=GPModel)
+models = _types.SimpleNamespace(GPRegression=GPRegression, GPModel=GPModel, InputWarpedGP=InputWarpedGP,
+                                InputWarpedGPModel=InputWarpedGPModel)
 methods = _types.SimpleNamespace(BayesianOptimization=BayesianOptimization)
 likelihoods = _types.SimpleNamespace(Gaussian=Gaussian)
 
 __all__ = ["kern", "models", "methods", "likelihoods", "acquisitions", "GPRegression", "GPModel", "BOModel",
+           "InputWarpedGP", "InputWarpedGPModel", "input_warping",
            "AcquisitionEI", "AcquisitionLCB", "AcquisitionMPI", "AcquisitionBase", "AcquisitionLP",
            "LocalPenalization", "estimate_L", "BayesianOptimization",
            "Design_space", "AcquisitionOptimizer", "ShardedCandidates", "merge_best", "Standardize"]

@@ -52,9 +52,14 @@ SIGNATURES = [
     ("gp_lml_grad", ctypes.c_int, [_vp, c_double_p, c_double_p, c_double_p]),
     ("gp_fit_grad", ctypes.c_int, [_vp, ctypes.c_int, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p,
                                    c_double_p]),
+    ("gp_lml_grad_x", ctypes.c_int, [_vp, c_double_p]),
+    ("gp_fit_grad_x", ctypes.c_int, [_vp, ctypes.c_int, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p,
+                                     c_double_p, c_double_p]),
     ("gp_fit_grad_batch", ctypes.c_int, [_vp, ctypes.c_int, c_double_p, c_double_p, c_double_p, ctypes.c_int, c_double_p,
                                          c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, c_int_p]),
     ("gp_set_candidates", ctypes.c_int, [_vp, c_double_p, ctypes.c_int64]),
+    ("gp_set_candidates_kumar", ctypes.c_int, [_vp, c_double_p, ctypes.c_int64, c_int_p, c_double_p, c_double_p, c_double_p,
+                                               c_double_p, c_double_p]),
     ("gp_predict", ctypes.c_int, [_vp, ctypes.c_int, c_double_p, c_double_p]),
     ("gp_predict_full_cov", ctypes.c_int, [_vp, ctypes.c_int, c_double_p, c_double_p]),
     ("gp_predict_grad", ctypes.c_int, [_vp, c_double_p, c_double_p]),
@@ -277,6 +282,23 @@ class Handle(object):
         check(self.lib, rc, "gp_fit_grad")
         return (lml.value, logdet.value, jit.value), (dv.value, dl, dn.value)
 
+    def lml_grad_x(self):
+        """dL/dX [N, D] of the training inputs at the current fit (gp_lml_grad_x)."""
+        out = np.empty((self.N, self.D))
+        check(self.lib, self.lib.gp_lml_grad_x(self.h, dptr(out)), "gp_lml_grad_x")
+        return out
+
+    def fit_grad_x(self, nls, maxtries=5):
+        """gp_fit_grad + gp_lml_grad_x as one call: ((lml, logdet, jitter), (dvariance, dlengthscale[nls], dnoise), dL_dX [N, D])."""
+        lml, logdet, jit = _fit_scalars()
+        dv, dn = ctypes.c_double(), ctypes.c_double()
+        dl = self._grad_ls(nls)
+        dX = np.empty((self.N, self.D))
+        rc = self.lib.gp_fit_grad_x(self.h, int(maxtries), ctypes.byref(lml), ctypes.byref(logdet), ctypes.byref(jit),
+                                    ctypes.byref(dv), dptr(dl), ctypes.byref(dn), dptr(dX))
+        check(self.lib, rc, "gp_fit_grad_x")
+        return (lml.value, logdet.value, jit.value), (dv.value, dl, dn.value), dX
+
     def fit_grad_batch(self, variances, lengthscales, noises, maxtries=5):
         """gp_fit_grad for R parameter vectors in one call (the resident fit is untouched).  ``lengthscales`` is [R, nls] with nls
         the last set_params' lengthscale count.  Returns ((lml, logdet, jitter) [R] each, (dvariance [R], dlengthscale [R, nls],
@@ -376,6 +398,24 @@ class Handle(object):
             raise ValueError("candidates have %d columns, model has %d" % (Xs.shape[1], self.D))
         check(self.lib, self.lib.gp_set_candidates(self.h, dptr(Xs), Xs.shape[0]), "gp_set_candidates")
         self.M = Xs.shape[0]
+
+    def set_candidates_kumar(self, Xs, warp, a, b, xmin, xmax, want_warped=False):
+        """gp_set_candidates of the Kumaraswamy-warped table, warped on the device: ``warp`` [D] 0 / 1, ``a``, ``b``, ``xmin``,
+        ``xmax`` [D] (read where ``warp`` is set; the bounds already widened by epsilon).  Returns the warped table with
+        ``want_warped``."""
+        Xs = as_f64(Xs, 2)
+        if Xs.shape[1] != self.D:
+            raise ValueError("candidates have %d columns, model has %d" % (Xs.shape[1], self.D))
+        warp = np.ascontiguousarray(warp, dtype=np.int32).reshape(-1)
+        vecs = [as_f64(np.atleast_1d(v), 1) for v in (a, b, xmin, xmax)]
+        if warp.size != self.D or any(v.size != self.D for v in vecs):
+            raise ValueError("warp, a, b, xmin and xmax need one entry per input dimension")
+        out = np.empty_like(Xs) if want_warped else None
+        rc = self.lib.gp_set_candidates_kumar(self.h, dptr(Xs), Xs.shape[0], warp.ctypes.data_as(c_int_p), dptr(vecs[0]),
+                                              dptr(vecs[1]), dptr(vecs[2]), dptr(vecs[3]), dptr(out) if want_warped else None)
+        check(self.lib, rc, "gp_set_candidates_kumar")
+        self.M = Xs.shape[0]
+        return out
 
     def predict(self, include_noise=True):
         mean = np.empty((self.M, self.P))

@@ -21,7 +21,12 @@ from scipy import optimize as _sopt
 from . import kern as _kern
 from .acquisitions import AcquisitionEI, AcquisitionLCB, AcquisitionMPI, AcquisitionLP, LocalPenalization
 from .gpmodel import GPModel
+from .input_warped_gp import InputWarpedGPModel
 from .parameterization import lbfgsb_lockstep, SCIPY_DEFAULT
+
+
+class InvalidConfigError(Exception):
+    """GPyOpt/GPyOpt/core/errors.py: a combination of options the loop cannot run."""
 
 
 def normalize(Y, normalization_type='stats'):
@@ -318,7 +323,7 @@ def kernel_from_name(name, input_dim, ARD=False):
 
 
 class BayesianOptimization(object):
-    """GPyOpt.methods.BayesianOptimization for model_type='GP' (bayesian_optimization.py:76-170)."""
+    """GPyOpt.methods.BayesianOptimization for model_type='GP' and 'input_warped_GP' (bayesian_optimization.py:76-170)."""
 
     def __init__(self, f, domain=None, constraints=None, cost_withGradients=None, model_type='GP', X=None, Y=None,
                  initial_design_numdata=5, initial_design_type='random', acquisition_type='EI', normalize_Y=True,
@@ -326,8 +331,11 @@ class BayesianOptimization(object):
                  evaluator_type='sequential', batch_size=1, num_cores=1, verbosity=False, verbosity_model=False,
                  maximize=False, de_duplication=False, model=None, acquisition=None, device=0, parallel_anchors=False,
                  **kwargs):
-        if model_type not in ('GP',) and model is None:
+        if model_type not in ('GP', 'input_warped_GP') and model is None:
             raise NotImplementedError("model_type %r is outside the accelerated path" % model_type)
+        if model_type == 'input_warped_GP' and evaluator_type == 'local_penalization' and batch_size > 1:
+            # arguments_manager.py:32-34 (the penaliser's distances live in un-warped space)
+            raise InvalidConfigError('local_penalization evaluator can only be used with GP models')
         if evaluator_type not in ('sequential', 'local_penalization', 'thompson_sampling', 'random', None):
             raise NotImplementedError("evaluator %r is outside the accelerated path" % evaluator_type)
         self.evaluator_type = evaluator_type
@@ -343,6 +351,14 @@ class BayesianOptimization(object):
         kernel = kwargs.get('kernel', None)
         if isinstance(kernel, str):
             kernel = kernel_from_name(kernel, self.space.dimensionality, ARD=kwargs.get('ARD', False))
+        if model is None and model_type == 'input_warped_GP':
+            # arguments_manager.py:137-147: only the Kumaraswamy warping exists (None selects it)
+            if kwargs.get('input_warping_function_type', "kumar_warping") != "kumar_warping":
+                print("Only support kumar_warping for input!")
+            model = InputWarpedGPModel(self.space, None, kernel, kwargs.get('noise_var', None), exact_feval,
+                                       kwargs.get('model_optimizer_type', 'lbfgs'), kwargs.get('max_iters', 1000),
+                                       kwargs.get('optimize_restarts', 5), verbosity_model, kwargs.get('ARD', False),
+                                       device=device)
         self.model = model if model is not None else GPModel(
             kernel=kernel, noise_var=kwargs.get('noise_var', None), exact_feval=exact_feval,
             optimizer=kwargs.get('model_optimizer_type', 'lbfgs'), max_iters=kwargs.get('max_iters', 1000),

@@ -24,10 +24,24 @@ void grads_from_sums(const double *h, const KernParams &kp, int ard, double *dva
     }
 }
 
-int lml_grad_impl(gp_ctx *g, double *dvariance, double *dlengthscale, double *dnoise, bool reset_phases) {
+// dL/dX of the training inputs into dT behind the pass's own partials, as a phase (Ky^-1 is in dWi: ensure_wi ran, dT is free)
+static int lml_grad_x_pass(gp_ctx *g, double **out) {
+    const long np = gradx_partial_elems(g->Npad);
+    int rc;
+    if ((rc = g->dT.reserve(np + g->N * g->D))) return rc;   // (never grows after ensure_wi: Npad^2 covers it)
+    const int ph = phase_begin(g, "lml_grad_x", 0.0, 8.0 * (double)g->N * g->N + 16.0 * (double)g->N * g->D);
+    launch_gradx(g->s, g->dX, g->N, g->Npad, g->kp, g->dAlpha, g->P, g->dWi, g->Npad, g->dT, g->dT + np);
+    phase_end(g, ph);
+    *out = g->dT + np;
+    return 0;
+}
+
+// dL_dX non-null: the input gradients behind the hyper-gradients, both handed over at the one synchronisation
+int lml_grad_impl(gp_ctx *g, double *dvariance, double *dlengthscale, double *dnoise, bool reset_phases, double *dL_dX) {
     if (!g || !dvariance || !dlengthscale || !dnoise) return fail(GP_ERR_ARG, "null argument");
     GP_FITTED(g);
     if (g->P > GP_GRAD_MAX_P) return fail(GP_ERR_ARG, "gp_lml_grad supports P <= %d", GP_GRAD_MAX_P);
+    if (dL_dX && g->kp.gower) return fail(GP_ERR_ARG, "gp_lml_grad_x: not defined for a Gower model");
     // (a Gower model gets the fork's values: K through the Gower branch in the variance gradient, Euclidean dK/dr on the kernel's own
     // lengthscale in the lengthscale gradients, stationary.py:218-238 -- not derivatives of its LML, which the host layer knows)
     int rc;
@@ -40,6 +54,11 @@ int lml_grad_impl(gp_ctx *g, double *dvariance, double *dlengthscale, double *dn
     const int npass = g->ard ? (g->D + GP_GRAD_CH - 1) / GP_GRAD_CH : 1;
     std::vector<double> host((size_t)GP_GRAD_NACC * npass);
     HIPCHK(hipMemcpyAsync(host.data(), g->dScal + SCAL_GRAD.off, sizeof(double) * host.size(), hipMemcpyDeviceToHost, g->s));
+    if (dL_dX) {
+        double *dev;
+        if ((rc = lml_grad_x_pass(g, &dev))) return rc;
+        HIPCHK(hipMemcpyAsync(dL_dX, dev, sizeof(double) * g->N * g->D, hipMemcpyDeviceToHost, g->s));
+    }
     GP_SYNC(g->s);
     grads_from_sums(host.data(), g->kp, g->ard, dvariance, dlengthscale, dnoise);
     return 0;
@@ -49,15 +68,28 @@ extern "C" int gp_lml_grad(gp_t *g, double *dvariance, double *dlengthscale, dou
     return lml_grad_impl(g, dvariance, dlengthscale, dnoise, true);
 }
 
+// ---- dL/dX of the training inputs (InputWarpedGP.parameters_changed: kern.gradients_X(dL_dK, X), input_warped_gp.py:94-103) ----
+extern "C" int gp_lml_grad_x(gp_t *g, double *dL_dX) {
+    if (!g || !dL_dX) return fail(GP_ERR_ARG, "null argument");
+    GP_FITTED(g);
+    if (g->P > GP_GRAD_MAX_P) return fail(GP_ERR_ARG, "gp_lml_grad_x supports P <= %d", GP_GRAD_MAX_P);
+    // the fork's Euclidean gradients_X on a Gower K is not a derivative of anything the warping could use
+    if (g->kp.gower) return fail(GP_ERR_ARG, "gp_lml_grad_x: not defined for a Gower model");
+    int rc;
+    g->nphases = 0;
+    if ((rc = ensure_wi(g))) return rc;
+    double *dev;
+    if ((rc = lml_grad_x_pass(g, &dev))) return rc;
+    HIPCHK(hipMemcpyAsync(dL_dX, dev, sizeof(double) * g->N * g->D, hipMemcpyDeviceToHost, g->s));
+    GP_SYNC(g->s);
+    return 0;
+}
+
 // gp_fit + gp_lml_grad as ONE call (what every L-BFGS evaluation of the hyper-parameter loop asks for:
 // Model.objective_function + objective_function_gradients, core/model.py:96-127).  The first stages of the solve for
 // L^-T ride behind the factorisation's latency-bound tail, like the candidate stages of gp_fit_predict.
-extern "C" int gp_fit_grad(gp_t *g, int maxtries, double *lml, double *logdet, double *jitter_used, double *dvariance,
-                double *dlengthscale, double *dnoise) {
-    if (!g || !dvariance || !dlengthscale || !dnoise) return fail(GP_ERR_ARG, "null argument");
-    GP_DEAD_CHECK(g);
-    if (!g->have_data || !g->have_params) return fail(GP_ERR_STATE, "set data and params before gp_fit_grad");
-    if (g->P > GP_GRAD_MAX_P) return fail(GP_ERR_ARG, "gp_lml_grad supports P <= %d", GP_GRAD_MAX_P);
+// The fit of that call (shared with gp_fit_grad_x):
+static int fit_grad_head(gp_ctx *g, int maxtries, double *lml, double *logdet, double *jitter_used) {
     HIPCHK(hipSetDevice(g->device));
     const int nt = (int)(g->Npad / GP_TILE);
     // emulated: Ky^-1 in residue form after the factorisation (wi_rns) instead of fp64 stages pipelined behind it
@@ -68,7 +100,31 @@ extern "C" int gp_fit_grad(gp_t *g, int maxtries, double *lml, double *logdet, d
     if (lml) *lml = g->lml;
     if (logdet) *logdet = g->logdet;
     if (jitter_used) *jitter_used = g->jitter;
+    return 0;
+}
+extern "C" int gp_fit_grad(gp_t *g, int maxtries, double *lml, double *logdet, double *jitter_used, double *dvariance,
+                double *dlengthscale, double *dnoise) {
+    if (!g || !dvariance || !dlengthscale || !dnoise) return fail(GP_ERR_ARG, "null argument");
+    GP_DEAD_CHECK(g);
+    if (!g->have_data || !g->have_params) return fail(GP_ERR_STATE, "set data and params before gp_fit_grad");
+    if (g->P > GP_GRAD_MAX_P) return fail(GP_ERR_ARG, "gp_lml_grad supports P <= %d", GP_GRAD_MAX_P);
+    int rc;
+    if ((rc = fit_grad_head(g, maxtries, lml, logdet, jitter_used))) return rc;
     return lml_grad_impl(g, dvariance, dlengthscale, dnoise, false);
+}
+
+// gp_fit_grad followed by the input-gradient pass, as ONE call with one final hand-over: what every L-BFGS evaluation of the
+// input-warped model asks for (the warped inputs changed, so the fit is new each time)
+extern "C" int gp_fit_grad_x(gp_t *g, int maxtries, double *lml, double *logdet, double *jitter_used, double *dvariance,
+                             double *dlengthscale, double *dnoise, double *dL_dX) {
+    if (!g || !dvariance || !dlengthscale || !dnoise || !dL_dX) return fail(GP_ERR_ARG, "null argument");
+    GP_DEAD_CHECK(g);
+    if (!g->have_data || !g->have_params) return fail(GP_ERR_STATE, "set data and params before gp_fit_grad_x");
+    if (g->P > GP_GRAD_MAX_P) return fail(GP_ERR_ARG, "gp_lml_grad_x supports P <= %d", GP_GRAD_MAX_P);
+    if (g->kp.gower) return fail(GP_ERR_ARG, "gp_lml_grad_x: not defined for a Gower model");
+    int rc;
+    if ((rc = fit_grad_head(g, maxtries, lml, logdet, jitter_used))) return rc;
+    return lml_grad_impl(g, dvariance, dlengthscale, dnoise, false, dL_dX);
 }
 
 // ---- second candidate-sized buffer (beta = K(Xs,X) Ky^-1, or the full covariance) -----------------

@@ -487,6 +487,6 @@ int ensure_wi(gp_ctx *g);
 int ensure_linv(gp_ctx *g);
 void lml_grad_passes(gp_ctx *g, const Members &m);
 void grads_from_sums(const double *h, const KernParams &kp, int ard, double *dvariance, double *dlengthscale, double *dnoise);
-int lml_grad_impl(gp_ctx *g, double *dvariance, double *dlengthscale, double *dnoise, bool reset_phases);
+int lml_grad_impl(gp_ctx *g, double *dvariance, double *dlengthscale, double *dnoise, bool reset_phases, double *dL_dX = nullptr);
 int ensure_grad_buffers(gp_ctx *g, long elemsBeta, long M);
 int run_predict_grad(gp_ctx *g);

@@ -18,6 +18,29 @@ extern "C" int gp_set_candidates(gp_t *g, const double *Xs, int64_t M) {
     return 0;
 }
 
+// gp_set_candidates of the Kumaraswamy-warped table (KumarWarping.f, input_warping_functions.py:179-200), warped on the device
+extern "C" int gp_set_candidates_kumar(gp_t *g, const double *Xs, int64_t M, const int *warp, const double *a, const double *b,
+                                       const double *xmin, const double *xmax, double *warped_out) {
+    if (!g || !Xs || !warp || !a || !b || !xmin || !xmax) return fail(GP_ERR_ARG, "null argument");
+    GP_DEAD_CHECK(g);
+    if (!g->have_data) return fail(GP_ERR_STATE, "gp_set_data first");
+    for (int q = 0; q < g->D; ++q) {
+        if (!warp[q]) continue;
+        if (!(a[q] > 0.0) || !(b[q] > 0.0) || !std::isfinite(a[q]) || !std::isfinite(b[q]))
+            return fail(GP_ERR_ARG, "gp_set_candidates_kumar: a, b must be positive and finite (dimension %d)", q);
+        if (!(xmax[q] > xmin[q]) || !std::isfinite(xmax[q]) || !std::isfinite(xmin[q]))
+            return fail(GP_ERR_ARG, "gp_set_candidates_kumar: xmax <= xmin (dimension %d)", q);
+    }
+    int rc;
+    if ((rc = gp_set_candidates(g, Xs, M))) return rc;
+    const long mc_max = std::min(g->mc_max, round_up(M, GP_TILE));   // the chunks of run_predict
+    for (long m0 = 0; m0 < M; m0 += mc_max)
+        launch_kumar_warp(g->s, g->dXs, m0, std::min(mc_max, (long)M - m0), g->D, warp, a, b, xmin, xmax);
+    if (warped_out) HIPCHK(hipMemcpyAsync(warped_out, g->dXs, sizeof(double) * M * g->D, hipMemcpyDeviceToHost, g->s));
+    GP_SYNC(g->s);
+    return 0;
+}
+
 int run_predict(gp_ctx *g, int include_noise, bool tiles_only) {
     if (!g->fitted) return fail(GP_ERR_STATE, "gp_fit first");
     if (g->M < 1) return fail(GP_ERR_STATE, "gp_set_candidates first");

@@ -316,6 +316,16 @@ void launch_dldk(hipStream_t s, double *out, long ldo, const double *alpha, long
 // zero the strict upper triangle of the nt diagonal 128-tiles (the factor's tiles keep the symmetric input there)
 void launch_zero_upper_diag(hipStream_t s, double *A, long lda, int nt);
 
+// ---- gradx.hip: input-side kernels of the input-warped GP -------------------------------------------------------------
+// out[i, q] = dL/dX_iq for i < N (row-major [N, D]): sum_j 2 dL_dK_ij g(r_ij) (x_iq - x_jq) / l_q^2 with dL_dK = 0.5 (alpha alpha^T -
+// P Wi), one pass over Wi (both triangles) per GP_GRAD_CH dimensions; partial: gradx_partial_elems(Npad) doubles of scratch
+long gradx_partial_elems(long Npad);
+void launch_gradx(hipStream_t s, const double *X, long N, long Npad, const KernParams &kp, const double *alpha, int P,
+                  const double *Wi, long ldw, double *partial, double *out);
+// rows [m0, m0 + mc) of the resident [M, D] table Xs (m0 D even) through the Kumaraswamy CDF, in place, where warp[q] is set
+void launch_kumar_warp(hipStream_t s, double *Xs, long m0, long mc, int D, const int *warp, const double *a, const double *b,
+                       const double *xmin, const double *xmax);
+
 // ---- rns.hip: fp64-equivalent contraction on the int8 matrix cores (option "emulate_fp64") -----------------------------
 #define GP_RNS_T 14
 #define GP_RNS_KMAX 8192   // longest contraction (bytes) one residue launch may take: see rns_reduce_f in rns.hip

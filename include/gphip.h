@@ -140,6 +140,22 @@ int gp_get_dl_dk(gp_t *gp, double *dL_dK);
 int gp_fit_grad(gp_t *gp, int maxtries, double *lml, double *logdet, double *jitter_used, double *dvariance,
                 double *dlengthscale, double *dnoise);
 
+/* InputWarpedGP.parameters_changed (GPy/GPy/models/input_warped_gp.py:94-103): kern.gradients_X(dL_dK, X) with X2 = None,
+ * Stationary.gradients_X (stationary.py:336-352 with tmp + tmp.T, _inv_dist :251-258) -- the LML's gradient with respect to the
+ * training inputs, which the warping function's update_grads turns into gradients of its parameters:
+ *   dL_dX[i, q] = (1 / l_q^2) sum_{j != i} 2 dL_dK_ij g(r_ij) (x_iq - x_jq),  g(r) = dK_dr(r) / r, 0 at r = 0
+ * dL_dX[N, D] row-major.  One pass over Ky^-1 per 16 dimensions (csrc/gradx.hip), no atomics: the same bits from run to run.
+ * Always true fp64; under "emulate_fp64" it reads whichever Ky^-1 the fit produced.  Requires gp_fit (GP_ERR_STATE); P <= 16
+ * and no Gower model (the fork's Euclidean gradients_X on a Gower K is not a derivative of anything), else GP_ERR_ARG.
+ * Leaves the fit, the validity flags and the resident candidates as gp_lml_grad leaves them. */
+int gp_lml_grad_x(gp_t *gp, double *dL_dX);
+
+/* gp_fit_grad followed by gp_lml_grad_x as ONE call with one final hand-over: what every L-BFGS evaluation of the
+ * input-warped model asks for (the warped inputs moved, so gp_set_data precedes it).  The first eight outputs are bitwise
+ * those of gp_fit_grad, dL_dX[N, D] bitwise that of gp_lml_grad_x after it.  Return codes as gp_fit_grad and gp_lml_grad_x. */
+int gp_fit_grad_x(gp_t *gp, int maxtries, double *lml, double *logdet, double *jitter_used, double *dvariance,
+                  double *dlengthscale, double *dnoise, double *dL_dX);
+
 /* gp_fit_grad for R parameter vectors over the resident (X, Y) in ONE call: member r has variance[r], lengthscale[r*nls ...]
  * (nls = 1, or D with ard, from the last gp_set_params) and noise[r]; kernel, ard and the Gower set-up are the context's.
  * Replaces the serial restarts of GPModel.updateModel (GPyOpt/GPyOpt/models/gpmodel.py:78-93: optimize_restarts of
@@ -156,6 +172,18 @@ int gp_fit_grad_batch(gp_t *gp, int R, const double *variance, const double *len
 /* ---- predict -----------------------------------------------------------
  * Candidates Xs[M,D] are made resident once; the calls below then run on them. */
 int gp_set_candidates(gp_t *gp, const double *Xs, int64_t M);
+
+/* gp_set_candidates(w(Xs)) for the input-warped GP: KumarWarping.f (GPy/GPy/util/input_warping_functions.py:179-200) applied
+ * to the table on the device.  The un-warped Xs[M, D] goes host-to-device as in gp_set_candidates; one elementwise kernel
+ * (csrc/gradx.hip) then overwrites the resident block, "mc_max" rows per launch:
+ *   column q with warp[q] != 0:  1 - (1 - u^a[q])^b[q],  u = (x - xmin[q]) / (xmax[q] - xmin[q])   (double-precision pow;
+ *                                u outside [0, 1] gives what NumPy's power gives the reference, NaN for fractional exponents)
+ *   column q with warp[q] == 0:  the value itself, bit for bit.
+ * warp, a, b, xmin, xmax have D entries each (a, b, xmin, xmax are read only where warp[q] is set); the caller passes xmin /
+ * xmax already widened by its epsilon.  warped_out[M, D], when not NULL, receives the warped table.  a or b non-positive or
+ * non-finite, or xmax <= xmin, is GP_ERR_ARG.  No state is kept: nothing else in the context learns of the warp. */
+int gp_set_candidates_kumar(gp_t *gp, const double *Xs, int64_t M, const int *warp, const double *a, const double *b,
+                            const double *xmin, const double *xmax, double *warped_out);
 
 /* PosteriorExact._raw_predict (posterior.py:273-302, full_cov = False) followed by
  * Gaussian.predictive_values (likelihoods/gaussian.py:102-110) when include_noise != 0:

@@ -1117,6 +1117,69 @@ def batch_restarts():
               % (parallel, float(np.median(times)), min(times), max(times), fs), flush=True)
 
 
+@command
+def lml_grad_x():
+    """The input-warped GP's device steps: the "lml_grad_x" phase beside "lml_grad" (HIP events, gp_last_phases), gp_fit_grad_x
+    against gp_fit_grad at N = 300, and gp_set_candidates_kumar against gp_set_candidates at M = 10^6 with the host time of
+    KumarWarping.f on the same table.  Every shape warmed up, medians of repeated calls (test tooling)."""
+    import time
+    import numpy as np
+    from gaussian_process_optimization_amd import _lib
+    from gaussian_process_optimization_amd.input_warping import KumarWarping
+    h = _lib.Handle(0)
+    def data(N, D, seed=1):
+        rng = np.random.default_rng(seed)
+        X = rng.uniform(0, 1, (N, D)); Y = (np.sin(3 * X.sum(1)) + 0.1 * rng.standard_normal(N))[:, None]
+        return X, Y
+    print("phases of gp_fit_grad_x (ARD RBF), medians; GB/s = algorithmic bytes / time", flush=True)
+    print("%6s %3s %5s | %10s %9s | %12s %9s | %6s" % ("N", "D", "reps", "lml_grad", "GB/s", "lml_grad_x", "GB/s", "ratio"), flush=True)
+    for N, D, reps in [(300, 3, 21), (4096, 8, 9), (16384, 8, 5)]:
+        X, Y = data(N, D); h.set_data(X, Y)
+        ls = 0.25 * np.sqrt(D) * np.linspace(0.8, 1.25, D)
+        rec = {"lml_grad": [], "lml_grad_x": []}
+        for r in range(reps + 1):            # (the first call warms the shape up)
+            h.set_params(0, 1, 1.0, ls, 1e-2)
+            h.fit_grad_x(D)
+            if r:
+                for p in h.phases():
+                    if p["name"] in rec: rec[p["name"]].append((p["ms"], p["bytes"]))
+        g = [float(np.median([m for m, _ in rec[k]])) for k in ("lml_grad", "lml_grad_x")]
+        b = [rec[k][0][1] for k in ("lml_grad", "lml_grad_x")]
+        print("%6d %3d %5d | %8.4f ms %9.1f | %10.4f ms %9.1f | %6.2f" % (N, D, reps, g[0], b[0] / g[0] / 1e6, g[1], b[1] / g[1] / 1e6,
+                                                                 g[1] / g[0]), flush=True)
+    # per-evaluation cost at N = 300, the two calls alternating in the same loop
+    X, Y = data(300, 3); h.set_data(X, Y); ls = np.array([0.4, 0.7, 1.1])
+    ta, tb = [], []
+    for r in range(41):
+        h.set_params(1, 1, 1.3, ls, 1e-2); t0 = time.perf_counter(); h.fit_grad(3); t1 = time.perf_counter()
+        h.set_params(1, 1, 1.3, ls, 1e-2); t2 = time.perf_counter(); h.fit_grad_x(3); t3 = time.perf_counter()
+        if r: ta.append((t1 - t0) * 1e3); tb.append((t3 - t2) * 1e3)
+    print("N = 300, D = 3 (Matern-5/2 ARD), 40 alternating calls: gp_fit_grad median %.4f ms, gp_fit_grad_x median %.4f ms (+%.4f ms)"
+          % (np.median(ta), np.median(tb), np.median(tb) - np.median(ta)), flush=True)
+    # the warp of a candidate table
+    M, D = 1000000, 8
+    rng = np.random.default_rng(3)
+    Xs = rng.uniform(0, 1, (M, D))
+    X, Y = data(512, D); h.set_data(X, Y)
+    w = KumarWarping(Xs, Xmin=np.zeros(D), Xmax=np.ones(D))
+    for q in range(D):
+        w.params[q][0].set(0.5 + 0.2 * q); w.params[q][1].set(2.0 - 0.15 * q)
+    args = w.device_arguments(D)
+    def med(fn, reps=7):
+        fn(); out = []
+        for _ in range(reps):
+            t0 = time.perf_counter(); fn(); out.append((time.perf_counter() - t0) * 1e3)
+        return float(np.median(out))
+    t_plain = med(lambda: h.set_candidates(Xs))
+    t_kumar = med(lambda: h.set_candidates_kumar(Xs, *args))
+    t_host = med(lambda: w.f(Xs, test_data=True), reps=3)
+    print("M = 10^6, D = 8 (all columns warped): gp_set_candidates %.2f ms, gp_set_candidates_kumar %.2f ms (+%.2f ms for the kernel), "
+          "KumarWarping.f on the host of this machine %.1f ms" % (t_plain, t_kumar, t_kumar - t_plain, t_host), flush=True)
+    got = h.set_candidates_kumar(Xs[:4096], *args, want_warped=True)
+    print("largest |device - NumPy| over 4096 rows of that table: %.3e" % float(np.max(np.abs(got - w.f(Xs[:4096], test_data=True)))), flush=True)
+    h.close()
+
+
 def main():
     if len(sys.argv) < 2 or sys.argv[1] in ("-h", "--help", "--list"):
         print(__doc__)
