@@ -7,6 +7,7 @@ Drop-in surface for the path GPyOpt/GPy sit on:
     m.log_likelihood(); m.predict(Xs); m.predictive_gradients(Xs); m.optimize()
     bo = gpo.methods.BayesianOptimization(f=None, domain=..., X=X, Y=Y)  # GPyOpt.methods
     mw = gpo.models.InputWarpedGP(X, Y, gpo.kern.Matern52(D))            # GPy.models.InputWarpedGP (Kumaraswamy warping)
+    mo = gpo.models.WarpedGP(X, Y, gpo.kern.Matern32(D))                 # GPy.models.WarpedGP (tanh warp of the outputs)
     acq = gpo.acquisitions.AcquisitionEI(gpo.GPModel(...), ...)           # GPyOpt.acquisitions
 
 Host code is plain Python + ctypes over the C-ABI in include/gphip.h; every
@@ -21,6 +22,8 @@ from .gp_regression import GPRegression, Gaussian, Standardize
 from .gpmodel import GPModel, BOModel
 from . import input_warping
 from .input_warped_gp import InputWarpedGP, InputWarpedGPModel
+from . import warping_functions
+from .warped_gp import WarpedGP, WarpedGPModel
 from . import acquisitions
 from .acquisitions import (AcquisitionEI, AcquisitionLCB, AcquisitionMPI, AcquisitionBase, AcquisitionLP,
                            LocalPenalization, estimate_L)
@@ -29,12 +32,12 @@ from .sharded import ShardedCandidates, merge_best
 
 # namespaces named like the reference packages
 models = _types.SimpleNamespace(GPRegression=GPRegression, GPModel=GPModel, InputWarpedGP=InputWarpedGP,
-                                InputWarpedGPModel=InputWarpedGPModel)
+                                InputWarpedGPModel=InputWarpedGPModel, WarpedGP=WarpedGP, WarpedGPModel=WarpedGPModel)
 methods = _types.SimpleNamespace(BayesianOptimization=BayesianOptimization)
 likelihoods = _types.SimpleNamespace(Gaussian=Gaussian)
 
 __all__ = ["kern", "models", "methods", "likelihoods", "acquisitions", "GPRegression", "GPModel", "BOModel",
-           "InputWarpedGP", "InputWarpedGPModel", "input_warping",
+           "InputWarpedGP", "InputWarpedGPModel", "input_warping", "WarpedGP", "WarpedGPModel", "warping_functions",
            "AcquisitionEI", "AcquisitionLCB", "AcquisitionMPI", "AcquisitionBase", "AcquisitionLP",
            "LocalPenalization", "estimate_L", "BayesianOptimization",
            "Design_space", "AcquisitionOptimizer", "ShardedCandidates", "merge_best", "Standardize"]

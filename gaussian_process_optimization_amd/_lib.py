@@ -61,6 +61,17 @@ SIGNATURES = [
     ("gp_set_candidates_kumar", ctypes.c_int, [_vp, c_double_p, ctypes.c_int64, c_int_p, c_double_p, c_double_p, c_double_p,
                                                c_double_p, c_double_p]),
     ("gp_predict", ctypes.c_int, [_vp, ctypes.c_int, c_double_p, c_double_p]),
+    ("gp_set_output_warp", ctypes.c_int, [_vp, ctypes.c_int, c_double_p, ctypes.c_double, c_double_p]),
+    ("gp_get_targets", ctypes.c_int, [_vp, c_double_p]),
+    ("gp_warp_grad", ctypes.c_int, [_vp, c_double_p, c_double_p]),
+    ("gp_fit_grad_warp", ctypes.c_int, [_vp, ctypes.c_int, c_double_p, ctypes.c_double, ctypes.c_int, c_double_p, c_double_p,
+                                        c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p]),
+    ("gp_predict_warped", ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_int, c_double_p,
+                                         c_double_p, ctypes.c_int, c_double_p, c_double_p, c_double_p, c_double_p]),
+    ("gp_warp_moments", ctypes.c_int, [_vp, c_double_p, c_double_p, ctypes.c_int64, ctypes.c_double, ctypes.c_double,
+                                       ctypes.c_int, c_double_p, c_double_p, ctypes.c_int, c_double_p, c_double_p, c_double_p,
+                                       c_double_p]),
+    ("gp_warp_inverse", ctypes.c_int, [_vp, c_double_p, ctypes.c_int64, c_double_p]),
     ("gp_predict_full_cov", ctypes.c_int, [_vp, ctypes.c_int, c_double_p, c_double_p]),
     ("gp_predict_grad", ctypes.c_int, [_vp, c_double_p, c_double_p]),
     ("gp_fmin", ctypes.c_int, [_vp, c_double_p]),
@@ -415,6 +426,92 @@ class Handle(object):
                                               dptr(vecs[1]), dptr(vecs[2]), dptr(vecs[3]), dptr(out) if want_warped else None)
         check(self.lib, rc, "gp_set_candidates_kumar")
         self.M = Xs.shape[0]
+        return out
+
+    # -- output warp (include/gphip.h, "output-warped GP") --------------------------
+    @staticmethod
+    def _psi(psi):
+        psi = as_f64(np.atleast_2d(psi), 2)
+        if psi.shape[1] != 3:
+            raise ValueError("psi needs one (a, b, c) row per term, got shape %s" % (psi.shape,))
+        return psi
+
+    def set_output_warp(self, psi=None, d=1.0):
+        """Warp the resident targets with f(y) = d y + sum a tanh(b (y + c)), ``psi`` [n_terms, 3]; returns sum log f'(y).
+        ``psi`` None (or empty) switches the warp off."""
+        lj = ctypes.c_double()
+        if psi is None or np.size(psi) == 0:
+            check(self.lib, self.lib.gp_set_output_warp(self.h, 0, None, 1.0, ctypes.byref(lj)), "gp_set_output_warp")
+            return 0.0
+        psi = self._psi(psi)
+        check(self.lib, self.lib.gp_set_output_warp(self.h, psi.shape[0], dptr(psi), float(d), ctypes.byref(lj)),
+              "gp_set_output_warp")
+        return lj.value
+
+    def targets(self):
+        """The resident targets [N, P] as the fit sees them (f of the raw ones under a warp)."""
+        out = np.empty((self.N, self.P))
+        check(self.lib, self.lib.gp_get_targets(self.h, dptr(out)), "gp_get_targets")
+        return out
+
+    def warp_grad(self, n_terms):
+        """(dpsi [n_terms, 3], dd): natural gradients of LML + log-Jacobian at the current fit."""
+        dpsi, dd = np.empty((int(n_terms), 3)), ctypes.c_double()
+        check(self.lib, self.lib.gp_warp_grad(self.h, dptr(dpsi), ctypes.byref(dd)), "gp_warp_grad")
+        return dpsi, dd.value
+
+    def fit_grad_warp(self, psi, d, nls, maxtries=5):
+        """set_output_warp + fit_grad + warp_grad as one call: ((lml, logdet, jitter), (dvariance, dlengthscale[nls], dnoise),
+        log_jacobian, (dpsi [n_terms, 3], dd))."""
+        psi = self._psi(psi)
+        lml, logdet, jit = _fit_scalars()
+        dv, dn, lj, dd = ctypes.c_double(), ctypes.c_double(), ctypes.c_double(), ctypes.c_double()
+        dl = self._grad_ls(nls)
+        dpsi = np.empty_like(psi)
+        rc = self.lib.gp_fit_grad_warp(self.h, psi.shape[0], dptr(psi), float(d), int(maxtries), ctypes.byref(lml),
+                                       ctypes.byref(logdet), ctypes.byref(jit), ctypes.byref(dv), dptr(dl), ctypes.byref(dn),
+                                       ctypes.byref(lj), dptr(dpsi), ctypes.byref(dd))
+        check(self.lib, rc, "gp_fit_grad_warp")
+        return (lml.value, logdet.value, jit.value), (dv.value, dl, dn.value), lj.value, (dpsi, dd.value)
+
+    @staticmethod
+    def _gauss_hermite(deg):
+        t, w = np.polynomial.hermite.hermgauss(int(deg))
+        return as_f64(t, 1), as_f64(w, 1)
+
+    def _moments(self, call, M, deg, median, partials):
+        t, w = self._gauss_hermite(deg)
+        mean, var = np.empty((M, 1)), np.empty((M, 1))
+        med = np.empty((M, 1)) if median else None
+        part = np.empty((M, 4)) if partials else None
+        call(t.size, dptr(t), dptr(w), 1 if median else 0, dptr(mean), dptr(var), dptr(med) if median else None,
+             dptr(part) if partials else None)
+        return mean, var, med, part
+
+    def predict_warped(self, include_noise=True, y_mean=0.0, y_std=1.0, deg=20, median=False, partials=False):
+        """Warped (mean [M, 1], var [M, 1], median [M, 1] or None, partials [M, 4] or None) of the resident candidates."""
+        def call(n, t, w, wm, mean, var, med, part):
+            check(self.lib, self.lib.gp_predict_warped(self.h, int(bool(include_noise)), float(y_mean), float(y_std), n, t, w,
+                                                       wm, mean, var, med, part), "gp_predict_warped")
+        return self._moments(call, self.M, deg, median, partials)
+
+    def warp_moments(self, mean, var, y_mean=0.0, y_std=1.0, deg=20, median=False, partials=False):
+        """The same for a latent posterior given by value (``mean``, ``var`` of M entries each)."""
+        mi, vi = as_f64(np.ravel(mean), 1), as_f64(np.ravel(var), 1)
+        if mi.size != vi.size or mi.size < 1:
+            raise ValueError("mean and var need the same, positive number of entries")
+
+        def call(n, t, w, wm, mo, vo, med, part):
+            check(self.lib, self.lib.gp_warp_moments(self.h, dptr(mi), dptr(vi), mi.size, float(y_mean), float(y_std), n, t, w,
+                                                     wm, mo, vo, med, part), "gp_warp_moments")
+        return self._moments(call, mi.size, deg, median, partials)
+
+    def warp_inverse(self, z):
+        """f^-1 of every entry of ``z`` with the warp in force, in the shape of ``z``."""
+        z = as_f64(z)
+        out = np.empty_like(z)
+        if z.size:
+            check(self.lib, self.lib.gp_warp_inverse(self.h, dptr(z.reshape(-1)), z.size, dptr(out.reshape(-1))), "gp_warp_inverse")
         return out
 
     def predict(self, include_noise=True):

@@ -26,6 +26,8 @@ extern "C" int gp_fit_grad_batch(gp_t *g, int R, const double *variance, const d
         return fail(GP_ERR_ARG, "null argument");
     GP_DEAD_CHECK(g);
     if (!g->have_data || !g->have_params) return fail(GP_ERR_STATE, "set data and params before gp_fit_grad_batch");
+    if (g->warp.n > 0)   // the members share Y, and each would need targets warped by parameters of its own
+        return fail(GP_ERR_STATE, "gp_fit_grad_batch: an output warp is on (gp_set_output_warp); use gp_fit_grad_warp");
     if (R < 1) return fail(GP_ERR_ARG, "R must be at least 1");
     if (R > GP_BATCH_MAX_R) return fail(GP_ERR_ARG, "gp_fit_grad_batch takes at most R = %d members (got %d)", GP_BATCH_MAX_R, R);
     if (g->Npad > GP_BATCH_MAX_NPAD)

@@ -493,6 +493,8 @@ extern "C" int gp_set_data(gp_t *g, const double *X, const double *Y, int64_t N,
     GP_DEAD_CHECK(g);
     if (N < 1 || D < 1 || D > GP_MAX_D || P < 1 || P > GP_MAX_RHS)
         return fail(GP_ERR_ARG, "bad shape N=%ld D=%d P=%d (D <= %d, P <= %d)", (long)N, D, P, GP_MAX_D, GP_MAX_RHS);
+    if (g->warp.n > 0 && P != 1)
+        return fail(GP_ERR_STATE, "an output warp is on (gp_set_output_warp): it takes P = 1, switch it off before data with P = %d", P);
     HIPCHK(hipSetDevice(g->device));
     GP_SYNC(g->s);
     const long Npad = round_up(N, GP_TILE);
@@ -520,6 +522,10 @@ extern "C" int gp_set_data(gp_t *g, const double *X, const double *Y, int64_t N,
     g->P = P;
     HIPCHK(hipMemcpyAsync(g->dX, X, sizeof(double) * N * D, hipMemcpyHostToDevice, g->s));
     HIPCHK(hipMemcpyAsync(g->dY, Y, sizeof(double) * N * P, hipMemcpyHostToDevice, g->s));
+    if (g->warp.n > 0) {   // an active output warp is applied to the new targets
+        int rc = warp_apply(g, true);
+        if (rc) return rc;
+    }
     GP_SYNC(g->s);
     g->have_data = true;
     fit_dropped(g);

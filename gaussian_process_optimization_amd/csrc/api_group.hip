@@ -134,6 +134,14 @@ extern "C" int gp_group_member(gp_group_t *grp, int i, gp_t **member) {
     return 0;
 }
 
+// A group replicates ONE model and scores in latent space: a member with an output warp on (set through gp_group_member) is refused
+static int group_unwarped(gp_group *grp) {
+    for (size_t i = 0; i < grp->m.size(); ++i)
+        if (grp->m[i]->warp.n > 0)
+            return fail(GP_ERR_STATE, "member %zu has an output warp on (gp_set_output_warp): groups do not take warped models", i);
+    return 0;
+}
+
 // fn(member) on every member in turn, on the calling thread (host-only settings: nothing to run side by side)
 template <class F>
 static int each_member(gp_group *grp, F fn) {
@@ -151,6 +159,7 @@ extern "C" int gp_group_set_option(gp_group_t *grp, const char *name, int64_t va
 
 extern "C" int gp_group_set_data(gp_group_t *grp, const double *X, const double *Y, int64_t N, int D, int P) {
     if (!grp) return fail(GP_ERR_ARG, "null group");
+    if (int rw = group_unwarped(grp)) return rw;
     return for_members(grp, [&](int i) { return gp_set_data(grp->m[i], X, Y, N, D, P); });
 }
 
@@ -168,6 +177,7 @@ extern "C" int gp_group_set_gower(gp_group_t *grp, int enable, const int *is_dis
 // another posterior).
 extern "C" int gp_group_fit(gp_group_t *grp, int maxtries, double *lml, double *logdet, double *jitter_used) {
     if (!grp) return fail(GP_ERR_ARG, "null group");
+    if (int rw = group_unwarped(grp)) return rw;
     const size_t n = grp->m.size();
     std::vector<double> l(n), d(n), j(n);
     int rc = for_members(grp, [&](int i) { return gp_fit(grp->m[i], maxtries, &l[i], &d[i], &j[i]); });
@@ -184,6 +194,7 @@ extern "C" int gp_group_fit(gp_group_t *grp, int maxtries, double *lml, double *
 
 extern "C" int gp_group_fmin(gp_group_t *grp, double *fmin) {
     if (!grp || !fmin) return fail(GP_ERR_ARG, "null argument");
+    if (int rw = group_unwarped(grp)) return rw;
     return gp_fmin(grp->m[0], fmin);
 }
 
@@ -191,6 +202,7 @@ extern "C" int gp_group_fmin(gp_group_t *grp, double *fmin) {
 extern "C" int gp_group_set_candidates(gp_group_t *grp, const double *Xs, int64_t M) {
     if (!grp || !Xs) return fail(GP_ERR_ARG, "null argument");
     if (M < 1) return fail(GP_ERR_ARG, "M < 1");
+    if (int rw = group_unwarped(grp)) return rw;
     const int n = (int)grp->m.size();
     grp->lo.assign(n, 0);
     grp->hi.assign(n, 0);
@@ -344,6 +356,7 @@ static int score_blocks(gp_group *grp, int k, Pairs &p, F score) {
     });
 }
 static int group_ready(gp_group *grp, int sense) {
+    if (int rw = group_unwarped(grp)) return rw;
     if (grp->M < 1) return fail(GP_ERR_STATE, "gp_group_set_candidates first");
     return check_sense(sense);
 }

@@ -2,6 +2,7 @@
 // entry points each unit offers the others.  (include/gphip.h is the public C ABI; gphip_internal.h the kernels.)
 #pragma once
 #include "gphip_internal.h"
+#include "warp_math.h"
 #include "../../include/gphip.h"
 
 #include <hip/hip_ext.h>
@@ -93,9 +94,13 @@ constexpr Slot SCAL_DOT_GRAD{8, GP_GRAD_MAX_P};          // ... as far as it goe
 constexpr Slot SCAL_GRAD{64, GP_MAX_D / GP_GRAD_CH * GP_GRAD_NACC};   // GP_GRAD_NACC sums per pass of GP_GRAD_CH dimensions
 constexpr Slot SCAL_FIT_RECORD{400, 4};                  // gp_comm_bcast_fit
 constexpr Slot SCAL_TRACE{420, 2};                       // trace and smallest diagonal entry, gp_posterior_samples
+constexpr Slot SCAL_WARP_LOGJAC{430, 1};                 // sum log f'(y) of the output warp (warp_y_kernel)
+constexpr Slot SCAL_WARP_GRAD{431, GP_WARP_NPSI};        // the warp's 3 T + 1 gradient sums (warp_grad_kernel)
 static_assert(GP_MAX_D % GP_GRAD_CH == 0, "whole gradient passes");
 static_assert(slots_ok({SCAL_LOGDET, SCAL_DOT, SCAL_FIT_RECORD, SCAL_TRACE}, SCAL_CAP), "dScal: a fit of up to GP_MAX_RHS outputs");
 static_assert(slots_ok({SCAL_LOGDET, SCAL_DOT_GRAD, SCAL_GRAD, SCAL_FIT_RECORD, SCAL_TRACE}, SCAL_CAP), "dScal: fit and gradient");
+static_assert(slots_ok({SCAL_LOGDET, SCAL_DOT_GRAD, SCAL_GRAD, SCAL_FIT_RECORD, SCAL_TRACE, SCAL_WARP_LOGJAC, SCAL_WARP_GRAD}, SCAL_CAP),
+              "dScal: fit and gradient of a warped model (gp_fit_grad_warp)");
 // dRedV (doubles) and dRedI (rows): the two-level arg-best reduction; what rides beside it
 constexpr long REDV_CAP = 512, REDI_CAP = 1024;
 constexpr Slot RED_PARTIAL{0, 256};                      // first-level winners, in both buffers (launch_argbest: <= 256 blocks)
@@ -298,6 +303,11 @@ struct gp_ctx {
     // gp_fit_grad_batch (api_batch.hip): buffers of its own, sized to the R and Npad in use -- never the resident fit's
     DevBuf<double> dBatch;
     DevBuf<signed char> dBatchAux;   // per-member KernParams table, then factorisation status words
+    // output warp (api_warp.hip): warp.n > 0 while one is on -- dY then holds f(dYraw), dYraw the targets gp_set_data brought
+    WarpParams warp{0, 1.0, {}, {}, {}};
+    DevBuf<double> dYraw;  // N: the raw targets of a warped model
+    double warp_logjac = 0.0;   // sum log f'(y) of the warp in force
+    DevBuf<double> dWarp;  // 9 M: posterior by value (mean, var), then warped mean, variance, median and the four partials
     bool dead = false;  // gp_shutdown ran: the device's streams are gone, only gp_destroy is still valid
 };
 
@@ -490,3 +500,4 @@ void grads_from_sums(const double *h, const KernParams &kp, int ard, double *dva
 int lml_grad_impl(gp_ctx *g, double *dvariance, double *dlengthscale, double *dnoise, bool reset_phases, double *dL_dX = nullptr);
 int ensure_grad_buffers(gp_ctx *g, long elemsBeta, long M);
 int run_predict_grad(gp_ctx *g);
+int warp_apply(gp_ctx *g, bool raw_in_dY);   // api_warp.hip: (dYraw <- dY when dY holds raw targets,) dY <- f(dYraw), warp_logjac; enqueued on g->s, the caller drains

@@ -215,7 +215,8 @@ int gp_posterior_samples(gp_t *gp, int include_noise, const double *Z, int S, in
 int gp_predict_grad(gp_t *gp, double *dmdx, double *dvdx);
 
 /* GPModel.get_fmin (GPyOpt/GPyOpt/models/gpmodel.py:125-129): min over the training
- * inputs of the posterior mean.  Cached per fit (the reference recomputes it per call). */
+ * inputs of the posterior mean.  Cached per fit (the reference recomputes it per call).  Under an output warp it stays
+ * in latent space: the minimum of the mean of f(Y). */
 int gp_fmin(gp_t *gp, double *fmin);
 
 /* AcquisitionBase.acquisition_function on the resident candidates
@@ -265,6 +266,70 @@ int gp_acq_lp_grad(gp_t *gp, int type, double par, double fmin, double y_mean, d
 int gp_acq_lp_argbest(gp_t *gp, int type, double par, double fmin, double y_mean, double y_std, int transform,
                       const double *Xb, int nb, const double *r_x0, const double *s_x0, int sense,
                       const int64_t *exclude, int nex, int64_t *idx, double *val);
+
+/* ---- output-warped GP ----------------------------------------------------------------------------------------------------
+ * GPy.models.WarpedGP (GPy/GPy/models/warped_gp.py:13-160) behind GPyOpt's WarpedGPModel (GPyOpt/GPyOpt/models/
+ * warpedgpmodel.py:15-68): the GP is fitted to f(Y), f the monotone warp of Snelson et al. (TanhFunction,
+ * GPy/GPy/util/warping_functions.py:71-169)
+ *   f(y) = d y + sum_i a_i tanh(b_i (y + c_i)),  i < n_terms <= 8,
+ * with psi[3 n_terms] = (a_0, b_0, c_0, a_1, ...) row-major as the reference's psi matrix.  Valid parameters are finite with
+ * a_i >= 0, b_i >= 0 and d > 0 (f is then strictly increasing); anything else, or n_terms outside 0..8, is GP_ERR_ARG.  The
+ * warp's arithmetic is csrc/warp_math.h, its kernels csrc/warp.hip; every reduction has a fixed order, so the same input
+ * gives the same bits on every call.
+ *
+ * While a warp is on, the fit, its gradients, the posterior and the acquisition entry points work in LATENT space, on f(Y):
+ * so does the cached minimum of the training mean (the fmin entry point).  The batched fit-and-gradient returns GP_ERR_STATE
+ * (its members share Y, and each would need targets warped by parameters of its own), and so do the group entry points that
+ * load, fit or score (a group replicates one un-warped model). */
+
+/* WarpedGP.transform_data + the Jacobian term of log_likelihood (warped_gp.py:42,47-57): the resident targets become
+ * f(Y_raw), *log_jacobian = sum_n log f'(y_n) -- what the host adds to the LML.  The raw targets are kept in a buffer of
+ * the context's own, so the call may be repeated with other parameters; n_terms = 0 switches the warp off and restores
+ * the raw targets (psi may be NULL, d is ignored, *log_jacobian = 0).  Needs data with P = 1 (GP_ERR_STATE otherwise);
+ * drops the fit.  A later upload of data with P = 1 warps the new targets with the parameters in force; with P != 1 it is
+ * refused (GP_ERR_STATE) until the warp is off. */
+int gp_set_output_warp(gp_t *gp, int n_terms, const double *psi, double d, double *log_jacobian);
+
+/* The resident targets as the fit sees them, Y[N, P]: the caller's own without a warp, f(Y_raw) under one -- WarpedGP's
+ * Y_normalized after transform_data (warped_gp.py:42). */
+int gp_get_targets(gp_t *gp, double *Y);
+
+/* TanhFunction.update_grads (warping_functions.py:159-169) with Kiy the resident alpha (warped_gp.py:44-45): natural-space
+ * gradients of LML + log-Jacobian with respect to the warp's parameters,
+ *   grad_psi = -sum_n alpha_n df/dpsi(y_n) + sum_n (df'/dpsi)(y_n) / f'(y_n),
+ * dpsi[3 n_terms] laid out as psi, *dd for d.  Requires a fit and an active warp (GP_ERR_STATE). */
+int gp_warp_grad(gp_t *gp, double *dpsi, double *dd);
+
+/* The three steps of one L-BFGS evaluation of the warped model (WarpedGP.parameters_changed, warped_gp.py:38-45) as ONE call:
+ * the warp of the targets with the new parameters, the fit with its hyper-gradients, the warp's gradients.  Outputs are
+ * bitwise those of the three calls in sequence; return codes theirs.  1 <= n_terms <= 8. */
+int gp_fit_grad_warp(gp_t *gp, int n_terms, const double *psi, double d, int maxtries, double *lml, double *logdet,
+                     double *jitter_used, double *dvariance, double *dlengthscale, double *dnoise, double *log_jacobian,
+                     double *dpsi, double *dd);
+
+/* WarpedGP.predict with predict_in_warped_space (warped_gp.py:62-116) over the resident candidates: the latent posterior
+ * (computed first unless the resident one is current), un-normalised as mean y_std + y_mean, var y_std^2 BEFORE the warp is
+ * inverted (warped_gp.py:101), is pushed through f^-1 at the deg <= 64 Gauss-Hermite nodes[deg] / weights[deg] the caller
+ * supplies (numpy.polynomial.hermite.hermgauss):
+ *   y_k = f^-1(m + sqrt2 sigma t_k);  mean[M] = sum w_k y_k / sqrt(pi);  var[M] = sum w_k y_k^2 / sqrt(pi) - mean^2.
+ * want_median != 0: median[M] = f^-1(m) as well.  partials[M, 4], when not NULL: (d mean / d m, d mean / d sigma,
+ * d var / d m, d var / d sigma) of the un-normalised m and sigma.  A candidate's numbers depend on its own (m, sigma) only,
+ * not on M or its row.  Deviations from the reference: sigma = sqrt(max(var, 0)) (the reference takes the root of a negative
+ * variance and returns NaN); f^-1 is a Newton iteration kept inside the bracket [(z - sum a) / d, (z + sum a) / d] and run to
+ * a step below 2^-52 max(1, |y|), not the reference's 250 damped sweeps with their stopping rule over the whole array
+ * (warping_functions.py:34-57), which are still far from the root for steep warps.  With the warp off f is the identity.
+ * Needs P = 1 (GP_ERR_STATE). */
+int gp_predict_warped(gp_t *gp, int include_noise, double y_mean, double y_std, int deg, const double *nodes,
+                      const double *weights, int want_median, double *mean, double *var, double *median, double *partials);
+
+/* The same moments for a latent posterior given by value, mean_in[M] / var_in[M]: the route of a handful of locations after
+ * the few-rows predict.  Bitwise what the resident route returns for the same (mean, var). */
+int gp_warp_moments(gp_t *gp, const double *mean_in, const double *var_in, int64_t M, double y_mean, double y_std, int deg,
+                    const double *nodes, const double *weights, int want_median, double *mean, double *var, double *median,
+                    double *partials);
+
+/* y[n] = f^-1(z[n]) with the warp in force: WarpedGP.predict_quantiles (warped_gp.py:118-132). */
+int gp_warp_inverse(gp_t *gp, const double *z, int64_t n, double *y);
 
 /* ---- a handful of locations per call: the acquisition optimiser's inner loop --------------------------------
  * scipy's L-BFGS-B evaluates the acquisition ONE location per call, hundreds of times between two fits

@@ -1180,6 +1180,86 @@ def lml_grad_x():
     h.close()
 
 
+@command
+def warped_predict():
+    """The output-warped GP's prediction at N = 512: gp_predict (the latent posterior), gp_predict_warped with that posterior
+    current (the warp stage alone: warp_moments_kernel and the read-back of mean and variance) and from scratch, for tables of
+    10^4 and 10^6 rows and 20 Gauss-Hermite nodes; beside them the host time of the NumPy restatement of warped_gp.py:62-116
+    (250 damped Newton sweeps over the [20, M] array, twice: mean and variance) on the same latent posterior.  Argument: the
+    rows of the 10^6 table the host restatement is timed on (default 10^5, scaled; 0: no host timing).  Medians of repeated
+    calls after a warm-up; the kernel's own duration comes from a rocprofv3 --kernel-trace --stats run of this command."""
+    import time
+    import numpy as np
+    from gaussian_process_optimization_amd import _lib
+    from gaussian_process_optimization_amd.warping_functions import TanhFunction
+    host_rows = int(sys.argv[1]) if len(sys.argv) > 1 else 100000
+    N, D, deg = 512, 3, 20
+    rng = np.random.default_rng(1)
+    X = rng.uniform(0, 1, (N, D))
+    Y = (np.exp(1.2 * np.sin(3 * X.sum(1))) - 1.0 + 0.05 * rng.standard_normal(N))[:, None]
+    psi, d = np.array([[0.7, 1.9, -0.4], [1.6, 0.5, 1.2], [0.3, 4.0, 0.1]]), 0.6
+    w = TanhFunction(3)
+    w.set_psi(psi, d)
+    h = _lib.Handle(0)
+    h.set_data(X, Y)
+    h.set_params(_lib.GP_KERNEL_MATERN32, True, 1.3, np.array([0.4, 0.7, 1.1]), 2e-2)
+    h.set_output_warp(psi, d)
+    h.fit()
+
+    def med(fn, reps):
+        fn()
+        out = []
+        for _ in range(reps):
+            t0 = time.perf_counter()
+            fn()
+            out.append((time.perf_counter() - t0) * 1e3)
+        return float(np.median(out)), min(out), max(out)
+
+    def host_moments(mean, std):
+        """warped_gp.py:62-87 with f_inv of warping_functions.py:34-57, as the reference's predict calls them."""
+        t, wt = np.polynomial.hermite.hermgauss(deg)
+
+        def term():
+            z = t[:, None].dot(std.T) * np.sqrt(2) + np.ones((deg, 1)).dot(mean.T)
+            y = np.ones_like(z)
+            it, update = 0, np.inf
+            while np.abs(update).sum() > 1e-10 and it < 250:
+                update = (w.f(y) - z) / w.fgrad_y(y)
+                y -= 0.1 * update
+                it += 1
+            return y
+        wmean = wt[None, :].dot(term()) / np.sqrt(np.pi)
+        return wmean, wt[None, :].dot(term() ** 2) / np.sqrt(np.pi) - wmean ** 2
+
+    print("N = %d, D = %d, Matern-3/2 ARD, 3 tanh terms, %d nodes; ms, median (min .. max)" % (N, D, deg), flush=True)
+    for M, reps in ((10000, 21), (1000000, 7)):
+        Xs = np.random.default_rng(2).uniform(0, 1, (M, D))
+        h.set_candidates(Xs)
+        t_pred = med(lambda: h.predict(True), reps)
+        h.predict(True)
+        t_warp = med(lambda: h.predict_warped(True, deg=deg), reps)          # the posterior is current: the warp stage alone
+
+        def scratch():
+            h.set_option("small_m", 8)                                     # (drops the resident posterior, nothing else)
+            h.predict_warped(True, deg=deg)
+        t_both = med(scratch, reps)
+        t_part = med(lambda: h.predict_warped(True, deg=deg, median=True, partials=True), reps)
+        print("M = %7d: gp_predict %.3f (%.3f .. %.3f) | warp stage alone %.3f (%.3f .. %.3f) | gp_predict_warped from scratch "
+              "%.3f (%.3f .. %.3f) | warp stage with median and partials %.3f (%.3f .. %.3f)" % ((M,) + t_pred + t_warp + t_both + t_part),
+              flush=True)
+        if host_rows:
+            m, v = h.predict(True)
+            rows = M if M <= host_rows else host_rows
+            t0 = time.perf_counter()
+            hm, hv = host_moments(m[:rows], np.sqrt(v[:rows]))
+            t_host = (time.perf_counter() - t0) * 1e3
+            dm, dv, _, _ = h.warp_moments(m[:rows], v[:rows], deg=deg)
+            print("             NumPy restatement on the host of this machine: %.0f ms for %d rows%s; largest |device - host| mean %.2e "
+                  "variance %.2e" % (t_host, rows, "" if rows == M else " (x %g for the table: %.0f ms)" % (M / rows, t_host * M / rows),
+                                     float(np.max(np.abs(dm[:, 0] - hm[0]))), float(np.max(np.abs(dv[:, 0] - hv[0])))), flush=True)
+    h.close()
+
+
 def main():
     if len(sys.argv) < 2 or sys.argv[1] in ("-h", "--help", "--list"):
         print(__doc__)
