@@ -8,6 +8,7 @@ Drop-in surface for the path GPyOpt/GPy sit on:
     bo = gpo.methods.BayesianOptimization(f=None, domain=..., X=X, Y=Y)  # GPyOpt.methods
     mw = gpo.models.InputWarpedGP(X, Y, gpo.kern.Matern52(D))            # GPy.models.InputWarpedGP (Kumaraswamy warping)
     mo = gpo.models.WarpedGP(X, Y, gpo.kern.Matern32(D))                 # GPy.models.WarpedGP (tanh warp of the outputs)
+    ms = gpo.models.SparseGPRegression(X, Y, num_inducing=128)           # GPy.models.SparseGPRegression (variational DTC)
     acq = gpo.acquisitions.AcquisitionEI(gpo.GPModel(...), ...)           # GPyOpt.acquisitions
 
 Host code is plain Python + ctypes over the C-ABI in include/gphip.h; every
@@ -19,6 +20,7 @@ import types as _types
 from . import _lib
 from . import kern
 from .gp_regression import GPRegression, Gaussian, Standardize
+from .sparse_gp import SparseGPRegression
 from .gpmodel import GPModel, BOModel
 from . import input_warping
 from .input_warped_gp import InputWarpedGP, InputWarpedGPModel
@@ -31,12 +33,12 @@ from .bayesian_optimization import BayesianOptimization, Design_space, Acquisiti
 from .sharded import ShardedCandidates, merge_best
 
 # namespaces named like the reference packages
-models = _types.SimpleNamespace(GPRegression=GPRegression, GPModel=GPModel, InputWarpedGP=InputWarpedGP,
+models = _types.SimpleNamespace(GPRegression=GPRegression, SparseGPRegression=SparseGPRegression, GPModel=GPModel, InputWarpedGP=InputWarpedGP,
                                 InputWarpedGPModel=InputWarpedGPModel, WarpedGP=WarpedGP, WarpedGPModel=WarpedGPModel)
 methods = _types.SimpleNamespace(BayesianOptimization=BayesianOptimization)
 likelihoods = _types.SimpleNamespace(Gaussian=Gaussian)
 
-__all__ = ["kern", "models", "methods", "likelihoods", "acquisitions", "GPRegression", "GPModel", "BOModel",
+__all__ = ["kern", "models", "methods", "likelihoods", "acquisitions", "GPRegression", "SparseGPRegression", "GPModel", "BOModel",
            "InputWarpedGP", "InputWarpedGPModel", "input_warping", "WarpedGP", "WarpedGPModel", "warping_functions",
            "AcquisitionEI", "AcquisitionLCB", "AcquisitionMPI", "AcquisitionBase", "AcquisitionLP",
            "LocalPenalization", "estimate_L", "BayesianOptimization",

@@ -72,6 +72,13 @@ SIGNATURES = [
                                        ctypes.c_int, c_double_p, c_double_p, ctypes.c_int, c_double_p, c_double_p, c_double_p,
                                        c_double_p]),
     ("gp_warp_inverse", ctypes.c_int, [_vp, c_double_p, ctypes.c_int64, c_double_p]),
+    ("gp_sparse_set_inducing", ctypes.c_int, [_vp, c_double_p, ctypes.c_int64]),
+    ("gp_sparse_fit", ctypes.c_int, [_vp, ctypes.c_int, c_double_p, c_double_p, c_double_p]),
+    ("gp_sparse_fit_grad", ctypes.c_int, [_vp, ctypes.c_int, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p]),
+    ("gp_sparse_posterior", ctypes.c_int, [_vp, c_double_p, c_double_p]),
+    ("gp_sparse_predict", ctypes.c_int, [_vp, c_double_p, ctypes.c_int64, ctypes.c_int, c_double_p, c_double_p, c_double_p,
+                                         c_double_p]),
+    ("gp_sparse_fmin", ctypes.c_int, [_vp, c_double_p]),
     ("gp_predict_full_cov", ctypes.c_int, [_vp, ctypes.c_int, c_double_p, c_double_p]),
     ("gp_predict_grad", ctypes.c_int, [_vp, c_double_p, c_double_p]),
     ("gp_fmin", ctypes.c_int, [_vp, c_double_p]),
@@ -513,6 +520,56 @@ class Handle(object):
         if z.size:
             check(self.lib, self.lib.gp_warp_inverse(self.h, dptr(z.reshape(-1)), z.size, dptr(out.reshape(-1))), "gp_warp_inverse")
         return out
+
+    # -- sparse GP (include/gphip.h, "sparse GP") --------------------------------------
+    def sparse_set_inducing(self, Z):
+        Z = as_f64(Z, 2)
+        if Z.shape[1] != self.D:
+            raise ValueError("inducing inputs have %d columns, model has %d" % (Z.shape[1], self.D))
+        check(self.lib, self.lib.gp_sparse_set_inducing(self.h, dptr(Z), Z.shape[0]), "gp_sparse_set_inducing")
+        self.Mz = Z.shape[0]
+
+    def sparse_fit(self, maxtries=5):
+        """(lml, jitter of Kmm's ladder, jitter of B's ladder)."""
+        lml, jk, jb = _fit_scalars()
+        check(self.lib, self.lib.gp_sparse_fit(self.h, int(maxtries), ctypes.byref(lml), ctypes.byref(jk), ctypes.byref(jb)),
+              "gp_sparse_fit")
+        return lml.value, jk.value, jb.value
+
+    def sparse_fit_grad(self, nls, maxtries=5):
+        """gp_sparse_fit and its gradients as one call: (lml, (dvariance, dlengthscale[nls], dnoise, dZ [Mz, D]))."""
+        lml, dv, dn = _fit_scalars()
+        dl = self._grad_ls(nls)
+        dZ = np.empty((self.Mz, self.D))
+        rc = self.lib.gp_sparse_fit_grad(self.h, int(maxtries), ctypes.byref(lml), ctypes.byref(dv), dptr(dl), ctypes.byref(dn),
+                                         dptr(dZ))
+        check(self.lib, rc, "gp_sparse_fit_grad")
+        return lml.value, (dv.value, dl, dn.value, dZ)
+
+    def sparse_posterior(self):
+        """(woodbury_vector [Mz, P], woodbury_inv [Mz, Mz]) of the sparse fit."""
+        wv, wi = np.empty((self.Mz, self.P)), np.empty((self.Mz, self.Mz))
+        check(self.lib, self.lib.gp_sparse_posterior(self.h, dptr(wv), dptr(wi)), "gp_sparse_posterior")
+        return wv, wi
+
+    def sparse_predict(self, Xs, include_noise=True, grad=False):
+        """(mean [M, P], var [M, 1]) at ``Xs`` and, with ``grad``, (dmdx [M, D, P], dvdx [M, D]) as well."""
+        Xs = as_f64(Xs, 2)
+        if Xs.shape[1] != self.D:
+            raise ValueError("candidates have %d columns, model has %d" % (Xs.shape[1], self.D))
+        M = Xs.shape[0]
+        mean, var = np.empty((M, self.P)), np.empty((M, 1))
+        dm = np.empty((M, self.D, self.P)) if grad else None
+        dv = np.empty((M, self.D)) if grad else None
+        rc = self.lib.gp_sparse_predict(self.h, dptr(Xs), M, int(bool(include_noise)), dptr(mean), dptr(var),
+                                        dptr(dm) if grad else None, dptr(dv) if grad else None)
+        check(self.lib, rc, "gp_sparse_predict")
+        return (mean, var, dm, dv) if grad else (mean, var)
+
+    def sparse_fmin(self):
+        v = ctypes.c_double()
+        check(self.lib, self.lib.gp_sparse_fmin(self.h, ctypes.byref(v)), "gp_sparse_fmin")
+        return v.value
 
     def predict(self, include_noise=True):
         mean = np.empty((self.M, self.P))

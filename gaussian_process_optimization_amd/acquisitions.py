@@ -126,8 +126,11 @@ class AcquisitionBase(object):
 
     # ---- device route ----------------------------------------------------------------------------------------------
     def _device_ok(self):
-        """True when libgphip can score this acquisition by itself: our GPModel, one output, unit cost, no constraints."""
+        """True when libgphip can score this acquisition by itself: our exact GPModel, one output, unit cost, no constraints.
+        (The device entries score the exact posterior: a sparse model takes the host rule over its own predictions.)"""
         if self._rule is None or not isinstance(self.model, GPModel) or self.model.model is None:
+            return False
+        if getattr(self.model, "sparse", False):
             return False
         if self.cost_withGradients is not constant_cost_withGradients:
             return False

@@ -516,6 +516,7 @@ extern "C" int gp_set_data(gp_t *g, const double *X, const double *Y, int64_t N,
         g->capN = capN;
         g->capP = capP;
     }
+    if (D != g->D) g->sp.Mz = 0;   // inducing inputs of another dimension are no inducing inputs of this data
     g->N = N;
     g->Npad = Npad;
     g->D = D;
@@ -529,6 +530,7 @@ extern "C" int gp_set_data(gp_t *g, const double *X, const double *Y, int64_t N,
     GP_SYNC(g->s);
     g->have_data = true;
     fit_dropped(g);
+    sparse_fit_dropped(g);
     g->kp.D = D;
     return 0;
 }
@@ -555,6 +557,7 @@ extern "C" int gp_set_gower(gp_t *g, int enable, const int *is_discrete, const d
         if (!is_discrete[d] && !(range[d] > 0.0)) return fail(GP_ERR_ARG, "range of dimension %d must be positive", d);
     }
     fit_dropped(g);
+    sparse_fit_dropped(g);
     return 0;
 }
 
@@ -574,6 +577,7 @@ extern "C" int gp_set_params(gp_t *g, int kernel, int ard, double variance, cons
     g->noise = noise;
     g->have_params = true;
     fit_dropped(g);
+    sparse_fit_dropped(g);
     return 0;
 }
 

@@ -162,6 +162,28 @@ struct DevBuf {
     }
 };
 
+// The sparse model (variational DTC over Mz inducing inputs, api_sparse.hip) on the context's X, Y, D, P, kernel parameters and
+// main stream: buffers and validity flag of its own -- nothing here is read or written by the exact model's entry points, and
+// the sparse entry points touch none of the exact model's buffers or flags.  n = Mzpad below.
+struct SparseState {
+    long Mz = 0, Mzpad = 0;    // inducing inputs set (gp_sparse_set_inducing): Mz > 0
+    bool fitted = false;       // the buffers below hold the fit of the current data, parameters and inducing inputs
+    bool grad_ready = false;   // ... and dWt / dDKmm hold the gradient weights of that fit
+    double lml = 0.0, jitter_kmm = 0.0, jitter_b = 0.0, beta = 0.0, dnoise = 0.0;
+    DevBuf<double> dZ;         // [Mz, D]
+    DevBuf<double> dKmm;       // (n + 128) x n: Kmm -> Lm (lower) with one zero RHS tile row below
+    DevBuf<double> dBm;        // (n + 128) x n: B -> LB
+    DevBuf<double> dInvT;      // 2 x n x 128: inverted diagonal tiles of Lm, then of LB
+    DevBuf<double> dLmiT, dLmi, dLbiT, dLbi;   // n x n: Lm^-T, Lm^-1, LB^-T, LB^-1
+    DevBuf<double> dVVt, dDm, dE, dWinv, dDKmm, dTmp, dTmp2;   // n x n: V V^T, DBi_plus_BiPBi, dL_dpsi2_beta, woodbury_inv, dL_dKmm, scratch
+    DevBuf<double> dKfu, dV, dWt;        // Npad x n, n x Npad, Npad x n: K(X, Z), Lm^-1 Kuf, Kfu E
+    DevBuf<double> dVec;       // 4 x capP x n: V Y, LBi Lmi psi1 Vf, LB^-T of it, the woodbury vector (rows of n per output)
+    DevBuf<double> dPartial;   // the gradient pass's slabs
+    DevBuf<double> dOut;       // scalars, hyper-parameter sums, dZ of both parts, training mean
+    DevBuf<int> dInfo;         // 4 status words of the factorisation in progress
+    DevBuf<double> dXs, dKx, dBt, dPred;   // prediction: candidates, K(Xs, Z) and Kx woodbury_inv per chunk, results
+};
+
 struct gp_ctx {
     int device = 0;
     hipStream_t s = nullptr;       // main stream
@@ -308,6 +330,7 @@ struct gp_ctx {
     DevBuf<double> dYraw;  // N: the raw targets of a warped model
     double warp_logjac = 0.0;   // sum log f'(y) of the warp in force
     DevBuf<double> dWarp;  // 9 M: posterior by value (mean, var), then warped mean, variance, median and the four partials
+    SparseState sp;     // the sparse model (api_sparse.hip)
     bool dead = false;  // gp_shutdown ran: the device's streams are gone, only gp_destroy is still valid
 };
 
@@ -327,6 +350,9 @@ static inline void fit_dropped(gp_ctx *g) {
     g->fitted = false;
     g->fmin_valid = false;
 }
+
+// the sparse fit no longer belongs to the data / parameters / inducing inputs in force
+static inline void sparse_fit_dropped(gp_ctx *g) { g->sp.fitted = g->sp.grad_ready = false; }
 
 static inline long round_up(long x, long m) { return (x + m - 1) / m * m; }
 
@@ -500,4 +526,6 @@ void grads_from_sums(const double *h, const KernParams &kp, int ard, double *dva
 int lml_grad_impl(gp_ctx *g, double *dvariance, double *dlengthscale, double *dnoise, bool reset_phases, double *dL_dX = nullptr);
 int ensure_grad_buffers(gp_ctx *g, long elemsBeta, long M);
 int run_predict_grad(gp_ctx *g);
+void panel_inv_steps(gp_ctx *g, hipStream_t s, double *Wb, long PB, const double *Lb, long lda, const double *Ib, int Wp, GemmOpt o,
+                     long sL, long sI);   // api_solve.hip: Wb (the identity on entry) <- L^-T of the Wp-tile lower factor at Lb
 int warp_apply(gp_ctx *g, bool raw_in_dY);   // api_warp.hip: (dYraw <- dY when dY holds raw targets,) dY <- f(dYraw), warp_logjac; enqueued on g->s, the caller drains

@@ -13,8 +13,8 @@
 
 // The solve itself, for diagonal panels of Wp tiles: Wb (PB x PB blocks, the identity on entry) becomes L_JJ^-T.  `o` carries
 // the launch's batch and the strides of Wb; sL / sI are those of the panel of L at Lb and of its inverted diagonal tiles at Ib.
-static void panel_inv_steps(gp_ctx *g, hipStream_t s, double *Wb, long PB, const double *Lb, long lda, const double *Ib, int Wp,
-                            GemmOpt o, long sL, long sI) {
+void panel_inv_steps(gp_ctx *g, hipStream_t s, double *Wb, long PB, const double *Lb, long lda, const double *Ib, int Wp, GemmOpt o,
+                     long sL, long sI) {
     for (int b = 0; b < Wp; ++b) {
         o.inplace = 1;
         o.sB = sI;

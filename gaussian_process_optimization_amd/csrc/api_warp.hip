@@ -50,6 +50,7 @@ extern "C" int gp_set_output_warp(gp_t *g, int n_terms, const double *psi, doubl
             g->warp = w;
             g->warp_logjac = 0.0;
             fit_dropped(g);
+            sparse_fit_dropped(g);
         }
         if (log_jacobian) *log_jacobian = 0.0;
         return 0;
@@ -61,6 +62,7 @@ extern "C" int gp_set_output_warp(gp_t *g, int n_terms, const double *psi, doubl
         return rc;
     }
     fit_dropped(g);
+    sparse_fit_dropped(g);
     GP_SYNC(g->s);
     if (log_jacobian) *log_jacobian = g->warp_logjac;
     return 0;

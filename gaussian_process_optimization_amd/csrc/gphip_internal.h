@@ -326,6 +326,32 @@ void launch_gradx(hipStream_t s, const double *X, long N, long Npad, const KernP
 void launch_kumar_warp(hipStream_t s, double *Xs, long m0, long mc, int D, const int *warp, const double *a, const double *b,
                        const double *xmin, const double *xmax);
 
+// ---- sparse.hip: kernels of the sparse GP (variational DTC) -------------------------------------------------------------------
+#define GP_SPARSE_GRAD_MAX_P 16               // outputs whose woodbury-vector row stays in the gradient lane's registers
+#define GP_SPARSE_NH (1 + GP_GRAD_CH)         // hyper-parameter sums per pass of GP_GRAD_CH dimensions: sum W k, then sum W g d_q^2
+// One pass per GP_GRAD_CH dimensions over the Nc x Mz block of weights W[n, m] = wscale Wt[n ldw + m] + ybeta sum_p Y[n, p] C[p ldc + m]
+// (P = 0: no y term) between the rows Z [Mz, D] and the columns Xc [Nc, D]:
+//   dZ[m, q]                  = zfac / l_q sum_n W g(r) d_q,   d_q = (z_mq - x_nq) / l_q
+//   hyper[pass GP_SPARSE_NH]     = sum_nm W k;   hyper[pass GP_SPARSE_NH + 1 + q] = sum_nm W g(r) d_q^2   (q = dimension - pass GP_GRAD_CH)
+// partial: sparse_grad_partial_elems(Mzpad, Nc) doubles of scratch; Wt has at least Nc rows of ldw >= Mzpad entries
+long sparse_grad_partial_elems(long Mzpad, long Nc);
+void launch_sparse_grad(hipStream_t s, const double *Z, long Mz, long Mzpad, const double *Xc, long Nc, const KernParams &kp,
+                        const double *Y, int P, const double *C, long ldc, double ybeta, const double *Wt, long ldw, double wscale,
+                        double *partial, double zfac, double *dZ, double *hyper);
+// n x n helpers (leading dimension n): out = a X + b Y + c I (Y may be null);  out = c I + sum_p v_p v_p^T, v_p = V + p ldv
+void launch_sparse_lincomb(hipStream_t s, double *out, const double *X, double a, const double *Y, double b, double c, long n);
+void launch_sparse_outer(hipStream_t s, double *out, const double *V, long ldv, int P, double c, long n);
+// out[p ldo + i] = scale sum_{k < K} M[i ldm + k] v[p vsp + k vsk],  i < rows, p < P
+void launch_sparse_thin(hipStream_t s, const double *M, long ldm, long rows, long K, const double *v, long vsp, long vsk, int P,
+                        double scale, double *out, long ldo);
+// out[0] = sum Y^2 (NP entries), out[1] = trace VVt (Mz), out[2] = sum c1^2 (P rows of n), out[3] = sum VVt o Dm (n x n)
+void launch_sparse_scalars(hipStream_t s, const double *Y, long NP, const double *VVt, const double *Dm, long Mz, long n, const double *c1,
+                           int P, double *out);
+// mean[c, p] = sum_m Kx[c, m] w[p ldw + m];  var[c] = max(kss - sum_m Bt[c, m] Kx[c, m], 1e-15) + noise_add,  c < M, m < Mz
+void launch_sparse_predict_reduce(hipStream_t s, const double *Kx, const double *Bt, long ld, long M, long Mz, const double *w, long ldw,
+                                  int P, double kss, double noise_add, double *mean, double *var);
+void launch_sparse_min(hipStream_t s, const double *v, long n, double *out);
+
 // ---- rns.hip: fp64-equivalent contraction on the int8 matrix cores (option "emulate_fp64") -----------------------------
 #define GP_RNS_T 14
 #define GP_RNS_KMAX 8192   // longest contraction (bytes) one residue launch may take: see rns_reduce_f in rns.hip

@@ -1,4 +1,4 @@
-"""``GPModel`` -- host mirror of ``GPyOpt.models.GPModel`` on top of the HIP ``GPRegression``.
+"""``GPModel`` -- host mirror of ``GPyOpt.models.GPModel`` on top of the HIP ``GPRegression`` / ``SparseGPRegression``.
 
 Reference: GPyOpt/GPyOpt/models/base.py:7-33 (BOModel contract),
 GPyOpt/GPyOpt/models/gpmodel.py:9-177 (GPModel).  Same constructor keywords, same
@@ -11,6 +11,7 @@ import numpy as np
 
 from . import kern as _kern
 from .gp_regression import GPRegression
+from .sparse_gp import SparseGPRegression
 
 
 _VAR_FLOOR = 1e-10      # the reference clips predictive variances here before taking the root (gpmodel.py:99)
@@ -35,16 +36,21 @@ class BOModel(object):
 
 
 class GPModel(BOModel):
-    """Exact GP surrogate on the device.  Keyword arguments, attributes and return conventions are GPyOpt's
+    """GP surrogate on the device: exact, or with ``sparse=True`` variational DTC over ``num_inducing`` inducing inputs
+    (``SparseGPRegression``, gpmodel.py:66-71).  Keyword arguments, attributes and return conventions are GPyOpt's
     (gpmodel.py:9-177); ``device`` (HIP ordinal) and ``parallel_restarts`` (the restarts in lockstep,
-    GPRegression.optimize_restarts(parallel=True); default False) are the additions."""
+    GPRegression.optimize_restarts(parallel=True); default False, exact model only) are the additions.  A sparse model is
+    scored by the acquisitions through ``predict`` / ``predict_withGradients`` (the device acquisition entries are the exact
+    model's)."""
     analytical_gradient_prediction = True
 
     def __init__(self, kernel=None, noise_var=None, exact_feval=False, optimizer='bfgs', max_iters=1000,
                  optimize_restarts=5, sparse=False, num_inducing=10, verbose=True, ARD=False, Gower=False,
                  space=None, device=0, parallel_restarts=False):
-        if sparse:
-            raise NotImplementedError("sparse GP is a different model family (out of scope)")
+        if sparse and parallel_restarts:
+            raise ValueError("parallel_restarts runs the exact model's batched restarts: not available with sparse=True")
+        if sparse and Gower and space is not None:
+            raise NotImplementedError("the sparse GP does not take the Gower kernel")
         vars(self).update(kernel=kernel, noise_var=noise_var, exact_feval=exact_feval, optimizer=optimizer,
                           max_iters=max_iters, optimize_restarts=optimize_restarts, sparse=sparse,
                           num_inducing=num_inducing, verbose=verbose, ARD=ARD, Gower=Gower, space=space, device=device,
@@ -64,8 +70,11 @@ class GPModel(BOModel):
         chosen, self.kernel = self.kernel, None      # a user kernel is consumed by the first model, as in the reference
         if chosen is None:
             chosen = _kern.Matern52(self.input_dim, variance=1., ARD=self.ARD, Gower=self.Gower, space=self.space)
-        noise = 0.01 * Y.var() if self.noise_var is None else self.noise_var
-        gp = GPRegression(X, Y, kernel=chosen, noise_var=noise, device=self.device)
+        if self.sparse:     # noise_var is not passed on: the likelihood starts at 1 (gpmodel.py:69-71)
+            gp = SparseGPRegression(X, Y, kernel=chosen, num_inducing=self.num_inducing, device=self.device)
+        else:
+            noise = 0.01 * Y.var() if self.noise_var is None else self.noise_var
+            gp = GPRegression(X, Y, kernel=chosen, noise_var=noise, device=self.device)
         if self.exact_feval:
             gp.Gaussian_noise.constrain_fixed(1e-6, warning=False)
         else:
@@ -104,7 +113,7 @@ class GPModel(BOModel):
         """``self.model.predict(self.model.X)[0].min()`` (gpmodel.py:125-129), evaluated on the device and cached per fit."""
         gp = self.model
         gp._ensure_fit()
-        lowest = gp._h.fmin()
+        lowest = gp._h.sparse_fmin() if self.sparse else gp._h.fmin()
         if gp.normalizer is not None:
             lowest = float(gp.normalizer.inverse_mean(np.array([[lowest]]))[0, 0])
         return lowest
@@ -114,8 +123,12 @@ class GPModel(BOModel):
         un-normalised mean / variance."""
         X = np.atleast_2d(X)
         gp = self.model
-        few = gp._few_rows(X)
-        if few is not None:     # posterior and gradients of a handful of locations in ONE device call (gp_predict_rows)
+        few = None if self.sparse else gp._few_rows(X)
+        if self.sparse:         # posterior and gradients in ONE device call (gp_sparse_predict)
+            mean, var, jac_mean, jac_var = gp._sparse_predict(X, True, grad=True)
+            if gp.normalizer is not None:
+                mean, var = gp.normalizer.inverse_mean(mean), gp.normalizer.inverse_variance(var)
+        elif few is not None:   # posterior and gradients of a handful of locations in ONE device call (gp_predict_rows)
             mean, var, jac_mean, jac_var = gp._h.predict_rows(few, include_noise=True, grad=True)
             if gp.normalizer is not None:
                 mean, var = gp.normalizer.inverse_mean(mean), gp.normalizer.inverse_variance(var)
@@ -132,7 +145,7 @@ class GPModel(BOModel):
     def copy(self):
         twin = GPModel(kernel=self.model.kern.copy(), noise_var=self.noise_var, exact_feval=self.exact_feval,
                        optimizer=self.optimizer, max_iters=self.max_iters, optimize_restarts=self.optimize_restarts,
-                       verbose=self.verbose, ARD=self.ARD, Gower=self.Gower, space=self.space, device=self.device,
+                       sparse=self.sparse, num_inducing=self.num_inducing, verbose=self.verbose, ARD=self.ARD, Gower=self.Gower, space=self.space, device=self.device,
                        parallel_restarts=self.parallel_restarts)
         twin._create_model(self.model.X, self.model.Y)
         twin.updateModel(self.model.X, self.model.Y, None, None)

@@ -1,0 +1,215 @@
+"""``SparseGPRegression`` -- host mirror of ``GPy.models.SparseGPRegression`` backed by libgphip's sparse entry points.
+
+Reference: GPy/GPy/models/sparse_gp_regression.py:33-66 (constructor: default kernel RBF, default Z a random subset of X,
+Gaussian likelihood of variance 1), GPy/GPy/core/sparse_gp.py:41-119 (Z as the parameter linked at index 0, ``set_Z``,
+``parameters_changed`` / ``_update_gradients``), GPy/GPy/inference/latent_function_inference/var_dtc.py:66-277 (the inference),
+posterior.py:225-248 (prediction through ``woodbury_inv``), GPy/GPy/core/gp.py:407-454 (``predictive_gradients`` over
+``_predictive_variable = Z``).
+
+All numerics run on the device (include/gphip.h, "sparse GP"): ``gp_sparse_fit_grad`` once per objective evaluation,
+``gp_sparse_predict`` per prediction.  This module is bookkeeping: the flat parameter vector [Z row-major, kern.variance,
+kern.lengthscale, Gaussian_noise.variance] with Z unconstrained, the Y normaliser, lazy refits.  Homoscedastic noise, certain
+inputs, no mean function; ``full_cov`` and posterior sampling are outside this path.
+"""
+import numpy as np
+
+from . import kern as _kern
+from .gp_regression import GPRegression
+from .parameterization import Param
+
+MAX_INDUCING = 2048     # GP_SPARSE_MAX_INDUCING (include/gphip.h)
+
+
+class Identity(object):
+    """The transform of an unconstrained parameter."""
+
+    def f(self, x):
+        return np.asarray(x, dtype=float)
+
+    def finv(self, f):
+        return np.asarray(f, dtype=float)
+
+    def gradfactor(self, f, df):
+        return df
+
+
+class _SparsePosteriorView(object):
+    """The fields of GPy's Posterior a sparse model serves (posterior.py:9-270): woodbury_vector [Mz, P], woodbury_inv [Mz, Mz]."""
+
+    def __init__(self, model):
+        self._m = model
+
+    @property
+    def woodbury_vector(self):
+        self._m._ensure_fit()
+        return self._m._h.sparse_posterior()[0]
+
+    @property
+    def woodbury_inv(self):
+        self._m._ensure_fit()
+        return self._m._h.sparse_posterior()[1]
+
+
+class SparseGPRegression(GPRegression):
+    """Sparse GP regression by variational DTC over ``num_inducing`` inducing inputs, on one MI355X.
+
+    :param X: input observations [N, D]
+    :param Y: observed values [N, P]
+    :param kernel: one of the ``kern.Stationary`` classes (defaults to RBF, sparse_gp_regression.py:37-38)
+    :param Z: inducing inputs [Mz, D]; default ``X[np.random.permutation(N)[:min(num_inducing, N)]]`` (the global NumPy
+              generator, as the reference, :41-43)
+    :param normalizer: ``True`` standardises Y
+    :param device: HIP device ordinal
+
+    The Gaussian noise starts at 1.  ``Z`` is the parameter ``inducing_inputs``, first in the flat vector and unconstrained."""
+
+    def __init__(self, X, Y, kernel=None, Z=None, num_inducing=10, normalizer=None, device=0, name="sparse_gp"):
+        X = np.asarray(X, dtype=float)
+        if X.ndim == 1:
+            X = X.reshape(-1, 1)
+        if kernel is None:
+            kernel = _kern.RBF(X.shape[1])
+        if Z is None:
+            i = np.random.permutation(X.shape[0])[:min(num_inducing, X.shape[0])]
+            Z = X.view(np.ndarray)[i].copy()
+        else:
+            Z = np.array(Z, dtype=float)
+            assert Z.ndim == 2 and Z.shape[1] == X.shape[1]
+        if getattr(kernel, "Gower", False) and getattr(kernel, "space", None) is not None:
+            raise NotImplementedError("the sparse GP does not take the Gower kernel")
+        self.Z = None
+        super(SparseGPRegression, self).__init__(X, Y, kernel=kernel, normalizer=normalizer, noise_var=1., device=device, name=name)
+        self.posterior = _SparsePosteriorView(self)
+        self._link_Z(Z)
+
+    # -- the inducing inputs ------------------------------------------------------------
+    def _link_Z(self, Z):
+        Z = np.asarray(Z, dtype=float)
+        if Z.ndim != 2 or Z.shape[1] != self.input_dim:
+            raise ValueError("Z needs %d columns, got shape %s" % (self.input_dim, Z.shape))
+        if not (1 <= Z.shape[0] <= MAX_INDUCING):
+            raise ValueError("the number of inducing inputs must lie in 1..%d, got %d" % (MAX_INDUCING, Z.shape[0]))
+        self.Z = Param("inducing_inputs", Z, Identity())
+        self.Z._parent = self
+        self.num_inducing = Z.shape[0]
+        self._dirty = True
+
+    def set_Z(self, Z, trigger_update=True):
+        """sparse_gp.py:69-74: a new set of inducing inputs (their number may change)."""
+        self._link_Z(Z)
+
+    @property
+    def Z_values(self):
+        """The inducing inputs as an [Mz, D] array."""
+        return self.Z.values.reshape(self.num_inducing, self.input_dim)
+
+    @property
+    def _predictive_variable(self):
+        return self.Z_values
+
+    def flattened_parameters(self):
+        """Z is linked at index 0 (sparse_gp.py:59): [Z, kern.variance, kern.lengthscale, Gaussian_noise.variance]."""
+        rest = super(SparseGPRegression, self).flattened_parameters()
+        return rest if self.Z is None else [self.Z] + rest
+
+    def parameter_names_flat(self):
+        names = super(SparseGPRegression, self).parameter_names_flat()
+        if self.Z is None:
+            return names
+        own = ["%s.%s[[%d]]" % (self.name, self.Z.name, i) for i in range(self.Z.size)]
+        return np.array(own + list(names))
+
+    # -- (re)fit ------------------------------------------------------------------------
+    def _push_params(self):
+        k = self.kern
+        if k.Gower and k.space is not None:
+            raise NotImplementedError("the sparse GP does not take the Gower kernel")
+        self._h.set_gower()
+        self._h.set_params(k._kernel_id, k.ARD, float(k.variance), k.lengthscale.values, float(self.likelihood.variance))
+        self._h.sparse_set_inducing(self.Z_values)
+
+    def _ensure_fit(self):
+        """SparseGP.parameters_changed (sparse_gp.py:76-81): inference on the device when anything changed."""
+        if not self._dirty:
+            return
+        self._push_params()
+        self._lml, self._jitter, self._jitter_b = self._h.sparse_fit(self.max_jitter_tries)
+        self._logdet = None
+        self._dirty = False
+
+    def _log_likelihood_gradients_natural(self):
+        """One gp_sparse_fit_grad per evaluation: the LML of this parameter vector is left behind for ``objective_function``."""
+        nls = self.kern.lengthscale.size
+        self._push_params()
+        self._lml, (dv, dl, dn, dZ) = self._h.sparse_fit_grad(nls, self.max_jitter_tries)
+        self._dirty = False
+        self.Z.gradient = dZ.reshape(-1)
+        self.kern.variance.gradient = np.atleast_1d(dv)
+        self.kern.lengthscale.gradient = dl
+        self.likelihood.variance.gradient = np.atleast_1d(dn)
+        return [(self.Z, dZ.reshape(-1)), (self.kern.variance, dv), (self.kern.lengthscale, dl), (self.likelihood.variance, dn)]
+
+    def _uses_gower(self):
+        return False
+
+    def _lockstep_applies(self, num_restarts):
+        return False      # the batched restart entry is the exact model's: the serial loop runs
+
+    def _device_group(self, devices):
+        raise NotImplementedError("replica groups score the exact GP: outside the sparse path")
+
+    # -- prediction ---------------------------------------------------------------------
+    def _sparse_predict(self, Xnew, include_noise, grad=False):
+        Xnew = np.asarray(Xnew, dtype=float)
+        if Xnew.ndim == 1:
+            Xnew = Xnew[None, :]
+        if Xnew.shape[1] != self.input_dim:
+            raise ValueError("candidates have %d columns, model has %d" % (Xnew.shape[1], self.input_dim))
+        self._ensure_fit()
+        return self._h.sparse_predict(Xnew, include_noise=include_noise, grad=grad)
+
+    def _raw_predict(self, Xnew, full_cov=False, kern=None):
+        """posterior.py:225-248 over the inducing inputs."""
+        if full_cov:
+            raise NotImplementedError("full_cov is outside the sparse path")
+        if kern is not None and kern is not self.kern:
+            raise NotImplementedError("prediction with a foreign kernel is outside the accelerated path")
+        e = self._empty(Xnew, False)
+        if e is not None:
+            return e
+        return self._sparse_predict(Xnew, False)
+
+    def predict(self, Xnew, full_cov=False, Y_metadata=None, kern=None, likelihood=None, include_likelihood=True):
+        """gp.py:297-354 on the sparse posterior; ``full_cov`` is not served."""
+        if full_cov:
+            raise NotImplementedError("full_cov is outside the sparse path")
+        if kern is not None and kern is not self.kern:
+            raise NotImplementedError("prediction with a foreign kernel is outside the accelerated path")
+        e = self._empty(Xnew, False)
+        if e is not None:
+            return e
+        mean, var = self._sparse_predict(Xnew, include_likelihood)
+        if self.normalizer is not None:
+            mean, var = self.normalizer.inverse_mean(mean), self.normalizer.inverse_variance(var)
+        return mean, var
+
+    def predictive_gradients(self, Xnew, kern=None):
+        """gp.py:407-454 over ``_predictive_variable = Z``: (dmu_dX [M, D, P], dv_dX [M, D])."""
+        Xn = np.asarray(Xnew, dtype=float)
+        if Xn.ndim == 2 and Xn.shape[0] == 0:
+            return np.empty((0, self.input_dim, self.output_dim)), np.empty((0, self.input_dim))
+        return self._sparse_predict(Xnew, False, grad=True)[2:]
+
+    def mean_gradients(self, Xnew):
+        return self.predictive_gradients(Xnew)[0]
+
+    def get_fmin(self):
+        """min over the training inputs of the posterior mean, first output (gp_sparse_fmin), in the normalised space."""
+        self._ensure_fit()
+        return self._h.sparse_fmin()
+
+    def posterior_covariance_between_points(self, X1, X2):
+        raise NotImplementedError("full covariances are outside the sparse path")
+
+    def posterior_samples_f(self, X, size=10, normals=None, **kw):
+        raise NotImplementedError("posterior sampling is outside the sparse path")

@@ -437,6 +437,47 @@ int gp_group_acq_topk(gp_group_t *grp, int type, double par, double fmin, double
 int gp_merge_best(int n, const double *vals, const int64_t *idxs, int sense, int64_t *idx, double *val);
 int gp_merge_topk(int n, const double *vals, const int64_t *idxs, int sense, int k, int64_t *idx, double *val);
 
+/* ---- sparse GP (variational DTC) -------------------------------------------
+ * GPy.models.SparseGPRegression (GPy/GPy/models/sparse_gp_regression.py:33-66) behind GPyOpt's GPModel(sparse=True)
+ * (GPyOpt/GPyOpt/models/gpmodel.py:66-71): VarDTC inference over Mz inducing inputs Z, O(N Mz^2) instead of O(N^3).
+ * Homoscedastic Gaussian noise, certain inputs, no mean function.  The sparse model lives on the same gp_t: it uses the
+ * context's X, Y, kernel and parameters (gp_set_data, gp_set_params) and keeps buffers and a validity flag of its own.  No
+ * sparse call reads or writes the exact model's state (factor, inverse factor, alpha, the resident candidates and their
+ * results, the cached fmin): gp_fit / gp_predict after any sequence of sparse calls return the bits a fresh context returns.
+ * Always true fp64 ("emulate_fp64" does not apply).  GP_ERR_STATE: no data or no parameters, the Gower option on, an output
+ * warp on, fit before gp_sparse_set_inducing, the other calls before a sparse fit.  The batched restarts, the sharded and
+ * group entries, gp_acq* / gp_*_rows and the full covariance stay exact-GP only. */
+#define GP_SPARSE_MAX_INDUCING 2048
+/* The inducing inputs Z [Mz, D], row-major (SparseGP.__init__ / set_Z, GPy/GPy/core/sparse_gp.py:53,69-74).  Drops the sparse
+ * fit.  Z survives gp_set_params and a gp_set_data of the same D (which drop the sparse fit only); a gp_set_data with another
+ * D drops Z as well.  GP_ERR_ARG: Mz outside 1..GP_SPARSE_MAX_INDUCING. */
+int gp_sparse_set_inducing(gp_t *gp, const double *Z, int64_t Mz);
+/* VarDTC.inference (var_dtc.py:66-216) with _compute_log_marginal_likelihood (:266-277): beta = 1 / max(noise, 1e-8), Kmm =
+ * K(Z) + 1e-8 I, Lm = jitchol(Kmm), B = I + beta Lm^-1 Kuf Kfu Lm^-T, LB = jitchol(B) (linalg.py:56-81; the jitter each ladder
+ * ended with in *jitter_kmm / *jitter_b, 0 when the first attempt succeeded; a failed ladder reports as gp_fit does).  Out
+ * pointers may be NULL. */
+int gp_sparse_fit(gp_t *gp, int maxtries, double *lml, double *jitter_kmm, double *jitter_b);
+/* gp_sparse_fit and the gradients of its LML, one call per L-BFGS evaluation (SparseGP.parameters_changed and
+ * _update_gradients, sparse_gp.py:76-119, over _compute_dL_dpsi / _compute_dL_dR, var_dtc.py:218-264):
+ * dvariance, dlengthscale [1, or D with ard] = update_gradients_diag + update_gradients_full(dL_dKnm, X, Z) +
+ * update_gradients_full(dL_dKmm, Z); dnoise = dL_dR, the derivative with respect to the noise variance by the reference's
+ * formula also where the 1e-8 clamp is active; dZ [Mz, D] = gradients_X(dL_dKmm, Z) + gradients_X(dL_dKnm^T, Z, X).
+ * The same inputs give the same bits on every call.  GP_ERR_ARG: P > 16. */
+int gp_sparse_fit_grad(gp_t *gp, int maxtries, double *lml, double *dvariance, double *dlengthscale, double *dnoise, double *dZ);
+/* Posterior.woodbury_vector [Mz, P] (Cpsi1Vf, var_dtc.py:142,199) and woodbury_inv [Mz, Mz] = Lm^-T (I - B^-1) Lm^-1
+ * (var_dtc.py:209-212) of the sparse fit; either may be NULL. */
+int gp_sparse_posterior(gp_t *gp, double *woodbury_vector, double *woodbury_inv);
+/* Posterior._raw_predict (posterior.py:225-248) at Xs [M, D], given by value: mean [M, P] = Kx w, var [M] = k** - diag(Kx
+ * woodbury_inv Kx^T) clipped below at 1e-15, then + noise with include_noise (gaussian.py:102-110).  dmdx [M, D, P] and dvdx
+ * [M, D] (either may be NULL): GP.predictive_gradients over _predictive_variable = Z (gp.py:407-454); the gradients are not
+ * clipped.  Candidates go in chunks of "mc_max" rows.  A row's results do not depend on the rows it is predicted with (table
+ * size, position, chunk): the same row gives the same bits in any table, and the same table the same bits on every call.  The
+ * exact model's resident candidate block (gp_set_candidates) is not touched. */
+int gp_sparse_predict(gp_t *gp, const double *Xs, int64_t M, int include_noise, double *mean, double *var, double *dmdx,
+                      double *dvdx);
+/* min over the training inputs of the sparse posterior mean Kfu w, first output column (GPModel.get_fmin, gpmodel.py:125-129) */
+int gp_sparse_fmin(gp_t *gp, double *fmin);
+
 /* ---- measurement ---------------------------------------------------------
  * Phase timings of the last gp_fit / gp_predict measured with HIP events on the
  * library's stream; names[i] is a static string, ms[i] milliseconds, flops[i] the
