@@ -79,6 +79,21 @@ SIGNATURES = [
     ("gp_sparse_predict", ctypes.c_int, [_vp, c_double_p, ctypes.c_int64, ctypes.c_int, c_double_p, c_double_p, c_double_p,
                                          c_double_p]),
     ("gp_sparse_fmin", ctypes.c_int, [_vp, c_double_p]),
+    ("gp_sparse_set_candidates", ctypes.c_int, [_vp, c_double_p, ctypes.c_int64]),
+    ("gp_sparse_acq", ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double,
+                                     ctypes.c_int, ctypes.c_int, c_double_p, ctypes.c_int, c_double_p, c_double_p, c_double_p,
+                                     c_double_p]),
+    ("gp_sparse_acq_argbest", ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double,
+                                             ctypes.c_double, ctypes.c_int, ctypes.c_int, c_double_p, ctypes.c_int, c_double_p,
+                                             c_double_p, ctypes.c_int, c_int64_p, ctypes.c_int, c_int64_p, c_double_p]),
+    ("gp_sparse_acq_topk", ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double,
+                                          ctypes.c_double, ctypes.c_int, ctypes.c_int, c_int64_p, c_double_p]),
+    # (void* for the pointers of the two rows entries, as for gp_predict_rows / gp_acq_rows below)
+    ("gp_sparse_predict_rows", ctypes.c_int, [_vp, _vp, ctypes.c_int64, ctypes.c_int, _vp, _vp, _vp, _vp]),
+    ("gp_sparse_acq_rows", ctypes.c_int, [_vp, _vp, ctypes.c_int64, ctypes.c_int, ctypes.c_double, ctypes.c_double,
+                                          ctypes.c_double, ctypes.c_double, ctypes.c_int, ctypes.c_int, _vp, ctypes.c_int,
+                                          _vp, _vp, _vp, _vp]),
+    ("gp_sparse_rows_stats", ctypes.c_int, [_vp, c_int64_p, c_int64_p]),
     ("gp_predict_full_cov", ctypes.c_int, [_vp, ctypes.c_int, c_double_p, c_double_p]),
     ("gp_predict_grad", ctypes.c_int, [_vp, c_double_p, c_double_p]),
     ("gp_fmin", ctypes.c_int, [_vp, c_double_p]),
@@ -223,6 +238,7 @@ class Handle(object):
         check(self.lib, self.lib.gp_create(ctypes.byref(h), int(device)), "gp_create")
         self.h = h
         self.device = int(device)
+        self.sparse_M = 0      # rows of the sparse model's candidate table (sparse_set_candidates); 0: the library refuses to score
 
     def close(self):
         if getattr(self, "h", None):
@@ -570,6 +586,97 @@ class Handle(object):
         v = ctypes.c_double()
         check(self.lib, self.lib.gp_sparse_fmin(self.h, ctypes.byref(v)), "gp_sparse_fmin")
         return v.value
+
+    # -- acquisitions over the sparse posterior (include/gphip.h): a table of the sparse model's own, and rows by value
+    def sparse_set_candidates(self, Xs):
+        Xs = as_f64(Xs, 2)
+        if Xs.shape[1] != self.D:
+            raise ValueError("candidates have %d columns, model has %d" % (Xs.shape[1], self.D))
+        check(self.lib, self.lib.gp_sparse_set_candidates(self.h, dptr(Xs), Xs.shape[0]), "gp_sparse_set_candidates")
+        self.sparse_M = Xs.shape[0]
+
+    @staticmethod
+    def _sparse_lp(lp):
+        """``lp`` = None or (transform, Xb, r_x0, s_x0) -> (on, transform, arrays kept alive, nb, pointers)."""
+        if lp is None:
+            return (0, 0) + _lp_args(None, None, None)
+        return (1, int(lp[0])) + _lp_args(lp[1], lp[2], lp[3])
+
+    def sparse_acq(self, type_, par, fmin, y_mean=0.0, y_std=1.0, grad=False, lp=None):
+        """Negated acquisition of the sparse table, [M, 1] (1-D with ``lp``, as AcquisitionLP returns it), and with ``grad`` its
+        gradient [M, D]: the return shapes of ``acq`` / ``acq_grad`` / ``acq_lp`` / ``acq_lp_grad``."""
+        on, tr, keep, nb, pX, pr, ps = self._sparse_lp(lp)
+        M = self.sparse_M
+        out = np.empty(M) if on else np.empty((M, 1))
+        dout = np.empty((M, self.D)) if grad else None
+        check(self.lib, self.lib.gp_sparse_acq(self.h, int(type_), float(par), float(fmin), float(y_mean), float(y_std), on, tr,
+                                               pX, nb, pr, ps, dptr(out), dptr(dout) if grad else None), "gp_sparse_acq")
+        return (out, dout) if grad else out
+
+    def sparse_acq_argbest(self, type_, par, fmin, sense, y_mean=0.0, y_std=1.0, lp=None, exclude=()):
+        on, tr, keep, nb, pX, pr, ps = self._sparse_lp(lp)
+        ex = np.asarray(list(exclude), dtype=np.int64)
+        idx, val = ctypes.c_int64(), ctypes.c_double()
+        check(self.lib, self.lib.gp_sparse_acq_argbest(self.h, int(type_), float(par), float(fmin), float(y_mean), float(y_std),
+                                                       on, tr, pX, nb, pr, ps, int(sense), ex.ctypes.data_as(c_int64_p),
+                                                       int(ex.size), ctypes.byref(idx), ctypes.byref(val)),
+              "gp_sparse_acq_argbest")
+        return idx.value, val.value
+
+    def sparse_acq_topk(self, type_, par, fmin, sense, k, y_mean=0.0, y_std=1.0):
+        idx = np.empty(k, dtype=np.int64)
+        val = np.empty(k)
+        check(self.lib, self.lib.gp_sparse_acq_topk(self.h, int(type_), float(par), float(fmin), float(y_mean), float(y_std),
+                                                    int(sense), int(k), idx.ctypes.data_as(c_int64_p), dptr(val)),
+              "gp_sparse_acq_topk")
+        return idx, val
+
+    def sparse_predict_rows(self, Xs, include_noise=True, grad=False):
+        """(mean [M, 1], var [M, 1]) and, with ``grad``, (dmdx [M, D, 1], dvdx [M, D]) as well: ``predict_rows`` on the sparse model."""
+        Xs = as_f64(Xs, 2)
+        M = Xs.shape[0]
+        mean, var = np.empty((M, 1)), np.empty((M, 1))
+        dm = np.empty((M, self.D, 1)) if grad else None
+        dv = np.empty((M, self.D)) if grad else None
+        rc = self.lib.gp_sparse_predict_rows(self.h, Xs.ctypes.data, M, 1 if include_noise else 0, mean.ctypes.data,
+                                             var.ctypes.data, dm.ctypes.data if grad else None, dv.ctypes.data if grad else None)
+        if rc:
+            check(self.lib, rc, "gp_sparse_predict_rows")
+        return (mean, var, dm, dv) if grad else (mean, var)
+
+    def sparse_mean_grad_rows(self, Xs):
+        """d mean / dx [M, D, 1] of a handful of locations, alone (the woodbury vector only)."""
+        Xs = as_f64(Xs, 2)
+        M = Xs.shape[0]
+        dm = np.empty((M, self.D, 1))
+        rc = self.lib.gp_sparse_predict_rows(self.h, Xs.ctypes.data, M, 0, None, None, dm.ctypes.data, None)
+        if rc:
+            check(self.lib, rc, "gp_sparse_predict_rows")
+        return dm
+
+    def sparse_acq_rows(self, Xs, type_, par, fmin, y_mean=0.0, y_std=1.0, grad=False, lp=None):
+        """``acq_rows`` on the sparse model: negated acquisition [M, 1] (1-D with ``lp``) and, with ``grad``, its gradient [M, D]."""
+        Xs = as_f64(Xs, 2)
+        M = Xs.shape[0]
+        out = np.empty(M) if lp is not None else np.empty((M, 1))
+        dout = np.empty((M, self.D)) if grad else None
+        on = tr = nb = 0
+        pX = pr = ps = keep = None
+        if lp is not None:
+            on, tr = 1, int(lp[0])
+            if lp[1] is not None:
+                keep = (as_f64(np.atleast_2d(lp[1]), 2), as_f64(np.atleast_1d(lp[2]), 1), as_f64(np.atleast_1d(lp[3]), 1))
+                nb, pX, pr, ps = keep[0].shape[0], keep[0].ctypes.data, keep[1].ctypes.data, keep[2].ctypes.data
+        rc = self.lib.gp_sparse_acq_rows(self.h, Xs.ctypes.data, M, int(type_), par, fmin, y_mean, y_std, on, tr, pX, nb, pr, ps,
+                                         out.ctypes.data, dout.ctypes.data if grad else None)
+        if rc:
+            check(self.lib, rc, "gp_sparse_acq_rows")
+        return (out, dout) if grad else out
+
+    def sparse_rows_stats(self):
+        a, b = ctypes.c_int64(), ctypes.c_int64()
+        check(self.lib, self.lib.gp_sparse_rows_stats(self.h, ctypes.byref(a), ctypes.byref(b)), "gp_sparse_rows_stats")
+        return dict(fused=a.value, fallback=b.value)
 
     def predict(self, include_noise=True):
         mean = np.empty((self.M, self.P))

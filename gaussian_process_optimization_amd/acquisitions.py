@@ -7,6 +7,8 @@ LP.py:10-140, GPyOpt/GPyOpt/core/evaluators/batch_local_penalization.py:7-70, GP
 Where the work runs.  With the HIP ``GPModel``, one output column, constant cost and no constraints, EVERY entry point goes to
 libgphip on the whole candidate block at once: values (``gp_acq``), values + x-gradients (``gp_acq_grad``), arg-best / top-k
 (``gp_acq_argbest`` / ``gp_acq_topk``), the penalised batch acquisition and its gradient (``gp_acq_lp`` / ``gp_acq_lp_grad``).
+A sparse ``GPModel`` built with ``device_acquisitions=True`` takes the same route through the sparse twins (``gp_sparse_acq``,
+``gp_sparse_acq_argbest`` / ``_topk``, ``gp_sparse_acq_rows``) over a candidate table of the sparse model's own.
 Anything else (a foreign ``BOModel``, a cost model, string constraints, several outputs) is scored by ``_Rule`` below from
 ``model.predict[_withGradients]``: each acquisition is one rule giving its value and its two partial derivatives with respect
 to the posterior mean and standard deviation, and every class shares the chain rule built on them.
@@ -139,6 +141,31 @@ class AcquisitionBase(object):
             return False
         return self.model.model.output_dim == 1
 
+    def _sparse_device_ok(self):
+        """True when libgphip scores this acquisition over the SPARSE posterior (gp_sparse_acq*): our GPModel with ``sparse=True``
+        and ``device_acquisitions=True``, one output, unit cost, no constraints."""
+        if self._rule is None or not isinstance(self.model, GPModel) or self.model.model is None:
+            return False
+        if not (getattr(self.model, "sparse", False) and getattr(self.model, "device_acquisitions", False)):
+            return False
+        if self.cost_withGradients is not constant_cost_withGradients:
+            return False
+        constrained = getattr(self.space, "has_constraints", None)
+        if constrained is not None and constrained():
+            return False
+        return self.model.model.output_dim == 1
+
+    def _sparse_stage(self, x, devices=None):
+        """Make ``x`` the sparse model's resident table (not uploaded again while it is the same table) and return what every
+        sparse scoring call takes: the handle owner, fmin and the normaliser's mean / std."""
+        gp = self.model.model
+        if devices is not None:
+            gp._device_group(devices)      # replica groups score the exact GP: NotImplementedError
+        gp._stage_table(np.atleast_2d(np.asarray(x, dtype=float)))
+        nz = gp.normalizer
+        shift, scale = (0.0, 1.0) if nz is None else (float(nz.mean[0]), float(nz.std[0]))
+        return gp, self._fmin(), shift, scale
+
     def _device_stage(self, x):
         """Make ``x`` the resident candidate block (refitting first if data or hyper-parameters changed) and return what
         every device scoring call takes: the handle owner, fmin and the normaliser's mean / std."""
@@ -176,6 +203,13 @@ class AcquisitionBase(object):
                 return gp._h.acq_rows(x, self._acq_id, self._par(), fmin, shift, scale)
             gp, fmin, shift, scale = self._device_stage(x)
             return gp._h.acq(self._acq_id, self._par(), fmin, shift, scale)
+        if self._sparse_device_ok():
+            few = self._device_few(x)
+            if few is not None:
+                x, gp, fmin, shift, scale = few
+                return gp._h.sparse_acq_rows(x, self._acq_id, self._par(), fmin, shift, scale)
+            gp, fmin, shift, scale = self._sparse_stage(x)
+            return gp._h.sparse_acq(self._acq_id, self._par(), fmin, shift, scale)
         price, _ = self.cost_withGradients(x)
         return -(self._compute_acq(x) * self.space.indicator_constraints(x)) / price
 
@@ -188,6 +222,13 @@ class AcquisitionBase(object):
                 return gp._h.acq_rows(x, self._acq_id, self._par(), fmin, shift, scale, grad=True)
             gp, fmin, shift, scale = self._device_stage(x)
             return gp._h.acq_grad(self._acq_id, self._par(), fmin, shift, scale)
+        if self._sparse_device_ok():
+            few = self._device_few(x)
+            if few is not None:
+                x, gp, fmin, shift, scale = few
+                return gp._h.sparse_acq_rows(x, self._acq_id, self._par(), fmin, shift, scale, grad=True)
+            gp, fmin, shift, scale = self._sparse_stage(x)
+            return gp._h.sparse_acq(self._acq_id, self._par(), fmin, shift, scale, grad=True)
         val, dval = self._compute_acq_withGradients(x)
         price, dprice = self.cost_withGradients(x)
         feasible = self.space.indicator_constraints(x)
@@ -217,6 +258,9 @@ class AcquisitionBase(object):
                 return grp.acq_argbest(self._acq_id, self._par(), fmin, sense, shift, scale)
             gp, fmin, shift, scale = self._device_stage(x)
             return gp._h.acq_argbest(self._acq_id, self._par(), fmin, sense, shift, scale)
+        if self._sparse_device_ok():
+            gp, fmin, shift, scale = self._sparse_stage(x, devices)
+            return gp._h.sparse_acq_argbest(self._acq_id, self._par(), fmin, sense, shift, scale)
         return _pick(self.acquisition_function(x)[:, 0], sense)
 
     def topk(self, x, k, sense=-1, devices=None):
@@ -229,6 +273,9 @@ class AcquisitionBase(object):
                 return grp.acq_topk(self._acq_id, self._par(), fmin, sense, k, shift, scale)
             gp, fmin, shift, scale = self._device_stage(x)
             return gp._h.acq_topk(self._acq_id, self._par(), fmin, sense, k, shift, scale)
+        if self._sparse_device_ok() and k <= 64:
+            gp, fmin, shift, scale = self._sparse_stage(x, devices)
+            return gp._h.sparse_acq_topk(self._acq_id, self._par(), fmin, sense, k, shift, scale)
         scores = self.acquisition_function(x)[:, 0]
         ranked = np.argsort(scores if sense < 0 else -scores, kind="stable")[:k]
         idx = np.full(k, -1, dtype=np.int64)
@@ -387,6 +434,15 @@ class AcquisitionLP(AcquisitionBase):
         base = self.acq
         return base is not None and base.model is self.model and base._device_ok() and self.transform in ('none', 'softplus')
 
+    def _lp_sparse_ok(self):
+        base = self.acq
+        return (base is not None and base.model is self.model and base._sparse_device_ok()
+                and self.transform in ('none', 'softplus'))
+
+    def _lp_spec(self):
+        """(transform, Xb, r_x0, s_x0) of the batch in force, as the sparse entries take it."""
+        return (1 if self.transform == 'softplus' else 0, self.X_batch, self.r_x0, self.s_x0)
+
     def _lp_call(self, x):
         base = self.acq
         gp, fmin, shift, scale = base._device_stage(x)
@@ -394,8 +450,9 @@ class AcquisitionLP(AcquisitionBase):
         batch = dict(Xb=self.X_batch, r_x0=self.r_x0, s_x0=self.s_x0, y_mean=shift, y_std=scale)
         return gp._h, head, batch
 
-    def _lp_few(self, x, grad):
-        """ONE gp_acq_rows call for up to ``_FEW_ROWS`` locations (None otherwise): the L-BFGS runs of compute_batch."""
+    def _lp_few(self, x, grad, sparse=False):
+        """ONE gp_acq_rows call (gp_sparse_acq_rows with ``sparse``) for up to ``_FEW_ROWS`` locations (None otherwise): the
+        L-BFGS runs of compute_batch."""
         few = self.acq._device_few(x)
         if few is None:
             return None
@@ -412,7 +469,8 @@ class AcquisitionLP(AcquisitionBase):
                       np.ascontiguousarray(np.atleast_1d(self.r_x0), dtype=float),
                       np.ascontiguousarray(np.atleast_1d(self.s_x0), dtype=float))
             self._lp_packed = (src, lp)
-        return gp._h.acq_rows(x, self.acq._acq_id, self.acq._par(), fmin, shift, scale, grad=grad, lp=lp)
+        rows = gp._h.sparse_acq_rows if sparse else gp._h.acq_rows
+        return rows(x, self.acq._acq_id, self.acq._par(), fmin, shift, scale, grad=grad, lp=lp)
 
     def acquisition_function(self, x):
         """1-D array like the reference's (LP.py:105-110)."""
@@ -422,6 +480,13 @@ class AcquisitionLP(AcquisitionBase):
                 return few
             h, head, batch = self._lp_call(x)
             return h.acq_lp(*head, **batch)
+        if self._lp_sparse_ok():
+            few = self._lp_few(x, False, sparse=True)
+            if few is not None:
+                return few
+            base = self.acq
+            gp, fmin, shift, scale = base._sparse_stage(x)
+            return gp._h.sparse_acq(base._acq_id, base._par(), fmin, shift, scale, lp=self._lp_spec())
         return self._score_on_host(x)
 
     def d_acquisition_function(self, x):
@@ -436,6 +501,13 @@ class AcquisitionLP(AcquisitionBase):
                 return few
             h, head, batch = self._lp_call(x)
             return h.acq_lp_grad(*head, **batch)
+        if self._lp_sparse_ok():
+            few = self._lp_few(x, True, sparse=True)
+            if few is not None:
+                return few
+            base = self.acq
+            gp, fmin, shift, scale = base._sparse_stage(x)
+            return gp._h.sparse_acq(base._acq_id, base._par(), fmin, shift, scale, grad=True, lp=self._lp_spec())
         neg, dneg = self.acq.acquisition_function_withGradients(x)
         with np.errstate(over='ignore', divide='ignore'):
             _, slope = _log_transform(-neg[:, 0], self.transform)
@@ -456,6 +528,11 @@ class AcquisitionLP(AcquisitionBase):
                                           y_std=scale)
             h, head, batch = self._lp_call(x)
             return h.acq_lp_argbest(head[0], head[1], head[2], head[3], sense, exclude=exclude, **batch)
+        if self._lp_sparse_ok():
+            base = self.acq
+            gp, fmin, shift, scale = base._sparse_stage(x, devices)
+            return gp._h.sparse_acq_argbest(base._acq_id, base._par(), fmin, sense, shift, scale, lp=self._lp_spec(),
+                                            exclude=exclude)
         scores = np.array(self.acquisition_function(x), dtype=float)
         scores[list(exclude)] = -np.inf if sense > 0 else np.inf
         return _pick(scores, sense)

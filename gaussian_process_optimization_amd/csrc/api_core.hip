@@ -358,6 +358,7 @@ extern "C" int gp_destroy(gp_t *g) {
     hipDeviceSynchronize();
     if (g->comm) ncclCommDestroy(g->comm);
     if (g->hRowsOut) hipHostFree(g->hRowsOut);
+    if (g->sp.hRowsOut) hipHostFree(g->sp.hRowsOut);
     // events recorded on the shared streams go first; the streams themselves belong to the per-device set shared by
     // every context of the process and are destroyed by gp_shutdown / the exit hook
     destroy_ctx_events(g);
@@ -516,7 +517,7 @@ extern "C" int gp_set_data(gp_t *g, const double *X, const double *Y, int64_t N,
         g->capN = capN;
         g->capP = capP;
     }
-    if (D != g->D) g->sp.Mz = 0;   // inducing inputs of another dimension are no inducing inputs of this data
+    if (D != g->D) g->sp.Mz = g->sp.tM = 0;   // inducing inputs (and a sparse candidate table) of another dimension are none of this data
     g->N = N;
     g->Npad = Npad;
     g->D = D;

@@ -171,6 +171,10 @@ struct SparseState {
     bool grad_ready = false;   // ... and dWt / dDKmm hold the gradient weights of that fit
     double lml = 0.0, jitter_kmm = 0.0, jitter_b = 0.0, beta = 0.0, dnoise = 0.0;
     DevBuf<double> dZ;         // [Mz, D]
+    DevBuf<double> dZs;        // [Mz, D]: Z / lengthscale of the current fit, built by the first fused rows call after it (sparse_rows.hip)
+    bool zs_valid = false;     // dZs belongs to the current fit
+    bool fmin_valid = false;   // fmin is the minimum of the training mean under the current fit (gp_sparse_fmin computes it once per fit)
+    double fmin = 0.0;
     DevBuf<double> dKmm;       // (n + 128) x n: Kmm -> Lm (lower) with one zero RHS tile row below
     DevBuf<double> dBm;        // (n + 128) x n: B -> LB
     DevBuf<double> dInvT;      // 2 x n x 128: inverted diagonal tiles of Lm, then of LB
@@ -182,6 +186,22 @@ struct SparseState {
     DevBuf<double> dOut;       // scalars, hyper-parameter sums, dZ of both parts, training mean
     DevBuf<int> dInfo;         // 4 status words of the factorisation in progress
     DevBuf<double> dXs, dKx, dBt, dPred;   // prediction: candidates, K(Xs, Z) and Kx woodbury_inv per chunk, results
+    // the resident candidate table of the acquisition entries (gp_sparse_set_candidates) and its lazily cached posterior:
+    // buffers of their own, so that gp_sparse_predict and the rows entries between two scoring calls leave them alone
+    long tM = 0;               // rows of the table (0: none)
+    DevBuf<double> dTab;       // [tM, D]
+    DevBuf<double> dTabPost;   // mean [tM], var [tM] (noise included), dmdx [tM, D], dvdx [tM, D]
+    DevBuf<double> dTabAcq, dTabDacq;   // scores [tM] and their gradients [tM, D]
+    bool tab_post = false, tab_grad = false;   // dTabPost holds mean / var (and the gradients) of the table under the current fit
+    // the rows entries: scratch of the fallback (table arithmetic on a handful of rows: locations, posterior, scores) and the
+    // fused path's per-workgroup sums, arrival counter, pinned result block, ticket and counter base (as the exact model's)
+    DevBuf<double> dScrX, dScrPost, dScrAcq;
+    DevBuf<double> dRowsPart;
+    DevBuf<unsigned int> dRowsCounter;
+    double *hRowsOut = nullptr;
+    double rows_ticket = 0.0;
+    unsigned int rows_counter_base = 0;
+    long rows_fused_calls = 0, rows_fallback_calls = 0;
 };
 
 struct gp_ctx {
@@ -351,8 +371,9 @@ static inline void fit_dropped(gp_ctx *g) {
     g->fmin_valid = false;
 }
 
-// the sparse fit no longer belongs to the data / parameters / inducing inputs in force
-static inline void sparse_fit_dropped(gp_ctx *g) { g->sp.fitted = g->sp.grad_ready = false; }
+// the sparse fit no longer belongs to the data / parameters / inducing inputs in force, and neither does the cached posterior of
+// the sparse candidate table (the table itself stays, as Z does)
+static inline void sparse_fit_dropped(gp_ctx *g) { g->sp.fitted = g->sp.grad_ready = g->sp.tab_post = g->sp.tab_grad = g->sp.fmin_valid = g->sp.zs_valid = false; }
 
 static inline long round_up(long x, long m) { return (x + m - 1) / m * m; }
 
@@ -508,6 +529,7 @@ static inline LpBatch lp_slots(const gp_ctx *g) { return LpBatch{g->dLp + LP_X.o
 RowsAcq rows_acq(const AcqSpec &a, const LpSpec *lp, const LpBatch &b);   // the fused path's kernel argument (lp null: base only)
 int run_acq(gp_ctx *g, const AcqSpec &a);
 int upload_lp_batch(gp_ctx *g, const LpSpec &lp, LpBatch *b);
+int rows_lp_batch(gp_ctx *g, const LpSpec &lp, LpBatch *b);   // api_rows.hip: the same, skipped while dLp still holds this batch
 int run_acq_lp(gp_ctx *g, const AcqSpec &a, const LpSpec &lp);
 int acq_values(gp_ctx *g, const AcqSpec &a, const LpSpec *lp, double *out, double *dout);   // api_grad.hip
 // gp_acq_argbest / gp_acq_lp_argbest and gp_acq_topk over the specs, preamble included (lp null: no penaliser)

@@ -79,7 +79,7 @@ static int rows_wait(gp_ctx *g, RowsWork &w, unsigned finish_grid) {
 }
 
 // the penaliser's batch on the device; re-uploaded only when it changed (an L-BFGS run keeps one batch for hundreds of calls)
-static int rows_lp_batch(gp_ctx *g, const LpSpec &lp, LpBatch *b) {
+int rows_lp_batch(gp_ctx *g, const LpSpec &lp, LpBatch *b) {
     const int nb = lp.nb;
     const size_t nx = (size_t)nb * g->D;
     bool same = g->lp_cache_nb == nb && g->lp_cache.size() == nx + 2 * (size_t)nb && g->dLp;

@@ -301,6 +301,38 @@ extern "C" int gp_sparse_posterior(gp_t *g, double *woodbury_vector, double *woo
     return 0;
 }
 
+// Posterior._raw_predict (posterior.py:225-248) and GP.predictive_gradients (gp.py:407-454) over the M rows at dX (device, [M, D]):
+// mean [M, P], var [M] and, with grads, dmdx [M, D, P] and dvdx [M, D], all on the device.  THE arithmetic of every posterior the
+// sparse entries serve outside the fused rows path -- gp_sparse_predict, the resident table's cache, the rows entries' fallback --:
+// chunks of "mc_max" rows, one pinned GEMM instance, one reduce, so that a row has the same bits wherever it is predicted.
+static int sparse_posterior_rows(gp_ctx *g, const double *dX, long M, int include_noise, bool grads, double *dmean, double *dvar,
+                                 double *ddm, double *ddv) {
+    SparseState &sp = g->sp;
+    const long n = sp.Mzpad, Mz = sp.Mz;
+    const int P = g->P, D = g->D, ntz = (int)(n / GP_TILE);
+    const long mc_max = std::min(round_up(g->mc_max, GP_TILE), round_up(M, GP_TILE));
+    hipStream_t s = g->s;
+    int rc;
+    if ((rc = sp.dKx.reserve(mc_max * n))) return rc;
+    if ((rc = sp.dBt.reserve(mc_max * n))) return rc;
+    const double *wv = sp.dVec + 3L * P * n;
+    // the product with woodbury_inv always runs as 64 x 64 work units: ONE GEMM instance whatever the table's size, so that a
+    // row's posterior does not depend on the rows it is predicted with (include/gphip.h)
+    GemmOpt pinned;
+    pinned.small = 1;
+    for (long m0 = 0; m0 < M; m0 += mc_max) {
+        const long mc = std::min(mc_max, (long)M - m0), mcpad = round_up(mc, GP_TILE);
+        launch_cross_k(s, sp.dKx, n, dX + m0 * D, mc, mcpad, sp.dZ, Mz, n, g->kp);
+        // Bt = Kx woodbury_inv (woodbury_inv symmetric: its rows serve as the B operand)
+        launch_gemm_nt(s, 0, sp.dBt, n, sp.dKx, n, sp.dWinv, n, 1, (int)n, TileSet{0, (int)(mcpad / GP_TILE), 0, ntz, 0}, pinned);
+        launch_sparse_predict_reduce(s, sp.dKx, sp.dBt, n, mc, Mz, wv, n, P, g->kp.variance, include_noise ? g->noise : 0.0,
+                                     dmean + m0 * P, dvar + m0);
+        // gp.py:432-453 with _predictive_variable = Z: gradients_X(w_p^T, Xs, Z) and gradients_X(-2 Kx woodbury_inv, Xs, Z)
+        if (grads) launch_predict_grad(s, dX + m0 * D, mc, sp.dZ, Mz, g->kp, wv, n, P, sp.dBt, n, ddm + m0 * D * P, ddv + m0 * D);
+    }
+    return 0;
+}
+
 extern "C" int gp_sparse_predict(gp_t *g, const double *Xs, int64_t M, int include_noise, double *mean, double *var, double *dmdx,
                                  double *dvdx) {
     if (!g || !Xs || !mean || !var) return fail(GP_ERR_ARG, "null argument");
@@ -308,34 +340,16 @@ extern "C" int gp_sparse_predict(gp_t *g, const double *Xs, int64_t M, int inclu
     int rc;
     if ((rc = sparse_fitted(g))) return rc;
     SparseState &sp = g->sp;
-    const long n = sp.Mzpad, Mz = sp.Mz;
-    const int P = g->P, D = g->D, ntz = (int)(n / GP_TILE);
+    const int P = g->P, D = g->D;
     const bool grads = dmdx || dvdx;
-    const long mc_max = std::min(round_up(g->mc_max, GP_TILE), round_up(M, GP_TILE));
     hipStream_t s = g->s;
     if ((rc = sp.dXs.reserve(M * D))) return rc;
-    if ((rc = sp.dKx.reserve(mc_max * n))) return rc;
-    if ((rc = sp.dBt.reserve(mc_max * n))) return rc;
     if ((rc = sp.dPred.reserve(M * (P + 1 + (long)D * P + D)))) return rc;
     double *dmean = sp.dPred, *dvar = dmean + M * P, *ddm = dvar + M, *ddv = ddm + M * D * P;
-    const double *wv = sp.dVec + 3L * P * n;
     HIPCHK(hipMemcpyAsync(sp.dXs, Xs, sizeof(double) * M * D, hipMemcpyHostToDevice, s));
-    // the product with woodbury_inv always runs as 64 x 64 work units: ONE GEMM instance whatever the table's size, so that a
-    // row's posterior does not depend on the rows it is predicted with (include/gphip.h)
-    GemmOpt pinned;
-    pinned.small = 1;
     g->nphases = 0;
-    int ph = phase_begin(g, "sparse_predict", 2.0 * (double)M * Mz * Mz, 8.0 * (double)M * Mz);
-    for (long m0 = 0; m0 < M; m0 += mc_max) {
-        const long mc = std::min(mc_max, (long)M - m0), mcpad = round_up(mc, GP_TILE);
-        launch_cross_k(s, sp.dKx, n, sp.dXs + m0 * D, mc, mcpad, sp.dZ, Mz, n, g->kp);
-        // Bt = Kx woodbury_inv (woodbury_inv symmetric: its rows serve as the B operand)
-        launch_gemm_nt(s, 0, sp.dBt, n, sp.dKx, n, sp.dWinv, n, 1, (int)n, TileSet{0, (int)(mcpad / GP_TILE), 0, ntz, 0}, pinned);
-        launch_sparse_predict_reduce(s, sp.dKx, sp.dBt, n, mc, Mz, wv, n, P, g->kp.variance, include_noise ? g->noise : 0.0,
-                                     dmean + m0 * P, dvar + m0);
-        // gp.py:432-453 with _predictive_variable = Z: gradients_X(w_p^T, Xs, Z) and gradients_X(-2 Kx woodbury_inv, Xs, Z)
-        if (grads) launch_predict_grad(s, sp.dXs + m0 * D, mc, sp.dZ, Mz, g->kp, wv, n, P, sp.dBt, n, ddm + m0 * D * P, ddv + m0 * D);
-    }
+    int ph = phase_begin(g, "sparse_predict", 2.0 * (double)M * sp.Mz * sp.Mz, 8.0 * (double)M * sp.Mz);
+    if ((rc = sparse_posterior_rows(g, sp.dXs, M, include_noise, grads, dmean, dvar, ddm, ddv))) return rc;
     phase_end(g, ph);
     HIPCHK(hipMemcpyAsync(mean, dmean, sizeof(double) * M * P, hipMemcpyDeviceToHost, s));
     HIPCHK(hipMemcpyAsync(var, dvar, sizeof(double) * M, hipMemcpyDeviceToHost, s));
@@ -351,11 +365,321 @@ extern "C" int gp_sparse_fmin(gp_t *g, double *fmin) {
     if ((rc = sparse_fitted(g))) return rc;
     SparseState &sp = g->sp;
     const long n = sp.Mzpad, Mz = sp.Mz, N = g->N;
+    if (sp.fmin_valid) {   // cached per fit, as gp_fmin: the acquisitions ask for it with every call
+        *fmin = sp.fmin;
+        return 0;
+    }
     double *mu = sp.dOut + SPO_DZ + 2 * Mz * g->D;
     // the posterior mean at the training inputs, psi1 w (first output column), and its minimum (gpmodel.py:125-129)
     launch_sparse_thin(g->s, sp.dKfu, n, N, Mz, sp.dVec + 3L * g->P * n, n, 1, 1, 1.0, mu, N);
     launch_sparse_min(g->s, mu, N, sp.dOut + SPO_MIN);
-    HIPCHK(hipMemcpyAsync(fmin, sp.dOut + SPO_MIN, sizeof(double), hipMemcpyDeviceToHost, g->s));
+    HIPCHK(hipMemcpyAsync(&sp.fmin, sp.dOut + SPO_MIN, sizeof(double), hipMemcpyDeviceToHost, g->s));
     GP_SYNC(g->s);
+    sp.fmin_valid = true;
+    *fmin = sp.fmin;
+    return 0;
+}
+
+// ---- acquisitions over the sparse model's resident candidate table ----------------------------------------------------------------
+// gp_acq* of the exact model restated over the sparse posterior: the table lives in sp.dTab, its posterior (noise included, as
+// GPModel.predict asks, gpmodel.py:102) is cached in sp.dTabPost until the sparse fit is dropped, and the scoring, penalising,
+// masking and reducing launchers are the exact model's, on buffers of the sparse model's own.
+extern "C" int gp_sparse_set_candidates(gp_t *g, const double *Xs, int64_t M) {
+    if (!g || !Xs) return fail(GP_ERR_ARG, "null argument");
+    GP_DEAD_CHECK(g);
+    if (M < 1) return fail(GP_ERR_ARG, "M < 1");
+    if (!g->have_data) return fail(GP_ERR_STATE, "gp_set_data first");
+    HIPCHK(hipSetDevice(g->device));
+    GP_SYNC(g->s);
+    SparseState &sp = g->sp;
+    int rc;
+    if ((rc = sp.dTab.reserve(M * g->D))) return rc;
+    HIPCHK(hipMemcpy(sp.dTab, Xs, sizeof(double) * M * g->D, hipMemcpyHostToDevice));
+    sp.tM = M;
+    sp.tab_post = sp.tab_grad = false;
+    return 0;
+}
+
+// what every scoring entry asks first: a sparse fit, a single output, a known acquisition, a sound batch, a table
+static int sparse_scoring(gp_ctx *g, const AcqSpec &a, const LpSpec *lp) {
+    int rc;
+    if ((rc = sparse_fitted(g))) return rc;
+    if ((rc = check_acq(g, a))) return rc;
+    if (lp && (rc = check_lp(*lp))) return rc;
+    if (g->sp.tM < 1) return fail(GP_ERR_STATE, "gp_sparse_set_candidates first");
+    return 0;
+}
+
+// mean / var (and, with grads, the gradients) of the resident table in sp.dTabPost: the bits gp_sparse_predict(include_noise = 1)
+// returns for those rows
+static int sparse_table_posterior(gp_ctx *g, bool grads) {
+    SparseState &sp = g->sp;
+    if (sp.tab_post && (!grads || sp.tab_grad)) return 0;
+    const long M = sp.tM, D = g->D;
+    int rc;
+    if (sp.dTabPost.cap < M * (2 + 2 * D)) sp.tab_post = sp.tab_grad = false;   // (reserve does not keep the contents)
+    if ((rc = sp.dTabPost.reserve(M * (2 + 2 * D)))) return rc;
+    double *dmean = sp.dTabPost, *dvar = dmean + M, *ddm = dvar + M, *ddv = ddm + M * D;
+    if ((rc = sparse_posterior_rows(g, sp.dTab, M, 1, grads, dmean, dvar, ddm, ddv))) return rc;
+    sp.tab_post = true;
+    sp.tab_grad = sp.tab_grad || grads;
+    return 0;
+}
+
+// scores of `M` rows at dX from their posterior at post (layout of sp.dTabPost) into acq [M] (and dacq [M, D] with grad)
+static int sparse_scores(gp_ctx *g, const AcqSpec &a, const LpSpec *lp, bool grad, const double *dX, long M, const double *post,
+                         double *acq, double *dacq) {
+    const int D = g->D;
+    const double *dmean = post, *dvar = dmean + M, *ddm = dvar + M, *ddv = ddm + M * D;
+    int rc;
+    LpBatch b;
+    if (!grad) {
+        launch_acq(g->s, a.type, a.par, a.fmin, a.y_mean, a.y_std, dmean, dvar, M, acq);
+        if (lp) {
+            if ((rc = upload_lp_batch(g, *lp, &b))) return rc;   // (shared scratch: the upload resets the rows entries' batch cache)
+            launch_lp(g->s, acq, dX, M, D, b.X, lp->nb, b.r, b.s, lp->transform, acq);
+        }
+    } else {
+        launch_acq_grad(g->s, a.type, a.par, a.fmin, a.y_mean, a.y_std, dmean, dvar, ddm, ddv, M, D, acq, dacq);
+        if (lp) {
+            if ((rc = upload_lp_batch(g, *lp, &b))) return rc;
+            launch_lp_grad(g->s, acq, dacq, dX, M, D, b.X, lp->nb, b.r, b.s, lp->transform);
+        }
+    }
+    return 0;
+}
+
+static int sparse_table_scores(gp_ctx *g, const AcqSpec &a, const LpSpec *lp, bool grad) {
+    SparseState &sp = g->sp;
+    int rc;
+    if ((rc = sparse_table_posterior(g, grad))) return rc;
+    if ((rc = sp.dTabAcq.reserve(sp.tM))) return rc;
+    if (grad && (rc = sp.dTabDacq.reserve(sp.tM * g->D))) return rc;
+    return sparse_scores(g, a, lp, grad, sp.dTab, sp.tM, sp.dTabPost, sp.dTabAcq, sp.dTabDacq);
+}
+
+extern "C" int gp_sparse_acq(gp_t *g, int type, double par, double fmin, double y_mean, double y_std, int lp, int transform,
+                             const double *Xb, int nb, const double *r_x0, const double *s_x0, double *out, double *dout) {
+    if (!g || !out) return fail(GP_ERR_ARG, "null argument");
+    const AcqSpec a{type, par, fmin, y_mean, y_std};
+    const LpSpec batch{transform, Xb, nb, r_x0, s_x0}, *pen = lp ? &batch : nullptr;
+    int rc;
+    if ((rc = sparse_scoring(g, a, pen))) return rc;
+    if ((rc = sparse_table_scores(g, a, pen, dout != nullptr))) return rc;
+    SparseState &sp = g->sp;
+    HIPCHK(hipMemcpyAsync(out, sp.dTabAcq, sizeof(double) * sp.tM, hipMemcpyDeviceToHost, g->s));
+    if (dout) HIPCHK(hipMemcpyAsync(dout, sp.dTabDacq, sizeof(double) * sp.tM * g->D, hipMemcpyDeviceToHost, g->s));
+    GP_SYNC(g->s);
+    return 0;
+}
+
+static void sparse_argbest_launch(gp_ctx *g, int sense) {
+    launch_argbest(g->s, g->sp.dTabAcq, g->sp.tM, sense, g->dRedV + RED_RESULT.off, g->dRedI + RED_RESULT.off,
+                   g->dRedV + RED_PARTIAL.off, g->dRedI + RED_PARTIAL.off);
+}
+
+extern "C" int gp_sparse_acq_argbest(gp_t *g, int type, double par, double fmin, double y_mean, double y_std, int lp, int transform,
+                                     const double *Xb, int nb, const double *r_x0, const double *s_x0, int sense,
+                                     const int64_t *exclude, int nex, int64_t *idx, double *val) {
+    if (!g || !idx || !val) return fail(GP_ERR_ARG, "null argument");
+    const AcqSpec a{type, par, fmin, y_mean, y_std};
+    const LpSpec batch{transform, Xb, nb, r_x0, s_x0}, *pen = lp ? &batch : nullptr;
+    int rc;
+    if ((rc = sparse_scoring(g, a, pen))) return rc;
+    if ((rc = check_sense(sense))) return rc;
+    if ((rc = check_exclude(exclude, nex, g->sp.tM))) return rc;
+    if ((rc = sparse_table_scores(g, a, pen, false))) return rc;
+    if (nex > 0) {   // rows already taken (run.py:1249-1252 masks them)
+        long long *rows = g->dRedI + REDI_EXCLUDE.off;
+        HIPCHK(hipMemcpyAsync(rows, exclude, sizeof(long long) * nex, hipMemcpyHostToDevice, g->s));
+        launch_mask(g->s, g->sp.dTabAcq, rows, nex, acq_empty(sense));
+    }
+    sparse_argbest_launch(g, sense);
+    double hv = 0.0;
+    long long hi = 0;
+    HIPCHK(hipMemcpyAsync(&hv, g->dRedV + RED_RESULT.off, sizeof(double), hipMemcpyDeviceToHost, g->s));
+    HIPCHK(hipMemcpyAsync(&hi, g->dRedI + RED_RESULT.off, sizeof(long long), hipMemcpyDeviceToHost, g->s));
+    GP_SYNC(g->s);
+    *val = hv;
+    *idx = (int64_t)hi;
+    return 0;
+}
+
+// k rounds of the deterministic arg-best reduction, each followed by masking the winner (acq_topk of the exact model)
+extern "C" int gp_sparse_acq_topk(gp_t *g, int type, double par, double fmin, double y_mean, double y_std, int sense, int k,
+                                  int64_t *idx, double *val) {
+    if (!g || !idx || !val) return fail(GP_ERR_ARG, "null argument");
+    const AcqSpec a{type, par, fmin, y_mean, y_std};
+    int rc;
+    if ((rc = sparse_scoring(g, a, nullptr))) return rc;
+    if ((rc = check_sense(sense))) return rc;
+    if ((rc = check_k(k))) return rc;
+    if ((rc = sparse_table_scores(g, a, nullptr, false))) return rc;
+    if ((rc = g->dComm.reserve(COMM_CAP))) return rc;
+    double *dv = g->dComm + COMM_TOPK_VAL.off;
+    long long *di = (long long *)(g->dComm + COMM_TOPK_ROW.off);
+    const int kk = (int)std::min<long>(k, g->sp.tM);
+    for (int j = 0; j < kk; ++j) {
+        sparse_argbest_launch(g, sense);
+        HIPCHK(hipMemcpyAsync(dv + j, g->dRedV + RED_RESULT.off, 8, hipMemcpyDeviceToDevice, g->s));
+        HIPCHK(hipMemcpyAsync(di + j, g->dRedI + RED_RESULT.off, 8, hipMemcpyDeviceToDevice, g->s));
+        launch_mask(g->s, g->sp.dTabAcq, g->dRedI + RED_RESULT.off, 1, acq_empty(sense));
+    }
+    std::vector<long long> hi(kk);
+    HIPCHK(hipMemcpyAsync(val, dv, sizeof(double) * kk, hipMemcpyDeviceToHost, g->s));
+    HIPCHK(hipMemcpyAsync(hi.data(), di, sizeof(long long) * kk, hipMemcpyDeviceToHost, g->s));
+    GP_SYNC(g->s);
+    for (int j = 0; j < kk; ++j) idx[j] = (int64_t)hi[j];
+    for (int j = kk; j < k; ++j) {  // fewer candidates than k: the tail is marked empty
+        idx[j] = -1;
+        val[j] = acq_empty(sense);
+    }
+    return 0;
+}
+
+// ---- a handful of locations per call (csrc/sparse_rows.hip) -------------------------------------------------------------------------
+// fused path: up to min("small_m", ROWS_WIDE_M) locations of a single-output model; a pass takes as many of them as fit the kernel
+// arguments (M D <= ROWS_MAX_XS: all eight up to D = 16, two at D = GP_MAX_D).  A location's bits do not depend on the split.
+static bool sparse_rows_fused_ok(const gp_ctx *g, int64_t M) {
+    return g->small_m > 0 && M >= 1 && M <= std::min<long>(g->small_m, ROWS_WIDE_M) && g->P == 1;
+}
+
+static int sparse_rows_scratch(gp_ctx *g) {
+    SparseState &sp = g->sp;
+    int rc;
+    if ((rc = sp.dRowsPart.reserve((long)sparse_rows_grid(GP_SPARSE_MAX_INDUCING) * SPARSE_ROWS_GROW))) return rc;
+    if (!sp.dRowsCounter) {
+        if ((rc = sp.dRowsCounter.reserve(1))) return rc;
+        HIPCHK(hipMemsetAsync(sp.dRowsCounter, 0, sizeof(unsigned int), g->s));
+    }
+    if (!sp.zs_valid) {   // Z / lengthscale, once per fit and only for models that come here
+        if ((rc = sp.dZs.reserve(sp.Mz * g->D))) return rc;
+        launch_sparse_scale_z(g->s, sp.dZ, sp.Mz, g->kp, sp.dZs);
+        sp.zs_valid = true;
+    }
+    if (!sp.hRowsOut) {   // coherent host memory the finishing workgroup writes and the host reads after the sync
+        HIPCHK(hipHostMalloc((void **)&sp.hRowsOut, sizeof(double) * (ROWS_OUT_DOUBLES + 1), hipHostMallocDefault));
+        sp.hRowsOut[ROWS_OUT_DOUBLES] = 0.0;
+    }
+    return 0;
+}
+
+// One pass is on the stream: account for its arrivals, wait, and make sure it finished (rows_wait of api_rows.hip, on the sparse
+// model's own counter and block).
+static int sparse_rows_wait(gp_ctx *g, double ticket, unsigned arrivals) {
+    SparseState &sp = g->sp;
+    sp.rows_counter_base += arrivals;
+    hipError_t e = hipStreamSynchronize(g->s);
+    int pending = gp_pending_error();
+    if (!pending && e == hipSuccess && sp.hRowsOut[ROWS_OUT_DOUBLES] == ticket) return 0;
+    const std::string noted = pending ? gp_last_error() : std::string();
+    hipStreamSynchronize(g->s);
+    hipMemset(sp.dRowsCounter, 0, sizeof(unsigned int));
+    sp.rows_counter_base = 0;
+    if (pending) return fail(GP_ERR_HIP, "%s", noted.c_str());
+    if (e != hipSuccess) return fail(GP_ERR_HIP, "hipStreamSynchronize -> %s (sparse one-location pass)", hipGetErrorString(e));
+    return fail(GP_ERR_HIP, "the sparse one-location kernel did not complete (ticket %.0f, expected %.0f)", sp.hRowsOut[ROWS_OUT_DOUBLES],
+                ticket);
+}
+
+// mode as launch_sparse_rows.  Results: mean / var / acq [M], dmdx / dvdx / dacq [M, D] (any may be null).
+static int sparse_rows_fused(gp_ctx *g, const double *Xs, int M, int mode, int include_noise, const RowsAcq &aq, double *mean,
+                             double *var, double *acq, double *dmdx, double *dvdx, double *dacq) {
+    SparseState &sp = g->sp;
+    int rc;
+    if ((rc = sparse_rows_scratch(g))) return rc;
+    const int D = g->D, width = std::min(M, ROWS_MAX_XS / D), ML = ROWS_WIDE_M;
+    const double *wv = sp.dVec + 3L * g->P * sp.Mzpad;
+    for (int m0 = 0; m0 < M; m0 += width) {
+        const int mc = std::min(width, M - m0);
+        RowsX rx;
+        rx.M = mc;
+        memcpy(rx.xs, Xs + (long)m0 * D, sizeof(double) * mc * D);
+        const double ticket = (sp.rows_ticket += 1.0);
+        launch_sparse_rows(g->s, sp.dWinv, sp.Mzpad, sp.Mz, rx, g->kp, sp.dZs, wv, mode, g->kp.variance, include_noise ? g->noise : 0.0,
+                           aq, sp.dRowsPart, sp.dRowsCounter, sp.rows_counter_base, sp.hRowsOut, ticket);
+        if ((rc = sparse_rows_wait(g, ticket, sparse_rows_grid(sp.Mz)))) return rc;
+        const double *o = sp.hRowsOut;
+        for (int m = 0; m < mc; ++m) {
+            if (mean) mean[m0 + m] = o[m];
+            if (var) var[m0 + m] = o[ML + m];
+            if (acq) acq[m0 + m] = o[2 * ML + m];
+            const double *gm = o + 3 * ML + (long)m * D, *gv = gm + (long)ML * D, *ga = gv + (long)ML * D;
+            if (dmdx) memcpy(dmdx + (long)(m0 + m) * D, gm, sizeof(double) * D);
+            if (dvdx) memcpy(dvdx + (long)(m0 + m) * D, gv, sizeof(double) * D);
+            if (dacq) memcpy(dacq + (long)(m0 + m) * D, ga, sizeof(double) * D);
+        }
+    }
+    ++sp.rows_fused_calls;
+    return 0;
+}
+
+// Everything the fused path does not take: the table arithmetic on scratch buffers (never the resident table or its cache).
+static int sparse_rows_fallback(gp_ctx *g, const double *Xs, long M, int include_noise, bool grads, const AcqSpec *a, const LpSpec *lp,
+                                double *mean, double *var, double *acq, double *dmdx, double *dvdx, double *dacq) {
+    SparseState &sp = g->sp;
+    const long D = g->D;
+    hipStream_t s = g->s;
+    int rc;
+    ++sp.rows_fallback_calls;
+    if ((rc = sp.dScrX.reserve(M * D))) return rc;
+    if ((rc = sp.dScrPost.reserve(M * (2 + 2 * D)))) return rc;
+    if ((rc = sp.dScrAcq.reserve(M * (1 + D)))) return rc;
+    double *dmean = sp.dScrPost, *dvar = dmean + M, *ddm = dvar + M, *ddv = ddm + M * D, *dacq_d = sp.dScrAcq + M;
+    HIPCHK(hipMemcpyAsync(sp.dScrX, Xs, sizeof(double) * M * D, hipMemcpyHostToDevice, s));
+    if ((rc = sparse_posterior_rows(g, sp.dScrX, M, include_noise, grads, dmean, dvar, ddm, ddv))) return rc;
+    if (a && (rc = sparse_scores(g, *a, lp, grads, sp.dScrX, M, sp.dScrPost, sp.dScrAcq, dacq_d))) return rc;
+    if (mean) HIPCHK(hipMemcpyAsync(mean, dmean, sizeof(double) * M, hipMemcpyDeviceToHost, s));
+    if (var) HIPCHK(hipMemcpyAsync(var, dvar, sizeof(double) * M, hipMemcpyDeviceToHost, s));
+    if (dmdx) HIPCHK(hipMemcpyAsync(dmdx, ddm, sizeof(double) * M * D, hipMemcpyDeviceToHost, s));
+    if (dvdx) HIPCHK(hipMemcpyAsync(dvdx, ddv, sizeof(double) * M * D, hipMemcpyDeviceToHost, s));
+    if (acq) HIPCHK(hipMemcpyAsync(acq, sp.dScrAcq, sizeof(double) * M, hipMemcpyDeviceToHost, s));
+    if (dacq) HIPCHK(hipMemcpyAsync(dacq, dacq_d, sizeof(double) * M * D, hipMemcpyDeviceToHost, s));
+    GP_SYNC(s);
+    return 0;
+}
+
+extern "C" int gp_sparse_predict_rows(gp_t *g, const double *Xs, int64_t M, int include_noise, double *mean, double *var, double *dmdx,
+                                      double *dvdx) {
+    if (!g || !Xs) return fail(GP_ERR_ARG, "null argument");
+    int rc;
+    if ((rc = sparse_fitted(g))) return rc;
+    if (g->P != 1) return fail(GP_ERR_ARG, "the rows entries need P == 1");
+    if (M < 1) return fail(GP_ERR_ARG, "M < 1");
+    if (dvdx && !dmdx) return fail(GP_ERR_ARG, "dvdx needs dmdx");
+    if (dmdx && !dvdx && (mean || var)) return fail(GP_ERR_ARG, "the mean's gradient alone (dvdx NULL) comes without mean / var");
+    const int mode = !dmdx ? 0 : dvdx ? 1 : 2;
+    if (sparse_rows_fused_ok(g, M)) {
+        RowsAcq aq{};
+        return sparse_rows_fused(g, Xs, (int)M, mode, include_noise, aq, mean, var, nullptr, dmdx, dvdx, nullptr);
+    }
+    return sparse_rows_fallback(g, Xs, M, include_noise, dmdx != nullptr, nullptr, nullptr, mean, var, nullptr, dmdx, dvdx, nullptr);
+}
+
+extern "C" int gp_sparse_acq_rows(gp_t *g, const double *Xs, int64_t M, int type, double par, double fmin, double y_mean, double y_std,
+                                  int lp, int transform, const double *Xb, int nb, const double *r_x0, const double *s_x0, double *out,
+                                  double *dout) {
+    if (!g || !Xs || !out) return fail(GP_ERR_ARG, "null argument");
+    int rc;
+    if ((rc = sparse_fitted(g))) return rc;
+    if (M < 1) return fail(GP_ERR_ARG, "M < 1");
+    const AcqSpec a{type, par, fmin, y_mean, y_std};
+    const LpSpec batch{transform, Xb, nb, r_x0, s_x0}, *pen = lp ? &batch : nullptr;
+    if ((rc = check_acq(g, a))) return rc;
+    if (pen && (rc = check_lp(*pen))) return rc;
+    if (sparse_rows_fused_ok(g, M)) {
+        LpBatch b;
+        if (pen && (rc = rows_lp_batch(g, *pen, &b))) return rc;   // (keeps the shared batch cache in step with dLp)
+        return sparse_rows_fused(g, Xs, (int)M, dout ? 1 : 0, 1, rows_acq(a, pen, b), nullptr, nullptr, out, nullptr, nullptr,
+                                 dout);   // with_noise=True, gpmodel.py:102
+    }
+    return sparse_rows_fallback(g, Xs, M, 1, dout != nullptr, &a, pen, nullptr, nullptr, out, nullptr, nullptr, dout);
+}
+
+// how many sparse rows calls took the fused path / the table arithmetic since the context was created (route checks in tests)
+extern "C" int gp_sparse_rows_stats(gp_t *g, int64_t *fused, int64_t *fallback) {
+    if (!g) return fail(GP_ERR_ARG, "null gp");
+    if (fused) *fused = g->sp.rows_fused_calls;
+    if (fallback) *fallback = g->sp.rows_fallback_calls;
     return 0;
 }

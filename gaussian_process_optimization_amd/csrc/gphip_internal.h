@@ -352,6 +352,21 @@ void launch_sparse_predict_reduce(hipStream_t s, const double *Kx, const double 
                                   int P, double kss, double noise_add, double *mean, double *var);
 void launch_sparse_min(hipStream_t s, const double *v, long n, double *out);
 
+// ---- sparse_rows.hip: a handful of locations on the sparse model as ONE launch over woodbury_inv ------------------------------
+#define SPARSE_ROWS_RB 8                                       // rows of woodbury_inv per workgroup (two per wave)
+#define SPARSE_ROWS_GROW (2 * ROWS_MAX_XS + 2 * ROWS_WIDE_M)   // doubles of per-workgroup sums (gpart: grid rows of them)
+// workgroups of a pass -- the arrivals its counter waits for (the host adds the same number to the counter's base after the pass)
+inline unsigned sparse_rows_grid(long Mz) { return (unsigned)((Mz + SPARSE_ROWS_RB - 1) / SPARSE_ROWS_RB); }
+// mode 0: mean / var (/ acquisition) of rx.M <= ROWS_WIDE_M locations with rx.M D <= ROWS_MAX_XS; 1: the gradients as well; 2: the
+// mean's gradient alone (Winv not read).  Winv [n, n] with n = Mz rounded up to GP_TILE, Zs [Mz, D] = Z / lengthscale
+// (launch_sparse_scale_z), w [Mz].  Results in the
+// host-visible block `out`, laid out for ROWS_WIDE_M locations whatever rx.M: [mean][var][acq][dmdx D][dvdx D][dacq D], and
+// the ticket at out[ROWS_OUT_DOUBLES].
+void launch_sparse_scale_z(hipStream_t s, const double *Z, long Mz, const KernParams &kp, double *Zs);
+void launch_sparse_rows(hipStream_t s, const double *Winv, long n, long Mz, const RowsX &rx, const KernParams &kp, const double *Zs,
+                        const double *w, int mode, double kss, double noise_add, const RowsAcq &aq, double *gpart,
+                        unsigned int *counter, unsigned int counter_base, double *out, double ticket);
+
 // ---- rns.hip: fp64-equivalent contraction on the int8 matrix cores (option "emulate_fp64") -----------------------------
 #define GP_RNS_T 14
 #define GP_RNS_KMAX 8192   // longest contraction (bytes) one residue launch may take: see rns_reduce_f in rns.hip

@@ -40,13 +40,18 @@ class GPModel(BOModel):
     (``SparseGPRegression``, gpmodel.py:66-71).  Keyword arguments, attributes and return conventions are GPyOpt's
     (gpmodel.py:9-177); ``device`` (HIP ordinal) and ``parallel_restarts`` (the restarts in lockstep,
     GPRegression.optimize_restarts(parallel=True); default False, exact model only) are the additions.  A sparse model is
-    scored by the acquisitions through ``predict`` / ``predict_withGradients`` (the device acquisition entries are the exact
-    model's)."""
+    scored by the acquisitions through ``predict`` / ``predict_withGradients`` unless ``device_acquisitions=True`` (sparse models
+    only; default False): the acquisitions then score it on the device (``gp_sparse_acq*``, ``gp_sparse_acq_rows``), and ``predict``,
+    ``predict_withGradients`` and the mean's gradients of up to eight locations -- the hammer precompute and ``estimate_L`` of the
+    local penalisation -- go down as ONE ``gp_sparse_predict_rows`` call each.  The two routes agree to rounding, not bitwise."""
     analytical_gradient_prediction = True
 
     def __init__(self, kernel=None, noise_var=None, exact_feval=False, optimizer='bfgs', max_iters=1000,
                  optimize_restarts=5, sparse=False, num_inducing=10, verbose=True, ARD=False, Gower=False,
-                 space=None, device=0, parallel_restarts=False):
+                 space=None, device=0, parallel_restarts=False, device_acquisitions=False):
+        if device_acquisitions and not sparse:
+            raise ValueError("device_acquisitions selects the sparse model's device route: it needs sparse=True (the exact model "
+                             "is always scored on the device)")
         if sparse and parallel_restarts:
             raise ValueError("parallel_restarts runs the exact model's batched restarts: not available with sparse=True")
         if sparse and Gower and space is not None:
@@ -54,7 +59,7 @@ class GPModel(BOModel):
         vars(self).update(kernel=kernel, noise_var=noise_var, exact_feval=exact_feval, optimizer=optimizer,
                           max_iters=max_iters, optimize_restarts=optimize_restarts, sparse=sparse,
                           num_inducing=num_inducing, verbose=verbose, ARD=ARD, Gower=Gower, space=space, device=device,
-                          parallel_restarts=parallel_restarts, model=None)
+                          parallel_restarts=parallel_restarts, device_acquisitions=bool(device_acquisitions), model=None)
 
     @staticmethod
     def fromConfig(config):
@@ -72,6 +77,7 @@ class GPModel(BOModel):
             chosen = _kern.Matern52(self.input_dim, variance=1., ARD=self.ARD, Gower=self.Gower, space=self.space)
         if self.sparse:     # noise_var is not passed on: the likelihood starts at 1 (gpmodel.py:69-71)
             gp = SparseGPRegression(X, Y, kernel=chosen, num_inducing=self.num_inducing, device=self.device)
+            gp.device_rows = self.device_acquisitions
         else:
             noise = 0.01 * Y.var() if self.noise_var is None else self.noise_var
             gp = GPRegression(X, Y, kernel=chosen, noise_var=noise, device=self.device)
@@ -146,7 +152,7 @@ class GPModel(BOModel):
         twin = GPModel(kernel=self.model.kern.copy(), noise_var=self.noise_var, exact_feval=self.exact_feval,
                        optimizer=self.optimizer, max_iters=self.max_iters, optimize_restarts=self.optimize_restarts,
                        sparse=self.sparse, num_inducing=self.num_inducing, verbose=self.verbose, ARD=self.ARD, Gower=self.Gower, space=self.space, device=self.device,
-                       parallel_restarts=self.parallel_restarts)
+                       parallel_restarts=self.parallel_restarts, device_acquisitions=self.device_acquisitions)
         twin._create_model(self.model.X, self.model.Y)
         twin.updateModel(self.model.X, self.model.Y, None, None)
         return twin

@@ -61,7 +61,12 @@ class SparseGPRegression(GPRegression):
     :param normalizer: ``True`` standardises Y
     :param device: HIP device ordinal
 
-    The Gaussian noise starts at 1.  ``Z`` is the parameter ``inducing_inputs``, first in the flat vector and unconstrained."""
+    The Gaussian noise starts at 1.  ``Z`` is the parameter ``inducing_inputs``, first in the flat vector and unconstrained.
+
+    ``device_rows`` (attribute, default False; ``GPModel(sparse=True, device_acquisitions=True)`` sets it): predictions and
+    predictive gradients of up to eight locations of a single-output model go down as ONE ``gp_sparse_predict_rows`` call, locations
+    by value, instead of ``gp_sparse_predict``.  Same results to rounding, not bitwise."""
+    device_rows = False
 
     def __init__(self, X, Y, kernel=None, Z=None, num_inducing=10, normalizer=None, device=0, name="sparse_gp"):
         X = np.asarray(X, dtype=float)
@@ -78,6 +83,7 @@ class SparseGPRegression(GPRegression):
         if getattr(kernel, "Gower", False) and getattr(kernel, "space", None) is not None:
             raise NotImplementedError("the sparse GP does not take the Gower kernel")
         self.Z = None
+        self._table = None          # the candidate table resident in the sparse model's own block (_stage_table)
         super(SparseGPRegression, self).__init__(X, Y, kernel=kernel, normalizer=normalizer, noise_var=1., device=device, name=name)
         self.posterior = _SparsePosteriorView(self)
         self._link_Z(Z)
@@ -159,6 +165,10 @@ class SparseGPRegression(GPRegression):
         raise NotImplementedError("replica groups score the exact GP: outside the sparse path")
 
     # -- prediction ---------------------------------------------------------------------
+    def _rows_route(self, Xnew, limit=8):
+        """True when ``Xnew`` [M, D] is a handful of locations that ``device_rows`` sends down by value."""
+        return bool(self.device_rows) and self.output_dim == 1 and 1 <= Xnew.shape[0] <= limit
+
     def _sparse_predict(self, Xnew, include_noise, grad=False):
         Xnew = np.asarray(Xnew, dtype=float)
         if Xnew.ndim == 1:
@@ -166,7 +176,23 @@ class SparseGPRegression(GPRegression):
         if Xnew.shape[1] != self.input_dim:
             raise ValueError("candidates have %d columns, model has %d" % (Xnew.shape[1], self.input_dim))
         self._ensure_fit()
+        if self._rows_route(Xnew):
+            return self._h.sparse_predict_rows(Xnew, include_noise=include_noise, grad=grad)
         return self._h.sparse_predict(Xnew, include_noise=include_noise, grad=grad)
+
+    def _stage_table(self, Xnew):
+        """Make ``Xnew`` the sparse model's resident candidate table (gp_sparse_set_candidates), refitting first if anything
+        changed.  The same table staged again -- every round of the local-penalisation loop -- is not uploaded again: the device
+        keeps it, and its cached posterior, across refits, predictions and rows calls."""
+        Xnew = np.asarray(Xnew, dtype=float)
+        if Xnew.ndim == 1:
+            Xnew = Xnew[None, :]
+        self._ensure_fit()
+        held = self._table
+        if held is None or held[0] is not self._h or held[1].shape != Xnew.shape or not np.array_equal(held[1], Xnew):
+            self._h.sparse_set_candidates(Xnew)
+            self._table = (self._h, np.array(Xnew, copy=True))
+        return Xnew
 
     def _raw_predict(self, Xnew, full_cov=False, kern=None):
         """posterior.py:225-248 over the inducing inputs."""
@@ -201,6 +227,12 @@ class SparseGPRegression(GPRegression):
         return self._sparse_predict(Xnew, False, grad=True)[2:]
 
     def mean_gradients(self, Xnew):
+        Xn = np.asarray(Xnew, dtype=float)
+        if Xn.ndim == 1:
+            Xn = Xn[None, :]
+        if Xn.ndim == 2 and Xn.shape[0] >= 1 and Xn.shape[1] == self.input_dim and self._rows_route(Xn):
+            self._ensure_fit()      # d mean / dx alone: the woodbury vector only, no pass over woodbury_inv (estimate_L's inner call)
+            return self._h.sparse_mean_grad_rows(Xn)
         return self.predictive_gradients(Xnew)[0]
 
     def get_fmin(self):

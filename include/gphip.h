@@ -445,8 +445,9 @@ int gp_merge_topk(int n, const double *vals, const int64_t *idxs, int sense, int
  * sparse call reads or writes the exact model's state (factor, inverse factor, alpha, the resident candidates and their
  * results, the cached fmin): gp_fit / gp_predict after any sequence of sparse calls return the bits a fresh context returns.
  * Always true fp64 ("emulate_fp64" does not apply).  GP_ERR_STATE: no data or no parameters, the Gower option on, an output
- * warp on, fit before gp_sparse_set_inducing, the other calls before a sparse fit.  The batched restarts, the sharded and
- * group entries, gp_acq* / gp_*_rows and the full covariance stay exact-GP only. */
+ * warp on, fit before gp_sparse_set_inducing, the other calls before a sparse fit.  The acquisitions have sparse twins below
+ * (gp_sparse_acq*, gp_sparse_*_rows: a candidate table, a cached posterior and a one-location path of the sparse model's own);
+ * the batched restarts, the sharded and group entries, the full covariance and posterior sampling stay exact-GP only. */
 #define GP_SPARSE_MAX_INDUCING 2048
 /* The inducing inputs Z [Mz, D], row-major (SparseGP.__init__ / set_Z, GPy/GPy/core/sparse_gp.py:53,69-74).  Drops the sparse
  * fit.  Z survives gp_set_params and a gp_set_data of the same D (which drop the sparse fit only); a gp_set_data with another
@@ -477,6 +478,49 @@ int gp_sparse_predict(gp_t *gp, const double *Xs, int64_t M, int include_noise, 
                       double *dvdx);
 /* min over the training inputs of the sparse posterior mean Kfu w, first output column (GPModel.get_fmin, gpmodel.py:125-129) */
 int gp_sparse_fmin(gp_t *gp, double *fmin);
+
+/* -- acquisitions over the sparse posterior.  Argument conventions are those of the exact entries: out holds the NEGATED
+ * acquisition, y_mean / y_std undo a Standardize normaliser, transform is 0 or 1, lp != 0 adds the local penalisation of
+ * gp_acq_lp over the batch Xb [nb, D], r_x0, s_x0 (nb = 0: the un-penalised log acquisition).  All need P = 1.  GP_ERR_STATE: what
+ * gp_sparse_predict refuses, and a table entry before gp_sparse_set_candidates; GP_ERR_ARG: P != 1, an unknown acquisition, a bad
+ * sense / k / exclude / batch, M < 1.  None of them reads or writes the exact model's state (its candidates, posterior, scores). */
+
+/* The sparse model's resident candidate table Xs [M, D], in a buffer of its own.  Its posterior is cached lazily by the scoring
+ * entries below -- mean and variance (noise included, as GPModel.predict asks, gpmodel.py:102), gradients once asked for -- and
+ * is, bit for bit, what gp_sparse_predict(include_noise = 1) returns for those rows.  Whatever drops the sparse fit drops the
+ * cache; the table survives as Z does (another D drops it).  gp_sparse_predict, gp_sparse_fmin and the two rows entries leave table
+ * and cache intact.  Needs data (GP_ERR_STATE). */
+int gp_sparse_set_candidates(gp_t *gp, const double *Xs, int64_t M);
+/* gp_acq / gp_acq_grad (lp = 0) or gp_acq_lp / gp_acq_lp_grad (lp != 0) on the table: out [M] and, when given, dout [M, D].  A
+ * row's score depends on its own posterior only: the same row gives the same bits in any table, at any position. */
+int gp_sparse_acq(gp_t *gp, int type, double par, double fmin, double y_mean, double y_std, int lp, int transform,
+                  const double *Xb, int nb, const double *r_x0, const double *s_x0, double *out, double *dout);
+/* gp_acq_argbest / gp_acq_lp_argbest of the same vector: sense, ties (lowest index), exclude as there. */
+int gp_sparse_acq_argbest(gp_t *gp, int type, double par, double fmin, double y_mean, double y_std, int lp, int transform,
+                          const double *Xb, int nb, const double *r_x0, const double *s_x0, int sense, const int64_t *exclude,
+                          int nex, int64_t *idx, double *val);
+/* gp_acq_topk: 1 <= k <= GP_TOPK_MAX, equal scores lowest index first, idx = -1 in the tail when M < k. */
+int gp_sparse_acq_topk(gp_t *gp, int type, double par, double fmin, double y_mean, double y_std, int sense, int k, int64_t *idx,
+                       double *val);
+
+/* A handful of locations per call, given by value: the acquisition optimiser's inner loop over a sparse model (see gp_predict_rows
+ * / gp_acq_rows for the exact model's twins and the argument rules: mean / var may be NULL, dvdx needs dmdx, dmdx alone comes
+ * without mean / var and is estimate_L's inner call, which needs the woodbury vector only).  For M <= option "small_m" (8)
+ * locations the call is ONE launch per pass with no copy commands (csrc/sparse_rows.hip): k = K(x, Z) generated into LDS, b =
+ * woodbury_inv k from one read of the Mz x Mz matrix for all locations of the pass, var = max(kss - k . b, 1e-15) (+ noise), the
+ * two gradients_X sums, the acquisition and the penaliser, written into a pinned result block.  A pass takes the locations that
+ * fit the kernel arguments (M D <= 128: all eight up to D = 16, two at D = 64).  A location's results are the same bits whatever
+ * its slot, its company and M (1 .. 8), and on every call.  More locations go through the table arithmetic on scratch buffers --
+ * the bits of gp_sparse_predict -- never through the resident table.  Fused path and table path agree to rounding, not bitwise:
+ * they contract in a different order (tests/test_gpu_sparse_acq.py).  gp_sparse_predict itself keeps the table arithmetic for
+ * every M, as its own contract asks. */
+int gp_sparse_predict_rows(gp_t *gp, const double *Xs, int64_t M, int include_noise, double *mean, double *var, double *dmdx,
+                           double *dvdx);
+int gp_sparse_acq_rows(gp_t *gp, const double *Xs, int64_t M, int type, double par, double fmin, double y_mean, double y_std,
+                       int lp, int transform, const double *Xb, int nb, const double *r_x0, const double *s_x0, double *out,
+                       double *dout);
+/* how many of those calls took the fused path / the table arithmetic since gp_create (route checks of the tests) */
+int gp_sparse_rows_stats(gp_t *gp, int64_t *fused, int64_t *fallback);
 
 /* ---- measurement ---------------------------------------------------------
  * Phase timings of the last gp_fit / gp_predict measured with HIP events on the
