@@ -9,6 +9,7 @@ Drop-in surface for the path GPyOpt/GPy sit on:
     mw = gpo.models.InputWarpedGP(X, Y, gpo.kern.Matern52(D))            # GPy.models.InputWarpedGP (Kumaraswamy warping)
     mo = gpo.models.WarpedGP(X, Y, gpo.kern.Matern32(D))                 # GPy.models.WarpedGP (tanh warp of the outputs)
     ms = gpo.models.SparseGPRegression(X, Y, num_inducing=128)           # GPy.models.SparseGPRegression (variational DTC)
+    mm = gpo.GPModel_MCMC(n_samples=10)                                  # GPyOpt.models.GPModel_MCMC (HMC over the hyper-parameters)
     acq = gpo.acquisitions.AcquisitionEI(gpo.GPModel(...), ...)           # GPyOpt.acquisitions
 
 Host code is plain Python + ctypes over the C-ABI in include/gphip.h; every
@@ -21,24 +22,27 @@ from . import _lib
 from . import kern
 from .gp_regression import GPRegression, Gaussian, Standardize
 from .sparse_gp import SparseGPRegression
-from .gpmodel import GPModel, BOModel
+from .gpmodel import GPModel, BOModel, GPModel_MCMC
+from . import priors
+from .mcmc import HMC
 from . import input_warping
 from .input_warped_gp import InputWarpedGP, InputWarpedGPModel
 from . import warping_functions
 from .warped_gp import WarpedGP, WarpedGPModel
 from . import acquisitions
 from .acquisitions import (AcquisitionEI, AcquisitionLCB, AcquisitionMPI, AcquisitionBase, AcquisitionLP,
-                           LocalPenalization, estimate_L)
+                           LocalPenalization, estimate_L, AcquisitionEI_MCMC, AcquisitionMPI_MCMC, AcquisitionLCB_MCMC)
 from .bayesian_optimization import BayesianOptimization, Design_space, AcquisitionOptimizer
 from .sharded import ShardedCandidates, merge_best
 
 # namespaces named like the reference packages
-models = _types.SimpleNamespace(GPRegression=GPRegression, SparseGPRegression=SparseGPRegression, GPModel=GPModel, InputWarpedGP=InputWarpedGP,
+models = _types.SimpleNamespace(GPRegression=GPRegression, SparseGPRegression=SparseGPRegression, GPModel=GPModel, GPModel_MCMC=GPModel_MCMC, InputWarpedGP=InputWarpedGP,
                                 InputWarpedGPModel=InputWarpedGPModel, WarpedGP=WarpedGP, WarpedGPModel=WarpedGPModel)
 methods = _types.SimpleNamespace(BayesianOptimization=BayesianOptimization)
 likelihoods = _types.SimpleNamespace(Gaussian=Gaussian)
 
-__all__ = ["kern", "models", "methods", "likelihoods", "acquisitions", "GPRegression", "SparseGPRegression", "GPModel", "BOModel",
+__all__ = ["kern", "models", "methods", "likelihoods", "acquisitions", "GPRegression", "SparseGPRegression", "GPModel", "BOModel", "GPModel_MCMC", "priors", "HMC",
+           "AcquisitionEI_MCMC", "AcquisitionMPI_MCMC", "AcquisitionLCB_MCMC",
            "InputWarpedGP", "InputWarpedGPModel", "input_warping", "WarpedGP", "WarpedGPModel", "warping_functions",
            "AcquisitionEI", "AcquisitionLCB", "AcquisitionMPI", "AcquisitionBase", "AcquisitionLP",
            "LocalPenalization", "estimate_L", "BayesianOptimization",

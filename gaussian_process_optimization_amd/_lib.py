@@ -94,6 +94,14 @@ SIGNATURES = [
                                           ctypes.c_double, ctypes.c_double, ctypes.c_int, ctypes.c_int, _vp, ctypes.c_int,
                                           _vp, _vp, _vp, _vp]),
     ("gp_sparse_rows_stats", ctypes.c_int, [_vp, c_int64_p, c_int64_p]),
+    ("gp_ens_fit", ctypes.c_int, [_vp, ctypes.c_int, c_double_p, c_double_p, c_double_p, ctypes.c_int, c_double_p, c_double_p,
+                                  c_double_p, c_double_p]),
+    ("gp_ens_info", ctypes.c_int, [_vp, c_int_p]),
+    # (void* for the pointers of the two rows entries, as for gp_predict_rows / gp_acq_rows below)
+    ("gp_ens_predict_rows", ctypes.c_int, [_vp, _vp, ctypes.c_int64, ctypes.c_int, _vp, _vp, _vp, _vp]),
+    ("gp_ens_acq_rows", ctypes.c_int, [_vp, _vp, ctypes.c_int64, ctypes.c_int, ctypes.c_double, _vp, _vp]),
+    ("gp_ens_acq", ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_double, c_double_p]),
+    ("gp_ens_acq_argbest", ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_double, ctypes.c_int, c_int64_p, c_double_p]),
     ("gp_predict_full_cov", ctypes.c_int, [_vp, ctypes.c_int, c_double_p, c_double_p]),
     ("gp_predict_grad", ctypes.c_int, [_vp, c_double_p, c_double_p]),
     ("gp_fmin", ctypes.c_int, [_vp, c_double_p]),
@@ -677,6 +685,67 @@ class Handle(object):
         a, b = ctypes.c_int64(), ctypes.c_int64()
         check(self.lib, self.lib.gp_sparse_rows_stats(self.h, ctypes.byref(a), ctypes.byref(b)), "gp_sparse_rows_stats")
         return dict(fused=a.value, fallback=b.value)
+
+    # -- the ensemble (include/gphip.h, gp_ens_*): S hyper-parameter members with resident posteriors --------------------------
+    def ens_fit(self, variances, lengthscales, noises, maxtries=5):
+        """Factor and keep S members ([S], [S, nls], [S]); returns (lml, logdet, jitter, fmin), [S] each."""
+        var = as_f64(np.atleast_1d(variances), 1)
+        noi = as_f64(np.atleast_1d(noises), 1)
+        S = var.size
+        want = getattr(self, "n_ls", None)
+        if want is None:
+            raise ValueError("set_params has not been called on this handle")
+        ls = np.ascontiguousarray(np.asarray(lengthscales, dtype=float))
+        if ls.ndim != 2 or ls.shape != (S, want) or noi.size != S:
+            raise ValueError("expected variances [S], lengthscales [S, %d] and noises [S]; got %s, %s, %s"
+                             % (want, var.shape, ls.shape, noi.shape))
+        lml, logdet, jit, fmin = np.empty(S), np.empty(S), np.empty(S), np.empty(S)
+        check(self.lib, self.lib.gp_ens_fit(self.h, int(S), dptr(var), dptr(ls), dptr(noi), int(maxtries), dptr(lml),
+                                            dptr(logdet), dptr(jit), dptr(fmin)), "gp_ens_fit")
+        self.ens_S = S
+        return lml, logdet, jit, fmin
+
+    def ens_info(self):
+        n = ctypes.c_int(0)
+        check(self.lib, self.lib.gp_ens_info(self.h, ctypes.byref(n)), "gp_ens_info")
+        return n.value
+
+    def ens_predict_rows(self, Xs, include_noise=True, grad=False):
+        """Every member's posterior at M <= 8 locations: (mean [S, M], var [S, M]) and, with ``grad``, (dmdx, dvdx) [S, M, D]."""
+        Xs = as_f64(Xs, 2)
+        M, S = Xs.shape[0], self.ens_info()
+        mean, var = np.empty((S, M)), np.empty((S, M))
+        dm = np.empty((S, M, self.D)) if grad else None
+        dv = np.empty((S, M, self.D)) if grad else None
+        rc = self.lib.gp_ens_predict_rows(self.h, Xs.ctypes.data, M, 1 if include_noise else 0, mean.ctypes.data,
+                                          var.ctypes.data, dm.ctypes.data if grad else None, dv.ctypes.data if grad else None)
+        if rc:
+            check(self.lib, rc, "gp_ens_predict_rows")
+        return (mean, var, dm, dv) if grad else (mean, var)
+
+    def ens_acq_rows(self, Xs, type_, par, grad=False):
+        """The integrated acquisition, negated, [M, 1] (and its gradient [M, D]) at M <= 8 locations."""
+        Xs = as_f64(Xs, 2)
+        M = Xs.shape[0]
+        out = np.empty((M, 1))
+        dout = np.empty((M, self.D)) if grad else None
+        rc = self.lib.gp_ens_acq_rows(self.h, Xs.ctypes.data, M, int(type_), par, out.ctypes.data,
+                                      dout.ctypes.data if grad else None)
+        if rc:
+            check(self.lib, rc, "gp_ens_acq_rows")
+        return (out, dout) if grad else out
+
+    def ens_acq(self, type_, par):
+        """The same value over the resident candidate table (set_candidates), [M, 1]."""
+        out = np.empty((self.M, 1))
+        check(self.lib, self.lib.gp_ens_acq(self.h, int(type_), float(par), dptr(out)), "gp_ens_acq")
+        return out
+
+    def ens_acq_argbest(self, type_, par, sense):
+        idx, val = ctypes.c_int64(), ctypes.c_double()
+        check(self.lib, self.lib.gp_ens_acq_argbest(self.h, int(type_), float(par), int(sense), ctypes.byref(idx),
+                                                    ctypes.byref(val)), "gp_ens_acq_argbest")
+        return idx.value, val.value
 
     def predict(self, include_noise=True):
         mean = np.empty((self.M, self.P))

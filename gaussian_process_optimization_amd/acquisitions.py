@@ -17,7 +17,7 @@ import numpy as np
 from scipy.special import erfc, log_ndtr, ndtr
 
 from . import _lib
-from .gpmodel import GPModel
+from .gpmodel import GPModel, GPModel_MCMC
 
 _FEW_ROWS = 8            # up to this many locations go down as ONE gp_*_rows call (include/gphip.h): the L-BFGS inner loop
 _ROOT_2 = np.sqrt(2)
@@ -357,6 +357,114 @@ class AcquisitionMPI(AcquisitionBase):
 
     def _par(self):
         return self.jitter
+
+
+# ---- acquisitions integrated over the hyper-parameter samples ----------------------------------------------------------
+class _IntegratedAcquisition(AcquisitionBase):
+    """The mean over the model's HMC samples of an EI / MPI / LCB rule, each sample with its own fmin, mean and standard
+    deviation (acquisitions/EI_mcmc.py:32-59, MPI_mcmc.py:32-59, LCB_mcmc.py:33-60).  With the HIP ``GPModel_MCMC``, unit cost
+    and no constraints the resident ensemble is scored on the device: up to ``_FEW_ROWS`` rows by ``gp_ens_acq_rows``, larger
+    blocks by ``gp_ens_acq`` over the candidate table (with gradients: in passes of ``_FEW_ROWS`` rows), ``argbest`` by
+    ``gp_ens_acq_argbest``.  Otherwise the reference's formulas run on the host over the model's lists."""
+    analytical_gradient_prediction = True
+
+    def __init__(self, model, space=None, optimizer=None, cost_withGradients=None):
+        super().__init__(model, space, optimizer, cost_withGradients=cost_withGradients)
+        assert self.model.MCMC_sampler, 'Samples from the hyper-parameters are needed to compute the integrated ' + self._name
+
+    def _ens_ok(self):
+        if not isinstance(self.model, GPModel_MCMC) or self.model.model is None or self.model.hmc_samples is None:
+            return False
+        if self.cost_withGradients is not constant_cost_withGradients:
+            return False
+        constrained = getattr(self.space, "has_constraints", None)
+        return not (constrained is not None and constrained())
+
+    def acquisition_function(self, x):
+        if not self._ens_ok():
+            return super().acquisition_function(x)
+        x = np.atleast_2d(np.asarray(x, dtype=float))
+        h = self.model.model._h
+        if x.shape[0] <= _FEW_ROWS:
+            return h.ens_acq_rows(x, self._acq_id, self._par())
+        h.set_candidates(x)
+        return h.ens_acq(self._acq_id, self._par())
+
+    def acquisition_function_withGradients(self, x):
+        if not self._ens_ok():
+            return super().acquisition_function_withGradients(x)
+        x = np.atleast_2d(np.asarray(x, dtype=float))
+        h = self.model.model._h
+        parts = [h.ens_acq_rows(x[i:i + _FEW_ROWS], self._acq_id, self._par(), grad=True) for i in range(0, x.shape[0], _FEW_ROWS)]
+        return np.vstack([p[0] for p in parts]), np.vstack([p[1] for p in parts])
+
+    def argbest(self, x, sense=-1, devices=None):
+        if not self._ens_ok() or devices is not None:
+            if devices is not None:
+                raise NotImplementedError("replica groups score one hyper-parameter vector: not available with GPModel_MCMC")
+            return _pick(self.acquisition_function(x)[:, 0], sense)
+        h = self.model.model._h
+        h.set_candidates(np.atleast_2d(np.asarray(x, dtype=float)))
+        return h.ens_acq_argbest(self._acq_id, self._par(), sense)
+
+    def _fmin(self):
+        raise NotImplementedError("an integrated acquisition has one fmin per sample")
+
+    def _compute_acq(self, x):
+        means, stds = self.model.predict(x)
+        fmins = self.model.get_fmin()
+        total = 0
+        for mu, sd, fmin in zip(means, stds, fmins):
+            total = total + self._rule.value(self._par(), fmin, mu, sd)
+        return total / len(means)
+
+    def _compute_acq_withGradients(self, x):
+        means, stds, dmdxs, dsdxs = self.model.predict_withGradients(x)
+        fmins = self.model.get_fmin()
+        total, dtotal = 0, 0
+        for mu, sd, fmin, dmu, dsd in zip(means, stds, fmins, dmdxs, dsdxs):
+            val, dval = self._rule.gradient(self._par(), fmin, mu, sd, dmu, dsd)
+            total, dtotal = total + val, dtotal + dval
+        return total / len(means), dtotal / len(means)
+
+
+class AcquisitionEI_MCMC(_IntegratedAcquisition):
+    """Integrated expected improvement (EI_mcmc.py:7-59)."""
+    _rule = _RULES["EI"]
+    _name = "EI"
+
+    def __init__(self, model, space=None, optimizer=None, cost_withGradients=None, jitter=0.01):
+        super().__init__(model, space, optimizer, cost_withGradients)
+        self.jitter = jitter
+
+    def _par(self):
+        return self.jitter
+
+
+class AcquisitionMPI_MCMC(_IntegratedAcquisition):
+    """Integrated probability of improvement (MPI_mcmc.py:7-59)."""
+    _rule = _RULES["MPI"]
+    _name = "MPI"
+
+    def __init__(self, model, space=None, optimizer=None, cost_withGradients=None, jitter=0.01):
+        super().__init__(model, space, optimizer, cost_withGradients)
+        self.jitter = jitter
+
+    def _par(self):
+        return self.jitter
+
+
+class AcquisitionLCB_MCMC(_IntegratedAcquisition):
+    """Integrated lower confidence bound (LCB_mcmc.py:7-60); a cost model is ignored, as in the reference."""
+    _rule = _RULES["LCB"]
+    _name = "GP-LCB"
+
+    def __init__(self, model, space=None, optimizer=None, cost_withGradients=None, exploration_weight=2):
+        super().__init__(model, space, optimizer, None)
+        self.exploration_weight = exploration_weight
+
+    def _par(self):
+        return self.exploration_weight
 
 
 # ---- local penalisation ---------------------------------------------------------------------------------------------

@@ -19,7 +19,8 @@ import numpy as np
 from scipy import optimize as _sopt
 
 from . import kern as _kern
-from .acquisitions import AcquisitionEI, AcquisitionLCB, AcquisitionMPI, AcquisitionLP, LocalPenalization
+from .acquisitions import (AcquisitionEI, AcquisitionLCB, AcquisitionMPI, AcquisitionLP, LocalPenalization, AcquisitionEI_MCMC,
+                           AcquisitionMPI_MCMC, AcquisitionLCB_MCMC)
 from .gpmodel import GPModel
 from .input_warped_gp import InputWarpedGPModel
 from .parameterization import lbfgsb_lockstep, SCIPY_DEFAULT
@@ -369,8 +370,26 @@ class BayesianOptimization(object):
         # arguments_manager.py:42-75
         jitter = kwargs.get('acquisition_jitter', 0.01)
         weight = kwargs.get('acquisition_weight', 2)
+        # arguments_manager.py:50-75 and the acquisitions' own asserts: the integrated acquisitions need the model's
+        # hyper-parameter samples, and a model that integrates them out is scored by nothing else
+        mcmc_model = bool(getattr(self.model, 'MCMC_sampler', False))
+        integrated = {'EI_MCMC': AcquisitionEI_MCMC, 'MPI_MCMC': AcquisitionMPI_MCMC, 'LCB_MCMC': AcquisitionLCB_MCMC}
+        if acquisition is None and acquisition_type in integrated and not mcmc_model:
+            raise InvalidConfigError("acquisition %r needs a model with MCMC_sampler (GPModel_MCMC)" % acquisition_type)
+        if acquisition is None and mcmc_model and acquisition_type not in integrated:
+            raise InvalidConfigError("a model with MCMC_sampler is scored by 'EI_MCMC', 'MPI_MCMC' or 'LCB_MCMC', not %r"
+                                     % acquisition_type)
+        if mcmc_model and batch_size > 1 and evaluator_type not in ('sequential', 'random', None):
+            raise NotImplementedError("evaluator %r is not available with a model that samples its hyper-parameters"
+                                      % evaluator_type)
         if acquisition is not None:
             self.acquisition = acquisition
+        elif acquisition_type == 'EI_MCMC':
+            self.acquisition = AcquisitionEI_MCMC(self.model, self.space, self.acquisition_optimizer, cost_withGradients, jitter)
+        elif acquisition_type == 'MPI_MCMC':
+            self.acquisition = AcquisitionMPI_MCMC(self.model, self.space, self.acquisition_optimizer, cost_withGradients, jitter)
+        elif acquisition_type == 'LCB_MCMC':
+            self.acquisition = AcquisitionLCB_MCMC(self.model, self.space, self.acquisition_optimizer, None, weight)
         elif acquisition_type in (None, 'EI'):
             self.acquisition = AcquisitionEI(self.model, self.space, self.acquisition_optimizer, cost_withGradients, jitter)
         elif acquisition_type == 'LCB':

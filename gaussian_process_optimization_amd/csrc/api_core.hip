@@ -359,6 +359,7 @@ extern "C" int gp_destroy(gp_t *g) {
     if (g->comm) ncclCommDestroy(g->comm);
     if (g->hRowsOut) hipHostFree(g->hRowsOut);
     if (g->sp.hRowsOut) hipHostFree(g->sp.hRowsOut);
+    if (g->ens.hOut) hipHostFree(g->ens.hOut);
     // events recorded on the shared streams go first; the streams themselves belong to the per-device set shared by
     // every context of the process and are destroyed by gp_shutdown / the exit hook
     destroy_ctx_events(g);
@@ -532,6 +533,7 @@ extern "C" int gp_set_data(gp_t *g, const double *X, const double *Y, int64_t N,
     g->have_data = true;
     fit_dropped(g);
     sparse_fit_dropped(g);
+    g->ens.S = 0;   // the ensemble was fitted to the data that just left
     g->kp.D = D;
     return 0;
 }

@@ -1,0 +1,366 @@
+// The ensemble entry points: S hyper-parameter members over the context's (X, Y) with RESIDENT posteriors, and the acquisitions
+// integrated over them -- GPModel_MCMC (GPyOpt/GPyOpt/models/gpmodel.py:180-355) with acquisitions/{EI,MPI,LCB}_mcmc.py.
+// The reference writes each HMC sample into the model and refactorises for every acquisition call (gpmodel.py:266-272, 307-315)
+// and again for get_fmin (:285-291): 2 S Cholesky factorisations per L-BFGS evaluation.  Here gp_ens_fit factors the S members
+// once, in the lockstep launch sequences of gp_fit_grad_batch (struct Members), and KEEPS each member's alpha, inverse factor,
+// parameters, jitter and fmin; a scoring call is then matrix-vector work over the S inverse factors in the launches of one
+// model's call (ens_rows.hip), or, over the resident candidate table, one cross covariance per member, one batched GEMM against
+// the inverse factors and one reduce.  Always true fp64.  The ensemble lives beside the context's own fit (EnsState).
+#include "api_internal.h"
+
+#define GP_ENS_MAX_S 64
+#define GP_ENS_MAX_NPAD 2048   // the batched fit's cap
+#define GP_ENS_TABLE_CHUNK 512 // candidate rows per pass of the table route
+
+static int ens_ready(gp_ctx *g) {
+    GP_DEAD_CHECK(g);
+    if (g->ens.S < 1) return fail(GP_ERR_STATE, "gp_ens_fit first");
+    HIPCHK(hipSetDevice(g->device));
+    return 0;
+}
+
+static const double *ens_noise(const gp_ctx *g) { return g->ens.dTab; }
+static const double *ens_fmin(const gp_ctx *g) { return g->ens.dTab + GP_ENS_MAX_S; }
+
+extern "C" int gp_ens_fit(gp_t *g, int S, const double *variance, const double *lengthscale, const double *noise, int maxtries,
+                          double *lml, double *logdet, double *jitter_used, double *fmin) {
+    if (!g || !variance || !lengthscale || !noise) return fail(GP_ERR_ARG, "null argument");
+    GP_DEAD_CHECK(g);
+    if (!g->have_data) return fail(GP_ERR_STATE, "gp_set_data before gp_ens_fit");
+    // what the shapes alone decide comes first: a data set the ensemble cannot take is refused before any parameters are asked for
+    if (S < 1 || S > GP_ENS_MAX_S) return fail(GP_ERR_ARG, "gp_ens_fit takes 1 <= S <= %d members (got %d)", GP_ENS_MAX_S, S);
+    if (g->Npad > GP_ENS_MAX_NPAD)
+        return fail(GP_ERR_ARG, "gp_ens_fit covers Npad <= %d (N = %ld pads to %ld)", GP_ENS_MAX_NPAD, g->N, g->Npad);
+    if (g->P != 1) return fail(GP_ERR_ARG, "gp_ens_fit needs P == 1");
+    if (!g->have_params) return fail(GP_ERR_STATE, "gp_set_params before gp_ens_fit");
+    if (g->kp.gower)   // the lengthscale does not enter a Gower K: sampling it is sampling its prior
+        return fail(GP_ERR_STATE, "gp_ens_fit: the Gower option is on (gp_set_gower)");
+    if (g->warp.n > 0) return fail(GP_ERR_STATE, "gp_ens_fit: an output warp is on (gp_set_output_warp)");
+    const int D = g->D, nls = g->ard ? D : 1;
+    for (int r = 0; r < S; ++r) {
+        if (!(variance[r] > 0.0)) return fail(GP_ERR_ARG, "member %d: variance must be positive", r);
+        if (!(noise[r] > 0.0)) return fail(GP_ERR_ARG, "member %d: noise must be positive", r);
+        for (int d = 0; d < nls; ++d)
+            if (!(lengthscale[(long)r * nls + d] > 0.0)) return fail(GP_ERR_ARG, "member %d: lengthscale must be positive", r);
+    }
+    HIPCHK(hipSetDevice(g->device));
+    EnsState &en = g->ens;
+    en.S = 0;   // invalid until every member is factored and kept
+
+    const long N = g->N, Npad = g->Npad;
+    const int P = 1, nt = (int)(Npad / GP_TILE), W = std::min(g->panel_tiles, nt), nJ = (nt + W - 1) / W;
+    const long PB = (long)W * GP_TILE;
+    // the batched fit's scratch (api_batch.hip), without Ky^-1 and the gradient passes; behind it the training mean of one member
+    Members m;
+    m.nb = S;
+    m.W = W;
+    m.lda = Npad;
+    m.sA = (Npad + GP_TILE) * Npad;
+    m.sI = (long)nt * GP_TILE * GP_TILE;
+    m.sP = (long)nJ * PB * PB;
+    m.sV = (long)P * Npad;
+    m.sT = Npad * Npad;
+    m.sS = SCAL_GRAD.off + SCAL_GRAD.len;
+    const long per = m.sA + m.sI + 2 * m.sP + 2 * m.sV + 2 * m.sT + m.sS + 2;
+    int rc;
+    if ((rc = g->dBatch.reserve(per * S + Npad))) return rc;
+    const size_t kp_bytes = (sizeof(KernParams) * S + 255) / 256 * 256;
+    if ((rc = g->dBatchAux.reserve((long)(kp_bytes + sizeof(int) * 4 * S)))) return rc;
+    if ((rc = en.dLi.reserve((long)S * Npad * Npad))) return rc;
+    if ((rc = en.dAlpha.reserve((long)S * Npad))) return rc;
+    if ((rc = en.dTab.reserve(2 * GP_ENS_MAX_S))) return rc;
+    if ((rc = en.dKp.reserve((long)sizeof(KernParams) * GP_ENS_MAX_S))) return rc;
+    m.A = g->dBatch;
+    m.invL = m.A + S * m.sA;
+    m.invP = m.invL + S * m.sI;
+    m.invPw = m.invP + S * m.sP;
+    m.alpha = m.invPw + S * m.sP;
+    m.w = m.alpha + S * m.sV;
+    m.T = m.Wi = m.w + S * m.sV;
+    m.T2 = m.partial = m.T + S * m.sT;
+    m.scal = m.T2 + S * m.sT;
+    double *dDiag = m.scal + S * m.sS, *dJit = dDiag + S, *dMu = dJit + S;
+    KernParams *dKp = (KernParams *)g->dBatchAux.p;
+    m.info = (int *)(g->dBatchAux + kp_bytes);
+
+    std::vector<KernParams> kp(S, g->kp);
+    std::vector<double> diag(S), diag0(S), jit(S, 0.0);
+    for (int r = 0; r < S; ++r) {
+        kp[r].variance = variance[r];
+        for (int d = 0; d < D; ++d) kp[r].ls[d] = g->ard ? lengthscale[(long)r * nls + d] : lengthscale[(long)r * nls];
+        ky_diag(kp[r], noise[r], &diag[r], &diag0[r]);
+    }
+    m.kp = kp.data();
+    m.kpt = dKp;
+    m.diag = diag.data();
+    m.diag_tab = dDiag;
+    m.jit = jit.data();
+    m.jit_tab = dJit;
+    HIPCHK(hipMemsetAsync(m.invL, 0, sizeof(double) * m.sI * S, g->s));
+    HIPCHK(hipMemcpyAsync(dKp, kp.data(), sizeof(KernParams) * S, hipMemcpyHostToDevice, g->s));
+    HIPCHK(hipMemcpyAsync(dDiag, diag.data(), sizeof(double) * S, hipMemcpyHostToDevice, g->s));
+
+    // the per-member jitter ladder of gp_fit_grad_batch: failed members are factored again, the others keep their factor
+    std::vector<int> tries(S, 0), active(S, 1), st(S, 0), info(4 * S);
+    for (int round = 0;; ++round) {
+        if (round > 0) HIPCHK(hipMemcpyAsync(dJit, jit.data(), sizeof(double) * S, hipMemcpyHostToDevice, g->s));
+        for (int m0 = 0, m1; m0 < S; m0 = m1 + 1) {
+            for (m1 = m0; m1 < S && active[m1];) ++m1;
+            if (m1 == m0) continue;
+            const Members run = members_range(m, m0, m1 - m0);
+            build_ky(g, run, round > 0);
+            GP_NOTE(hipMemsetAsync(run.info, 0, sizeof(int) * 4 * run.nb, g->s));
+            factor_buf(g, run, nt, nt + 1);
+        }
+        HIPCHK(hipMemcpyAsync(info.data(), m.info, sizeof(int) * 4 * S, hipMemcpyDeviceToHost, g->s));
+        GP_SYNC(g->s);
+        bool again = false;
+        for (int r = 0; r < S; ++r) {
+            if (!active[r]) continue;
+            if (info[4 * r] != 0) st[r] = ladder_step(diag0[r], maxtries, info[4 * r], &jit[r], &tries[r]);
+            active[r] = info[4 * r] != 0 && st[r] == 0;
+            again = again || active[r];
+        }
+        if (!again) break;
+    }
+    for (int r = 0; r < S; ++r) {   // one member that cannot be factored fails the call: the ensemble stays invalid
+        if (st[r] == GP_ERR_NOT_PD_DIAG) return fail(st[r], "not pd: non-positive diagonal elements");
+        if (st[r]) {
+            g_err = "not positive definite, even with jitter.";
+            return st[r];
+        }
+    }
+
+    panel_inv_members(g, m);
+    alpha_lml(g, g->s, m);
+    identity_blocks(g->s, m.T, Npad, S);
+    solve_rows(g, m, nt, 1);   // L^-T into T2
+    // kept: Li = (L^-T)^T with exact zeros above the diagonal, alpha, and the minimum of the training mean y - d alpha
+    // (GPModel_MCMC.get_fmin, gpmodel.py:285-291), d the whole diagonal the member's K got
+    for (int r = 0; r < S; ++r) {
+        launch_transpose_tri(g->s, en.dLi + (long)r * Npad * Npad, m.T2 + (long)r * m.sT, Npad, 0);
+        launch_train_mean_identity(g->s, g->dY, m.alpha + (long)r * m.sV, diag[r] + jit[r], N, dMu);
+        launch_argbest(g->s, dMu, N, -1, en.dTab + GP_ENS_MAX_S + r, g->dRedI + RED_RESULT.off, g->dRedV + RED_PARTIAL.off,
+                       g->dRedI + RED_PARTIAL.off);
+    }
+    HIPCHK(hipMemcpyAsync(en.dAlpha, m.alpha, sizeof(double) * S * Npad, hipMemcpyDeviceToDevice, g->s));
+    HIPCHK(hipMemcpyAsync(en.dKp.p, kp.data(), sizeof(KernParams) * S, hipMemcpyHostToDevice, g->s));
+    HIPCHK(hipMemcpyAsync(en.dTab, noise, sizeof(double) * S, hipMemcpyHostToDevice, g->s));
+    if (en.dCounter) {   // the arrival counters start again with every ensemble: another S leaves members that never counted
+        HIPCHK(hipMemsetAsync(en.dCounter, 0, sizeof(unsigned int) * (1 + GP_ENS_MAX_S), g->s));
+        en.member_base = en.ens_base = 0;
+    }
+    std::vector<double> sc((size_t)m.sS * S);
+    en.fmin.assign(S, 0.0);
+    HIPCHK(hipMemcpyAsync(sc.data(), m.scal, sizeof(double) * m.sS * S, hipMemcpyDeviceToHost, g->s));
+    HIPCHK(hipMemcpyAsync(en.fmin.data(), en.dTab + GP_ENS_MAX_S, sizeof(double) * S, hipMemcpyDeviceToHost, g->s));
+    GP_SYNC(g->s);
+
+    for (int r = 0; r < S; ++r) {
+        const double *s = sc.data() + (size_t)m.sS * r;
+        if (logdet) logdet[r] = s[SCAL_LOGDET.off];
+        if (lml) lml[r] = lml_from_scalars(N, P, s);
+        if (jitter_used) jitter_used[r] = jit[r];
+        if (fmin) fmin[r] = en.fmin[r];
+    }
+    en.kp = kp;
+    en.noise.assign(noise, noise + S);
+    en.jitter = jit;
+    en.S = S;
+    return 0;
+}
+
+extern "C" int gp_ens_info(gp_t *g, int *S) {
+    if (!g || !S) return fail(GP_ERR_ARG, "null argument");
+    GP_DEAD_CHECK(g);
+    *S = g->ens.S;
+    return 0;
+}
+
+// ---- the rows route ------------------------------------------------------------------------------------------------------------
+static int ens_rows_table(gp_ctx *g, EnsRows *t) {
+    EnsState &en = g->ens;
+    const long Npad = g->Npad, S = en.S;
+    const int nt = (int)(Npad / GP_TILE);
+    const long nch = (nt - 1) / 8 + 1, nrb = (long)nt * (GP_TILE / ENS_ROWS_RB);
+    t->sW = nch * ROWS_MAX_M * Npad;
+    t->sB = nrb * ROWS_MAX_M * Npad;
+    t->sM = nch * ROWS_MAX_M;
+    t->sV = nrb * ROWS_MAX_M;
+    t->sG = (long)rows_gpart_elems(g->N);
+    int rc;
+    if ((rc = en.dWork.reserve(S * (t->sW + t->sB + t->sM + t->sV + t->sG + ENS_POST_STRIDE)))) return rc;
+    t->wpart = en.dWork;
+    t->bpart = t->wpart + S * t->sW;
+    t->meanpart = t->bpart + S * t->sB;
+    t->vpart = t->meanpart + S * t->sM;
+    t->gpart = t->vpart + S * t->sV;
+    t->post = t->gpart + S * t->sG;
+    if (!en.dCounter) {
+        if ((rc = en.dCounter.reserve(1 + GP_ENS_MAX_S))) return rc;
+        HIPCHK(hipMemsetAsync(en.dCounter, 0, sizeof(unsigned int) * (1 + GP_ENS_MAX_S), g->s));
+        en.member_base = en.ens_base = 0;
+    }
+    if (!en.hOut) {
+        HIPCHK(hipHostMalloc((void **)&en.hOut, sizeof(double) * (ROWS_OUT_DOUBLES + 1), hipHostMallocDefault));
+        en.hOut[ROWS_OUT_DOUBLES] = 0.0;
+    }
+    t->counter = en.dCounter;
+    t->Li = en.dLi;
+    t->sLi = Npad * Npad;
+    t->alpha = en.dAlpha;
+    t->sAlpha = Npad;
+    t->kpt = (const KernParams *)en.dKp.p;
+    t->noise = ens_noise(g);
+    t->fmin = ens_fmin(g);
+    return 0;
+}
+
+// rows_wait of api_rows.hip for the S-fold grid: every member's counter took rows_finish_grid(N) arrivals, the ensemble's S
+static int ens_wait(gp_ctx *g, double ticket) {
+    EnsState &en = g->ens;
+    en.member_base += rows_finish_grid(g->N);
+    en.ens_base += (unsigned)en.S;
+    hipError_t e = hipStreamSynchronize(g->s);
+    int pending = gp_pending_error();
+    if (!pending && e == hipSuccess && en.hOut[ROWS_OUT_DOUBLES] == ticket) return 0;
+    const std::string noted = pending ? gp_last_error() : std::string();
+    hipStreamSynchronize(g->s);
+    hipMemset(en.dCounter, 0, sizeof(unsigned int) * (1 + GP_ENS_MAX_S));
+    en.member_base = en.ens_base = 0;
+    if (pending) return fail(GP_ERR_HIP, "%s", noted.c_str());
+    if (e != hipSuccess) return fail(GP_ERR_HIP, "hipStreamSynchronize -> %s (ensemble pass)", hipGetErrorString(e));
+    return fail(GP_ERR_HIP, "the ensemble kernels did not complete (ticket %.0f, expected %.0f)", en.hOut[ROWS_OUT_DOUBLES], ticket);
+}
+
+// passes of up to ROWS_MAX_M locations (four per pass is what the ensemble takes: no wide pass); post (when given) receives the S members' result blocks of each pass before unpack runs
+template <class Unpack>
+static int ens_passes(gp_ctx *g, const double *Xs, int M, int want_grad, int include_noise, int acq_on, int type, double par,
+                      std::vector<double> *post, Unpack unpack) {
+    int rc;
+    EnsRows t;
+    if ((rc = ens_rows_table(g, &t))) return rc;
+    EnsState &en = g->ens;
+    const int D = g->D;
+    // locations per pass: ROWS_MAX_M while their coordinates fit the kernel arguments (D <= 32), else what fits (3 at D = 33, 2 at
+    // D = GP_MAX_D); a location's bits do not depend on its company, so the split is invisible in the results
+    const int width = std::min(ROWS_MAX_M, ROWS_MAX_XS / D);
+    if (post) post->resize((size_t)en.S * ENS_POST_STRIDE);
+    for (int m0 = 0; m0 < M; m0 += width) {
+        const int mc = std::min(width, M - m0);
+        RowsX rx;
+        rx.M = mc;
+        memcpy(rx.xs, Xs + (long)m0 * D, sizeof(double) * mc * D);
+        const double ticket = (en.ticket += 1.0);
+        launch_ens_rows(g->s, t, en.S, rx, g->dX, g->N, g->Npad, want_grad, include_noise, acq_on, type, par, en.member_base, en.ens_base,
+                        en.hOut, ticket);
+        if (post)
+            HIPCHK(hipMemcpyAsync(post->data(), t.post, sizeof(double) * en.S * ENS_POST_STRIDE, hipMemcpyDeviceToHost, g->s));
+        if ((rc = ens_wait(g, ticket))) return rc;
+        unpack(m0, mc, rows_layout(mc));
+    }
+    return 0;
+}
+
+extern "C" int gp_ens_predict_rows(gp_t *g, const double *Xs, int64_t M, int include_noise, double *mean, double *var, double *dmdx,
+                                   double *dvdx) {
+    if (!g || !Xs) return fail(GP_ERR_ARG, "null argument");
+    int rc;
+    if ((rc = ens_ready(g))) return rc;
+    if (M < 1 || M > ROWS_WIDE_M) return fail(GP_ERR_ARG, "gp_ens_predict_rows takes 1 <= M <= %d locations", ROWS_WIDE_M);
+    if ((dmdx == nullptr) != (dvdx == nullptr)) return fail(GP_ERR_ARG, "dmdx and dvdx come together");
+    const int D = g->D, S = g->ens.S;
+    std::vector<double> post;
+    return ens_passes(g, Xs, (int)M, dmdx != nullptr, include_noise, 0, GP_ACQ_EI, 0.0, &post, [&](int m0, int mc, int MV) {
+        for (int z = 0; z < S; ++z) {
+            const double *o = post.data() + (size_t)z * ENS_POST_STRIDE;
+            for (int mm = 0; mm < mc; ++mm) {
+                const long at = (long)z * M + m0 + mm;
+                if (mean) mean[at] = o[mm];
+                if (var) var[at] = o[MV + mm];
+                if (dmdx) {
+                    memcpy(dmdx + at * D, o + 3 * MV + (long)mm * D, sizeof(double) * D);
+                    memcpy(dvdx + at * D, o + 3 * MV + (long)MV * D + (long)mm * D, sizeof(double) * D);
+                }
+            }
+        }
+    });
+}
+
+static int ens_check_acq(int type) {
+    if (type < GP_ACQ_EI || type > GP_ACQ_MPI) return fail(GP_ERR_ARG, "unknown acquisition %d", type);
+    return 0;
+}
+
+extern "C" int gp_ens_acq_rows(gp_t *g, const double *Xs, int64_t M, int type, double par, double *out, double *dout) {
+    if (!g || !Xs || !out) return fail(GP_ERR_ARG, "null argument");
+    int rc;
+    if ((rc = ens_ready(g))) return rc;
+    if (M < 1 || M > ROWS_WIDE_M) return fail(GP_ERR_ARG, "gp_ens_acq_rows takes 1 <= M <= %d locations", ROWS_WIDE_M);
+    if ((rc = ens_check_acq(type))) return rc;
+    const int D = g->D;
+    const double *o = nullptr;
+    return ens_passes(g, Xs, (int)M, dout != nullptr, 1, 1, type, par, nullptr, [&](int m0, int mc, int MV) {   // with_noise, gpmodel.py:271
+        o = g->ens.hOut;
+        for (int mm = 0; mm < mc; ++mm) {
+            out[m0 + mm] = o[2 * MV + mm];
+            if (dout) memcpy(dout + (long)(m0 + mm) * D, o + 3 * MV + 2L * MV * D + (long)mm * D, sizeof(double) * D);
+        }
+    });
+}
+
+// ---- the table route -------------------------------------------------------------------------------------------------------------
+// scores of the resident candidates (gp_set_candidates) into en.dAcq
+static int ens_table_scores(gp_ctx *g, int type, double par) {
+    EnsState &en = g->ens;
+    if (g->M < 1) return fail(GP_ERR_STATE, "gp_set_candidates first");
+    int rc;
+    if ((rc = ens_check_acq(type))) return rc;
+    const long M = g->M, N = g->N, Npad = g->Npad, S = en.S;
+    const int nt = (int)(Npad / GP_TILE);
+    const long chunk = std::min<long>(GP_ENS_TABLE_CHUNK, round_up(M, GP_TILE));
+    if ((rc = en.dKx.reserve(S * chunk * Npad))) return rc;
+    if ((rc = en.dW.reserve(S * chunk * Npad))) return rc;
+    if ((rc = en.dAcq.reserve(M))) return rc;
+    for (long m0 = 0; m0 < M; m0 += chunk) {
+        const long mc = std::min(chunk, M - m0), mcpad = round_up(mc, GP_TILE);
+        for (int z = 0; z < S; ++z)
+            launch_cross_k(g->s, en.dKx + z * chunk * Npad, Npad, g->dXs + m0 * g->D, mc, mcpad, g->dX, N, Npad, en.kp[z]);
+        GemmOpt o;   // W_z = Kx_z Li_z^T for every member in one launch
+        o.batch = o.members = (int)S;
+        o.sC = o.sA = chunk * Npad;
+        o.sB = Npad * Npad;
+        gemm(g, g->s, 0, en.dW, Npad, en.dKx, Npad, en.dLi, Npad, 1, (int)Npad, TileSet{0, (int)(mcpad / GP_TILE), 0, nt, 0}, o);
+        launch_ens_table_reduce(g->s, en.dKx, en.dW, chunk, Npad, N, en.dAlpha, Npad, (const KernParams *)en.dKp.p, ens_noise(g),
+                                ens_fmin(g), (int)S, type, par, mc, en.dAcq + m0);
+    }
+    return 0;
+}
+
+extern "C" int gp_ens_acq(gp_t *g, int type, double par, double *out) {
+    if (!g || !out) return fail(GP_ERR_ARG, "null argument");
+    int rc;
+    if ((rc = ens_ready(g))) return rc;
+    if ((rc = ens_table_scores(g, type, par))) return rc;
+    HIPCHK(hipMemcpyAsync(out, g->ens.dAcq, sizeof(double) * g->M, hipMemcpyDeviceToHost, g->s));
+    GP_SYNC(g->s);
+    return 0;
+}
+
+extern "C" int gp_ens_acq_argbest(gp_t *g, int type, double par, int sense, int64_t *idx, double *val) {
+    if (!g || !idx || !val) return fail(GP_ERR_ARG, "null argument");
+    int rc;
+    if ((rc = ens_ready(g))) return rc;
+    if ((rc = check_sense(sense))) return rc;
+    if ((rc = ens_table_scores(g, type, par))) return rc;
+    launch_argbest(g->s, g->ens.dAcq, g->M, sense, g->dRedV + RED_RESULT.off, g->dRedI + RED_RESULT.off, g->dRedV + RED_PARTIAL.off,
+                   g->dRedI + RED_PARTIAL.off);
+    double hv = 0.0;
+    long long hi = 0;
+    HIPCHK(hipMemcpyAsync(&hv, g->dRedV + RED_RESULT.off, sizeof(double), hipMemcpyDeviceToHost, g->s));
+    HIPCHK(hipMemcpyAsync(&hi, g->dRedI + RED_RESULT.off, sizeof(long long), hipMemcpyDeviceToHost, g->s));
+    GP_SYNC(g->s);
+    *val = hv;
+    *idx = (int64_t)hi;
+    return 0;
+}

@@ -204,6 +204,26 @@ struct SparseState {
     long rows_fused_calls = 0, rows_fallback_calls = 0;
 };
 
+// The ensemble (api_ens.hip): S hyper-parameter members over the context's X, Y -- each with alpha, explicit inverse factor,
+// parameters, jitter and fmin of its own -- kept beside the context's own fit and independent of it: nothing here is read or
+// written by the other entry points (gp_set_data alone drops it), and the ensemble entries leave the context's fit, candidates'
+// posterior and parameters as they were.
+struct EnsState {
+    int S = 0;                 // members of the valid ensemble (0: none)
+    DevBuf<double> dLi;        // [S] Npad x Npad inverse factors (lower, row-major, zeros above the diagonal)
+    DevBuf<double> dAlpha;     // [S] Npad
+    DevBuf<double> dTab;       // noise [S], fmin [S]
+    DevBuf<signed char> dKp;   // KernParams [S]
+    DevBuf<double> dWork;      // the rows passes' partials per member, then the members' result blocks
+    DevBuf<unsigned int> dCounter;   // [0] members arrived, [1 + z] member z's workgroups
+    double *hOut = nullptr;    // pinned result block of the integrated acquisition (+ the ticket behind it)
+    double ticket = 0.0;
+    unsigned int member_base = 0, ens_base = 0;
+    std::vector<double> noise, fmin, jitter;
+    std::vector<KernParams> kp;
+    DevBuf<double> dKx, dW, dAcq;    // table route: K_z(Xs, X) and Kx Li_z^T per chunk, the scores
+};
+
 struct gp_ctx {
     int device = 0;
     hipStream_t s = nullptr;       // main stream
@@ -351,6 +371,7 @@ struct gp_ctx {
     double warp_logjac = 0.0;   // sum log f'(y) of the warp in force
     DevBuf<double> dWarp;  // 9 M: posterior by value (mean, var), then warped mean, variance, median and the four partials
     SparseState sp;     // the sparse model (api_sparse.hip)
+    EnsState ens;       // the ensemble (api_ens.hip)
     bool dead = false;  // gp_shutdown ran: the device's streams are gone, only gp_destroy is still valid
 };
 

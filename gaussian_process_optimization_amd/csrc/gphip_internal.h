@@ -283,6 +283,32 @@ void launch_rows_mean_grad(hipStream_t s, const RowsX &rx, const KernParams &kp,
                            const RowsWork &w, double *out);
 void launch_transpose_tri(hipStream_t s, double *dst, const double *src, long n, int mode);
 
+// ---- ens_rows.hip: the same passes over an ensemble of S members, the member as a grid dimension --------------------------------
+#define ENS_ROWS_RB 32                       // rows of the tile per workgroup: what rows_block_height gives every matrix the ensemble takes
+#define ENS_POST_STRIDE ROWS_OUT_DOUBLES     // doubles between two members' result blocks (each laid out as the single model's)
+struct EnsRows {              // member z's operand at base + z * stride
+    const double *Li;         // inverse factors, Npad x Npad each
+    long sLi;
+    const double *alpha;
+    long sAlpha;
+    const KernParams *kpt;    // per-member parameters
+    const double *noise, *fmin;
+    double *wpart, *bpart, *meanpart, *vpart, *gpart;   // RowsWork partials per member
+    long sW, sB, sM, sV, sG;
+    double *post;             // per-member result blocks
+    unsigned int *counter;    // [0]: members arrived; [1 + z]: workgroups of member z arrived (neither is ever reset between passes)
+};
+// One pass of rx.M <= ROWS_MAX_M locations: forward (+ backward) + finish, whatever S.  Member z's workgroups count from member_base
+// at counter[1 + z], the members from ens_base at counter[0]; the host adds rows_finish_grid(N) and S to them after the pass.
+// acq_on: the integrated rule (type, par; negated) into the host-visible block `out`; the ticket lands behind it either way.
+void launch_ens_rows(hipStream_t s, const EnsRows &t, int S, const RowsX &rx, const double *X, long N, long Npad, int want_grad,
+                     int include_noise, int acq_on, int type, double par, unsigned member_base, unsigned ens_base, double *out,
+                     double ticket);
+// out[c] = mean over members of the negated rule at candidate row c < M, from Kx = K_z(Xs, X) and W = Kx Li_z^T ([S][ldr][Npad] each)
+void launch_ens_table_reduce(hipStream_t s, const double *Kx, const double *W, long ldr, long Npad, long N, const double *alpha,
+                             long sAlpha, const KernParams *kpt, const double *noise, const double *fmin, int S, int type, double par,
+                             long M, double *out);
+
 // ---- grad.hip ---------------------------------------------------------------------------------
 #define GP_GRAD_CH 16
 #define GP_GRAD_NACC (GP_GRAD_CH + 2)

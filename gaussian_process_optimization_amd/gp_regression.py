@@ -235,7 +235,9 @@ class GPRegression(Parameterized):
         return self._lml
 
     def objective_function(self):
-        """Model.objective_function, core/model.py:96-110 (no priors on this path)."""
+        """Model.objective_function, core/model.py:96-110: -log likelihood, and -log prior when a prior is set."""
+        if self._has_priors():
+            return -float(self.log_likelihood()) - self.log_prior()
         return -float(self.log_likelihood())
 
     def _log_likelihood_gradients_natural(self):
@@ -259,7 +261,12 @@ class GPRegression(Parameterized):
 
     def objective_function_gradients(self):
         """Model.objective_function_gradients, core/model.py:112-127: d(-lml)/d(optimizer_array)."""
-        return -self._transform_gradients(self._log_likelihood_gradients_natural())
+        natural = self._log_likelihood_gradients_natural()
+        if self._has_priors():   # core/model.py:112-127: the priors' gradients join the likelihood's before the chain rule
+            natural = [(p, np.asarray(g, dtype=float).reshape(-1) + (p.prior.lnpdf_grad(p.values) + (
+                p.transform.log_jacobian_grad(p.values) if hasattr(p.transform, "log_jacobian_grad") else 0.0)
+                if p.prior is not None else 0.0)) for p, g in natural]
+        return -self._transform_gradients(natural)
 
     @property
     def gradient(self):

@@ -10,7 +10,9 @@ value on every acquisition call), ``predict_withGradients`` (:131-142).
 import numpy as np
 
 from . import kern as _kern
+from . import priors as _priors
 from .gp_regression import GPRegression
+from .mcmc import HMC
 from .sparse_gp import SparseGPRegression
 
 
@@ -166,3 +168,101 @@ class GPModel(BOModel):
     def get_covariance_between_points(self, x1, x2):
         """Posterior covariance between two point sets (gpmodel.py:173-177)."""
         return self.model.posterior_covariance_between_points(x1, x2)
+
+
+class GPModel_MCMC(BOModel):
+    """GP surrogate whose hyper-parameters are integrated out by HMC (GPyOpt/GPyOpt/models/gpmodel.py:180-355): same
+    constructor keywords plus ``device``, the same lists of one array per sample from ``predict``, ``predict_withGradients`` and
+    ``get_fmin``.  The reference writes every sample into the model and refactorises for each of those calls (:266-272, 285-291,
+    307-315); here ``updateModel`` ends with ONE ``gp_ens_fit`` that factors the samples in lockstep and keeps their posteriors
+    on the device, and the calls above read that ensemble (``gp_ens_predict_rows``, eight locations per call)."""
+    MCMC_sampler = True
+    analytical_gradient_prediction = True
+
+    def __init__(self, kernel=None, noise_var=None, exact_feval=False, n_samples=10, n_burnin=100, subsample_interval=10,
+                 step_size=1e-1, leapfrog_steps=20, verbose=False, device=0):
+        vars(self).update(kernel=kernel, noise_var=noise_var, exact_feval=exact_feval, verbose=verbose, n_samples=n_samples,
+                          subsample_interval=subsample_interval, n_burnin=n_burnin, step_size=step_size,
+                          leapfrog_steps=leapfrog_steps, device=device, model=None, hmc=None, hmc_samples=None, _fmins=None)
+
+    def _create_model(self, X, Y):
+        """Default kernel RBF with variance 1, default noise 1 % of Var(Y); Gamma priors with mean 2 and variance 4 on the
+        kernel parameters and on the noise; ``exact_feval`` fixes the noise at 1e-6 (gpmodel.py:213-238)."""
+        self.input_dim = X.shape[1]
+        chosen, self.kernel = self.kernel, None
+        if chosen is None:
+            chosen = _kern.RBF(self.input_dim, variance=1.)
+        noise = Y.var() * 0.01 if self.noise_var is None else self.noise_var
+        gp = GPRegression(X, Y, kernel=chosen, noise_var=noise, device=self.device)
+        gp.kern.set_prior(_priors.Gamma.from_EV(2., 4.))
+        gp.likelihood.variance.set_prior(_priors.Gamma.from_EV(2., 4.))
+        if self.exact_feval:
+            gp.Gaussian_noise.constrain_fixed(1e-6, warning=False)
+        else:
+            gp.Gaussian_noise.constrain_positive(warning=False)
+        self.model = gp
+
+    def updateModel(self, X_all, Y_all, X_new, Y_new):
+        """gpmodel.py:240-255: the MAP search, a 1 % perturbation of every parameter, the HMC chain, its thinning -- then the
+        kept samples are factored once and stay resident."""
+        if self.model is None:
+            self._create_model(X_all, Y_all)
+        else:
+            self.model.set_XY(X_all, Y_all)
+        gp = self.model
+        gp.optimize(max_iters=200)
+        gp[:] = gp.param_array * (1. + np.random.randn(gp.param_array.size) * 0.01)
+        self.hmc = HMC(gp, stepsize=self.step_size)
+        ss = self.hmc.sample(num_samples=self.n_burnin + self.n_samples * self.subsample_interval, hmc_iters=self.leapfrog_steps)
+        self.hmc_samples = ss[self.n_burnin::self.subsample_interval]
+        self._fit_ensemble()
+
+    def _members(self):
+        """(variance [S], lengthscale [S, nls], noise [S]) of the kept samples: a sample holds the unfixed parameters in
+        ``param_array`` order -- kernel variance, lengthscale(s), then the noise unless ``exact_feval`` fixed it."""
+        gp, ss = self.model, np.atleast_2d(self.hmc_samples)
+        nls = gp.kern.lengthscale.size
+        noise = ss[:, 1 + nls] if ss.shape[1] > 1 + nls else np.full(ss.shape[0], float(gp.likelihood.variance))
+        return ss[:, 0].copy(), ss[:, 1:1 + nls].copy(), np.asarray(noise, dtype=float).copy()
+
+    def _fit_ensemble(self):
+        gp = self.model
+        gp._push_params()      # kernel family, ARD and lengthscale count of the members come from the handle's parameters
+        gp._dirty = True       # (which drops the handle's own fit: the model refits when it is next asked for itself)
+        var, ls, noise = self._members()
+        _, _, _, self._fmins = gp._h.ens_fit(var, ls, noise, gp.max_jitter_tries)
+
+    def _rows(self, X, grad):
+        """The S posteriors at the rows of ``X``, eight locations per device call: (mean, var[, dmdx, dvdx]) as [S, M(, D)]."""
+        X = np.atleast_2d(np.asarray(X, dtype=float))
+        parts = [self.model._h.ens_predict_rows(X[i:i + 8], True, grad=grad) for i in range(0, X.shape[0], 8)]
+        return [np.concatenate([p[k] for p in parts], axis=1) for k in range(4 if grad else 2)]
+
+    def predict(self, X):
+        """Lists of S means [M, 1] and S standard deviations [M, 1] (gpmodel.py:257-277)."""
+        mean, var = self._rows(X, False)
+        return [m[:, None] for m in mean], [np.sqrt(np.clip(v, _VAR_FLOOR, np.inf))[:, None] for v in var]
+
+    def get_fmin(self):
+        """The S minima of the members' posterior means over the training inputs (gpmodel.py:279-295), kept by the fit."""
+        return [float(f) for f in self._fmins]
+
+    def predict_withGradients(self, X):
+        """Lists of S means, standard deviations [M, 1] and their x-gradients [M, D] (gpmodel.py:297-324)."""
+        mean, var, dm, dv = self._rows(X, True)
+        stds = [np.sqrt(np.clip(v, _VAR_FLOOR, np.inf))[:, None] for v in var]
+        return [m[:, None] for m in mean], stds, [d for d in dm], [d / (2 * s) for d, s in zip(dv, stds)]
+
+    def copy(self):
+        """A working twin (the reference's ``copy`` builds the wrong class, gpmodel.py:331)."""
+        twin = GPModel_MCMC(kernel=self.model.kern.copy(), noise_var=self.noise_var, exact_feval=self.exact_feval,
+                            n_samples=self.n_samples, n_burnin=self.n_burnin, subsample_interval=self.subsample_interval,
+                            step_size=self.step_size, leapfrog_steps=self.leapfrog_steps, verbose=self.verbose, device=self.device)
+        twin.updateModel(self.model.X, self.model.Y, None, None)
+        return twin
+
+    def get_model_parameters(self):
+        return np.atleast_2d(self.model[:])
+
+    def get_model_parameters_names(self):
+        return self.model.parameter_names_flat().tolist()

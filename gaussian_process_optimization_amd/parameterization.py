@@ -34,6 +34,14 @@ class Logexp(object):
         f = np.asarray(f, dtype=float)
         return df * np.where(f > _LIM_VAL, 1.0, -np.expm1(-f))
 
+    def log_jacobian(self, f):
+        """ln |df / dx| of the transform at the model-space value f: what a prior on f adds to the log density over x."""
+        f = np.asarray(f, dtype=float)
+        return np.where(f > _LIM_VAL, f, np.log(np.expm1(f))) - f
+
+    def log_jacobian_grad(self, f):
+        return 1.0 / np.expm1(np.asarray(f, dtype=float))
+
 
 class Logistic(object):
     """Bounded transform onto (lower, upper)."""
@@ -65,6 +73,7 @@ class Param(object):
         self.gradient = np.zeros_like(self._v)
         self.transform = transform if transform is not None else Logexp()
         self.is_fixed = False
+        self.prior = None
         self._parent = None
 
     # -- value access -----------------------------------------------------------
@@ -139,6 +148,17 @@ class Param(object):
     def constrain_positive(self, warning=True):
         self.transform = Logexp()
         self.is_fixed = False
+
+    def set_prior(self, prior, warning=True):
+        """Priorizable.set_prior (priorizable.py:25-41): a prior on the positive half-line constrains the parameter positive."""
+        self.prior = prior
+        if getattr(prior, "domain", None) == "positive" and not isinstance(self.transform, Logexp):
+            self.transform = Logexp()      # (a fixed parameter stays fixed: the fix is no transformation)
+        self._changed()
+
+    def unset_priors(self):
+        self.prior = None
+        self._changed()
 
 
 class Parameterized(object):
@@ -219,6 +239,51 @@ class Parameterized(object):
             p._v[:] = p.transform.f(x[i:i + p.size])
             i += p.size
         self._notify()
+
+    @property
+    def unfixed_param_array(self):
+        """The values of the parameters that are not fixed, in ``param_array`` order (what HMC records, hmc.py:46,56)."""
+        ps = [p for p in self.flattened_parameters() if not p.is_fixed]
+        return np.concatenate([p.values for p in ps]) if ps else np.zeros(0)
+
+    # -- priors (priorizable.py:25-82) ---------------------------------------------------------
+    def set_prior(self, prior, warning=True):
+        for p in self.flattened_parameters():
+            p.set_prior(prior, warning)
+
+    def unset_priors(self):
+        for p in self.flattened_parameters():
+            p.unset_priors()
+
+    def _has_priors(self):
+        return any(p.prior is not None for p in self.flattened_parameters())
+
+    def log_prior(self):
+        """Sum of the priors' log densities plus, where a priored parameter is transformed, the log Jacobian of its transform
+        (priorizable.py:49-65); 0 without priors."""
+        total = 0.0
+        for p in self.flattened_parameters():
+            if p.prior is None:
+                continue
+            total += float(np.sum(p.prior.lnpdf(p.values)))
+            if hasattr(p.transform, "log_jacobian"):
+                total += float(np.sum(p.transform.log_jacobian(p.values)))
+        return total
+
+    def _log_prior_gradients(self):
+        """d log_prior / d param_array (priorizable.py:67-82): zeros where no prior is set; the scalar 0 without priors."""
+        ps = self.flattened_parameters()
+        if not any(p.prior is not None for p in ps):
+            return 0.
+        out = []
+        for p in ps:
+            g = np.zeros(p.size)
+            if p.prior is not None:
+                g += p.prior.lnpdf_grad(p.values)
+                if hasattr(p.transform, "log_jacobian_grad"):
+                    g += p.transform.log_jacobian_grad(p.values)
+            out.append(g)
+        return np.concatenate(out)
 
     def _transform_gradients(self, natural_grads):
         """Chain rule through the transforms (paramz Model._transform_gradients)."""

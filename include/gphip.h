@@ -522,6 +522,44 @@ int gp_sparse_acq_rows(gp_t *gp, const double *Xs, int64_t M, int type, double p
 /* how many of those calls took the fused path / the table arithmetic since gp_create (route checks of the tests) */
 int gp_sparse_rows_stats(gp_t *gp, int64_t *fused, int64_t *fallback);
 
+/* ---- ensemble: S hyper-parameter members with resident posteriors, acquisitions integrated over them ----------------
+ * GPModel_MCMC (GPyOpt/GPyOpt/models/gpmodel.py:180-355) with acquisitions/{EI,MPI,LCB}_mcmc.py.  An ensemble is S members
+ * over the context's (X, Y), each with hyper-parameters of its own (an HMC sample, gpmodel.py:243-262); it is kept beside the
+ * context's own fit and independent of it.  gp_set_data drops it; gp_set_params, gp_fit and gp_set_candidates do not, and no
+ * ensemble entry touches the context's fit, candidate posterior or parameters.  Always true fp64.  Kernels: csrc/ens_rows.hip.
+ *
+ * GP_ERR_ARG: S outside 1..64, Npad > 2048 (the batched fit's caps), P != 1, M outside 1..8 of the rows entries, an unknown
+ * acquisition, a bad sense.  GP_ERR_STATE: no data or parameters, the Gower option on (the lengthscale does not enter a Gower
+ * K), an output warp on, a scoring call before a valid gp_ens_fit, a table call before gp_set_candidates. */
+
+/* Replaces the model.param_array = sample; model._trigger_params_changed() of every call (gpmodel.py:266-272, 285-291, 307-315):
+ * the S members are factored ONCE, in lockstep, with the launch sequences and the per-member jitter ladder of
+ * gp_fit_grad_batch, and each member's alpha, explicit inverse factor, parameters, jitter and fmin are KEPT.  lengthscale is
+ * [S, nls] with nls of the last gp_set_params (kernel family and ard come from there too).  fmin[z] = min over the training
+ * inputs of member z's posterior mean (get_fmin, gpmodel.py:285-291).  lml / logdet / jitter_used / fmin may be NULL.  A
+ * member that cannot be factored after maxtries fails the whole call with gp_fit's not-positive-definite code; the ensemble
+ * is then invalid. */
+int gp_ens_fit(gp_t *gp, int S, const double *variance, const double *lengthscale, const double *noise, int maxtries, double *lml,
+               double *logdet, double *jitter_used, double *fmin);
+/* *S = members of the valid ensemble, 0 when there is none. */
+int gp_ens_info(gp_t *gp, int *S);
+/* GPModel_MCMC.predict / predict_withGradients (gpmodel.py:264-276, 293-323) without the clip: every member's posterior at
+ * M <= 8 locations given by value, mean / var [S][M] (either may be NULL), dmdx / dvdx [S][M][D] (both or neither).  Member z's
+ * numbers are, bit for bit, gp_predict_rows' on a context fitted with z's parameters: whatever S, z's position and the other
+ * locations of the call.  The launches of a call do not depend on S (the member is a grid dimension). */
+int gp_ens_predict_rows(gp_t *gp, const double *Xs, int64_t M, int include_noise, double *mean, double *var, double *dmdx,
+                        double *dvdx);
+/* AcquisitionEI_MCMC / MPI_MCMC / LCB_MCMC ._compute_acq[_withGradients] (EI_mcmc.py:32-59, MPI_mcmc.py:32-59,
+ * LCB_mcmc.py:33-60), negated as gp_acq_rows returns it: the mean over members of the rule (csrc/acq_math.h) at the member's own
+ * fmin, mean and std = sqrt(max(var + noise, 1e-10)), dstd = dvar / (2 std) (gpmodel.py:313-317); no normaliser.  out [M],
+ * dout [M, D] or NULL, M <= 8.  Members are added in member order: bitwise repeatable. */
+int gp_ens_acq_rows(gp_t *gp, const double *Xs, int64_t M, int type, double par, double *out, double *dout);
+/* The same value over the table made resident by gp_set_candidates, any M: one cross covariance per member, one batched GEMM
+ * against the inverse factors, one reduce.  Agrees with gp_ens_acq_rows to rounding (another contraction order). */
+int gp_ens_acq(gp_t *gp, int type, double par, double *out);
+/* arg-best of that vector: sense +1 largest, -1 smallest; ties go to the lowest index. */
+int gp_ens_acq_argbest(gp_t *gp, int type, double par, int sense, int64_t *idx, double *val);
+
 /* ---- measurement ---------------------------------------------------------
  * Phase timings of the last gp_fit / gp_predict measured with HIP events on the
  * library's stream; names[i] is a static string, ms[i] milliseconds, flops[i] the
