@@ -162,6 +162,8 @@ SIGNATURES = [
     ("gp_gemm_busy", ctypes.c_int, [_vp, c_double_p]),
     ("gp_gemm_trace", ctypes.c_int, [_vp, ctypes.c_int, c_int64_p, c_int_p, c_double_p]),
     ("gp_synchronize", ctypes.c_int, [_vp]),
+    ("gp_debug_gemm", ctypes.c_int, [_vp, ctypes.c_int, c_double_p, c_double_p, c_double_p, ctypes.c_int64, ctypes.c_int,
+                                     ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
     ("gp_set_option", ctypes.c_int, [_vp, ctypes.c_char_p, ctypes.c_int64]),
 ]
 
@@ -921,6 +923,17 @@ class Handle(object):
 
     def set_option(self, name, value):
         check(self.lib, self.lib.gp_set_option(self.h, name.encode(), int(value)), "gp_set_option")
+
+    def debug_gemm(self, mode, C, A, B, K, r0, r1, c0, c1, tri=False):
+        """Test hook: one GEMM launch on host operands (gp_debug_gemm); returns the new C, the arguments stay as they are."""
+        A, B = as_f64(A, 2), as_f64(B, 2)
+        out = np.array(C, dtype=np.float64, order="C")
+        ld = out.shape[1]
+        if A.shape != (r1 * 128, ld) or B.shape != (c1 * 128, ld) or out.shape[0] != r1 * 128:
+            raise ValueError("C, A [r1 * 128, ld] and B [c1 * 128, ld] share one pitch")
+        check(self.lib, self.lib.gp_debug_gemm(self.h, int(mode), dptr(out), dptr(A), dptr(B), ld, int(K), int(r0), int(r1),
+                                               int(c0), int(c1), int(bool(tri))), "gp_debug_gemm")
+        return out
 
     # -- RCCL ------------------------------------------------------------------
     def comm_unique_id(self):

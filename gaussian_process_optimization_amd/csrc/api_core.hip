@@ -2,6 +2,8 @@
 // launcher and the small getters.  See include/gphip.h for the contract (reference file:line per entry point).
 #include "api_internal.h"
 
+#define BK_MIN 16  // the GEMM's stage depth (gemm.hip): every contraction length is a multiple of it
+
 thread_local std::string g_err;
 
 // first failed launch / stream operation of the calling thread since the last report (gphip_internal.h)
@@ -155,8 +157,12 @@ void gemm(gp_ctx *g, hipStream_t s, int mode, double *C, long ldc, const double 
     const long n = tileset_count(ts) * (o.batch / o.members), n_all = tileset_count(ts) * o.batch;
     if (n <= 0 || K <= 0) return;
     GemmOpt oo = o;
-    if (n >= 1024 && !oo.stagger) oo.stagger = g->stagger;
-    if (n >= 1024 && g->waves8) oo.waves8 = 1;  // 4 waves/SIMD: +2 % on the long launches (measured)
+    if (n >= g->long_min_tiles && !oo.stagger) oo.stagger = g->stagger;
+    if (n >= g->long_min_tiles && g->waves8) oo.waves8 = 1;  // 4 waves/SIMD: +2 % on the long launches (measured)
+    // The scheduled K loop where a long launch has the chip to itself: on the context's own stream.  On the look-ahead's side
+    // streams (trailing updates and pipelined candidate stages beside the factorisation's latency chain) each launch is faster
+    // with it too, but the step is not: the chain, which sets the pace there, loses more than the launches gain (measured).
+    oo.sched = g->gemm_sched && (s == g->s || g->gemm_sched_side);
     // ... or split each tile into two 64-row strips (a strip reads only its own rows of A: still safe in place)
     if (oo.inplace && g->trsm_rows64 && !oo.waves8) oo.rows64 = g->trsm_rows64;  // 1 / 64: two strips, 32: four
     // short launches (the factorisation's latency chain, the uneven triangular-K products) run as 64x64 work units
@@ -401,6 +407,9 @@ static const OptDesc g_options[] = {
     {"chain_small_below", &gp_ctx::chain_small_below, OPT_RAW},
     {"waves8", &gp_ctx::waves8, OPT_BOOL},
     {"stagger", &gp_ctx::stagger, OPT_RAW},
+    {"gemm_sched", &gp_ctx::gemm_sched, OPT_BOOL},
+    {"gemm_sched_side", &gp_ctx::gemm_sched_side, OPT_BOOL},
+    {"long_min_tiles", &gp_ctx::long_min_tiles, OPT_FLOOR, 1},
     {"trsm_rows64", &gp_ctx::trsm_rows64, OPT_RAW},
     {"rns_group_fit", &gp_ctx::rns_group_fit, OPT_RANGE, 1, 16},
     {"rns_group", &gp_ctx::rns_group, OPT_RANGE, 1, 16},
@@ -475,6 +484,29 @@ extern "C" int gp_set_option(gp_t *g, const char *name, int64_t value) {
         g->mc_max = round_up(value, GP_TILE);
     } else
         return fail(GP_ERR_ARG, "unknown option %s", name);
+    return 0;
+}
+
+// Test hook (tests/test_gpu_gemm_sched.py): one GEMM launch on host operands, through gemm() and so through the instance selection
+// and the options every other launch of the context takes.
+extern "C" int gp_debug_gemm(gp_t *g, int mode, double *C, const double *A, const double *B, int64_t ld, int K, int r0, int r1,
+                             int c0, int c1, int tri) {
+    if (!g || !C || !A || !B) return fail(GP_ERR_ARG, "null argument");
+    GP_DEAD_CHECK(g);
+    if (mode < 0 || mode > 1 || K < BK_MIN || K % BK_MIN || r0 < 0 || r1 <= r0 || c0 < 0 || c1 <= c0 || r1 > 256 || c1 > 256 ||
+        (tri && r1 <= c1 - 1) || ld % 2 || ld < K || ld < (int64_t)c1 * GP_TILE)
+        return fail(GP_ERR_ARG, "gp_debug_gemm: bad shape (mode %d K %d rows %d..%d columns %d..%d ld %ld)", mode, K, r0, r1, c0, c1, (long)ld);
+    HIPCHK(hipSetDevice(g->device));
+    const long ra = (long)r1 * GP_TILE, rb = (long)c1 * GP_TILE;
+    DevBuf<double> dC, dA, dB;
+    int rc;
+    if ((rc = dC.reserve(ra * ld)) || (rc = dA.reserve(ra * ld)) || (rc = dB.reserve(rb * ld))) return rc;
+    HIPCHK(hipMemcpyAsync(dC, C, (size_t)(ra * ld) * sizeof(double), hipMemcpyHostToDevice, g->s));
+    HIPCHK(hipMemcpyAsync(dA, A, (size_t)(ra * ld) * sizeof(double), hipMemcpyHostToDevice, g->s));
+    HIPCHK(hipMemcpyAsync(dB, B, (size_t)(rb * ld) * sizeof(double), hipMemcpyHostToDevice, g->s));
+    gemm(g, g->s, mode, dC, ld, dA, ld, dB, ld, 1, K, TileSet{r0, r1, c0, c1, tri ? 1 : 0});
+    HIPCHK(hipMemcpyAsync(C, dC, (size_t)(ra * ld) * sizeof(double), hipMemcpyDeviceToHost, g->s));
+    GP_SYNC(g->s);
     return 0;
 }
 

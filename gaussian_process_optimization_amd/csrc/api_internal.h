@@ -335,6 +335,9 @@ struct gp_ctx {
     int trsm_rows64 = 32;    // in-place panel solves as 64- or 32-row strips of the tile (2 or 4 workgroups per tile)
     int waves8 = 1;
     int stagger = 3;  // see gemm.hip: odd-slot workgroups start 3 * 1024 cycles late (+1.5 % measured)
+    int gemm_sched = 1;       // the 8-wave instance with the scheduled K loop (gemm_nt_sched_kernel); 0: the plain loop.  The same bits
+    int gemm_sched_side = 0;  // ... also on the side streams of the look-ahead factorisation (gemm() says why not)
+    int long_min_tiles = 1024;  // launches of at least this many 128-tiles are "long": 8-wave instance, stagger (tests lower it)
     int pipe_stages_grad = 0, pipe_start_pct_grad = 40;  // the same for gp_fit_grad (stages of the solve for L^-T)
     int pipe_stages = 0;         // gp_fit_predict: candidate stages that ride behind the factorisation (rest afterwards)
     int pipe_done = 0;           // ... how many did, in the last factorisation

@@ -23,10 +23,13 @@
 // MFMAs of a half need are read in the middle of the half before it (round 3: 65.9 -> 69.0
 // TFLOP/s for the kernel alone).  Two workgroups per CU (73.7 KB LDS each, <=256 VGPRs) keep a second
 // wave per SIMD ready while the first sits at the barrier or in the C epilogue.
+// The 8-wave instance of the long launches has a second K loop (SCHED, gemm_nt_sched_kernel) in which every fragment read,
+// staging load and LDS write has a fixed place between two MFMAs of the wave: +4 % for the kernel alone, bitwise the same C.
 //
 // Roofline: algorithmic flops per launch = 2 * 128*128 * K * ntiles; bound = fp64 MFMA.
 #include "gphip_internal.h"
 #include <algorithm>
+#include <type_traits>
 
 #define BK 16
 #define LSTR 18  // LDS row pitch in doubles
@@ -100,8 +103,10 @@ __device__ __forceinline__ void tile_from_linear(long t, const GemmArgs &a, int 
 // BM = 64 with BT = 128 (ROWS variant): the workgroup computes a 64-row strip of all 128 columns of the tile -- two
 // workgroups per tile, each reading only its own rows of A, so an IN-PLACE product (C aliases A: the panel solve)
 // can be split over two CUs.
-template <int MODE, int BT, int NWN, bool PAIR = false, int BM = BT>
-__global__ __launch_bounds__(128 * NWN, (BT == 128 ? (BM < BT ? 2 : NWN) : 4)) void gemm_nt_kernel(GemmArgs a) {
+// SCHED (the 8-wave 128x128 instance only): the K loop with every memory instruction of a stage at a fixed place between two of
+// the wave's own MFMAs -- see the schedule in front of that loop.  Same products, same order per accumulator: bitwise the same C.
+template <int MODE, int BT, int NWN, bool PAIR, int BM, bool SCHED>
+__device__ __forceinline__ void gemm_nt_body(const GemmArgs &a) {
     constexpr int NTH = 128 * NWN;         // threads: 2 x NWN waves
     constexpr int MT = BM / 32;            // 16x16 MFMA tiles per wave along m
     constexpr int NT = BT / NWN / 16;      // ... and along n
@@ -254,6 +259,95 @@ __global__ __launch_bounds__(128 * NWN, (BT == 128 ? (BM < BT ? 2 : NWN) : 4)) v
     }
 #define GP_MMA(A_, B_, m_, n_, e_) acc[m_][n_] = __builtin_amdgcn_mfma_f64_16x16x4f64((A_)[e_], (B_)[e_], acc[m_][n_], 0, 0, MODE == 1 ? 1 : 0)
 #define GP_A1(m_) ((m_) < PA ? pa[m_] : af[m_])
+    if constexpr (SCHED) {
+        // Scheduled stage: the same 32 MFMAs, 12 fragment reads, 4 global loads and 4 LDS writes per wave as below, but none of
+        // them in a clump and none left to the compiler's placement.  Every memory instruction sits behind one MFMA of the wave
+        // (sched_barrier fences on both sides), so it issues in the shadow of that MFMA's 64 matrix-pipe cycles, and the wave
+        // reaches the stage's barrier straight from an MFMA with nothing but its last LDS write in flight:
+        //   H1 e=0   M00 r(af0) M01 r(bf0) M10 r(bf1) M11 M20 M21 M30 M31             r: second-half fragments of this stage
+        //   H1 e=1   M10 w M11 r(af1) M20 w M21 r(af2) M30 w M31 r(af3) M00 w M01     w: next stage -> the other buffer
+        //   H2 e=0   M00 barrier g M01 g M10 g M11 g M20 r(pa0) M21 r(pb0) M30 r(pb1) M31
+        //            g: global loads of the stage after the next.  The barrier (not in the last stage: nothing was written) stands
+        //            behind the second half's first MFMA, whose 64 cycles cover the wait for the last LDS write.
+        //   H2 e=1   M10 M11 r(af1) M20 M21 r(af2) M30 M31 r(af3) M00 M01             r: first-half fragments of the next stage
+        // A half's e=1 MFMAs run row tiles 1, 2, 3, 0, so that af[1..3] are free for the next half's fragments two by two MFMAs
+        // before the half ends (row 0 has a register of its own in either half).  Accumulator (m, n) still sees H1 e=0, H1 e=1,
+        // H2 e=0, H2 e=1 in that order.  The global loads are issued a whole stage (32 MFMAs of the wave, >= 2048 cycles) before
+        // the LDS writes that consume them, twice the cover of the unscheduled loop, so those writes can sit between MFMAs
+        // without a wait behind them.  Stages with nothing to write or load are instances of their own: no branch inside a stage.
+        static_assert(MT == 4 && NT == 2 && LQA == 2 && LQ == 2 && PA == 1 && PF && !PAIR, "schedule written for the 8-wave 128x128 instance");
+#define GP_F __builtin_amdgcn_sched_barrier(0)
+#define GP_S1(m_, n_, e_) GP_MMA(GP_A1(m_), pb[n_], m_, n_, e_)
+#define GP_S2(m_, n_, e_) GP_MMA(af[m_], bf[n_], m_, n_, e_)
+#define GP_LD(p_) (*(const double2_t *)(p_))
+        // LDS addresses are one VGPR each (A fragments and B fragments of the stage being multiplied, staging slot in the other
+        // buffer) plus an immediate; the three flip buffers behind the barrier.
+        const double *as = smem + aoff, *bs = smem + boff;
+        double *Aw = smem + SBUF + soff;
+        int flip = SBUF;
+        auto stage = [&](auto w_, auto l_) __attribute__((always_inline)) {
+            constexpr bool W = decltype(w_)::value;  // a next stage exists: write it, read its first-half fragments
+            constexpr bool L = decltype(l_)::value;  // a stage after the next exists: load it
+            double *const Bw = Aw + BM * LSTR;
+            // ---- first half, e = 0 ----
+            GP_S1(0, 0, 0); GP_F; af[0] = GP_LD(as + 2); GP_F;
+            GP_S1(0, 1, 0); GP_F; bf[0] = GP_LD(bs + 2); GP_F;
+            GP_S1(1, 0, 0); GP_F; bf[1] = GP_LD(bs + 16 * LSTR + 2); GP_F;
+            GP_S1(1, 1, 0); GP_S1(2, 0, 0); GP_S1(2, 1, 0); GP_S1(3, 0, 0); GP_S1(3, 1, 0); GP_F;
+            // ---- first half, e = 1 ----
+            GP_S1(1, 0, 1); GP_F; if (W) *(double2_t *)(Aw) = ra[0]; GP_F;
+            GP_S1(1, 1, 1); GP_F; af[1] = GP_LD(as + 16 * LSTR + 2); GP_F;
+            GP_S1(2, 0, 1); GP_F; if (W) *(double2_t *)(Aw + LR * LSTR) = ra[1]; GP_F;
+            GP_S1(2, 1, 1); GP_F; af[2] = GP_LD(as + 32 * LSTR + 2); GP_F;
+            GP_S1(3, 0, 1); GP_F; if (W) *(double2_t *)(Bw) = rb[0]; GP_F;
+            GP_S1(3, 1, 1); GP_F; af[3] = GP_LD(as + 48 * LSTR + 2); GP_F;
+            GP_S1(0, 0, 1); GP_F; if (W) *(double2_t *)(Bw + LR * LSTR) = rb[1]; GP_F;
+            GP_S1(0, 1, 1); GP_F;
+            GP_S2(0, 0, 0); GP_F;
+            if (W) {
+                __syncthreads();
+                as += flip;
+                bs += flip;
+                Aw -= flip;
+                flip = -flip;
+            }
+            const double *const as2 = as, *const bs2 = bs;  // (the next stage's buffer from here on)
+            // ---- second half, e = 0 ----
+            if (L) { ap += BK; bp += BK; }
+            GP_F; if (L) ra[0] = GP_LD(ap); GP_F;
+            GP_S2(0, 1, 0); GP_F; if (L) ra[1] = GP_LD(ap + a32); GP_F;
+            GP_S2(1, 0, 0); GP_F; if (L) rb[0] = GP_LD(bp); GP_F;
+            GP_S2(1, 1, 0); GP_F; if (L) rb[1] = GP_LD(bp + b32); GP_F;
+            GP_S2(2, 0, 0); GP_F; if (W) pa[0] = GP_LD(as2); GP_F;
+            GP_S2(2, 1, 0); GP_F; if (W) pb[0] = GP_LD(bs2); GP_F;
+            GP_S2(3, 0, 0); GP_F; if (W) pb[1] = GP_LD(bs2 + 16 * LSTR); GP_F;
+            GP_S2(3, 1, 0); GP_F;
+            // ---- second half, e = 1 ----
+            GP_S2(1, 0, 1); GP_S2(1, 1, 1); GP_F; if (W) af[1] = GP_LD(as2 + 16 * LSTR); GP_F;
+            GP_S2(2, 0, 1); GP_S2(2, 1, 1); GP_F; if (W) af[2] = GP_LD(as2 + 32 * LSTR); GP_F;
+            GP_S2(3, 0, 1); GP_S2(3, 1, 1); GP_F; if (W) af[3] = GP_LD(as2 + 48 * LSTR); GP_F;
+            GP_S2(0, 0, 1); GP_S2(0, 1, 1); GP_F;
+        };
+        if (nk > 1) {
+            ap += BK;
+            bp += BK;
+            ra[0] = GP_LD(ap); ra[1] = GP_LD(ap + a32);
+            rb[0] = GP_LD(bp); rb[1] = GP_LD(bp + b32);
+        }
+        using Y = std::true_type;
+        using N = std::false_type;
+        int kt = 0;
+        for (; kt + 2 < nk; ++kt) stage(Y{}, Y{});
+        if (kt + 1 < nk) {
+            stage(Y{}, N{});
+            ++kt;
+        }
+        if (kt < nk) stage(N{}, N{});
+#undef GP_LD
+#undef GP_S2
+#undef GP_S1
+#undef GP_F
+    } else
     for (int kt = 0; kt < nk; ++kt) {
         const int buf = kt & 1;
         const bool more = (kt + 1 < nk);
@@ -345,6 +439,16 @@ __global__ __launch_bounds__(128 * NWN, (BT == 128 ? (BM < BT ? 2 : NWN) : 4)) v
     }  // pass
 }
 
+template <int MODE, int BT, int NWN, bool PAIR = false, int BM = BT>
+__global__ __launch_bounds__(128 * NWN, (BT == 128 ? (BM < BT ? 2 : NWN) : 4)) void gemm_nt_kernel(GemmArgs a) {
+    gemm_nt_body<MODE, BT, NWN, PAIR, BM, false>(a);
+}
+// the 8-wave 128x128 instance with the scheduled K loop (GemmOpt::sched); a symbol of its own, so that profiles tell the two apart
+template <int MODE>
+__global__ __launch_bounds__(512, 4) void gemm_nt_sched_kernel(GemmArgs a) {
+    gemm_nt_body<MODE, 128, 4, false, 128, true>(a);
+}
+
 void launch_gemm_nt(hipStream_t s, int mode, double *C, long ldc, const double *A, long lda,
                     const double *B, long ldb, int b_mul, int K, TileSet ts, const GemmOpt &o) {
     long n = tileset_count(ts);
@@ -391,6 +495,12 @@ void launch_gemm_nt(hipStream_t s, int mode, double *C, long ldc, const double *
             GP_LAUNCH((gemm_nt_kernel<0, 64, 2>), grid, dim3(256), 0, s, a);
         else
             GP_LAUNCH((gemm_nt_kernel<1, 64, 2>), grid, dim3(256), 0, s, a);
+    } else if (o.waves8 && o.sched) {
+        dim3 grid((unsigned)n, (unsigned)o.batch);
+        if (mode == 0)
+            GP_LAUNCH((gemm_nt_sched_kernel<0>), grid, dim3(512), 0, s, a);
+        else
+            GP_LAUNCH((gemm_nt_sched_kernel<1>), grid, dim3(512), 0, s, a);
     } else if (o.waves8) {
         dim3 grid((unsigned)n, (unsigned)o.batch);
         if (mode == 0)

@@ -586,6 +586,12 @@ int gp_gemm_busy(gp_t *gp, double *busy_ms);
 /* per-launch record of the profiled GEMM launches: output tiles, K (negative: triangular contraction), ms */
 int gp_gemm_trace(gp_t *gp, int cap, int64_t *tiles, int *K, double *ms);
 int gp_synchronize(gp_t *gp);
+/* Test hook: ONE launch of the fp64 GEMM (csrc/gemm.hip) on host operands, through the instance selection and the options every
+ * launch of the context takes.  mode 0: C = A B^T, 1: C -= A B^T over the 128 x 128 output tiles (i, c), c in [c0, c1), i in
+ * [tri ? c : r0, r1), contraction length K (a multiple of 16).  C and A are [r1 * 128, ld], B is [c1 * 128, ld], row-major with one
+ * even pitch ld >= max(K, c1 * 128); r1, c1 <= 256.  Tiles outside the set keep their C. */
+int gp_debug_gemm(gp_t *gp, int mode, double *C, const double *A, const double *B, int64_t ld, int K, int r0, int r1, int c0,
+                  int c1, int tri);
 /* Tunables (none changes a result beyond rounding; tests/test_gpu_random_shapes.py sweeps the blocking ones):
  *   "panel_tiles"        outer panel width of the factorisation and of the inverted panels, in 128-tiles (default 6)
  *   "lookahead"          0/1: one panel of look-ahead on separate streams (default 1)
@@ -594,6 +600,12 @@ int gp_synchronize(gp_t *gp);
  *   "mc_max"             candidate rows per chunk (default 16384)
  *   "small_below", "chain_small_below"   launches with fewer 128-tiles run as 64x64 work units (1400 / 400 on the chain)
  *   "waves8", "stagger", "trsm_rows64", "supertile"   GEMM launch shape
+ *   "gemm_sched"         K loop of the 8-wave GEMM instance (launches of >= "long_min_tiles" output tiles): 1 = every fragment read,
+ *                        staging load and LDS write at a fixed place between two MFMAs (gemm_nt_sched_kernel), 0 = the plain loop
+ *                        (gemm_nt_kernel<., 128, 4, false, 128>).  Bitwise the same results; the paired triangular-K twin always
+ *                        runs the plain loop, and so do the launches on the look-ahead factorisation's side streams unless
+ *                        "gemm_sched_side" = 1 (default 0: beside the latency chain the step is slower with it).  "long_min_tiles" (default 1024, >= 1): the tile count from which a launch takes the
+ *                        8-wave instance and the stagger; 1 with "small_below" = "chain_small_below" = 0 sends every launch there
  *   "pipe_stages", "pipe_start_pct"   gp_fit_predict: how many candidate stages ride behind the factorisation (0 = automatic:
  *                        14 % of the panels, 3 at N = 16384) and
  *                        after which share of its panels they are released (-1 = automatic: 32 up to 24 panels, 40 beyond)

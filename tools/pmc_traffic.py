@@ -2,7 +2,9 @@
 as /opt/skills/guides/MI355X_MICROARCH.md prescribes; both counters are in KB).
 
 usage: pmc_traffic.py <dir of the FETCH_SIZE pass> <dir of the WRITE_SIZE pass> <out.json>
-                      [--kernel SUBSTRING] [--min-wgs N] [--f16 F] [--f8 F] [--mode gemm|stream]
+                      [--kernel SUBSTRING]... [--min-wgs N] [--f16 F] [--f8 F] [--mode gemm|stream]
+--kernel may be given several times: the launches of every named symbol count as one kernel (the 8-wave GEMM instance has two
+K loops, gemm_nt_kernel<1, 128, 4, false, 128> and gemm_nt_sched_kernel<1>, with the same loads and stores).
 
 gfx950 corrections, calibrated on this box with tools/micro/fetch_calib (known byte counts, same access patterns):
   --f16  bytes per counted FETCH_SIZE byte for 16-byte-per-lane streaming loads (the guide's value: 2.0)
@@ -22,19 +24,20 @@ import os
 
 ap = argparse.ArgumentParser()
 ap.add_argument("fetch_dir"); ap.add_argument("write_dir"); ap.add_argument("out")
-ap.add_argument("--kernel", default="gemm_nt_kernel<1, 128, 4, false, 128>")
+ap.add_argument("--kernel", action="append", default=None)
 ap.add_argument("--min-wgs", type=int, default=1)
 ap.add_argument("--f16", type=float, default=2.0)
 ap.add_argument("--f8", type=float, default=2.0)
 ap.add_argument("--mode", default="gemm")
 a = ap.parse_args()
+kernels = a.kernel or ["gemm_nt_kernel<1, 128, 4, false, 128>", "gemm_nt_sched_kernel<1>"]
 
 
 def collect(d, counter):
     per = {}
     for f in glob.glob(d + "/**/*counter_collection.csv", recursive=True):
         for r in csv.DictReader(open(f)):
-            if r["Counter_Name"] != counter or a.kernel not in r["Kernel_Name"]:
+            if r["Counter_Name"] != counter or not any(k in r["Kernel_Name"] for k in kernels):
                 continue
             wgs = int(r["Grid_Size"]) // int(r["Workgroup_Size"])
             if wgs < a.min_wgs:
@@ -50,7 +53,7 @@ write_b = sum(v[1] for v in wr.values()) / max(len(wr), 1) * 1024.0
 wgs = sum(v[0] for v in fe.values()) / n
 here = os.path.dirname(os.path.abspath(__file__))
 src = os.path.join(here, "..", "gaussian_process_optimization_amd", "csrc", "gemm.hip")
-out = {"kernel": a.kernel, "launches": len(fe), "avg_workgroups_per_launch": wgs,
+out = {"kernel": " + ".join(kernels), "launches": len(fe), "avg_workgroups_per_launch": wgs,
        "FETCH_SIZE_bytes_per_launch_raw": fetch_raw, "WRITE_SIZE_bytes_per_launch": write_b,
        "correction_16B_loads": a.f16, "correction_8B_C_tile_loads": a.f8,
        "gemm_hip_sha256_16": hashlib.sha256(open(src, "rb").read()).hexdigest()[:16]}
