@@ -43,6 +43,41 @@ int gp_pending_error() {
 // entry point starts: GP_DEAD_CHECK, the first thing every gp_* function does with its context.
 void gp_clear_stale_note() { g_note_set = false; }
 
+// ---- the completion of a fused rows pass (PassOwner, api_internal.h) ----
+int PassOwner::make_ready(hipStream_t s) {
+    int rc;
+    if (!counter) {
+        if ((rc = counter.reserve(words))) return rc;
+        HIPCHK(hipMemsetAsync(counter, 0, sizeof(unsigned int) * words, s));
+    }
+    if (!block) {   // coherent host memory the finishing workgroup writes and the host reads after the sync
+        HIPCHK(hipHostMalloc((void **)&block, sizeof(double) * (ROWS_OUT_DOUBLES + 1), hipHostMallocDefault));
+        block[ROWS_OUT_DOUBLES] = 0.0;
+    }
+    return 0;
+}
+int PassOwner::restart(hipStream_t s) {
+    if (!counter) return 0;
+    HIPCHK(hipMemsetAsync(counter, 0, sizeof(unsigned int) * words, s));
+    base[0] = base[1] = 0;
+    return 0;
+}
+int PassOwner::wait(hipStream_t s, const PassReport &r, unsigned a0, unsigned a1) {
+    base[0] += a0;
+    base[1] += a1;
+    hipError_t e = hipStreamSynchronize(s);
+    int pending = gp_pending_error();
+    if (!pending && e == hipSuccess && block[ROWS_OUT_DOUBLES] == r.ticket) return 0;
+    // a launch did not complete and the counter may hold anything: cleared with the bases, so that the next call starts clean
+    const std::string noted = pending ? gp_last_error() : std::string();
+    hipStreamSynchronize(s);
+    hipMemset(counter, 0, sizeof(unsigned int) * words);
+    base[0] = base[1] = 0;
+    if (pending) return fail(GP_ERR_HIP, "%s", noted.c_str());
+    if (e != hipSuccess) return fail(GP_ERR_HIP, "hipStreamSynchronize -> %s (%s)", hipGetErrorString(e), who);
+    return fail(GP_ERR_HIP, "%s did not complete (ticket %.0f, expected %.0f)", who, block[ROWS_OUT_DOUBLES], r.ticket);
+}
+
 static std::mutex g_ds_mu;
 static std::map<int, DevStreams> g_ds;
 static std::set<gp_ctx *> g_live;  // contexts created and not yet destroyed
@@ -363,13 +398,10 @@ extern "C" int gp_destroy(gp_t *g) {
     hipSetDevice(g->device);
     hipDeviceSynchronize();
     if (g->comm) ncclCommDestroy(g->comm);
-    if (g->hRowsOut) hipHostFree(g->hRowsOut);
-    if (g->sp.hRowsOut) hipHostFree(g->sp.hRowsOut);
-    if (g->ens.hOut) hipHostFree(g->ens.hOut);
     // events recorded on the shared streams go first; the streams themselves belong to the per-device set shared by
     // every context of the process and are destroyed by gp_shutdown / the exit hook
     destroy_ctx_events(g);
-    delete g;   // every device buffer is freed by its DevBuf
+    delete g;   // every device buffer is freed by its DevBuf, the pinned result blocks by their PassOwner
     return 0;
 }
 
@@ -474,7 +506,7 @@ extern "C" int gp_set_option(gp_t *g, const char *name, int64_t value) {
         potrf_set_debug_lds((int)value);   // process-wide test hook: forces refused diagonal-tile launches (tests/test_gpu_round4.py)
     } else if (!strcmp(name, "debug_rows_skew")) {
         // test hook: shifts the arrival base of the one-location path's next pass, so that no workgroup finishes it
-        g->rows_counter_base += (unsigned int)value;
+        g->pass.base[0] += (unsigned int)value;
     } else if (!strcmp(name, "small_m")) {
         if (value < 0 || value > 8) return fail(GP_ERR_ARG, "small_m out of range (0..8)");
         g->small_m = value;

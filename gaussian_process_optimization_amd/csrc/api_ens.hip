@@ -8,7 +8,6 @@
 // the inverse factors and one reduce.  Always true fp64.  The ensemble lives beside the context's own fit (EnsState).
 #include "api_internal.h"
 
-#define GP_ENS_MAX_S 64
 #define GP_ENS_MAX_NPAD 2048   // the batched fit's cap
 #define GP_ENS_TABLE_CHUNK 512 // candidate rows per pass of the table route
 
@@ -146,10 +145,7 @@ extern "C" int gp_ens_fit(gp_t *g, int S, const double *variance, const double *
     HIPCHK(hipMemcpyAsync(en.dAlpha, m.alpha, sizeof(double) * S * Npad, hipMemcpyDeviceToDevice, g->s));
     HIPCHK(hipMemcpyAsync(en.dKp.p, kp.data(), sizeof(KernParams) * S, hipMemcpyHostToDevice, g->s));
     HIPCHK(hipMemcpyAsync(en.dTab, noise, sizeof(double) * S, hipMemcpyHostToDevice, g->s));
-    if (en.dCounter) {   // the arrival counters start again with every ensemble: another S leaves members that never counted
-        HIPCHK(hipMemsetAsync(en.dCounter, 0, sizeof(unsigned int) * (1 + GP_ENS_MAX_S), g->s));
-        en.member_base = en.ens_base = 0;
-    }
+    if ((rc = en.pass.restart(g->s))) return rc;   // the arrival counters start again with every ensemble: another S leaves members that never counted
     std::vector<double> sc((size_t)m.sS * S);
     en.fmin.assign(S, 0.0);
     HIPCHK(hipMemcpyAsync(sc.data(), m.scal, sizeof(double) * m.sS * S, hipMemcpyDeviceToHost, g->s));
@@ -196,16 +192,8 @@ static int ens_rows_table(gp_ctx *g, EnsRows *t) {
     t->vpart = t->meanpart + S * t->sM;
     t->gpart = t->vpart + S * t->sV;
     t->post = t->gpart + S * t->sG;
-    if (!en.dCounter) {
-        if ((rc = en.dCounter.reserve(1 + GP_ENS_MAX_S))) return rc;
-        HIPCHK(hipMemsetAsync(en.dCounter, 0, sizeof(unsigned int) * (1 + GP_ENS_MAX_S), g->s));
-        en.member_base = en.ens_base = 0;
-    }
-    if (!en.hOut) {
-        HIPCHK(hipHostMalloc((void **)&en.hOut, sizeof(double) * (ROWS_OUT_DOUBLES + 1), hipHostMallocDefault));
-        en.hOut[ROWS_OUT_DOUBLES] = 0.0;
-    }
-    t->counter = en.dCounter;
+    if ((rc = en.pass.ready(g->s))) return rc;
+    t->counter = en.pass.counter;
     t->Li = en.dLi;
     t->sLi = Npad * Npad;
     t->alpha = en.dAlpha;
@@ -216,24 +204,9 @@ static int ens_rows_table(gp_ctx *g, EnsRows *t) {
     return 0;
 }
 
-// rows_wait of api_rows.hip for the S-fold grid: every member's counter took rows_finish_grid(N) arrivals, the ensemble's S
-static int ens_wait(gp_ctx *g, double ticket) {
-    EnsState &en = g->ens;
-    en.member_base += rows_finish_grid(g->N);
-    en.ens_base += (unsigned)en.S;
-    hipError_t e = hipStreamSynchronize(g->s);
-    int pending = gp_pending_error();
-    if (!pending && e == hipSuccess && en.hOut[ROWS_OUT_DOUBLES] == ticket) return 0;
-    const std::string noted = pending ? gp_last_error() : std::string();
-    hipStreamSynchronize(g->s);
-    hipMemset(en.dCounter, 0, sizeof(unsigned int) * (1 + GP_ENS_MAX_S));
-    en.member_base = en.ens_base = 0;
-    if (pending) return fail(GP_ERR_HIP, "%s", noted.c_str());
-    if (e != hipSuccess) return fail(GP_ERR_HIP, "hipStreamSynchronize -> %s (ensemble pass)", hipGetErrorString(e));
-    return fail(GP_ERR_HIP, "the ensemble kernels did not complete (ticket %.0f, expected %.0f)", en.hOut[ROWS_OUT_DOUBLES], ticket);
-}
-
-// passes of up to ROWS_MAX_M locations (four per pass is what the ensemble takes: no wide pass); post (when given) receives the S members' result blocks of each pass before unpack runs
+// passes of up to ROWS_MAX_M locations (four per pass is what the ensemble takes: no wide pass): every member's counter takes
+// rows_finish_grid(N) arrivals, the ensemble's S.  post (when given) receives the S members' result blocks of each pass before
+// unpack(m0, mc, block) runs
 template <class Unpack>
 static int ens_passes(gp_ctx *g, const double *Xs, int M, int want_grad, int include_noise, int acq_on, int type, double par,
                       std::vector<double> *post, Unpack unpack) {
@@ -241,25 +214,19 @@ static int ens_passes(gp_ctx *g, const double *Xs, int M, int want_grad, int inc
     EnsRows t;
     if ((rc = ens_rows_table(g, &t))) return rc;
     EnsState &en = g->ens;
-    const int D = g->D;
+    if (post) post->resize((size_t)en.S * ENS_POST_STRIDE);
     // locations per pass: ROWS_MAX_M while their coordinates fit the kernel arguments (D <= 32), else what fits (3 at D = 33, 2 at
     // D = GP_MAX_D); a location's bits do not depend on its company, so the split is invisible in the results
-    const int width = std::min(ROWS_MAX_M, ROWS_MAX_XS / D);
-    if (post) post->resize((size_t)en.S * ENS_POST_STRIDE);
-    for (int m0 = 0; m0 < M; m0 += width) {
-        const int mc = std::min(width, M - m0);
-        RowsX rx;
-        rx.M = mc;
-        memcpy(rx.xs, Xs + (long)m0 * D, sizeof(double) * mc * D);
-        const double ticket = (en.ticket += 1.0);
-        launch_ens_rows(g->s, t, en.S, rx, g->dX, g->N, g->Npad, want_grad, include_noise, acq_on, type, par, en.member_base, en.ens_base,
-                        en.hOut, ticket);
-        if (post)
-            HIPCHK(hipMemcpyAsync(post->data(), t.post, sizeof(double) * en.S * ENS_POST_STRIDE, hipMemcpyDeviceToHost, g->s));
-        if ((rc = ens_wait(g, ticket))) return rc;
-        unpack(m0, mc, rows_layout(mc));
-    }
-    return 0;
+    return rows_passes(g, en.pass, Xs, M, std::min(ROWS_MAX_M, ROWS_MAX_XS / g->D),
+                       [&](const RowsX &rx, const PassReport &r, unsigned *arrivals) {
+                           launch_ens_rows(g->s, t, en.S, rx, g->dX, g->N, g->Npad, want_grad, include_noise, acq_on, type, par, r);
+                           if (post)
+                               HIPCHK(hipMemcpyAsync(post->data(), t.post, sizeof(double) * en.S * ENS_POST_STRIDE, hipMemcpyDeviceToHost, g->s));
+                           arrivals[0] = rows_finish_grid(g->N);
+                           arrivals[1] = (unsigned)en.S;
+                           return 0;
+                       },
+                       unpack);
 }
 
 extern "C" int gp_ens_predict_rows(gp_t *g, const double *Xs, int64_t M, int include_noise, double *mean, double *var, double *dmdx,
@@ -271,7 +238,8 @@ extern "C" int gp_ens_predict_rows(gp_t *g, const double *Xs, int64_t M, int inc
     if ((dmdx == nullptr) != (dvdx == nullptr)) return fail(GP_ERR_ARG, "dmdx and dvdx come together");
     const int D = g->D, S = g->ens.S;
     std::vector<double> post;
-    return ens_passes(g, Xs, (int)M, dmdx != nullptr, include_noise, 0, GP_ACQ_EI, 0.0, &post, [&](int m0, int mc, int MV) {
+    return ens_passes(g, Xs, (int)M, dmdx != nullptr, include_noise, 0, GP_ACQ_EI, 0.0, &post, [&](int m0, int mc, const double *) {
+        const int MV = rows_layout(mc);
         for (int z = 0; z < S; ++z) {
             const double *o = post.data() + (size_t)z * ENS_POST_STRIDE;
             for (int mm = 0; mm < mc; ++mm) {
@@ -299,9 +267,8 @@ extern "C" int gp_ens_acq_rows(gp_t *g, const double *Xs, int64_t M, int type, d
     if (M < 1 || M > ROWS_WIDE_M) return fail(GP_ERR_ARG, "gp_ens_acq_rows takes 1 <= M <= %d locations", ROWS_WIDE_M);
     if ((rc = ens_check_acq(type))) return rc;
     const int D = g->D;
-    const double *o = nullptr;
-    return ens_passes(g, Xs, (int)M, dout != nullptr, 1, 1, type, par, nullptr, [&](int m0, int mc, int MV) {   // with_noise, gpmodel.py:271
-        o = g->ens.hOut;
+    return ens_passes(g, Xs, (int)M, dout != nullptr, 1, 1, type, par, nullptr, [&](int m0, int mc, const double *o) {   // with_noise, gpmodel.py:271
+        const int MV = rows_layout(mc);
         for (int mm = 0; mm < mc; ++mm) {
             out[m0 + mm] = o[2 * MV + mm];
             if (dout) memcpy(dout + (long)(m0 + mm) * D, o + 3 * MV + 2L * MV * D + (long)mm * D, sizeof(double) * D);

@@ -162,6 +162,31 @@ struct DevBuf {
     }
 };
 
+// How a fused rows pass completes, and its one owner.  The last workgroup to arrive at a device counter writes the results into
+// a pinned block and the pass's ticket behind them; the counter is never reset, each pass counts from a base the host advances
+// by the pass's arrivals.  After the sync the host compares the ticket: a pass that did not complete fails loudly -- counter and
+// bases cleared, so that the next call starts clean -- instead of handing back the previous call's numbers.  The exact model, the
+// sparse model and the ensemble hold one owner each (gp_ctx::pass, SparseState::pass, EnsState::pass): counters, tickets and
+// blocks of their own.  An owner that was never used makes no HIP call (as DevBuf).
+#define GP_ENS_MAX_S 64
+struct PassOwner {
+    const int words;                 // counter words: 1; the ensemble 1 + GP_ENS_MAX_S ([0] members arrived, [1 + z] member z's workgroups)
+    const char *const who;           // the error text's subject
+    DevBuf<unsigned int> counter;
+    unsigned int base[2] = {0, 0};   // arrivals the words hold from the passes so far: of the (members') workgroups, of the ensemble's members
+    double *block = nullptr;         // pinned, device-visible: ROWS_OUT_DOUBLES results, then the ticket
+    double ticket = 0.0;             // counts the passes; the finishing workgroup writes it back
+    PassOwner(int words_, const char *who_) : words(words_), who(who_) {}
+    ~PassOwner() { if (block) (void)hipHostFree(block); }
+    // (api_core.hip) first use: the counter, zeroed on the stream, and the block with its ticket slot at 0
+    int ready(hipStream_t s) { return counter && block ? 0 : make_ready(s); }
+    int make_ready(hipStream_t s);
+    int restart(hipStream_t s);      // every counter word zeroed on the stream, the bases 0 (no-op before the first use)
+    PassReport next() { return PassReport{counter, base[0], base[1], block, ticket += 1.0}; }
+    // pass r is on the stream with a0 (and a1) arrivals to come: advance the bases, wait, and make sure it finished (see above)
+    int wait(hipStream_t s, const PassReport &r, unsigned a0, unsigned a1);
+};
+
 // The sparse model (variational DTC over Mz inducing inputs, api_sparse.hip) on the context's X, Y, D, P, kernel parameters and
 // main stream: buffers and validity flag of its own -- nothing here is read or written by the exact model's entry points, and
 // the sparse entry points touch none of the exact model's buffers or flags.  n = Mzpad below.
@@ -194,13 +219,10 @@ struct SparseState {
     DevBuf<double> dTabAcq, dTabDacq;   // scores [tM] and their gradients [tM, D]
     bool tab_post = false, tab_grad = false;   // dTabPost holds mean / var (and the gradients) of the table under the current fit
     // the rows entries: scratch of the fallback (table arithmetic on a handful of rows: locations, posterior, scores) and the
-    // fused path's per-workgroup sums, arrival counter, pinned result block, ticket and counter base (as the exact model's)
+    // fused path's per-workgroup sums and the owner of its passes' completion
     DevBuf<double> dScrX, dScrPost, dScrAcq;
     DevBuf<double> dRowsPart;
-    DevBuf<unsigned int> dRowsCounter;
-    double *hRowsOut = nullptr;
-    double rows_ticket = 0.0;
-    unsigned int rows_counter_base = 0;
+    PassOwner pass{1, "the sparse one-location kernel"};
     long rows_fused_calls = 0, rows_fallback_calls = 0;
 };
 
@@ -215,10 +237,7 @@ struct EnsState {
     DevBuf<double> dTab;       // noise [S], fmin [S]
     DevBuf<signed char> dKp;   // KernParams [S]
     DevBuf<double> dWork;      // the rows passes' partials per member, then the members' result blocks
-    DevBuf<unsigned int> dCounter;   // [0] members arrived, [1 + z] member z's workgroups
-    double *hOut = nullptr;    // pinned result block of the integrated acquisition (+ the ticket behind it)
-    double ticket = 0.0;
-    unsigned int member_base = 0, ens_base = 0;
+    PassOwner pass{1 + GP_ENS_MAX_S, "the ensemble kernels"};   // the block takes the integrated acquisition
     std::vector<double> noise, fmin, jitter;
     std::vector<KernParams> kp;
     DevBuf<double> dKx, dW, dAcq;    // table route: K_z(Xs, X) and Kx Li_z^T per chunk, the scores
@@ -278,11 +297,8 @@ struct gp_ctx {
     // the explicit inverse factor and the scratch of the fused one-row path (onerow.hip, api_rows.hip)
     DevBuf<double> dLi;    // L^-1, lower triangular, Npad x Npad row-major, zeros above the diagonal
     DevBuf<double> dRows;  // RowsWork partials
-    DevBuf<unsigned int> dRowsCounter;
-    double *hRowsOut = nullptr;          // pinned, device-visible result block of the fused path (+ the ticket behind it)
-    double rows_ticket = 0.0;            // counts the fused passes; the finishing workgroup writes it back
-    unsigned int rows_counter_base = 0;  // arrivals the counter holds from the passes before this one
-    std::vector<double> lp_cache;        // local-penalisation batch as last uploaded (Xb | r | s), skipped when unchanged
+    PassOwner pass{1, "the one-location kernels"};   // completion of the fused path's passes
+    std::vector<double> lp_cache;       // local-penalisation batch as last uploaded (Xb | r | s), skipped when unchanged
     int lp_cache_nb = -1;
     long rows_fused_calls = 0, rows_fallback_calls = 0;
     long rows_narrow_passes = 0, rows_wide_passes = 0;   // fused passes of at most ROWS_MAX_M locations / of 5 .. ROWS_WIDE_M (gp_rows_pass_stats)
@@ -400,6 +416,42 @@ static inline void fit_dropped(gp_ctx *g) {
 static inline void sparse_fit_dropped(gp_ctx *g) { g->sp.fitted = g->sp.grad_ready = g->sp.tab_post = g->sp.tab_grad = g->sp.fmin_valid = g->sp.zs_valid = false; }
 
 static inline long round_up(long x, long m) { return (x + m - 1) / m * m; }
+
+// The pass loop of the three fused rows paths: `width` locations per pass, each pass with a ticket and counter bases of its own
+// from `own`.  launch(rx, r, arrivals) puts a pass on the stream and says how many arrivals its counters take (arrivals[1]: the
+// ensemble's members), or returns an error; unpack(m0, mc, block) takes the results of locations [m0, m0 + mc) out of the pinned
+// block.  A template over the two callables, inlined: no std::function and no allocation on a ~40 us call.
+template <class Launch, class Unpack>
+static inline int rows_passes(gp_ctx *g, PassOwner &own, const double *Xs, int M, int width, Launch launch, Unpack unpack) {
+    const int D = g->D;
+    for (int m0 = 0; m0 < M; m0 += width) {
+        const int mc = std::min(width, M - m0);
+        RowsX rx;
+        rx.M = mc;
+        memcpy(rx.xs, Xs + (long)m0 * D, sizeof(double) * mc * D);
+        const PassReport r = own.next();
+        unsigned arrivals[2] = {0, 0};
+        int rc;
+        if ((rc = launch(rx, r, arrivals))) return rc;
+        if ((rc = own.wait(g->s, r, arrivals[0], arrivals[1]))) return rc;
+        unpack(m0, mc, own.block);
+    }
+    return 0;
+}
+// Locations [m0, m0 + mc) of a call out of a block laid out for MV locations -- [mean][var][acq][dmdx][dvdx][dacq], gphip_internal.h
+// -- into the caller's mean / var / acq [M] and dmdx / dvdx / dacq [M, D] (any may be null).
+static inline void rows_unpack(const double *o, int MV, int m0, int mc, int D, double *mean, double *var, double *acq, double *dmdx,
+                               double *dvdx, double *dacq) {
+    for (int m = 0; m < mc; ++m) {
+        if (mean) mean[m0 + m] = o[m];
+        if (var) var[m0 + m] = o[MV + m];
+        if (acq) acq[m0 + m] = o[2 * MV + m];
+        const double *gm = o + 3 * MV + (long)m * D, *gv = gm + (long)MV * D, *ga = gv + (long)MV * D;
+        if (dmdx) memcpy(dmdx + (long)(m0 + m) * D, gm, sizeof(double) * D);
+        if (dvdx) memcpy(dvdx + (long)(m0 + m) * D, gv, sizeof(double) * D);
+        if (dacq) memcpy(dacq + (long)(m0 + m) * D, ga, sizeof(double) * D);
+    }
+}
 
 // the factorisation's trailing update runs in residue form (option emulate_fp64 with emulate_fit; panel edges on 256-column blocks)
 static inline bool emu_fit_applies(const gp_ctx *g) {

@@ -45,37 +45,7 @@ static int rows_scratch(gp_ctx *g, RowsWork *w) {
     w->meanpart = w->bpart + n_b;
     w->vpart = w->meanpart + n_m;
     w->gpart = w->vpart + n_v;
-    if (!g->dRowsCounter) {
-        if ((rc = g->dRowsCounter.reserve(1))) return rc;
-        HIPCHK(hipMemsetAsync(g->dRowsCounter, 0, sizeof(unsigned int), g->s));
-    }
-    w->counter = g->dRowsCounter;
-    if (!g->hRowsOut) {   // 3 MV (1 + D) doubles + the ticket; coherent host memory the finish kernel writes and the host reads after the sync
-        HIPCHK(hipHostMalloc((void **)&g->hRowsOut, sizeof(double) * (ROWS_OUT_DOUBLES + 1), hipHostMallocDefault));
-        g->hRowsOut[ROWS_OUT_DOUBLES] = 0.0;
-    }
-    w->ticket = (g->rows_ticket += 1.0);
-    w->counter_base = g->rows_counter_base;
-    return 0;
-}
-
-// One pass is on the stream: account for its arrivals, wait, and make sure it finished.  The finishing workgroup writes the pass's
-// ticket behind the results; if the stream reports an error or the ticket is not this pass's, a launch did not complete and the
-// arrival counter may hold anything: counter and base are cleared so that the next call starts clean, and this one fails loudly
-// instead of handing back the previous call's numbers.
-static int rows_wait(gp_ctx *g, RowsWork &w, unsigned finish_grid) {
-    g->rows_counter_base += finish_grid;
-    hipError_t e = hipStreamSynchronize(g->s);
-    int pending = gp_pending_error();
-    if (!pending && e == hipSuccess && g->hRowsOut[ROWS_OUT_DOUBLES] == w.ticket) return 0;
-    const std::string noted = pending ? gp_last_error() : std::string();
-    hipStreamSynchronize(g->s);
-    hipMemset(g->dRowsCounter, 0, sizeof(unsigned int));
-    g->rows_counter_base = 0;
-    if (pending) return fail(GP_ERR_HIP, "%s", noted.c_str());
-    if (e != hipSuccess) return fail(GP_ERR_HIP, "hipStreamSynchronize -> %s (one-location pass)", hipGetErrorString(e));
-    return fail(GP_ERR_HIP, "the one-location kernels did not complete (ticket %.0f, expected %.0f)", g->hRowsOut[ROWS_OUT_DOUBLES],
-                w.ticket);
+    return g->pass.ready(g->s);
 }
 
 // the penaliser's batch on the device; re-uploaded only when it changed (an L-BFGS run keeps one batch for hundreds of calls)
@@ -107,37 +77,31 @@ RowsAcq rows_acq(const AcqSpec &a, const LpSpec *lp, const LpBatch &b) {   // (R
     return RowsAcq{1, a.type, a.par, a.fmin, a.y_mean, a.y_std, 1, lp->transform, lp->nb, b.X, b.r, b.s};
 }
 
-// The pass loop of the fused path: rows_pass_width locations per pass, each pass with a ticket and a counter base of its own.
-// launch(rx, w) puts a pass on the stream and returns how many workgroups arrive at its counter; unpack(m0, mc, MV, o) takes
-// the results of locations [m0, m0 + mc) out of the pinned block o, laid out for MV locations (gphip_internal.h).  With a phase
-// name a profiled context times each pass: `cost` reads of the inverse factor's triangle, and as many N^2 products per location.
+// The exact model's passes through rows_passes (api_internal.h): rows_pass_width locations per pass.  launch(rx, w, r) puts a pass
+// on the stream and returns how many workgroups arrive at its counter; unpack(m0, mc, MV, o) takes the results of locations
+// [m0, m0 + mc) out of the pinned block o, laid out for MV locations (gphip_internal.h).  With a phase name a profiled context
+// times each pass: `cost` reads of the inverse factor's triangle, and as many N^2 products per location.
 template <class Launch, class Unpack>
-static int rows_passes(gp_ctx *g, const double *Xs, int M, const char *phase, double cost, Launch launch, Unpack unpack) {
+static int rows_exact_passes(gp_ctx *g, const double *Xs, int M, const char *phase, double cost, Launch launch, Unpack unpack) {
     int rc;
     RowsWork w;
     if ((rc = rows_scratch(g, &w))) return rc;
-    const int D = g->D;
     const bool timed = phase && g->profiling;
     if (timed) g->nphases = 0;
-    const int width = rows_pass_width(g, M);
-    for (int m0 = 0; m0 < M; m0 += width) {
-        const int mc = std::min(width, M - m0);
-        RowsX rx;
-        rx.M = mc;
-        memcpy(rx.xs, Xs + (long)m0 * D, sizeof(double) * mc * D);
-        const int ph = timed ? phase_begin(g, phase, cost * (double)g->N * g->N * mc, cost * 8.0 * (double)g->N * g->N / 2) : -1;
-        if (m0 > 0) {
-            w.ticket = (g->rows_ticket += 1.0);
-            w.counter_base = g->rows_counter_base;
-        }
-        const unsigned arrivals = launch(rx, w);
-        if (timed) phase_end(g, ph);
-        if ((rc = rows_wait(g, w, arrivals))) return rc;
-        ++(mc > ROWS_MAX_M ? g->rows_wide_passes : g->rows_narrow_passes);
-        unpack(m0, mc, rows_layout(mc), g->hRowsOut);
-    }
-    ++g->rows_fused_calls;
-    return 0;
+    rc = rows_passes(
+        g, g->pass, Xs, M, rows_pass_width(g, M),
+        [&](const RowsX &rx, const PassReport &r, unsigned *arrivals) {
+            const int ph = timed ? phase_begin(g, phase, cost * (double)g->N * g->N * rx.M, cost * 8.0 * (double)g->N * g->N / 2) : -1;
+            arrivals[0] = launch(rx, w, r);
+            if (timed) phase_end(g, ph);
+            return 0;
+        },
+        [&](int m0, int mc, const double *o) {
+            ++(mc > ROWS_MAX_M ? g->rows_wide_passes : g->rows_narrow_passes);
+            unpack(m0, mc, rows_layout(mc), o);
+        });
+    if (!rc) ++g->rows_fused_calls;
+    return rc;
 }
 
 // The fused path over the inverse factor.  want_grad selects forward + backward + finish; otherwise forward + finish.
@@ -146,25 +110,14 @@ static int rows_fused(gp_ctx *g, const double *Xs, int M, int include_noise, int
                       double *var, double *acq, double *dmdx, double *dvdx, double *dacq) {
     int rc;
     if ((rc = ensure_linv(g))) return rc;
-    const int D = g->D;
-    return rows_passes(
+    return rows_exact_passes(
         g, Xs, M, want_grad ? "rows_fused_grad" : "rows_fused", want_grad ? 2.0 : 1.0,
-        [&](const RowsX &rx, const RowsWork &w) {
+        [&](const RowsX &rx, const RowsWork &w, const PassReport &r) {
             launch_rows(g->s, g->dLi, g->Npad, rx, g->kp, g->dX, g->N, g->dAlpha, want_grad, g->kp.variance,
-                        include_noise ? g->noise : 0.0, aq, w, g->hRowsOut, g->rows_nt < 0 ? (g->Npad > 8192 ? 1 : 0) : g->rows_nt);
+                        include_noise ? g->noise : 0.0, aq, w, r, g->rows_nt < 0 ? (g->Npad > 8192 ? 1 : 0) : g->rows_nt);
             return rows_finish_grid(g->N);
         },
-        [&](int m0, int mc, int MV, const double *o) {
-            for (int m = 0; m < mc; ++m) {
-                if (mean) mean[m0 + m] = o[m];
-                if (var) var[m0 + m] = o[MV + m];
-                if (acq) acq[m0 + m] = o[2 * MV + m];
-                const double *gm = o + 3 * MV + (long)m * D, *gv = gm + (long)MV * D, *ga = gv + (long)MV * D;
-                if (dmdx) memcpy(dmdx + (long)(m0 + m) * D, gm, sizeof(double) * D);
-                if (dvdx) memcpy(dvdx + (long)(m0 + m) * D, gv, sizeof(double) * D);
-                if (dacq) memcpy(dacq + (long)(m0 + m) * D, ga, sizeof(double) * D);
-            }
-        });
+        [&](int m0, int mc, int MV, const double *o) { rows_unpack(o, MV, m0, mc, g->D, mean, var, acq, dmdx, dvdx, dacq); });
 }
 
 // The posterior of a handful of locations: gp_set_candidates + gp_predict (+ gp_predict_grad when dmdx / dvdx are given) as ONE
@@ -181,10 +134,10 @@ extern "C" int gp_predict_rows(gp_t *g, const double *Xs, int64_t M, int include
         // d mean / dx alone: one pass over the training points, no inverse factor, no substitutions (estimate_L's inner call)
         if (rows_fused_ok(g, M)) {
             const int D = g->D;
-            return rows_passes(
+            return rows_exact_passes(
                 g, Xs, (int)M, nullptr, 0.0,
-                [&](const RowsX &rx, const RowsWork &w) {
-                    launch_rows_mean_grad(g->s, rx, g->kp, g->dX, g->N, g->dAlpha, w, g->hRowsOut);
+                [&](const RowsX &rx, const RowsWork &w, const PassReport &r) {
+                    launch_rows_mean_grad(g->s, rx, g->kp, g->dX, g->N, g->dAlpha, w, r);
                     return rows_mean_grad_grid(g->N);
                 },
                 [&](int m0, int mc, int MV, const double *o) { memcpy(dmdx + (long)m0 * D, o + 3 * MV, sizeof(double) * mc * D); });

@@ -548,38 +548,13 @@ static int sparse_rows_scratch(gp_ctx *g) {
     SparseState &sp = g->sp;
     int rc;
     if ((rc = sp.dRowsPart.reserve((long)sparse_rows_grid(GP_SPARSE_MAX_INDUCING) * SPARSE_ROWS_GROW))) return rc;
-    if (!sp.dRowsCounter) {
-        if ((rc = sp.dRowsCounter.reserve(1))) return rc;
-        HIPCHK(hipMemsetAsync(sp.dRowsCounter, 0, sizeof(unsigned int), g->s));
-    }
+    if ((rc = sp.pass.ready(g->s))) return rc;
     if (!sp.zs_valid) {   // Z / lengthscale, once per fit and only for models that come here
         if ((rc = sp.dZs.reserve(sp.Mz * g->D))) return rc;
         launch_sparse_scale_z(g->s, sp.dZ, sp.Mz, g->kp, sp.dZs);
         sp.zs_valid = true;
     }
-    if (!sp.hRowsOut) {   // coherent host memory the finishing workgroup writes and the host reads after the sync
-        HIPCHK(hipHostMalloc((void **)&sp.hRowsOut, sizeof(double) * (ROWS_OUT_DOUBLES + 1), hipHostMallocDefault));
-        sp.hRowsOut[ROWS_OUT_DOUBLES] = 0.0;
-    }
     return 0;
-}
-
-// One pass is on the stream: account for its arrivals, wait, and make sure it finished (rows_wait of api_rows.hip, on the sparse
-// model's own counter and block).
-static int sparse_rows_wait(gp_ctx *g, double ticket, unsigned arrivals) {
-    SparseState &sp = g->sp;
-    sp.rows_counter_base += arrivals;
-    hipError_t e = hipStreamSynchronize(g->s);
-    int pending = gp_pending_error();
-    if (!pending && e == hipSuccess && sp.hRowsOut[ROWS_OUT_DOUBLES] == ticket) return 0;
-    const std::string noted = pending ? gp_last_error() : std::string();
-    hipStreamSynchronize(g->s);
-    hipMemset(sp.dRowsCounter, 0, sizeof(unsigned int));
-    sp.rows_counter_base = 0;
-    if (pending) return fail(GP_ERR_HIP, "%s", noted.c_str());
-    if (e != hipSuccess) return fail(GP_ERR_HIP, "hipStreamSynchronize -> %s (sparse one-location pass)", hipGetErrorString(e));
-    return fail(GP_ERR_HIP, "the sparse one-location kernel did not complete (ticket %.0f, expected %.0f)", sp.hRowsOut[ROWS_OUT_DOUBLES],
-                ticket);
 }
 
 // mode as launch_sparse_rows.  Results: mean / var / acq [M], dmdx / dvdx / dacq [M, D] (any may be null).
@@ -588,30 +563,19 @@ static int sparse_rows_fused(gp_ctx *g, const double *Xs, int M, int mode, int i
     SparseState &sp = g->sp;
     int rc;
     if ((rc = sparse_rows_scratch(g))) return rc;
-    const int D = g->D, width = std::min(M, ROWS_MAX_XS / D), ML = ROWS_WIDE_M;
+    const int D = g->D;
     const double *wv = sp.dVec + 3L * g->P * sp.Mzpad;
-    for (int m0 = 0; m0 < M; m0 += width) {
-        const int mc = std::min(width, M - m0);
-        RowsX rx;
-        rx.M = mc;
-        memcpy(rx.xs, Xs + (long)m0 * D, sizeof(double) * mc * D);
-        const double ticket = (sp.rows_ticket += 1.0);
-        launch_sparse_rows(g->s, sp.dWinv, sp.Mzpad, sp.Mz, rx, g->kp, sp.dZs, wv, mode, g->kp.variance, include_noise ? g->noise : 0.0,
-                           aq, sp.dRowsPart, sp.dRowsCounter, sp.rows_counter_base, sp.hRowsOut, ticket);
-        if ((rc = sparse_rows_wait(g, ticket, sparse_rows_grid(sp.Mz)))) return rc;
-        const double *o = sp.hRowsOut;
-        for (int m = 0; m < mc; ++m) {
-            if (mean) mean[m0 + m] = o[m];
-            if (var) var[m0 + m] = o[ML + m];
-            if (acq) acq[m0 + m] = o[2 * ML + m];
-            const double *gm = o + 3 * ML + (long)m * D, *gv = gm + (long)ML * D, *ga = gv + (long)ML * D;
-            if (dmdx) memcpy(dmdx + (long)(m0 + m) * D, gm, sizeof(double) * D);
-            if (dvdx) memcpy(dvdx + (long)(m0 + m) * D, gv, sizeof(double) * D);
-            if (dacq) memcpy(dacq + (long)(m0 + m) * D, ga, sizeof(double) * D);
-        }
-    }
-    ++sp.rows_fused_calls;
-    return 0;
+    rc = rows_passes(
+        g, sp.pass, Xs, M, std::min(M, ROWS_MAX_XS / D),
+        [&](const RowsX &rx, const PassReport &r, unsigned *arrivals) {
+            launch_sparse_rows(g->s, sp.dWinv, sp.Mzpad, sp.Mz, rx, g->kp, sp.dZs, wv, mode, g->kp.variance,
+                               include_noise ? g->noise : 0.0, aq, sp.dRowsPart, r);
+            arrivals[0] = sparse_rows_grid(sp.Mz);
+            return 0;
+        },
+        [&](int m0, int mc, const double *o) { rows_unpack(o, ROWS_WIDE_M, m0, mc, D, mean, var, acq, dmdx, dvdx, dacq); });
+    if (!rc) ++sp.rows_fused_calls;
+    return rc;
 }
 
 // Everything the fused path does not take: the table arithmetic on scratch buffers (never the resident table or its cache).

@@ -74,24 +74,22 @@ __global__ __launch_bounds__(256) void ens_finish_kernel(EnsRows t, RowsX rx, co
 
 template <int MV>
 static void launch_ens_rows_t(hipStream_t s, const EnsRows &t, int S, const RowsX &rx, const double *X, long N, long Npad, int want_grad,
-                              int include_noise, int acq_on, int type, double par, unsigned member_base, unsigned ens_base, double *out,
-                              double ticket) {
+                              int include_noise, int acq_on, int type, double par, const PassReport &r) {
     const int nt = (int)(Npad / GP_TILE);
     const dim3 tiles((unsigned)rows_tiles(nt) * (GP_TILE / ENS_ROWS_RB), (unsigned)S);
     const dim3 fin(rows_finish_grid(N), (unsigned)S);
     GP_LAUNCH(ens_forward_kernel<MV>, tiles, dim3(256), 0, s, t, rx, X, N, Npad, nt);
     if (want_grad) GP_LAUNCH(ens_backward_kernel<MV>, tiles, dim3(256), 0, s, t, rx.M, Npad);
-    GP_LAUNCH(ens_finish_kernel<MV>, fin, dim3(256), 0, s, t, rx, X, N, Npad, nt, want_grad, include_noise, acq_on, type, par, S, member_base,
-              ens_base, out, ticket);
+    GP_LAUNCH(ens_finish_kernel<MV>, fin, dim3(256), 0, s, t, rx, X, N, Npad, nt, want_grad, include_noise, acq_on, type, par, S, r.base,
+              r.base2, r.out, r.ticket);
 }
 
 void launch_ens_rows(hipStream_t s, const EnsRows &t, int S, const RowsX &rx, const double *X, long N, long Npad, int want_grad,
-                     int include_noise, int acq_on, int type, double par, unsigned member_base, unsigned ens_base, double *out,
-                     double ticket) {
+                     int include_noise, int acq_on, int type, double par, const PassReport &r) {
     if (rx.M == 1)
-        launch_ens_rows_t<1>(s, t, S, rx, X, N, Npad, want_grad, include_noise, acq_on, type, par, member_base, ens_base, out, ticket);
+        launch_ens_rows_t<1>(s, t, S, rx, X, N, Npad, want_grad, include_noise, acq_on, type, par, r);
     else
-        launch_ens_rows_t<ROWS_MAX_M>(s, t, S, rx, X, N, Npad, want_grad, include_noise, acq_on, type, par, member_base, ens_base, out, ticket);
+        launch_ens_rows_t<ROWS_MAX_M>(s, t, S, rx, X, N, Npad, want_grad, include_noise, acq_on, type, par, r);
 }
 
 // ---- the table route's reduce: one workgroup per candidate row c --------------------------------------------------------------------

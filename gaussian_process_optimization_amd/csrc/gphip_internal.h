@@ -261,9 +261,15 @@ struct RowsAcq {
 #define ROWS_OUT_DOUBLES (3 * ROWS_WIDE_M * (1 + GP_MAX_D))   // result block (sized for a wide pass); one more double behind it carries the call's ticket
 struct RowsWork {             // device scratch (api_rows.hip sizes it): every partial has one writer
     double *wpart, *bpart, *meanpart, *vpart, *gpart;
+};
+// Where a pass reports (host side: the launchers of the three fused rows paths unpack it into the LAST arguments of their
+// finishing kernel, in this order; the ensemble alone has the second base).  The path's PassOwner (api_internal.h) hands out
+// one per pass and checks the ticket after the sync.
+struct PassReport {
     unsigned int *counter;    // arrival counter of the finishing kernels: never reset between calls, each pass counts from its own base
-    unsigned int counter_base;
-    double ticket;            // written behind the results by the workgroup that finishes the call: the host checks it (a launch that
+    unsigned int base, base2; // ... the ensemble's two: of member z's workgroups at counter[1 + z], of the members at counter[0]
+    double *out;              // pinned, host-visible result block
+    double ticket;            // written behind the results by the workgroup that finishes the pass: the host checks it (a launch that
                               // did not complete must not leave the previous call's numbers in the block)
 };
 inline int rows_layout(int M) { return M == 1 ? 1 : M <= ROWS_MAX_M ? ROWS_MAX_M : ROWS_WIDE_M; }   // the MV a pass of M locations is laid out for
@@ -271,17 +277,17 @@ long rows_tiles(int nt);
 int rows_block_height(int nt);   // rows of the tile per workgroup: 32 for matrices of a few tiles, else 128
 size_t rows_gpart_elems(long N);
 // Workgroups of the pass's last launch -- the arrivals its counter waits for; the host adds the same number to the counter's base
-// after every pass (api_rows.hip rows_wait), so launcher and host take it from here.
+// after every pass (PassOwner::wait, api_internal.h), so launcher and host take it from here.
 inline unsigned rows_finish_grid(long N) { return (unsigned)((N + 63) / 64); }       // rows_finish_kernel: 64 training rows per workgroup
 inline unsigned rows_mean_grad_grid(long N) { return (unsigned)((N + 255) / 256); }  // rows_mean_grad_kernel: one row per thread
 // results (host-visible block of 3 MV (1 + D) doubles, MV = rows_layout(M): 1 for M = 1, ROWS_MAX_M up to 4, ROWS_WIDE_M above):
 //   [mean MV][var MV][acq MV][dmdx MV D][dvdx MV D][dacq MV D]
 void launch_rows(hipStream_t s, const double *Li, long Npad, const RowsX &rx, const KernParams &kp, const double *X, long N,
                  const double *alpha, int want_grad, double kss, double noise_add, const RowsAcq &aq, const RowsWork &w,
-                 double *out, int nt_loads);
-// the mean's gradient alone: dmdx [M, D] at out + 3 MV (one pass over the training points, no inverse factor)
+                 const PassReport &r, int nt_loads);
+// the mean's gradient alone: dmdx [M, D] at r.out + 3 MV (one pass over the training points, no inverse factor)
 void launch_rows_mean_grad(hipStream_t s, const RowsX &rx, const KernParams &kp, const double *X, long N, const double *alpha,
-                           const RowsWork &w, double *out);
+                           const RowsWork &w, const PassReport &r);
 void launch_transpose_tri(hipStream_t s, double *dst, const double *src, long n, int mode);
 
 // ---- ens_rows.hip: the same passes over an ensemble of S members, the member as a grid dimension --------------------------------
@@ -299,12 +305,12 @@ struct EnsRows {              // member z's operand at base + z * stride
     double *post;             // per-member result blocks
     unsigned int *counter;    // [0]: members arrived; [1 + z]: workgroups of member z arrived (neither is ever reset between passes)
 };
-// One pass of rx.M <= ROWS_MAX_M locations: forward (+ backward) + finish, whatever S.  Member z's workgroups count from member_base
-// at counter[1 + z], the members from ens_base at counter[0]; the host adds rows_finish_grid(N) and S to them after the pass.
-// acq_on: the integrated rule (type, par; negated) into the host-visible block `out`; the ticket lands behind it either way.
+// One pass of rx.M <= ROWS_MAX_M locations: forward (+ backward) + finish, whatever S.  Member z's workgroups count from r.base
+// at counter[1 + z], the members from r.base2 at counter[0]; the host adds rows_finish_grid(N) and S to them after the pass
+// (PassOwner::wait).  acq_on: the integrated rule (type, par; negated) into the host-visible block r.out; the ticket lands behind
+// it either way.  (t.counter is the owner's counter, as r.counter.)
 void launch_ens_rows(hipStream_t s, const EnsRows &t, int S, const RowsX &rx, const double *X, long N, long Npad, int want_grad,
-                     int include_noise, int acq_on, int type, double par, unsigned member_base, unsigned ens_base, double *out,
-                     double ticket);
+                     int include_noise, int acq_on, int type, double par, const PassReport &r);
 // out[c] = mean over members of the negated rule at candidate row c < M, from Kx = K_z(Xs, X) and W = Kx Li_z^T ([S][ldr][Npad] each)
 void launch_ens_table_reduce(hipStream_t s, const double *Kx, const double *W, long ldr, long Npad, long N, const double *alpha,
                              long sAlpha, const KernParams *kpt, const double *noise, const double *fmin, int S, int type, double par,
@@ -382,17 +388,18 @@ void launch_sparse_min(hipStream_t s, const double *v, long n, double *out);
 // ---- sparse_rows.hip: a handful of locations on the sparse model as ONE launch over woodbury_inv ------------------------------
 #define SPARSE_ROWS_RB 8                                       // rows of woodbury_inv per workgroup (two per wave)
 #define SPARSE_ROWS_GROW (2 * ROWS_MAX_XS + 2 * ROWS_WIDE_M)   // doubles of per-workgroup sums (gpart: grid rows of them)
-// workgroups of a pass -- the arrivals its counter waits for (the host adds the same number to the counter's base after the pass)
+// workgroups of a pass -- the arrivals its counter waits for (the host adds the same number to the counter's base after the pass:
+// PassOwner::wait, api_internal.h)
 inline unsigned sparse_rows_grid(long Mz) { return (unsigned)((Mz + SPARSE_ROWS_RB - 1) / SPARSE_ROWS_RB); }
 // mode 0: mean / var (/ acquisition) of rx.M <= ROWS_WIDE_M locations with rx.M D <= ROWS_MAX_XS; 1: the gradients as well; 2: the
 // mean's gradient alone (Winv not read).  Winv [n, n] with n = Mz rounded up to GP_TILE, Zs [Mz, D] = Z / lengthscale
 // (launch_sparse_scale_z), w [Mz].  Results in the
-// host-visible block `out`, laid out for ROWS_WIDE_M locations whatever rx.M: [mean][var][acq][dmdx D][dvdx D][dacq D], and
-// the ticket at out[ROWS_OUT_DOUBLES].
+// host-visible block r.out, laid out for ROWS_WIDE_M locations whatever rx.M: [mean][var][acq][dmdx D][dvdx D][dacq D], and
+// the ticket at r.out[ROWS_OUT_DOUBLES].
 void launch_sparse_scale_z(hipStream_t s, const double *Z, long Mz, const KernParams &kp, double *Zs);
 void launch_sparse_rows(hipStream_t s, const double *Winv, long n, long Mz, const RowsX &rx, const KernParams &kp, const double *Zs,
                         const double *w, int mode, double kss, double noise_add, const RowsAcq &aq, double *gpart,
-                        unsigned int *counter, unsigned int counter_base, double *out, double ticket);
+                        const PassReport &r);
 
 // ---- rns.hip: fp64-equivalent contraction on the int8 matrix cores (option "emulate_fp64") -----------------------------
 #define GP_RNS_T 14

@@ -254,14 +254,14 @@ __global__ __launch_bounds__(256) void rows_mean_grad_kernel(RowsX rx, KernParam
 }
 
 void launch_rows_mean_grad(hipStream_t s, const RowsX &rx, const KernParams &kp, const double *X, long N, const double *alpha,
-                           const RowsWork &w, double *out) {
+                           const RowsWork &w, const PassReport &r) {
     const unsigned grid = rows_mean_grad_grid(N);
     if (rx.M == 1)
-        GP_LAUNCH(rows_mean_grad_kernel<1>, dim3(grid), dim3(256), 0, s, rx, kp, X, N, alpha, w.gpart, w.counter, w.counter_base, out, w.ticket);
+        GP_LAUNCH(rows_mean_grad_kernel<1>, dim3(grid), dim3(256), 0, s, rx, kp, X, N, alpha, w.gpart, r.counter, r.base, r.out, r.ticket);
     else if (rx.M > ROWS_MAX_M)
-        GP_LAUNCH(rows_mean_grad_kernel<ROWS_WIDE_M>, dim3(grid), dim3(256), 0, s, rx, kp, X, N, alpha, w.gpart, w.counter, w.counter_base, out, w.ticket);
+        GP_LAUNCH(rows_mean_grad_kernel<ROWS_WIDE_M>, dim3(grid), dim3(256), 0, s, rx, kp, X, N, alpha, w.gpart, r.counter, r.base, r.out, r.ticket);
     else
-        GP_LAUNCH(rows_mean_grad_kernel<ROWS_MAX_M>, dim3(grid), dim3(256), 0, s, rx, kp, X, N, alpha, w.gpart, w.counter, w.counter_base, out, w.ticket);
+        GP_LAUNCH(rows_mean_grad_kernel<ROWS_MAX_M>, dim3(grid), dim3(256), 0, s, rx, kp, X, N, alpha, w.gpart, r.counter, r.base, r.out, r.ticket);
 }
 
 // ---- launchers -------------------------------------------------------------------------------------------------------------------------
@@ -272,7 +272,7 @@ int rows_block_height(int nt) { return nt <= 16 ? 32 : GP_TILE; }
 template <int MV, int RB, bool NT>
 static void launch_rows_t(hipStream_t s, const double *Li, long Npad, const RowsX &rx, const KernParams &kp, const double *X, long N,
                           const double *alpha, int want_grad, double kss, double noise_add, const RowsAcq &aq, const RowsWork &w,
-                          double *out) {
+                          const PassReport &r) {
     const int nt = (int)(Npad / GP_TILE);
     const unsigned tiles = (unsigned)rows_tiles(nt) * (GP_TILE / RB);
     const unsigned fin = rows_finish_grid(N);
@@ -283,14 +283,14 @@ static void launch_rows_t(hipStream_t s, const double *Li, long Npad, const Rows
     if (want_grad)
         GP_LAUNCH((rows_backward_kernel<MV, RB, NT>), dim3(tiles), dim3(256), 0, s, Li, Npad, w.wpart, Npad, rx.M, w.bpart, w.vpart);
     GP_LAUNCH(rows_finish_kernel<MV>, dim3(fin), dim3(256), 0, s, rx, kp, X, N, alpha, w.wpart, w.bpart, w.meanpart, w.vpart, Npad, nt,
-              RB, want_grad, kss, noise_add, aq, w.gpart, w.counter, w.counter_base, out, w.ticket);
+              RB, want_grad, kss, noise_add, aq, w.gpart, r.counter, r.base, r.out, r.ticket);
 }
 
 void launch_rows(hipStream_t s, const double *Li, long Npad, const RowsX &rx, const KernParams &kp, const double *X, long N,
                  const double *alpha, int want_grad, double kss, double noise_add, const RowsAcq &aq, const RowsWork &w,
-                 double *out, int nt_loads) {
+                 const PassReport &r, int nt_loads) {
     const bool low = rows_block_height((int)(Npad / GP_TILE)) == 32;
-#define RW_GO(MV, RB, NT) launch_rows_t<MV, RB, NT>(s, Li, Npad, rx, kp, X, N, alpha, want_grad, kss, noise_add, aq, w, out)
+#define RW_GO(MV, RB, NT) launch_rows_t<MV, RB, NT>(s, Li, Npad, rx, kp, X, N, alpha, want_grad, kss, noise_add, aq, w, r)
     if (rx.M == 1) {
         if (low) RW_GO(1, 32, false);
         else if (nt_loads) RW_GO(1, GP_TILE, true);

@@ -283,11 +283,11 @@ void launch_sparse_scale_z(hipStream_t s, const double *Z, long Mz, const KernPa
 
 void launch_sparse_rows(hipStream_t s, const double *Winv, long n, long Mz, const RowsX &rx, const KernParams &kp, const double *Zs,
                         const double *w, int mode, double kss, double noise_add, const RowsAcq &aq, double *gpart,
-                        unsigned int *counter, unsigned int counter_base, double *out, double ticket) {
+                        const PassReport &r) {
     const unsigned grid = sparse_rows_grid(Mz);
 #define SR_GO(MV)                                                                                                                     \
-    GP_LAUNCH(sparse_rows_kernel<MV>, dim3(grid), dim3(256), 0, s, Winv, n, Mz, rx, kp, Zs, w, mode, kss, noise_add, aq, gpart, counter, \
-              counter_base, out, ticket)
+    GP_LAUNCH(sparse_rows_kernel<MV>, dim3(grid), dim3(256), 0, s, Winv, n, Mz, rx, kp, Zs, w, mode, kss, noise_add, aq, gpart, r.counter, \
+              r.base, r.out, r.ticket)
     if (rx.M == 1) SR_GO(1);
     else if (rx.M <= ROWS_MAX_M) SR_GO(ROWS_MAX_M);
     else SR_GO(ROWS_WIDE_M);

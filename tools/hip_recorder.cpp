@@ -5,8 +5,10 @@
 // hipStreamWaitEvent, memsets and copies (with destination and source), all-gathers, synchronisations, allocations.  Streams and
 // events are numbered by first appearance.  The numbers an entry point returns are meaningless (zeros); the factorisation's status
 // word reads 0, so a fit takes its first attempt ($HIP_RECORDER_FAIL=n: the first n status words read 1 instead, which walks the
-// jitter ladder).  Two things are acted out because the host code waits for them: the finishing kernels of the one-location path
-// hand their ticket back, and the RCCL stand-ins give out communicators (of ONE rank: an all-gather copies send to receive).
+// jitter ladder).  Two things are acted out because the host code waits for them: the finishing kernels of the fused rows passes
+// (exact, sparse, ensemble) hand their ticket back ($HIP_RECORDER_NO_TICKET set to anything but 0, looked up at every launch: they
+// withhold it, which walks the host's recovery), and the RCCL stand-ins give out communicators (of ONE rank: an all-gather copies
+// send to receive).
 // What it is for: a refactor of host code must leave this log unchanged.
 //
 // Build a recording libgphip.so from the objects of a normal build (make -C gaussian_process_optimization_amd/csrc), in a copy
@@ -14,9 +16,12 @@
 //   g++ -O1 -fPIC -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -c tools/hip_recorder.cpp -o hip_recorder.o
 //   g++ -shared -fPIC gaussian_process_optimization_amd/csrc/*.o hip_recorder.o -o <copy>/gaussian_process_optimization_amd/libgphip.so
 //   PYTHONPATH=<copy> HIP_RECORDER_LOG=case1.log python tools/stream_ops.py 1
-// (struct GemmArgs below mirrors csrc/gemm.hip; ROWS_OUT_DOUBLES and the argument positions in rows_ticket csrc/onerow.hip.)
+// (struct GemmArgs below mirrors csrc/gemm.hip; ROWS_OUT_DOUBLES is the library's own, from its header.)
+#pragma GCC diagnostic ignored "-Wattributes"   // (the header's ext_vector_type typedefs mean nothing to g++ and are not used here)
+#include "../gaussian_process_optimization_amd/csrc/gphip_internal.h"
 #include <hip/hip_runtime_api.h>
 #include <rccl/rccl.h>
+#include <cxxabi.h>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -68,11 +73,21 @@ static void log_args(FILE *f, const std::string &mangled, void **args) {
         return;
     }
 }
-// rows_finish_kernel / rows_mean_grad_kernel: the last argument (ticket) goes behind the result block, the last but one
-#define ROWS_OUT_DOUBLES (3 * 4 * (1 + 64))
-static void rows_ticket(const std::string &name, void **args) {
-    const int nargs = name.find("rows_finish_kernel") != std::string::npos ? 21 : name.find("rows_mean_grad_kernel") != std::string::npos ? 10 : 0;
-    if (nargs) (*(double **)args[nargs - 2])[ROWS_OUT_DOUBLES] = *(double *)args[nargs - 1];
+// The finishing kernels of the fused rows passes: in every one of them the pinned result block and the pass's ticket are the LAST
+// TWO arguments, and the ticket goes behind the block.  (How many arguments a kernel has is read off its demangled signature.)
+static const char *const kFinishing[] = {"rows_finish_kernel", "rows_mean_grad_kernel", "sparse_rows_kernel", "ens_finish_kernel"};
+static void rows_ticket(const std::string &mangled, void **args) {
+    bool finishing = false;
+    for (const char *k : kFinishing) finishing = finishing || mangled.find(k) != std::string::npos;
+    const char *off = getenv("HIP_RECORDER_NO_TICKET");
+    if (!finishing || (off && atoi(off))) return;
+    char *sig = abi::__cxa_demangle(mangled.c_str(), nullptr, nullptr, nullptr);
+    if (!sig) return;
+    const char *open = strrchr(sig, '(');
+    int nargs = open && open[1] != ')' ? 1 : 0;
+    for (const char *c = open; c && *c; ++c) nargs += *c == ',';
+    free(sig);
+    if (nargs >= 2) (*(double **)args[nargs - 2])[ROWS_OUT_DOUBLES] = *(double *)args[nargs - 1];
 }
 struct Cfg { dim3 g, b; size_t sh; hipStream_t s; };
 static thread_local Cfg g_cfg;

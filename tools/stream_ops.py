@@ -1,8 +1,8 @@
 """One case of the stream-operation comparison between two builds (profiles/r09_scheduler_strands.txt, r10_scoring_layer.txt):
-every strand of the factorisation scheduler (1 ... 9) and the scoring entry points (s1 ... s5), each call made twice (the first
+every strand of the factorisation scheduler (1 ... 9) and the scoring entry points (s1 ... s8), each call made twice (the first
 allocates, the second is the steady state).  Run it under rocprofv3 --kernel-trace / --hip-trace on a GPU, or against a library
 linked with tools/hip_recorder.cpp anywhere.  The scoring cases save every array and scalar they got back when given a path.
-usage: stream_ops.py <case: 1 2 3 4a 4b 5 6a 6b 7 8 9 s1 s2 s3 s4a s4b s5> [results.npz]"""
+usage: stream_ops.py <case: 1 2 3 4a 4b 5 6a 6b 7 8 9 s1 s2 s3 s4a s4b s5 s6 s7 s8> [results.npz]"""
 import sys
 import numpy as np
 from gaussian_process_optimization_amd import _lib
@@ -97,6 +97,37 @@ elif case.startswith("s"):
         setup(300); h.comm_init(h.comm_unique_id(), 0, 1)
         keep("allgather_best", lambda: h.comm_allgather_best(-0.25, 123456789012, 1))
         keep("allgather_topk", lambda: h.comm_allgather_topk(np.arange(5) * 0.5, np.arange(5) + (1 << 40), 1))
+    elif case in ("s6", "s7", "s8"):   # the fused rows passes of the sparse model (s6), the ensemble (s7), and all three interleaved (s8)
+        setup(300, 9); Xs = problem(300, 9)[2]
+        def sparse_fit():
+            h.sparse_set_inducing(problem(40, seed=3)[0]); h.sparse_fit(); return h.sparse_fmin()
+        def ens_fit(S):
+            h.ens_fit(np.linspace(1.0, 1.4, S), np.linspace(0.4, 0.6, S)[:, None], np.linspace(1e-2, 2e-2, S))
+        if case == "s6":   # M = 9 takes the fallback
+            fmin = sparse_fit()
+            for M in (1, 4, 5, 8, 9):
+                for grad in (False, True):
+                    keep("sparse_predict_rows%d%d" % (M, grad), lambda: h.sparse_predict_rows(Xs[:M], True, grad))
+                    for lp in (None, (1, Xb, r0, s0)):
+                        keep("sparse_acq_rows%d%d%s" % (M, grad, lp and lp[0]), lambda: h.sparse_acq_rows(Xs[:M], EI, 0.01, fmin, grad=grad, lp=lp))
+            got["sparse_rows_stats"] = np.array(sorted(h.sparse_rows_stats().items()), dtype=object)[:, 1].astype(np.int64)
+        elif case == "s7":   # the second fit, with another S, restarts the counters
+            ens_fit(3)
+            for M in (1, 4, 5, 8):
+                if M == 5: ens_fit(2)
+                for grad in (False, True):
+                    keep("ens_predict_rows%d%d" % (M, grad), lambda: h.ens_predict_rows(Xs[:M], True, grad))
+                    keep("ens_acq_rows%d%d" % (M, grad), lambda: h.ens_acq_rows(Xs[:M], EI, 0.01, grad=grad))
+        else:
+            h.fit(); fmin = h.fmin(); smin = sparse_fit(); ens_fit(3)
+            for M in (1, 5):
+                for grad in (False, True):
+                    keep("acq_rows%d%d" % (M, grad), lambda: h.acq_rows(Xs[:M], EI, 0.01, fmin, grad=grad))
+                    keep("sparse_acq_rows%d%d" % (M, grad), lambda: h.sparse_acq_rows(Xs[:M], EI, 0.01, smin, grad=grad))
+                    keep("ens_acq_rows%d%d" % (M, grad), lambda: h.ens_acq_rows(Xs[:M], EI, 0.01, grad=grad))
+                    keep("predict_rows%d%d" % (M, grad), lambda: h.predict_rows(Xs[:M], True, grad))
+                    keep("ens_predict_rows%d%d" % (M, grad), lambda: h.ens_predict_rows(Xs[:M], True, grad))
+                    keep("sparse_predict_rows%d%d" % (M, grad), lambda: h.sparse_predict_rows(Xs[:M], True, grad))
     else:
         raise SystemExit("unknown case")
     print(case, {k: float(np.sum(v)) for k, v in got.items()})
