@@ -126,6 +126,8 @@ SIGNATURES = [
                                    _vp, _vp, _vp, _vp]),
     ("gp_rows_stats", ctypes.c_int, [_vp, c_int64_p, c_int64_p]),
     ("gp_rows_pass_stats", ctypes.c_int, [_vp, c_int64_p, c_int64_p]),
+    ("gp_append", ctypes.c_int, [_vp, c_double_p, ctypes.c_int64, c_double_p, c_double_p, c_double_p]),
+    ("gp_append_stats", ctypes.c_int, [_vp, c_int64_p, c_int64_p, c_int64_p]),
     ("gp_comm_unique_id", ctypes.c_int, [ctypes.c_char_p]),
     ("gp_comm_init", ctypes.c_int, [_vp, ctypes.c_char_p, ctypes.c_int, ctypes.c_int]),
     ("gp_comm_destroy", ctypes.c_int, [_vp]),
@@ -278,6 +280,33 @@ class Handle(object):
         check(self.lib, self.lib.gp_set_params(self.h, int(kernel), int(bool(ard)), float(variance), dptr(ls),
                                                float(noise)), "gp_set_params")
         self.n_ls = ls.size
+
+    def append(self, Xnew, Yall):
+        """gp_append: ``Xnew`` [k, D] joins the data of the valid fit, ``Yall`` [N + k, P] replaces all targets; the factor grows by
+        k rows instead of being rebuilt.  Returns (lml, logdet).  A border that is not positive definite raises
+        ``numpy.linalg.LinAlgError`` and leaves the handle as it was: the caller refits (``set_data`` + ``fit``)."""
+        Xnew = as_f64(Xnew, 2)
+        Yall = as_f64(Yall, 2)
+        N = getattr(self, "N", None)
+        if N is None:
+            raise ValueError("append extends a fit: set_data, set_params and fit come first")
+        if Xnew.shape[1] != self.D:
+            raise ValueError("Xnew has %d columns, the model %d" % (Xnew.shape[1], self.D))
+        if Yall.shape != (N + Xnew.shape[0], self.P):
+            raise ValueError("Yall must hold ALL targets, shape %s; got %s" % ((N + Xnew.shape[0], self.P), Yall.shape))
+        lml, logdet = ctypes.c_double(), ctypes.c_double()
+        rc = self.lib.gp_append(self.h, dptr(Xnew), Xnew.shape[0], dptr(Yall), ctypes.byref(lml), ctypes.byref(logdet))
+        if rc > 0:
+            raise np.linalg.LinAlgError("gp_append: the border is not positive definite (row %d of the grown matrix)" % rc)
+        check(self.lib, rc, "gp_append")
+        self.N = N + Xnew.shape[0]
+        return lml.value, logdet.value
+
+    def append_stats(self):
+        """(borders written inside the last tile, borders that opened a new tile, calls refused) since the handle was created."""
+        a, b, c = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
+        check(self.lib, self.lib.gp_append_stats(self.h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)), "gp_append_stats")
+        return a.value, b.value, c.value
 
     def _grad_ls(self, nls):
         """The lengthscale-gradient buffer for gp_lml_grad / gp_fit_grad: the library writes one entry per lengthscale of the

@@ -365,7 +365,7 @@ class BayesianOptimization(object):
             optimizer=kwargs.get('model_optimizer_type', 'lbfgs'), max_iters=kwargs.get('max_iters', 1000),
             optimize_restarts=kwargs.get('optimize_restarts', 5), verbose=verbosity_model,
             ARD=kwargs.get('ARD', False), Gower=kwargs.get('Gower', False), space=self.space, device=device,
-            parallel_restarts=kwargs.get('parallel_restarts', False))
+            parallel_restarts=kwargs.get('parallel_restarts', False), incremental=kwargs.get('incremental', False))
         self.acquisition_optimizer = AcquisitionOptimizer(self.space, acquisition_optimizer_type, parallel=parallel_anchors)
         # arguments_manager.py:42-75
         jitter = kwargs.get('acquisition_jitter', 0.01)

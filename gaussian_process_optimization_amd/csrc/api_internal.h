@@ -308,6 +308,8 @@ struct gp_ctx {
                                          // lower triangle exceeds the 256 MiB Infinity Cache, N > 8192 -- measured -10 % at N = 16384,
                                          // +10 % at N = 4096 where the next call finds the factor cached: profiles/r05_small_calls.txt)
     DevBuf<double> dLp;    // local-penalisation batch: centres, radii, scales (LP_*)
+    DevBuf<double> dApp;   // gp_append (api_append.hip): the border's scratch -- nothing in it outlives the call
+    long append_in_place = 0, append_relayout = 0, append_refused = 0;   // borders written inside the last tile / into a new tile, calls refused (gp_append_stats)
     DevBuf<double> dX2, dK2;  // gp_cross_kernel_matrix: second input set and K(X, X2)
     DevBuf<double> dCov;   // full covariance / beta scratch
     DevBuf<double> dInvP, dInvPw;  // inverted diagonal panels L_JJ^-1 (+ build workspace)
@@ -414,6 +416,20 @@ static inline void fit_dropped(gp_ctx *g) {
 // the sparse fit no longer belongs to the data / parameters / inducing inputs in force, and neither does the cached posterior of
 // the sparse candidate table (the table itself stays, as Z does)
 static inline void sparse_fit_dropped(gp_ctx *g) { g->sp.fitted = g->sp.grad_ready = g->sp.tab_post = g->sp.tab_grad = g->sp.fmin_valid = g->sp.zs_valid = false; }
+
+// The factor in dA has GROWN by rows (gp_append): L, the inverted diagonal tiles and -- where it was valid -- the inverse factor
+// were extended and stay; rows_calls_since_fit keeps counting towards the inverse factor's build.  Everything else derived from
+// the old factor or the old data is dropped, as gp_set_data drops it.
+static inline void factor_grown(gp_ctx *g) {
+    g->wi_valid = false;
+    g->w_in_t2 = false;
+    g->invp_valid = false;
+    g->lr_valid = false;
+    g->predicted = false;
+    g->fmin_valid = false;
+    sparse_fit_dropped(g);
+    g->ens.S = 0;
+}
 
 static inline long round_up(long x, long m) { return (x + m - 1) / m * m; }
 

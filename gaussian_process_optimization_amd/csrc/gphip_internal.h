@@ -316,6 +316,31 @@ void launch_ens_table_reduce(hipStream_t s, const double *Kx, const double *W, l
                              long sAlpha, const KernParams *kpt, const double *noise, const double *fmin, int S, int type, double par,
                              long M, double *out);
 
+// ---- append.hip: a border of k <= 128 new rows inside one diagonal tile (gp_append) ------------------------------------------------
+#define GP_APPEND_V 8      // new rows per pass over the factor / the inverse factor
+// O[c ldo + i] = sum_{j <= i} Mat[i ld + j] V[c ldv + j], i < n, c < kc <= GP_APPEND_V: Mat lower triangular (zeros above the diagonal),
+// ncols allocated columns (even), V finite up to ncols.  Rows n .. of O are left alone.
+void launch_append_rowdot(hipStream_t s, const double *Mat, long ld, long n, long ncols, const double *V, long ldv, int kc, double *O,
+                          long ldo, int nt_loads);
+// R[c ldr + j] = sum_{i >= j, i < n} V[c ldv + i] Mat[i ld + j] for j < n, 0 for n <= j < ncols, c < kc <= GP_APPEND_V, through the
+// partials part: append_col_chunks(n) GP_APPEND_V ldp doubles with ldp >= n rounded up to GP_TILE
+int append_col_chunks(long n);
+void launch_append_colsum(hipStream_t s, const double *Mat, long ld, long n, long ncols, const double *V, long ldv, int kc, double *part,
+                          long ldp, double *R, long ldr, int nt_loads);
+// S (one tile, symmetric, the identity beyond k) = Knn + ((Euclidean: variance, Gower: Knn's own diagonal) + diag_add + jitter) I -
+// T T^T for the k rows T of n entries; gpart: append_gram_elems(n, k) doubles; flag[0] = 1 where an entry of S is not finite
+long append_gram_elems(long n, int k);
+void launch_append_schur(hipStream_t s, const double *T, long ldt, long n, int k, double *gpart, const double *Knn, double variance,
+                         int gower, double diag_add, double jitter, double *S, int *flag);
+// O[a ldo + j] = -sum_{b <= a} Linv[a 128 + b] R[b ldr + j], a < k, j < ncols
+void launch_append_negmul(hipStream_t s, const double *Linv, const double *R, long ldr, int k, long ncols, double *O, long ldo);
+// rows row0 .. row0 + k - 1 of dst = [ src21 (columns < c0) | lower triangle of the tile tile22 | 0 ] over ncols columns
+void launch_append_commit_rows(hipStream_t s, double *dst, long ld, long ncols, long row0, int k, long c0, const double *src21, long ld21,
+                               const double *tile22);
+void launch_append_identity_rows(hipStream_t s, double *dst, long ld, long ncols, long r0, long r1);
+// O[p ldo + i] = Y[i P + p], i < N; 0 for N <= i < ncols
+void launch_append_yrows(hipStream_t s, const double *Y, long N, int P, long ncols, double *O, long ldo);
+
 // ---- grad.hip ---------------------------------------------------------------------------------
 #define GP_GRAD_CH 16
 #define GP_GRAD_NACC (GP_GRAD_CH + 2)

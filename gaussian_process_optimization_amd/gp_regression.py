@@ -168,6 +168,35 @@ class GPRegression(Parameterized):
         self._data_epoch += 1
         self._dirty = True
 
+    _appendable = True     # the models whose handle state gp_append extends (the warped and sparse subclasses refit)
+
+    def append_XY(self, X_new, Y_all):
+        """``X_new`` [k, D] joins the inputs, ``Y_all`` [N + k, P] replaces ALL targets: ``set_XY`` on the grown data, except
+        that a model whose fit is current keeps it -- the factor on the device grows by k rows (``gp_append``, O(k N^2)) instead
+        of being rebuilt at the next call.  A model that is dirty (its hyper-parameters moved since the fit), a border that is
+        not positive definite, or more than 128 new rows take exactly the ``set_XY`` route, jitter ladder included."""
+        X_new = np.atleast_2d(np.asarray(X_new, dtype=float))
+        Y_all = np.asarray(Y_all, dtype=float)
+        if Y_all.ndim == 1:
+            Y_all = Y_all[:, None]
+        assert X_new.shape[1] == self.X.shape[1]
+        assert Y_all.shape[0] == self.X.shape[0] + X_new.shape[0]
+        X_all = np.concatenate([self.X, X_new], axis=0)
+        if self._dirty or not self._appendable or not 1 <= X_new.shape[0] <= 128 or Y_all.shape[1] != self.Y.shape[1]:
+            return self.set_XY(X_all, Y_all)
+        if self.normalizer is not None:
+            self.normalizer.scale_by(Y_all)
+            Y_norm = self.normalizer.normalize(Y_all)
+        else:
+            Y_norm = Y_all
+        try:
+            self._lml, self._logdet = self._h.append(X_new, Y_norm)
+        except np.linalg.LinAlgError:
+            return self.set_XY(X_all, Y_all)
+        self.X, self.Y, self.Y_normalized = X_all, Y_all, Y_norm
+        self.num_data = X_all.shape[0]
+        self._data_epoch += 1
+
     def set_X(self, X):
         self.set_XY(X=X)
 

@@ -45,12 +45,16 @@ class GPModel(BOModel):
     scored by the acquisitions through ``predict`` / ``predict_withGradients`` unless ``device_acquisitions=True`` (sparse models
     only; default False): the acquisitions then score it on the device (``gp_sparse_acq*``, ``gp_sparse_acq_rows``), and ``predict``,
     ``predict_withGradients`` and the mean's gradients of up to eight locations -- the hammer precompute and ``estimate_L`` of the
-    local penalisation -- go down as ONE ``gp_sparse_predict_rows`` call each.  The two routes agree to rounding, not bitwise."""
+    local penalisation -- go down as ONE ``gp_sparse_predict_rows`` call each.  The two routes agree to rounding, not bitwise.
+    ``incremental=True`` (exact model only; default False) lets ``updateModel`` append new observations to the fitted factor
+    when the hyper-parameters are kept (``max_iters <= 0``), see there."""
     analytical_gradient_prediction = True
 
     def __init__(self, kernel=None, noise_var=None, exact_feval=False, optimizer='bfgs', max_iters=1000,
                  optimize_restarts=5, sparse=False, num_inducing=10, verbose=True, ARD=False, Gower=False,
-                 space=None, device=0, parallel_restarts=False, device_acquisitions=False):
+                 space=None, device=0, parallel_restarts=False, device_acquisitions=False, incremental=False):
+        if sparse and incremental:
+            raise ValueError("incremental appends to the exact model's factor: not available with sparse=True")
         if device_acquisitions and not sparse:
             raise ValueError("device_acquisitions selects the sparse model's device route: it needs sparse=True (the exact model "
                              "is always scored on the device)")
@@ -61,7 +65,8 @@ class GPModel(BOModel):
         vars(self).update(kernel=kernel, noise_var=noise_var, exact_feval=exact_feval, optimizer=optimizer,
                           max_iters=max_iters, optimize_restarts=optimize_restarts, sparse=sparse,
                           num_inducing=num_inducing, verbose=verbose, ARD=ARD, Gower=Gower, space=space, device=device,
-                          parallel_restarts=parallel_restarts, device_acquisitions=bool(device_acquisitions), model=None)
+                          parallel_restarts=parallel_restarts, device_acquisitions=bool(device_acquisitions),
+                          incremental=bool(incremental), model=None)
 
     @staticmethod
     def fromConfig(config):
@@ -91,9 +96,14 @@ class GPModel(BOModel):
 
     def updateModel(self, X_all, Y_all, X_new, Y_new):
         """New data in, then the hyper-parameter search: one L-BFGS run, or ``optimize_restarts`` of them (gpmodel.py:78-93);
-        ``max_iters = 0`` keeps the hyper-parameters."""
+        ``max_iters = 0`` keeps the hyper-parameters.  With ``incremental=True`` a model whose hyper-parameters stay
+        (``max_iters <= 0``) and whose inputs are, bit for bit, the head of ``X_all`` takes the new rows by ``append_XY``: the
+        factor on the device grows instead of being rebuilt."""
         if self.model is not None:
-            self.model.set_XY(X_all, Y_all)
+            if self.incremental and self.max_iters <= 0 and self._is_head(X_all):
+                self.model.append_XY(np.asarray(X_all, dtype=float)[self.model.X.shape[0]:], Y_all)
+            else:
+                self.model.set_XY(X_all, Y_all)
         else:
             self._create_model(X_all, Y_all)
         if self.max_iters <= 0:
@@ -105,6 +115,13 @@ class GPModel(BOModel):
             if self.parallel_restarts:   # the restarts in lockstep, one gp_fit_grad_batch per round (GPRegression.optimize_restarts)
                 search["parallel"] = True
             self.model.optimize_restarts(num_restarts=self.optimize_restarts, verbose=self.verbose, **search)
+
+    def _is_head(self, X_all):
+        """``X_all`` is the model's inputs, bit for bit, with at least one more row under them."""
+        X_all, X = np.asarray(X_all, dtype=float), self.model.X
+        N = X.shape[0]
+        return (X_all.ndim == 2 and X_all.shape[1] == X.shape[1] and X_all.shape[0] > N and
+                np.ascontiguousarray(X_all[:N]).tobytes() == np.ascontiguousarray(X).tobytes())
 
     def _predict(self, X, full_cov, include_likelihood):
         mean, var = self.model.predict(np.atleast_2d(X), full_cov=full_cov, include_likelihood=include_likelihood)
@@ -154,7 +171,8 @@ class GPModel(BOModel):
         twin = GPModel(kernel=self.model.kern.copy(), noise_var=self.noise_var, exact_feval=self.exact_feval,
                        optimizer=self.optimizer, max_iters=self.max_iters, optimize_restarts=self.optimize_restarts,
                        sparse=self.sparse, num_inducing=self.num_inducing, verbose=self.verbose, ARD=self.ARD, Gower=self.Gower, space=self.space, device=self.device,
-                       parallel_restarts=self.parallel_restarts, device_acquisitions=self.device_acquisitions)
+                       parallel_restarts=self.parallel_restarts, device_acquisitions=self.device_acquisitions,
+                       incremental=self.incremental)
         twin._create_model(self.model.X, self.model.Y)
         twin.updateModel(self.model.X, self.model.Y, None, None)
         return twin

@@ -38,6 +38,8 @@ class InputWarpedGP(GPRegression):
     * A Gower kernel raises ``NotImplementedError``; ``optimize_restarts(parallel=True)`` runs the serial loop (the members
       of the batched search share X, warped models do not)."""
 
+    _appendable = False    # append_XY refits: the fit of this model is more than the exact GP's factor of (X, Y)
+
     def __init__(self, X, Y, kernel=None, normalizer=False, warping_function=None, warping_indices=None, Xmin=None, Xmax=None,
                  epsilon=None, device=0):
         X = np.asarray(X, dtype=float)

@@ -68,6 +68,8 @@ class SparseGPRegression(GPRegression):
     by value, instead of ``gp_sparse_predict``.  Same results to rounding, not bitwise."""
     device_rows = False
 
+    _appendable = False    # append_XY refits: the fit of this model is more than the exact GP's factor of (X, Y)
+
     def __init__(self, X, Y, kernel=None, Z=None, num_inducing=10, normalizer=None, device=0, name="sparse_gp"):
         X = np.asarray(X, dtype=float)
         if X.ndim == 1:

@@ -34,6 +34,8 @@ class WarpedGP(GPRegression):
     * ``optimize_restarts(parallel=True)`` runs the serial loop (the members of the batched search share Y, warped models do
       not), and replica groups are refused."""
 
+    _appendable = False    # append_XY refits: the fit of this model is more than the exact GP's factor of (X, Y)
+
     def __init__(self, X, Y, kernel=None, warping_function=None, warping_terms=3, normalizer=False, device=0):
         X = np.asarray(X, dtype=float)
         if X.ndim == 1:

@@ -362,6 +362,25 @@ int gp_rows_stats(gp_t *gp, int64_t *fused, int64_t *fallback);
 /* how many passes of at most four locations / wide passes (5 .. 8 locations) the fused path has made since gp_create */
 int gp_rows_pass_stats(gp_t *gp, int64_t *narrow, int64_t *wide);
 
+/* ---- appending observations ------------------------------------------------------------------------------------------
+ * Append k rows to the data of a valid fit and extend the fit to them without refactoring: the factor of
+ * [[K11, K12], [K21, K22]] is the old factor with k rows under it, O(k N^2) against the N^3 / 3 of gp_set_data + gp_fit.
+ * Xnew [k, D]; Yall [N + k, P] replaces ALL targets (the BO loop re-normalises them).  Hyper-parameters, Gower setting and
+ * the jitter of the fit stay as they are; 1 <= k <= 128.  Always true fp64 ("emulate_fp64" does not apply).
+ * 0: done -- *lml / *logdet (either may be NULL) of the grown model, gp_get_fit_state agrees.  L, the inverted diagonal tiles
+ * and, where it was valid, the explicit inverse factor of the one-location path are extended and stay valid (an inverse factor
+ * that did not exist is not built; the build rule of the *_rows entries goes on counting); the resident candidates stay,
+ * everything else derived from the old factor or the old data -- Ky^-1, the candidates' posterior, the cached fmin, the sparse
+ * fit, the ensemble -- is dropped and rebuilt by the call that needs it.
+ * >0: the border's pivot was not positive or not finite (1-based row in the grown matrix); the context is left exactly as
+ * before the call (N rows, fit valid), and the caller refits (gp_set_data + gp_fit, with its jitter ladder).
+ * GP_ERR_STATE: no valid fit, or an output warp is on.  GP_ERR_ARG: k outside 1..128, a NULL argument.  Refusals leave the
+ * context untouched. */
+int gp_append(gp_t *gp, const double *Xnew, int64_t k, const double *Yall, double *lml, double *logdet);
+/* borders written inside the last 128-row tile / into a new tile (a call that crosses a tile boundary counts once in each),
+ * and calls refused or returned with a positive code, since gp_create */
+int gp_append_stats(gp_t *gp, int64_t *in_place, int64_t *relayout, int64_t *refused);
+
 /* ---- multi-GPU (one process per GPU; RCCL over xGMI) ---------------------
  * The candidate table shards across ranks; every rank holds a replica of the
  * fitted model.  uid is ncclUniqueId (128 bytes) produced on rank 0 and carried
