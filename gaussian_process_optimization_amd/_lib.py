@@ -57,7 +57,13 @@ SIGNATURES = [
                                      c_double_p, c_double_p]),
     ("gp_fit_grad_batch", ctypes.c_int, [_vp, ctypes.c_int, c_double_p, c_double_p, c_double_p, ctypes.c_int, c_double_p,
                                          c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, c_int_p]),
-    ("gp_set_candidates", ctypes.c_int, [_vp, c_double_p, ctypes.c_int64]),
+    ("gp_fit_grad_x_batch", ctypes.c_int, [_vp, ctypes.c_int, c_double_p, c_double_p, c_double_p, c_double_p, ctypes.c_int,
+                                           c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p,
+                                           c_int_p]),
+    ("gp_fit_grad_warp_batch", ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, c_double_p, c_double_p, c_double_p, c_double_p,
+                                              c_double_p, ctypes.c_int, c_double_p, c_double_p, c_double_p, c_double_p,
+                                              c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, c_int_p]),
+    ("gp_set_candidates",ctypes.c_int, [_vp, c_double_p, ctypes.c_int64]),
     ("gp_set_candidates_kumar", ctypes.c_int, [_vp, c_double_p, ctypes.c_int64, c_int_p, c_double_p, c_double_p, c_double_p,
                                                c_double_p, c_double_p]),
     ("gp_predict", ctypes.c_int, [_vp, ctypes.c_int, c_double_p, c_double_p]),
@@ -396,6 +402,61 @@ class Handle(object):
                                         dptr(jit), dptr(dv), dptr(dl), dptr(dn), status.ctypes.data_as(c_int_p))
         check(self.lib, rc, "gp_fit_grad_batch")
         return (lml, logdet, jit), (dv, dl, dn), status
+
+    def _batch_params(self, variances, lengthscales, noises):
+        """(R, variance [R], lengthscale [R, nls], noise [R]) of a batch call, checked against the last set_params."""
+        var = as_f64(np.atleast_1d(variances), 1)
+        noi = as_f64(np.atleast_1d(noises), 1)
+        R = var.size
+        want = getattr(self, "n_ls", None)
+        if want is None:
+            raise ValueError("set_params has not been called on this handle")
+        ls = np.asarray(lengthscales, dtype=float)
+        if ls.ndim != 2 or ls.shape != (R, want):
+            raise ValueError("lengthscales has shape %s, expected (%d, %d): one row per member, one entry per lengthscale of "
+                             "the model" % (ls.shape, R, want))
+        if noi.size != R:
+            raise ValueError("variances and noises differ in length (%d, %d)" % (R, noi.size))
+        return R, var, np.ascontiguousarray(ls), noi
+
+    def fit_grad_x_batch(self, Xw, variances, lengthscales, noises, maxtries=5):
+        """gp_fit_grad_x for R members in one call, member r over the inputs ``Xw[r]`` ([R, N, D], already warped) and the
+        resident targets; the resident fit and data are untouched.  Returns ((lml, logdet, jitter) [R] each, (dvariance [R],
+        dlengthscale [R, nls], dnoise [R]), dL_dX [R, N, D], status [R]); a member with status[r] != 0 has NaN outputs."""
+        R, var, ls, noi = self._batch_params(variances, lengthscales, noises)
+        Xw = as_f64(Xw, 3)
+        if Xw.shape != (R, self.N, self.D):
+            raise ValueError("Xw has shape %s, expected (%d, %d, %d): the training inputs of every member"
+                             % (Xw.shape, R, self.N, self.D))
+        lml, logdet, jit = np.empty(R), np.empty(R), np.empty(R)
+        dv, dl, dn = np.empty(R), np.empty((R, ls.shape[1])), np.empty(R)
+        dX = np.empty((R, self.N, self.D))
+        status = np.zeros(R, dtype=np.int32)
+        rc = self.lib.gp_fit_grad_x_batch(self.h, int(R), dptr(Xw), dptr(var), dptr(ls), dptr(noi), int(maxtries), dptr(lml),
+                                          dptr(logdet), dptr(jit), dptr(dv), dptr(dl), dptr(dn), dptr(dX),
+                                          status.ctypes.data_as(c_int_p))
+        check(self.lib, rc, "gp_fit_grad_x_batch")
+        return (lml, logdet, jit), (dv, dl, dn), dX, status
+
+    def fit_grad_warp_batch(self, psis, ds, variances, lengthscales, noises, maxtries=5):
+        """gp_fit_grad_warp for R members in one call, member r with the tanh warp (``psis[r]`` [n_terms, 3], ``ds[r]``) of the
+        resident RAW targets; the resident fit, targets and warp are untouched.  Returns ((lml, logdet, jitter) [R] each,
+        (dvariance [R], dlengthscale [R, nls], dnoise [R]), log_jacobian [R], (dpsi [R, n_terms, 3], dd [R]), status [R]); a
+        member with status[r] != 0 has NaN outputs."""
+        R, var, ls, noi = self._batch_params(variances, lengthscales, noises)
+        psis = as_f64(psis, 3)
+        ds = as_f64(np.atleast_1d(ds), 1)
+        if psis.shape[0] != R or psis.shape[2] != 3 or ds.size != R:
+            raise ValueError("psis needs shape (%d, n_terms, 3) and ds %d entries, got %s and %d" % (R, R, psis.shape, ds.size))
+        lml, logdet, jit = np.empty(R), np.empty(R), np.empty(R)
+        dv, dl, dn = np.empty(R), np.empty((R, ls.shape[1])), np.empty(R)
+        lj, dpsi, dd = np.empty(R), np.empty_like(psis), np.empty(R)
+        status = np.zeros(R, dtype=np.int32)
+        rc = self.lib.gp_fit_grad_warp_batch(self.h, int(R), int(psis.shape[1]), dptr(psis), dptr(ds), dptr(var), dptr(ls),
+                                             dptr(noi), int(maxtries), dptr(lml), dptr(logdet), dptr(jit), dptr(dv), dptr(dl),
+                                             dptr(dn), dptr(lj), dptr(dpsi), dptr(dd), status.ctypes.data_as(c_int_p))
+        check(self.lib, rc, "gp_fit_grad_warp_batch")
+        return (lml, logdet, jit), (dv, dl, dn), lj, (dpsi, dd), status
 
     def fit_state(self):
         lml, logdet, jit = _fit_scalars()

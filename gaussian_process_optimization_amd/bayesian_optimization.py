@@ -359,7 +359,7 @@ class BayesianOptimization(object):
             model = InputWarpedGPModel(self.space, None, kernel, kwargs.get('noise_var', None), exact_feval,
                                        kwargs.get('model_optimizer_type', 'lbfgs'), kwargs.get('max_iters', 1000),
                                        kwargs.get('optimize_restarts', 5), verbosity_model, kwargs.get('ARD', False),
-                                       device=device)
+                                       device=device, parallel_restarts=kwargs.get('parallel_restarts', False))
         self.model = model if model is not None else GPModel(
             kernel=kernel, noise_var=kwargs.get('noise_var', None), exact_feval=exact_feval,
             optimizer=kwargs.get('model_optimizer_type', 'lbfgs'), max_iters=kwargs.get('max_iters', 1000),

@@ -272,6 +272,8 @@ Members ctx_members(gp_ctx *g) {
     m.partial = g->dT;   // free once Ky^-1 is in dWi
     m.scal = g->dScal;
     m.kp = &g->kp;
+    m.X = g->dX;
+    m.Y = g->dY;
     return m;
 }
 
@@ -282,6 +284,8 @@ Members members_range(const Members &m, int m0, int nb) {
     r.invL += m0 * m.sI;
     r.info += 4 * m0;
     r.scal += m0 * m.sS;
+    r.X += m0 * m.sX;
+    r.Y += m0 * m.sY;
     for (double **q : {&r.invP, &r.invPw}) *q += m0 * m.sP;
     for (double **q : {&r.alpha, &r.w}) *q += m0 * m.sV;
     for (double **q : {&r.T, &r.T2, &r.Wi, &r.partial}) *q += m0 * m.sT;

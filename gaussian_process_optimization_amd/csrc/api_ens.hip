@@ -95,6 +95,8 @@ extern "C" int gp_ens_fit(gp_t *g, int S, const double *variance, const double *
     m.diag_tab = dDiag;
     m.jit = jit.data();
     m.jit_tab = dJit;
+    m.X = g->dX;   // shared by the members: strides 0
+    m.Y = g->dY;
     HIPCHK(hipMemsetAsync(m.invL, 0, sizeof(double) * m.sI * S, g->s));
     HIPCHK(hipMemcpyAsync(dKp, kp.data(), sizeof(KernParams) * S, hipMemcpyHostToDevice, g->s));
     HIPCHK(hipMemcpyAsync(dDiag, diag.data(), sizeof(double) * S, hipMemcpyHostToDevice, g->s));

@@ -7,9 +7,9 @@
 // K, the jitter of a repeated attempt (jitchol retries factor (Ky + jitter I): it lands on the assembled diagonal, linalg.py:69)
 // and the RHS rows of m's members
 void build_ky(gp_ctx *g, const Members &m, bool jittered) {
-    launch_kbuild(g->s, m.A, m.lda, g->dX, g->N, g->Npad, m.kp[0], m.diag[0], 0, m.nb, m.sA, m.kpt, m.diag_tab);
+    launch_kbuild(g->s, m.A, m.lda, m.X, g->N, g->Npad, m.kp[0], m.diag[0], 0, m.nb, m.sA, m.kpt, m.diag_tab, m.sX);
     if (jittered) launch_add_diag(g->s, m.A, m.lda, g->N, m.jit[0], m.nb, m.sA, m.jit_tab);
-    launch_set_rhs(g->s, m.A, m.lda, g->dY, g->N, g->Npad, g->P, m.nb, m.sA);
+    launch_set_rhs(g->s, m.A, m.lda, m.Y, g->N, g->Npad, g->P, m.nb, m.sA, m.sY);
 }
 
 // ---- blocked right-looking Cholesky (two-level: 128-column steps inside panel_tiles-wide panels) ----
@@ -331,15 +331,16 @@ __device__ __forceinline__ void dot_ay_body(const double *alpha, long lda_, cons
 __global__ void dot_ay_kernel(const double *alpha, long lda_, const double *Y, long N, int P, double *out) {
     dot_ay_body(alpha, lda_, Y, N, P, out);
 }
-// member z = blockIdx.z of gp_fit_grad_batch: alpha + z sV, results at out + z so
-__global__ void dot_ay_batch_kernel(const double *alpha, long sV, long lda_, const double *Y, long N, int P, double *out, long so) {
+// member z = blockIdx.z of gp_fit_grad_batch: alpha + z sV, targets Y + z sY (0: shared), results at out + z so
+__global__ void dot_ay_batch_kernel(const double *alpha, long sV, long lda_, const double *Y, long sY, long N, int P, double *out,
+                                    long so) {
     const long z = blockIdx.z;
-    dot_ay_body(alpha + z * sV, lda_, Y, N, P, out + z * so);
+    dot_ay_body(alpha + z * sV, lda_, Y + z * sY, N, P, out + z * so);
 }
 static void launch_dot_ay(hipStream_t s, const double *alpha, long lda_, const double *Y, long N, int P, double *out, int nb, long sV,
-                          long so) {
+                          long so, long sY) {
     if (nb > 1)
-        GP_LAUNCH(dot_ay_batch_kernel, dim3(P, 1, nb), dim3(1024), 0, s, alpha, sV, lda_, Y, N, P, out, so);
+        GP_LAUNCH(dot_ay_batch_kernel, dim3(P, 1, nb), dim3(1024), 0, s, alpha, sV, lda_, Y, sY, N, P, out, so);
     else
         GP_LAUNCH(dot_ay_kernel, dim3(P), dim3(1024), 0, s, alpha, lda_, Y, N, P, out);
 }
@@ -349,7 +350,7 @@ void alpha_lml(gp_ctx *g, hipStream_t s, const Members &m) {
     const long Npad = g->Npad;
     launch_logdet(s, m.A, m.lda, g->N, m.scal + SCAL_LOGDET.off, m.nb, m.sA, m.sS);
     launch_trsv_backward(s, m.A, m.lda, m.invP, m.W, Npad, m.A + Npad * m.lda, m.lda, g->P, m.alpha, m.w, m.nb, m.sA, m.sP, m.sV);
-    launch_dot_ay(s, m.alpha, Npad, g->dY, g->N, g->P, m.scal + SCAL_DOT.off, m.nb, m.sV, m.sS);
+    launch_dot_ay(s, m.alpha, Npad, m.Y, g->N, g->P, m.scal + SCAL_DOT.off, m.nb, m.sV, m.sS, m.sY);
 }
 
 // ---- host arithmetic of one fit, per member ----

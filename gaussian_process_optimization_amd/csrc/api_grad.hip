@@ -6,8 +6,8 @@
 void lml_grad_passes(gp_ctx *g, const Members &m) {
     int pass = 0;
     for (int d0 = 0; d0 < g->D; d0 += GP_GRAD_CH, ++pass) {
-        launch_lml_grad(g->s, g->dX, g->N, g->Npad, m.kp[0], g->ard, d0, m.alpha, g->P, m.Wi, g->Npad, m.partial,
-                        m.scal + SCAL_GRAD.off + pass * GP_GRAD_NACC, m.nb, m.kpt, m.sV, m.sT, m.sT, m.sS);
+        launch_lml_grad(g->s, m.X, g->N, g->Npad, m.kp[0], g->ard, d0, m.alpha, g->P, m.Wi, g->Npad, m.partial,
+                        m.scal + SCAL_GRAD.off + pass * GP_GRAD_NACC, m.nb, m.kpt, m.sV, m.sT, m.sT, m.sS, m.sX);
         if (!g->ard) break;
     }
 }

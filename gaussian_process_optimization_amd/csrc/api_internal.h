@@ -483,13 +483,16 @@ static inline GemmOpt inplace_opt() {
 
 // ---- members ------------------------------------------------------------------------------------------------------------
 // Where the operands of the single-stream fit-and-gradient sequences live, and how many independent problems ("members": the
-// context's X, Y and shapes, each with hyper-parameters of its own) ride side by side in every launch.  Member z's operand is
-// at base + z * stride.  The context's own fit is ONE member over its buffers (ctx_members, strides unused); gp_fit_grad_batch
-// passes nb members over g->dBatch.  The sequences below are written once over this description; which kernel a launch of one
+// context's shapes, each with hyper-parameters of its own) ride side by side in every launch.  Member z's operand is
+// at base + z * stride, its inputs and targets included: stride 0 where the members share the context's X or Y
+// (gp_fit_grad_batch), a stride where each has its own (the warped models' batches, api_batch.hip).  The context's own fit is ONE
+// member over its buffers (ctx_members, strides unused); the batch entries pass nb members over g->dBatch.  The sequences below are written once over this description; which kernel a launch of one
 // or of several members runs is the launchers' business (gphip_internal.h) and gemm()'s.
 struct Members {
     int nb = 1;
     long sA = 0, sI = 0, sP = 0, sV = 0, sT = 0, sS = 0;   // per-member strides (doubles) of the operand groups below, in their order
+    const double *X = nullptr, *Y = nullptr;   // inputs [N, D] and targets [N, P], row-major
+    long sX = 0, sY = 0;                       // ... and their per-member strides (0: shared)
     double *A = nullptr;      // Ky / L (lower) and, below it, the RHS rows: leading dimension lda
     long lda = 0;
     double *invL = nullptr;   // inverted diagonal tiles

@@ -188,16 +188,17 @@ void potrf_set_debug_lds(int bytes);   // test hook: dynamic LDS added to every 
 
 // ---- launches that take members ---------------------------------------------------------------------------------------------
 // The launchers with a trailing `nb` run nb independent problems ("members") side by side: member z at base + z * stride
-// (blockIdx.z, or blockIdx.x for the one-workgroup kernels).  One member (the default) is the single-member kernel with the
+// (blockIdx.z, or blockIdx.x for the one-workgroup kernels); the inputs and targets of member z are at X + z * sX, Y + z * sY
+// (strides 0: the members share them).  One member (the default) is the single-member kernel with the
 // values given on the host (kp, diag_add, v); several are its _batch twin, which runs the same body per member -- the per-tile
 // arithmetic of the single launch -- and reads per-member values from device tables (kpt[z], diag_tab[z], v_tab[z]), kp then
 // being the first member's: what selects the instance and the LDS size.  Only the launchers ask "one member or several".
 
 // Ky lower tiles (incl. diagonal tiles in full) from X; padding rows get identity.  (Several members: lower tiles only.)
 void launch_kbuild(hipStream_t s, double *A, long lda, const double *X, long N, long Npad, const KernParams &kp, double diag_add,
-                   int full, int nb = 1, long sA = 0, const KernParams *kpt = nullptr, const double *diag_tab = nullptr);
+                   int full, int nb = 1, long sA = 0, const KernParams *kpt = nullptr, const double *diag_tab = nullptr, long sX = 0);
 // RHS rows: A[(Npad + p)*lda + i] = Y[i*P + p] (zero for i >= N, and rows p >= P zero)
-void launch_set_rhs(hipStream_t s, double *A, long lda, const double *Y, long N, long Npad, int P, int nb = 1, long sA = 0);
+void launch_set_rhs(hipStream_t s, double *A, long lda, const double *Y, long N, long Npad, int P, int nb = 1, long sA = 0, long sY = 0);
 // T[c*ldt + i] = k(xs_c, x_i) for c < M, i < N; zero in the padding.
 void launch_cross_k(hipStream_t s, double *T, long ldt, const double *Xs, long M, long Mpad,
                     const double *X, long N, long Npad, const KernParams &kp);
@@ -350,7 +351,7 @@ void launch_symmetrize(hipStream_t s, double *A, long ld, long n, int nb = 1, lo
 void launch_symmetrize_scale(hipStream_t s, double *A, long ld, long n, double scale, int nb = 1, long sA = 0);
 void launch_lml_grad(hipStream_t s, const double *X, long N, long Npad, const KernParams &kp, int ard, int d0, const double *alpha,
                      int P, const double *Wi, long ldw, double *partial, double *out, int nb = 1, const KernParams *kpt = nullptr,
-                     long sV = 0, long sW = 0, long sP = 0, long so = 0);
+                     long sV = 0, long sW = 0, long sP = 0, long so = 0, long sX = 0);
 void launch_predict_grad(hipStream_t s, const double *Xs, long M, const double *X, long N, const KernParams &kp,
                          const double *alpha, long lda_, int P, const double *beta, long ldb, double *dmdx,
                          double *dvdx);
@@ -378,8 +379,10 @@ void launch_zero_upper_diag(hipStream_t s, double *A, long lda, int nt);
 // out[i, q] = dL/dX_iq for i < N (row-major [N, D]): sum_j 2 dL_dK_ij g(r_ij) (x_iq - x_jq) / l_q^2 with dL_dK = 0.5 (alpha alpha^T -
 // P Wi), one pass over Wi (both triangles) per GP_GRAD_CH dimensions; partial: gradx_partial_elems(Npad) doubles of scratch
 long gradx_partial_elems(long Npad);
+// (nb members: member z's inputs at X + z sX, rows at out + z so, the rest as launch_lml_grad)
 void launch_gradx(hipStream_t s, const double *X, long N, long Npad, const KernParams &kp, const double *alpha, int P,
-                  const double *Wi, long ldw, double *partial, double *out);
+                  const double *Wi, long ldw, double *partial, double *out, int nb = 1, const KernParams *kpt = nullptr,
+                  long sX = 0, long sV = 0, long sW = 0, long sP = 0, long so = 0);
 // rows [m0, m0 + mc) of the resident [M, D] table Xs (m0 D even) through the Kumaraswamy CDF, in place, where warp[q] is set
 void launch_kumar_warp(hipStream_t s, double *Xs, long m0, long mc, int D, const int *warp, const double *a, const double *b,
                        const double *xmin, const double *xmax);

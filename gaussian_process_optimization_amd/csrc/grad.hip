@@ -217,13 +217,14 @@ __global__ __launch_bounds__(256) void lml_grad_tile_kernel(const double *X, lon
                                                             long ldw, double *partial) {
     lml_grad_tile_body<FP>(X, N, kp, ard, d0, alpha, lda_, P, Wi, ldw, partial);
 }
-// member z = blockIdx.z of gp_fit_grad_batch: parameters kpt[z], alpha + z sV, Ky^-1 at Wi + z sW, partials at partial + z sP
+// member z = blockIdx.z of gp_fit_grad_batch: inputs X + z sX (0: shared), parameters kpt[z], alpha + z sV, Ky^-1 at Wi + z sW,
+// partials at partial + z sP
 template <int FP>
-__global__ __launch_bounds__(256) void lml_grad_tile_batch_kernel(const double *X, long N, const KernParams *kpt, int ard, int d0,
-                                                                  const double *alpha, long sV, long lda_, int P, const double *Wi,
-                                                                  long sW, long ldw, double *partial, long sP) {
+__global__ __launch_bounds__(256) void lml_grad_tile_batch_kernel(const double *X, long sX, long N, const KernParams *kpt, int ard,
+                                                                  int d0, const double *alpha, long sV, long lda_, int P,
+                                                                  const double *Wi, long sW, long ldw, double *partial, long sP) {
     const long z = blockIdx.z;
-    lml_grad_tile_body<FP>(X, N, kpt[z], ard, d0, alpha + z * sV, lda_, P, Wi + z * sW, ldw, partial + z * sP);
+    lml_grad_tile_body<FP>(X + z * sX, N, kpt[z], ard, d0, alpha + z * sV, lda_, P, Wi + z * sW, ldw, partial + z * sP);
 }
 
 __device__ __forceinline__ void sum_partials_body(const double *partial, long ntile, int nacc, double *out) {
@@ -255,7 +256,7 @@ __global__ __launch_bounds__(1024) void sum_partials_batch_kernel(const double *
 // partial + z sP and sums at out + z so; kp (the first member's, host) gives D and the Gower setting: the LDS size
 void launch_lml_grad(hipStream_t s, const double *X, long N, long Npad, const KernParams &kp, int ard, int d0, const double *alpha,
                      int P, const double *Wi, long ldw, double *partial, double *out, int nb, const KernParams *kpt, long sV,
-                     long sW, long sP, long so) {
+                     long sW, long sP, long so, long sX) {
     const int nt = (int)(Npad / GP_TILE);
     const long ntile = (long)nt * (nt + 1) / 2;
     const size_t shm = ((size_t)(kp.gower ? 4 : 2) * kp.D * GP_TILE + (size_t)2 * P * GP_TILE) * sizeof(double);
@@ -265,11 +266,11 @@ void launch_lml_grad(hipStream_t s, const double *X, long N, long Npad, const Ke
     const int fp = GP_FAMILY_PAIR(kp.kernel);
     if (nb > 1) {
         if (fp)
-            GP_LAUNCH(lml_grad_tile_batch_kernel<1>, dim3((unsigned)ntile, split, (unsigned)nb), dim3(256), shm, s, X, N, kpt, ard,
-                      d0, alpha, sV, Npad, P, Wi, sW, ldw, partial, sP);
+            GP_LAUNCH(lml_grad_tile_batch_kernel<1>, dim3((unsigned)ntile, split, (unsigned)nb), dim3(256), shm, s, X, sX, N, kpt,
+                      ard, d0, alpha, sV, Npad, P, Wi, sW, ldw, partial, sP);
         else
-            GP_LAUNCH(lml_grad_tile_batch_kernel<0>, dim3((unsigned)ntile, split, (unsigned)nb), dim3(256), shm, s, X, N, kpt, ard,
-                      d0, alpha, sV, Npad, P, Wi, sW, ldw, partial, sP);
+            GP_LAUNCH(lml_grad_tile_batch_kernel<0>, dim3((unsigned)ntile, split, (unsigned)nb), dim3(256), shm, s, X, sX, N, kpt,
+                      ard, d0, alpha, sV, Npad, P, Wi, sW, ldw, partial, sP);
         GP_LAUNCH(sum_partials_batch_kernel, dim3(NACC, 1, (unsigned)nb), dim3(1024), 0, s, partial, sP, ntile * split, NACC, out,
                   so);
         return;

@@ -25,10 +25,25 @@
 // chunk's column tiles in ascending column order; the row's two lanes are added h0 + h1; gradx_sum_kernel adds
 // the chunks in ascending order.
 // partial[(chunk * Npad + i) * GCH + q]
-template <int FP>
-__global__ __launch_bounds__(GX_THREADS) void gradx_tile_kernel(const double *X, long N, long Npad, KernParams kp, int d0,
-                                                                const double *alpha, long lda_, int P, const double *Wi, long ldw,
-                                                                double *partial) {
+// MEMBERS = 1 (gp_fit_grad_x_batch): member z = blockIdx.z with inputs X + z sX, parameters kpt[z] (device table; kp1 is not
+// read), alpha + z sV, Ky^-1 at Wi + z sW, partials at partial + z sP; the grid's x and y are the single launch's, so a member's
+// row sums are added in the order the constants above fix.  MEMBERS = 0: one problem, parameters kp1 by value (kpt and the
+// strides are not read).  One template and not a body with a _batch twin: with the body in a function of its own the
+// single-member instances took 147 / 146 VGPRs instead of 137 / 135 (same occupancy step, but the figures DESIGN.md quotes);
+// this form keeps all four instances at 137 / 135 with no scratch.
+template <int FP, int MEMBERS>
+__global__ __launch_bounds__(GX_THREADS) void gradx_tile_kernel(const double *X, long sX, long N, long Npad, KernParams kp1,
+                                                                const KernParams *kpt, int d0, const double *alpha, long sV,
+                                                                long lda_, int P, const double *Wi, long sW, long ldw,
+                                                                double *partial, long sP) {
+    const KernParams &kp = MEMBERS ? kpt[blockIdx.z] : kp1;
+    if (MEMBERS) {
+        const long z = blockIdx.z;
+        X += z * sX;
+        alpha += z * sV;
+        Wi += z * sW;
+        partial += z * sP;
+    }
     extern __shared__ __attribute__((aligned(16))) double sm[];
     const int D = kp.D;
     double *xi = sm;                        // [D][128]
@@ -117,8 +132,8 @@ __global__ __launch_bounds__(GX_THREADS) void gradx_tile_kernel(const double *X,
 }
 
 // out[i, d0 + q] = (sum over the chunks, ascending) / l_q for i < N: (x - x') / l^2 = scaled difference / l
-__global__ __launch_bounds__(256) void gradx_sum_kernel(const double *partial, long N, long Npad, int nchunk, KernParams kp, int d0,
-                                                        double *out) {
+__device__ __forceinline__ void gradx_sum_body(const double *partial, long N, long Npad, int nchunk, const KernParams &kp, int d0,
+                                               double *out) {
     const long e = (long)blockIdx.x * 256 + threadIdx.x;
     const long i = e / GCH;
     const int q = (int)(e - i * GCH);
@@ -127,6 +142,15 @@ __global__ __launch_bounds__(256) void gradx_sum_kernel(const double *partial, l
     for (int k = 0; k < nchunk; ++k) s += partial[((long)k * Npad + i) * GCH + q];
     out[i * kp.D + d0 + q] = s / kp.ls[d0 + q];
 }
+__global__ __launch_bounds__(256) void gradx_sum_kernel(const double *partial, long N, long Npad, int nchunk, KernParams kp, int d0,
+                                                        double *out) {
+    gradx_sum_body(partial, N, Npad, nchunk, kp, d0, out);
+}
+__global__ __launch_bounds__(256) void gradx_sum_batch_kernel(const double *partial, long sP, long N, long Npad, int nchunk,
+                                                              const KernParams *kpt, int d0, double *out, long so) {
+    const long z = blockIdx.z;
+    gradx_sum_body(partial + z * sP, N, Npad, nchunk, kpt[z], d0, out + z * so);
+}
 
 long gradx_partial_elems(long Npad) {
     const long nt = Npad / GP_TILE;
@@ -134,20 +158,36 @@ long gradx_partial_elems(long Npad) {
 }
 
 // out (device, [N, D] row-major): dL/dX of every training row; partial: gradx_partial_elems(Npad) doubles of scratch
+// nb > 1: the same passes for nb members, member z with inputs X + z sX, parameters kpt[z] (device), alpha + z sV, Ky^-1 at
+// Wi + z sW, partials at partial + z sP and rows at out + z so; kp (the first member's, host) gives D and the family: the instance
+// and the LDS size
 void launch_gradx(hipStream_t s, const double *X, long N, long Npad, const KernParams &kp, const double *alpha, int P,
-                  const double *Wi, long ldw, double *partial, double *out) {
+                  const double *Wi, long ldw, double *partial, double *out, int nb, const KernParams *kpt, long sX, long sV,
+                  long sW, long sP, long so) {
     const int nt = (int)(Npad / GP_TILE);
     const int nchunk = (nt + GX_CHUNK - 1) / GX_CHUNK;
     const size_t stage = ((size_t)2 * kp.D * GP_TILE + (size_t)2 * P * GP_TILE) * sizeof(double);
     const size_t shm = std::max(stage, (size_t)GX_H * GP_TILE * sizeof(double));
     const int fp = GP_FAMILY_PAIR(kp.kernel);
+    const dim3 grid((unsigned)nt, (unsigned)nchunk, (unsigned)nb);
     for (int d0 = 0; d0 < kp.D; d0 += GCH) {
+        if (nb > 1) {
+            if (fp)
+                GP_LAUNCH((gradx_tile_kernel<1, 1>), grid, dim3(GX_THREADS), shm, s, X, sX, N, Npad, kp, kpt, d0, alpha, sV, Npad, P, Wi,
+                          sW, ldw, partial, sP);
+            else
+                GP_LAUNCH((gradx_tile_kernel<0, 1>), grid, dim3(GX_THREADS), shm, s, X, sX, N, Npad, kp, kpt, d0, alpha, sV, Npad, P, Wi,
+                          sW, ldw, partial, sP);
+            GP_LAUNCH(gradx_sum_batch_kernel, dim3((unsigned)((N * GCH + 255) / 256), 1, (unsigned)nb), dim3(256), 0, s, partial, sP,
+                      N, Npad, nchunk, kpt, d0, out, so);
+            continue;
+        }
         if (fp)
-            GP_LAUNCH(gradx_tile_kernel<1>, dim3((unsigned)nt, (unsigned)nchunk), dim3(GX_THREADS), shm, s, X, N, Npad, kp, d0, alpha,
-                      Npad, P, Wi, ldw, partial);
+            GP_LAUNCH((gradx_tile_kernel<1, 0>), grid, dim3(GX_THREADS), shm, s, X, 0L, N, Npad, kp, nullptr, d0, alpha, 0L, Npad, P, Wi,
+                      0L, ldw, partial, 0L);
         else
-            GP_LAUNCH(gradx_tile_kernel<0>, dim3((unsigned)nt, (unsigned)nchunk), dim3(GX_THREADS), shm, s, X, N, Npad, kp, d0, alpha,
-                      Npad, P, Wi, ldw, partial);
+            GP_LAUNCH((gradx_tile_kernel<0, 0>), grid, dim3(GX_THREADS), shm, s, X, 0L, N, Npad, kp, nullptr, d0, alpha, 0L, Npad, P, Wi,
+                      0L, ldw, partial, 0L);
         GP_LAUNCH(gradx_sum_kernel, dim3((unsigned)((N * GCH + 255) / 256)), dim3(256), 0, s, partial, N, Npad, nchunk, kp, d0, out);
     }
 }

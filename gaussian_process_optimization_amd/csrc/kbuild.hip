@@ -134,15 +134,16 @@ __global__ __launch_bounds__(256) void kbuild_kernel(double *A, long lda, const 
                                                      KernParams kp, double diag_add, int full, int nt) {
     kbuild_body<DU, FP>(A, lda, X, N, Npad, kp, diag_add, full, nt);
 }
-// member z = blockIdx.z of a batch (gp_fit_grad_batch): its own matrix at A + z sA, parameters kpt[z], diagonal term diag_add[z]
+// member z = blockIdx.z of a batch (gp_fit_grad_batch): its own matrix at A + z sA, parameters kpt[z], diagonal term diag_add[z],
+// inputs X + z sX (sX = 0: the members share X)
 template <int DU, int FP>
-__global__ __launch_bounds__(256) void kbuild_batch_kernel(double *A, long lda, long sA, const double *X, long N, long Npad,
+__global__ __launch_bounds__(256) void kbuild_batch_kernel(double *A, long lda, long sA, const double *X, long sX, long N, long Npad,
                                                            const KernParams *kpt, const double *diag_add, int nt) {
     const long z = blockIdx.z;
-    kbuild_body<DU, FP>(A + z * sA, lda, X, N, Npad, kpt[z], diag_add[z], 0, nt);
+    kbuild_body<DU, FP>(A + z * sA, lda, X + z * sX, N, Npad, kpt[z], diag_add[z], 0, nt);
 }
 
-static void launch_kbuild_members(hipStream_t s, double *A, long lda, long sA, const double *X, long N, long Npad, int DU, int fp,
+static void launch_kbuild_members(hipStream_t s, double *A, long lda, long sA, const double *X, long sX, long N, long Npad, int DU, int fp,
                                   size_t shm, const KernParams *kpt, const double *diag_tab, int nb);
 // the <DU, pair> instance of a tile kernel for the run-time pair fp
 #define KB_LAUNCH_PAIR(kernel, DU, fp, ...)                       \
@@ -154,13 +155,13 @@ static void launch_kbuild_members(hipStream_t s, double *A, long lda, long sA, c
 // nb > 1: the lower tiles of nb members' matrices in one launch; kernel, D and the Gower setting -- what picks the instance and
 // the LDS size -- are the same for every member, so kp (the first member's) chooses for all
 void launch_kbuild(hipStream_t s, double *A, long lda, const double *X, long N, long Npad, const KernParams &kp, double diag_add,
-                   int full, int nb, long sA, const KernParams *kpt, const double *diag_tab) {
+                   int full, int nb, long sA, const KernParams *kpt, const double *diag_tab, long sX) {
     const int nt = (int)(Npad / GP_TILE);
     const long nblk = full ? (long)nt * nt : (long)nt * (nt + 1) / 2;
     const int DU = kp.gower ? 0 : (kp.D <= 8 ? 8 : (kp.D <= 16 ? 16 : 0));
     const size_t shm = (size_t)2 * (DU ? DU : kp.D) * GP_TILE * sizeof(double);
     const int fp = GP_FAMILY_PAIR(kp.kernel);
-    if (nb > 1) return launch_kbuild_members(s, A, lda, sA, X, N, Npad, DU, fp, shm, kpt, diag_tab, nb);
+    if (nb > 1) return launch_kbuild_members(s, A, lda, sA, X, sX, N, Npad, DU, fp, shm, kpt, diag_tab, nb);
     if (DU == 8)
         KB_LAUNCH_PAIR(kbuild_kernel, 8, fp, dim3((unsigned)nblk), dim3(256), shm, s, A, lda, X, N, Npad, kp, diag_add, full, nt);
     else if (DU == 16)
@@ -178,14 +179,14 @@ __device__ __forceinline__ void set_rhs_body(double *A, long lda, const double *
 __global__ void set_rhs_kernel(double *A, long lda, const double *Y, long N, long Npad, int P) {
     set_rhs_body(A, lda, Y, N, Npad, P);
 }
-__global__ void set_rhs_batch_kernel(double *A, long lda, long sA, const double *Y, long N, long Npad, int P) {
-    set_rhs_body(A + (long)blockIdx.z * sA, lda, Y, N, Npad, P);
+__global__ void set_rhs_batch_kernel(double *A, long lda, long sA, const double *Y, long sY, long N, long Npad, int P) {
+    set_rhs_body(A + (long)blockIdx.z * sA, lda, Y + (long)blockIdx.z * sY, N, Npad, P);
 }
 
-void launch_set_rhs(hipStream_t s, double *A, long lda, const double *Y, long N, long Npad, int P, int nb, long sA) {
+void launch_set_rhs(hipStream_t s, double *A, long lda, const double *Y, long N, long Npad, int P, int nb, long sA, long sY) {
     if (nb > 1) {
         dim3 grid((unsigned)((Npad + 255) / 256), GP_MAX_RHS, (unsigned)nb);
-        GP_LAUNCH(set_rhs_batch_kernel, grid, dim3(256), 0, s, A, lda, sA, Y, N, Npad, P);
+        GP_LAUNCH(set_rhs_batch_kernel, grid, dim3(256), 0, s, A, lda, sA, Y, sY, N, Npad, P);
         return;
     }
     dim3 grid((unsigned)((Npad + 255) / 256), GP_MAX_RHS);
@@ -317,14 +318,14 @@ void launch_cross_k_rows(hipStream_t s, double *T, long ldt, const double *Xs, i
 }
 
 // (defined last: the batch instances stay behind every other kernel of this file in the code object)
-static void launch_kbuild_members(hipStream_t s, double *A, long lda, long sA, const double *X, long N, long Npad, int DU, int fp,
+static void launch_kbuild_members(hipStream_t s, double *A, long lda, long sA, const double *X, long sX, long N, long Npad, int DU, int fp,
                                   size_t shm, const KernParams *kpt, const double *diag_tab, int nb) {
     const int nt = (int)(Npad / GP_TILE);
     const dim3 grid((unsigned)((long)nt * (nt + 1) / 2), 1, (unsigned)nb);   // (lower tiles only)
     if (DU == 8)
-        KB_LAUNCH_PAIR(kbuild_batch_kernel, 8, fp, grid, dim3(256), shm, s, A, lda, sA, X, N, Npad, kpt, diag_tab, nt);
+        KB_LAUNCH_PAIR(kbuild_batch_kernel, 8, fp, grid, dim3(256), shm, s, A, lda, sA, X, sX, N, Npad, kpt, diag_tab, nt);
     else if (DU == 16)
-        KB_LAUNCH_PAIR(kbuild_batch_kernel, 16, fp, grid, dim3(256), shm, s, A, lda, sA, X, N, Npad, kpt, diag_tab, nt);
+        KB_LAUNCH_PAIR(kbuild_batch_kernel, 16, fp, grid, dim3(256), shm, s, A, lda, sA, X, sX, N, Npad, kpt, diag_tab, nt);
     else
-        KB_LAUNCH_PAIR(kbuild_batch_kernel, 0, fp, grid, dim3(256), shm, s, A, lda, sA, X, N, Npad, kpt, diag_tab, nt);
+        KB_LAUNCH_PAIR(kbuild_batch_kernel, 0, fp, grid, dim3(256), shm, s, A, lda, sA, X, sX, N, Npad, kpt, diag_tab, nt);
 }

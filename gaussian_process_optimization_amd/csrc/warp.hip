@@ -28,7 +28,7 @@ __device__ __forceinline__ double wp_block_sum(double v, double *sh) {
 
 // ---- Y <- f(Y_raw) and sum_n log f'(y_n)  (WarpedGP.transform_data / log_likelihood, warped_gp.py:47-57) ----------------------
 // One workgroup: thread t takes observations t, t + WARP_NT, ... in order.
-__global__ __launch_bounds__(WARP_NT) void warp_y_kernel(const double *Yraw, long N, WarpParams w, double *Y, double *logjac) {
+__device__ __forceinline__ void warp_y_body(const double *Yraw, long N, const WarpParams &w, double *Y, double *logjac) {
     __shared__ double sh[WARP_NT / 64];
     double s = 0.0;
     for (long i = threadIdx.x; i < N; i += WARP_NT) {
@@ -40,14 +40,28 @@ __global__ __launch_bounds__(WARP_NT) void warp_y_kernel(const double *Yraw, lon
     s = wp_block_sum<WARP_NT>(s, sh);
     if (threadIdx.x == 0) logjac[0] = s;
 }
+__global__ __launch_bounds__(WARP_NT) void warp_y_kernel(const double *Yraw, long N, WarpParams w, double *Y, double *logjac) {
+    warp_y_body(Yraw, N, w, Y, logjac);
+}
+// member z = blockIdx.x of gp_fit_grad_warp_batch, one workgroup each: the shared raw targets through the member's warp wt[z]
+// (device table) into its target block Y + z sY, sum log f_z' into logjac[z so]
+__global__ __launch_bounds__(WARP_NT) void warp_y_batch_kernel(const double *Yraw, long N, const WarpParams *__restrict__ wt, double *Y, long sY,
+                                                               double *logjac, long so) {
+    const long z = blockIdx.x;
+    const WarpParams &w = wt[z];   // (read in place: a private copy is indexed by the term and would live in scratch)
+    warp_y_body(Yraw, N, w, Y + z * sY, logjac + z * so);
+}
 void launch_warp_y(hipStream_t s, const double *Yraw, long N, const WarpParams &w, double *Y, double *logjac) {
     GP_LAUNCH(warp_y_kernel, dim3(1), dim3(WARP_NT), 0, s, Yraw, N, w, Y, logjac);
+}
+void launch_warp_y_members(hipStream_t s, const double *Yraw, long N, const WarpParams *wt, double *Y, long sY, double *logjac,
+                           long so, int nb) {
+    GP_LAUNCH(warp_y_batch_kernel, dim3((unsigned)nb), dim3(WARP_NT), 0, s, Yraw, N, wt, Y, sY, logjac, so);
 }
 
 // ---- the 3 T + 1 sums of TanhFunction.update_grads (warping_functions.py:159-169) ------------------------------------------------
 // out[(a_0, b_0, c_0, a_1, ..., d)]; one workgroup, per-thread sums in observation order, then one workgroup sum per parameter.
-__global__ __launch_bounds__(WARP_GRAD_NT) void warp_grad_kernel(const double *Yraw, const double *alpha, long N, WarpParams w,
-                                                                 double *out) {
+__device__ __forceinline__ void warp_grad_body(const double *Yraw, const double *alpha, long N, const WarpParams &w, double *out) {
     __shared__ double sh[WARP_GRAD_NT / 64];
     double g[GP_WARP_NPSI];
 #pragma unroll
@@ -63,8 +77,23 @@ __global__ __launch_bounds__(WARP_GRAD_NT) void warp_grad_kernel(const double *Y
     const double vd = wp_block_sum<WARP_GRAD_NT>(g[GP_WARP_NPSI - 1], sh);   // d: the last slot of the sums, behind the terms in out
     if (threadIdx.x == 0) out[3 * w.n] = vd;
 }
+__global__ __launch_bounds__(WARP_GRAD_NT) void warp_grad_kernel(const double *Yraw, const double *alpha, long N, WarpParams w,
+                                                                 double *out) {
+    warp_grad_body(Yraw, alpha, N, w, out);
+}
+// member z = blockIdx.x of gp_fit_grad_warp_batch, one workgroup each: its alpha + z sV and warp wt[z], sums at out + z so
+__global__ __launch_bounds__(WARP_GRAD_NT) void warp_grad_batch_kernel(const double *Yraw, const double *alpha, long sV, long N,
+                                                                       const WarpParams *__restrict__ wt, double *out, long so) {
+    const long z = blockIdx.x;
+    const WarpParams &w = wt[z];   // (read in place: a private copy is indexed by the term and would live in scratch)
+    warp_grad_body(Yraw, alpha + z * sV, N, w, out + z * so);
+}
 void launch_warp_grad(hipStream_t s, const double *Yraw, const double *alpha, long N, const WarpParams &w, double *out) {
     GP_LAUNCH(warp_grad_kernel, dim3(1), dim3(WARP_GRAD_NT), 0, s, Yraw, alpha, N, w, out);
+}
+void launch_warp_grad_members(hipStream_t s, const double *Yraw, const double *alpha, long sV, long N, const WarpParams *wt,
+                              double *out, long so, int nb) {
+    GP_LAUNCH(warp_grad_batch_kernel, dim3((unsigned)nb), dim3(WARP_GRAD_NT), 0, s, Yraw, alpha, sV, N, wt, out, so);
 }
 
 // ---- y = f^-1(z), one element per lane (predict_quantiles, warped_gp.py:118-132) -------------------------------------------------

@@ -112,6 +112,12 @@ __host__ __device__ inline double warp_inv(const WarpParams &w, double sum_a, do
 void launch_warp_y(hipStream_t s, const double *Yraw, long N, const WarpParams &w, double *Y, double *logjac);
 // out[3 n + 1] = sum_i of warp_grad_terms(Yraw[i], alpha[i])
 void launch_warp_grad(hipStream_t s, const double *Yraw, const double *alpha, long N, const WarpParams &w, double *out);
+// the two above for nb members, one workgroup each (gp_fit_grad_warp_batch): member z warps the SHARED raw targets with wt[z]
+// (device table) into Y + z sY, log-Jacobian at logjac[z so]; its gradient sums from alpha + z sV go to out + z so
+void launch_warp_y_members(hipStream_t s, const double *Yraw, long N, const WarpParams *wt, double *Y, long sY, double *logjac,
+                           long so, int nb);
+void launch_warp_grad_members(hipStream_t s, const double *Yraw, const double *alpha, long sV, long N, const WarpParams *wt,
+                              double *out, long so, int nb);
 void launch_warp_inverse(hipStream_t s, const double *z, long n, const WarpParams &w, double *y);
 // warped mean / variance [M] of the Gaussians (mean, var) [M] (device pointers); median [M] and partials [M, 4] may be null
 void launch_warp_moments(hipStream_t s, const double *mean, const double *var, long M, double y_mean, double y_std,

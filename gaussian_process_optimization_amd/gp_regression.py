@@ -265,9 +265,13 @@ class GPRegression(Parameterized):
 
     def objective_function(self):
         """Model.objective_function, core/model.py:96-110: -log likelihood, and -log prior when a prior is set."""
+        return self._objective_value(self.log_likelihood())
+
+    def _objective_value(self, log_likelihood):
+        """The objective at the CURRENT parameters from their log likelihood (shared with the batched restarts)."""
         if self._has_priors():
-            return -float(self.log_likelihood()) - self.log_prior()
-        return -float(self.log_likelihood())
+            return -float(log_likelihood) - self.log_prior()
+        return -float(log_likelihood)
 
     def _log_likelihood_gradients_natural(self):
         nls = self.kern.lengthscale.size
@@ -290,12 +294,16 @@ class GPRegression(Parameterized):
 
     def objective_function_gradients(self):
         """Model.objective_function_gradients, core/model.py:112-127: d(-lml)/d(optimizer_array)."""
-        natural = self._log_likelihood_gradients_natural()
+        return -self._transform_gradients(self._natural_with_priors(self._log_likelihood_gradients_natural()))
+
+    def _natural_with_priors(self, natural):
+        """The natural gradients of the log likelihood with the priors' at the CURRENT parameters added (shared with the
+        batched restarts)."""
         if self._has_priors():   # core/model.py:112-127: the priors' gradients join the likelihood's before the chain rule
             natural = [(p, np.asarray(g, dtype=float).reshape(-1) + (p.prior.lnpdf_grad(p.values) + (
                 p.transform.log_jacobian_grad(p.values) if hasattr(p.transform, "log_jacobian_grad") else 0.0)
                 if p.prior is not None else 0.0)) for p, g in natural]
-        return -self._transform_gradients(natural)
+        return natural
 
     @property
     def gradient(self):

@@ -35,8 +35,10 @@ class InputWarpedGP(GPRegression):
       ``posterior_covariance_between_points`` warp their locations first: tables above eight rows on the device
       (``gp_set_candidates_kumar``), fewer on the host.  ``predictive_gradients`` and ``mean_gradients`` return gradients with
       respect to the UN-WARPED inputs.
-    * A Gower kernel raises ``NotImplementedError``; ``optimize_restarts(parallel=True)`` runs the serial loop (the members
-      of the batched search share X, warped models do not)."""
+    * A Gower kernel raises ``NotImplementedError``.
+    * ``optimize_restarts(parallel=True)`` advances the restarts in lockstep, one ``gp_fit_grad_x_batch`` per round: every
+      member travels with training inputs of its own, warped on the host by its warping parameters (``_batch_objective``).
+      The size rule is the plain model's: up to 64 restarts and 2048 padded rows, the serial loop beyond."""
 
     _appendable = False    # append_XY refits: the fit of this model is more than the exact GP's factor of (X, Y)
 
@@ -102,7 +104,10 @@ class InputWarpedGP(GPRegression):
 
     def objective_function(self):
         """-(LML + log prior) (Model.objective_function, core/model.py:96-110)."""
-        return -float(self.log_likelihood()) - self.log_prior()
+        return self._objective_value(self.log_likelihood())
+
+    def _objective_value(self, log_likelihood):
+        return -float(log_likelihood) - self.log_prior()
 
     def _log_likelihood_gradients_natural(self):
         nls = self.kern.lengthscale.size
@@ -123,15 +128,37 @@ class InputWarpedGP(GPRegression):
         out.extend((p, p.gradient.copy()) for p in self.warping_function.flattened_parameters())
         return out
 
-    def objective_function_gradients(self):
-        """d(-(LML + log prior)) / d(optimizer_array)."""
-        natural = [(p, np.asarray(g, dtype=float).reshape(-1) + (p.prior.lnpdf_grad(p.values) if getattr(p, "prior", None)
-                                                                 is not None else 0.0))
-                   for p, g in self._log_likelihood_gradients_natural()]
-        return -self._transform_gradients(natural)
+    def _natural_with_priors(self, natural):
+        """d(LML + log prior) in natural space (``objective_function_gradients`` chains it through the transforms)."""
+        return [(p, np.asarray(g, dtype=float).reshape(-1) + (p.prior.lnpdf_grad(p.values) if getattr(p, "prior", None)
+                                                              is not None else 0.0)) for p, g in natural]
 
-    def _lockstep_applies(self, num_restarts):
-        return False
+    def _batch_objective(self, xs):
+        """``_obj_grad`` for every row of ``xs`` from ONE gp_fit_grad_x_batch.  Each member's training inputs are warped here, on
+        the host, with the ``transform_data`` the serial loop uses -- the member's inputs are the serial loop's bits -- and
+        travel with the call; the resident data and ``_warp_signature`` are left alone, so the ``_ensure_fit`` that closes the
+        search re-warps as it does after the serial loop.  A member that is not positive definite even with jitter is a wall
+        (1e10, zero gradient)."""
+        k, nls = xs.shape[0], self.kern.lengthscale.size
+        var, ls, noise = np.empty(k), np.empty((k, nls)), np.empty(k)
+        Xw = np.empty((k,) + self.X_untransformed.shape)
+        for j in range(k):
+            self.optimizer_array = xs[j]
+            var[j], ls[j], noise[j] = float(self.kern.variance), self.kern.lengthscale.values, float(self.likelihood.variance)
+            Xw[j] = self.transform_data(self.X_untransformed)
+        (lml, _, _), (dv, dl, dn), dL_dX, status = self._h.fit_grad_x_batch(Xw, var, ls, noise, self.max_jitter_tries)
+        f, g = np.empty(k), np.zeros_like(xs)
+        for j in range(k):
+            if status[j] != 0:
+                f[j] = 1e10
+                continue
+            self.optimizer_array = xs[j]     # (update_grads, the priors and the chain-rule factors are taken at this member's parameters)
+            self.warping_function.update_grads(self.X_untransformed, dL_dX[j])
+            natural = [(self.kern.variance, dv[j]), (self.kern.lengthscale, dl[j]), (self.likelihood.variance, dn[j])]
+            natural.extend((p, p.gradient.copy()) for p in self.warping_function.flattened_parameters())
+            f[j] = self._objective_value(lml[j])
+            g[j] = -self._transform_gradients(self._natural_with_priors(natural))
+        return f, g
 
     # -- prediction ---------------------------------------------------------------------
     def _stage(self, Xnew, fit=True):
@@ -181,6 +208,8 @@ class InputWarpedGPModel(BOModel):
     """Bayesian optimisation surrogate: ``InputWarpedGP`` with Kumaraswamy warping of every continuous and discrete variable
     of ``space``, in order (input_warped_gpmodel.py:9-88).  Constructor keywords are the reference's plus ``device``; default
     kernel Matern-5/2; noise as ``GPModel`` sets it up.  ``predict`` returns (mean, std) with the variance floored at 1e-10.
+    ``parallel_restarts=True`` (an addition, default False) runs the hyper-parameter restarts of ``updateModel`` in lockstep
+    (``optimize_restarts(parallel=True)``), as ``GPModel`` does.
 
     Not a ``GPModel``: the device acquisition entries would score un-warped locations, so the acquisitions take their host
     adapter over ``predict`` / ``predict_withGradients``.
@@ -192,12 +221,12 @@ class InputWarpedGPModel(BOModel):
     analytical_gradient_prediction = True
 
     def __init__(self, space, warping_function=None, kernel=None, noise_var=None, exact_feval=False, optimizer='bfgs',
-                 max_iters=1000, optimize_restarts=5, verbose=False, ARD=False, device=0):
+                 max_iters=1000, optimize_restarts=5, verbose=False, ARD=False, device=0, parallel_restarts=False):
         self.space = space
         self.warping_indices = warping_indices_of(space)
         vars(self).update(warping_function=warping_function, kernel=kernel, noise_var=noise_var, exact_feval=exact_feval,
                           optimizer=optimizer, max_iters=max_iters, optimize_restarts=optimize_restarts, verbose=verbose,
-                          ARD=ARD, device=device, model=None)
+                          ARD=ARD, device=device, model=None, parallel_restarts=bool(parallel_restarts))
 
     def _create_model(self, X, Y):
         self.input_dim = X.shape[1]
@@ -225,6 +254,8 @@ class InputWarpedGPModel(BOModel):
         if self.optimize_restarts == 1:
             self.model.optimize(messages=False, ipython_notebook=False, **search)
         else:
+            if self.parallel_restarts:   # the restarts in lockstep, one gp_fit_grad_x_batch per round (InputWarpedGP._batch_objective)
+                search["parallel"] = True
             self.model.optimize_restarts(num_restarts=self.optimize_restarts, verbose=self.verbose, **search)
 
     def predict(self, X, with_noise=True):

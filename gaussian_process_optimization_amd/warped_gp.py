@@ -31,8 +31,10 @@ class WarpedGP(GPRegression):
     * Deviations: the inverse warp is the device's bracketed Newton iteration, not the reference's damped sweeps; a negative
       latent variance gives sigma = 0 instead of NaN; the initial warp parameters are all ones (the reference draws
       ``warping_params`` at random and never uses them).
-    * ``optimize_restarts(parallel=True)`` runs the serial loop (the members of the batched search share Y, warped models do
-      not), and replica groups are refused."""
+    * ``optimize_restarts(parallel=True)`` advances the restarts in lockstep, one ``gp_fit_grad_warp_batch`` per round: every
+      member warps the device's raw targets with warp parameters of its own (``_batch_objective``).  Tanh warps only, up to
+      64 restarts and 2048 padded rows; the serial loop otherwise.
+    * Replica groups are refused."""
 
     _appendable = False    # append_XY refits: the fit of this model is more than the exact GP's factor of (X, Y)
 
@@ -114,8 +116,52 @@ class WarpedGP(GPRegression):
         return [(self.kern.variance, dv), (self.kern.lengthscale, dl), (self.likelihood.variance, dn),
                 (wf.a, dpsi[:, 0].copy()), (wf.b, dpsi[:, 1].copy()), (wf.c, dpsi[:, 2].copy()), (wf.d, np.atleast_1d(dd))]
 
+    def _batch_objective(self, xs):
+        """``_obj_grad`` for every row of ``xs`` from ONE gp_fit_grad_warp_batch: each member warps the device's raw targets
+        with warp parameters of its own and fits them with its kernel parameters.  The objective is -(LML + log-Jacobian) (and
+        the priors'), its gradient the natural gradients -- the warp's ``dpsi`` into a / b / c, ``dd`` into d -- through the
+        transforms' chain rule; a member that is not positive definite even with jitter is a wall (1e10, zero gradient).  The
+        resident targets, warp and fit are left alone."""
+        wf = self.warping_function
+        k, nls = xs.shape[0], self.kern.lengthscale.size
+        var, ls, noise = np.empty(k), np.empty((k, nls)), np.empty(k)
+        psi, d = np.empty((k, wf.n_terms, 3)), np.empty(k)
+        for j in range(k):
+            self.optimizer_array = xs[j]
+            var[j], ls[j], noise[j] = float(self.kern.variance), self.kern.lengthscale.values, float(self.likelihood.variance)
+            psi[j], d[j] = wf.psi, float(wf.d)
+        (lml, _, _), (dv, dl, dn), logjac, (dpsi, dd), status = self._h.fit_grad_warp_batch(psi, d, var, ls, noise,
+                                                                                          self.max_jitter_tries)
+        f, g = np.empty(k), np.zeros_like(xs)
+        for j in range(k):
+            if status[j] != 0:
+                f[j] = 1e10
+                continue
+            self.optimizer_array = xs[j]     # (the priors and the chain-rule factors are taken at this member's parameters)
+            natural = [(self.kern.variance, dv[j]), (self.kern.lengthscale, dl[j]), (self.likelihood.variance, dn[j]),
+                       (wf.a, dpsi[j][:, 0].copy()), (wf.b, dpsi[j][:, 1].copy()), (wf.c, dpsi[j][:, 2].copy()),
+                       (wf.d, np.atleast_1d(dd[j]))]
+            f[j] = self._objective_value(lml[j] + logjac[j])
+            g[j] = -self._transform_gradients(self._natural_with_priors(natural))
+        return f, g
+
     def _lockstep_applies(self, num_restarts):
+        """Whether the PLAIN batched entry applies (gp_fit_grad_batch, whose members share the resident targets): never for this
+        model -- the library refuses it while an output warp is on.  The restarts of this model ride the warp batch, by
+        ``_warp_lockstep_applies``."""
         return False
+
+    def _warp_lockstep_applies(self, num_restarts):
+        """The plain model's size rule, for the tanh warp (an ``IdentityFunction`` model keeps the serial loop)."""
+        return self._tanh() and GPRegression._lockstep_applies(self, num_restarts)
+
+    def optimize_restarts(self, num_restarts=10, robust=False, verbose=True, parallel=False, num_processes=None, **kwargs):
+        """``GPRegression.optimize_restarts``; ``parallel=True`` takes the lockstep route over gp_fit_grad_warp_batch where
+        ``_warp_lockstep_applies``, the serial loop otherwise."""
+        if parallel and self._warp_lockstep_applies(num_restarts):
+            return self._optimize_restarts_lockstep(num_restarts, robust, verbose, **kwargs)
+        return super(WarpedGP, self).optimize_restarts(num_restarts, robust=robust, verbose=verbose, parallel=parallel,
+                                                       num_processes=num_processes, **kwargs)
 
     def _device_group(self, devices):
         raise NotImplementedError("replica groups score in latent space: outside the output-warped path")
@@ -173,8 +219,9 @@ class WarpedGP(GPRegression):
 
 class WarpedGPModel(BOModel):
     """Bayesian optimisation surrogate over ``WarpedGP`` (warpedgpmodel.py:15-68).  Constructor keywords are the reference's
-    plus ``device``; default kernel Matern-3/2; one ``optimize`` per update (``optimize_restarts`` is kept and unused, as in
-    the reference); ``predict`` returns (mean, std) in the space of the observations with the variance floored at 1e-10;
+    plus ``device`` and ``parallel_restarts``; default kernel Matern-3/2; one ``optimize`` per update (``optimize_restarts``
+    is kept and unused, as in the reference) unless ``parallel_restarts=True`` (an addition, default False): then
+    ``optimize_restarts`` restarts run in lockstep, ``optimize_restarts(parallel=True)``, as ``GPModel`` does; ``predict`` returns (mean, std) in the space of the observations with the variance floored at 1e-10;
     ``get_fmin`` is ``predict(X)[0].min()`` as the reference computes it, cached per fit.
 
     Not a ``GPModel``: the device acquisition entries score the latent GP, so the acquisitions take their host adapter over
@@ -186,8 +233,8 @@ class WarpedGPModel(BOModel):
     analytical_gradient_prediction = True
 
     def __init__(self, kernel=None, noise_var=None, exact_feval=False, optimizer='bfgs', max_iters=1000, optimize_restarts=5,
-                 warping_function=None, warping_terms=3, verbose=False, device=0):
-        vars(self).update(kernel=kernel, noise_var=noise_var, exact_feval=exact_feval, optimizer=optimizer, max_iters=max_iters,
+                 warping_function=None, warping_terms=3, verbose=False, device=0, parallel_restarts=False):
+        vars(self).update(parallel_restarts=bool(parallel_restarts), kernel=kernel, noise_var=noise_var, exact_feval=exact_feval, optimizer=optimizer, max_iters=max_iters,
                           optimize_restarts=optimize_restarts, warping_function=warping_function, warping_terms=warping_terms,
                           verbose=verbose, device=device, model=None)
         self._fmin_cache = None
@@ -211,7 +258,12 @@ class WarpedGPModel(BOModel):
             self._create_model(X_all, Y_all)
         else:
             self.model.set_XY(X_all, Y_all)
-        if self.max_iters > 0:
+        if self.max_iters <= 0:
+            return
+        if self.parallel_restarts:   # the restarts in lockstep, one gp_fit_grad_warp_batch per round (WarpedGP._batch_objective)
+            self.model.optimize_restarts(num_restarts=self.optimize_restarts, verbose=self.verbose, parallel=True,
+                                         optimizer=self.optimizer, max_iters=self.max_iters)
+        else:
             self.model.optimize(optimizer=self.optimizer, messages=self.verbose, max_iters=self.max_iters)
 
     def predict(self, X, with_noise=True):

@@ -169,6 +169,21 @@ int gp_fit_grad_batch(gp_t *gp, int R, const double *variance, const double *len
                       double *lml, double *logdet, double *jitter_used, double *dvariance, double *dlengthscale, double *dnoise,
                       int *status);
 
+/* gp_fit_grad_x for R members in ONE call, member r over inputs of its own, Xw[r] ([R, N, D] row-major, already warped by the
+ * caller); Y, kernel family, ard are the context's, the parameters per member as in the plain batch entry.  dL_dX is [R, N, D].
+ * What InputWarpedGP's restarts in lockstep ask for (GPy/GPy/models/input_warped_gp.py:94-103 per member): each member's warp
+ * parameters differ, so its training inputs do.  The contract is the plain batch entry's -- 1 <= R <= 64, Npad <= 2048,
+ * positive parameters, the jitter ladder per member, status[r] with NaN outputs (the member's dL_dX block included) for a member
+ * that fails, always true fp64, buffers of the batch's own -- plus gp_lml_grad_x's refusals: the Gower option on, P > 16
+ * (GP_ERR_ARG).  Xw travels in one copy (R N D doubles, at most 64 x 2048 x 64).  The resident fit, X, Y, raw targets, output
+ * warp and its log-Jacobian, candidates and every validity flag are untouched; with an output warp on, the members fit the
+ * warped targets the context holds.  Where Npad <= 768 member r's outputs are bitwise those of gp_set_data(Xw[r], Y) +
+ * gp_fit_grad_x with its parameters (the single call takes the single-stream route the batch mirrors); above, they agree to
+ * rounding. */
+int gp_fit_grad_x_batch(gp_t *gp, int R, const double *Xw, const double *variance, const double *lengthscale,
+                        const double *noise, int maxtries, double *lml, double *logdet, double *jitter_used, double *dvariance,
+                        double *dlengthscale, double *dnoise, double *dL_dX, int *status);
+
 /* ---- predict -----------------------------------------------------------
  * Candidates Xs[M,D] are made resident once; the calls below then run on them. */
 int gp_set_candidates(gp_t *gp, const double *Xs, int64_t M);
@@ -278,8 +293,9 @@ int gp_acq_lp_argbest(gp_t *gp, int type, double par, double fmin, double y_mean
  * gives the same bits on every call.
  *
  * While a warp is on, the fit, its gradients, the posterior and the acquisition entry points work in LATENT space, on f(Y):
- * so does the cached minimum of the training mean (the fmin entry point).  The batched fit-and-gradient returns GP_ERR_STATE
- * (its members share Y, and each would need targets warped by parameters of its own), and so do the group entry points that
+ * so does the cached minimum of the training mean (the fmin entry point).  The plain batched fit-and-gradient returns GP_ERR_STATE
+ * (its members share Y, and each would need targets warped by parameters of its own: that is the warp batch entry below, whose
+ * members each warp the raw targets), and so do the group entry points that
  * load, fit or score (a group replicates one un-warped model). */
 
 /* WarpedGP.transform_data + the Jacobian term of log_likelihood (warped_gp.py:42,47-57): the resident targets become
@@ -306,6 +322,19 @@ int gp_warp_grad(gp_t *gp, double *dpsi, double *dd);
 int gp_fit_grad_warp(gp_t *gp, int n_terms, const double *psi, double d, int maxtries, double *lml, double *logdet,
                      double *jitter_used, double *dvariance, double *dlengthscale, double *dnoise, double *log_jacobian,
                      double *dpsi, double *dd);
+
+/* gp_fit_grad_warp for R members in ONE call (WarpedGP's restarts in lockstep): member r fits f_r(Y_raw), f_r the tanh warp
+ * psi[r] ([R, n_terms, 3]), d[r], of the context's RAW targets (those of gp_set_data, whether or not a warp is on), with
+ * kernel parameters of its own as in the plain batch entry.  log_jacobian[R], dpsi[R, n_terms, 3], dd[R] are the member's
+ * sum log f_r', and the gradients gp_warp_grad gives.  The contract is the plain batch entry's -- 1 <= R <= 64, Npad <= 2048,
+ * positive kernel parameters, the jitter ladder per member, status[r] with NaN outputs (log_jacobian, dpsi and dd included) for
+ * a member that fails, always true fp64 -- plus: P = 1, 1 <= n_terms <= 8 and valid warp parameters for every member, else
+ * GP_ERR_ARG.  The resident fit, X, Y, raw targets, the warp in force and its log-Jacobian, candidates and every validity flag
+ * are untouched: the members' targets live in the batch's own buffers.  Bitwise gp_fit_grad_warp per member where Npad <= 768. */
+int gp_fit_grad_warp_batch(gp_t *gp, int R, int n_terms, const double *psi, const double *d, const double *variance,
+                           const double *lengthscale, const double *noise, int maxtries, double *lml, double *logdet,
+                           double *jitter_used, double *dvariance, double *dlengthscale, double *dnoise, double *log_jacobian,
+                           double *dpsi, double *dd, int *status);
 
 /* WarpedGP.predict with predict_in_warped_space (warped_gp.py:62-116) over the resident candidates: the latent posterior
  * (computed first unless the resident one is current), un-normalised as mean y_std + y_mean, var y_std^2 BEFORE the warp is
