@@ -108,6 +108,15 @@ SIGNATURES = [
     ("gp_ens_acq_rows", ctypes.c_int, [_vp, _vp, ctypes.c_int64, ctypes.c_int, ctypes.c_double, _vp, _vp]),
     ("gp_ens_acq", ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_double, c_double_p]),
     ("gp_ens_acq_argbest", ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_double, ctypes.c_int, c_int64_p, c_double_p]),
+    ("gp_es_set_representers", ctypes.c_int, [_vp, c_double_p, ctypes.c_int, ctypes.c_double, ctypes.c_double, c_double_p,
+                                              c_double_p]),
+    ("gp_es_pmin", ctypes.c_int, [_vp, c_double_p, c_double_p, ctypes.c_int, ctypes.c_int, ctypes.c_double, c_double_p,
+                                  c_double_p, c_double_p, c_int_p, c_int_p]),
+    ("gp_es_set_belief", ctypes.c_int, [_vp, c_double_p, c_double_p, c_double_p, c_double_p, ctypes.c_int, c_double_p,
+                                        ctypes.c_int]),
+    ("gp_es_acq", ctypes.c_int, [_vp, ctypes.c_double, c_double_p]),
+    ("gp_es_acq_argbest", ctypes.c_int, [_vp, ctypes.c_double, ctypes.c_int, c_int64_p, c_double_p]),
+    ("gp_es_acq_rows", ctypes.c_int, [_vp, _vp, ctypes.c_int64, ctypes.c_double, _vp]),
     ("gp_predict_full_cov", ctypes.c_int, [_vp, ctypes.c_int, c_double_p, c_double_p]),
     ("gp_predict_grad", ctypes.c_int, [_vp, c_double_p, c_double_p]),
     ("gp_fmin", ctypes.c_int, [_vp, c_double_p]),
@@ -837,6 +846,58 @@ class Handle(object):
         idx, val = ctypes.c_int64(), ctypes.c_double()
         check(self.lib, self.lib.gp_ens_acq_argbest(self.h, int(type_), float(par), int(sense), ctypes.byref(idx),
                                                     ctypes.byref(val)), "gp_ens_acq_argbest")
+        return idx.value, val.value
+
+    # -- entropy search (include/gphip.h, gp_es_*) -------------------------------------------------------------------------
+    def es_set_representers(self, Xr, y_mean=0.0, y_std=1.0):
+        """Make ``Xr`` [R, D] the resident representers; (mu [R], cov [R, R]): their posterior with noise, un-normalised."""
+        Xr = as_f64(Xr, 2)
+        R = Xr.shape[0]
+        mu, cov = np.empty(max(R, 1)), np.empty((max(R, 1), max(R, 1)))
+        check(self.lib, self.lib.gp_es_set_representers(self.h, dptr(Xr), R, float(y_mean), float(y_std), dptr(mu), dptr(cov)),
+              "gp_es_set_representers")
+        return mu, cov
+
+    def es_pmin(self, mu, cov, max_sweeps=50, tol=1e-3):
+        """The EP sweeps of the R chains over the Gaussian (mu, cov): (P, MP, logS [R, R - 1], status [R], sweeps [R])."""
+        mu, cov = as_f64(mu, 1), as_f64(cov, 2)
+        R = mu.shape[0]
+        if cov.shape != (R, R):
+            raise ValueError("cov must be [R, R]")
+        P, MP, logS = (np.zeros((R, max(R - 1, 0))) for _ in range(3))
+        status, sweeps = np.zeros(max(R, 1), dtype=np.int32), np.zeros(max(R, 1), dtype=np.int32)
+        check(self.lib, self.lib.gp_es_pmin(self.h, dptr(mu), dptr(cov), R, int(max_sweeps), float(tol), dptr(P), dptr(MP),
+                                            dptr(logS), status.ctypes.data_as(c_int_p), sweeps.ctypes.data_as(c_int_p)),
+              "gp_es_pmin")
+        return P, MP, logS, status[:R], sweeps[:R]
+
+    def es_set_belief(self, logP, u, G, Q, W):
+        logP, u, G, Q, W = as_f64(np.ravel(logP), 1), as_f64(np.ravel(u), 1), as_f64(G, 2), as_f64(Q, 3), as_f64(np.ravel(W), 1)
+        R = logP.shape[0]
+        if u.shape != (R,) or G.shape != (R, R) or Q.shape != (R, R, R):
+            raise ValueError("belief arrays disagree about R")
+        check(self.lib, self.lib.gp_es_set_belief(self.h, dptr(logP), dptr(u), dptr(G), dptr(Q), R, dptr(W), W.shape[0]),
+              "gp_es_set_belief")
+
+    def es_acq(self, y_std=1.0):
+        """The negated information gain of the resident candidates, [M, 1]."""
+        out = np.empty((self.M, 1))
+        check(self.lib, self.lib.gp_es_acq(self.h, float(y_std), dptr(out)), "gp_es_acq")
+        return out
+
+    def es_acq_rows(self, Xs, y_std=1.0):
+        """The same value at the locations ``Xs`` [M, D] given by value, [M, 1]: up to eight take the fused rows path."""
+        Xs = as_f64(Xs, 2)
+        out = np.empty((Xs.shape[0], 1))
+        rc = self.lib.gp_es_acq_rows(self.h, Xs.ctypes.data, Xs.shape[0], float(y_std), out.ctypes.data)
+        if rc:
+            check(self.lib, rc, "gp_es_acq_rows")
+        return out
+
+    def es_acq_argbest(self, sense, y_std=1.0):
+        idx, val = ctypes.c_int64(), ctypes.c_double()
+        check(self.lib, self.lib.gp_es_acq_argbest(self.h, float(y_std), int(sense), ctypes.byref(idx), ctypes.byref(val)),
+              "gp_es_acq_argbest")
         return idx.value, val.value
 
     def predict(self, include_noise=True):

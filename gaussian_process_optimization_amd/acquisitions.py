@@ -12,6 +12,9 @@ A sparse ``GPModel`` built with ``device_acquisitions=True`` takes the same rout
 Anything else (a foreign ``BOModel``, a cost model, string constraints, several outputs) is scored by ``_Rule`` below from
 ``model.predict[_withGradients]``: each acquisition is one rule giving its value and its two partial derivatives with respect
 to the posterior mean and standard deviation, and every class shares the chain rule built on them.
+
+``AcquisitionEntropySearch`` (ES.py:11-207) is not a rule of mean and deviation: it scores through ``gp_es_*`` (representers, EP
+sweeps, tables, one-location calls) with the belief's closing algebra in ``entropy_search.py``; see the class.
 """
 import numpy as np
 from scipy.special import erfc, log_ndtr, ndtr
@@ -716,3 +719,190 @@ class LocalPenalization(object):
                 rows.append(lp.argbest(table, sense, exclude=rows, devices=devices)[0])
         lp.update_batches(None, None, None)
         return rows
+
+
+# ---- entropy search ---------------------------------------------------------------------------------------------------
+class AcquisitionEntropySearch(AcquisitionBase):
+    """Entropy search (Hennig & Schuler 2012; ES.py:11-207): the expected reduction of the entropy of the belief over where the
+    minimum lies, the belief held on ``num_representer_points`` points drawn by ``sampler`` from ``proposal_function`` (default:
+    log expected improvement inside the bounds, -inf outside; it takes one location or a matrix of them).  Constructor
+    arguments and refusals are the reference's; ``device`` is the addition.
+
+    Where the work runs.  With the exact HIP ``GPModel``, one output, unit cost and no constraints (and ``device`` left True):
+    the representers' posterior (``gp_es_set_representers``), the EP sweeps of p_min (``gp_es_pmin``) and every score
+    (``gp_es_acq`` / ``gp_es_acq_argbest`` over the candidate block, ``gp_es_acq_rows`` for up to eight locations) run on the device; the closing algebra of the belief stays
+    on the host (entropy_search.py).  Otherwise -- a sparse model, a cost model, constraints, ``device=False`` -- the reference's
+    per-candidate arithmetic runs on the host over ``predict``, ``predict_covariance`` and ``get_covariance_between_points``.
+
+    A deliberate difference: the reference samples representers and computes the belief once and never again
+    (``_required_parameters_initialized``); here both are renewed whenever the model's fit has changed (new data or new
+    hyper-parameters), since the belief describes the posterior it was computed from."""
+    analytical_gradient_prediction = False
+
+    def __init__(self, model, space, sampler, optimizer=None, cost_withGradients=None, num_samples=100,
+                 num_representer_points=50, proposal_function=None, burn_in_steps=50, device=True):
+        if not isinstance(model, GPModel):
+            raise RuntimeError("The current entropy search implementation supports only GPModel as model")
+        from scipy.stats import norm
+        super().__init__(model, space, optimizer, cost_withGradients=cost_withGradients)
+        self.analytical_gradient_acq = False
+        self.input_dim = len(self.space.get_bounds())
+        self.num_repr_points = num_representer_points
+        self.burn_in_steps = burn_in_steps
+        self.sampler = sampler
+        self.device = bool(device)
+        self.proposal_function = proposal_function or self._default_proposal()
+        self.W = norm.ppf(np.linspace(1. / (num_samples + 1), 1 - 1. / (num_samples + 1), num_samples))[np.newaxis, :]
+        self.repr_points = self.repr_points_log = self.logP = None
+        self._fit_signature = None
+        self._belief_on_device = False
+
+    @staticmethod
+    def fromConfig(model, space, optimizer, cost_withGradients, config):
+        raise NotImplementedError("Not implemented")
+
+    def _default_proposal(self):
+        box = np.asarray(self.space.get_bounds(), dtype=float)
+        ei = AcquisitionEI(self.model, self.space)
+
+        def log_ei(x):
+            x = np.asarray(x, dtype=float)
+            rows = np.atleast_2d(x)
+            inside = np.all((box[:, 0] <= rows) & (rows <= box[:, 1]), axis=1)
+            out = np.full(rows.shape[0], -np.inf)
+            if inside.any():
+                gain = -ei.acquisition_function(rows[inside]) if ei._device_ok() else ei._compute_acq(rows[inside])
+                with np.errstate(divide='ignore'):
+                    out[inside] = np.log(np.clip(np.ravel(gain), 0., np.inf))
+            return float(out[0]) if x.ndim == 1 else out
+        return log_ei
+
+    # ---- the belief ------------------------------------------------------------------------------------------------------
+    def _es_device_ok(self):
+        if not self.device or self.model.model is None or getattr(self.model, "sparse", False):
+            return False
+        if self.cost_withGradients is not constant_cost_withGradients:
+            return False
+        constrained = getattr(self.space, "has_constraints", None)
+        if constrained is not None and constrained():
+            return False
+        return self.model.model.output_dim == 1
+
+    def _signature(self):
+        """What the belief was computed for: the GP object, its data and its parameters."""
+        gp = self.model.model
+        return (id(gp), getattr(gp, "_data_epoch", None), np.asarray(getattr(gp, "param_array", ()), dtype=float).tobytes())
+
+    def _normaliser(self):
+        nz = self.model.model.normalizer
+        return (0.0, 1.0) if nz is None else (float(nz.mean[0]), float(nz.std[0]))
+
+    def _update_parameters(self):
+        """Representers, their log-proposal values and the belief over them (ES.py:85-112), for the model's current fit."""
+        from . import entropy_search as _es
+        pts, logs = self.sampler.get_samples(self.num_repr_points, self.proposal_function, self.burn_in_steps)
+        pts, logs = np.atleast_2d(np.asarray(pts, dtype=float)), np.asarray(logs, dtype=float).reshape(-1)
+        if np.any(np.isnan(logs)) or np.any(np.isposinf(logs)):
+            raise RuntimeError("Sampler generated representer points with invalid log values: {}".format(logs))
+        keep = ~np.isneginf(logs)      # a representer the proposal gives no mass cannot be the minimum (ES.py:97-102)
+        pts, logs = pts[keep], logs[keep]
+        if pts.shape[0] < 1:
+            raise RuntimeError("Sampler generated no representer point with a finite log value")
+        on_device = self._es_device_ok()
+        gp = self.model.model
+        if on_device:
+            gp._ensure_fit()
+            shift, scale = self._normaliser()
+            mu, cov = gp._h.es_set_representers(pts, shift, scale)
+            cov = np.maximum(cov, 1e-10)       # GPModel._predict's floor, on every entry (gpmodel.py:99)
+        else:
+            mu = np.ravel(self.model.predict(pts)[0])
+            cov = self.model.predict_covariance(pts)
+        R = pts.shape[0]
+        if R == 1:      # one point is the minimum with certainty: nothing to propagate
+            belief = (np.zeros(1), np.zeros((1, 1)), np.zeros((1, 1)), np.zeros((1, 1, 1)))
+        else:
+            sites = gp._h.es_pmin(mu, cov) if on_device else None
+            belief = _es.joint_min(mu, cov, sites)
+        self.repr_points, self.repr_points_log = pts, logs.reshape(-1, 1)
+        self.dlogPdMu, self.dlogPdSigma, self.dlogPdMudMu = belief[1:]
+        self.logP = belief[0].reshape(-1, 1)
+        self._Q = _es.quadratic_forms(self.dlogPdSigma, self.dlogPdMudMu)
+        if on_device:
+            gp._h.es_set_belief(self.logP, self.repr_points_log, self.dlogPdMu, self._Q, self.W)
+        self._fit_signature = self._signature()
+        self._belief_on_device = on_device
+
+    def _required_parameters_initialized(self):
+        return not (self.repr_points is None or self.repr_points_log is None or self.logP is None)
+
+    def _refresh(self, on_device):
+        """The belief of the current fit, on the device when the scoring call will look for it there."""
+        if on_device:
+            self.model.model._ensure_fit()
+        if (not self._required_parameters_initialized() or self._fit_signature != self._signature()
+                or (on_device and not self._belief_on_device)):
+            self._update_parameters()
+
+    def _check_dim(self, x):
+        if x.shape[1] != self.input_dim:
+            raise ValueError("Dimensionality mismatch: x should be of size {}, but is of size {}".format(self.input_dim, x.shape[1]))
+
+    # ---- the contract ----------------------------------------------------------------------------------------------------
+    def _device_block(self, x):
+        x = np.atleast_2d(np.asarray(x, dtype=float))
+        self._check_dim(x)
+        self._refresh(True)
+        gp = self.model.model
+        gp._stage(x)
+        return gp, self._normaliser()[1]
+
+    def acquisition_function(self, x):
+        if self._es_device_ok():
+            x = np.atleast_2d(np.asarray(x, dtype=float))
+            if x.shape[0] <= _FEW_ROWS:      # the optimiser's calls: ONE gp_es_acq_rows, locations by value
+                self._check_dim(x)
+                self._refresh(True)
+                return self.model.model._h.es_acq_rows(x, self._normaliser()[1])
+            gp, scale = self._device_block(x)
+            return gp._h.es_acq(scale)
+        return super().acquisition_function(np.atleast_2d(np.asarray(x, dtype=float)))
+
+    def acquisition_function_withGradients(self, x):
+        return self._compute_acq_withGradients(x)
+
+    def argbest(self, x, sense=-1, devices=None):
+        if devices is not None:
+            raise NotImplementedError("entropy search scores its table on one device")
+        if self._es_device_ok():
+            gp, scale = self._device_block(x)
+            return gp._h.es_acq_argbest(sense, scale)
+        return _pick(self.acquisition_function(x)[:, 0], sense)
+
+    def topk(self, x, k, sense=-1, devices=None):
+        if devices is not None:
+            raise NotImplementedError("entropy search scores its table on one device")
+        scores = self.acquisition_function(x)[:, 0]
+        ranked = np.argsort(scores if sense < 0 else -scores, kind="stable")[:k]
+        idx = np.full(k, -1, dtype=np.int64)
+        val = np.full(k, np.inf if sense < 0 else -np.inf)
+        idx[:ranked.size] = ranked
+        val[:ranked.size] = scores[ranked]
+        return idx, val
+
+    def _compute_acq(self, x):
+        """The host route: ES.py:124-170 candidate by candidate over the model's own predictions."""
+        from . import entropy_search as _es
+        x = np.atleast_2d(np.asarray(x, dtype=float))
+        self._check_dim(x)
+        self._refresh(False)
+        out = np.zeros((x.shape[0], 1))
+        for j in range(x.shape[0]):
+            row = x[[j], :]
+            _, sd = self.model.predict(row, with_noise=False)
+            m = self.model.get_covariance_between_points(self.repr_points, row) / sd
+            out[j, 0] = _es.score(m, self.logP, self.repr_points_log, self.dlogPdMu, self._Q, self.W)
+        return out
+
+    def _compute_acq_withGradients(self, x):
+        raise NotImplementedError("Analytic derivatives are not supported.")

@@ -20,7 +20,8 @@ from scipy import optimize as _sopt
 
 from . import kern as _kern
 from .acquisitions import (AcquisitionEI, AcquisitionLCB, AcquisitionMPI, AcquisitionLP, LocalPenalization, AcquisitionEI_MCMC,
-                           AcquisitionMPI_MCMC, AcquisitionLCB_MCMC)
+                           AcquisitionMPI_MCMC, AcquisitionLCB_MCMC, AcquisitionEntropySearch)
+from .entropy_search import AffineInvariantEnsembleSampler
 from .gpmodel import GPModel
 from .input_warped_gp import InputWarpedGPModel
 from .parameterization import lbfgsb_lockstep, SCIPY_DEFAULT
@@ -382,8 +383,17 @@ class BayesianOptimization(object):
         if mcmc_model and batch_size > 1 and evaluator_type not in ('sequential', 'random', None):
             raise NotImplementedError("evaluator %r is not available with a model that samples its hyper-parameters"
                                       % evaluator_type)
+        entropy = isinstance(acquisition, AcquisitionEntropySearch) or (acquisition is None and acquisition_type == 'ES')
+        if entropy and evaluator_type == 'local_penalization':
+            raise InvalidConfigError("local_penalization needs the acquisition's gradients, which entropy search does not have")
         if acquisition is not None:
             self.acquisition = acquisition
+        elif acquisition_type == 'ES':
+            # the sampler of the representer points and ES.py's keywords (acquisitions/ES.py:12-14)
+            self.acquisition = AcquisitionEntropySearch(
+                self.model, self.space, AffineInvariantEnsembleSampler(self.space, seed=kwargs.get('sampler_seed', None)),
+                self.acquisition_optimizer, cost_withGradients, num_samples=kwargs.get('num_samples', 100),
+                num_representer_points=kwargs.get('num_representer_points', 50), burn_in_steps=kwargs.get('burn_in_steps', 50))
         elif acquisition_type == 'EI_MCMC':
             self.acquisition = AcquisitionEI_MCMC(self.model, self.space, self.acquisition_optimizer, cost_withGradients, jitter)
         elif acquisition_type == 'MPI_MCMC':

@@ -243,6 +243,20 @@ struct EnsState {
     DevBuf<double> dKx, dW, dAcq;    // table route: K_z(Xs, X) and Kx Li_z^T per chunk, the scores
 };
 
+// Entropy search (api_es.hip): the representers of a fit and the belief over them.  R > 0 while dVR / dXr belong to the factor
+// in dA; everything that drops or changes the factor drops both (factor_results_dropped, factor_grown).
+struct EsState {
+    int R = 0;                 // representers resident (0: none)
+    int S = 0;                 // quantiles of the belief
+    bool belief = false;       // dBelief holds a belief over the R representers
+    DevBuf<double> dXr;        // [R, D]
+    DevBuf<double> dVR;        // 128 x Npad: row r = L^-1 K(X, xr_r), zero rows and columns in the padding
+    DevBuf<double> dBelief;    // logP [64], u [64], Gt [64 x 64], W [1024], Qt [R^3] (belief index last)
+    DevBuf<double> dC;         // mc_pad x 128: a chunk's covariance candidate x representer
+    DevBuf<double> dEp;        // gp_es_pmin: mu, cov, P, MP, logS, then status / sweeps words
+    DevBuf<double> dRowsPart;  // gp_es_acq_rows: the workgroups' shares of V_R w and |w|^2 (es_rows_part_elems)
+};
+
 struct gp_ctx {
     int device = 0;
     hipStream_t s = nullptr;       // main stream
@@ -393,6 +407,7 @@ struct gp_ctx {
     DevBuf<double> dWarp;  // 9 M: posterior by value (mean, var), then warped mean, variance, median and the four partials
     SparseState sp;     // the sparse model (api_sparse.hip)
     EnsState ens;       // the ensemble (api_ens.hip)
+    EsState es;         // entropy search: representers and belief (api_es.hip)
     bool dead = false;  // gp_shutdown ran: the device's streams are gone, only gp_destroy is still valid
 };
 
@@ -405,6 +420,8 @@ static inline void factor_results_dropped(gp_ctx *g) {
     g->invp_valid = false;
     g->lr_valid = false;
     g->predicted = false;
+    g->es.R = 0;
+    g->es.belief = false;
 }
 // ... and dA no longer holds a fit of the current data and parameters at all.
 static inline void fit_dropped(gp_ctx *g) {
@@ -429,6 +446,8 @@ static inline void factor_grown(gp_ctx *g) {
     g->fmin_valid = false;
     sparse_fit_dropped(g);
     g->ens.S = 0;
+    g->es.R = 0;
+    g->es.belief = false;
 }
 
 static inline long round_up(long x, long m) { return (x + m - 1) / m * m; }
@@ -608,7 +627,9 @@ void solve_step(gp_ctx *g, hipStream_t s, const Members &m, int J, int rows);
 void solve_rows(gp_ctx *g, const Members &m, int mt, int trapezoid, int J_from = 0);
 int solve_rows_rns(gp_ctx *g, double *T, double *S, int mt, const RnsSolveOpt &opt = RnsSolveOpt());
 int fit_impl(gp_ctx *g, int maxtries, Pipe kind, int include_noise);
-int run_predict(gp_ctx *g, int include_noise, bool tiles_only = false);   // tiles_only: never the small-M path (the caller uses dT2 as a padded tile operand)
+// chunk(m0, mc, mcpad), when given, runs after each chunk's reduce while dT2 still holds that chunk's solved rows (api_es.hip)
+using ChunkHook = std::function<int(long, long, long)>;
+int run_predict(gp_ctx *g, int include_noise, bool tiles_only = false, const ChunkHook *chunk = nullptr);   // tiles_only: never the small-M path (the caller uses dT2 as a padded tile operand)
 int ensure_out(gp_ctx *g);
 // What to score, as the C boundary got it: the base acquisition, and the local penaliser on top of it (the batch on the HOST)
 struct AcqSpec { int type; double par, fmin, y_mean, y_std; };
@@ -618,6 +639,7 @@ int check_lp(const LpSpec &lp);                     // transform 0 / 1, 0 <= nb 
 int check_sense(int sense);
 int check_k(int k);
 int check_exclude(const int64_t *exclude, int nex, int64_t M);
+int argbest_read(gp_ctx *g, const double *v, long n, int sense, int64_t *idx, double *val);   // api_predict.hip: lowest index among the best of v[0, n), drained
 static inline double acq_empty(int sense) { return sense > 0 ? -INFINITY : INFINITY; }   // the value no candidate loses to
 struct LpBatch { double *X = nullptr, *r = nullptr, *s = nullptr; };   // the batch on the device
 static inline LpBatch lp_slots(const gp_ctx *g) { return LpBatch{g->dLp + LP_X.off, g->dLp + LP_R.off, g->dLp + LP_S.off}; }
@@ -645,4 +667,9 @@ int ensure_grad_buffers(gp_ctx *g, long elemsBeta, long M);
 int run_predict_grad(gp_ctx *g);
 void panel_inv_steps(gp_ctx *g, hipStream_t s, double *Wb, long PB, const double *Lb, long lda, const double *Ib, int Wp, GemmOpt o,
                      long sL, long sI);   // api_solve.hip: Wb (the identity on entry) <- L^-T of the Wp-tile lower factor at Lb
+// api_es.hip: what a scoring call needs -- an exact single-output model without a warp, representers and a belief --, and the
+// pointers of the belief for a launch
+int es_ready(gp_ctx *g, double y_std);
+struct EsBelief { const double *Qt, *Gt, *logP, *u, *W; };
+EsBelief es_belief(const gp_ctx *g);
 int warp_apply(gp_ctx *g, bool raw_in_dY);   // api_warp.hip: (dYraw <- dY when dY holds raw targets,) dY <- f(dYraw), warp_logjac; enqueued on g->s, the caller drains

@@ -41,7 +41,7 @@ extern "C" int gp_set_candidates_kumar(gp_t *g, const double *Xs, int64_t M, con
     return 0;
 }
 
-int run_predict(gp_ctx *g, int include_noise, bool tiles_only) {
+int run_predict(gp_ctx *g, int include_noise, bool tiles_only, const ChunkHook *chunk) {
     if (!g->fitted) return fail(GP_ERR_STATE, "gp_fit first");
     if (g->M < 1) return fail(GP_ERR_STATE, "gp_set_candidates first");
     HIPCHK(hipSetDevice(g->device));
@@ -95,6 +95,7 @@ int run_predict(gp_ctx *g, int include_noise, bool tiles_only) {
         launch_predict_reduce(g->s, g->dT2, Npad, mc, N, g->dA + Npad * Npad, Npad, P, g->kp.variance,
                               include_noise ? g->noise : 0.0, g->dMean + m0 * P, g->dVar + m0);
         phase_end(g, ph);
+        if (chunk && (rc = (*chunk)(m0, mc, mcpad))) return rc;
     }
     g->predicted = true;
     g->predicted_noise = include_noise ? 1 : 0;
@@ -152,7 +153,7 @@ static void argbest_launch(gp_ctx *g, const double *v, long n, int sense) {
 }
 static void mask_rows(gp_ctx *g, const long long *rows, int n, int sense) { launch_mask(g->s, g->dAcq, rows, n, acq_empty(sense)); }
 // lowest index among the best of v[0, n), drained (idx may be null: the value alone)
-static int argbest_read(gp_ctx *g, const double *v, long n, int sense, int64_t *idx, double *val) {
+int argbest_read(gp_ctx *g, const double *v, long n, int sense, int64_t *idx, double *val) {
     argbest_launch(g, v, n, sense);
     double hv = 0.0;
     long long hi = 0;

@@ -184,6 +184,36 @@ extern "C" int gp_acq_rows(gp_t *g, const double *Xs, int64_t M, int type, doubl
     return acq_values(g, a, pen, out, dout);
 }
 
+// gp_es_acq for a handful of locations given by value (ES has no analytic gradient: L-BFGS-B runs on differences, D + 1
+// one-location calls per step).  Fused: the forward pass over the inverse factor as for every rows call, then ONE kernel that
+// forms C = k(x, Xr) - V_R w, the variance and the score and reports through the pass's owner (csrc/es.hip).
+extern "C" int gp_es_acq_rows(gp_t *g, const double *Xs, int64_t M, double y_std, double *out) {
+    if (!g || !Xs || !out) return fail(GP_ERR_ARG, "null argument");
+    GP_FITTED(g);
+    if (M < 1) return fail(GP_ERR_ARG, "M < 1");
+    int rc;
+    if ((rc = es_ready(g, y_std))) return rc;
+    if (rows_fused_ok(g, M) && rows_use_factor(g)) {
+        if ((rc = ensure_linv(g))) return rc;
+        EsState &es = g->es;
+        if ((rc = es.dRowsPart.reserve((long)es_rows_part_elems(g->Npad)))) return rc;
+        const EsBelief b = es_belief(g);
+        return rows_exact_passes(
+            g, Xs, (int)M, "rows_es", 1.0,
+            [&](const RowsX &rx, const RowsWork &w, const PassReport &r) {
+                launch_rows_forward(g->s, g->dLi, g->Npad, rx, g->kp, g->dX, g->N, g->dAlpha, w,
+                                    g->rows_nt < 0 ? (g->Npad > 8192 ? 1 : 0) : g->rows_nt);
+                launch_es_rows(g->s, rx, g->kp, es.dXr, es.R, es.dVR, g->Npad, w.wpart, es.dRowsPart, g->kp.variance, y_std, b.Qt, b.Gt,
+                               b.logP, b.u, b.W, es.S, r);
+                return es_rows_grid(g->Npad);
+            },
+            [&](int m0, int mc, int MV, const double *o) { rows_unpack(o, MV, m0, mc, g->D, nullptr, nullptr, out, nullptr, nullptr, nullptr); });
+    }
+    ++g->rows_fallback_calls;
+    if ((rc = gp_set_candidates(g, Xs, M))) return rc;
+    return gp_es_acq(g, y_std, out);
+}
+
 // how many *_rows calls took the fused path / the batched entry points since the context was created (route checks in tests)
 extern "C" int gp_rows_stats(gp_t *g, int64_t *fused, int64_t *fallback) {
     if (!g) return fail(GP_ERR_ARG, "null gp");

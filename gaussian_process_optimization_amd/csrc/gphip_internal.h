@@ -236,6 +236,14 @@ void launch_acq(hipStream_t s, int type, double par, double fmin, double y_mean,
 void launch_argbest(hipStream_t s, const double *v, long n, int sense, double *best_val, long long *best_idx,
                     double *scratch_val, long long *scratch_idx);
 
+// ---- es.hip: entropy search -- the EP sweeps of p_min (one workgroup per chain) and the scoring of candidate rows -----------
+void launch_es_pmin(hipStream_t s, const double *mu, const double *cov, int R, int max_sweeps, double tol, double *P, double *MP,
+                    double *logS, int *status, int *sweeps);
+// C [mc, ldc] latent covariance candidate x representer, var [mc] latent variance without noise; Qt [R, R, R] and Gt [R, R] with
+// the belief index last; out [mc] the negated information gain
+void launch_es_score(hipStream_t s, const double *C, long ldc, const double *var, long mc, double y_std, int R, const double *Qt,
+                     const double *Gt, const double *logP, const double *u, const double *W, int S, double *out);
+
 // ---- smallm.hip: a handful of candidate rows as matrix-vector work (the acquisition optimiser's one-row calls) ----------
 // S[m, :] = T[m, :] L^-T for m < M by forward substitution over the panels (T consumed), inverted diagonal panels invP (W tiles)
 void launch_small_forward_solve(hipStream_t s, const double *L, long lda, const double *invP, int W, long Npad, double *T,
@@ -286,9 +294,20 @@ inline unsigned rows_mean_grad_grid(long N) { return (unsigned)((N + 255) / 256)
 void launch_rows(hipStream_t s, const double *Li, long Npad, const RowsX &rx, const KernParams &kp, const double *X, long N,
                  const double *alpha, int want_grad, double kss, double noise_add, const RowsAcq &aq, const RowsWork &w,
                  const PassReport &r, int nt_loads);
+// the forward launch of launch_rows alone: w.wpart (and w.meanpart) of the pass, no finishing kernel, no arrival at the counter
+void launch_rows_forward(hipStream_t s, const double *Li, long Npad, const RowsX &rx, const KernParams &kp, const double *X, long N,
+                         const double *alpha, const RowsWork &w, int nt_loads);
 // the mean's gradient alone: dmdx [M, D] at r.out + 3 MV (one pass over the training points, no inverse factor)
 void launch_rows_mean_grad(hipStream_t s, const RowsX &rx, const KernParams &kp, const double *X, long N, const double *alpha,
                            const RowsWork &w, const PassReport &r);
+// es.hip: a handful of locations behind the fused rows path's forward pass (launch_rows_forward): the scores into r.out at the
+// acquisition's place of the rows layout, the ticket behind them; cpart: es_rows_part_elems(Npad) doubles; es_rows_grid(Npad)
+// workgroups arrive at the pass's counter
+unsigned es_rows_grid(long Npad);
+size_t es_rows_part_elems(long Npad);
+void launch_es_rows(hipStream_t s, const RowsX &rx, const KernParams &kp, const double *Xr, int R, const double *VR, long Npad,
+                    const double *wpart, double *cpart, double kss, double y_std, const double *Qt, const double *Gt,
+                    const double *logP, const double *u, const double *W, int S, const PassReport &r);
 void launch_transpose_tri(hipStream_t s, double *dst, const double *src, long n, int mode);
 
 // ---- ens_rows.hip: the same passes over an ensemble of S members, the member as a grid dimension --------------------------------

@@ -272,7 +272,7 @@ int rows_block_height(int nt) { return nt <= 16 ? 32 : GP_TILE; }
 template <int MV, int RB, bool NT>
 static void launch_rows_t(hipStream_t s, const double *Li, long Npad, const RowsX &rx, const KernParams &kp, const double *X, long N,
                           const double *alpha, int want_grad, double kss, double noise_add, const RowsAcq &aq, const RowsWork &w,
-                          const PassReport &r) {
+                          const PassReport &r, bool forward_only) {
     const int nt = (int)(Npad / GP_TILE);
     const unsigned tiles = (unsigned)rows_tiles(nt) * (GP_TILE / RB);
     const unsigned fin = rows_finish_grid(N);
@@ -280,17 +280,18 @@ static void launch_rows_t(hipStream_t s, const double *Li, long Npad, const Rows
         GP_LAUNCH((rows_forward_wide_kernel<RB, NT>), dim3(tiles), dim3(256), 0, s, Li, Npad, rx, kp, X, N, alpha, w.wpart, Npad, nt, w.meanpart);
     else
         GP_LAUNCH((rows_forward_kernel<MV, RB, NT>), dim3(tiles), dim3(256), 0, s, Li, Npad, rx, kp, X, N, alpha, w.wpart, Npad, nt, w.meanpart);
+    if (forward_only) return;
     if (want_grad)
         GP_LAUNCH((rows_backward_kernel<MV, RB, NT>), dim3(tiles), dim3(256), 0, s, Li, Npad, w.wpart, Npad, rx.M, w.bpart, w.vpart);
     GP_LAUNCH(rows_finish_kernel<MV>, dim3(fin), dim3(256), 0, s, rx, kp, X, N, alpha, w.wpart, w.bpart, w.meanpart, w.vpart, Npad, nt,
               RB, want_grad, kss, noise_add, aq, w.gpart, r.counter, r.base, r.out, r.ticket);
 }
 
-void launch_rows(hipStream_t s, const double *Li, long Npad, const RowsX &rx, const KernParams &kp, const double *X, long N,
-                 const double *alpha, int want_grad, double kss, double noise_add, const RowsAcq &aq, const RowsWork &w,
-                 const PassReport &r, int nt_loads) {
+static void launch_rows_any(hipStream_t s, const double *Li, long Npad, const RowsX &rx, const KernParams &kp, const double *X, long N,
+                            const double *alpha, int want_grad, double kss, double noise_add, const RowsAcq &aq, const RowsWork &w,
+                            const PassReport &r, int nt_loads, bool forward_only) {
     const bool low = rows_block_height((int)(Npad / GP_TILE)) == 32;
-#define RW_GO(MV, RB, NT) launch_rows_t<MV, RB, NT>(s, Li, Npad, rx, kp, X, N, alpha, want_grad, kss, noise_add, aq, w, r)
+#define RW_GO(MV, RB, NT) launch_rows_t<MV, RB, NT>(s, Li, Npad, rx, kp, X, N, alpha, want_grad, kss, noise_add, aq, w, r, forward_only)
     if (rx.M == 1) {
         if (low) RW_GO(1, 32, false);
         else if (nt_loads) RW_GO(1, GP_TILE, true);
@@ -305,6 +306,18 @@ void launch_rows(hipStream_t s, const double *Li, long Npad, const RowsX &rx, co
         else RW_GO(ROWS_WIDE_M, GP_TILE, false);
     }
 #undef RW_GO
+}
+
+void launch_rows(hipStream_t s, const double *Li, long Npad, const RowsX &rx, const KernParams &kp, const double *X, long N,
+                 const double *alpha, int want_grad, double kss, double noise_add, const RowsAcq &aq, const RowsWork &w,
+                 const PassReport &r, int nt_loads) {
+    launch_rows_any(s, Li, Npad, rx, kp, X, N, alpha, want_grad, kss, noise_add, aq, w, r, nt_loads, false);
+}
+
+// the forward launch alone: another kernel finishes the pass from w.wpart (es.hip)
+void launch_rows_forward(hipStream_t s, const double *Li, long Npad, const RowsX &rx, const KernParams &kp, const double *X, long N,
+                         const double *alpha, const RowsWork &w, int nt_loads) {
+    launch_rows_any(s, Li, Npad, rx, kp, X, N, alpha, 0, 0.0, 0.0, RowsAcq{}, w, PassReport{}, nt_loads, true);
 }
 
 // ---- Li = (L^-T)^T: lower triangular, explicit zeros above the diagonal; and back -------------------------------------------------------

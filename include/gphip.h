@@ -608,6 +608,57 @@ int gp_ens_acq(gp_t *gp, int type, double par, double *out);
 /* arg-best of that vector: sense +1 largest, -1 smallest; ties go to the lowest index. */
 int gp_ens_acq_argbest(gp_t *gp, int type, double par, int sense, int64_t *idx, double *val);
 
+/* ---- entropy search ------------------------------------------------------------------------------------------------------
+ * AcquisitionEntropySearch (GPyOpt/GPyOpt/acquisitions/ES.py) with util/epmgp.py: a belief over which of R representer points is
+ * the minimum, and for every candidate the expected change of that belief's entropy.  The device takes the representers'
+ * posterior, the EP sweeps of p_min and the scoring of candidate tables; the closing algebra of min_faktor (epmgp.py:166-208)
+ * and the renormalisation of joint_min (:92-119) stay on the host (R solves of order R - 1), which hands the belief back with
+ * gp_es_set_belief.  Exact single-output model only.  Always true fp64 ("emulate_fp64" covers the candidate solve of the table
+ * as for gp_predict, never the kernels of csrc/es.hip).
+ * State: representers and belief belong to the fit they were made with; everything that drops or changes the fit (gp_set_data,
+ * gp_set_params, gp_set_gower, gp_kernel_matrix, every gp_fit*, gp_append, gp_set_output_warp, gp_comm_bcast_fit) drops both, and
+ * scoring without them is GP_ERR_STATE -- never a score from a stale belief.  GP_ERR_STATE as well: no fit, an output warp on, a
+ * sparse fit or an ensemble held by the context.  GP_ERR_ARG: R outside 1..GP_ES_MAX_R, S outside 1..GP_ES_MAX_S, P > 1. */
+#define GP_ES_MAX_R 64
+#define GP_ES_MAX_S 1024
+/* ES._update_parameters' model calls (ES.py:105-108): Xr [R, D] becomes resident with V_R = L^-1 K(X, Xr) (a padded 128 x Npad
+ * block); mu [R] and cov [R, R] receive the representers' posterior mean and full covariance WITH noise (posterior.py:280-284,
+ * gaussian.py:104-105), un-normalised as mean y_std + y_mean, cov y_std^2.  No floor is applied (GPModel._predict applies its
+ * 1e-10 on the host).  The resident candidates stay; their cached posterior is dropped.  Drops an earlier belief. */
+int gp_es_set_representers(gp_t *gp, const double *Xr, int R, double y_mean, double y_std, double *mu, double *cov);
+/* The EP sweeps of min_faktor / lt_factor / log_relative_gauss (epmgp.py:122-153, 211-288) for the R chains "representer k is the
+ * minimum" of the Gaussian (mu [R], cov [R, R]) given by value: a pure function of its arguments that needs no data and no fit.
+ * One workgroup per chain, its working mean and covariance in LDS, the factors visited in the reference's order, the
+ * reference's thresholds (|z| > 6, float32 eps, + 1e-25 under the root), at most max_sweeps sweeps (the reference: 50), stopped
+ * where a sweep's sum |d| < tol (the reference: 1e-3) or at the first NaN d.  Out, per chain k: the site parameters P, MP, logS
+ * [R, R - 1]; status[k] = 0 converged, 1 sweep limit, -1 a factor ended the chain (exit_flag -1 or a NaN d: the reference yields
+ * logZ = -inf and zero derivatives), -2 NaN in V (the reference raises); sweeps[k] = sweeps begun. */
+int gp_es_pmin(gp_t *gp, const double *mu, const double *cov, int R, int max_sweeps, double tol, double *P, double *MP,
+               double *logS, int *status, int *sweeps);
+/* The belief over the resident representers: logP [R], the representers' log-proposal values u [R], G [R, R] = dlogPdMu,
+ * Q [R, R, R] with Q_i = (H_i + H_i^T) / 4 - (T_i + T_i^T) / 2 (H = dlogPdMudMu, T_i = dlogPdSigma[i] unpacked into the lower
+ * triangle in row-major order, diagonal whole), so that m^T Q_i m is ES.py:148-154's deterministic change for the innovation m;
+ * W [S] the normal quantiles of ES.py:76-78.  GP_ERR_STATE: no representers, or R differs from theirs. */
+int gp_es_set_belief(gp_t *gp, const double *logP, const double *u, const double *G, const double *Q, int R, const double *W,
+                     int S);
+/* ES._compute_acq (ES.py:124-170) over the resident candidates, negated as acquisition_function returns it: out [M].  Per chunk
+ * of the candidate solve C = K(Xs, Xr) - (K(Xs, X) L^-T) V_R^T; the candidate's variance without noise, floored at 1e-10 after
+ * un-normalising (gpmodel.py:99 through ES.py:199); m = C / s, det_i = m^T Q_i m, g_i = G_i . m; for each w of W the log-sum-exp
+ * over i of logP_i + det_i + g_i w (the maximum instead where any w of the candidate gives an infinite one, ES.py:162-163),
+ * dHp = sum_i e^l (l + u_i); out = -mean_w dHp.  y_std as in gp_acq.  Fixed summation order, no atomics: a candidate's value
+ * does not depend on M or on its row. */
+int gp_es_acq(gp_t *gp, double y_std, double *out);
+/* arg-best of that vector: sense +1 largest, -1 smallest; ties go to the lowest index. */
+int gp_es_acq_argbest(gp_t *gp, double y_std, int sense, int64_t *idx, double *val);
+/* gp_set_candidates + gp_es_acq for the locations Xs [M, D] given by value: what the acquisition optimiser asks for (ES has no
+ * analytic gradient, so L-BFGS-B differences D + 1 one-location calls per step).  For M <= option "small_m" (8) locations that
+ * fit the fused rows path (see gp_predict_rows: the same rules, the same build policy of the inverse factor) a pass is the path's
+ * forward launch over L^-1 -- w = L^-1 k* -- and ONE more kernel: C = k(x, Xr) - V_R w, the variance kss - |w|^2, the score, into
+ * the pinned result block behind the pass's ticket; no copy commands either side.  A location's value is the same bits whatever
+ * its slot and its company.  Otherwise the call is the two table calls.  The routes agree to rounding (tests: 1e-9) and both
+ * count in gp_rows_stats.  The resident candidate block is unspecified afterwards. */
+int gp_es_acq_rows(gp_t *gp, const double *Xs, int64_t M, double y_std, double *out);
+
 /* ---- measurement ---------------------------------------------------------
  * Phase timings of the last gp_fit / gp_predict measured with HIP events on the
  * library's stream; names[i] is a static string, ms[i] milliseconds, flops[i] the
