@@ -246,14 +246,50 @@ def _fit_scalars():
     return ctypes.c_double(), ctypes.c_double(), ctypes.c_double()
 
 
+def _lp_pack(lp, ptr=dptr):
+    """THE packer of the penaliser: ``lp`` = None or (transform, Xb, r_x0, s_x0) -> (on, transform, arrays kept alive, nb,
+    pointers to Xb, r_x0, s_x0 as ``ptr`` makes them); no batch is nb = 0 and null pointers."""
+    if lp is None:
+        return 0, 0, None, 0, None, None, None
+    if lp[1] is None:
+        return 1, int(lp[0]), None, 0, None, None, None
+    keep = (as_f64(np.atleast_2d(lp[1]), 2), as_f64(np.atleast_1d(lp[2]), 1), as_f64(np.atleast_1d(lp[3]), 1))
+    return 1, int(lp[0]), keep, keep[0].shape[0], ptr(keep[0]), ptr(keep[1]), ptr(keep[2])
+
+
 def _lp_args(Xb, r_x0, s_x0):
-    """The penaliser's batch as (arrays kept alive, nb, pointers to Xb, r_x0, s_x0); no batch is nb = 0 and null pointers."""
-    if Xb is None:
-        return None, 0, None, None, None
-    Xb = as_f64(np.atleast_2d(Xb), 2)
-    r = as_f64(np.atleast_1d(r_x0), 1)
-    s = as_f64(np.atleast_1d(s_x0), 1)
-    return (Xb, r, s), Xb.shape[0], dptr(Xb), dptr(r), dptr(s)
+    """The batch alone, for the entries that take the transform by itself: (arrays kept alive, nb, pointers)."""
+    return _lp_pack((0, Xb, r_x0, s_x0))[2:]
+
+
+def _address(a):
+    """An array's address as a plain integer, for the rows entries declared with ``void *``: a typed pointer costs ~4 us apiece."""
+    return a.ctypes.data
+
+
+def _acq_rows_entry(symbol, doc):
+    """``Handle.acq_rows`` / ``Handle.sparse_acq_rows``: one body around the C symbol each names.  The L-BFGS inner loop lives here
+    (~40 us a call, host-bound), so nothing is delegated: addresses instead of typed pointers, no helper for the common cases."""
+    def rows(self, Xs, type_, par, fmin, y_mean=0.0, y_std=1.0, grad=False, lp=None):
+        Xs = np.ascontiguousarray(Xs, dtype=np.float64)
+        if Xs.ndim != 2:
+            raise ValueError("expected a 2-D array, got shape %s" % (Xs.shape,))
+        M = Xs.shape[0]
+        dout = np.empty((M, self.D)) if grad else None
+        if lp is None:
+            out = np.empty((M, 1))
+            on = tr = nb = 0
+            pX = pr = ps = None
+        else:
+            out = np.empty(M)
+            on, tr, keep, nb, pX, pr, ps = _lp_pack(lp, _address)
+        rc = getattr(self.lib, symbol)(self.h, Xs.ctypes.data, M, int(type_), par, fmin, y_mean, y_std, on, tr, pX, nb, pr, ps,
+                                       out.ctypes.data, dout.ctypes.data if grad else None)
+        if rc:
+            check(self.lib, rc, symbol)
+        return (out, dout) if grad else out
+    rows.__doc__ = doc
+    return rows
 
 
 class Handle(object):
@@ -704,17 +740,10 @@ class Handle(object):
         check(self.lib, self.lib.gp_sparse_set_candidates(self.h, dptr(Xs), Xs.shape[0]), "gp_sparse_set_candidates")
         self.sparse_M = Xs.shape[0]
 
-    @staticmethod
-    def _sparse_lp(lp):
-        """``lp`` = None or (transform, Xb, r_x0, s_x0) -> (on, transform, arrays kept alive, nb, pointers)."""
-        if lp is None:
-            return (0, 0) + _lp_args(None, None, None)
-        return (1, int(lp[0])) + _lp_args(lp[1], lp[2], lp[3])
-
     def sparse_acq(self, type_, par, fmin, y_mean=0.0, y_std=1.0, grad=False, lp=None):
         """Negated acquisition of the sparse table, [M, 1] (1-D with ``lp``, as AcquisitionLP returns it), and with ``grad`` its
         gradient [M, D]: the return shapes of ``acq`` / ``acq_grad`` / ``acq_lp`` / ``acq_lp_grad``."""
-        on, tr, keep, nb, pX, pr, ps = self._sparse_lp(lp)
+        on, tr, keep, nb, pX, pr, ps = _lp_pack(lp)
         M = self.sparse_M
         out = np.empty(M) if on else np.empty((M, 1))
         dout = np.empty((M, self.D)) if grad else None
@@ -723,7 +752,7 @@ class Handle(object):
         return (out, dout) if grad else out
 
     def sparse_acq_argbest(self, type_, par, fmin, sense, y_mean=0.0, y_std=1.0, lp=None, exclude=()):
-        on, tr, keep, nb, pX, pr, ps = self._sparse_lp(lp)
+        on, tr, keep, nb, pX, pr, ps = _lp_pack(lp)
         ex = np.asarray(list(exclude), dtype=np.int64)
         idx, val = ctypes.c_int64(), ctypes.c_double()
         check(self.lib, self.lib.gp_sparse_acq_argbest(self.h, int(type_), float(par), float(fmin), float(y_mean), float(y_std),
@@ -763,24 +792,8 @@ class Handle(object):
             check(self.lib, rc, "gp_sparse_predict_rows")
         return dm
 
-    def sparse_acq_rows(self, Xs, type_, par, fmin, y_mean=0.0, y_std=1.0, grad=False, lp=None):
-        """``acq_rows`` on the sparse model: negated acquisition [M, 1] (1-D with ``lp``) and, with ``grad``, its gradient [M, D]."""
-        Xs = as_f64(Xs, 2)
-        M = Xs.shape[0]
-        out = np.empty(M) if lp is not None else np.empty((M, 1))
-        dout = np.empty((M, self.D)) if grad else None
-        on = tr = nb = 0
-        pX = pr = ps = keep = None
-        if lp is not None:
-            on, tr = 1, int(lp[0])
-            if lp[1] is not None:
-                keep = (as_f64(np.atleast_2d(lp[1]), 2), as_f64(np.atleast_1d(lp[2]), 1), as_f64(np.atleast_1d(lp[3]), 1))
-                nb, pX, pr, ps = keep[0].shape[0], keep[0].ctypes.data, keep[1].ctypes.data, keep[2].ctypes.data
-        rc = self.lib.gp_sparse_acq_rows(self.h, Xs.ctypes.data, M, int(type_), par, fmin, y_mean, y_std, on, tr, pX, nb, pr, ps,
-                                         out.ctypes.data, dout.ctypes.data if grad else None)
-        if rc:
-            check(self.lib, rc, "gp_sparse_acq_rows")
-        return (out, dout) if grad else out
+    sparse_acq_rows = _acq_rows_entry("gp_sparse_acq_rows", """``acq_rows`` on the sparse model: negated acquisition [M, 1] (1-D with
+        ``lp``) and, with ``grad``, its gradient [M, D].""")
 
     def sparse_rows_stats(self):
         a, b = ctypes.c_int64(), ctypes.c_int64()
@@ -974,25 +987,8 @@ class Handle(object):
             check(self.lib, rc, "gp_predict_rows")
         return dm
 
-    def acq_rows(self, Xs, type_, par, fmin, y_mean=0.0, y_std=1.0, grad=False, lp=None):
-        """Negated acquisition [M, 1] (and its gradient [M, D]); ``lp`` = (transform, Xb, r_x0, s_x0) adds the local
-        penalisation, in which case the value comes back 1-D as AcquisitionLP returns it."""
-        Xs = as_f64(Xs, 2)
-        M = Xs.shape[0]
-        out = np.empty(M) if lp is not None else np.empty((M, 1))
-        dout = np.empty((M, self.D)) if grad else None
-        on = tr = nb = 0
-        pX = pr = ps = keep = None
-        if lp is not None:
-            on, tr = 1, int(lp[0])
-            if lp[1] is not None:
-                keep = (as_f64(np.atleast_2d(lp[1]), 2), as_f64(np.atleast_1d(lp[2]), 1), as_f64(np.atleast_1d(lp[3]), 1))
-                nb, pX, pr, ps = keep[0].shape[0], keep[0].ctypes.data, keep[1].ctypes.data, keep[2].ctypes.data
-        rc = self.lib.gp_acq_rows(self.h, Xs.ctypes.data, M, int(type_), par, fmin, y_mean, y_std, on, tr, pX, nb, pr, ps,
-                                  out.ctypes.data, dout.ctypes.data if grad else None)
-        if rc:
-            check(self.lib, rc, "gp_acq_rows")
-        return (out, dout) if grad else out
+    acq_rows = _acq_rows_entry("gp_acq_rows", """Negated acquisition [M, 1] (and its gradient [M, D]); ``lp`` = (transform, Xb, r_x0,
+        s_x0) adds the local penalisation, in which case the value comes back 1-D as AcquisitionLP returns it.""")
 
     def rows_stats(self):
         a, b = ctypes.c_int64(), ctypes.c_int64()

@@ -105,6 +105,129 @@ def _pick(values, sense):
     return i, float(values[i])
 
 
+def _host_topk(scores, k, sense):
+    """The ``k`` best entries of a 1-D score vector in order, (indices, values): equal scores lowest index first, index -1 and
+    the value nothing loses to in the tail when there are fewer than ``k`` (what gp_acq_topk returns)."""
+    ranked = np.argsort(scores if sense < 0 else -scores, kind="stable")[:k]
+    idx = np.full(k, -1, dtype=np.int64)
+    val = np.full(k, np.inf if sense < 0 else -np.inf)
+    idx[:ranked.size] = ranked
+    val[:ranked.size] = scores[ranked]
+    return idx, val
+
+
+def _unit_cost_unconstrained(acq):
+    """Unit cost and no constraints: what every device route asks of the acquisition object besides its model."""
+    if acq.cost_withGradients is not constant_cost_withGradients:
+        return False
+    constrained = getattr(acq.space, "has_constraints", None)
+    return not (constrained is not None and constrained())
+
+
+def _normaliser(gp):
+    """(mean, std) the targets of ``gp`` were normalised with: the ``y_mean`` / ``y_std`` of every scoring call."""
+    nz = gp.normalizer
+    return (0.0, 1.0) if nz is None else (float(nz.mean[0]), float(nz.std[0]))
+
+
+# ---- the device routes of EI / LCB / MPI and of the penalised acquisition on top of them ---------------------------------
+class _Route(object):
+    """How the acquisition ``acq`` (an AcquisitionBase with a ``_rule``) reaches libgphip for one kind of model, as four
+    operations with the same arguments for every kind (few rows inside ``score``, table values, arg-best, top-k); ``lp`` is
+    None or the penaliser's (transform, Xb, r_x0, s_x0).  The two routes are module constants: a call creates no object."""
+    rows = None         # the Handle method of the few-rows call
+
+    def score(self, acq, x, grad, lp):
+        """Up to ``_FEW_ROWS`` locations go down by value in ONE gp_*_rows call (what scipy's L-BFGS-B issues, optimizer.py:36-61:
+        hundreds of calls between two fits, each bound by host time); more become the resident table (``values``)."""
+        x = np.asarray(x, dtype=float)
+        if x.ndim != 2:
+            x = np.atleast_2d(x)
+        if x.shape[0] > _FEW_ROWS:
+            return self.values(acq, x, grad, lp)
+        gp = acq.model.model
+        gp._ensure_fit()
+        shift, scale = _normaliser(gp)
+        return getattr(gp._h, self.rows)(x, acq._acq_id, acq._par(), acq._fmin(), shift, scale, grad=grad, lp=lp)
+
+
+class _ExactRoute(_Route):
+    """gp_acq* over the resident candidate block of the exact model; ``devices``: over replicas of it (gp_group_*)."""
+    rows = "acq_rows"
+
+    @staticmethod
+    def _stage(acq, x):
+        """Make ``x`` the resident candidate block (refitting first if data or hyper-parameters changed) and return what
+        every scoring call takes: the handle, fmin and the normaliser's mean / std."""
+        gp = acq.model.model
+        x = np.atleast_2d(np.asarray(x, dtype=float))
+        if gp._dirty:
+            gp._stage(x, fit=False)        # pending refit: fit + posterior at x go down as ONE call
+            gp._predict_resident(True)     # GPModel.predict: with_noise=True (gpmodel.py:102)
+        else:
+            gp._stage(x)
+        return (gp._h, acq._fmin()) + _normaliser(gp)
+
+    @staticmethod
+    def _group(acq, x, devices):
+        """``x`` split over the replicas of the model on ``devices``: the group, fmin, normaliser mean / std."""
+        gp = acq.model.model
+        grp = gp._device_group(devices)
+        grp.set_candidates(np.atleast_2d(np.asarray(x, dtype=float)))
+        nz = gp.normalizer
+        fmin = grp.fmin() if acq._rule.needs_fmin else 0.0
+        if acq._rule.needs_fmin and nz is not None:
+            fmin = float(nz.inverse_mean(np.array([[fmin]]))[0, 0])
+        return (grp, fmin) + _normaliser(gp)
+
+    def values(self, acq, x, grad, lp):
+        h, fmin, shift, scale = self._stage(acq, x)
+        if lp is None:      # the exact handle names its four table calls: acq / acq_grad / acq_lp / acq_lp_grad
+            return (h.acq_grad if grad else h.acq)(acq._acq_id, acq._par(), fmin, shift, scale)
+        return (h.acq_lp_grad if grad else h.acq_lp)(acq._acq_id, acq._par(), fmin, lp[0], Xb=lp[1], r_x0=lp[2], s_x0=lp[3],
+                                                     y_mean=shift, y_std=scale)
+
+    def argbest(self, acq, x, sense, lp, exclude, devices):
+        o, fmin, shift, scale = self._stage(acq, x) if devices is None else self._group(acq, x, devices)
+        if lp is None:
+            return o.acq_argbest(acq._acq_id, acq._par(), fmin, sense, shift, scale)
+        return o.acq_lp_argbest(acq._acq_id, acq._par(), fmin, lp[0], sense, Xb=lp[1], r_x0=lp[2], s_x0=lp[3], exclude=exclude,
+                                y_mean=shift, y_std=scale)
+
+    def topk(self, acq, x, k, sense, devices):
+        o, fmin, shift, scale = self._stage(acq, x) if devices is None else self._group(acq, x, devices)
+        return o.acq_topk(acq._acq_id, acq._par(), fmin, sense, k, shift, scale)
+
+
+class _SparseRoute(_Route):
+    """gp_sparse_acq* over the sparse model's own candidate table."""
+    rows = "sparse_acq_rows"
+
+    @staticmethod
+    def _stage(acq, x, devices=None):
+        """Make ``x`` the sparse model's resident table (not uploaded again while it is the same table)."""
+        gp = acq.model.model
+        if devices is not None:
+            gp._device_group(devices)      # replica groups score the exact GP: NotImplementedError
+        gp._stage_table(np.atleast_2d(np.asarray(x, dtype=float)))
+        return (gp._h, acq._fmin()) + _normaliser(gp)
+
+    def values(self, acq, x, grad, lp):
+        h, fmin, shift, scale = self._stage(acq, x)
+        return h.sparse_acq(acq._acq_id, acq._par(), fmin, shift, scale, grad=grad, lp=lp)
+
+    def argbest(self, acq, x, sense, lp, exclude, devices):
+        h, fmin, shift, scale = self._stage(acq, x, devices)
+        return h.sparse_acq_argbest(acq._acq_id, acq._par(), fmin, sense, shift, scale, lp=lp, exclude=exclude)
+
+    def topk(self, acq, x, k, sense, devices):
+        h, fmin, shift, scale = self._stage(acq, x, devices)
+        return h.sparse_acq_topk(acq._acq_id, acq._par(), fmin, sense, k, shift, scale)
+
+
+_EXACT, _SPARSE = _ExactRoute(), _SparseRoute()
+
+
 class AcquisitionBase(object):
     """base.py:7-68.  Subclasses either name a ``_rule`` (EI / LCB / MPI) or override ``_compute_acq`` /
     ``_compute_acq_withGradients`` as in GPyOpt."""
@@ -132,106 +255,42 @@ class AcquisitionBase(object):
     # ---- device route ----------------------------------------------------------------------------------------------
     def _device_ok(self):
         """True when libgphip can score this acquisition by itself: our exact GPModel, one output, unit cost, no constraints.
-        (The device entries score the exact posterior: a sparse model takes the host rule over its own predictions.)"""
-        if self._rule is None or not isinstance(self.model, GPModel) or self.model.model is None:
+        (The device entries score the exact posterior: a sparse model takes the sparse route or the host rule.)"""
+        m = self.model
+        if self._rule is None or not isinstance(m, GPModel) or m.model is None or getattr(m, "sparse", False):
             return False
-        if getattr(self.model, "sparse", False):
-            return False
-        if self.cost_withGradients is not constant_cost_withGradients:
-            return False
-        constrained = getattr(self.space, "has_constraints", None)
-        if constrained is not None and constrained():
-            return False
-        return self.model.model.output_dim == 1
+        return _unit_cost_unconstrained(self) and m.model.output_dim == 1
 
     def _sparse_device_ok(self):
         """True when libgphip scores this acquisition over the SPARSE posterior (gp_sparse_acq*): our GPModel with ``sparse=True``
         and ``device_acquisitions=True``, one output, unit cost, no constraints."""
-        if self._rule is None or not isinstance(self.model, GPModel) or self.model.model is None:
+        m = self.model
+        if self._rule is None or not isinstance(m, GPModel) or m.model is None:
             return False
-        if not (getattr(self.model, "sparse", False) and getattr(self.model, "device_acquisitions", False)):
+        if not (getattr(m, "sparse", False) and getattr(m, "device_acquisitions", False)):
             return False
-        if self.cost_withGradients is not constant_cost_withGradients:
-            return False
-        constrained = getattr(self.space, "has_constraints", None)
-        if constrained is not None and constrained():
-            return False
-        return self.model.model.output_dim == 1
+        return _unit_cost_unconstrained(self) and m.model.output_dim == 1
 
-    def _sparse_stage(self, x, devices=None):
-        """Make ``x`` the sparse model's resident table (not uploaded again while it is the same table) and return what every
-        sparse scoring call takes: the handle owner, fmin and the normaliser's mean / std."""
-        gp = self.model.model
-        if devices is not None:
-            gp._device_group(devices)      # replica groups score the exact GP: NotImplementedError
-        gp._stage_table(np.atleast_2d(np.asarray(x, dtype=float)))
-        nz = gp.normalizer
-        shift, scale = (0.0, 1.0) if nz is None else (float(nz.mean[0]), float(nz.std[0]))
-        return gp, self._fmin(), shift, scale
-
-    def _device_stage(self, x):
-        """Make ``x`` the resident candidate block (refitting first if data or hyper-parameters changed) and return what
-        every device scoring call takes: the handle owner, fmin and the normaliser's mean / std."""
-        gp = self.model.model
-        x = np.atleast_2d(np.asarray(x, dtype=float))
-        if gp._dirty:
-            gp._stage(x, fit=False)        # pending refit: fit + posterior at x go down as ONE call
-            gp._predict_resident(True)     # GPModel.predict: with_noise=True (gpmodel.py:102)
-        else:
-            gp._stage(x)
-        nz = gp.normalizer
-        shift, scale = (0.0, 1.0) if nz is None else (float(nz.mean[0]), float(nz.std[0]))
-        return gp, self._fmin(), shift, scale
-
-    def _device_few(self, x):
-        """The handful-of-locations route (what scipy's L-BFGS-B issues, optimizer.py:36-61): ``x`` as a 2-D float array when it
-        has at most ``_FEW_ROWS`` rows -- the caller then makes ONE gp_acq_rows call, locations by value -- else None.
-        Also returns what that call takes: the handle owner, fmin and the normaliser's mean / std."""
-        x = np.atleast_2d(np.asarray(x, dtype=float))
-        if x.shape[0] > _FEW_ROWS:
-            return None
-        gp = self.model.model
-        gp._ensure_fit()
-        nz = gp.normalizer
-        shift, scale = (0.0, 1.0) if nz is None else (float(nz.mean[0]), float(nz.std[0]))
-        return x, gp, self._fmin(), shift, scale
+    def _route(self):
+        """THE choice of where this acquisition is scored: the exact route, the sparse route, or None (the host rule)."""
+        if self._device_ok():
+            return _EXACT
+        return _SPARSE if self._sparse_device_ok() else None
 
     # ---- the contract ----------------------------------------------------------------------------------------------
     def acquisition_function(self, x):
         """-(acq(x) * feasibility(x)) / cost(x), [M, 1]  (base.py:33-39)."""
-        if self._device_ok():
-            few = self._device_few(x)
-            if few is not None:
-                x, gp, fmin, shift, scale = few
-                return gp._h.acq_rows(x, self._acq_id, self._par(), fmin, shift, scale)
-            gp, fmin, shift, scale = self._device_stage(x)
-            return gp._h.acq(self._acq_id, self._par(), fmin, shift, scale)
-        if self._sparse_device_ok():
-            few = self._device_few(x)
-            if few is not None:
-                x, gp, fmin, shift, scale = few
-                return gp._h.sparse_acq_rows(x, self._acq_id, self._par(), fmin, shift, scale)
-            gp, fmin, shift, scale = self._sparse_stage(x)
-            return gp._h.sparse_acq(self._acq_id, self._par(), fmin, shift, scale)
+        route = self._route()
+        if route is not None:
+            return route.score(self, x, False, None)
         price, _ = self.cost_withGradients(x)
         return -(self._compute_acq(x) * self.space.indicator_constraints(x)) / price
 
     def acquisition_function_withGradients(self, x):
         """The same value and its x-gradient [M, D]  (base.py:42-50)."""
-        if self._device_ok():
-            few = self._device_few(x)
-            if few is not None:
-                x, gp, fmin, shift, scale = few
-                return gp._h.acq_rows(x, self._acq_id, self._par(), fmin, shift, scale, grad=True)
-            gp, fmin, shift, scale = self._device_stage(x)
-            return gp._h.acq_grad(self._acq_id, self._par(), fmin, shift, scale)
-        if self._sparse_device_ok():
-            few = self._device_few(x)
-            if few is not None:
-                x, gp, fmin, shift, scale = few
-                return gp._h.sparse_acq_rows(x, self._acq_id, self._par(), fmin, shift, scale, grad=True)
-            gp, fmin, shift, scale = self._sparse_stage(x)
-            return gp._h.sparse_acq(self._acq_id, self._par(), fmin, shift, scale, grad=True)
+        route = self._route()
+        if route is not None:
+            return route.score(self, x, True, None)
         val, dval = self._compute_acq_withGradients(x)
         price, dprice = self.cost_withGradients(x)
         feasible = self.space.indicator_constraints(x)
@@ -239,53 +298,23 @@ class AcquisitionBase(object):
         dquotient = (dval * price - val * dprice) / (price ** 2)
         return -quotient * feasible, -dquotient * feasible
 
-    def _group_stage(self, x, devices):
-        """``x`` split over the replicas of the model on ``devices`` (gp_group_*): the group, fmin, normaliser mean / std."""
-        gp = self.model.model
-        grp = gp._device_group(devices)
-        grp.set_candidates(np.atleast_2d(np.asarray(x, dtype=float)))
-        nz = gp.normalizer
-        shift, scale = (0.0, 1.0) if nz is None else (float(nz.mean[0]), float(nz.std[0]))
-        fmin = grp.fmin() if self._rule.needs_fmin else 0.0
-        if self._rule.needs_fmin and nz is not None:
-            fmin = float(nz.inverse_mean(np.array([[fmin]]))[0, 0])
-        return grp, fmin, shift, scale
-
     def argbest(self, x, sense=-1, devices=None):
         """Row index and value of the best entry of ``acquisition_function(x)``: sense=-1 the smallest (GPyOpt's convention,
         anchor_points_generator.py:61), sense=+1 the largest (run.py:1241 takes ``np.argmax``).  Ties -> lowest index.
         ``devices=[0, 1, ...]``: the table is split over replicas of the model on those GPUs, still from this one process."""
-        if self._device_ok():
-            if devices is not None:
-                grp, fmin, shift, scale = self._group_stage(x, devices)
-                return grp.acq_argbest(self._acq_id, self._par(), fmin, sense, shift, scale)
-            gp, fmin, shift, scale = self._device_stage(x)
-            return gp._h.acq_argbest(self._acq_id, self._par(), fmin, sense, shift, scale)
-        if self._sparse_device_ok():
-            gp, fmin, shift, scale = self._sparse_stage(x, devices)
-            return gp._h.sparse_acq_argbest(self._acq_id, self._par(), fmin, sense, shift, scale)
+        route = self._route()
+        if route is not None:
+            return route.argbest(self, x, sense, None, (), devices)
         return _pick(self.acquisition_function(x)[:, 0], sense)
 
     def topk(self, x, k, sense=-1, devices=None):
         """The ``k`` best rows in order, (indices, values): what ``AnchorPointsGenerator.get`` keeps
         (anchor_points_generator.py:59-61).  Equal scores lowest index first; fewer than ``k`` rows -> index -1 in the tail.
         ``devices``: as in ``argbest``."""
-        if self._device_ok() and k <= 64:
-            if devices is not None:
-                grp, fmin, shift, scale = self._group_stage(x, devices)
-                return grp.acq_topk(self._acq_id, self._par(), fmin, sense, k, shift, scale)
-            gp, fmin, shift, scale = self._device_stage(x)
-            return gp._h.acq_topk(self._acq_id, self._par(), fmin, sense, k, shift, scale)
-        if self._sparse_device_ok() and k <= 64:
-            gp, fmin, shift, scale = self._sparse_stage(x, devices)
-            return gp._h.sparse_acq_topk(self._acq_id, self._par(), fmin, sense, k, shift, scale)
-        scores = self.acquisition_function(x)[:, 0]
-        ranked = np.argsort(scores if sense < 0 else -scores, kind="stable")[:k]
-        idx = np.full(k, -1, dtype=np.int64)
-        val = np.full(k, np.inf if sense < 0 else -np.inf)
-        idx[:ranked.size] = ranked
-        val[:ranked.size] = scores[ranked]
-        return idx, val
+        route = self._route()
+        if route is not None and k <= 64:
+            return route.topk(self, x, k, sense, devices)
+        return _host_topk(self.acquisition_function(x)[:, 0], k, sense)
 
     def optimize(self, duplicate_manager=None):
         """Hand the (negated) acquisition to the acquisition optimiser (base.py:52-60)."""
@@ -378,10 +407,7 @@ class _IntegratedAcquisition(AcquisitionBase):
     def _ens_ok(self):
         if not isinstance(self.model, GPModel_MCMC) or self.model.model is None or self.model.hmc_samples is None:
             return False
-        if self.cost_withGradients is not constant_cost_withGradients:
-            return False
-        constrained = getattr(self.space, "has_constraints", None)
-        return not (constrained is not None and constrained())
+        return _unit_cost_unconstrained(self)
 
     def acquisition_function(self, x):
         if not self._ens_ok():
@@ -511,7 +537,7 @@ class AcquisitionLP(AcquisitionBase):
         self.X_batch, have_batch = X_batch, X_batch is not None
         if have_batch:
             self.r_x0, self.s_x0 = self._ball_parameters(X_batch, L, Min)
-        self._lp_packed = None          # (transform, Xb, r, s) as contiguous float64, built once per batch (see _lp_few)
+        self._lp_packed = None          # (transform, Xb, r, s) as contiguous float64, built once per batch (see _lp_spec)
 
     def _ball_parameters(self, centres, L, Min):
         mu, spread = self.model.predict(np.atleast_2d(centres))
@@ -541,63 +567,48 @@ class AcquisitionLP(AcquisitionBase):
         return term.sum(axis=1)[:, None]
 
     # -- device route ------------------------------------------------------------------------------------------------
-    def _lp_device_ok(self):
+    def _lp_route(self):
+        """The route of the base acquisition, when it scores this model and the transform is one the device knows."""
         base = self.acq
-        return base is not None and base.model is self.model and base._device_ok() and self.transform in ('none', 'softplus')
+        if base is None or base.model is not self.model or self.transform not in ('none', 'softplus'):
+            return None
+        return base._route()
+
+    def _lp_device_ok(self):
+        return self._lp_route() is _EXACT
 
     def _lp_sparse_ok(self):
-        base = self.acq
-        return (base is not None and base.model is self.model and base._sparse_device_ok()
-                and self.transform in ('none', 'softplus'))
+        return self._lp_route() is _SPARSE
+
+    @property
+    def _softplus(self):
+        """The ``transform`` argument of the device entries: 1 softplus, 0 none."""
+        return 1 if self.transform == 'softplus' else 0
 
     def _lp_spec(self):
-        """(transform, Xb, r_x0, s_x0) of the batch in force, as the sparse entries take it."""
-        return (1 if self.transform == 'softplus' else 0, self.X_batch, self.r_x0, self.s_x0)
-
-    def _lp_call(self, x):
-        base = self.acq
-        gp, fmin, shift, scale = base._device_stage(x)
-        head = (base._acq_id, base._par(), fmin, 1 if self.transform == 'softplus' else 0)
-        batch = dict(Xb=self.X_batch, r_x0=self.r_x0, s_x0=self.s_x0, y_mean=shift, y_std=scale)
-        return gp._h, head, batch
-
-    def _lp_few(self, x, grad, sparse=False):
-        """ONE gp_acq_rows call (gp_sparse_acq_rows with ``sparse``) for up to ``_FEW_ROWS`` locations (None otherwise): the
-        L-BFGS runs of compute_batch."""
-        few = self.acq._device_few(x)
-        if few is None:
-            return None
-        x, gp, fmin, shift, scale = few
+        """(transform, Xb, r_x0, s_x0) of the batch in force as contiguous float64, built once per batch: an L-BFGS run of
+        compute_batch makes hundreds of calls with one batch (per object identity of the batch attributes: assigning new
+        arrays renews it)."""
         src = (self.X_batch, self.r_x0, self.s_x0, self.transform)
         held = getattr(self, "_lp_packed", None)
-        lp = held[1] if held is not None and all(a is b for a, b in zip(held[0], src)) else None
-        if lp is None:      # an L-BFGS run makes hundreds of calls with one batch: convert it once (per object identity of the
-            tr = 1 if self.transform == 'softplus' else 0          # batch attributes: assigning new arrays renews it)
-            if self.X_batch is None:
-                lp = (tr, None, None, None)
-            else:
-                lp = (tr, np.ascontiguousarray(np.atleast_2d(self.X_batch), dtype=float),
-                      np.ascontiguousarray(np.atleast_1d(self.r_x0), dtype=float),
-                      np.ascontiguousarray(np.atleast_1d(self.s_x0), dtype=float))
-            self._lp_packed = (src, lp)
-        rows = gp._h.sparse_acq_rows if sparse else gp._h.acq_rows
-        return rows(x, self.acq._acq_id, self.acq._par(), fmin, shift, scale, grad=grad, lp=lp)
+        if held is not None:
+            was = held[0]
+            if was[0] is src[0] and was[1] is src[1] and was[2] is src[2] and was[3] is src[3]:
+                return held[1]
+        if self.X_batch is None:
+            lp = (self._softplus, None, None, None)
+        else:
+            lp = (self._softplus, np.ascontiguousarray(np.atleast_2d(self.X_batch), dtype=float),
+                  np.ascontiguousarray(np.atleast_1d(self.r_x0), dtype=float),
+                  np.ascontiguousarray(np.atleast_1d(self.s_x0), dtype=float))
+        self._lp_packed = (src, lp)
+        return lp
 
     def acquisition_function(self, x):
         """1-D array like the reference's (LP.py:105-110)."""
-        if self._lp_device_ok():
-            few = self._lp_few(x, False)
-            if few is not None:
-                return few
-            h, head, batch = self._lp_call(x)
-            return h.acq_lp(*head, **batch)
-        if self._lp_sparse_ok():
-            few = self._lp_few(x, False, sparse=True)
-            if few is not None:
-                return few
-            base = self.acq
-            gp, fmin, shift, scale = base._sparse_stage(x)
-            return gp._h.sparse_acq(base._acq_id, base._par(), fmin, shift, scale, lp=self._lp_spec())
+        route = self._lp_route()
+        if route is not None:
+            return route.score(self.acq, x, False, self._lp_spec())
         return self._score_on_host(x)
 
     def d_acquisition_function(self, x):
@@ -606,19 +617,9 @@ class AcquisitionLP(AcquisitionBase):
     def acquisition_function_withGradients(self, x):
         """(value [M], gradient [M, D])  (LP.py:112-140)."""
         x = np.atleast_2d(np.asarray(x, dtype=float))
-        if self._lp_device_ok():
-            few = self._lp_few(x, True)
-            if few is not None:
-                return few
-            h, head, batch = self._lp_call(x)
-            return h.acq_lp_grad(*head, **batch)
-        if self._lp_sparse_ok():
-            few = self._lp_few(x, True, sparse=True)
-            if few is not None:
-                return few
-            base = self.acq
-            gp, fmin, shift, scale = base._sparse_stage(x)
-            return gp._h.sparse_acq(base._acq_id, base._par(), fmin, shift, scale, grad=True, lp=self._lp_spec())
+        route = self._lp_route()
+        if route is not None:
+            return route.score(self.acq, x, True, self._lp_spec())
         neg, dneg = self.acq.acquisition_function_withGradients(x)
         with np.errstate(over='ignore', divide='ignore'):
             _, slope = _log_transform(-neg[:, 0], self.transform)
@@ -630,20 +631,9 @@ class AcquisitionLP(AcquisitionBase):
     def argbest(self, x, sense=+1, exclude=(), devices=None):
         """Arg-best of ``acquisition_function(x)`` with the rows in ``exclude`` masked out (run.py:1241,1249-1252).
         ``devices``: the table split over replicas of the model on those GPUs, from this one process (gp_group_*)."""
-        if self._lp_device_ok():
-            if devices is not None:
-                base = self.acq
-                grp, fmin, shift, scale = base._group_stage(x, devices)
-                return grp.acq_lp_argbest(base._acq_id, base._par(), fmin, 1 if self.transform == 'softplus' else 0, sense,
-                                          Xb=self.X_batch, r_x0=self.r_x0, s_x0=self.s_x0, exclude=exclude, y_mean=shift,
-                                          y_std=scale)
-            h, head, batch = self._lp_call(x)
-            return h.acq_lp_argbest(head[0], head[1], head[2], head[3], sense, exclude=exclude, **batch)
-        if self._lp_sparse_ok():
-            base = self.acq
-            gp, fmin, shift, scale = base._sparse_stage(x, devices)
-            return gp._h.sparse_acq_argbest(base._acq_id, base._par(), fmin, sense, shift, scale, lp=self._lp_spec(),
-                                            exclude=exclude)
+        route = self._lp_route()
+        if route is not None:
+            return route.argbest(self.acq, x, sense, self._lp_spec(), exclude, devices)
         scores = np.array(self.acquisition_function(x), dtype=float)
         scores[list(exclude)] = -np.inf if sense > 0 else np.inf
         return _pick(scores, sense)
@@ -781,21 +771,12 @@ class AcquisitionEntropySearch(AcquisitionBase):
     def _es_device_ok(self):
         if not self.device or self.model.model is None or getattr(self.model, "sparse", False):
             return False
-        if self.cost_withGradients is not constant_cost_withGradients:
-            return False
-        constrained = getattr(self.space, "has_constraints", None)
-        if constrained is not None and constrained():
-            return False
-        return self.model.model.output_dim == 1
+        return _unit_cost_unconstrained(self) and self.model.model.output_dim == 1
 
     def _signature(self):
         """What the belief was computed for: the GP object, its data and its parameters."""
         gp = self.model.model
         return (id(gp), getattr(gp, "_data_epoch", None), np.asarray(getattr(gp, "param_array", ()), dtype=float).tobytes())
-
-    def _normaliser(self):
-        nz = self.model.model.normalizer
-        return (0.0, 1.0) if nz is None else (float(nz.mean[0]), float(nz.std[0]))
 
     def _update_parameters(self):
         """Representers, their log-proposal values and the belief over them (ES.py:85-112), for the model's current fit."""
@@ -812,7 +793,7 @@ class AcquisitionEntropySearch(AcquisitionBase):
         gp = self.model.model
         if on_device:
             gp._ensure_fit()
-            shift, scale = self._normaliser()
+            shift, scale = _normaliser(gp)
             mu, cov = gp._h.es_set_representers(pts, shift, scale)
             cov = np.maximum(cov, 1e-10)       # GPModel._predict's floor, on every entry (gpmodel.py:99)
         else:
@@ -855,7 +836,7 @@ class AcquisitionEntropySearch(AcquisitionBase):
         self._refresh(True)
         gp = self.model.model
         gp._stage(x)
-        return gp, self._normaliser()[1]
+        return gp, _normaliser(gp)[1]
 
     def acquisition_function(self, x):
         if self._es_device_ok():
@@ -863,7 +844,7 @@ class AcquisitionEntropySearch(AcquisitionBase):
             if x.shape[0] <= _FEW_ROWS:      # the optimiser's calls: ONE gp_es_acq_rows, locations by value
                 self._check_dim(x)
                 self._refresh(True)
-                return self.model.model._h.es_acq_rows(x, self._normaliser()[1])
+                return self.model.model._h.es_acq_rows(x, _normaliser(self.model.model)[1])
             gp, scale = self._device_block(x)
             return gp._h.es_acq(scale)
         return super().acquisition_function(np.atleast_2d(np.asarray(x, dtype=float)))
@@ -882,13 +863,7 @@ class AcquisitionEntropySearch(AcquisitionBase):
     def topk(self, x, k, sense=-1, devices=None):
         if devices is not None:
             raise NotImplementedError("entropy search scores its table on one device")
-        scores = self.acquisition_function(x)[:, 0]
-        ranked = np.argsort(scores if sense < 0 else -scores, kind="stable")[:k]
-        idx = np.full(k, -1, dtype=np.int64)
-        val = np.full(k, np.inf if sense < 0 else -np.inf)
-        idx[:ranked.size] = ranked
-        val[:ranked.size] = scores[ranked]
-        return idx, val
+        return _host_topk(self.acquisition_function(x)[:, 0], k, sense)
 
     def _compute_acq(self, x):
         """The host route: ES.py:124-170 candidate by candidate over the model's own predictions."""

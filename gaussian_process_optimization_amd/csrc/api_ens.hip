@@ -311,9 +311,7 @@ extern "C" int gp_ens_acq(gp_t *g, int type, double par, double *out) {
     int rc;
     if ((rc = ens_ready(g))) return rc;
     if ((rc = ens_table_scores(g, type, par))) return rc;
-    HIPCHK(hipMemcpyAsync(out, g->ens.dAcq, sizeof(double) * g->M, hipMemcpyDeviceToHost, g->s));
-    GP_SYNC(g->s);
-    return 0;
+    return scores_out(g, g->ens.dAcq, nullptr, g->M, g->D, out, nullptr);
 }
 
 extern "C" int gp_ens_acq_argbest(gp_t *g, int type, double par, int sense, int64_t *idx, double *val) {
@@ -322,14 +320,5 @@ extern "C" int gp_ens_acq_argbest(gp_t *g, int type, double par, int sense, int6
     if ((rc = ens_ready(g))) return rc;
     if ((rc = check_sense(sense))) return rc;
     if ((rc = ens_table_scores(g, type, par))) return rc;
-    launch_argbest(g->s, g->ens.dAcq, g->M, sense, g->dRedV + RED_RESULT.off, g->dRedI + RED_RESULT.off, g->dRedV + RED_PARTIAL.off,
-                   g->dRedI + RED_PARTIAL.off);
-    double hv = 0.0;
-    long long hi = 0;
-    HIPCHK(hipMemcpyAsync(&hv, g->dRedV + RED_RESULT.off, sizeof(double), hipMemcpyDeviceToHost, g->s));
-    HIPCHK(hipMemcpyAsync(&hi, g->dRedI + RED_RESULT.off, sizeof(long long), hipMemcpyDeviceToHost, g->s));
-    GP_SYNC(g->s);
-    *val = hv;
-    *idx = (int64_t)hi;
-    return 0;
+    return select_best(g, g->ens.dAcq, g->M, sense, nullptr, 0, idx, val);
 }

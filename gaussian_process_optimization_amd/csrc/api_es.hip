@@ -164,9 +164,7 @@ extern "C" int gp_es_acq(gp_t *g, double y_std, double *out) {
     GP_SCORING(g);
     int rc;
     if ((rc = run_es_acq(g, y_std))) return rc;
-    HIPCHK(hipMemcpyAsync(out, g->dAcq, sizeof(double) * g->M, hipMemcpyDeviceToHost, g->s));
-    GP_SYNC(g->s);
-    return 0;
+    return scores_out(g, g->dAcq, nullptr, g->M, g->D, out, nullptr);
 }
 
 extern "C" int gp_es_acq_argbest(gp_t *g, double y_std, int sense, int64_t *idx, double *val) {
@@ -175,5 +173,5 @@ extern "C" int gp_es_acq_argbest(gp_t *g, double y_std, int sense, int64_t *idx,
     int rc;
     if ((rc = check_sense(sense))) return rc;
     if ((rc = run_es_acq(g, y_std))) return rc;
-    return argbest_read(g, g->dAcq, g->M, sense, idx, val);
+    return select_best(g, g->dAcq, g->M, sense, nullptr, 0, idx, val);
 }

@@ -217,39 +217,12 @@ extern "C" int gp_predict_grad(gp_t *g, double *dmdx, double *dvdx) {
     return grads_out(g, dmdx, dvdx);
 }
 
-// the base acquisition's negated value and gradient of every resident candidate into dAcq [M] and dDacq [M, D]
-static int run_acq_grad(gp_ctx *g, const AcqSpec &a) {
-    int rc;
-    if ((rc = check_acq(g, a))) return rc;
-    if ((rc = ensure_out(g))) return rc;
-    if ((rc = run_predict_grad(g))) return rc;
-    if (!g->predicted || g->predicted_noise != 1)      // (the substitution route of a handful of rows leaves mean / variance behind)
-        if ((rc = run_predict(g, 1))) return rc;
-    launch_acq_grad(g->s, a.type, a.par, a.fmin, a.y_mean, a.y_std, g->dMean, g->dVar, g->dDm, g->dDv, g->M, g->D, g->dAcq, g->dDacq);
-    return 0;
-}
-
 // The negated acquisition of the resident candidates -- penalised when lp is given -- to out [M] and, when dout is given, its
-// x-gradient to dout [M, D], drained.  With the penaliser and a gradient: the base acquisition's value and gradient, then the log
-// transform and the penaliser as an epilogue over the same buffers (AcquisitionLP.acquisition_function_withGradients,
-// GPyOpt/GPyOpt/acquisitions/LP.py:112-140).
+// x-gradient to dout [M, D], drained (AcquisitionLP.acquisition_function_withGradients, GPyOpt/GPyOpt/acquisitions/LP.py:112-140).
 int acq_values(gp_ctx *g, const AcqSpec &a, const LpSpec *lp, double *out, double *dout) {
     int rc;
-    if (!dout) {
-        if ((rc = lp ? run_acq_lp(g, a, *lp) : run_acq(g, a))) return rc;
-    } else {
-        if (lp && (rc = check_lp(*lp))) return rc;
-        if ((rc = run_acq_grad(g, a))) return rc;
-        if (lp) {
-            LpBatch b;
-            if ((rc = upload_lp_batch(g, *lp, &b))) return rc;
-            launch_lp_grad(g->s, g->dAcq, g->dDacq, g->dXs, g->M, g->D, b.X, lp->nb, b.r, b.s, lp->transform);
-        }
-    }
-    HIPCHK(hipMemcpyAsync(out, g->dAcq, sizeof(double) * g->M, hipMemcpyDeviceToHost, g->s));
-    if (dout) HIPCHK(hipMemcpyAsync(dout, g->dDacq, sizeof(double) * g->M * g->D, hipMemcpyDeviceToHost, g->s));
-    GP_SYNC(g->s);
-    return 0;
+    if ((rc = run_acq(g, a, lp, dout != nullptr))) return rc;
+    return scores_out(g, g->dAcq, g->dDacq, g->M, g->D, out, dout);
 }
 
 extern "C" int gp_acq_grad(gp_t *g, int type, double par, double fmin, double y_mean, double y_std, double *out, double *dout) {

@@ -639,15 +639,20 @@ int check_lp(const LpSpec &lp);                     // transform 0 / 1, 0 <= nb 
 int check_sense(int sense);
 int check_k(int k);
 int check_exclude(const int64_t *exclude, int nex, int64_t M);
-int argbest_read(gp_ctx *g, const double *v, long n, int sense, int64_t *idx, double *val);   // api_predict.hip: lowest index among the best of v[0, n), drained
+// What every resident table (exact, sparse, ensemble, entropy search) scores, selects and hands over through (api_predict.hip)
+int argbest_read(gp_ctx *g, const double *v, long n, int sense, int64_t *idx, double *val);   // lowest index among the best of v[0, n), drained
+struct ScoreRows { const double *X; long M; const double *mean, *var, *dm, *dv; double *acq, *dacq; };   // M rows on the device and where their scores go
+int score_rows(gp_ctx *g, const AcqSpec &a, const LpSpec *lp, bool grad, const ScoreRows &r);   // base acquisition (+ gradient), then the penaliser; no checks, no posterior
+int select_best(gp_ctx *g, double *scores, long M, int sense, const int64_t *exclude, int nex, int64_t *idx, double *val);   // masks exclude [nex], then argbest_read
+int select_topk(gp_ctx *g, double *scores, long M, int sense, int k, int64_t *idx, double *val);   // k rounds of arg-best + mask; the tail past M is -1 / acq_empty
+int scores_out(gp_ctx *g, const double *acq, const double *dacq, long M, int D, double *out, double *dout);   // the drained copies (null: skipped)
 static inline double acq_empty(int sense) { return sense > 0 ? -INFINITY : INFINITY; }   // the value no candidate loses to
 struct LpBatch { double *X = nullptr, *r = nullptr, *s = nullptr; };   // the batch on the device
 static inline LpBatch lp_slots(const gp_ctx *g) { return LpBatch{g->dLp + LP_X.off, g->dLp + LP_R.off, g->dLp + LP_S.off}; }
 RowsAcq rows_acq(const AcqSpec &a, const LpSpec *lp, const LpBatch &b);   // the fused path's kernel argument (lp null: base only)
-int run_acq(gp_ctx *g, const AcqSpec &a);
+int run_acq(gp_ctx *g, const AcqSpec &a, const LpSpec *lp, bool grad);   // the exact table's scores into dAcq (dDacq with grad), checks and posterior included
 int upload_lp_batch(gp_ctx *g, const LpSpec &lp, LpBatch *b);
 int rows_lp_batch(gp_ctx *g, const LpSpec &lp, LpBatch *b);   // api_rows.hip: the same, skipped while dLp still holds this batch
-int run_acq_lp(gp_ctx *g, const AcqSpec &a, const LpSpec &lp);
 int acq_values(gp_ctx *g, const AcqSpec &a, const LpSpec *lp, double *out, double *dout);   // api_grad.hip
 // gp_acq_argbest / gp_acq_lp_argbest and gp_acq_topk over the specs, preamble included (lp null: no penaliser)
 int acq_argbest(gp_ctx *g, const AcqSpec &a, const LpSpec *lp, int sense, const int64_t *exclude, int nex, int64_t *idx, double *val);

@@ -146,12 +146,12 @@ int check_exclude(const int64_t *exclude, int nex, int64_t M) {   // rows alread
     return 0;
 }
 
-// ---- arg-best: the two-level reduction into RED_RESULT, and its read-back ----------------------------------------------------
+// ---- what every resident table shares (exact, sparse, ensemble, entropy search): scoring, selecting, handing over ------------
+// arg-best: the two-level reduction into RED_RESULT
 static void argbest_launch(gp_ctx *g, const double *v, long n, int sense) {
     launch_argbest(g->s, v, n, sense, g->dRedV + RED_RESULT.off, g->dRedI + RED_RESULT.off, g->dRedV + RED_PARTIAL.off,
                    g->dRedI + RED_PARTIAL.off);
 }
-static void mask_rows(gp_ctx *g, const long long *rows, int n, int sense) { launch_mask(g->s, g->dAcq, rows, n, acq_empty(sense)); }
 // lowest index among the best of v[0, n), drained (idx may be null: the value alone)
 int argbest_read(gp_ctx *g, const double *v, long n, int sense, int64_t *idx, double *val) {
     argbest_launch(g, v, n, sense);
@@ -162,6 +162,70 @@ int argbest_read(gp_ctx *g, const double *v, long n, int sense, int64_t *idx, do
     GP_SYNC(g->s);
     *val = hv;
     if (idx) *idx = (int64_t)hi;
+    return 0;
+}
+
+// The base acquisition of r's rows from their posterior -- value and x-gradient with grad --, then the log transform and the
+// penaliser over the same buffers when lp is given (AcquisitionLP, GPyOpt/GPyOpt/acquisitions/LP.py:105-140).  No checks, no
+// posterior: each model's preamble and its route to one come first.  Not drained.
+int score_rows(gp_ctx *g, const AcqSpec &a, const LpSpec *lp, bool grad, const ScoreRows &r) {
+    if (grad)
+        launch_acq_grad(g->s, a.type, a.par, a.fmin, a.y_mean, a.y_std, r.mean, r.var, r.dm, r.dv, r.M, g->D, r.acq, r.dacq);
+    else
+        launch_acq(g->s, a.type, a.par, a.fmin, a.y_mean, a.y_std, r.mean, r.var, r.M, r.acq);
+    if (!lp) return 0;
+    int rc;
+    LpBatch b;
+    if ((rc = upload_lp_batch(g, *lp, &b))) return rc;   // (shared scratch: the upload resets the rows entries' batch cache)
+    if (grad)
+        launch_lp_grad(g->s, r.acq, r.dacq, r.X, r.M, g->D, b.X, lp->nb, b.r, b.s, lp->transform);
+    else
+        launch_lp(g->s, r.acq, r.X, r.M, g->D, b.X, lp->nb, b.r, b.s, lp->transform, r.acq);
+    return 0;
+}
+
+// The winner among scores[0, M), the rows of exclude [nex] out of the running (run.py:1249-1252 masks the rows already taken)
+int select_best(gp_ctx *g, double *scores, long M, int sense, const int64_t *exclude, int nex, int64_t *idx, double *val) {
+    if (nex > 0) {
+        long long *rows = g->dRedI + REDI_EXCLUDE.off;
+        HIPCHK(hipMemcpyAsync(rows, exclude, sizeof(long long) * nex, hipMemcpyHostToDevice, g->s));
+        launch_mask(g->s, scores, rows, nex, acq_empty(sense));
+    }
+    return argbest_read(g, scores, M, sense, idx, val);
+}
+
+// top-k of scores[0, M) (anchor_points_generator.py:61: argsort(scores)[:num_anchor]): k rounds of the deterministic arg-best
+// reduction, each followed by masking the winner on the device: ties resolve to the lowest index in every round, i.e. the order
+// of a stable sort by (score, index).
+int select_topk(gp_ctx *g, double *scores, long M, int sense, int k, int64_t *idx, double *val) {
+    int rc;
+    if ((rc = g->dComm.reserve(COMM_CAP))) return rc;
+    double *dv = g->dComm + COMM_TOPK_VAL.off;
+    long long *di = (long long *)(g->dComm + COMM_TOPK_ROW.off);
+    const int kk = (int)std::min<long>(k, M);
+    for (int j = 0; j < kk; ++j) {
+        argbest_launch(g, scores, M, sense);
+        HIPCHK(hipMemcpyAsync(dv + j, g->dRedV + RED_RESULT.off, 8, hipMemcpyDeviceToDevice, g->s));
+        HIPCHK(hipMemcpyAsync(di + j, g->dRedI + RED_RESULT.off, 8, hipMemcpyDeviceToDevice, g->s));
+        launch_mask(g->s, scores, g->dRedI + RED_RESULT.off, 1, acq_empty(sense));
+    }
+    std::vector<long long> hi(kk);
+    HIPCHK(hipMemcpyAsync(val, dv, sizeof(double) * kk, hipMemcpyDeviceToHost, g->s));
+    HIPCHK(hipMemcpyAsync(hi.data(), di, sizeof(long long) * kk, hipMemcpyDeviceToHost, g->s));
+    GP_SYNC(g->s);
+    for (int j = 0; j < kk; ++j) idx[j] = (int64_t)hi[j];
+    for (int j = kk; j < k; ++j) {  // fewer candidates than k: the tail is marked empty
+        idx[j] = -1;
+        val[j] = acq_empty(sense);
+    }
+    return 0;
+}
+
+// scores [M] (and their x-gradients [M, D]) to the caller, drained; a null destination is skipped
+int scores_out(gp_ctx *g, const double *acq, const double *dacq, long M, int D, double *out, double *dout) {
+    if (out) HIPCHK(hipMemcpyAsync(out, acq, sizeof(double) * M, hipMemcpyDeviceToHost, g->s));
+    if (dout) HIPCHK(hipMemcpyAsync(dout, dacq, sizeof(double) * M * D, hipMemcpyDeviceToHost, g->s));
+    GP_SYNC(g->s);
     return 0;
 }
 
@@ -182,14 +246,18 @@ extern "C" int gp_fmin(gp_t *g, double *fmin) {
     return 0;
 }
 
-int run_acq(gp_ctx *g, const AcqSpec &a) {
+// The exact table's scores into dAcq (and dDacq with grad), not drained: the checks, the posterior with noise (GPModel.predict:
+// with_noise=True, gpmodel.py:102) -- with grad the predictive gradients first, whose substitution route of a handful of rows
+// leaves mean / variance behind --, then score_rows
+int run_acq(gp_ctx *g, const AcqSpec &a, const LpSpec *lp, bool grad) {
     int rc;
+    if (lp && (rc = check_lp(*lp))) return rc;
     if ((rc = check_acq(g, a))) return rc;
     if ((rc = ensure_out(g))) return rc;
+    if (grad && (rc = run_predict_grad(g))) return rc;
     if (!g->predicted || g->predicted_noise != 1)
-        if ((rc = run_predict(g, 1))) return rc;  // GPModel.predict: with_noise=True (gpmodel.py:102)
-    launch_acq(g->s, a.type, a.par, a.fmin, a.y_mean, a.y_std, g->dMean, g->dVar, g->M, g->dAcq);
-    return 0;
+        if ((rc = run_predict(g, 1))) return rc;
+    return score_rows(g, a, lp, grad, ScoreRows{g->dXs, g->M, g->dMean, g->dVar, g->dDm, g->dDv, g->dAcq, g->dDacq});
 }
 
 extern "C" int gp_acq(gp_t *g, int type, double par, double fmin, double y_mean, double y_std, double *out) {
@@ -206,13 +274,8 @@ int acq_argbest(gp_ctx *g, const AcqSpec &a, const LpSpec *lp, int sense, const 
     int rc;
     if ((rc = check_sense(sense))) return rc;
     if ((rc = check_exclude(exclude, nex, g->M))) return rc;
-    if ((rc = lp ? run_acq_lp(g, a, *lp) : run_acq(g, a))) return rc;
-    if (nex > 0) {
-        long long *rows = g->dRedI + REDI_EXCLUDE.off;
-        HIPCHK(hipMemcpyAsync(rows, exclude, sizeof(long long) * nex, hipMemcpyHostToDevice, g->s));
-        mask_rows(g, rows, nex, sense);
-    }
-    return argbest_read(g, g->dAcq, g->M, sense, idx, val);
+    if ((rc = run_acq(g, a, lp, false))) return rc;
+    return select_best(g, g->dAcq, g->M, sense, exclude, nex, idx, val);
 }
 
 extern "C" int gp_acq_argbest(gp_t *g, int type, double par, double fmin, double y_mean, double y_std, int sense, int64_t *idx,
@@ -232,16 +295,6 @@ int upload_lp_batch(gp_ctx *g, const LpSpec &lp, LpBatch *b) {
         HIPCHK(hipMemcpyAsync(b->r, lp.r0, sizeof(double) * lp.nb, hipMemcpyHostToDevice, g->s));
         HIPCHK(hipMemcpyAsync(b->s, lp.s0, sizeof(double) * lp.nb, hipMemcpyHostToDevice, g->s));
     }
-    return 0;
-}
-
-int run_acq_lp(gp_ctx *g, const AcqSpec &a, const LpSpec &lp) {
-    int rc;
-    if ((rc = check_lp(lp))) return rc;
-    if ((rc = run_acq(g, a))) return rc;
-    LpBatch b;
-    if ((rc = upload_lp_batch(g, lp, &b))) return rc;
-    launch_lp(g->s, g->dAcq, g->dXs, g->M, g->D, b.X, lp.nb, b.r, b.s, lp.transform, g->dAcq);
     return 0;
 }
 
@@ -281,36 +334,15 @@ extern "C" int gp_predict_full_cov(gp_t *g, int include_noise, double *mean, dou
     return 0;
 }
 
-// ---- top-k of the acquisition scores (anchor_points_generator.py:61: argsort(scores)[:num_anchor]) ---------------
-// k rounds of the deterministic arg-best reduction, each followed by masking the winner on the device: ties resolve
-// to the lowest index in every round, i.e. the order of a stable sort by (score, index).
+// ---- top-k of the acquisition scores --------------------------------------------------------------------------------
 int acq_topk(gp_ctx *g, const AcqSpec &a, int sense, int k, int64_t *idx, double *val) {
     if (!g || !idx || !val) return fail(GP_ERR_ARG, "null argument");
     GP_SCORING(g);
     int rc;
     if ((rc = check_sense(sense))) return rc;
     if ((rc = check_k(k))) return rc;
-    if ((rc = run_acq(g, a))) return rc;
-    if ((rc = g->dComm.reserve(COMM_CAP))) return rc;
-    double *dv = g->dComm + COMM_TOPK_VAL.off;
-    long long *di = (long long *)(g->dComm + COMM_TOPK_ROW.off);
-    const int kk = (int)std::min<long>(k, g->M);
-    for (int j = 0; j < kk; ++j) {
-        argbest_launch(g, g->dAcq, g->M, sense);
-        HIPCHK(hipMemcpyAsync(dv + j, g->dRedV + RED_RESULT.off, 8, hipMemcpyDeviceToDevice, g->s));
-        HIPCHK(hipMemcpyAsync(di + j, g->dRedI + RED_RESULT.off, 8, hipMemcpyDeviceToDevice, g->s));
-        mask_rows(g, g->dRedI + RED_RESULT.off, 1, sense);
-    }
-    std::vector<long long> hi(kk);
-    HIPCHK(hipMemcpyAsync(val, dv, sizeof(double) * kk, hipMemcpyDeviceToHost, g->s));
-    HIPCHK(hipMemcpyAsync(hi.data(), di, sizeof(long long) * kk, hipMemcpyDeviceToHost, g->s));
-    GP_SYNC(g->s);
-    for (int j = 0; j < kk; ++j) idx[j] = (int64_t)hi[j];
-    for (int j = kk; j < k; ++j) {  // fewer candidates than k: the tail is marked empty
-        idx[j] = -1;
-        val[j] = acq_empty(sense);
-    }
-    return 0;
+    if ((rc = run_acq(g, a, nullptr, false))) return rc;
+    return select_topk(g, g->dAcq, g->M, sense, k, idx, val);
 }
 
 extern "C" int gp_acq_topk(gp_t *g, int type, double par, double fmin, double y_mean, double y_std, int sense, int k,

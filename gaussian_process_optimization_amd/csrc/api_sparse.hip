@@ -429,24 +429,8 @@ static int sparse_table_posterior(gp_ctx *g, bool grads) {
 // scores of `M` rows at dX from their posterior at post (layout of sp.dTabPost) into acq [M] (and dacq [M, D] with grad)
 static int sparse_scores(gp_ctx *g, const AcqSpec &a, const LpSpec *lp, bool grad, const double *dX, long M, const double *post,
                          double *acq, double *dacq) {
-    const int D = g->D;
-    const double *dmean = post, *dvar = dmean + M, *ddm = dvar + M, *ddv = ddm + M * D;
-    int rc;
-    LpBatch b;
-    if (!grad) {
-        launch_acq(g->s, a.type, a.par, a.fmin, a.y_mean, a.y_std, dmean, dvar, M, acq);
-        if (lp) {
-            if ((rc = upload_lp_batch(g, *lp, &b))) return rc;   // (shared scratch: the upload resets the rows entries' batch cache)
-            launch_lp(g->s, acq, dX, M, D, b.X, lp->nb, b.r, b.s, lp->transform, acq);
-        }
-    } else {
-        launch_acq_grad(g->s, a.type, a.par, a.fmin, a.y_mean, a.y_std, dmean, dvar, ddm, ddv, M, D, acq, dacq);
-        if (lp) {
-            if ((rc = upload_lp_batch(g, *lp, &b))) return rc;
-            launch_lp_grad(g->s, acq, dacq, dX, M, D, b.X, lp->nb, b.r, b.s, lp->transform);
-        }
-    }
-    return 0;
+    const double *dmean = post, *dvar = dmean + M, *ddm = dvar + M, *ddv = ddm + M * g->D;
+    return score_rows(g, a, lp, grad, ScoreRows{dX, M, dmean, dvar, ddm, ddv, acq, dacq});
 }
 
 static int sparse_table_scores(gp_ctx *g, const AcqSpec &a, const LpSpec *lp, bool grad) {
@@ -466,16 +450,7 @@ extern "C" int gp_sparse_acq(gp_t *g, int type, double par, double fmin, double 
     int rc;
     if ((rc = sparse_scoring(g, a, pen))) return rc;
     if ((rc = sparse_table_scores(g, a, pen, dout != nullptr))) return rc;
-    SparseState &sp = g->sp;
-    HIPCHK(hipMemcpyAsync(out, sp.dTabAcq, sizeof(double) * sp.tM, hipMemcpyDeviceToHost, g->s));
-    if (dout) HIPCHK(hipMemcpyAsync(dout, sp.dTabDacq, sizeof(double) * sp.tM * g->D, hipMemcpyDeviceToHost, g->s));
-    GP_SYNC(g->s);
-    return 0;
-}
-
-static void sparse_argbest_launch(gp_ctx *g, int sense) {
-    launch_argbest(g->s, g->sp.dTabAcq, g->sp.tM, sense, g->dRedV + RED_RESULT.off, g->dRedI + RED_RESULT.off,
-                   g->dRedV + RED_PARTIAL.off, g->dRedI + RED_PARTIAL.off);
+    return scores_out(g, g->sp.dTabAcq, g->sp.dTabDacq, g->sp.tM, g->D, out, dout);
 }
 
 extern "C" int gp_sparse_acq_argbest(gp_t *g, int type, double par, double fmin, double y_mean, double y_std, int lp, int transform,
@@ -489,23 +464,9 @@ extern "C" int gp_sparse_acq_argbest(gp_t *g, int type, double par, double fmin,
     if ((rc = check_sense(sense))) return rc;
     if ((rc = check_exclude(exclude, nex, g->sp.tM))) return rc;
     if ((rc = sparse_table_scores(g, a, pen, false))) return rc;
-    if (nex > 0) {   // rows already taken (run.py:1249-1252 masks them)
-        long long *rows = g->dRedI + REDI_EXCLUDE.off;
-        HIPCHK(hipMemcpyAsync(rows, exclude, sizeof(long long) * nex, hipMemcpyHostToDevice, g->s));
-        launch_mask(g->s, g->sp.dTabAcq, rows, nex, acq_empty(sense));
-    }
-    sparse_argbest_launch(g, sense);
-    double hv = 0.0;
-    long long hi = 0;
-    HIPCHK(hipMemcpyAsync(&hv, g->dRedV + RED_RESULT.off, sizeof(double), hipMemcpyDeviceToHost, g->s));
-    HIPCHK(hipMemcpyAsync(&hi, g->dRedI + RED_RESULT.off, sizeof(long long), hipMemcpyDeviceToHost, g->s));
-    GP_SYNC(g->s);
-    *val = hv;
-    *idx = (int64_t)hi;
-    return 0;
+    return select_best(g, g->sp.dTabAcq, g->sp.tM, sense, exclude, nex, idx, val);
 }
 
-// k rounds of the deterministic arg-best reduction, each followed by masking the winner (acq_topk of the exact model)
 extern "C" int gp_sparse_acq_topk(gp_t *g, int type, double par, double fmin, double y_mean, double y_std, int sense, int k,
                                   int64_t *idx, double *val) {
     if (!g || !idx || !val) return fail(GP_ERR_ARG, "null argument");
@@ -515,26 +476,7 @@ extern "C" int gp_sparse_acq_topk(gp_t *g, int type, double par, double fmin, do
     if ((rc = check_sense(sense))) return rc;
     if ((rc = check_k(k))) return rc;
     if ((rc = sparse_table_scores(g, a, nullptr, false))) return rc;
-    if ((rc = g->dComm.reserve(COMM_CAP))) return rc;
-    double *dv = g->dComm + COMM_TOPK_VAL.off;
-    long long *di = (long long *)(g->dComm + COMM_TOPK_ROW.off);
-    const int kk = (int)std::min<long>(k, g->sp.tM);
-    for (int j = 0; j < kk; ++j) {
-        sparse_argbest_launch(g, sense);
-        HIPCHK(hipMemcpyAsync(dv + j, g->dRedV + RED_RESULT.off, 8, hipMemcpyDeviceToDevice, g->s));
-        HIPCHK(hipMemcpyAsync(di + j, g->dRedI + RED_RESULT.off, 8, hipMemcpyDeviceToDevice, g->s));
-        launch_mask(g->s, g->sp.dTabAcq, g->dRedI + RED_RESULT.off, 1, acq_empty(sense));
-    }
-    std::vector<long long> hi(kk);
-    HIPCHK(hipMemcpyAsync(val, dv, sizeof(double) * kk, hipMemcpyDeviceToHost, g->s));
-    HIPCHK(hipMemcpyAsync(hi.data(), di, sizeof(long long) * kk, hipMemcpyDeviceToHost, g->s));
-    GP_SYNC(g->s);
-    for (int j = 0; j < kk; ++j) idx[j] = (int64_t)hi[j];
-    for (int j = kk; j < k; ++j) {  // fewer candidates than k: the tail is marked empty
-        idx[j] = -1;
-        val[j] = acq_empty(sense);
-    }
-    return 0;
+    return select_topk(g, g->sp.dTabAcq, g->sp.tM, sense, k, idx, val);
 }
 
 // ---- a handful of locations per call (csrc/sparse_rows.hip) -------------------------------------------------------------------------
@@ -597,10 +539,7 @@ static int sparse_rows_fallback(gp_ctx *g, const double *Xs, long M, int include
     if (var) HIPCHK(hipMemcpyAsync(var, dvar, sizeof(double) * M, hipMemcpyDeviceToHost, s));
     if (dmdx) HIPCHK(hipMemcpyAsync(dmdx, ddm, sizeof(double) * M * D, hipMemcpyDeviceToHost, s));
     if (dvdx) HIPCHK(hipMemcpyAsync(dvdx, ddv, sizeof(double) * M * D, hipMemcpyDeviceToHost, s));
-    if (acq) HIPCHK(hipMemcpyAsync(acq, sp.dScrAcq, sizeof(double) * M, hipMemcpyDeviceToHost, s));
-    if (dacq) HIPCHK(hipMemcpyAsync(dacq, dacq_d, sizeof(double) * M * D, hipMemcpyDeviceToHost, s));
-    GP_SYNC(s);
-    return 0;
+    return scores_out(g, sp.dScrAcq, dacq_d, M, g->D, acq, dacq);
 }
 
 extern "C" int gp_sparse_predict_rows(gp_t *g, const double *Xs, int64_t M, int include_noise, double *mean, double *var, double *dmdx,

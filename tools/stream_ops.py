@@ -2,7 +2,8 @@
 every strand of the factorisation scheduler (1 ... 9) and the scoring entry points (s1 ... s8), each call made twice (the first
 allocates, the second is the steady state).  Run it under rocprofv3 --kernel-trace / --hip-trace on a GPU, or against a library
 linked with tools/hip_recorder.cpp anywhere.  The scoring cases save every array and scalar they got back when given a path.
-usage: stream_ops.py <case: 1 2 3 4a 4b 5 6a 6b 7 8 9 s1 s2 s3 s4a s4b s5 s6 s7 s8> [results.npz]"""
+s9 ... s12 are the table entries of the sparse model, the ensemble and entropy search, and all four tables interleaved.
+usage: stream_ops.py <case: 1 2 3 4a 4b 5 6a 6b 7 8 9 s1 s2 s3 s4a s4b s5 s6 s7 s8 s9 s10 s11 s12> [results.npz]"""
 import sys
 import numpy as np
 from gaussian_process_optimization_amd import _lib
@@ -128,6 +129,59 @@ elif case.startswith("s"):
                     keep("predict_rows%d%d" % (M, grad), lambda: h.predict_rows(Xs[:M], True, grad))
                     keep("ens_predict_rows%d%d" % (M, grad), lambda: h.ens_predict_rows(Xs[:M], True, grad))
                     keep("sparse_predict_rows%d%d" % (M, grad), lambda: h.sparse_predict_rows(Xs[:M], True, grad))
+    elif case in ("s9", "s10", "s11", "s12"):   # the candidate tables of the sparse model (s9), the ensemble (s10), ES (s11), all four (s12)
+        setup(300, 1001); Xs = problem(300, 1001)[2]; ex = range(0, 512, 2)
+        def sparse_fit():
+            h.sparse_set_inducing(problem(40, seed=3)[0]); h.sparse_fit(); return h.sparse_fmin()
+        def ens_fit(S=3):
+            h.ens_fit(np.linspace(1.0, 1.4, S), np.linspace(0.4, 0.6, S)[:, None], np.linspace(1e-2, 2e-2, S))
+        def es_belief(R=6, S=4):   # from host arrays: the EP sites come from a kernel, which a recorder does not run
+            h.es_set_representers(rng.uniform(0, 1, (R, D)))
+            h.es_set_belief(np.log(np.full(R, 1.0 / R)), np.zeros(R), rng.standard_normal((R, R)), rng.standard_normal((R, R, R)), np.linspace(-1, 1, S))
+        def sparse_table(fmin, M, tag=""):
+            twice(lambda: h.sparse_set_candidates(Xs[:M]))
+            for grad in (False, True):
+                for lp in (None, (1, Xb, r0, s0)):
+                    keep("sparse_acq%d%s%s" % (grad, lp and lp[0], tag), lambda: h.sparse_acq(EI, 0.01, fmin, grad=grad, lp=lp))
+            keep("sparse_acq_argbest" + tag, lambda: h.sparse_acq_argbest(EI, 0.01, fmin, -1, lp=(1, Xb, r0, s0), exclude=[e for e in ex if e < M]))
+            keep("sparse_acq_topk" + tag, lambda: h.sparse_acq_topk(LCB, 2.0, fmin, +1, 5))
+        def ens_table(tag=""):
+            keep("ens_acq" + tag, lambda: h.ens_acq(EI, 0.01))
+            for sense in (-1, +1): keep("ens_acq_argbest%d%s" % (sense, tag), lambda: h.ens_acq_argbest(LCB, 2.0, sense))
+        def es_table(tag=""):
+            keep("es_acq" + tag, lambda: h.es_acq(1.0))
+            for sense in (-1, +1): keep("es_acq_argbest%d%s" % (sense, tag), lambda: h.es_acq_argbest(sense, 1.0))
+        if case == "s9":
+            fmin = sparse_fit()
+            for M in (1001, 3): sparse_table(fmin, M, "/%d" % M)
+            for grad in (False, True):   # M = 9: the fallback of the rows entry, over scratch
+                for lp in (None, (1, Xb, r0, s0)):
+                    keep("sparse_acq_rows9%d%s" % (grad, lp and lp[0]), lambda: h.sparse_acq_rows(Xs[:9], EI, 0.01, fmin, grad=grad, lp=lp))
+        elif case == "s10":
+            ens_fit()
+            for M in (1001, 3): twice(lambda: h.set_candidates(Xs[:M])); ens_table("/%d" % M)
+        elif case == "s11":
+            h.fit(); es_belief()
+            for M in (1001, 3): twice(lambda: h.set_candidates(Xs[:M])); es_table("/%d" % M)
+        else:   # gp_es_* refuses a context that holds a sparse fit or an ensemble: ES beside the exact table, then the other two, then ES again
+            def exact(tag, M):
+                keep("acq_lp_argbest" + tag, lambda: h.acq_lp_argbest(EI, 0.01, fmin, 1, -1, Xb, r0, s0, exclude=[e for e in ex if e < M]))
+                yield
+                keep("acq_rows" + tag, lambda: h.acq_rows(Xs[:3], EI, 0.01, fmin, grad=True, lp=(1, Xb, r0, s0)))
+                keep("acq_topk" + tag, lambda: h.acq_topk(LCB, 2.0, fmin, +1, 5))
+                yield
+                keep("acq_lp_grad" + tag, lambda: h.acq_lp_grad(EI, 0.01, fmin, 1, Xb, r0, s0))
+                yield
+            for M in (1001, 3):
+                X, Y, _ = problem(300); h.set_data(X, Y); h.set_params(0, 0, 1.2, [0.5], 1e-2); h.set_candidates(Xs[:M])
+                h.fit(); fmin = h.fmin(); es_belief()
+                for n, _ in enumerate(exact("/%d.es" % M, M)): es_table("/%d.%d" % (M, n))
+                smin = sparse_fit(); ens_fit()
+                for n, _ in enumerate(exact("/%d" % M, M)):
+                    if n == 0: sparse_table(smin, M, "/%d" % M)
+                    if n == 1: keep("sparse_acq_rows/%d" % M, lambda: h.sparse_acq_rows(Xs[:9], EI, 0.01, smin, grad=True, lp=(0, Xb, r0, s0)))
+                    if n == 2: keep("sparse_acq_topk2/%d" % M, lambda: h.sparse_acq_topk(EI, 0.01, smin, -1, 5))
+                    ens_table("/%d.%d" % (M, n))
     else:
         raise SystemExit("unknown case")
     print(case, {k: float(np.sum(v)) for k, v in got.items()})
