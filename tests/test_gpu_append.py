@@ -14,7 +14,8 @@ The non-positive pivot: an input whose border pivot is <= 0 in fp64 reproducibly
 diagonal always gets, coincident rows at noise 0 leave a pivot of +1e-8 .. 2e-8 whose sign is decided by rounding of order
 cond eps ~ 1e-8 -- so that case is left out.  The positive return, the untouched context (the split's undo included) and the model's
 fall-back to the refit are exercised with a border that is not FINITE instead (a NaN coordinate), which the entry point reports
-the same way.
+the same way.  (With a slightly NEGATIVE noise the pivot of a repeated row is -2 delta, away from rounding: that finite border, and
+appends to a fit that needed jitter, are in tests/test_gpu_jitter_routes.py.)
 """
 import json
 import os

@@ -1,5 +1,6 @@
 """GPU: gp_fit_grad_batch -- R members against gp_fit_grad one at a time, against the oracle, per-member jitter, the Gower
 set-up, the untouched resident fit, the size limits, and optimize_restarts(parallel=True) against the serial restarts."""
+import ctypes
 import json
 import os
 
@@ -137,6 +138,48 @@ def test_jitter_per_member(h):
             h.set_params(0, False, var[r], ls[r], noise[r])
             with pytest.raises(np.linalg.LinAlgError):
                 h.fit_grad(1, 0)
+            assert np.isnan(res0[0][0][r])
+        else:
+            assert np.array_equal(_batch_rows(res0, r), _batch_rows(res, r))
+
+
+def test_jitter_per_member_later_tile(h):
+    """The same over three tiles (tests/_jitter_cases.py: N = 300, rows 260 .. 299 repeat rows 0 .. 39): the members of
+    test_jitter_per_member, whose hard ones give way in the first tile and carry what is left through two more, and two members
+    whose first non-positive pivot lies among the repeated rows -- in the third tile of potrf_tile_batch_kernel, with a
+    per-member info.  tests/test_jitter_cases_host.py checks on the CPU that the hard members fail un-jittered, and where."""
+    import _jitter_cases as J
+    X, Y = J.batch_problem()
+    h.set_data(X, Y)
+    var, ls, noise = J.BATCH_VAR, J.BATCH_LS, J.BATCH_NOISE
+    R = var.size
+    h.set_params(0, False, var[0], ls[0], noise[0])
+    res = h.fit_grad_batch(var, ls, noise)
+    jit = res[0][2]
+    for r in range(R):
+        ref = _single(h, 0, False, var[r], ls[r], noise[r])
+        assert ref is not None and res[2][r] == 0
+        assert jit[r] == ref[2]
+        assert np.array_equal(_batch_rows(res, r), ref), (r, _batch_rows(res, r), ref)   # Npad = 384 <= 768: the same bits
+        if noise[r] > 1e-6:
+            assert jit[r] == 0.0
+    assert np.all(jit[noise < 1e-6] > 0) and np.all(jit[noise > 1e-6] == 0)
+    for r in J.BATCH_THIRD_TILE:          # the first rung, nine orders above the rounding that decided the failure
+        assert jit[r] == pytest.approx((var[r] + (noise[r] + 1e-8)) * 1e-6, rel=1e-12)
+    # with no retries allowed, exactly the members that needed jitter fail -- alone, with gp_fit_grad's code
+    res0 = h.fit_grad_batch(var, ls, noise, maxtries=0)
+    st = res0[2]
+    assert np.array_equal(st != 0, jit > 0)
+    for r in range(R):
+        if st[r]:
+            h.set_params(0, False, var[r], ls[r], noise[r])
+            lml, logdet, jt = _lib._fit_scalars()
+            dv, dn, dl = ctypes.c_double(), ctypes.c_double(), np.empty(1)
+            rc = h.lib.gp_fit_grad(h.h, 0, ctypes.byref(lml), ctypes.byref(logdet), ctypes.byref(jt), ctypes.byref(dv),
+                                   _lib.dptr(dl), ctypes.byref(dn))
+            assert rc == st[r] and 0 < rc <= J.BATCH_N, (r, rc, st[r])
+            if r in J.BATCH_THIRD_TILE:
+                assert rc > J.BATCH_N - J.BATCH_DUP > 2 * J.TILE
             assert np.isnan(res0[0][0][r])
         else:
             assert np.array_equal(_batch_rows(res0, r), _batch_rows(res, r))
