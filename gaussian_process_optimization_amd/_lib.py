@@ -33,6 +33,7 @@ SIGNATURES = [
     ("gp_shutdown", ctypes.c_int, []),
     ("gp_get_fit_state", ctypes.c_int, [_vp, c_double_p, c_double_p, c_double_p]),
     ("gp_get_dl_dk", ctypes.c_int, [_vp, c_double_p]),
+    ("gp_lml_grad_lds", ctypes.c_int, [_vp, c_int64_p, c_int64_p]),
     ("gp_posterior_samples", ctypes.c_int, [_vp, ctypes.c_int, c_double_p, ctypes.c_int, ctypes.c_int, c_double_p,
                                             c_double_p, c_double_p]),
     ("gp_acq_topk", ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double,
@@ -405,6 +406,13 @@ class Handle(object):
                                   ctypes.byref(dv), dptr(dl), ctypes.byref(dn))
         check(self.lib, rc, "gp_fit_grad")
         return (lml.value, logdet.value, jit.value), (dv.value, dl, dn.value)
+
+    def lml_grad_lds(self):
+        """(bytes of LDS a workgroup of the gradient pass needs for this data and Gower setting, bytes the device gives one): the
+        gradient entries raise ValueError while the first exceeds the second."""
+        need, avail = ctypes.c_int64(), ctypes.c_int64()
+        check(self.lib, self.lib.gp_lml_grad_lds(self.h, ctypes.byref(need), ctypes.byref(avail)), "gp_lml_grad_lds")
+        return need.value, avail.value
 
     def lml_grad_x(self):
         """dL/dX [N, D] of the training inputs at the current fit (gp_lml_grad_x)."""

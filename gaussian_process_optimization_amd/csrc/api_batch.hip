@@ -50,6 +50,9 @@ static int fit_grad_members(gp_ctx *g, const char *who, int R, const double *var
                     bx ? "gp_fit_grad_x" : (bw ? "gp_fit_grad_warp" : "gp_fit_grad"));
     if (g->P > GP_GRAD_MAX_P) return fail(GP_ERR_ARG, "%s supports P <= %d", who, GP_GRAD_MAX_P);
     if (bx && g->kp.gower) return fail(GP_ERR_ARG, "%s: not defined for a Gower model", who);   // (as gp_lml_grad_x)
+    if (int e = lml_grad_lds_check(g, who)) return e;   // D and P jointly, against the LDS of a workgroup (api_internal.h)
+    if (bx)
+        if (int e = gradx_lds_check(g, who)) return e;
     if (bw && g->P != 1) return fail(GP_ERR_ARG, "%s: an output warp takes P = 1 (the data has P = %d)", who, g->P);
     if (bw && (bw->n_terms < 1 || bw->n_terms > GP_WARP_MAX_TERMS))
         return fail(GP_ERR_ARG, "%s takes a warp of 1..%d terms", who, GP_WARP_MAX_TERMS);

@@ -326,8 +326,11 @@ extern "C" int gp_create(gp_t **out, int device) {
     HIPCHK(hipGetDeviceCount(&n));
     if (device < 0 || device >= n) return fail(GP_ERR_ARG, "device %d out of range (%d visible)", device, n);
     HIPCHK(hipSetDevice(device));
+    int lds = 0;   // what the gradient entries hold their staging against (lml_grad_lds_check)
+    HIPCHK(hipDeviceGetAttribute(&lds, hipDeviceAttributeMaxSharedMemoryPerBlock, device));
     gp_ctx *g = new gp_ctx();
     g->device = device;
+    g->lds_per_wg = lds;
     for (int i = 0; i < MAX_PHASES; ++i) g->phases[i].used = false;
     {
         DevStreams d;

@@ -2,6 +2,28 @@
 // Reference: Stationary.update_gradients_full (stationary.py:218-238), GP.predictive_gradients (gp.py:407-454).
 #include "api_internal.h"
 
+int lml_grad_lds_check(const gp_ctx *g, const char *who) {
+    const size_t need = lml_grad_lds_bytes(g->D, g->kp.gower, g->P);
+    if (need <= (size_t)g->lds_per_wg) return 0;
+    return fail(GP_ERR_ARG, "%s: D = %d, P = %d, Gower %s need %zu bytes of LDS per workgroup in the gradient pass, the device has %ld",
+                who, g->D, g->P, g->kp.gower ? "on" : "off", need, g->lds_per_wg);
+}
+int gradx_lds_check(const gp_ctx *g, const char *who) {
+    const size_t need = gradx_lds_bytes(g->D, g->P);
+    if (need <= (size_t)g->lds_per_wg) return 0;
+    return fail(GP_ERR_ARG, "%s: D = %d, P = %d need %zu bytes of LDS per workgroup in the input-gradient pass, the device has %ld", who,
+                g->D, g->P, need, g->lds_per_wg);
+}
+
+extern "C" int gp_lml_grad_lds(gp_t *g, int64_t *need, int64_t *available) {
+    if (!g || !need || !available) return fail(GP_ERR_ARG, "null argument");
+    GP_DEAD_CHECK(g);
+    if (!g->have_data) return fail(GP_ERR_STATE, "gp_set_data first");
+    *need = (int64_t)lml_grad_lds_bytes(g->D, g->kp.gower, g->P);
+    *available = g->lds_per_wg;
+    return 0;
+}
+
 // the fused dL_dK reduction for m's members: one pass per GP_GRAD_CH dimensions, its GP_GRAD_NACC sums side by side in SCAL_GRAD
 void lml_grad_passes(gp_ctx *g, const Members &m) {
     int pass = 0;
@@ -42,9 +64,11 @@ int lml_grad_impl(gp_ctx *g, double *dvariance, double *dlengthscale, double *dn
     GP_FITTED(g);
     if (g->P > GP_GRAD_MAX_P) return fail(GP_ERR_ARG, "gp_lml_grad supports P <= %d", GP_GRAD_MAX_P);
     if (dL_dX && g->kp.gower) return fail(GP_ERR_ARG, "gp_lml_grad_x: not defined for a Gower model");
+    int rc;
+    if ((rc = lml_grad_lds_check(g, dL_dX ? "gp_fit_grad_x" : "gp_lml_grad"))) return rc;
+    if (dL_dX && (rc = gradx_lds_check(g, "gp_fit_grad_x"))) return rc;
     // (a Gower model gets the fork's values: K through the Gower branch in the variance gradient, Euclidean dK/dr on the kernel's own
     // lengthscale in the lengthscale gradients, stationary.py:218-238 -- not derivatives of its LML, which the host layer knows)
-    int rc;
     if (reset_phases) g->nphases = 0;
     if ((rc = ensure_wi(g))) return rc;
     // per-tile partials live in dT (free after ensure_wi): ntile * NACC doubles << Npad^2
@@ -76,6 +100,7 @@ extern "C" int gp_lml_grad_x(gp_t *g, double *dL_dX) {
     // the fork's Euclidean gradients_X on a Gower K is not a derivative of anything the warping could use
     if (g->kp.gower) return fail(GP_ERR_ARG, "gp_lml_grad_x: not defined for a Gower model");
     int rc;
+    if ((rc = gradx_lds_check(g, "gp_lml_grad_x"))) return rc;
     g->nphases = 0;
     if ((rc = ensure_wi(g))) return rc;
     double *dev;
@@ -109,6 +134,7 @@ extern "C" int gp_fit_grad(gp_t *g, int maxtries, double *lml, double *logdet, d
     if (!g->have_data || !g->have_params) return fail(GP_ERR_STATE, "set data and params before gp_fit_grad");
     if (g->P > GP_GRAD_MAX_P) return fail(GP_ERR_ARG, "gp_lml_grad supports P <= %d", GP_GRAD_MAX_P);
     int rc;
+    if ((rc = lml_grad_lds_check(g, "gp_fit_grad"))) return rc;   // before the factorisation: a refused call leaves the fit as it was
     if ((rc = fit_grad_head(g, maxtries, lml, logdet, jitter_used))) return rc;
     return lml_grad_impl(g, dvariance, dlengthscale, dnoise, false);
 }
@@ -123,6 +149,8 @@ extern "C" int gp_fit_grad_x(gp_t *g, int maxtries, double *lml, double *logdet,
     if (g->P > GP_GRAD_MAX_P) return fail(GP_ERR_ARG, "gp_lml_grad_x supports P <= %d", GP_GRAD_MAX_P);
     if (g->kp.gower) return fail(GP_ERR_ARG, "gp_lml_grad_x: not defined for a Gower model");
     int rc;
+    if ((rc = lml_grad_lds_check(g, "gp_fit_grad_x"))) return rc;
+    if ((rc = gradx_lds_check(g, "gp_fit_grad_x"))) return rc;
     if ((rc = fit_grad_head(g, maxtries, lml, logdet, jitter_used))) return rc;
     return lml_grad_impl(g, dvariance, dlengthscale, dnoise, false, dL_dX);
 }

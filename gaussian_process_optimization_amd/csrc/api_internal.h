@@ -83,6 +83,10 @@ constexpr bool slots_ok(const Slot (&s)[n], long cap) {
     return true;
 }
 #define GP_GRAD_MAX_P 16    // gp_lml_grad / gp_fit_grad: outputs whose alpha . y fit in front of the gradient sums
+// ... and D and P are limited JOINTLY by the LDS of a workgroup (gp_ctx::lds_per_wg, 163840 B on gfx950): the fused pass stages
+// both tiles of the inputs and of alpha, lml_grad_lds_bytes = 576 + 2048 ((gower ? 2 : 1) D + P) bytes -- D + P <= 79, a Gower
+// model 2 D + P <= 79.  lml_grad_lds_check refuses the rest up front (GP_ERR_ARG); gradx and the sparse pass fit at every
+// accepted (D, P) on that device and are checked all the same.
 #define GP_LP_MAX_NB 256    // rows of a local-penalisation batch
 #define GP_EXCLUDE_MAX 256  // excluded rows of gp_acq_lp_argbest
 #define GP_COMM_MAX_RANKS 128
@@ -259,6 +263,7 @@ struct EsState {
 
 struct gp_ctx {
     int device = 0;
+    long lds_per_wg = 0;           // hipDeviceAttributeMaxSharedMemoryPerBlock of the device (gp_create)
     hipStream_t s = nullptr;       // main stream
     hipStream_t s_panel = nullptr; // look-ahead (panel chain) stream: high priority, all CUs
     hipStream_t s_bulk = nullptr;  // trailing-update stream of the look-ahead Cholesky: masked off the reserved CUs
@@ -665,6 +670,10 @@ int wi_lauum(gp_ctx *g);
 int wi_rns(gp_ctx *g);
 int ensure_wi(gp_ctx *g);
 int ensure_linv(gp_ctx *g);
+// GP_ERR_ARG, with D, P, Gower, the bytes needed and the bytes there are, when a workgroup of launch_lml_grad / launch_gradx over
+// the context's (D, Gower setting, P) needs more LDS than the device has; nothing is launched or changed.  `who`: the entry
+int lml_grad_lds_check(const gp_ctx *g, const char *who);
+int gradx_lds_check(const gp_ctx *g, const char *who);
 void lml_grad_passes(gp_ctx *g, const Members &m);
 void grads_from_sums(const double *h, const KernParams &kp, int ard, double *dvariance, double *dlengthscale, double *dnoise);
 int lml_grad_impl(gp_ctx *g, double *dvariance, double *dlengthscale, double *dnoise, bool reset_phases, double *dL_dX = nullptr);

@@ -223,6 +223,9 @@ extern "C" int gp_sparse_fit_grad(gp_t *g, int maxtries, double *lml, double *dv
     int rc;
     if ((rc = sparse_preamble(g, true))) return rc;
     if (g->P > GP_SPARSE_GRAD_MAX_P) return fail(GP_ERR_ARG, "gp_sparse_fit_grad supports P <= %d", GP_SPARSE_GRAD_MAX_P);
+    if (sparse_grad_lds_bytes(g->D, g->P) > (size_t)g->lds_per_wg)
+        return fail(GP_ERR_ARG, "gp_sparse_fit_grad: D = %d, P = %d need %zu bytes of LDS per workgroup in the gradient pass, the device has %ld",
+                    g->D, g->P, sparse_grad_lds_bytes(g->D, g->P), g->lds_per_wg);
     if ((rc = sparse_fit_impl(g, maxtries))) return rc;
     SparseState &sp = g->sp;
     const long n = sp.Mzpad, Mz = sp.Mz, N = g->N, Npad = g->Npad;

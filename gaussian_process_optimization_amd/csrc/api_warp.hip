@@ -99,6 +99,8 @@ extern "C" int gp_fit_grad_warp(gp_t *g, int n_terms, const double *psi, double 
     if (!g || !psi || !dvariance || !dlengthscale || !dnoise || !dpsi || !dd) return fail(GP_ERR_ARG, "null argument");
     if (n_terms < 1) return fail(GP_ERR_ARG, "gp_fit_grad_warp takes a warp of 1..%d terms", GP_WARP_MAX_TERMS);
     int rc;
+    // gp_fit_grad's refusal of a shape whose gradient pass does not fit the LDS, before the warp changes the targets
+    if (!g->dead && g->have_data && (rc = lml_grad_lds_check(g, "gp_fit_grad_warp"))) return rc;
     if ((rc = gp_set_output_warp(g, n_terms, psi, d, log_jacobian))) return rc;
     if ((rc = gp_fit_grad(g, maxtries, lml, logdet, jitter_used, dvariance, dlengthscale, dnoise))) return rc;
     return gp_warp_grad(g, dpsi, dd);

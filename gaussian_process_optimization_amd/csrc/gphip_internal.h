@@ -368,6 +368,8 @@ void launch_set_identity(hipStream_t s, double *T, long ld, long n);
 void launch_symmetrize(hipStream_t s, double *A, long ld, long n, int nb = 1, long sA = 0);
 // A = scale * lower(A), mirrored into the upper triangle
 void launch_symmetrize_scale(hipStream_t s, double *A, long ld, long n, double scale, int nb = 1, long sA = 0);
+// LDS bytes a workgroup of that launch needs, its static part included, from (kp.D, kp.gower, P)
+size_t lml_grad_lds_bytes(int D, int gower, int P);
 void launch_lml_grad(hipStream_t s, const double *X, long N, long Npad, const KernParams &kp, int ard, int d0, const double *alpha,
                      int P, const double *Wi, long ldw, double *partial, double *out, int nb = 1, const KernParams *kpt = nullptr,
                      long sV = 0, long sW = 0, long sP = 0, long so = 0, long sX = 0);
@@ -398,6 +400,7 @@ void launch_zero_upper_diag(hipStream_t s, double *A, long lda, int nt);
 // out[i, q] = dL/dX_iq for i < N (row-major [N, D]): sum_j 2 dL_dK_ij g(r_ij) (x_iq - x_jq) / l_q^2 with dL_dK = 0.5 (alpha alpha^T -
 // P Wi), one pass over Wi (both triangles) per GP_GRAD_CH dimensions; partial: gradx_partial_elems(Npad) doubles of scratch
 long gradx_partial_elems(long Npad);
+size_t gradx_lds_bytes(int D, int P);   // LDS bytes a workgroup of launch_gradx needs
 // (nb members: member z's inputs at X + z sX, rows at out + z so, the rest as launch_lml_grad)
 void launch_gradx(hipStream_t s, const double *X, long N, long Npad, const KernParams &kp, const double *alpha, int P,
                   const double *Wi, long ldw, double *partial, double *out, int nb = 1, const KernParams *kpt = nullptr,
@@ -415,6 +418,7 @@ void launch_kumar_warp(hipStream_t s, double *Xs, long m0, long mc, int D, const
 //   hyper[pass GP_SPARSE_NH]     = sum_nm W k;   hyper[pass GP_SPARSE_NH + 1 + q] = sum_nm W g(r) d_q^2   (q = dimension - pass GP_GRAD_CH)
 // partial: sparse_grad_partial_elems(Mzpad, Nc) doubles of scratch; Wt has at least Nc rows of ldw >= Mzpad entries
 long sparse_grad_partial_elems(long Mzpad, long Nc);
+size_t sparse_grad_lds_bytes(int D, int P);   // LDS bytes a workgroup of launch_sparse_grad needs
 void launch_sparse_grad(hipStream_t s, const double *Z, long Mz, long Mzpad, const double *Xc, long Nc, const KernParams &kp,
                         const double *Y, int P, const double *C, long ldc, double ybeta, const double *Wt, long ldw, double wscale,
                         double *partial, double zfac, double *dZ, double *hyper);

@@ -251,6 +251,13 @@ __global__ __launch_bounds__(1024) void sum_partials_batch_kernel(const double *
     sum_partials_body(partial + z * sP, ntile, nacc, out + z * so);
 }
 
+// LDS of one workgroup of lml_grad_tile*_kernel in bytes, the static red[4][NACC] included: both inputs' tiles ([D][128] each,
+// twice over for a Gower model's second staging) and both alpha tiles ([P][128] each).  The entries that reach launch_lml_grad
+// hold it against the device's limit before anything is launched (lml_grad_lds_check, api_grad.hip)
+size_t lml_grad_lds_bytes(int D, int gower, int P) {
+    return sizeof(double) * 4 * NACC + ((size_t)(gower ? 4 : 2) * D + (size_t)2 * P) * GP_TILE * sizeof(double);
+}
+
 // out (device, NACC doubles): sums for dims [d0, d0+GCH)
 // nb > 1: the same pass for nb members, member z with parameters kpt[z] (device), alpha + z sV, Ky^-1 at Wi + z sW, partials at
 // partial + z sP and sums at out + z so; kp (the first member's, host) gives D and the Gower setting: the LDS size
@@ -259,7 +266,7 @@ void launch_lml_grad(hipStream_t s, const double *X, long N, long Npad, const Ke
                      long sW, long sP, long so, long sX) {
     const int nt = (int)(Npad / GP_TILE);
     const long ntile = (long)nt * (nt + 1) / 2;
-    const size_t shm = ((size_t)(kp.gower ? 4 : 2) * kp.D * GP_TILE + (size_t)2 * P * GP_TILE) * sizeof(double);
+    const size_t shm = lml_grad_lds_bytes(kp.D, kp.gower, P) - sizeof(double) * 4 * NACC;   // the dynamic part
     // few tiles (N <= ~2900): four workgroups per tile, 32 rows each -- 6 workgroups of 128 x 128 covariance evaluations were a
     // quarter of an LML + gradient evaluation at N = 300; the partial sums are added per (tile, quarter) in the same fixed order
     const unsigned split = ntile < 256 ? 4u : 1u;

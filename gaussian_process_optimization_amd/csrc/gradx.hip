@@ -157,6 +157,13 @@ long gradx_partial_elems(long Npad) {
     return (nt + GX_CHUNK - 1) / GX_CHUNK * Npad * GCH;
 }
 
+// LDS of one workgroup of gradx_tile_kernel in bytes (all of it dynamic): the row and the column tile of the inputs and of alpha,
+// and never less than the reduction's GX_H - 1 rows of 128 (held against the device's limit by gradx_lds_check, api_grad.hip)
+size_t gradx_lds_bytes(int D, int P) {
+    const size_t stage = ((size_t)2 * D * GP_TILE + (size_t)2 * P * GP_TILE) * sizeof(double);
+    return std::max(stage, (size_t)GX_H * GP_TILE * sizeof(double));
+}
+
 // out (device, [N, D] row-major): dL/dX of every training row; partial: gradx_partial_elems(Npad) doubles of scratch
 // nb > 1: the same passes for nb members, member z with inputs X + z sX, parameters kpt[z] (device), alpha + z sV, Ky^-1 at
 // Wi + z sW, partials at partial + z sP and rows at out + z so; kp (the first member's, host) gives D and the family: the instance
@@ -166,8 +173,7 @@ void launch_gradx(hipStream_t s, const double *X, long N, long Npad, const KernP
                   long sW, long sP, long so) {
     const int nt = (int)(Npad / GP_TILE);
     const int nchunk = (nt + GX_CHUNK - 1) / GX_CHUNK;
-    const size_t stage = ((size_t)2 * kp.D * GP_TILE + (size_t)2 * P * GP_TILE) * sizeof(double);
-    const size_t shm = std::max(stage, (size_t)GX_H * GP_TILE * sizeof(double));
+    const size_t shm = gradx_lds_bytes(kp.D, P);
     const int fp = GP_FAMILY_PAIR(kp.kernel);
     const dim3 grid((unsigned)nt, (unsigned)nchunk, (unsigned)nb);
     for (int d0 = 0; d0 < kp.D; d0 += GCH) {

@@ -183,14 +183,21 @@ long sparse_grad_partial_elems(long Mzpad, long Nc) {
     return (ntc + SP_CHUNK - 1) / SP_CHUNK * SP_NACC * Mzpad;
 }
 
+// LDS of one workgroup of sparse_grad_tile_kernel in bytes (all of it dynamic): the inducing rows' tile, the column tile of the
+// inputs and of the P targets, and never less than the reduction's SP_NACC rows of 128 (gp_sparse_fit_grad holds it against the
+// device's limit before anything is launched)
+size_t sparse_grad_lds_bytes(int D, int P) {
+    const size_t stage = ((size_t)2 * D + P) * GP_TILE * sizeof(double);
+    return std::max(stage, (size_t)SP_NACC * GP_TILE * sizeof(double));
+}
+
 void launch_sparse_grad(hipStream_t s, const double *Z, long Mz, long Mzpad, const double *Xc, long Nc, const KernParams &kp,
                         const double *Y, int P, const double *C, long ldc, double ybeta, const double *Wt, long ldw, double wscale,
                         double *partial, double zfac, double *dZ, double *hyper) {
     const int ntz = (int)(Mzpad / GP_TILE);
     const int ntc = (int)((Nc + GP_TILE - 1) / GP_TILE);
     const int nchunk = (ntc + SP_CHUNK - 1) / SP_CHUNK;
-    const size_t stage = ((size_t)2 * kp.D + P) * GP_TILE * sizeof(double);
-    const size_t shm = std::max(stage, (size_t)SP_NACC * GP_TILE * sizeof(double));
+    const size_t shm = sparse_grad_lds_bytes(kp.D, P);
     const int fp = GP_FAMILY_PAIR(kp.kernel);
     int pass = 0;
     for (int d0 = 0; d0 < kp.D; d0 += GCH, ++pass) {

@@ -124,8 +124,20 @@ int gp_cross_kernel_matrix(gp_t *gp, const double *X2, int64_t M2, double *K);
  *   dL_dK = 0.5 (alpha alpha^T - P Ky^-1) (exact_gaussian_inference.py:70);
  *   dnoise = sum diag(dL_dK) (gaussian.py:78-79);
  *   dvariance, dlengthscale[1 or D] = Stationary.update_gradients_full (stationary.py:218-238).
- * Natural-space gradients of the LML; the Logexp chain rule stays on the host. Requires gp_fit. */
+ * Natural-space gradients of the LML; the Logexp chain rule stays on the host. Requires gp_fit.
+ * Limits (GP_ERR_ARG, nothing is launched and the context is left as it was): P <= 16 (GP_GRAD_MAX_P), and D and P JOINTLY --
+ * the fused pass stages both 128-row tiles of the inputs (twice over for a Gower model) and of alpha in LDS,
+ *   576 + 2048 ((Gower ? 2 : 1) D + P) bytes a workgroup,
+ * which must fit what the device gives a workgroup (hipDeviceAttributeMaxSharedMemoryPerBlock, read in gp_create).  On gfx950
+ * (163840 bytes): D + P <= 79, for a Gower model 2 D + P <= 79 -- D = 64 with P = 16 is refused, and a Gower model of D >= 40
+ * has no gradient entry.  The message names D, P, the Gower setting, the bytes needed and the bytes there are.  The same limit
+ * holds for gp_fit_grad, gp_fit_grad_x, gp_fit_grad_warp and the three batch entries below, checked before their factorisation;
+ * gp_lml_grad_x (2048 (D + P) bytes) and gp_sparse_fit_grad (1024 (2 D + P)) fit at every accepted shape there and are checked
+ * all the same. */
 int gp_lml_grad(gp_t *gp, double *dvariance, double *dlengthscale, double *dnoise);
+/* The two sides of that comparison for the context's data and Gower setting: *need bytes of LDS a workgroup of the gradient
+ * pass, *available bytes the device gives one.  Requires gp_set_data (GP_ERR_STATE). */
+int gp_lml_grad_lds(gp_t *gp, int64_t *need, int64_t *available);
 
 /* grad_dict['dL_dK'] of ExactGaussianInference.inference (exact_gaussian_inference.py:70,74):
  *   dL_dK[N,N] = 0.5 (alpha alpha^T - P Ky^-1), the matrix GP.parameters_changed hands to
