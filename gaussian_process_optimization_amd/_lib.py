@@ -82,6 +82,10 @@ SIGNATURES = [
     ("gp_sparse_set_inducing", ctypes.c_int, [_vp, c_double_p, ctypes.c_int64]),
     ("gp_sparse_fit", ctypes.c_int, [_vp, ctypes.c_int, c_double_p, c_double_p, c_double_p]),
     ("gp_sparse_fit_grad", ctypes.c_int, [_vp, ctypes.c_int, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p]),
+    ("gp_sparse_fit_grad_batch", ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int64, c_double_p, c_double_p, c_double_p, c_double_p,
+                                                ctypes.c_int, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p,
+                                                c_double_p, c_int_p]),
+    ("gp_sparse_batch_bytes", ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64)]),
     ("gp_sparse_posterior", ctypes.c_int, [_vp, c_double_p, c_double_p]),
     ("gp_sparse_predict", ctypes.c_int, [_vp, c_double_p, ctypes.c_int64, ctypes.c_int, c_double_p, c_double_p, c_double_p,
                                          c_double_p]),
@@ -714,6 +718,32 @@ class Handle(object):
                                          dptr(dZ))
         check(self.lib, rc, "gp_sparse_fit_grad")
         return lml.value, (dv.value, dl, dn.value, dZ)
+
+    def sparse_fit_grad_batch(self, Z, variances, lengthscales, noises, maxtries=5):
+        """gp_sparse_fit_grad for R members in one call, member r over the inducing inputs ``Z[r]`` ([R, Mz, D]) and its own
+        parameters; the resident inducing inputs, sparse fit and everything else on the handle are untouched.  Returns
+        ((lml, jitter_kmm, jitter_b) [R] each, (dvariance [R], dlengthscale [R, nls], dnoise [R], dZ [R, Mz, D]), status [R]);
+        a member with status[r] != 0 has NaN outputs."""
+        R, var, ls, noi = self._batch_params(variances, lengthscales, noises)
+        Z = as_f64(Z, 3)
+        if Z.shape[0] != R or Z.shape[2] != self.D:
+            raise ValueError("Z has shape %s, expected (%d, Mz, %d): the inducing inputs of every member" % (Z.shape, R, self.D))
+        Mz = Z.shape[1]
+        lml, jk, jb = np.empty(R), np.empty(R), np.empty(R)
+        dv, dl, dn = np.empty(R), np.empty((R, ls.shape[1])), np.empty(R)
+        dZ = np.empty((R, Mz, self.D))
+        status = np.zeros(R, dtype=np.int32)
+        rc = self.lib.gp_sparse_fit_grad_batch(self.h, int(R), int(Mz), dptr(Z), dptr(var), dptr(ls), dptr(noi), int(maxtries),
+                                               dptr(lml), dptr(jk), dptr(jb), dptr(dv), dptr(dl), dptr(dn), dptr(dZ),
+                                               status.ctypes.data_as(c_int_p))
+        check(self.lib, rc, "gp_sparse_fit_grad_batch")
+        return (lml, jk, jb), (dv, dl, dn, dZ), status
+
+    def sparse_batch_bytes(self, R, Mz):
+        """Bytes of device buffers sparse_fit_grad_batch would hold for R members of Mz inducing inputs over the resident data."""
+        out = ctypes.c_int64(0)
+        check(self.lib, self.lib.gp_sparse_batch_bytes(self.h, int(R), int(Mz), ctypes.byref(out)), "gp_sparse_batch_bytes")
+        return int(out.value)
 
     def sparse_posterior(self):
         """(woodbury_vector [Mz, P], woodbury_inv [Mz, Mz]) of the sparse fit."""

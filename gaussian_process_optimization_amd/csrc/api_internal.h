@@ -405,6 +405,10 @@ struct gp_ctx {
     // gp_fit_grad_batch (api_batch.hip): buffers of its own, sized to the R and Npad in use -- never the resident fit's
     DevBuf<double> dBatch;
     DevBuf<signed char> dBatchAux;   // per-member KernParams table, then factorisation status words
+    // gp_sparse_fit_grad_batch (api_sparse_batch.hip): buffers of its own, sized to the R, Mz and Npad in use -- never the
+    // resident sparse fit's, the sparse candidate table's or the exact batch's
+    DevBuf<double> dSpBatch;
+    DevBuf<signed char> dSpBatchAux;   // per-member KernParams table, then factorisation status words
     // output warp (api_warp.hip): warp.n > 0 while one is on -- dY then holds f(dYraw), dYraw the targets gp_set_data brought
     WarpParams warp{0, 1.0, {}, {}, {}};
     DevBuf<double> dYraw;  // N: the raw targets of a warped model

@@ -200,8 +200,11 @@ void launch_kbuild(hipStream_t s, double *A, long lda, const double *X, long N, 
 // RHS rows: A[(Npad + p)*lda + i] = Y[i*P + p] (zero for i >= N, and rows p >= P zero)
 void launch_set_rhs(hipStream_t s, double *A, long lda, const double *Y, long N, long Npad, int P, int nb = 1, long sA = 0, long sY = 0);
 // T[c*ldt + i] = k(xs_c, x_i) for c < M, i < N; zero in the padding.
+// nb > 1: nb members in one launch, member z = blockIdx.z with its own block at T + z sT, its own second input set at X + z sX and
+// parameters kpt[z] (device); Xs is shared, and kp (the first member's) picks the instance and the LDS size for all
 void launch_cross_k(hipStream_t s, double *T, long ldt, const double *Xs, long M, long Mpad,
-                    const double *X, long N, long Npad, const KernParams &kp);
+                    const double *X, long N, long Npad, const KernParams &kp, int nb = 1, long sT = 0, long sX = 0,
+                    const KernParams *kpt = nullptr);
 
 // the same for M <= 8 candidate rows only (rows 0 .. M-1 of T, columns 0 .. Npad-1; no padding rows): the small-M path
 void launch_cross_k_rows(hipStream_t s, double *T, long ldt, const double *Xs, int M, const double *X, long N, long Npad,
@@ -419,18 +422,35 @@ void launch_kumar_warp(hipStream_t s, double *Xs, long m0, long mc, int D, const
 // partial: sparse_grad_partial_elems(Mzpad, Nc) doubles of scratch; Wt has at least Nc rows of ldw >= Mzpad entries
 long sparse_grad_partial_elems(long Mzpad, long Nc);
 size_t sparse_grad_lds_bytes(int D, int P);   // LDS bytes a workgroup of launch_sparse_grad needs
+// mb (gp_sparse_fit_grad_batch): the same pass for mb->nb members in the same launches, member z = blockIdx.z with rows Z + z sZ,
+// columns Xc + z sXc (0: shared), parameters kpt[z] (device; kp then only picks the instance and the LDS size), woodbury rows
+// C + z sC, weights Wt + z sW, ybeta_tab[z] / wscale_tab[z] in place of ybeta / wscale (null: the value given), slabs at
+// partial + z sP, results at dZ + z sDZ and hyper + z sH.  The chunking of the columns and the order of every sum are functions of
+// (Nc, Mz) alone: a member gets the bits it gets alone.  Null: one problem, as before.
+struct SparseGradMembers {
+    int nb = 1;
+    long sZ = 0, sXc = 0, sC = 0, sW = 0, sP = 0, sDZ = 0, sH = 0;
+    const KernParams *kpt = nullptr;
+    const double *ybeta_tab = nullptr, *wscale_tab = nullptr;
+};
 void launch_sparse_grad(hipStream_t s, const double *Z, long Mz, long Mzpad, const double *Xc, long Nc, const KernParams &kp,
                         const double *Y, int P, const double *C, long ldc, double ybeta, const double *Wt, long ldw, double wscale,
-                        double *partial, double zfac, double *dZ, double *hyper);
-// n x n helpers (leading dimension n): out = a X + b Y + c I (Y may be null);  out = c I + sum_p v_p v_p^T, v_p = V + p ldv
-void launch_sparse_lincomb(hipStream_t s, double *out, const double *X, double a, const double *Y, double b, double c, long n);
-void launch_sparse_outer(hipStream_t s, double *out, const double *V, long ldv, int P, double c, long n);
-// out[p ldo + i] = scale sum_{k < K} M[i ldm + k] v[p vsp + k vsk],  i < rows, p < P
+                        double *partial, double zfac, double *dZ, double *hyper, const SparseGradMembers *mb = nullptr);
+// n x n helpers (leading dimension n): out = a X + b Y + c I (Y may be null);  out = c I + sum_p v_p v_p^T, v_p = V + p ldv.
+// nb members per launch: member z's operands at base + z stride, a_tab[z] / b_tab[z] / scale_tab[z] in place of a / b / scale
+// where a table is given.  The defaults are the single problem.
+void launch_sparse_lincomb(hipStream_t s, double *out, const double *X, double a, const double *Y, double b, double c, long n, int nb = 1,
+                           long sO = 0, long sX = 0, long sY = 0, const double *a_tab = nullptr, const double *b_tab = nullptr);
+void launch_sparse_outer(hipStream_t s, double *out, const double *V, long ldv, int P, double c, long n, int nb = 1, long sO = 0,
+                         long sV = 0);
+// out[p ldo + i] = scale sum_{k < K} M[i ldm + k] v[p vsp + k vsk],  i < rows, p < P  (members: M + z sM, v + z sv, out + z so)
 void launch_sparse_thin(hipStream_t s, const double *M, long ldm, long rows, long K, const double *v, long vsp, long vsk, int P,
-                        double scale, double *out, long ldo);
+                        double scale, double *out, long ldo, int nb = 1, long sM = 0, long sv = 0, long so = 0,
+                        const double *scale_tab = nullptr);
 // out[0] = sum Y^2 (NP entries), out[1] = trace VVt (Mz), out[2] = sum c1^2 (P rows of n), out[3] = sum VVt o Dm (n x n)
+// (members: Y shared, VVt / Dm + z sT, c1 + z sc, out + z so)
 void launch_sparse_scalars(hipStream_t s, const double *Y, long NP, const double *VVt, const double *Dm, long Mz, long n, const double *c1,
-                           int P, double *out);
+                           int P, double *out, int nb = 1, long sT = 0, long sc = 0, long so = 0);
 // mean[c, p] = sum_m Kx[c, m] w[p ldw + m];  var[c] = max(kss - sum_m Bt[c, m] Kx[c, m], 1e-15) + noise_add,  c < M, m < Mz
 void launch_sparse_predict_reduce(hipStream_t s, const double *Kx, const double *Bt, long ld, long M, long Mz, const double *w, long ldw,
                                   int P, double kss, double noise_add, double *mean, double *var);

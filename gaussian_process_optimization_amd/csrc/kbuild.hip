@@ -195,8 +195,8 @@ void launch_set_rhs(hipStream_t s, double *A, long lda, const double *Y, long N,
 
 // T[c][i] = k(xs_c, x_i); tiles (tc over candidates, ti over training points)
 template <int DU, int FP>
-__global__ __launch_bounds__(256) void cross_k_kernel(double *T, long ldt, const double *Xs, long M, const double *X,
-                                                      long N, KernParams kp, int nti) {
+__device__ __forceinline__ void cross_k_body(double *T, long ldt, const double *Xs, long M, const double *X, long N,
+                                             const KernParams &kp, int nti) {
     extern __shared__ __attribute__((aligned(16))) double sm[];
     const int DS = DU > 0 ? DU : kp.D;
     double *xc = sm;
@@ -260,14 +260,22 @@ __global__ __launch_bounds__(256) void cross_k_kernel(double *T, long ldt, const
         *(double2_t *)(T + gcand * ldt + gi) = out;
     }
 }
+template <int DU, int FP>
+__global__ __launch_bounds__(256) void cross_k_kernel(double *T, long ldt, const double *Xs, long M, const double *X,
+                                                      long N, KernParams kp, int nti) {
+    cross_k_body<DU, FP>(T, ldt, Xs, M, X, N, kp, nti);
+}
+static void launch_cross_k_members(hipStream_t s, double *T, long ldt, long sT, const double *Xs, long M, const double *X, long sX, long N,
+                                   int DU, int fp, size_t shm, const KernParams *kpt, int nti, unsigned nblk, int nb);
 
 void launch_cross_k(hipStream_t s, double *T, long ldt, const double *Xs, long M, long Mpad, const double *X,
-                    long N, long Npad, const KernParams &kp) {
+                    long N, long Npad, const KernParams &kp, int nb, long sT, long sX, const KernParams *kpt) {
     const int ntc = (int)(Mpad / GP_TILE), nti = (int)(Npad / GP_TILE);
     const int DU = kp.gower ? 0 : (kp.D <= 8 ? 8 : (kp.D <= 16 ? 16 : 0));
     const size_t shm = (size_t)2 * (DU ? DU : kp.D) * GP_TILE * sizeof(double);
     const dim3 grid((unsigned)((long)ntc * nti));
     const int fp = GP_FAMILY_PAIR(kp.kernel);
+    if (nb > 1) return launch_cross_k_members(s, T, ldt, sT, Xs, M, X, sX, N, DU, fp, shm, kpt, nti, grid.x, nb);
     if (DU == 8)
         KB_LAUNCH_PAIR(cross_k_kernel, 8, fp, grid, dim3(256), shm, s, T, ldt, Xs, M, X, N, kp, nti);
     else if (DU == 16)
@@ -328,4 +336,23 @@ static void launch_kbuild_members(hipStream_t s, double *A, long lda, long sA, c
         KB_LAUNCH_PAIR(kbuild_batch_kernel, 16, fp, grid, dim3(256), shm, s, A, lda, sA, X, sX, N, Npad, kpt, diag_tab, nt);
     else
         KB_LAUNCH_PAIR(kbuild_batch_kernel, 0, fp, grid, dim3(256), shm, s, A, lda, sA, X, sX, N, Npad, kpt, diag_tab, nt);
+}
+
+// member z = blockIdx.z of a batch (gp_sparse_fit_grad_batch): its own block at T + z sT, its own second input set at X + z sX
+// (the inducing inputs) and parameters kpt[z]; the rows Xs (the data) are shared
+template <int DU, int FP>
+__global__ __launch_bounds__(256) void cross_k_batch_kernel(double *T, long ldt, long sT, const double *Xs, long M, const double *X,
+                                                            long sX, long N, const KernParams *kpt, int nti) {
+    const long z = blockIdx.z;
+    cross_k_body<DU, FP>(T + z * sT, ldt, Xs, M, X + z * sX, N, kpt[z], nti);
+}
+static void launch_cross_k_members(hipStream_t s, double *T, long ldt, long sT, const double *Xs, long M, const double *X, long sX, long N,
+                                   int DU, int fp, size_t shm, const KernParams *kpt, int nti, unsigned nblk, int nb) {
+    const dim3 grid(nblk, 1, (unsigned)nb);
+    if (DU == 8)
+        KB_LAUNCH_PAIR(cross_k_batch_kernel, 8, fp, grid, dim3(256), shm, s, T, ldt, sT, Xs, M, X, sX, N, kpt, nti);
+    else if (DU == 16)
+        KB_LAUNCH_PAIR(cross_k_batch_kernel, 16, fp, grid, dim3(256), shm, s, T, ldt, sT, Xs, M, X, sX, N, kpt, nti);
+    else
+        KB_LAUNCH_PAIR(cross_k_batch_kernel, 0, fp, grid, dim3(256), shm, s, T, ldt, sT, Xs, M, X, sX, N, kpt, nti);
 }

@@ -32,10 +32,9 @@
 // hyper-parameter sums).
 // partial[(chunk * SP_NACC + a) * Mzpad + m]
 template <int FP>
-__global__ __launch_bounds__(SP_THREADS) void sparse_grad_tile_kernel(const double *Z, long Mz, long Mzpad, const double *Xc, long Nc,
-                                                                      KernParams kp, int d0, const double *Y, int P, const double *C,
-                                                                      long ldc, double ybeta, const double *Wt, long ldw, double wscale,
-                                                                      double *partial) {
+__device__ __forceinline__ void sparse_grad_tile_body(const double *Z, long Mz, long Mzpad, const double *Xc, long Nc, const KernParams &kp,
+                                                      int d0, const double *Y, int P, const double *C, long ldc, double ybeta,
+                                                      const double *Wt, long ldw, double wscale, double *partial) {
     extern __shared__ __attribute__((aligned(16))) double sm[];
     const int D = kp.D;
     double *zi = sm;                        // [D][128]
@@ -133,15 +132,42 @@ __global__ __launch_bounds__(SP_THREADS) void sparse_grad_tile_kernel(const doub
     }
 }
 
+template <int FP>
+__global__ __launch_bounds__(SP_THREADS) void sparse_grad_tile_kernel(const double *Z, long Mz, long Mzpad, const double *Xc, long Nc,
+                                                                      KernParams kp, int d0, const double *Y, int P, const double *C,
+                                                                      long ldc, double ybeta, const double *Wt, long ldw, double wscale,
+                                                                      double *partial) {
+    sparse_grad_tile_body<FP>(Z, Mz, Mzpad, Xc, Nc, kp, d0, Y, P, C, ldc, ybeta, Wt, ldw, wscale, partial);
+}
+// member z = blockIdx.z of a batch (gp_sparse_fit_grad_batch): rows Z + z sZ, columns Xc + z sXc (0: the shared data), parameters
+// kpt[z] (device table), woodbury rows C + z sC, weights Wt + z sW, the scales ybeta_tab[z] / wscale_tab[z] (a null table: the
+// value given) and slabs at partial + z sP.  The body is the single problem's: a member's sums are added in the order the
+// constants above fix.
+template <int FP>
+__global__ __launch_bounds__(SP_THREADS) void sparse_grad_tile_batch_kernel(const double *Z, long sZ, long Mz, long Mzpad, const double *Xc,
+                                                                            long sXc, long Nc, const KernParams *kpt, int d0,
+                                                                            const double *Y, int P, const double *C, long sC, long ldc,
+                                                                            double ybeta, const double *ybeta_tab, const double *Wt,
+                                                                            long sW, long ldw, double wscale, const double *wscale_tab,
+                                                                            double *partial, long sP) {
+    const long z = blockIdx.z;
+    sparse_grad_tile_body<FP>(Z + z * sZ, Mz, Mzpad, Xc + z * sXc, Nc, kpt[z], d0, Y, P, C + z * sC, ldc,
+                              ybeta_tab ? ybeta_tab[z] : ybeta, Wt + z * sW, ldw, wscale_tab ? wscale_tab[z] : wscale, partial + z * sP);
+}
+
 // dZ[m, d0 + q] = zfac (sum over the chunks, ascending) / l_q for m < Mz: (z - x) / l^2 = scaled difference / l
+// (member z = blockIdx.z: slabs at partial + z sP, lengthscales of kpt[z], rows at dZ + z sD; a null kpt: one problem, kp's)
 __global__ __launch_bounds__(256) void sparse_dz_sum_kernel(const double *partial, long Mz, long Mzpad, int nchunk, KernParams kp, int d0,
-                                                            double zfac, double *dZ) {
+                                                            double zfac, double *dZ, long sP, long sD, const KernParams *kpt) {
     const long m = (long)blockIdx.x * 256 + threadIdx.x;   // adjacent lanes take adjacent rows: the slabs are read coalesced
     const int q = blockIdx.y;
+    const long z = blockIdx.z;
     if (m >= Mz || d0 + q >= kp.D) return;
+    partial += z * sP;
     double s = 0.0;
     for (int k = 0; k < nchunk; ++k) s += partial[((long)k * SP_NACC + 1 + q) * Mzpad + m];
-    dZ[m * kp.D + d0 + q] = zfac * s / kp.ls[d0 + q];
+    const double l = kpt ? kpt[z].ls[d0 + q] : kp.ls[d0 + q];
+    dZ[z * sD + m * kp.D + d0 + q] = zfac * s / l;
 }
 
 __device__ __forceinline__ double sp_wave_sum(double v) {
@@ -163,10 +189,13 @@ __device__ __forceinline__ double sp_block_sum(double v, double *sh) {
 }
 
 // out[0] = sum W k, out[1 + q] = sum W g d_q^2 of the pass, over the chunks and the rows m < Mz: one workgroup per sum
+// (member z = blockIdx.y: slabs at partial + z sP, sums at out + z sO)
 __global__ __launch_bounds__(1024) void sparse_hyper_sum_kernel(const double *partial, long Mz, long Mzpad, int nchunk, int D, int d0,
-                                                                double *out) {
+                                                                double *out, long sP, long sO) {
     __shared__ double sh[16];
     const int a = blockIdx.x;
+    partial += (long)blockIdx.y * sP;
+    out += (long)blockIdx.y * sO;
     const int src = a == 0 ? 0 : GCH + a;
     double s = 0.0;
     if (a == 0 || d0 + a - 1 < D)
@@ -193,75 +222,109 @@ size_t sparse_grad_lds_bytes(int D, int P) {
 
 void launch_sparse_grad(hipStream_t s, const double *Z, long Mz, long Mzpad, const double *Xc, long Nc, const KernParams &kp,
                         const double *Y, int P, const double *C, long ldc, double ybeta, const double *Wt, long ldw, double wscale,
-                        double *partial, double zfac, double *dZ, double *hyper) {
+                        double *partial, double zfac, double *dZ, double *hyper, const SparseGradMembers *mb) {
     const int ntz = (int)(Mzpad / GP_TILE);
     const int ntc = (int)((Nc + GP_TILE - 1) / GP_TILE);
     const int nchunk = (ntc + SP_CHUNK - 1) / SP_CHUNK;
     const size_t shm = sparse_grad_lds_bytes(kp.D, P);
     const int fp = GP_FAMILY_PAIR(kp.kernel);
+    const unsigned nb = mb ? (unsigned)mb->nb : 1u;
+    const SparseGradMembers one{};
+    const SparseGradMembers &m = mb ? *mb : one;
     int pass = 0;
     for (int d0 = 0; d0 < kp.D; d0 += GCH, ++pass) {
-        if (fp)
+        if (mb) {   // kernel family, D and P -- what picks the instance and the LDS size -- are the same for every member
+            const dim3 grid((unsigned)ntz, (unsigned)nchunk, nb);
+            if (fp)
+                GP_LAUNCH(sparse_grad_tile_batch_kernel<1>, grid, dim3(SP_THREADS), shm, s, Z, m.sZ, Mz, Mzpad, Xc, m.sXc, Nc, m.kpt, d0, Y,
+                          P, C, m.sC, ldc, ybeta, m.ybeta_tab, Wt, m.sW, ldw, wscale, m.wscale_tab, partial, m.sP);
+            else
+                GP_LAUNCH(sparse_grad_tile_batch_kernel<0>, grid, dim3(SP_THREADS), shm, s, Z, m.sZ, Mz, Mzpad, Xc, m.sXc, Nc, m.kpt, d0, Y,
+                          P, C, m.sC, ldc, ybeta, m.ybeta_tab, Wt, m.sW, ldw, wscale, m.wscale_tab, partial, m.sP);
+        } else if (fp)
             GP_LAUNCH(sparse_grad_tile_kernel<1>, dim3((unsigned)ntz, (unsigned)nchunk), dim3(SP_THREADS), shm, s, Z, Mz, Mzpad, Xc, Nc,
                       kp, d0, Y, P, C, ldc, ybeta, Wt, ldw, wscale, partial);
         else
             GP_LAUNCH(sparse_grad_tile_kernel<0>, dim3((unsigned)ntz, (unsigned)nchunk), dim3(SP_THREADS), shm, s, Z, Mz, Mzpad, Xc, Nc,
                       kp, d0, Y, P, C, ldc, ybeta, Wt, ldw, wscale, partial);
-        GP_LAUNCH(sparse_dz_sum_kernel, dim3((unsigned)((Mz + 255) / 256), GCH), dim3(256), 0, s, partial, Mz, Mzpad, nchunk, kp, d0,
-                  zfac, dZ);
-        GP_LAUNCH(sparse_hyper_sum_kernel, dim3(GP_SPARSE_NH), dim3(1024), 0, s, partial, Mz, Mzpad, nchunk, kp.D, d0,
-                  hyper + (long)pass * GP_SPARSE_NH);
+        GP_LAUNCH(sparse_dz_sum_kernel, dim3((unsigned)((Mz + 255) / 256), GCH, nb), dim3(256), 0, s, partial, Mz, Mzpad, nchunk, kp, d0,
+                  zfac, dZ, m.sP, m.sDZ, m.kpt);
+        GP_LAUNCH(sparse_hyper_sum_kernel, dim3(GP_SPARSE_NH, nb), dim3(1024), 0, s, partial, Mz, Mzpad, nchunk, kp.D, d0,
+                  hyper + (long)pass * GP_SPARSE_NH, m.sP, m.sH);
     }
 }
 
 // ---- the small dense helpers of the Mz x Mz algebra (n = Mzpad, leading dimension n) -----------------------------------------
+// Each helper takes nb members in one launch (the member is the last grid index): member z's operands at base + z stride, its
+// per-member coefficient from a device table where one is given (null: the value in the arguments, for every member).  One
+// member with zero strides and no tables is the single problem: the same body, the same bits.
 // out = a X + b Y + c I  (Y may be null)
 __global__ __launch_bounds__(256) void sparse_lincomb_kernel(double *out, const double *X, double a, const double *Y, double b, double c,
-                                                             long n) {
+                                                             long n, long sO, long sX, long sY, const double *a_tab, const double *b_tab) {
     const long e = (long)blockIdx.x * 256 + threadIdx.x;
     if (e >= n * n) return;
+    const long z = blockIdx.y;
+    out += z * sO;
+    X += z * sX;
+    if (a_tab) a = a_tab[z];
+    if (b_tab) b = b_tab[z];
     const long i = e / n, j = e - i * n;
     double v = a * X[e];
-    if (Y) v = fma(b, Y[e], v);
+    if (Y) v = fma(b, Y[z * sY + e], v);
     out[e] = v + (i == j ? c : 0.0);
 }
-void launch_sparse_lincomb(hipStream_t s, double *out, const double *X, double a, const double *Y, double b, double c, long n) {
-    GP_LAUNCH(sparse_lincomb_kernel, dim3((unsigned)((n * n + 255) / 256)), dim3(256), 0, s, out, X, a, Y, b, c, n);
+void launch_sparse_lincomb(hipStream_t s, double *out, const double *X, double a, const double *Y, double b, double c, long n, int nb,
+                           long sO, long sX, long sY, const double *a_tab, const double *b_tab) {
+    GP_LAUNCH(sparse_lincomb_kernel, dim3((unsigned)((n * n + 255) / 256), (unsigned)nb), dim3(256), 0, s, out, X, a, Y, b, c, n, sO, sX,
+              sY, a_tab, b_tab);
 }
 // out = c I + sum_p v_p v_p^T,  v_p = V + p ldv (n entries)
-__global__ __launch_bounds__(256) void sparse_outer_kernel(double *out, const double *V, long ldv, int P, double c, long n) {
+__global__ __launch_bounds__(256) void sparse_outer_kernel(double *out, const double *V, long ldv, int P, double c, long n, long sO,
+                                                           long sV) {
     const long e = (long)blockIdx.x * 256 + threadIdx.x;
     if (e >= n * n) return;
+    out += (long)blockIdx.y * sO;
+    V += (long)blockIdx.y * sV;
     const long i = e / n, j = e - i * n;
     double v = 0.0;
     for (int p = 0; p < P; ++p) v = fma(V[p * ldv + i], V[p * ldv + j], v);
     out[e] = v + (i == j ? c : 0.0);
 }
-void launch_sparse_outer(hipStream_t s, double *out, const double *V, long ldv, int P, double c, long n) {
-    GP_LAUNCH(sparse_outer_kernel, dim3((unsigned)((n * n + 255) / 256)), dim3(256), 0, s, out, V, ldv, P, c, n);
+void launch_sparse_outer(hipStream_t s, double *out, const double *V, long ldv, int P, double c, long n, int nb, long sO, long sV) {
+    GP_LAUNCH(sparse_outer_kernel, dim3((unsigned)((n * n + 255) / 256), (unsigned)nb), dim3(256), 0, s, out, V, ldv, P, c, n, sO, sV);
 }
 // out[p ldo + i] = scale sum_{k < K} M[i ldm + k] v[p vsp + k vsk]   for i < rows, p < P: one workgroup per (i, p), thread t
 // takes k = t, t + 256, ... in order, the threads added as a fixed tree
 __global__ __launch_bounds__(256) void sparse_thin_kernel(const double *M, long ldm, long K, const double *v, long vsp, long vsk,
-                                                          double scale, double *out, long ldo) {
+                                                          double scale, double *out, long ldo, long sM, long sv, long so,
+                                                          const double *scale_tab) {
     __shared__ double sh[4];
-    const long i = blockIdx.x, p = blockIdx.y;
+    const long i = blockIdx.x, p = blockIdx.y, z = blockIdx.z;
+    M += z * sM;
+    v += z * sv;
+    if (scale_tab) scale = scale_tab[z];
     double s = 0.0;
     for (long k = threadIdx.x; k < K; k += 256) s = fma(M[i * ldm + k], v[p * vsp + k * vsk], s);
     s = sp_block_sum<256>(s, sh);
-    if (threadIdx.x == 0) out[p * ldo + i] = scale * s;
+    if (threadIdx.x == 0) out[z * so + p * ldo + i] = scale * s;
 }
 void launch_sparse_thin(hipStream_t s, const double *M, long ldm, long rows, long K, const double *v, long vsp, long vsk, int P,
-                        double scale, double *out, long ldo) {
-    GP_LAUNCH(sparse_thin_kernel, dim3((unsigned)rows, (unsigned)P), dim3(256), 0, s, M, ldm, K, v, vsp, vsk, scale, out, ldo);
+                        double scale, double *out, long ldo, int nb, long sM, long sv, long so, const double *scale_tab) {
+    GP_LAUNCH(sparse_thin_kernel, dim3((unsigned)rows, (unsigned)P, (unsigned)nb), dim3(256), 0, s, M, ldm, K, v, vsp, vsk, scale, out,
+              ldo, sM, sv, so, scale_tab);
 }
 // out[0] = sum Y^2, out[1] = trace(VVt) (i < Mz), out[2] = sum_p |c_p|^2 (data_fit), out[3] = sum VVt o Dm (n x n; VVt is zero in
 // the padding): one workgroup each
 __global__ __launch_bounds__(1024) void sparse_scalars_kernel(const double *Y, long NP, const double *VVt, const double *Dm, long Mz, long n,
-                                                              const double *c1, int P, double *out) {
+                                                              const double *c1, int P, double *out, long sT, long sc, long so) {
     __shared__ double sh[16];
     double s = 0.0;
     const int t = threadIdx.x;
+    const long z = blockIdx.y;
+    VVt += z * sT;
+    Dm += z * sT;
+    c1 += z * sc;
+    out += z * so;
     if (blockIdx.x == 0) {
         for (long e = t; e < NP; e += 1024) s = fma(Y[e], Y[e], s);
     } else if (blockIdx.x == 1) {
@@ -275,8 +338,8 @@ __global__ __launch_bounds__(1024) void sparse_scalars_kernel(const double *Y, l
     if (t == 0) out[blockIdx.x] = s;
 }
 void launch_sparse_scalars(hipStream_t s, const double *Y, long NP, const double *VVt, const double *Dm, long Mz, long n, const double *c1,
-                           int P, double *out) {
-    GP_LAUNCH(sparse_scalars_kernel, dim3(4), dim3(1024), 0, s, Y, NP, VVt, Dm, Mz, n, c1, P, out);
+                           int P, double *out, int nb, long sT, long sc, long so) {
+    GP_LAUNCH(sparse_scalars_kernel, dim3(4, (unsigned)nb), dim3(1024), 0, s, Y, NP, VVt, Dm, Mz, n, c1, P, out, sT, sc, so);
 }
 
 // ---- posterior reduction (posterior.py:225-248) -----------------------------------------------------------------------------

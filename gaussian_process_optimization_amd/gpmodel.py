@@ -47,12 +47,18 @@ class GPModel(BOModel):
     ``predict_withGradients`` and the mean's gradients of up to eight locations -- the hammer precompute and ``estimate_L`` of the
     local penalisation -- go down as ONE ``gp_sparse_predict_rows`` call each.  The two routes agree to rounding, not bitwise.
     ``incremental=True`` (exact model only; default False) lets ``updateModel`` append new observations to the fitted factor
-    when the hyper-parameters are kept (``max_iters <= 0``), see there."""
+    when the hyper-parameters are kept (``max_iters <= 0``), see there.
+    ``lockstep_restarts=True`` (sparse models only; default False) runs the sparse model's restarts in lockstep, one
+    ``gp_sparse_fit_grad_batch`` per round of L-BFGS steps (``SparseGPRegression.optimize_restarts(parallel=True)``).  There are
+    two flags because ``parallel_restarts`` was defined, and is tested, as the exact model's batch: with ``sparse=True`` it keeps
+    raising, so that a configuration written for the exact model never silently changes meaning, and the sparse route is asked
+    for by name."""
     analytical_gradient_prediction = True
 
     def __init__(self, kernel=None, noise_var=None, exact_feval=False, optimizer='bfgs', max_iters=1000,
                  optimize_restarts=5, sparse=False, num_inducing=10, verbose=True, ARD=False, Gower=False,
-                 space=None, device=0, parallel_restarts=False, device_acquisitions=False, incremental=False):
+                 space=None, device=0, parallel_restarts=False, device_acquisitions=False, incremental=False,
+                 lockstep_restarts=False):
         if sparse and incremental:
             raise ValueError("incremental appends to the exact model's factor: not available with sparse=True")
         if device_acquisitions and not sparse:
@@ -60,13 +66,16 @@ class GPModel(BOModel):
                              "is always scored on the device)")
         if sparse and parallel_restarts:
             raise ValueError("parallel_restarts runs the exact model's batched restarts: not available with sparse=True")
+        if lockstep_restarts and not sparse:
+            raise ValueError("lockstep_restarts selects the sparse model's batched restarts: it needs sparse=True (the exact "
+                             "model's are parallel_restarts)")
         if sparse and Gower and space is not None:
             raise NotImplementedError("the sparse GP does not take the Gower kernel")
         vars(self).update(kernel=kernel, noise_var=noise_var, exact_feval=exact_feval, optimizer=optimizer,
                           max_iters=max_iters, optimize_restarts=optimize_restarts, sparse=sparse,
                           num_inducing=num_inducing, verbose=verbose, ARD=ARD, Gower=Gower, space=space, device=device,
                           parallel_restarts=parallel_restarts, device_acquisitions=bool(device_acquisitions),
-                          incremental=bool(incremental), model=None)
+                          incremental=bool(incremental), lockstep_restarts=bool(lockstep_restarts), model=None)
 
     @staticmethod
     def fromConfig(config):
@@ -112,7 +121,9 @@ class GPModel(BOModel):
         if self.optimize_restarts == 1:
             self.model.optimize(messages=False, ipython_notebook=False, **search)
         else:
-            if self.parallel_restarts:   # the restarts in lockstep, one gp_fit_grad_batch per round (GPRegression.optimize_restarts)
+            # the restarts in lockstep: one gp_fit_grad_batch per round (GPRegression.optimize_restarts), or, for the sparse
+            # model, one gp_sparse_fit_grad_batch (SparseGPRegression)
+            if self.parallel_restarts or self.lockstep_restarts:
                 search["parallel"] = True
             self.model.optimize_restarts(num_restarts=self.optimize_restarts, verbose=self.verbose, **search)
 
@@ -172,7 +183,7 @@ class GPModel(BOModel):
                        optimizer=self.optimizer, max_iters=self.max_iters, optimize_restarts=self.optimize_restarts,
                        sparse=self.sparse, num_inducing=self.num_inducing, verbose=self.verbose, ARD=self.ARD, Gower=self.Gower, space=self.space, device=self.device,
                        parallel_restarts=self.parallel_restarts, device_acquisitions=self.device_acquisitions,
-                       incremental=self.incremental)
+                       incremental=self.incremental, lockstep_restarts=self.lockstep_restarts)
         twin._create_model(self.model.X, self.model.Y)
         twin.updateModel(self.model.X, self.model.Y, None, None)
         return twin

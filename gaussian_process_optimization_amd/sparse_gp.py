@@ -6,7 +6,8 @@ Gaussian likelihood of variance 1), GPy/GPy/core/sparse_gp.py:41-119 (Z as the p
 posterior.py:225-248 (prediction through ``woodbury_inv``), GPy/GPy/core/gp.py:407-454 (``predictive_gradients`` over
 ``_predictive_variable = Z``).
 
-All numerics run on the device (include/gphip.h, "sparse GP"): ``gp_sparse_fit_grad`` once per objective evaluation,
+All numerics run on the device (include/gphip.h, "sparse GP"): ``gp_sparse_fit_grad`` once per objective evaluation -- or one
+``gp_sparse_fit_grad_batch`` per round of evaluations of all restarts, ``optimize_restarts(parallel=True)`` --,
 ``gp_sparse_predict`` per prediction.  This module is bookkeeping: the flat parameter vector [Z row-major, kern.variance,
 kern.lengthscale, Gaussian_noise.variance] with Z unconstrained, the Y normaliser, lazy refits.  Homoscedastic noise, certain
 inputs, no mean function; ``full_cov`` and posterior sampling are outside this path.
@@ -18,6 +19,9 @@ from .gp_regression import GPRegression
 from .parameterization import Param
 
 MAX_INDUCING = 2048     # GP_SPARSE_MAX_INDUCING (include/gphip.h)
+BATCH_MAX_R = 64                # gp_sparse_fit_grad_batch's limit on the members
+BATCH_MAX_BYTES = 16 << 30      # GP_SPARSE_BATCH_MAX_BYTES
+LOCKSTEP_MAX_INDUCING = MAX_INDUCING   # profiles/sparse_restarts_timing.txt excludes nothing (see _lockstep_applies)
 
 
 class Identity(object):
@@ -160,8 +164,45 @@ class SparseGPRegression(GPRegression):
     def _uses_gower(self):
         return False
 
+    def _batch_objective(self, xs):
+        """``_obj_grad`` for every row of ``xs`` from ONE gp_sparse_fit_grad_batch: each member's Z, variance, lengthscale(s) and
+        noise through the transforms (fixed / bounded noise included), the natural gradients back through the chain rule in the
+        order of ``flattened_parameters()`` (Z first).  A member whose ladders end without a factor is a wall (1e10, zero
+        gradient), as in ``_obj_grad``.  The resident inducing inputs and sparse fit are left alone."""
+        k, nls = xs.shape[0], self.kern.lengthscale.size
+        Z = np.empty((k, self.num_inducing, self.input_dim))
+        var, ls, noise = np.empty(k), np.empty((k, nls)), np.empty(k)
+        for j in range(k):
+            self.optimizer_array = xs[j]
+            Z[j] = self.Z_values
+            var[j], ls[j], noise[j] = float(self.kern.variance), self.kern.lengthscale.values, float(self.likelihood.variance)
+        (lml, _, _), (dv, dl, dn, dZ), status = self._h.sparse_fit_grad_batch(Z, var, ls, noise, self.max_jitter_tries)
+        f, g = np.empty(k), np.zeros_like(xs)
+        for j in range(k):
+            if status[j] != 0:
+                f[j] = 1e10
+                continue
+            self.optimizer_array = xs[j]     # (the priors and the chain-rule factors are taken at this member's parameters)
+            natural = [(self.Z, dZ[j].reshape(-1)), (self.kern.variance, dv[j]), (self.kern.lengthscale, dl[j]),
+                       (self.likelihood.variance, dn[j])]
+            f[j] = self._objective_value(lml[j])
+            g[j] = -self._transform_gradients(self._natural_with_priors(natural))
+        return f, g
+
     def _lockstep_applies(self, num_restarts):
-        return False      # the batched restart entry is the exact model's: the serial loop runs
+        """``optimize_restarts(parallel=True)`` runs the restarts in lockstep, one gp_sparse_fit_grad_batch per round of L-BFGS
+        steps, for 1..64 restarts of a non-empty optimiser vector whose batch buffers (``gp_sparse_batch_bytes``) stay within
+        GP_SPARSE_BATCH_MAX_BYTES; otherwise the serial loop runs.  LOCKSTEP_MAX_INDUCING would narrow it to the numbers of
+        inducing inputs at which profiles/sparse_restarts_timing.txt shows the R = 5 batch call faster than five single calls:
+        the record's rows "Mz 10 / 128 / 512 / 1024 / 2048, R 5" read 4.88x / 4.79x / 2.78x / 1.80x / 1.52x (N = 16384, D = 8), so
+        nothing up to the cap on Mz is excluded."""
+        if not (1 <= num_restarts <= BATCH_MAX_R and self.optimizer_array.size > 0):
+            return False
+        if self.num_inducing > LOCKSTEP_MAX_INDUCING:
+            return False
+        self._push_params()      # (the byte count is taken over the data and parameters the context holds)
+        self._dirty = True
+        return self._h.sparse_batch_bytes(num_restarts, self.num_inducing) <= BATCH_MAX_BYTES
 
     def _device_group(self, devices):
         raise NotImplementedError("replica groups score the exact GP: outside the sparse path")

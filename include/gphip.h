@@ -507,7 +507,8 @@ int gp_merge_topk(int n, const double *vals, const int64_t *idxs, int sense, int
  * Always true fp64 ("emulate_fp64" does not apply).  GP_ERR_STATE: no data or no parameters, the Gower option on, an output
  * warp on, fit before gp_sparse_set_inducing, the other calls before a sparse fit.  The acquisitions have sparse twins below
  * (gp_sparse_acq*, gp_sparse_*_rows: a candidate table, a cached posterior and a one-location path of the sparse model's own);
- * the batched restarts, the sharded and group entries, the full covariance and posterior sampling stay exact-GP only. */
+ * restarts in lockstep have a sparse entry of their own (gp_sparse_fit_grad_batch below); the exact model's batched restarts,
+ * the sharded and group entries, the full covariance and posterior sampling stay exact-GP only. */
 #define GP_SPARSE_MAX_INDUCING 2048
 /* The inducing inputs Z [Mz, D], row-major (SparseGP.__init__ / set_Z, GPy/GPy/core/sparse_gp.py:53,69-74).  Drops the sparse
  * fit.  Z survives gp_set_params and a gp_set_data of the same D (which drop the sparse fit only); a gp_set_data with another
@@ -525,6 +526,41 @@ int gp_sparse_fit(gp_t *gp, int maxtries, double *lml, double *jitter_kmm, doubl
  * formula also where the 1e-8 clamp is active; dZ [Mz, D] = gradients_X(dL_dKmm, Z) + gradients_X(dL_dKnm^T, Z, X).
  * The same inputs give the same bits on every call.  GP_ERR_ARG: P > 16. */
 int gp_sparse_fit_grad(gp_t *gp, int maxtries, double *lml, double *dvariance, double *dlengthscale, double *dnoise, double *dZ);
+/* gp_sparse_fit_grad for R members in ONE call: what the restarts of GPModel(sparse=True) in lockstep ask for
+ * (GPyOpt/GPyOpt/models/gpmodel.py:78-93 over sparse_gp.py:76-119), one call per round of L-BFGS steps.
+ * What a member computes: member r is gp_sparse_set_inducing(Z[r]) + gp_set_params(variance[r], lengthscale[r], noise[r]) +
+ * gp_sparse_fit_grad over the context's X, Y, kernel family and ard (nls = 1, or D with ard, from the last gp_set_params): VarDTC
+ * with both jitter ladders per member and beta = 1 / max(noise, 1e-8).  Z is [R, Mz, D], lengthscale [R, nls], dZ [R, Mz, D],
+ * dlengthscale [R, nls], everything else [R].
+ * Bits: member r's lml, jitter_kmm, jitter_b (those of gp_sparse_fit), dvariance, dlengthscale, dnoise and dZ are bitwise those
+ * of the single call, whatever R is, whatever slot the member is in and whatever the other members are: a launch over members
+ * runs the body of the single call's kernel (the same summation orders, fixed by constants and never by the grid, no float
+ * atomics), with the member as blockIdx.z / .y or the GEMM's batch index, and the GEMM takes the instance it picks for one
+ * member's tiles.  No launch of the sequence gives up the single call's bits at any accepted shape.  (woodbury_inv, which none of
+ * these outputs depends on, is not formed.)
+ * Status and failures: status[r] is 0, or the code gp_sparse_fit_grad returns for that member (a ladder that ended without a
+ * factor); its outputs are then NaN.  A failed member does not fail the call.
+ * Jitter ladders: in each ladder (Kmm, then B) only the members whose factorisation failed are factored again, alone with the
+ * other failed members; runs of consecutive members share launches.  One copy of the members' info words and one
+ * synchronisation per ladder round; the mean diagonal of B is fetched for failed members only.
+ * GP_ERR_ARG: R outside 1..64; Mz outside 1..GP_SPARSE_MAX_INDUCING; a null pointer; a non-positive variance, lengthscale or
+ * noise; P > 16; D and P beyond a workgroup's LDS in the gradient pass (as gp_sparse_fit_grad); more than
+ * GP_SPARSE_BATCH_MAX_BYTES of buffers (below).  GP_ERR_STATE: no data or no parameters, the Gower option on, an output warp on.
+ * Untouched state: the batch has buffers of its own, allocated at first use and owned by the context beside its other buffers.
+ * It reads or writes none of: the resident inducing inputs, the resident sparse fit (woodbury vector and inverse, lml, gradient
+ * weights), the sparse candidate table and its cached posterior, the cached sparse fmin, the exact model's factor, alpha, Ky^-1,
+ * candidates and results, the exact batch's buffers, or any validity flag.  It needs no prior gp_sparse_set_inducing.
+ * Always true fp64 ("emulate_fp64" does not apply).
+ * Memory: per member 2 (n + 128) n + 10 n^2 + 3 Npad n doubles and the small vectors, n = Mz rounded up to 128 -- 0.5 GB at
+ * N = 16384, Mz = 1024.  GP_SPARSE_BATCH_MAX_BYTES is a policy cap, not a measurement: 16 GiB is a sixteenth of the device's
+ * 288 GB, leaves the exact model, its candidates and several contexts their room beside it, and still takes 30 such members --
+ * six rounds' worth of GPyOpt's five restarts.  gp_sparse_batch_bytes reports what a call would allocate (the same checks of R
+ * and Mz, nothing allocated), so that a caller decides without restating the formula. */
+#define GP_SPARSE_BATCH_MAX_BYTES (16LL << 30)
+int gp_sparse_fit_grad_batch(gp_t *gp, int R, int64_t Mz, const double *Z, const double *variance, const double *lengthscale,
+                             const double *noise, int maxtries, double *lml, double *jitter_kmm, double *jitter_b,
+                             double *dvariance, double *dlengthscale, double *dnoise, double *dZ, int *status);
+int gp_sparse_batch_bytes(gp_t *gp, int R, int64_t Mz, int64_t *bytes);
 /* Posterior.woodbury_vector [Mz, P] (Cpsi1Vf, var_dtc.py:142,199) and woodbury_inv [Mz, Mz] = Lm^-T (I - B^-1) Lm^-1
  * (var_dtc.py:209-212) of the sparse fit; either may be NULL. */
 int gp_sparse_posterior(gp_t *gp, double *woodbury_vector, double *woodbury_inv);
