@@ -29,6 +29,8 @@ from . import input_warping
 from .input_warped_gp import InputWarpedGP, InputWarpedGPModel
 from . import warping_functions
 from .warped_gp import WarpedGP, WarpedGPModel
+from . import cost
+from .cost import CostModel
 from . import acquisitions
 from .acquisitions import (AcquisitionEI, AcquisitionLCB, AcquisitionMPI, AcquisitionBase, AcquisitionLP,
                            LocalPenalization, estimate_L, AcquisitionEI_MCMC, AcquisitionMPI_MCMC, AcquisitionLCB_MCMC,
@@ -50,4 +52,4 @@ __all__ = ["kern", "models", "methods", "likelihoods", "acquisitions", "GPRegres
            "InputWarpedGP", "InputWarpedGPModel", "input_warping", "WarpedGP", "WarpedGPModel", "warping_functions",
            "AcquisitionEI", "AcquisitionLCB", "AcquisitionMPI", "AcquisitionBase", "AcquisitionLP",
            "LocalPenalization", "estimate_L", "BayesianOptimization",
-           "Design_space", "AcquisitionOptimizer", "ShardedCandidates", "merge_best", "Standardize"]
+           "Design_space", "AcquisitionOptimizer", "ShardedCandidates", "merge_best", "Standardize", "cost", "CostModel"]

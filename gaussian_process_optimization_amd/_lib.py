@@ -19,6 +19,7 @@ c_int_p = ctypes.POINTER(ctypes.c_int)
 GP_KERNEL_RBF, GP_KERNEL_MATERN52 = 0, 1
 GP_KERNEL_MATERN32, GP_KERNEL_EXPONENTIAL = 2, 3
 GP_ACQ_EI, GP_ACQ_LCB, GP_ACQ_MPI = 0, 1, 2
+GP_ACQ_PER_COST = 0x100      # or-ed into a scoring call's type: the scores are divided by the resident cost surface
 GP_ERR_ARG, GP_ERR_HIP, GP_ERR_STATE, GP_ERR_RCCL, GP_ERR_NOT_PD_DIAG = -1, -2, -3, -4, -5
 
 # every symbol include/gphip.h declares: (name, restype, argtypes)
@@ -187,6 +188,10 @@ SIGNATURES = [
     ("gp_debug_gemm", ctypes.c_int, [_vp, ctypes.c_int, c_double_p, c_double_p, c_double_p, ctypes.c_int64, ctypes.c_int,
                                      ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
     ("gp_set_option", ctypes.c_int, [_vp, ctypes.c_char_p, ctypes.c_int64]),
+    ("gp_cost_set", ctypes.c_int, [_vp, c_double_p, ctypes.c_int64, c_double_p, ctypes.c_int, ctypes.c_int, ctypes.c_double,
+                                   c_double_p, ctypes.c_double, ctypes.c_double]),
+    ("gp_cost_info", ctypes.c_int, [_vp, c_int64_p]),
+    ("gp_cost_rows", ctypes.c_int, [_vp, _vp, ctypes.c_int64, _vp, _vp]),
 ]
 
 _lib = None
@@ -307,6 +312,7 @@ class Handle(object):
         self.h = h
         self.device = int(device)
         self.sparse_M = 0      # rows of the sparse model's candidate table (sparse_set_candidates); 0: the library refuses to score
+        self.cost_key = None   # whose cost surface the handle holds: set by the caller of cost_set, dropped with the surface
 
     def close(self):
         if getattr(self, "h", None):
@@ -327,6 +333,8 @@ class Handle(object):
             raise ValueError("X and Y row counts differ")
         check(self.lib, self.lib.gp_set_data(self.h, dptr(X), dptr(Y), X.shape[0], X.shape[1], Y.shape[1]),
               "gp_set_data")
+        if getattr(self, "D", X.shape[1]) != X.shape[1]:
+            self.cost_key = None       # the library drops a cost surface of another width
         self.N, self.D, self.P = X.shape[0], X.shape[1], Y.shape[1]
 
     def set_params(self, kernel, ard, variance, lengthscale, noise):
@@ -1027,6 +1035,48 @@ class Handle(object):
 
     acq_rows = _acq_rows_entry("gp_acq_rows", """Negated acquisition [M, 1] (and its gradient [M, D]); ``lp`` = (transform, Xb, r_x0,
         s_x0) adds the local penalisation, in which case the value comes back 1-D as AcquisitionLP returns it.""")
+
+    # -- the cost surface of cost-aware EI / MPI (include/gphip.h, gp_cost_*) ---------------------------------------------
+    def cost_set(self, Xc, alpha, kernel, ard, variance, lengthscale, shift=0.0, scale=1.0, key=None):
+        """Make (Xc [Nc, D], alpha [Nc], kernel parameters, normaliser) the handle's cost surface -- a copy: nothing of the
+        cost GP is kept; ``Xc=None`` clears it.  ``key`` is remembered as ``cost_key`` (the routes' staleness check)."""
+        if Xc is None:
+            check(self.lib, self.lib.gp_cost_set(self.h, None, 0, None, 0, 0, 1.0, None, 0.0, 1.0), "gp_cost_set")
+            self.cost_key = None
+            return
+        Xc = as_f64(Xc, 2)
+        alpha = as_f64(np.ravel(alpha), 1)
+        ls = as_f64(np.atleast_1d(lengthscale), 1)
+        D = getattr(self, "D", None)
+        if D is None:
+            raise RuntimeError("gp_cost_set: set_data first (the surface has the handle's D columns)")
+        if Xc.shape[1] != D:
+            raise ValueError("gp_cost_set: the surface has %d columns, the handle has %d" % (Xc.shape[1], D))
+        if alpha.size != Xc.shape[0] or ls.size != (D if ard else 1):
+            raise ValueError("gp_cost_set: expected alpha [%d] and lengthscale [%d]; got %s, %s"
+                             % (Xc.shape[0], D if ard else 1, alpha.shape, ls.shape))
+        self.cost_key = None
+        check(self.lib, self.lib.gp_cost_set(self.h, dptr(Xc), Xc.shape[0], dptr(alpha), int(kernel), int(bool(ard)),
+                                             float(variance), dptr(ls), float(shift), float(scale)), "gp_cost_set")
+        self.cost_key = key
+
+    def cost_info(self):
+        n = ctypes.c_int64(0)
+        check(self.lib, self.lib.gp_cost_info(self.h, ctypes.byref(n)), "gp_cost_info")
+        return n.value
+
+    def cost_rows(self, Xs, grad=False):
+        """log cost [M] of the resident surface at the rows of ``Xs`` and, with ``grad``, its x-gradient [M, D]."""
+        Xs = as_f64(Xs, 2)
+        if Xs.shape[1] != self.D:
+            raise ValueError("locations have %d columns, the handle has %d" % (Xs.shape[1], self.D))
+        M = Xs.shape[0]
+        logc = np.empty(M)
+        dlogc = np.empty((M, self.D)) if grad else None
+        rc = self.lib.gp_cost_rows(self.h, Xs.ctypes.data, M, logc.ctypes.data, dlogc.ctypes.data if grad else None)
+        if rc:
+            check(self.lib, rc, "gp_cost_rows")
+        return (logc, dlogc) if grad else logc
 
     def rows_stats(self):
         a, b = ctypes.c_int64(), ctypes.c_int64()

@@ -9,7 +9,9 @@ libgphip on the whole candidate block at once: values (``gp_acq``), values + x-g
 (``gp_acq_argbest`` / ``gp_acq_topk``), the penalised batch acquisition and its gradient (``gp_acq_lp`` / ``gp_acq_lp_grad``).
 A sparse ``GPModel`` built with ``device_acquisitions=True`` takes the same route through the sparse twins (``gp_sparse_acq``,
 ``gp_sparse_acq_argbest`` / ``_topk``, ``gp_sparse_acq_rows``) over a candidate table of the sparse model's own.
-Anything else (a foreign ``BOModel``, a cost model, string constraints, several outputs) is scored by ``_Rule`` below from
+EI and MPI under the evaluation-time cost model (``cost.CostModel`` over our exact ``GPModel``) stay on those routes: the handle
+holds a snapshot of the cost GP's posterior mean (``gp_cost_set``) and divides the scores itself (``GP_ACQ_PER_COST``).
+Anything else (a foreign ``BOModel``, a user's cost function, string constraints, several outputs) is scored by ``_Rule`` below from
 ``model.predict[_withGradients]``: each acquisition is one rule giving its value and its two partial derivatives with respect
 to the posterior mean and standard deviation, and every class shares the chain rule built on them.
 
@@ -20,6 +22,7 @@ import numpy as np
 from scipy.special import erfc, log_ndtr, ndtr
 
 from . import _lib
+from .cost import CostModel, constant_cost_withGradients
 from .gpmodel import GPModel, GPModel_MCMC
 
 _FEW_ROWS = 8            # up to this many locations go down as ONE gp_*_rows call (include/gphip.h): the L-BFGS inner loop
@@ -39,12 +42,6 @@ def get_quantiles(acquisition_par, fmin, m, s):
     pdf = np.exp(-0.5 * z ** 2) / _ROOT_2PI
     cdf = 0.5 * erfc(-z / _ROOT_2)
     return pdf, cdf, z
-
-
-def constant_cost_withGradients(x):
-    """Unit cost and zero cost gradient (core/task/cost.py:76)."""
-    rows = x.shape[0]
-    return np.ones((rows, 1)), np.zeros(x.shape)
 
 
 class _Unconstrained(object):
@@ -124,6 +121,50 @@ def _unit_cost_unconstrained(acq):
     return not (constrained is not None and constrained())
 
 
+def _unconstrained(acq):
+    constrained = getattr(acq.space, "has_constraints", None)
+    return not (constrained is not None and constrained())
+
+
+def _device_cost(acq):
+    """The ``CostModel`` whose cost the device can divide by, or None: ``cost_withGradients`` is the bound
+    ``_cost_gp_withGradients`` of a ``CostModel`` whose cost GP is our exact ``GPModel`` -- fitted, one output, no Gower kernel, on
+    the scored model's device.  (A user's callable is not one, whatever it computes: it keeps the host rule.)"""
+    fn = acq.cost_withGradients
+    cm = getattr(fn, "__self__", None)
+    if not isinstance(cm, CostModel) or getattr(fn, "__func__", None) is not CostModel._cost_gp_withGradients:
+        return None
+    m = getattr(cm, "cost_model", None)
+    if type(m) is not GPModel or m.sparse or m.model is None or not cm._fitted():
+        return None
+    if m.model.output_dim != 1 or m._gower() or getattr(m.model.kern, "Gower", False):
+        return None
+    if not hasattr(m.model.kern, "_kernel_id") or m.device != getattr(acq.model, "device", None):
+        return None
+    return cm
+
+
+def _cost_ok(acq):
+    """Unit cost or a device cost, and no constraints: what the device routes ask of the acquisition besides its model."""
+    return _unit_cost_unconstrained(acq) or (_device_cost(acq) is not None and _unconstrained(acq))
+
+
+def _sync_cost(acq, h):
+    """Before a flagged call on handle ``h`` (its data set): upload the cost surface unless ``h`` holds this cost model's
+    current generation.  The surface is the cost GP's inputs, alpha, kernel parameters and normaliser."""
+    cm = _device_cost(acq)
+    if cm is None:
+        return
+    key = (id(cm), cm.generation)
+    if h.cost_key == key:
+        return
+    gp = cm.cost_model.model
+    gp._ensure_fit()
+    k = gp.kern
+    shift, scale = _normaliser(gp)
+    h.cost_set(gp.X, gp._h.alpha(), k._kernel_id, k.ARD, float(k.variance), k.lengthscale.values, shift, scale, key=key)
+
+
 def _normaliser(gp):
     """(mean, std) the targets of ``gp`` were normalised with: the ``y_mean`` / ``y_std`` of every scoring call."""
     nz = gp.normalizer
@@ -147,6 +188,8 @@ class _Route(object):
             return self.values(acq, x, grad, lp)
         gp = acq.model.model
         gp._ensure_fit()
+        if acq._per_cost:
+            _sync_cost(acq, gp._h)
         shift, scale = _normaliser(gp)
         return getattr(gp._h, self.rows)(x, acq._acq_id, acq._par(), acq._fmin(), shift, scale, grad=grad, lp=lp)
 
@@ -166,11 +209,16 @@ class _ExactRoute(_Route):
             gp._predict_resident(True)     # GPModel.predict: with_noise=True (gpmodel.py:102)
         else:
             gp._stage(x)
+        if acq._per_cost:
+            _sync_cost(acq, gp._h)
         return (gp._h, acq._fmin()) + _normaliser(gp)
 
     @staticmethod
     def _group(acq, x, devices):
         """``x`` split over the replicas of the model on ``devices``: the group, fmin, normaliser mean / std."""
+        if acq._per_cost:
+            raise NotImplementedError("replica groups score without a cost model: not available with cost_withGradients="
+                                      "'evaluation_time'")
         gp = acq.model.model
         grp = gp._device_group(devices)
         grp.set_candidates(np.atleast_2d(np.asarray(x, dtype=float)))
@@ -210,6 +258,8 @@ class _SparseRoute(_Route):
         if devices is not None:
             gp._device_group(devices)      # replica groups score the exact GP: NotImplementedError
         gp._stage_table(np.atleast_2d(np.asarray(x, dtype=float)))
+        if acq._per_cost:
+            _sync_cost(acq, gp._h)
         return (gp._h, acq._fmin()) + _normaliser(gp)
 
     def values(self, acq, x, grad, lp):
@@ -243,8 +293,17 @@ class AcquisitionBase(object):
 
     # ---- what the rule needs ---------------------------------------------------------------------------------------
     @property
+    def _per_cost(self):
+        """The device divides this acquisition's scores by the cost: EI or MPI (LCB takes no cost) under a device cost."""
+        return (self.cost_withGradients is not constant_cost_withGradients and self._rule is not None
+                and self._rule.device_id != _lib.GP_ACQ_LCB and _device_cost(self) is not None)
+
+    @property
     def _acq_id(self):
-        return None if self._rule is None else self._rule.device_id
+        """The ``type`` of the scoring calls: the rule, with GP_ACQ_PER_COST under a device cost."""
+        if self._rule is None:
+            return None
+        return self._rule.device_id | _lib.GP_ACQ_PER_COST if self._per_cost else self._rule.device_id
 
     def _par(self):
         raise NotImplementedError
@@ -254,12 +313,13 @@ class AcquisitionBase(object):
 
     # ---- device route ----------------------------------------------------------------------------------------------
     def _device_ok(self):
-        """True when libgphip can score this acquisition by itself: our exact GPModel, one output, unit cost, no constraints.
+        """True when libgphip can score this acquisition by itself: our exact GPModel, one output, unit cost or a device cost
+        (``_device_cost``), no constraints.
         (The device entries score the exact posterior: a sparse model takes the sparse route or the host rule.)"""
         m = self.model
         if self._rule is None or not isinstance(m, GPModel) or m.model is None or getattr(m, "sparse", False):
             return False
-        return _unit_cost_unconstrained(self) and m.model.output_dim == 1
+        return _cost_ok(self) and m.model.output_dim == 1
 
     def _sparse_device_ok(self):
         """True when libgphip scores this acquisition over the SPARSE posterior (gp_sparse_acq*): our GPModel with ``sparse=True``
@@ -269,7 +329,7 @@ class AcquisitionBase(object):
             return False
         if not (getattr(m, "sparse", False) and getattr(m, "device_acquisitions", False)):
             return False
-        return _unit_cost_unconstrained(self) and m.model.output_dim == 1
+        return _cost_ok(self) and m.model.output_dim == 1
 
     def _route(self):
         """THE choice of where this acquisition is scored: the exact route, the sparse route, or None (the host rule)."""
@@ -407,13 +467,19 @@ class _IntegratedAcquisition(AcquisitionBase):
     def _ens_ok(self):
         if not isinstance(self.model, GPModel_MCMC) or self.model.model is None or self.model.hmc_samples is None:
             return False
-        return _unit_cost_unconstrained(self)
+        return _cost_ok(self)
+
+    def _ens_handle(self):
+        h = self.model.model._h
+        if self._per_cost:
+            _sync_cost(self, h)
+        return h
 
     def acquisition_function(self, x):
         if not self._ens_ok():
             return super().acquisition_function(x)
         x = np.atleast_2d(np.asarray(x, dtype=float))
-        h = self.model.model._h
+        h = self._ens_handle()
         if x.shape[0] <= _FEW_ROWS:
             return h.ens_acq_rows(x, self._acq_id, self._par())
         h.set_candidates(x)
@@ -423,7 +489,7 @@ class _IntegratedAcquisition(AcquisitionBase):
         if not self._ens_ok():
             return super().acquisition_function_withGradients(x)
         x = np.atleast_2d(np.asarray(x, dtype=float))
-        h = self.model.model._h
+        h = self._ens_handle()
         parts = [h.ens_acq_rows(x[i:i + _FEW_ROWS], self._acq_id, self._par(), grad=True) for i in range(0, x.shape[0], _FEW_ROWS)]
         return np.vstack([p[0] for p in parts]), np.vstack([p[1] for p in parts])
 
@@ -432,7 +498,7 @@ class _IntegratedAcquisition(AcquisitionBase):
             if devices is not None:
                 raise NotImplementedError("replica groups score one hyper-parameter vector: not available with GPModel_MCMC")
             return _pick(self.acquisition_function(x)[:, 0], sense)
-        h = self.model.model._h
+        h = self._ens_handle()
         h.set_candidates(np.atleast_2d(np.asarray(x, dtype=float)))
         return h.ens_acq_argbest(self._acq_id, self._par(), sense)
 
@@ -571,6 +637,8 @@ class AcquisitionLP(AcquisitionBase):
         """The route of the base acquisition, when it scores this model and the transform is one the device knows."""
         base = self.acq
         if base is None or base.model is not self.model or self.transform not in ('none', 'softplus'):
+            return None
+        if base._per_cost:      # the device penalises the base acquisition at unit cost: a base with a cost keeps the host rule
             return None
         return base._route()
 

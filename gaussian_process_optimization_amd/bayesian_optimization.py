@@ -21,6 +21,7 @@ from scipy import optimize as _sopt
 from . import kern as _kern
 from .acquisitions import (AcquisitionEI, AcquisitionLCB, AcquisitionMPI, AcquisitionLP, LocalPenalization, AcquisitionEI_MCMC,
                            AcquisitionMPI_MCMC, AcquisitionLCB_MCMC, AcquisitionEntropySearch)
+from .cost import CostModel
 from .entropy_search import AffineInvariantEnsembleSampler
 from .gpmodel import GPModel
 from .input_warped_gp import InputWarpedGPModel
@@ -324,6 +325,11 @@ def kernel_from_name(name, input_dim, ARD=False):
     return KERNEL_NAMES[name](input_dim, ARD=ARD)
 
 
+def _clock():
+    """Wall-clock seconds: what the evaluation times of ``cost_withGradients='evaluation_time'`` are differences of."""
+    return time.time()
+
+
 class BayesianOptimization(object):
     """GPyOpt.methods.BayesianOptimization for model_type='GP' and 'input_warped_GP' (bayesian_optimization.py:76-170)."""
 
@@ -368,6 +374,9 @@ class BayesianOptimization(object):
             ARD=kwargs.get('ARD', False), Gower=kwargs.get('Gower', False), space=self.space, device=device,
             parallel_restarts=kwargs.get('parallel_restarts', False), incremental=kwargs.get('incremental', False))
         self.acquisition_optimizer = AcquisitionOptimizer(self.space, acquisition_optimizer_type, parallel=parallel_anchors)
+        # core/bo.py:31: the cost the acquisitions divide by; 'evaluation_time' fits a GP to the logarithm of the evaluation times
+        self.cost = CostModel(cost_withGradients, device=device)
+        cost_withGradients = self.cost.cost_withGradients
         # arguments_manager.py:42-75
         jitter = kwargs.get('acquisition_jitter', 0.01)
         weight = kwargs.get('acquisition_weight', 2)
@@ -429,14 +438,27 @@ class BayesianOptimization(object):
         if Y is None:
             if f is None:
                 raise ValueError("f=None requires X and Y")
-            Y = self._evaluate(self.X)
+            Y = self._evaluate(self.X, record_cost=True)
         self.Y = np.asarray(Y, dtype=float).reshape(-1, 1)
         self.num_acquisitions = 0
         self.suggested_sample = None
         self.cum_time = 0.0
 
-    def _evaluate(self, X):
-        Y = np.asarray(self.f(X), dtype=float).reshape(-1, 1)
+    def _evaluate(self, X, record_cost=False):
+        """The objective at the rows of ``X``.  Under ``cost_withGradients='evaluation_time'`` one row at a time, each call
+        timed (core/task/objective.py:64-77); with ``record_cost`` the times then go to the cost model (bo.py:120-122,195-196)."""
+        if self.cost.cost_type != 'evaluation_time':
+            Y = np.asarray(self.f(X), dtype=float).reshape(-1, 1)
+            return -Y if self.maximize else Y
+        X = np.atleast_2d(X)
+        values, costs = [], []
+        for row in X:
+            started = _clock()
+            values.append(np.asarray(self.f(np.atleast_2d(row)), dtype=float).reshape(-1, 1))
+            costs.append(_clock() - started)
+        if record_cost:
+            self.cost.update_cost_model(X, costs)
+        Y = np.vstack(values)
         return -Y if self.maximize else Y
 
     # -- core/bo.py:236-254 ----------------------------------------------------------------
@@ -477,7 +499,7 @@ class BayesianOptimization(object):
                                   np.sqrt(np.sum((self.X[-1, :] - self.X[-2, :]) ** 2)) <= eps):
                 break
             x = self._compute_next_evaluations()
-            y = self._evaluate(x)
+            y = self._evaluate(x, record_cost=True)
             self.X = np.vstack((self.X, x))
             self.Y = np.vstack((self.Y, y))
             self.num_acquisitions += 1

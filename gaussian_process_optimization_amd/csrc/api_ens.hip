@@ -221,7 +221,9 @@ static int ens_passes(gp_ctx *g, const double *Xs, int M, int want_grad, int inc
     // D = GP_MAX_D); a location's bits do not depend on its company, so the split is invisible in the results
     return rows_passes(g, en.pass, Xs, M, std::min(ROWS_MAX_M, ROWS_MAX_XS / g->D),
                        [&](const RowsX &rx, const PassReport &r, unsigned *arrivals) {
-                           launch_ens_rows(g->s, t, en.S, rx, g->dX, g->N, g->Npad, want_grad, include_noise, acq_on, type, par, r);
+                           launch_ens_rows(g->s, t, en.S, rx, g->dX, g->N, g->Npad, want_grad, include_noise, acq_on, acq_base(type), par, r);
+                           // the cost does not depend on the member: the quotient goes under the average, behind the pass
+                           if (acq_on && acq_per_cost(type)) cost_divide_block(g, rx, want_grad != 0, r.out, rows_layout(rx.M));
                            if (post)
                                HIPCHK(hipMemcpyAsync(post->data(), t.post, sizeof(double) * en.S * ENS_POST_STRIDE, hipMemcpyDeviceToHost, g->s));
                            arrivals[0] = rows_finish_grid(g->N);
@@ -257,9 +259,9 @@ extern "C" int gp_ens_predict_rows(gp_t *g, const double *Xs, int64_t M, int inc
     });
 }
 
-static int ens_check_acq(int type) {
-    if (type < GP_ACQ_EI || type > GP_ACQ_MPI) return fail(GP_ERR_ARG, "unknown acquisition %d", type);
-    return 0;
+static int ens_check_acq(const gp_ctx *g, int type) {
+    if (acq_base(type) < GP_ACQ_EI || acq_base(type) > GP_ACQ_MPI) return fail(GP_ERR_ARG, "unknown acquisition %d", type);
+    return check_per_cost(g, type, false);
 }
 
 extern "C" int gp_ens_acq_rows(gp_t *g, const double *Xs, int64_t M, int type, double par, double *out, double *dout) {
@@ -267,7 +269,7 @@ extern "C" int gp_ens_acq_rows(gp_t *g, const double *Xs, int64_t M, int type, d
     int rc;
     if ((rc = ens_ready(g))) return rc;
     if (M < 1 || M > ROWS_WIDE_M) return fail(GP_ERR_ARG, "gp_ens_acq_rows takes 1 <= M <= %d locations", ROWS_WIDE_M);
-    if ((rc = ens_check_acq(type))) return rc;
+    if ((rc = ens_check_acq(g, type))) return rc;
     const int D = g->D;
     return ens_passes(g, Xs, (int)M, dout != nullptr, 1, 1, type, par, nullptr, [&](int m0, int mc, const double *o) {   // with_noise, gpmodel.py:271
         const int MV = rows_layout(mc);
@@ -284,7 +286,7 @@ static int ens_table_scores(gp_ctx *g, int type, double par) {
     EnsState &en = g->ens;
     if (g->M < 1) return fail(GP_ERR_STATE, "gp_set_candidates first");
     int rc;
-    if ((rc = ens_check_acq(type))) return rc;
+    if ((rc = ens_check_acq(g, type))) return rc;
     const long M = g->M, N = g->N, Npad = g->Npad, S = en.S;
     const int nt = (int)(Npad / GP_TILE);
     const long chunk = std::min<long>(GP_ENS_TABLE_CHUNK, round_up(M, GP_TILE));
@@ -301,8 +303,9 @@ static int ens_table_scores(gp_ctx *g, int type, double par) {
         o.sB = Npad * Npad;
         gemm(g, g->s, 0, en.dW, Npad, en.dKx, Npad, en.dLi, Npad, 1, (int)Npad, TileSet{0, (int)(mcpad / GP_TILE), 0, nt, 0}, o);
         launch_ens_table_reduce(g->s, en.dKx, en.dW, chunk, Npad, N, en.dAlpha, Npad, (const KernParams *)en.dKp.p, ens_noise(g),
-                                ens_fmin(g), (int)S, type, par, mc, en.dAcq + m0);
+                                ens_fmin(g), (int)S, acq_base(type), par, mc, en.dAcq + m0);
     }
+    if (acq_per_cost(type)) return cost_divide(g, g->dXs, M, false, en.dAcq, nullptr);   // after the average over the members
     return 0;
 }
 

@@ -261,6 +261,20 @@ struct EsState {
     DevBuf<double> dRowsPart;  // gp_es_acq_rows: the workgroups' shares of V_R w and |w|^2 (es_rows_part_elems)
 };
 
+// The cost surface (api_cost.hip): a snapshot of a cost GP's posterior mean -- inputs over lengthscale, alpha, kernel parameters,
+// normaliser -- in buffers of the context's own; nothing of the handle it came from is kept.  Nc > 0 while one is resident.  The
+// fit, the posterior caches and the candidates do not depend on it; the cached logc of a resident table does (gp_ctx::cost_tab).
+struct CostState {
+    long Nc = 0;
+    int ld = 0;                // doubles between two rows of dXcs: max(D, 8), zeros beyond D
+    KernParams kp{};           // kernel, D, variance, lengthscales of the cost GP (never Gower)
+    double shift = 0.0, scale = 1.0;   // m_c = shift + scale K alpha: the cost model's output normaliser
+    DevBuf<double> dXcs, dAlpha;       // [Nc, ld], [Nc]
+    DevBuf<double> dTabLogc;   // logc of the resident table gp_ctx::cost_tab names
+    DevBuf<double> dWork;      // rows not in a resident table: locations [M, D], logc [M], dlogc [M, D]; dlogc of a table
+    DevBuf<double> dPart;      // the chunks' partial sums of a values-only table launch cut along the surface (cost.hip)
+};
+
 struct gp_ctx {
     int device = 0;
     long lds_per_wg = 0;           // hipDeviceAttributeMaxSharedMemoryPerBlock of the device (gp_create)
@@ -305,6 +319,8 @@ struct gp_ctx {
     bool invp_valid = false;   // dInvP holds the inverted diagonal panels of the factor, invp_W tiles wide
     bool lr_valid = false;     // dLr belongs to the current factor
     bool predicted = false;    // dMean / dVar hold the posterior of the resident candidates (noise as predicted_noise), dT / dT2 what its solve left
+    int cost_tab = 0;          // cost.dTabLogc holds logc of: 0 nothing, 1 the candidates in dXs, 2 the sparse model's table (sp.dTab);
+                               // dropped where either table or the surface changes (gp_set_candidates*, gp_sparse_set_candidates, gp_cost_set)
     // candidates
     long M = 0;
     DevBuf<double> dXs;
@@ -417,6 +433,7 @@ struct gp_ctx {
     SparseState sp;     // the sparse model (api_sparse.hip)
     EnsState ens;       // the ensemble (api_ens.hip)
     EsState es;         // entropy search: representers and belief (api_es.hip)
+    CostState cost;     // the cost surface of the flagged scoring calls (api_cost.hip)
     bool dead = false;  // gp_shutdown ran: the device's streams are gone, only gp_destroy is still valid
 };
 
@@ -641,9 +658,19 @@ using ChunkHook = std::function<int(long, long, long)>;
 int run_predict(gp_ctx *g, int include_noise, bool tiles_only = false, const ChunkHook *chunk = nullptr);   // tiles_only: never the small-M path (the caller uses dT2 as a padded tile operand)
 int ensure_out(gp_ctx *g);
 // What to score, as the C boundary got it: the base acquisition, and the local penaliser on top of it (the batch on the HOST)
+// type: GP_ACQ_*, with GP_ACQ_PER_COST or-ed in when the scores are to be divided by the resident cost surface
 struct AcqSpec { int type; double par, fmin, y_mean, y_std; };
 struct LpSpec { int transform; const double *Xb; int nb; const double *r0, *s0; };
-int check_acq(const gp_ctx *g, const AcqSpec &a);   // a single-output model, a known acquisition
+static inline int acq_base(int type) { return type & ~GP_ACQ_PER_COST; }            // the acquisition itself
+static inline bool acq_per_cost(int type) { return (type & GP_ACQ_PER_COST) != 0; }
+// a single-output model, a known acquisition; with the flag: EI or MPI, a resident surface, no penaliser (lp null)
+int check_acq(const gp_ctx *g, const AcqSpec &a, const LpSpec *lp = nullptr);
+int check_per_cost(const gp_ctx *g, int type, bool lp);   // the flag's own conditions (no-op without it)
+// api_cost.hip: the quotient behind the scores.  cost_divide: M rows at X on the device, acq [M] (and dacq [M, D] with grad) in
+// place; a resident table (X == dXs or sp.dTab) pays the values' pass once per table and surface.  cost_divide_block: the
+// locations of a fused rows pass, applied to its pinned result block (laid out for MV locations) behind the pass on the stream
+int cost_divide(gp_ctx *g, const double *X, long M, bool grad, double *acq, double *dacq);
+void cost_divide_block(gp_ctx *g, const RowsX &rx, bool grad, double *blk, int MV);
 int check_lp(const LpSpec &lp);                     // transform 0 / 1, 0 <= nb <= GP_LP_MAX_NB, a batch where nb > 0
 int check_sense(int sense);
 int check_k(int k);

@@ -15,6 +15,7 @@ extern "C" int gp_set_candidates(gp_t *g, const double *Xs, int64_t M) {
     HIPCHK(hipMemcpy(g->dXs, Xs, sizeof(double) * M * g->D, hipMemcpyHostToDevice));
     g->M = M;
     g->predicted = false;
+    if (g->cost_tab == 1) g->cost_tab = 0;
     return 0;
 }
 
@@ -125,9 +126,19 @@ extern "C" int gp_predict(gp_t *g, int include_noise, double *mean, double *var)
 }
 
 // ---- the checks of what a caller asks to have scored, one each --------------------------------------------------------------
-int check_acq(const gp_ctx *g, const AcqSpec &a) {
+int check_acq(const gp_ctx *g, const AcqSpec &a, const LpSpec *lp) {
     if (g->P != 1) return fail(GP_ERR_ARG, "acquisitions need P == 1");
-    if (a.type < GP_ACQ_EI || a.type > GP_ACQ_MPI) return fail(GP_ERR_ARG, "unknown acquisition %d", a.type);
+    const int base = acq_base(a.type);
+    if (base < GP_ACQ_EI || base > GP_ACQ_MPI) return fail(GP_ERR_ARG, "unknown acquisition %d", a.type);
+    return check_per_cost(g, a.type, lp != nullptr);
+}
+// GP_ACQ_PER_COST: improvement per unit of cost is EI's and MPI's (LCB.py ignores the cost, LP.py:27 builds the penalised
+// acquisition with unit cost), over a surface that is there
+int check_per_cost(const gp_ctx *g, int type, bool lp) {
+    if (!acq_per_cost(type)) return 0;
+    if (acq_base(type) == GP_ACQ_LCB) return fail(GP_ERR_ARG, "GP_ACQ_PER_COST: LCB takes no cost");
+    if (lp) return fail(GP_ERR_ARG, "GP_ACQ_PER_COST: the penalised acquisition takes no cost");
+    if (g->cost.Nc < 1) return fail(GP_ERR_ARG, "GP_ACQ_PER_COST without a cost surface (gp_cost_set)");
     return 0;
 }
 int check_lp(const LpSpec &lp) {
@@ -170,9 +181,10 @@ int argbest_read(gp_ctx *g, const double *v, long n, int sense, int64_t *idx, do
 // posterior: each model's preamble and its route to one come first.  Not drained.
 int score_rows(gp_ctx *g, const AcqSpec &a, const LpSpec *lp, bool grad, const ScoreRows &r) {
     if (grad)
-        launch_acq_grad(g->s, a.type, a.par, a.fmin, a.y_mean, a.y_std, r.mean, r.var, r.dm, r.dv, r.M, g->D, r.acq, r.dacq);
+        launch_acq_grad(g->s, acq_base(a.type), a.par, a.fmin, a.y_mean, a.y_std, r.mean, r.var, r.dm, r.dv, r.M, g->D, r.acq, r.dacq);
     else
-        launch_acq(g->s, a.type, a.par, a.fmin, a.y_mean, a.y_std, r.mean, r.var, r.M, r.acq);
+        launch_acq(g->s, acq_base(a.type), a.par, a.fmin, a.y_mean, a.y_std, r.mean, r.var, r.M, r.acq);
+    if (acq_per_cost(a.type)) return cost_divide(g, r.X, r.M, grad, r.acq, r.dacq);   // (never with lp: check_per_cost)
     if (!lp) return 0;
     int rc;
     LpBatch b;
@@ -252,7 +264,7 @@ extern "C" int gp_fmin(gp_t *g, double *fmin) {
 int run_acq(gp_ctx *g, const AcqSpec &a, const LpSpec *lp, bool grad) {
     int rc;
     if (lp && (rc = check_lp(*lp))) return rc;
-    if ((rc = check_acq(g, a))) return rc;
+    if ((rc = check_acq(g, a, lp))) return rc;
     if ((rc = ensure_out(g))) return rc;
     if (grad && (rc = run_predict_grad(g))) return rc;
     if (!g->predicted || g->predicted_noise != 1)

@@ -73,8 +73,8 @@ int rows_lp_batch(gp_ctx *g, const LpSpec &lp, LpBatch *b) {
 }
 
 RowsAcq rows_acq(const AcqSpec &a, const LpSpec *lp, const LpBatch &b) {   // (RowsAcq: on, the base acquisition, lp, the penaliser)
-    if (!lp) return RowsAcq{1, a.type, a.par, a.fmin, a.y_mean, a.y_std, 0, 0, 0, nullptr, nullptr, nullptr};
-    return RowsAcq{1, a.type, a.par, a.fmin, a.y_mean, a.y_std, 1, lp->transform, lp->nb, b.X, b.r, b.s};
+    if (!lp) return RowsAcq{1, acq_base(a.type), a.par, a.fmin, a.y_mean, a.y_std, 0, 0, 0, nullptr, nullptr, nullptr};
+    return RowsAcq{1, acq_base(a.type), a.par, a.fmin, a.y_mean, a.y_std, 1, lp->transform, lp->nb, b.X, b.r, b.s};
 }
 
 // The exact model's passes through rows_passes (api_internal.h): rows_pass_width locations per pass.  launch(rx, w, r) puts a pass
@@ -107,7 +107,7 @@ static int rows_exact_passes(gp_ctx *g, const double *Xs, int M, const char *pha
 // The fused path over the inverse factor.  want_grad selects forward + backward + finish; otherwise forward + finish.
 // Results: mean / var / acq [M], dmdx / dvdx / dacq [M, D] (any may be null).
 static int rows_fused(gp_ctx *g, const double *Xs, int M, int include_noise, int want_grad, const RowsAcq &aq, double *mean,
-                      double *var, double *acq, double *dmdx, double *dvdx, double *dacq) {
+                      double *var, double *acq, double *dmdx, double *dvdx, double *dacq, bool per_cost = false) {
     int rc;
     if ((rc = ensure_linv(g))) return rc;
     return rows_exact_passes(
@@ -115,6 +115,7 @@ static int rows_fused(gp_ctx *g, const double *Xs, int M, int include_noise, int
         [&](const RowsX &rx, const RowsWork &w, const PassReport &r) {
             launch_rows(g->s, g->dLi, g->Npad, rx, g->kp, g->dX, g->N, g->dAlpha, want_grad, g->kp.variance,
                         include_noise ? g->noise : 0.0, aq, w, r, g->rows_nt < 0 ? (g->Npad > 8192 ? 1 : 0) : g->rows_nt);
+            if (per_cost) cost_divide_block(g, rx, want_grad != 0, r.out, rows_layout(rx.M));   // behind the pass, before the drain
             return rows_finish_grid(g->N);
         },
         [&](int m0, int mc, int MV, const double *o) { rows_unpack(o, MV, m0, mc, g->D, mean, var, acq, dmdx, dvdx, dacq); });
@@ -171,13 +172,13 @@ extern "C" int gp_acq_rows(gp_t *g, const double *Xs, int64_t M, int type, doubl
     const AcqSpec a{type, par, fmin, y_mean, y_std};
     const LpSpec batch{transform, Xb, nb, r_x0, s_x0}, *pen = lp ? &batch : nullptr;
     int rc;
-    if ((rc = check_acq(g, a))) return rc;
+    if ((rc = check_acq(g, a, pen))) return rc;
     if (pen && (rc = check_lp(*pen))) return rc;
     if (rows_fused_ok(g, M) && rows_use_factor(g)) {
         LpBatch b;
         if (pen && (rc = rows_lp_batch(g, *pen, &b))) return rc;
         return rows_fused(g, Xs, (int)M, 1, dout != nullptr, rows_acq(a, pen, b), nullptr, nullptr, out, nullptr, nullptr,
-                          dout);   // with_noise=True, gpmodel.py:102
+                          dout, acq_per_cost(type));   // with_noise=True, gpmodel.py:102
     }
     ++g->rows_fallback_calls;
     if ((rc = gp_set_candidates(g, Xs, M))) return rc;

@@ -400,6 +400,7 @@ extern "C" int gp_sparse_set_candidates(gp_t *g, const double *Xs, int64_t M) {
     HIPCHK(hipMemcpy(sp.dTab, Xs, sizeof(double) * M * g->D, hipMemcpyHostToDevice));
     sp.tM = M;
     sp.tab_post = sp.tab_grad = false;
+    if (g->cost_tab == 2) g->cost_tab = 0;
     return 0;
 }
 
@@ -407,7 +408,7 @@ extern "C" int gp_sparse_set_candidates(gp_t *g, const double *Xs, int64_t M) {
 static int sparse_scoring(gp_ctx *g, const AcqSpec &a, const LpSpec *lp) {
     int rc;
     if ((rc = sparse_fitted(g))) return rc;
-    if ((rc = check_acq(g, a))) return rc;
+    if ((rc = check_acq(g, a, lp))) return rc;
     if (lp && (rc = check_lp(*lp))) return rc;
     if (g->sp.tM < 1) return fail(GP_ERR_STATE, "gp_sparse_set_candidates first");
     return 0;
@@ -504,7 +505,7 @@ static int sparse_rows_scratch(gp_ctx *g) {
 
 // mode as launch_sparse_rows.  Results: mean / var / acq [M], dmdx / dvdx / dacq [M, D] (any may be null).
 static int sparse_rows_fused(gp_ctx *g, const double *Xs, int M, int mode, int include_noise, const RowsAcq &aq, double *mean,
-                             double *var, double *acq, double *dmdx, double *dvdx, double *dacq) {
+                             double *var, double *acq, double *dmdx, double *dvdx, double *dacq, bool per_cost = false) {
     SparseState &sp = g->sp;
     int rc;
     if ((rc = sparse_rows_scratch(g))) return rc;
@@ -515,6 +516,7 @@ static int sparse_rows_fused(gp_ctx *g, const double *Xs, int M, int mode, int i
         [&](const RowsX &rx, const PassReport &r, unsigned *arrivals) {
             launch_sparse_rows(g->s, sp.dWinv, sp.Mzpad, sp.Mz, rx, g->kp, sp.dZs, wv, mode, g->kp.variance,
                                include_noise ? g->noise : 0.0, aq, sp.dRowsPart, r);
+            if (per_cost) cost_divide_block(g, rx, mode == 1, r.out, ROWS_WIDE_M);   // behind the pass, before the drain
             arrivals[0] = sparse_rows_grid(sp.Mz);
             return 0;
         },
@@ -571,13 +573,13 @@ extern "C" int gp_sparse_acq_rows(gp_t *g, const double *Xs, int64_t M, int type
     if (M < 1) return fail(GP_ERR_ARG, "M < 1");
     const AcqSpec a{type, par, fmin, y_mean, y_std};
     const LpSpec batch{transform, Xb, nb, r_x0, s_x0}, *pen = lp ? &batch : nullptr;
-    if ((rc = check_acq(g, a))) return rc;
+    if ((rc = check_acq(g, a, pen))) return rc;
     if (pen && (rc = check_lp(*pen))) return rc;
     if (sparse_rows_fused_ok(g, M)) {
         LpBatch b;
         if (pen && (rc = rows_lp_batch(g, *pen, &b))) return rc;   // (keeps the shared batch cache in step with dLp)
         return sparse_rows_fused(g, Xs, (int)M, dout ? 1 : 0, 1, rows_acq(a, pen, b), nullptr, nullptr, out, nullptr, nullptr,
-                                 dout);   // with_noise=True, gpmodel.py:102
+                                 dout, acq_per_cost(type));   // with_noise=True, gpmodel.py:102
     }
     return sparse_rows_fallback(g, Xs, M, 1, dout != nullptr, &a, pen, nullptr, nullptr, out, nullptr, nullptr, dout);
 }

@@ -472,6 +472,21 @@ void launch_sparse_rows(hipStream_t s, const double *Winv, long n, long Mz, cons
                         const double *w, int mode, double kss, double noise_add, const RowsAcq &aq, double *gpart,
                         const PassReport &r);
 
+// ---- cost.hip: the cost surface of cost-aware EI / MPI and the quotient it puts under the scores --------------------------------
+// logc[i] = shift + scale sum_j alpha[j] k(xs_i, Xc_j) and (dlogc given) its x-gradient [M, D], over the surface Xcs = Xc / lengthscale
+// [Nc, ld] (ld = max(D, 8), zeros beyond D).  One summation order per location in both launches: the same bits (cost.hip).
+// part: cost_table_part_elems(M, Nc, D) doubles of scratch (0: none wanted) for a values-only call, which is then cut along the
+// surface too -- a table of few rows on every compute unit; null: one workgroup per 64 / 256 candidates over the whole surface
+size_t cost_table_part_elems(long M, long Nc, int D);
+void launch_cost_table(hipStream_t s, const double *Xs, long M, const double *Xcs, int ld, const double *alpha, long Nc,
+                       const KernParams &kp, double shift, double scale, double *logc, double *dlogc, double *part);
+// rx.M <= ROWS_WIDE_M locations by value.  blk null: logc [M] (and, with grad, dlogc [M, D]) are written; blk given: the quotient is
+// applied in place to the negated scores (and, with grad, their gradients) of a rows result block laid out for MV locations
+void launch_cost_rows(hipStream_t s, const RowsX &rx, const double *Xcs, int ld, const double *alpha, long Nc, const KernParams &kp,
+                      double shift, double scale, int grad, double *logc, double *dlogc, double *blk, int MV);
+// neg <- neg / c, dneg <- (dneg - neg_old dlogc) / c with c = exp(logc), element-wise in place (dneg null: values only)
+void launch_cost_apply(hipStream_t s, const double *logc, const double *dlogc, long M, int D, double *neg, double *dneg);
+
 // ---- rns.hip: fp64-equivalent contraction on the int8 matrix cores (option "emulate_fp64") -----------------------------
 #define GP_RNS_T 14
 #define GP_RNS_KMAX 8192   // longest contraction (bytes) one residue launch may take: see rns_reduce_f in rns.hip

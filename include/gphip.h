@@ -42,6 +42,9 @@ typedef struct gp_ctx gp_t;
 #define GP_ACQ_EI 0
 #define GP_ACQ_LCB 1
 #define GP_ACQ_MPI 2
+/* or-ed into the `type` of a scoring entry: the scores are divided by the cost of the resident cost surface (the cost entries
+ * near the end of this header).  Without it every entry behaves as it always did. */
+#define GP_ACQ_PER_COST 0x100
 
 /* error codes (< 0) */
 #define GP_ERR_ARG (-1)
@@ -792,6 +795,35 @@ int gp_debug_gemm(gp_t *gp, int mode, double *C, const double *A, const double *
  * The number of CUs kept free of the trailing update for the look-ahead chain is fixed per process
  * (environment GPHIP_RESERVE_CUS, default 32; "reserve_cus" only checks the value). */
 int gp_set_option(gp_t *gp, const char *name, int64_t value);
+
+/* ---- cost-aware EI / MPI: the evaluation-time cost model (GPyOpt/core/task/cost.py, acquisitions/base.py:33-50) ------------
+ * The cost is exp(m_c(x)), m_c the posterior mean of a second GP over the logarithm of the evaluation times.  A posterior mean
+ * needs no factor:  m_c(x) = shift + scale sum_j alpha_j k(x, Xc_j),  so the cost surface is the snapshot (Xc, alpha, kernel
+ * parameters, normaliser) and any handle can own a copy.
+ *
+ * gp_cost_set copies the surface into buffers of the context's own (no pointer to another handle is kept): Xc [Nc, D] with D
+ * the handle's, alpha [Nc] (gp_get_alpha of the cost GP), kernel one of GP_KERNEL_* (Euclidean, ARD or not: lengthscale [D] or
+ * [1]), shift / scale the cost GP's output normaliser (its y_mean / y_std; 0 and 1 without one).  Nc = 0 clears the surface.  It
+ * needs gp_set_data (GP_ERR_STATE: D is the data's), is valid before or after gp_fit, and touches neither the fit nor the
+ * posterior caches; gp_set_data with another D drops the surface.  GP_ERR_ARG: a null pointer, Nc < 0, an unknown kernel, a
+ * variance or lengthscale that is not positive and finite, a non-finite shift or scale.
+ * gp_cost_info: *Nc = rows of the resident surface, 0 when there is none.
+ * gp_cost_rows: logc [M] = m_c at the M locations Xs [M, D] and, when dlogc is given, its x-gradient [M, D].  GP_ERR_STATE
+ * without a surface.  The terms of a location are summed in ONE order (chunks of 32 rows in row order, the chunks in order): its
+ * bits do not depend on M, on its row, or on whether it came in a table (M > 8, or the resident candidates of a flagged scoring
+ * call) or among a few rows.  The Exponential family keeps the _inv_dist convention: a location that coincides with an Xc_j
+ * takes 0 from it into the gradient.
+ *
+ * GP_ACQ_PER_COST in the `type` of gp_acq, gp_acq_grad, gp_acq_argbest, gp_acq_topk, gp_acq_rows, gp_sparse_acq,
+ * gp_sparse_acq_argbest, gp_sparse_acq_topk, gp_sparse_acq_rows, gp_ens_acq, gp_ens_acq_argbest and gp_ens_acq_rows divides the
+ * negated scores by c = exp(logc): neg <- neg / c, dneg <- (dneg - neg dlogc) / c (for the ensemble after the average over the
+ * members).  GP_ERR_ARG: no surface, LCB (LCB.py takes no cost), a penalised call (lp: LP.py:27 builds the penalised acquisition
+ * with unit cost).  The entropy-search entries, the penalised-only entries (gp_acq_lp*) and the group entries take no flag.  The
+ * logc of a resident table is computed once per table and surface: values, arg-best and top-k of one table pay the pass once. */
+int gp_cost_set(gp_t *gp, const double *Xc, int64_t Nc, const double *alpha, int kernel, int ard, double variance,
+                const double *lengthscale, double shift, double scale);
+int gp_cost_info(gp_t *gp, int64_t *Nc);
+int gp_cost_rows(gp_t *gp, const double *Xs, int64_t M, double *logc, double *dlogc);
 
 #ifdef __cplusplus
 }
