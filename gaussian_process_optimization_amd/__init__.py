@@ -20,6 +20,7 @@ import types as _types
 
 from . import _lib
 from . import kern
+from . import mappings
 from .gp_regression import GPRegression, Gaussian, Standardize
 from .sparse_gp import SparseGPRegression
 from .gpmodel import GPModel, BOModel, GPModel_MCMC
@@ -46,7 +47,7 @@ models = _types.SimpleNamespace(GPRegression=GPRegression, SparseGPRegression=Sp
 methods = _types.SimpleNamespace(BayesianOptimization=BayesianOptimization)
 likelihoods = _types.SimpleNamespace(Gaussian=Gaussian)
 
-__all__ = ["kern", "models", "methods", "likelihoods", "acquisitions", "GPRegression", "SparseGPRegression", "GPModel", "BOModel", "GPModel_MCMC", "priors", "HMC",
+__all__ = ["kern", "mappings", "models", "methods", "likelihoods", "acquisitions", "GPRegression", "SparseGPRegression", "GPModel", "BOModel", "GPModel_MCMC", "priors", "HMC",
            "AcquisitionEI_MCMC", "AcquisitionMPI_MCMC", "AcquisitionLCB_MCMC",
            "AcquisitionEntropySearch", "entropy_search", "McmcSampler", "AffineInvariantEnsembleSampler",
            "InputWarpedGP", "InputWarpedGPModel", "input_warping", "WarpedGP", "WarpedGPModel", "warping_functions",

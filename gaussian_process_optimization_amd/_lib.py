@@ -192,6 +192,9 @@ SIGNATURES = [
                                    c_double_p, ctypes.c_double, ctypes.c_double]),
     ("gp_cost_info", ctypes.c_int, [_vp, c_int64_p]),
     ("gp_cost_rows", ctypes.c_int, [_vp, _vp, ctypes.c_int64, _vp, _vp]),
+    ("gp_mean_set", ctypes.c_int, [_vp, c_double_p, c_double_p]),
+    ("gp_mean_info", ctypes.c_int, [_vp, c_int_p, c_int_p]),
+    ("gp_mean_grad", ctypes.c_int, [_vp, c_double_p, c_double_p]),
 ]
 
 _lib = None
@@ -1077,6 +1080,36 @@ class Handle(object):
         if rc:
             check(self.lib, rc, "gp_cost_rows")
         return (logc, dlogc) if grad else logc
+
+    # -- the mean function m(x) = x^T A + b of the exact GP (include/gphip.h, gp_mean_*) -----------------------------------
+    def mean_set(self, A=None, b=None):
+        """Make ``A`` [D, P] and ``b`` [P] the handle's mean function -- a copy; either may be None (that part is not there),
+        both None clears it.  Drops the fit, as ``set_params`` does."""
+        D, P = getattr(self, "D", None), getattr(self, "P", None)
+        if D is None:
+            raise RuntimeError("gp_mean_set: set_data first (A is [D, P] and b [P] of the data)")
+        if A is not None:
+            A = as_f64(A, 2)
+            if A.shape != (D, P):
+                raise ValueError("gp_mean_set: A has shape %s, the data wants (%d, %d)" % (A.shape, D, P))
+        if b is not None:
+            b = as_f64(np.ravel(b), 1)
+            if b.size != P:
+                raise ValueError("gp_mean_set: b has %d entries, the data wants %d" % (b.size, P))
+        check(self.lib, self.lib.gp_mean_set(self.h, None if A is None else dptr(A), None if b is None else dptr(b)),
+              "gp_mean_set")
+
+    def mean_info(self):
+        """(has_A, has_b) of the resident mean function; (False, False): none."""
+        a, b = ctypes.c_int(0), ctypes.c_int(0)
+        check(self.lib, self.lib.gp_mean_info(self.h, ctypes.byref(a), ctypes.byref(b)), "gp_mean_info")
+        return bool(a.value), bool(b.value)
+
+    def mean_grad(self):
+        """dL/dA = X^T alpha [D, P] and dL/db = 1^T alpha [P] of the current fit."""
+        dA, db = np.empty((self.D, self.P)), np.empty(self.P)
+        check(self.lib, self.lib.gp_mean_grad(self.h, dptr(dA), dptr(db)), "gp_mean_grad")
+        return dA, db
 
     def rows_stats(self):
         a, b = ctypes.c_int64(), ctypes.c_int64()

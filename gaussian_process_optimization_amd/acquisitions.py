@@ -839,6 +839,8 @@ class AcquisitionEntropySearch(AcquisitionBase):
     def _es_device_ok(self):
         if not self.device or self.model.model is None or getattr(self.model, "sparse", False):
             return False
+        if getattr(self.model.model, "mean_function", None) is not None:   # the gp_es_* entries refuse a resident mean function
+            return False
         return _unit_cost_unconstrained(self) and self.model.model.output_dim == 1
 
     def _signature(self):

@@ -372,7 +372,8 @@ class BayesianOptimization(object):
             optimizer=kwargs.get('model_optimizer_type', 'lbfgs'), max_iters=kwargs.get('max_iters', 1000),
             optimize_restarts=kwargs.get('optimize_restarts', 5), verbose=verbosity_model,
             ARD=kwargs.get('ARD', False), Gower=kwargs.get('Gower', False), space=self.space, device=device,
-            parallel_restarts=kwargs.get('parallel_restarts', False), incremental=kwargs.get('incremental', False))
+            parallel_restarts=kwargs.get('parallel_restarts', False), incremental=kwargs.get('incremental', False),
+            mean_function=kwargs.get('mean_function', None))
         self.acquisition_optimizer = AcquisitionOptimizer(self.space, acquisition_optimizer_type, parallel=parallel_anchors)
         # core/bo.py:31: the cost the acquisitions divide by; 'evaluation_time' fits a GP to the logarithm of the evaluation times
         self.cost = CostModel(cost_withGradients, device=device)

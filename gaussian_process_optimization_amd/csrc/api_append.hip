@@ -213,6 +213,8 @@ static int append_refused(gp_ctx *g, int code, const char *fmt, long a = 0, long
 extern "C" int gp_append(gp_t *g, const double *Xnew, int64_t k, const double *Yall, double *lml, double *logdet) {
     if (!g || !Xnew || !Yall) return fail(GP_ERR_ARG, "null argument");
     GP_DEAD_CHECK(g);
+    if (g->mean.on())   // the border's right-hand sides would be raw targets beside residuals
+        return append_refused(g, GP_ERR_STATE, "gp_append: not available while a mean function is resident (gp_mean_set(NULL, NULL) clears it)");
     if (!g->fitted) return append_refused(g, GP_ERR_STATE, "gp_append extends a valid fit: gp_fit first");
     if (g->warp.n > 0) return append_refused(g, GP_ERR_STATE, "gp_append: an output warp is on (its targets are refitted, not appended)");
     if (k < 1 || k > GP_TILE) return append_refused(g, GP_ERR_ARG, "gp_append: k = %ld outside 1..%ld", (long)k, (long)GP_TILE);

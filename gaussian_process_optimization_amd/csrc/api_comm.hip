@@ -22,6 +22,7 @@ extern "C" int gp_comm_version(int *version) {
 extern "C" int gp_comm_init(gp_t *g, const char *uid128, int rank, int nranks) {
     if (!g || !uid128) return fail(GP_ERR_ARG, "null argument");
     GP_DEAD_CHECK(g);
+    GP_NO_MEAN(g, "gp_comm_init");
     if (nranks < 1 || rank < 0 || rank >= nranks) return fail(GP_ERR_ARG, "bad rank %d / %d", rank, nranks);
     HIPCHK(hipSetDevice(g->device));
     if (g->comm) {
@@ -79,6 +80,7 @@ void unpack_pairs(const double *rec, size_t n, double *v, int64_t *ix) {
 // a live context with a communicator, its device current
 static int comm_ready(gp_ctx *g) {
     GP_DEAD_CHECK(g);
+    GP_NO_MEAN(g, "the comm entry points");
     if (!g->comm) return fail(GP_ERR_STATE, "gp_comm_init first");
     if (g->nranks > GP_COMM_MAX_RANKS) return fail(GP_ERR_ARG, "nranks > %d", GP_COMM_MAX_RANKS);
     HIPCHK(hipSetDevice(g->device));
@@ -129,6 +131,7 @@ static void apply_fit_record(gp_ctx *g, const double *rec) {
 extern "C" int gp_comm_bcast_fit(gp_t *g, int root) {
     if (!g) return fail(GP_ERR_ARG, "null gp");
     GP_DEAD_CHECK(g);
+    GP_NO_MEAN(g, "gp_comm_bcast_fit");
     if (!g->comm) return fail(GP_ERR_STATE, "gp_comm_init first");
     if (!g->have_data || !g->have_params) return fail(GP_ERR_STATE, "every rank needs data and params set");
     HIPCHK(hipSetDevice(g->device));

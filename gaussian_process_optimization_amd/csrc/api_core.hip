@@ -596,10 +596,17 @@ extern "C" int gp_set_data(gp_t *g, const double *X, const double *Y, int64_t N,
         g->cost.Nc = 0;
         g->cost_tab = 0;
     }
+    if (g->mean.on() && (D != g->D || P != g->P)) g->mean.has_A = g->mean.has_b = g->mean.stale = false;   // A [D, P], b [P] of other data
     g->D = D;
     g->P = P;
     HIPCHK(hipMemcpyAsync(g->dX, X, sizeof(double) * N * D, hipMemcpyHostToDevice, g->s));
     HIPCHK(hipMemcpyAsync(g->dY, Y, sizeof(double) * N * P, hipMemcpyHostToDevice, g->s));
+    if (g->mean.on()) {   // a resident mean function stays: the raw targets beside the residuals, rebuilt before the next factorisation
+        int rc = g->dYraw.reserve(g->capN * (long)g->capP);
+        if (rc) return rc;
+        HIPCHK(hipMemcpyAsync(g->dYraw, Y, sizeof(double) * N * P, hipMemcpyHostToDevice, g->s));
+        g->mean.stale = true;
+    }
     if (g->warp.n > 0) {   // an active output warp is applied to the new targets
         int rc = warp_apply(g, true);
         if (rc) return rc;

@@ -13,6 +13,7 @@
 
 static int ens_ready(gp_ctx *g) {
     GP_DEAD_CHECK(g);
+    GP_NO_MEAN(g, "the ensemble entry points");
     if (g->ens.S < 1) return fail(GP_ERR_STATE, "gp_ens_fit first");
     HIPCHK(hipSetDevice(g->device));
     return 0;
@@ -25,6 +26,7 @@ extern "C" int gp_ens_fit(gp_t *g, int S, const double *variance, const double *
                           double *lml, double *logdet, double *jitter_used, double *fmin) {
     if (!g || !variance || !lengthscale || !noise) return fail(GP_ERR_ARG, "null argument");
     GP_DEAD_CHECK(g);
+    GP_NO_MEAN(g, "gp_ens_fit");
     if (!g->have_data) return fail(GP_ERR_STATE, "gp_set_data before gp_ens_fit");
     // what the shapes alone decide comes first: a data set the ensemble cannot take is refused before any parameters are asked for
     if (S < 1 || S > GP_ENS_MAX_S) return fail(GP_ERR_ARG, "gp_ens_fit takes 1 <= S <= %d members (got %d)", GP_ENS_MAX_S, S);

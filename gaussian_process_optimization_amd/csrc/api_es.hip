@@ -24,6 +24,7 @@ static void swap_buf(DevBuf<double> &a, DevBuf<double> &b) {
 extern "C" int gp_es_set_representers(gp_t *g, const double *Xr, int R, double y_mean, double y_std, double *mu, double *cov) {
     if (!g || !Xr || !mu || !cov) return fail(GP_ERR_ARG, "null argument");
     GP_FITTED(g);
+    GP_NO_MEAN(g, "gp_es_set_representers");
     int rc;
     if ((rc = check_R(R))) return rc;
     if ((rc = check_es_model(g))) return rc;
@@ -66,6 +67,7 @@ extern "C" int gp_es_pmin(gp_t *g, const double *mu, const double *cov, int R, i
                           double *logS, int *status, int *sweeps) {
     if (!g || !mu || !cov || !status || !sweeps) return fail(GP_ERR_ARG, "null argument");
     GP_DEAD_CHECK(g);
+    GP_NO_MEAN(g, "gp_es_pmin");
     int rc;
     if ((rc = check_R(R))) return rc;
     if (max_sweeps < 1 || max_sweeps > 100000) return fail(GP_ERR_ARG, "max_sweeps out of range (1..100000)");
@@ -97,6 +99,7 @@ extern "C" int gp_es_set_belief(gp_t *g, const double *logP, const double *u, co
                                 const double *W, int S) {
     if (!g || !logP || !u || !G || !Q || !W) return fail(GP_ERR_ARG, "null argument");
     GP_FITTED(g);
+    GP_NO_MEAN(g, "gp_es_set_belief");
     int rc;
     if ((rc = check_R(R))) return rc;
     if (S < 1 || S > GP_ES_MAX_S) return fail(GP_ERR_ARG, "S out of range (1..%d)", GP_ES_MAX_S);
@@ -162,6 +165,7 @@ static int run_es_acq(gp_ctx *g, double y_std) {
 extern "C" int gp_es_acq(gp_t *g, double y_std, double *out) {
     if (!g || !out) return fail(GP_ERR_ARG, "null argument");
     GP_SCORING(g);
+    GP_NO_MEAN(g, "gp_es_acq");
     int rc;
     if ((rc = run_es_acq(g, y_std))) return rc;
     return scores_out(g, g->dAcq, nullptr, g->M, g->D, out, nullptr);
@@ -170,6 +174,7 @@ extern "C" int gp_es_acq(gp_t *g, double y_std, double *out) {
 extern "C" int gp_es_acq_argbest(gp_t *g, double y_std, int sense, int64_t *idx, double *val) {
     if (!g || !idx || !val) return fail(GP_ERR_ARG, "null argument");
     GP_SCORING(g);
+    GP_NO_MEAN(g, "gp_es_acq_argbest");
     int rc;
     if ((rc = check_sense(sense))) return rc;
     if ((rc = run_es_acq(g, y_std))) return rc;

@@ -490,6 +490,7 @@ int fit_impl(gp_ctx *g, int maxtries, Pipe kind, int include_noise) {
     const long N = g->N, Npad = g->Npad;
     const int P = g->P;
     int rc;
+    if ((rc = mean_residuals(g))) return rc;   // a resident mean function: dY = Y - m(X) is what everything below factors against
     PredPipe pp;
     if (kind != Pipe::None && (rc = make_pipe(g, kind, &pp))) return rc;
     double diag_add, diag0;
@@ -545,6 +546,7 @@ int fit_impl(gp_ctx *g, int maxtries, Pipe kind, int include_noise) {
         ph = phase_begin(g, "reduce", 0.0, 8.0 * (double)N * g->M);
         launch_predict_reduce(g->s, g->dT2, Npad, g->M, N, g->dA + Npad * Npad, Npad, P, g->kp.variance,
                               include_noise ? g->noise : 0.0, g->dMean, g->dVar);
+        mean_add(g, g->dXs, g->M, g->dMean);
         phase_end(g, ph);
     }
 

@@ -96,6 +96,7 @@ extern "C" int gp_lml_grad(gp_t *g, double *dvariance, double *dlengthscale, dou
 extern "C" int gp_lml_grad_x(gp_t *g, double *dL_dX) {
     if (!g || !dL_dX) return fail(GP_ERR_ARG, "null argument");
     GP_FITTED(g);
+    GP_NO_MEAN(g, "gp_lml_grad_x");
     if (g->P > GP_GRAD_MAX_P) return fail(GP_ERR_ARG, "gp_lml_grad_x supports P <= %d", GP_GRAD_MAX_P);
     // the fork's Euclidean gradients_X on a Gower K is not a derivative of anything the warping could use
     if (g->kp.gower) return fail(GP_ERR_ARG, "gp_lml_grad_x: not defined for a Gower model");
@@ -146,6 +147,7 @@ extern "C" int gp_fit_grad_x(gp_t *g, int maxtries, double *lml, double *logdet,
     if (!g || !dvariance || !dlengthscale || !dnoise || !dL_dX) return fail(GP_ERR_ARG, "null argument");
     GP_DEAD_CHECK(g);
     if (!g->have_data || !g->have_params) return fail(GP_ERR_STATE, "set data and params before gp_fit_grad_x");
+    GP_NO_MEAN(g, "gp_fit_grad_x");
     if (g->P > GP_GRAD_MAX_P) return fail(GP_ERR_ARG, "gp_lml_grad_x supports P <= %d", GP_GRAD_MAX_P);
     if (g->kp.gower) return fail(GP_ERR_ARG, "gp_lml_grad_x: not defined for a Gower model");
     int rc;
@@ -190,10 +192,12 @@ int run_predict_grad(gp_ctx *g) {
         launch_small_forward_solve(g->s, g->dA, Npad, g->dInvP, g->invp_W, Npad, g->dT, g->dT2, Npad, (int)M);   // dT2 = w rows
         launch_predict_reduce(g->s, g->dT2, Npad, M, N, g->dA + Npad * Npad, Npad, g->P, g->kp.variance, g->noise, g->dMean,
                               g->dVar);
+        mean_add(g, g->dXs, M, g->dMean);
         g->predicted = true;       // GPModel.predict: with_noise=True (gpmodel.py:102)
         g->predicted_noise = 1;
         launch_trsv_backward(g->s, g->dA, Npad, g->dInvP, g->invp_W, Npad, g->dT2, Npad, (int)M, g->dCov, g->dT);   // beta = L^-T w
         launch_predict_grad(g->s, g->dXs, M, g->dX, N, g->kp, g->dAlpha, Npad, g->P, g->dCov, Npad, g->dDm, g->dDv);
+        mean_add_grad(g, M, g->dDm);
         return 0;
     }
     if ((rc = ensure_wi(g))) return rc;
@@ -218,6 +222,7 @@ int run_predict_grad(gp_ctx *g) {
         launch_predict_grad(g->s, g->dXs + m0 * g->D, mc, g->dX, N, g->kp, g->dAlpha, Npad, g->P, g->dCov, Npad,
                             g->dDm + m0 * g->D * g->P, g->dDv + m0 * g->D);
     }
+    mean_add_grad(g, M, g->dDm);   // a resident mean function: dmdx[m, d, p] += A[d, p]
     g->predicted = false;  // dT no longer holds the solved candidates
     return 0;
 }
@@ -239,6 +244,7 @@ extern "C" int gp_predict_grad(gp_t *g, double *dmdx, double *dvdx) {
         // neither Ky^-1 nor K(X*, X) Ky^-1 -- one pass of O(M N D) instead of 2 N^3 / 3 + N^2 M flops
         if ((rc = ensure_grad_buffers(g, 1, g->M))) return rc;
         launch_predict_grad(g->s, g->dXs, g->M, g->dX, g->N, g->kp, g->dAlpha, g->Npad, g->P, nullptr, 0, g->dDm, g->dDv);
+        mean_add_grad(g, g->M, g->dDm);
     } else if ((rc = run_predict_grad(g))) {
         return rc;
     }

@@ -139,6 +139,9 @@ static int group_unwarped(gp_group *grp) {
     for (size_t i = 0; i < grp->m.size(); ++i)
         if (grp->m[i]->warp.n > 0)
             return fail(GP_ERR_STATE, "member %zu has an output warp on (gp_set_output_warp): groups do not take warped models", i);
+    for (size_t i = 0; i < grp->m.size(); ++i)   // ... and neither does one with a mean function (gp_mean_set through gp_group_member)
+        if (grp->m[i]->mean.on())
+            return fail(GP_ERR_STATE, "member %zu has a mean function resident (gp_mean_set): groups do not take a mean function", i);
     return 0;
 }
 

@@ -67,6 +67,14 @@ void gp_clear_stale_note();
 #define GP_FITTED(g) GP_READY(g, false)
 #define GP_SCORING(g) GP_READY(g, true)
 
+// The entries whose prediction side would not add m(x), or that read dY as targets: refused while a mean function is resident,
+// before anything is launched or changed
+#define GP_NO_MEAN(g, who)                                                                          \
+    do {                                                                                            \
+        if ((g)->mean.on())                                                                         \
+            return fail(GP_ERR_STATE, "%s: not available while a mean function is resident (gp_mean_set(NULL, NULL) clears it)", who); \
+    } while (0)
+
 // ---- scratch map ----------------------------------------------------------------------------------------------------------
 // Where everything lives in the small device buffers that several units carve up: offset and length (in elements) of every
 // slot, in this one place.  gp_create (api_core.hip) reserves the *_CAP of dScal, dRedV and dRedI once; dComm and dLp are
@@ -275,6 +283,18 @@ struct CostState {
     DevBuf<double> dPart;      // the chunks' partial sums of a values-only table launch cut along the surface (cost.hip)
 };
 
+// The affine mean function m(x) = x^T A + b of the exact GP (api_mean.hip): a snapshot of the mapping's parameters in a buffer of
+// the context's own.  While one is resident dYraw keeps the targets gp_set_data brought (the output warp's buffer and convention)
+// and dY holds the residuals Y - m(X) every fit route factors against; `stale` while dY still has to be rebuilt from them
+// (mean_residuals, before the next factorisation).  D and P are the data's.
+struct MeanState {
+    bool has_A = false, has_b = false;
+    bool stale = false;
+    DevBuf<double> dAb;        // A [D, P] row-major, then b [P]; an absent part as zeros
+    DevBuf<double> dPart;      // gp_mean_grad: the chunks' partial sums, then the (D + 1) P results
+    bool on() const { return has_A || has_b; }
+};
+
 struct gp_ctx {
     int device = 0;
     long lds_per_wg = 0;           // hipDeviceAttributeMaxSharedMemoryPerBlock of the device (gp_create)
@@ -434,6 +454,7 @@ struct gp_ctx {
     EnsState ens;       // the ensemble (api_ens.hip)
     EsState es;         // entropy search: representers and belief (api_es.hip)
     CostState cost;     // the cost surface of the flagged scoring calls (api_cost.hip)
+    MeanState mean;     // the mean function (api_mean.hip)
     bool dead = false;  // gp_shutdown ran: the device's streams are gone, only gp_destroy is still valid
 };
 
@@ -717,4 +738,12 @@ void panel_inv_steps(gp_ctx *g, hipStream_t s, double *Wb, long PB, const double
 int es_ready(gp_ctx *g, double y_std);
 struct EsBelief { const double *Qt, *Gt, *logP, *u, *W; };
 EsBelief es_belief(const gp_ctx *g);
+// api_mean.hip (each a no-op without a resident mean function): dY <- dYraw - m(X) where it is stale, enqueued and drained;
+// mean [M, P] += m(X) for M rows X on the device; dmdx [M, D, P] += A; the fused rows passes' kernel argument
+int mean_residuals(gp_ctx *g);
+void mean_add(gp_ctx *g, const double *X, long M, double *mean);
+void mean_add_grad(gp_ctx *g, long M, double *dmdx);
+static inline RowsMean rows_mean(const gp_ctx *g) {
+    return g->mean.on() ? RowsMean{1, g->mean.dAb.p, g->mean.dAb.p + (long)g->D * g->P} : RowsMean{0, nullptr, nullptr};
+}
 int warp_apply(gp_ctx *g, bool raw_in_dY);   // api_warp.hip: (dYraw <- dY when dY holds raw targets,) dY <- f(dYraw), warp_logjac; enqueued on g->s, the caller drains

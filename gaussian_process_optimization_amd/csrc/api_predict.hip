@@ -25,6 +25,7 @@ extern "C" int gp_set_candidates_kumar(gp_t *g, const double *Xs, int64_t M, con
     if (!g || !Xs || !warp || !a || !b || !xmin || !xmax) return fail(GP_ERR_ARG, "null argument");
     GP_DEAD_CHECK(g);
     if (!g->have_data) return fail(GP_ERR_STATE, "gp_set_data first");
+    GP_NO_MEAN(g, "gp_set_candidates_kumar");
     for (int q = 0; q < g->D; ++q) {
         if (!warp[q]) continue;
         if (!(a[q] > 0.0) || !(b[q] > 0.0) || !std::isfinite(a[q]) || !std::isfinite(b[q]))
@@ -67,6 +68,7 @@ int run_predict(gp_ctx *g, int include_noise, bool tiles_only, const ChunkHook *
         ph = phase_begin(g, "reduce", 0.0, 8.0 * (double)N * M);
         launch_predict_reduce(g->s, g->dT2, Npad, M, N, g->dA + Npad * Npad, Npad, P, g->kp.variance,
                               include_noise ? g->noise : 0.0, g->dMean, g->dVar);
+        mean_add(g, g->dXs, M, g->dMean);   // a resident mean function: m(x*) joins the mean upstream of every cache and score
         phase_end(g, ph);
         g->predicted = true;
         g->predicted_noise = include_noise ? 1 : 0;
@@ -95,6 +97,7 @@ int run_predict(gp_ctx *g, int include_noise, bool tiles_only, const ChunkHook *
         ph = phase_begin(g, "reduce", 0.0, 8.0 * (double)N * mc);
         launch_predict_reduce(g->s, g->dT2, Npad, mc, N, g->dA + Npad * Npad, Npad, P, g->kp.variance,
                               include_noise ? g->noise : 0.0, g->dMean + m0 * P, g->dVar + m0);
+        mean_add(g, g->dXs + m0 * g->D, mc, g->dMean + m0 * P);
         phase_end(g, ph);
         if (chunk && (rc = (*chunk)(m0, mc, mcpad))) return rc;
     }
@@ -246,10 +249,13 @@ extern "C" int gp_fmin(gp_t *g, double *fmin) {
     GP_FITTED(g);
     if (g->P != 1) return fail(GP_ERR_ARG, "gp_fmin needs P == 1");
     if (!g->fmin_valid) {
-        if (g->fmin_direct)
+        // (a resident mean function: m(X_i) + r_i - d alpha_i = y_i - d alpha_i with the RAW targets; K alpha + m(X) directly)
+        if (g->fmin_direct) {
             launch_train_mean(g->s, g->dX, g->N, g->kp, g->dAlpha, g->dMu);
-        else
-            launch_train_mean_identity(g->s, g->dY, g->dAlpha, g->noise + 1e-8 + g->jitter, g->N, g->dMu);
+            mean_add(g, g->dX, g->N, g->dMu);
+        } else {
+            launch_train_mean_identity(g->s, g->mean.on() ? g->dYraw : g->dY, g->dAlpha, g->noise + 1e-8 + g->jitter, g->N, g->dMu);
+        }
         int rc;
         if ((rc = argbest_read(g, g->dMu, g->N, -1, nullptr, &g->fmin))) return rc;
         g->fmin_valid = true;

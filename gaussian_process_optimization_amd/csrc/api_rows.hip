@@ -114,7 +114,7 @@ static int rows_fused(gp_ctx *g, const double *Xs, int M, int include_noise, int
         g, Xs, M, want_grad ? "rows_fused_grad" : "rows_fused", want_grad ? 2.0 : 1.0,
         [&](const RowsX &rx, const RowsWork &w, const PassReport &r) {
             launch_rows(g->s, g->dLi, g->Npad, rx, g->kp, g->dX, g->N, g->dAlpha, want_grad, g->kp.variance,
-                        include_noise ? g->noise : 0.0, aq, w, r, g->rows_nt < 0 ? (g->Npad > 8192 ? 1 : 0) : g->rows_nt);
+                        include_noise ? g->noise : 0.0, aq, w, r, g->rows_nt < 0 ? (g->Npad > 8192 ? 1 : 0) : g->rows_nt, rows_mean(g));
             if (per_cost) cost_divide_block(g, rx, want_grad != 0, r.out, rows_layout(rx.M));   // behind the pass, before the drain
             return rows_finish_grid(g->N);
         },
@@ -138,7 +138,7 @@ extern "C" int gp_predict_rows(gp_t *g, const double *Xs, int64_t M, int include
             return rows_exact_passes(
                 g, Xs, (int)M, nullptr, 0.0,
                 [&](const RowsX &rx, const RowsWork &w, const PassReport &r) {
-                    launch_rows_mean_grad(g->s, rx, g->kp, g->dX, g->N, g->dAlpha, w, r);
+                    launch_rows_mean_grad(g->s, rx, g->kp, g->dX, g->N, g->dAlpha, w, r, rows_mean(g));
                     return rows_mean_grad_grid(g->N);
                 },
                 [&](int m0, int mc, int MV, const double *o) { memcpy(dmdx + (long)m0 * D, o + 3 * MV, sizeof(double) * mc * D); });
@@ -191,6 +191,7 @@ extern "C" int gp_acq_rows(gp_t *g, const double *Xs, int64_t M, int type, doubl
 extern "C" int gp_es_acq_rows(gp_t *g, const double *Xs, int64_t M, double y_std, double *out) {
     if (!g || !Xs || !out) return fail(GP_ERR_ARG, "null argument");
     GP_FITTED(g);
+    GP_NO_MEAN(g, "gp_es_acq_rows");
     if (M < 1) return fail(GP_ERR_ARG, "M < 1");
     int rc;
     if ((rc = es_ready(g, y_std))) return rc;

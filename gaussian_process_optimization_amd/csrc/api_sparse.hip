@@ -28,6 +28,7 @@ static_assert(GP_MAX_D / GP_GRAD_CH * GP_SPARSE_NH <= 4 * GP_SPARSE_NH && SPO_MI
 
 static int sparse_preamble(gp_ctx *g, bool need_z) {
     GP_DEAD_CHECK(g);
+    GP_NO_MEAN(g, "the sparse entry points");
     if (!g->have_data || !g->have_params) return fail(GP_ERR_STATE, "set data and params before the sparse entry points");
     if (g->kp.gower) return fail(GP_ERR_STATE, "the sparse GP does not take the Gower option");
     if (g->warp.n > 0) return fail(GP_ERR_STATE, "the sparse GP does not take an output warp (gp_set_output_warp)");
@@ -39,6 +40,7 @@ static int sparse_preamble(gp_ctx *g, bool need_z) {
 extern "C" int gp_sparse_set_inducing(gp_t *g, const double *Z, int64_t Mz) {
     if (!g || !Z) return fail(GP_ERR_ARG, "null argument");
     GP_DEAD_CHECK(g);
+    GP_NO_MEAN(g, "gp_sparse_set_inducing");
     if (Mz < 1 || Mz > GP_SPARSE_MAX_INDUCING) return fail(GP_ERR_ARG, "Mz out of range (1..%d)", GP_SPARSE_MAX_INDUCING);
     if (!g->have_data) return fail(GP_ERR_STATE, "gp_set_data first");
     HIPCHK(hipSetDevice(g->device));
@@ -390,6 +392,7 @@ extern "C" int gp_sparse_fmin(gp_t *g, double *fmin) {
 extern "C" int gp_sparse_set_candidates(gp_t *g, const double *Xs, int64_t M) {
     if (!g || !Xs) return fail(GP_ERR_ARG, "null argument");
     GP_DEAD_CHECK(g);
+    GP_NO_MEAN(g, "gp_sparse_set_candidates");
     if (M < 1) return fail(GP_ERR_ARG, "M < 1");
     if (!g->have_data) return fail(GP_ERR_STATE, "gp_set_data first");
     HIPCHK(hipSetDevice(g->device));

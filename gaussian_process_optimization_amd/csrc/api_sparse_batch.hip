@@ -62,6 +62,7 @@ static SpbLayout spb_layout(const gp_ctx *g, int R, long Mz) {
 // the checks both entries share; nothing is allocated or launched
 static int spb_check(gp_ctx *g, int R, int64_t Mz) {
     GP_DEAD_CHECK(g);
+    GP_NO_MEAN(g, "gp_sparse_fit_grad_batch");
     if (!g->have_data || !g->have_params) return fail(GP_ERR_STATE, "set data and params before gp_sparse_fit_grad_batch");
     if (g->kp.gower) return fail(GP_ERR_STATE, "the sparse GP does not take the Gower option");
     if (g->warp.n > 0) return fail(GP_ERR_STATE, "the sparse GP does not take an output warp (gp_set_output_warp)");

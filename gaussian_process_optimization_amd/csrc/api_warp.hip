@@ -40,6 +40,7 @@ extern "C" int gp_set_output_warp(gp_t *g, int n_terms, const double *psi, doubl
     WarpParams w;
     int rc;
     if ((rc = warp_from_args(n_terms, psi, d, &w))) return rc;
+    GP_NO_MEAN(g, "gp_set_output_warp");
     if (!g->have_data) return fail(GP_ERR_STATE, "gp_set_data first");
     if (w.n > 0 && g->P != 1) return fail(GP_ERR_STATE, "an output warp takes P = 1 (the data has P = %d)", g->P);
     HIPCHK(hipSetDevice(g->device));
@@ -81,6 +82,7 @@ extern "C" int gp_get_targets(gp_t *g, double *Y) {
 extern "C" int gp_warp_grad(gp_t *g, double *dpsi, double *dd) {
     if (!g || !dpsi || !dd) return fail(GP_ERR_ARG, "null argument");
     GP_FITTED(g);
+    GP_NO_MEAN(g, "gp_warp_grad");
     if (g->warp.n < 1) return fail(GP_ERR_STATE, "gp_set_output_warp first");
     const int np = 3 * g->warp.n + 1;
     double host[GP_WARP_NPSI];
@@ -98,6 +100,7 @@ extern "C" int gp_fit_grad_warp(gp_t *g, int n_terms, const double *psi, double 
                                 double *dpsi, double *dd) {
     if (!g || !psi || !dvariance || !dlengthscale || !dnoise || !dpsi || !dd) return fail(GP_ERR_ARG, "null argument");
     if (n_terms < 1) return fail(GP_ERR_ARG, "gp_fit_grad_warp takes a warp of 1..%d terms", GP_WARP_MAX_TERMS);
+    GP_NO_MEAN(g, "gp_fit_grad_warp");
     int rc;
     // gp_fit_grad's refusal of a shape whose gradient pass does not fit the LDS, before the warp changes the targets
     if (!g->dead && g->have_data && (rc = lml_grad_lds_check(g, "gp_fit_grad_warp"))) return rc;
@@ -136,6 +139,7 @@ extern "C" int gp_predict_warped(gp_t *g, int include_noise, double y_mean, doub
                                  double *partials) {
     if (!g || !mean || !var || (want_median && !median)) return fail(GP_ERR_ARG, "null argument");
     GP_SCORING(g);
+    GP_NO_MEAN(g, "gp_predict_warped");
     if (g->P != 1) return fail(GP_ERR_STATE, "gp_predict_warped needs P == 1");
     WarpNodes gh;
     int rc;

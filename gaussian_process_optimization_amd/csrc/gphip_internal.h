@@ -270,6 +270,10 @@ struct RowsAcq {
     int lp, transform, nb;    // local penalisation (LP.py): on / log transform / batch size
     const double *Xb, *r0, *s0;
 };
+struct RowsMean {             // the affine mean function of a P = 1 model (mean.hip): A [D] and b [1] on the device; on = 0: none
+    int on;
+    const double *A, *b;
+};
 #define ROWS_OUT_DOUBLES (3 * ROWS_WIDE_M * (1 + GP_MAX_D))   // result block (sized for a wide pass); one more double behind it carries the call's ticket
 struct RowsWork {             // device scratch (api_rows.hip sizes it): every partial has one writer
     double *wpart, *bpart, *meanpart, *vpart, *gpart;
@@ -296,13 +300,14 @@ inline unsigned rows_mean_grad_grid(long N) { return (unsigned)((N + 255) / 256)
 //   [mean MV][var MV][acq MV][dmdx MV D][dvdx MV D][dacq MV D]
 void launch_rows(hipStream_t s, const double *Li, long Npad, const RowsX &rx, const KernParams &kp, const double *X, long N,
                  const double *alpha, int want_grad, double kss, double noise_add, const RowsAcq &aq, const RowsWork &w,
-                 const PassReport &r, int nt_loads);
+                 const PassReport &r, int nt_loads, const RowsMean &mf = RowsMean{0, nullptr, nullptr});
+// (mf.on: the mean-bearing instances of the finishing kernel add m(x) to the mean and A to dmdx; off: the instances and bits as ever)
 // the forward launch of launch_rows alone: w.wpart (and w.meanpart) of the pass, no finishing kernel, no arrival at the counter
 void launch_rows_forward(hipStream_t s, const double *Li, long Npad, const RowsX &rx, const KernParams &kp, const double *X, long N,
                          const double *alpha, const RowsWork &w, int nt_loads);
 // the mean's gradient alone: dmdx [M, D] at r.out + 3 MV (one pass over the training points, no inverse factor)
 void launch_rows_mean_grad(hipStream_t s, const RowsX &rx, const KernParams &kp, const double *X, long N, const double *alpha,
-                           const RowsWork &w, const PassReport &r);
+                           const RowsWork &w, const PassReport &r, const RowsMean &mf = RowsMean{0, nullptr, nullptr});
 // es.hip: a handful of locations behind the fused rows path's forward pass (launch_rows_forward): the scores into r.out at the
 // acquisition's place of the rows layout, the ticket behind them; cpart: es_rows_part_elems(Npad) doubles; es_rows_grid(Npad)
 // workgroups arrive at the pass's counter
@@ -486,6 +491,16 @@ void launch_cost_rows(hipStream_t s, const RowsX &rx, const double *Xcs, int ld,
                       double shift, double scale, int grad, double *logc, double *dlogc, double *blk, int MV);
 // neg <- neg / c, dneg <- (dneg - neg_old dlogc) / c with c = exp(logc), element-wise in place (dneg null: values only)
 void launch_cost_apply(hipStream_t s, const double *logc, const double *dlogc, long M, int D, double *neg, double *dneg);
+
+// ---- mean.hip: the affine mean function m(x) = x^T A + b of the exact GP ------------------------------------------------------------
+// Ab: A [D, P] row-major, then b [P] (an absent part as zeros).  m(x)_p starts from b_p and takes the D products in dimension order
+#define MEAN_GRAD_CH 256   // training rows per first-level partial of launch_mean_grad: the summation order's only constant
+void launch_mean_residual(hipStream_t s, const double *X, const double *Y, long N, int D, int P, const double *Ab, double *R);   // R = Y - m(X)
+void launch_mean_add(hipStream_t s, const double *Xs, long M, int D, int P, const double *Ab, double *mean);   // mean [M, P] += m(Xs)
+void launch_mean_add_grad(hipStream_t s, long M, int D, int P, const double *Ab, double *dmdx);               // dmdx [M, D, P] += A
+// out [(D + 1) P]: X^T alpha [D, P], then 1^T alpha [P]; alpha [P] rows of ldal; part: mean_grad_chunks(N) (D + 1) P doubles
+int mean_grad_chunks(long N);
+void launch_mean_grad(hipStream_t s, const double *X, const double *alpha, long ldal, long N, int D, int P, double *part, double *out);
 
 // ---- rns.hip: fp64-equivalent contraction on the int8 matrix cores (option "emulate_fp64") -----------------------------
 #define GP_RNS_T 14

@@ -42,15 +42,15 @@ __global__ __launch_bounds__(256) void rows_backward_kernel(const double *Li, lo
                                                             double *bpart, double *vpart) {
     rows_backward_body<MV, RB, NT>(blockIdx.x, Li, ld, wpart, Npad, M, bpart, vpart);
 }
-template <int MV>
+template <int MV, bool MEAN>
 __global__ __launch_bounds__(256) void rows_finish_kernel(RowsX rx, KernParams kp, const double *X, long N, const double *alpha,
                                                           const double *wpart, const double *bpart, const double *meanpart,
                                                           const double *vpart, long Npad, int nt, int rbh, int want_grad,
                                                           double kss, double noise_add, RowsAcq aq, double *gpart,
                                                           unsigned int *counter, unsigned int counter_base, double *out,
-                                                          double ticket) {
-    if (!rows_finish_body<MV>(blockIdx.x, gridDim.x, rx, kp, X, N, alpha, wpart, bpart, meanpart, vpart, Npad, nt, rbh, want_grad, kss,
-                              noise_add, aq, gpart, counter, counter_base, out))
+                                                          double ticket, const double *mA, const double *mb) {
+    if (!rows_finish_body<MV, MEAN>(blockIdx.x, gridDim.x, rx, kp, X, N, alpha, wpart, bpart, meanpart, vpart, Npad, nt, rbh, want_grad,
+                                    kss, noise_add, aq, gpart, counter, counter_base, out, mA, mb))
         return;
     if (threadIdx.x == 0) out[ROWS_OUT_DOUBLES] = ticket;   // this pass is complete (the host checks the ticket behind the results)
 }
@@ -199,10 +199,11 @@ __global__ __launch_bounds__(256) void rows_forward_wide_kernel(const double *Li
 // over the training points.  What estimate_L's L-BFGS-B asks for, one location at a time and D + 1 times per step (it differentiates by
 // forward differences, batch_local_penalization.py:55-67).  grid = ceil(N / 256); the last workgroup to arrive adds the workgroups'
 // sums in workgroup order and writes dmdx [M, D] at out + 3 MV (the place rows_finish_kernel writes it).
-template <int MV>
+// MEAN: the instances of a model with a mean function add its A [D] (rows_finish_body)
+template <int MV, bool MEAN>
 __global__ __launch_bounds__(256) void rows_mean_grad_kernel(RowsX rx, KernParams kp, const double *X, long N, const double *alpha,
                                                              double *gpart, unsigned int *counter, unsigned int counter_base,
-                                                             double *out, double ticket) {
+                                                             double *out, double ticket, const double *mA) {
     __shared__ double xs_s[ROWS_MAX_XS];
     __shared__ double sh[4][ROWS_MAX_XS];
     __shared__ double fin_s[8][ROWS_MAX_XS];
@@ -247,21 +248,25 @@ __global__ __launch_bounds__(256) void rows_mean_grad_kernel(RowsX rx, KernParam
     for (int v = tid; v < nval; v += 256) {
         double s = 0.0;
         for (int j = 0; j < 8; ++j) s += fin_s[j][v];
-        out[3 * MV + v] = s / kp.ls[v % D];   // (x - x') / l^2 = scaled difference / l
+        const double gm = s / kp.ls[v % D];   // (x - x') / l^2 = scaled difference / l
+        out[3 * MV + v] = MEAN ? gm + mA[v % D] : gm;
     }
     __syncthreads();
     if (tid == 0) out[ROWS_OUT_DOUBLES] = ticket;
 }
 
 void launch_rows_mean_grad(hipStream_t s, const RowsX &rx, const KernParams &kp, const double *X, long N, const double *alpha,
-                           const RowsWork &w, const PassReport &r) {
+                           const RowsWork &w, const PassReport &r, const RowsMean &mf) {
     const unsigned grid = rows_mean_grad_grid(N);
-    if (rx.M == 1)
-        GP_LAUNCH(rows_mean_grad_kernel<1>, dim3(grid), dim3(256), 0, s, rx, kp, X, N, alpha, w.gpart, r.counter, r.base, r.out, r.ticket);
-    else if (rx.M > ROWS_MAX_M)
-        GP_LAUNCH(rows_mean_grad_kernel<ROWS_WIDE_M>, dim3(grid), dim3(256), 0, s, rx, kp, X, N, alpha, w.gpart, r.counter, r.base, r.out, r.ticket);
-    else
-        GP_LAUNCH(rows_mean_grad_kernel<ROWS_MAX_M>, dim3(grid), dim3(256), 0, s, rx, kp, X, N, alpha, w.gpart, r.counter, r.base, r.out, r.ticket);
+#define RW_MG(MV, MEAN) GP_LAUNCH((rows_mean_grad_kernel<MV, MEAN>), dim3(grid), dim3(256), 0, s, rx, kp, X, N, alpha, w.gpart, r.counter, r.base, r.out, r.ticket, mf.A)
+    if (rx.M == 1) {
+        if (mf.on) RW_MG(1, true); else RW_MG(1, false);
+    } else if (rx.M > ROWS_MAX_M) {
+        if (mf.on) RW_MG(ROWS_WIDE_M, true); else RW_MG(ROWS_WIDE_M, false);
+    } else {
+        if (mf.on) RW_MG(ROWS_MAX_M, true); else RW_MG(ROWS_MAX_M, false);
+    }
+#undef RW_MG
 }
 
 // ---- launchers -------------------------------------------------------------------------------------------------------------------------
@@ -272,7 +277,7 @@ int rows_block_height(int nt) { return nt <= 16 ? 32 : GP_TILE; }
 template <int MV, int RB, bool NT>
 static void launch_rows_t(hipStream_t s, const double *Li, long Npad, const RowsX &rx, const KernParams &kp, const double *X, long N,
                           const double *alpha, int want_grad, double kss, double noise_add, const RowsAcq &aq, const RowsWork &w,
-                          const PassReport &r, bool forward_only) {
+                          const PassReport &r, bool forward_only, const RowsMean &mf) {
     const int nt = (int)(Npad / GP_TILE);
     const unsigned tiles = (unsigned)rows_tiles(nt) * (GP_TILE / RB);
     const unsigned fin = rows_finish_grid(N);
@@ -283,15 +288,20 @@ static void launch_rows_t(hipStream_t s, const double *Li, long Npad, const Rows
     if (forward_only) return;
     if (want_grad)
         GP_LAUNCH((rows_backward_kernel<MV, RB, NT>), dim3(tiles), dim3(256), 0, s, Li, Npad, w.wpart, Npad, rx.M, w.bpart, w.vpart);
-    GP_LAUNCH(rows_finish_kernel<MV>, dim3(fin), dim3(256), 0, s, rx, kp, X, N, alpha, w.wpart, w.bpart, w.meanpart, w.vpart, Npad, nt,
-              RB, want_grad, kss, noise_add, aq, w.gpart, r.counter, r.base, r.out, r.ticket);
+    if (mf.on)
+        GP_LAUNCH((rows_finish_kernel<MV, true>), dim3(fin), dim3(256), 0, s, rx, kp, X, N, alpha, w.wpart, w.bpart, w.meanpart, w.vpart,
+                  Npad, nt, RB, want_grad, kss, noise_add, aq, w.gpart, r.counter, r.base, r.out, r.ticket, mf.A, mf.b);
+    else
+        GP_LAUNCH((rows_finish_kernel<MV, false>), dim3(fin), dim3(256), 0, s, rx, kp, X, N, alpha, w.wpart, w.bpart, w.meanpart, w.vpart,
+                  Npad, nt, RB, want_grad, kss, noise_add, aq, w.gpart, r.counter, r.base, r.out, r.ticket, (const double *)nullptr,
+                  (const double *)nullptr);
 }
 
 static void launch_rows_any(hipStream_t s, const double *Li, long Npad, const RowsX &rx, const KernParams &kp, const double *X, long N,
                             const double *alpha, int want_grad, double kss, double noise_add, const RowsAcq &aq, const RowsWork &w,
-                            const PassReport &r, int nt_loads, bool forward_only) {
+                            const PassReport &r, int nt_loads, bool forward_only, const RowsMean &mf) {
     const bool low = rows_block_height((int)(Npad / GP_TILE)) == 32;
-#define RW_GO(MV, RB, NT) launch_rows_t<MV, RB, NT>(s, Li, Npad, rx, kp, X, N, alpha, want_grad, kss, noise_add, aq, w, r, forward_only)
+#define RW_GO(MV, RB, NT) launch_rows_t<MV, RB, NT>(s, Li, Npad, rx, kp, X, N, alpha, want_grad, kss, noise_add, aq, w, r, forward_only, mf)
     if (rx.M == 1) {
         if (low) RW_GO(1, 32, false);
         else if (nt_loads) RW_GO(1, GP_TILE, true);
@@ -310,14 +320,14 @@ static void launch_rows_any(hipStream_t s, const double *Li, long Npad, const Ro
 
 void launch_rows(hipStream_t s, const double *Li, long Npad, const RowsX &rx, const KernParams &kp, const double *X, long N,
                  const double *alpha, int want_grad, double kss, double noise_add, const RowsAcq &aq, const RowsWork &w,
-                 const PassReport &r, int nt_loads) {
-    launch_rows_any(s, Li, Npad, rx, kp, X, N, alpha, want_grad, kss, noise_add, aq, w, r, nt_loads, false);
+                 const PassReport &r, int nt_loads, const RowsMean &mf) {
+    launch_rows_any(s, Li, Npad, rx, kp, X, N, alpha, want_grad, kss, noise_add, aq, w, r, nt_loads, false, mf);
 }
 
 // the forward launch alone: another kernel finishes the pass from w.wpart (es.hip)
 void launch_rows_forward(hipStream_t s, const double *Li, long Npad, const RowsX &rx, const KernParams &kp, const double *X, long N,
                          const double *alpha, const RowsWork &w, int nt_loads) {
-    launch_rows_any(s, Li, Npad, rx, kp, X, N, alpha, 0, 0.0, 0.0, RowsAcq{}, w, PassReport{}, nt_loads, true);
+    launch_rows_any(s, Li, Npad, rx, kp, X, N, alpha, 0, 0.0, 0.0, RowsAcq{}, w, PassReport{}, nt_loads, true, RowsMean{0, nullptr, nullptr});
 }
 
 // ---- Li = (L^-T)^T: lower triangular, explicit zeros above the diagonal; and back -------------------------------------------------------

@@ -234,12 +234,16 @@ __device__ __forceinline__ void rows_backward_body(unsigned bid, const double *L
 // gpart row (per workgroup): [2 M D gradient sums | M sums of w^2], RW_GROW doubles apart
 // out (host-visible): [mean MV][var MV][acq MV][dmdx MV D][dvdx MV D][dacq MV D]
 #define RW_GROW (2 * ROWS_MAX_XS + ROWS_WIDE_M)
-template <int MV>
+// MEAN: the mean-bearing instances -- the affine mean function m(x) = b + sum_d x_d A_d (mean.hip: from b, the products in dimension
+// order by fma; the location as it arrived by value) joins the mean, and A the mean's gradient, where the results are formed:
+// upstream of the acquisition and the penaliser.  The instances without it are the code they were.
+template <int MV, bool MEAN = false>
 __device__ __forceinline__ bool rows_finish_body(unsigned bid, unsigned nblk, const RowsX &rx, const KernParams &kp, const double *X, long N, const double *alpha,
                                                           const double *wpart, const double *bpart, const double *meanpart,
                                                           const double *vpart, long Npad, int nt, int rbh, int want_grad,
                                                           double kss, double noise_add, const RowsAcq &aq, double *gpart,
-                                                          unsigned int *counter, unsigned int counter_base, double *out) {
+                                                          unsigned int *counter, unsigned int counter_base, double *out,
+                                                          const double *mA = nullptr, const double *mb = nullptr) {
     __shared__ double xs_s[ROWS_MAX_XS], xraw_s[ROWS_MAX_XS];
     __shared__ double part_s[4][MV][64];
     __shared__ double fin_s[8][RW_GROW + 2 * ROWS_WIDE_M];
@@ -329,7 +333,12 @@ __device__ __forceinline__ bool rows_finish_body(unsigned bid, unsigned nblk, co
     __syncthreads();
     if (tid < M) {
         const int m = tid;
-        const double mean = res_s[ntot - M + m];
+        double mean = res_s[ntot - M + m];
+        if constexpr (MEAN) {
+            double mx = mb[0];
+            for (int d = 0; d < D; ++d) mx = fma(xraw_s[m * D + d], mA[d], mx);
+            mean += mx;
+        }
         const double ssq = res_s[nsum + (want_grad ? m : m - M)];       // gradient call: after the 2 M D sums; value call: the sums themselves
         const double var = (kss - ssq) + noise_add;
         out[m] = mean;
@@ -337,7 +346,7 @@ __device__ __forceinline__ bool rows_finish_body(unsigned bid, unsigned nblk, co
         double *dm = out + 3 * MV + m * D, *dv = out + 3 * MV + MV * D + m * D, *da = out + 3 * MV + 2 * MV * D + m * D;
         if (want_grad)
             for (int d = 0; d < D; ++d) {
-                dm[d] = res_s[m * D + d];
+                dm[d] = MEAN ? res_s[m * D + d] + mA[d] : res_s[m * D + d];
                 dv[d] = res_s[M * D + m * D + d];
             }
         if (aq.on) {

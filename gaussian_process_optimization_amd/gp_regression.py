@@ -14,6 +14,7 @@ import numpy as np
 from scipy import optimize as _sopt
 
 from . import _lib
+from . import mappings as _mappings
 from .kern import RBF, Stationary, gower_config
 from .parameterization import Param, Parameterized, lbfgsb_lockstep
 
@@ -102,14 +103,16 @@ class GPRegression(Parameterized):
     :param kernel: ``kern.RBF`` / ``ExpQuad`` / ``Matern52`` / ``Matern32`` / ``Exponential`` / ``OU`` (defaults to RBF, gp_regression.py:31-32)
     :param normalizer: ``True`` standardises Y (gp.py:73-84)
     :param noise_var: Gaussian noise variance (default 1)
+    :param mean_function: ``mappings.Linear``, ``mappings.Constant`` or an ``mappings.Additive`` of those: the affine trend
+        m(x) = x^T A + b (gp.py:89-95).  Its parameters lead the flat vector, before the kernel's and the likelihood's; it acts on
+        the normalised targets and is added before the normaliser is undone (gp.py:267, 293-294, 344-352).  Resident on the
+        device (``gp_mean_set``): every prediction, gradient and acquisition route sees the full mean
     :param device: HIP device ordinal
     """
 
     def __init__(self, X, Y, kernel=None, Y_metadata=None, normalizer=None, noise_var=1., mean_function=None,
                  device=0, name="GP regression"):
         super(GPRegression, self).__init__(name)
-        if mean_function is not None:
-            raise NotImplementedError("mean functions are outside the accelerated path")
         X = np.asarray(X, dtype=float)
         if kernel is None:
             kernel = RBF(X.shape[1])
@@ -119,6 +122,16 @@ class GPRegression(Parameterized):
         self.kern._device = int(device)     # kern.K evaluates on the owning model's device (kern.py, _scratch_handle)
         self.likelihood = Gaussian(variance=noise_var)
         self.Gaussian_noise = self.likelihood
+        self.mean_function = mean_function
+        if mean_function is not None:   # gp.py:89-95: linked BEFORE the kernel and the likelihood (:108-109)
+            if not self._takes_mean_function:
+                raise NotImplementedError("%s does not take a mean function on the accelerated path" % type(self).__name__)
+            assert isinstance(mean_function, _mappings.Mapping)
+            Y_ = np.asarray(Y)
+            assert mean_function.input_dim == X.shape[1]
+            assert mean_function.output_dim == (1 if Y_.ndim == 1 else Y_.shape[1])
+            _mappings.check_affine(mean_function)
+            self.link_parameter(mean_function)
         self.link_parameters(self.kern, self.likelihood)
         if normalizer is True:
             self.normalizer = Standardize()
@@ -169,6 +182,7 @@ class GPRegression(Parameterized):
         self._dirty = True
 
     _appendable = True     # the models whose handle state gp_append extends (the warped and sparse subclasses refit)
+    _takes_mean_function = True   # ... and the ones that take ``mean_function`` (the warped and sparse subclasses refuse it)
 
     def append_XY(self, X_new, Y_all):
         """``X_new`` [k, D] joins the inputs, ``Y_all`` [N + k, P] replaces ALL targets: ``set_XY`` on the grown data, except
@@ -182,7 +196,8 @@ class GPRegression(Parameterized):
         assert X_new.shape[1] == self.X.shape[1]
         assert Y_all.shape[0] == self.X.shape[0] + X_new.shape[0]
         X_all = np.concatenate([self.X, X_new], axis=0)
-        if self._dirty or not self._appendable or not 1 <= X_new.shape[0] <= 128 or Y_all.shape[1] != self.Y.shape[1]:
+        if (self._dirty or not self._appendable or self.mean_function is not None   # (gp_append refuses a resident mean: refit)
+                or not 1 <= X_new.shape[0] <= 128 or Y_all.shape[1] != self.Y.shape[1]):
             return self.set_XY(X_all, Y_all)
         if self.normalizer is not None:
             self.normalizer.scale_by(Y_all)
@@ -219,12 +234,16 @@ class GPRegression(Parameterized):
         k = self.kern
         gower = gower_config(k.space, k.input_dim) if (k.Gower and k.space is not None) else None
         _set_params_and_gower(self._h, k, float(self.likelihood.variance), gower)
+        if self.mean_function is not None:
+            self._h.mean_set(*_mappings.affine_parts(self.mean_function))
 
     def _device_group(self, devices):
         """The model replicated on ``devices`` (HIP ordinals; one may repeat) for scoring ONE candidate table on all of them
         from this single process (include/gphip.h, gp_group_*; run.py:1240-1241 over the GPUs of the node).  Created on first
         use, and brought in step -- data, hyper-parameters, Gower set-up, refit of every replica -- whenever the model has
         changed since the group last fitted."""
+        if self.mean_function is not None:
+            raise NotImplementedError("replica groups do not take a mean function")
         key = tuple(int(d) for d in devices)
         grp = self._groups.get(key)
         if grp is None:
@@ -290,7 +309,12 @@ class GPRegression(Parameterized):
         self.kern.variance.gradient = np.atleast_1d(dv)
         self.kern.lengthscale.gradient = dl
         self.likelihood.variance.gradient = np.atleast_1d(dn)
-        return [(self.kern.variance, dv), (self.kern.lengthscale, dl), (self.likelihood.variance, dn)]
+        natural = [(self.kern.variance, dv), (self.kern.lengthscale, dl), (self.likelihood.variance, dn)]
+        if self.mean_function is not None:
+            # gp.py:270-271: dL_dm = alpha through the mapping's update_gradients -- X^T alpha and 1^T alpha from ONE device call
+            _mappings.set_affine_gradients(self.mean_function, *self._h.mean_grad())
+            natural = [(p, p.gradient) for p in self.mean_function.flattened_parameters()] + natural
+        return natural
 
     def objective_function_gradients(self):
         """Model.objective_function_gradients, core/model.py:112-127: d(-lml)/d(optimizer_array)."""
@@ -399,7 +423,11 @@ class GPRegression(Parameterized):
         return qs
 
     def predictive_gradients(self, Xnew, kern=None):
-        """gp.py:407-454: (dmu_dX [M, D, P], dv_dX [M, D])."""
+        """gp.py:407-454: (dmu_dX [M, D, P], dv_dX [M, D]).
+
+        One stated deviation: with a mean function the reference leaves the mapping's ``gradients_X`` out of dmu_dX
+        (gp.py:429-434 differentiates the kernel term only).  Here dmu_dX -- and ``mean_gradients`` -- include A: the
+        acquisition optimiser follows these gradients, and it must follow the true ones."""
         Xn = np.asarray(Xnew, dtype=float)
         if Xn.ndim == 2 and Xn.shape[0] == 0:
             return np.empty((0, self.input_dim, self.output_dim)), np.empty((0, self.input_dim))
@@ -575,6 +603,8 @@ class GPRegression(Parameterized):
 
     def _lockstep_applies(self, num_restarts):
         npad = -(-self.num_data // 128) * 128
+        if self.mean_function is not None:   # the batch entries refuse a resident mean (members would need means of their own)
+            return False
         return (1 <= num_restarts <= _BATCH_MAX_R and npad <= _BATCH_MAX_NPAD and self.optimizer_array.size > 0
                 and not (self._uses_gower() and self.gower_gradients == 'differences'))
 

@@ -52,13 +52,18 @@ class GPModel(BOModel):
     ``gp_sparse_fit_grad_batch`` per round of L-BFGS steps (``SparseGPRegression.optimize_restarts(parallel=True)``).  There are
     two flags because ``parallel_restarts`` was defined, and is tested, as the exact model's batch: with ``sparse=True`` it keeps
     raising, so that a configuration written for the exact model never silently changes meaning, and the sparse route is asked
-    for by name."""
+    for by name.
+    ``mean_function=<mappings.Mapping>`` (exact model only; an addition) gives the GP an affine trend (``GPRegression(mean_function=
+    ...)``: ``mappings.Linear``, ``Constant`` or an ``Additive`` of those).  The device acquisition routes stay on and see the
+    full mean."""
     analytical_gradient_prediction = True
 
     def __init__(self, kernel=None, noise_var=None, exact_feval=False, optimizer='bfgs', max_iters=1000,
                  optimize_restarts=5, sparse=False, num_inducing=10, verbose=True, ARD=False, Gower=False,
                  space=None, device=0, parallel_restarts=False, device_acquisitions=False, incremental=False,
-                 lockstep_restarts=False):
+                 lockstep_restarts=False, mean_function=None):
+        if sparse and mean_function is not None:
+            raise NotImplementedError("the sparse GP does not take a mean function")
         if sparse and incremental:
             raise ValueError("incremental appends to the exact model's factor: not available with sparse=True")
         if device_acquisitions and not sparse:
@@ -75,7 +80,8 @@ class GPModel(BOModel):
                           max_iters=max_iters, optimize_restarts=optimize_restarts, sparse=sparse,
                           num_inducing=num_inducing, verbose=verbose, ARD=ARD, Gower=Gower, space=space, device=device,
                           parallel_restarts=parallel_restarts, device_acquisitions=bool(device_acquisitions),
-                          incremental=bool(incremental), lockstep_restarts=bool(lockstep_restarts), model=None)
+                          incremental=bool(incremental), lockstep_restarts=bool(lockstep_restarts), mean_function=mean_function,
+                          model=None)
 
     @staticmethod
     def fromConfig(config):
@@ -96,7 +102,7 @@ class GPModel(BOModel):
             gp.device_rows = self.device_acquisitions
         else:
             noise = 0.01 * Y.var() if self.noise_var is None else self.noise_var
-            gp = GPRegression(X, Y, kernel=chosen, noise_var=noise, device=self.device)
+            gp = GPRegression(X, Y, kernel=chosen, noise_var=noise, mean_function=self.mean_function, device=self.device)
         if self.exact_feval:
             gp.Gaussian_noise.constrain_fixed(1e-6, warning=False)
         else:
@@ -183,7 +189,8 @@ class GPModel(BOModel):
                        optimizer=self.optimizer, max_iters=self.max_iters, optimize_restarts=self.optimize_restarts,
                        sparse=self.sparse, num_inducing=self.num_inducing, verbose=self.verbose, ARD=self.ARD, Gower=self.Gower, space=self.space, device=self.device,
                        parallel_restarts=self.parallel_restarts, device_acquisitions=self.device_acquisitions,
-                       incremental=self.incremental, lockstep_restarts=self.lockstep_restarts)
+                       incremental=self.incremental, lockstep_restarts=self.lockstep_restarts,
+                       mean_function=None if self.model.mean_function is None else self.model.mean_function.copy())
         twin._create_model(self.model.X, self.model.Y)
         twin.updateModel(self.model.X, self.model.Y, None, None)
         return twin
@@ -209,7 +216,9 @@ class GPModel_MCMC(BOModel):
     analytical_gradient_prediction = True
 
     def __init__(self, kernel=None, noise_var=None, exact_feval=False, n_samples=10, n_burnin=100, subsample_interval=10,
-                 step_size=1e-1, leapfrog_steps=20, verbose=False, device=0):
+                 step_size=1e-1, leapfrog_steps=20, verbose=False, device=0, mean_function=None):
+        if mean_function is not None:
+            raise NotImplementedError("GPModel_MCMC does not take a mean function (the ensemble entries refuse one)")
         vars(self).update(kernel=kernel, noise_var=noise_var, exact_feval=exact_feval, verbose=verbose, n_samples=n_samples,
                           subsample_interval=subsample_interval, n_burnin=n_burnin, step_size=step_size,
                           leapfrog_steps=leapfrog_steps, device=device, model=None, hmc=None, hmc_samples=None, _fmins=None)

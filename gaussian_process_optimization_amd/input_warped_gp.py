@@ -41,9 +41,10 @@ class InputWarpedGP(GPRegression):
       The size rule is the plain model's: up to 64 restarts and 2048 padded rows, the serial loop beyond."""
 
     _appendable = False    # append_XY refits: the fit of this model is more than the exact GP's factor of (X, Y)
+    _takes_mean_function = False   # the input-gradient entries do not carry a mean function
 
     def __init__(self, X, Y, kernel=None, normalizer=False, warping_function=None, warping_indices=None, Xmin=None, Xmax=None,
-                 epsilon=None, device=0):
+                 epsilon=None, device=0, mean_function=None):
         X = np.asarray(X, dtype=float)
         if X.ndim == 1:
             X = X.reshape(-1, 1)
@@ -55,7 +56,8 @@ class InputWarpedGP(GPRegression):
         self.warping_function = (KumarWarping(self.X_untransformed, warping_indices, epsilon, Xmin, Xmax)
                                  if warping_function is None else warping_function)
         self._warp_signature = None
-        super(InputWarpedGP, self).__init__(X, Y, kernel=kernel, normalizer=normalizer, device=device, name="input warped gp")
+        super(InputWarpedGP, self).__init__(X, Y, kernel=kernel, normalizer=normalizer, mean_function=mean_function, device=device,
+                                            name="input warped gp")
         self.kernel = self.kern
         self.link_parameter(self.warping_function)
 

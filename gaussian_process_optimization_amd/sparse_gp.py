@@ -73,8 +73,9 @@ class SparseGPRegression(GPRegression):
     device_rows = False
 
     _appendable = False    # append_XY refits: the fit of this model is more than the exact GP's factor of (X, Y)
+    _takes_mean_function = False   # the sparse entries do not carry a mean function
 
-    def __init__(self, X, Y, kernel=None, Z=None, num_inducing=10, normalizer=None, device=0, name="sparse_gp"):
+    def __init__(self, X, Y, kernel=None, Z=None, num_inducing=10, normalizer=None, device=0, name="sparse_gp", mean_function=None):
         X = np.asarray(X, dtype=float)
         if X.ndim == 1:
             X = X.reshape(-1, 1)
@@ -90,7 +91,8 @@ class SparseGPRegression(GPRegression):
             raise NotImplementedError("the sparse GP does not take the Gower kernel")
         self.Z = None
         self._table = None          # the candidate table resident in the sparse model's own block (_stage_table)
-        super(SparseGPRegression, self).__init__(X, Y, kernel=kernel, normalizer=normalizer, noise_var=1., device=device, name=name)
+        super(SparseGPRegression, self).__init__(X, Y, kernel=kernel, normalizer=normalizer, noise_var=1., mean_function=mean_function,
+                                                 device=device, name=name)
         self.posterior = _SparsePosteriorView(self)
         self._link_Z(Z)
 

@@ -37,8 +37,9 @@ class WarpedGP(GPRegression):
     * Replica groups are refused."""
 
     _appendable = False    # append_XY refits: the fit of this model is more than the exact GP's factor of (X, Y)
+    _takes_mean_function = False   # the device refuses a mean function beside an output warp
 
-    def __init__(self, X, Y, kernel=None, warping_function=None, warping_terms=3, normalizer=False, device=0):
+    def __init__(self, X, Y, kernel=None, warping_function=None, warping_terms=3, normalizer=False, device=0, mean_function=None):
         X = np.asarray(X, dtype=float)
         if X.ndim == 1:
             X = X.reshape(-1, 1)
@@ -50,7 +51,8 @@ class WarpedGP(GPRegression):
         self.predict_in_warped_space = True
         self._logjac = 0.0
         self._fit_count = 0
-        super(WarpedGP, self).__init__(X, Y, kernel=kernel, normalizer=normalizer, device=device, name="warped gp")
+        super(WarpedGP, self).__init__(X, Y, kernel=kernel, normalizer=normalizer, mean_function=mean_function, device=device,
+                                       name="warped gp")
         if self.output_dim != 1:
             raise ValueError("WarpedGP takes one output column, Y has %d" % self.output_dim)
         self.link_parameter(self.warping_function)

@@ -825,6 +825,42 @@ int gp_cost_set(gp_t *gp, const double *Xc, int64_t Nc, const double *alpha, int
 int gp_cost_info(gp_t *gp, int64_t *Nc);
 int gp_cost_rows(gp_t *gp, const double *Xs, int64_t M, double *logc, double *dlogc);
 
+/* ---- mean function: an affine trend m(x) = x^T A + b under the exact GP ------------------------------------------------------
+ * GPRegression(..., mean_function=...) over GPy's mappings.Linear, mappings.Constant and their Additive sum (core/gp.py:89-95,
+ * 267-271, 293-294; exact_gaussian_inference.py:42-50, 74): the fit runs on Y - m(X), m(x*) is added to the posterior mean, and
+ * dL/dm = alpha is pushed through the mapping's update_gradients.
+ *
+ * gp_mean_set copies A [D, P] (row-major) and b [P] into a buffer of the context's own; either may be NULL (a part that is not
+ * there), both NULL clears the mean.  It needs gp_set_data (GP_ERR_STATE: D and P are the data's), is refused while an output warp
+ * is on (GP_ERR_STATE) and for a non-finite entry (GP_ERR_ARG), and drops what gp_set_params drops: the fit, the cached posterior
+ * and fmin, representers and belief.  The mean survives gp_set_params and a gp_set_data with the same D and P; another D or P drops
+ * it.  While a mean is resident the context keeps the raw targets beside the residuals Y - X A - 1 b^T, which are rebuilt before the
+ * next factorisation whenever the data or the mean changed -- per element from b_p, the D products in dimension order by fma, so
+ * the same inputs give the same bits on every call -- and gp_fit, gp_fit_grad, gp_lml_grad and gp_fit_predict run unchanged on
+ * them: LML, log det, alpha and the hyper-parameter gradients are GPy's with YYT_factor = Y - m.  Always true fp64
+ * ("emulate_fp64" does not apply).  (gp_get_targets hands out what the fit reads: once a fit has run, these residuals.)
+ * gp_mean_info: *has_A / *has_b = 1 where that part is resident (either pointer may be NULL).
+ * gp_mean_grad: dA [D, P] = X^T alpha, db [P] = 1^T alpha of the current fit (either may be NULL; GP_ERR_STATE before a fit; valid
+ * with or without a resident mean).  A two-level sum over N whose order is fixed by one constant (chunks of 256 rows in row order,
+ * the chunks in order): bitwise repeatable, no atomics.
+ *
+ * Posterior: m(x*) joins the mean where it is formed -- behind the reduction of every table route (gp_predict, gp_fit_predict,
+ * gp_predict_full_cov, gp_posterior_samples and the cache the scoring entries read), inside the finish pass of the fused rows
+ * route (gp_predict_rows, gp_acq_rows: instances of their own) -- and A joins dmdx (gp_predict_grad, the rows entries).  So EI /
+ * LCB / MPI values and gradients, arg-best, top-k, the penalised entries and GP_ACQ_PER_COST see the full mean, and gp_fmin is
+ * min_i (y_i - (noise + 1e-8 + jitter) alpha_i) over the RAW targets.  A Gower model takes a mean as any other: m never enters K.
+ * With no mean resident every kernel is launched as before and returns the same bits.
+ *
+ * Refused while a mean is resident (GP_ERR_STATE, the message names the mean function, nothing is launched, the context stays
+ * usable): gp_set_output_warp, gp_warp_grad, gp_fit_grad_warp, gp_predict_warped; the gp_sparse_*, gp_ens_* and gp_es_* entries
+ * (their counters gp_sparse_rows_stats and gp_ens_info still answer); gp_append; gp_fit_grad_batch, gp_fit_grad_x_batch,
+ * gp_fit_grad_warp_batch; gp_lml_grad_x, gp_fit_grad_x, gp_set_candidates_kumar; the gp_group_* entries that touch data, fit or
+ * scores, and gp_comm_init, gp_comm_allgather_best, gp_comm_allgather_topk, gp_comm_bcast_fit.  Their prediction sides do not add
+ * m, or they read the fit's targets as the data. */
+int gp_mean_set(gp_t *gp, const double *A, const double *b);
+int gp_mean_info(gp_t *gp, int *has_A, int *has_b);
+int gp_mean_grad(gp_t *gp, double *dA, double *db);
+
 #ifdef __cplusplus
 }
 #endif
