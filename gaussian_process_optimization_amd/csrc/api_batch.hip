@@ -14,9 +14,11 @@
 // caller's warped X, Members::X at a stride) and adds the input-gradient pass with the member in blockIdx.z (gradx.hip);
 // gp_fit_grad_warp_batch gives every member targets of its own (the raw targets through the member's tanh warp, Members::Y at a
 // stride) and adds the warp's gradient sums, one workgroup per member (warp.hip).
-// Left here: the checks, the carving of the buffers, the per-member parameter tables, which members are factored again in which
-// round of the jitter ladder, and the per-member results.  The batch has buffers of its own: the context's resident fit (L, alpha,
-// Ky^-1, parameters, fitted / predicted state) is left as it was.  Always true fp64 (option "emulate_fp64" does not apply).
+// Left here: the checks, the per-member results, and the front end every batched entry shares -- the per-member parameters
+// (member_params) and the carving of the batch's buffers (batch_members), which the ensemble (api_ens.hip) uses too; which
+// members are factored again in which round of the jitter ladder is members_ladder's (api_factor.hip).  The batch has buffers
+// of its own: the context's resident fit (L, alpha, Ky^-1, parameters, fitted / predicted state) is left as it was.  Always true
+// fp64 (option "emulate_fp64" does not apply).
 #include "api_internal.h"
 
 #define GP_BATCH_MAX_R 64
@@ -34,8 +36,75 @@ struct BatchWarp {            // gp_fit_grad_warp_batch
 };
 #define GP_BATCH_WARP_OUT (1 + GP_WARP_NPSI)   // per member on the device: sum log f', then the 3 T + 1 gradient sums
 
-// The shared body of the three batch entries: checks, the carving of dBatch, the parameter tables, the per-member jitter ladder
-// and the sequence after the factorisation.  `who` names the entry in the messages.
+// ---- the front end of every batched entry (api_internal.h, "members") ------------------------------------------------------------
+int member_params(const gp_ctx *g, int nb, const double *variance, const double *lengthscale, const double *noise,
+                  std::vector<KernParams> *kp) {
+    const int D = g->D, nls = g->ard ? D : 1;
+    for (int r = 0; r < nb; ++r) {
+        if (!(variance[r] > 0.0)) return fail(GP_ERR_ARG, "member %d: variance must be positive", r);
+        if (!(noise[r] > 0.0)) return fail(GP_ERR_ARG, "member %d: noise must be positive", r);
+        for (int d = 0; d < nls; ++d)
+            if (!(lengthscale[(long)r * nls + d] > 0.0)) return fail(GP_ERR_ARG, "member %d: lengthscale must be positive", r);
+    }
+    kp->assign(nb, g->kp);
+    for (int r = 0; r < nb; ++r) {
+        (*kp)[r].variance = variance[r];
+        for (int d = 0; d < D; ++d) (*kp)[r].ls[d] = g->ard ? lengthscale[(long)r * nls + d] : lengthscale[(long)r * nls];
+    }
+    return 0;
+}
+
+int batch_members(gp_ctx *g, const std::vector<KernParams> &kp, const std::vector<double> &diag, long extra, size_t aux_extra,
+                  Members *mp, double **dJit, double **extra_at, signed char **aux_at) {
+    Members &m = *mp;
+    const long Npad = g->Npad;
+    const int R = (int)kp.size(), nt = (int)(Npad / GP_TILE), W = std::min(g->panel_tiles, nt), nJ = (nt + W - 1) / W;
+    const long PB = (long)W * GP_TILE;
+    m.nb = R;
+    m.W = W;
+    m.lda = Npad;
+    m.sA = (Npad + GP_TILE) * Npad;
+    m.sI = (long)nt * GP_TILE * GP_TILE;
+    m.sP = (long)nJ * PB * PB;
+    m.sV = (long)g->P * Npad;
+    m.sT = Npad * Npad;
+    m.sS = SCAL_GRAD.off + SCAL_GRAD.len;   // log det, alpha . y and every gradient pass's sums of a member
+    const long per = m.sA + m.sI + 2 * m.sP + 2 * m.sV + 2 * m.sT + m.sS + 2;
+    int rc;
+    if ((rc = g->dBatch.reserve(per * R + extra))) return rc;
+    const size_t kp_bytes = (sizeof(KernParams) * R + 255) / 256 * 256, info_bytes = (sizeof(int) * 4 * R + 255) / 256 * 256;
+    if ((rc = g->dBatchAux.reserve((long)(aux_extra ? kp_bytes + info_bytes + aux_extra : kp_bytes + sizeof(int) * 4 * R)))) return rc;
+    m.A = g->dBatch;
+    m.invL = m.A + R * m.sA;
+    m.invP = m.invL + R * m.sI;
+    m.invPw = m.invP + R * m.sP;
+    m.alpha = m.invPw + R * m.sP;
+    m.w = m.alpha + R * m.sV;
+    m.T = m.Wi = m.w + R * m.sV;        // the identity, then (zeroed) Ky^-1
+    m.T2 = m.partial = m.T + R * m.sT;  // L^-T, then the gradient partials (free after the product)
+    m.scal = m.T2 + R * m.sT;
+    double *dDiag = m.scal + R * m.sS;
+    *dJit = dDiag + R;
+    *extra_at = *dJit + R;
+    KernParams *dKp = (KernParams *)g->dBatchAux.p;
+    m.info = (int *)(g->dBatchAux + kp_bytes);
+    if (aux_at) *aux_at = g->dBatchAux + kp_bytes + info_bytes;
+    m.kp = kp.data();
+    m.kpt = dKp;
+    m.diag = diag.data();
+    m.diag_tab = dDiag;
+    m.jit_tab = *dJit;
+    // the diagonal-tile kernel writes the lower block triangle of each inverted tile only: the blocks above it must be zero (as
+    // set_data leaves the context's dInvL); the buffer is reused across calls of other shapes, so this is per call
+    HIPCHK(hipMemsetAsync(m.invL, 0, sizeof(double) * m.sI * R, g->s));
+    HIPCHK(hipMemcpyAsync(dKp, kp.data(), sizeof(KernParams) * R, hipMemcpyHostToDevice, g->s));
+    HIPCHK(hipMemcpyAsync(dDiag, diag.data(), sizeof(double) * R, hipMemcpyHostToDevice, g->s));
+    return 0;
+}
+
+// The shared body of the three batch entries: checks, the members over dBatch (batch_members) with the warped models' blocks
+// behind them, the per-member jitter ladder (ky_ladder) and the sequence after the factorisation.  `who` names the entry in the
+// messages.
 static int fit_grad_members(gp_ctx *g, const char *who, int R, const double *variance, const double *lengthscale, const double *noise,
                             int maxtries, double *lml, double *logdet, double *jitter_used, double *dvariance, double *dlengthscale,
                             double *dnoise, int *status, const BatchInputs *bx, const BatchWarp *bw) {
@@ -58,12 +127,8 @@ static int fit_grad_members(gp_ctx *g, const char *who, int R, const double *var
     if (bw && (bw->n_terms < 1 || bw->n_terms > GP_WARP_MAX_TERMS))
         return fail(GP_ERR_ARG, "%s takes a warp of 1..%d terms", who, GP_WARP_MAX_TERMS);
     const int D = g->D, nls = g->ard ? D : 1;
-    for (int r = 0; r < R; ++r) {
-        if (!(variance[r] > 0.0)) return fail(GP_ERR_ARG, "member %d: variance must be positive", r);
-        if (!(noise[r] > 0.0)) return fail(GP_ERR_ARG, "member %d: noise must be positive", r);
-        for (int d = 0; d < nls; ++d)
-            if (!(lengthscale[(long)r * nls + d] > 0.0)) return fail(GP_ERR_ARG, "member %d: lengthscale must be positive", r);
-    }
+    std::vector<KernParams> kp;   // per-member parameters
+    if (int e = member_params(g, R, variance, lengthscale, noise, &kp)) return e;
     std::vector<WarpParams> wp;
     if (bw) {
         wp.resize(R);
@@ -85,100 +150,36 @@ static int fit_grad_members(gp_ctx *g, const char *who, int R, const double *var
     HIPCHK(hipSetDevice(g->device));
 
     const long N = g->N, Npad = g->Npad;
-    const int P = g->P, nt = (int)(Npad / GP_TILE), W = std::min(g->panel_tiles, nt), nJ = (nt + W - 1) / W;
-    const long PB = (long)W * GP_TILE;
-    Members m;
-    m.nb = R;
-    m.W = W;
-    m.lda = Npad;
-    m.sA = (Npad + GP_TILE) * Npad;
-    m.sI = (long)nt * GP_TILE * GP_TILE;
-    m.sP = (long)nJ * PB * PB;
-    m.sV = (long)P * Npad;
-    m.sT = Npad * Npad;
-    m.sS = SCAL_GRAD.off + SCAL_GRAD.len;   // log det, alpha . y and every gradient pass's sums of a member
-    const long per = m.sA + m.sI + 2 * m.sP + 2 * m.sV + 2 * m.sT + m.sS + 2;
+    const int P = g->P, nt = (int)(Npad / GP_TILE);
     // behind the plain batch's members: the warp's results and the members' targets, or the members' inputs
     const long sX = bx ? N * D : 0, sY = bw ? Npad : 0, sWo = bw ? GP_BATCH_WARP_OUT : 0;
     // the input-gradient pass puts its partials into the member's T2 block (free once the gradient passes' own partials are
     // summed).  With its rows behind them it would still fit -- (ceil(nt / 4) 16 + D) Npad <= (16 nt + 64) Npad <= 128 nt Npad =
     // Npad^2 for every nt >= 1, Npad = 128 with D = 64 included: 2048 + 8192 of 16384 -- but the rows go to a block of their
     // own, [R, N, D] as the caller wants them, so that they leave in one contiguous copy
-    if (bx && gradx_partial_elems(Npad) > m.sT) return fail(GP_ERR_STATE, "%s: the input-gradient partials do not fit a member's block", who);
-    int rc;
-    if ((rc = g->dBatch.reserve((per + 2 * sX + sY + sWo) * R))) return rc;
-    const size_t kp_bytes = (sizeof(KernParams) * R + 255) / 256 * 256, info_bytes = (sizeof(int) * 4 * R + 255) / 256 * 256;
-    if ((rc = g->dBatchAux.reserve((long)(bw ? kp_bytes + info_bytes + sizeof(WarpParams) * R : kp_bytes + sizeof(int) * 4 * R))))
-        return rc;
-    m.A = g->dBatch;
-    m.invL = m.A + R * m.sA;
-    m.invP = m.invL + R * m.sI;
-    m.invPw = m.invP + R * m.sP;
-    m.alpha = m.invPw + R * m.sP;
-    m.w = m.alpha + R * m.sV;
-    m.T = m.Wi = m.w + R * m.sV;        // the identity, then (zeroed) Ky^-1
-    m.T2 = m.partial = m.T + R * m.sT;  // L^-T, then the gradient partials (free after the product)
-    m.scal = m.T2 + R * m.sT;
-    double *dDiag = m.scal + R * m.sS, *dJit = dDiag + R;
-    double *dWarpOut = dJit + R, *dYb = dWarpOut + R * sWo, *dXb = dYb + R * sY, *dGx = dXb + R * sX;
-    KernParams *dKp = (KernParams *)g->dBatchAux.p;
-    m.info = (int *)(g->dBatchAux + kp_bytes);
-    WarpParams *dWp = bw ? (WarpParams *)(g->dBatchAux + kp_bytes + info_bytes) : nullptr;   // beside kpt: the members' warps
+    if (bx && gradx_partial_elems(Npad) > Npad * Npad) return fail(GP_ERR_STATE, "%s: the input-gradient partials do not fit a member's block", who);
+    std::vector<double> diag(R), diag0(R), jit(R, 0.0);
+    for (int r = 0; r < R; ++r) ky_diag(kp[r], noise[r], &diag[r], &diag0[r]);
+    Members m;
+    double *dJit, *dWarpOut;
+    signed char *aux;
+    if (int rc = batch_members(g, kp, diag, (2 * sX + sY + sWo) * R, bw ? sizeof(WarpParams) * R : 0, &m, &dJit, &dWarpOut, &aux)) return rc;
+    double *dYb = dWarpOut + R * sWo, *dXb = dYb + R * sY, *dGx = dXb + R * sX;
+    WarpParams *dWp = bw ? (WarpParams *)aux : nullptr;   // beside kpt: the members' warps
     const double *dYraw = g->warp.n > 0 ? g->dYraw.p : g->dY.p;   // the RAW targets (dY holds f of them while a warp is on)
     m.X = bx ? dXb : g->dX.p;
     m.sX = sX;
     m.Y = bw ? dYb : g->dY.p;
     m.sY = sY;
-
-    // per-member parameters: the context's kernel, dimension and Gower set-up with the member's variance / lengthscale(s)
-    std::vector<KernParams> kp(R, g->kp);
-    std::vector<double> diag(R), diag0(R), jit(R, 0.0);
-    for (int r = 0; r < R; ++r) {
-        kp[r].variance = variance[r];
-        for (int d = 0; d < D; ++d) kp[r].ls[d] = g->ard ? lengthscale[(long)r * nls + d] : lengthscale[(long)r * nls];
-        ky_diag(kp[r], noise[r], &diag[r], &diag0[r]);
-    }
-    m.kp = kp.data();
-    m.kpt = dKp;
-    m.diag = diag.data();
-    m.diag_tab = dDiag;
     m.jit = jit.data();
-    m.jit_tab = dJit;
-    // the diagonal-tile kernel writes the lower block triangle of each inverted tile only: the blocks above it must be zero (as
-    // set_data leaves the context's dInvL); the buffer is reused across calls of other shapes, so this is per call
-    HIPCHK(hipMemsetAsync(m.invL, 0, sizeof(double) * m.sI * R, g->s));
-    HIPCHK(hipMemcpyAsync(dKp, kp.data(), sizeof(KernParams) * R, hipMemcpyHostToDevice, g->s));
-    HIPCHK(hipMemcpyAsync(dDiag, diag.data(), sizeof(double) * R, hipMemcpyHostToDevice, g->s));
     if (bx) HIPCHK(hipMemcpyAsync(dXb, bx->Xw, sizeof(double) * sX * R, hipMemcpyHostToDevice, g->s));   // the members' inputs, one copy
     if (bw) {   // the members' targets Y_z = f_z(Y_raw) and sum log f_z'
         HIPCHK(hipMemcpyAsync(dWp, wp.data(), sizeof(WarpParams) * R, hipMemcpyHostToDevice, g->s));
         launch_warp_y_members(g->s, dYraw, N, dWp, dYb, sY, dWarpOut, sWo, R);
     }
 
-    // jitter ladder per member (ladder_step, as fit_impl): a member whose factorisation fails is factored again with the next
-    // jitter, alone with the other failed members (runs of consecutive members share launches); the others keep their factor
-    std::vector<int> tries(R, 0), active(R, 1), st(R, 0), info(4 * R);
-    for (int round = 0;; ++round) {
-        if (round > 0) HIPCHK(hipMemcpyAsync(dJit, jit.data(), sizeof(double) * R, hipMemcpyHostToDevice, g->s));
-        for (int m0 = 0, m1; m0 < R; m0 = m1 + 1) {   // [m0, m1): a run of consecutive active members
-            for (m1 = m0; m1 < R && active[m1];) ++m1;
-            if (m1 == m0) continue;
-            const Members run = members_range(m, m0, m1 - m0);
-            build_ky(g, run, round > 0);
-            GP_NOTE(hipMemsetAsync(run.info, 0, sizeof(int) * 4 * run.nb, g->s));
-            factor_buf(g, run, nt, nt + 1);
-        }
-        HIPCHK(hipMemcpyAsync(info.data(), m.info, sizeof(int) * 4 * R, hipMemcpyDeviceToHost, g->s));
-        GP_SYNC(g->s);
-        bool again = false;
-        for (int r = 0; r < R; ++r) {
-            if (!active[r]) continue;
-            if (info[4 * r] != 0) st[r] = ladder_step(diag0[r], maxtries, info[4 * r], &jit[r], &tries[r]);   // gp_fit_grad's code
-            active[r] = info[4 * r] != 0 && st[r] == 0;
-            again = again || active[r];
-        }
-        if (!again) break;
-    }
+    std::vector<int> st(R, 0);
+    if (int rc = ky_ladder(g, m, maxtries, diag0, jit, dJit, st)) return rc;
 
     // everything after the factorisation: all members in the same launches (a failed member's numbers are computed and dropped)
     panel_inv_members(g, m);

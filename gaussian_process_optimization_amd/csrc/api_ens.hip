@@ -37,102 +37,34 @@ extern "C" int gp_ens_fit(gp_t *g, int S, const double *variance, const double *
     if (g->kp.gower)   // the lengthscale does not enter a Gower K: sampling it is sampling its prior
         return fail(GP_ERR_STATE, "gp_ens_fit: the Gower option is on (gp_set_gower)");
     if (g->warp.n > 0) return fail(GP_ERR_STATE, "gp_ens_fit: an output warp is on (gp_set_output_warp)");
-    const int D = g->D, nls = g->ard ? D : 1;
-    for (int r = 0; r < S; ++r) {
-        if (!(variance[r] > 0.0)) return fail(GP_ERR_ARG, "member %d: variance must be positive", r);
-        if (!(noise[r] > 0.0)) return fail(GP_ERR_ARG, "member %d: noise must be positive", r);
-        for (int d = 0; d < nls; ++d)
-            if (!(lengthscale[(long)r * nls + d] > 0.0)) return fail(GP_ERR_ARG, "member %d: lengthscale must be positive", r);
-    }
+    std::vector<KernParams> kp;
+    if (int e = member_params(g, S, variance, lengthscale, noise, &kp)) return e;
     HIPCHK(hipSetDevice(g->device));
     EnsState &en = g->ens;
     en.S = 0;   // invalid until every member is factored and kept
 
     const long N = g->N, Npad = g->Npad;
-    const int P = 1, nt = (int)(Npad / GP_TILE), W = std::min(g->panel_tiles, nt), nJ = (nt + W - 1) / W;
-    const long PB = (long)W * GP_TILE;
-    // the batched fit's scratch (api_batch.hip), without Ky^-1 and the gradient passes; behind it the training mean of one member
-    Members m;
-    m.nb = S;
-    m.W = W;
-    m.lda = Npad;
-    m.sA = (Npad + GP_TILE) * Npad;
-    m.sI = (long)nt * GP_TILE * GP_TILE;
-    m.sP = (long)nJ * PB * PB;
-    m.sV = (long)P * Npad;
-    m.sT = Npad * Npad;
-    m.sS = SCAL_GRAD.off + SCAL_GRAD.len;
-    const long per = m.sA + m.sI + 2 * m.sP + 2 * m.sV + 2 * m.sT + m.sS + 2;
+    const int P = 1, nt = (int)(Npad / GP_TILE);
     int rc;
-    if ((rc = g->dBatch.reserve(per * S + Npad))) return rc;
-    const size_t kp_bytes = (sizeof(KernParams) * S + 255) / 256 * 256;
-    if ((rc = g->dBatchAux.reserve((long)(kp_bytes + sizeof(int) * 4 * S)))) return rc;
     if ((rc = en.dLi.reserve((long)S * Npad * Npad))) return rc;
     if ((rc = en.dAlpha.reserve((long)S * Npad))) return rc;
     if ((rc = en.dTab.reserve(2 * GP_ENS_MAX_S))) return rc;
     if ((rc = en.dKp.reserve((long)sizeof(KernParams) * GP_ENS_MAX_S))) return rc;
-    m.A = g->dBatch;
-    m.invL = m.A + S * m.sA;
-    m.invP = m.invL + S * m.sI;
-    m.invPw = m.invP + S * m.sP;
-    m.alpha = m.invPw + S * m.sP;
-    m.w = m.alpha + S * m.sV;
-    m.T = m.Wi = m.w + S * m.sV;
-    m.T2 = m.partial = m.T + S * m.sT;
-    m.scal = m.T2 + S * m.sT;
-    double *dDiag = m.scal + S * m.sS, *dJit = dDiag + S, *dMu = dJit + S;
-    KernParams *dKp = (KernParams *)g->dBatchAux.p;
-    m.info = (int *)(g->dBatchAux + kp_bytes);
-
-    std::vector<KernParams> kp(S, g->kp);
     std::vector<double> diag(S), diag0(S), jit(S, 0.0);
-    for (int r = 0; r < S; ++r) {
-        kp[r].variance = variance[r];
-        for (int d = 0; d < D; ++d) kp[r].ls[d] = g->ard ? lengthscale[(long)r * nls + d] : lengthscale[(long)r * nls];
-        ky_diag(kp[r], noise[r], &diag[r], &diag0[r]);
-    }
-    m.kp = kp.data();
-    m.kpt = dKp;
-    m.diag = diag.data();
-    m.diag_tab = dDiag;
-    m.jit = jit.data();
-    m.jit_tab = dJit;
+    for (int r = 0; r < S; ++r) ky_diag(kp[r], noise[r], &diag[r], &diag0[r]);
+    // the batched fit's members (batch_members), used without Ky^-1 and the gradient passes; behind them the training mean of one
+    Members m;
+    double *dJit, *dMu;
+    if ((rc = batch_members(g, kp, diag, Npad, 0, &m, &dJit, &dMu, nullptr))) return rc;
     m.X = g->dX;   // shared by the members: strides 0
     m.Y = g->dY;
-    HIPCHK(hipMemsetAsync(m.invL, 0, sizeof(double) * m.sI * S, g->s));
-    HIPCHK(hipMemcpyAsync(dKp, kp.data(), sizeof(KernParams) * S, hipMemcpyHostToDevice, g->s));
-    HIPCHK(hipMemcpyAsync(dDiag, diag.data(), sizeof(double) * S, hipMemcpyHostToDevice, g->s));
+    m.jit = jit.data();
 
-    // the per-member jitter ladder of gp_fit_grad_batch: failed members are factored again, the others keep their factor
-    std::vector<int> tries(S, 0), active(S, 1), st(S, 0), info(4 * S);
-    for (int round = 0;; ++round) {
-        if (round > 0) HIPCHK(hipMemcpyAsync(dJit, jit.data(), sizeof(double) * S, hipMemcpyHostToDevice, g->s));
-        for (int m0 = 0, m1; m0 < S; m0 = m1 + 1) {
-            for (m1 = m0; m1 < S && active[m1];) ++m1;
-            if (m1 == m0) continue;
-            const Members run = members_range(m, m0, m1 - m0);
-            build_ky(g, run, round > 0);
-            GP_NOTE(hipMemsetAsync(run.info, 0, sizeof(int) * 4 * run.nb, g->s));
-            factor_buf(g, run, nt, nt + 1);
-        }
-        HIPCHK(hipMemcpyAsync(info.data(), m.info, sizeof(int) * 4 * S, hipMemcpyDeviceToHost, g->s));
-        GP_SYNC(g->s);
-        bool again = false;
-        for (int r = 0; r < S; ++r) {
-            if (!active[r]) continue;
-            if (info[4 * r] != 0) st[r] = ladder_step(diag0[r], maxtries, info[4 * r], &jit[r], &tries[r]);
-            active[r] = info[4 * r] != 0 && st[r] == 0;
-            again = again || active[r];
-        }
-        if (!again) break;
-    }
-    for (int r = 0; r < S; ++r) {   // one member that cannot be factored fails the call: the ensemble stays invalid
-        if (st[r] == GP_ERR_NOT_PD_DIAG) return fail(st[r], "not pd: non-positive diagonal elements");
-        if (st[r]) {
-            g_err = "not positive definite, even with jitter.";
-            return st[r];
-        }
-    }
+    // the per-member jitter ladder; one member that cannot be factored fails the call: the ensemble stays invalid
+    std::vector<int> st(S, 0);
+    if ((rc = ky_ladder(g, m, maxtries, diag0, jit, dJit, st))) return rc;
+    for (int r = 0; r < S; ++r)
+        if ((rc = ladder_failure(st[r]))) return rc;
 
     panel_inv_members(g, m);
     alpha_lml(g, g->s, m);

@@ -368,6 +368,59 @@ int ladder_step(double diag0, int maxtries, int info, double *jitter, int *tries
     if (*tries > maxtries || !std::isfinite(*jitter)) return info > 0 ? info : 1;
     return 0;
 }
+int ladder_failure(int st) {
+    if (st == GP_ERR_NOT_PD_DIAG) return fail(st, "not pd: non-positive diagonal elements");
+    if (st) g_err = "not positive definite, even with jitter.";
+    return st;
+}
+// the ladder per member (api_internal.h): runs of consecutive failed members share launches
+int members_ladder(gp_ctx *g, const Members &m, int nt, int maxtries, std::vector<int> &active, std::vector<double> &jit, double *dJit,
+                   std::vector<int> &st, const MembersBuild &build, const MembersDiag0 &diag0) {
+    const int R = m.nb;
+    std::vector<int> tries(R, 0), info(4 * (size_t)R);
+    std::vector<double> d0(R, 0.0);
+    for (int round = 0;; ++round) {
+        if (round > 0 && dJit) HIPCHK(hipMemcpyAsync(dJit, jit.data(), sizeof(double) * R, hipMemcpyHostToDevice, g->s));
+        for (int m0 = 0, m1; m0 < R; m0 = m1 + 1) {   // [m0, m1): a run of consecutive active members
+            for (m1 = m0; m1 < R && active[m1];) ++m1;
+            if (m1 == m0) continue;
+            const Members run = members_range(m, m0, m1 - m0);
+            if (int rc = build(run, m0, round > 0)) return rc;
+            HIPCHK(hipMemsetAsync(run.info, 0, sizeof(int) * 4 * run.nb, g->s));
+            factor_buf(g, run, nt, nt + 1);
+        }
+        HIPCHK(hipMemcpyAsync(info.data(), m.info, sizeof(int) * 4 * R, hipMemcpyDeviceToHost, g->s));
+        GP_SYNC(g->s);
+        if (round == 0) {
+            std::vector<int> failed;
+            for (int r = 0; r < R; ++r)
+                if (active[r] && info[4 * r] != 0) failed.push_back(r);
+            if (int rc = failed.empty() ? 0 : diag0(failed, d0)) return rc;
+        }
+        bool again = false;
+        for (int r = 0; r < R; ++r) {
+            if (!active[r]) continue;
+            if (info[4 * r] != 0) st[r] = ladder_step(d0[r], maxtries, info[4 * r], &jit[r], &tries[r]);
+            active[r] = info[4 * r] != 0 && st[r] == 0;
+            again = again || active[r];
+        }
+        if (!again) return 0;
+    }
+}
+// the exact model's: every member of m, Ky by build_ky (which adds the jitter and sets the RHS rows), diag0 from ky_diag
+int ky_ladder(gp_ctx *g, const Members &m, int maxtries, const std::vector<double> &diag0, std::vector<double> &jit, double *dJit,
+              std::vector<int> &st) {
+    std::vector<int> active(m.nb, 1);
+    return members_ladder(g, m, (int)(g->Npad / GP_TILE), maxtries, active, jit, dJit, st,
+                          [&](const Members &run, int, bool jittered) {
+                              build_ky(g, run, jittered);
+                              return 0;
+                          },
+                          [&](const std::vector<int> &failed, std::vector<double> &d0) {
+                              for (int r : failed) d0[r] = diag0[r];
+                              return 0;
+                          });
+}
 // scal: [0] log det, [8, 8 + P) alpha . y
 double lml_from_scalars(long N, int P, const double *scal) {
     double fit = 0.0;

@@ -586,6 +586,38 @@ static inline GemmOpt member_opt(const Members &m, GemmOpt o, long sC, long sA, 
     o.sB = sB;
     return o;
 }
+// The front end the batched entries share (api_batch.hip).
+// member_params: variance[r], noise[r] and member r's lengthscale(s) are positive (GP_ERR_ARG names the member), then kp[r] = the
+// context's kernel, dimension and Gower set-up with member r's variance and lengthscale(s).  Host only: nothing is reserved or
+// launched.
+int member_params(const gp_ctx *g, int nb, const double *variance, const double *lengthscale, const double *noise,
+                  std::vector<KernParams> *kp);
+// batch_members: kp.size() exact-model members over g->dBatch / g->dBatchAux -- the strides, every operand group of *m with the
+// members side by side, the parameter, diagonal and jitter tables (m->kpt, diag_tab, jit_tab; *dJit the last, to write), m->info
+// behind the parameter table.  On g->s: m->invL is zeroed, kp and diag (m->kp, m->diag: they outlive m) go to their tables.
+// Behind the members the caller's own `extra` doubles from *extra_at on and, behind the (then 256-byte padded) info words, its
+// `aux_extra` bytes at *aux_at (may be null without any).  m->jit, X and Y are the caller's.
+int batch_members(gp_ctx *g, const std::vector<KernParams> &kp, const std::vector<double> &diag, long extra, size_t aux_extra,
+                  Members *m, double **dJit, double **extra_at, signed char **aux_at);
+// members_ladder: one jitter ladder (GPy/GPy/util/linalg.py:56-81) per member of m, those with active[r] set, factored in place
+// in the members' A with nt tile columns and one RHS tile row below.  A round: for each run of consecutive active members,
+// build(run, m0, jittered) writes everything the factorisation reads (the jitter of the attempt, jit[r] -- m.jit on the host, in
+// dJit = m.jit_tab when given -- and the RHS rows included), the run's status words are cleared and factor_buf runs; then one
+// copy of the status words and one synchronisation, and ladder_step per failed member: a failed member is factored again with the
+// next jitter, alone with the other failed members, the others keep their factor.  diag0(failed, d0) is called once, after the
+// first round when members failed, and fills d0[r], the mean diagonal the ladder starts from, for them.  Leaves st[r] (0, or the
+// code the single call ends with) and jit[r] (the jitter of the member's last attempt); `active` is consumed.
+// Deliberately NOT callers: fit_impl's ladder (api_factor.hip) and the posterior covariance's (api_predict.hip), which wrap the
+// look-ahead scheduler with its pipes and a covariance that is not a Members problem.
+using MembersBuild = std::function<int(const Members &run, int m0, bool jittered)>;
+using MembersDiag0 = std::function<int(const std::vector<int> &failed, std::vector<double> &d0)>;
+int members_ladder(gp_ctx *g, const Members &m, int nt, int maxtries, std::vector<int> &active, std::vector<double> &jit, double *dJit,
+                   std::vector<int> &st, const MembersBuild &build, const MembersDiag0 &diag0);
+// ... as the exact model's members take it: all of m's, Ky by build_ky, diag0[r] known beforehand (ky_diag)
+int ky_ladder(gp_ctx *g, const Members &m, int maxtries, const std::vector<double> &diag0, std::vector<double> &jit, double *dJit,
+              std::vector<int> &st);
+// a member's non-zero status as the error of a call that one failed member fails
+int ladder_failure(int st);
 
 // Pipelined candidate solve (gp_fit_predict): as soon as panel J of L is final (chain(J) done), two more
 // streams run, behind the factorisation and at low priority,

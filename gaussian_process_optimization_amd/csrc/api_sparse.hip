@@ -91,33 +91,25 @@ static int sparse_chol(gp_ctx *g, double *A, double *invT, double *LiT, Build bu
     SparseState &sp = g->sp;
     const long n = sp.Mzpad;
     const int ntz = (int)(n / GP_TILE);
-    Members m;
+    Members m;   // one member: the ladder of the batched fits (members_ladder) with nb = 1
     m.A = A;
     m.lda = n;
     m.invL = invT;
     m.info = sp.dInfo;
-    double jitter = 0.0, d0 = 0.0;
-    int tries = 0, info = 0, rc;
+    std::vector<int> active(1, 1), st(1, 0);
+    std::vector<double> jit(1, 0.0);
     // the diagonal-tile kernel writes the lower block triangle of each inverted tile only: the blocks above it must be zero
     HIPCHK(hipMemsetAsync(invT, 0, sizeof(double) * n * GP_TILE, g->s));
-    for (;;) {
-        build();
-        if (tries > 0) launch_add_diag(g->s, A, n, sp.Mz, jitter);
-        HIPCHK(hipMemsetAsync(A + n * n, 0, sizeof(double) * GP_TILE * n, g->s));
-        HIPCHK(hipMemsetAsync(sp.dInfo, 0, sizeof(int) * 4, g->s));
-        factor_buf(g, m, ntz, ntz + 1);
-        HIPCHK(hipMemcpyAsync(&info, sp.dInfo, sizeof(int), hipMemcpyDeviceToHost, g->s));
-        GP_SYNC(g->s);
-        if (info == 0) break;
-        if (tries == 0 && (rc = diag0(&d0))) return rc;
-        const int rcl = ladder_step(d0, maxtries, info, &jitter, &tries);
-        if (rcl == GP_ERR_NOT_PD_DIAG) return fail(rcl, "not pd: non-positive diagonal elements");
-        if (rcl) {
-            g_err = "not positive definite, even with jitter.";
-            return rcl;
-        }
-    }
-    *jitter_out = jitter;
+    int rc = members_ladder(g, m, ntz, maxtries, active, jit, nullptr, st,
+                            [&](const Members &, int, bool jittered) {
+                                build();
+                                if (jittered) launch_add_diag(g->s, A, n, sp.Mz, jit[0]);
+                                HIPCHK(hipMemsetAsync(A + n * n, 0, sizeof(double) * GP_TILE * n, g->s));
+                                return 0;
+                            },
+                            [&](const std::vector<int> &, std::vector<double> &d0) { return diag0(&d0[0]); });
+    if (rc || (rc = ladder_failure(st[0]))) return rc;
+    *jitter_out = jit[0];
     launch_set_identity_blocks(g->s, LiT, n, 1);
     panel_inv_steps(g, g->s, LiT, n, A, n, invT, ntz, GemmOpt(), 0, 0);
     return 0;

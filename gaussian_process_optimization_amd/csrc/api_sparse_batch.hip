@@ -8,9 +8,9 @@
 // pass of sparse.hip, the batch dimension of the GEMM.  A launch over members runs the body of the single call's kernel, and
 // gemm() takes the instance it picks for ONE member's tiles: a member does the single call's arithmetic, bit for bit, whatever R,
 // its slot and its company.  woodbury_inv, which no output of this call depends on, is not formed.
-// Both jitter ladders (Kmm, then B) are per member as in fit_grad_members (api_batch.hip): a failed member is factored again with
-// the next jitter, alone with the other failed members -- runs of consecutive members share launches --, one copy of the info
-// words and one synchronisation per round.  A member whose ladder ends without a factor keeps running through the later launches
+// Both jitter ladders (Kmm, then B) are members_ladder (api_internal.h), the one the exact batch and the ensemble run: a failed
+// member is factored again with the next jitter, alone with the other failed members -- runs of consecutive members share launches
+// --, one copy of the info words and one synchronisation per round.  A member whose ladder ends without a factor keeps running through the later launches
 // on whatever its buffers hold (no index depends on a value); its numbers are dropped and its outputs are NaN.
 // Buffers: g->dSpBatch / dSpBatchAux, carved below, operand group by operand group with the members side by side.  Nothing of
 // the context's sparse state (g->sp), of the exact model or of the exact batch is read or written; no validity flag moves.
@@ -80,47 +80,6 @@ extern "C" int gp_sparse_batch_bytes(gp_t *g, int R, int64_t Mz, int64_t *bytes)
     return 0;
 }
 
-// One jitter ladder (linalg.py:56-81) over m's members, those with active[r] set: build(run) writes the matrices of a run of
-// consecutive members, diag0(failed) fills d0 for the members whose first attempt failed.  st[r]: 0, or the code the single call
-// ends with; jit[r]: the jitter the member's last attempt ran with.
-template <class Build, class Diag0>
-static int spb_ladder(gp_ctx *g, const Members &m, long n, long Mz, int maxtries, std::vector<int> &active, std::vector<double> &jit,
-                      double *dJit, std::vector<int> &st, Build build, Diag0 diag0) {
-    const int R = m.nb, ntz = (int)(n / GP_TILE);
-    std::vector<int> tries(R, 0), info(4 * (size_t)R);
-    std::vector<double> d0(R, 0.0);
-    for (int round = 0;; ++round) {
-        if (round > 0) HIPCHK(hipMemcpyAsync(dJit, jit.data(), sizeof(double) * R, hipMemcpyHostToDevice, g->s));
-        for (int m0 = 0, m1; m0 < R; m0 = m1 + 1) {   // [m0, m1): a run of consecutive active members
-            for (m1 = m0; m1 < R && active[m1];) ++m1;
-            if (m1 == m0) continue;
-            const Members run = members_range(m, m0, m1 - m0);
-            build(run, m0);
-            if (round > 0) launch_add_diag(g->s, run.A, n, Mz, run.jit[0], run.nb, run.sA, run.jit_tab);
-            // the zero RHS tile row below each member's matrix
-            HIPCHK(hipMemset2DAsync(run.A + n * n, sizeof(double) * m.sA, 0, sizeof(double) * GP_TILE * n, run.nb, g->s));
-            HIPCHK(hipMemsetAsync(run.info, 0, sizeof(int) * 4 * run.nb, g->s));
-            factor_buf(g, run, ntz, ntz + 1);
-        }
-        HIPCHK(hipMemcpyAsync(info.data(), m.info, sizeof(int) * 4 * R, hipMemcpyDeviceToHost, g->s));
-        GP_SYNC(g->s);
-        if (round == 0) {
-            std::vector<int> failed;
-            for (int r = 0; r < R; ++r)
-                if (active[r] && info[4 * r] != 0) failed.push_back(r);
-            if (int rc = failed.empty() ? 0 : diag0(failed, d0)) return rc;
-        }
-        bool again = false;
-        for (int r = 0; r < R; ++r) {
-            if (!active[r]) continue;
-            if (info[4 * r] != 0) st[r] = ladder_step(d0[r], maxtries, info[4 * r], &jit[r], &tries[r]);
-            active[r] = info[4 * r] != 0 && st[r] == 0;
-            again = again || active[r];
-        }
-        if (!again) return 0;
-    }
-}
-
 extern "C" int gp_sparse_fit_grad_batch(gp_t *g, int R, int64_t Mz, const double *Z, const double *variance, const double *lengthscale,
                                         const double *noise, int maxtries, double *lml, double *jitter_kmm, double *jitter_b,
                                         double *dvariance, double *dlengthscale, double *dnoise, double *dZ, int *status) {
@@ -134,12 +93,8 @@ extern "C" int gp_sparse_fit_grad_batch(gp_t *g, int R, int64_t Mz, const double
         return fail(GP_ERR_ARG, "gp_sparse_fit_grad_batch: D = %d, P = %d need %zu bytes of LDS per workgroup in the gradient pass, the device has %ld",
                     g->D, g->P, sparse_grad_lds_bytes(g->D, g->P), g->lds_per_wg);
     const int D = g->D, P = g->P, nls = g->ard ? D : 1;
-    for (int r = 0; r < R; ++r) {
-        if (!(variance[r] > 0.0)) return fail(GP_ERR_ARG, "member %d: variance must be positive", r);
-        if (!(noise[r] > 0.0)) return fail(GP_ERR_ARG, "member %d: noise must be positive", r);
-        for (int d = 0; d < nls; ++d)
-            if (!(lengthscale[(long)r * nls + d] > 0.0)) return fail(GP_ERR_ARG, "member %d: lengthscale must be positive", r);
-    }
+    std::vector<KernParams> kp;   // per-member parameters
+    if ((rc = member_params(g, R, variance, lengthscale, noise, &kp))) return rc;
     const SpbLayout L = spb_layout(g, R, Mz);
     const int64_t bytes = (int64_t)L.total * (int64_t)sizeof(double) + (int64_t)L.aux_bytes;
     if (bytes > GP_SPARSE_BATCH_MAX_BYTES)
@@ -164,12 +119,9 @@ extern "C" int gp_sparse_fit_grad_batch(gp_t *g, int R, int64_t Mz, const double
     const long sT = L.sT, sR = L.sR, sK = L.sK, sVec = L.sVec;
     double *vec0 = Vec, *vec1 = vec0 + (long)P * n, *vec2 = vec1 + (long)P * n, *vec3 = vec2 + (long)P * n;
 
-    // per-member parameters and the coefficient tables (host arithmetic as the single call's)
-    std::vector<KernParams> kp(R, g->kp);
+    // the coefficient tables (host arithmetic as the single call's)
     std::vector<double> tab((size_t)SPB_NTAB * R, 0.0), beta(R), diag(R, 1e-8);
     for (int r = 0; r < R; ++r) {
-        kp[r].variance = variance[r];
-        for (int d = 0; d < D; ++d) kp[r].ls[d] = g->ard ? lengthscale[(long)r * nls + d] : lengthscale[(long)r * nls];
         beta[r] = 1.0 / std::max(noise[r], 1e-8);   // var_dtc.py:80
         tab[(size_t)SPB_TAB_BETA * R + r] = beta[r];
         tab[(size_t)SPB_TAB_HBETA * R + r] = -0.5 * P * beta[r];
@@ -181,27 +133,6 @@ extern "C" int gp_sparse_fit_grad_batch(gp_t *g, int R, int64_t Mz, const double
     HIPCHK(hipMemcpyAsync(dZin, Z, sizeof(double) * L.sZ * R, hipMemcpyHostToDevice, s));
     // the diagonal-tile kernel writes the lower block triangle of each inverted tile only: the blocks above it must be zero
     HIPCHK(hipMemsetAsync(InvM, 0, sizeof(double) * L.sI * 2 * R, s));
-    auto mo = [&](long sC, long sA, long sB) {
-        GemmOpt o;
-        o.batch = o.members = R;
-        o.sC = sC;
-        o.sA = sA;
-        o.sB = sB;
-        return o;
-    };
-    auto nt_square = [&](double *C, const double *A, const double *B) {
-        gemm(g, s, 0, C, n, A, n, B, n, 1, (int)n, TileSet{0, ntz, 0, ntz, 0}, mo(sT, sT, sT));
-    };
-    auto both_sides = [&](double *S, const double *LiT, const double *M) {   // S = L^-T M L^-1 (M symmetric)
-        nt_square(Tmp2, LiT, M);
-        nt_square(S, Tmp2, LiT);
-    };
-    auto inverse_T = [&](double *LiT, double *Li, const double *A, const double *invT) {   // L^-T by the solve of the identity, L^-1
-        identity_blocks(s, LiT, n, R);
-        panel_inv_steps(g, s, LiT, n, A, n, invT, ntz, mo(sT, sT, 0), sK, L.sI);
-        launch_transpose_blocks(s, Li, LiT, n, R);
-    };
-
     std::vector<int> st(R, 0), active(R, 1);
     std::vector<double> jit_m(R, 0.0), jit_b(R, 0.0);
     Members m;
@@ -217,41 +148,62 @@ extern "C" int gp_sparse_fit_grad_batch(gp_t *g, int R, int64_t Mz, const double
     m.diag = diag.data();
     m.diag_tab = dDiag;
     m.jit_tab = dJit;
+    auto nt_square = [&](double *C, const double *A, const double *B) {
+        gemm(g, s, 0, C, n, A, n, B, n, 1, (int)n, TileSet{0, ntz, 0, ntz, 0}, member_opt(m, GemmOpt(), sT, sT, sT));
+    };
+    auto both_sides = [&](double *S, const double *LiT, const double *M) {   // S = L^-T M L^-1 (M symmetric)
+        nt_square(Tmp2, LiT, M);
+        nt_square(S, Tmp2, LiT);
+    };
+    auto inverse_T = [&](double *LiT, double *Li, const double *A, const double *invT) {   // L^-T by the solve of the identity, L^-1
+        identity_blocks(s, LiT, n, R);
+        panel_inv_steps(g, s, LiT, n, A, n, invT, ntz, member_opt(m, GemmOpt(), sT, sT, 0), sK, L.sI);
+        launch_transpose_blocks(s, Li, LiT, n, R);
+    };
+    // behind the matrix build of an attempt of either ladder: the jitter, and the zero RHS tile row below each member's matrix
+    auto jitter_rhs = [&](const Members &run, bool jittered) {
+        if (jittered) launch_add_diag(s, run.A, n, Mz, run.jit[0], run.nb, run.sA, run.jit_tab);
+        HIPCHK(hipMemset2DAsync(run.A + n * n, sizeof(double) * sK, 0, sizeof(double) * GP_TILE * n, run.nb, s));
+        return 0;
+    };
+
     // Kmm = K(Z) + const_jitter I (var_dtc.py:93-95), Lm, Lm^-T, Lm^-1
     m.A = Kmm;
     m.invL = InvM;
     m.jit = jit_m.data();
-    rc = spb_ladder(g, m, n, Mz, maxtries, active, jit_m, dJit, st,
-                    [&](const Members &run, int) {
-                        launch_kbuild(s, run.A, n, run.X, Mz, n, run.kp[0], 1e-8, 0, run.nb, run.sA, run.kpt, run.diag_tab, run.sX);
-                    },
-                    [&](const std::vector<int> &failed, std::vector<double> &d0) {
-                        for (int r : failed) d0[r] = kp[r].variance + 1e-8;
-                        return 0;
-                    });
+    rc = members_ladder(g, m, ntz, maxtries, active, jit_m, dJit, st,
+                        [&](const Members &run, int, bool jittered) {
+                            launch_kbuild(s, run.A, n, run.X, Mz, n, run.kp[0], 1e-8, 0, run.nb, run.sA, run.kpt, run.diag_tab, run.sX);
+                            return jitter_rhs(run, jittered);
+                        },
+                        [&](const std::vector<int> &failed, std::vector<double> &d0) {
+                            for (int r : failed) d0[r] = kp[r].variance + 1e-8;
+                            return 0;
+                        });
     if (rc) return rc;
     inverse_T(LmiT, Lmi, Kmm, InvM);
     // psi1 = K(X, Z) (var_dtc.py:125); V = Lm^-1 psi1^T (:130 without sqrt(beta)); A = beta V V^T (:131); B = I + A (:134)
     launch_cross_k(s, Kfu, n, g->dX, N, Npad, dZin, Mz, n, kp[0], R, sR, L.sZ, dKp);
-    gemm(g, s, 0, V, Npad, Lmi, n, Kfu, n, 1, (int)n, TileSet{0, ntz, 0, nt, 0}, mo(sR, sT, sR));
-    gemm(g, s, 0, VVt, n, V, Npad, V, Npad, 1, (int)Npad, TileSet{0, ntz, 0, ntz, 0}, mo(sT, sR, sR));
+    gemm(g, s, 0, V, Npad, Lmi, n, Kfu, n, 1, (int)n, TileSet{0, ntz, 0, nt, 0}, member_opt(m, GemmOpt(), sR, sT, sR));
+    gemm(g, s, 0, VVt, n, V, Npad, V, Npad, 1, (int)Npad, TileSet{0, ntz, 0, ntz, 0}, member_opt(m, GemmOpt(), sT, sR, sR));
     // B's ladder: the members that have an Lm
     for (int r = 0; r < R; ++r) active[r] = st[r] == 0;
     m.A = Bm;
     m.invL = InvB;
     m.jit = jit_b.data();
-    rc = spb_ladder(g, m, n, Mz, maxtries, active, jit_b, dJit, st,
-                    [&](const Members &run, int m0) {
-                        launch_sparse_lincomb(s, run.A, VVt + m0 * sT, 0.0, nullptr, 0.0, 1.0, n, run.nb, sK, sT, 0, dBeta + m0, nullptr);
-                    },
-                    [&](const std::vector<int> &failed, std::vector<double> &d0) {   // mean diagonal of B = 1 + beta trace(VVt) / Mz
-                        std::vector<double> tr(2 * (size_t)R);
-                        for (int r : failed) launch_trace(s, VVt + r * sT, n, Mz, dTrace + 2L * r);
-                        HIPCHK(hipMemcpyAsync(tr.data(), dTrace, sizeof(double) * 2 * R, hipMemcpyDeviceToHost, s));
-                        GP_SYNC(s);
-                        for (int r : failed) d0[r] = 1.0 + beta[r] * tr[2 * (size_t)r] / (double)Mz;
-                        return 0;
-                    });
+    rc = members_ladder(g, m, ntz, maxtries, active, jit_b, dJit, st,
+                        [&](const Members &run, int m0, bool jittered) {
+                            launch_sparse_lincomb(s, run.A, VVt + m0 * sT, 0.0, nullptr, 0.0, 1.0, n, run.nb, sK, sT, 0, dBeta + m0, nullptr);
+                            return jitter_rhs(run, jittered);
+                        },
+                        [&](const std::vector<int> &failed, std::vector<double> &d0) {   // mean diagonal of B = 1 + beta trace(VVt) / Mz
+                            std::vector<double> tr(2 * (size_t)R);
+                            for (int r : failed) launch_trace(s, VVt + r * sT, n, Mz, dTrace + 2L * r);
+                            HIPCHK(hipMemcpyAsync(tr.data(), dTrace, sizeof(double) * 2 * R, hipMemcpyDeviceToHost, s));
+                            GP_SYNC(s);
+                            for (int r : failed) d0[r] = 1.0 + beta[r] * tr[2 * (size_t)r] / (double)Mz;
+                            return 0;
+                        });
     if (rc) return rc;
     inverse_T(LbiT, Lbi, Bm, InvB);
     // _LBi_Lmi_psi1Vf, Cpsi1Vf (var_dtc.py:138-142), one row of n per output
@@ -270,7 +222,7 @@ extern "C" int gp_sparse_fit_grad_batch(gp_t *g, int R, int64_t Mz, const double
     // dL_dpsi2_beta = 0.5 Lm^-T (P I - DBi_plus_BiPBi) Lm^-1 (var_dtc.py:221); Wt = psi1 dL_dpsi2_beta (:232 without 2 beta)
     launch_sparse_lincomb(s, Tmp, Dm, -0.5, nullptr, 0.0, 0.5 * P, n, R, sT, sT, 0);
     both_sides(E, LmiT, Tmp);
-    gemm(g, s, 0, Wt, n, Kfu, n, E, n, 1, (int)n, TileSet{0, nt, 0, ntz, 0}, mo(sR, sR, sT));
+    gemm(g, s, 0, Wt, n, Kfu, n, E, n, 1, (int)n, TileSet{0, nt, 0, ntz, 0}, member_opt(m, GemmOpt(), sR, sR, sT));
     // the Kmm part (gradients_X's tmp + tmp.T: twice the symmetric weight), then the Knm part: dL_dKnm = beta Y w^T + 2 beta Wt
     double *dZmm = Out + SPB_DZ, *dZnm = dZmm + Mz * D;
     SparseGradMembers gm;

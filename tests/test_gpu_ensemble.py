@@ -424,6 +424,35 @@ def test_jitter_ladder_per_member(h):
     assert h.ens_info() == 0                                         # the failed call left no ensemble
 
 
+def test_exhausted_ladder_is_the_single_fits_code_and_message(h):
+    """A member that exhausts the ladder, over three tiles (tests/_jitter_cases.py, N = 300: members 0 and 2 of the batched case
+    around its member 6, whose first non-positive pivot lies among the repeated rows of the third tile).  With the ladder the
+    member stops on the first rung and its neighbours keep jitter 0; with maxtries = 0 gp_ens_fit returns the code gp_fit_grad
+    returns for that member alone, with the library's message for it, and gp_ens_info reports no ensemble."""
+    import _jitter_cases as J
+    X, Y = J.batch_problem()
+    h.set_data(X, Y)
+    pick = [0, 6, 2]
+    var, ls, noise = J.BATCH_VAR[pick], J.BATCH_LS[pick], J.BATCH_NOISE[pick]
+    h.set_params(0, False, var[1], ls[1], noise[1])
+    lml, logdet, jt = _lib._fit_scalars()
+    dv, dn, dl = ctypes.c_double(), ctypes.c_double(), np.empty(1)
+    alone = h.lib.gp_fit_grad(h.h, 0, ctypes.byref(lml), ctypes.byref(logdet), ctypes.byref(jt), ctypes.byref(dv), _lib.dptr(dl),
+                              ctypes.byref(dn))
+    h.set_params(0, False, var[0], ls[0], noise[0])
+    jit = h.ens_fit(var, ls, noise)[2]
+    print("jitter per member:", jit, "gp_fit_grad alone without the ladder:", alone)
+    assert h.ens_info() == 3 and jit[0] == 0.0 and jit[2] == 0.0
+    assert jit[1] == pytest.approx((var[1] + (noise[1] + 1e-8)) * 1e-6, rel=1e-12)
+    out = [np.empty(3) for _ in range(4)]
+    rc = h.lib.gp_ens_fit(h.h, 3, _lib.dptr(var), _lib.dptr(ls), _lib.dptr(noise), 0, *[_lib.dptr(o) for o in out])
+    msg = h.lib.gp_last_error().decode()
+    print("gp_ens_fit without the ladder:", rc, repr(msg))
+    assert rc == alone and J.BATCH_N - J.BATCH_DUP < rc <= J.BATCH_N
+    assert msg == "not positive definite, even with jitter."
+    assert h.ens_info() == 0
+
+
 # ---- 6. the model level --------------------------------------------------------------------------------------------------------------
 def _objective(x):
     x = np.atleast_2d(x)
