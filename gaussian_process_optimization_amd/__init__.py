@@ -32,6 +32,8 @@ from . import warping_functions
 from .warped_gp import WarpedGP, WarpedGPModel
 from . import cost
 from .cost import CostModel
+from . import feasibility
+from .feasibility import FeasibilityModel
 from . import acquisitions
 from .acquisitions import (AcquisitionEI, AcquisitionLCB, AcquisitionMPI, AcquisitionBase, AcquisitionLP,
                            LocalPenalization, estimate_L, AcquisitionEI_MCMC, AcquisitionMPI_MCMC, AcquisitionLCB_MCMC,
@@ -53,4 +55,4 @@ __all__ = ["kern", "mappings", "models", "methods", "likelihoods", "acquisitions
            "InputWarpedGP", "InputWarpedGPModel", "input_warping", "WarpedGP", "WarpedGPModel", "warping_functions",
            "AcquisitionEI", "AcquisitionLCB", "AcquisitionMPI", "AcquisitionBase", "AcquisitionLP",
            "LocalPenalization", "estimate_L", "BayesianOptimization",
-           "Design_space", "AcquisitionOptimizer", "ShardedCandidates", "merge_best", "Standardize", "cost", "CostModel"]
+           "Design_space", "AcquisitionOptimizer", "ShardedCandidates", "merge_best", "Standardize", "cost", "CostModel", "feasibility", "FeasibilityModel"]

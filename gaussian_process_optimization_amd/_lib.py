@@ -20,6 +20,9 @@ GP_KERNEL_RBF, GP_KERNEL_MATERN52 = 0, 1
 GP_KERNEL_MATERN32, GP_KERNEL_EXPONENTIAL = 2, 3
 GP_ACQ_EI, GP_ACQ_LCB, GP_ACQ_MPI = 0, 1, 2
 GP_ACQ_PER_COST = 0x100      # or-ed into a scoring call's type: the scores are divided by the resident cost surface
+GP_ACQ_POF = 3               # the rule whose value is 1: valid only with GP_ACQ_TIMES_FEAS (the probability of feasibility alone)
+GP_ACQ_TIMES_FEAS = 0x200    # or-ed into a table scoring call's type: the scores are multiplied by the cached probability of feasibility
+GP_FEAS_MAX = 8
 GP_ERR_ARG, GP_ERR_HIP, GP_ERR_STATE, GP_ERR_RCCL, GP_ERR_NOT_PD_DIAG = -1, -2, -3, -4, -5
 
 # every symbol include/gphip.h declares: (name, restype, argtypes)
@@ -192,6 +195,15 @@ SIGNATURES = [
                                    c_double_p, ctypes.c_double, ctypes.c_double]),
     ("gp_cost_info", ctypes.c_int, [_vp, c_int64_p]),
     ("gp_cost_rows", ctypes.c_int, [_vp, _vp, ctypes.c_int64, _vp, _vp]),
+    ("gp_feas_table", ctypes.c_int, [_vp, ctypes.POINTER(_vp), ctypes.c_int, c_double_p, c_double_p, c_double_p]),
+    ("gp_feas_info", ctypes.c_int, [_vp, c_int_p, c_int64_p]),
+    ("gp_feas_get_table", ctypes.c_int, [_vp, c_double_p]),
+    ("gp_feas_rows", ctypes.c_int, [ctypes.POINTER(_vp), ctypes.c_int, c_double_p, c_double_p, c_double_p, _vp, ctypes.c_int64,
+                                    _vp, _vp]),
+    ("gp_acq_rows_feas", ctypes.c_int, [_vp, ctypes.POINTER(_vp), ctypes.c_int, c_double_p, c_double_p, c_double_p, _vp,
+                                        ctypes.c_int64, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double,
+                                        ctypes.c_double, _vp, _vp]),
+    ("gp_fmin_rows", ctypes.c_int, [_vp, c_int64_p, ctypes.c_int64, c_double_p]),
     ("gp_mean_set", ctypes.c_int, [_vp, c_double_p, c_double_p]),
     ("gp_mean_info", ctypes.c_int, [_vp, c_int_p, c_int_p]),
     ("gp_mean_grad", ctypes.c_int, [_vp, c_double_p, c_double_p]),
@@ -305,6 +317,39 @@ def _acq_rows_entry(symbol, doc):
     return rows
 
 
+class FeasPack(object):
+    """The constraint side of a feasibility call, packed once per refit: K handles with their bounds and output normalisers as the
+    C entries take them (``gp_feas_*``, ``gp_acq_rows_feas``).  Holds the Handle objects, so none is collected under a call."""
+
+    def __init__(self, handles, bounds, c_mean, c_std):
+        self.handles = list(handles)
+        self.K = len(self.handles)
+        if not 1 <= self.K <= GP_FEAS_MAX:
+            raise ValueError("between 1 and %d constraints, got %d" % (GP_FEAS_MAX, self.K))
+        self.bounds = as_f64(np.ravel(bounds), 1)
+        self.c_mean = as_f64(np.ravel(c_mean), 1)
+        self.c_std = as_f64(np.ravel(c_std), 1)
+        if not (self.bounds.size == self.c_mean.size == self.c_std.size == self.K):
+            raise ValueError("bounds, c_mean and c_std take one entry per constraint")
+        self.D = self.handles[0].D
+        self.lib = self.handles[0].lib
+        self.cons = (_vp * self.K)(*[h.h for h in self.handles])
+        self.args = (self.cons, self.K, dptr(self.bounds), dptr(self.c_mean), dptr(self.c_std))
+
+    def rows(self, Xs, grad=False):
+        """log prod_k Phi [M] at the rows of ``Xs`` and, with ``grad``, its x-gradient [M, D] (gp_feas_rows)."""
+        Xs = as_f64(Xs, 2)
+        if Xs.shape[1] != self.D:
+            raise ValueError("locations have %d columns, the constraint models have %d" % (Xs.shape[1], self.D))
+        M = Xs.shape[0]
+        logF = np.empty(M)
+        dlogF = np.empty((M, self.D)) if grad else None
+        rc = self.lib.gp_feas_rows(*(self.args + (Xs.ctypes.data, M, logF.ctypes.data, dlogF.ctypes.data if grad else None)))
+        if rc:
+            check(self.lib, rc, "gp_feas_rows")
+        return (logF, dlogF) if grad else logF
+
+
 class Handle(object):
     """Owns one gp_t (one device)."""
 
@@ -316,6 +361,7 @@ class Handle(object):
         self.device = int(device)
         self.sparse_M = 0      # rows of the sparse model's candidate table (sparse_set_candidates); 0: the library refuses to score
         self.cost_key = None   # whose cost surface the handle holds: set by the caller of cost_set, dropped with the surface
+        self.feas_key = None   # whose probability of feasibility the handle caches over its candidates: set by the caller of feas_table
 
     def close(self):
         if getattr(self, "h", None):
@@ -338,6 +384,7 @@ class Handle(object):
               "gp_set_data")
         if getattr(self, "D", X.shape[1]) != X.shape[1]:
             self.cost_key = None       # the library drops a cost surface of another width
+            self.feas_key = None       # ... and a probability of feasibility cached over candidates of another width
         self.N, self.D, self.P = X.shape[0], X.shape[1], Y.shape[1]
 
     def set_params(self, kernel, ard, variance, lengthscale, noise):
@@ -600,6 +647,7 @@ class Handle(object):
             raise ValueError("candidates have %d columns, model has %d" % (Xs.shape[1], self.D))
         check(self.lib, self.lib.gp_set_candidates(self.h, dptr(Xs), Xs.shape[0]), "gp_set_candidates")
         self.M = Xs.shape[0]
+        self.feas_key = None   # the library drops the probability of feasibility cached over the old table
 
     def set_candidates_kumar(self, Xs, warp, a, b, xmin, xmax, want_warped=False):
         """gp_set_candidates of the Kumaraswamy-warped table, warped on the device: ``warp`` [D] 0 / 1, ``a``, ``b``, ``xmin``,
@@ -1038,6 +1086,53 @@ class Handle(object):
 
     acq_rows = _acq_rows_entry("gp_acq_rows", """Negated acquisition [M, 1] (and its gradient [M, D]); ``lp`` = (transform, Xb, r_x0,
         s_x0) adds the local penalisation, in which case the value comes back 1-D as AcquisitionLP returns it.""")
+
+    # -- black-box constraints (include/gphip.h, gp_feas_*): the probability of feasibility behind EI / MPI ----------------------
+    def feas_table(self, pack, key=None):
+        """Cache log prod_k Phi of ``pack`` (a FeasPack) over the resident candidates; ``pack=None`` clears it.  The constraint
+        handles' resident tables are this handle's afterwards.  ``key`` is remembered as ``feas_key`` (the staleness check)."""
+        self.feas_key = None
+        if pack is None:
+            check(self.lib, self.lib.gp_feas_table(self.h, None, 0, None, None, None), "gp_feas_table")
+            return
+        check(self.lib, self.lib.gp_feas_table(self.h, *pack.args), "gp_feas_table")
+        for h in pack.handles:
+            h.M = self.M
+            h.feas_key = None
+        self.feas_key = key
+
+    def feas_info(self):
+        K, M = ctypes.c_int(0), ctypes.c_int64(0)
+        check(self.lib, self.lib.gp_feas_info(self.h, ctypes.byref(K), ctypes.byref(M)), "gp_feas_info")
+        return K.value, M.value
+
+    def feas_get_table(self):
+        K, M = self.feas_info()
+        logF = np.empty(M)
+        check(self.lib, self.lib.gp_feas_get_table(self.h, dptr(logF)), "gp_feas_get_table")
+        return logF
+
+    def acq_rows_feas(self, pack, Xs, type_, par, fmin, y_mean=0.0, y_std=1.0, grad=False):
+        """Negated acquisition times the probability of feasibility [M, 1] (and its gradient [M, D]) at the rows of ``Xs``: this
+        handle's and the constraint handles' fused passes, the fold and one drain in ONE call (gp_acq_rows_feas)."""
+        Xs = np.ascontiguousarray(Xs, dtype=np.float64)
+        if Xs.ndim != 2 or Xs.shape[1] != self.D:
+            raise ValueError("expected locations [M, %d], got shape %s" % (self.D, Xs.shape))
+        M = Xs.shape[0]
+        out = np.empty((M, 1))
+        dout = np.empty((M, self.D)) if grad else None
+        rc = self.lib.gp_acq_rows_feas(self.h, pack.cons, pack.K, pack.args[2], pack.args[3], pack.args[4], Xs.ctypes.data, M,
+                                       int(type_), par, fmin, y_mean, y_std, out.ctypes.data, dout.ctypes.data if grad else None)
+        if rc:
+            check(self.lib, rc, "gp_acq_rows_feas")
+        return (out, dout) if grad else out
+
+    def fmin_rows(self, rows):
+        """``fmin`` over the listed training rows alone (gp_fmin_rows): the incumbent among the feasible observations."""
+        rows = np.ascontiguousarray(np.ravel(rows), dtype=np.int64)
+        v = ctypes.c_double()
+        check(self.lib, self.lib.gp_fmin_rows(self.h, rows.ctypes.data_as(c_int64_p), rows.size, ctypes.byref(v)), "gp_fmin_rows")
+        return v.value
 
     # -- the cost surface of cost-aware EI / MPI (include/gphip.h, gp_cost_*) ---------------------------------------------
     def cost_set(self, Xc, alpha, kernel, ard, variance, lengthscale, shift=0.0, scale=1.0, key=None):

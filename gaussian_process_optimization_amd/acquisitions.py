@@ -11,6 +11,10 @@ A sparse ``GPModel`` built with ``device_acquisitions=True`` takes the same rout
 ``gp_sparse_acq_argbest`` / ``_topk``, ``gp_sparse_acq_rows``) over a candidate table of the sparse model's own.
 EI and MPI under the evaluation-time cost model (``cost.CostModel`` over our exact ``GPModel``) stay on those routes: the handle
 holds a snapshot of the cost GP's posterior mean (``gp_cost_set``) and divides the scores itself (``GP_ACQ_PER_COST``).
+EI and MPI with black-box constraints (``feasibility=<FeasibilityModel>``) score ``a(x) F(x)``, F the probability of feasibility of
+the constraint GPs, with the incumbent over the feasible observations: tables through ``gp_feas_table`` + ``GP_ACQ_TIMES_FEAS``
+(values, arg-best, top-k, and the penalised values / arg-best of ``AcquisitionLP``), one-location and lockstep calls through
+``gp_acq_rows_feas``; while no observation is feasible the rule is ``GP_ACQ_POF``, the probability of feasibility alone.
 Anything else (a foreign ``BOModel``, a user's cost function, string constraints, several outputs) is scored by ``_Rule`` below from
 ``model.predict[_withGradients]``: each acquisition is one rule giving its value and its two partial derivatives with respect
 to the posterior mean and standard deviation, and every class shares the chain rule built on them.
@@ -171,6 +175,25 @@ def _normaliser(gp):
     return (0.0, 1.0) if nz is None else (float(nz.mean[0]), float(nz.std[0]))
 
 
+def _sync_feas(acq, h):
+    """Before a flagged table call on handle ``h`` (its candidates resident): cache the probability of feasibility over them
+    unless ``h`` holds this feasibility model's current generation for this table (``Handle.set_candidates`` drops the key with
+    the table).  Returns the key."""
+    fm = acq.feasibility
+    key = (id(fm), fm.generation)
+    if h.feas_key != key or not _feas_resident(acq, h):
+        h.feas_table(acq._feas_pack(), key=key)
+    return key
+
+
+def _feas_resident(acq, h):
+    """Whether the LIBRARY still holds the cache ``h.feas_key`` speaks of, over a table of ``h.M`` rows: a rows call that took
+    the substitution fallback (gp_acq_rows_feas, gp_acq_rows, gp_predict_rows: the first calls after a fit above N = 4096,
+    options small_m / rows_build) made its locations the resident table inside the C entry and dropped the cache with the old one,
+    which the Python-side key does not see."""
+    return h.feas_info() == (acq.feasibility.num_constraints, h.M)
+
+
 # ---- the device routes of EI / LCB / MPI and of the penalised acquisition on top of them ---------------------------------
 class _Route(object):
     """How the acquisition ``acq`` (an AcquisitionBase with a ``_rule``) reaches libgphip for one kind of model, as four
@@ -184,13 +207,20 @@ class _Route(object):
         x = np.asarray(x, dtype=float)
         if x.ndim != 2:
             x = np.atleast_2d(x)
-        if x.shape[0] > _FEW_ROWS:
+        feas = getattr(acq, "feasibility", None) is not None
+        if feas and lp is not None:       # penalised rows fold the penaliser inside the fused finish: tables only
+            if grad:
+                raise NotImplementedError("the penalised acquisition over black-box constraints has no gradient calls")
+            return self.values(acq, x, False, lp)
+        if x.shape[0] > _FEW_ROWS and not (feas and grad):
             return self.values(acq, x, grad, lp)
         gp = acq.model.model
         gp._ensure_fit()
         if acq._per_cost:
             _sync_cost(acq, gp._h)
         shift, scale = _normaliser(gp)
+        if feas:      # any number of rows: gp_acq_rows_feas makes the groups of eight itself (the lockstep optimiser's call)
+            return gp._h.acq_rows_feas(acq._feas_pack(), x, acq._acq_id, acq._par(), acq._fmin(), shift, scale, grad=grad)
         return getattr(gp._h, self.rows)(x, acq._acq_id, acq._par(), acq._fmin(), shift, scale, grad=grad, lp=lp)
 
 
@@ -203,14 +233,25 @@ class _ExactRoute(_Route):
         """Make ``x`` the resident candidate block (refitting first if data or hyper-parameters changed) and return what
         every scoring call takes: the handle, fmin and the normaliser's mean / std."""
         gp = acq.model.model
+        given = x
         x = np.atleast_2d(np.asarray(x, dtype=float))
-        if gp._dirty:
+        feas = getattr(acq, "feasibility", None) is not None
+        held = getattr(acq, "_feas_table", None)
+        # the same table object again under the same generation (the penalised table loop): it is still resident, with its cache
+        again = (feas and not gp._dirty and held is not None and held[0] is given and held[1] == x.shape
+                 and gp._h.feas_key == held[2] and held[2] == (id(acq.feasibility), acq.feasibility.generation)
+                 and gp._h.M == x.shape[0] and _feas_resident(acq, gp._h))
+        if again:
+            pass
+        elif gp._dirty:
             gp._stage(x, fit=False)        # pending refit: fit + posterior at x go down as ONE call
             gp._predict_resident(True)     # GPModel.predict: with_noise=True (gpmodel.py:102)
         else:
             gp._stage(x)
         if acq._per_cost:
             _sync_cost(acq, gp._h)
+        if feas:
+            acq._feas_table = (given, x.shape, _sync_feas(acq, gp._h))
         return (gp._h, acq._fmin()) + _normaliser(gp)
 
     @staticmethod
@@ -219,6 +260,8 @@ class _ExactRoute(_Route):
         if acq._per_cost:
             raise NotImplementedError("replica groups score without a cost model: not available with cost_withGradients="
                                       "'evaluation_time'")
+        if getattr(acq, "feasibility", None) is not None:
+            raise NotImplementedError("replica groups score without black-box constraints: not available with feasibility=")
         gp = acq.model.model
         grp = gp._device_group(devices)
         grp.set_candidates(np.atleast_2d(np.asarray(x, dtype=float)))
@@ -229,6 +272,8 @@ class _ExactRoute(_Route):
         return (grp, fmin) + _normaliser(gp)
 
     def values(self, acq, x, grad, lp):
+        if grad and getattr(acq, "feasibility", None) is not None:
+            raise NotImplementedError("the table gradient entries take no probability of feasibility")
         h, fmin, shift, scale = self._stage(acq, x)
         if lp is None:      # the exact handle names its four table calls: acq / acq_grad / acq_lp / acq_lp_grad
             return (h.acq_grad if grad else h.acq)(acq._acq_id, acq._par(), fmin, shift, scale)
@@ -283,6 +328,13 @@ class AcquisitionBase(object):
     ``_compute_acq_withGradients`` as in GPyOpt."""
     analytical_gradient_prediction = False
     _rule = None
+    feasibility = None      # a FeasibilityModel: black-box constraints behind EI / MPI (``_set_feasibility``)
+    # (table, shape, key) of the last table this acquisition had the probability of feasibility cached for.  The table is known
+    # by OBJECT IDENTITY and shape (and the library is asked whether its cache still stands): scoring the same ndarray again
+    # under the same generation neither uploads it nor caches it again -- so a caller who refills that array IN PLACE must pass
+    # a new array (or a copy), or gets the scores of the old contents.  The reference also keeps the caller's table alive.
+    _feas_table = None
+    _feas_incumbent = None  # (key, value): the feasible incumbent of one fit and one generation (``_feasible_fmin``)
 
     def __init__(self, model, space=None, optimizer=None, cost_withGradients=None):
         self.model = model
@@ -300,16 +352,67 @@ class AcquisitionBase(object):
 
     @property
     def _acq_id(self):
-        """The ``type`` of the scoring calls: the rule, with GP_ACQ_PER_COST under a device cost."""
+        """The ``type`` of the scoring calls: the rule, with GP_ACQ_PER_COST under a device cost; under black-box constraints
+        with GP_ACQ_TIMES_FEAS, the rule GP_ACQ_POF while no observation is feasible."""
         if self._rule is None:
             return None
-        return self._rule.device_id | _lib.GP_ACQ_PER_COST if self._per_cost else self._rule.device_id
+        rule = self._rule.device_id
+        if self.feasibility is not None:
+            rule = (_lib.GP_ACQ_POF if self._no_feasible_row() else rule) | _lib.GP_ACQ_TIMES_FEAS
+        return rule | _lib.GP_ACQ_PER_COST if self._per_cost else rule
 
     def _par(self):
         raise NotImplementedError
 
     def _fmin(self):
+        if self.feasibility is not None:
+            return self._feasible_fmin()
         return self.model.get_fmin() if self._rule.needs_fmin else 0.0
+
+    # ---- black-box constraints ---------------------------------------------------------------------------------------
+    def _set_feasibility(self, feasibility):
+        """EI / MPI over our exact GPModel take a FeasibilityModel; every other scored model raises."""
+        if feasibility is None:
+            return
+        m = self.model
+        if type(m) is not GPModel or getattr(m, "sparse", False):
+            raise NotImplementedError("black-box constraints score our exact GPModel: a foreign, sparse, MCMC or warped model "
+                                      "is not available with feasibility=")
+        self.feasibility = feasibility
+
+    def _no_feasible_row(self):
+        return self.feasibility.feasible_rows.size == 0
+
+    def _feasible_fmin(self):
+        """The incumbent over the feasible observations (gp_fmin_rows); 0 while there is none (GP_ACQ_POF reads no fmin)."""
+        rows = self.feasibility.feasible_rows
+        if rows.size == 0 or not self._rule.needs_fmin:
+            return 0.0
+        gp = self.model.model
+        gp._ensure_fit()
+        if self.feasibility.num_rows != gp.X.shape[0]:
+            raise ValueError("the feasibility model saw %d observations, the scored model has %d: update both with the same X"
+                             % (self.feasibility.num_rows, gp.X.shape[0]))
+        # once per fit and generation, as gp_fmin is cached per fit: an L-BFGS run asks for it with every location
+        key = (id(self.feasibility), self.feasibility.generation, id(gp), getattr(gp, "_data_epoch", None),
+               getattr(gp, "_lml", None), getattr(gp, "_jitter", None))
+        held = self._feas_incumbent
+        if held is not None and held[0] == key:
+            return held[1]
+        lowest = gp._h.fmin_rows(rows)
+        if gp.normalizer is not None:
+            lowest = float(gp.normalizer.inverse_mean(np.array([[lowest]]))[0, 0])
+        self._feas_incumbent = (key, lowest)
+        return lowest
+
+    def _feas_pack(self):
+        pack = self.feasibility.device_pack(self.model.device)
+        if pack is None:
+            raise NotImplementedError("the constraint models are not exact GPModels on the scored model's device")
+        return pack
+
+    def _feas_on_device(self):
+        return self.feasibility is None or self.feasibility.device_pack(self.model.device) is not None
 
     # ---- device route ----------------------------------------------------------------------------------------------
     def _device_ok(self):
@@ -319,7 +422,7 @@ class AcquisitionBase(object):
         m = self.model
         if self._rule is None or not isinstance(m, GPModel) or m.model is None or getattr(m, "sparse", False):
             return False
-        return _cost_ok(self) and m.model.output_dim == 1
+        return _cost_ok(self) and m.model.output_dim == 1 and self._feas_on_device()
 
     def _sparse_device_ok(self):
         """True when libgphip scores this acquisition over the SPARSE posterior (gp_sparse_acq*): our GPModel with ``sparse=True``
@@ -344,6 +447,11 @@ class AcquisitionBase(object):
         if route is not None:
             return route.score(self, x, False, None)
         price, _ = self.cost_withGradients(x)
+        if self.feasibility is not None:      # constraint models scored on the host: the same product from log_probability
+            x = np.atleast_2d(np.asarray(x, dtype=float))
+            val = np.ones((x.shape[0], 1)) if self._no_feasible_row() else self._compute_acq(x)
+            val = val * np.exp(self.feasibility.log_probability(x))[:, None]
+            return -(val * self.space.indicator_constraints(x)) / price
         return -(self._compute_acq(x) * self.space.indicator_constraints(x)) / price
 
     def acquisition_function_withGradients(self, x):
@@ -351,7 +459,17 @@ class AcquisitionBase(object):
         route = self._route()
         if route is not None:
             return route.score(self, x, True, None)
-        val, dval = self._compute_acq_withGradients(x)
+        if self.feasibility is not None:
+            x = np.atleast_2d(np.asarray(x, dtype=float))
+            if self._no_feasible_row():
+                val, dval = np.ones((x.shape[0], 1)), np.zeros(x.shape)
+            else:
+                val, dval = self._compute_acq_withGradients(x)
+            logF, dlogF = self.feasibility.log_probability_withGradients(x)
+            F = np.exp(logF)[:, None]
+            val, dval = val * F, F * (dval + val * dlogF)
+        else:
+            val, dval = self._compute_acq_withGradients(x)
         price, dprice = self.cost_withGradients(x)
         feasible = self.space.indicator_constraints(x)
         quotient = val / price
@@ -399,13 +517,16 @@ class AcquisitionBase(object):
 
 
 class AcquisitionEI(AcquisitionBase):
-    """Expected improvement (EI.py:7-51): ``jitter`` is the improvement margin."""
+    """Expected improvement (EI.py:7-51): ``jitter`` is the improvement margin.  ``feasibility`` (a ``FeasibilityModel``) weights it
+    by the probability of feasibility of black-box constraints.  A candidate table scored repeatedly under it is recognised by
+    object identity and shape: refill a table in place and it must be passed as a new array (see ``_feas_table``)."""
     analytical_gradient_prediction = True
     _rule = _RULES["EI"]
 
-    def __init__(self, model, space=None, optimizer=None, cost_withGradients=None, jitter=0.01):
+    def __init__(self, model, space=None, optimizer=None, cost_withGradients=None, jitter=0.01, feasibility=None):
         super().__init__(model, space, optimizer, cost_withGradients=cost_withGradients)
         self.jitter = jitter
+        self._set_feasibility(feasibility)
 
     @staticmethod
     def fromConfig(model, space, optimizer, cost_withGradients, config):
@@ -420,7 +541,9 @@ class AcquisitionLCB(AcquisitionBase):
     analytical_gradient_prediction = True
     _rule = _RULES["LCB"]
 
-    def __init__(self, model, space=None, optimizer=None, cost_withGradients=None, exploration_weight=2):
+    def __init__(self, model, space=None, optimizer=None, cost_withGradients=None, exploration_weight=2, feasibility=None):
+        if feasibility is not None:      # -mean + w sd changes sign: a product with a probability is meaningless
+            raise ValueError("LCB takes no black-box constraints: use EI or MPI with feasibility=")
         super().__init__(model, space, optimizer)
         self.exploration_weight = exploration_weight
         if cost_withGradients is not None:
@@ -435,13 +558,15 @@ class AcquisitionLCB(AcquisitionBase):
 
 
 class AcquisitionMPI(AcquisitionBase):
-    """Maximum probability of improvement (MPI.py:7-51)."""
+    """Maximum probability of improvement (MPI.py:7-51).  ``feasibility``: as for ``AcquisitionEI``, the same identity contract for
+    a table scored repeatedly."""
     analytical_gradient_prediction = True
     _rule = _RULES["MPI"]
 
-    def __init__(self, model, space=None, optimizer=None, cost_withGradients=None, jitter=0.01):
+    def __init__(self, model, space=None, optimizer=None, cost_withGradients=None, jitter=0.01, feasibility=None):
         super().__init__(model, space, optimizer, cost_withGradients=cost_withGradients)
         self.jitter = jitter
+        self._set_feasibility(feasibility)
 
     @staticmethod
     def fromConfig(model, space, optimizer, cost_withGradients, config):
@@ -684,6 +809,9 @@ class AcquisitionLP(AcquisitionBase):
 
     def acquisition_function_withGradients(self, x):
         """(value [M], gradient [M, D])  (LP.py:112-140)."""
+        if getattr(self.acq, "feasibility", None) is not None:
+            raise NotImplementedError("the penalised acquisition over black-box constraints scores tables (values, arg-best): "
+                                      "it has no gradient calls")
         x = np.atleast_2d(np.asarray(x, dtype=float))
         route = self._lp_route()
         if route is not None:

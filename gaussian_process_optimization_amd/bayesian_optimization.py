@@ -22,6 +22,7 @@ from . import kern as _kern
 from .acquisitions import (AcquisitionEI, AcquisitionLCB, AcquisitionMPI, AcquisitionLP, LocalPenalization, AcquisitionEI_MCMC,
                            AcquisitionMPI_MCMC, AcquisitionLCB_MCMC, AcquisitionEntropySearch)
 from .cost import CostModel
+from .feasibility import FeasibilityModel
 from .entropy_search import AffineInvariantEnsembleSampler
 from .gpmodel import GPModel
 from .input_warped_gp import InputWarpedGPModel
@@ -331,14 +332,23 @@ def _clock():
 
 
 class BayesianOptimization(object):
-    """GPyOpt.methods.BayesianOptimization for model_type='GP' and 'input_warped_GP' (bayesian_optimization.py:76-170)."""
+    """GPyOpt.methods.BayesianOptimization for model_type='GP' and 'input_warped_GP' (bayesian_optimization.py:76-170).
+
+    Black-box constraints (an addition): ``constraint_function(X) -> [n, K]`` is evaluated wherever ``f`` is (``C`` holds the
+    values of the initial design, for ``f=None`` use), a location is feasible where every column is ``<= constraint_bounds``
+    (a scalar or one bound per column).  A ``FeasibilityModel`` -- one exact GP per constraint -- is refitted with the surrogate
+    and EI / MPI score ``a(x) F(x)`` with the incumbent over the feasible observations (``feasibility.py``).  ``x_opt`` /
+    ``fx_opt`` are then the best FEASIBLE observation; while there is none they are the LEAST VIOLATING one: the observation
+    with the smallest total violation ``sum_k max(c_k - bound_k, 0) / std_k`` (``std_k`` the standard deviation of column k over
+    the observations), the lowest objective among equals.  The evaluators 'sequential', 'random' and 'thompson_sampling' work;
+    'local_penalization' raises ``InvalidConfigError`` (its optimiser needs penalised rows, which take no constraints)."""
 
     def __init__(self, f, domain=None, constraints=None, cost_withGradients=None, model_type='GP', X=None, Y=None,
                  initial_design_numdata=5, initial_design_type='random', acquisition_type='EI', normalize_Y=True,
                  exact_feval=False, acquisition_optimizer_type='lbfgs', model_update_interval=1,
                  evaluator_type='sequential', batch_size=1, num_cores=1, verbosity=False, verbosity_model=False,
                  maximize=False, de_duplication=False, model=None, acquisition=None, device=0, parallel_anchors=False,
-                 **kwargs):
+                 constraint_function=None, C=None, constraint_bounds=0.0, **kwargs):
         if model_type not in ('GP', 'input_warped_GP') and model is None:
             raise NotImplementedError("model_type %r is outside the accelerated path" % model_type)
         if model_type == 'input_warped_GP' and evaluator_type == 'local_penalization' and batch_size > 1:
@@ -346,6 +356,13 @@ class BayesianOptimization(object):
             raise InvalidConfigError('local_penalization evaluator can only be used with GP models')
         if evaluator_type not in ('sequential', 'local_penalization', 'thompson_sampling', 'random', None):
             raise NotImplementedError("evaluator %r is outside the accelerated path" % evaluator_type)
+        constrained = constraint_function is not None or C is not None
+        if constrained and evaluator_type == 'local_penalization' and batch_size > 1:
+            raise InvalidConfigError("local_penalization optimises penalised rows, which take no black-box constraints: use the "
+                                     "'sequential', 'random' or 'thompson_sampling' evaluator with constraint_function")
+        self.constraint_function = constraint_function
+        self.feasibility = None
+        self.C = None
         self.evaluator_type = evaluator_type
         self.batch_size = batch_size
         self.f = f
@@ -441,6 +458,22 @@ class BayesianOptimization(object):
                 raise ValueError("f=None requires X and Y")
             Y = self._evaluate(self.X, record_cost=True)
         self.Y = np.asarray(Y, dtype=float).reshape(-1, 1)
+        if constrained:
+            if C is None:
+                C = self._evaluate_constraints(self.X)
+            self.C = np.asarray(C, dtype=float).reshape(self.X.shape[0], -1)
+            self.feasibility = FeasibilityModel(self.C.shape[1], constraint_bounds, device=device, exact_feval=exact_feval,
+                                                optimizer=kwargs.get('model_optimizer_type', 'lbfgs'),
+                                                max_iters=kwargs.get('max_iters', 1000),
+                                                optimize_restarts=kwargs.get('optimize_restarts', 5), verbose=verbosity_model,
+                                                ARD=kwargs.get('ARD', False))
+            scored = self.acquisition.acq if isinstance(self.acquisition, AcquisitionLP) else self.acquisition
+            if isinstance(scored, AcquisitionLCB):
+                raise ValueError("LCB takes no black-box constraints: use acquisition_type 'EI' or 'MPI' with constraint_function")
+            if not isinstance(scored, (AcquisitionEI, AcquisitionMPI)) or scored._rule is None or \
+                    isinstance(scored, (AcquisitionEI_MCMC, AcquisitionMPI_MCMC)):
+                raise NotImplementedError("black-box constraints weight EI and MPI over the exact GPModel")
+            scored._set_feasibility(self.feasibility)
         self.num_acquisitions = 0
         self.suggested_sample = None
         self.cum_time = 0.0
@@ -462,11 +495,33 @@ class BayesianOptimization(object):
         Y = np.vstack(values)
         return -Y if self.maximize else Y
 
+    def _evaluate_constraints(self, X):
+        """The constraint values [n, K] at the rows of ``X``."""
+        if self.constraint_function is None:
+            raise ValueError("constraint values C without a constraint_function cover the initial design only")
+        X = np.atleast_2d(X)
+        return np.asarray(self.constraint_function(X), dtype=float).reshape(X.shape[0], -1)
+
     # -- core/bo.py:236-254 ----------------------------------------------------------------
     def _update_model(self, normalization_type='stats'):
         if self.num_acquisitions % self.model_update_interval == 0:
             Y_inmodel = normalize(self.Y, normalization_type) if self.normalize_Y else self.Y
             self.model.updateModel(self.X, Y_inmodel, None, None)
+            if self.feasibility is not None:      # the constraint GPs are refitted with the surrogate, on the same rows
+                self.feasibility.update(self.X, self.C)
+
+    def _best_observation(self):
+        """Row of the reported optimum: the lowest objective; under black-box constraints among the feasible observations, or
+        the least violating one while there is none (see the class)."""
+        if self.feasibility is None:
+            return int(np.argmin(self.Y))
+        ok = self.feasibility.feasible(self.C)
+        if ok.any():
+            rows = np.flatnonzero(ok)
+            return int(rows[np.argmin(self.Y[rows, 0])])
+        viol = self.feasibility.violation(self.C)
+        rows = np.flatnonzero(viol == viol.min())
+        return int(rows[np.argmin(self.Y[rows, 0])])
 
     # -- core/bo.py:216-234 ----------------------------------------------------------------
     def _compute_next_evaluations(self, pending_zipped_X=None, ignored_zipped_X=None):
@@ -501,6 +556,8 @@ class BayesianOptimization(object):
                 break
             x = self._compute_next_evaluations()
             y = self._evaluate(x, record_cost=True)
+            if self.feasibility is not None:
+                self.C = np.vstack((self.C, self._evaluate_constraints(x)))
             self.X = np.vstack((self.X, x))
             self.Y = np.vstack((self.Y, y))
             self.num_acquisitions += 1
@@ -508,6 +565,6 @@ class BayesianOptimization(object):
             if verbosity or self.verbosity:
                 print("num acquisition: %d, time elapsed: %.2fs" % (self.num_acquisitions, time.time() - t0))
         self.cum_time = time.time() - t0
-        i = int(np.argmin(self.Y))
+        i = self._best_observation()
         self.x_opt, self.fx_opt = self.X[i], float(self.Y[i, 0])
         return self.x_opt, self.fx_opt

@@ -56,6 +56,28 @@ __device__ __forceinline__ double gp_log_ndtr(double z) {
     return log_lhs + log(right_hand_side);
 }
 
+// One black-box constraint's share of the probability of feasibility at a location (Gardner et al. 2014; Gelbart et al. 2014):
+// (mean, var) of the constraint GP's NORMALISED posterior, (c_mean, c_std) its output normaliser, b its upper bound.  Un-normalised
+// and clipped exactly as acq_terms does; z = (b - m) / s.  Out: log Phi(z), and what feas_grad needs -- the inverse Mills ratio
+// lambda(z) = phi(z) / Phi(z) = exp(-z^2 / 2 - log(2 pi) / 2 - log Phi(z)), formed in log space: it stays finite (~ -z) where Phi
+// underflows, and nothing is divided by a Phi that rounded to zero.
+__device__ __forceinline__ void feas_terms(double mean, double var, double c_mean, double c_std, double b, double &logphi,
+                                           double &lam, double &z, double &s) {
+    const double m = mean * c_std + c_mean;
+    double v = var * (c_std * c_std);
+    v = (v < 1e-10) ? 1e-10 : v;
+    s = sqrt(v);
+    z = (b - m) / s;
+    logphi = gp_log_ndtr(z);
+    lam = exp(-0.5 * z * z - 0.91893853320467274178032973640562 - logphi);
+}
+// d log Phi(z) / dx_d = lambda (-dm - z ds) / s with dm = c_std dmdx, ds = c_std^2 dvdx / (2 s)
+__device__ __forceinline__ double feas_grad(double lam, double z, double s, double c_std, double dmdx, double dvdx) {
+    const double dm = c_std * dmdx;
+    const double ds = (c_std * c_std) * dvdx / (2.0 * s);
+    return lam * (-dm - z * ds) / s;
+}
+
 // AcquisitionLP._penalized_acquisition (LP.py:70-89) for one location: negacq = -acq(x) in, the penalised score out.
 // transform: 0 = none (log(acq + 1e-50)), 1 = softplus (LP.py:77-83)
 __device__ __forceinline__ double lp_value(double negacq, const double *x, int D, const double *Xb, int nb, const double *r0,

@@ -592,6 +592,7 @@ extern "C" int gp_set_data(gp_t *g, const double *X, const double *Y, int64_t N,
     if (D != g->D) g->sp.Mz = g->sp.tM = 0;   // inducing inputs (and a sparse candidate table) of another dimension are none of this data
     g->N = N;
     g->Npad = Npad;
+    if (D != g->D) g->feas.K = 0;             // nor can a probability of feasibility cached over candidates of another width
     if (g->cost.Nc && g->cost.kp.D != D) {   // a surface of another width cannot serve these inputs
         g->cost.Nc = 0;
         g->cost_tab = 0;

@@ -283,6 +283,16 @@ struct CostState {
     DevBuf<double> dPart;      // the chunks' partial sums of a values-only table launch cut along the surface (cost.hip)
 };
 
+// The probability of feasibility over the resident candidates (api_feas.hip): log prod_k Phi of K constraint GPs, a snapshot in a
+// buffer of the context's own -- nothing of the constraint handles is kept.  K > 0 while dTabLogF holds the M rows' values.
+struct FeasState {
+    int K = 0;
+    long M = 0;
+    DevBuf<double> dTabLogF;   // [M]
+    DevBuf<double> dWork;      // gp_fmin_rows: the listed rows (8 bytes each), then their values
+};
+static_assert(GP_FEAS_MAX == FEAS_MAX_K, "the kernels' argument takes GP_FEAS_MAX constraints");
+
 // The affine mean function m(x) = x^T A + b of the exact GP (api_mean.hip): a snapshot of the mapping's parameters in a buffer of
 // the context's own.  While one is resident dYraw keeps the targets gp_set_data brought (the output warp's buffer and convention)
 // and dY holds the residuals Y - m(X) every fit route factors against; `stale` while dY still has to be rebuilt from them
@@ -455,6 +465,7 @@ struct gp_ctx {
     EsState es;         // entropy search: representers and belief (api_es.hip)
     CostState cost;     // the cost surface of the flagged scoring calls (api_cost.hip)
     MeanState mean;     // the mean function (api_mean.hip)
+    FeasState feas;     // the cached probability of feasibility of the flagged table entries (api_feas.hip)
     bool dead = false;  // gp_shutdown ran: the device's streams are gone, only gp_destroy is still valid
 };
 
@@ -712,10 +723,14 @@ int run_predict(gp_ctx *g, int include_noise, bool tiles_only = false, const Chu
 int ensure_out(gp_ctx *g);
 // What to score, as the C boundary got it: the base acquisition, and the local penaliser on top of it (the batch on the HOST)
 // type: GP_ACQ_*, with GP_ACQ_PER_COST or-ed in when the scores are to be divided by the resident cost surface
-struct AcqSpec { int type; double par, fmin, y_mean, y_std; };
+// feas_ok: the entry understands GP_ACQ_TIMES_FEAS / GP_ACQ_POF (the exact table's value entries); everywhere else the bits stay
+// in what acq_base returns and the call ends as an unknown acquisition
+struct AcqSpec { int type; double par, fmin, y_mean, y_std; bool feas_ok = false; };
 struct LpSpec { int transform; const double *Xb; int nb; const double *r0, *s0; };
 static inline int acq_base(int type) { return type & ~GP_ACQ_PER_COST; }            // the acquisition itself
 static inline bool acq_per_cost(int type) { return (type & GP_ACQ_PER_COST) != 0; }
+static inline bool acq_times_feas(const AcqSpec &a) { return a.feas_ok && (a.type & GP_ACQ_TIMES_FEAS) != 0; }
+static inline int acq_rule(const AcqSpec &a) { return acq_base(a.feas_ok ? a.type & ~GP_ACQ_TIMES_FEAS : a.type); }   // the rule a taught entry scores
 // a single-output model, a known acquisition; with the flag: EI or MPI, a resident surface, no penaliser (lp null)
 int check_acq(const gp_ctx *g, const AcqSpec &a, const LpSpec *lp = nullptr);
 int check_per_cost(const gp_ctx *g, int type, bool lp);   // the flag's own conditions (no-op without it)
@@ -724,6 +739,15 @@ int check_per_cost(const gp_ctx *g, int type, bool lp);   // the flag's own cond
 // locations of a fused rows pass, applied to its pinned result block (laid out for MV locations) behind the pass on the stream
 int cost_divide(gp_ctx *g, const double *X, long M, bool grad, double *acq, double *dacq);
 void cost_divide_block(gp_ctx *g, const RowsX &rx, bool grad, double *blk, int MV);
+// api_feas.hip.  feas_apply: acq [M] of the resident candidates times exp of the cached log F (pof: -exp alone), on the stream
+void feas_apply(gp_ctx *g, bool pof, double *acq);
+int train_values(gp_ctx *g);   // api_predict.hip: gp_fmin's quantity of every training row into dMu [N], not drained
+// api_rows.hip: whether an M-location call of g takes the fused route now (counts towards the inverse factor's build policy), and
+// one fused pass of g -- posterior, and the acquisition aq when on -- put on the stream WITHOUT the wait: *r is the pass's
+// report, *arrivals what PassOwner::wait is owed.  The caller has several handles' passes of one device behind each other.
+bool rows_take_fused(gp_ctx *g, int64_t M);
+int rows_prepare(gp_ctx *g);   // inverse factor, scratch, owner: everything that may synchronise, ahead of the first pass
+void rows_enqueue(gp_ctx *g, const RowsX &rx, int include_noise, int want_grad, const RowsAcq &aq, PassReport *r, unsigned *arrivals);
 int check_lp(const LpSpec &lp);                     // transform 0 / 1, 0 <= nb <= GP_LP_MAX_NB, a batch where nb > 0
 int check_sense(int sense);
 int check_k(int k);

@@ -16,6 +16,7 @@ extern "C" int gp_set_candidates(gp_t *g, const double *Xs, int64_t M) {
     g->M = M;
     g->predicted = false;
     if (g->cost_tab == 1) g->cost_tab = 0;
+    g->feas.K = 0;   // the cached probability of feasibility was this table's
     return 0;
 }
 
@@ -131,8 +132,18 @@ extern "C" int gp_predict(gp_t *g, int include_noise, double *mean, double *var)
 // ---- the checks of what a caller asks to have scored, one each --------------------------------------------------------------
 int check_acq(const gp_ctx *g, const AcqSpec &a, const LpSpec *lp) {
     if (g->P != 1) return fail(GP_ERR_ARG, "acquisitions need P == 1");
-    const int base = acq_base(a.type);
-    if (base < GP_ACQ_EI || base > GP_ACQ_MPI) return fail(GP_ERR_ARG, "unknown acquisition %d", a.type);
+    const int base = acq_rule(a);
+    const bool feas = acq_times_feas(a);
+    if (base == GP_ACQ_POF && a.feas_ok) {
+        if (!feas) return fail(GP_ERR_ARG, "GP_ACQ_POF is valid only together with GP_ACQ_TIMES_FEAS");
+    } else if (base < GP_ACQ_EI || base > GP_ACQ_MPI) {
+        return fail(GP_ERR_ARG, "unknown acquisition %d", a.type);
+    }
+    if (feas) {
+        if (base == GP_ACQ_LCB) return fail(GP_ERR_ARG, "GP_ACQ_TIMES_FEAS: LCB takes no probability of feasibility");
+        if (g->feas.K < 1 || g->feas.M != g->M)
+            return fail(GP_ERR_ARG, "GP_ACQ_TIMES_FEAS without a probability of feasibility of the resident candidates (gp_feas_table)");
+    }
     return check_per_cost(g, a.type, lp != nullptr);
 }
 // GP_ACQ_PER_COST: improvement per unit of cost is EI's and MPI's (LCB.py ignores the cost, LP.py:27 builds the penalised
@@ -183,10 +194,14 @@ int argbest_read(gp_ctx *g, const double *v, long n, int sense, int64_t *idx, do
 // penaliser over the same buffers when lp is given (AcquisitionLP, GPyOpt/GPyOpt/acquisitions/LP.py:105-140).  No checks, no
 // posterior: each model's preamble and its route to one come first.  Not drained.
 int score_rows(gp_ctx *g, const AcqSpec &a, const LpSpec *lp, bool grad, const ScoreRows &r) {
+    const int rule = acq_rule(a);
     if (grad)
-        launch_acq_grad(g->s, acq_base(a.type), a.par, a.fmin, a.y_mean, a.y_std, r.mean, r.var, r.dm, r.dv, r.M, g->D, r.acq, r.dacq);
-    else
-        launch_acq(g->s, acq_base(a.type), a.par, a.fmin, a.y_mean, a.y_std, r.mean, r.var, r.M, r.acq);
+        launch_acq_grad(g->s, rule, a.par, a.fmin, a.y_mean, a.y_std, r.mean, r.var, r.dm, r.dv, r.M, g->D, r.acq, r.dacq);
+    else if (rule != GP_ACQ_POF)
+        launch_acq(g->s, rule, a.par, a.fmin, a.y_mean, a.y_std, r.mean, r.var, r.M, r.acq);
+    // the probability of feasibility first, then the cost, then the penaliser's log transform (values of the resident table only:
+    // check_acq)
+    if (acq_times_feas(a)) feas_apply(g, rule == GP_ACQ_POF, r.acq);
     if (acq_per_cost(a.type)) return cost_divide(g, r.X, r.M, grad, r.acq, r.dacq);   // (never with lp: check_per_cost)
     if (!lp) return 0;
     int rc;
@@ -244,19 +259,24 @@ int scores_out(gp_ctx *g, const double *acq, const double *dacq, long M, int D, 
     return 0;
 }
 
+int train_values(gp_ctx *g) {
+    // (a resident mean function: m(X_i) + r_i - d alpha_i = y_i - d alpha_i with the RAW targets; K alpha + m(X) directly)
+    if (g->fmin_direct) {
+        launch_train_mean(g->s, g->dX, g->N, g->kp, g->dAlpha, g->dMu);
+        mean_add(g, g->dX, g->N, g->dMu);
+    } else {
+        launch_train_mean_identity(g->s, g->mean.on() ? g->dYraw : g->dY, g->dAlpha, g->noise + 1e-8 + g->jitter, g->N, g->dMu);
+    }
+    return 0;
+}
+
 extern "C" int gp_fmin(gp_t *g, double *fmin) {
     if (!g || !fmin) return fail(GP_ERR_ARG, "null argument");
     GP_FITTED(g);
     if (g->P != 1) return fail(GP_ERR_ARG, "gp_fmin needs P == 1");
     if (!g->fmin_valid) {
-        // (a resident mean function: m(X_i) + r_i - d alpha_i = y_i - d alpha_i with the RAW targets; K alpha + m(X) directly)
-        if (g->fmin_direct) {
-            launch_train_mean(g->s, g->dX, g->N, g->kp, g->dAlpha, g->dMu);
-            mean_add(g, g->dX, g->N, g->dMu);
-        } else {
-            launch_train_mean_identity(g->s, g->mean.on() ? g->dYraw : g->dY, g->dAlpha, g->noise + 1e-8 + g->jitter, g->N, g->dMu);
-        }
         int rc;
+        if ((rc = train_values(g))) return rc;
         if ((rc = argbest_read(g, g->dMu, g->N, -1, nullptr, &g->fmin))) return rc;
         g->fmin_valid = true;
     }
@@ -281,7 +301,7 @@ int run_acq(gp_ctx *g, const AcqSpec &a, const LpSpec *lp, bool grad) {
 extern "C" int gp_acq(gp_t *g, int type, double par, double fmin, double y_mean, double y_std, double *out) {
     if (!g || !out) return fail(GP_ERR_ARG, "null argument");
     GP_SCORING(g);
-    return acq_values(g, AcqSpec{type, par, fmin, y_mean, y_std}, nullptr, out, nullptr);
+    return acq_values(g, AcqSpec{type, par, fmin, y_mean, y_std, true}, nullptr, out, nullptr);
 }
 
 // The winner among the resident candidates of the acquisition -- penalised when lp is given --, the rows of exclude [nex] out of
@@ -298,7 +318,7 @@ int acq_argbest(gp_ctx *g, const AcqSpec &a, const LpSpec *lp, int sense, const 
 
 extern "C" int gp_acq_argbest(gp_t *g, int type, double par, double fmin, double y_mean, double y_std, int sense, int64_t *idx,
                    double *val) {
-    return acq_argbest(g, AcqSpec{type, par, fmin, y_mean, y_std}, nullptr, sense, nullptr, 0, idx, val);
+    return acq_argbest(g, AcqSpec{type, par, fmin, y_mean, y_std, true}, nullptr, sense, nullptr, 0, idx, val);
 }
 
 // ---- local penalisation (batch acquisition of run.py:1238-1257; GPyOpt/GPyOpt/acquisitions/LP.py) -----------
@@ -321,14 +341,14 @@ extern "C" int gp_acq_lp(gp_t *g, int type, double par, double fmin, double y_me
     if (!g || !out) return fail(GP_ERR_ARG, "null argument");
     GP_SCORING(g);
     const LpSpec lp{transform, Xb, nb, r_x0, s_x0};
-    return acq_values(g, AcqSpec{type, par, fmin, y_mean, y_std}, &lp, out, nullptr);
+    return acq_values(g, AcqSpec{type, par, fmin, y_mean, y_std, true}, &lp, out, nullptr);
 }
 
 extern "C" int gp_acq_lp_argbest(gp_t *g, int type, double par, double fmin, double y_mean, double y_std, int transform,
                       const double *Xb, int nb, const double *r_x0, const double *s_x0, int sense,
                       const int64_t *exclude, int nex, int64_t *idx, double *val) {
     const LpSpec lp{transform, Xb, nb, r_x0, s_x0};
-    return acq_argbest(g, AcqSpec{type, par, fmin, y_mean, y_std}, &lp, sense, exclude, nex, idx, val);
+    return acq_argbest(g, AcqSpec{type, par, fmin, y_mean, y_std, true}, &lp, sense, exclude, nex, idx, val);
 }
 
 // full_cov = True branch of PosteriorExact._raw_predict (posterior.py:280-284)
@@ -365,7 +385,7 @@ int acq_topk(gp_ctx *g, const AcqSpec &a, int sense, int k, int64_t *idx, double
 
 extern "C" int gp_acq_topk(gp_t *g, int type, double par, double fmin, double y_mean, double y_std, int sense, int k,
                 int64_t *idx, double *val) {
-    return acq_topk(g, AcqSpec{type, par, fmin, y_mean, y_std}, sense, k, idx, val);
+    return acq_topk(g, AcqSpec{type, par, fmin, y_mean, y_std, true}, sense, k, idx, val);
 }
 
 // ---- posterior samples of the latent function (GP.posterior_samples_f, gp.py:581-609) ------------------------

@@ -121,6 +121,24 @@ static int rows_fused(gp_ctx *g, const double *Xs, int M, int include_noise, int
         [&](int m0, int mc, int MV, const double *o) { rows_unpack(o, MV, m0, mc, g->D, mean, var, acq, dmdx, dvdx, dacq); });
 }
 
+// What api_feas.hip sequences: several handles' passes of one device behind each other on the shared stream, one drain at the end
+bool rows_take_fused(gp_ctx *g, int64_t M) { return rows_fused_ok(g, M) && rows_use_factor(g); }
+int rows_prepare(gp_ctx *g) {
+    int rc;
+    if ((rc = ensure_linv(g))) return rc;
+    RowsWork w;
+    return rows_scratch(g, &w);
+}
+void rows_enqueue(gp_ctx *g, const RowsX &rx, int include_noise, int want_grad, const RowsAcq &aq, PassReport *r, unsigned *arrivals) {
+    RowsWork w;
+    (void)rows_scratch(g, &w);   // (reserved by rows_prepare: the pointers alone)
+    *r = g->pass.next();
+    launch_rows(g->s, g->dLi, g->Npad, rx, g->kp, g->dX, g->N, g->dAlpha, want_grad, g->kp.variance, include_noise ? g->noise : 0.0,
+                aq, w, *r, g->rows_nt < 0 ? (g->Npad > 8192 ? 1 : 0) : g->rows_nt, rows_mean(g));
+    *arrivals = rows_finish_grid(g->N);
+    ++(rx.M > ROWS_MAX_M ? g->rows_wide_passes : g->rows_narrow_passes);
+}
+
 // The posterior of a handful of locations: gp_set_candidates + gp_predict (+ gp_predict_grad when dmdx / dvdx are given) as ONE
 // call (PosteriorExact._raw_predict, posterior.py:273-302; GP.predictive_gradients, gp.py:407-454).
 extern "C" int gp_predict_rows(gp_t *g, const double *Xs, int64_t M, int include_noise, double *mean, double *var, double *dmdx,

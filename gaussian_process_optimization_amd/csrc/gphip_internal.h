@@ -502,6 +502,27 @@ void launch_mean_add_grad(hipStream_t s, long M, int D, int P, const double *Ab,
 int mean_grad_chunks(long N);
 void launch_mean_grad(hipStream_t s, const double *X, const double *alpha, long ldal, long N, int D, int P, double *part, double *out);
 
+// ---- feas.hip: the probability of feasibility of K constraint GPs and the product it puts behind EI / MPI ------------------------
+// K constraints at a handful of locations: constraint k's normalised posterior -- mean / var [M], dm / dv [M, D] (read with grad
+// only) on the device or in a pinned result block --, its output normaliser and its upper bound
+#define FEAS_MAX_K 8   // constraints per call (GP_FEAS_MAX of the public header)
+struct FeasRows {
+    int K;
+    const double *mean[FEAS_MAX_K], *var[FEAS_MAX_K], *dm[FEAS_MAX_K], *dv[FEAS_MAX_K];
+    double bound[FEAS_MAX_K], c_mean[FEAS_MAX_K], c_std[FEAS_MAX_K];
+};
+// logF[i] = (first ? 0 : logF[i]) + log Phi((b - m_i) / s_i) over a table's posterior: the constraints are added one launch each
+void launch_feas_table(hipStream_t s, const double *mean, const double *var, long M, double c_mean, double c_std, double b,
+                       int first, double *logF);
+// acq[i] <- (pof ? -1 : acq[i]) exp(logF[i])
+void launch_feas_apply(hipStream_t s, const double *logF, long M, int pof, double *acq);
+// M locations, one workgroup each.  neg given: neg [M] <- neg F and (grad) dneg [M, D] <- F (dneg + neg dlogF) in place, with pof
+// neg = -1 and dneg = 0 taken as what came in; neg null: logF [M] and (grad) dlogF [M, D] are written.  The sum over k runs in
+// index order, as launch_feas_table's launches do
+void launch_feas_rows(hipStream_t s, const FeasRows &fr, int M, int D, int grad, int pof, double *neg, double *dneg, double *logF,
+                      double *dlogF);
+void launch_feas_gather(hipStream_t s, const double *v, const long long *rows, long n, double *out);   // out[i] = v[rows[i]]
+
 // ---- rns.hip: fp64-equivalent contraction on the int8 matrix cores (option "emulate_fp64") -----------------------------
 #define GP_RNS_T 14
 #define GP_RNS_KMAX 8192   // longest contraction (bytes) one residue launch may take: see rns_reduce_f in rns.hip

@@ -45,6 +45,13 @@ typedef struct gp_ctx gp_t;
 /* or-ed into the `type` of a scoring entry: the scores are divided by the cost of the resident cost surface (the cost entries
  * near the end of this header).  Without it every entry behaves as it always did. */
 #define GP_ACQ_PER_COST 0x100
+/* black-box constraints (the feasibility entries at the end of this header).  GP_ACQ_TIMES_FEAS, or-ed into the `type` of the
+ * entries named there, multiplies the scores by the cached probability of feasibility; GP_ACQ_POF is the rule whose value is 1
+ * and whose gradient is 0 -- valid only together with GP_ACQ_TIMES_FEAS: the probability of feasibility alone, for the time
+ * while no observation is feasible.  Without the flag every entry behaves as it always did. */
+#define GP_ACQ_POF 3
+#define GP_ACQ_TIMES_FEAS 0x200
+#define GP_FEAS_MAX 8 /* constraints per call */
 
 /* error codes (< 0) */
 #define GP_ERR_ARG (-1)
@@ -860,6 +867,59 @@ int gp_cost_rows(gp_t *gp, const double *Xs, int64_t M, double *logc, double *dl
 int gp_mean_set(gp_t *gp, const double *A, const double *b);
 int gp_mean_info(gp_t *gp, int *has_A, int *has_b);
 int gp_mean_grad(gp_t *gp, double *dA, double *db);
+
+/* ---- black-box constraints: feasibility-weighted EI / MPI (Gardner et al. 2014; Gelbart et al. 2014) ---------------------------
+ * K <= GP_FEAS_MAX constraints c_k(x) <= bound[k] are known through evaluations only; each is modelled by a GP of its own, and
+ * the acquisition is weighted by the probability of feasibility
+ *     F(x) = prod_k Phi(z_k),   z_k = (bound[k] - m_k(x)) / s_k(x),
+ * m_k = mean c_std[k] + c_mean[k] and s_k = sqrt(max(var c_std[k]^2, 1e-10)) the un-normalised predictive mean and standard
+ * deviation of constraint GP k, likelihood noise included (GPModel.predict's convention), clipped as the acquisitions clip
+ * theirs.  Everything is carried as log F = sum_k log Phi(z_k), summed in index order on every route; a location 45 sigma inside
+ * the infeasible side has a finite log F and a finite gradient  sum_k lambda(z_k) (-dm_k - z_k ds_k) / s_k,  lambda = phi / Phi
+ * formed in log space.
+ *
+ * A constraint handle is an ordinary gp_t: a fitted exact model (gp_fit) that holds neither a sparse fit nor an ensemble, on the
+ * scored handle's device with the same D, P = 1 and no output warp, not the scored handle itself, every handle once.  Its
+ * N, kernel, Gower set-up and mean function are its own.  GP_ERR_STATE: a handle that is not fitted; GP_ERR_ARG: everything
+ * else, K outside 1 .. GP_FEAS_MAX, a c_std that is not positive and finite, a non-finite bound or c_mean.  No pointer to a
+ * constraint handle is kept after a call returns.
+ *
+ * gp_feas_table caches log F over gp's resident candidates (GP_ERR_STATE without gp_set_data / gp_set_candidates; gp's own fit is
+ * not needed).  For each constraint in turn gp's table is copied, device to device, into that handle's resident candidates --
+ * AFTERWARDS THE CONSTRAINT HANDLE'S RESIDENT TABLE IS gp's, its cached posterior that table's --, the handle's table posterior
+ * runs with the likelihood noise, and log Phi is added to gp's cache.  The cache is a snapshot: refitting or destroying a
+ * constraint handle afterwards leaves it as it is (a new call refreshes it); gp_set_candidates / gp_set_candidates_kumar on gp,
+ * gp_set_data with another D, and K = 0 (which takes null arguments) drop it.
+ * gp_feas_info: *K constraints and *M rows of the cache, both 0 when there is none.  gp_feas_get_table: logF [M]; GP_ERR_STATE
+ * without a cache.
+ *
+ * GP_ACQ_TIMES_FEAS in the `type` of gp_acq, gp_acq_argbest, gp_acq_topk, gp_acq_lp and gp_acq_lp_argbest multiplies the negated
+ * scores by F behind the base rule -- ahead of the division of GP_ACQ_PER_COST and ahead of the penaliser's log transform, so a
+ * penalised table scores EI F.  GP_ERR_ARG: LCB (its sign makes a product meaningless), no cache or one of another table size,
+ * GP_ACQ_POF without the flag.  Every other entry refuses both: the table gradient entries, gp_acq_rows, the sparse, ensemble,
+ * entropy-search, group and comm entries.
+ *
+ * gp_feas_rows: logF [M] and, when dlogF is given, its x-gradient [M, D] at M >= 1 locations Xs [M, D], through the constraint
+ * handles' fused rows passes in groups of up to 8 locations (passes of 4 where M D > 128 doubles).
+ * gp_acq_rows_feas: the acquisition optimiser's call.  Per pass: the scored handle's fused pass (type: GP_ACQ_EI, GP_ACQ_MPI or
+ * GP_ACQ_POF, with GP_ACQ_TIMES_FEAS implied and GP_ACQ_PER_COST allowed; likelihood noise included), each constraint handle's
+ * fused pass (gradients when dout is given), the fold  neg <- neg F, dneg <- F (dneg + neg dlogF)  into the scored handle's
+ * result block, the cost division where asked for, then ONE drain -- no host round trip in between.  A handle that cannot take
+ * the fused route (gp_rows_stats: option small_m, M D too wide, the inverse factor's build policy) goes through
+ * gp_set_candidates and its table posterior instead -- its results stay on the device and are folded from there, and its
+ * resident table is the group's locations afterwards (for gp that drops the cache of gp_feas_table).  There is no penaliser.
+ *
+ * gp_fmin_rows: gp_fmin's quantity -- y_i - (noise + 1e-8 + jitter) alpha_i over the raw targets -- minimised over the listed
+ * training rows (the feasible ones); with every row listed it is gp_fmin bit for bit.  GP_ERR_ARG: n < 1, a row outside [0, N). */
+int gp_feas_table(gp_t *gp, gp_t *const *cons, int K, const double *bound, const double *c_mean, const double *c_std);
+int gp_feas_info(gp_t *gp, int *K, int64_t *M);
+int gp_feas_get_table(gp_t *gp, double *logF);
+int gp_feas_rows(gp_t *const *cons, int K, const double *bound, const double *c_mean, const double *c_std, const double *Xs,
+                 int64_t M, double *logF, double *dlogF);
+int gp_acq_rows_feas(gp_t *gp, gp_t *const *cons, int K, const double *bound, const double *c_mean, const double *c_std,
+                     const double *Xs, int64_t M, int type, double par, double fmin, double y_mean, double y_std, double *out,
+                     double *dout);
+int gp_fmin_rows(gp_t *gp, const int64_t *rows, int64_t n, double *fmin);
 
 #ifdef __cplusplus
 }
