@@ -109,6 +109,12 @@ SIGNATURES = [
                                           ctypes.c_double, ctypes.c_double, ctypes.c_int, ctypes.c_int, _vp, ctypes.c_int,
                                           _vp, _vp, _vp, _vp]),
     ("gp_sparse_rows_stats", ctypes.c_int, [_vp, c_int64_p, c_int64_p]),
+    ("gp_sparse_predict_full_cov", ctypes.c_int, [_vp, c_double_p, ctypes.c_int64, ctypes.c_int, c_double_p, c_double_p]),
+    ("gp_sparse_posterior_samples", ctypes.c_int, [_vp, c_double_p, ctypes.c_int64, ctypes.c_int, c_double_p, ctypes.c_int,
+                                                   ctypes.c_int, c_double_p, c_double_p, c_double_p]),
+    ("gp_sparse_cov_set_points", ctypes.c_int, [_vp, c_double_p, ctypes.c_int64]),
+    # (void* for the pointers of the per-candidate entry, as for the rows entries above)
+    ("gp_sparse_cov_between", ctypes.c_int, [_vp, _vp, ctypes.c_int64, _vp]),
     ("gp_ens_fit", ctypes.c_int, [_vp, ctypes.c_int, c_double_p, c_double_p, c_double_p, ctypes.c_int, c_double_p, c_double_p,
                                   c_double_p, c_double_p]),
     ("gp_ens_info", ctypes.c_int, [_vp, c_int_p]),
@@ -360,6 +366,7 @@ class Handle(object):
         self.h = h
         self.device = int(device)
         self.sparse_M = 0      # rows of the sparse model's candidate table (sparse_set_candidates); 0: the library refuses to score
+        self.sparse_R = 0      # rows of the sparse model's second point set (sparse_cov_set_points); 0: sparse_cov_between is refused
         self.cost_key = None   # whose cost surface the handle holds: set by the caller of cost_set, dropped with the surface
         self.feas_key = None   # whose probability of feasibility the handle caches over its candidates: set by the caller of feas_table
 
@@ -896,6 +903,52 @@ class Handle(object):
         a, b = ctypes.c_int64(), ctypes.c_int64()
         check(self.lib, self.lib.gp_sparse_rows_stats(self.h, ctypes.byref(a), ctypes.byref(b)), "gp_sparse_rows_stats")
         return dict(fused=a.value, fallback=b.value)
+
+    # -- the joint posterior of the sparse model (include/gphip.h, csrc/api_sparse_cov.hip)
+    def _sparse_rows_of(self, Xs, what):
+        Xs = as_f64(Xs, 2)
+        if Xs.shape[1] != self.D:
+            raise ValueError("%s have %d columns, model has %d" % (what, Xs.shape[1], self.D))
+        return Xs
+
+    def sparse_predict_full_cov(self, Xs, include_noise=True):
+        """(mean [M, P], cov [M, M]) of the sparse posterior at ``Xs``; cov is bitwise symmetric."""
+        Xs = self._sparse_rows_of(Xs, "candidates")
+        M = Xs.shape[0]
+        mean, cov = np.empty((M, self.P)), np.empty((M, M))
+        rc = self.lib.gp_sparse_predict_full_cov(self.h, dptr(Xs), M, int(bool(include_noise)), dptr(mean), dptr(cov))
+        check(self.lib, rc, "gp_sparse_predict_full_cov")
+        return mean, cov
+
+    def sparse_posterior_samples(self, Xs, Z, include_noise=False, maxtries=5):
+        """Z[S, M] standard normals -> (mean[M, P], dev[S, M], jitter) over the sparse posterior at ``Xs``: draw s of output d =
+        mean[:, d] + dev[s]."""
+        Xs = self._sparse_rows_of(Xs, "candidates")
+        Z = as_f64(Z, 2)
+        M = Xs.shape[0]
+        if Z.shape[1] != M:
+            raise ValueError("Z needs one column per row of Xs")
+        mean, dev = np.empty((M, self.P)), np.empty((Z.shape[0], M))
+        jit = ctypes.c_double()
+        rc = self.lib.gp_sparse_posterior_samples(self.h, dptr(Xs), M, int(bool(include_noise)), dptr(Z), Z.shape[0], int(maxtries),
+                                                  dptr(mean), dptr(dev), ctypes.byref(jit))
+        check(self.lib, rc, "gp_sparse_posterior_samples")
+        return mean, dev, jit.value
+
+    def sparse_cov_set_points(self, X2):
+        """Make ``X2`` [R, D] the resident second point set of ``sparse_cov_between``."""
+        X2 = self._sparse_rows_of(X2, "the points")
+        check(self.lib, self.lib.gp_sparse_cov_set_points(self.h, dptr(X2), X2.shape[0]), "gp_sparse_cov_set_points")
+        self.sparse_R = X2.shape[0]
+
+    def sparse_cov_between(self, X1):
+        """cov [M1, R]: the sparse posterior covariance between the rows of ``X1`` and the resident points."""
+        X1 = self._sparse_rows_of(X1, "locations")
+        cov = np.empty((X1.shape[0], self.sparse_R))
+        rc = self.lib.gp_sparse_cov_between(self.h, X1.ctypes.data, X1.shape[0], cov.ctypes.data)
+        if rc:
+            check(self.lib, rc, "gp_sparse_cov_between")
+        return cov
 
     # -- the ensemble (include/gphip.h, gp_ens_*): S hyper-parameter members with resident posteriors --------------------------
     def ens_fit(self, variances, lengthscales, noises, maxtries=5):

@@ -918,7 +918,9 @@ class AcquisitionEntropySearch(AcquisitionBase):
     the representers' posterior (``gp_es_set_representers``), the EP sweeps of p_min (``gp_es_pmin``) and every score
     (``gp_es_acq`` / ``gp_es_acq_argbest`` over the candidate block, ``gp_es_acq_rows`` for up to eight locations) run on the device; the closing algebra of the belief stays
     on the host (entropy_search.py).  Otherwise -- a sparse model, a cost model, constraints, ``device=False`` -- the reference's
-    per-candidate arithmetic runs on the host over ``predict``, ``predict_covariance`` and ``get_covariance_between_points``.
+    per-candidate arithmetic runs on the host over ``predict``, ``predict_covariance`` and ``get_covariance_between_points``; a
+    sparse model serves a whole block of candidates with one ``predict`` and one ``get_covariance_between_points`` (the
+    representers stay resident on the device: ``gp_sparse_cov_between``).
 
     A deliberate difference: the reference samples representers and computes the belief once and never again
     (``_required_parameters_initialized``); here both are renewed whenever the model's fit has changed (new data or new
@@ -1070,6 +1072,14 @@ class AcquisitionEntropySearch(AcquisitionBase):
         self._check_dim(x)
         self._refresh(False)
         out = np.zeros((x.shape[0], 1))
+        if getattr(self.model, "sparse", False) and x.shape[0] > 0:
+            # a sparse model: the whole block in two device calls (gp_sparse_predict, gp_sparse_cov_between over the resident
+            # representers), then the same arithmetic per candidate
+            _, sd = self.model.predict(x, with_noise=False)
+            cov = self.model.get_covariance_between_points(self.repr_points, x)
+            for j in range(x.shape[0]):
+                out[j, 0] = _es.score(cov[:, [j]] / sd[j], self.logP, self.repr_points_log, self.dlogPdMu, self._Q, self.W)
+            return out
         for j in range(x.shape[0]):
             row = x[[j], :]
             _, sd = self.model.predict(row, with_noise=False)

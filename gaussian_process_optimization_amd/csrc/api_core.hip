@@ -589,7 +589,7 @@ extern "C" int gp_set_data(gp_t *g, const double *X, const double *Y, int64_t N,
         g->capN = capN;
         g->capP = capP;
     }
-    if (D != g->D) g->sp.Mz = g->sp.tM = 0;   // inducing inputs (and a sparse candidate table) of another dimension are none of this data
+    if (D != g->D) g->sp.Mz = g->sp.tM = g->sp.cR = 0;   // inducing inputs (and a sparse candidate table or point set) of another dimension are none of this data
     g->N = N;
     g->Npad = Npad;
     if (D != g->D) g->feas.K = 0;             // nor can a probability of feasibility cached over candidates of another width

@@ -199,6 +199,29 @@ struct PassOwner {
     int wait(hipStream_t s, const PassReport &r, unsigned a0, unsigned a1);
 };
 
+// Pinned, device-visible host memory and its owner (as DevBuf: reserve only grows, the contents are not kept)
+struct PinBuf {
+    double *p = nullptr;
+    long cap = 0;
+    PinBuf() = default;
+    PinBuf(const PinBuf &) = delete;
+    PinBuf &operator=(const PinBuf &) = delete;
+    ~PinBuf() { if (p) (void)hipHostFree(p); }
+    int reserve(long n) {
+        if (n <= cap && p) return 0;
+        if (p) (void)hipHostFree(p);
+        p = nullptr;
+        cap = 0;
+        const hipError_t e = hipHostMalloc((void **)&p, (size_t)n * sizeof(double), hipHostMallocDefault);
+        if (e != hipSuccess) {
+            p = nullptr;
+            return fail(GP_ERR_HIP, "hipHostMalloc(%ld doubles) -> %s", n, hipGetErrorString(e));
+        }
+        cap = n;
+        return 0;
+    }
+};
+
 // The sparse model (variational DTC over Mz inducing inputs, api_sparse.hip) on the context's X, Y, D, P, kernel parameters and
 // main stream: buffers and validity flag of its own -- nothing here is read or written by the exact model's entry points, and
 // the sparse entry points touch none of the exact model's buffers or flags.  n = Mzpad below.
@@ -236,6 +259,23 @@ struct SparseState {
     DevBuf<double> dRowsPart;
     PassOwner pass{1, "the sparse one-location kernel"};
     long rows_fused_calls = 0, rows_fallback_calls = 0;
+    // the joint posterior (api_sparse_cov.hip): buffers of its own, nothing of the table cache or of the exact model.  M = rows of
+    // the call, Mpad = M rounded up to the tile, R = cR
+    DevBuf<double> dCovX;      // [M, D]: the locations of the call
+    DevBuf<double> dCovA;      // Mpad x n: K(Xs, Z), then T = U LB^-T; Rpad x n: K(X2, Z) while G is built
+    DevBuf<double> dCovU;      // Mpad x n: U = K(Xs, Z) Lm^-T
+    DevBuf<double> dCovC, dCovW;   // Mpad x Mpad: the covariance / its factor, T T^T
+    DevBuf<double> dCovZ;      // 2 x Spad x Mpad: the caller's normals, the deviations
+    DevBuf<double> dCovInv;    // Mpad x 128: inverted diagonal tiles of the covariance's factor
+    DevBuf<double> dCovMean;   // P x Mpad: the mean, one row per output
+    DevBuf<double> dCovStat;   // trace and smallest diagonal entry of the matrix to factor
+    long cR = 0;               // rows of the second point set (gp_sparse_cov_set_points; 0: none)
+    DevBuf<double> dX2, dX2s;  // [cR, D]: the points, and the points / lengthscale of the current fit
+    DevBuf<double> dG;         // Rpad x n: G = K(X2, Z) woodbury_inv of the current fit, zero rows in the padding
+    bool g_valid = false;      // dG and dX2s belong to the current fit and points
+    DevBuf<double> dCovOut;    // [M1, cR]: gp_sparse_cov_between beyond ROWS_WIDE_M locations
+    PinBuf covPin;             // [ROWS_WIDE_M, cR]: ... and up to that many, written by the kernel
+    PassOwner cov_pass{1, "the sparse covariance kernel"};   // its counter and ticket (the block holds the ticket only)
 };
 
 // The ensemble (api_ens.hip): S hyper-parameter members over the context's X, Y -- each with alpha, explicit inverse factor,
@@ -489,8 +529,10 @@ static inline void fit_dropped(gp_ctx *g) {
 }
 
 // the sparse fit no longer belongs to the data / parameters / inducing inputs in force, and neither does the cached posterior of
-// the sparse candidate table (the table itself stays, as Z does)
-static inline void sparse_fit_dropped(gp_ctx *g) { g->sp.fitted = g->sp.grad_ready = g->sp.tab_post = g->sp.tab_grad = g->sp.fmin_valid = g->sp.zs_valid = false; }
+// the sparse candidate table (the table itself stays, as Z does), nor G of the second point set (the points stay too)
+static inline void sparse_fit_dropped(gp_ctx *g) {
+    g->sp.fitted = g->sp.grad_ready = g->sp.tab_post = g->sp.tab_grad = g->sp.fmin_valid = g->sp.zs_valid = g->sp.g_valid = false;
+}
 
 // The factor in dA has GROWN by rows (gp_append): L, the inverted diagonal tiles and -- where it was valid -- the inverse factor
 // were extended and stay; rows_calls_since_fit keeps counting towards the inverse factor's build.  Everything else derived from
@@ -687,6 +729,7 @@ enum { EV_CHAIN = 0, EV_BULK = 1, EV_INVP = 2, EV_MISC = 3, EV_FAR = 4, EV_CONV 
 
 // ---- internal entry points (defined in the api_*.hip unit named in the comment of each group) ----
 void shutdown_all();
+int sparse_fitted(gp_ctx *g);   // api_sparse.hip: what every entry over a sparse fit asks first (alive, no mean function, data, parameters, Z, a fit)
 int make_bulk_stream(int device, int reserve, hipStream_t *out);
 int get_streams(int device, int reserve, DevStreams *out);
 int phase_begin(gp_ctx *g, const char *name, double flops, double bytes);

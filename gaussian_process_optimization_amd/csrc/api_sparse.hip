@@ -269,7 +269,7 @@ extern "C" int gp_sparse_fit_grad(gp_t *g, int maxtries, double *lml, double *dv
     return 0;
 }
 
-static int sparse_fitted(gp_ctx *g) {
+int sparse_fitted(gp_ctx *g) {
     int rc;
     if ((rc = sparse_preamble(g, true))) return rc;
     if (!g->sp.fitted) return fail(GP_ERR_STATE, "gp_sparse_fit first");

@@ -477,6 +477,20 @@ void launch_sparse_rows(hipStream_t s, const double *Winv, long n, long Mz, cons
                         const double *w, int mode, double kss, double noise_add, const RowsAcq &aq, double *gpart,
                         const PassReport &r);
 
+// ---- sparse_cov.hip: the sparse posterior covariance between locations and a resident second point set --------------------------
+#define SPARSE_COV_RB 8                                        // rows of G per workgroup (two per wave)
+// workgroups along G's rows -- for the by-value launch the arrivals its counter waits for
+inline unsigned sparse_cov_grid(long R) { return (unsigned)((R + SPARSE_COV_RB - 1) / SPARSE_COV_RB); }
+// cov[i, r] = k(x1_i, x2_r) - sum_j G[r, j] k(x1_i, z_j) for r < R.  G [Rpad, n] = K(X2, Z) woodbury_inv (n = Mz rounded up to
+// GP_TILE, Rpad = R rounded up to it, zero rows in the padding), X2s [R, D] and Zs [Mz, D] the points over the lengthscales
+// (launch_sparse_scale_z).  _rows: the rx.M <= ROWS_WIDE_M locations of rx (rx.M D <= ROWS_MAX_XS) into the host-visible out
+// [rx.M, R], the ticket at r.out[ROWS_OUT_DOUBLES].  _table: X1 [M1, D] and out [M1, R] on the device, in blocks of ROWS_WIDE_M
+// locations through the same kernel body: a row has the same bits on either route, in any company.
+void launch_sparse_cov_rows(hipStream_t s, const double *G, long n, long Mz, long R, const double *X2s, const RowsX &rx,
+                            const KernParams &kp, const double *Zs, double *out, const PassReport &r);
+void launch_sparse_cov_table(hipStream_t s, const double *G, long n, long Mz, long R, const double *X2s, const double *X1, long M1,
+                             const KernParams &kp, const double *Zs, double *out);
+
 // ---- cost.hip: the cost surface of cost-aware EI / MPI and the quotient it puts under the scores --------------------------------
 // logc[i] = shift + scale sum_j alpha[j] k(xs_i, Xc_j) and (dlogc given) its x-gradient [M, D], over the surface Xcs = Xc / lengthscale
 // [Nc, ld] (ld = max(D, 8), zeros beyond D).  One summation order per location in both launches: the same bits (cost.hip).

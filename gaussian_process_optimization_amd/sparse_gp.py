@@ -10,7 +10,8 @@ All numerics run on the device (include/gphip.h, "sparse GP"): ``gp_sparse_fit_g
 ``gp_sparse_fit_grad_batch`` per round of evaluations of all restarts, ``optimize_restarts(parallel=True)`` --,
 ``gp_sparse_predict`` per prediction.  This module is bookkeeping: the flat parameter vector [Z row-major, kern.variance,
 kern.lengthscale, Gaussian_noise.variance] with Z unconstrained, the Y normaliser, lazy refits.  Homoscedastic noise, certain
-inputs, no mean function; ``full_cov`` and posterior sampling are outside this path.
+inputs, no mean function.  The joint posterior -- ``full_cov``, ``posterior_samples_f``, ``posterior_covariance_between_points`` --
+comes from ``gp_sparse_predict_full_cov``, ``gp_sparse_posterior_samples`` and ``gp_sparse_cov_between``.
 """
 import numpy as np
 
@@ -91,6 +92,7 @@ class SparseGPRegression(GPRegression):
             raise NotImplementedError("the sparse GP does not take the Gower kernel")
         self.Z = None
         self._table = None          # the candidate table resident in the sparse model's own block (_stage_table)
+        self._points = None         # the second point set resident for posterior_covariance_between_points (_stage_points)
         super(SparseGPRegression, self).__init__(X, Y, kernel=kernel, normalizer=normalizer, noise_var=1., mean_function=mean_function,
                                                  device=device, name=name)
         self.posterior = _SparsePosteriorView(self)
@@ -239,29 +241,60 @@ class SparseGPRegression(GPRegression):
             self._table = (self._h, np.array(Xnew, copy=True))
         return Xnew
 
+    def _stage_points(self, X1):
+        """Make ``X1`` the resident second point set (gp_sparse_cov_set_points), refitting first if anything changed.  The same
+        points staged again -- entropy search's representers, once per candidate block -- are not uploaded again: the device keeps
+        them across refits and rebuilds what it derives from them."""
+        self._ensure_fit()
+        held = self._points
+        if held is None or held[0] is not self._h or held[1].shape != X1.shape or not np.array_equal(held[1], X1):
+            self._joint_entry("sparse_cov_set_points")(X1)
+            self._points = (self._h, np.array(X1, copy=True))
+
+    def _joint_entry(self, name):
+        """The handle's method ``name`` of the joint posterior; a handle that does not offer it cannot serve the call."""
+        entry = getattr(self._h, name, None)
+        if entry is None:
+            raise NotImplementedError("this handle does not serve the sparse joint posterior (%s)" % name)
+        return entry
+
+    def _joint_rows(self, Xnew):
+        Xnew = np.asarray(Xnew, dtype=float)
+        if Xnew.ndim == 1:
+            Xnew = Xnew[None, :]
+        if Xnew.shape[1] != self.input_dim:
+            raise ValueError("candidates have %d columns, model has %d" % (Xnew.shape[1], self.input_dim))
+        self._ensure_fit()
+        return Xnew
+
     def _raw_predict(self, Xnew, full_cov=False, kern=None):
         """posterior.py:225-248 over the inducing inputs."""
-        if full_cov:
-            raise NotImplementedError("full_cov is outside the sparse path")
         if kern is not None and kern is not self.kern:
             raise NotImplementedError("prediction with a foreign kernel is outside the accelerated path")
-        e = self._empty(Xnew, False)
+        e = self._empty(Xnew, full_cov)
         if e is not None:
             return e
+        if full_cov:
+            return self._joint_entry("sparse_predict_full_cov")(self._joint_rows(Xnew), include_noise=False)
         return self._sparse_predict(Xnew, False)
 
     def predict(self, Xnew, full_cov=False, Y_metadata=None, kern=None, likelihood=None, include_likelihood=True):
-        """gp.py:297-354 on the sparse posterior; ``full_cov`` is not served."""
-        if full_cov:
-            raise NotImplementedError("full_cov is outside the sparse path")
+        """gp.py:297-354 on the sparse posterior."""
         if kern is not None and kern is not self.kern:
             raise NotImplementedError("prediction with a foreign kernel is outside the accelerated path")
-        e = self._empty(Xnew, False)
+        e = self._empty(Xnew, full_cov)
         if e is not None:
             return e
-        mean, var = self._sparse_predict(Xnew, include_likelihood)
+        if full_cov:
+            mean, var = self._joint_entry("sparse_predict_full_cov")(self._joint_rows(Xnew), include_noise=include_likelihood)
+        else:
+            mean, var = self._sparse_predict(Xnew, include_likelihood)
         if self.normalizer is not None:
-            mean, var = self.normalizer.inverse_mean(mean), self.normalizer.inverse_variance(var)
+            mean = self.normalizer.inverse_mean(mean)
+            if full_cov and mean.shape[1] > 1:
+                var = self.normalizer.inverse_covariance(var)
+            else:
+                var = self.normalizer.inverse_variance(var)
         return mean, var
 
     def predictive_gradients(self, Xnew, kern=None):
@@ -286,7 +319,34 @@ class SparseGPRegression(GPRegression):
         return self._h.sparse_fmin()
 
     def posterior_covariance_between_points(self, X1, X2):
-        raise NotImplementedError("full covariances are outside the sparse path")
+        """The off-diagonal block of the full posterior covariance (posterior.py:229-232 over ``_predictive_variable = Z``) of the
+        stacked points, K(X1, X2) - K(X1, Z) woodbury_inv K(Z, X2), in the model's (normalised) output space: what
+        ``GPRegression.posterior_covariance_between_points`` defines.  (The reference's own method, gp.py:714-721, hands the
+        training inputs to a factor that is Mz x Mz: a shape error unless N = Mz.)  ``X1`` is made resident and kept while it
+        stays the same, bit for bit; ``X2`` travels: one ``gp_sparse_cov_between`` per call."""
+        X1 = self._joint_rows(np.atleast_2d(np.asarray(X1, dtype=float)))
+        X2 = self._joint_rows(np.atleast_2d(np.asarray(X2, dtype=float)))
+        if X1.shape[0] == 0 or X2.shape[0] == 0:
+            return np.empty((X1.shape[0], X2.shape[0]))
+        self._stage_points(X1)
+        return np.ascontiguousarray(self._joint_entry("sparse_cov_between")(X2).T)
 
     def posterior_samples_f(self, X, size=10, normals=None, **kw):
-        raise NotImplementedError("posterior sampling is outside the sparse path")
+        """gp.py:581-609 on the sparse posterior: draws of the latent function at X, [Nnew, output_dim, size], with the semantics of
+        ``GPRegression.posterior_samples_f`` -- ``normals`` [output_dim, size, Nnew] for reproducible draws,
+        ``posterior_samples_jitter_``, LinAlgError on an exhausted ladder, the normaliser's std on the deviations."""
+        X = self._joint_rows(np.atleast_2d(np.asarray(X, dtype=float)))
+        M, P = X.shape[0], self.output_dim
+        if normals is None:
+            normals = np.random.standard_normal((P, size, M))
+        normals = np.asarray(normals, dtype=float).reshape(P, size, M)
+        m, dev, self.posterior_samples_jitter_ = self._joint_entry("sparse_posterior_samples")(
+            X, normals.reshape(P * size, M), include_noise=False, maxtries=self.max_jitter_tries)
+        dev = dev.reshape(P, size, M)
+        if self.normalizer is not None:
+            m = self.normalizer.inverse_mean(m)
+            dev = dev * np.asarray(self.normalizer.std, dtype=float).reshape(-1, 1, 1)
+        fsim = np.empty((M, P, size))
+        for d in range(P):
+            fsim[:, d, :] = m[:, d:d + 1] + dev[d].T
+        return fsim

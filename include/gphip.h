@@ -628,6 +628,36 @@ int gp_sparse_acq_rows(gp_t *gp, const double *Xs, int64_t M, int type, double p
 /* how many of those calls took the fused path / the table arithmetic since gp_create (route checks of the tests) */
 int gp_sparse_rows_stats(gp_t *gp, int64_t *fused, int64_t *fallback);
 
+/* -- the joint posterior of the sparse model (csrc/api_sparse_cov.hip).  All four entries refuse what gp_sparse_predict refuses
+ * (GP_ERR_STATE: no sparse fit, a mean function resident, a dead context), a null pointer and a count below 1 (GP_ERR_ARG); a
+ * refused call leaves the context as it was.  They work on buffers of the sparse model's own: the exact model's candidates,
+ * posterior and results, the sparse candidate table with its cached posterior and the cost snapshot are neither read nor written. */
+
+/* full_cov = True of Posterior._raw_predict over _predictive_variable = Z (posterior.py:229-232) at Xs [M, D], given by value:
+ * mean [M, P] (may be NULL) and cov [M, M] = K(Xs, Xs) - K(Xs, Z) woodbury_inv K(Z, Xs), + noise I with include_noise
+ * (gaussian.py:104-105).  Formed as K(Xs, Xs) - U U^T + T T^T with U = K(Xs, Z) Lm^-T and T = U LB^-T (woodbury_inv = Lm^-T
+ * (I - B^-1) Lm^-1): lower tiles, mirrored -- cov is bitwise symmetric, and the same call gives the same bits.  Unlike
+ * gp_sparse_predict's variance the diagonal is not clipped.  GP_ERR_ARG: M rounded up to the tile (128) beyond "mc_max". */
+int gp_sparse_predict_full_cov(gp_t *gp, const double *Xs, int64_t M, int include_noise, double *mean, double *cov);
+/* gp_posterior_samples over that covariance: dev [S, M], dev[s, :] = C z_s with C C^T = cov (+ jitter I) factored on the device
+ * under jitchol's ladder (mean of cov's diagonal x 1e-6 x 10^k, at most maxtries steps; *jitter_used is 0 when none was needed)
+ * and z_s = Z[s, :] the caller's standard normals, Z [S, M].  mean [M, P] (may be NULL) is bitwise the mean of
+ * gp_sparse_predict_full_cov.  GP_ERR_NOT_PD_DIAG: the first attempt failed and cov has a non-positive diagonal entry; a positive
+ * code: the ladder ended without a factor.  GP_ERR_ARG also for M beyond "mc_max" as above. */
+int gp_sparse_posterior_samples(gp_t *gp, const double *Xs, int64_t M, int include_noise, const double *Z, int S, int maxtries,
+                                double *mean, double *dev, double *jitter_used);
+/* A second point set X2 [R, D], 1 <= R <= "mc_max", made resident for gp_sparse_cov_between.  G = K(X2, Z) woodbury_inv is built
+ * by the first gp_sparse_cov_between after a fit or a new point set and kept: whatever drops the sparse fit drops G, the points
+ * stay as the candidate table does (another D drops them).  Needs data (GP_ERR_STATE), not a fit. */
+int gp_sparse_cov_set_points(gp_t *gp, const double *X2, int64_t R);
+/* cov [M1, R], cov[i, r] = k(x1_i, x2_r) - sum_j G[r, j] k(x1_i, z_j): the posterior covariance (no noise) between the locations
+ * X1 [M1, D], given by value, and the resident points.  Up to 8 locations are ONE launch per pass with no copy commands (the
+ * locations in the kernel arguments, M1 D <= 128 per pass, the result in a pinned block); more go through the same kernel body
+ * in blocks of eight.  Every entry has one writer and a fixed summation order: a location's row has the same bits whatever M1,
+ * its position and its company, its first R' entries the same bits as against the first R' points alone, and the same call the
+ * same bits.  GP_ERR_STATE also before gp_sparse_cov_set_points. */
+int gp_sparse_cov_between(gp_t *gp, const double *X1, int64_t M1, double *cov);
+
 /* ---- ensemble: S hyper-parameter members with resident posteriors, acquisitions integrated over them ----------------
  * GPModel_MCMC (GPyOpt/GPyOpt/models/gpmodel.py:180-355) with acquisitions/{EI,MPI,LCB}_mcmc.py.  An ensemble is S members
  * over the context's (X, Y), each with hyper-parameters of its own (an HMC sample, gpmodel.py:243-262); it is kept beside the
