@@ -37,7 +37,9 @@ from .feasibility import FeasibilityModel
 from . import acquisitions
 from .acquisitions import (AcquisitionEI, AcquisitionLCB, AcquisitionMPI, AcquisitionBase, AcquisitionLP,
                            LocalPenalization, estimate_L, AcquisitionEI_MCMC, AcquisitionMPI_MCMC, AcquisitionLCB_MCMC,
-                           AcquisitionEntropySearch)
+                           AcquisitionEntropySearch, AcquisitionMES)
+from . import max_value
+from .max_value import MinValueSampler
 from . import entropy_search
 from .entropy_search import McmcSampler, AffineInvariantEnsembleSampler
 from .bayesian_optimization import BayesianOptimization, Design_space, AcquisitionOptimizer
@@ -51,7 +53,7 @@ likelihoods = _types.SimpleNamespace(Gaussian=Gaussian)
 
 __all__ = ["kern", "mappings", "models", "methods", "likelihoods", "acquisitions", "GPRegression", "SparseGPRegression", "GPModel", "BOModel", "GPModel_MCMC", "priors", "HMC",
            "AcquisitionEI_MCMC", "AcquisitionMPI_MCMC", "AcquisitionLCB_MCMC",
-           "AcquisitionEntropySearch", "entropy_search", "McmcSampler", "AffineInvariantEnsembleSampler",
+           "AcquisitionMES", "max_value", "MinValueSampler", "AcquisitionEntropySearch", "entropy_search", "McmcSampler", "AffineInvariantEnsembleSampler",
            "InputWarpedGP", "InputWarpedGPModel", "input_warping", "WarpedGP", "WarpedGPModel", "warping_functions",
            "AcquisitionEI", "AcquisitionLCB", "AcquisitionMPI", "AcquisitionBase", "AcquisitionLP",
            "LocalPenalization", "estimate_L", "BayesianOptimization",

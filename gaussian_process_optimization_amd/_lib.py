@@ -21,6 +21,8 @@ GP_KERNEL_MATERN32, GP_KERNEL_EXPONENTIAL = 2, 3
 GP_ACQ_EI, GP_ACQ_LCB, GP_ACQ_MPI = 0, 1, 2
 GP_ACQ_PER_COST = 0x100      # or-ed into a scoring call's type: the scores are divided by the resident cost surface
 GP_ACQ_POF = 3               # the rule whose value is 1: valid only with GP_ACQ_TIMES_FEAS (the probability of feasibility alone)
+GP_ACQ_MES = 4               # max-value entropy search over the handle's resident samples of the minimum's value (gp_mes_set)
+GP_MES_MAX_K, GP_MES_MAX_G = 64, 64   # samples of the minimum's value; trial values per gp_mes_logsurv call
 GP_ACQ_TIMES_FEAS = 0x200    # or-ed into a table scoring call's type: the scores are multiplied by the cached probability of feasibility
 GP_FEAS_MAX = 8
 GP_ERR_ARG, GP_ERR_HIP, GP_ERR_STATE, GP_ERR_RCCL, GP_ERR_NOT_PD_DIAG = -1, -2, -3, -4, -5
@@ -213,6 +215,10 @@ SIGNATURES = [
     ("gp_mean_set", ctypes.c_int, [_vp, c_double_p, c_double_p]),
     ("gp_mean_info", ctypes.c_int, [_vp, c_int_p, c_int_p]),
     ("gp_mean_grad", ctypes.c_int, [_vp, c_double_p, c_double_p]),
+    ("gp_mes_set", ctypes.c_int, [_vp, c_double_p, ctypes.c_int]),
+    ("gp_mes_info", ctypes.c_int, [_vp, c_int_p]),
+    ("gp_mes_logsurv", ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_double, ctypes.c_double, c_double_p, ctypes.c_int, c_double_p]),
+    ("gp_mes_bracket", ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double, c_double_p, c_double_p]),
 ]
 
 _lib = None
@@ -368,6 +374,7 @@ class Handle(object):
         self.sparse_M = 0      # rows of the sparse model's candidate table (sparse_set_candidates); 0: the library refuses to score
         self.sparse_R = 0      # rows of the sparse model's second point set (sparse_cov_set_points); 0: sparse_cov_between is refused
         self.cost_key = None   # whose cost surface the handle holds: set by the caller of cost_set, dropped with the surface
+        self.mes_key = None    # whose samples of the minimum's value the handle holds: set by the caller of mes_set
         self.feas_key = None   # whose probability of feasibility the handle caches over its candidates: set by the caller of feas_table
 
     def close(self):
@@ -1228,6 +1235,38 @@ class Handle(object):
         if rc:
             check(self.lib, rc, "gp_cost_rows")
         return (logc, dlogc) if grad else logc
+
+    # -- max-value entropy search (include/gphip.h, gp_mes_*): the samples behind GP_ACQ_MES and the sampler's reductions ---------
+    def mes_set(self, ystar, key=None):
+        """Make ``ystar`` [K] the handle's samples of the minimum's value (un-normalised) -- a copy; ``None`` or an empty array
+        clears them.  ``key`` is remembered as ``mes_key`` (the routes' staleness check)."""
+        self.mes_key = None
+        if ystar is None or np.size(ystar) == 0:
+            check(self.lib, self.lib.gp_mes_set(self.h, None, 0), "gp_mes_set")
+            return
+        ystar = as_f64(np.ravel(ystar), 1)
+        check(self.lib, self.lib.gp_mes_set(self.h, dptr(ystar), ystar.size), "gp_mes_set")
+        self.mes_key = key
+
+    def mes_info(self):
+        K = ctypes.c_int(0)
+        check(self.lib, self.lib.gp_mes_info(self.h, ctypes.byref(K)), "gp_mes_info")
+        return K.value
+
+    def mes_logsurv(self, y, include_noise=False, y_mean=0.0, y_std=1.0):
+        """sum_i log Phi((m_i - y_g) / s_i) [G] over the resident candidates' table posterior at the trial values ``y`` [G]."""
+        y = as_f64(np.ravel(y), 1)
+        out = np.empty(y.size)
+        check(self.lib, self.lib.gp_mes_logsurv(self.h, int(bool(include_noise)), float(y_mean), float(y_std), dptr(y), y.size,
+                                                dptr(out)), "gp_mes_logsurv")
+        return out
+
+    def mes_bracket(self, nsig=8.0, include_noise=False, y_mean=0.0, y_std=1.0):
+        """(min_i (m_i - nsig s_i), min_i (m_i + nsig s_i)) over the resident candidates' table posterior."""
+        lo, hi = ctypes.c_double(), ctypes.c_double()
+        check(self.lib, self.lib.gp_mes_bracket(self.h, int(bool(include_noise)), float(y_mean), float(y_std), float(nsig),
+                                                ctypes.byref(lo), ctypes.byref(hi)), "gp_mes_bracket")
+        return lo.value, hi.value
 
     # -- the mean function m(x) = x^T A + b of the exact GP (include/gphip.h, gp_mean_*) -----------------------------------
     def mean_set(self, A=None, b=None):

@@ -95,9 +95,51 @@ class _ProbabilityOfImprovement(_Rule):
         return cdf, slope, slope * z
 
 
+class _MaxValueEntropy(_Rule):
+    """Max-value entropy search (Wang & Jegelka 2017, mirrored for a minimum) over K samples y* of the minimum's value, which
+    travel in the ``par`` slot of ``terms`` (the rule has no other parameter and reads no fmin):
+        g_k = (mu - y*_k) / sd,  h(g) = g lambda(g) / 2 - log Phi(g),  value = mean_k h(g_k),
+        h'(g) = -(lambda / 2) (1 + g^2 + g lambda),  d value / d mu = mean_k h'(g_k) / sd,  d value / d sd = -mean_k h'(g_k) g_k / sd,
+    lambda = phi / Phi formed in log space; at and below g = -20, where those forms cancel, h, lambda and the bracket of h' come
+    from the asymptotic series of Phi, as on the device (``mes_h``, csrc/acq_math.h)."""
+
+    @staticmethod
+    def _h(g):
+        """(h, h') [shape of g]."""
+        far = g <= -20.0
+        near = np.where(far, 0.0, g)
+        logcdf = log_ndtr(near)
+        with np.errstate(under='ignore'):
+            lam = np.exp(-0.5 * near * near - 0.5 * np.log(2 * np.pi) - logcdf)
+            h = 0.5 * near * lam - logcdf
+            hp = -(0.5 * lam) * (1.0 + near * near + near * lam)
+        if np.any(far):
+            gf = np.where(far, g, -20.0)
+            g2 = gf * gf
+            t = 1.0 / g2
+            term, R, S, W = np.ones_like(t), np.ones_like(t), np.zeros_like(t), np.zeros_like(t)
+            for i in range(1, 17):      # T_i = (-1)^i (2i-1)!! g^-2i: R = 1 + sum T_i, S = sum -2 i T_i, W = sum T_i g^2
+                term = term * (-(2 * i - 1) * t)
+                R = R + term
+                S = S + (-2 * i) * term
+                W = W + term * g2
+            h = np.where(far, W / (2.0 * R) + np.log(-gf) + 0.5 * np.log(2 * np.pi) - np.log(R), h)
+            hp = np.where(far, -(0.5 * (-gf / R)) * (S / R), hp)
+        return h, hp
+
+    def terms(self, ystar, fmin, mu, sd):
+        y = np.asarray(ystar, dtype=float).reshape(1, -1)
+        sd = np.maximum(np.asarray(sd, dtype=float).reshape(-1, 1), _STD_FLOOR)
+        g = (np.asarray(mu, dtype=float).reshape(-1, 1) - y) / sd
+        h, slope = self._h(g)
+        return (h.mean(axis=1, keepdims=True), slope.mean(axis=1, keepdims=True) / sd,
+                -(slope * g).mean(axis=1, keepdims=True) / sd)
+
+
 _RULES = {"EI": _ExpectedImprovement(_lib.GP_ACQ_EI, True),
           "LCB": _LowerConfidenceBound(_lib.GP_ACQ_LCB, False),
-          "MPI": _ProbabilityOfImprovement(_lib.GP_ACQ_MPI, True)}
+          "MPI": _ProbabilityOfImprovement(_lib.GP_ACQ_MPI, True),
+          "MES": _MaxValueEntropy(_lib.GP_ACQ_MES, False)}
 
 
 def _pick(values, sense):
@@ -169,6 +211,15 @@ def _sync_cost(acq, h):
     h.cost_set(gp.X, gp._h.alpha(), k._kernel_id, k.ARD, float(k.variance), k.lengthscale.values, shift, scale, key=key)
 
 
+def _sync_mes(acq, h):
+    """Before a scoring call on handle ``h`` of an acquisition that scores over samples of the minimum's value (AcquisitionMES):
+    the samples of the model's current fit, resident on ``h``.  Drawing them makes the sampler's table the resident candidates,
+    so this comes BEFORE the call's own table is staged."""
+    sync = getattr(acq, "_sync_mes", None)
+    if sync is not None:
+        sync(h)
+
+
 def _normaliser(gp):
     """(mean, std) the targets of ``gp`` were normalised with: the ``y_mean`` / ``y_std`` of every scoring call."""
     nz = gp.normalizer
@@ -218,6 +269,7 @@ class _Route(object):
         gp._ensure_fit()
         if acq._per_cost:
             _sync_cost(acq, gp._h)
+        _sync_mes(acq, gp._h)
         shift, scale = _normaliser(gp)
         if feas:      # any number of rows: gp_acq_rows_feas makes the groups of eight itself (the lockstep optimiser's call)
             return gp._h.acq_rows_feas(acq._feas_pack(), x, acq._acq_id, acq._par(), acq._fmin(), shift, scale, grad=grad)
@@ -233,6 +285,7 @@ class _ExactRoute(_Route):
         """Make ``x`` the resident candidate block (refitting first if data or hyper-parameters changed) and return what
         every scoring call takes: the handle, fmin and the normaliser's mean / std."""
         gp = acq.model.model
+        _sync_mes(acq, gp._h)      # (its sampler stages a table of its own: ahead of this call's)
         given = x
         x = np.atleast_2d(np.asarray(x, dtype=float))
         feas = getattr(acq, "feasibility", None) is not None
@@ -262,6 +315,8 @@ class _ExactRoute(_Route):
                                       "'evaluation_time'")
         if getattr(acq, "feasibility", None) is not None:
             raise NotImplementedError("replica groups score without black-box constraints: not available with feasibility=")
+        if getattr(acq, "_sync_mes", None) is not None:
+            raise NotImplementedError("replica groups hold no samples of the minimum's value: MES scores its table on one device")
         gp = acq.model.model
         grp = gp._device_group(devices)
         grp.set_candidates(np.atleast_2d(np.asarray(x, dtype=float)))
@@ -574,6 +629,82 @@ class AcquisitionMPI(AcquisitionBase):
 
     def _par(self):
         return self.jitter
+
+
+class AcquisitionMES(AcquisitionBase):
+    """Max-value entropy search (Wang & Jegelka, ICML 2017): the expected reduction of the entropy of the VALUE y* of the global
+    minimum, a closed form of the posterior mean and deviation at a location given ``num_samples`` samples of y* -- so, unlike
+    ``AcquisitionEntropySearch``, it has an analytic gradient and runs through every route EI has: values, gradients, arg-best,
+    top-k, the one-location calls, ``AcquisitionLP`` and the evaluation-time cost (it is a gain, >= 0, as EI is).  GPyOpt has no
+    MES: an addition.
+
+    The samples come from ``max_value.MinValueSampler`` over ``grid_size`` uniform draws of the space plus the model's X, drawn
+    with ``seed`` and clipped at the incumbent; they are redrawn whenever the model's fit has changed (new data or new
+    hyper-parameters), as the belief of ``AcquisitionEntropySearch`` is.  With the exact HIP ``GPModel`` (one output) the sampler's
+    sums and every score run on the device (``gp_mes_*``, ``GP_ACQ_MES``); a foreign, sparse or warped model is scored on the host
+    from ``model.predict[_withGradients]`` by the same rule.  Not available: a model that samples its hyper-parameters, black-box
+    constraints, replica groups."""
+    analytical_gradient_prediction = True
+    _rule = _RULES["MES"]
+
+    def __init__(self, model, space, optimizer=None, cost_withGradients=None, num_samples=10, grid_size=10000, seed=None):
+        if isinstance(model, GPModel_MCMC):
+            raise NotImplementedError("MES scores one posterior: not available with a model that samples its hyper-parameters")
+        from .max_value import MinValueSampler
+        super().__init__(model, space, optimizer, cost_withGradients=cost_withGradients)
+        self.sampler = MinValueSampler(model, self.space, num_samples, grid_size, seed)
+        self.ystar = None
+        self.draws = 0                  # how often the samples were drawn (the handles' staleness key; tests)
+        self._fit_signature = None
+
+    @staticmethod
+    def fromConfig(model, space, optimizer, cost_withGradients, config):
+        return AcquisitionMES(model, space, optimizer, cost_withGradients, num_samples=config.get('num_min_samples', 10),
+                              grid_size=config.get('mes_grid_size', 10000), seed=config.get('sampler_seed', None))
+
+    def _par(self):
+        return 0.0
+
+    def _set_feasibility(self, feasibility):
+        if feasibility is not None:
+            raise NotImplementedError("MES takes no black-box constraints: feasibility= weights EI and MPI")
+
+    def _device_ok(self):
+        """Our exact GPModel itself (a warped or sparse model keeps the host rule)."""
+        return type(self.model) is GPModel and super()._device_ok()
+
+    def _sparse_device_ok(self):
+        return False
+
+    def _signature(self):
+        """What the samples were drawn for: the GP object, its data and its parameters (AcquisitionEntropySearch._signature)."""
+        gp = getattr(self.model, "model", None)
+        return (id(gp), getattr(gp, "_data_epoch", None), np.asarray(getattr(gp, "param_array", ()), dtype=float).tobytes())
+
+    def _samples(self):
+        """The samples of the model's current fit, drawn when it has changed."""
+        sig = self._signature()
+        if self.ystar is None or self._fit_signature != sig:
+            self.ystar = np.ascontiguousarray(self.sampler.sample(), dtype=float)
+            self._fit_signature = self._signature()
+            self.draws += 1
+        return self.ystar
+
+    def _sync_mes(self, h):
+        self.model.model._ensure_fit()
+        ystar = self._samples()
+        key = (id(self), self.draws)
+        if h.mes_key != key:      # (the library keeps the samples across refits and new data: the key alone decides)
+            h.mes_set(ystar, key=key)
+
+    def _compute_acq(self, x):
+        mu, sd = self.model.predict(x)
+        return self._rule.value(self._samples(), 0.0, mu, sd)
+
+    def _compute_acq_withGradients(self, x):
+        ystar = self._samples()
+        mu, sd, dmu_dx, dsd_dx = self.model.predict_withGradients(x)
+        return self._rule.gradient(ystar, 0.0, mu, sd, dmu_dx, dsd_dx)
 
 
 # ---- acquisitions integrated over the hyper-parameter samples ----------------------------------------------------------

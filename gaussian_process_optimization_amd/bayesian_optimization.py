@@ -20,7 +20,7 @@ from scipy import optimize as _sopt
 
 from . import kern as _kern
 from .acquisitions import (AcquisitionEI, AcquisitionLCB, AcquisitionMPI, AcquisitionLP, LocalPenalization, AcquisitionEI_MCMC,
-                           AcquisitionMPI_MCMC, AcquisitionLCB_MCMC, AcquisitionEntropySearch)
+                           AcquisitionMPI_MCMC, AcquisitionLCB_MCMC, AcquisitionEntropySearch, AcquisitionMES)
 from .cost import CostModel
 from .feasibility import FeasibilityModel
 from .entropy_search import AffineInvariantEnsembleSampler
@@ -341,7 +341,13 @@ class BayesianOptimization(object):
     ``fx_opt`` are then the best FEASIBLE observation; while there is none they are the LEAST VIOLATING one: the observation
     with the smallest total violation ``sum_k max(c_k - bound_k, 0) / std_k`` (``std_k`` the standard deviation of column k over
     the observations), the lowest objective among equals.  The evaluators 'sequential', 'random' and 'thompson_sampling' work;
-    'local_penalization' raises ``InvalidConfigError`` (its optimiser needs penalised rows, which take no constraints)."""
+    'local_penalization' raises ``InvalidConfigError`` (its optimiser needs penalised rows, which take no constraints).
+
+    Max-value entropy search (an addition): ``acquisition_type='MES'`` with the keywords ``num_min_samples`` (10 samples of the
+    minimum's value), ``mes_grid_size`` (10000 uniform locations under the sampler, besides X) and ``sampler_seed``
+    (``AcquisitionMES``).  It has gradients, so every evaluator works with it, 'local_penalization' and ``parallel_anchors=True``
+    included, and so does ``cost_withGradients='evaluation_time'``; with ``constraint_function`` it raises
+    ``NotImplementedError``."""
 
     def __init__(self, f, domain=None, constraints=None, cost_withGradients=None, model_type='GP', X=None, Y=None,
                  initial_design_numdata=5, initial_design_type='random', acquisition_type='EI', normalize_Y=True,
@@ -421,6 +427,10 @@ class BayesianOptimization(object):
                 self.model, self.space, AffineInvariantEnsembleSampler(self.space, seed=kwargs.get('sampler_seed', None)),
                 self.acquisition_optimizer, cost_withGradients, num_samples=kwargs.get('num_samples', 100),
                 num_representer_points=kwargs.get('num_representer_points', 50), burn_in_steps=kwargs.get('burn_in_steps', 50))
+        elif acquisition_type == 'MES':
+            self.acquisition = AcquisitionMES(self.model, self.space, self.acquisition_optimizer, cost_withGradients,
+                                              num_samples=kwargs.get('num_min_samples', 10),
+                                              grid_size=kwargs.get('mes_grid_size', 10000), seed=kwargs.get('sampler_seed', None))
         elif acquisition_type == 'EI_MCMC':
             self.acquisition = AcquisitionEI_MCMC(self.model, self.space, self.acquisition_optimizer, cost_withGradients, jitter)
         elif acquisition_type == 'MPI_MCMC':
@@ -470,6 +480,9 @@ class BayesianOptimization(object):
             scored = self.acquisition.acq if isinstance(self.acquisition, AcquisitionLP) else self.acquisition
             if isinstance(scored, AcquisitionLCB):
                 raise ValueError("LCB takes no black-box constraints: use acquisition_type 'EI' or 'MPI' with constraint_function")
+            if isinstance(scored, AcquisitionMES):
+                raise NotImplementedError("MES takes no black-box constraints: use acquisition_type 'EI' or 'MPI' with "
+                                          "constraint_function")
             if not isinstance(scored, (AcquisitionEI, AcquisitionMPI)) or scored._rule is None or \
                     isinstance(scored, (AcquisitionEI_MCMC, AcquisitionMPI_MCMC)):
                 raise NotImplementedError("black-box constraints weight EI and MPI over the exact GPModel")

@@ -78,6 +78,64 @@ __device__ __forceinline__ double feas_grad(double lam, double z, double s, doub
     return lam * (-dm - z * ds) / s;
 }
 
+// ---- max-value entropy search (Wang & Jegelka, ICML 2017), mirrored for a minimum ------------------------------------------------
+// h(g) = g lambda(g) / 2 - log Phi(g) and h'(g) = -(lambda / 2) B(g), B = 1 + g^2 + g lambda, lambda = phi / Phi.
+// g > -20: log Phi by gp_log_ndtr, lambda = exp(-g^2 / 2 - log(2 pi) / 2 - log Phi) in log space as feas_terms forms it, h and B
+// from their terms.
+// g <= -20 -- where gp_log_ndtr switches to the asymptotic series as well -- those forms cancel: B -> 2 / g^2 loses g^4 / 2 ulp, h
+// ~ log|g| is the difference of two terms of size g^2 / 2, and so is lambda's exponent.  There everything comes from the series
+// itself: with t = 1 / g^2, T_i = (-1)^i (2i - 1)!! t^i, R = 1 + sum_i T_i  (Phi(g) = phi(g) / (-g) R),
+//     lambda = -g / R,   B = (sum_{i >= 1} -2 i T_i) / R = 2 t - 10 t^2 + 74 t^3 - ...,
+//     h = W / (2 R) + log(-g) + log(2 pi) / 2 - log R,   W = sum_{i >= 1} T_i g^2 = -1 + 3 t - 15 t^2 + ...
+// (g lambda / 2 = -g^2 / (2 R) and -log Phi = g^2 / 2 + log(-g) + log(2 pi) / 2 - log R: the two g^2 / 2 meet in (g^2 / 2)(R - 1) / R.)
+// No term cancels at any g <= -20.  Sixteen terms: the first one dropped is below 1e-24 of the sums at g = -20 and falls with |g|.
+__device__ __forceinline__ void mes_h(double g, double &h, double &hp) {
+    if (g > -20.0) {
+        const double logphi = gp_log_ndtr(g);
+        const double lam = exp(-0.5 * g * g - 0.91893853320467274178032973640562 - logphi);
+        h = 0.5 * g * lam - logphi;
+        hp = -(0.5 * lam) * (1.0 + g * g + g * lam);
+        return;
+    }
+    const double g2 = g * g, t = 1.0 / g2;
+    double term = 1.0, R = 1.0, S = 0.0, W = 0.0;
+    for (int i = 1; i <= 16; ++i) {
+        term *= -(double)(2 * i - 1) * t;
+        R += term;
+        S += (double)(-2 * i) * term;
+        W += term * g2;
+    }
+    const double lam = -g / R;
+    h = W / (2.0 * R) + log(-g) + 0.91893853320467274178032973640562 - log(R);
+    hp = -(0.5 * lam) * (S / R);
+}
+
+// MES at (mean, var) of the NORMALISED model over the K samples ystar [K] of the minimum's value (un-normalised, as fmin is):
+//   g_k = (m - ystar_k) / s,  f = (1 / K) sum_k h(g_k)   (k = 0 .. K - 1 in index order)
+//   c_m = d f / dm = ((1 / K) sum_k h'(g_k)) / s,  c_s = d f / ds = -((1 / K) sum_k h'(g_k) g_k) / s
+// m, s and ds_scale exactly as acq_terms forms them.  h and h' stay finite where Phi underflows (g << 0) and go to 0 without
+// leaving the finite range where phi does (g >> 0).
+__device__ __forceinline__ void mes_terms(const double *ystar, int K, double y_mean, double y_std, double mean, double var, double &f,
+                                          double &c_m, double &c_s, double &ds_scale) {
+    const double m = mean * y_std + y_mean;
+    double v = var * (y_std * y_std);
+    v = (v < 1e-10) ? 1e-10 : v;
+    const double s = sqrt(v);
+    ds_scale = (y_std * y_std) / (2.0 * s);
+    double sh = 0.0, sm = 0.0, ss = 0.0;
+    for (int k = 0; k < K; ++k) {
+        const double g = (m - ystar[k]) / s;
+        double h, hp;
+        mes_h(g, h, hp);
+        sh += h;
+        sm += hp;
+        ss += hp * g;
+    }
+    f = sh / (double)K;
+    c_m = (sm / (double)K) / s;
+    c_s = -((ss / (double)K) / s);
+}
+
 // AcquisitionLP._penalized_acquisition (LP.py:70-89) for one location: negacq = -acq(x) in, the penalised score out.
 // transform: 0 = none (log(acq + 1e-50)), 1 = softplus (LP.py:77-83)
 __device__ __forceinline__ double lp_value(double negacq, const double *x, int D, const double *Xb, int nb, const double *r0,

@@ -262,7 +262,7 @@ int acq_values(gp_ctx *g, const AcqSpec &a, const LpSpec *lp, double *out, doubl
 extern "C" int gp_acq_grad(gp_t *g, int type, double par, double fmin, double y_mean, double y_std, double *out, double *dout) {
     if (!g || !out || !dout) return fail(GP_ERR_ARG, "null argument");
     GP_SCORING(g);
-    return acq_values(g, AcqSpec{type, par, fmin, y_mean, y_std}, nullptr, out, dout);
+    return acq_values(g, exact_spec(g, AcqSpec{type, par, fmin, y_mean, y_std}), nullptr, out, dout);
 }
 
 extern "C" int gp_acq_lp_grad(gp_t *g, int type, double par, double fmin, double y_mean, double y_std, int transform,
@@ -270,7 +270,7 @@ extern "C" int gp_acq_lp_grad(gp_t *g, int type, double par, double fmin, double
     if (!g || !out || !dout) return fail(GP_ERR_ARG, "null argument");
     GP_SCORING(g);
     const LpSpec lp{transform, Xb, nb, r_x0, s_x0};
-    return acq_values(g, AcqSpec{type, par, fmin, y_mean, y_std}, &lp, out, dout);
+    return acq_values(g, exact_spec(g, AcqSpec{type, par, fmin, y_mean, y_std}), &lp, out, dout);
 }
 
 // ---- dL_dK = 0.5 (alpha alpha^T - P Ky^-1)  (exact_gaussian_inference.py:70) -------------------------------

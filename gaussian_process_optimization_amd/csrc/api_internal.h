@@ -345,6 +345,15 @@ struct MeanState {
     bool on() const { return has_A || has_b; }
 };
 
+// Max-value entropy search (api_mes.hip): the caller's K samples of the minimum's value, in a buffer of the context's own, and the
+// scratch of the sampler's two reductions.  The samples are the caller's numbers in the caller's units: no fit, data or candidate
+// call touches them.
+struct MesState {
+    int K = 0;                 // samples resident (0: none)
+    DevBuf<double> dY;         // [GP_MES_MAX_K]
+    DevBuf<double> dPart;      // the chunks' partial sums / minima, then the results (mes_part_elems)
+};
+
 struct gp_ctx {
     int device = 0;
     long lds_per_wg = 0;           // hipDeviceAttributeMaxSharedMemoryPerBlock of the device (gp_create)
@@ -506,6 +515,7 @@ struct gp_ctx {
     CostState cost;     // the cost surface of the flagged scoring calls (api_cost.hip)
     MeanState mean;     // the mean function (api_mean.hip)
     FeasState feas;     // the cached probability of feasibility of the flagged table entries (api_feas.hip)
+    MesState mes;       // the samples of the minimum's value behind GP_ACQ_MES (api_mes.hip)
     bool dead = false;  // gp_shutdown ran: the device's streams are gone, only gp_destroy is still valid
 };
 
@@ -768,12 +778,24 @@ int ensure_out(gp_ctx *g);
 // type: GP_ACQ_*, with GP_ACQ_PER_COST or-ed in when the scores are to be divided by the resident cost surface
 // feas_ok: the entry understands GP_ACQ_TIMES_FEAS / GP_ACQ_POF (the exact table's value entries); everywhere else the bits stay
 // in what acq_base returns and the call ends as an unknown acquisition
-struct AcqSpec { int type; double par, fmin, y_mean, y_std; bool feas_ok = false; };
+// mes_ok: the entry understands GP_ACQ_MES (the exact model's scoring entries, through exact_spec); everywhere else the rule is an
+// unknown acquisition.  mes_y / mes_K: the context's resident samples on the device (exact_spec fills them in)
+struct AcqSpec { int type; double par, fmin, y_mean, y_std; bool feas_ok = false; bool mes_ok = false; const double *mes_y = nullptr; int mes_K = 0; };
 struct LpSpec { int transform; const double *Xb; int nb; const double *r0, *s0; };
 static inline int acq_base(int type) { return type & ~GP_ACQ_PER_COST; }            // the acquisition itself
 static inline bool acq_per_cost(int type) { return (type & GP_ACQ_PER_COST) != 0; }
 static inline bool acq_times_feas(const AcqSpec &a) { return a.feas_ok && (a.type & GP_ACQ_TIMES_FEAS) != 0; }
 static inline int acq_rule(const AcqSpec &a) { return acq_base(a.feas_ok ? a.type & ~GP_ACQ_TIMES_FEAS : a.type); }   // the rule a taught entry scores
+// what an exact-model scoring entry hands on: a with GP_ACQ_MES understood and the resident samples attached (g may be null: the
+// entry's own null check follows)
+static inline AcqSpec exact_spec(const gp_ctx *g, AcqSpec a) {
+    a.mes_ok = true;
+    if (g) {
+        a.mes_y = g->mes.dY.p;
+        a.mes_K = g->mes.K;
+    }
+    return a;
+}
 // a single-output model, a known acquisition; with the flag: EI or MPI, a resident surface, no penaliser (lp null)
 int check_acq(const gp_ctx *g, const AcqSpec &a, const LpSpec *lp = nullptr);
 int check_per_cost(const gp_ctx *g, int type, bool lp);   // the flag's own conditions (no-op without it)

@@ -134,7 +134,10 @@ int check_acq(const gp_ctx *g, const AcqSpec &a, const LpSpec *lp) {
     if (g->P != 1) return fail(GP_ERR_ARG, "acquisitions need P == 1");
     const int base = acq_rule(a);
     const bool feas = acq_times_feas(a);
-    if (base == GP_ACQ_POF && a.feas_ok) {
+    if (base == GP_ACQ_MES && a.mes_ok) {
+        if (feas) return fail(GP_ERR_ARG, "GP_ACQ_TIMES_FEAS: MES takes no probability of feasibility");
+        if (a.mes_K < 1) return fail(GP_ERR_STATE, "GP_ACQ_MES without samples of the minimum's value (gp_mes_set)");
+    } else if (base == GP_ACQ_POF && a.feas_ok) {
         if (!feas) return fail(GP_ERR_ARG, "GP_ACQ_POF is valid only together with GP_ACQ_TIMES_FEAS");
     } else if (base < GP_ACQ_EI || base > GP_ACQ_MPI) {
         return fail(GP_ERR_ARG, "unknown acquisition %d", a.type);
@@ -195,7 +198,10 @@ int argbest_read(gp_ctx *g, const double *v, long n, int sense, int64_t *idx, do
 // posterior: each model's preamble and its route to one come first.  Not drained.
 int score_rows(gp_ctx *g, const AcqSpec &a, const LpSpec *lp, bool grad, const ScoreRows &r) {
     const int rule = acq_rule(a);
-    if (grad)
+    if (rule == GP_ACQ_MES)   // (par and fmin are not read)
+        launch_mes_acq(g->s, a.mes_y, a.mes_K, a.y_mean, a.y_std, r.mean, r.var, grad ? r.dm : nullptr, grad ? r.dv : nullptr, r.M, g->D,
+                       r.acq, grad ? r.dacq : nullptr);
+    else if (grad)
         launch_acq_grad(g->s, rule, a.par, a.fmin, a.y_mean, a.y_std, r.mean, r.var, r.dm, r.dv, r.M, g->D, r.acq, r.dacq);
     else if (rule != GP_ACQ_POF)
         launch_acq(g->s, rule, a.par, a.fmin, a.y_mean, a.y_std, r.mean, r.var, r.M, r.acq);
@@ -301,7 +307,7 @@ int run_acq(gp_ctx *g, const AcqSpec &a, const LpSpec *lp, bool grad) {
 extern "C" int gp_acq(gp_t *g, int type, double par, double fmin, double y_mean, double y_std, double *out) {
     if (!g || !out) return fail(GP_ERR_ARG, "null argument");
     GP_SCORING(g);
-    return acq_values(g, AcqSpec{type, par, fmin, y_mean, y_std, true}, nullptr, out, nullptr);
+    return acq_values(g, exact_spec(g, AcqSpec{type, par, fmin, y_mean, y_std, true}), nullptr, out, nullptr);
 }
 
 // The winner among the resident candidates of the acquisition -- penalised when lp is given --, the rows of exclude [nex] out of
@@ -318,7 +324,7 @@ int acq_argbest(gp_ctx *g, const AcqSpec &a, const LpSpec *lp, int sense, const 
 
 extern "C" int gp_acq_argbest(gp_t *g, int type, double par, double fmin, double y_mean, double y_std, int sense, int64_t *idx,
                    double *val) {
-    return acq_argbest(g, AcqSpec{type, par, fmin, y_mean, y_std, true}, nullptr, sense, nullptr, 0, idx, val);
+    return acq_argbest(g, exact_spec(g, AcqSpec{type, par, fmin, y_mean, y_std, true}), nullptr, sense, nullptr, 0, idx, val);
 }
 
 // ---- local penalisation (batch acquisition of run.py:1238-1257; GPyOpt/GPyOpt/acquisitions/LP.py) -----------
@@ -341,14 +347,14 @@ extern "C" int gp_acq_lp(gp_t *g, int type, double par, double fmin, double y_me
     if (!g || !out) return fail(GP_ERR_ARG, "null argument");
     GP_SCORING(g);
     const LpSpec lp{transform, Xb, nb, r_x0, s_x0};
-    return acq_values(g, AcqSpec{type, par, fmin, y_mean, y_std, true}, &lp, out, nullptr);
+    return acq_values(g, exact_spec(g, AcqSpec{type, par, fmin, y_mean, y_std, true}), &lp, out, nullptr);
 }
 
 extern "C" int gp_acq_lp_argbest(gp_t *g, int type, double par, double fmin, double y_mean, double y_std, int transform,
                       const double *Xb, int nb, const double *r_x0, const double *s_x0, int sense,
                       const int64_t *exclude, int nex, int64_t *idx, double *val) {
     const LpSpec lp{transform, Xb, nb, r_x0, s_x0};
-    return acq_argbest(g, AcqSpec{type, par, fmin, y_mean, y_std, true}, &lp, sense, exclude, nex, idx, val);
+    return acq_argbest(g, exact_spec(g, AcqSpec{type, par, fmin, y_mean, y_std, true}), &lp, sense, exclude, nex, idx, val);
 }
 
 // full_cov = True branch of PosteriorExact._raw_predict (posterior.py:280-284)
@@ -385,7 +391,7 @@ int acq_topk(gp_ctx *g, const AcqSpec &a, int sense, int k, int64_t *idx, double
 
 extern "C" int gp_acq_topk(gp_t *g, int type, double par, double fmin, double y_mean, double y_std, int sense, int k,
                 int64_t *idx, double *val) {
-    return acq_topk(g, AcqSpec{type, par, fmin, y_mean, y_std, true}, sense, k, idx, val);
+    return acq_topk(g, exact_spec(g, AcqSpec{type, par, fmin, y_mean, y_std, true}), sense, k, idx, val);
 }
 
 // ---- posterior samples of the latent function (GP.posterior_samples_f, gp.py:581-609) ------------------------

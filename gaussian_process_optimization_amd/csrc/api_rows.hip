@@ -73,8 +73,8 @@ int rows_lp_batch(gp_ctx *g, const LpSpec &lp, LpBatch *b) {
 }
 
 RowsAcq rows_acq(const AcqSpec &a, const LpSpec *lp, const LpBatch &b) {   // (RowsAcq: on, the base acquisition, lp, the penaliser)
-    if (!lp) return RowsAcq{1, acq_base(a.type), a.par, a.fmin, a.y_mean, a.y_std, 0, 0, 0, nullptr, nullptr, nullptr};
-    return RowsAcq{1, acq_base(a.type), a.par, a.fmin, a.y_mean, a.y_std, 1, lp->transform, lp->nb, b.X, b.r, b.s};
+    if (!lp) return RowsAcq{1, acq_base(a.type), a.par, a.fmin, a.y_mean, a.y_std, 0, 0, 0, nullptr, nullptr, nullptr, a.mes_y, a.mes_K};
+    return RowsAcq{1, acq_base(a.type), a.par, a.fmin, a.y_mean, a.y_std, 1, lp->transform, lp->nb, b.X, b.r, b.s, a.mes_y, a.mes_K};
 }
 
 // The exact model's passes through rows_passes (api_internal.h): rows_pass_width locations per pass.  launch(rx, w, r) puts a pass
@@ -187,7 +187,7 @@ extern "C" int gp_acq_rows(gp_t *g, const double *Xs, int64_t M, int type, doubl
     if (!g || !Xs || !out) return fail(GP_ERR_ARG, "null argument");
     GP_FITTED(g);
     if (M < 1) return fail(GP_ERR_ARG, "M < 1");
-    const AcqSpec a{type, par, fmin, y_mean, y_std};
+    const AcqSpec a = exact_spec(g, AcqSpec{type, par, fmin, y_mean, y_std});
     const LpSpec batch{transform, Xb, nb, r_x0, s_x0}, *pen = lp ? &batch : nullptr;
     int rc;
     if ((rc = check_acq(g, a, pen))) return rc;

@@ -239,6 +239,26 @@ void launch_acq(hipStream_t s, int type, double par, double fmin, double y_mean,
 void launch_argbest(hipStream_t s, const double *v, long n, int sense, double *best_val, long long *best_idx,
                     double *scratch_val, long long *scratch_idx);
 
+// ---- mes.hip: max-value entropy search -- the rule over a table, and the sums the sampler of the minimum's value needs ---------
+// the negated MES scores of M rows from their posterior (and, with dout, the x-gradients [M, D]): mes_terms of acq_math.h
+void launch_mes_acq(hipStream_t s, const double *ystar, int K, double y_mean, double y_std, const double *mean, const double *var,
+                    const double *dmdx, const double *dvdx, long M, int D, double *out, double *dout);
+#define MES_CHUNK 256        // rows per chunk of the two-level sums (one workgroup, one row per thread)
+#define MES_MAX_G 64         // trial values per launch (GP_MES_MAX_G)
+struct MesY {
+    int G;
+    double y[MES_MAX_G];      // the trial values, by value
+};
+inline long mes_chunks(long M) { return (M + MES_CHUNK - 1) / MES_CHUNK; }
+inline size_t mes_part_elems(long M) { return (size_t)(mes_chunks(M) + 1) * MES_MAX_G; }   // the chunks' sums, then the results
+// res[g] = sum_{i < M} log Phi((m_i - y_g) / s_i): chunks of MES_CHUNK rows in row order, a fixed tree inside the chunk, the
+// chunks in order; part: mes_part_elems(M) doubles, the results in its last MES_MAX_G
+void launch_mes_logsurv(hipStream_t s, const double *mean, const double *var, long M, double y_mean, double y_std, const MesY &y,
+                        double *part);
+// res[0] = min_i (m_i - nsig s_i), res[1] = min_i (m_i + nsig s_i); part as above
+void launch_mes_bracket(hipStream_t s, const double *mean, const double *var, long M, double y_mean, double y_std, double nsig,
+                        double *part);
+
 // ---- es.hip: entropy search -- the EP sweeps of p_min (one workgroup per chain) and the scoring of candidate rows -----------
 void launch_es_pmin(hipStream_t s, const double *mu, const double *cov, int R, int max_sweeps, double tol, double *P, double *MP,
                     double *logS, int *status, int *sweeps);
@@ -269,6 +289,8 @@ struct RowsAcq {
     double par, fmin, y_mean, y_std;
     int lp, transform, nb;    // local penalisation (LP.py): on / log transform / batch size
     const double *Xb, *r0, *s0;
+    const double *mes_y;      // GP_ACQ_MES: the K samples of the minimum's value on the device (the MES instances of the finish read them)
+    int mes_K;
 };
 struct RowsMean {             // the affine mean function of a P = 1 model (mean.hip): A [D] and b [1] on the device; on = 0: none
     int on;

@@ -42,14 +42,14 @@ __global__ __launch_bounds__(256) void rows_backward_kernel(const double *Li, lo
                                                             double *bpart, double *vpart) {
     rows_backward_body<MV, RB, NT>(blockIdx.x, Li, ld, wpart, Npad, M, bpart, vpart);
 }
-template <int MV, bool MEAN>
+template <int MV, bool MEAN, bool MES>
 __global__ __launch_bounds__(256) void rows_finish_kernel(RowsX rx, KernParams kp, const double *X, long N, const double *alpha,
                                                           const double *wpart, const double *bpart, const double *meanpart,
                                                           const double *vpart, long Npad, int nt, int rbh, int want_grad,
                                                           double kss, double noise_add, RowsAcq aq, double *gpart,
                                                           unsigned int *counter, unsigned int counter_base, double *out,
                                                           double ticket, const double *mA, const double *mb) {
-    if (!rows_finish_body<MV, MEAN>(blockIdx.x, gridDim.x, rx, kp, X, N, alpha, wpart, bpart, meanpart, vpart, Npad, nt, rbh, want_grad,
+    if (!rows_finish_body<MV, MEAN, MES>(blockIdx.x, gridDim.x, rx, kp, X, N, alpha, wpart, bpart, meanpart, vpart, Npad, nt, rbh, want_grad,
                                     kss, noise_add, aq, gpart, counter, counter_base, out, mA, mb))
         return;
     if (threadIdx.x == 0) out[ROWS_OUT_DOUBLES] = ticket;   // this pass is complete (the host checks the ticket behind the results)
@@ -288,13 +288,16 @@ static void launch_rows_t(hipStream_t s, const double *Li, long Npad, const Rows
     if (forward_only) return;
     if (want_grad)
         GP_LAUNCH((rows_backward_kernel<MV, RB, NT>), dim3(tiles), dim3(256), 0, s, Li, Npad, w.wpart, Npad, rx.M, w.bpart, w.vpart);
-    if (mf.on)
-        GP_LAUNCH((rows_finish_kernel<MV, true>), dim3(fin), dim3(256), 0, s, rx, kp, X, N, alpha, w.wpart, w.bpart, w.meanpart, w.vpart,
-                  Npad, nt, RB, want_grad, kss, noise_add, aq, w.gpart, r.counter, r.base, r.out, r.ticket, mf.A, mf.b);
-    else
-        GP_LAUNCH((rows_finish_kernel<MV, false>), dim3(fin), dim3(256), 0, s, rx, kp, X, N, alpha, w.wpart, w.bpart, w.meanpart, w.vpart,
-                  Npad, nt, RB, want_grad, kss, noise_add, aq, w.gpart, r.counter, r.base, r.out, r.ticket, (const double *)nullptr,
-                  (const double *)nullptr);
+#define RW_FIN(MEAN, MES, A, B)                                                                                                      \
+    GP_LAUNCH((rows_finish_kernel<MV, MEAN, MES>), dim3(fin), dim3(256), 0, s, rx, kp, X, N, alpha, w.wpart, w.bpart, w.meanpart, w.vpart, \
+              Npad, nt, RB, want_grad, kss, noise_add, aq, w.gpart, r.counter, r.base, r.out, r.ticket, (const double *)(A), (const double *)(B))
+    const bool mes = aq.on && aq.type == GP_ACQ_MES;   // the rule's own instances (rows_body.h)
+    if (mf.on) {
+        if (mes) RW_FIN(true, true, mf.A, mf.b); else RW_FIN(true, false, mf.A, mf.b);
+    } else {
+        if (mes) RW_FIN(false, true, nullptr, nullptr); else RW_FIN(false, false, nullptr, nullptr);
+    }
+#undef RW_FIN
 }
 
 static void launch_rows_any(hipStream_t s, const double *Li, long Npad, const RowsX &rx, const KernParams &kp, const double *X, long N,

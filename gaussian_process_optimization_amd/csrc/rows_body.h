@@ -237,7 +237,10 @@ __device__ __forceinline__ void rows_backward_body(unsigned bid, const double *L
 // MEAN: the mean-bearing instances -- the affine mean function m(x) = b + sum_d x_d A_d (mean.hip: from b, the products in dimension
 // order by fma; the location as it arrived by value) joins the mean, and A the mean's gradient, where the results are formed:
 // upstream of the acquisition and the penaliser.  The instances without it are the code they were.
-template <int MV, bool MEAN = false>
+// MES: the instances that score GP_ACQ_MES -- mes_terms over the aq.mes_K resident samples, serially in the location's lane, in
+// index order -- in acq_terms' place; the penaliser and everything before it are shared.  Instances of their own, so that the EI /
+// LCB / MPI instances carry no branch and no code of the rule.
+template <int MV, bool MEAN = false, bool MES = false>
 __device__ __forceinline__ bool rows_finish_body(unsigned bid, unsigned nblk, const RowsX &rx, const KernParams &kp, const double *X, long N, const double *alpha,
                                                           const double *wpart, const double *bpart, const double *meanpart,
                                                           const double *vpart, long Npad, int nt, int rbh, int want_grad,
@@ -351,7 +354,10 @@ __device__ __forceinline__ bool rows_finish_body(unsigned bid, unsigned nblk, co
             }
         if (aq.on) {
             double f, c_m, c_s, ds_scale;
-            acq_terms(aq.type, aq.par, aq.fmin, aq.y_mean, aq.y_std, mean, var, f, c_m, c_s, ds_scale);
+            if constexpr (MES)
+                mes_terms(aq.mes_y, aq.mes_K, aq.y_mean, aq.y_std, mean, var, f, c_m, c_s, ds_scale);
+            else
+                acq_terms(aq.type, aq.par, aq.fmin, aq.y_mean, aq.y_std, mean, var, f, c_m, c_s, ds_scale);
             double neg = -f;
             if (want_grad)
                 for (int d = 0; d < D; ++d) da[d] = -(c_m * (dm[d] * aq.y_std) + c_s * (dv[d] * ds_scale));

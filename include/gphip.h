@@ -52,6 +52,11 @@ typedef struct gp_ctx gp_t;
 #define GP_ACQ_POF 3
 #define GP_ACQ_TIMES_FEAS 0x200
 #define GP_FEAS_MAX 8 /* constraints per call */
+/* max-value entropy search (the gp_mes_* entries at the end of this header): the rule over the resident samples of the minimum's
+ * value; `par` and `fmin` of a scoring call are ignored */
+#define GP_ACQ_MES 4
+#define GP_MES_MAX_K 64 /* samples of the minimum's value */
+#define GP_MES_MAX_G 64 /* trial values per gp_mes_logsurv call */
 
 /* error codes (< 0) */
 #define GP_ERR_ARG (-1)
@@ -950,6 +955,50 @@ int gp_acq_rows_feas(gp_t *gp, gp_t *const *cons, int K, const double *bound, co
                      const double *Xs, int64_t M, int type, double par, double fmin, double y_mean, double y_std, double *out,
                      double *dout);
 int gp_fmin_rows(gp_t *gp, const int64_t *rows, int64_t n, double *fmin);
+
+/* ---- max-value entropy search (Wang & Jegelka, ICML 2017), mirrored for a minimum ----------------------------------------------
+ * MES scores a location by the information its evaluation carries about the VALUE y* of the global minimum.  Given K samples
+ * y*_0 .. y*_{K-1} of it (un-normalised, as fmin is) the score is a closed form of the posterior at the location: with m = mean
+ * y_std + y_mean and s = sqrt(max(var y_std^2, 1e-10)) as every rule here forms them,
+ *     g_k = (m - y*_k) / s,   h(g) = g lambda(g) / 2 - log Phi(g),   alpha = (1 / K) sum_k h(g_k),
+ *     h'(g) = -(lambda / 2) (1 + g^2 + g lambda),   d alpha / dm = (1 / K) sum_k h'(g_k) / s,
+ *     d alpha / ds = -(1 / K) sum_k h'(g_k) g_k / s,
+ * lambda = phi / Phi formed in log space.  At and below g = -20 those forms cancel (h ~ log|g| between two terms of size g^2 / 2,
+ * lambda's exponent likewise, the bracket of h' -> 2 / g^2), and h, lambda and the bracket come from the asymptotic series of Phi
+ * instead: h and h' are good to a few 1e-15 relative at every g <= -20, finite where Phi underflows.  The three sums run over k = 0 .. K-1 in index order on every route, then are divided by K.  The
+ * entries return -alpha and -d alpha / dx, the x-gradient assembled as for EI, LCB and MPI.
+ *
+ * gp_mes_set copies K samples into a buffer of the context's own (no caller pointer is kept); K = 0 clears (ystar may then be
+ * NULL).  GP_ERR_ARG: K outside 0 .. GP_MES_MAX_K, a null pointer with K > 0, a sample that is not finite.  It touches neither the
+ * fit nor any posterior cache, and the samples survive gp_fit, gp_set_params, gp_set_data and gp_set_candidates: they are the
+ * caller's numbers in the caller's units, and keeping them current is the caller's business.
+ * gp_mes_info: *K = samples resident, 0 when there are none.
+ *
+ * GP_ACQ_MES as the `type` of gp_acq, gp_acq_grad, gp_acq_argbest, gp_acq_topk, gp_acq_lp, gp_acq_lp_grad, gp_acq_lp_argbest and
+ * gp_acq_rows (fused narrow and wide passes -- instances of the finishing kernel of their own --, the batched fallback, with or
+ * without the penaliser) scores the rule over the resident samples; `par` and `fmin` are ignored.  GP_ACQ_PER_COST is allowed with
+ * it (MES >= 0 is a gain, as EI is).  GP_ERR_STATE: no samples resident.  GP_ERR_ARG: GP_ACQ_TIMES_FEAS with it.  Every other
+ * entry -- gp_acq_rows_feas, the sparse, ensemble, entropy-search, group and comm entries -- refuses it as an unknown acquisition.
+ * Without a MES call every kernel is launched as before and returns the same bits.
+ *
+ * Sampling y* (the Gumbel approximation of the paper): over the M resident candidates with independent marginals
+ *     log S(y) = log Pr[y* > y] ~ sum_i log Phi((m_i - y) / s_i).
+ * gp_mes_logsurv: out[g] = that sum at the G trial values y [G], 1 <= G <= GP_MES_MAX_G, over the table posterior with
+ * (include_noise = 1) or without the likelihood noise -- the sampler wants the latent one, y* being the minimum of f; it runs the
+ * table posterior first where the cache does not hold it with that noise, and a scoring call afterwards re-runs its own (the cache
+ * is keyed by the noise).  One pass over the table, each row's (m, s) loaded once for all G values.  The order of the sum is fixed
+ * by ONE constant: chunks of 256 rows in row order, inside a chunk the four waves' fixed trees added in wave order, the chunks in
+ * order; no atomics.  out[g] depends on y[g] and the table alone -- the same bits whatever G is and wherever the value stands --
+ * and repeated calls are bitwise equal.
+ * gp_mes_bracket: *lo = min_i (m_i - nsig s_i), *hi = min_i (m_i + nsig s_i), reduced on the device, every operation rounded on
+ * its own (NumPy's bits on the same posterior).  With nsig = 8, S rounds to 1 at *lo and is below 1e-15 at *hi: a bracket for
+ * every quantile.
+ * Both need a fit and resident candidates (GP_ERR_STATE) and P = 1; GP_ERR_ARG: a null pointer, G out of range, a trial value,
+ * y_mean or nsig that is not finite, nsig < 0, a y_std that is not positive and finite. */
+int gp_mes_set(gp_t *gp, const double *ystar, int K);
+int gp_mes_info(gp_t *gp, int *K);
+int gp_mes_logsurv(gp_t *gp, int include_noise, double y_mean, double y_std, const double *y, int G, double *out);
+int gp_mes_bracket(gp_t *gp, int include_noise, double y_mean, double y_std, double nsig, double *lo, double *hi);
 
 #ifdef __cplusplus
 }
