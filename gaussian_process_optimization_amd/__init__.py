@@ -37,7 +37,9 @@ from .feasibility import FeasibilityModel
 from . import acquisitions
 from .acquisitions import (AcquisitionEI, AcquisitionLCB, AcquisitionMPI, AcquisitionBase, AcquisitionLP,
                            LocalPenalization, estimate_L, AcquisitionEI_MCMC, AcquisitionMPI_MCMC, AcquisitionLCB_MCMC,
-                           AcquisitionEntropySearch, AcquisitionMES)
+                           AcquisitionEntropySearch, AcquisitionMES, AcquisitionTS)
+from . import posterior_paths
+from .posterior_paths import PosteriorPaths
 from . import max_value
 from .max_value import MinValueSampler
 from . import entropy_search
@@ -53,7 +55,7 @@ likelihoods = _types.SimpleNamespace(Gaussian=Gaussian)
 
 __all__ = ["kern", "mappings", "models", "methods", "likelihoods", "acquisitions", "GPRegression", "SparseGPRegression", "GPModel", "BOModel", "GPModel_MCMC", "priors", "HMC",
            "AcquisitionEI_MCMC", "AcquisitionMPI_MCMC", "AcquisitionLCB_MCMC",
-           "AcquisitionMES", "max_value", "MinValueSampler", "AcquisitionEntropySearch", "entropy_search", "McmcSampler", "AffineInvariantEnsembleSampler",
+           "AcquisitionTS", "posterior_paths", "PosteriorPaths", "AcquisitionMES", "max_value", "MinValueSampler", "AcquisitionEntropySearch", "entropy_search", "McmcSampler", "AffineInvariantEnsembleSampler",
            "InputWarpedGP", "InputWarpedGPModel", "input_warping", "WarpedGP", "WarpedGPModel", "warping_functions",
            "AcquisitionEI", "AcquisitionLCB", "AcquisitionMPI", "AcquisitionBase", "AcquisitionLP",
            "LocalPenalization", "estimate_L", "BayesianOptimization",

@@ -22,6 +22,7 @@ GP_ACQ_EI, GP_ACQ_LCB, GP_ACQ_MPI = 0, 1, 2
 GP_ACQ_PER_COST = 0x100      # or-ed into a scoring call's type: the scores are divided by the resident cost surface
 GP_ACQ_POF = 3               # the rule whose value is 1: valid only with GP_ACQ_TIMES_FEAS (the probability of feasibility alone)
 GP_ACQ_MES = 4               # max-value entropy search over the handle's resident samples of the minimum's value (gp_mes_set)
+GP_PATHS_MAX_S, GP_PATHS_MAX_F, GP_PATHS_MAX_ROWS = 64, 4096, 8   # posterior paths: paths, features, locations per rows call
 GP_MES_MAX_K, GP_MES_MAX_G = 64, 64   # samples of the minimum's value; trial values per gp_mes_logsurv call
 GP_ACQ_TIMES_FEAS = 0x200    # or-ed into a table scoring call's type: the scores are multiplied by the cached probability of feasibility
 GP_FEAS_MAX = 8
@@ -219,6 +220,11 @@ SIGNATURES = [
     ("gp_mes_info", ctypes.c_int, [_vp, c_int_p]),
     ("gp_mes_logsurv", ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_double, ctypes.c_double, c_double_p, ctypes.c_int, c_double_p]),
     ("gp_mes_bracket", ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double, c_double_p, c_double_p]),
+    ("gp_paths_set", ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, c_double_p, c_double_p, c_double_p, c_double_p]),
+    ("gp_paths_info", ctypes.c_int, [_vp, c_int_p, c_int_p]),
+    ("gp_paths_table", ctypes.c_int, [_vp, ctypes.c_double, ctypes.c_double, c_double_p]),
+    ("gp_paths_argbest", ctypes.c_int, [_vp, ctypes.c_double, ctypes.c_double, ctypes.c_int, c_int64_p, c_double_p]),
+    ("gp_paths_rows", ctypes.c_int, [_vp, _vp, ctypes.c_int, _vp, ctypes.c_double, ctypes.c_double, _vp, _vp]),
 ]
 
 _lib = None
@@ -376,6 +382,7 @@ class Handle(object):
         self.cost_key = None   # whose cost surface the handle holds: set by the caller of cost_set, dropped with the surface
         self.mes_key = None    # whose samples of the minimum's value the handle holds: set by the caller of mes_set
         self.feas_key = None   # whose probability of feasibility the handle caches over its candidates: set by the caller of feas_table
+        self.paths_key = None  # whose posterior paths the handle holds: set by the caller of paths_set
 
     def close(self):
         if getattr(self, "h", None):
@@ -1267,6 +1274,63 @@ class Handle(object):
         check(self.lib, self.lib.gp_mes_bracket(self.h, int(bool(include_noise)), float(y_mean), float(y_std), float(nsig),
                                                 ctypes.byref(lo), ctypes.byref(hi)), "gp_mes_bracket")
         return lo.value, hi.value
+
+    # -- posterior paths (include/gphip.h, gp_paths_*): function samples by pathwise conditioning on the resident factor ----------
+    def paths_set(self, omega_unit, phase, w, z_eps, key=None):
+        """Make S = ``w.shape[0]`` paths of F = ``w.shape[1]`` features resident from draws that do not depend on the
+        hyper-parameters: ``omega_unit`` [F, D], ``phase`` [F], ``w`` [S, F], ``z_eps`` [S, N].  ``w`` None clears.  ``key`` is
+        remembered as ``paths_key`` (the routes' staleness check); the library itself drops the paths with the factor."""
+        self.paths_key = None
+        if w is None or np.size(w) == 0:
+            check(self.lib, self.lib.gp_paths_set(self.h, 0, 0, None, None, None, None), "gp_paths_set")
+            return
+        omega_unit, phase, w, z_eps = as_f64(omega_unit, 2), as_f64(np.ravel(phase), 1), as_f64(w, 2), as_f64(z_eps, 2)
+        S, F = w.shape
+        if omega_unit.shape != (F, self.D) or phase.size != F or z_eps.shape != (S, self.N):
+            raise ValueError("paths_set: omega_unit [F, D], phase [F], w [S, F], z_eps [S, N] with F = %d, S = %d, D = %d, N = %d; got "
+                             "%s, %s, %s, %s" % (F, S, self.D, self.N, omega_unit.shape, phase.shape, w.shape, z_eps.shape))
+        check(self.lib, self.lib.gp_paths_set(self.h, S, F, dptr(omega_unit), dptr(phase), dptr(w), dptr(z_eps)), "gp_paths_set")
+        self.paths_key = key
+
+    def paths_info(self):
+        """(S, F) of the resident paths, (0, 0) when none belong to the current fit."""
+        S, F = ctypes.c_int(0), ctypes.c_int(0)
+        check(self.lib, self.lib.gp_paths_info(self.h, ctypes.byref(S), ctypes.byref(F)), "gp_paths_info")
+        return S.value, F.value
+
+    def paths_table(self, y_mean=0.0, y_std=1.0):
+        """Every resident path over the resident candidates: [S, M], de-normalised."""
+        S = self.paths_info()[0]
+        out = np.empty((max(S, 1), self.M))
+        check(self.lib, self.lib.gp_paths_table(self.h, float(y_mean), float(y_std), dptr(out)), "gp_paths_table")
+        return out[:S]
+
+    def paths_argbest(self, sense=-1, y_mean=0.0, y_std=1.0):
+        """Per path the best row of that table (lowest index among ties) and its value: (idx [S], val [S])."""
+        idx = np.empty(GP_PATHS_MAX_S, dtype=np.int64)
+        val = np.empty(GP_PATHS_MAX_S)
+        check(self.lib, self.lib.gp_paths_argbest(self.h, float(y_mean), float(y_std), int(sense), idx.ctypes.data_as(c_int64_p),
+                                                  dptr(val)), "gp_paths_argbest")
+        S = self.paths_info()[0]
+        return idx[:S].copy(), val[:S].copy()
+
+    def paths_rows(self, Xs, path, y_mean=0.0, y_std=1.0, grad=False):
+        """Up to GP_PATHS_MAX_ROWS locations by value, row i on path ``path[i]``: values [M] and, with ``grad``, gradients [M, D]."""
+        Xs = np.ascontiguousarray(Xs, dtype=np.float64)
+        if Xs.ndim != 2 or Xs.shape[1] != self.D:
+            raise ValueError("expected locations of shape [M, %d], got %s" % (self.D, Xs.shape))
+        M = Xs.shape[0]
+        path = np.ascontiguousarray(np.broadcast_to(np.asarray(path, dtype=np.int32).ravel(), (M,)) if np.size(path) == 1
+                                    else np.asarray(path, dtype=np.int32).ravel())
+        if path.size != M:
+            raise ValueError("one path index per location: %d locations, %d indices" % (M, path.size))
+        out = np.empty(M)
+        dout = np.empty((M, self.D)) if grad else None
+        rc = self.lib.gp_paths_rows(self.h, Xs.ctypes.data, M, path.ctypes.data, y_mean, y_std, out.ctypes.data,
+                                    dout.ctypes.data if grad else None)
+        if rc:
+            check(self.lib, rc, "gp_paths_rows")
+        return (out, dout) if grad else out
 
     # -- the mean function m(x) = x^T A + b of the exact GP (include/gphip.h, gp_mean_*) -----------------------------------
     def mean_set(self, A=None, b=None):

@@ -640,19 +640,22 @@ class AcquisitionMES(AcquisitionBase):
 
     The samples come from ``max_value.MinValueSampler`` over ``grid_size`` uniform draws of the space plus the model's X, drawn
     with ``seed`` and clipped at the incumbent; they are redrawn whenever the model's fit has changed (new data or new
-    hyper-parameters), as the belief of ``AcquisitionEntropySearch`` is.  With the exact HIP ``GPModel`` (one output) the sampler's
+    hyper-parameters), as the belief of ``AcquisitionEntropySearch`` is.  ``sampler='paths'`` takes the samples the paper itself
+    takes instead of the Gumbel fit: the minima over that table of ``num_samples`` posterior paths of ``num_features`` features
+    (posterior_paths.py; the exact HIP ``GPModel`` only).  With the exact HIP ``GPModel`` (one output) the sampler's
     sums and every score run on the device (``gp_mes_*``, ``GP_ACQ_MES``); a foreign, sparse or warped model is scored on the host
     from ``model.predict[_withGradients]`` by the same rule.  Not available: a model that samples its hyper-parameters, black-box
     constraints, replica groups."""
     analytical_gradient_prediction = True
     _rule = _RULES["MES"]
 
-    def __init__(self, model, space, optimizer=None, cost_withGradients=None, num_samples=10, grid_size=10000, seed=None):
+    def __init__(self, model, space, optimizer=None, cost_withGradients=None, num_samples=10, grid_size=10000, seed=None,
+                 sampler='gumbel', num_features=1024):
         if isinstance(model, GPModel_MCMC):
             raise NotImplementedError("MES scores one posterior: not available with a model that samples its hyper-parameters")
         from .max_value import MinValueSampler
         super().__init__(model, space, optimizer, cost_withGradients=cost_withGradients)
-        self.sampler = MinValueSampler(model, self.space, num_samples, grid_size, seed)
+        self.sampler = MinValueSampler(model, self.space, num_samples, grid_size, seed, sampler=sampler, num_features=num_features)
         self.ystar = None
         self.draws = 0                  # how often the samples were drawn (the handles' staleness key; tests)
         self._fit_signature = None
@@ -705,6 +708,175 @@ class AcquisitionMES(AcquisitionBase):
         ystar = self._samples()
         mu, sd, dmu_dx, dsd_dx = self.model.predict_withGradients(x)
         return self._rule.gradient(ystar, 0.0, mu, sd, dmu_dx, dsd_dx)
+
+
+class AcquisitionTS(AcquisitionBase):
+    """Thompson sampling proper: the acquisition IS a sample of the posterior function, -f_s(x) under LCB's sign convention (so
+    ``acquisition_function`` returns f_s, to be minimised), with its analytic gradient.  The samples are posterior paths
+    (posterior_paths.py, pathwise conditioning; GPyOpt has nothing of the kind: its 'thompson_sampling' evaluator draws
+    independent marginals to pick anchors and then optimises the ordinary acquisition).  ``num_paths`` paths of ``num_features``
+    random Fourier features are resident at a time; ``select_path(s)`` chooses the one scored.  They are drawn with ``seed`` and
+    redrawn whenever the model's fit has changed, and ``optimize`` draws fresh ones for every suggestion.  Table values, arg-best,
+    top-k and the one-location calls all run on the device (``gp_paths_*``).  Only the exact HIP ``GPModel`` with one output, a
+    Euclidean kernel and no mean function has paths; a cost model, black-box constraints and ``AcquisitionLP`` are refused."""
+    analytical_gradient_prediction = True
+
+    def __init__(self, model, space=None, optimizer=None, cost_withGradients=None, num_paths=1, num_features=1024, seed=None,
+                 feasibility=None):
+        if type(model) is not GPModel or getattr(model, "sparse", False):
+            raise NotImplementedError("Thompson sampling draws posterior paths of our exact GPModel: a foreign, sparse, MCMC or "
+                                      "warped model has none")
+        if cost_withGradients is not None and cost_withGradients is not constant_cost_withGradients:
+            raise NotImplementedError("Thompson sampling takes no cost model: a sample of the function is not a gain to divide")
+        if feasibility is not None:
+            raise NotImplementedError("Thompson sampling takes no black-box constraints: feasibility= weights EI and MPI")
+        if not 1 <= int(num_paths) <= _lib.GP_PATHS_MAX_S:
+            raise ValueError("between 1 and %d paths, got %r" % (_lib.GP_PATHS_MAX_S, num_paths))
+        if not 1 <= int(num_features) <= _lib.GP_PATHS_MAX_F:
+            raise ValueError("between 1 and %d features, got %r" % (_lib.GP_PATHS_MAX_F, num_features))
+        super().__init__(model, space, optimizer)
+        self.num_paths, self.num_features = int(num_paths), int(num_features)
+        self._rng = np.random.default_rng(seed)
+        self.paths = None
+        self.path = 0
+        self.draws = 0                  # how often the paths were drawn (tests)
+        self._fit_signature = None
+
+    @staticmethod
+    def fromConfig(model, space, optimizer, cost_withGradients, config):
+        return AcquisitionTS(model, space, optimizer, cost_withGradients, num_paths=config.get('num_paths', 1),
+                             num_features=config.get('num_features', 1024), seed=config.get('sampler_seed', None))
+
+    def _set_feasibility(self, feasibility):
+        if feasibility is not None:
+            raise NotImplementedError("Thompson sampling takes no black-box constraints: feasibility= weights EI and MPI")
+
+    def select_path(self, s):
+        """Score path ``s`` of the resident ``num_paths`` from now on."""
+        if not 0 <= int(s) < self.num_paths:
+            raise ValueError("path %r outside 0..%d" % (s, self.num_paths - 1))
+        self.path = int(s)
+
+    def _signature(self):
+        from .posterior_paths import fit_signature
+        gp = self.model.model
+        return (id(gp),) + fit_signature(gp)
+
+    def redraw(self, num_paths=None):
+        """New paths for the model's current fit (``num_paths`` of them from now on, when given)."""
+        from .posterior_paths import PosteriorPaths, draw
+        if num_paths is not None:
+            if not 1 <= int(num_paths) <= _lib.GP_PATHS_MAX_S:
+                raise ValueError("between 1 and %d paths, got %r" % (_lib.GP_PATHS_MAX_S, num_paths))
+            self.num_paths = int(num_paths)
+            self.path = min(self.path, self.num_paths - 1)
+        gp = self.model.model
+        if gp is None:
+            raise RuntimeError("the model has no data yet: updateModel first")
+        gp._ensure_fit()
+        seed = int(self._rng.integers(0, 2 ** 63 - 1))
+        self.paths = PosteriorPaths(gp, draws=draw(gp.kern, gp.num_data, gp.input_dim, self.num_paths, self.num_features, seed))
+        self._fit_signature = self._signature()
+        self.draws += 1
+        return self.paths
+
+    def _paths(self):
+        """The paths of the model's current fit, drawn when it has changed (or when other paths took their place on the handle)."""
+        gp = self.model.model
+        if gp is None:
+            raise RuntimeError("the model has no data yet: updateModel first")
+        gp._ensure_fit()
+        if (self.paths is None or self._fit_signature != self._signature() or self.paths.size != self.num_paths
+                or gp._h.paths_key != self.paths._key):
+            self.redraw()
+        return self.paths
+
+    def _indicator(self, x):
+        constrained = getattr(self.space, "has_constraints", None)
+        return self.space.indicator_constraints(x) if constrained is not None and constrained() else None
+
+    def _locations(self, x):
+        x = np.asarray(x, dtype=float)
+        return x if x.ndim == 2 else np.atleast_2d(x)
+
+    def values_on_paths(self, x, path, grad=False):
+        """f [M, 1] (and df/dx [M, D]) at the rows of ``x``, row i on path ``path[i]`` (or all on one): in groups of up to
+        ``_FEW_ROWS`` rows, one gp_paths_rows call each -- the lockstep optimisers' call."""
+        x = self._locations(x)
+        paths = self._paths()
+        M = x.shape[0]
+        path = np.broadcast_to(np.asarray(path, dtype=np.int32).ravel(), (M,)) if np.size(path) == 1 else np.asarray(path, dtype=np.int32)
+        f = np.empty((M, 1))
+        df = np.empty(x.shape) if grad else None
+        for k in range(0, M, _FEW_ROWS):
+            r = paths.model._h.paths_rows(x[k:k + _FEW_ROWS], path[k:k + _FEW_ROWS], *paths._normaliser(), grad=grad)
+            if grad:
+                f[k:k + _FEW_ROWS, 0], df[k:k + _FEW_ROWS] = r
+            else:
+                f[k:k + _FEW_ROWS, 0] = r
+        ind = self._indicator(x)
+        if ind is not None:
+            f = f * ind
+            if grad:
+                df = df * ind
+        return (f, df) if grad else f
+
+    def _table(self, x):
+        """The resident paths over the rows of ``x`` as the resident table: (handle, normaliser mean, std)."""
+        paths = self._paths()
+        h = paths.model._h
+        h.set_candidates(x)
+        return (h,) + paths._normaliser()
+
+    def acquisition_function(self, x):
+        """f_s(x) of the selected path, [M, 1]: up to ``_FEW_ROWS`` rows by value, more through the table kernel."""
+        x = self._locations(x)
+        if x.shape[0] <= _FEW_ROWS:
+            return self.values_on_paths(x, self.path)
+        h, shift, scale = self._table(x)
+        f = h.paths_table(shift, scale)[self.path][:, None].copy()
+        ind = self._indicator(x)
+        return f if ind is None else f * ind
+
+    def acquisition_function_withGradients(self, x):
+        return self.values_on_paths(x, self.path, grad=True)
+
+    def table_on_paths(self, x):
+        """Every resident path over the rows of ``x``: [M, num_paths] (the batch evaluator's anchor table)."""
+        x = self._locations(x)
+        h, shift, scale = self._table(x)
+        t = h.paths_table(shift, scale).T
+        ind = self._indicator(x)
+        return t if ind is None else t * ind
+
+    def argbest(self, x, sense=-1, devices=None):
+        if devices is not None:
+            raise NotImplementedError("replica groups hold no posterior paths: Thompson sampling scores its table on one device")
+        x = self._locations(x)
+        if self._indicator(x) is not None:
+            return _pick(self.acquisition_function(x)[:, 0], sense)
+        h, shift, scale = self._table(x)
+        idx, val = h.paths_argbest(sense, shift, scale)
+        return int(idx[self.path]), float(val[self.path])
+
+    def topk(self, x, k, sense=-1, devices=None):
+        if devices is not None:
+            raise NotImplementedError("replica groups hold no posterior paths: Thompson sampling scores its table on one device")
+        x = self._locations(x)
+        return _host_topk(self.acquisition_function(x)[:, 0] if x.shape[0] > _FEW_ROWS else
+                          self.values_on_paths(x, self.path)[:, 0], k, sense)
+
+    def optimize(self, duplicate_manager=None):
+        """A fresh path for every suggestion, then the acquisition optimiser on it."""
+        self.redraw()
+        return super().optimize(duplicate_manager=duplicate_manager)
+
+    def _compute_acq(self, x):
+        return -self.acquisition_function(x)
+
+    def _compute_acq_withGradients(self, x):
+        f, df = self.acquisition_function_withGradients(x)
+        return -f, -df
 
 
 # ---- acquisitions integrated over the hyper-parameter samples ----------------------------------------------------------
@@ -845,6 +1017,9 @@ class AcquisitionLP(AcquisitionBase):
     analytical_gradient_prediction = True
 
     def __init__(self, model, space=None, optimizer=None, acquisition=None, transform='none'):
+        if isinstance(acquisition, AcquisitionTS):
+            raise NotImplementedError("Thompson sampling spreads a batch by drawing one path per element: it is not penalised "
+                                      "(use the 'thompson_sampling' evaluator)")
         super().__init__(model, space, optimizer)
         self.acq = acquisition
         kind = str(transform).lower()

@@ -20,7 +20,7 @@ from scipy import optimize as _sopt
 
 from . import kern as _kern
 from .acquisitions import (AcquisitionEI, AcquisitionLCB, AcquisitionMPI, AcquisitionLP, LocalPenalization, AcquisitionEI_MCMC,
-                           AcquisitionMPI_MCMC, AcquisitionLCB_MCMC, AcquisitionEntropySearch, AcquisitionMES)
+                           AcquisitionMPI_MCMC, AcquisitionLCB_MCMC, AcquisitionEntropySearch, AcquisitionMES, AcquisitionTS)
 from .cost import CostModel
 from .feasibility import FeasibilityModel
 from .entropy_search import AffineInvariantEnsembleSampler
@@ -203,22 +203,23 @@ class AcquisitionOptimizer(object):
 LOCKSTEP_GROUP = 8      # anchors per lockstep group: what ONE gp_acq_rows call takes (acquisitions._FEW_ROWS)
 
 
-def _lbfgs_from_anchors(space, anchors, f_df, maxiter=1000):
+def _lbfgs_from_anchors(space, anchors, f_df, maxiter=1000, indexed=False):
     """``_lbfgs_from_anchor`` for every anchor, the runs of a group of up to ``LOCKSTEP_GROUP`` anchors advancing in lockstep
     (parameterization.lbfgsb_lockstep): each round's posted points go to ``f_df`` as the rows of ONE call.  A row's value and
     gradient do not depend on its company (include/gphip.h, gp_*_rows), so every run takes the steps its serial run takes;
-    the abnormal-line-search fallback and ``round_optimum`` are applied per anchor.  Returns the [1, D] optima in anchor order."""
+    the abnormal-line-search fallback and ``round_optimum`` are applied per anchor.  Returns the [1, D] optima in anchor order.
+    ``indexed``: every anchor has an objective of its own -- ``f_df(xs, which)`` also gets the anchors the rows belong to."""
     bounds = space.get_bounds()
-
-    def fbatch(xs):
-        fx, dfx = f_df(xs)
-        return np.asarray(fx, dtype=float).reshape(-1), np.asarray(dfx, dtype=float).reshape(xs.shape[0], -1)
-
     anchors = [np.asarray(a, dtype=float) for a in anchors]
     out = []
     for k in range(0, len(anchors), LOCKSTEP_GROUP):
+        def fbatch(xs, idx=None, k=k):
+            fx, dfx = f_df(xs, k + np.asarray(idx)) if indexed else f_df(xs)
+            return np.asarray(fx, dtype=float).reshape(-1), np.asarray(dfx, dtype=float).reshape(xs.shape[0], -1)
+
         group = anchors[k:k + LOCKSTEP_GROUP]
-        for a, res in zip(group, lbfgsb_lockstep(fbatch, group, max_iters=maxiter, bounds=bounds, maxfun=SCIPY_DEFAULT)):
+        for a, res in zip(group, lbfgsb_lockstep(fbatch, group, max_iters=maxiter, bounds=bounds, maxfun=SCIPY_DEFAULT,
+                                                 with_index=indexed)):
             if isinstance(res, BaseException):
                 raise res
             x = np.atleast_2d(res[0])
@@ -305,6 +306,45 @@ class ThompsonBatch(SamplingBasedBatchEvaluator):
         return np.vstack([self.optimize_anchor_point(a) for a in anchors])
 
 
+class ThompsonPathsBatch(SamplingBasedBatchEvaluator):
+    """The batch of ``AcquisitionTS`` (no counterpart in the reference): ``batch_size`` posterior paths are drawn, element b is
+    the minimiser of path b -- its anchor the best of ``num_samples`` uniform locations under ITS path (its own column of one
+    anchor table), refined by L-BFGS on that path.  Distinct joint samples spread the batch by themselves: no penaliser.  With the
+    optimiser in lockstep mode the B runs advance together, each round's points going down as ONE gp_paths_rows call per group
+    of eight, row i on path i."""
+
+    def __init__(self, acquisition, batch_size, num_samples=1000):
+        if not isinstance(acquisition, AcquisitionTS):
+            raise TypeError("ThompsonPathsBatch spreads a batch over the paths of an AcquisitionTS")
+        super(ThompsonPathsBatch, self).__init__(acquisition, batch_size)
+        self.num_samples = num_samples
+
+    def get_anchor_points(self):
+        """[batch_size, D]: per path the lowest row of one table of uniform locations (reduced on the device)."""
+        acq = self.acquisition
+        X = self.space.samples_uniform(self.num_samples)
+        if acq._indicator(X) is not None:
+            rows = np.argmin(acq.table_on_paths(X), axis=0)
+        else:
+            h, shift, scale = acq._table(X)
+            rows = h.paths_argbest(-1, shift, scale)[0]
+        return X[rows, :]
+
+    def compute_batch_without_duplicate_logic(self):
+        acq, B = self.acquisition, self.batch_size
+        acq.redraw(num_paths=B)
+        anchors = self.get_anchor_points()
+        optimizer = acq.optimizer
+        if optimizer is not None and optimizer.lockstep(acq.acquisition_function_withGradients):
+            # a round's rows are the runs still going: each on the path of its own anchor
+            return np.vstack(_lbfgs_from_anchors(self.space, anchors, lambda xs, which: acq.values_on_paths(xs, which, grad=True),
+                                                 indexed=True))
+        out = []
+        for b in range(B):
+            out.append(_lbfgs_from_anchor(self.space, anchors[b], None, lambda x, p=b: acq.values_on_paths(x, p, grad=True)))
+        return np.vstack(out)
+
+
 class RandomBatch(SamplingBasedBatchEvaluator):
     """core/evaluators/batch_random.py:9-48: first element = the optimised acquisition, the rest uniform."""
 
@@ -347,6 +387,12 @@ class BayesianOptimization(object):
     minimum's value), ``mes_grid_size`` (10000 uniform locations under the sampler, besides X) and ``sampler_seed``
     (``AcquisitionMES``).  It has gradients, so every evaluator works with it, 'local_penalization' and ``parallel_anchors=True``
     included, and so does ``cost_withGradients='evaluation_time'``; with ``constraint_function`` it raises
+    ``NotImplementedError``.
+
+    Thompson sampling proper (an addition): ``acquisition_type='TS'`` with the keywords ``num_features`` (1024 random Fourier
+    features of the prior term) and ``sampler_seed`` minimises a sample of the posterior FUNCTION (``AcquisitionTS``, posterior
+    paths).  'sequential' draws one fresh path per suggestion; 'thompson_sampling' with ``batch_size`` B draws B paths and
+    returns the minimiser of each (``ThompsonPathsBatch``); 'local_penalization', a cost model and ``constraint_function`` raise
     ``NotImplementedError``."""
 
     def __init__(self, f, domain=None, constraints=None, cost_withGradients=None, model_type='GP', X=None, Y=None,
@@ -431,6 +477,9 @@ class BayesianOptimization(object):
             self.acquisition = AcquisitionMES(self.model, self.space, self.acquisition_optimizer, cost_withGradients,
                                               num_samples=kwargs.get('num_min_samples', 10),
                                               grid_size=kwargs.get('mes_grid_size', 10000), seed=kwargs.get('sampler_seed', None))
+        elif acquisition_type == 'TS':
+            self.acquisition = AcquisitionTS(self.model, self.space, self.acquisition_optimizer, cost_withGradients,
+                                             num_features=kwargs.get('num_features', 1024), seed=kwargs.get('sampler_seed', None))
         elif acquisition_type == 'EI_MCMC':
             self.acquisition = AcquisitionEI_MCMC(self.model, self.space, self.acquisition_optimizer, cost_withGradients, jitter)
         elif acquisition_type == 'MPI_MCMC':
@@ -451,8 +500,14 @@ class BayesianOptimization(object):
         elif evaluator_type in ('random', None):
             self.evaluator = RandomBatch(self.acquisition, batch_size)
         elif evaluator_type == 'thompson_sampling':
-            self.evaluator = ThompsonBatch(self.acquisition, batch_size)
+            # Thompson sampling proper draws one posterior path per batch element; every other acquisition keeps the reference's
+            # marginal draws for the anchors
+            self.evaluator = (ThompsonPathsBatch if isinstance(self.acquisition, AcquisitionTS) else ThompsonBatch)(
+                self.acquisition, batch_size)
         elif evaluator_type == 'local_penalization':
+            if isinstance(self.acquisition, AcquisitionTS):
+                raise NotImplementedError("Thompson sampling spreads a batch by drawing one path per element: use the "
+                                          "'thompson_sampling' evaluator, not 'local_penalization'")
             if not isinstance(self.acquisition, AcquisitionLP):
                 self.acquisition = AcquisitionLP(self.model, self.space, self.acquisition_optimizer, self.acquisition,
                                                  transform=kwargs.get('acquisition_transformation', 'none'))

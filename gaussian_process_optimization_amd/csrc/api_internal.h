@@ -354,6 +354,26 @@ struct MesState {
     DevBuf<double> dPart;      // the chunks' partial sums / minima, then the results (mes_part_elems)
 };
 
+// Posterior paths (api_paths.hip): S function samples by pathwise conditioning on the resident factor -- the scaled draws of the
+// prior term and the update's weights V.  S > 0 while they belong to the factor in dA; everything that drops or grows the factor
+// drops them (factor_results_dropped, factor_grown).
+struct PathsState {
+    int S = 0, F = 0;          // paths and features resident (0: none)
+    int Spad = 0, Fpad = 0;    // ... rounded up to the matrix cores' 16: zero rows / zero weights in the padding
+    double amp = 0.0;          // a = sqrt(2 variance / F)
+    DevBuf<double> dOmega;     // [Fpad, D]: omega_unit / lengthscale
+    DevBuf<double> dPhase;     // [Fpad]
+    DevBuf<double> dWt;        // [Spad, Fpad], path-major
+    DevBuf<double> dV;         // [Spad, Npad], path-major: one path's column of V is contiguous
+    DevBuf<double> dR, dZ;     // 128 x Npad each: z_eps -> the residuals (the solve's running right-hand side), the forward solve
+    DevBuf<double> dTab;       // [S, M]: the table of gp_paths_table / gp_paths_argbest
+    DevBuf<double> dPart;      // ... and its partial sums over chunks of the training rows (paths_table_part_elems)
+    DevBuf<double> dRedV;      // the arg-best reduction's first-level winners and results, per path
+    DevBuf<long long> dRedI;
+    DevBuf<double> dRows;      // gp_paths_rows: the chunks' partial sums
+    PassOwner pass{1, "the path kernel"};   // completion of gp_paths_rows
+};
+
 struct gp_ctx {
     int device = 0;
     long lds_per_wg = 0;           // hipDeviceAttributeMaxSharedMemoryPerBlock of the device (gp_create)
@@ -516,6 +536,7 @@ struct gp_ctx {
     MeanState mean;     // the mean function (api_mean.hip)
     FeasState feas;     // the cached probability of feasibility of the flagged table entries (api_feas.hip)
     MesState mes;       // the samples of the minimum's value behind GP_ACQ_MES (api_mes.hip)
+    PathsState paths;   // posterior function samples over the resident factor (api_paths.hip)
     bool dead = false;  // gp_shutdown ran: the device's streams are gone, only gp_destroy is still valid
 };
 
@@ -530,6 +551,7 @@ static inline void factor_results_dropped(gp_ctx *g) {
     g->predicted = false;
     g->es.R = 0;
     g->es.belief = false;
+    g->paths.S = 0;
 }
 // ... and dA no longer holds a fit of the current data and parameters at all.
 static inline void fit_dropped(gp_ctx *g) {
@@ -558,6 +580,7 @@ static inline void factor_grown(gp_ctx *g) {
     g->ens.S = 0;
     g->es.R = 0;
     g->es.belief = false;
+    g->paths.S = 0;
 }
 
 static inline long round_up(long x, long m) { return (x + m - 1) / m * m; }

@@ -340,6 +340,40 @@ void launch_es_rows(hipStream_t s, const RowsX &rx, const KernParams &kp, const 
                     const double *logP, const double *u, const double *W, int S, const PassReport &r);
 void launch_transpose_tri(hipStream_t s, double *dst, const double *src, long n, int mode);
 
+// ---- paths.hip: posterior function samples by pathwise conditioning (api_paths.hip) --------------------------------------------
+// f_s(x) = amp sum_j Wt[s, j] cos(omega_j . x + phase_j) + sum_n k(x, X_n) V[s, n].  omega [Fpad, D], phase [Fpad], Wt [Spad, Fpad],
+// V [Spad, ldv]: Spad and Fpad multiples of PATHS_MMA, zeros in the padding
+#define PATHS_MMA 16           // rows / columns of the fp64 matrix instruction: the padding of S and F
+#define PATHS_MAX_SPAD 64      // GP_PATHS_MAX_S rounded up to it
+#define PATHS_ROWS_M 8         // locations per launch_paths_rows (GP_PATHS_MAX_ROWS)
+#define PATHS_ROWS_CH 256      // training rows / features per first-level partial of launch_paths_rows
+#define PATHS_ROWS_GROW (ROWS_MAX_XS + PATHS_ROWS_M)   // doubles of per-workgroup sums: value and D gradient entries per location
+struct PathsPrior {
+    int F, Fpad, Spad;
+    double amp;
+    const double *omega, *phase, *Wt;
+};
+// R[s, n] = Y[n] - amp sum_j Wt[s, j] cos(omega_j . X_n + phase_j) - sd R[s, n] for s < S, n < N (R holds z_eps on entry); R [., ldr]
+void launch_paths_residual(hipStream_t s, const PathsPrior &pp, int S, int D, const double *X, const double *Y, long N, double sd,
+                           double *R, long ldr);
+// out[s, i] = y_std f_s(xs_i) + y_mean for s < S, i < M: out [S, M]; part: paths_table_part_elems(M, N, S) doubles of scratch (0: a
+// table of so many rows that one workgroup per 64 of them fills the chip; part may then be null)
+size_t paths_table_part_elems(long M, long N, int S);
+size_t paths_table_lds_bytes(int D, int Spad);   // LDS bytes a workgroup of that launch needs
+void launch_paths_table(hipStream_t s, const PathsPrior &pp, int S, const KernParams &kp, const double *Xs, long M, const double *X,
+                        long N, const double *V, long ldv, double y_mean, double y_std, double *out, double *part);
+// per path s < S the best of tab[s, 0 .. M) (lowest index among ties) into rv[s] / ri[s]; rv / ri hold paths_argbest_elems(S)
+// entries each: the results, then the first-level winners
+inline long paths_argbest_elems(int S) { return (long)S * 257; }
+void launch_paths_argbest(hipStream_t s, const double *tab, long M, int S, int sense, double *rv, long long *ri);
+// rx.M <= PATHS_ROWS_M locations by value, location m on path `path[m]`: value at r.out[m], gradient (want_grad) at
+// r.out[PATHS_ROWS_M + m D + d], the ticket at r.out[ROWS_OUT_DOUBLES]; gpart: paths_rows_grid(N, F) PATHS_ROWS_GROW doubles
+struct PathsPick { int path[PATHS_ROWS_M]; };
+inline unsigned paths_rows_grid(long N, int F) { return (unsigned)((N + PATHS_ROWS_CH - 1) / PATHS_ROWS_CH + (F + PATHS_ROWS_CH - 1) / PATHS_ROWS_CH); }
+void launch_paths_rows(hipStream_t s, const PathsPrior &pp, const RowsX &rx, const PathsPick &pk, const KernParams &kp, const double *X,
+                       long N, const double *V, long ldv, int want_grad, double y_mean, double y_std, double *gpart,
+                       const PassReport &r);
+
 // ---- ens_rows.hip: the same passes over an ensemble of S members, the member as a grid dimension --------------------------------
 #define ENS_ROWS_RB 32                       // rows of the tile per workgroup: what rows_block_height gives every matrix the ensemble takes
 #define ENS_POST_STRIDE ROWS_OUT_DOUBLES     // doubles between two members' result blocks (each laid out as the single model's)

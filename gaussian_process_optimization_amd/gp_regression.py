@@ -486,6 +486,15 @@ class GPRegression(Parameterized):
             fsim[:, d, :] = m[:, d:d + 1] + dev[d].T
         return fsim
 
+    def posterior_paths(self, size=10, num_features=1024, seed=None, draws=None):
+        """``size`` samples of the posterior FUNCTION by pathwise conditioning (posterior_paths.py; no counterpart in the
+        reference): an object that evaluates them anywhere -- ``paths(X)`` [M, size] --, differentiates them
+        (``paths.value_and_gradient(X, path)``) and minimises them over a table (``paths.argmin(X)``), without the M x M
+        covariance ``posterior_samples_f`` factors.  ``num_features`` random Fourier features carry the prior term; ``draws``
+        (posterior_paths.draw) makes the paths reproducible.  Valid for the current fit only."""
+        from .posterior_paths import PosteriorPaths
+        return PosteriorPaths(self, size=size, num_features=num_features, seed=seed, draws=draws)
+
     # -- optimisation -------------------------------------------------------------------
     def _uses_gower(self):
         return bool(self.kern.Gower and self.kern.space is not None)

@@ -76,7 +76,11 @@ class MinValueSampler(object):
     draws from ``numpy.random.RandomState(seed)`` and clips at ``model.get_fmin()``.  After ``sample()``: ``last_brackets``
     {q: (lo, hi)}, ``last_quantiles`` {q: y_q}, ``last_fit`` (a, b), ``last_first`` (the first bracket), ``last_on_device``, ``last_latent``."""
 
-    def __init__(self, model, space, num_samples=10, grid_size=10000, seed=None):
+    def __init__(self, model, space, num_samples=10, grid_size=10000, seed=None, sampler='gumbel', num_features=1024):
+        if sampler not in ('gumbel', 'paths'):
+            raise ValueError("sampler must be 'gumbel' or 'paths', got %r" % (sampler,))
+        self.sampler = sampler
+        self.num_features = int(num_features)
         if not 1 <= int(num_samples) <= 64:
             raise ValueError("num_samples must be between 1 and 64 (GP_MES_MAX_K), got %r" % (num_samples,))
         if int(grid_size) < 1:
@@ -146,6 +150,8 @@ class MinValueSampler(object):
 
     def sample(self, table=None):
         """``num_samples`` values of y*, all at most ``model.get_fmin()``."""
+        if self.sampler == 'paths':
+            return self._sample_paths(table)
         br = self.brackets(table)
         quant = {q: 0.5 * (br[q][0] + br[q][1]) for q in QUANTILES}
         a, b = gumbel_fit(quant[0.25], quant[0.5], quant[0.75])
@@ -153,3 +159,18 @@ class MinValueSampler(object):
         fmin = float(np.min(self.model.get_fmin()))
         self.last_brackets, self.last_quantiles, self.last_fit = br, quant, (a, b)
         return np.minimum(a + b * np.log(-np.log(u)), fmin)
+
+    def _sample_paths(self, table=None):
+        """The sampler the MES paper itself uses: ``num_samples`` posterior paths (posterior_paths.py), each minimised over the
+        table on the device (gp_paths_argbest: 2 K numbers come back), clipped at the incumbent as the Gumbel draws are."""
+        gp = self._device_gp()
+        if gp is None:
+            raise NotImplementedError("sampler='paths' draws posterior paths of our exact GPModel: a foreign, sparse or warped "
+                                      "model keeps sampler='gumbel'")
+        from .posterior_paths import PosteriorPaths, draw
+        table = self.table() if table is None else np.atleast_2d(np.asarray(table, dtype=float))
+        gp._ensure_fit()
+        paths = PosteriorPaths(gp, draws=draw(gp.kern, gp.num_data, gp.input_dim, self.num_samples, self.num_features, self.seed))
+        self.last_on_device, self.last_latent = True, True
+        self.last_argmin, values = paths.argmin(table)
+        return np.minimum(values, float(np.min(self.model.get_fmin())))

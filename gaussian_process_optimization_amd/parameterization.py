@@ -311,7 +311,7 @@ class Parameterized(object):
 SCIPY_DEFAULT = "scipy"     # lbfgsb_lockstep(maxfun=SCIPY_DEFAULT): leave maxfun to fmin_l_bfgs_b's own default
 
 
-def lbfgsb_lockstep(fbatch, x0s, max_iters=1000, factr=None, pgtol=None, bounds=None, maxfun=None):
+def lbfgsb_lockstep(fbatch, x0s, max_iters=1000, factr=None, pgtol=None, bounds=None, maxfun=None, with_index=False):
     """R ``scipy.optimize.fmin_l_bfgs_b`` runs in lockstep over ONE batch objective (optimize_restarts(parallel=True)).
 
     ``fbatch(xs)`` takes the points of the still-running instances, ``xs[k, n]`` (rows in instance order), and returns
@@ -321,7 +321,8 @@ def lbfgsb_lockstep(fbatch, x0s, max_iters=1000, factr=None, pgtol=None, bounds=
     ``maxfun`` replaces max_iters as the evaluation limit, ``SCIPY_DEFAULT`` leaves it to scipy (what a caller that passes
     ``maxiter`` alone gets: the acquisition optimiser).  When every running instance has posted, one ``fbatch`` call is made and
     the values are handed back; a finished instance leaves the batch.  The L-BFGS-B state lives in each call's own arrays
-    (scipy passes it all to setulb), so every instance follows the path a serial run from its start takes.
+    (scipy passes it all to setulb), so every instance follows the path a serial run from its start takes.  ``with_index``:
+    ``fbatch(xs, idx)`` also gets the instances the rows belong to (an objective that differs from instance to instance).
 
     Returns one entry per start, in order: the ``(x, f, d)`` of ``fmin_l_bfgs_b``, or the exception its run raised."""
     x0s = [np.asarray(x, dtype=float) for x in x0s]
@@ -376,7 +377,7 @@ def lbfgsb_lockstep(fbatch, x0s, max_iters=1000, factr=None, pgtol=None, bounds=
             idx = sorted(posted)
             xs = np.stack([posted.pop(r) for r in idx])
         try:
-            res = fbatch(xs)
+            res = fbatch(xs, list(idx)) if with_index else fbatch(xs)
             f, g = np.asarray(res[0], dtype=float), np.asarray(res[1], dtype=float)
             errors = res[2] if len(res) > 2 else [None] * len(idx)
             reply = {r: (errors[j] if errors[j] is not None else (float(f[j]), g[j].copy())) for j, r in enumerate(idx)}

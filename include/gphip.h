@@ -1000,6 +1000,54 @@ int gp_mes_info(gp_t *gp, int *K);
 int gp_mes_logsurv(gp_t *gp, int include_noise, double y_mean, double y_std, const double *y, int G, double *out);
 int gp_mes_bracket(gp_t *gp, int include_noise, double y_mean, double y_std, double nsig, double *lo, double *hi);
 
+/* ---- posterior paths: samples of the posterior FUNCTION by pathwise conditioning ----------------------------------------------
+ * (Wilson et al., "Efficiently sampling functions from Gaussian process posteriors", ICML 2020.)  A path is
+ *     f_s(x) = a sum_j w_js cos(omega_j^T x + b_j)  +  sum_n k(x, X_n) V_ns,       a = sqrt(2 variance / F),
+ *     V_s = (K + d I)^-1 (y - Phi(X) w_s - eps_s),   eps_s = sqrt(d) z_s,   Phi(X)_nj = a cos(omega_j^T X_n + b_j),
+ * d = noise + 1e-8 + jitter: the whole diagonal the resident factor carries, so that the update is exact for that factor.  The
+ * first term is a random-Fourier-feature draw from the prior, the second an exact update through the factor of the fit: whatever F
+ * is, f_s(X_i) = y_i - eps_si - d V_is.  Scope: the exact model with P = 1 and a Euclidean RBF, Matern-5/2, Matern-3/2 or
+ * Exponential covariance, ARD or not.  Refused before anything is launched or changed: a Gower model (no spectral density,
+ * GP_ERR_ARG), P != 1 (GP_ERR_ARG), a resident mean function or an output warp (GP_ERR_STATE), no fit (GP_ERR_STATE).
+ *
+ * gp_paths_set: S paths (1 .. GP_PATHS_MAX_S) of F features (1 .. GP_PATHS_MAX_F) from draws that do not depend on the
+ * hyper-parameters: omega_unit [F, D] frequencies of the unit-lengthscale kernel, phase [F] in [0, 2 pi), w [S, F] and z_eps [S, N]
+ * standard normals.  The library scales them from the RESIDENT parameters -- omega_jd = omega_unit_jd / lengthscale_d, a from the
+ * variance, eps from d -- forms Phi(X) w (cos tiles in LDS against the fp64 matrix cores), the residuals, and V by the two
+ * substitutions against the resident factor that alpha takes; nothing is factored.  S = 0 clears (the pointers may be NULL).
+ * GP_ERR_ARG: S or F out of range, a null pointer, a draw that is not finite.  The paths belong to the factor: gp_fit,
+ * gp_set_params, gp_set_data, gp_append and everything else that drops or grows it drop them, and the entries below then return
+ * GP_ERR_STATE.  gp_paths_info: *S and *F of the resident paths, 0 and 0 when there are none.
+ *
+ * Values come back de-normalised, y_std f_s + y_mean (y_std positive and finite, y_mean finite, else GP_ERR_ARG).
+ * gp_paths_table: out [S, M] (path-major), every resident path over the M resident candidates (gp_set_candidates; GP_ERR_STATE
+ * without).  One kernel for a table that fills the chip by its rows alone, the kernel and a short summing launch otherwise (below):
+ * tiles of K(x_i, X_n) are formed in LDS and contracted with V on the fp64 matrix cores, the feature term in the same kernel;
+ * K(Xs, X) is never stored.  Per (path, candidate) the sum runs over n in tile order and over j in index order; a
+ * table of few rows is also cut into chunks of training rows -- a function of (M, N) alone -- whose sums a second launch adds in
+ * chunk order, so that it still fills the chip (scratch: (chunks + 1) S M doubles).  No atomics, the same bits whatever S is.
+ * A workgroup of the kernel needs 8 (2 * 64 (D + 1) + 32 D + 2560 + 36 Spad) bytes of LDS, Spad = S rounded up to 16 -- a limit
+ * JOINT in D and S: 121856 bytes at D = 64 and S = 64, inside the 163840 of gfx950, so every accepted (D, S) fits there; on a
+ * device that gives a workgroup less, gp_paths_table and gp_paths_argbest return GP_ERR_ARG (the message names D, S and both byte
+ * counts) before anything is launched.
+ * gp_paths_argbest: idx [S], val [S]: per path the best row of that table (sense -1 minimum, +1 maximum; the lowest index among
+ * ties), reduced on the device in one launch sequence for all paths.
+ * gp_paths_rows: M <= 8 locations Xs [M, D] by value, row i on path path[i] (0 <= path[i] < S): out [M] and, when dout is given,
+ * the x-gradient dout [M, D] = y_std (sum_n dk(x, X_n)/dx V_n - a sum_j w_j omega_j sin(omega_j^T x + b_j)).  The locations
+ * travel in the kernel arguments, as many per pass as M D <= 128 coordinates allow -- all eight up to D = 16, two at D = 64 --
+ * as in every rows entry; a pass is one launch and one synchronisation: partial sums over chunks of 256 training rows / features
+ * with one writer each, combined in chunk order by the last workgroup to arrive, into a pinned block.  A row's bits depend on
+ * neither the other rows, nor their paths, nor the pass it rides in.  Exponential at a coincident training point contributes 0 to
+ * the gradient (the _inv_dist convention of every gradient here). */
+#define GP_PATHS_MAX_S 64   /* paths resident at a time */
+#define GP_PATHS_MAX_F 4096 /* random Fourier features of the prior term */
+#define GP_PATHS_MAX_ROWS 8 /* locations per gp_paths_rows call */
+int gp_paths_set(gp_t *gp, int S, int F, const double *omega_unit, const double *phase, const double *w, const double *z_eps);
+int gp_paths_info(gp_t *gp, int *S, int *F);
+int gp_paths_table(gp_t *gp, double y_mean, double y_std, double *out);
+int gp_paths_argbest(gp_t *gp, double y_mean, double y_std, int sense, int64_t *idx, double *val);
+int gp_paths_rows(gp_t *gp, const double *Xs, int M, const int *path, double y_mean, double y_std, double *out, double *dout);
+
 #ifdef __cplusplus
 }
 #endif

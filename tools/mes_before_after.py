@@ -20,8 +20,8 @@ OUT = os.path.join(ROOT, "profiles", "mes_before_after.txt")
 SIDES = ("parent", "tree")
 
 
-def main(src):
-    out = ["existing kernels before / after max-value entropy search: the parent commit and this tree in ONE visit, alternating", "",
+def main(src, what="max-value entropy search", dest=None):
+    out = ["existing kernels before / after %s: the parent commit and this tree in ONE visit, alternating" % what, "",
            "bench.py --gpus 1 --steps 20 --warmup 3 (N = 16384, D = 8, M = 10000; ms per fit+predict step)"]
     for side in SIDES:
         v = []
@@ -43,7 +43,7 @@ def main(src):
     for k in sorted(rows):
         cell = lambda s: "  ".join("%.3f %.3f" % x for x in rows[k].get(s, []))     # noqa: E731
         out.append("%6d %5d | %-31s | %-31s" % (k[0], k[1], cell("parent"), cell("tree")))
-    open(OUT, "w").write("\n".join(out) + "\n")
+    open(dest or OUT, "w").write("\n".join(out) + "\n")
     print("\n".join(out))
     return 0
 
