@@ -23,6 +23,7 @@ GP_ACQ_PER_COST = 0x100      # or-ed into a scoring call's type: the scores are 
 GP_ACQ_POF = 3               # the rule whose value is 1: valid only with GP_ACQ_TIMES_FEAS (the probability of feasibility alone)
 GP_ACQ_MES = 4               # max-value entropy search over the handle's resident samples of the minimum's value (gp_mes_set)
 GP_PATHS_MAX_S, GP_PATHS_MAX_F, GP_PATHS_MAX_ROWS = 64, 4096, 8   # posterior paths: paths, features, locations per rows call
+GP_QEI_MAX_S, GP_QEI_MAX_Q = 4096, 8   # joint expected improvement: base samples resident, locations of a batch
 GP_MES_MAX_K, GP_MES_MAX_G = 64, 64   # samples of the minimum's value; trial values per gp_mes_logsurv call
 GP_ACQ_TIMES_FEAS = 0x200    # or-ed into a table scoring call's type: the scores are multiplied by the cached probability of feasibility
 GP_FEAS_MAX = 8
@@ -225,6 +226,11 @@ SIGNATURES = [
     ("gp_paths_table", ctypes.c_int, [_vp, ctypes.c_double, ctypes.c_double, c_double_p]),
     ("gp_paths_argbest", ctypes.c_int, [_vp, ctypes.c_double, ctypes.c_double, ctypes.c_int, c_int64_p, c_double_p]),
     ("gp_paths_rows", ctypes.c_int, [_vp, _vp, ctypes.c_int, _vp, ctypes.c_double, ctypes.c_double, _vp, _vp]),
+    ("gp_qei_set", ctypes.c_int, [_vp, c_double_p, ctypes.c_int, ctypes.c_int]),
+    ("gp_qei_info", ctypes.c_int, [_vp, c_int_p, c_int_p]),
+    ("gp_qei_stats", ctypes.c_int, [_vp, c_int64_p, c_int64_p]),
+    ("gp_qei_rows", ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double,
+                                   ctypes.c_double, _vp, _vp, _vp, _vp]),
 ]
 
 _lib = None
@@ -1331,6 +1337,52 @@ class Handle(object):
         if rc:
             check(self.lib, rc, "gp_paths_rows")
         return (out, dout) if grad else out
+
+    # -- joint expected improvement (include/gphip.h, gp_qei_*): a batch of q locations scored as a whole ---------------------------
+    qei_key = None      # whose base samples are resident (AcquisitionQEI's staleness check)
+
+    def qei_set(self, Z, key=None):
+        """Make the base samples ``Z`` [S, q] (standard normals) resident -- a copy; they survive every fit of the handle.
+        ``key`` is remembered as ``qei_key``."""
+        Z = as_f64(Z, 2)
+        self.qei_key = None
+        check(self.lib, self.lib.gp_qei_set(self.h, dptr(Z), Z.shape[0], Z.shape[1]), "gp_qei_set")
+        self.qei_key = key
+
+    def qei_info(self):
+        """(S, q) of the resident base samples, (0, 0) without."""
+        S, q = ctypes.c_int(0), ctypes.c_int(0)
+        check(self.lib, self.lib.gp_qei_info(self.h, ctypes.byref(S), ctypes.byref(q)), "gp_qei_info")
+        return S.value, q.value
+
+    def qei_stats(self):
+        """(calls, calls with a gradient) gp_qei_rows has answered on this handle."""
+        a, b = ctypes.c_int64(0), ctypes.c_int64(0)
+        check(self.lib, self.lib.gp_qei_stats(self.h, ctypes.byref(a), ctypes.byref(b)), "gp_qei_stats")
+        return a.value, b.value
+
+    def qei_rows(self, Xq, par=0.0, fmin=0.0, y_mean=0.0, y_std=1.0, include_noise=True, grad=False, posterior=False):
+        """The NEGATED joint expected improvement of the batch ``Xq`` [q, D] over the resident base samples (their leading q
+        columns); with ``grad`` its negated gradient [q, D] as well; with ``posterior`` also the joint mean [q] and covariance
+        [q, q] that were factored (de-normalised).  Returns the value, or a tuple (value[, gradient][, mean, cov]).  A pivot of the
+        covariance that is not positive raises ``np.linalg.LinAlgError`` (``.args[1]``: its 1-based row)."""
+        Xq = np.ascontiguousarray(Xq, dtype=np.float64)
+        if Xq.ndim != 2 or Xq.shape[1] != self.D:
+            raise ValueError("expected locations of shape [q, %d], got %s" % (self.D, Xq.shape))
+        q = Xq.shape[0]
+        out = np.empty(1)
+        dout = np.empty((q, self.D)) if grad else None
+        mean = np.empty(q) if posterior else None
+        cov = np.empty((q, q)) if posterior else None
+        rc = self.lib.gp_qei_rows(self.h, Xq.ctypes.data, q, int(bool(include_noise)), float(par), float(fmin), float(y_mean),
+                                  float(y_std), out.ctypes.data, dout.ctypes.data if grad else None,
+                                  mean.ctypes.data if posterior else None, cov.ctypes.data if posterior else None)
+        if rc > 0:
+            raise np.linalg.LinAlgError("gp_qei_rows: the batch's joint covariance is not positive definite at row %d" % rc, rc)
+        if rc:
+            check(self.lib, rc, "gp_qei_rows")
+        res = (out[0],) + ((dout,) if grad else ()) + ((mean, cov) if posterior else ())
+        return res if len(res) > 1 else res[0]
 
     # -- the mean function m(x) = x^T A + b of the exact GP (include/gphip.h, gp_mean_*) -----------------------------------
     def mean_set(self, A=None, b=None):

@@ -26,6 +26,7 @@ from .feasibility import FeasibilityModel
 from .entropy_search import AffineInvariantEnsembleSampler
 from .gpmodel import GPModel
 from .input_warped_gp import InputWarpedGPModel
+from .joint_ei import AcquisitionQEI, JointBatch
 from .parameterization import lbfgsb_lockstep, SCIPY_DEFAULT
 
 
@@ -393,7 +394,14 @@ class BayesianOptimization(object):
     features of the prior term) and ``sampler_seed`` minimises a sample of the posterior FUNCTION (``AcquisitionTS``, posterior
     paths).  'sequential' draws one fresh path per suggestion; 'thompson_sampling' with ``batch_size`` B draws B paths and
     returns the minimiser of each (``ThompsonPathsBatch``); 'local_penalization', a cost model and ``constraint_function`` raise
-    ``NotImplementedError``."""
+    ``NotImplementedError``.
+
+    Joint expected improvement (an addition): ``acquisition_type='qEI'`` with ``batch_size`` q (1 .. 8; more raises ``ValueError``)
+    and the keywords ``num_qei_samples`` (256 base samples) and ``sampler_seed`` scores and optimises the batch AS A WHOLE
+    (``AcquisitionQEI``; the evaluator is ``JointBatch``, whatever ``evaluator_type`` of 'sequential', None or 'joint' was given).
+    'local_penalization', 'thompson_sampling' and 'random' raise ``InvalidConfigError``: they build a batch point by point.
+    ``parallel_anchors=True`` is ignored for it: a batch already fills the wide pass over the inverse factor, and the starts'
+    L-BFGS runs go one after the other.  A cost model and ``constraint_function`` raise ``NotImplementedError``."""
 
     def __init__(self, f, domain=None, constraints=None, cost_withGradients=None, model_type='GP', X=None, Y=None,
                  initial_design_numdata=5, initial_design_type='random', acquisition_type='EI', normalize_Y=True,
@@ -406,9 +414,20 @@ class BayesianOptimization(object):
         if model_type == 'input_warped_GP' and evaluator_type == 'local_penalization' and batch_size > 1:
             # arguments_manager.py:32-34 (the penaliser's distances live in un-warped space)
             raise InvalidConfigError('local_penalization evaluator can only be used with GP models')
-        if evaluator_type not in ('sequential', 'local_penalization', 'thompson_sampling', 'random', None):
+        if evaluator_type not in ('sequential', 'local_penalization', 'thompson_sampling', 'random', 'joint', None):
             raise NotImplementedError("evaluator %r is outside the accelerated path" % evaluator_type)
+        joint = isinstance(acquisition, AcquisitionQEI) or (acquisition is None and acquisition_type == 'qEI')
+        if joint and evaluator_type not in ('sequential', 'joint', None):
+            raise InvalidConfigError("joint expected improvement optimises the batch as a whole: evaluator %r builds one point by "
+                                     "point (use 'sequential', None or 'joint')" % evaluator_type)
+        if evaluator_type == 'joint' and not joint:
+            raise InvalidConfigError("the 'joint' evaluator returns the batch acquisition_type='qEI' optimises")
+        if joint and not 1 <= int(batch_size) <= 8:
+            raise ValueError("joint expected improvement takes batches of 1 to 8 points, got batch_size=%r" % (batch_size,))
         constrained = constraint_function is not None or C is not None
+        if joint and constrained:
+            raise NotImplementedError("joint expected improvement (qEI) takes no black-box constraints: use acquisition_type 'EI' "
+                                      "or 'MPI' with constraint_function")
         if constrained and evaluator_type == 'local_penalization' and batch_size > 1:
             raise InvalidConfigError("local_penalization optimises penalised rows, which take no black-box constraints: use the "
                                      "'sequential', 'random' or 'thompson_sampling' evaluator with constraint_function")
@@ -480,6 +499,10 @@ class BayesianOptimization(object):
         elif acquisition_type == 'TS':
             self.acquisition = AcquisitionTS(self.model, self.space, self.acquisition_optimizer, cost_withGradients,
                                              num_features=kwargs.get('num_features', 1024), seed=kwargs.get('sampler_seed', None))
+        elif acquisition_type == 'qEI':
+            self.acquisition = AcquisitionQEI(self.model, self.space, self.acquisition_optimizer, batch_size=batch_size,
+                                              num_samples=kwargs.get('num_qei_samples', 256), jitter=jitter,
+                                              seed=kwargs.get('sampler_seed', None), cost_withGradients=cost_withGradients)
         elif acquisition_type == 'EI_MCMC':
             self.acquisition = AcquisitionEI_MCMC(self.model, self.space, self.acquisition_optimizer, cost_withGradients, jitter)
         elif acquisition_type == 'MPI_MCMC':
@@ -495,7 +518,9 @@ class BayesianOptimization(object):
         else:
             raise NotImplementedError("acquisition %r is outside the accelerated path" % acquisition_type)
         # arguments_manager.py:17-38 (evaluator_creator): local penalisation wraps the acquisition (LP.py)
-        if batch_size == 1 or evaluator_type == 'sequential':
+        if joint:
+            self.evaluator = JointBatch(self.acquisition, batch_size)      # the acquisition's rows ARE batches: always its own evaluator
+        elif batch_size == 1 or evaluator_type == 'sequential':
             self.evaluator = None                      # Sequential: one optimised point (arguments_manager.py:23-24)
         elif evaluator_type in ('random', None):
             self.evaluator = RandomBatch(self.acquisition, batch_size)

@@ -374,6 +374,16 @@ struct PathsState {
     PassOwner pass{1, "the path kernel"};   // completion of gp_paths_rows
 };
 
+// Joint expected improvement (api_qei.hip): the caller's base samples, in a buffer of the context's own, and what the joint step
+// leaves the closing pass.  The samples are standard normals that belong to no fit: no fit, parameter, data or append call touches
+// them (common random numbers across refits); they go with the handle.
+struct QeiState {
+    int S = 0, q = 0;          // samples and columns resident (0: none)
+    DevBuf<double> dZ;         // [q, S]: column-major, a column of the caller's Z contiguous
+    DevBuf<double> dState;     // QEI_STATE_DOUBLES: status, mbar, A (qei.hip)
+    long calls = 0, grad_calls = 0;   // gp_qei_rows calls answered since the context was created, and those with a gradient (gp_qei_stats)
+};
+
 struct gp_ctx {
     int device = 0;
     long lds_per_wg = 0;           // hipDeviceAttributeMaxSharedMemoryPerBlock of the device (gp_create)
@@ -537,6 +547,7 @@ struct gp_ctx {
     FeasState feas;     // the cached probability of feasibility of the flagged table entries (api_feas.hip)
     MesState mes;       // the samples of the minimum's value behind GP_ACQ_MES (api_mes.hip)
     PathsState paths;   // posterior function samples over the resident factor (api_paths.hip)
+    QeiState qei;       // the base samples of the joint expected improvement (api_qei.hip)
     bool dead = false;  // gp_shutdown ran: the device's streams are gone, only gp_destroy is still valid
 };
 
@@ -834,6 +845,7 @@ int train_values(gp_ctx *g);   // api_predict.hip: gp_fmin's quantity of every t
 // one fused pass of g -- posterior, and the acquisition aq when on -- put on the stream WITHOUT the wait: *r is the pass's
 // report, *arrivals what PassOwner::wait is owed.  The caller has several handles' passes of one device behind each other.
 bool rows_take_fused(gp_ctx *g, int64_t M);
+int rows_scratch(gp_ctx *g, RowsWork *w);   // the passes' partials over dRows, sized for a wide pass, and the owner made ready
 int rows_prepare(gp_ctx *g);   // inverse factor, scratch, owner: everything that may synchronise, ahead of the first pass
 void rows_enqueue(gp_ctx *g, const RowsX &rx, int include_noise, int want_grad, const RowsAcq &aq, PassReport *r, unsigned *arrivals);
 int check_lp(const LpSpec &lp);                     // transform 0 / 1, 0 <= nb <= GP_LP_MAX_NB, a batch where nb > 0

@@ -30,7 +30,7 @@ static bool rows_use_factor(gp_ctx *g) {
     return ++g->rows_calls_since_fit > g->Npad / GP_TILE / 6;
 }
 
-static int rows_scratch(gp_ctx *g, RowsWork *w) {
+int rows_scratch(gp_ctx *g, RowsWork *w) {
     const long Npad = g->Npad;
     const int nt = (int)(Npad / GP_TILE);
     const long nch = nt > 0 ? (nt - 1) / 8 + 1 : 1;

@@ -327,6 +327,8 @@ void launch_rows(hipStream_t s, const double *Li, long Npad, const RowsX &rx, co
 // the forward launch of launch_rows alone: w.wpart (and w.meanpart) of the pass, no finishing kernel, no arrival at the counter
 void launch_rows_forward(hipStream_t s, const double *Li, long Npad, const RowsX &rx, const KernParams &kp, const double *X, long N,
                          const double *alpha, const RowsWork &w, int nt_loads);
+// the backward launch alone, behind launch_rows_forward of M locations: w.bpart and w.vpart from w.wpart
+void launch_rows_backward(hipStream_t s, const double *Li, long Npad, int M, const RowsWork &w, int nt_loads);
 // the mean's gradient alone: dmdx [M, D] at r.out + 3 MV (one pass over the training points, no inverse factor)
 void launch_rows_mean_grad(hipStream_t s, const RowsX &rx, const KernParams &kp, const double *X, long N, const double *alpha,
                            const RowsWork &w, const PassReport &r, const RowsMean &mf = RowsMean{0, nullptr, nullptr});
@@ -373,6 +375,33 @@ inline unsigned paths_rows_grid(long N, int F) { return (unsigned)((N + PATHS_RO
 void launch_paths_rows(hipStream_t s, const PathsPrior &pp, const RowsX &rx, const PathsPick &pk, const KernParams &kp, const double *X,
                        long N, const double *V, long ldv, int want_grad, double y_mean, double y_std, double *gpart,
                        const PassReport &r);
+
+// ---- qei.hip: the joint expected improvement of q <= ROWS_WIDE_M locations behind the fused rows path's passes (api_qei.hip) ------------
+// result block (r.out): [value][status][mean q][cov q x q, row-major][dout q x D]; the ticket at r.out[ROWS_OUT_DOUBLES]
+#define QEI_MAX_S 4096
+#define QEI_OUT_VALUE 0
+#define QEI_OUT_STATUS 1
+#define QEI_OUT_MEAN 2
+#define QEI_OUT_COV (QEI_OUT_MEAN + ROWS_WIDE_M)
+#define QEI_OUT_GRAD (QEI_OUT_COV + ROWS_WIDE_M * ROWS_WIDE_M)
+// state (device, QEI_STATE_DOUBLES): what the joint step leaves the closing pass: [status][mbar q][A q x q], both for the NORMALISED model
+#define QEI_STATE_DOUBLES (1 + ROWS_WIDE_M + ROWS_WIDE_M * ROWS_WIDE_M)
+struct QeiArgs {
+    const double *Z;          // base samples on the device, COLUMN-major: entry (s, l) at Z[l * ldz + s]; a call of q locations reads
+    int S, ldz;               // the leading q columns
+    double par, fmin, y_mean, y_std;
+};
+// w_i . w_j for j <= i < M from w.wpart (laid out for rows_layout(M)): per 64 training rows one partial at w.gpart, in the order of
+// the finishing kernel's value call
+void launch_qei_gram(hipStream_t s, int M, long N, long Npad, const RowsWork &w);
+// one workgroup: m, Sigma, its factor, the samples, the adjoint; value / mean / cov into r.out, mbar and A into state.  A pivot that
+// is not positive or not finite: its 1-based row into both status words and nothing else.  want_grad = 0: the ticket as well.
+void launch_qei_joint(hipStream_t s, const RowsX &rx, const KernParams &kp, long N, long Npad, const RowsWork &w, double kss,
+                      double noise_add, const QeiArgs &qa, int want_grad, double *state, const PassReport &r);
+// the closing pass over the training points: rows_finish_grid(N) workgroups arrive at the pass's counter, the last one writes the
+// negated gradient [M, D] at r.out + QEI_OUT_GRAD (status 0) and the ticket (always)
+void launch_qei_close(hipStream_t s, const RowsX &rx, const KernParams &kp, const double *X, long N, long Npad, const double *alpha,
+                      const RowsWork &w, const double *state, const PassReport &r);
 
 // ---- ens_rows.hip: the same passes over an ensemble of S members, the member as a grid dimension --------------------------------
 #define ENS_ROWS_RB 32                       // rows of the tile per workgroup: what rows_block_height gives every matrix the ensemble takes

@@ -333,6 +333,30 @@ void launch_rows_forward(hipStream_t s, const double *Li, long Npad, const RowsX
     launch_rows_any(s, Li, Npad, rx, kp, X, N, alpha, 0, 0.0, 0.0, RowsAcq{}, w, PassReport{}, nt_loads, true, RowsMean{0, nullptr, nullptr});
 }
 
+// the backward launch alone, over the w.wpart a forward launch of M locations left: w.bpart (and w.vpart), the instances launch_rows
+// runs for that M and that matrix (qei.hip finishes the pass)
+void launch_rows_backward(hipStream_t s, const double *Li, long Npad, int M, const RowsWork &w, int nt_loads) {
+    const int nt = (int)(Npad / GP_TILE);
+    const bool low = rows_block_height(nt) == 32;
+#define RW_BK(MV, RB, NT)                                                                                                              \
+    GP_LAUNCH((rows_backward_kernel<MV, RB, NT>), dim3((unsigned)rows_tiles(nt) * (GP_TILE / RB)), dim3(256), 0, s, Li, Npad, w.wpart, Npad, M, \
+              w.bpart, w.vpart)
+    if (M == 1) {
+        if (low) RW_BK(1, 32, false);
+        else if (nt_loads) RW_BK(1, GP_TILE, true);
+        else RW_BK(1, GP_TILE, false);
+    } else if (M <= ROWS_MAX_M) {
+        if (low) RW_BK(ROWS_MAX_M, 32, false);
+        else if (nt_loads) RW_BK(ROWS_MAX_M, GP_TILE, true);
+        else RW_BK(ROWS_MAX_M, GP_TILE, false);
+    } else {
+        if (low) RW_BK(ROWS_WIDE_M, 32, false);
+        else if (nt_loads) RW_BK(ROWS_WIDE_M, GP_TILE, true);
+        else RW_BK(ROWS_WIDE_M, GP_TILE, false);
+    }
+#undef RW_BK
+}
+
 // ---- Li = (L^-T)^T: lower triangular, explicit zeros above the diagonal; and back -------------------------------------------------------
 // mode 0: dst lower <- transpose of src upper;  mode 1: dst upper <- transpose of src lower.  32 x 32 LDS tiles.
 __global__ __launch_bounds__(256) void transpose_tri_kernel(double *dst, const double *src, long n, int mode) {

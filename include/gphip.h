@@ -1048,6 +1048,51 @@ int gp_paths_table(gp_t *gp, double y_mean, double y_std, double *out);
 int gp_paths_argbest(gp_t *gp, double y_mean, double y_std, int sense, int64_t *idx, double *val);
 int gp_paths_rows(gp_t *gp, const double *Xs, int M, const int *path, double y_mean, double y_std, double *out, double *dout);
 
+/* ---- joint (batch) expected improvement qEI -----------------------------------------------------------------------------------
+ * (Ginsbourger, Le Riche & Carraro 2010; Wang, Clark, Liu & Frazier 2016; Wilson, Hutter & Deisenroth, NeurIPS 2018.)  A batch of
+ * q locations is scored as a whole,
+ *     qEI(x_1 .. x_q) = E[max(0, max_j (fmin - par - y_j))],
+ * over their JOINT posterior, by Monte Carlo with fixed base samples: y_s = m + C z_s, C C^T = Sigma (lower, rows in the caller's
+ * order), z_s the first q entries of row s of Z; I_sj = fmin - par - y_sj, j*(s) = argmax_j I_sj (the lowest j on a tie), sample
+ * s active when I_{s j*} > 0, qEI = (1 / S) sum_active I_{s j*}.  With Z fixed this is a deterministic function of the q D
+ * coordinates with the gradient
+ *     d qEI / d x_i = mbar_i dm_i/dx_i + sum_j A_ij dk(x_i, x_j)/dx_i - J_i^T (sum_j A_ij beta_j),
+ * mbar_j = -(1 / S) #{active s: j*(s) = j}, Cbar_jl = -(1 / S) sum_{active s, j*(s) = j} z_sl (l <= j), P = tril(C^T Cbar) with its
+ * diagonal halved, Sigma_bar = sym(C^-T P C^-1), A = 2 Sigma_bar, beta_j = Ky^-1 k(X, x_j), J_i the [N, D] input Jacobian of
+ * k(X, x_i).  The posterior is gp_predict_rows': m_i = k_i^T alpha, Sigma_ij = k(x_i, x_j) - w_i . w_j with w_i = L^-1 k_i, the
+ * likelihood noise on the diagonal with include_noise; m and Sigma de-normalised (y_std m + y_mean, y_std^2 Sigma) before the
+ * factorisation, as gp_acq_rows de-normalises mean and variance (no clip: a variance that is not positive ends the call, below).
+ *
+ * gp_qei_set: Z [S, q] standard normals, 1 <= S <= GP_QEI_MAX_S, 1 <= q <= GP_QEI_MAX_Q, made resident (a copy).  They belong to
+ * no fit: gp_fit, gp_set_params, gp_set_data and gp_append leave them (common random numbers across refits); they go with the
+ * handle.  GP_ERR_ARG: a null pointer, S or q out of range, a sample that is not finite.  gp_qei_info: *S and *q resident, 0 and 0
+ * without.  gp_qei_stats: gp_qei_rows calls answered since the context was created, and those of them with a gradient
+ * (gp_rows_stats and gp_rows_pass_stats count what they counted: these calls do not move them).
+ *
+ * gp_qei_rows: Xq [q, D] by value, q up to the resident q (a smaller q reads the leading q columns of Z: the same bits as a
+ * handle given Z[:, :q]).  out[0] = -qEI and, when dout is given, dout [q, D] = -d qEI / d x (the sign of gp_acq / gp_acq_grad);
+ * mean [q] and cov [q, q] (row-major, de-normalised, the matrix that was factored) when given; dout, mean, cov may be NULL.  The
+ * diagonal of cov at y_std = 1 is gp_predict_rows' variance of a value call, bit for bit.  Launches: the fused rows path's forward
+ * pass over the inverse factor for all q locations at once (pass layouts 1, 4 and 8 as there); the Gram of the w_i per 64
+ * training rows; ONE workgroup that assembles m and Sigma, factors it, walks the samples (thread t takes s = t, t + 256, ... in
+ * order, the threads' sums are added in thread order within groups of 64, the groups in order) and forms mbar and A; for a gradient the rows path's backward pass and a
+ * closing pass over the training points that mixes A into the beta_j -- t_i = sum_j A_ij beta_j, so the q x q adjoint costs no
+ * further pass over the factor -- and whose last workgroup writes the results into the pinned block.  A value call skips the
+ * last two.  No copy commands either side of the launches, no atomics but the arrival counter: repeated calls are bitwise equal,
+ * and the value has the same bits with and without dout.  The inverse factor is built at the first call after a fit where it
+ * does not exist.  Always true fp64 (option "emulate_fp64" does not reach it).
+ * Returns: 0; a POSITIVE value r when pivot r (1-based row of Sigma, caller's order) is not positive or not finite -- coincident
+ * locations without noise: nothing is written; GP_ERR_STATE: no fit, no resident samples, P != 1, a Gower kernel, an output warp
+ * or a mean function in force; GP_ERR_ARG: a null gp / Xq / out, q outside 1 .. resident q, q D > 128 coordinates, a location,
+ * par, fmin or y_mean that is not finite, a y_std that is not positive and finite.  A refused call launches and changes nothing. */
+#define GP_QEI_MAX_S 4096 /* base samples resident at a time */
+#define GP_QEI_MAX_Q 8    /* locations of a batch */
+int gp_qei_set(gp_t *gp, const double *Z, int S, int q);
+int gp_qei_info(gp_t *gp, int *S, int *q);
+int gp_qei_stats(gp_t *gp, int64_t *calls, int64_t *grad_calls);
+int gp_qei_rows(gp_t *gp, const double *Xq, int q, int include_noise, double par, double fmin, double y_mean, double y_std,
+                double *out, double *dout, double *mean, double *cov);
+
 #ifdef __cplusplus
 }
 #endif
