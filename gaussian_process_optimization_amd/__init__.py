@@ -48,6 +48,9 @@ from . import entropy_search
 from .entropy_search import McmcSampler, AffineInvariantEnsembleSampler
 from .bayesian_optimization import BayesianOptimization, Design_space, AcquisitionOptimizer
 from .sharded import ShardedCandidates, merge_best
+from . import multi_objective
+from .multi_objective import (AcquisitionEHVI, MultiObjectiveBayesianOptimization, pareto_front, hypervolume,
+                              nondominated_cells)
 
 # namespaces named like the reference packages
 models = _types.SimpleNamespace(GPRegression=GPRegression, SparseGPRegression=SparseGPRegression, GPModel=GPModel, GPModel_MCMC=GPModel_MCMC, InputWarpedGP=InputWarpedGP,
@@ -61,4 +64,6 @@ __all__ = ["kern", "mappings", "models", "methods", "likelihoods", "acquisitions
            "InputWarpedGP", "InputWarpedGPModel", "input_warping", "WarpedGP", "WarpedGPModel", "warping_functions",
            "AcquisitionEI", "AcquisitionLCB", "AcquisitionMPI", "AcquisitionBase", "AcquisitionLP",
            "LocalPenalization", "estimate_L", "BayesianOptimization",
-           "Design_space", "AcquisitionOptimizer", "ShardedCandidates", "merge_best", "Standardize", "cost", "CostModel", "feasibility", "FeasibilityModel"]
+           "Design_space", "AcquisitionOptimizer", "ShardedCandidates", "merge_best", "Standardize", "cost", "CostModel", "feasibility", "FeasibilityModel",
+           "multi_objective", "AcquisitionEHVI", "MultiObjectiveBayesianOptimization", "pareto_front", "hypervolume",
+           "nondominated_cells"]

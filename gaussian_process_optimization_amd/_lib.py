@@ -27,6 +27,7 @@ GP_QEI_MAX_S, GP_QEI_MAX_Q = 4096, 8   # joint expected improvement: base sample
 GP_MES_MAX_K, GP_MES_MAX_G = 64, 64   # samples of the minimum's value; trial values per gp_mes_logsurv call
 GP_ACQ_TIMES_FEAS = 0x200    # or-ed into a table scoring call's type: the scores are multiplied by the cached probability of feasibility
 GP_FEAS_MAX = 8
+GP_EHVI_MAX_OBJ, GP_EHVI_MAX_LEVELS, GP_EHVI_MAX_CELLS = 3, 256, 32768   # expected hypervolume improvement: objectives, levels per objective, cells
 GP_ERR_ARG, GP_ERR_HIP, GP_ERR_STATE, GP_ERR_RCCL, GP_ERR_NOT_PD_DIAG = -1, -2, -3, -4, -5
 
 # every symbol include/gphip.h declares: (name, restype, argtypes)
@@ -231,6 +232,14 @@ SIGNATURES = [
     ("gp_qei_stats", ctypes.c_int, [_vp, c_int64_p, c_int64_p]),
     ("gp_qei_rows", ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double,
                                    ctypes.c_double, _vp, _vp, _vp, _vp]),
+    ("gp_ehvi_set", ctypes.c_int, [_vp, ctypes.c_int, c_double_p, c_int_p, c_int_p, c_int_p, ctypes.c_int]),
+    ("gp_ehvi_info", ctypes.c_int, [_vp, c_int_p, c_int_p]),
+    ("gp_ehvi_table", ctypes.c_int, [_vp, ctypes.POINTER(_vp), ctypes.c_int, c_double_p, c_double_p, _vp]),
+    ("gp_ehvi_argbest", ctypes.c_int, [_vp, ctypes.POINTER(_vp), ctypes.c_int, c_double_p, c_double_p, ctypes.c_int, c_int64_p,
+                                       ctypes.c_int, c_int64_p, c_double_p]),
+    ("gp_ehvi_topk", ctypes.c_int, [_vp, ctypes.POINTER(_vp), ctypes.c_int, c_double_p, c_double_p, ctypes.c_int, ctypes.c_int,
+                                    c_int64_p, c_double_p]),
+    ("gp_ehvi_rows", ctypes.c_int, [_vp, ctypes.POINTER(_vp), ctypes.c_int, c_double_p, c_double_p, _vp, ctypes.c_int64, _vp, _vp]),
 ]
 
 _lib = None
@@ -372,6 +381,91 @@ class FeasPack(object):
         if rc:
             check(self.lib, rc, "gp_feas_rows")
         return (logF, dlogF) if grad else logF
+
+
+class EhviPack(object):
+    """The objective side of an expected-hypervolume-improvement call (``gp_ehvi_*``): K = 2 or 3 handles, the first of which is
+    scored and owns the cell decomposition, with their output normalisers.  Holds the Handle objects, so none is collected under a
+    call."""
+
+    def __init__(self, handles, y_mean, y_std):
+        self.handles = list(handles)
+        self.K = len(self.handles)
+        if not 2 <= self.K <= GP_EHVI_MAX_OBJ:
+            raise ValueError("between 2 and %d objectives, got %d" % (GP_EHVI_MAX_OBJ, self.K))
+        self.y_mean = as_f64(np.ravel(y_mean), 1)
+        self.y_std = as_f64(np.ravel(y_std), 1)
+        if not (self.y_mean.size == self.y_std.size == self.K):
+            raise ValueError("y_mean and y_std take one entry per objective")
+        self.scored = self.handles[0]
+        self.D = self.scored.D
+        self.lib = self.scored.lib
+        self.others = (_vp * (self.K - 1))(*[h.h for h in self.handles[1:]])
+        self.args = (self.scored.h, self.others, self.K, dptr(self.y_mean), dptr(self.y_std))
+
+    def set_cells(self, levels, cell_lo, cell_hi):
+        """Make the decomposition resident on the scored handle (gp_ehvi_set): ``levels`` a list of K arrays (entry 0 of each
+        stands for -inf), ``cell_lo`` / ``cell_hi`` [C, K] indices into them."""
+        levels = [as_f64(np.ravel(l), 1) for l in levels]
+        nlev = np.array([l.size for l in levels], dtype=np.intc)
+        flat = as_f64(np.concatenate(levels), 1)
+        lo = np.ascontiguousarray(np.atleast_2d(cell_lo), dtype=np.intc)
+        hi = np.ascontiguousarray(np.atleast_2d(cell_hi), dtype=np.intc)
+        if len(levels) != self.K or lo.shape != hi.shape or lo.ndim != 2 or lo.shape[1] != self.K:
+            raise ValueError("expected %d level arrays and cells [C, %d], got %d and %s, %s"
+                             % (self.K, self.K, len(levels), lo.shape, hi.shape))
+        check(self.lib, self.lib.gp_ehvi_set(self.scored.h, self.K, dptr(flat), nlev.ctypes.data_as(c_int_p),
+                                             lo.ctypes.data_as(c_int_p), hi.ctypes.data_as(c_int_p), lo.shape[0]), "gp_ehvi_set")
+
+    def clear(self):
+        check(self.lib, self.lib.gp_ehvi_set(self.scored.h, 0, None, None, None, None, 0), "gp_ehvi_set")
+
+    def info(self):
+        K, C = ctypes.c_int(0), ctypes.c_int(0)
+        check(self.lib, self.lib.gp_ehvi_info(self.scored.h, ctypes.byref(K), ctypes.byref(C)), "gp_ehvi_info")
+        return K.value, C.value
+
+    def _tables_moved(self):
+        for h in self.handles[1:]:   # their resident tables are the scored handle's now
+            h.M = self.scored.M
+            h.feas_key = None
+
+    def table(self):
+        """-EHVI [M, 1] over the scored handle's resident candidates (gp_ehvi_table)."""
+        out = np.empty((self.scored.M, 1))
+        check(self.lib, self.lib.gp_ehvi_table(*(self.args + (out.ctypes.data,))), "gp_ehvi_table")
+        self._tables_moved()
+        return out
+
+    def argbest(self, sense, exclude=()):
+        ex = np.asarray(list(exclude), dtype=np.int64)
+        idx, val = ctypes.c_int64(), ctypes.c_double()
+        check(self.lib, self.lib.gp_ehvi_argbest(*(self.args + (int(sense), ex.ctypes.data_as(c_int64_p), int(ex.size),
+                                                                ctypes.byref(idx), ctypes.byref(val)))), "gp_ehvi_argbest")
+        self._tables_moved()
+        return idx.value, val.value
+
+    def topk(self, sense, k):
+        idx = np.empty(k, dtype=np.int64)
+        val = np.empty(k)
+        check(self.lib, self.lib.gp_ehvi_topk(*(self.args + (int(sense), int(k), idx.ctypes.data_as(c_int64_p), dptr(val)))),
+              "gp_ehvi_topk")
+        self._tables_moved()
+        return idx, val
+
+    def rows(self, Xs, grad=False):
+        """-EHVI [M, 1] at the rows of ``Xs`` and, with ``grad``, its x-gradient [M, D]: every handle's fused pass, the fold and
+        one drain in ONE call (gp_ehvi_rows)."""
+        Xs = np.ascontiguousarray(Xs, dtype=np.float64)
+        if Xs.ndim != 2 or Xs.shape[1] != self.D:
+            raise ValueError("expected locations [M, %d], got shape %s" % (self.D, Xs.shape))
+        M = Xs.shape[0]
+        out = np.empty((M, 1))
+        dout = np.empty((M, self.D)) if grad else None
+        rc = self.lib.gp_ehvi_rows(*(self.args + (Xs.ctypes.data, M, out.ctypes.data, dout.ctypes.data if grad else None)))
+        if rc:
+            check(self.lib, rc, "gp_ehvi_rows")
+        return (out, dout) if grad else out
 
 
 class Handle(object):

@@ -1020,6 +1020,8 @@ class AcquisitionLP(AcquisitionBase):
         if isinstance(acquisition, AcquisitionTS):
             raise NotImplementedError("Thompson sampling spreads a batch by drawing one path per element: it is not penalised "
                                       "(use the 'thompson_sampling' evaluator)")
+        if getattr(acquisition, "_takes_no_penaliser", None):      # (multi_objective.AcquisitionEHVI: the sentence why)
+            raise NotImplementedError(acquisition._takes_no_penaliser)
         super().__init__(model, space, optimizer)
         self.acq = acquisition
         kind = str(transform).lower()

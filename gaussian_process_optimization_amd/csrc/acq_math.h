@@ -78,6 +78,29 @@ __device__ __forceinline__ double feas_grad(double lam, double z, double s, doub
     return lam * (-dm - z * ds) / s;
 }
 
+// ---- expected hypervolume improvement (Emmerich et al. 2011; Yang et al. 2019) ---------------------------------------------------
+// One coordinate c of the cell decomposition against one objective at a location: (mean, var) of the objective GP's NORMALISED
+// posterior, (y_mean, y_std) its output normaliser, un-normalised and clipped exactly as acq_terms does.  z = (c - m) / s,
+//   Psi = s (z Phi(z) + phi(z))   -- EI with incumbent c and no jitter: d Psi / dm = -Phi, d Psi / ds = phi --
+// and c = -inf (index 0 of every level array) yields zeros.  No product is contracted into an fma: the bits are those of the
+// operations as written, whatever the surrounding kernel.
+__device__ __forceinline__ void ehvi_level(double mean, double var, double y_mean, double y_std, double c, double &Psi, double &Phi,
+                                           double &phi, double &s) {
+#pragma clang fp contract(off)
+    const double m = mean * y_std + y_mean;
+    double v = var * (y_std * y_std);
+    v = (v < 1e-10) ? 1e-10 : v;
+    s = sqrt(v);
+    if (c == -INFINITY) {
+        Psi = Phi = phi = 0.0;
+        return;
+    }
+    const double z = (c - m) / s;
+    phi = exp(-0.5 * z * z) / 2.50662827463100050241576528481105;
+    Phi = 0.5 * erfc(-z / 1.41421356237309504880168872420970);
+    Psi = s * (z * Phi + phi);
+}
+
 // ---- max-value entropy search (Wang & Jegelka, ICML 2017), mirrored for a minimum ------------------------------------------------
 // h(g) = g lambda(g) / 2 - log Phi(g) and h'(g) = -(lambda / 2) B(g), B = 1 + g^2 + g lambda, lambda = phi / Phi.
 // g > -20: log Phi by gp_log_ndtr, lambda = exp(-g^2 / 2 - log(2 pi) / 2 - log Phi) in log space as feas_terms forms it, h and B

@@ -42,6 +42,8 @@ int check_cons(const gp_ctx *gp, gp_t *const *cons, int K, const double *bound, 
     return 0;
 }
 
+}   // namespace
+
 // the table posterior of handle c over M locations already in its dXs: mean / var with noise and (grad) dDm / dDv, on the device
 int table_posterior(gp_ctx *c, bool grad) {
     int rc;
@@ -51,7 +53,6 @@ int table_posterior(gp_ctx *c, bool grad) {
         if ((rc = run_predict(c, 1))) return rc;
     return 0;
 }
-}   // namespace
 
 void feas_apply(gp_ctx *g, bool pof, double *acq) { launch_feas_apply(g->s, g->feas.dTabLogF, g->M, pof ? 1 : 0, acq); }
 

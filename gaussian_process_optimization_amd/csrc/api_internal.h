@@ -333,6 +333,18 @@ struct FeasState {
 };
 static_assert(GP_FEAS_MAX == FEAS_MAX_K, "the kernels' argument takes GP_FEAS_MAX constraints");
 
+// Expected hypervolume improvement (api_ehvi.hip): the cell decomposition of the region the observed Pareto front does not
+// dominate, on the SCORED handle (objective 0) -- K level arrays behind each other and the cells' packed index pairs, as EhviCells
+// (gphip_internal.h) hands them to the kernels.  K > 0 while one is resident.  Raw objective units: no fit, data or candidate call
+// touches it.
+struct EhviState {
+    int K = 0, C = 0;
+    int L[EHVI_MAX_K] = {0, 0, 0}, off[EHVI_MAX_K] = {0, 0, 0};
+    DevBuf<double> dLevels;          // [sum_k L[k]]
+    DevBuf<unsigned int> dCells;     // [C, K]: lo | hi << 16
+};
+static_assert(GP_EHVI_MAX_OBJ == EHVI_MAX_K && GP_EHVI_MAX_LEVELS == EHVI_MAX_L, "the kernels' LDS table takes the public caps");
+
 // The affine mean function m(x) = x^T A + b of the exact GP (api_mean.hip): a snapshot of the mapping's parameters in a buffer of
 // the context's own.  While one is resident dYraw keeps the targets gp_set_data brought (the output warp's buffer and convention)
 // and dY holds the residuals Y - m(X) every fit route factors against; `stale` while dY still has to be rebuilt from them
@@ -545,6 +557,7 @@ struct gp_ctx {
     CostState cost;     // the cost surface of the flagged scoring calls (api_cost.hip)
     MeanState mean;     // the mean function (api_mean.hip)
     FeasState feas;     // the cached probability of feasibility of the flagged table entries (api_feas.hip)
+    EhviState ehvi;     // the cell decomposition behind the expected hypervolume improvement (api_ehvi.hip)
     MesState mes;       // the samples of the minimum's value behind GP_ACQ_MES (api_mes.hip)
     PathsState paths;   // posterior function samples over the resident factor (api_paths.hip)
     QeiState qei;       // the base samples of the joint expected improvement (api_qei.hip)
@@ -840,6 +853,8 @@ int cost_divide(gp_ctx *g, const double *X, long M, bool grad, double *acq, doub
 void cost_divide_block(gp_ctx *g, const RowsX &rx, bool grad, double *blk, int MV);
 // api_feas.hip.  feas_apply: acq [M] of the resident candidates times exp of the cached log F (pof: -exp alone), on the stream
 void feas_apply(gp_ctx *g, bool pof, double *acq);
+// the table posterior of handle c over the locations already in its dXs: mean / var with noise and (grad) dDm / dDv, not drained
+int table_posterior(gp_ctx *c, bool grad);
 int train_values(gp_ctx *g);   // api_predict.hip: gp_fmin's quantity of every training row into dMu [N], not drained
 // api_rows.hip: whether an M-location call of g takes the fused route now (counts towards the inverse factor's build policy), and
 // one fused pass of g -- posterior, and the acquisition aq when on -- put on the stream WITHOUT the wait: *r is the pass's

@@ -622,6 +622,29 @@ void launch_feas_rows(hipStream_t s, const FeasRows &fr, int M, int D, int grad,
                       double *dlogF);
 void launch_feas_gather(hipStream_t s, const double *v, const long long *rows, long n, double *out);   // out[i] = v[rows[i]]
 
+// ---- ehvi.hip: expected hypervolume improvement of K independent objective GPs over a cell decomposition -------------------------
+#define EHVI_MAX_K 3        // objectives (GP_EHVI_MAX_OBJ of the public header)
+#define EHVI_MAX_L 256      // levels per objective (GP_EHVI_MAX_LEVELS)
+#define EHVI_THREADS 256    // one workgroup of four waves per location
+// The decomposition on the device: objective k's L[k] levels at levels + off[k] (entry 0 is -inf), and C cells of K words each,
+// word [c * K + k] = lo | hi << 16 with lo < hi indices into objective k's levels
+struct EhviCells {
+    int K, C;
+    int L[EHVI_MAX_K], off[EHVI_MAX_K];
+    const double *levels;
+    const unsigned int *cells;
+};
+// objective k's normalised posterior at the locations -- mean / var [M], dm / dv [M, D] (read with grad only), on the device or in
+// a pinned result block -- and its output normaliser
+struct EhviRows {
+    const double *mean[EHVI_MAX_K], *var[EHVI_MAX_K], *dm[EHVI_MAX_K], *dv[EHVI_MAX_K];
+    double y_mean[EHVI_MAX_K], y_std[EHVI_MAX_K];
+};
+// neg [M] <- -EHVI over a table's posteriors, one workgroup per row
+void launch_ehvi_table(hipStream_t s, const EhviCells &ec, const EhviRows &er, long M, double *neg);
+// M locations, one workgroup each: neg [M] <- -EHVI and (grad) dneg [M, D] <- -d EHVI / dx.  The same device routine as the table's
+void launch_ehvi_rows(hipStream_t s, const EhviCells &ec, const EhviRows &er, int M, int D, int grad, double *neg, double *dneg);
+
 // ---- rns.hip: fp64-equivalent contraction on the int8 matrix cores (option "emulate_fp64") -----------------------------
 #define GP_RNS_T 14
 #define GP_RNS_KMAX 8192   // longest contraction (bytes) one residue launch may take: see rns_reduce_f in rns.hip

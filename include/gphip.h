@@ -1093,6 +1093,54 @@ int gp_qei_stats(gp_t *gp, int64_t *calls, int64_t *grad_calls);
 int gp_qei_rows(gp_t *gp, const double *Xq, int q, int include_noise, double par, double fmin, double y_mean, double y_std,
                 double *out, double *dout, double *mean, double *cov);
 
+/* ---- multi-objective: expected hypervolume improvement (Emmerich et al. 2011; Yang et al. 2019) ---------------------------------
+ * K = 2 or 3 objectives, all minimised, each modelled by an exact GP on a handle of its own (independent objectives).  With the
+ * region of (-inf, r] that the observed Pareto front does not dominate cut into C axis-parallel cells [l_c, u_c] (l_ck = -inf
+ * allowed),
+ *     EHVI(x) = sum_c prod_k (Psi_k(u_ck) - Psi_k(l_ck)),   Psi_k(c) = s_k (z Phi(z) + phi(z)),  z = (c - m_k) / s_k,  Psi_k(-inf) = 0,
+ * m_k / s_k objective k's predictive mean and standard deviation at x, un-normalised by (y_mean[k], y_std[k]) and clipped at
+ * 1e-10 as every rule here, likelihood noise included.  Psi is EI with incumbent c and no jitter: d Psi / dm = -Phi, d Psi / ds = phi.
+ *
+ * The decomposition is the caller's (multi_objective.nondominated_cells builds it) and lives on the SCORED handle, objective 0:
+ * gp_ehvi_set copies it to the device.  levels: objective k's nlev[k] coordinates, the K arrays behind each other; entry 0 of each
+ * is -inf (read as such whatever is stored there), the others finite and increasing, the last one r_k.  cell_lo / cell_hi [C, K]:
+ * indices into objective k's levels, lo < hi.  The values are in raw objective units, so the state survives refits; K = 0 and
+ * gp_destroy drop it.  GP_ERR_ARG: K outside 2 .. GP_EHVI_MAX_OBJ (0 clears), nlev[k] outside 2 .. GP_EHVI_MAX_LEVELS, C outside
+ * 1 .. GP_EHVI_MAX_CELLS, levels not finite or not increasing above index 0, an index out of range, lo >= hi.
+ * gp_ehvi_info: *K and *C, both 0 when there is none.
+ *
+ * `others` are the K - 1 handles of objectives 1 .. K - 1; y_mean / y_std [K] the output normalisers, objective 0 first.
+ * GP_ERR_STATE: no gp_ehvi_set, a handle without a fit (the table entries: no resident candidates on gp).  GP_ERR_ARG: a K that
+ * differs from the state's, a handle listed twice or equal to gp, another device or another D, P != 1, a sparse fit, an ensemble or
+ * an output warp on any handle, a y_mean that is not finite, a y_std that is not positive and finite.
+ *
+ * gp_ehvi_table: -EHVI over gp's resident candidates into gp's score table, and into out [M] when given.  The table goes to the
+ * other handles device to device (it is their resident table afterwards, as after gp_feas_table); K table posteriors, then ONE
+ * launch with one workgroup per row.  gp_ehvi_argbest / gp_ehvi_topk: the same, then the selector of gp_acq_argbest /
+ * gp_acq_topk (lowest index among equal scores; sense -1 picks the largest EHVI).
+ * gp_ehvi_rows: out [M] = -EHVI and, when dout is given, dout [M, D] = -d EHVI / dx at M >= 1 locations Xs [M, D], the
+ * acquisition optimiser's call.  Groups of up to eight locations, passes of four where M D > 128; per pass every handle's fused
+ * one-location pass, the fold (one workgroup per location), then the owners' waits: one drain, no host round trip in between.  A
+ * handle that cannot take the fused route goes through its table posterior over the group (its resident table is the group's
+ * locations afterwards) and is folded from its device buffers.
+ * A location's bits do not depend on its company, and the value is the same bits with and without dout (the posterior behind a
+ * value-only call is the gradient call's, backward launch included; the table entry's scores agree with it to rounding, and bit
+ * for bit when both fold the same posterior):
+ * one device routine serves both kernels -- the K L levels' Psi / Phi / phi once into LDS, thread t takes cells t, t + 256, ... in
+ * order, the threads' sums meet in a reduction of fixed shape, no atomics. */
+#define GP_EHVI_MAX_OBJ 3
+#define GP_EHVI_MAX_LEVELS 256
+#define GP_EHVI_MAX_CELLS 32768
+int gp_ehvi_set(gp_t *gp, int K, const double *levels, const int *nlev, const int *cell_lo, const int *cell_hi, int C);
+int gp_ehvi_info(gp_t *gp, int *K, int *C);
+int gp_ehvi_table(gp_t *gp, gp_t *const *others, int K, const double *y_mean, const double *y_std, double *out);
+int gp_ehvi_argbest(gp_t *gp, gp_t *const *others, int K, const double *y_mean, const double *y_std, int sense,
+                    const int64_t *exclude, int nex, int64_t *idx, double *val);
+int gp_ehvi_topk(gp_t *gp, gp_t *const *others, int K, const double *y_mean, const double *y_std, int sense, int k, int64_t *idx,
+                 double *val);
+int gp_ehvi_rows(gp_t *gp, gp_t *const *others, int K, const double *y_mean, const double *y_std, const double *Xs, int64_t M,
+                 double *out, double *dout);
+
 #ifdef __cplusplus
 }
 #endif
