@@ -71,7 +71,7 @@ def family(name, variance, r):
 def surface(name, variance, ls, Xc, alpha, shift, scale, Xs, block=64):
     """(logc [M], dlogc [M, D], bound_logc [M], bound_dlogc [M, D], sum_abs [M]) in long double; ``ls`` [D] (isotropic: repeated).
     sum_abs = |scale| sum_j |alpha_j k_j|, the scale of the issue's bound."""
-    Xc, Xs = np.asarray(Xc, dtype=np.float64), np.asarray(Xs, dtype=np.float64)
+    Xc, Xs = np.asarray(Xc), np.asarray(Xs)                          # (doubles, or long doubles as they are: tests/_domain_cases.py)
     l = np.asarray(ls, dtype=np.float64).astype(T)
     al = np.asarray(alpha, dtype=np.float64).astype(T)
     Nc, D = Xc.shape
