@@ -24,6 +24,7 @@ GP_ACQ_POF = 3               # the rule whose value is 1: valid only with GP_ACQ
 GP_ACQ_MES = 4               # max-value entropy search over the handle's resident samples of the minimum's value (gp_mes_set)
 GP_PATHS_MAX_S, GP_PATHS_MAX_F, GP_PATHS_MAX_ROWS = 64, 4096, 8   # posterior paths: paths, features, locations per rows call
 GP_QEI_MAX_S, GP_QEI_MAX_Q = 4096, 8   # joint expected improvement: base samples resident, locations of a batch
+GP_KG_MAX_A = 256                      # knowledge gradient: discretisation points resident
 GP_MES_MAX_K, GP_MES_MAX_G = 64, 64   # samples of the minimum's value; trial values per gp_mes_logsurv call
 GP_ACQ_TIMES_FEAS = 0x200    # or-ed into a table scoring call's type: the scores are multiplied by the cached probability of feasibility
 GP_FEAS_MAX = 8
@@ -227,6 +228,12 @@ SIGNATURES = [
     ("gp_paths_table", ctypes.c_int, [_vp, ctypes.c_double, ctypes.c_double, c_double_p]),
     ("gp_paths_argbest", ctypes.c_int, [_vp, ctypes.c_double, ctypes.c_double, ctypes.c_int, c_int64_p, c_double_p]),
     ("gp_paths_rows", ctypes.c_int, [_vp, _vp, ctypes.c_int, _vp, ctypes.c_double, ctypes.c_double, _vp, _vp]),
+    ("gp_kg_set_points", ctypes.c_int, [_vp, c_double_p, ctypes.c_int, ctypes.c_double, ctypes.c_double, _vp]),
+    ("gp_kg_info", ctypes.c_int, [_vp, c_int_p]),
+    ("gp_kg_acq", ctypes.c_int, [_vp, ctypes.c_double, c_double_p]),
+    ("gp_kg_acq_argbest", ctypes.c_int, [_vp, ctypes.c_double, ctypes.c_int, c_int64_p, c_double_p]),
+    ("gp_kg_acq_topk", ctypes.c_int, [_vp, ctypes.c_double, ctypes.c_int, ctypes.c_int, c_int64_p, c_double_p]),
+    ("gp_kg_rows", ctypes.c_int, [_vp, _vp, ctypes.c_int64, ctypes.c_double, _vp, _vp]),
     ("gp_qei_set", ctypes.c_int, [_vp, c_double_p, ctypes.c_int, ctypes.c_int]),
     ("gp_qei_info", ctypes.c_int, [_vp, c_int_p, c_int_p]),
     ("gp_qei_stats", ctypes.c_int, [_vp, c_int64_p, c_int64_p]),
@@ -465,6 +472,70 @@ class EhviPack(object):
         rc = self.lib.gp_ehvi_rows(*(self.args + (Xs.ctypes.data, M, out.ctypes.data, dout.ctypes.data if grad else None)))
         if rc:
             check(self.lib, rc, "gp_ehvi_rows")
+        return (out, dout) if grad else out
+
+
+class KgEntries(object):
+    """The knowledge gradient's entries of a handle (include/gphip.h, gp_kg_*): discrete KG over resident discretisation points.
+    ``handle.kg`` makes one; it holds nothing but the handle."""
+
+    def __init__(self, handle):
+        self.handle = handle
+
+    def set_points(self, Xa, y_mean=0.0, y_std=1.0, key=None):
+        """Make ``Xa`` [A, D] the resident discretisation points; returns their posterior means [A], un-normalised.  ``key`` is
+        remembered as the handle's ``kg_key``."""
+        h = self.handle
+        Xa = as_f64(Xa, 2)
+        if Xa.shape[1] != h.D:
+            raise ValueError("expected points of shape [A, %d], got %s" % (h.D, Xa.shape))
+        A = Xa.shape[0]
+        mu = np.empty(max(A, 1))
+        h.kg_key = None
+        check(h.lib, h.lib.gp_kg_set_points(h.h, dptr(Xa), A, float(y_mean), float(y_std), mu.ctypes.data), "gp_kg_set_points")
+        h.kg_key = key
+        return mu[:A]
+
+    def info(self):
+        """How many discretisation points are resident (0: none, or a new fit dropped them)."""
+        h = self.handle
+        A = ctypes.c_int(0)
+        check(h.lib, h.lib.gp_kg_info(h.h, ctypes.byref(A)), "gp_kg_info")
+        return A.value
+
+    def acq(self, y_std=1.0):
+        """+KG of the resident candidates, [M, 1]."""
+        h = self.handle
+        out = np.empty((h.M, 1))
+        check(h.lib, h.lib.gp_kg_acq(h.h, float(y_std), dptr(out)), "gp_kg_acq")
+        return out
+
+    def acq_argbest(self, sense, y_std=1.0):
+        h = self.handle
+        idx, val = ctypes.c_int64(), ctypes.c_double()
+        check(h.lib, h.lib.gp_kg_acq_argbest(h.h, float(y_std), int(sense), ctypes.byref(idx), ctypes.byref(val)), "gp_kg_acq_argbest")
+        return idx.value, val.value
+
+    def acq_topk(self, sense, k, y_std=1.0):
+        h = self.handle
+        idx = np.empty(k, dtype=np.int64)
+        val = np.empty(k)
+        check(h.lib, h.lib.gp_kg_acq_topk(h.h, float(y_std), int(sense), int(k), idx.ctypes.data_as(c_int64_p), dptr(val)),
+              "gp_kg_acq_topk")
+        return idx, val
+
+    def rows(self, Xs, y_std=1.0, grad=False):
+        """-KG at the locations ``Xs`` [M, D] given by value, [M, 1]; with ``grad`` its gradient [M, D] as well (up to eight
+        locations: the fused rows path)."""
+        h = self.handle
+        Xs = np.ascontiguousarray(Xs, dtype=np.float64)
+        if Xs.ndim != 2 or Xs.shape[1] != h.D:
+            raise ValueError("expected locations of shape [M, %d], got %s" % (h.D, Xs.shape))
+        out = np.empty((Xs.shape[0], 1))
+        dout = np.empty((Xs.shape[0], h.D)) if grad else None
+        rc = h.lib.gp_kg_rows(h.h, Xs.ctypes.data, Xs.shape[0], float(y_std), out.ctypes.data, dout.ctypes.data if grad else None)
+        if rc:
+            check(h.lib, rc, "gp_kg_rows")
         return (out, dout) if grad else out
 
 
@@ -1477,6 +1548,14 @@ class Handle(object):
             check(self.lib, rc, "gp_qei_rows")
         res = (out[0],) + ((dout,) if grad else ()) + ((mean, cov) if posterior else ())
         return res if len(res) > 1 else res[0]
+
+    # -- knowledge gradient (include/gphip.h, gp_kg_*): the entries are ``KgEntries``' methods, reached as ``handle.kg.<entry>`` ---------
+    kg_key = None       # whose discretisation points are resident (AcquisitionKG's staleness check; the library drops the points
+                        # with the fit, which kg.info() tells)
+
+    @property
+    def kg(self):
+        return KgEntries(self)
 
     # -- the mean function m(x) = x^T A + b of the exact GP (include/gphip.h, gp_mean_*) -----------------------------------
     def mean_set(self, A=None, b=None):

@@ -27,6 +27,7 @@ from .entropy_search import AffineInvariantEnsembleSampler
 from .gpmodel import GPModel
 from .input_warped_gp import InputWarpedGPModel
 from .joint_ei import AcquisitionQEI, JointBatch
+from .knowledge_gradient import AcquisitionKG
 from .parameterization import lbfgsb_lockstep, SCIPY_DEFAULT
 
 
@@ -401,7 +402,13 @@ class BayesianOptimization(object):
     (``AcquisitionQEI``; the evaluator is ``JointBatch``, whatever ``evaluator_type`` of 'sequential', None or 'joint' was given).
     'local_penalization', 'thompson_sampling' and 'random' raise ``InvalidConfigError``: they build a batch point by point.
     ``parallel_anchors=True`` is ignored for it: a batch already fills the wide pass over the inverse factor, and the starts'
-    L-BFGS runs go one after the other.  A cost model and ``constraint_function`` raise ``NotImplementedError``."""
+    L-BFGS runs go one after the other.  A cost model and ``constraint_function`` raise ``NotImplementedError``.
+
+    Knowledge gradient (an addition): ``acquisition_type='KG'`` with the keywords ``num_kg_points`` (64 discretisation points, at most
+    256), ``kg_table_size`` (10000 uniform locations the lowest posterior means are taken from) and ``sampler_seed`` scores the
+    expected decrease of the minimum of the posterior mean (``AcquisitionKG``): the acquisition for noisy observations, which reads
+    no f_min.  It has gradients, and ``parallel_anchors=True`` works.  Sequential evaluator only: a batch (``batch_size`` > 1 with
+    any other evaluator) raises ``InvalidConfigError``; a cost model and ``constraint_function`` raise ``NotImplementedError``."""
 
     def __init__(self, f, domain=None, constraints=None, cost_withGradients=None, model_type='GP', X=None, Y=None,
                  initial_design_numdata=5, initial_design_type='random', acquisition_type='EI', normalize_Y=True,
@@ -425,6 +432,13 @@ class BayesianOptimization(object):
         if joint and not 1 <= int(batch_size) <= 8:
             raise ValueError("joint expected improvement takes batches of 1 to 8 points, got batch_size=%r" % (batch_size,))
         constrained = constraint_function is not None or C is not None
+        kg = isinstance(acquisition, AcquisitionKG) or (acquisition is None and acquisition_type == 'KG')
+        if kg and batch_size > 1 and evaluator_type != 'sequential':
+            raise InvalidConfigError("the knowledge gradient suggests one point at a time: evaluator %r builds a batch (batch KG is "
+                                     "not implemented; use 'sequential')" % evaluator_type)
+        if kg and constrained:
+            raise NotImplementedError("the knowledge gradient (KG) takes no black-box constraints: use acquisition_type 'EI' or "
+                                      "'MPI' with constraint_function")
         if joint and constrained:
             raise NotImplementedError("joint expected improvement (qEI) takes no black-box constraints: use acquisition_type 'EI' "
                                       "or 'MPI' with constraint_function")
@@ -503,6 +517,11 @@ class BayesianOptimization(object):
             self.acquisition = AcquisitionQEI(self.model, self.space, self.acquisition_optimizer, batch_size=batch_size,
                                               num_samples=kwargs.get('num_qei_samples', 256), jitter=jitter,
                                               seed=kwargs.get('sampler_seed', None), cost_withGradients=cost_withGradients)
+        elif acquisition_type == 'KG':
+            self.acquisition = AcquisitionKG(self.model, self.space, self.acquisition_optimizer,
+                                             num_points=kwargs.get('num_kg_points', 64),
+                                             kg_table_size=kwargs.get('kg_table_size', 10000),
+                                             sampler_seed=kwargs.get('sampler_seed', None), cost_withGradients=cost_withGradients)
         elif acquisition_type == 'EI_MCMC':
             self.acquisition = AcquisitionEI_MCMC(self.model, self.space, self.acquisition_optimizer, cost_withGradients, jitter)
         elif acquisition_type == 'MPI_MCMC':

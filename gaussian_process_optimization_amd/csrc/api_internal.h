@@ -396,6 +396,18 @@ struct QeiState {
     long calls = 0, grad_calls = 0;   // gp_qei_rows calls answered since the context was created, and those with a gradient (gp_qei_stats)
 };
 
+// The knowledge gradient (api_kg.hip): the discretisation points of a fit.  A > 0 while dVA / dMuA / dXa belong to the factor in dA;
+// everything that drops ES's representers drops them (factor_results_dropped, factor_grown).  Nothing is shared with EsState.
+struct KgState {
+    int A = 0;                 // discretisation points resident (0: none)
+    DevBuf<double> dXa;        // [A, D]
+    DevBuf<double> dVA;        // 256 x Npad: row i = L^-1 K(X, a_i), zero rows and columns in the padding
+    DevBuf<double> dMuA;       // [A]: the points' latent posterior means
+    DevBuf<double> dC;         // mc_pad x 256: a chunk's covariance candidate x point
+    DevBuf<double> dRowsPart;  // gp_kg_rows: the workgroups' shares of V_A w and |w|^2 (kg_rows_part_elems)
+    DevBuf<double> dState;     // gp_kg_rows: ROWS_WIDE_M state rows of KG_STATE_STRIDE doubles (kg.hip)
+};
+
 struct gp_ctx {
     int device = 0;
     long lds_per_wg = 0;           // hipDeviceAttributeMaxSharedMemoryPerBlock of the device (gp_create)
@@ -561,6 +573,7 @@ struct gp_ctx {
     MesState mes;       // the samples of the minimum's value behind GP_ACQ_MES (api_mes.hip)
     PathsState paths;   // posterior function samples over the resident factor (api_paths.hip)
     QeiState qei;       // the base samples of the joint expected improvement (api_qei.hip)
+    KgState kg;         // the knowledge gradient's discretisation points (api_kg.hip)
     bool dead = false;  // gp_shutdown ran: the device's streams are gone, only gp_destroy is still valid
 };
 
@@ -575,6 +588,7 @@ static inline void factor_results_dropped(gp_ctx *g) {
     g->predicted = false;
     g->es.R = 0;
     g->es.belief = false;
+    g->kg.A = 0;
     g->paths.S = 0;
 }
 // ... and dA no longer holds a fit of the current data and parameters at all.
@@ -604,6 +618,7 @@ static inline void factor_grown(gp_ctx *g) {
     g->ens.S = 0;
     g->es.R = 0;
     g->es.belief = false;
+    g->kg.A = 0;
     g->paths.S = 0;
 }
 
@@ -906,6 +921,7 @@ void panel_inv_steps(gp_ctx *g, hipStream_t s, double *Wb, long PB, const double
                      long sL, long sI);   // api_solve.hip: Wb (the identity on entry) <- L^-T of the Wp-tile lower factor at Lb
 // api_es.hip: what a scoring call needs -- an exact single-output model without a warp, representers and a belief --, and the
 // pointers of the belief for a launch
+int kg_ready(gp_ctx *g, double y_std);   // api_kg.hip: an exact single-output model as KG takes it, resident points, a usable y_std
 int es_ready(gp_ctx *g, double y_std);
 struct EsBelief { const double *Qt, *Gt, *logP, *u, *W; };
 EsBelief es_belief(const gp_ctx *g);

@@ -234,6 +234,56 @@ extern "C" int gp_es_acq_rows(gp_t *g, const double *Xs, int64_t M, double y_std
     return gp_es_acq(g, y_std, out);
 }
 
+// The knowledge gradient at a handful of locations given by value, negated as gp_acq_rows returns its scores, and with dout its
+// closed-form gradient (kernels: csrc/kg.hip).  Fused: the forward pass over the inverse factor, the shares of C = k(x, X_A) - V_A w
+// and a scoring launch of one workgroup per location that leaves the adjoint coefficients; for a gradient the coefficients are mixed into the backward
+// pass's right-hand sides, so that the UNCHANGED backward pass reads the inverse factor once more, and a closing pass over the
+// training points ends the call.  Beyond the fused path: the two table calls, values only.
+extern "C" int gp_kg_rows(gp_t *g, const double *Xs, int64_t M, double y_std, double *out, double *dout) {
+    if (!g || !Xs || !out) return fail(GP_ERR_ARG, "null argument");
+    GP_FITTED(g);
+    GP_NO_MEAN(g, "gp_kg_rows");
+    if (M < 1) return fail(GP_ERR_ARG, "M < 1");
+    int rc;
+    if ((rc = kg_ready(g, y_std))) return rc;
+    for (int64_t i = 0; i < M * g->D; ++i)
+        if (!std::isfinite(Xs[i])) return fail(GP_ERR_ARG, "gp_kg_rows: a location is not finite");
+    const bool fused = rows_fused_ok(g, M);
+    if (dout && !fused) return fail(GP_ERR_ARG, "gp_kg_rows: the gradient needs a shape the fused rows path takes (M <= %ld)", g->small_m);
+    // the build policy's counter moves with every call the fused path could take, as in gp_acq_rows; a gradient call takes the
+    // factor whatever the policy says (built at the first one)
+    const bool factor = fused && rows_use_factor(g);
+    if (fused && (dout || factor)) {
+        if ((rc = ensure_linv(g))) return rc;
+        KgState &kg = g->kg;
+        if ((rc = kg.dRowsPart.reserve((long)kg_rows_part_elems(g->Npad)))) return rc;
+        if ((rc = kg.dState.reserve((long)ROWS_WIDE_M * KG_STATE_STRIDE))) return rc;
+        const int want_grad = dout != nullptr;
+        const int nt_loads = g->rows_nt < 0 ? (g->Npad > 8192 ? 1 : 0) : g->rows_nt;
+        return rows_exact_passes(
+            g, Xs, (int)M, want_grad ? "rows_kg_grad" : "rows_kg", want_grad ? 2.0 : 1.0,
+            [&](const RowsX &rx, const RowsWork &w, const PassReport &r) {
+                launch_rows_forward(g->s, g->dLi, g->Npad, rx, g->kp, g->dX, g->N, g->dAlpha, w, nt_loads);
+                launch_kg_rows(g->s, rx, g->kp, kg.dXa, kg.A, kg.dVA, kg.dMuA, g->Npad, w, kg.dRowsPart, g->kp.variance, g->noise, y_std,
+                               want_grad, kg.dState, r);
+                unsigned arrivals = (unsigned)rx.M;   // the scoring kernel: one workgroup per location
+                if (want_grad) {
+                    launch_kg_mix(g->s, rx.M, g->N, g->Npad, w, kg.dVA, kg.A, kg.dState);
+                    launch_rows_backward(g->s, g->dLi, g->Npad, rx.M, w, nt_loads);
+                    launch_kg_close(g->s, rx, g->kp, g->dX, g->N, g->Npad, g->dAlpha, w, kg.dXa, kg.A, kg.dState, r, r.base + arrivals);
+                    arrivals += rows_finish_grid(g->N);
+                }
+                return arrivals;
+            },
+            [&](int m0, int mc, int MV, const double *o) { rows_unpack(o, MV, m0, mc, g->D, nullptr, nullptr, out, nullptr, nullptr, dout); });
+    }
+    ++g->rows_fallback_calls;
+    if ((rc = gp_set_candidates(g, Xs, M))) return rc;
+    if ((rc = gp_kg_acq(g, y_std, out))) return rc;
+    for (int64_t i = 0; i < M; ++i) out[i] = -out[i];
+    return 0;
+}
+
 // how many *_rows calls took the fused path / the batched entry points since the context was created (route checks in tests)
 extern "C" int gp_rows_stats(gp_t *g, int64_t *fused, int64_t *fallback) {
     if (!g) return fail(GP_ERR_ARG, "null gp");

@@ -403,6 +403,29 @@ void launch_qei_joint(hipStream_t s, const RowsX &rx, const KernParams &kp, long
 void launch_qei_close(hipStream_t s, const RowsX &rx, const KernParams &kp, const double *X, long N, long Npad, const double *alpha,
                       const RowsWork &w, const double *state, const PassReport &r);
 
+// ---- kg.hip: the discrete knowledge gradient over A resident discretisation points (api_kg.hip) -----------------------------------------
+// C [mc, ldc] latent covariance candidate x point, mean / var [mc] the candidates' latent posterior (var without noise), muA [A] the
+// points' latent means; out [mc] = +KG
+void launch_kg_score(hipStream_t s, const double *C, long ldc, const double *mean, const double *var, long mc, double y_std,
+                     double noise, int A, const double *muA, double *out);
+// state (device): per location KG_STATE_STRIDE doubles [cv_i, i < A | ... | cw at 256 | cm at 257], what the scoring leaves the mix and
+// the closing pass (kg.hip)
+#define KG_STATE_STRIDE 264
+// behind launch_rows_forward (two launches: the shares, then one workgroup per location): -KG into r.out at the acquisition's place
+// of the rows layout; rx.M workgroups arrive at the pass's counter from r.base; cpart: kg_rows_part_elems(Npad) doubles.
+// want_grad = 0: the ticket as well; else the state rows.
+unsigned kg_rows_grid(long Npad);
+size_t kg_rows_part_elems(long Npad);
+void launch_kg_rows(hipStream_t s, const RowsX &rx, const KernParams &kp, const double *Xa, int A, const double *VA, const double *muA,
+                    long Npad, const RowsWork &w, double *cpart, double kss, double noise, double y_std, int want_grad, double *state,
+                    const PassReport &r);
+// w.wpart <- the adjoint's right-hand sides cw_m w_m + sum_i cv_mi V_A[i] (chunk 0; zeros in the other chunks), for launch_rows_backward
+void launch_kg_mix(hipStream_t s, int M, long N, long Npad, const RowsWork &w, const double *VA, int A, const double *state);
+// the closing pass over the training points: rows_finish_grid(N) workgroups arrive at the pass's counter from counter_base, the last
+// one writes the negated gradient [M, D] at the rows layout's dacq and the ticket
+void launch_kg_close(hipStream_t s, const RowsX &rx, const KernParams &kp, const double *X, long N, long Npad, const double *alpha,
+                     const RowsWork &w, const double *Xa, int A, const double *state, const PassReport &r, unsigned counter_base);
+
 // ---- ens_rows.hip: the same passes over an ensemble of S members, the member as a grid dimension --------------------------------
 #define ENS_ROWS_RB 32                       // rows of the tile per workgroup: what rows_block_height gives every matrix the ensemble takes
 #define ENS_POST_STRIDE ROWS_OUT_DOUBLES     // doubles between two members' result blocks (each laid out as the single model's)

@@ -1141,6 +1141,54 @@ int gp_ehvi_topk(gp_t *gp, gp_t *const *others, int K, const double *y_mean, con
 int gp_ehvi_rows(gp_t *gp, gp_t *const *others, int K, const double *y_mean, const double *y_std, const double *Xs, int64_t M,
                  double *out, double *dout);
 
+/* ---- knowledge gradient (Frazier, Powell & Dayanik 2009; Scott, Frazier & Powell 2011) ---------------------------------------------
+ * The expected decrease of the minimum of the posterior mean after one more (noisy) observation at x, the minimum taken over a
+ * resident discretisation set X_A = {a_0 .. a_{A-1}} and x itself.  With w = L^-1 k(X, x), v = kss - |w|^2, sigma^2 the likelihood
+ * variance gp_predict's include_noise adds, everything de-normalised by y_std (the shift y_mean cancels):
+ *     v'  = max(y_std^2 v, 1e-10)                                   (the floor of gpmodel.py:99, as gp_es_acq applies it)
+ *     sd  = sqrt(v' + y_std^2 sigma^2)
+ *     a_i = y_std mu(a_i),  b_i = y_std^2 (k(x, a_i) - V_A[i] . w) / sd,   i < A;      a_A = y_std mu(x),  b_A = v' / sd
+ *     a*  = min_i a_i (lowest index on a tie),  a~_i = a_i - a* >= 0
+ *     KG(x) = -E_Z[min_i (a~_i + b_i Z)] = -sum_i (a~_i p_i + b_i q_i),   p_i = Phi(hi_i) - Phi(lo_i),  q_i = phi(lo_i) - phi(hi_i)
+ * [lo_i, hi_i] the interval of z on which line i is the lowest (empty for dominated lines; of lines identical to the bit the lowest
+ * index owns it), found in interval form: line i intersects the half-lines (b_i - b_j) z <= a~_j - a~_i over all j.  p_i comes from
+ * erfc on the side of the tail.  Gradient, j* = argmin_i a_i:
+ *     dKG/dx = ([j* = A] - p_A) y_std dmu(x)/dx - sum_i q_i db_i/dx
+ *     db_i/dx = y_std^2 (dk(x, a_i)/dx - J(x)^T beta_{a_i}) / sd - b_i dsd / sd  (i < A),   db_A/dx = dv' / sd - b_A dsd / sd
+ *     dv' = -2 y_std^2 J(x)^T beta_x (0 where the floor holds),  dsd = dv' / (2 sd),  beta_{a_i} = L^-T V_A[i],  beta_x = L^-T w
+ * J(x) the [N, D] input Jacobian of k(X, x), 0 where the distance is exactly 0.
+ *
+ * gp_kg_set_points: Xa [A, D] becomes resident with V_A = L^-1 K(X, Xa) (a padded 256 x Npad block of its own) and the points'
+ * latent means; mu [A], when given, receives them un-normalised (mean y_std + y_mean).  Entropy search's representers and their
+ * bits are left alone, and gp_es_set_representers leaves the points: both may be resident.  The resident candidates stay; their
+ * cached posterior is dropped.  The points belong to the fit: everything that drops the representers drops them.  gp_kg_info:
+ * *A resident, 0 without.
+ * gp_kg_acq: out [M] = +KG over the resident candidates.  Per chunk of the candidate solve C = K(Xs, Xa) - (K(Xs, X) L^-T) V_A^T,
+ * the GEMM of gp_es_acq against V_A, then one workgroup per candidate.  gp_kg_acq_argbest / gp_kg_acq_topk: the selector of
+ * gp_acq_argbest / gp_acq_topk over that vector (sense +1 picks the largest KG; lowest index among equal scores).
+ * gp_kg_rows: M >= 1 locations Xs [M, D] by value; out [M] = -KG and, when dout is given, dout [M, D] = -dKG/dx (the sign of
+ * gp_acq / gp_acq_grad).  For M <= option "small_m" (8) locations that fit the fused rows path (pass layouts 1, 4 and 8, the
+ * build policy of the inverse factor as for gp_acq_rows; a gradient call always takes the factor) a pass is the forward launch
+ * over L^-1, the shares of V_A w per 256 training rows, a scoring launch of one workgroup per location that forms the C's, scores
+ * and leaves p, q and the adjoint coefficients, and for a gradient: a kernel that mixes them into the backward pass's right-hand
+ * sides, w' = cw w + sum_i cv_i V_A[i] -- by linearity L^-T w' carries beta_x and
+ * every beta_{a_i}, so L^-1 is read twice as in gp_acq_rows and no B_A = L^-T V_A is kept --, the rows path's backward pass, and a
+ * closing pass over the training points.  Results and ticket go into the pinned block: no copy commands either side.  Larger M,
+ * or a shape the fused path refuses, takes the two table calls, values only: a dout there is GP_ERR_ARG.  The routes agree to
+ * rounding (tests: 1e-9).  On the fused path a location's value and gradient are the same bits whatever its slot and its company,
+ * repeated calls are bitwise equal, and the value is the same bits with and without dout.  Fixed summation order, no atomics but
+ * the arrival counter.  Always true fp64 ("emulate_fp64" covers the candidate solve of the table as for gp_predict).
+ * GP_ERR_STATE: no fit, no resident points (scoring), P != 1, a sparse fit, an ensemble, an output warp, a mean function or a Gower
+ * kernel in force.  GP_ERR_ARG: A outside 1 .. GP_KG_MAX_A, null pointers, inputs that are not finite, a y_std that is not positive
+ * and finite.  A refused call launches and changes nothing. */
+#define GP_KG_MAX_A 256
+int gp_kg_set_points(gp_t *gp, const double *Xa, int A, double y_mean, double y_std, double *mu);
+int gp_kg_info(gp_t *gp, int *A);
+int gp_kg_acq(gp_t *gp, double y_std, double *out);
+int gp_kg_acq_argbest(gp_t *gp, double y_std, int sense, int64_t *idx, double *val);
+int gp_kg_acq_topk(gp_t *gp, double y_std, int sense, int k, int64_t *idx, double *val);
+int gp_kg_rows(gp_t *gp, const double *Xs, int64_t M, double y_std, double *out, double *dout);
+
 #ifdef __cplusplus
 }
 #endif
