@@ -23,7 +23,8 @@ from . import kern
 from . import mappings
 from .gp_regression import GPRegression, Gaussian, Standardize
 from .sparse_gp import SparseGPRegression
-from .gpmodel import GPModel, BOModel, GPModel_MCMC
+from .gpmodel import GPModel, BOModel, GPModel_MCMC, GPClassModel
+from .gp_classification import GPClassification, Bernoulli
 from . import priors
 from .mcmc import HMC
 from . import input_warping
@@ -55,12 +56,12 @@ from .multi_objective import (AcquisitionEHVI, MultiObjectiveBayesianOptimizatio
                               nondominated_cells)
 
 # namespaces named like the reference packages
-models = _types.SimpleNamespace(GPRegression=GPRegression, SparseGPRegression=SparseGPRegression, GPModel=GPModel, GPModel_MCMC=GPModel_MCMC, InputWarpedGP=InputWarpedGP,
+models = _types.SimpleNamespace(GPRegression=GPRegression, GPClassification=GPClassification, GPClassModel=GPClassModel, SparseGPRegression=SparseGPRegression, GPModel=GPModel, GPModel_MCMC=GPModel_MCMC, InputWarpedGP=InputWarpedGP,
                                 InputWarpedGPModel=InputWarpedGPModel, WarpedGP=WarpedGP, WarpedGPModel=WarpedGPModel)
 methods = _types.SimpleNamespace(BayesianOptimization=BayesianOptimization)
-likelihoods = _types.SimpleNamespace(Gaussian=Gaussian)
+likelihoods = _types.SimpleNamespace(Gaussian=Gaussian, Bernoulli=Bernoulli)
 
-__all__ = ["kern", "mappings", "models", "methods", "likelihoods", "acquisitions", "GPRegression", "SparseGPRegression", "GPModel", "BOModel", "GPModel_MCMC", "priors", "HMC",
+__all__ = ["GPClassification", "GPClassModel", "Bernoulli", "kern", "mappings", "models", "methods", "likelihoods", "acquisitions", "GPRegression", "SparseGPRegression", "GPModel", "BOModel", "GPModel_MCMC", "priors", "HMC",
            "AcquisitionEI_MCMC", "AcquisitionMPI_MCMC", "AcquisitionLCB_MCMC",
            "AcquisitionTS", "AcquisitionQEI", "JointBatch", "joint_ei", "AcquisitionKG", "knowledge_gradient", "posterior_paths", "PosteriorPaths", "AcquisitionMES", "max_value", "MinValueSampler", "AcquisitionEntropySearch", "entropy_search", "McmcSampler", "AffineInvariantEnsembleSampler",
            "InputWarpedGP", "InputWarpedGPModel", "input_warping", "WarpedGP", "WarpedGPModel", "warping_functions",

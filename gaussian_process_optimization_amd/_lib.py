@@ -30,6 +30,8 @@ GP_ACQ_TIMES_FEAS = 0x200    # or-ed into a table scoring call's type: the score
 GP_FEAS_MAX = 8
 GP_EHVI_MAX_OBJ, GP_EHVI_MAX_LEVELS, GP_EHVI_MAX_CELLS = 3, 256, 32768   # expected hypervolume improvement: objectives, levels per objective, cells
 GP_ERR_ARG, GP_ERR_HIP, GP_ERR_STATE, GP_ERR_RCCL, GP_ERR_NOT_PD_DIAG = -1, -2, -3, -4, -5
+GP_LAPLACE_NOT_CONVERGED = 1 << 30     # gp_laplace_fit: the Newton iteration reached its cap
+LAPLACE_MAX_ITER = 40                  # ... the cap the Python layer asks for
 
 # every symbol include/gphip.h declares: (name, restype, argtypes)
 _vp = ctypes.c_void_p
@@ -234,6 +236,11 @@ SIGNATURES = [
     ("gp_kg_acq_argbest", ctypes.c_int, [_vp, ctypes.c_double, ctypes.c_int, c_int64_p, c_double_p]),
     ("gp_kg_acq_topk", ctypes.c_int, [_vp, ctypes.c_double, ctypes.c_int, ctypes.c_int, c_int64_p, c_double_p]),
     ("gp_kg_rows", ctypes.c_int, [_vp, _vp, ctypes.c_int64, ctypes.c_double, _vp, _vp]),
+    ("gp_laplace_fit", ctypes.c_int, [_vp, c_double_p, ctypes.c_int, c_double_p, c_double_p, c_int_p, c_int_p, c_int_p]),
+    ("gp_laplace_fit_grad", ctypes.c_int, [_vp, c_double_p, ctypes.c_int, c_double_p, c_double_p, c_int_p, c_int_p, c_int_p,
+                                           c_double_p]),
+    ("gp_laplace_info", ctypes.c_int, [_vp, c_int_p, c_int_p, c_double_p, c_double_p]),
+    ("gp_laplace_get_mode", ctypes.c_int, [_vp, c_double_p, c_double_p]),
     ("gp_qei_set", ctypes.c_int, [_vp, c_double_p, ctypes.c_int, ctypes.c_int]),
     ("gp_qei_info", ctypes.c_int, [_vp, c_int_p, c_int_p]),
     ("gp_qei_stats", ctypes.c_int, [_vp, c_int64_p, c_int64_p]),
@@ -640,6 +647,59 @@ class Handle(object):
         rc = self.lib.gp_fit(self.h, int(maxtries), ctypes.byref(lml), ctypes.byref(logdet), ctypes.byref(jit))
         check(self.lib, rc, "gp_fit")
         return lml.value, logdet.value, jit.value
+
+    # -- GP classification (gp_laplace_*) ----------------------------------------
+    def _laplace_labels(self, y):
+        y = as_f64(np.ravel(y), 1)
+        if y.size != getattr(self, "N", -1):
+            raise ValueError("one label per training row: got %d, the data has %s" % (y.size, getattr(self, "N", None)))
+        return y
+
+    def _laplace_check(self, rc, what):
+        if rc == GP_LAPLACE_NOT_CONVERGED:
+            raise RuntimeError("%s: %s" % (what, self.lib.gp_last_error().decode()))
+        if rc > 0:
+            raise np.linalg.LinAlgError("%s: B = I + W^1/2 K W^1/2 is not positive definite (pivot %d)" % (what, rc))
+        check(self.lib, rc, what)
+
+    def laplace_fit(self, y, cap=LAPLACE_MAX_ITER):
+        """gp_laplace_fit: the probit Laplace fit of the labels ``y`` [N] in {-1, +1} under the handle's data and kernel, at most
+        ``cap`` Newton steps.  Returns
+        (log Z, log|B|, Newton steps, halvings); the handle is then Laplace-fitted (the latent posterior through ``predict*``).
+        Raises RuntimeError when ``cap`` steps did not converge, numpy.linalg.LinAlgError on a failed pivot."""
+        y = self._laplace_labels(y)
+        lz, ld = ctypes.c_double(), ctypes.c_double()
+        it, hv, cv = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+        rc = self.lib.gp_laplace_fit(self.h, dptr(y), int(cap), ctypes.byref(lz), ctypes.byref(ld), ctypes.byref(it),
+                                     ctypes.byref(hv), ctypes.byref(cv))
+        self._laplace_check(rc, "gp_laplace_fit")
+        return lz.value, ld.value, it.value, hv.value
+
+    def laplace_fit_grad(self, y, nls, cap=LAPLACE_MAX_ITER):
+        """gp_laplace_fit_grad: the fit and d log Z / d (variance, lengthscale(s)).  Returns ((log Z, log|B|, steps, halvings),
+        (dvariance, dlengthscale [nls]))."""
+        y = self._laplace_labels(y)
+        grad = np.empty(1 + self._grad_ls(nls).size)
+        lz, ld = ctypes.c_double(), ctypes.c_double()
+        it, hv, cv = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+        rc = self.lib.gp_laplace_fit_grad(self.h, dptr(y), int(cap), ctypes.byref(lz), ctypes.byref(ld), ctypes.byref(it),
+                                          ctypes.byref(hv), ctypes.byref(cv), dptr(grad))
+        self._laplace_check(rc, "gp_laplace_fit_grad")
+        return (lz.value, ld.value, it.value, hv.value), (grad[0], grad[1:].copy())
+
+    def laplace_info(self):
+        """(Newton steps, halvings, min W, max W) of the last Laplace fit (gp_laplace_info)."""
+        it, hv = ctypes.c_int(), ctypes.c_int()
+        lo, hi = ctypes.c_double(), ctypes.c_double()
+        check(self.lib, self.lib.gp_laplace_info(self.h, ctypes.byref(it), ctypes.byref(hv), ctypes.byref(lo), ctypes.byref(hi)),
+              "gp_laplace_info")
+        return it.value, hv.value, lo.value, hi.value
+
+    def laplace_mode(self):
+        """(f [N] at the mode, W [N]) of the Laplace-fitted handle (gp_laplace_get_mode)."""
+        f, W = np.empty(self.N), np.empty(self.N)
+        check(self.lib, self.lib.gp_laplace_get_mode(self.h, dptr(f), dptr(W)), "gp_laplace_get_mode")
+        return f, W
 
     def fit_predict(self, include_noise=True, maxtries=5):
         """gp_fit + gp_predict on the resident candidates as one pipelined pass."""

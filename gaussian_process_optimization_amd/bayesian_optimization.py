@@ -378,7 +378,9 @@ class BayesianOptimization(object):
 
     Black-box constraints (an addition): ``constraint_function(X) -> [n, K]`` is evaluated wherever ``f`` is (``C`` holds the
     values of the initial design, for ``f=None`` use), a location is feasible where every column is ``<= constraint_bounds``
-    (a scalar or one bound per column).  A ``FeasibilityModel`` -- one exact GP per constraint -- is refitted with the surrogate
+    (a scalar or one bound per column); ``constraint_kinds`` names each column ``'value'`` (the default) or ``'binary'`` -- a
+    yes / no outcome, 1 where the constraint was violated and 0 where it was satisfied, modelled by a GP classifier
+    (``FeasibilityModel(kinds=...)``).  A ``FeasibilityModel`` -- one exact GP per constraint -- is refitted with the surrogate
     and EI / MPI score ``a(x) F(x)`` with the incumbent over the feasible observations (``feasibility.py``).  ``x_opt`` /
     ``fx_opt`` are then the best FEASIBLE observation; while there is none they are the LEAST VIOLATING one: the observation
     with the smallest total violation ``sum_k max(c_k - bound_k, 0) / std_k`` (``std_k`` the standard deviation of column k over
@@ -415,7 +417,7 @@ class BayesianOptimization(object):
                  exact_feval=False, acquisition_optimizer_type='lbfgs', model_update_interval=1,
                  evaluator_type='sequential', batch_size=1, num_cores=1, verbosity=False, verbosity_model=False,
                  maximize=False, de_duplication=False, model=None, acquisition=None, device=0, parallel_anchors=False,
-                 constraint_function=None, C=None, constraint_bounds=0.0, **kwargs):
+                 constraint_function=None, C=None, constraint_bounds=0.0, constraint_kinds=None, **kwargs):
         if model_type not in ('GP', 'input_warped_GP') and model is None:
             raise NotImplementedError("model_type %r is outside the accelerated path" % model_type)
         if model_type == 'input_warped_GP' and evaluator_type == 'local_penalization' and batch_size > 1:
@@ -432,6 +434,13 @@ class BayesianOptimization(object):
         if joint and not 1 <= int(batch_size) <= 8:
             raise ValueError("joint expected improvement takes batches of 1 to 8 points, got batch_size=%r" % (batch_size,))
         constrained = constraint_function is not None or C is not None
+        if constraint_kinds is not None and not constrained:
+            raise ValueError("constraint_kinds without constraint_function or C: there are no constraint columns to name")
+        if constraint_kinds is not None and not isinstance(constraint_kinds, str) and \
+                any(k not in ('value', 'binary') for k in constraint_kinds):
+            raise ValueError("constraint_kinds takes 'value' or 'binary' per constraint column, got %r" % (constraint_kinds,))
+        if isinstance(constraint_kinds, str) and constraint_kinds not in ('value', 'binary'):
+            raise ValueError("constraint_kinds takes 'value' or 'binary', got %r" % (constraint_kinds,))
         kg = isinstance(acquisition, AcquisitionKG) or (acquisition is None and acquisition_type == 'KG')
         if kg and batch_size > 1 and evaluator_type != 'sequential':
             raise InvalidConfigError("the knowledge gradient suggests one point at a time: evaluator %r builds a batch (batch KG is "
@@ -571,7 +580,8 @@ class BayesianOptimization(object):
             if C is None:
                 C = self._evaluate_constraints(self.X)
             self.C = np.asarray(C, dtype=float).reshape(self.X.shape[0], -1)
-            self.feasibility = FeasibilityModel(self.C.shape[1], constraint_bounds, device=device, exact_feval=exact_feval,
+            self.feasibility = FeasibilityModel(self.C.shape[1], constraint_bounds, kinds=constraint_kinds, device=device,
+                                                exact_feval=exact_feval,
                                                 optimizer=kwargs.get('model_optimizer_type', 'lbfgs'),
                                                 max_iters=kwargs.get('max_iters', 1000),
                                                 optimize_restarts=kwargs.get('optimize_restarts', 5), verbose=verbosity_model,

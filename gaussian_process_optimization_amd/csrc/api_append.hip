@@ -215,6 +215,8 @@ extern "C" int gp_append(gp_t *g, const double *Xnew, int64_t k, const double *Y
     GP_DEAD_CHECK(g);
     if (g->mean.on())   // the border's right-hand sides would be raw targets beside residuals
         return append_refused(g, GP_ERR_STATE, "gp_append: not available while a mean function is resident (gp_mean_set(NULL, NULL) clears it)");
+    if (g->lap.on)   // the border would be that of K + noise, the factor is that of K + W^-1 at a mode the new rows move
+        return append_refused(g, GP_ERR_STATE, "gp_append: not available on a Laplace-fitted handle (gp_laplace_fit): refit");
     if (!g->fitted) return append_refused(g, GP_ERR_STATE, "gp_append extends a valid fit: gp_fit first");
     if (g->warp.n > 0) return append_refused(g, GP_ERR_STATE, "gp_append: an output warp is on (its targets are refitted, not appended)");
     if (k < 1 || k > GP_TILE) return append_refused(g, GP_ERR_ARG, "gp_append: k = %ld outside 1..%ld", (long)k, (long)GP_TILE);

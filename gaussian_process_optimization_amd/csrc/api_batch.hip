@@ -110,6 +110,7 @@ static int fit_grad_members(gp_ctx *g, const char *who, int R, const double *var
                             double *dnoise, int *status, const BatchInputs *bx, const BatchWarp *bw) {
     GP_DEAD_CHECK(g);
     GP_NO_MEAN(g, who);
+    GP_NO_LAPLACE(g, who);   // (the members would regress on the labels under the noise of that state)
     if (!g->have_data || !g->have_params) return fail(GP_ERR_STATE, "set data and params before %s", who);
     if (!bx && !bw && g->warp.n > 0)   // the members share Y, and each would need targets warped by parameters of its own
         return fail(GP_ERR_STATE, "gp_fit_grad_batch: an output warp is on (gp_set_output_warp); use gp_fit_grad_warp");

@@ -137,6 +137,8 @@ extern "C" int gp_comm_bcast_fit(gp_t *g, int root) {
     HIPCHK(hipSetDevice(g->device));
     if (root < 0 || root >= g->nranks) return fail(GP_ERR_ARG, "root %d out of range", root);
     if (g->rank == root && !g->fitted) return fail(GP_ERR_STATE, "the root rank must be fitted");
+    // (the record carries neither that state nor its noise of 1: the receivers would come out as regression fits of a factor of K + W^-1)
+    if (g->rank == root) GP_NO_LAPLACE(g, "gp_comm_bcast_fit");
     const long Npad = g->Npad;
     // host-side fit state rides along as a small record: a receiver's gp_fmin uses the root's jitter
     // (y - (noise + 1e-8 + jitter) alpha) and reports the root's LML / log det

@@ -660,6 +660,7 @@ extern "C" int gp_set_params(gp_t *g, int kernel, int ard, double variance, cons
     g->kp.variance = variance;
     for (int d = 0; d < g->D; ++d) g->kp.ls[d] = ard ? lengthscale[d] : lengthscale[0];
     g->ard = ard ? 1 : 0;
+    laplace_dropped(g);   // (before the new noise is stored: dropping that state puts the old one back)
     g->noise = noise;
     g->have_params = true;
     fit_dropped(g);
@@ -743,6 +744,7 @@ extern "C" int gp_kernel_matrix(gp_t *g, double *K) {
     HIPCHK(hipMemcpy2D(K, sizeof(double) * N, g->dA, sizeof(double) * g->Npad, sizeof(double) * N, N,
                        hipMemcpyDeviceToHost));
     factor_results_dropped(g);
+    laplace_dropped(g);   // (a Laplace fit's factor went with dA as well: no state, gp_set_params' noise back)
     g->fitted = false;  // dA was overwritten; fmin_valid is left alone -- fmin was taken from dY and dAlpha, which still hold what they did
     return 0;
 }

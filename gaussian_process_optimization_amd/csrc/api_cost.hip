@@ -11,6 +11,7 @@ extern "C" int gp_cost_set(gp_t *g, const double *Xc, int64_t Nc, const double *
     if (!g) return fail(GP_ERR_ARG, "null gp");
     GP_DEAD_CHECK(g);
     CostState &c = g->cost;
+    if (Nc != 0) GP_NO_LAPLACE(g, "gp_cost_set");
     if (Nc == 0) {   // clear
         c.Nc = 0;
         g->cost_tab = 0;

@@ -9,6 +9,7 @@ constexpr long ESB_LOGP = 0, ESB_U = GP_ES_MAX_R, ESB_GT = 2 * GP_ES_MAX_R, ESB_
 static int check_R(int R) { return R >= 1 && R <= GP_ES_MAX_R ? 0 : fail(GP_ERR_ARG, "R out of range (1..%d)", GP_ES_MAX_R); }
 // what every entry that touches the model's posterior asks of the context beyond a fit
 static int check_es_model(const gp_ctx *g) {
+    GP_NO_LAPLACE(g, "entropy search");
     if (g->P != 1) return fail(GP_ERR_ARG, "entropy search needs P == 1");
     if (g->warp.n > 0) return fail(GP_ERR_STATE, "entropy search: an output warp is on");
     if (g->sp.fitted) return fail(GP_ERR_STATE, "entropy search: the context holds a sparse fit");

@@ -543,6 +543,7 @@ int fit_impl(gp_ctx *g, int maxtries, Pipe kind, int include_noise) {
     const long N = g->N, Npad = g->Npad;
     const int P = g->P;
     int rc;
+    if (g->lap.on) fit_dropped(g);   // a Laplace-fitted context: its factor goes, and gp_set_params' noise is back before ky_diag reads it
     if ((rc = mean_residuals(g))) return rc;   // a resident mean function: dY = Y - m(X) is what everything below factors against
     PredPipe pp;
     if (kind != Pipe::None && (rc = make_pipe(g, kind, &pp))) return rc;

@@ -291,6 +291,7 @@ extern "C" int gp_acq_rows_feas(gp_t *g, gp_t *const *cons, int K, const double 
 extern "C" int gp_fmin_rows(gp_t *g, const int64_t *rows, int64_t n, double *fmin) {
     if (!g || !rows || !fmin) return fail(GP_ERR_ARG, "null argument");
     GP_FITTED(g);
+    GP_NO_LAPLACE(g, "gp_fmin_rows");   // (before anything is copied: train_values would refuse after the rows went up)
     if (g->P != 1) return fail(GP_ERR_ARG, "gp_fmin_rows needs P == 1");
     if (n < 1) return fail(GP_ERR_ARG, "n < 1");
     for (int64_t i = 0; i < n; ++i)

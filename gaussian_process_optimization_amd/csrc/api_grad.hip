@@ -62,6 +62,7 @@ static int lml_grad_x_pass(gp_ctx *g, double **out) {
 int lml_grad_impl(gp_ctx *g, double *dvariance, double *dlengthscale, double *dnoise, bool reset_phases, double *dL_dX) {
     if (!g || !dvariance || !dlengthscale || !dnoise) return fail(GP_ERR_ARG, "null argument");
     GP_FITTED(g);
+    GP_NO_LAPLACE(g, "gp_lml_grad");
     if (g->P > GP_GRAD_MAX_P) return fail(GP_ERR_ARG, "gp_lml_grad supports P <= %d", GP_GRAD_MAX_P);
     if (dL_dX && g->kp.gower) return fail(GP_ERR_ARG, "gp_lml_grad_x: not defined for a Gower model");
     int rc;
@@ -96,6 +97,7 @@ extern "C" int gp_lml_grad(gp_t *g, double *dvariance, double *dlengthscale, dou
 extern "C" int gp_lml_grad_x(gp_t *g, double *dL_dX) {
     if (!g || !dL_dX) return fail(GP_ERR_ARG, "null argument");
     GP_FITTED(g);
+    GP_NO_LAPLACE(g, "gp_lml_grad_x");
     GP_NO_MEAN(g, "gp_lml_grad_x");
     if (g->P > GP_GRAD_MAX_P) return fail(GP_ERR_ARG, "gp_lml_grad_x supports P <= %d", GP_GRAD_MAX_P);
     // the fork's Euclidean gradients_X on a Gower K is not a derivative of anything the warping could use
@@ -279,6 +281,7 @@ extern "C" int gp_acq_lp_grad(gp_t *g, int type, double par, double fmin, double
 extern "C" int gp_get_dl_dk(gp_t *g, double *dL_dK) {
     if (!g || !dL_dK) return fail(GP_ERR_ARG, "null argument");
     GP_FITTED(g);
+    GP_NO_LAPLACE(g, "gp_get_dl_dk");
     int rc;
     if ((rc = ensure_wi(g))) return rc;  // leaves dT free (Npad x Npad)
     const long N = g->N, Npad = g->Npad;

@@ -144,6 +144,14 @@ static int group_unwarped(gp_group *grp) {
             return fail(GP_ERR_STATE, "member %zu has a mean function resident (gp_mean_set): groups do not take a mean function", i);
     return 0;
 }
+// ... nor a classifier (gp_laplace_fit through gp_group_member): refused by the entries that read the members' fits -- fmin, the
+// candidates and the scoring entries.  gp_group_set_data, gp_group_set_params and gp_group_fit go through: they clear that state
+static int group_no_laplace(gp_group *grp) {
+    for (size_t i = 0; i < grp->m.size(); ++i)
+        if (grp->m[i]->lap.on)
+            return fail(GP_ERR_STATE, "member %zu is Laplace-fitted (gp_laplace_fit): groups replicate regression models only; gp_group_fit clears that state", i);
+    return 0;
+}
 
 // fn(member) on every member in turn, on the calling thread (host-only settings: nothing to run side by side)
 template <class F>
@@ -198,6 +206,7 @@ extern "C" int gp_group_fit(gp_group_t *grp, int maxtries, double *lml, double *
 extern "C" int gp_group_fmin(gp_group_t *grp, double *fmin) {
     if (!grp || !fmin) return fail(GP_ERR_ARG, "null argument");
     if (int rw = group_unwarped(grp)) return rw;
+    if (int rl = group_no_laplace(grp)) return rl;
     return gp_fmin(grp->m[0], fmin);
 }
 
@@ -360,6 +369,7 @@ static int score_blocks(gp_group *grp, int k, Pairs &p, F score) {
 }
 static int group_ready(gp_group *grp, int sense) {
     if (int rw = group_unwarped(grp)) return rw;
+    if (int rl = group_no_laplace(grp)) return rl;
     if (grp->M < 1) return fail(GP_ERR_STATE, "gp_group_set_candidates first");
     return check_sense(sense);
 }

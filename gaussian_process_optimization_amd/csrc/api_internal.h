@@ -408,6 +408,20 @@ struct KgState {
     DevBuf<double> dState;     // gp_kg_rows: ROWS_WIDE_M state rows of KG_STATE_STRIDE doubles (kg.hip)
 };
 
+// GP classification (api_laplace.hip): what a Laplace fit keeps beside the context's own buffers.  `on` while the context is
+// "Laplace-fitted": dA holds the factor of K + W^-1, dAlpha the mode's a, and noise is 1 (noise_saved: what gp_set_params gave,
+// put back where the state is dropped).  Every regression fit, gp_set_data and gp_set_params drop it (laplace_dropped).
+enum { LAP_Y = 0, LAP_A, LAP_F, LAP_DA, LAP_DF, LAP_W, LAP_SW, LAP_B, LAP_T, LAP_RHS, LAP_SOL, LAP_S2, LAP_TMP, LAP_AU, LAP_U, LAP_NVEC };
+struct LapState {
+    bool on = false;
+    double noise_saved = 0.0;
+    DevBuf<double> dK;         // Npad x Npad: the full K of the fit in progress (no noise, no 1e-8), built once per call
+    DevBuf<double> dVec;       // LAP_NVEC vectors of Npad (LAP_AU and LAP_U adjacent: the gradient pass's two rows a, u)
+    DevBuf<double> dRes;       // LAP_RES_DOUBLES: the step's result block
+    int iters = 0, halvings = 0;   // of the last fit (gp_laplace_info)
+    double wmin = 0.0, wmax = 0.0;
+};
+
 struct gp_ctx {
     int device = 0;
     long lds_per_wg = 0;           // hipDeviceAttributeMaxSharedMemoryPerBlock of the device (gp_create)
@@ -574,8 +588,24 @@ struct gp_ctx {
     PathsState paths;   // posterior function samples over the resident factor (api_paths.hip)
     QeiState qei;       // the base samples of the joint expected improvement (api_qei.hip)
     KgState kg;         // the knowledge gradient's discretisation points (api_kg.hip)
+    LapState lap;       // GP classification: the Laplace fit's buffers and state (api_laplace.hip)
     bool dead = false;  // gp_shutdown ran: the device's streams are gone, only gp_destroy is still valid
 };
+
+// The context stops being Laplace-fitted: the noise gp_set_params gave is in force again.  (Before anything reads g->noise for a
+// regression fit, and before gp_set_params stores a new one.)
+static inline void laplace_dropped(gp_ctx *g) {
+    if (!g->lap.on) return;
+    g->lap.on = false;
+    g->noise = g->lap.noise_saved;
+}
+// The entries that read more of a fit than its factor, inverse factor, alpha and noise -- targets, log-likelihood pieces, the
+// Gaussian LML's weights -- would answer silently wrong on a Laplace-fitted context: refused before anything is launched or changed
+#define GP_NO_LAPLACE(g, who)                                                                       \
+    do {                                                                                            \
+        if ((g)->lap.on)                                                                            \
+            return fail(GP_ERR_STATE, "%s: not available on a Laplace-fitted handle (gp_laplace_fit): a regression fit, gp_set_data or gp_set_params clears that state", who); \
+    } while (0)
 
 // A new factor is about to be (or has been) written to dA: nothing derived from the old one may be served again.
 static inline void factor_results_dropped(gp_ctx *g) {
@@ -593,6 +623,7 @@ static inline void factor_results_dropped(gp_ctx *g) {
 }
 // ... and dA no longer holds a fit of the current data and parameters at all.
 static inline void fit_dropped(gp_ctx *g) {
+    laplace_dropped(g);
     factor_results_dropped(g);
     g->fitted = false;
     g->fmin_valid = false;

@@ -7,6 +7,7 @@ static_assert(KG_LD % GP_TILE == 0, "V_A and C are padded tile operands");
 
 // what every entry that touches the model's posterior asks of the context beyond a fit
 static int check_kg_model(const gp_ctx *g) {
+    GP_NO_LAPLACE(g, "the knowledge gradient");
     if (g->P != 1) return fail(GP_ERR_STATE, "the knowledge gradient needs P == 1");
     if (g->warp.n > 0) return fail(GP_ERR_STATE, "the knowledge gradient: an output warp is on");
     if (g->sp.fitted) return fail(GP_ERR_STATE, "the knowledge gradient: the context holds a sparse fit");

@@ -27,6 +27,7 @@ extern "C" int gp_mean_set(gp_t *g, const double *A, const double *b) {
     if (!g) return fail(GP_ERR_ARG, "null gp");
     GP_DEAD_CHECK(g);
     if (!g->have_data) return fail(GP_ERR_STATE, "gp_mean_set: gp_set_data first (A is [D, P] and b [P] of the data)");
+    GP_NO_LAPLACE(g, "gp_mean_set");
     if (g->warp.n > 0)
         return fail(GP_ERR_STATE, "gp_mean_set: an output warp is on (gp_set_output_warp): a mean function and a warp do not combine");
     MeanState &mf = g->mean;
@@ -72,6 +73,7 @@ extern "C" int gp_mean_info(gp_t *g, int *has_A, int *has_b) {
 extern "C" int gp_mean_grad(gp_t *g, double *dA, double *db) {
     if (!g) return fail(GP_ERR_ARG, "null gp");
     GP_FITTED(g);
+    GP_NO_LAPLACE(g, "gp_mean_grad");
     MeanState &mf = g->mean;
     const int D = g->D, P = g->P, nout = (D + 1) * P;
     const long npart = (long)mean_grad_chunks(g->N) * nout;

@@ -14,6 +14,7 @@ extern "C" int gp_mes_set(gp_t *g, const double *ystar, int K) {
         g->mes.K = 0;
         return 0;
     }
+    GP_NO_LAPLACE(g, "gp_mes_set");
     if (!ystar) return fail(GP_ERR_ARG, "null argument");
     for (int k = 0; k < K; ++k)
         if (!std::isfinite(ystar[k])) return fail(GP_ERR_ARG, "gp_mes_set: sample %d is not finite", k);
@@ -36,6 +37,7 @@ extern "C" int gp_mes_info(gp_t *g, int *K) {
 // the resident candidates' table posterior with the noise the caller asks for (the cache is keyed by it: run_acq, gp_predict_warped
 // and gp_feas_table ask for theirs the same way), and the reductions' scratch
 static int mes_table(gp_ctx *g, int include_noise, double y_std, const char *who) {
+    GP_NO_LAPLACE(g, who);
     if (g->P != 1) return fail(GP_ERR_ARG, "%s needs P == 1", who);
     if (!(y_std > 0.0) || !std::isfinite(y_std)) return fail(GP_ERR_ARG, "%s: y_std must be positive and finite", who);
     int rc;

@@ -46,6 +46,7 @@ extern "C" int gp_paths_set(gp_t *g, int S, int F, const double *omega_unit, con
         g->paths.S = g->paths.F = 0;
         return 0;
     }
+    GP_NO_LAPLACE(g, "gp_paths_set");   // (the update's residuals are y + eps - prior draw: targets, not labels)
     if (F < 1 || F > GP_PATHS_MAX_F) return fail(GP_ERR_ARG, "gp_paths_set: F out of range (1..%d)", GP_PATHS_MAX_F);
     if (!omega_unit || !phase || !w || !z_eps) return fail(GP_ERR_ARG, "null argument");
     GP_FITTED(g);

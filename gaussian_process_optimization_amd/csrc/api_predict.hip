@@ -82,7 +82,7 @@ int run_predict(gp_ctx *g, int include_noise, bool tiles_only, const ChunkHook *
         launch_cross_k(g->s, g->dT, Npad, g->dXs + m0 * g->D, mc, mcpad, g->dX, g->N, Npad, g->kp);
         phase_end(g, ph);
         ph = phase_begin(g, g->emulate_fp64 ? "cand_solve_emulated" : "cand_solve", (double)N * N * mc, 0.0);
-        if (g->emulate_fp64) {
+        if (g->emulate_fp64 && !g->lap.on) {   // (a Laplace-fitted context: true fp64, its factor has no fixed-point bound)
             rc = solve_rows_rns(g, g->dT, g->dT2, (int)(mcpad / GP_TILE));
             if (rc == GP_ERR_RANGE) {   // non-finite candidates / factor: this chunk again in true fp64 (NaNs propagate as in the reference)
                 ++g->emu_fallbacks;
@@ -134,6 +134,7 @@ int check_acq(const gp_ctx *g, const AcqSpec &a, const LpSpec *lp) {
     if (g->P != 1) return fail(GP_ERR_ARG, "acquisitions need P == 1");
     const int base = acq_rule(a);
     const bool feas = acq_times_feas(a);
+    if (base == GP_ACQ_MES && a.mes_ok) GP_NO_LAPLACE(g, "GP_ACQ_MES");
     if (base == GP_ACQ_MES && a.mes_ok) {
         if (feas) return fail(GP_ERR_ARG, "GP_ACQ_TIMES_FEAS: MES takes no probability of feasibility");
         if (a.mes_K < 1) return fail(GP_ERR_STATE, "GP_ACQ_MES without samples of the minimum's value (gp_mes_set)");
@@ -153,6 +154,7 @@ int check_acq(const gp_ctx *g, const AcqSpec &a, const LpSpec *lp) {
 // acquisition with unit cost), over a surface that is there
 int check_per_cost(const gp_ctx *g, int type, bool lp) {
     if (!acq_per_cost(type)) return 0;
+    GP_NO_LAPLACE(g, "GP_ACQ_PER_COST");
     if (acq_base(type) == GP_ACQ_LCB) return fail(GP_ERR_ARG, "GP_ACQ_PER_COST: LCB takes no cost");
     if (lp) return fail(GP_ERR_ARG, "GP_ACQ_PER_COST: the penalised acquisition takes no cost");
     if (g->cost.Nc < 1) return fail(GP_ERR_ARG, "GP_ACQ_PER_COST without a cost surface (gp_cost_set)");
@@ -266,6 +268,7 @@ int scores_out(gp_ctx *g, const double *acq, const double *dacq, long M, int D, 
 }
 
 int train_values(gp_ctx *g) {
+    GP_NO_LAPLACE(g, "gp_fmin");   // (y - d alpha: the targets of a Laplace fit are labels)
     // (a resident mean function: m(X_i) + r_i - d alpha_i = y_i - d alpha_i with the RAW targets; K alpha + m(X) directly)
     if (g->fmin_direct) {
         launch_train_mean(g->s, g->dX, g->N, g->kp, g->dAlpha, g->dMu);

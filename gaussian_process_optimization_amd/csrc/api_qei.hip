@@ -52,6 +52,7 @@ extern "C" int gp_qei_rows(gp_t *g, const double *Xq, int q, int include_noise, 
                            double *out, double *dout, double *mean, double *cov) {
     if (!g || !Xq || !out) return fail(GP_ERR_ARG, "null argument");
     GP_FITTED(g);
+    GP_NO_LAPLACE(g, "gp_qei_rows");
     QeiState &st = g->qei;
     if (st.S < 1) return fail(GP_ERR_STATE, "gp_qei_rows: no base samples are resident (gp_qei_set)");
     if (g->P != 1) return fail(GP_ERR_STATE, "gp_qei_rows needs P == 1");

@@ -204,7 +204,7 @@ int ensure_wi(gp_ctx *g) {
     if ((rc = g->dWi.reserve(Npad * Npad))) return rc;
     double *T = g->dT;
     hipStream_t s = g->s;
-    if (g->emulate_fp64 && g->emulate_fit && g->invp_W % 2 == 0) {
+    if (g->emulate_fp64 && g->emulate_fit && g->invp_W % 2 == 0 && !g->lap.on) {   // (a Laplace fit is true fp64 throughout)
         rc = wi_rns(g);
         if (rc == 0) {
             g->wi_valid = true;

@@ -120,6 +120,7 @@ static int sparse_fit_impl(gp_ctx *g, int maxtries) {
     int rc;
     if ((rc = sparse_reserve(g))) return rc;
     sparse_fit_dropped(g);
+    if (g->lap.on) fit_dropped(g);   // a regression fit clears the Laplace state: gp_set_params' noise is back before beta reads it
     const long n = sp.Mzpad, Mz = sp.Mz, N = g->N, Npad = g->Npad;
     const int P = g->P, ntz = (int)(n / GP_TILE), nt = (int)(Npad / GP_TILE);
     const double beta = 1.0 / std::max(g->noise, 1e-8);   // var_dtc.py:80
@@ -272,6 +273,7 @@ extern "C" int gp_sparse_fit_grad(gp_t *g, int maxtries, double *lml, double *dv
 int sparse_fitted(gp_ctx *g) {
     int rc;
     if ((rc = sparse_preamble(g, true))) return rc;
+    GP_NO_LAPLACE(g, "the sparse model's entries");   // (they read the context's noise, which is 1 in that state; gp_sparse_fit clears it)
     if (!g->sp.fitted) return fail(GP_ERR_STATE, "gp_sparse_fit first");
     return 0;
 }

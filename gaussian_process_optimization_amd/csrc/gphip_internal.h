@@ -489,6 +489,27 @@ size_t lml_grad_lds_bytes(int D, int gower, int P);
 void launch_lml_grad(hipStream_t s, const double *X, long N, long Npad, const KernParams &kp, int ard, int d0, const double *alpha,
                      int P, const double *Wi, long ldw, double *partial, double *out, int nb = 1, const KernParams *kpt = nullptr,
                      long sV = 0, long sW = 0, long sP = 0, long so = 0, long sX = 0);
+// the same pass with the weights of the Laplace marginal, dL_dK = 1/2 (a a^T + a u^T + u a^T - R): au [2, Npad] holds a and u,
+// R [Npad, ldr] = (K + W^-1)^-1; one member, no Gower model.  LDS: lml_grad_lds_bytes(D, 0, 2)
+void launch_lap_grad(hipStream_t s, const double *X, long N, long Npad, const KernParams &kp, int ard, int d0, const double *au,
+                     const double *R, long ldr, double *partial, double *out);
+
+// ---- laplace.hip: GP classification, Laplace's method with a probit link (api_laplace.hip) -----------------------------------
+// labels y in {-1, +1}; every vector has Npad entries; K is the full Npad x Npad matrix of launch_kbuild(full = 1, diag_add = 0)
+void launch_lap_site(hipStream_t s, const double *y, const double *f, long N, long Npad, double *W, double *sw, double *b, double *t);
+// out_i = scale_i sum_j M[i, j] v_j (scale null: 1), or from_i - that; i, j < N
+void launch_lap_matvec(hipStream_t s, const double *M, long ld, const double *v, long N, const double *scale, const double *from,
+                       double *out);
+void launch_lap_bbuild(hipStream_t s, double *A, long lda, const double *K, long ldk, const double *sw, long N, long Npad);
+void launch_lap_dir(hipStream_t s, const double *b, const double *sw, const double *w, const double *a, long N, long Npad, double *da);
+#define LAP_RES_DOUBLES 8   // res of launch_lap_psi: psi, -a.f / 2, sum log p, max |da|, max |a + step da|; of launch_lap_wrange: min, max
+void launch_lap_psi(hipStream_t s, const double *y, const double *a, const double *da, const double *f, const double *df, double step,
+                    long N, double *res);
+void launch_lap_accept(hipStream_t s, double *a, const double *da, double *f, const double *df, double step, long N);
+void launch_lap_wrange(hipStream_t s, const double *W, long N, double *res);
+void launch_lap_scale_factor(hipStream_t s, double *A, long lda, double *invL, const double *sw, long N, long Npad);
+void launch_lap_ltvec(hipStream_t s, const double *A, long lda, const double *a, long N, long Npad, double *z);
+void launch_lap_s2(hipStream_t s, const double *R, long ldr, const double *W, const double *t, long N, long Npad, double *s2);
 void launch_predict_grad(hipStream_t s, const double *Xs, long M, const double *X, long N, const KernParams &kp,
                          const double *alpha, long lda_, int P, const double *beta, long ldb, double *dmdx,
                          double *dvdx);

@@ -100,7 +100,9 @@ void launch_symmetrize(hipStream_t s, double *A, long ld, long n, int nb, long s
 #define NACC (GCH + 2)
 // partial[tile][NACC]: [0] sum K dL_dK (w), [1] sum diag dL_dK, [2+q] sum w g dL_dK dq^2 (ARD) or [2] sum w g dL_dK r^2 (iso)
 // FP: the family pair GP_FAMILY_PAIR(kp.kernel), chosen on the host (gphip_internal.h)
-template <int FP>
+// LAP = 1, the weights of the Laplace marginal (laplace.hip, R&W Algorithm 5.1): alpha holds the two rows a and u, Wi holds
+// R = (K + W^-1)^-1, and dL_dK = 1/2 (a a^T + a u^T + u a^T - R).  The Gaussian instances (LAP = 0) compile to what they were.
+template <int FP, int LAP = 0>
 __device__ __forceinline__ void lml_grad_tile_body(const double *X, long N, const KernParams &kp, int ard, int d0, const double *alpha,
                                                    long lda_, int P, const double *Wi, long ldw, double *partial) {
     extern __shared__ __attribute__((aligned(16))) double sm[];
@@ -173,8 +175,9 @@ __device__ __forceinline__ void lml_grad_tile_body(const double *X, long N, cons
                 }
             }
             double aa = 0.0;
-            for (int p = 0; p < P; ++p) aa = fma(ai[p * GP_TILE + r], aj[p * GP_TILE + c], aa);
-            const double dLdK = 0.5 * (aa - (double)P * w2[e]);  // exact_gaussian_inference.py:70
+            if (LAP) aa = fma(ai[r], aj[c] + aj[GP_TILE + c], ai[GP_TILE + r] * aj[c]);
+            else for (int p = 0; p < P; ++p) aa = fma(ai[p * GP_TILE + r], aj[p * GP_TILE + c], aa);
+            const double dLdK = 0.5 * (aa - (LAP ? 1.0 : (double)P) * w2[e]);  // exact_gaussian_inference.py:70
             double kv, gv;
             gp_k_and_g_pair<FP>(kp.kernel, kp.variance, s, kv, gv);
             const bool diag = (gcc == gr);
@@ -216,6 +219,13 @@ __global__ __launch_bounds__(256) void lml_grad_tile_kernel(const double *X, lon
                                                             const double *alpha, long lda_, int P, const double *Wi,
                                                             long ldw, double *partial) {
     lml_grad_tile_body<FP>(X, N, kp, ard, d0, alpha, lda_, P, Wi, ldw, partial);
+}
+// the Laplace weights: au = the rows a and u (P = 2 in the staging), R in Wi's place
+template <int FP>
+__global__ __launch_bounds__(256) void lml_grad_tile_lap_kernel(const double *X, long N, KernParams kp, int ard, int d0,
+                                                                const double *au, long lda_, const double *R, long ldr,
+                                                                double *partial) {
+    lml_grad_tile_body<FP, 1>(X, N, kp, ard, d0, au, lda_, 2, R, ldr, partial);
 }
 // member z = blockIdx.z of gp_fit_grad_batch: inputs X + z sX (0: shared), parameters kpt[z], alpha + z sV, Ky^-1 at Wi + z sW,
 // partials at partial + z sP
@@ -288,6 +298,22 @@ void launch_lml_grad(hipStream_t s, const double *X, long N, long Npad, const Ke
     else
         GP_LAUNCH(lml_grad_tile_kernel<0>, dim3((unsigned)ntile, split), dim3(256), shm, s, X, N, kp, ard, d0, alpha, Npad, P, Wi,
                   ldw, partial);
+    GP_LAUNCH(sum_partials_kernel, dim3(NACC), dim3(1024), 0, s, partial, ntile * split, NACC, out);
+}
+
+// The same pass with the Laplace weights (one member, never a Gower model): au [2, Npad] = a, u; R [Npad, ldr]
+void launch_lap_grad(hipStream_t s, const double *X, long N, long Npad, const KernParams &kp, int ard, int d0, const double *au,
+                     const double *R, long ldr, double *partial, double *out) {
+    const int nt = (int)(Npad / GP_TILE);
+    const long ntile = (long)nt * (nt + 1) / 2;
+    const size_t shm = lml_grad_lds_bytes(kp.D, 0, 2) - sizeof(double) * 4 * NACC;
+    const unsigned split = ntile < 256 ? 4u : 1u;
+    if (GP_FAMILY_PAIR(kp.kernel))
+        GP_LAUNCH(lml_grad_tile_lap_kernel<1>, dim3((unsigned)ntile, split), dim3(256), shm, s, X, N, kp, ard, d0, au, Npad, R, ldr,
+                  partial);
+    else
+        GP_LAUNCH(lml_grad_tile_lap_kernel<0>, dim3((unsigned)ntile, split), dim3(256), shm, s, X, N, kp, ard, d0, au, Npad, R, ldr,
+                  partial);
     GP_LAUNCH(sum_partials_kernel, dim3(NACC), dim3(1024), 0, s, partial, ntile * split, NACC, out);
 }
 

@@ -15,7 +15,13 @@ observations, scored on the device (``gp_feas_table`` + ``GP_ACQ_TIMES_FEAS`` fo
 optimiser's calls); while no observation is feasible the rule is the probability of feasibility alone (``GP_ACQ_POF``).
 ``generation`` tells the routes when a cached table is stale.
 
-When every constraint model is our exact ``GPModel`` on one device ``log_probability`` runs through ``gp_feas_rows``; otherwise
+A constraint known only as a yes / no -- the simulation diverged, the build failed -- is a BINARY column (``kinds``): it holds 1
+where the constraint was violated and 0 where it was satisfied, is not standardised (c_mean 0, c_std 1), has bound 0, and its
+model is a ``GPClassModel`` (probit classifier, Laplace fit).  That model answers with the latent mean m and sqrt(s^2 + 1), so
+``Phi((0 - m) / sqrt(s^2 + 1))`` -- the very term above -- is the probability that the constraint is satisfied, and the device
+fold takes the classifier's handle as it takes a regression handle.
+
+When every constraint model is our exact ``GPModel`` (or ``GPClassModel``) on one device ``log_probability`` runs through ``gp_feas_rows``; otherwise
 (a foreign model) the same formulas run in NumPy on top of ``predict_withGradients`` -- which is also the host comparator of the
 device route (``host=True``).
 """
@@ -24,7 +30,7 @@ from scipy.special import log_ndtr
 
 from . import _lib
 from . import gpmodel as _gpmodel
-from .gpmodel import GPModel
+from .gpmodel import GPModel, GPClassModel
 
 _VAR_FLOOR = 1e-10
 _HALF_LOG_2PI = 0.5 * np.log(2 * np.pi)
@@ -37,9 +43,13 @@ def _normaliser(gp):
 
 class FeasibilityModel(object):
     """``num_constraints`` constraint GPs (``GPModel(device=device, **gpmodel_kwargs)`` each; ``models`` may be replaced by any
-    objects with ``updateModel`` and ``predict_withGradients``), upper bounds ``bounds`` (a scalar or one per constraint)."""
+    objects with ``updateModel`` and ``predict_withGradients``), upper bounds ``bounds`` (a scalar or one per constraint).
+    ``kinds``: per column ``'value'`` (the default: a real-valued ``c_k(x) <= bounds[k]``) or ``'binary'`` (1 = violated, 0 =
+    satisfied; bound 0, no standardisation, a ``GPClassModel``)."""
 
-    def __init__(self, num_constraints, bounds=0.0, device=0, **gpmodel_kwargs):
+    _CLASS_KWARGS = ("optimizer", "max_iters", "optimize_restarts", "verbose", "ARD")
+
+    def __init__(self, num_constraints, bounds=0.0, kinds=None, device=0, **gpmodel_kwargs):
         K = int(num_constraints)
         if not 1 <= K <= _lib.GP_FEAS_MAX:
             raise ValueError("between 1 and %d constraints, got %r" % (_lib.GP_FEAS_MAX, num_constraints))
@@ -49,8 +59,19 @@ class FeasibilityModel(object):
         self.bounds = np.broadcast_to(np.asarray(bounds, dtype=float), (K,)).copy()
         if not np.all(np.isfinite(self.bounds)):
             raise ValueError("the bounds must be finite")
+        if kinds is None:
+            kinds = ('value',) * K
+        if isinstance(kinds, str):
+            kinds = (kinds,) * K
+        self.kinds = tuple(kinds)
+        if len(self.kinds) != K or any(k not in ('value', 'binary') for k in self.kinds):
+            raise ValueError("kinds takes 'value' or 'binary' for each of the %d constraints, got %r" % (K, kinds))
+        self.binary = np.array([k == 'binary' for k in self.kinds])
+        self.bounds[self.binary] = 0.0       # a binary column's bound is 0 on the latent scale
         self.device = device
-        self.models = [GPModel(device=device, **gpmodel_kwargs) for _ in range(K)]
+        class_kwargs = {k: v for k, v in gpmodel_kwargs.items() if k in self._CLASS_KWARGS}
+        self.models = [GPClassModel(device=device, **class_kwargs) if b else GPModel(device=device, **gpmodel_kwargs)
+                       for b in self.binary]
         self.generation = 0
         self.c_mean, self.c_std = np.zeros(K), np.ones(K)
         self.feasible_rows = np.empty(0, dtype=np.int64)
@@ -63,15 +84,23 @@ class FeasibilityModel(object):
         C = np.atleast_2d(np.asarray(C, dtype=float))
         if C.shape[1] != self.num_constraints:
             raise ValueError("expected %d constraint columns, got %d" % (self.num_constraints, C.shape[1]))
-        return np.all(C <= self.bounds, axis=1)
+        self._check_binary(C)
+        return np.all(np.where(self.binary, C == 0.0, C <= self.bounds), axis=1)
+
+    def _check_binary(self, C):
+        if self.binary.any() and not np.all((C[:, self.binary] == 0.0) | (C[:, self.binary] == 1.0)):
+            raise ValueError("a binary constraint column holds 1 (violated) or 0 (satisfied)")
 
     def violation(self, C):
         """How far each row is from feasibility: the sum over the constraints of max(c_k - bounds[k], 0) in units of column k's
-        standard deviation over the rows of ``C`` (0 for a feasible row).  THE definition of 'least violating'
-        (``BayesianOptimization`` reports the row that minimises it while no observation is feasible)."""
+        standard deviation over the rows of ``C`` (0 for a feasible row); a binary column adds its label, 1 where violated.  THE
+        definition of 'least violating' (``BayesianOptimization`` reports the row that minimises it while no observation is
+        feasible)."""
         C = np.atleast_2d(np.asarray(C, dtype=float))
+        self._check_binary(C)
         std = C.std(axis=0)
-        return (np.maximum(C - self.bounds, 0.0) / np.where(std > 0, std, 1.0)).sum(axis=1)
+        value = np.maximum(C - self.bounds, 0.0) / np.where(std > 0, std, 1.0)
+        return np.where(self.binary, C, value).sum(axis=1)
 
     def update(self, X, C):
         """Fit constraint GP k to (X, standardised C[:, k]) and move ``generation``; ``feasible_rows`` are the rows of X (the
@@ -80,8 +109,10 @@ class FeasibilityModel(object):
         C = np.atleast_2d(np.asarray(C, dtype=float))
         if C.shape != (X.shape[0], self.num_constraints):
             raise ValueError("expected constraint values [%d, %d], got %s" % (X.shape[0], self.num_constraints, C.shape))
+        self._check_binary(C)
         mean, std = C.mean(axis=0), C.std(axis=0)
         std = np.where(std > 0, std, 1.0)
+        mean, std = np.where(self.binary, 0.0, mean), np.where(self.binary, 1.0, std)   # labels are not standardised
         for k, m in enumerate(self.models):
             m.updateModel(X, ((C[:, k] - mean[k]) / std[k])[:, None], None, None)
         self.c_mean, self.c_std = mean, std
@@ -92,10 +123,11 @@ class FeasibilityModel(object):
 
     # ---- where it runs -----------------------------------------------------------------------------------------------------
     def _device_models(self, device=None):
-        """True when every constraint model is our exact GPModel, fitted, one output, on one device (``device`` when given)."""
+        """True when every constraint model is our exact GPModel or GPClassModel, fitted, one output, on one device (``device``
+        when given)."""
         dev = self.models[0].device if device is None else device
         for m in self.models:
-            if type(m) is not _gpmodel.GPModel or m.sparse or m.model is None or m.device != dev:
+            if type(m) not in (_gpmodel.GPModel, _gpmodel.GPClassModel) or m.sparse or m.model is None or m.device != dev:
                 return False
             if m.model.output_dim != 1 or not hasattr(m.model.kern, "_kernel_id"):
                 return False

@@ -304,3 +304,68 @@ class GPModel_MCMC(BOModel):
 
     def get_model_parameters_names(self):
         return self.model.parameter_names_flat().tolist()
+
+
+class GPClassModel(BOModel):
+    """A GP classifier as a BO surrogate (``GPClassification``: Bernoulli likelihood, probit link, Laplace fit on the device), in
+    the shape ``FeasibilityModel`` takes a constraint model in.  ``updateModel(X, Y, ...)`` takes labels in {0, 1};
+    ``predict`` / ``predict_withGradients`` return the LATENT mean and sqrt(s^2 + 1) (``with_noise=False``: sqrt(s^2)), so that
+    Phi((0 - mean) / std) is the probability of label 0 -- the term the constraint fold evaluates.  While the labels hold one
+    class only the model is fitted at its current hyper-parameters without a search."""
+    analytical_gradient_prediction = True
+    sparse = False
+
+    def __init__(self, kernel=None, optimizer='bfgs', max_iters=1000, optimize_restarts=5, verbose=True, ARD=False, device=0):
+        vars(self).update(kernel=kernel, optimizer=optimizer, max_iters=max_iters, optimize_restarts=optimize_restarts,
+                          verbose=verbose, ARD=ARD, device=device, model=None)
+
+    def _create_model(self, X, Y):
+        from .gp_classification import GPClassification
+        self.input_dim = X.shape[1]
+        chosen, self.kernel = self.kernel, None
+        if chosen is None:
+            chosen = _kern.Matern52(self.input_dim, variance=1., ARD=self.ARD)
+        self.model = GPClassification(X, Y, kernel=chosen, device=self.device)
+
+    def updateModel(self, X_all, Y_all, X_new, Y_new):
+        if self.model is not None:
+            self.model.set_XY(X_all, Y_all)
+        else:
+            self._create_model(np.asarray(X_all, dtype=float), Y_all)
+        labels = np.ravel(self.model.Y)
+        if self.max_iters <= 0 or labels.min() == labels.max():
+            return
+        search = dict(optimizer=self.optimizer, max_iters=self.max_iters)
+        if self.optimize_restarts == 1:
+            self.model.optimize(messages=False, ipython_notebook=False, **search)
+        else:
+            self.model.optimize_restarts(num_restarts=self.optimize_restarts, verbose=self.verbose, **search)
+
+    def predict(self, X, with_noise=True):
+        mean, var = GPRegression.predict(self.model, np.atleast_2d(X), include_likelihood=with_noise)
+        return mean, np.sqrt(np.maximum(var, _VAR_FLOOR))
+
+    def predict_proba(self, X):
+        """p(label = 1 | x) [M, 1]."""
+        return self.model.predict(np.atleast_2d(X))[0]
+
+    def predict_withGradients(self, X):
+        X = np.atleast_2d(X)
+        gp = self.model
+        few = gp._few_rows(X)
+        if few is not None:
+            mean, var, jac_mean, jac_var = gp._h.predict_rows(few, include_noise=True, grad=True)
+        else:
+            mean, var = GPRegression.predict(gp, X, include_likelihood=True)
+            jac_mean, jac_var = gp.predictive_gradients(X)
+        std = np.sqrt(np.maximum(var, _VAR_FLOOR))
+        return mean, std, jac_mean[..., 0], jac_var / (2 * std)
+
+    def get_fmin(self):
+        raise NotImplementedError("a classifier has no observed minimum")
+
+    def get_model_parameters(self):
+        return np.atleast_2d(self.model[:])
+
+    def get_model_parameters_names(self):
+        return self.model.parameter_names_flat().tolist()

@@ -1189,6 +1189,43 @@ int gp_kg_acq_argbest(gp_t *gp, double y_std, int sense, int64_t *idx, double *v
 int gp_kg_acq_topk(gp_t *gp, double y_std, int sense, int k, int64_t *idx, double *val);
 int gp_kg_rows(gp_t *gp, const double *Xs, int64_t M, double y_std, double *out, double *dout);
 
+/* ---- GP classification: Bernoulli likelihood, probit link, Laplace's approximation (api_laplace.hip) --------------------------
+ * Rasmussen & Williams, Algorithms 3.1 and 5.1.  labels [N] in {-1, +1} (anything else: GP_ERR_ARG); X and the kernel are the
+ * context's (gp_set_data with P = 1 -- its Y is not read -- and gp_set_params, whose noise is ignored: K carries no noise and no
+ * 1e-8).  With z = y f and n = phi(z) / Phi(z) the sites are log p = log Phi(z), g = y n, W = n (n + z) floored at 1e-20,
+ * t = y (n (z^2 - 1) + 3 z n^2 + 2 n^3), n formed in log space.
+ * gp_laplace_fit: Newton's iteration in a = K^-1 f from a = 0; per step the sites, B = I + W^1/2 K W^1/2 and its factorisation
+ * (the one gp_fit takes at that N; no jitter ladder: B has eigenvalues >= 1), two triangular solves, one product K da; the step
+ * is halved while psi(a) = -a.K a / 2 + sum log p decreases.  It stops when the accepted step is at most 1e-10 of max |a| or psi
+ * has not moved by 1e-13 of its size twice in a row.  *logz = -a.f / 2 + sum log p - log|B| / 2, *logdet_b = log|B|, *iters and
+ * *halvings the steps and halvings taken, *converged 1 (out-parameters may be NULL).  Returns 0; GP_LAPLACE_NOT_CONVERGED when
+ * max_iter (1 .. GP_LAPLACE_MAX_ITER) steps did not suffice or the line search failed (30 halvings; gp_last_error says which);
+ * another positive code when a pivot of B failed (non-finite inputs);
+ * either way no fit is left.  On success the context is "Laplace-fitted": its factor is that of K + W^-1 (diag(W^-1/2) L), its
+ * alpha is a, its noise 1, so gp_predict, gp_predict_rows, gp_predict_grad, the candidate tables, gp_feas_* and gp_acq_rows_feas
+ * answer with the latent posterior -- with include_noise variance s^2 + 1, as p(y = 1 | x) = Phi(m / sqrt(1 + s^2)) takes it.
+ * gp_set_data, gp_set_params and every regression fit clear the state (and put gp_set_params' noise back).  Refused on such a
+ * context (GP_ERR_STATE): gp_append, gp_fmin, gp_fmin_rows, gp_lml_grad, gp_lml_grad_x, gp_get_dl_dk, gp_mean_set, gp_mean_grad,
+ * gp_paths_set, gp_qei_rows, the knowledge-gradient and entropy-search entries, gp_mes_set / gp_mes_logsurv / gp_mes_bracket and
+ * GP_ACQ_MES, gp_cost_set and GP_ACQ_PER_COST, gp_group_fmin and the gp_group_acq_* entries (gp_group_set_data, _set_params and
+ * _fit clear the state), the batched fits, the sparse model's entries over a sparse fit (gp_sparse_fit itself clears the state)
+ * and gp_comm_bcast_fit from such a root.  gp_kernel_matrix drops the state with the factor it overwrites.  The fit itself is refused
+ * (GP_ERR_STATE) with P != 1, a Gower kernel, an output warp or a mean function.  Always true fp64; the same inputs give the
+ * same bits.  Memory: one more Npad x Npad matrix (K) beside the factor's.
+ * gp_laplace_fit_grad: the fit, then grad [1 + nls] = d logz / d (variance, lengthscale(s)) (nls = 1, or D with ard), implicit
+ * part included: sum_ij G_ij dK_ij with G = (a a^T - R + u a^T + a u^T) / 2, R = (K + W^-1)^-1, s2 = diag(K - K R K) t / 2,
+ * u = (I - R K) s2.  D beyond what the gradient pass's LDS takes: GP_ERR_ARG before the fit.
+ * gp_laplace_info: steps, halvings and min / max of W of the last fit; gp_laplace_get_mode: f [N] at the mode and W [N] (either
+ * may be NULL).  Both need a Laplace-fitted context (GP_ERR_STATE). */
+#define GP_LAPLACE_MAX_ITER 1000
+#define GP_LAPLACE_NOT_CONVERGED 1073741824
+int gp_laplace_fit(gp_t *gp, const double *labels, int max_iter, double *logz, double *logdet_b, int *iters, int *halvings,
+                   int *converged);
+int gp_laplace_fit_grad(gp_t *gp, const double *labels, int max_iter, double *logz, double *logdet_b, int *iters, int *halvings,
+                        int *converged, double *grad);
+int gp_laplace_info(gp_t *gp, int *iters, int *halvings, double *wmin, double *wmax);
+int gp_laplace_get_mode(gp_t *gp, double *f, double *W);
+
 #ifdef __cplusplus
 }
 #endif
