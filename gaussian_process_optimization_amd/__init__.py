@@ -43,6 +43,8 @@ from . import joint_ei
 from .joint_ei import AcquisitionQEI, JointBatch
 from . import knowledge_gradient
 from .knowledge_gradient import AcquisitionKG
+from . import noisy_ei
+from .noisy_ei import AcquisitionNEI
 from . import posterior_paths
 from .posterior_paths import PosteriorPaths
 from . import max_value
@@ -63,7 +65,7 @@ likelihoods = _types.SimpleNamespace(Gaussian=Gaussian, Bernoulli=Bernoulli)
 
 __all__ = ["GPClassification", "GPClassModel", "Bernoulli", "kern", "mappings", "models", "methods", "likelihoods", "acquisitions", "GPRegression", "SparseGPRegression", "GPModel", "BOModel", "GPModel_MCMC", "priors", "HMC",
            "AcquisitionEI_MCMC", "AcquisitionMPI_MCMC", "AcquisitionLCB_MCMC",
-           "AcquisitionTS", "AcquisitionQEI", "JointBatch", "joint_ei", "AcquisitionKG", "knowledge_gradient", "posterior_paths", "PosteriorPaths", "AcquisitionMES", "max_value", "MinValueSampler", "AcquisitionEntropySearch", "entropy_search", "McmcSampler", "AffineInvariantEnsembleSampler",
+           "AcquisitionTS", "AcquisitionQEI", "JointBatch", "joint_ei", "AcquisitionKG", "knowledge_gradient", "AcquisitionNEI", "noisy_ei", "posterior_paths", "PosteriorPaths", "AcquisitionMES", "max_value", "MinValueSampler", "AcquisitionEntropySearch", "entropy_search", "McmcSampler", "AffineInvariantEnsembleSampler",
            "InputWarpedGP", "InputWarpedGPModel", "input_warping", "WarpedGP", "WarpedGPModel", "warping_functions",
            "AcquisitionEI", "AcquisitionLCB", "AcquisitionMPI", "AcquisitionBase", "AcquisitionLP",
            "LocalPenalization", "estimate_L", "BayesianOptimization",

@@ -25,6 +25,8 @@ GP_ACQ_MES = 4               # max-value entropy search over the handle's reside
 GP_PATHS_MAX_S, GP_PATHS_MAX_F, GP_PATHS_MAX_ROWS = 64, 4096, 8   # posterior paths: paths, features, locations per rows call
 GP_QEI_MAX_S, GP_QEI_MAX_Q = 4096, 8   # joint expected improvement: base samples resident, locations of a batch
 GP_KG_MAX_A = 256                      # knowledge gradient: discretisation points resident
+GP_NEI_MAX_S = 64                      # noisy EI: fantasies resident
+GP_NEI_MAX_ROWS = 8                    # ... and locations of a fused gp_nei_rows call
 GP_MES_MAX_K, GP_MES_MAX_G = 64, 64   # samples of the minimum's value; trial values per gp_mes_logsurv call
 GP_ACQ_TIMES_FEAS = 0x200    # or-ed into a table scoring call's type: the scores are multiplied by the cached probability of feasibility
 GP_FEAS_MAX = 8
@@ -236,6 +238,15 @@ SIGNATURES = [
     ("gp_kg_acq_argbest", ctypes.c_int, [_vp, ctypes.c_double, ctypes.c_int, c_int64_p, c_double_p]),
     ("gp_kg_acq_topk", ctypes.c_int, [_vp, ctypes.c_double, ctypes.c_int, ctypes.c_int, c_int64_p, c_double_p]),
     ("gp_kg_rows", ctypes.c_int, [_vp, _vp, ctypes.c_int64, ctypes.c_double, _vp, _vp]),
+    ("gp_nei_set", ctypes.c_int, [_vp, _vp, ctypes.c_int, _vp, _vp]),
+    ("gp_nei_info", ctypes.c_int, [_vp, c_int_p, c_double_p, c_double_p]),
+    ("gp_nei_get", ctypes.c_int, [_vp, _vp, _vp]),
+    ("gp_nei_stats", ctypes.c_int, [_vp, c_int64_p, c_int_p, c_int_p]),
+    ("gp_nei_table", ctypes.c_int, [_vp, ctypes.c_double, ctypes.c_double, ctypes.c_double, c_double_p]),
+    ("gp_nei_argbest", ctypes.c_int, [_vp, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_int, c_int64_p, c_double_p]),
+    ("gp_nei_topk", ctypes.c_int, [_vp, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_int, ctypes.c_int, c_int64_p,
+                                   c_double_p]),
+    ("gp_nei_rows", ctypes.c_int, [_vp, _vp, ctypes.c_int64, ctypes.c_double, ctypes.c_double, ctypes.c_double, _vp, _vp]),
     ("gp_laplace_fit", ctypes.c_int, [_vp, c_double_p, ctypes.c_int, c_double_p, c_double_p, c_int_p, c_int_p, c_int_p]),
     ("gp_laplace_fit_grad", ctypes.c_int, [_vp, c_double_p, ctypes.c_int, c_double_p, c_double_p, c_int_p, c_int_p, c_int_p,
                                            c_double_p]),
@@ -543,6 +554,90 @@ class KgEntries(object):
         rc = h.lib.gp_kg_rows(h.h, Xs.ctypes.data, Xs.shape[0], float(y_std), out.ctypes.data, dout.ctypes.data if grad else None)
         if rc:
             check(h.lib, rc, "gp_kg_rows")
+        return (out, dout) if grad else out
+
+
+class NeiEntries(object):
+    """Noisy expected improvement's entries of a handle (include/gphip.h, gp_nei_*).  The handle is the TWIN: a near-noiseless fit
+    of the model's kernel over the model's inputs, on which the fantasies become resident.  ``handle.nei`` makes one; it holds
+    nothing but the handle."""
+
+    def __init__(self, handle):
+        self.handle = handle
+
+    def set(self, model, Z, E):
+        """Draw S fantasies of the noiseless training values from the standard normals ``Z``, ``E`` [S, N] through the factor of
+        ``model`` (a fitted Handle over the same inputs and kernel) and this handle's.  Nothing is factored."""
+        h = self.handle
+        Z = as_f64(Z, 2)
+        E = as_f64(E, 2)
+        if Z.shape != E.shape or Z.shape[1] != h.N:
+            raise ValueError("expected Z and E of one shape [S, %d], got %s and %s" % (h.N, Z.shape, E.shape))
+        check(h.lib, h.lib.gp_nei_set(h.h, model.h, Z.shape[0], Z.ctypes.data, E.ctypes.data), "gp_nei_set")
+
+    def clear(self):
+        h = self.handle
+        check(h.lib, h.lib.gp_nei_set(h.h, None, 0, None, None), "gp_nei_set")
+
+    def info(self):
+        """(S, d_model, d_twin): the fantasies resident (0: none, or a new fit dropped them) and the two factors' diagonals."""
+        h = self.handle
+        S, d, d0 = ctypes.c_int(0), ctypes.c_double(0.0), ctypes.c_double(0.0)
+        check(h.lib, h.lib.gp_nei_info(h.h, ctypes.byref(S), ctypes.byref(d), ctypes.byref(d0)), "gp_nei_info")
+        return S.value, d.value, d0.value
+
+    def get(self):
+        """(F [S, N], fstar [S]): the fantasies and their minima, normalised."""
+        h = self.handle
+        S = self.info()[0]
+        F = np.empty((max(S, 1), h.N))
+        fstar = np.empty(max(S, 1))
+        check(h.lib, h.lib.gp_nei_get(h.h, F.ctypes.data, fstar.ctypes.data), "gp_nei_get")
+        return F[:S], fstar[:S]
+
+    def stats(self):
+        """Route checks: how often the handle's inverse factor was built, and of the last pass of the last ``rows`` call the kernels
+        launched and how many of them read the inverse factor (0, 0: the table route)."""
+        h = self.handle
+        b, n, r = ctypes.c_int64(0), ctypes.c_int(0), ctypes.c_int(0)
+        check(h.lib, h.lib.gp_nei_stats(h.h, ctypes.byref(b), ctypes.byref(n), ctypes.byref(r)), "gp_nei_stats")
+        return dict(linv_builds=b.value, launches=n.value, reads=r.value)
+
+    def table(self, par=0.0, y_mean=0.0, y_std=1.0):
+        """+NEI of the resident candidates, [M, 1]."""
+        h = self.handle
+        out = np.empty((h.M, 1))
+        check(h.lib, h.lib.gp_nei_table(h.h, float(par), float(y_mean), float(y_std), dptr(out)), "gp_nei_table")
+        return out
+
+    def argbest(self, sense, par=0.0, y_mean=0.0, y_std=1.0):
+        h = self.handle
+        idx, val = ctypes.c_int64(), ctypes.c_double()
+        check(h.lib, h.lib.gp_nei_argbest(h.h, float(par), float(y_mean), float(y_std), int(sense), ctypes.byref(idx), ctypes.byref(val)),
+              "gp_nei_argbest")
+        return idx.value, val.value
+
+    def topk(self, sense, k, par=0.0, y_mean=0.0, y_std=1.0):
+        h = self.handle
+        idx = np.empty(k, dtype=np.int64)
+        val = np.empty(k)
+        check(h.lib, h.lib.gp_nei_topk(h.h, float(par), float(y_mean), float(y_std), int(sense), int(k), idx.ctypes.data_as(c_int64_p),
+                                       dptr(val)), "gp_nei_topk")
+        return idx, val
+
+    def rows(self, Xs, par=0.0, y_mean=0.0, y_std=1.0, grad=False):
+        """-NEI at the locations ``Xs`` [M, D] given by value, [M, 1]; with ``grad`` its gradient [M, D] as well (up to eight
+        locations: the fused rows path)."""
+        h = self.handle
+        Xs = np.ascontiguousarray(Xs, dtype=np.float64)
+        if Xs.ndim != 2 or Xs.shape[1] != h.D:
+            raise ValueError("expected locations of shape [M, %d], got %s" % (h.D, Xs.shape))
+        out = np.empty((Xs.shape[0], 1))
+        dout = np.empty((Xs.shape[0], h.D)) if grad else None
+        rc = h.lib.gp_nei_rows(h.h, Xs.ctypes.data, Xs.shape[0], float(par), float(y_mean), float(y_std), out.ctypes.data,
+                               dout.ctypes.data if grad else None)
+        if rc:
+            check(h.lib, rc, "gp_nei_rows")
         return (out, dout) if grad else out
 
 
@@ -1616,6 +1711,11 @@ class Handle(object):
     @property
     def kg(self):
         return KgEntries(self)
+
+    # -- noisy expected improvement (include/gphip.h, gp_nei_*): ``NeiEntries``' methods on the TWIN, reached as ``handle.nei.<entry>``
+    @property
+    def nei(self):
+        return NeiEntries(self)
 
     # -- the mean function m(x) = x^T A + b of the exact GP (include/gphip.h, gp_mean_*) -----------------------------------
     def mean_set(self, A=None, b=None):

@@ -28,6 +28,7 @@ from .gpmodel import GPModel
 from .input_warped_gp import InputWarpedGPModel
 from .joint_ei import AcquisitionQEI, JointBatch
 from .knowledge_gradient import AcquisitionKG
+from .noisy_ei import AcquisitionNEI
 from .parameterization import lbfgsb_lockstep, SCIPY_DEFAULT
 
 
@@ -410,7 +411,15 @@ class BayesianOptimization(object):
     256), ``kg_table_size`` (10000 uniform locations the lowest posterior means are taken from) and ``sampler_seed`` scores the
     expected decrease of the minimum of the posterior mean (``AcquisitionKG``): the acquisition for noisy observations, which reads
     no f_min.  It has gradients, and ``parallel_anchors=True`` works.  Sequential evaluator only: a batch (``batch_size`` > 1 with
-    any other evaluator) raises ``InvalidConfigError``; a cost model and ``constraint_function`` raise ``NotImplementedError``."""
+    any other evaluator) raises ``InvalidConfigError``; a cost model and ``constraint_function`` raise ``NotImplementedError``.
+
+    Noisy expected improvement (an addition): ``acquisition_type='NEI'`` with the keywords ``num_fantasies`` (16 draws, at most 64),
+    ``twin_noise`` (1e-6, the noise of the near-noiseless twin fit) and ``sampler_seed`` scores EI averaged over draws of the
+    noiseless function values at the observations, each with its own incumbent (``AcquisitionNEI``): EI for noisy observations,
+    where plain EI plugs in the lowest posterior mean as if it were known.  It has gradients, and ``parallel_anchors=True`` works;
+    the 'sequential', 'random' and 'thompson_sampling' evaluators take it.  ``exact_feval=True`` (no noise to integrate over) and
+    'local_penalization' raise ``InvalidConfigError``; a cost model, ``constraint_function``, and an MCMC, sparse, warped or Gower
+    model or a mean function raise ``NotImplementedError``."""
 
     def __init__(self, f, domain=None, constraints=None, cost_withGradients=None, model_type='GP', X=None, Y=None,
                  initial_design_numdata=5, initial_design_type='random', acquisition_type='EI', normalize_Y=True,
@@ -448,6 +457,16 @@ class BayesianOptimization(object):
         if kg and constrained:
             raise NotImplementedError("the knowledge gradient (KG) takes no black-box constraints: use acquisition_type 'EI' or "
                                       "'MPI' with constraint_function")
+        nei = isinstance(acquisition, AcquisitionNEI) or (acquisition is None and acquisition_type == 'NEI')
+        if nei and exact_feval:
+            raise InvalidConfigError("noisy expected improvement (NEI) integrates over the observation noise: exact_feval=True "
+                                     "leaves none (use acquisition_type 'EI')")
+        if nei and evaluator_type == 'local_penalization' and batch_size > 1:
+            raise InvalidConfigError("noisy expected improvement (NEI) is not penalised: use the 'sequential', 'random' or "
+                                     "'thompson_sampling' evaluator")
+        if nei and constrained:
+            raise NotImplementedError("noisy expected improvement (NEI) takes no black-box constraints: use acquisition_type 'EI' "
+                                      "or 'MPI' with constraint_function")
         if joint and constrained:
             raise NotImplementedError("joint expected improvement (qEI) takes no black-box constraints: use acquisition_type 'EI' "
                                       "or 'MPI' with constraint_function")
@@ -531,6 +550,11 @@ class BayesianOptimization(object):
                                              num_points=kwargs.get('num_kg_points', 64),
                                              kg_table_size=kwargs.get('kg_table_size', 10000),
                                              sampler_seed=kwargs.get('sampler_seed', None), cost_withGradients=cost_withGradients)
+        elif acquisition_type == 'NEI':
+            self.acquisition = AcquisitionNEI(self.model, self.space, self.acquisition_optimizer, jitter=jitter,
+                                              num_fantasies=kwargs.get('num_fantasies', 16),
+                                              twin_noise=kwargs.get('twin_noise', 1e-6),
+                                              sampler_seed=kwargs.get('sampler_seed', None), cost_withGradients=cost_withGradients)
         elif acquisition_type == 'EI_MCMC':
             self.acquisition = AcquisitionEI_MCMC(self.model, self.space, self.acquisition_optimizer, cost_withGradients, jitter)
         elif acquisition_type == 'MPI_MCMC':

@@ -1,6 +1,7 @@
 // Lifecycle of a context (gp_t), the per-device stream set, options, data / parameter upload, the accounted GEMM
 // launcher and the small getters.  See include/gphip.h for the contract (reference file:line per entry point).
 #include "api_internal.h"
+#include <atomic>
 
 #define BK_MIN 16  // the GEMM's stage depth (gemm.hip): every contraction length is a multiple of it
 
@@ -82,6 +83,19 @@ static std::mutex g_ds_mu;
 static std::map<int, DevStreams> g_ds;
 static std::set<gp_ctx *> g_live;  // contexts created and not yet destroyed
 static bool g_atexit_registered = false;
+
+unsigned long long next_fit_gen() {
+    static std::atomic<unsigned long long> gen{0};
+    return ++gen;
+}
+bool ctx_fit_is(gp_ctx *g, unsigned long long gen) {
+    std::lock_guard<std::mutex> lk(g_ds_mu);
+    return g_live.count(g) != 0 && g->fitted && g->fit_gen == gen;
+}
+bool ctx_alive(gp_ctx *g) {
+    std::lock_guard<std::mutex> lk(g_ds_mu);
+    return g_live.count(g) != 0;
+}
 
 // Ordered shutdown (exported as gp_shutdown, and registered with atexit() at the first stream creation so that it runs
 // BEFORE the HIP runtime's and a profiler's own exit handlers, which were registered earlier): quiesce every device the

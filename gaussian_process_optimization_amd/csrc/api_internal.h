@@ -408,6 +408,30 @@ struct KgState {
     DevBuf<double> dState;     // gp_kg_rows: ROWS_WIDE_M state rows of KG_STATE_STRIDE doubles (kg.hip)
 };
 
+// Noisy expected improvement (api_nei.hip), resident on the TWIN: S fantasies of the noiseless training values drawn through the
+// model's factor and this context's.  S > 0 while the blocks belong to the factor in dA (factor_results_dropped and factor_grown
+// drop them) and to the model's fit: `model` is looked up among the live contexts and its fit_gen compared before every use.
+struct gp_ctx;
+struct NeiState {
+    int S = 0;
+    double d = 0.0, d0 = 0.0;  // the diagonals of the two factors: noise + 1e-8 + jitter of the model, of the twin
+    gp_ctx *model = nullptr;   // never dereferenced before nei_model_unchanged found it alive
+    unsigned long long model_gen = 0;
+    DevBuf<double> dA0;        // [NEI_SPAD, Npad] fantasy-major: a_s = K0^-1 F_s, zero rows and columns in the padding
+    DevBuf<double> dU;         // [128, Npad]: U_s = L0^-1 F_s, the forward substitution's result (the gradient's mix reads it)
+    DevBuf<double> dF;         // [NEI_SPAD, Npad]: the fantasies
+    DevBuf<double> dFstar;     // [NEI_SPAD]: their minima
+    DevBuf<double> dZt;        // 2 x [Npad, NEI_SPAD]: Z and E transposed, of the call in progress
+    DevBuf<double> dR, dG;     // 128 x Npad each: the running right-hand side / the solves' workspace
+    DevBuf<int> dFlag;         // the X comparison's word
+    DevBuf<double> dTab;       // [S, M]: the means of the table
+    DevBuf<double> dPart;      // ... and the product's partial sums (paths_table_part_elems)
+    DevBuf<double> dRowsPart;  // gp_nei_rows: the workgroups' shares (nei_rows_part_elems)
+    DevBuf<double> dState;     // gp_nei_rows: ROWS_WIDE_M state rows of KG_STATE_STRIDE doubles
+    int pass_launches = 0, pass_reads = 0;   // kernels the last pass of the last gp_nei_rows call put on the stream, and how many of them
+                                             // read the inverse factor (0, 0: the call took the table route); counted where they are launched
+};
+
 // GP classification (api_laplace.hip): what a Laplace fit keeps beside the context's own buffers.  `on` while the context is
 // "Laplace-fitted": dA holds the factor of K + W^-1, dAlpha the mode's a, and noise is 1 (noise_saved: what gp_set_params gave,
 // put back where the state is dropped).  Every regression fit, gp_set_data and gp_set_params drop it (laplace_dropped).
@@ -589,6 +613,9 @@ struct gp_ctx {
     QeiState qei;       // the base samples of the joint expected improvement (api_qei.hip)
     KgState kg;         // the knowledge gradient's discretisation points (api_kg.hip)
     LapState lap;       // GP classification: the Laplace fit's buffers and state (api_laplace.hip)
+    NeiState nei;       // noisy expected improvement: the fantasies this context holds as a twin (api_nei.hip)
+    long linv_builds = 0;             // how often ensure_linv built the inverse factor since the context was created (gp_nei_stats)
+    unsigned long long fit_gen = 0;   // a process-wide serial taken whenever the factor is dropped or grows: what gp_nei_set records of its model
     bool dead = false;  // gp_shutdown ran: the device's streams are gone, only gp_destroy is still valid
 };
 
@@ -607,8 +634,16 @@ static inline void laplace_dropped(gp_ctx *g) {
             return fail(GP_ERR_STATE, "%s: not available on a Laplace-fitted handle (gp_laplace_fit): a regression fit, gp_set_data or gp_set_params clears that state", who); \
     } while (0)
 
+unsigned long long next_fit_gen();   // api_core.hip: 1, 2, ... over the process, never repeated
+bool ctx_alive(gp_ctx *g);           // api_core.hip: g was created and not yet destroyed
+// api_core.hip: g is a live context whose fit is current and has generation `gen` -- looked up and read under the lock gp_destroy
+// takes before it frees a context, so a model destroyed on another thread is never dereferenced
+bool ctx_fit_is(gp_ctx *g, unsigned long long gen);
+
 // A new factor is about to be (or has been) written to dA: nothing derived from the old one may be served again.
 static inline void factor_results_dropped(gp_ctx *g) {
+    g->fit_gen = next_fit_gen();
+    g->nei.S = 0;
     g->wi_valid = false;
     g->li_valid = false;
     g->rows_calls_since_fit = 0;
@@ -639,6 +674,8 @@ static inline void sparse_fit_dropped(gp_ctx *g) {
 // were extended and stay; rows_calls_since_fit keeps counting towards the inverse factor's build.  Everything else derived from
 // the old factor or the old data is dropped, as gp_set_data drops it.
 static inline void factor_grown(gp_ctx *g) {
+    g->fit_gen = next_fit_gen();
+    g->nei.S = 0;
     g->wi_valid = false;
     g->w_in_t2 = false;
     g->invp_valid = false;
@@ -952,6 +989,8 @@ void panel_inv_steps(gp_ctx *g, hipStream_t s, double *Wb, long PB, const double
                      long sL, long sI);   // api_solve.hip: Wb (the identity on entry) <- L^-T of the Wp-tile lower factor at Lb
 // api_es.hip: what a scoring call needs -- an exact single-output model without a warp, representers and a belief --, and the
 // pointers of the belief for a launch
+int nei_ready(gp_ctx *g, double y_mean, double y_std, const char *who);   // api_nei.hip: resident fantasies of an unchanged model, a usable normaliser
+int nei_table_scores(gp_ctx *g, double par, double y_mean, double y_std, const char *who);   // api_nei.hip: +NEI of the resident candidates into dAcq (not drained)
 int kg_ready(gp_ctx *g, double y_std);   // api_kg.hip: an exact single-output model as KG takes it, resident points, a usable y_std
 int es_ready(gp_ctx *g, double y_std);
 struct EsBelief { const double *Qt, *Gt, *logP, *u, *W; };

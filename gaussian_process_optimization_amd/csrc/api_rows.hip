@@ -284,6 +284,66 @@ extern "C" int gp_kg_rows(gp_t *g, const double *Xs, int64_t M, double y_std, do
     return 0;
 }
 
+// Noisy expected improvement at a handful of locations given by value, on the TWIN, negated as gp_acq_rows returns its scores, and
+// with dout its closed-form gradient (kernels: csrc/nei.hip).  Fused: the forward pass over the twin's inverse factor, the shares
+// of k . a_s and |w|^2, and a scoring launch of one workgroup per location that leaves p and c; for a gradient the adjoint
+// w' = cw w + sum_s cv_s U_s (U = L0^-1 F, so that L0^-T w' = cw beta_x - y_std A0 p) is mixed into the right-hand sides of the
+// UNCHANGED backward pass by the knowledge gradient's mix kernel, and its closing pass, without cross terms, ends the call: the
+// inverse factor is read twice whatever S.  Beyond the fused path: the table route, values only.
+extern "C" int gp_nei_rows(gp_t *g, const double *Xs, int64_t M, double par, double y_mean, double y_std, double *out, double *dout) {
+    if (!g || !Xs || !out) return fail(GP_ERR_ARG, "null argument");
+    GP_FITTED(g);
+    if (M < 1) return fail(GP_ERR_ARG, "M < 1");
+    int rc;
+    if ((rc = nei_ready(g, y_mean, y_std, "gp_nei_rows"))) return rc;
+    if (!std::isfinite(par)) return fail(GP_ERR_ARG, "gp_nei_rows: par must be finite");
+    for (int64_t i = 0; i < M * g->D; ++i)
+        if (!std::isfinite(Xs[i])) return fail(GP_ERR_ARG, "gp_nei_rows: a location is not finite");
+    const bool fused = rows_fused_ok(g, M);
+    if (dout && !fused) return fail(GP_ERR_ARG, "gp_nei_rows: the gradient needs a shape the fused rows path takes (M <= %ld)", g->small_m);
+    // the build policy's counter moves with every call the fused path could take, as in gp_acq_rows; a gradient call takes the
+    // factor whatever the policy says (built at the first one)
+    const bool factor = fused && rows_use_factor(g);
+    if (fused && (dout || factor)) {
+        if ((rc = ensure_linv(g))) return rc;
+        NeiState &ne = g->nei;
+        if ((rc = ne.dRowsPart.reserve((long)nei_rows_part_elems(g->Npad)))) return rc;
+        if ((rc = ne.dState.reserve((long)ROWS_WIDE_M * KG_STATE_STRIDE))) return rc;
+        const int want_grad = dout != nullptr;
+        const int nt_loads = g->rows_nt < 0 ? (g->Npad > 8192 ? 1 : 0) : g->rows_nt;
+        return rows_exact_passes(
+            g, Xs, (int)M, want_grad ? "rows_nei_grad" : "rows_nei", want_grad ? 2.0 : 1.0,
+            [&](const RowsX &rx, const RowsWork &w, const PassReport &r) {
+                // every kernel of the pass is counted where it is launched, and so is every one that reads g->dLi (gp_nei_stats)
+                int launches = 0, reads = 0;
+                launch_rows_forward(g->s, g->dLi, g->Npad, rx, g->kp, g->dX, g->N, g->dAlpha, w, nt_loads);
+                ++launches, ++reads;
+                launches += launch_nei_rows(g->s, rx, g->kp, g->dX, g->N, g->Npad, ne.dA0, ne.S, ne.dFstar, w, ne.dRowsPart, g->kp.variance,
+                                            g->noise, par, y_mean, y_std, want_grad, ne.dState, r);
+                unsigned arrivals = (unsigned)rx.M;   // the scoring kernel: one workgroup per location
+                if (want_grad) {
+                    launch_kg_mix(g->s, rx.M, g->N, g->Npad, w, ne.dU, ne.S, ne.dState);
+                    ++launches;
+                    launch_rows_backward(g->s, g->dLi, g->Npad, rx.M, w, nt_loads);
+                    ++launches, ++reads;
+                    launch_kg_close(g->s, rx, g->kp, g->dX, g->N, g->Npad, g->dAlpha, w, nullptr, 0, ne.dState, r, r.base + arrivals);
+                    ++launches;
+                    arrivals += rows_finish_grid(g->N);
+                }
+                ne.pass_launches = launches;
+                ne.pass_reads = reads;
+                return arrivals;
+            },
+            [&](int m0, int mc, int MV, const double *o) { rows_unpack(o, MV, m0, mc, g->D, nullptr, nullptr, out, nullptr, nullptr, dout); });
+    }
+    ++g->rows_fallback_calls;
+    g->nei.pass_launches = g->nei.pass_reads = 0;
+    if ((rc = gp_set_candidates(g, Xs, M))) return rc;
+    if ((rc = gp_nei_table(g, par, y_mean, y_std, out))) return rc;
+    for (int64_t i = 0; i < M; ++i) out[i] = -out[i];
+    return 0;
+}
+
 // how many *_rows calls took the fused path / the batched entry points since the context was created (route checks in tests)
 extern "C" int gp_rows_stats(gp_t *g, int64_t *fused, int64_t *fallback) {
     if (!g) return fail(GP_ERR_ARG, "null gp");

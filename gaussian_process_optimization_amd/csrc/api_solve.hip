@@ -257,6 +257,7 @@ int ensure_linv(gp_ctx *g) {
     }
     launch_transpose_tri(g->s, g->dLi, g->dT2, Npad, 0);
     g->li_valid = true;
+    ++g->linv_builds;
     return 0;
 }
 

@@ -426,6 +426,34 @@ void launch_kg_mix(hipStream_t s, int M, long N, long Npad, const RowsWork &w, c
 void launch_kg_close(hipStream_t s, const RowsX &rx, const KernParams &kp, const double *X, long N, long Npad, const double *alpha,
                      const RowsWork &w, const double *Xa, int A, const double *state, const PassReport &r, unsigned counter_base);
 
+// ---- nei.hip: noisy expected improvement over S <= NEI_SPAD fantasies of the training values (api_nei.hip) ----------------------------
+#define NEI_SPAD 64            // GP_NEI_MAX_S: rows of the fantasy-major blocks A0, U, F (zero rows beyond S)
+// G[s ldg + i] = sum_{j <= i} L[i ldl + j] Zt[j NEI_SPAD + s], i < N, s < NEI_SPAD: one read of L's lower triangle.  Zt [N, NEI_SPAD]
+// holds the draws transposed, zero columns beyond S.  Each (s, i) is its own dot product in j order
+void launch_nei_lz(hipStream_t s, const double *L, long ldl, long N, const double *Zt, double *G, long ldg);
+// mode 0: B[s, i] = y_i - sd Em[s, i] (into F) and R[s, i] = B[s, i] - G[s, i] (G holds g on entry, the residual on exit);
+// mode 1: F[s, i] = F[s, i] - dd V[s, i].  s < S, i < N; every block fantasy-major [., ld], Em (the draws E) included
+void launch_nei_assemble(hipStream_t s, int mode, int S, long N, const double *Y, const double *Em, double sd, double dd, double *G,
+                         const double *V, double *F, long ld);
+// fstar[s] = min_i F[s ld + i], i < N: one workgroup per fantasy, a fixed tree, no atomics
+void launch_nei_colmin(hipStream_t s, const double *F, long ld, long N, int S, double *fstar);
+// the X of two handles compared on the device: flag[0] = 1 where an entry differs (flag zeroed by the caller on the stream)
+void launch_nei_same_x(hipStream_t s, const double *Xa, const double *Xb, long n, int *flag);
+// table: mtab [S, M] = sum_n k(x_i, X_n) A0[s, n] (normalised), var [M] the twin's predictive variance with noise; out [M] = +NEI
+void launch_nei_score(hipStream_t s, const double *mtab, const double *var, long M, int S, const double *fstar, double par,
+                      double y_mean, double y_std, double *out);
+// state (device): per location KG_STATE_STRIDE doubles laid out as the knowledge gradient's, [cv_s = -y_std p_s, s < S | ... |
+// cw = -c y_std^2 / sd at 256 (0 where the floor holds) | cm = 0 at 257]: launch_kg_mix and launch_kg_close serve the gradient
+// with U in V_A's place and no cross terms (A = 0 in the closing pass).
+// behind launch_rows_forward (two launches: the shares, then one workgroup per location): -NEI into r.out at the acquisition's
+// place of the rows layout; rx.M workgroups arrive at the pass's counter from r.base; cpart: nei_rows_part_elems(Npad) doubles.
+// want_grad = 0: the ticket as well; else the state rows.  Returns the kernels it launched (2)
+unsigned nei_rows_grid(long Npad);
+size_t nei_rows_part_elems(long Npad);
+int launch_nei_rows(hipStream_t s, const RowsX &rx, const KernParams &kp, const double *X, long N, long Npad, const double *A0, int S,
+                     const double *fstar, const RowsWork &w, double *cpart, double kss, double noise_add, double par, double y_mean,
+                     double y_std, int want_grad, double *state, const PassReport &r);
+
 // ---- ens_rows.hip: the same passes over an ensemble of S members, the member as a grid dimension --------------------------------
 #define ENS_ROWS_RB 32                       // rows of the tile per workgroup: what rows_block_height gives every matrix the ensemble takes
 #define ENS_POST_STRIDE ROWS_OUT_DOUBLES     // doubles between two members' result blocks (each laid out as the single model's)

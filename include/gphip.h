@@ -1189,6 +1189,67 @@ int gp_kg_acq_argbest(gp_t *gp, double y_std, int sense, int64_t *idx, double *v
 int gp_kg_acq_topk(gp_t *gp, double y_std, int sense, int k, int64_t *idx, double *val);
 int gp_kg_rows(gp_t *gp, const double *Xs, int64_t M, double y_std, double *out, double *dout);
 
+/* ---- noisy expected improvement (Letham, Karrer, Ottoni & Bakshy 2019) ---------------------------------------------------------------
+ * EI averaged over S draws ("fantasies") of the noiseless function values at the training inputs.  Two handles on one device hold
+ * the same X, kernel family, variance and lengthscales: the MODEL is the noisy fit, factor L L^T = Ky = K + d I with
+ * d = noise + 1e-8 + jitter and normalised targets y; the TWIN is a near-noiseless fit of the same kernel, L0 L0^T = K0 = K + d0 I,
+ * d0 = noise0 + 1e-8 + jitter0 (its Y is not read).  The latent f has prior covariance K0 and y = f + eps, eps ~ N(0, (d - d0) I),
+ * so that the model's covariance is exactly Ky.  Matheron's rule, from standard normals Z, E [S, N] (row s is fantasy s):
+ *     g_s = L0 z_s,   r_s = y - g_s - sqrt(d - d0) e_s,   V_s = Ky^-1 r_s,
+ *     F_s = y - sqrt(d - d0) e_s - (d - d0) V_s   (= g_s + K0 Ky^-1 r_s),   a_s = K0^-1 F_s,   fstar_s = min_i F_is.
+ * At a location x: k = k(X, x), w = L0^-1 k, m_s = k . a_s, and s the twin's predictive standard deviation as gp_acq_rows forms it
+ * (variance kss - |w|^2 + noise0, times y_std^2, floored at 1e-10, root floored at 1e-10).  mu_s = y_std m_s + y_mean,
+ * t_s = y_std fstar_s + y_mean, u_s = (t_s - par - mu_s) / s:
+ *     NEI(x) = (1 / S) sum_s s (u_s Phi(u_s) + phi(u_s))                              (s = 0 .. S - 1 in index order)
+ *     dNEI/dx = -y_std J^T (A0 p) + c ds/dx,   p_s = Phi(u_s) / S,   c = (1 / S) sum_s phi(u_s),   A0 = [a_1 .. a_S]
+ * J the [N, D] input Jacobian of k(X, x) (0 where the distance is exactly 0), ds/dx = -(y_std^2 / s) J^T L0^-T w, 0 where the
+ * floor holds.
+ *
+ * gp_nei_set(twin, model, S, Z, E): the state becomes resident on the TWIN -- A0 and U = L0^-1 F ([64, Npad] each, fantasy-major),
+ * F, fstar, d and d0.  Nothing is factored.  g = L0 z is one streaming read of L0's lower triangle by a kernel of its own (dA's
+ * upper tiles hold what the factorisation left there, so the GEMM does not apply); the residual and F are one kernel; the column
+ * minima a fixed-order reduction; the four substitutions are the two alpha takes, S right-hand sides each, against either factor
+ * (the model's inverted diagonal panels are built where they were not: nothing else of the model changes).  Each fantasy is its own
+ * dot products: the leading S columns of a larger draw give the same bits.  S = 0 clears the state (model, Z, E may be NULL).
+ * The state belongs to both factors: whatever drops or grows the twin's factor drops it, and every gp_nei_* entry returns
+ * GP_ERR_STATE once the model has been refitted, appended to, given new data or parameters, or destroyed.
+ * gp_nei_info: *S resident (0 without), *d_model and *d_twin (any may be NULL).  gp_nei_get: F [S, N] and fstar [S], normalised
+ * (either may be NULL).
+ * gp_nei_table: out [M] = +NEI over the twin's resident candidates: the variance from the candidate solve of gp_predict, the S
+ * means from gp_paths_table's fused kernel-build-and-product with A0 in V's place and no feature term (K(Xs, X) is not stored),
+ * then one scoring launch.  gp_nei_argbest / gp_nei_topk: the selector of gp_acq_argbest / gp_acq_topk over that vector (sense +1
+ * picks the largest NEI; lowest index among equal scores).  The LDS of the product is joint in D and S as for gp_paths_table: a
+ * shape that does not fit is GP_ERR_ARG naming both byte counts.
+ * gp_nei_rows: M >= 1 locations by value; out [M] = -NEI and, when dout is given, dout [M, D] = -dNEI/dx.  For M <= option
+ * "small_m" (8) locations that fit the fused rows path (layouts 1, 4, 8; the inverse factor's build policy as for gp_acq_rows, a
+ * gradient call always takes the factor) a pass is: the forward launch over L0^-1; the shares of k . a_s and |w|^2 per 256
+ * training rows, one writer each; a scoring launch of one workgroup per location that adds the shares in order, scores the S
+ * fantasies and leaves p and c; and for a gradient: the mix w' = -(c y_std^2 / s) w - y_std sum_s p_s U_s into the backward
+ * pass's right-hand sides -- L0^-T w' is the whole adjoint, since L0^-T U_s = a_s --, the rows path's unchanged backward pass and
+ * the closing pass over the training points whose last workgroup writes the pinned block.  L0^-1 is read twice for a gradient,
+ * once for a value, whatever S.  Other shapes take the table route, values only: a dout there is GP_ERR_ARG.  On the fused path
+ * repeated calls are bitwise equal, the value has the same bits with and without dout, and a location has the same bits whatever
+ * its slot, its company and its pass layout.  No atomics but the arrival counter; always true fp64.
+ * gp_nei_stats (route checks; any pointer may be NULL): *linv_builds how often the handle's inverse factor was built since
+ * gp_create (once per fit that a rows call follows), *pass_launches the kernels the last pass of the last gp_nei_rows call put on
+ * the stream and *pass_reads how many of them read L0^-1 -- 3 and 1 for a value call, 6 and 2 for a gradient call, 0 and 0 where
+ * the call took the table route.  Counted where the kernels are launched.
+ * GP_ERR_STATE: either handle unfitted, P != 1, a Gower kernel, a mean function, an output warp, a Laplace or sparse fit or an
+ * ensemble on either handle, no resident state (scoring), the model changed since gp_nei_set.  GP_ERR_ARG: null pointers,
+ * different devices, N, D, kernel, ARD flag, variance, lengthscales or X (compared on the device), d <= d0, S outside
+ * 0 .. GP_NEI_MAX_S, a draw or a location that is not finite, a normaliser that is not usable.  A refused call launches and changes
+ * nothing. */
+#define GP_NEI_MAX_S 64
+#define GP_NEI_MAX_ROWS 8
+int gp_nei_set(gp_t *twin, gp_t *model, int S, const double *Z, const double *E);
+int gp_nei_info(gp_t *twin, int *S, double *d_model, double *d_twin);
+int gp_nei_get(gp_t *twin, double *F, double *fstar);
+int gp_nei_stats(gp_t *twin, int64_t *linv_builds, int *pass_launches, int *pass_reads);
+int gp_nei_table(gp_t *twin, double par, double y_mean, double y_std, double *out);
+int gp_nei_argbest(gp_t *twin, double par, double y_mean, double y_std, int sense, int64_t *idx, double *val);
+int gp_nei_topk(gp_t *twin, double par, double y_mean, double y_std, int sense, int k, int64_t *idx, double *val);
+int gp_nei_rows(gp_t *twin, const double *Xs, int64_t M, double par, double y_mean, double y_std, double *out, double *dout);
+
 /* ---- GP classification: Bernoulli likelihood, probit link, Laplace's approximation (api_laplace.hip) --------------------------
  * Rasmussen & Williams, Algorithms 3.1 and 5.1.  labels [N] in {-1, +1} (anything else: GP_ERR_ARG); X and the kernel are the
  * context's (gp_set_data with P = 1 -- its Y is not read -- and gp_set_params, whose noise is ignored: K carries no noise and no
